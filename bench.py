@@ -10,6 +10,12 @@ One step = one pass of the hot path (EgoTAPAutoEncoder.forward through the C ABI
 batch of 256 synthetic stereo heatmap sets already resident in HBM.  The batch shards by sample with no
 data-path collective, so N GPUs run N shards: weak scaling; value = N*256*K / max-rank time.
 Rank 0 prints ONE JSON line.
+
+A plain run measures the headline alone: set-up, W warm-up steps, K timed steps, the result line.  --full adds everything
+else on top of the same headline: the GEMM roofline (HIP event pairs around every GEMM launch of the timed steps), the
+bf16x3 / bf16 fast modes, the full pipeline from RGB, the EgoCap / 128x128 geometry, the training legs, small-batch latency,
+the CPU baseline and the oracle parity check.  --dump-outputs DIR writes the poses of the last timed step as DIR/pose.npy
+(float32 [B, 16, 3]; DIR/pose_rank<r>.npy per rank at N > 1); the inputs are a pure function of the arguments.
 """
 from __future__ import annotations
 
@@ -550,6 +556,30 @@ def bench_latency(net, p, dev):
     return out
 
 
+def headline_fields(args, p, B, world, elapsed, per_rank_ms, legs):
+    """The headline part of the result line: the fp32 lifting head's rate over the K timed steps (max over ranks)."""
+    import torch.distributed as dist
+    fps = world * B * args.steps / elapsed
+    flops_frame = lift_flops_per_frame(p)
+    return {
+        "metric": "stereo frames/sec (2D->3D lift, B=256, 256x256)", "value": round(fps, 1), "unit": "stereo frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.preset} 16-joint lifting head (heatmaps [B,90,64,64] -> joints [B,16,3]), "
+                               f"forward only, fp32, batch {B} per GPU, inputs resident in HBM",
+                   "batch_per_gpu": B, "global_batch": world * B, "heatmap": p.hm_size, "rgb": 4 * p.hm_size,
+                   "parallelism": f"dp{world} (batch shards, no collective)"},
+        "flops_per_frame": flops_frame,
+        "end_to_end_tflops_per_gpu": round(fps * flops_frame / world / 1e12, 2),
+        "end_to_end_frac_of_f32_mfma_peak": round(fps * flops_frame / world / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
+        "distributed": {"backend": dist_backend(), "world_size_seen": dist.get_world_size() if dist.is_initialized() else 1,
+                        "launched_as": "torch.distributed.run, one rank per GPU" if world > 1 else "single process",
+                        "per_rank_ms_per_step": per_rank_ms,
+                        "data_path_collective": "none (batch shards; samples are independent in eval)",
+                        "legs_at_this_n": legs},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -571,7 +601,12 @@ def main():
     ap.add_argument("--train-batch-bf16", type=int, default=1024, help="per-GPU batch of the bf16 training measurement (BASELINE config 3)")
     ap.add_argument("--all-legs", action="store_true", help="N > 1: also run the single-GPU secondary legs on every rank (default at N > 1: "
                                                             "headline + the data-parallel training legs, the ones with a collective)")
+    ap.add_argument("--full", action="store_true", help="also run the roofline timing, the secondary legs, the CPU baseline and the parity "
+                                                        "check (the options above shape them); without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the poses of the last timed step to DIR/pose.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -637,9 +672,23 @@ def main():
     def barrier():
         parallel.barrier(dev)
 
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     elapsed, pose, t1 = timed_lift(net, hm, args.steps, args.warmup, lib, L, h, barrier, dev, timing, world)
     headline_per_rank_ms = list(timed_lift.per_rank_ms)
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "pose.npy" if world == 1 else f"pose_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), pose.float().cpu().numpy())
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_fields(args, p, B, world, elapsed, headline_per_rank_ms,
+                                             "headline only (--full: roofline, secondary legs, CPU baseline, parity check)")), flush=True)
+        if world > 1:
+            barrier()
+            dist.destroy_process_group()
+        return
 
     roof = None
     if timing:
@@ -817,31 +866,15 @@ def main():
     elif rank == 0 and gpu_vs_oracle is not None:
         parity_note = f"the cpu_baseline sample (B = {args.cpu_batch})"
     if rank == 0:
-        frames = world * B * args.steps
-        fps = frames / elapsed
-        flops_frame = lift_flops_per_frame(p)
-        line = {
-            "metric": "stereo frames/sec (2D->3D lift, B=256, 256x256)", "value": round(fps, 1), "unit": "stereo frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.preset} 16-joint lifting head (heatmaps [B,90,64,64] -> joints [B,16,3]), "
-                                   f"forward only, fp32, batch {B} per GPU, inputs resident in HBM",
-                       "batch_per_gpu": B, "global_batch": world * B, "heatmap": p.hm_size, "rgb": 4 * p.hm_size,
-                       "parallelism": f"dp{world} (batch shards, no collective)"},
-            "flops_per_frame": flops_frame,
-            "end_to_end_tflops_per_gpu": round(fps * flops_frame / world / 1e12, 2),
-            "end_to_end_frac_of_f32_mfma_peak": round(fps * flops_frame / world / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
-            "distributed": {"backend": dist_backend(), "world_size_seen": dist.get_world_size() if dist.is_initialized() else 1,
-                            "launched_as": "torch.distributed.run, one rank per GPU" if world > 1 else "single process",
-                            "per_rank_ms_per_step": headline_per_rank_ms,
-                            "data_path_collective": "none (batch shards; samples are independent in eval)",
-                            "legs_at_this_n": "all" if single_gpu_legs or args.lift_only else
-                                              "headline + fast modes + data-parallel training legs (single-GPU legs: run with --gpus 1 or --all-legs)"},
+        line = headline_fields(args, p, B, world, elapsed, headline_per_rank_ms,
+                               "all" if single_gpu_legs or args.lift_only else
+                               "headline + fast modes + data-parallel training legs (single-GPU legs: run with --gpus 1 or --all-legs)")
+        line.update({
             "roofline": roof, "cpu_baseline": cpu, "max_abs_diff_vs_oracle": gpu_vs_oracle,
             "parity_checked_on": parity_note if parity_note is not None else "not checked in this run (--no-cpu-baseline at N = 1)",
             "fast_mode_bf16x3": fast, "fast_mode_bf16": fast16, "full_pipeline_from_rgb": full, "config5_geometry_egocap_hm128": config5,
             "train_step_lifting_head": train, "small_batch_latency": latency,
-        }
+        })
         print(json.dumps(line), flush=True)
     if world > 1:
         barrier()

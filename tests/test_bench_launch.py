@@ -53,7 +53,7 @@ def test_bench_two_rank_rehearsal_prints_the_n2_line_with_its_distributed_fields
     env = dict(os.environ, EGOTAP_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--no-fast-mode",
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "32", "--no-fast-mode",
                           "--train-steps", "1", "--train-batch", "8", "--train-batch-bf16", "8"], capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -73,3 +73,37 @@ def test_bench_two_rank_rehearsal_prints_the_n2_line_with_its_distributed_fields
         assert len(leg["per_rank_ms_per_step"]) == 2 and leg["allreduce_exposed_ms_last_step"] is not None
         assert leg["allreduce_op"].startswith("sum")                # gloo: sum + scaling pass (RCCL: ReduceOp.AVG)
     assert tr["config3_bf16_b1024"]["config4_global_batch"] == 16
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) measures the headline alone -- no roofline, secondary legs, CPU baseline or parity check in the line -- and
+    --dump-outputs writes the poses of the last timed step: the inputs are a pure function of the arguments, so the dump matches the oracle on
+    the same synthetic weights and heatmaps."""
+    import json
+    import numpy as np
+    import torch
+    from egotap_amd import spec
+    from egotap_amd.synthetic import synth_input, synth_state_dict
+    from oracle import lift_ref as O
+    if torch.cuda.device_count() < 1:
+        pytest.skip("needs a GPU")
+    B = 32
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "stereo frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3
+    assert d["value"] > 0 and abs(d["value"] - B / (d["ms_per_step"] / 1e3)) < 2e-3 * d["value"]
+    for k in ("roofline", "cpu_baseline", "fast_mode_bf16x3", "train_step_lifting_head", "small_batch_latency"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["pose.npy"]
+    pose = np.load(tmp_path / "out" / "pose.npy")
+    assert pose.dtype == np.float32 and pose.shape == (B, 16, 3) and np.isfinite(pose).all()
+    p = spec.lift_preset("UnrealEgo")
+    hm = torch.from_numpy(synth_input("hm_bench_rank0", (B, p.in_channels, p.hm_size, p.hm_size)))
+    with torch.no_grad():
+        ref = O.lift_forward(hm[:2], O.to_torch_sd(synth_state_dict(spec.lift_state_spec(p))), p).numpy()
+    assert np.abs(pose[:2] - ref).max() < 1e-4

@@ -1,11 +1,13 @@
 #!/bin/bash
-# Runs on the GPU box (through gpurun): rocprofv3 passes, outputs under gpurun_out/prof*/ (scratch); tools/summarize_prof.py digests them
+# Runs on an MI355X: rocprofv3 passes, raw outputs under $EGOTAP_PROF_DIR/prof*/ (default prof_raw/, git-ignored scratch);
+# tools/summarize_prof.py digests them
 # into profiles/rNN_*.  Every command gets FOUR separate passes (never combined: PMC + tracing together is refused on this pool):
 #   1 kernel trace + stats (durations)   2 FETCH_SIZE   3 WRITE_SIZE   4 MFMA busy / clock / wave counters
 # usage: tools/profile_bench.sh [headline] [config3] [hm16] [stage1] [all]     (default: headline config3)
 set -e
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
+RAW=${EGOTAP_PROF_DIR:-prof_raw}
 passes() {   # $1 = output dir, rest = python arguments
   local OUT=$1; shift
   rm -rf $OUT; mkdir -p $OUT
@@ -21,12 +23,12 @@ passes() {   # $1 = output dir, rest = python arguments
 SETS="$@"; [ -z "$SETS" ] && SETS="headline config3"
 for s in $SETS; do
   case $s in
-    headline) passes gpurun_out/prof bench.py --steps 5 --warmup 2 --lift-only --no-fast-mode --no-cpu-baseline --no-kernel-timing ;;
-    config3)  passes gpurun_out/prof_c3 tools/train_bf16_probe.py 1024 bf16 ;;
-    hm16)     passes gpurun_out/prof_hm tools/hm_bf16_probe.py 256 64 bf16 ;;
-    stage1)   passes gpurun_out/prof_st1 tools/stage1_probe.py 32 f32 ;;
-    rgbdef)   passes gpurun_out/prof_rgbdef tools/from_rgb_probe.py 1024 default ;;
-    all)      passes gpurun_out/prof_all bench.py --steps 2 --warmup 1 --full-steps 1 --train-steps 1 --no-cpu-baseline --no-kernel-timing ;;
+    headline) passes $RAW/prof bench.py --steps 5 --warmup 2 --lift-only --no-fast-mode --no-cpu-baseline --no-kernel-timing ;;
+    config3)  passes $RAW/prof_c3 tools/train_bf16_probe.py 1024 bf16 ;;
+    hm16)     passes $RAW/prof_hm tools/hm_bf16_probe.py 256 64 bf16 ;;
+    stage1)   passes $RAW/prof_st1 tools/stage1_probe.py 32 f32 ;;
+    rgbdef)   passes $RAW/prof_rgbdef tools/from_rgb_probe.py 1024 default ;;
+    all)      passes $RAW/prof_all bench.py --full --steps 2 --warmup 1 --full-steps 1 --train-steps 1 --no-cpu-baseline --no-kernel-timing ;;
   esac
 done
-du -sh gpurun_out/prof*
+du -sh $RAW/prof*

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Digest gpurun_out/prof (written by tools/profile_bench.sh on the GPU box) into profiles/<tag>_*.
+"""Digest the raw rocprofv3 output of tools/profile_bench.sh ($EGOTAP_PROF_DIR, default prof_raw/) into profiles/<tag>_*.
 
 usage: python tools/summarize_prof.py r01
 Copies the rocprofv3 kernel stats CSV and writes a markdown summary with per-kernel average
@@ -14,14 +14,15 @@ import shutil
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(REPO, "gpurun_out", "prof")
+RAW = os.path.join(REPO, os.environ.get("EGOTAP_PROF_DIR", "prof_raw"))
+SRC = os.path.join(RAW, "prof")
 HEADLINE_CMD = "python3 bench.py --steps 5 --warmup 2 --lift-only --no-fast-mode --no-cpu-baseline --no-kernel-timing"
 CONFIG3_CMD = "python3 tools/train_bf16_probe.py 1024 bf16"
-ALL_CMD = "python3 bench.py --steps 2 --warmup 1 --full-steps 1 --train-steps 1 --no-cpu-baseline --no-kernel-timing"
+ALL_CMD = "python3 bench.py --full --steps 2 --warmup 1 --full-steps 1 --train-steps 1 --no-cpu-baseline --no-kernel-timing"
 
 
 def newest(pat):
-    """gpurun merges every call's files into gpurun_out/: keep only the newest file of a pass"""
+    """repeated passes leave their files side by side: keep only the newest file of a pass"""
     fs = sorted(glob.glob(os.path.join(SRC, pat)), key=os.path.getmtime)
     return fs[-1:] if fs else []
 
@@ -52,27 +53,27 @@ def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
     if os.path.isdir(SRC):
         one(tag, HEADLINE_CMD, "B = 256; the timed workload of bench.py alone: fp32 lifting head forward")
-    SRC = os.path.join(REPO, "gpurun_out", "prof_c3")
+    SRC = os.path.join(RAW, "prof_c3")
     if os.path.isdir(SRC):
         one(tag + "_config3", CONFIG3_CMD, "BASELINE config 3: UnrealEgo training step (forward + backward + AdamW), bf16 storage, batch 1024, 1 warm-up + 2 "
             "timed steps; per-launch HBM bytes are meaningful (one batch size)")
-    SRC = os.path.join(REPO, "gpurun_out", "prof_hm")
+    SRC = os.path.join(RAW, "prof_hm")
     if os.path.isdir(SRC):
         one(tag + "_estimators_bf16", "python3 tools/hm_bf16_probe.py 256 64 bf16", "both heatmap estimators, 256 stereo frames of 256x256 RGB, EGOTAP_PREC_BF16: "
             "fused stem + max-pool on the bf16 matrix cores (stem_bf16s.h) -> layer1 on the direct halo-tile kernel (conv64_bf16s.h) -> layers 2-4 and the "
             "U-Net decoder as implicit GEMMs on bf16 channels-last tensors (conv_bf16s.h); "
             "2 warm-up + 3 timed passes x 2 nets", traffic_json=False)
-    SRC = os.path.join(REPO, "gpurun_out", "prof_st1")
+    SRC = os.path.join(RAW, "prof_st1")
     if os.path.isdir(SRC):
         one(tag + "_stage1_f32", "python3 tools/stage1_probe.py 32 f32", "stage-1 training step of the position heatmap estimator, fp32, B = 32 stereo frames: "
             "train-mode forward, loss, backward, Adam; 1 warm-up + 2 timed steps", traffic_json=False)
-    SRC = os.path.join(REPO, "gpurun_out", "prof_rgbdef")
+    SRC = os.path.join(RAW, "prof_rgbdef")
     if os.path.isdir(SRC):
         one(tag + "_from_rgb_default", "python3 tools/from_rgb_probe.py 1024 default", "[r5] the lifting head's training step FROM RGB as train.py runs it: the two "
             "frozen estimators in train mode (batch-statistics BatchNorm per eye on the bf16 channels-last kernels: stem statistics pass + fused stem, "
             "bn_colstats / bn_finish / bn_apply per BatchNorm, backbone over the whole batch, decoder in chunks of 256), then the bf16-storage step of the head; "
             "B = 1024, 2 warm-up + 2 timed steps", traffic_json=False)
-    SRC = os.path.join(REPO, "gpurun_out", "prof_all")
+    SRC = os.path.join(RAW, "prof_all")
     if os.path.isdir(SRC):
         one(tag + "_all_legs", ALL_CMD, "every leg: fp32 headline, bf16x3 / bf16 fast modes, full pipeline in both modes, EgoCap / 128x128 geometry, "
             "training steps in f32 / bf16x3 / bf16 (B = 1024), stage-1 training, small-batch latency -- launches of one kernel mix batch sizes, "
