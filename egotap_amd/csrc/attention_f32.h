@@ -16,6 +16,7 @@
 #ifdef EGOTAP_ATTN_F32_OLD      // A/B builds (EGOTAP_CXXFLAGS=-DEGOTAP_ATTN_F32_OLD): round 2's kernel, both operands staged in 64 registers
 #include "../../tools/experiments/attention_f32_r2.h"
 #else
+#define EGOTAP_ATTN_F32_LIVE 1      // attention_f32_live_launch below (the pose-only forward's pruned last layer)
 
 template <int NW>
 struct AttnCfg {
@@ -28,10 +29,14 @@ struct AttnCfg {
 template <int NW>
 __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* __restrict__ QKV,
                                                                  float* __restrict__ CTX, int N, int heads,
-                                                                 int qgroups, float scale_log2e, float* __restrict__ LSE, int ksplit) {
+                                                                 int qgroups, float scale_log2e, float* __restrict__ LSE, int ksplit,
+                                                                 const float* __restrict__ Qsrc, long ldq, int Nq) {
     // [r4] ksplit > 1 (serving batches: B x heads x query groups is a fraction of the chip): workgroup (pair, query group, split) attends to
     // key tiles [split * ntiles / ksplit, ...) only and writes its own normalised output and log-sum-exp -- CTX / LSE are then the PARTIAL
     // buffers [ksplit][B * N][D] / [ksplit][B * heads * N], merged by attention_f32_merge_kernel.
+    // [r6] Queries: Nq per image, row b * Nq + q of Qsrc (row stride ldq); CTX / LSE rows follow the queries.  The full forward passes
+    // Qsrc = QKV, ldq = 3 D, Nq = N; the pose-only forward's last layer passes its compact live-token Q (Nq = T ppd^2 < N) against the
+    // physical K / V of all N tokens.
     using Cfg = AttnCfg<NW>;
     constexpr int DH = Cfg::DH, KT = Cfg::KT, KLD = Cfg::KLD, THREADS = Cfg::THREADS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -53,15 +58,15 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
     const long ld = 3L * D;
     const float* base = QKV + (long)b * N * ld + h * DH;     // q of token 0 of this (b, h)
     const int qb = qg * NW + wid;                              // 32-row query block of this wave
-    const bool valid = qb * 32 < N;                            // wave-uniform
+    const bool valid = qb * 32 < Nq;                           // wave-uniform
     // [r5] N need not be a multiple of 32 (the reference allows any heatmap side that is a multiple of 16, net_architecture.py:327: N = 144 at
     // 32 x 32 heatmaps, 1296 at 96 x 96): the LAST query block and the LAST key tile start at N - 32 and overlap their predecessors; the
     // overlapping keys -- already counted by the tile before -- are masked to -inf, the overlapping queries are simply computed twice (same bits)
-    const int q0 = min(qb * 32, N - 32);
+    const int q0 = min(qb * 32, Nq - 32);
 
     float qreg[64];
     {
-        const float* qp = base + (long)(q0 + l31) * ld + 4 * lh;
+        const float* qp = Qsrc + ((long)b * Nq + q0 + l31) * ldq + h * DH + 4 * lh;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const f32x4 v = *(const f32x4*)(qp + 8 * t);
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
         const float inv = 1.0f / l_tot;
         // training: log-sum-exp of the scaled scores (natural log) per query row, for the flash-style backward
         const long part = ksplit > 1 ? (long)split * (gridDim.x / (ksplit * qgroups)) : 0;      // split * (B * heads): offset of this split's partial buffers, in pairs
-        if (LSE != nullptr && lh == 0) LSE[(part + (long)b * heads + h) * N + q0 + l31] = m_run * 0.6931471805599453f + logf(l_tot);      // m_run is in base-2 units
+        if (LSE != nullptr && lh == 0) LSE[(part + (long)b * heads + h) * Nq + q0 + l31] = m_run * 0.6931471805599453f + logf(l_tot);      // m_run is in base-2 units
         float* Os = smem + wid * 32 * KLD;     // [32 q][132]
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
@@ -207,7 +212,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
                 *(f32x4*)(Os + l31 * KLD + dt * 32 + 8 * g + 4 * lh) = v;
             }
         // same wave reads back what it wrote: no barrier needed, only LDS completion (compiler waits)
-        float* out = CTX + (part / heads * N + (long)b * N + q0) * D + h * DH;       // (part / heads = split * B images)
+        float* out = CTX + (part / heads * Nq + (long)b * Nq + q0) * D + h * DH;     // (part / heads = split * B images)
 #pragma unroll
         for (int it = 0; it < 16; ++it) {
             const int row = it * 2 + lh;
@@ -250,6 +255,17 @@ static __global__ __launch_bounds__(256) void attention_f32_merge_kernel(const f
     *(f32x4*)(ctx + off) = acc;
 }
 
+// [r6] the key-split count attention_f32_launch picks for a forward (scratch given, no LSE): the pose-only forward keeps the full problem's
+// decision and prunes its queries only where that is 1
+static int attention_f32_ksplit(int B, int N, int heads, size_t scratch_floats, int num_cu) {
+    const long wgs = (long)B * heads * (((N + 31) / 32 + 1) / 2);
+    const int ntiles = (N + 31) / 32;
+    // as many ranges as keep the chip at ~2 waves per SIMD (a workgroup is two waves: 4.5 workgroups per CU), each a whole number of key tiles
+    for (int k = 8; k >= 2; --k)
+        if (ntiles % k == 0 && wgs * k <= 9L * num_cu / 2 && (size_t)k * ((size_t)B * N * heads * 128 + (size_t)B * heads * N) <= scratch_floats) return k;
+    return 1;
+}
+
 // scratch / scratch_floats (inference at serving batches only; LSE must be null): room for the key-split partials.  The split count
 // fills ~4.5 two-wave workgroups per CU: B = 1 / 2 (72 / 144 workgroups) -> 6 ranges of 3 key tiles, B = 4 -> 3, B = 8 -> 2, B >= 16 -> none.
 static hipError_t attention_f32_launch(const float* QKV, float* CTX, int B, int N, int heads, hipStream_t stream,
@@ -262,17 +278,12 @@ static hipError_t attention_f32_launch(const float* QKV, float* CTX, int B, int 
     const int qgroups = ((N + 31) / 32 + NW - 1) / NW;
     const float scale_log2e = 1.4426950408889634f / sqrtf(128.0f);
     const long wgs = (long)B * heads * qgroups;
-    int ksplit = 1;
-    if (scratch != nullptr && LSE == nullptr) {
-        const int ntiles = (N + 31) / 32;
-        // as many ranges as keep the chip at ~2 waves per SIMD (a workgroup is two waves: 4.5 workgroups per CU), each a whole number of key tiles
-        for (int k = 8; k >= 2; --k)
-            if (ntiles % k == 0 && wgs * k <= 9L * num_cu / 2 && (size_t)k * ((size_t)B * N * heads * 128 + (size_t)B * heads * N) <= scratch_floats) { ksplit = k; break; }
-    }
+    const int ksplit = scratch != nullptr && LSE == nullptr ? attention_f32_ksplit(B, N, heads, scratch_floats, num_cu) : 1;
     if (ksplit > 1) {
         float* part = scratch;
         float* lse_part = scratch + (size_t)ksplit * B * N * heads * 128;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(wgs * ksplit)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, part, N, heads, qgroups, scale_log2e, lse_part, ksplit);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(wgs * ksplit)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, part, N, heads, qgroups, scale_log2e, lse_part, ksplit,
+                           QKV, 3L * heads * Cfg::DH, N);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         const long total = (long)B * N * heads * 32;
@@ -280,7 +291,21 @@ static hipError_t attention_f32_launch(const float* QKV, float* CTX, int B, int 
         return hipGetLastError();
     }
     hipLaunchKernelGGL(kern, dim3(B * heads * qgroups), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, CTX, N, heads,
-                       qgroups, scale_log2e, LSE, 1);
+                       qgroups, scale_log2e, LSE, 1, QKV, 3L * heads * Cfg::DH, N);
+    return hipGetLastError();
+}
+
+// [r6] queries of Nq live tokens per image (compact Q rows b * Nq + q, stride ldq; CTX rows likewise, stride heads * 128) against the K / V
+// columns of all N physical tokens of QKV [B * N, 3 D]: the last ViT layer of the pose-only forward.  No key split (see attention_f32_ksplit).
+static hipError_t attention_f32_live_launch(const float* Q, long ldq, int Nq, const float* QKV, float* CTX, int B, int N, int heads, hipStream_t stream) {
+    constexpr int NW = 2;
+    using Cfg = AttnCfg<NW>;
+    if (B <= 0) return hipSuccess;
+    if (N < 32 || N % 4 != 0 || Nq < 32 || Nq > N || ldq % 4 != 0) return hipErrorInvalidValue;
+    const int qgroups = ((Nq + 31) / 32 + NW - 1) / NW;
+    const float scale_log2e = 1.4426950408889634f / sqrtf(128.0f);
+    hipLaunchKernelGGL(attention_f32_kernel<NW>, dim3(B * heads * qgroups), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, CTX, N, heads,
+                       qgroups, scale_log2e, (float*)nullptr, 1, Q, ldq, Nq);
     return hipGetLastError();
 }
 #endif

@@ -468,12 +468,14 @@ template <class AL> struct AlName;
 template <> struct AlName<ALoadPlain> { static constexpr const char* v = "ALoadPlain"; };
 template <> struct AlName<ALoadPatch> { static constexpr const char* v = "ALoadPatch"; };
 template <> struct AlName<ALoadTokens> { static constexpr const char* v = "ALoadTokens"; };
+template <> struct AlName<ALoadLive> { static constexpr const char* v = "ALoadLive"; };
 template <> struct AlName<ALoadRot> { static constexpr const char* v = "ALoadRot"; };
 template <> struct AlName<ALoadStereo> { static constexpr const char* v = "ALoadStereo"; };
 template <> struct AlName<ALoadStereoGated> { static constexpr const char* v = "ALoadStereoGated"; };
 template <class E> struct EpiName;
 template <> struct EpiName<EpiBias> { static constexpr const char* v = "EpiBias"; };
 template <> struct EpiName<EpiBiasRes> { static constexpr const char* v = "EpiBiasRes"; };
+template <> struct EpiName<EpiBiasResLive> { static constexpr const char* v = "EpiBiasResLive"; };
 template <> struct EpiName<EpiBiasGelu> { static constexpr const char* v = "EpiBiasGelu"; };
 template <> struct EpiName<EpiBnLrelu> { static constexpr const char* v = "EpiBnLrelu"; };
 template <> struct EpiName<EpiPatch> { static constexpr const char* v = "EpiPatch"; };
@@ -882,11 +884,60 @@ static hipError_t gemm_res_ln(Handle* h, const char* role, const float* A, long 
     return launch_ln(X, Y, ln_g, ln_b, M, 1e-12f, s);
 }
 
-extern "C" int egotap_lift_forward(egotap_handle h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes,
-                                   void* stream) {
+// [r6] A compact product of the pose-only forward (M = B T ppd^2: at B = 256 and N = 1024, 1 920 tiles of 256 x 256 = 7.5 rounds on 256 CUs):
+// the tile rows that fill WHOLE rounds on the 256 x 256 kernel, and the rows past them as unsplit 128 x 128 tiles when that is estimated faster
+// than one more half-empty round (the constants of gemm_small_route).  Same k order per output element in both kernels: same bits.
+// rebase(x, m0): the loader / epilogue of the same product seen from compact row m0 on.
+static ALoadPlain rebase(const ALoadPlain& a, int m0) { return ALoadPlain{a.A + (long)m0 * a.lda, a.lda}; }
+static ALoadLive rebase(ALoadLive a, int m0) { a.lr.m0 += m0; return a; }
+static EpiBias rebase(const EpiBias& e, int) { return e; }
+static EpiBiasGelu rebase(const EpiBiasGelu& e, int) { return e; }
+static EpiBiasRes rebase(EpiBiasRes e, int m0) { e.R += (long)m0 * e.ldr; return e; }
+static EpiBiasResLive rebase(EpiBiasResLive e, int m0) { e.lr.m0 += m0; return e; }
+template <class AL, class Epi>
+static hipError_t gemm_rounds(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc, int M, int N, int K,
+                              hipStream_t s) {
+    const int cus = device_cu_count(), tn = N / 256;
+    const long tiles = (long)((M + 255) / 256) * tn;
+    const int mh = (int)((tiles / cus) * cus / tn) * 256;          // rows of the whole rounds
+    if (N % 256 == 0 && K % 32 == 0 && mh > 0 && mh < M) {
+        const double t_round = K * 0.2319 + 5.0;
+        const double t_big = (double)((tiles + cus - 1) / cus) * t_round;
+        const double t_split = (double)(((long)(mh / 256) * tn + cus - 1) / cus) * t_round + 4.0 + gemm_f32_direct_estimate_us<TileA>(M - mh, N, K, cus);
+        if (t_split < t_big) {
+            hipError_t e = gemm_big(h, role, al, W, epi, C, ldc, mh, N, K, s);
+            if (e != hipSuccess) return e;
+            return gemm<TileA>(h, role, rebase(al, mh), W, rebase(epi, mh), C + (long)mh * ldc, ldc, M - mh, N, K, s);
+        }
+    }
+    return gemm_big(h, role, al, W, epi, C, ldc, M, N, K, s);
+}
+
+// [r6] Whether the pose-only forward runs the last ViT layer on the live rows alone (egotap_lift_predict_pose): fc1 reads only the first T
+// cells of the grid, so the dummy cells' queries, attention rows, projections, MLP and final LayerNorm in that layer are never used -- only
+// their K and V feed the live rows.  Every product involved is row-independent and the pruned launches run the same kernels with the same
+// k order, so the pose keeps its bits -- provided nothing SPLITS: exact fp32 only, every last-layer product of the full problem on the
+// 256 x 256 kernel (GS_BIG: the large batches) and its attention unsplit.  Anything else takes the full path.
+static bool lift_prune_last(Handle* h, int B) {
+#ifdef EGOTAP_ATTN_F32_LIVE
+    const int D = h->D, M = B * h->seq, Nq = h->T * h->ppd * h->ppd;
+    if (h->precision != EGOTAP_PREC_F32 || h->debug_stop != 0 || h->cfg.vit_layers < 1 || Nq < 32 || Nq >= h->seq || D % 256 != 0) return false;
+    const int cus = device_cu_count();
+    if (gemm_small_route(h, true, M, 3 * D, D, D, cus, true).kind != GS_BIG || gemm_small_route(h, true, M, D, D, D, cus).kind != GS_BIG ||
+        gemm_small_route(h, true, M, 4 * D, D, 4 * D, cus, true).kind != GS_BIG || gemm_small_route(h, true, M, D, 4 * D, D, cus).kind != GS_BIG)
+        return false;
+    return attention_f32_ksplit(B, h->seq, h->cfg.vit_heads, SPLITK_FLOATS, cus) == 1;
+#else
+    (void)h; (void)B;
+    return false;
+#endif
+}
+
+static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream, bool pose_only,
+                             const char* who) {
     EGO_CHECK(h, "null handle");
     if (B == 0) return EGOTAP_OK;
-    EGO_CHECK(B > 0 && hm && pose && ws, "egotap_lift_forward: null argument or negative batch");
+    EGO_CHECK(B > 0 && hm && pose && ws, "%s: null argument or negative batch", who);
     EGO_CHECK(((uintptr_t)hm & 15) == 0 && ((uintptr_t)ws & 255) == 0, "hm must be 16-byte and ws 256-byte aligned");
     int rc = lift_resolve(h);
     if (rc != EGOTAP_OK) return rc;
@@ -1000,9 +1051,31 @@ extern "C" int egotap_lift_forward(egotap_handle h, const float* hm, int B, floa
     // H3-H8: pre-LN transformer layers.  [r4] Every LayerNorm but the first follows a residual projection: gemm_res_ln runs the two as one launch
     // where the projection is split over K (serving batches); ln1 of layer i + 1 (or the final LayerNorm) therefore rides with layer i's MLP.
     const int NL = h->cfg.vit_layers;
+    const bool prune = pose_only && lift_prune_last(h, B);
     EGO_HIP(launch_ln(X, Y, NL > 0 ? p.layer[0].ln1_g : p.lnf_g, NL > 0 ? p.layer[0].ln1_b : p.lnf_b, M, 1e-12f, s));
     for (int i = 0; i < NL; ++i) {
         const auto& L = p.layer[i];
+#ifdef EGOTAP_ATTN_F32_LIVE
+        if (prune && i + 1 == NL) {
+            // [r6] the last layer on the live rows, compact order (b, cell < T, patch row, patch col) = fc1's (LiveRows, gemm_f32.h).  Slices:
+            // K | V of all M rows into QKV's K / V columns, compact Q into its Q columns (rows 0 .. Mc); compact attention output in CTX; the
+            // compact residual stream Xc in QKV (dead after the attention), its LayerNorms in Y (dead after the projections), the MLP in HID.
+            const LiveRows lr{h->seq, h->side, h->ppd, h->grid, h->T};
+            const int Nq = h->T * h->ppd * h->ppd, Mc = B * Nq;
+            float* Xc = QKV;
+            SegMat Wkv; Wkv.p[0] = L.k_w; Wkv.p[1] = L.v_w; Wkv.p[2] = L.v_w; Wkv.seg = D; Wkv.ld = D;
+            SegVec bkv; bkv.p[0] = L.k_b; bkv.p[1] = L.v_b; bkv.p[2] = L.v_b; bkv.seg = D;
+            EGO_HIP((gemm_big(h, "kv", ALoadPlain{Y, D}, Wkv, EpiBias{bkv}, QKV + D, 3L * D, M, 2 * D, D, s)));
+            EGO_HIP((gemm_rounds(h, "q_live", ALoadLive{Y, D, lr}, segmat1(L.q_w, D, D), EpiBias{segvec1(L.q_b, D)}, QKV, 3L * D, Mc, D, D, s)));
+            EGO_HIP(attention_f32_live_launch(QKV, 3L * D, Nq, QKV, CTX, B, h->seq, h->cfg.vit_heads, s));
+            EGO_HIP((gemm_rounds(h, "attn_out_live", ALoadPlain{CTX, D}, segmat1(L.o_w, D, D), EpiBiasResLive{segvec1(L.o_b, D), X, D, lr}, Xc, D, Mc, D, D, s)));
+            EGO_HIP(launch_ln(Xc, Y, L.ln2_g, L.ln2_b, Mc, 1e-12f, s));
+            EGO_HIP((gemm_rounds(h, "mlp_up_live", ALoadPlain{Y, D}, segmat1(L.up_w, 4 * D, D), EpiBiasGelu{segvec1(L.up_b, 4 * D)}, HID, 4L * D, Mc, 4 * D, D, s)));
+            EGO_HIP((gemm_rounds(h, "mlp_down_live", ALoadPlain{HID, 4L * D}, segmat1(L.dn_w, D, 4 * D), EpiBiasRes{segvec1(L.dn_b, D), Xc, D}, Xc, D, Mc, D, 4 * D, s)));
+            EGO_HIP(launch_ln(Xc, Y, p.lnf_g, p.lnf_b, Mc, 1e-12f, s));       // compact tokens: fc1 reads them as plain rows below
+            break;
+        }
+#endif
         {
             SegMat Wqkv; Wqkv.p[0] = L.q_w; Wqkv.p[1] = L.k_w; Wqkv.p[2] = L.v_w; Wqkv.seg = D; Wqkv.ld = D;
             SegVec bqkv; bqkv.p[0] = L.q_b; bqkv.p[1] = L.k_b; bqkv.p[2] = L.v_b; bqkv.seg = D;
@@ -1026,13 +1099,16 @@ extern "C" int egotap_lift_forward(egotap_handle h, const float* hm, int B, floa
     const bool skinny_fc1 = BT < SKINNY_ROWS || (h->precision == EGOTAP_PREC_F32 && (long)((BT + 255) / 256) * (2048 / 256) < 100);
     {
         const int K1 = h->ppd * h->ppd * D;
-        ALoadTokens al{Y, h->T, D, h->seq, h->side, h->ppd, h->grid};
-        if (skinny_fc1 && BT <= 64)     // [r4] at most 64 rows: the 64-row tile (TileS)
-            EGO_HIP((gemm_f32_splitk_launch<TileS>(al, segmat1(p.pos_fc[0].w, 2048, K1), bn(p.pos_fc[0]), Z1, 2048, SPK, SPLITK_FLOATS, BT, 2048, K1, s, device_cu_count())));
-        else if (skinny_fc1)       // few row tiles: split K over the CUs
-            EGO_HIP((gemm_f32_splitk_launch<TileA>(al, segmat1(p.pos_fc[0].w, 2048, K1), bn(p.pos_fc[0]), Z1, 2048, SPK, SPLITK_FLOATS, BT, 2048, K1, s)));
-        else
-            EGO_HIP((gemm_big(h, "pos_fc1", al, segmat1(p.pos_fc[0].w, 2048, K1), bn(p.pos_fc[0]), Z1, 2048, BT, 2048, K1, s)));
+        auto fc1 = [&](const auto& al) -> hipError_t {
+            if (skinny_fc1 && BT <= 64)     // [r4] at most 64 rows: the 64-row tile (TileS)
+                return gemm_f32_splitk_launch<TileS>(al, segmat1(p.pos_fc[0].w, 2048, K1), bn(p.pos_fc[0]), Z1, 2048, SPK, SPLITK_FLOATS, BT, 2048, K1, s, device_cu_count());
+            if (skinny_fc1)                 // few row tiles: split K over the CUs
+                return gemm_f32_splitk_launch<TileA>(al, segmat1(p.pos_fc[0].w, 2048, K1), bn(p.pos_fc[0]), Z1, 2048, SPK, SPLITK_FLOATS, BT, 2048, K1, s);
+            return gemm_big(h, "pos_fc1", al, segmat1(p.pos_fc[0].w, 2048, K1), bn(p.pos_fc[0]), Z1, 2048, BT, 2048, K1, s);
+        };
+        // [r6] after the pruned last layer Y holds the compact tokens, row (b, i) = ppd^2 * D contiguous floats: the same values in the same k order
+        if (prune) EGO_HIP(fc1(ALoadPlain{Y, (long)K1}));
+        else EGO_HIP(fc1(ALoadTokens{Y, h->T, D, h->seq, h->side, h->ppd, h->grid}));
         EGO_HIP((fc_gemm(h, "pos_fc2", ALoadPlain{Z1, 2048}, segmat1(p.pos_fc[1].w, 512, 2048), bn(p.pos_fc[1]), Z2, 512, BT, 512, 2048, SPK, s)));
         EGO_HIP((fc_gemm(h, "pos_fc3", ALoadPlain{Z2, 512}, segmat1(p.pos_fc[2].w, hid, 512), bn(p.pos_fc[2]), POSZ, hid, BT, hid, 512, SPK, s)));
     }
@@ -1089,6 +1165,13 @@ extern "C" int egotap_lift_forward(egotap_handle h, const float* hm, int B, floa
                        J, hid, H, h->cfg.estimate_head);
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
+}
+
+extern "C" int egotap_lift_forward(egotap_handle h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream) {
+    return lift_forward_impl(h, hm, B, pose, ws, ws_bytes, stream, false, "egotap_lift_forward");
+}
+extern "C" int egotap_lift_predict_pose(egotap_handle h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream) {
+    return lift_forward_impl(h, hm, B, pose, ws, ws_bytes, stream, true, "egotap_lift_predict_pose");
 }
 #endif
 

@@ -82,6 +82,33 @@ struct ALoadTokens {
     __host__ bool dma_ok() const { return D % 4 == 0 && ((uintptr_t)Y & 15) == 0; }
 };
 
+// [r6] The pose-only forward's compact row order over the ViT's live tokens: row m = (b, cell i < T, patch row, patch col) -- fc1's
+// order, so fc1 reads the compact final-LayerNorm tokens as plain rows of ppd^2 * D -- mapped to its physical row b * seq + pr * side + pc
+// of the tiled image.  The grid's dummy cells (i >= T) have no compact row.
+struct LiveRows {
+    int seq, side, ppd, grid, T;
+    int m0 = 0;        // compact row of m = 0 (a product cut into row ranges)
+    __host__ __device__ __forceinline__ long phys(int m) const {
+        m += m0;
+        const int pp = ppd * ppd, L = T * pp;
+        const int b = m / L, r = m - b * L, i = r / pp, s = r - i * pp;
+        const int pr = (i / grid) * ppd + s / ppd, pc = (i % grid) * ppd + s % ppd;
+        return (long)b * seq + pr * side + pc;
+    }
+};
+// plain rows gathered in the compact order above (the last ViT layer's Q projection of the pose-only forward)
+struct ALoadLive {
+    const float* A;    // [B * seq, lda] physical rows
+    long lda;
+    LiveRows lr;
+    struct Row { const float* p; };
+    __device__ __forceinline__ Row row(int m) const { return Row{A + lr.phys(m) * lda}; }
+    __device__ __forceinline__ f32x4 load(const Row& r, int k) const { return *(const f32x4*)(r.p + k); }
+    static constexpr bool HAS_PTR = true;
+    __device__ __forceinline__ const float* ptr(const Row& r, int k) const { return r.p + k; }
+    __host__ bool dma_ok() const { return lda % 4 == 0 && lda < (1L << 21) && ((uintptr_t)A & 15) == 0; }
+};
+
 // fc1 of the rotation encoder: row (b, eye*J + j) = [cos map | sin map] of limb j of that eye.
 // Reference: net_architecture.py:690-694 (channel order L_cos, L_sin, R_cos, R_sin after 2J position maps).
 struct ALoadRot {
@@ -165,6 +192,22 @@ struct EpiBiasRes {       // C = acc + bias + R[m, n]   (R may alias C)
     __device__ __forceinline__ Col4 col4(int n0) const { return Col4{bias.at4(n0)}; }
     static constexpr bool HAS_RES = true;
     __device__ __forceinline__ f32x4 res4(int m, int n0) const { return *(const f32x4*)(R + (long)m * ldr + n0); }
+    __device__ __forceinline__ f32x4 apply4(f32x4 acc, const Col4& c, f32x4 res, int m, int n0) const { return acc + c.b + res; }
+};
+struct EpiBiasResLive {   // C = acc + bias + R[phys(m), n]: compact output row m, residual read from its physical row (LiveRows)
+    SegVec bias;
+    const float* R;    // must not alias C
+    long ldr;
+    LiveRows lr;
+    struct Col { float b; };
+    __device__ __forceinline__ Col col(int n) const { return Col{bias.at(n)}; }
+    __device__ __forceinline__ float apply(float acc, const Col& c, int m, int n) const {
+        return acc + c.b + R[lr.phys(m) * ldr + n];
+    }
+    struct Col4 { f32x4 b; };
+    __device__ __forceinline__ Col4 col4(int n0) const { return Col4{bias.at4(n0)}; }
+    static constexpr bool HAS_RES = true;
+    __device__ __forceinline__ f32x4 res4(int m, int n0) const { return *(const f32x4*)(R + lr.phys(m) * ldr + n0); }
     __device__ __forceinline__ f32x4 apply4(f32x4 acc, const Col4& c, f32x4 res, int m, int n0) const { return acc + c.b + res; }
 };
 struct EpiBiasGelu {      // exact erf GELU (modeling_vit.py:320-327, hidden_act='gelu')

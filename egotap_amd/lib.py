@@ -34,6 +34,7 @@ _PROTOS = {
     "egotap_unbound_count": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "egotap_lift_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
     "egotap_lift_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_lift_predict_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_debug_stop": (C.c_int, [C.c_void_p, C.c_int]),
     "egotap_set_precision": (C.c_int, [C.c_void_p, C.c_int]),

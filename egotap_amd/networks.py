@@ -239,7 +239,9 @@ class EgoTAPAutoEncoder(nn.Module):
             with torch.cuda.device(dev):
                 self._bind(dev)
                 ws = self._workspace(B, dev)
-                _lib.check(_lib.load().egotap_lift_forward(
+                # predict_pose: the pose-only entry (same bits; the last ViT layer skips the rows fc1 never reads), forward(): every intermediate
+                entry = _lib.load().egotap_lift_predict_pose if pose_only else _lib.load().egotap_lift_forward
+                _lib.check(entry(
                     self._ensure_handle(), C.c_void_p(hm.data_ptr()), B, C.c_void_p(pose.data_ptr()),
                     C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         if pose_only:
@@ -248,8 +250,9 @@ class EgoTAPAutoEncoder(nn.Module):
 
     def predict_pose_graphed(self, input):
         """predict_pose through a captured HIP graph (serving at small batches, where the ~130 launches of a forward cost more than
-        the kernels): egotap_lift_forward is captured once per (batch, device, precision, parameter pointers) with a static input
-        and output buffer and replayed afterwards -- same kernels, same bits (tests/test_gpu_lift.py).  Eval mode only; the returned
+        the kernels): the forward is captured once per (batch, device, precision, parameter pointers) with a static input
+        and output buffer and replayed afterwards -- same kernels, same bits (tests/test_gpu_lift.py).  [r6] Captures the pose-only entry
+        (egotap_lift_predict_pose), as predict_pose runs it.  Eval mode only; the returned
         tensor is the graph's static output buffer (valid until the next call with the same batch)."""
         if self.training:
             raise RuntimeError("predict_pose_graphed is an inference path: call .eval() first")
@@ -280,8 +283,8 @@ class EgoTAPAutoEncoder(nn.Module):
             keep = (ws, getattr(self, "_ascratch", None), getattr(self, "_wscratch", None))
 
             def run():
-                _lib.check(lib.egotap_lift_forward(h, C.c_void_p(static_in.data_ptr()), B, C.c_void_p(static_out.data_ptr()),
-                                                   C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                _lib.check(lib.egotap_lift_predict_pose(h, C.c_void_p(static_in.data_ptr()), B, C.c_void_p(static_out.data_ptr()),
+                                                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.device(dev), torch.cuda.stream(side):

@@ -79,9 +79,15 @@ int egotap_unbound_count(egotap_handle h, int net, int* count);
  * not computed here: the host mirror returns cached zeros. */
 int egotap_lift_workspace_bytes(egotap_handle h, int B, size_t* bytes);
 int egotap_lift_forward(egotap_handle h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream);
+/* [r6] predict_pose: the same arguments, checks and pose bits as egotap_lift_forward, but only `pose` is defined afterwards.  Where
+ * every product of the last ViT layer would run unsplit (exact fp32, batches that fill the chip) that layer runs on the live tokens
+ * alone -- the grid's dummy cells feed it only through their keys and values, and fc1 never reads their outputs.  Otherwise, and
+ * whenever egotap_lift_debug_stop is set, it runs the full forward. */
+int egotap_lift_predict_pose(egotap_handle h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream);
 
 /* where an intermediate lives inside ws after egotap_lift_forward (for parity tests):
- * name in {"tokens","pos_embed","rot_embed","skel_embed"}; offset in bytes, numel in floats */
+ * name in {"tokens","pos_embed","rot_embed","skel_embed"}; offset in bytes, numel in floats.
+ * After egotap_lift_predict_pose "tokens" (and "x") are unspecified: the pruned last layer leaves compact rows there. */
 int egotap_lift_intermediate(egotap_handle h, int B, const char* name, size_t* offset, int64_t* numel);
 
 /* HeatMap_UnrealEgo_Shared.forward(left, right) (model/net_architecture.py:25-173; resnet18 backbone), eval mode:
