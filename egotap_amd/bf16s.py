@@ -156,3 +156,15 @@ def fc1_dgrad_tokens(h, dz, wt, B, seq, D):
     dtok = torch.empty((B * seq, D), dtype=torch.bfloat16, device=dz.device)
     _lib.check(_lib.load().egotap_bf16_fc1_dgrad_tokens(h, _p(dz), _p(wt), _p(dtok), B, _s()))
     return dtok
+
+
+def fc1_dgrad_rot(h, dz, wt, dhm, B):
+    """rotation channels of the heatmaps' gradient dhm fp32 [B, 6J, S, S] from fc1's dz bf16 [B*T, 2048] and fc1.weight^T bf16 [2 S^2, 2048]"""
+    _lib.check(_lib.load().egotap_bf16_fc1_dgrad_rot(h, _p(dz), _p(wt), _p(dhm), B, _s()))
+    return dhm
+
+
+def patch_dgrad(h, dx, wt, dhm, B):
+    """position channels of dhm fp32 [B, 6J, S, S] from the patch embedding's dx bf16 [B*seq, D] and projection.weight^T bf16 [256, D]"""
+    _lib.check(_lib.load().egotap_bf16_patch_dgrad(h, _p(dx), _p(wt), _p(dhm), B, _s()))
+    return dhm

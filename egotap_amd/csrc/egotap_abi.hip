@@ -2096,7 +2096,7 @@ using TnBig = TnCfg<256, 256, 16, 4, 2>;     // 8 waves, 64x128 per wave
 using TnSmall = TnCfg<128, 128, 16, 2, 2>;   // 4 waves, 64x64 per wave
 
 enum { LD_PLAIN = 0, LD_PATCH = 1, LD_TOKENS = 2, LD_ROT = 3, LD_STEREO = 4, LD_STEREO_GATED = 5 };
-enum { TE_NONE = 0, TE_BIAS = 1, TE_BIAS_RES = 2, TE_BIAS_GELU_SAVE = 3, TE_ACCUM = 4, TE_GELU_GRAD = 5, TE_PATCH = 6 };
+enum { TE_NONE = 0, TE_BIAS = 1, TE_BIAS_RES = 2, TE_BIAS_GELU_SAVE = 3, TE_ACCUM = 4, TE_GELU_GRAD = 5, TE_PATCH = 6, TE_SCATTER_PATCH = 7, TE_SCATTER_ROT = 8 };
 
 template <class AL, class Epi>
 static hipError_t nt_any(Handle* h, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc, int M, int N, int K, hipStream_t s) {
@@ -2139,8 +2139,30 @@ static hipError_t nt_epi(const AL& al, const float* w, const float* b, float* y,
     }
 }
 
+// Input gradient of the lifting head w.r.t. its heatmaps (plain A = the gradient at the patch embedding's output [B * seq, D] or at the rotation
+// encoder's fc1 pre-activation [B * T, 2048], W = the transposed weight): scattered straight into dhm by the epilogue.  Only these routes are
+// instantiated (each is one kernel per epilogue): bf16x3 / bf16 arithmetic on the persistent kernel, fp32 on the LDS-DMA kernel, small M on
+// the 128 x 128 tiles.
+template <class Epi>
+static hipError_t nt_scatter(Handle* h, const float* A, long lda, const float* wt, const Epi& epi, int M, int N, int K, hipStream_t s) {
+    const ALoadPlain al{A, lda};
+    const SegMat W = segmat1(wt, N, K);
+    float* C = epi.hm;                      // (the kernels store through epi.dst(); C is not addressed)
+    if (N % 256 == 0 && K % 32 == 0 && M >= 1024 && h->precision == EGOTAP_PREC_BF16X3)
+        return gemm_bf16_persist_launch<BfCfg<3, 1>, ALoadPlain, Epi>(al, W, epi, C, N, M, N, K, device_cu_count(), s);
+    if (N % 256 == 0 && K % 32 == 0 && M >= 1024 && h->precision == EGOTAP_PREC_BF16)
+        return gemm_bf16_persist_launch<BfCfg<1, 1>, ALoadPlain, Epi>(al, W, epi, C, N, M, N, K, device_cu_count(), s);
+    if (N % DmaF32Cfg::BN == 0 && K % DmaF32Cfg::BK == 0 && M >= 1024 && al.dma_ok())
+        return gemm_f32_dma_launch(al, W, epi, C, N, M, N, K, device_cu_count(), s);
+    if (N % 128 == 0 && K % 32 == 0) return gemm_f32_launch<TileA, ALoadPlain, Epi>(al, W, epi, C, N, M, N, K, s);
+    return hipErrorInvalidValue;
+}
+
 // y[M,N] = epi(A(x) W^T (+ b)); `loader` gathers A from x exactly as the eval forward does; aux = gate source (F) for LD_STEREO_GATED.
 // r: residual / accumulate source / saved pre-activation (by epi); z: pre-activation output for TE_BIAS_GELU_SAVE.
+// TE_SCATTER_PATCH / TE_SCATTER_ROT (loader LD_PLAIN, no bias): y = dhm fp32 [B, C, S, S] (16-byte aligned), the heatmap gradient of the patch
+// embedding (x = its output gradient [B * seq, D], w = projection.weight^T [256, D]; M = B * seq, N = 256, K = D) or of the rotation
+// encoder's fc1 (x = its pre-activation gradient [B * T, 2048], w = fc1.weight^T [2 S^2, 2048]; M = B * T, N = 2 S^2, K = 2048)
 #if EGOTAP_IN(1)
 extern "C" int egotap_train_gemm_nt(egotap_handle h, int loader, const float* x, int64_t lda, const float* aux, const float* w, const float* b,
                                     float* y, int M, int N, int K, int epi, const float* r, float* z, int Bsz, void* stream) {
@@ -2149,6 +2171,19 @@ extern "C" int egotap_train_gemm_nt(egotap_handle h, int loader, const float* x,
     hipStream_t s = (hipStream_t)stream;
     const int S = h->cfg.hm_size;
     hipError_t e;
+    if (epi == TE_SCATTER_PATCH || epi == TE_SCATTER_ROT) {
+        const bool patch = epi == TE_SCATTER_PATCH;
+        const int rows = patch ? h->seq : h->T;
+        EGO_CHECK(loader == LD_PLAIN && M > 0 && M % rows == 0 && N == (patch ? 256 : 2 * S * S) && K == (patch ? h->D : 2048),
+                  "egotap_train_gemm_nt: the %s scatter takes plain rows, M a multiple of %d, N = %d, K = %d (got loader %d, M=%d N=%d K=%d)",
+                  patch ? "patch" : "rotation", rows, patch ? 256 : 2 * S * S, patch ? h->D : 2048, loader, M, N, K);
+        EGO_CHECK(((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0 && lda % 4 == 0, "egotap_train_gemm_nt: dhm and x must be 16-byte aligned, lda a multiple of 4");
+        e = patch ? nt_scatter(h, x, lda, w, EpiScatterPatch{{}, y, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T}, M, N, K, s)
+                  : nt_scatter(h, x, lda, w, EpiScatterRot{{}, y, h->C, h->J, S * S}, M, N, K, s);
+        if (e == hipErrorInvalidValue) { egotap_set_error("egotap_train_gemm_nt: unsupported shape M=%d N=%d K=%d epi=%d", M, N, K, epi); return EGOTAP_ERR_INVALID; }
+        EGO_HIP(e);
+        return EGOTAP_OK;
+    }
     switch (loader) {
         case LD_PLAIN: e = nt_epi(ALoadPlain{x, (long)lda}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
         case LD_TOKENS: e = nt_epi(ALoadTokens{x, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
@@ -3275,6 +3310,30 @@ extern "C" int egotap_bf16_fc1_dgrad_tokens(egotap_handle h, const void* dz, con
 }
 #endif
 
+#if EGOTAP_IN(3)
+// input gradient of fc1 of the rotation encoder, scattered back to the heatmaps (the inverse of the XRot gather): dz bf16 [B*T, 2048], wt bf16
+// [2 S^2, 2048] = fc1.weight^T (egotap_bf16_prep_weight), dhm fp32 [B, C, S, S] (16-byte aligned): channels [2J, 6J) written, each element once
+extern "C" int egotap_bf16_fc1_dgrad_rot(egotap_handle h, const void* dz, const void* wt, float* dhm, int B, void* stream) {
+    EGO_CHECK(h && dz && wt && dhm && B > 0 && ((uintptr_t)dhm & 15) == 0, "egotap_bf16_fc1_dgrad_rot: bad argument");
+    const int BT = B * h->T, S = h->cfg.hm_size;
+    EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dz, 2048L}, (const __bf16*)wt, 2048L, SEpiScatterRot{dhm, h->C, h->J, S * S}, BT, 2 * S * S, 2048,
+                                    device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+#endif
+
+#if EGOTAP_IN(3)
+// input gradient of the patch embedding, scattered back to the heatmaps (the inverse of the XPatch gather): dx bf16 [B*seq, D], wt bf16 [256, D]
+// = projection.weight^T, dhm fp32 [B, C, S, S] (16-byte aligned): channels [0, 2J) written, each element once; dummy cells store nothing
+extern "C" int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const void* wt, float* dhm, int B, void* stream) {
+    EGO_CHECK(h && dx && wt && dhm && B > 0 && ((uintptr_t)dhm & 15) == 0, "egotap_bf16_patch_dgrad: bad argument");
+    const int M = B * h->seq, D = h->D, S = h->cfg.hm_size;
+    EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dx, (long)D}, (const __bf16*)wt, (long)D,
+                                    SEpiScatterPatch{dhm, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T}, M, 256, D, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+#endif
+
 // ------------------------------------------------------------------------------------------------ one-call training step
 // egotap_lift_forward_train + egotap_lift_backward: the lifting head's training-mode forward (activations kept in `saved`) and its
 // whole backward as ONE call each (egotap_lift_forward(…, saved, …) / egotap_lift_backward; reference:
@@ -3505,12 +3564,15 @@ static int lift_forward_train16(Handle* h, const float* hm, int B, float* pose, 
     return EGOTAP_OK;
 }
 
-static int lift_backward16(Handle* h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
-                           void* const* bucket_events, int n_events, void* stream) {
+static int lift_backward16(const char* fn, Handle* h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes, void* ws,
+                           size_t ws_bytes, void* const* bucket_events, int n_events, void* stream, float* dhm) {
     LiftTrain16Plan t; LiftBwd16Plan w;
     EGO_RC(lift_train16_plan(h, B, t, w));
-    EGO_CHECK(saved_bytes >= t.total, "egotap_lift_backward: saved buffer too small (%zu < %zu)", saved_bytes, t.total);
-    EGO_CHECK(ws_bytes >= w.total, "egotap_lift_backward: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    EGO_CHECK(saved_bytes >= t.total, "%s: saved buffer too small (%zu < %zu)", fn, saved_bytes, t.total);
+    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
+    const size_t K1r = 2 * (size_t)h->cfg.hm_size * h->cfg.hm_size;
+    // dhm: the bf16 copies of rotation fc1.weight (+ its transpose) and of projection.weight (+ transpose) live in the scratch while it is free
+    EGO_CHECK(!dhm || w.scr_bytes >= 2 * 2048 * K1r * 2, "%s: scratch too small for the transposed rotation fc1 weight", fn);
     const int L = h->cfg.vit_layers;
     const LiftParams& p = h->lp;
     const LiftParams& g = h->lg;
@@ -3558,7 +3620,13 @@ static int lift_backward16(Handle* h, const float* hm, const float* dpose, int B
             } else {
                 EGO_RC(egotap_bf16_from_f32(dz, Wh(w.dzb), (int64_t)BT * 2048, stream));
                 EGO_RC(egotap_bf16_fc1_wgrad(h, e, Wh(w.dzb), e == 0 ? Hb(t.tokens) : Hb(t.hmb), G(gc.w), B, ZERO, scr, scrb, stream));
-                if (e == 0) EGO_RC(egotap_bf16_fc1_dgrad_tokens(h, Wh(w.dzb), Hb(t.w_fc1p_t), dtok, B, stream));
+                if (e == 0) {
+                    EGO_RC(egotap_bf16_fc1_dgrad_tokens(h, Wh(w.dzb), Hb(t.w_fc1p_t), dtok, B, stream));
+                } else if (dhm) {           // the heatmaps' rotation channels: the scratch is free between this weight gradient and the next
+                    __bf16* wr = (__bf16*)scr;
+                    EGO_RC(egotap_bf16_prep_weight(fc.w, wr, wr + 2048 * K1r, 2048, (int)K1r, 2048, stream));
+                    EGO_RC(egotap_bf16_fc1_dgrad_rot(h, Wh(w.dzb), wr + 2048 * K1r, dhm, B, stream));
+                }
             }
         }
         return EGOTAP_OK;
@@ -3594,7 +3662,7 @@ static int lift_backward16(Handle* h, const float* hm, const float* dpose, int B
         for (int q = 0; q < 3; ++q)
             EGO_RC(egotap_bf16_gemm_tn((const __bf16*)A3 + (size_t)q * D, 3 * D, Hb(l.y1), D, gw[q], M, D, D, 0, ZERO, scr, scrb, stream));
         EGO_RC(egotap_bf16_gemm_nt(A3, 3 * D, Hb(l.w_qkv_t), nullptr, M, D, 3 * D, 0, nullptr, R0, nullptr, D, stream));             // dy1
-        EGO_RC(egotap_bf16_layernorm_bwd(S(t.X[i]), R0, P_.ln1_g, S(l.m1), S(l.r1), F1, F0, i > 0 ? R1 : nullptr, G(G_.ln1_g), G(G_.ln1_b),
+        EGO_RC(egotap_bf16_layernorm_bwd(S(t.X[i]), R0, P_.ln1_g, S(l.m1), S(l.r1), F1, F0, i > 0 || dhm ? R1 : nullptr, G(G_.ln1_g), G(G_.ln1_b),
                                          i > 0 ? G(g.layer[i - 1].dn_b) : nullptr, M, 0, scr, scrb, stream));                        // dx = F0, R1
     }
     // patch embedding (fp32 operands: the input heatmaps)
@@ -3603,6 +3671,11 @@ static int lift_backward16(Handle* h, const float* hm, const float* dpose, int B
     EGO_RC(egotap_train_patch_split(h, g.pos_emb, G(g.patch_b), G(g.mask_tok), 0, stream));
     EGO_RC(bucket_done());
     EGO_RC(bucket_done());
+    if (dhm) {                      // the heatmaps' position channels, behind the last bucket event (its all-reduce overlaps this product)
+        __bf16* pw = (__bf16*)scr;
+        EGO_RC(egotap_bf16_prep_weight(p.patch_w, pw, pw + (size_t)D * 256, D, 256, D, stream));
+        EGO_RC(egotap_bf16_patch_dgrad(h, R1, pw + (size_t)D * 256, dhm, B, stream));
+    }
     return EGOTAP_OK;
 }
 
@@ -3656,21 +3729,21 @@ extern "C" int egotap_lift_forward_train(egotap_handle h, const float* hm, int B
     return EGOTAP_OK;
 }
 
-extern "C" int egotap_lift_backward(egotap_handle h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes,
-                                    void* ws, size_t ws_bytes, void* const* bucket_events, int n_events, void* stream) {
-    EGO_CHECK(h && hm && dpose && saved && ws && B > 0, "egotap_lift_backward: bad argument");
+// the backward of egotap_lift_backward (dhm == nullptr) and of egotap_lift_backward_dhm (fn: the entry's name, for its messages)
+static int lift_backward_impl(const char* fn, Handle* h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes,
+                              void* ws, size_t ws_bytes, void* const* bucket_events, int n_events, void* stream, float* dhm) {
     EGO_RC(lift_resolve(h));
     if (!h->grad_resolved) {
         EGO_RC(lift_resolve_into(h, h->bound_grad, h->lg, false));
         h->grad_resolved = true;
     }
     const int L = h->cfg.vit_layers;
-    EGO_CHECK(n_events == 0 || (bucket_events && n_events == L + 2), "egotap_lift_backward: %d bucket events, the arena has %d buckets", n_events, L + 2);
-    if (lift_train_bf16s(h)) return lift_backward16(h, hm, dpose, B, saved, saved_bytes, ws, ws_bytes, bucket_events, n_events, stream);
+    EGO_CHECK(n_events == 0 || (bucket_events && n_events == L + 2), "%s: %d bucket events, the arena has %d buckets", fn, n_events, L + 2);
+    if (lift_train_bf16s(h)) return lift_backward16(fn, h, hm, dpose, B, saved, saved_bytes, ws, ws_bytes, bucket_events, n_events, stream, dhm);
     LiftTrainPlan t; LiftBwdPlan w;
     EGO_RC(lift_train_plan(h, B, t, w));
-    EGO_CHECK(saved_bytes >= t.total, "egotap_lift_backward: saved buffer too small (%zu < %zu)", saved_bytes, t.total);
-    EGO_CHECK(ws_bytes >= w.total, "egotap_lift_backward: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    EGO_CHECK(saved_bytes >= t.total, "%s: saved buffer too small (%zu < %zu)", fn, saved_bytes, t.total);
+    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
     const LiftParams& p = h->lp;
     const LiftParams& g = h->lg;
     auto G = [](const float* q) { return (float*)q; };
@@ -3709,7 +3782,13 @@ extern "C" int egotap_lift_backward(egotap_handle h, const float* hm, const floa
             EGO_RC(egotap_train_bn_lrelu_bwd(S(f.z), S(f.y), dy, fc.g, S(f.mean), S(f.rstd), dz, G(gc.g), G(gc.beta), BT, n, 0, scr, scrb, stream));
             EGO_RC(egotap_train_gemm_tn(h, loader, dz, 0, a_in, nullptr, G(gc.w), BT, n, K, 0, 0, scr, scrb, stream));
             EGO_RC(egotap_train_colsum(dz, 0, G(gc.b), BT, n, 0, scr, scrb, stream));
-            if (j == 0 && e == 1) return EGOTAP_OK;                          // the rotation encoder's input is data
+            if (j == 0 && e == 1) {                                          // the rotation encoder's input: the heatmaps
+                if (dhm) {                                                   // their rotation channels, while dz (E[0]) is live
+                    EGO_RC(egotap_train_transpose(fc.w, W(w.WT), n, K, 0, stream));                                              // [2 S^2, 2048]
+                    EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, W(w.WT), nullptr, dhm, BT, K, n, TE_SCATTER_ROT, nullptr, nullptr, 0, stream));
+                }
+                return EGOTAP_OK;
+            }
             EGO_RC(egotap_train_transpose(fc.w, W(w.WT), n, K, 0, stream));  // [K, n]
             float* dnext = j == 0 ? W(w.R[1]) : W(w.E[1]);
             EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, W(w.WT), nullptr, dnext, BT, K, n, 0, nullptr, nullptr, 0, stream));
@@ -3763,6 +3842,31 @@ extern "C" int egotap_lift_backward(egotap_handle h, const float* hm, const floa
     EGO_RC(egotap_train_patch_split(h, g.pos_emb, G(g.patch_b), G(g.mask_tok), 0, stream));
     EGO_RC(bucket_done());
     EGO_RC(bucket_done());
+    if (dhm) {                      // the heatmaps' position channels, behind the last bucket event (its all-reduce overlaps this product)
+        EGO_RC(egotap_train_transpose(p.patch_w, WT, D, 256, 0, stream));                                                       // [256, D]
+        EGO_RC(egotap_train_gemm_nt(h, 0, dx, 0, nullptr, WT, nullptr, dhm, M, 256, D, TE_SCATTER_PATCH, nullptr, nullptr, 0, stream));
+    }
     return EGOTAP_OK;
+}
+
+extern "C" int egotap_lift_backward(egotap_handle h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes,
+                                    void* ws, size_t ws_bytes, void* const* bucket_events, int n_events, void* stream) {
+    EGO_CHECK(h && hm && dpose && saved && ws && B > 0, "egotap_lift_backward: bad argument");
+    return lift_backward_impl("egotap_lift_backward", h, hm, dpose, B, saved, saved_bytes, ws, ws_bytes, bucket_events, n_events, stream, nullptr);
+}
+
+// egotap_lift_backward that also returns the gradient w.r.t. the input heatmaps: dhm fp32 [B, C, S, S] (contiguous, 16-byte aligned, not
+// overlapping hm), every element written exactly once -- position channels from the patch embedding, rotation channels from the rotation
+// encoder's fc1.  dhm == nullptr: exactly egotap_lift_backward (same launches, same bits).  Same workspace (egotap_lift_train_bytes).
+extern "C" int egotap_lift_backward_dhm(egotap_handle h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes,
+                                        void* ws, size_t ws_bytes, void* const* bucket_events, int n_events, void* stream, float* dhm) {
+    EGO_CHECK(h && hm && dpose && saved && ws && B > 0, "egotap_lift_backward_dhm: bad argument");
+    if (dhm) {
+        const size_t bytes = (size_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size * sizeof(float);
+        const uintptr_t a = (uintptr_t)dhm, b = (uintptr_t)hm;
+        EGO_CHECK((a & 15) == 0, "egotap_lift_backward_dhm: dhm must be 16-byte aligned");
+        EGO_CHECK(a + bytes <= b || b + bytes <= a, "egotap_lift_backward_dhm: dhm must not overlap hm");
+    }
+    return lift_backward_impl("egotap_lift_backward_dhm", h, hm, dpose, B, saved, saved_bytes, ws, ws_bytes, bucket_events, n_events, stream, dhm);
 }
 #endif

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_bf16_persist_ker
                     f32x4 o = {0.f, 0.f, 0.f, 0.f};
                     if (ok) o = epi.apply4(*(const f32x4*)(Es + (s4 * 8 + er) * ELD + ec), cc, rs[s4], mb + s4 * 8, n0);
                     if (more) rs[s4] = epi.res4(min(mb0 + in * 32 + s4 * 8, M - 1), nb0 + jn * 32);
-                    if (ok) *(f32x4*)(C + (long)(mb + s4 * 8) * ldc + n0) = o;
+                    if (ok) epi_store4(epi, C, ldc, mb + s4 * 8, n0, o);
                 }
             }
         }

@@ -31,6 +31,7 @@ template <class Epi>
 __global__ __launch_bounds__(DmaCfg::THREADS, 2) void gemm_bf16_dma_kernel(const __bf16* __restrict__ A, long lda, SegMatB W, Epi epi, float* C,
                                                                           long ldc, int M, int N, int K, int tiles_m, int tiles_n) {
     using Cfg = DmaCfg;
+    static_assert(!epi_scatters<Epi>::value, "row-major output only");
     constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, NS = Cfg::NS, TM = Cfg::TM, TN = Cfg::TN, ROWB = Cfg::ROWB, ELD = Cfg::ELD;
     extern __shared__ __attribute__((aligned(16))) char smem_dma[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;

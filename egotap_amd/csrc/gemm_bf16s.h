@@ -330,6 +330,41 @@ struct SEpiScatterTokens {
         store_bf16x8(out + tok * D + c, v);
     }
 };
+// input gradient of the lifting head w.r.t. its heatmaps, fp32 into dhm [B, C, S, S] (NCHW; SEpiHeatNCHW of conv_bf16s.h is the other fp32
+// NCHW output): the inverses of XPatch (row = ViT token, column = pixel of its 16 x 16 patch; dummy cells store nothing) and XRot (row =
+// (frame, eye, limb), columns = [cos plane | sin plane]).  Every heatmap element is one (row, column): written once, no clearing.
+struct SEpiScatterPatch {
+    static constexpr int W = 4, STORES = 1;
+    float* hm;
+    int C, S, seq, side, ppd, grid, T;
+    typedef SNoAux Col;
+    typedef SNoAux Aux;
+    __device__ __forceinline__ Col col(int n) const { return Col{}; }
+    __device__ __forceinline__ Aux fetch(int m, int n) const { return Aux{}; }
+    __device__ __forceinline__ void emit(float* v, const Col&, const Aux&, int m, int n) const {
+        const int b = m / seq, tok = m - b * seq;
+        const int pr = tok / side, pc = tok - pr * side;
+        const int cell = (pr / ppd) * grid + pc / ppd;
+        if (cell >= T) return;
+        *(f32x4*)(hm + ((long)(b * C + cell) * S + (pr % ppd) * 16 + (n >> 4)) * S + (pc % ppd) * 16 + (n & 15)) = f32x4{v[0], v[1], v[2], v[3]};
+    }
+};
+template <> struct s_epi_exact<SEpiScatterPatch> { static constexpr bool value = false; };    // a wave whose rows are all dummy cells stores nothing
+struct SEpiScatterRot {
+    static constexpr int W = 4, STORES = 1;
+    float* hm;
+    int C, J, HW;
+    typedef SNoAux Col;
+    typedef SNoAux Aux;
+    __device__ __forceinline__ Col col(int n) const { return Col{}; }
+    __device__ __forceinline__ Aux fetch(int m, int n) const { return Aux{}; }
+    __device__ __forceinline__ void emit(float* v, const Col&, const Aux&, int m, int n) const {
+        const int T = 2 * J;
+        const int b = m / T, t = m - b * T;
+        const int eye = t / J, j = t - eye * J, cs = n / HW;
+        *(f32x4*)(hm + (long)(b * C + 2 * J + eye * 2 * J + cs * J + j) * HW + (n - cs * HW)) = f32x4{v[0], v[1], v[2], v[3]};
+    }
+};
 
 // ---------------------------------------------------------------------------------------------------- kernel
 // NI = 16-column MFMA tiles per wave: 4 -> a 256 x 256 output tile (the default); [r3] 2 -> 256 x 128, 1 -> 256 x 64, for GEMMs whose N

@@ -345,6 +345,52 @@ struct EpiGeluGrad {      // C = acc * gelu'(Z[m, n])   (input gradient of the M
     }
 };
 
+// ---- input gradient of the lifting head w.r.t. its heatmaps: C = acc, written into dhm [B, C, S, S] (fp32, NCHW) at dst(m, n) instead of
+// row-major C.  Each element of the heatmaps is read by exactly one (row, column) of its forward loader, so each is written exactly once.
+struct EpiScatterPatch : EpiNone {    // inverse of ALoadPatch: row m = ViT token, column k = pixel (k >> 4, k & 15) of its 16 x 16 patch
+    float* hm;
+    int C, S, seq, side, ppd, grid, T;
+    __device__ __forceinline__ float* dst(int m, int n) const {      // nullptr: a dummy cell of the grid, which no heatmap pixel feeds
+        const int b = m / seq, tok = m - b * seq;
+        const int pr = tok / side, pc = tok - pr * side;
+        const int cell = (pr / ppd) * grid + pc / ppd;
+        if (cell >= T) return nullptr;
+        return hm + ((long)(b * C + cell) * S + (pr % ppd) * 16 + (n >> 4)) * S + (pc % ppd) * 16 + (n & 15);
+    }
+};
+struct EpiScatterRot : EpiNone {      // inverse of ALoadRot: row (b, eye * J + j), columns [cos plane | sin plane] of that limb
+    float* hm;
+    int C, J, HW;
+    __device__ __forceinline__ float* dst(int m, int n) const {
+        const int T = 2 * J;
+        const int b = m / T, t = m - b * T;
+        const int eye = t / J, j = t - eye * J, cs = n / HW;
+        return hm + (long)(b * C + 2 * J + eye * 2 * J + cs * J + j) * HW + (n - cs * HW);
+    }
+};
+template <class E> struct epi_scatters : std::false_type {};
+template <> struct epi_scatters<EpiScatterPatch> : std::true_type {};
+template <> struct epi_scatters<EpiScatterRot> : std::true_type {};
+// the output stores of gemm_f32_kernel, gemm_f32_dma_kernel and gemm_bf16_persist_kernel (the kernels a scattering epilogue is
+// instantiated with; the others refuse one at compile time): row-major C, or the epilogue's own address (4 consecutive n stay contiguous:
+// n0 is a multiple of 4 and a patch run / heatmap plane holds a multiple of 4 floats)
+template <class Epi>
+__device__ __forceinline__ void epi_store(const Epi& epi, float* C, long ldc, int m, int n, float v) {
+    if constexpr (epi_scatters<Epi>::value) {
+        if (float* p = epi.dst(m, n)) *p = v;
+    } else {
+        C[(long)m * ldc + n] = v;
+    }
+}
+template <class Epi>
+__device__ __forceinline__ void epi_store4(const Epi& epi, float* C, long ldc, int m, int n0, const f32x4& v) {
+    if constexpr (epi_scatters<Epi>::value) {
+        if (float* p = epi.dst(m, n0)) *(f32x4*)p = v;
+    } else {
+        *(f32x4*)(C + (long)m * ldc + n0) = v;
+    }
+}
+
 // ----------------------------------------------------------------------------- kernel
 template <int BM_, int BN_, int BK_, int WM_, int WN_, int MINW_>
 struct GemmCfg {
@@ -472,7 +518,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = mbase + (r & 3) + 8 * (r >> 2);
-                if (m < M) C[(long)m * ldc + n] = epi.apply(acc[i][j][r], cc, m, n);
+                if (m < M) epi_store(epi, C, ldc, m, n, epi.apply(acc[i][j][r], cc, m, n));
             }
         }
     }
@@ -500,6 +546,7 @@ struct PipeCfg : GemmCfg<BM_, BN_, BK_, WM_, WN_, MINW_> {
 template <class Cfg, class ALoad, class Epi>
 __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_pipe_kernel(
     ALoad al, SegMat W, Epi epi, float* C, long ldc, int M, int N, int K, int tiles_m, int tiles_n) {
+    static_assert(!epi_scatters<Epi>::value, "row-major output only");
     constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, LDK = Cfg::LDK, NS = Cfg::NS;
     constexpr int TM = Cfg::TM, TN = Cfg::TN, A_V4 = Cfg::A_V4, B_V4 = Cfg::B_V4, RPP = Cfg::ROWS_PER_PASS;
     constexpr int G = BK / 8;
@@ -655,6 +702,7 @@ static hipError_t gemm_f32_pipe_launch(const ALoad& al, const SegMat& W, const E
 template <class Cfg, class ALoad, class Epi>
 __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_persist_kernel(
     ALoad al, SegMat W, Epi epi, float* C, long ldc, int M, int N, int K, int tiles_m, int tiles_n) {
+    static_assert(!epi_scatters<Epi>::value, "row-major output only");
     constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, LDK = Cfg::LDK, NS = Cfg::NS;
     constexpr int TM = Cfg::TM, TN = Cfg::TN, A_V4 = Cfg::A_V4, B_V4 = Cfg::B_V4, RPP = Cfg::ROWS_PER_PASS;
     constexpr int G = BK / 8, ELD = 36;
@@ -979,6 +1027,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_splitk_kerne
 template <class Epi>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ P, Epi epi, float* __restrict__ C, long ldc, int M, int N,
                                                             int splits) {
+    static_assert(!epi_scatters<Epi>::value, "row-major output only");
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)M * N) return;
     const int m = (int)(i / N), n = (int)(i - (long)m * N);

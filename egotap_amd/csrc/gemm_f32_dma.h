@@ -184,7 +184,7 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
                 const int m = mb + hf * 16 + s2 * 8;
                 if (FULL || m < M) {
                     const f32x4 o = epi.apply4(*(const f32x4*)(Es + (s2 * 8 + er) * ELD + ec), cc, rs[s2], m, n0);
-                    *(f32x4*)(C + (long)m * ldc + n0) = o;
+                    epi_store4(epi, C, ldc, m, n0, o);
                 }
             }
             if (Epi::HAS_RES) { rs[0] = rn[0]; rs[1] = rn[1]; }

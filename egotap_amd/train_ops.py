@@ -13,6 +13,7 @@ from . import lib as _lib
 
 LD_PLAIN, LD_PATCH, LD_TOKENS, LD_ROT, LD_STEREO, LD_STEREO_GATED = range(6)
 TE_NONE, TE_BIAS, TE_BIAS_RES, TE_BIAS_GELU_SAVE, TE_ACCUM, TE_GELU_GRAD = range(6)
+TE_SCATTER_PATCH, TE_SCATTER_ROT = 7, 8          # out = the heatmaps' gradient [B, 6J, S, S] (include/egotap.h, egotap_train_gemm_nt)
 
 
 def _p(t):

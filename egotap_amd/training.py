@@ -96,6 +96,11 @@ def _publish_grads(P, G, held=None):
 _train_ws = T.Scratch()
 
 
+def _input_grad(dhm, dtype):
+    """the heatmaps' gradient as autograd expects it: the input's dtype (forward ran on an fp32 copy), None when it was not asked for"""
+    return dhm if dhm is None or dhm.dtype == dtype else dhm.to(dtype)
+
+
 def release_scratch(net=None):
     """drop the grow-only scratch buffers of the training path (between benchmark legs; the next step allocates them again)"""
     _train_ws.buf = None
@@ -130,6 +135,7 @@ class LiftTrainOneCallFn(torch.autograd.Function):
         B = hm.shape[0]
         net._act_scratch(B, dev)
         lib = _lib.load()
+        in_dtype = hm.dtype
         hm = hm.detach().float().contiguous()
         sb, wb = C.c_size_t(), C.c_size_t()
         _lib.check(lib.egotap_lift_train_bytes(h, B, C.byref(sb), C.byref(wb)))
@@ -153,7 +159,7 @@ class LiftTrainOneCallFn(torch.autograd.Function):
         for k, b in net.named_buffers():
             if k.endswith("num_batches_tracked"):
                 b.add_(1)
-        ctx.egotap = dict(net=net, P=P, keys=keys, B=B, hm=hm, saved=saved, wb=wb.value, pool=pool)
+        ctx.egotap = dict(net=net, P=P, keys=keys, B=B, hm=hm, in_dtype=in_dtype, saved=saved, wb=wb.value, pool=pool)
         return pose
 
     @staticmethod
@@ -175,15 +181,21 @@ class LiftTrainOneCallFn(torch.autograd.Function):
             evp = (C.c_void_p * nb)(*[e.cuda_event for e in events])
         ws = _train_ws.get(S["wb"], dev)
         dpose = dpose.detach().float().contiguous()
-        _lib.check(lib.egotap_lift_backward(h, T._p(S["hm"]), T._p(dpose), B, T._p(S["saved"]), S["saved"].numel(), T._p(ws), ws.numel(),
-                                            evp, len(events), T._s()))
+        if ctx.needs_input_grad[1]:        # the heatmaps' gradient too: every element written by the library, nothing to clear
+            dhm = torch.empty(S["hm"].shape, dtype=torch.float32, device=dev)
+            _lib.check(lib.egotap_lift_backward_dhm(h, T._p(S["hm"]), T._p(dpose), B, T._p(S["saved"]), S["saved"].numel(), T._p(ws), ws.numel(),
+                                                    evp, len(events), T._s(), T._p(dhm)))
+        else:
+            dhm = None
+            _lib.check(lib.egotap_lift_backward(h, T._p(S["hm"]), T._p(dpose), B, T._p(S["saved"]), S["saved"].numel(), T._p(ws), ws.numel(),
+                                                evp, len(events), T._s()))
         for k, e in enumerate(events):
             red.bucket_ready(ga["bounds"][k], ga["bounds"][k + 1], after=e)
         red.finish()
         _publish_grads(P, G, held)
         S["pool"]["busy"] = False
         ctx.egotap = None
-        return (None, None) + (None,) * len(keys)
+        return (None, _input_grad(dhm, S["in_dtype"])) + (None,) * len(keys)
 
 
 class LiftTrainFn(torch.autograd.Function):
@@ -208,8 +220,9 @@ class LiftTrainFn(torch.autograd.Function):
         lib = _lib.load()
         st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
         v = "pos_heatmap_encoder.vit."
+        in_dtype = hm.dtype
         hm = hm.detach().float().contiguous()
-        saved = {"hm": hm}
+        saved = {"hm": hm, "in_dtype": in_dtype}
         x = torch.empty((M, D), dtype=torch.float32, device=dev)
         _lib.check(lib.egotap_train_patch_fwd(h, T._p(hm), B, T._p(P[v + "embeddings.patch_embeddings.projection.weight"]),
                                               T._p(P[v + "embeddings.patch_embeddings.projection.bias"]), T._p(P[v + "embeddings.mask_token"]),
@@ -280,6 +293,7 @@ class LiftTrainFn(torch.autograd.Function):
         red = net._reducer()
         red.begin(ga["flat"])
         dpose = dpose.detach().float().contiguous()
+        dhm = torch.empty(S["hm"].shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         v = "pos_heatmap_encoder.vit."
         posz, rotz, hs1 = S["pos_acts"][-1]["y"], S["rot_acts"][-1]["y"], S["hs1"]
         # pose head + propagation units
@@ -302,7 +316,8 @@ class LiftTrainFn(torch.autograd.Function):
         del ws
 
         def encoder_bwd(acts, dy):
-            """returns the gradient w.r.t. the gathered fc1 input rows (None for the rotation encoder: its input is data)"""
+            """returns the gradient w.r.t. the gathered fc1 input rows (None for the rotation encoder: its input is the heatmaps, whose
+            rotation channels it writes into dhm when that is asked for)"""
             for j in (2, 1, 0):
                 a = acts[j]
                 f = a["name"]
@@ -310,6 +325,8 @@ class LiftTrainFn(torch.autograd.Function):
                 T.gemm_tn(h, dz, a["a_in"], G[f + ".fc.weight"], BT, a["N"], a["K"], loader=a["loader"])
                 T.colsum(dz, G[f + ".fc.bias"], BT, a["N"])
                 if j == 0 and a["loader"] == T.LD_ROT:
+                    if dhm is not None:
+                        T.gemm_nt(h, dz, T.transpose(P[f + ".fc.weight"]), None, BT, a["K"], a["N"], epi=T.TE_SCATTER_ROT, out=dhm)
                     return None
                 wt = T.transpose(P[f + ".fc.weight"])                     # [K, N]
                 dy = T.gemm_nt(h, dz, wt, None, BT, a["K"], a["N"], epi=T.TE_NONE)
@@ -360,10 +377,13 @@ class LiftTrainFn(torch.autograd.Function):
         nb = len(ga["bounds"])
         red.bucket_ready(ga["bounds"][nb - 3], ga["bounds"][nb - 2])
         red.bucket_ready(ga["bounds"][nb - 2], ga["bounds"][nb - 1])
+        if dhm is not None:               # the heatmaps' position channels, under the last bucket's all-reduce
+            pw = P[v + "embeddings.patch_embeddings.projection.weight"].detach().reshape(D, 256)
+            T.gemm_nt(h, dx, T.transpose(pw), None, M, 256, D, epi=T.TE_SCATTER_PATCH, out=dhm)
         red.finish()
         _publish_grads(P, G, held)
         ctx.egotap = None
-        return (None, None) + (None,) * len(keys)
+        return (None, _input_grad(dhm, S["in_dtype"])) + (None,) * len(keys)
 
 
 class LiftTrainBf16Fn(torch.autograd.Function):
@@ -414,10 +434,11 @@ class LiftTrainBf16Fn(torch.autograd.Function):
         lib = _lib.load()
         st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
         v = "pos_heatmap_encoder.vit."
+        in_dtype = hm.dtype
         hm = hm.detach().float().contiguous()
         W = LiftTrainBf16Fn._prep(net, P, dev)
         hm_b = S.from_f32(hm)                                       # bf16 copy of the input heatmaps: the rotation encoder's fc1 operand
-        saved = {"hm": hm, "hm_b": hm_b}
+        saved = {"hm": hm, "hm_b": hm_b, "in_dtype": in_dtype}
         x = torch.empty((M, D), dtype=torch.float32, device=dev)
         # patch embedding on the bf16-storage GEMM: bf16 heatmaps, a per-step bf16 copy of the projection weight (as the one-call ABI does)
         pw = P[v + "embeddings.patch_embeddings.projection.weight"]
@@ -493,6 +514,7 @@ class LiftTrainBf16Fn(torch.autograd.Function):
         red = net._reducer()
         red.begin(ga["flat"])
         dpose = dpose.detach().float().contiguous()
+        dhm = torch.empty(Sv["hm"].shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         v = "pos_heatmap_encoder.vit."
         posz, rotz, hs1 = Sv["pos_acts"][-1]["y"], Sv["rot_acts"][-1]["y"], Sv["hs1"]
         # net._stage_trace = {} (tests): every intermediate of this backward is kept under a name, together with the forward's saved
@@ -531,7 +553,14 @@ class LiftTrainBf16Fn(torch.autograd.Function):
                 else:
                     dzb = S.from_f32(dz)
                     S.fc1_wgrad(h, which, dzb, src, G[f + ".fc.weight"], B)
-                    return S.fc1_dgrad_tokens(h, dzb, wt, B, seq, D) if wt is not None else None
+                    if wt is not None:
+                        return S.fc1_dgrad_tokens(h, dzb, wt, B, seq, D)
+                    if dhm is not None:       # the heatmaps' rotation channels: fc1.weight^T in bf16, built for this product only
+                        wr = P[f + ".fc.weight"]
+                        wrt = torch.empty((a["K"], a["N"]), dtype=torch.bfloat16, device=dev)
+                        S.prep_weight(wr, torch.empty(wr.shape, dtype=torch.bfloat16, device=dev), wrt)
+                        S.fc1_dgrad_rot(h, dzb, wrt, dhm, B)
+                    return None
 
         encoder_bwd(Sv["rot_acts"], drotz, 1, Sv["hm_b"], None)
         dtok = encoder_bwd(Sv["pos_acts"], dposz, 0, Sv["tokens"], W["fc1p_t"])       # bf16 [M, D], token order
@@ -581,7 +610,7 @@ class LiftTrainBf16Fn(torch.autograd.Function):
             del dqkv
             prev_bias = G[f"{v}encoder.layer.{i - 1}.output.dense.bias"] if i > 0 else None
             dx, dxb = S.layernorm_bwd(L["x"], dy1, P[l + "layernorm_before.weight"], L["m1"], L["r1"], G[l + "layernorm_before.weight"],
-                                      G[l + "layernorm_before.bias"], dres=dxm, dcolsum=prev_bias, want_bf16=i > 0)
+                                      G[l + "layernorm_before.bias"], dres=dxm, dcolsum=prev_bias, want_bf16=i > 0 or dhm is not None)
             if tr is not None:
                 t_.update(dx_out=dx, dxb_out=dxb)
             del dy1, dxm
@@ -594,10 +623,15 @@ class LiftTrainBf16Fn(torch.autograd.Function):
         nb = len(ga["bounds"])
         red.bucket_ready(ga["bounds"][nb - 3], ga["bounds"][nb - 2])
         red.bucket_ready(ga["bounds"][nb - 2], ga["bounds"][nb - 1])
+        if dhm is not None:               # the heatmaps' position channels (bf16 dx of layer 0, bf16 projection.weight^T)
+            pw = P[v + "embeddings.patch_embeddings.projection.weight"].detach().reshape(D, 256)
+            pwt = torch.empty((256, D), dtype=torch.bfloat16, device=dev)
+            S.prep_weight(pw, torch.empty((D, 256), dtype=torch.bfloat16, device=dev), pwt)
+            S.patch_dgrad(h, dxb, pwt, dhm, B)
         red.finish()
         _publish_grads(P, G, held)
         ctx.egotap = None
-        return (None, None) + (None,) * len(keys)
+        return (None, _input_grad(dhm, Sv["in_dtype"])) + (None,) * len(keys)
 
 
 class PoseLossFn(torch.autograd.Function):

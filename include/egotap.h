@@ -209,7 +209,11 @@ int egotap_synth_heatmaps(const float* pts2d_left, const float* pts2d_right, con
  * utils/loss.py:54-85, network.py:72-78 AdamW).  All buffers are caller-owned device memory; reductions have a fixed order.
  * loader: 0 plain, 1 ViT patch gather, 2 per-heatmap token regroup, 3 stereo cos/sin gather, 4 stereo joint features,
  *         5 stereo joint features x sigmoid gate (aux).  epi: 0 none, 1 bias, 2 bias + residual r, 3 bias + GELU (stores
- *         the pre-activation to z), 4 accumulate onto r, 5 multiply by GELU'(r). */
+ *         the pre-activation to z), 4 accumulate onto r, 5 multiply by GELU'(r), 7 / 8 scatter into the heatmaps' gradient:
+ *         y = dhm f32 [B, 6J, S, S] (16-byte aligned), loader 0, no bias.  7: position channels [0, 2J) from the patch embedding's
+ *         output gradient (x [B*seq, D], w = projection.weight^T [256, D]; M = B*seq, N = 256, K = D; dummy grid cells are no pixel);
+ *         8: rotation channels [2J, 6J) from the rotation encoder's fc1 pre-activation gradient (x [B*T, 2048], w = fc1.weight^T
+ *         [2 S^2, 2048]; M = B*T, N = 2 S^2, K = 2048).  Each writes every element of its channels exactly once. */
 int egotap_train_gemm_nt(egotap_handle h, int loader, const float* x, int64_t lda, const float* aux, const float* w, const float* b,
                          float* y, int M, int N, int K, int epi, const float* r, float* z, int Bsz, void* stream);
 int egotap_train_gemm_tn(egotap_handle h, int loader, const float* dy, int64_t ldy, const float* x, const float* aux, float* dw, int M,
@@ -283,6 +287,13 @@ int egotap_lift_forward_train(egotap_handle h, const float* hm, int B, float* po
                               size_t ws_bytes, void* stream);
 int egotap_lift_backward(egotap_handle h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes, void* ws,
                          size_t ws_bytes, void* const* bucket_events, int n_events, void* stream);
+/* egotap_lift_backward that also writes the gradient w.r.t. the input heatmaps (autograd reaching the head's input, as the reference's
+ * plain-PyTorch head does: the estimators can then be trained through the pose loss).  dhm device f32 [B, 6J, S, S], contiguous,
+ * 16-byte aligned, not overlapping hm; every element is written exactly once (no clearing needed), bit-reproducibly.  The rotation
+ * channels are computed inside the backward, the position channels after the last bucket event.  Same saved buffer and workspace
+ * (egotap_lift_train_bytes).  dhm == NULL: exactly egotap_lift_backward, launch for launch. */
+int egotap_lift_backward_dhm(egotap_handle h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes, void* ws,
+                             size_t ws_bytes, void* const* bucket_events, int n_events, void* stream, float* dhm);
 
 /* ---- heatmap-estimator training operators (fp32), called by the autograd glue (egotap_amd/hm_training.py) ----------------
  * One optimisation step of the stage-1 model (model/heatmap_shared_model.py:98-172): HeatMap_UnrealEgo_Shared in train mode
@@ -383,6 +394,11 @@ int egotap_bf16_patch_fwd(egotap_handle h, const void* hmb, const void* w, const
 int egotap_bf16_fc1_wgrad(egotap_handle h, int which, const void* dz, const void* src, float* dw, int B, const void* zeros, void* ws, size_t ws_bytes,
                           void* stream);
 int egotap_bf16_fc1_dgrad_tokens(egotap_handle h, const void* dz, const void* wt, void* dtok, int B, void* stream);
+/* the heatmaps' gradient in the bf16-storage step, fp32 into dhm [B, 6J, S, S] (16-byte aligned), each element written once:
+ *   fc1_dgrad_rot  rotation channels [2J, 6J): dz bf16 [B*T, 2048] x wt bf16 [2 S^2, 2048] (rotation fc1.weight^T)
+ *   patch_dgrad    position channels [0, 2J): dx bf16 [B*seq, D] (patch-embedding output gradient) x wt bf16 [256, D] (projection.weight^T) */
+int egotap_bf16_fc1_dgrad_rot(egotap_handle h, const void* dz, const void* wt, float* dhm, int B, void* stream);
+int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const void* wt, float* dhm, int B, void* stream);
 
 
 #ifdef __cplusplus

@@ -257,6 +257,35 @@ def gen_train():
     print("train_step: losses", float(loss_pose), float(loss_cos), "params without grad:", no_grad)
 
 
+DHM_STRIDE = 97         # sample of hm.grad every DHM_STRIDE elements (7 600 of the 737 280 at B = 2)
+
+
+def gen_train_dhm():
+    """gen_train's step (same weights, inputs, train-mode BatchNorm and loss) with the heatmaps requiring a gradient: the
+    reference's head is plain PyTorch, so autograd reaches its input.  Records hm.grad as a strided sample and its L2 norm per
+    (frame, channel) plane -- the fixture of the head's input gradient (egotap_lift_backward_dhm)."""
+    import model.net_architecture as na
+    import utils.loss as L
+
+    opt = make_opt("UnrealEgo")
+    net = na.EgoTAPAutoEncoder(opt, input_channel_scale=2)
+    load_synth(net)
+    net.train()
+    B = 2
+    hm = torch.from_numpy(synth_input("hm_train", (B, 90, 64, 64))).requires_grad_()
+    gt = torch.from_numpy(synth_input("gt_train", (B, 16, 3), -1.0, 1.0))
+    pose = net(hm)[0]
+    lam_m, lam_c = 0.1, -0.01
+    loss_pose = L.LossFuncMPJPE()(pose, gt) * lam_m
+    loss_cos = L.LossFuncCosSim(joint_preset="UnrealEgo", estimate_head=True)(pose, gt) * lam_c * lam_m
+    (loss_pose + loss_cos).backward()
+    g = hm.grad.detach()
+    out = {"pose": pose.detach().numpy(), "dhm_stride": np.array(DHM_STRIDE), "dhm_sample": g.reshape(-1)[::DHM_STRIDE].numpy().copy(),
+           "dhm_plane_norms": g.double().reshape(B, 90, -1).norm(dim=2).numpy()}
+    np.savez_compressed(os.path.join(GOLD, "train_dhm_ue_b2.npz"), **out)
+    print("train_dhm: |dhm|", float(g.double().norm()), "sample", out["dhm_sample"].size)
+
+
 def _wrapper_opt(tmp, is_train, use_gt_heatmap, preset="UnrealEgo"):
     """the shipped PoseEstimator flag set (scripts/train/PoseEstimator/unrealego.sh, scripts/test/unrealego.sh; egocap.sh for the
     EgoCap preset) without --use_amp (fp16 autocast needs a GPU) on CPU"""
@@ -850,7 +879,7 @@ def gen_synth():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,sched,synth,hmtrain,wrapper,wrapper_rgb")
+    ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,train_dhm,sched,synth,hmtrain,wrapper,wrapper_rgb")
     args = ap.parse_args()
     which = set(args.only.split(","))
     os.makedirs(GOLD, exist_ok=True)
@@ -871,6 +900,8 @@ def main():
         gen_procrustes()
     if "train" in which:
         gen_train()
+    if "train_dhm" in which:
+        gen_train_dhm()
     if "sched" in which:
         gen_sched()
     if "synth" in which:
