@@ -3337,56 +3337,55 @@ extern "C" int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const vo
 // ------------------------------------------------------------------------------------------------ one-call training step
 // egotap_lift_forward_train + egotap_lift_backward: the lifting head's training-mode forward (activations kept in `saved`) and its
 // whole backward as ONE call each (egotap_lift_forward(…, saved, …) / egotap_lift_backward; reference:
-// egotap_autoencoder_model.py:284-311 loss.backward()).  They compose the granular training operators above in the order
-// egotap_amd/training.py used to (the per-operator tests keep calling those), read the parameters bound with egotap_bind_param
-// and write the gradients into the buffers bound with egotap_bind_grad.  fp32 tensors; arithmetic of the large GEMMs follows
-// egotap_set_precision (f32 / bf16x3; bf16 here means bf16 operand copies, the bf16-STORAGE step is egotap_amd/training.py's
-// LiftTrainBf16Fn).  Everything is enqueued on the caller's stream; no allocation, no synchronisation.
+// egotap_autoencoder_model.py:284-311 loss.backward()).  They compose the granular training operators above in the order of
+// egotap_amd/training.py's operator-by-operator Functions (LiftTrainFn, LiftTrainBf16Fn; the tests hold both bit-identical to this),
+// read the parameters bound with egotap_bind_param and write the gradients into the buffers bound with egotap_bind_grad.  Two storage forms:
+//  - fp32 tensors; the large GEMMs' arithmetic follows egotap_set_precision (f32 / bf16x3, and bf16 operand copies when vit_dim != 1024);
+//  - bf16 storage (EGOTAP_PREC_BF16 with vit_dim 1024: BASELINE config 3, the wrapper's --use_amp): bf16 ViT activations and per-step bf16
+//    weight copies in `saved`; the residual stream, the statistics, the small layers and every gradient stay fp32.
+// They differ in the patch-embedding forward, the ViT layers and the encoders' fc1 (lift_forward_train16 / lift_backward16 against the fp32
+// bodies in the entries); the plan, the buffer checks, fc2 / fc3 and the BatchNorms, the propagation units, the pose head, the bucket events
+// and the patch-embedding gradients are shared.  Everything is enqueued on the caller's stream; no allocation, no synchronisation.
 #if EGOTAP_IN(0)
-struct LiftTrainPlan {      // byte offsets into `saved`
-    size_t X[9];            // X[i]: input of ViT layer i (X[0] = embeddings), X[L]: input of the final LayerNorm
-    struct Layer { size_t m1, r1, y1, qkv, ctx, lse, xm, m2, r2, y2, z, hid; } layer[8];
-    size_t mf, rf, tokens;
+#define EGO_RC(call) do { const int rc_ = (call); if (rc_ != EGOTAP_OK) return rc_; } while (0)
+
+struct LiftTrainPlan {      // byte offsets into `saved`; hmb, the w_* weight copies and b_qkv only in bf16 storage (0 otherwise)
+    size_t hmb, X[9];       // X[i]: input of ViT layer i (X[0] = embeddings), X[L]: input of the final LayerNorm
+    struct Layer { size_t m1, r1, y1, qkv, ctx, lse, xm, m2, r2, y2, z, hid, w_qkv, w_qkv_t, w_o, w_o_t, w_up, w_up_t, w_dn, w_dn_t, b_qkv; } layer[8];
+    size_t mf, rf, tokens, w_fc1p, w_fc1p_t, w_fc1r;
     struct Fc { size_t z, y, mean, rstd; } pos[3], rot[3];
     size_t pu, pu_hs1, pu_bytes, total;
 };
-struct LiftBwdPlan {        // byte offsets into the backward workspace
-    size_t R[3], A4, A3, WT, E[2], dposz, drotz, dhs1, delta, pu, pu_bytes, scr, scr_bytes, total;
+struct LiftBwdPlan {        // byte offsets into the backward workspace; R, A4, A3 in fp32 storage, F, Rb, A4b (= A3b), dzb, zero in bf16 storage
+    size_t R[3], A4, A3, F[2], Rb[2], A4b, A3b, dzb, zero, WT, E[2], dposz, drotz, dhs1, delta, pu, pu_bytes, scr, scr_bytes, total;
 };
 static const int FC_OUT[2] = {2048, 512};
-
-// the bf16-STORAGE step (EGOTAP_PREC_BF16 with vit_dim 1024: BASELINE config 3, the wrapper's --use_amp): bf16 activations and per-step
-// bf16 weight copies, everything else as above.  Byte offsets into `saved` / the workspace.
-struct LiftTrain16Plan {
-    size_t hmb, X[9];
-    struct Layer { size_t m1, r1, y1, qkv, ctx, lse, xm, m2, r2, y2, z, hid, w_qkv, w_qkv_t, w_o, w_o_t, w_up, w_up_t, w_dn, w_dn_t, b_qkv; } layer[8];
-    size_t mf, rf, tokens, w_fc1p, w_fc1p_t, w_fc1r;
-    LiftTrainPlan::Fc pos[3], rot[3];
-    size_t pu, pu_hs1, pu_bytes, total;
-};
-struct LiftBwd16Plan {
-    size_t F[2], Rb[2], A4b, A3b, E[2], dzb, WT, dposz, drotz, dhs1, delta, zero, pu, pu_bytes, scr, scr_bytes, total;
-};
 static bool lift_train_bf16s(const Handle* h) { return h->precision == EGOTAP_PREC_BF16 && h->D == 1024; }
 
-static int lift_train16_plan(Handle* h, int B, LiftTrain16Plan& t, LiftBwd16Plan& w) {
+static int lift_train_plan(Handle* h, int B, LiftTrainPlan& t, LiftBwdPlan& w) {
+    const bool bf = lift_train_bf16s(h);
     const size_t M = (size_t)B * h->seq, D = h->D, BT = (size_t)B * h->T, heads = h->cfg.vit_heads, L = h->cfg.vit_layers;
     const size_t K1 = (size_t)h->ppd * h->ppd * D, K1r = 2 * (size_t)h->cfg.hm_size * h->cfg.hm_size;
+    t = LiftTrainPlan();
+    w = LiftBwdPlan();
     size_t o = 0;
     auto bytes = [&](size_t n) { size_t r = o; o = al256(o + n); return r; };
     auto f32 = [&](size_t n) { return bytes(n * 4); };
     auto b16 = [&](size_t n) { return bytes(n * 2); };
-    t.hmb = b16((size_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size);
+    auto act = [&](size_t n) { return bytes(n * (bf ? 2 : 4)); };       // what the ViT's GEMMs read: bf16 in bf16 storage
+    if (bf) t.hmb = b16((size_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size);
     for (size_t i = 0; i <= L; ++i) t.X[i] = f32(M * D);
     for (size_t i = 0; i < L; ++i) {
         auto& l = t.layer[i];
-        l.m1 = f32(M); l.r1 = f32(M); l.y1 = b16(M * D); l.qkv = b16(M * 3 * D); l.ctx = b16(M * D); l.lse = f32((size_t)B * heads * h->seq);
-        l.xm = f32(M * D); l.m2 = f32(M); l.r2 = f32(M); l.y2 = b16(M * D); l.z = b16(M * 4 * D); l.hid = b16(M * 4 * D);
-        l.w_qkv = b16(3 * D * D); l.w_qkv_t = b16(3 * D * D); l.w_o = b16(D * D); l.w_o_t = b16(D * D);
-        l.w_up = b16(4 * D * D); l.w_up_t = b16(4 * D * D); l.w_dn = b16(4 * D * D); l.w_dn_t = b16(4 * D * D); l.b_qkv = f32(3 * D);
+        l.m1 = f32(M); l.r1 = f32(M); l.y1 = act(M * D); l.qkv = act(M * 3 * D); l.ctx = act(M * D); l.lse = f32((size_t)B * heads * h->seq);
+        l.xm = f32(M * D); l.m2 = f32(M); l.r2 = f32(M); l.y2 = act(M * D); l.z = act(M * 4 * D); l.hid = act(M * 4 * D);
+        if (bf) {
+            l.w_qkv = b16(3 * D * D); l.w_qkv_t = b16(3 * D * D); l.w_o = b16(D * D); l.w_o_t = b16(D * D);
+            l.w_up = b16(4 * D * D); l.w_up_t = b16(4 * D * D); l.w_dn = b16(4 * D * D); l.w_dn_t = b16(4 * D * D); l.b_qkv = f32(3 * D);
+        }
     }
-    t.mf = f32(M); t.rf = f32(M); t.tokens = b16(M * D);
-    t.w_fc1p = b16(2048 * K1); t.w_fc1p_t = b16(2048 * K1); t.w_fc1r = b16(2048 * K1r);
+    t.mf = f32(M); t.rf = f32(M); t.tokens = act(M * D);
+    if (bf) { t.w_fc1p = b16(2048 * K1); t.w_fc1p_t = b16(2048 * K1); t.w_fc1r = b16(2048 * K1r); }
     for (int e = 0; e < 2; ++e)
         for (int j = 0; j < 3; ++j) {
             const size_t n = j < 2 ? (size_t)FC_OUT[j] : (size_t)h->hid;
@@ -3394,87 +3393,46 @@ static int lift_train16_plan(Handle* h, int B, LiftTrain16Plan& t, LiftBwd16Plan
             f.z = f32(BT * n); f.y = f32(BT * n); f.mean = f32(n); f.rstd = f32(n);
         }
     size_t pub = 0, hs1 = 0;
-    int rc = egotap_train_pu_saved_bytes(h, B, &pub, &hs1);
-    if (rc != EGOTAP_OK) return rc;
+    EGO_RC(egotap_train_pu_saved_bytes(h, B, &pub, &hs1));
     t.pu = bytes(pub + 4); t.pu_hs1 = hs1; t.pu_bytes = pub;
     t.total = o;
 
     o = 0;
-    w.F[0] = f32(M * D); w.F[1] = f32(M * D); w.Rb[0] = b16(M * D); w.Rb[1] = b16(M * D);
-    w.A4b = b16(M * 4 * D); w.A3b = w.A4b;       // dz (MLP) is dead before dqkv (attention) is produced: one slot
-    w.E[0] = f32(BT * 2048); w.E[1] = f32(BT * 2048); w.dzb = b16(BT * 2048);
-    w.WT = f32((size_t)2048 * 512);
+    if (bf) {
+        w.F[0] = f32(M * D); w.F[1] = f32(M * D); w.Rb[0] = b16(M * D); w.Rb[1] = b16(M * D);
+        w.A4b = b16(M * 4 * D); w.A3b = w.A4b;       // dz (MLP) is dead before dqkv (attention) is produced: one slot
+        w.E[0] = f32(BT * 2048); w.E[1] = f32(BT * 2048); w.dzb = b16(BT * 2048);
+        w.WT = f32((size_t)2048 * 512);
+    } else {
+        for (int i = 0; i < 3; ++i) w.R[i] = f32(M * D);
+        w.A4 = f32(M * 4 * D); w.A3 = f32(M * 3 * D);
+        w.WT = f32(std::max((size_t)4 * D * D, K1 * 2048));
+        w.E[0] = f32(BT * 2048); w.E[1] = f32(BT * 2048);
+    }
     w.dposz = f32(BT * h->hid); w.drotz = f32(BT * h->hid); w.dhs1 = f32((size_t)h->J * B * h->H);
     w.delta = f32((size_t)B * heads * h->seq);
-    w.zero = bytes(4096);
+    if (bf) w.zero = bytes(4096);
     size_t pwb = 0;
-    rc = egotap_train_pu_bwd_ws_bytes(h, B, &pwb);
-    if (rc != EGOTAP_OK) return rc;
+    EGO_RC(egotap_train_pu_bwd_ws_bytes(h, B, &pwb));
     w.pu = bytes(pwb + 4); w.pu_bytes = pwb;
-    const size_t nb = (M + 63) / 64;
-    w.scr_bytes = std::max(std::max((size_t)4 * 4 * D * D * 8, (size_t)4 * 2048 * K1 * 2), (3 * nb + 3 + 3 * ((nb + 63) / 64)) * 4096 + 4096);
-    w.scr_bytes = std::max(w.scr_bytes, (size_t)64 << 20);
-    w.scr_bytes = std::max(w.scr_bytes, (size_t)B * (h->seq / 32) * 3 * D * 4 + ((size_t)64 << 20));      // per-block bias-gradient sums of the attention backward
-    w.scr = bytes(w.scr_bytes);
-    w.total = o;
-    return EGOTAP_OK;
-}
-
-static int lift_train_plan(Handle* h, int B, LiftTrainPlan& t, LiftBwdPlan& w) {
-    const size_t M = (size_t)B * h->seq, D = h->D, BT = (size_t)B * h->T, heads = h->cfg.vit_heads, L = h->cfg.vit_layers;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = al256(o + floats * 4); return r; };
-    for (size_t i = 0; i <= L; ++i) t.X[i] = take(M * D);
-    for (size_t i = 0; i < L; ++i) {
-        auto& l = t.layer[i];
-        l.m1 = take(M); l.r1 = take(M); l.y1 = take(M * D); l.qkv = take(M * 3 * D); l.ctx = take(M * D); l.lse = take((size_t)B * heads * h->seq);
-        l.xm = take(M * D); l.m2 = take(M); l.r2 = take(M); l.y2 = take(M * D); l.z = take(M * 4 * D); l.hid = take(M * 4 * D);
-    }
-    t.mf = take(M); t.rf = take(M); t.tokens = take(M * D);
-    for (int e = 0; e < 2; ++e)
-        for (int j = 0; j < 3; ++j) {
-            const size_t n = j < 2 ? (size_t)FC_OUT[j] : (size_t)h->hid;
-            LiftTrainPlan::Fc& f = e == 0 ? t.pos[j] : t.rot[j];
-            f.z = take(BT * n); f.y = take(BT * n); f.mean = take(n); f.rstd = take(n);
-        }
-    size_t pub = 0, hs1 = 0;
-    int rc = egotap_train_pu_saved_bytes(h, B, &pub, &hs1);
-    if (rc != EGOTAP_OK) return rc;
-    t.pu = take(pub / 4 + 1); t.pu_hs1 = hs1; t.pu_bytes = pub;
-    t.total = o;
-
-    o = 0;
-    const size_t K1 = (size_t)h->ppd * h->ppd * D, K1r = 2 * (size_t)h->cfg.hm_size * h->cfg.hm_size;
-    for (int i = 0; i < 3; ++i) w.R[i] = take(M * D);
-    w.A4 = take(M * 4 * D); w.A3 = take(M * 3 * D);
-    w.WT = take(std::max((size_t)4 * D * D, K1 * 2048));
-    w.E[0] = take(BT * 2048); w.E[1] = take(BT * 2048);
-    w.dposz = take(BT * h->hid); w.drotz = take(BT * h->hid); w.dhs1 = take((size_t)h->J * B * h->H);
-    w.delta = take((size_t)B * heads * h->seq);
-    size_t pwb = 0;
-    rc = egotap_train_pu_bwd_ws_bytes(h, B, &pwb);
-    if (rc != EGOTAP_OK) return rc;
-    w.pu = take(pwb / 4 + 1); w.pu_bytes = pwb;
     // split-M slabs of the weight-gradient GEMMs (8 slabs of the largest [N, K]) / column-sum partials / LayerNorm partials
-    w.scr_bytes = std::max((size_t)64 << 20, (size_t)4 * 2048 * std::max(K1, K1r) * 8);
-    w.scr = take(w.scr_bytes / 4);
+    if (bf) {
+        const size_t nb = (M + 63) / 64;
+        w.scr_bytes = std::max(std::max((size_t)4 * 4 * D * D * 8, (size_t)4 * 2048 * K1 * 2), (3 * nb + 3 + 3 * ((nb + 63) / 64)) * 4096 + 4096);
+        w.scr_bytes = std::max(w.scr_bytes, (size_t)64 << 20);
+        w.scr_bytes = std::max(w.scr_bytes, (size_t)B * (h->seq / 32) * 3 * D * 4 + ((size_t)64 << 20));      // per-block bias-gradient sums of the attention backward
+    } else {
+        w.scr_bytes = std::max((size_t)64 << 20, (size_t)4 * 2048 * std::max(K1, K1r) * 8);
+    }
+    w.scr = bytes(w.scr_bytes);
     w.total = o;
     return EGOTAP_OK;
 }
 
 extern "C" int egotap_lift_train_bytes(egotap_handle h, int B, size_t* saved_bytes, size_t* ws_bytes) {
     EGO_CHECK(h && saved_bytes && ws_bytes && B > 0, "egotap_lift_train_bytes: bad argument");
-    if (lift_train_bf16s(h)) {
-        LiftTrain16Plan t; LiftBwd16Plan w;
-        const int rc = lift_train16_plan(h, B, t, w);
-        if (rc != EGOTAP_OK) return rc;
-        *saved_bytes = t.total;
-        *ws_bytes = w.total;
-        return EGOTAP_OK;
-    }
     LiftTrainPlan t; LiftBwdPlan w;
-    const int rc = lift_train_plan(h, B, t, w);
-    if (rc != EGOTAP_OK) return rc;
+    EGO_RC(lift_train_plan(h, B, t, w));
     *saved_bytes = t.total;
     *ws_bytes = w.total;
     return EGOTAP_OK;
@@ -3493,21 +3451,61 @@ extern "C" int egotap_bind_grad(egotap_handle h, const char* key, void* dev_ptr,
     return EGOTAP_OK;
 }
 
-#define EGO_RC(call) do { const int rc_ = (call); if (rc_ != EGOTAP_OK) return rc_; } while (0)
+// one call's plans and buffers: S / Hb address the fp32 / bf16 slots of `saved`, W / Wh those of the workspace
+struct LiftStep {
+    LiftTrainPlan t;
+    LiftBwdPlan w;
+    char *sb, *wb;
+    float* S(size_t off) const { return (float*)(sb + off); }
+    void* Hb(size_t off) const { return sb + off; }
+    float* W(size_t off) const { return (float*)(wb + off); }
+    void* Wh(size_t off) const { return wb + off; }
+    void* scr() const { return wb + w.scr; }
+};
+static float* G(const float* q) { return (float*)q; }      // a bound gradient (h->lg holds them as const pointers)
 
-static int lift_forward_train16(Handle* h, const float* hm, int B, float* pose, void* saved, size_t saved_bytes, void* ws, size_t ws_bytes,
-                                void* stream) {
-    LiftTrain16Plan t; LiftBwd16Plan w;
-    EGO_RC(lift_train16_plan(h, B, t, w));
-    EGO_CHECK(saved_bytes >= t.total, "egotap_lift_forward_train: saved buffer too small (%zu < %zu)", saved_bytes, t.total);
-    EGO_CHECK(ws_bytes >= w.total, "egotap_lift_forward_train: workspace too small (%zu < %zu)", ws_bytes, w.total);
+// plans the step for B and checks the caller's buffers against the plan (fn: the entry's name, for its messages)
+static int lift_step(const char* fn, Handle* h, int B, const void* saved, size_t saved_bytes, void* ws, size_t ws_bytes, LiftStep& c) {
+    EGO_RC(lift_train_plan(h, B, c.t, c.w));
+    EGO_CHECK(saved_bytes >= c.t.total, "%s: saved buffer too small (%zu < %zu)", fn, saved_bytes, c.t.total);
+    EGO_CHECK(ws_bytes >= c.w.total, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, c.w.total);
+    c.sb = (char*)saved;
+    c.wb = (char*)ws;
+    return EGOTAP_OK;
+}
+
+// the forward after the final LayerNorm, both storage forms: the two FC encoders, the propagation units and the pose head.  Only fc1 differs:
+// the bf16-storage kernel on the bf16 tokens / heatmaps and the step's bf16 weight copy, or the fp32 GEMM gathering its rows itself
+static int lift_heads_fwd(Handle* h, const LiftStep& c, const float* hm, int B, float* pose, void* stream) {
     const LiftParams& p = h->lp;
-    char* sb = (char*)saved;
-    auto S = [&](size_t off) { return (float*)(sb + off); };
-    auto Hb = [&](size_t off) { return (void*)(sb + off); };
-    void* scr = (char*)ws + w.scr;
+    const LiftTrainPlan& t = c.t;
+    const int BT = B * h->T;
+    for (int e = 0; e < 2; ++e) {
+        const LiftTrainPlan::Fc* f = e == 0 ? t.pos : t.rot;
+        for (int j = 0; j < 3; ++j) {
+            const int n = j < 2 ? FC_OUT[j] : h->hid;
+            const LiftParams::Fc& fc = e == 0 ? p.pos_fc[j] : p.rot_fc[j];
+            if (j > 0)
+                EGO_RC(egotap_train_gemm_nt(h, 0, c.S(f[j - 1].y), 0, nullptr, fc.w, fc.b, c.S(f[j].z), BT, n, FC_OUT[j - 1], 1, nullptr, nullptr, 0, stream));
+            else if (lift_train_bf16s(h))
+                EGO_RC(egotap_bf16_fc1_fwd(h, e, c.Hb(e == 0 ? t.tokens : t.hmb), c.Hb(e == 0 ? t.w_fc1p : t.w_fc1r), fc.b, c.S(f[0].z), B, stream));
+            else            // loader 2: the tokens' fc1 rows, 3: the heatmaps' rotation channels
+                EGO_RC(egotap_train_gemm_nt(h, e == 0 ? 2 : 3, e == 0 ? c.S(t.tokens) : hm, 0, nullptr, fc.w, fc.b, c.S(f[0].z), BT, n,
+                                            e == 0 ? h->ppd * h->ppd * h->D : 2 * h->cfg.hm_size * h->cfg.hm_size, 1, nullptr, nullptr, 0, stream));
+            // train-mode BatchNorm1d: batch statistics, running statistics updated in the bound buffers (momentum 0.1, unbiased variance)
+            EGO_RC(egotap_train_bn_lrelu_fwd(c.S(f[j].z), c.S(f[j].y), fc.g, fc.beta, c.S(f[j].mean), c.S(f[j].rstd), (float*)fc.mean, (float*)fc.var,
+                                             BT, n, 1e-5f, 0.1f, c.scr(), c.w.scr_bytes, stream));
+        }
+    }
+    EGO_RC(egotap_train_pu_fwd(h, c.S(t.pos[2].y), c.S(t.rot[2].y), B, c.sb + t.pu, t.pu_bytes, stream));
+    return egotap_train_pose_head_fwd(h, c.S(t.pos[2].y), c.S(t.pu + t.pu_hs1), B, pose, stream);
+}
+
+static int lift_forward_train16(Handle* h, const LiftStep& c, const float* hm, int B, float* pose, void* stream) {
+    const LiftParams& p = h->lp;
+    const LiftTrainPlan& t = c.t;
     hipStream_t s = (hipStream_t)stream;
-    const int M = B * h->seq, D = h->D, BT = B * h->T, heads = h->cfg.vit_heads, L = h->cfg.vit_layers;
+    const int M = B * h->seq, D = h->D, heads = h->cfg.vit_heads, L = h->cfg.vit_layers;
     const int K1 = h->ppd * h->ppd * D, K1r = 2 * h->cfg.hm_size * h->cfg.hm_size;
     // per-step bf16 copies of the GEMM weights (and transposed copies for the input-gradient GEMMs), kept with the activations
     for (int i = 0; i < L; ++i) {
@@ -3515,168 +3513,37 @@ static int lift_forward_train16(Handle* h, const float* hm, int B, float* pose, 
         const auto& l = t.layer[i];
         const float* qkvw[3] = {P_.q_w, P_.k_w, P_.v_w};
         for (int q = 0; q < 3; ++q)
-            EGO_RC(egotap_bf16_prep_weight(qkvw[q], (__bf16*)Hb(l.w_qkv) + (size_t)q * D * D, (__bf16*)Hb(l.w_qkv_t) + (size_t)q * D, D, D, 3 * D, stream));
-        EGO_RC(egotap_bf16_prep_weight(P_.o_w, Hb(l.w_o), Hb(l.w_o_t), D, D, D, stream));
-        EGO_RC(egotap_bf16_prep_weight(P_.up_w, Hb(l.w_up), Hb(l.w_up_t), 4 * D, D, 4 * D, stream));
-        EGO_RC(egotap_bf16_prep_weight(P_.dn_w, Hb(l.w_dn), Hb(l.w_dn_t), D, 4 * D, D, stream));
-        hipLaunchKernelGGL(concat3_kernel, dim3((D + 255) / 256), dim3(256), 0, s, P_.q_b, P_.k_b, P_.v_b, S(l.b_qkv), D);
+            EGO_RC(egotap_bf16_prep_weight(qkvw[q], (__bf16*)c.Hb(l.w_qkv) + (size_t)q * D * D, (__bf16*)c.Hb(l.w_qkv_t) + (size_t)q * D, D, D, 3 * D, stream));
+        EGO_RC(egotap_bf16_prep_weight(P_.o_w, c.Hb(l.w_o), c.Hb(l.w_o_t), D, D, D, stream));
+        EGO_RC(egotap_bf16_prep_weight(P_.up_w, c.Hb(l.w_up), c.Hb(l.w_up_t), 4 * D, D, 4 * D, stream));
+        EGO_RC(egotap_bf16_prep_weight(P_.dn_w, c.Hb(l.w_dn), c.Hb(l.w_dn_t), D, 4 * D, D, stream));
+        hipLaunchKernelGGL(concat3_kernel, dim3((D + 255) / 256), dim3(256), 0, s, P_.q_b, P_.k_b, P_.v_b, c.S(l.b_qkv), D);
         EGO_HIP(hipGetLastError());
     }
-    EGO_RC(egotap_bf16_prep_weight(p.pos_fc[0].w, Hb(t.w_fc1p), Hb(t.w_fc1p_t), 2048, K1, 2048, stream));
-    EGO_RC(egotap_bf16_prep_weight(p.rot_fc[0].w, Hb(t.w_fc1r), nullptr, 2048, K1r, 2048, stream));
-    EGO_RC(egotap_bf16_from_f32(hm, Hb(t.hmb), (int64_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size, stream));
+    EGO_RC(egotap_bf16_prep_weight(p.pos_fc[0].w, c.Hb(t.w_fc1p), c.Hb(t.w_fc1p_t), 2048, K1, 2048, stream));
+    EGO_RC(egotap_bf16_prep_weight(p.rot_fc[0].w, c.Hb(t.w_fc1r), nullptr, 2048, K1r, 2048, stream));
+    EGO_RC(egotap_bf16_from_f32(hm, c.Hb(t.hmb), (int64_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size, stream));
     {   // [r3] patch embedding on the bf16-storage GEMM (bf16 heatmaps by LDS DMA); its bf16 weight copy (512 KB) and a page of zeros live in
         // the step's scratch for the duration of the launch (the weight gradient still reads the fp32 heatmaps: egotap_lift_backward)
-        char* pscr = (char*)ws + w.scr;
+        char* pscr = (char*)c.scr();
         EGO_HIP(zero_fill(pscr, 256, s));
         EGO_RC(egotap_bf16_prep_weight(p.patch_w, pscr + 256, nullptr, D, 256, D, stream));
-        EGO_RC(egotap_bf16_patch_fwd(h, Hb(t.hmb), pscr + 256, p.patch_b, p.mask_tok, p.pos_emb, pscr, S(t.X[0]), B, stream));
+        EGO_RC(egotap_bf16_patch_fwd(h, c.Hb(t.hmb), pscr + 256, p.patch_b, p.mask_tok, p.pos_emb, pscr, c.S(t.X[0]), B, stream));
     }
     for (int i = 0; i < L; ++i) {
         const auto& P_ = p.layer[i];
         const auto& l = t.layer[i];
-        float* x = S(t.X[i]);
-        EGO_RC(egotap_bf16_layernorm_fwd(x, Hb(l.y1), P_.ln1_g, P_.ln1_b, S(l.m1), S(l.r1), M, 1e-12f, stream));
-        EGO_RC(egotap_bf16_gemm_nt(Hb(l.y1), D, Hb(l.w_qkv), S(l.b_qkv), M, 3 * D, D, 0, nullptr, Hb(l.qkv), nullptr, 3 * D, stream));
-        EGO_RC(egotap_bf16_attention_fwd(Hb(l.qkv), Hb(l.ctx), S(l.lse), B, h->seq, heads, stream));
-        EGO_RC(egotap_bf16_gemm_nt(Hb(l.ctx), D, Hb(l.w_o), P_.o_b, M, D, D, 1, x, S(l.xm), nullptr, D, stream));
-        EGO_RC(egotap_bf16_layernorm_fwd(S(l.xm), Hb(l.y2), P_.ln2_g, P_.ln2_b, S(l.m2), S(l.r2), M, 1e-12f, stream));
-        EGO_RC(egotap_bf16_gemm_nt(Hb(l.y2), D, Hb(l.w_up), P_.up_b, M, 4 * D, D, 2, nullptr, Hb(l.z), Hb(l.hid), 4 * D, stream));
-        EGO_RC(egotap_bf16_gemm_nt(Hb(l.hid), 4 * D, Hb(l.w_dn), P_.dn_b, M, D, 4 * D, 1, S(l.xm), S(t.X[i + 1]), nullptr, D, stream));
+        float* x = c.S(t.X[i]);
+        EGO_RC(egotap_bf16_layernorm_fwd(x, c.Hb(l.y1), P_.ln1_g, P_.ln1_b, c.S(l.m1), c.S(l.r1), M, 1e-12f, stream));
+        EGO_RC(egotap_bf16_gemm_nt(c.Hb(l.y1), D, c.Hb(l.w_qkv), c.S(l.b_qkv), M, 3 * D, D, 0, nullptr, c.Hb(l.qkv), nullptr, 3 * D, stream));
+        EGO_RC(egotap_bf16_attention_fwd(c.Hb(l.qkv), c.Hb(l.ctx), c.S(l.lse), B, h->seq, heads, stream));
+        EGO_RC(egotap_bf16_gemm_nt(c.Hb(l.ctx), D, c.Hb(l.w_o), P_.o_b, M, D, D, 1, x, c.S(l.xm), nullptr, D, stream));
+        EGO_RC(egotap_bf16_layernorm_fwd(c.S(l.xm), c.Hb(l.y2), P_.ln2_g, P_.ln2_b, c.S(l.m2), c.S(l.r2), M, 1e-12f, stream));
+        EGO_RC(egotap_bf16_gemm_nt(c.Hb(l.y2), D, c.Hb(l.w_up), P_.up_b, M, 4 * D, D, 2, nullptr, c.Hb(l.z), c.Hb(l.hid), 4 * D, stream));
+        EGO_RC(egotap_bf16_gemm_nt(c.Hb(l.hid), 4 * D, c.Hb(l.w_dn), P_.dn_b, M, D, 4 * D, 1, c.S(l.xm), c.S(t.X[i + 1]), nullptr, D, stream));
     }
-    EGO_RC(egotap_bf16_layernorm_fwd(S(t.X[L]), Hb(t.tokens), p.lnf_g, p.lnf_b, S(t.mf), S(t.rf), M, 1e-12f, stream));
-    for (int e = 0; e < 2; ++e) {
-        const float* a_in = nullptr;
-        int K = 0;
-        for (int j = 0; j < 3; ++j) {
-            const int n = j < 2 ? FC_OUT[j] : h->hid;
-            const LiftParams::Fc& fc = e == 0 ? p.pos_fc[j] : p.rot_fc[j];
-            const LiftTrainPlan::Fc& f = e == 0 ? t.pos[j] : t.rot[j];
-            if (j == 0) EGO_RC(egotap_bf16_fc1_fwd(h, e, e == 0 ? Hb(t.tokens) : Hb(t.hmb), e == 0 ? Hb(t.w_fc1p) : Hb(t.w_fc1r), fc.b, S(f.z), B, stream));
-            else EGO_RC(egotap_train_gemm_nt(h, 0, a_in, 0, nullptr, fc.w, fc.b, S(f.z), BT, n, K, 1, nullptr, nullptr, 0, stream));
-            EGO_RC(egotap_train_bn_lrelu_fwd(S(f.z), S(f.y), fc.g, fc.beta, S(f.mean), S(f.rstd), (float*)fc.mean, (float*)fc.var, BT, n, 1e-5f,
-                                             0.1f, scr, w.scr_bytes, stream));
-            a_in = S(f.y); K = n;
-        }
-    }
-    EGO_RC(egotap_train_pu_fwd(h, S(t.pos[2].y), S(t.rot[2].y), B, sb + t.pu, t.pu_bytes, stream));
-    EGO_RC(egotap_train_pose_head_fwd(h, S(t.pos[2].y), (const float*)(sb + t.pu + t.pu_hs1), B, pose, stream));
-    return EGOTAP_OK;
-}
-
-static int lift_backward16(const char* fn, Handle* h, const float* hm, const float* dpose, int B, const void* saved, size_t saved_bytes, void* ws,
-                           size_t ws_bytes, void* const* bucket_events, int n_events, void* stream, float* dhm) {
-    LiftTrain16Plan t; LiftBwd16Plan w;
-    EGO_RC(lift_train16_plan(h, B, t, w));
-    EGO_CHECK(saved_bytes >= t.total, "%s: saved buffer too small (%zu < %zu)", fn, saved_bytes, t.total);
-    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
-    const size_t K1r = 2 * (size_t)h->cfg.hm_size * h->cfg.hm_size;
-    // dhm: the bf16 copies of rotation fc1.weight (+ its transpose) and of projection.weight (+ transpose) live in the scratch while it is free
-    EGO_CHECK(!dhm || w.scr_bytes >= 2 * 2048 * K1r * 2, "%s: scratch too small for the transposed rotation fc1 weight", fn);
-    const int L = h->cfg.vit_layers;
-    const LiftParams& p = h->lp;
-    const LiftParams& g = h->lg;
-    auto G = [](const float* q) { return (float*)q; };
-    const char* sb = (const char*)saved;
-    auto S = [&](size_t off) { return (const float*)(sb + off); };
-    auto Hb = [&](size_t off) { return (const void*)(sb + off); };
-    char* wb = (char*)ws;
-    auto W = [&](size_t off) { return (float*)(wb + off); };
-    auto Wh = [&](size_t off) { return (void*)(wb + off); };
-    void* scr = wb + w.scr;
-    const size_t scrb = w.scr_bytes;
-    hipStream_t s = (hipStream_t)stream;
-    const int M = B * h->seq, D = h->D, BT = B * h->T, heads = h->cfg.vit_heads;
-    const void* ZERO = wb + w.zero;
-    EGO_HIP(zero_fill(wb + w.zero, 4096, s));
-    int bucket = 0;
-    auto bucket_done = [&]() -> int {
-        if (n_events) EGO_HIP(hipEventRecord((hipEvent_t)bucket_events[bucket], s));
-        ++bucket;
-        return EGOTAP_OK;
-    };
-    const float *posz = S(t.pos[2].y), *rotz = S(t.rot[2].y), *hs1 = (const float*)(sb + t.pu + t.pu_hs1);
-    EGO_RC(egotap_train_pose_head_bwd(h, posz, hs1, dpose, B, W(w.dposz), W(w.dhs1), G(g.pose_w), G(g.pose_b), G(g.glob_w), G(g.glob_b), 0, stream));
-    float* pug[14] = {G(g.x2f0_w), G(g.x2f0_b), G(g.x2h0_w), G(g.x2h0_b), G(g.b2h0_w), G(g.b2h0_b), G(g.h2h0_w), G(g.h2h0_b),
-                      G(g.x2f1_w), G(g.x2f1_b), G(g.x2h1_w), G(g.x2h1_b), G(g.h2h1_w), G(g.h2h1_b)};
-    EGO_RC(egotap_train_pu_bwd(h, posz, rotz, B, sb + t.pu, W(w.dhs1), W(w.dposz), W(w.drotz), pug, 0, wb + w.pu, w.pu_bytes, stream));
-    // FC encoders: fc3, fc2 in fp32 (small), fc1 on the bf16 kernels; the position encoder returns the token gradient (bf16, token order)
-    auto encoder_bwd = [&](int e, const float* dy, void* dtok) -> int {
-        for (int j = 2; j >= 0; --j) {
-            const int n = j < 2 ? FC_OUT[j] : h->hid;
-            const LiftParams::Fc& fc = e == 0 ? p.pos_fc[j] : p.rot_fc[j];
-            const LiftParams::Fc& gc = e == 0 ? g.pos_fc[j] : g.rot_fc[j];
-            const LiftTrainPlan::Fc& f = e == 0 ? t.pos[j] : t.rot[j];
-            float* dz = W(w.E[0]);
-            EGO_RC(egotap_train_bn_lrelu_bwd(S(f.z), S(f.y), dy, fc.g, S(f.mean), S(f.rstd), dz, G(gc.g), G(gc.beta), BT, n, 0, scr, scrb, stream));
-            EGO_RC(egotap_train_colsum(dz, 0, G(gc.b), BT, n, 0, scr, scrb, stream));
-            if (j > 0) {
-                const int K = FC_OUT[j - 1];
-                const float* a_in = S((e == 0 ? t.pos[j - 1] : t.rot[j - 1]).y);
-                EGO_RC(egotap_train_gemm_tn(h, 0, dz, 0, a_in, nullptr, G(gc.w), BT, n, K, 0, 0, scr, scrb, stream));
-                EGO_RC(egotap_train_transpose(fc.w, W(w.WT), n, K, 0, stream));
-                EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, W(w.WT), nullptr, W(w.E[1]), BT, K, n, 0, nullptr, nullptr, 0, stream));
-                dy = W(w.E[1]);
-            } else {
-                EGO_RC(egotap_bf16_from_f32(dz, Wh(w.dzb), (int64_t)BT * 2048, stream));
-                EGO_RC(egotap_bf16_fc1_wgrad(h, e, Wh(w.dzb), e == 0 ? Hb(t.tokens) : Hb(t.hmb), G(gc.w), B, ZERO, scr, scrb, stream));
-                if (e == 0) {
-                    EGO_RC(egotap_bf16_fc1_dgrad_tokens(h, Wh(w.dzb), Hb(t.w_fc1p_t), dtok, B, stream));
-                } else if (dhm) {           // the heatmaps' rotation channels: the scratch is free between this weight gradient and the next
-                    __bf16* wr = (__bf16*)scr;
-                    EGO_RC(egotap_bf16_prep_weight(fc.w, wr, wr + 2048 * K1r, 2048, (int)K1r, 2048, stream));
-                    EGO_RC(egotap_bf16_fc1_dgrad_rot(h, Wh(w.dzb), wr + 2048 * K1r, dhm, B, stream));
-                }
-            }
-        }
-        return EGOTAP_OK;
-    };
-    EGO_RC(encoder_bwd(1, W(w.drotz), nullptr));
-    EGO_RC(encoder_bwd(0, W(w.dposz), Wh(w.Rb[0])));
-    float *F0 = W(w.F[0]), *F1 = W(w.F[1]);
-    void *R0 = Wh(w.Rb[0]), *R1 = Wh(w.Rb[1]), *A4 = Wh(w.A4b), *A3 = Wh(w.A3b);
-    // final LayerNorm: dtok (R0) -> dx (F0, bf16 copy R1); column sums of dx = the last layer's output.dense.bias gradient
-    EGO_RC(egotap_bf16_layernorm_bwd(S(t.X[L]), R0, p.lnf_g, S(t.mf), S(t.rf), nullptr, F0, R1, G(g.lnf_g), G(g.lnf_b), G(g.layer[L - 1].dn_b), M, 0,
-                                     scr, scrb, stream));
-    for (int i = L - 1; i >= 0; --i) {
-        EGO_RC(bucket_done());                                                   // everything above layer i is final
-        const auto& P_ = p.layer[i];
-        const auto& G_ = g.layer[i];
-        const auto& l = t.layer[i];
-        // MLP (dx = F0 fp32, R1 bf16)
-        EGO_RC(egotap_bf16_gemm_tn(R1, D, Hb(l.hid), 4 * D, G(G_.dn_w), M, D, 4 * D, 0, ZERO, scr, scrb, stream));
-        // dz; its column sums (= the intermediate.dense bias gradient) leave the epilogue as per-wave partial sums in R0 (free until dy2)
-        EGO_RC(egotap_bf16_gemm_nt(R1, D, Hb(l.w_dn_t), nullptr, M, 4 * D, D, 3, Hb(l.z), A4, R0, 4 * D, stream));
-        EGO_RC(egotap_train_colsum((const float*)R0, 0, G(G_.up_b), 2 * ((M + 255) / 256), 4 * D, 0, scr, scrb, stream));
-        EGO_RC(egotap_bf16_gemm_tn(A4, 4 * D, Hb(l.y2), D, G(G_.up_w), M, 4 * D, D, 0, ZERO, scr, scrb, stream));
-        EGO_RC(egotap_bf16_gemm_nt(A4, 4 * D, Hb(l.w_up_t), nullptr, M, D, 4 * D, 0, nullptr, R0, nullptr, D, stream));             // dy2
-        EGO_RC(egotap_bf16_layernorm_bwd(S(l.xm), R0, P_.ln2_g, S(l.m2), S(l.r2), F0, F1, R1, G(G_.ln2_g), G(G_.ln2_b), G(G_.o_b), M, 0, scr, scrb,
-                                         stream));                                                                                   // dxm = F1, R1
-        // attention
-        EGO_RC(egotap_bf16_gemm_tn(R1, D, Hb(l.ctx), D, G(G_.o_w), M, D, D, 0, ZERO, scr, scrb, stream));
-        EGO_RC(egotap_bf16_gemm_nt(R1, D, Hb(l.w_o_t), nullptr, M, D, D, 0, nullptr, R0, nullptr, D, stream));                       // dctx
-        // dqkv, and the q | k | v bias gradients from the kernels' epilogues (no pass over dqkv)
-        EGO_RC(egotap_bf16_attention_bwd_bias(Hb(l.qkv), Hb(l.ctx), R0, S(l.lse), W(w.delta), A3, G(G_.q_b), G(G_.k_b), G(G_.v_b), B, h->seq, heads, scr, scrb,
-                                              stream));
-        float* gw[3] = {G(G_.q_w), G(G_.k_w), G(G_.v_w)};
-        for (int q = 0; q < 3; ++q)
-            EGO_RC(egotap_bf16_gemm_tn((const __bf16*)A3 + (size_t)q * D, 3 * D, Hb(l.y1), D, gw[q], M, D, D, 0, ZERO, scr, scrb, stream));
-        EGO_RC(egotap_bf16_gemm_nt(A3, 3 * D, Hb(l.w_qkv_t), nullptr, M, D, 3 * D, 0, nullptr, R0, nullptr, D, stream));             // dy1
-        EGO_RC(egotap_bf16_layernorm_bwd(S(t.X[i]), R0, P_.ln1_g, S(l.m1), S(l.r1), F1, F0, i > 0 || dhm ? R1 : nullptr, G(G_.ln1_g), G(G_.ln1_b),
-                                         i > 0 ? G(g.layer[i - 1].dn_b) : nullptr, M, 0, scr, scrb, stream));                        // dx = F0, R1
-    }
-    // patch embedding (fp32 operands: the input heatmaps)
-    EGO_RC(egotap_train_gemm_tn(h, 1, F0, 0, hm, nullptr, G(g.patch_w), M, D, 256, 0, 0, scr, scrb, stream));
-    EGO_RC(egotap_train_colsum(F0, 0, G(g.pos_emb), B, h->seq * D, 0, scr, scrb, stream));
-    EGO_RC(egotap_train_patch_split(h, g.pos_emb, G(g.patch_b), G(g.mask_tok), 0, stream));
-    EGO_RC(bucket_done());
-    EGO_RC(bucket_done());
-    if (dhm) {                      // the heatmaps' position channels, behind the last bucket event (its all-reduce overlaps this product)
-        __bf16* pw = (__bf16*)scr;
-        EGO_RC(egotap_bf16_prep_weight(p.patch_w, pw, pw + (size_t)D * 256, D, 256, D, stream));
-        EGO_RC(egotap_bf16_patch_dgrad(h, R1, pw + (size_t)D * 256, dhm, B, stream));
-    }
-    return EGOTAP_OK;
+    EGO_RC(egotap_bf16_layernorm_fwd(c.S(t.X[L]), c.Hb(t.tokens), p.lnf_g, p.lnf_b, c.S(t.mf), c.S(t.rf), M, 1e-12f, stream));
+    return lift_heads_fwd(h, c, hm, B, pose, stream);
 }
 
 extern "C" int egotap_lift_forward_train(egotap_handle h, const float* hm, int B, float* pose, void* saved, size_t saved_bytes, void* ws,
@@ -3685,47 +3552,153 @@ extern "C" int egotap_lift_forward_train(egotap_handle h, const float* hm, int B
     EGO_CHECK(h->seq % 32 == 0, "egotap_lift_forward_train: training needs a ViT sequence that is a multiple of 32 (heatmap sides 64, 128, ...: every shipped configuration); "
               "this head has %d tokens (heatmap side %d) -- evaluation runs at any side that is a multiple of 16", h->seq, h->cfg.hm_size);
     EGO_RC(lift_resolve(h));
-    if (lift_train_bf16s(h)) return lift_forward_train16(h, hm, B, pose, saved, saved_bytes, ws, ws_bytes, stream);
-    LiftTrainPlan t; LiftBwdPlan w;
-    EGO_RC(lift_train_plan(h, B, t, w));
-    EGO_CHECK(saved_bytes >= t.total, "egotap_lift_forward_train: saved buffer too small (%zu < %zu)", saved_bytes, t.total);
-    EGO_CHECK(ws_bytes >= w.total, "egotap_lift_forward_train: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    LiftStep c;
+    EGO_RC(lift_step("egotap_lift_forward_train", h, B, saved, saved_bytes, ws, ws_bytes, c));
+    if (lift_train_bf16s(h)) return lift_forward_train16(h, c, hm, B, pose, stream);
     const LiftParams& p = h->lp;
-    char* sb = (char*)saved;
-    auto S = [&](size_t off) { return (float*)(sb + off); };
-    void* scr = (char*)ws + w.scr;
-    const int M = B * h->seq, D = h->D, BT = B * h->T, heads = h->cfg.vit_heads, L = h->cfg.vit_layers;
+    const LiftTrainPlan& t = c.t;
+    const int M = B * h->seq, D = h->D, heads = h->cfg.vit_heads, L = h->cfg.vit_layers;
     const int prec = h->precision == EGOTAP_PREC_BF16 ? EGOTAP_PREC_BF16 : EGOTAP_PREC_F32;   // attention: exact unless the whole step is bf16
-    EGO_RC(egotap_train_patch_fwd(h, hm, B, p.patch_w, p.patch_b, p.mask_tok, p.pos_emb, S(t.X[0]), stream));
+    EGO_RC(egotap_train_patch_fwd(h, hm, B, p.patch_w, p.patch_b, p.mask_tok, p.pos_emb, c.S(t.X[0]), stream));
     for (int i = 0; i < L; ++i) {
         const auto& P_ = p.layer[i];
         const auto& l = t.layer[i];
-        float* x = S(t.X[i]);
-        EGO_RC(egotap_train_layernorm_fwd(x, S(l.y1), P_.ln1_g, P_.ln1_b, S(l.m1), S(l.r1), M, 1e-12f, stream));
-        EGO_RC(egotap_train_qkv_fwd(h, S(l.y1), P_.q_w, P_.q_b, P_.k_w, P_.k_b, P_.v_w, P_.v_b, S(l.qkv), M, D, stream));
-        EGO_RC(egotap_train_attention_fwd(S(l.qkv), S(l.ctx), S(l.lse), B, h->seq, heads, prec, stream));
-        EGO_RC(egotap_train_gemm_nt(h, 0, S(l.ctx), 0, nullptr, P_.o_w, P_.o_b, S(l.xm), M, D, D, 2, x, nullptr, 0, stream));
-        EGO_RC(egotap_train_layernorm_fwd(S(l.xm), S(l.y2), P_.ln2_g, P_.ln2_b, S(l.m2), S(l.r2), M, 1e-12f, stream));
-        EGO_RC(egotap_train_gemm_nt(h, 0, S(l.y2), 0, nullptr, P_.up_w, P_.up_b, S(l.hid), M, 4 * D, D, 3, nullptr, S(l.z), 0, stream));
-        EGO_RC(egotap_train_gemm_nt(h, 0, S(l.hid), 0, nullptr, P_.dn_w, P_.dn_b, S(t.X[i + 1]), M, D, 4 * D, 2, S(l.xm), nullptr, 0, stream));
+        float* x = c.S(t.X[i]);
+        EGO_RC(egotap_train_layernorm_fwd(x, c.S(l.y1), P_.ln1_g, P_.ln1_b, c.S(l.m1), c.S(l.r1), M, 1e-12f, stream));
+        EGO_RC(egotap_train_qkv_fwd(h, c.S(l.y1), P_.q_w, P_.q_b, P_.k_w, P_.k_b, P_.v_w, P_.v_b, c.S(l.qkv), M, D, stream));
+        EGO_RC(egotap_train_attention_fwd(c.S(l.qkv), c.S(l.ctx), c.S(l.lse), B, h->seq, heads, prec, stream));
+        EGO_RC(egotap_train_gemm_nt(h, 0, c.S(l.ctx), 0, nullptr, P_.o_w, P_.o_b, c.S(l.xm), M, D, D, 2, x, nullptr, 0, stream));
+        EGO_RC(egotap_train_layernorm_fwd(c.S(l.xm), c.S(l.y2), P_.ln2_g, P_.ln2_b, c.S(l.m2), c.S(l.r2), M, 1e-12f, stream));
+        EGO_RC(egotap_train_gemm_nt(h, 0, c.S(l.y2), 0, nullptr, P_.up_w, P_.up_b, c.S(l.hid), M, 4 * D, D, 3, nullptr, c.S(l.z), 0, stream));
+        EGO_RC(egotap_train_gemm_nt(h, 0, c.S(l.hid), 0, nullptr, P_.dn_w, P_.dn_b, c.S(t.X[i + 1]), M, D, 4 * D, 2, c.S(l.xm), nullptr, 0, stream));
     }
-    EGO_RC(egotap_train_layernorm_fwd(S(t.X[L]), S(t.tokens), p.lnf_g, p.lnf_b, S(t.mf), S(t.rf), M, 1e-12f, stream));
-    for (int e = 0; e < 2; ++e) {
-        const float* a_in = e == 0 ? S(t.tokens) : hm;
-        int loader = e == 0 ? 2 : 3, K = e == 0 ? h->ppd * h->ppd * D : 2 * h->cfg.hm_size * h->cfg.hm_size;
-        for (int j = 0; j < 3; ++j) {
+    EGO_RC(egotap_train_layernorm_fwd(c.S(t.X[L]), c.S(t.tokens), p.lnf_g, p.lnf_b, c.S(t.mf), c.S(t.rf), M, 1e-12f, stream));
+    return lift_heads_fwd(h, c, hm, B, pose, stream);
+}
+
+// one event per gradient-arena bucket (arena order, egotap_amd/training.py _arena_layout), recorded once every gradient in it is final
+struct LiftBuckets {
+    void* const* events;
+    int n_events, next;
+    hipStream_t s;
+    int done() {
+        if (n_events) EGO_HIP(hipEventRecord((hipEvent_t)events[next], s));
+        ++next;
+        return EGOTAP_OK;
+    }
+};
+
+// pose head + propagation units (fp32 in both storage forms): dposz, drotz and dhs1 into the workspace
+static int lift_head_bwd(Handle* h, const LiftStep& c, const float* dpose, int B, void* stream) {
+    const LiftParams& g = h->lg;
+    const LiftTrainPlan& t = c.t;
+    const LiftBwdPlan& w = c.w;
+    const float *posz = c.S(t.pos[2].y), *rotz = c.S(t.rot[2].y), *hs1 = c.S(t.pu + t.pu_hs1);
+    EGO_RC(egotap_train_pose_head_bwd(h, posz, hs1, dpose, B, c.W(w.dposz), c.W(w.dhs1), G(g.pose_w), G(g.pose_b), G(g.glob_w), G(g.glob_b), 0, stream));
+    float* pug[14] = {G(g.x2f0_w), G(g.x2f0_b), G(g.x2h0_w), G(g.x2h0_b), G(g.b2h0_w), G(g.b2h0_b), G(g.h2h0_w), G(g.h2h0_b),
+                      G(g.x2f1_w), G(g.x2f1_b), G(g.x2h1_w), G(g.x2h1_b), G(g.h2h1_w), G(g.h2h1_b)};
+    return egotap_train_pu_bwd(h, posz, rotz, B, c.sb + t.pu, c.W(w.dhs1), c.W(w.dposz), c.W(w.drotz), pug, 0, c.wb + w.pu, w.pu_bytes, stream);
+}
+
+// patch embedding (fp32 operands: the input heatmaps): weight, position embeddings (sum over the batch: dx viewed as [B, seq * D]),
+// bias / mask token; that completes the last two buckets
+static int lift_patch_bwd(Handle* h, const LiftStep& c, const float* hm, const float* dx, int B, LiftBuckets& bk, void* stream) {
+    const LiftParams& g = h->lg;
+    EGO_RC(egotap_train_gemm_tn(h, 1, dx, 0, hm, nullptr, G(g.patch_w), B * h->seq, h->D, 256, 0, 0, c.scr(), c.w.scr_bytes, stream));
+    EGO_RC(egotap_train_colsum(dx, 0, G(g.pos_emb), B, h->seq * h->D, 0, c.scr(), c.w.scr_bytes, stream));
+    EGO_RC(egotap_train_patch_split(h, g.pos_emb, G(g.patch_b), G(g.mask_tok), 0, stream));
+    EGO_RC(bk.done());
+    return bk.done();
+}
+
+static int lift_backward16(const char* fn, Handle* h, const LiftStep& c, const float* hm, const float* dpose, int B, LiftBuckets& bk, void* stream,
+                           float* dhm) {
+    const LiftTrainPlan& t = c.t;
+    const LiftBwdPlan& w = c.w;
+    const size_t K1r = 2 * (size_t)h->cfg.hm_size * h->cfg.hm_size;
+    // dhm: the bf16 copies of rotation fc1.weight (+ its transpose) and of projection.weight (+ transpose) live in the scratch while it is free
+    EGO_CHECK(!dhm || w.scr_bytes >= 2 * 2048 * K1r * 2, "%s: scratch too small for the transposed rotation fc1 weight", fn);
+    const int L = h->cfg.vit_layers;
+    const LiftParams& p = h->lp;
+    const LiftParams& g = h->lg;
+    void* scr = c.scr();
+    const size_t scrb = w.scr_bytes;
+    hipStream_t s = (hipStream_t)stream;
+    const int M = B * h->seq, D = h->D, BT = B * h->T, heads = h->cfg.vit_heads;
+    const void* ZERO = c.wb + w.zero;
+    EGO_HIP(zero_fill(c.wb + w.zero, 4096, s));
+    EGO_RC(lift_head_bwd(h, c, dpose, B, stream));
+    // FC encoders: fc3, fc2 in fp32 (small), fc1 on the bf16 kernels; the position encoder returns the token gradient (bf16, token order)
+    auto encoder_bwd = [&](int e, const float* dy, void* dtok) -> int {
+        for (int j = 2; j >= 0; --j) {
             const int n = j < 2 ? FC_OUT[j] : h->hid;
             const LiftParams::Fc& fc = e == 0 ? p.pos_fc[j] : p.rot_fc[j];
+            const LiftParams::Fc& gc = e == 0 ? g.pos_fc[j] : g.rot_fc[j];
             const LiftTrainPlan::Fc& f = e == 0 ? t.pos[j] : t.rot[j];
-            EGO_RC(egotap_train_gemm_nt(h, loader, a_in, 0, nullptr, fc.w, fc.b, S(f.z), BT, n, K, 1, nullptr, nullptr, 0, stream));
-            // train-mode BatchNorm1d: batch statistics, running statistics updated in the bound buffers (momentum 0.1, unbiased variance)
-            EGO_RC(egotap_train_bn_lrelu_fwd(S(f.z), S(f.y), fc.g, fc.beta, S(f.mean), S(f.rstd), (float*)fc.mean, (float*)fc.var, BT, n, 1e-5f,
-                                             0.1f, scr, w.scr_bytes, stream));
-            a_in = S(f.y); loader = 0; K = n;
+            float* dz = c.W(w.E[0]);
+            EGO_RC(egotap_train_bn_lrelu_bwd(c.S(f.z), c.S(f.y), dy, fc.g, c.S(f.mean), c.S(f.rstd), dz, G(gc.g), G(gc.beta), BT, n, 0, scr, scrb, stream));
+            EGO_RC(egotap_train_colsum(dz, 0, G(gc.b), BT, n, 0, scr, scrb, stream));
+            if (j > 0) {
+                const int K = FC_OUT[j - 1];
+                const float* a_in = c.S((e == 0 ? t.pos[j - 1] : t.rot[j - 1]).y);
+                EGO_RC(egotap_train_gemm_tn(h, 0, dz, 0, a_in, nullptr, G(gc.w), BT, n, K, 0, 0, scr, scrb, stream));
+                EGO_RC(egotap_train_transpose(fc.w, c.W(w.WT), n, K, 0, stream));
+                EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, c.W(w.WT), nullptr, c.W(w.E[1]), BT, K, n, 0, nullptr, nullptr, 0, stream));
+                dy = c.W(w.E[1]);
+            } else {
+                EGO_RC(egotap_bf16_from_f32(dz, c.Wh(w.dzb), (int64_t)BT * 2048, stream));
+                EGO_RC(egotap_bf16_fc1_wgrad(h, e, c.Wh(w.dzb), e == 0 ? c.Hb(t.tokens) : c.Hb(t.hmb), G(gc.w), B, ZERO, scr, scrb, stream));
+                if (e == 0) {
+                    EGO_RC(egotap_bf16_fc1_dgrad_tokens(h, c.Wh(w.dzb), c.Hb(t.w_fc1p_t), dtok, B, stream));
+                } else if (dhm) {           // the heatmaps' rotation channels: the scratch is free between this weight gradient and the next
+                    __bf16* wr = (__bf16*)scr;
+                    EGO_RC(egotap_bf16_prep_weight(fc.w, wr, wr + 2048 * K1r, 2048, (int)K1r, 2048, stream));
+                    EGO_RC(egotap_bf16_fc1_dgrad_rot(h, c.Wh(w.dzb), wr + 2048 * K1r, dhm, B, stream));
+                }
+            }
         }
+        return EGOTAP_OK;
+    };
+    EGO_RC(encoder_bwd(1, c.W(w.drotz), nullptr));
+    EGO_RC(encoder_bwd(0, c.W(w.dposz), c.Wh(w.Rb[0])));
+    float *F0 = c.W(w.F[0]), *F1 = c.W(w.F[1]);
+    void *R0 = c.Wh(w.Rb[0]), *R1 = c.Wh(w.Rb[1]), *A4 = c.Wh(w.A4b), *A3 = c.Wh(w.A3b);
+    // final LayerNorm: dtok (R0) -> dx (F0, bf16 copy R1); column sums of dx = the last layer's output.dense.bias gradient
+    EGO_RC(egotap_bf16_layernorm_bwd(c.S(t.X[L]), R0, p.lnf_g, c.S(t.mf), c.S(t.rf), nullptr, F0, R1, G(g.lnf_g), G(g.lnf_b), G(g.layer[L - 1].dn_b), M, 0,
+                                     scr, scrb, stream));
+    for (int i = L - 1; i >= 0; --i) {
+        EGO_RC(bk.done());                                                       // everything above layer i is final
+        const auto& P_ = p.layer[i];
+        const auto& G_ = g.layer[i];
+        const auto& l = t.layer[i];
+        // MLP (dx = F0 fp32, R1 bf16)
+        EGO_RC(egotap_bf16_gemm_tn(R1, D, c.Hb(l.hid), 4 * D, G(G_.dn_w), M, D, 4 * D, 0, ZERO, scr, scrb, stream));
+        // dz; its column sums (= the intermediate.dense bias gradient) leave the epilogue as per-wave partial sums in R0 (free until dy2)
+        EGO_RC(egotap_bf16_gemm_nt(R1, D, c.Hb(l.w_dn_t), nullptr, M, 4 * D, D, 3, c.Hb(l.z), A4, R0, 4 * D, stream));
+        EGO_RC(egotap_train_colsum((const float*)R0, 0, G(G_.up_b), 2 * ((M + 255) / 256), 4 * D, 0, scr, scrb, stream));
+        EGO_RC(egotap_bf16_gemm_tn(A4, 4 * D, c.Hb(l.y2), D, G(G_.up_w), M, 4 * D, D, 0, ZERO, scr, scrb, stream));
+        EGO_RC(egotap_bf16_gemm_nt(A4, 4 * D, c.Hb(l.w_up_t), nullptr, M, D, 4 * D, 0, nullptr, R0, nullptr, D, stream));             // dy2
+        EGO_RC(egotap_bf16_layernorm_bwd(c.S(l.xm), R0, P_.ln2_g, c.S(l.m2), c.S(l.r2), F0, F1, R1, G(G_.ln2_g), G(G_.ln2_b), G(G_.o_b), M, 0, scr, scrb,
+                                         stream));                                                                                   // dxm = F1, R1
+        // attention
+        EGO_RC(egotap_bf16_gemm_tn(R1, D, c.Hb(l.ctx), D, G(G_.o_w), M, D, D, 0, ZERO, scr, scrb, stream));
+        EGO_RC(egotap_bf16_gemm_nt(R1, D, c.Hb(l.w_o_t), nullptr, M, D, D, 0, nullptr, R0, nullptr, D, stream));                       // dctx
+        // dqkv, and the q | k | v bias gradients from the kernels' epilogues (no pass over dqkv)
+        EGO_RC(egotap_bf16_attention_bwd_bias(c.Hb(l.qkv), c.Hb(l.ctx), R0, c.S(l.lse), c.W(w.delta), A3, G(G_.q_b), G(G_.k_b), G(G_.v_b), B, h->seq, heads,
+                                              scr, scrb, stream));
+        float* gw[3] = {G(G_.q_w), G(G_.k_w), G(G_.v_w)};
+        for (int q = 0; q < 3; ++q)
+            EGO_RC(egotap_bf16_gemm_tn((const __bf16*)A3 + (size_t)q * D, 3 * D, c.Hb(l.y1), D, gw[q], M, D, D, 0, ZERO, scr, scrb, stream));
+        EGO_RC(egotap_bf16_gemm_nt(A3, 3 * D, c.Hb(l.w_qkv_t), nullptr, M, D, 3 * D, 0, nullptr, R0, nullptr, D, stream));             // dy1
+        EGO_RC(egotap_bf16_layernorm_bwd(c.S(t.X[i]), R0, P_.ln1_g, c.S(l.m1), c.S(l.r1), F1, F0, i > 0 || dhm ? R1 : nullptr, G(G_.ln1_g), G(G_.ln1_b),
+                                         i > 0 ? G(g.layer[i - 1].dn_b) : nullptr, M, 0, scr, scrb, stream));                        // dx = F0, R1
     }
-    EGO_RC(egotap_train_pu_fwd(h, S(t.pos[2].y), S(t.rot[2].y), B, sb + t.pu, t.pu_bytes, stream));
-    EGO_RC(egotap_train_pose_head_fwd(h, S(t.pos[2].y), (const float*)(sb + t.pu + t.pu_hs1), B, pose, stream));
+    EGO_RC(lift_patch_bwd(h, c, hm, F0, B, bk, stream));
+    if (dhm) {                      // the heatmaps' position channels, behind the last bucket event (its all-reduce overlaps this product)
+        __bf16* pw = (__bf16*)scr;
+        EGO_RC(egotap_bf16_prep_weight(p.patch_w, pw, pw + (size_t)D * 256, D, 256, D, stream));
+        EGO_RC(egotap_bf16_patch_dgrad(h, R1, pw + (size_t)D * 256, dhm, B, stream));
+    }
     return EGOTAP_OK;
 }
 
@@ -3739,35 +3712,19 @@ static int lift_backward_impl(const char* fn, Handle* h, const float* hm, const 
     }
     const int L = h->cfg.vit_layers;
     EGO_CHECK(n_events == 0 || (bucket_events && n_events == L + 2), "%s: %d bucket events, the arena has %d buckets", fn, n_events, L + 2);
-    if (lift_train_bf16s(h)) return lift_backward16(fn, h, hm, dpose, B, saved, saved_bytes, ws, ws_bytes, bucket_events, n_events, stream, dhm);
-    LiftTrainPlan t; LiftBwdPlan w;
-    EGO_RC(lift_train_plan(h, B, t, w));
-    EGO_CHECK(saved_bytes >= t.total, "%s: saved buffer too small (%zu < %zu)", fn, saved_bytes, t.total);
-    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, w.total);
+    LiftStep c;
+    EGO_RC(lift_step(fn, h, B, saved, saved_bytes, ws, ws_bytes, c));
+    LiftBuckets bk{bucket_events, n_events, 0, (hipStream_t)stream};
+    if (lift_train_bf16s(h)) return lift_backward16(fn, h, c, hm, dpose, B, bk, stream, dhm);
+    const LiftTrainPlan& t = c.t;
+    const LiftBwdPlan& w = c.w;
     const LiftParams& p = h->lp;
     const LiftParams& g = h->lg;
-    auto G = [](const float* q) { return (float*)q; };
-    const char* sb = (const char*)saved;
-    auto S = [&](size_t off) { return (const float*)(sb + off); };
-    char* wb = (char*)ws;
-    auto W = [&](size_t off) { return (float*)(wb + off); };
-    void* scr = wb + w.scr;
+    void* scr = c.scr();
     const size_t scrb = w.scr_bytes;
-    hipStream_t s = (hipStream_t)stream;
     const int M = B * h->seq, D = h->D, BT = B * h->T, heads = h->cfg.vit_heads;
     const int prec = h->precision == EGOTAP_PREC_BF16 ? EGOTAP_PREC_BF16 : EGOTAP_PREC_F32;
-    int bucket = 0;
-    auto bucket_done = [&]() -> int {     // every gradient of the next bucket (arena order, egotap_amd/training.py _arena_layout) is final
-        if (n_events) EGO_HIP(hipEventRecord((hipEvent_t)bucket_events[bucket], s));
-        ++bucket;
-        return EGOTAP_OK;
-    };
-    const float *posz = S(t.pos[2].y), *rotz = S(t.rot[2].y), *hs1 = (const float*)(sb + t.pu + t.pu_hs1);
-    // pose head + propagation units
-    EGO_RC(egotap_train_pose_head_bwd(h, posz, hs1, dpose, B, W(w.dposz), W(w.dhs1), G(g.pose_w), G(g.pose_b), G(g.glob_w), G(g.glob_b), 0, stream));
-    float* pug[14] = {G(g.x2f0_w), G(g.x2f0_b), G(g.x2h0_w), G(g.x2h0_b), G(g.b2h0_w), G(g.b2h0_b), G(g.h2h0_w), G(g.h2h0_b),
-                      G(g.x2f1_w), G(g.x2f1_b), G(g.x2h1_w), G(g.x2h1_b), G(g.h2h1_w), G(g.h2h1_b)};
-    EGO_RC(egotap_train_pu_bwd(h, posz, rotz, B, sb + t.pu, W(w.dhs1), W(w.dposz), W(w.drotz), pug, 0, wb + w.pu, w.pu_bytes, stream));
+    EGO_RC(lift_head_bwd(h, c, dpose, B, stream));
     // the two FC encoders, last block first; returns in *dA the gradient w.r.t. the gathered fc1 rows (position encoder only)
     auto encoder_bwd = [&](int e, const float* dy, float** dA) -> int {
         for (int j = 2; j >= 0; --j) {
@@ -3777,32 +3734,32 @@ static int lift_backward_impl(const char* fn, Handle* h, const float* hm, const 
             const LiftParams::Fc& fc = e == 0 ? p.pos_fc[j] : p.rot_fc[j];
             const LiftParams::Fc& gc = e == 0 ? g.pos_fc[j] : g.rot_fc[j];
             const LiftTrainPlan::Fc& f = e == 0 ? t.pos[j] : t.rot[j];
-            const float* a_in = j > 0 ? S((e == 0 ? t.pos[j - 1] : t.rot[j - 1]).y) : (e == 0 ? S(t.tokens) : hm);
-            float* dz = W(w.E[0]);
-            EGO_RC(egotap_train_bn_lrelu_bwd(S(f.z), S(f.y), dy, fc.g, S(f.mean), S(f.rstd), dz, G(gc.g), G(gc.beta), BT, n, 0, scr, scrb, stream));
+            const float* a_in = j > 0 ? c.S((e == 0 ? t.pos[j - 1] : t.rot[j - 1]).y) : (e == 0 ? c.S(t.tokens) : hm);
+            float* dz = c.W(w.E[0]);
+            EGO_RC(egotap_train_bn_lrelu_bwd(c.S(f.z), c.S(f.y), dy, fc.g, c.S(f.mean), c.S(f.rstd), dz, G(gc.g), G(gc.beta), BT, n, 0, scr, scrb, stream));
             EGO_RC(egotap_train_gemm_tn(h, loader, dz, 0, a_in, nullptr, G(gc.w), BT, n, K, 0, 0, scr, scrb, stream));
             EGO_RC(egotap_train_colsum(dz, 0, G(gc.b), BT, n, 0, scr, scrb, stream));
             if (j == 0 && e == 1) {                                          // the rotation encoder's input: the heatmaps
                 if (dhm) {                                                   // their rotation channels, while dz (E[0]) is live
-                    EGO_RC(egotap_train_transpose(fc.w, W(w.WT), n, K, 0, stream));                                              // [2 S^2, 2048]
-                    EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, W(w.WT), nullptr, dhm, BT, K, n, TE_SCATTER_ROT, nullptr, nullptr, 0, stream));
+                    EGO_RC(egotap_train_transpose(fc.w, c.W(w.WT), n, K, 0, stream));                                            // [2 S^2, 2048]
+                    EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, c.W(w.WT), nullptr, dhm, BT, K, n, TE_SCATTER_ROT, nullptr, nullptr, 0, stream));
                 }
                 return EGOTAP_OK;
             }
-            EGO_RC(egotap_train_transpose(fc.w, W(w.WT), n, K, 0, stream));  // [K, n]
-            float* dnext = j == 0 ? W(w.R[1]) : W(w.E[1]);
-            EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, W(w.WT), nullptr, dnext, BT, K, n, 0, nullptr, nullptr, 0, stream));
+            EGO_RC(egotap_train_transpose(fc.w, c.W(w.WT), n, K, 0, stream));  // [K, n]
+            float* dnext = j == 0 ? c.W(w.R[1]) : c.W(w.E[1]);
+            EGO_RC(egotap_train_gemm_nt(h, 0, dz, 0, nullptr, c.W(w.WT), nullptr, dnext, BT, K, n, 0, nullptr, nullptr, 0, stream));
             dy = dnext;
             if (j == 0) *dA = dnext;
         }
         return EGOTAP_OK;
     };
     float* dA = nullptr;
-    EGO_RC(encoder_bwd(1, W(w.drotz), nullptr));
-    EGO_RC(encoder_bwd(0, W(w.dposz), &dA));
-    float *R0 = W(w.R[0]), *R1 = W(w.R[1]), *R2 = W(w.R[2]), *A4 = W(w.A4), *A3 = W(w.A3), *WT = W(w.WT);
+    EGO_RC(encoder_bwd(1, c.W(w.drotz), nullptr));
+    EGO_RC(encoder_bwd(0, c.W(w.dposz), &dA));
+    float *R0 = c.W(w.R[0]), *R1 = c.W(w.R[1]), *R2 = c.W(w.R[2]), *A4 = c.W(w.A4), *A3 = c.W(w.A3), *WT = c.W(w.WT);
     EGO_RC(egotap_train_tokens_scatter(h, dA, R0, B, stream));                                                   // dtok
-    EGO_RC(egotap_train_layernorm_bwd(S(t.X[L]), R0, p.lnf_g, S(t.mf), S(t.rf), nullptr, R1, G(g.lnf_g), G(g.lnf_b), M, 0, scr, scrb, stream));
+    EGO_RC(egotap_train_layernorm_bwd(c.S(t.X[L]), R0, p.lnf_g, c.S(t.mf), c.S(t.rf), nullptr, R1, G(g.lnf_g), G(g.lnf_b), M, 0, scr, scrb, stream));
     float* dx = R1;
     for (int i = L - 1; i >= 0; --i) {
         const auto& P_ = p.layer[i];
@@ -3810,38 +3767,33 @@ static int lift_backward_impl(const char* fn, Handle* h, const float* hm, const 
         const auto& l = t.layer[i];
         // output.dense.bias of layer i closes the bucket of layer i + 1 (or of the head, for the last layer)
         // [r3] every bias gradient of the layer comes out of the weight-gradient GEMM that stages the same dY (egotap_train_gemm_tn_bias)
-        EGO_RC(egotap_train_gemm_tn_bias(h, dx, 0, S(l.hid), G(G_.dn_w), G(G_.dn_b), M, D, 4 * D, 0, scr, scrb, stream));
-        EGO_RC(bucket_done());
+        EGO_RC(egotap_train_gemm_tn_bias(h, dx, 0, c.S(l.hid), G(G_.dn_w), G(G_.dn_b), M, D, 4 * D, 0, scr, scrb, stream));
+        EGO_RC(bk.done());
         // MLP
         EGO_RC(egotap_train_transpose(P_.dn_w, WT, D, 4 * D, 0, stream));
-        EGO_RC(egotap_train_gemm_nt(h, 0, dx, 0, nullptr, WT, nullptr, A4, M, 4 * D, D, 5, S(l.z), nullptr, 0, stream));          // dz
-        EGO_RC(egotap_train_gemm_tn_bias(h, A4, 0, S(l.y2), G(G_.up_w), G(G_.up_b), M, 4 * D, D, 0, scr, scrb, stream));
+        EGO_RC(egotap_train_gemm_nt(h, 0, dx, 0, nullptr, WT, nullptr, A4, M, 4 * D, D, 5, c.S(l.z), nullptr, 0, stream));          // dz
+        EGO_RC(egotap_train_gemm_tn_bias(h, A4, 0, c.S(l.y2), G(G_.up_w), G(G_.up_b), M, 4 * D, D, 0, scr, scrb, stream));
         EGO_RC(egotap_train_transpose(P_.up_w, WT, 4 * D, D, 0, stream));
         EGO_RC(egotap_train_gemm_nt(h, 0, A4, 0, nullptr, WT, nullptr, R0, M, D, 4 * D, 0, nullptr, nullptr, 0, stream));          // dy2
-        EGO_RC(egotap_train_layernorm_bwd(S(l.xm), R0, P_.ln2_g, S(l.m2), S(l.r2), dx, R2, G(G_.ln2_g), G(G_.ln2_b), M, 0, scr, scrb, stream));
+        EGO_RC(egotap_train_layernorm_bwd(c.S(l.xm), R0, P_.ln2_g, c.S(l.m2), c.S(l.r2), dx, R2, G(G_.ln2_g), G(G_.ln2_b), M, 0, scr, scrb, stream));
         float* dxm = R2;
         // attention
-        EGO_RC(egotap_train_gemm_tn_bias(h, dxm, 0, S(l.ctx), G(G_.o_w), G(G_.o_b), M, D, D, 0, scr, scrb, stream));
+        EGO_RC(egotap_train_gemm_tn_bias(h, dxm, 0, c.S(l.ctx), G(G_.o_w), G(G_.o_b), M, D, D, 0, scr, scrb, stream));
         EGO_RC(egotap_train_transpose(P_.o_w, WT, D, D, 0, stream));
         EGO_RC(egotap_train_gemm_nt(h, 0, dxm, 0, nullptr, WT, nullptr, R0, M, D, D, 0, nullptr, nullptr, 0, stream));             // dctx
-        EGO_RC(egotap_train_attention_bwd(S(l.qkv), S(l.ctx), R0, S(l.lse), W(w.delta), A3, B, h->seq, heads, prec, stream));   // dqkv
+        EGO_RC(egotap_train_attention_bwd(c.S(l.qkv), c.S(l.ctx), R0, c.S(l.lse), c.W(w.delta), A3, B, h->seq, heads, prec, stream));   // dqkv
         const float* pw[3] = {P_.q_w, P_.k_w, P_.v_w};
         float* gw[3] = {G(G_.q_w), G(G_.k_w), G(G_.v_w)};
         float* gb[3] = {G(G_.q_b), G(G_.k_b), G(G_.v_b)};
         for (int q = 0; q < 3; ++q) {
-            EGO_RC(egotap_train_gemm_tn_bias(h, A3 + (size_t)q * D, 3 * D, S(l.y1), gw[q], gb[q], M, D, D, 0, scr, scrb, stream));
+            EGO_RC(egotap_train_gemm_tn_bias(h, A3 + (size_t)q * D, 3 * D, c.S(l.y1), gw[q], gb[q], M, D, D, 0, scr, scrb, stream));
             EGO_RC(egotap_train_transpose(pw[q], WT + (size_t)q * D, D, D, 3 * D, stream));                                         // [Wq^T | Wk^T | Wv^T]
         }
         EGO_RC(egotap_train_gemm_nt(h, 0, A3, 0, nullptr, WT, nullptr, R0, M, D, 3 * D, 0, nullptr, nullptr, 0, stream));          // dy1
-        EGO_RC(egotap_train_layernorm_bwd(S(t.X[i]), R0, P_.ln1_g, S(l.m1), S(l.r1), dxm, R1, G(G_.ln1_g), G(G_.ln1_b), M, 0, scr, scrb, stream));
+        EGO_RC(egotap_train_layernorm_bwd(c.S(t.X[i]), R0, P_.ln1_g, c.S(l.m1), c.S(l.r1), dxm, R1, G(G_.ln1_g), G(G_.ln1_b), M, 0, scr, scrb, stream));
         dx = R1;
     }
-    // patch embedding: weight, position embeddings (sum over the batch: dx viewed as [B, seq * D]), bias / mask token
-    EGO_RC(egotap_train_gemm_tn(h, 1, dx, 0, hm, nullptr, G(g.patch_w), M, D, 256, 0, 0, scr, scrb, stream));
-    EGO_RC(egotap_train_colsum(dx, 0, G(g.pos_emb), B, h->seq * D, 0, scr, scrb, stream));
-    EGO_RC(egotap_train_patch_split(h, g.pos_emb, G(g.patch_b), G(g.mask_tok), 0, stream));
-    EGO_RC(bucket_done());
-    EGO_RC(bucket_done());
+    EGO_RC(lift_patch_bwd(h, c, hm, dx, B, bk, stream));
     if (dhm) {                      // the heatmaps' position channels, behind the last bucket event (its all-reduce overlaps this product)
         EGO_RC(egotap_train_transpose(p.patch_w, WT, D, 256, 0, stream));                                                       // [256, D]
         EGO_RC(egotap_train_gemm_nt(h, 0, dx, 0, nullptr, WT, nullptr, dhm, M, 256, D, TE_SCATTER_PATCH, nullptr, nullptr, 0, stream));

@@ -366,20 +366,6 @@ static __global__ __launch_bounds__(256) void bn_finish_kernel(const float* __re
     }
 }
 
-// ----------------------------------------------------------------------------- GELU backward (exact erf form)
-// dz = dh * (0.5 (1 + erf(z/sqrt2)) + z * exp(-z^2/2) / sqrt(2 pi))
-static __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__ Zp, const float* __restrict__ dH, float* __restrict__ dZ,
-                                                       long n4) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const f32x4 z = *(const f32x4*)(Zp + i * 4), d = *(const f32x4*)(dH + i * 4);
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        o[k] = d[k] * dgelu_erf(z[k]);
-    *(f32x4*)(dZ + i * 4) = o;
-}
-
 // out[i] += in[i] (gradient accumulation of a residual branch), n4 float4
 static __global__ __launch_bounds__(256) void add_inplace_kernel(float* __restrict__ out, const float* __restrict__ in, long n4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,13 +1,19 @@
 """Training step of the lifting head on the HIP operators: PyTorch is autograd glue only.
 
-``LiftTrainFn`` is ONE torch.autograd.Function for the whole head (heatmaps + parameters -> pose): its forward runs
-the training-mode network through libegotap_hip.so keeping the activations, its backward walks the layers in reverse
-through the backward operators and hands every parameter gradient back to autograd, so ``loss.backward()`` /
-``optimizer.step()`` in the wrapper read exactly like the reference (model/egotap_autoencoder_model.py:299-323).
-``PoseLossFn`` is the loss (utils/loss.py:54-85), ``EgotapAdamW`` the optimizer (model/network.py:72-78) -- both HIP.
+Three torch.autograd.Functions run the whole head (heatmaps + parameters -> pose) in train mode.  Each forward keeps the activations,
+each backward hands every parameter gradient (and the heatmaps' gradient, when the input requires one) back to autograd, so
+``loss.backward()`` / ``optimizer.step()`` in the wrapper read exactly like the reference (model/egotap_autoencoder_model.py:299-323):
 
-``LiftTrainFn`` runs the fp32 / bf16x3 arithmetic on fp32 tensors; ``LiftTrainBf16Fn`` is the reduced-precision mode (bf16
-activations in HBM, fp32 master weights and accumulation) behind the wrapper's --use_amp.
+- ``LiftTrainOneCallFn``: the step on the one-call ABI (egotap_lift_forward_train / egotap_lift_backward), which picks the fp32-tensor or
+  the bf16-storage step itself.  ``lift_train_forward``, and so the wrapper, uses it by default.
+- ``LiftTrainFn``: the fp32-tensor step (f32 / bf16x3 arithmetic) composed operator by operator from Python.
+- ``LiftTrainBf16Fn``: the bf16-storage step (bf16 activations in HBM, fp32 master weights and accumulation; the wrapper's --use_amp)
+  composed the same way.
+
+The two compositions run when ``net.one_call_training`` is False (and ``LiftTrainFn`` for bf16 arithmetic on fp32 tensors at vit_dim
+1024, ``net.bf16_storage = False``); tests/test_gpu_train_step.py holds the one-call ABI bit-identical to them.  They share everything
+but the patch embedding's forward, the ViT layers and the encoders' fc1.  ``PoseLossFn`` is the loss (utils/loss.py:54-85),
+``EgotapAdamW`` the optimizer (model/network.py:72-78) -- both HIP.
 """
 from __future__ import annotations
 
@@ -119,6 +125,101 @@ def _bind_grads(net, h, ga, G):
         net._grads_bound = sig
 
 
+def _step_setup(net, hm, params):
+    """what every training forward starts with: the parameters by name, the handle with every tensor bound, the input's dtype and the
+    fp32 heatmaps the step runs on"""
+    P = dict(zip(_param_order(net.preset), params))
+    h = net._ensure_handle()
+    net._bind(hm.device)
+    return P, h, hm.dtype, hm.detach().float().contiguous()
+
+
+def _heads_fwd(net, h, P, B, fc1):
+    """the composed forward after the ViT, both storage forms: the two FC encoders, the propagation units and the pose head.  fc1(e, w, b)
+    is the caller's fc1 of encoder e (0: position, 1: rotation); fc2, fc3 and every train-mode BatchNorm1d (batch statistics, running
+    statistics and num_batches_tracked updated) are common.  Returns the pose and what the backward reads."""
+    p = net.preset
+    BT = B * p.tokens
+    bufs = dict(net.named_buffers())
+    acts = []
+    for e, name in enumerate(("pos_heatmap_encoder", "rot_heatmap_encoder")):
+        blocks, a_in = [], None
+        for j, n_out in enumerate((2048, 512, p.hidden), start=1):
+            f = f"{name}.fc{j}"
+            w = P[f + ".fc.weight"]
+            z = fc1(e, w, P[f + ".fc.bias"]) if j == 1 else T.gemm_nt(h, a_in, w, P[f + ".fc.bias"], BT, n_out, w.shape[1], epi=T.TE_BIAS)
+            y, mean, rstd = T.bn_lrelu_fwd(z, P[f + ".bn.weight"], P[f + ".bn.bias"], bufs[f + ".bn.running_mean"], bufs[f + ".bn.running_var"])
+            bufs[f + ".bn.num_batches_tracked"].add_(1)
+            blocks.append(dict(a_in=a_in, z=z, y=y, mean=mean, rstd=rstd, K=w.shape[1], N=n_out, name=f))
+            a_in = y
+        acts.append(blocks)
+    lib = _lib.load()
+    posz, rotz = acts[0][-1]["y"], acts[1][-1]["y"]
+    nb, off = C.c_size_t(), C.c_size_t()
+    _lib.check(lib.egotap_train_pu_saved_bytes(h, B, C.byref(nb), C.byref(off)))
+    pu_saved = torch.empty(nb.value, dtype=torch.uint8, device=posz.device)
+    _lib.check(lib.egotap_train_pu_fwd(h, T._p(posz), T._p(rotz), B, T._p(pu_saved), pu_saved.numel(), T._s()))
+    hs1 = pu_saved[off.value: off.value + 4 * p.n_joints_hm * B * p.pu_hidden].view(torch.float32)
+    pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=posz.device)
+    _lib.check(lib.egotap_train_pose_head_fwd(h, T._p(posz), T._p(hs1), B, T._p(pose), T._s()))
+    return pose, dict(pos_acts=acts[0], rot_acts=acts[1], pu_saved=pu_saved, hs1=hs1)
+
+
+def _open_backward(net, P):
+    """the gradient arena (every entry is fully overwritten by the backward), the gradients it would overwrite, the started reducer"""
+    ga, G = _grad_arena(net, P)
+    held = _held_grads(P, G)
+    red = net._reducer()
+    red.begin(ga["flat"])
+    return ga, G, held, red
+
+
+def _heads_bwd(net, h, S, G, dpose):
+    """pose head + propagation units backward (fp32 in every mode): returns the gradients w.r.t. the two encoders' outputs"""
+    p, B = net.preset, S["B"]
+    lib = _lib.load()
+    posz, rotz = S["pos_acts"][-1]["y"], S["rot_acts"][-1]["y"]
+    dposz, drotz = torch.empty_like(posz), torch.empty_like(rotz)
+    dhs1 = torch.empty(p.n_joints_hm * B * p.pu_hidden, dtype=torch.float32, device=posz.device)
+    _lib.check(lib.egotap_train_pose_head_bwd(h, T._p(posz), T._p(S["hs1"]), T._p(dpose), B, T._p(dposz), T._p(dhs1),
+                                              T._p(G["pose_mlp.pose_fcs.0.weight"]), T._p(G["pose_mlp.pose_fcs.0.bias"]),
+                                              T._p(G.get("global_mlp.pose_fcs.0.weight")), T._p(G.get("global_mlp.pose_fcs.0.bias")), 0, T._s()))
+    wsb = C.c_size_t()
+    _lib.check(lib.egotap_train_pu_bwd_ws_bytes(h, B, C.byref(wsb)))
+    ws = torch.empty(wsb.value, dtype=torch.uint8, device=posz.device)
+    ptrs = (C.c_void_p * 14)()
+    c = "skel_sequential_layer.lstm_custom.layers."
+    for i, nme in enumerate(("0.x2f", "0.x2h", "0.b2h", "0.h2h", "1.x2f", "1.x2h", "1.h2h")):
+        ptrs[2 * i] = G[c + nme + ".weight"].data_ptr()
+        ptrs[2 * i + 1] = G[c + nme + ".bias"].data_ptr()
+    _lib.check(lib.egotap_train_pu_bwd(h, T._p(posz), T._p(rotz), B, T._p(S["pu_saved"]), T._p(dhs1), T._p(dposz), T._p(drotz), ptrs, 0,
+                                       T._p(ws), ws.numel(), T._s()))
+    return dposz, drotz
+
+
+def _patch_bwd(net, h, S, G, dx, red, ga):
+    """patch embedding backward (fp32 operands: the input heatmaps): weight, position embeddings (sum over the batch: dx viewed as
+    [B, seq * D]), bias / mask token; that completes the last two buckets"""
+    p, B, v = net.preset, S["B"], "pos_heatmap_encoder.vit."
+    T.gemm_tn(h, dx, S["hm"], G[v + "embeddings.patch_embeddings.projection.weight"], B * p.seq, p.vit_dim, 256, loader=T.LD_PATCH)
+    dpos = G[v + "embeddings.position_embeddings"]
+    T.colsum(dx, dpos, B, p.seq * p.vit_dim)
+    _lib.check(_lib.load().egotap_train_patch_split(h, T._p(dpos), T._p(G[v + "embeddings.patch_embeddings.projection.bias"]),
+                                                    T._p(G[v + "embeddings.mask_token"]), 0, T._s()))
+    nb = len(ga["bounds"])
+    red.bucket_ready(ga["bounds"][nb - 3], ga["bounds"][nb - 2])
+    red.bucket_ready(ga["bounds"][nb - 2], ga["bounds"][nb - 1])
+
+
+def _close_backward(ctx, red, P, G, held, dhm):
+    """the end of a composed backward: the reducer's last all-reduce, the gradients published, the heatmaps' gradient returned"""
+    red.finish()
+    _publish_grads(P, G, held)
+    in_dtype = ctx.egotap["in_dtype"]
+    ctx.egotap = None
+    return (None, _input_grad(dhm, in_dtype)) + (None,) * len(P)
+
+
 class LiftTrainOneCallFn(torch.autograd.Function):
     """The training step (fp32 / bf16x3 arithmetic on fp32 tensors, or the bf16-storage step under EGOTAP_PREC_BF16) on the one-call ABI: egotap_lift_forward_train keeps the activations in one caller-owned buffer,
     egotap_lift_backward writes every gradient into the flat arena (bound once with egotap_bind_grad) and records one event per arena
@@ -126,17 +227,10 @@ class LiftTrainOneCallFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, hm, *params):
-        p = net.preset
-        keys = _param_order(p)
-        P = dict(zip(keys, params))
-        dev = hm.device
-        h = net._ensure_handle()
-        net._bind(dev)
-        B = hm.shape[0]
+        P, h, in_dtype, hm = _step_setup(net, hm, params)
+        p, dev, B = net.preset, hm.device, hm.shape[0]
         net._act_scratch(B, dev)
         lib = _lib.load()
-        in_dtype = hm.dtype
-        hm = hm.detach().float().contiguous()
         sb, wb = C.c_size_t(), C.c_size_t()
         _lib.check(lib.egotap_lift_train_bytes(h, B, C.byref(sb), C.byref(wb)))
         # the activations' buffer is kept by the module between steps (no 30 GB allocation per step, whose cost depends on what else
@@ -159,13 +253,13 @@ class LiftTrainOneCallFn(torch.autograd.Function):
         for k, b in net.named_buffers():
             if k.endswith("num_batches_tracked"):
                 b.add_(1)
-        ctx.egotap = dict(net=net, P=P, keys=keys, B=B, hm=hm, in_dtype=in_dtype, saved=saved, wb=wb.value, pool=pool)
+        ctx.egotap = dict(net=net, P=P, B=B, hm=hm, in_dtype=in_dtype, saved=saved, wb=wb.value, pool=pool)
         return pose
 
     @staticmethod
     def backward(ctx, dpose):
         S = ctx.egotap
-        net, P, keys, B = S["net"], S["P"], S["keys"], S["B"]
+        net, P, B = S["net"], S["P"], S["B"]
         h = net._ensure_handle()
         lib = _lib.load()
         dev = dpose.device
@@ -195,38 +289,30 @@ class LiftTrainOneCallFn(torch.autograd.Function):
         _publish_grads(P, G, held)
         S["pool"]["busy"] = False
         ctx.egotap = None
-        return (None, _input_grad(dhm, S["in_dtype"])) + (None,) * len(keys)
+        return (None, _input_grad(dhm, S["in_dtype"])) + (None,) * len(P)
 
 
 class LiftTrainFn(torch.autograd.Function):
-    """The same step composed operator by operator from Python (what the one-call ABI does inside the library): kept as the
+    """The fp32-tensor step composed operator by operator from Python (what the one-call ABI does inside the library): kept as the
     reference composition for tests/test_gpu_train_step.py (bit-identical gradients) and for `net.one_call_training = False`."""
 
     @staticmethod
     def forward(ctx, net, hm, *params):
-        p = net.preset
-        keys = _param_order(p)
-        P = dict(zip(keys, params))
-        dev = hm.device
-        h = net._ensure_handle()
+        P, h, in_dtype, hm = _step_setup(net, hm, params)
+        p, dev = net.preset, hm.device
+        net._act_scratch(hm.shape[0], dev)
         # attention: exact fp32 unless the whole step is bf16.  Recomputing P = exp(S - lse) from split-bf16 scores (2^-16 per
         # product) costs ~1e-4 relative in every probability, and gradients that are sums with heavy cancellation (mask_token)
         # then miss the reference-golden gate (2.6 % of the tensor's typical magnitude against 0.5 %): bf16x3 stays fp32-grade.
         prec = "bf16" if getattr(net, "precision", "f32") == "bf16" else "f32"
-        net._bind(dev)
-        net._act_scratch(hm.shape[0], dev)
-        B, D, seq, heads, J, T_, hid = hm.shape[0], p.vit_dim, p.seq, p.vit_heads, p.n_joints_hm, p.tokens, p.hidden
-        M, BT = B * seq, B * T_
+        B, D, seq, heads = hm.shape[0], p.vit_dim, p.seq, p.vit_heads
+        M = B * seq
         lib = _lib.load()
-        st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
         v = "pos_heatmap_encoder.vit."
-        in_dtype = hm.dtype
-        hm = hm.detach().float().contiguous()
-        saved = {"hm": hm, "in_dtype": in_dtype}
         x = torch.empty((M, D), dtype=torch.float32, device=dev)
         _lib.check(lib.egotap_train_patch_fwd(h, T._p(hm), B, T._p(P[v + "embeddings.patch_embeddings.projection.weight"]),
                                               T._p(P[v + "embeddings.patch_embeddings.projection.bias"]), T._p(P[v + "embeddings.mask_token"]),
-                                              T._p(P[v + "embeddings.position_embeddings"]), T._p(x), st()))
+                                              T._p(P[v + "embeddings.position_embeddings"]), T._p(x), T._s()))
         layers = []
         for i in range(p.vit_layers):
             l = f"{v}encoder.layer.{i}."
@@ -234,7 +320,7 @@ class LiftTrainFn(torch.autograd.Function):
             y1, m1, r1 = T.layernorm_fwd(x, P[l + "layernorm_before.weight"], P[l + "layernorm_before.bias"])
             qkv = torch.empty((M, 3 * D), dtype=torch.float32, device=dev)
             _lib.check(lib.egotap_train_qkv_fwd(h, T._p(y1), T._p(P[a + "query.weight"]), T._p(P[a + "query.bias"]), T._p(P[a + "key.weight"]),
-                                                T._p(P[a + "key.bias"]), T._p(P[a + "value.weight"]), T._p(P[a + "value.bias"]), T._p(qkv), M, D, st()))
+                                                T._p(P[a + "key.bias"]), T._p(P[a + "value.weight"]), T._p(P[a + "value.bias"]), T._p(qkv), M, D, T._s()))
             ctx_, lse = T.attention_fwd(qkv, B, seq, heads, prec)
             xm = T.gemm_nt(h, ctx_, P[l + "attention.output.dense.weight"], P[l + "attention.output.dense.bias"], M, D, D, epi=T.TE_BIAS_RES, r=x)
             y2, m2, r2 = T.layernorm_fwd(xm, P[l + "layernorm_after.weight"], P[l + "layernorm_after.bias"])
@@ -244,87 +330,39 @@ class LiftTrainFn(torch.autograd.Function):
             layers.append(dict(x=x, m1=m1, r1=r1, y1=y1, qkv=qkv, ctx=ctx_, lse=lse, xm=xm, m2=m2, r2=r2, y2=y2, z=z, hid=hid_))
             x = xo
         tokens, mf, rf = T.layernorm_fwd(x, P[v + "layernorm.weight"], P[v + "layernorm.bias"])
-        saved.update(layers=layers, xf=x, mf=mf, rf=rf, tokens=tokens)
-
-        def encoder(name, loader, src, k1):
-            acts = []
-            a_in, ld, K = src, loader, k1
-            for j, n_out in enumerate((2048, 512, hid), start=1):
-                f = f"{name}.fc{j}"
-                zz = T.gemm_nt(h, a_in, P[f + ".fc.weight"], P[f + ".fc.bias"], BT, n_out, K, loader=ld, epi=T.TE_BIAS)
-                bufs = dict(net.named_buffers())
-                yy, mean, rstd = T.bn_lrelu_fwd(zz, P[f + ".bn.weight"], P[f + ".bn.bias"], bufs[f + ".bn.running_mean"], bufs[f + ".bn.running_var"])
-                bufs[f + ".bn.num_batches_tracked"].add_(1)
-                acts.append(dict(a_in=a_in, z=zz, y=yy, mean=mean, rstd=rstd, loader=ld, K=K, N=n_out, name=f))
-                a_in, ld, K = yy, T.LD_PLAIN, n_out
-            return acts
-
-        pos_acts = encoder("pos_heatmap_encoder", T.LD_TOKENS, tokens, p.ppd * p.ppd * D)
-        rot_acts = encoder("rot_heatmap_encoder", T.LD_ROT, hm, 2 * p.hm_size * p.hm_size)
-        posz, rotz = pos_acts[-1]["y"], rot_acts[-1]["y"]
-        nb, off = C.c_size_t(), C.c_size_t()
-        _lib.check(lib.egotap_train_pu_saved_bytes(h, B, C.byref(nb), C.byref(off)))
-        pu_saved = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.egotap_train_pu_fwd(h, T._p(posz), T._p(rotz), B, T._p(pu_saved), pu_saved.numel(), st()))
-        hs1 = pu_saved[off.value: off.value + 4 * J * B * p.pu_hidden].view(torch.float32)
-        pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
-        _lib.check(lib.egotap_train_pose_head_fwd(h, T._p(posz), T._p(hs1), B, T._p(pose), st()))
-        saved.update(pos_acts=pos_acts, rot_acts=rot_acts, pu_saved=pu_saved, hs1=hs1, P=P, keys=keys, net=net, B=B)
+        # fc1 gathers its rows itself: the tokens (position encoder), the heatmaps' rotation channels (rotation encoder)
+        pose, saved = _heads_fwd(net, h, P, B, lambda e, w, b: T.gemm_nt(h, (tokens, hm)[e], w, b, B * p.tokens, 2048, w.shape[1],
+                                                                       loader=(T.LD_TOKENS, T.LD_ROT)[e], epi=T.TE_BIAS))
+        saved.update(hm=hm, in_dtype=in_dtype, prec=prec, layers=layers, xf=x, mf=mf, rf=rf, tokens=tokens, P=P, net=net, B=B)
         ctx.egotap = saved
         return pose
 
     @staticmethod
     def backward(ctx, dpose):
         S = ctx.egotap
-        net, P, keys, B = S["net"], S["P"], S["keys"], S["B"]
+        net, P, B, prec = S["net"], S["P"], S["B"], S["prec"]
         p = net.preset
         h = net._ensure_handle()
-        # attention: exact fp32 unless the whole step is bf16.  Recomputing P = exp(S - lse) from split-bf16 scores (2^-16 per
-        # product) costs ~1e-4 relative in every probability, and gradients that are sums with heavy cancellation (mask_token)
-        # then miss the reference-golden gate (2.6 % of the tensor's typical magnitude against 0.5 %): bf16x3 stays fp32-grade.
-        prec = "bf16" if getattr(net, "precision", "f32") == "bf16" else "f32"
         dev = dpose.device
-        D, seq, heads, J, T_, hid, H = p.vit_dim, p.seq, p.vit_heads, p.n_joints_hm, p.tokens, p.hidden, p.pu_hidden
-        M, BT = B * seq, B * T_
+        D, seq, heads = p.vit_dim, p.seq, p.vit_heads
+        M, BT = B * seq, B * p.tokens
         lib = _lib.load()
-        st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        ga, G = _grad_arena(net, P)                            # every entry is fully overwritten below
-        held = _held_grads(P, G)
-        red = net._reducer()
-        red.begin(ga["flat"])
+        ga, G, held, red = _open_backward(net, P)
         dpose = dpose.detach().float().contiguous()
         dhm = torch.empty(S["hm"].shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         v = "pos_heatmap_encoder.vit."
-        posz, rotz, hs1 = S["pos_acts"][-1]["y"], S["rot_acts"][-1]["y"], S["hs1"]
-        # pose head + propagation units
-        dposz, drotz = torch.empty_like(posz), torch.empty_like(rotz)
-        dhs1 = torch.empty(J * B * H, dtype=torch.float32, device=dev)
-        gw = G.get("global_mlp.pose_fcs.0.weight")
-        gb = G.get("global_mlp.pose_fcs.0.bias")
-        _lib.check(lib.egotap_train_pose_head_bwd(h, T._p(posz), T._p(hs1), T._p(dpose), B, T._p(dposz), T._p(dhs1),
-                                                  T._p(G["pose_mlp.pose_fcs.0.weight"]), T._p(G["pose_mlp.pose_fcs.0.bias"]), T._p(gw), T._p(gb), 0, st()))
-        wsb = C.c_size_t()
-        _lib.check(lib.egotap_train_pu_bwd_ws_bytes(h, B, C.byref(wsb)))
-        ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * 14)()
-        c = "skel_sequential_layer.lstm_custom.layers."
-        for i, nme in enumerate(("0.x2f", "0.x2h", "0.b2h", "0.h2h", "1.x2f", "1.x2h", "1.h2h")):
-            ptrs[2 * i] = G[c + nme + ".weight"].data_ptr()
-            ptrs[2 * i + 1] = G[c + nme + ".bias"].data_ptr()
-        _lib.check(lib.egotap_train_pu_bwd(h, T._p(posz), T._p(rotz), B, T._p(S["pu_saved"]), T._p(dhs1), T._p(dposz), T._p(drotz), ptrs, 0,
-                                           T._p(ws), ws.numel(), st()))
-        del ws
+        dposz, drotz = _heads_bwd(net, h, S, G, dpose)
 
-        def encoder_bwd(acts, dy):
-            """returns the gradient w.r.t. the gathered fc1 input rows (None for the rotation encoder: its input is the heatmaps, whose
-            rotation channels it writes into dhm when that is asked for)"""
+        def encoder_bwd(acts, dy, src, loader):
+            """src, loader: fc1's input and how it is gathered.  Returns the gradient w.r.t. the gathered fc1 input rows (None for the
+            rotation encoder: its input is the heatmaps, whose rotation channels it writes into dhm when that is asked for)"""
             for j in (2, 1, 0):
                 a = acts[j]
                 f = a["name"]
                 dz = T.bn_lrelu_bwd(a["z"], a["y"], dy, P[f + ".bn.weight"], a["mean"], a["rstd"], G[f + ".bn.weight"], G[f + ".bn.bias"])
-                T.gemm_tn(h, dz, a["a_in"], G[f + ".fc.weight"], BT, a["N"], a["K"], loader=a["loader"])
+                T.gemm_tn(h, dz, a["a_in"] if j else src, G[f + ".fc.weight"], BT, a["N"], a["K"], loader=loader if j == 0 else T.LD_PLAIN)
                 T.colsum(dz, G[f + ".fc.bias"], BT, a["N"])
-                if j == 0 and a["loader"] == T.LD_ROT:
+                if j == 0 and loader == T.LD_ROT:
                     if dhm is not None:
                         T.gemm_nt(h, dz, T.transpose(P[f + ".fc.weight"]), None, BT, a["K"], a["N"], epi=T.TE_SCATTER_ROT, out=dhm)
                     return None
@@ -332,10 +370,10 @@ class LiftTrainFn(torch.autograd.Function):
                 dy = T.gemm_nt(h, dz, wt, None, BT, a["K"], a["N"], epi=T.TE_NONE)
             return dy
 
-        encoder_bwd(S["rot_acts"], drotz)
-        dA = encoder_bwd(S["pos_acts"], dposz)                            # [B*T, ppd*ppd*D], heatmap-major
+        encoder_bwd(S["rot_acts"], drotz, S["hm"], T.LD_ROT)
+        dA = encoder_bwd(S["pos_acts"], dposz, S["tokens"], T.LD_TOKENS)  # [B*T, ppd*ppd*D], heatmap-major
         dtok = torch.empty((M, D), dtype=torch.float32, device=dev)
-        _lib.check(lib.egotap_train_tokens_scatter(h, T._p(dA), T._p(dtok), B, st()))
+        _lib.check(lib.egotap_train_tokens_scatter(h, T._p(dA), T._p(dtok), B, T._s()))
         del dA
         dx = T.layernorm_bwd(S["xf"], dtok, P[v + "layernorm.weight"], S["mf"], S["rf"], G[v + "layernorm.weight"], G[v + "layernorm.bias"])
         del dtok
@@ -368,31 +406,20 @@ class LiftTrainFn(torch.autograd.Function):
             del dqkv
             dx = T.layernorm_bwd(L["x"], dy1, P[l + "layernorm_before.weight"], L["m1"], L["r1"], G[l + "layernorm_before.weight"],
                                  G[l + "layernorm_before.bias"], dres=dxm)
-        # patch embedding: weight, position embeddings, bias / mask token
-        T.gemm_tn(h, dx, S["hm"], G[v + "embeddings.patch_embeddings.projection.weight"], M, D, 256, loader=T.LD_PATCH)
-        dpos = G[v + "embeddings.position_embeddings"]
-        T.colsum(dx, dpos, B, seq * D)                                    # sum over the batch: dx viewed as [B, seq*D]
-        _lib.check(lib.egotap_train_patch_split(h, T._p(dpos), T._p(G[v + "embeddings.patch_embeddings.projection.bias"]),
-                                                T._p(G[v + "embeddings.mask_token"]), 0, st()))
-        nb = len(ga["bounds"])
-        red.bucket_ready(ga["bounds"][nb - 3], ga["bounds"][nb - 2])
-        red.bucket_ready(ga["bounds"][nb - 2], ga["bounds"][nb - 1])
+        _patch_bwd(net, h, S, G, dx, red, ga)
         if dhm is not None:               # the heatmaps' position channels, under the last bucket's all-reduce
             pw = P[v + "embeddings.patch_embeddings.projection.weight"].detach().reshape(D, 256)
             T.gemm_nt(h, dx, T.transpose(pw), None, M, 256, D, epi=T.TE_SCATTER_PATCH, out=dhm)
-        red.finish()
-        _publish_grads(P, G, held)
-        ctx.egotap = None
-        return (None, _input_grad(dhm, S["in_dtype"])) + (None,) * len(keys)
+        return _close_backward(ctx, red, P, G, held, dhm)
 
 
 class LiftTrainBf16Fn(torch.autograd.Function):
-    """The training step of the head in the bf16-STORAGE mode (EGOTAP_PREC_BF16; BASELINE configs 3-5, the wrapper's --use_amp):
-    the ViT's activations live in HBM as bf16 (written by their producers: LayerNorm, the GEMM epilogues, attention), the fp32 master
-    weights are rounded once per step (bf16 copy + transposed bf16 copy for the input-gradient GEMMs), every large product reads bf16
-    operands through the LDS DMA (csrc/gemm_bf16s.h, gemm_tn_bf16s.h) with fp32 accumulation; the residual stream, LayerNorm / BatchNorm
-    statistics, the small FC layers, the propagation units, the pose head, all gradients and the optimizer state stay fp32.
-    Same autograd contract as LiftTrainFn (model/egotap_autoencoder_model.py:299-323 drives it unchanged)."""
+    """The training step of the head in the bf16-STORAGE mode (EGOTAP_PREC_BF16; BASELINE configs 3-5, the wrapper's --use_amp),
+    composed operator by operator: the ViT's activations live in HBM as bf16 (written by their producers: LayerNorm, the GEMM epilogues,
+    attention), the fp32 master weights are rounded once per step (bf16 copy + transposed bf16 copy for the input-gradient GEMMs), every
+    large product reads bf16 operands through the LDS DMA (csrc/gemm_bf16s.h, gemm_tn_bf16s.h) with fp32 accumulation; the residual
+    stream, LayerNorm / BatchNorm statistics, the small FC layers, the propagation units, the pose head, all gradients and the optimizer
+    state stay fp32.  Same autograd contract as LiftTrainFn (model/egotap_autoencoder_model.py:299-323 drives it unchanged)."""
 
     @staticmethod
     def _prep(net, P, dev):
@@ -423,22 +450,14 @@ class LiftTrainBf16Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net, hm, *params):
         from . import bf16s as S
-        p = net.preset
-        keys = _param_order(p)
-        P = dict(zip(keys, params))
-        dev = hm.device
-        h = net._ensure_handle()
-        net._bind(dev)
-        B, D, seq, heads, J, T_, hid = hm.shape[0], p.vit_dim, p.seq, p.vit_heads, p.n_joints_hm, p.tokens, p.hidden
-        M, BT = B * seq, B * T_
+        P, h, in_dtype, hm = _step_setup(net, hm, params)
+        p, dev = net.preset, hm.device
+        B, D, seq, heads = hm.shape[0], p.vit_dim, p.seq, p.vit_heads
+        M = B * seq
         lib = _lib.load()
-        st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
         v = "pos_heatmap_encoder.vit."
-        in_dtype = hm.dtype
-        hm = hm.detach().float().contiguous()
         W = LiftTrainBf16Fn._prep(net, P, dev)
         hm_b = S.from_f32(hm)                                       # bf16 copy of the input heatmaps: the rotation encoder's fc1 operand
-        saved = {"hm": hm, "hm_b": hm_b, "in_dtype": in_dtype}
         x = torch.empty((M, D), dtype=torch.float32, device=dev)
         # patch embedding on the bf16-storage GEMM: bf16 heatmaps, a per-step bf16 copy of the projection weight (as the one-call ABI does)
         pw = P[v + "embeddings.patch_embeddings.projection.weight"]
@@ -446,7 +465,7 @@ class LiftTrainBf16Fn(torch.autograd.Function):
         S.prep_weight(pw.detach().reshape(D, 256), pwb)
         _lib.check(lib.egotap_bf16_patch_fwd(h, T._p(hm_b), T._p(pwb), T._p(P[v + "embeddings.patch_embeddings.projection.bias"]),
                                              T._p(P[v + "embeddings.mask_token"]), T._p(P[v + "embeddings.position_embeddings"]),
-                                             T._p(S.zero_page(dev)), T._p(x), B, st()))
+                                             T._p(S.zero_page(dev)), T._p(x), B, T._s()))
         layers = []
         for i in range(p.vit_layers):
             l = f"{v}encoder.layer.{i}."
@@ -463,37 +482,9 @@ class LiftTrainBf16Fn(torch.autograd.Function):
             layers.append(dict(x=x, m1=m1, r1=r1, y1=y1, qkv=qkv, ctx=ctx_, lse=lse, xm=xm, m2=m2, r2=r2, y2=y2, z=z, hid=hid_))
             x = xo
         tokens, mf, rf = S.layernorm_fwd(x, P[v + "layernorm.weight"], P[v + "layernorm.bias"])
-        saved.update(layers=layers, xf=x, mf=mf, rf=rf, tokens=tokens)
-        bufs = dict(net.named_buffers())
-
-        def encoder(name, which, src, wb):
-            acts = []
-            a_in = None
-            for j, n_out in enumerate((2048, 512, hid), start=1):
-                f = f"{name}.fc{j}"
-                if j == 1:
-                    zz = S.fc1_fwd(h, which, src, wb, P[f + ".fc.bias"], B, T_)
-                    K = wb.shape[1]
-                else:
-                    K = a_in.shape[1]
-                    zz = T.gemm_nt(h, a_in, P[f + ".fc.weight"], P[f + ".fc.bias"], BT, n_out, K, epi=T.TE_BIAS)
-                yy, mean, rstd = T.bn_lrelu_fwd(zz, P[f + ".bn.weight"], P[f + ".bn.bias"], bufs[f + ".bn.running_mean"], bufs[f + ".bn.running_var"])
-                bufs[f + ".bn.num_batches_tracked"].add_(1)
-                acts.append(dict(a_in=a_in, z=zz, y=yy, mean=mean, rstd=rstd, K=K, N=n_out, name=f))
-                a_in = yy
-            return acts
-
-        pos_acts = encoder("pos_heatmap_encoder", 0, tokens, W["fc1p"])
-        rot_acts = encoder("rot_heatmap_encoder", 1, hm_b, W["fc1r"])
-        posz, rotz = pos_acts[-1]["y"], rot_acts[-1]["y"]
-        nb, off = C.c_size_t(), C.c_size_t()
-        _lib.check(lib.egotap_train_pu_saved_bytes(h, B, C.byref(nb), C.byref(off)))
-        pu_saved = torch.empty(nb.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.egotap_train_pu_fwd(h, T._p(posz), T._p(rotz), B, T._p(pu_saved), pu_saved.numel(), st()))
-        hs1 = pu_saved[off.value: off.value + 4 * J * B * p.pu_hidden].view(torch.float32)
-        pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
-        _lib.check(lib.egotap_train_pose_head_fwd(h, T._p(posz), T._p(hs1), B, T._p(pose), st()))
-        saved.update(pos_acts=pos_acts, rot_acts=rot_acts, pu_saved=pu_saved, hs1=hs1, P=P, keys=keys, net=net, B=B, W=W)
+        # fc1 on the bf16 kernel: bf16 tokens / heatmaps and the step's bf16 weight copies
+        pose, saved = _heads_fwd(net, h, P, B, lambda e, w, b: S.fc1_fwd(h, e, (tokens, hm_b)[e], (W["fc1p"], W["fc1r"])[e], b, B, p.tokens))
+        saved.update(hm=hm, hm_b=hm_b, in_dtype=in_dtype, layers=layers, xf=x, mf=mf, rf=rf, tokens=tokens, P=P, net=net, B=B, W=W)
         ctx.egotap = saved
         return pose
 
@@ -501,44 +492,22 @@ class LiftTrainBf16Fn(torch.autograd.Function):
     def backward(ctx, dpose):
         from . import bf16s as S
         Sv = ctx.egotap
-        net, P, keys, B, W = Sv["net"], Sv["P"], Sv["keys"], Sv["B"], Sv["W"]
+        net, P, B, W = Sv["net"], Sv["P"], Sv["B"], Sv["W"]
         p = net.preset
         h = net._ensure_handle()
         dev = dpose.device
-        D, seq, heads, J, T_, hid, H = p.vit_dim, p.seq, p.vit_heads, p.n_joints_hm, p.tokens, p.hidden, p.pu_hidden
-        M, BT = B * seq, B * T_
-        lib = _lib.load()
-        st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)      # noqa: E731
-        ga, G = _grad_arena(net, P)                            # every entry is fully overwritten below
-        held = _held_grads(P, G)
-        red = net._reducer()
-        red.begin(ga["flat"])
+        D, seq, heads = p.vit_dim, p.seq, p.vit_heads
+        BT = B * p.tokens
+        ga, G, held, red = _open_backward(net, P)
         dpose = dpose.detach().float().contiguous()
         dhm = torch.empty(Sv["hm"].shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         v = "pos_heatmap_encoder.vit."
-        posz, rotz, hs1 = Sv["pos_acts"][-1]["y"], Sv["rot_acts"][-1]["y"], Sv["hs1"]
         # net._stage_trace = {} (tests): every intermediate of this backward is kept under a name, together with the forward's saved
         # activations, so that each stage can be checked against its own inputs (tests/test_gpu_bf16_stages.py)
         tr = getattr(net, "_stage_trace", None)
         if tr is not None:
             tr.update(saved=Sv, W=W, dpose=dpose)
-        # pose head + propagation units (fp32, as in every mode)
-        dposz, drotz = torch.empty_like(posz), torch.empty_like(rotz)
-        dhs1 = torch.empty(J * B * H, dtype=torch.float32, device=dev)
-        gw, gb = G.get("global_mlp.pose_fcs.0.weight"), G.get("global_mlp.pose_fcs.0.bias")
-        _lib.check(lib.egotap_train_pose_head_bwd(h, T._p(posz), T._p(hs1), T._p(dpose), B, T._p(dposz), T._p(dhs1),
-                                                  T._p(G["pose_mlp.pose_fcs.0.weight"]), T._p(G["pose_mlp.pose_fcs.0.bias"]), T._p(gw), T._p(gb), 0, st()))
-        wsb = C.c_size_t()
-        _lib.check(lib.egotap_train_pu_bwd_ws_bytes(h, B, C.byref(wsb)))
-        ws = torch.empty(wsb.value, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * 14)()
-        c = "skel_sequential_layer.lstm_custom.layers."
-        for i, nme in enumerate(("0.x2f", "0.x2h", "0.b2h", "0.h2h", "1.x2f", "1.x2h", "1.h2h")):
-            ptrs[2 * i] = G[c + nme + ".weight"].data_ptr()
-            ptrs[2 * i + 1] = G[c + nme + ".bias"].data_ptr()
-        _lib.check(lib.egotap_train_pu_bwd(h, T._p(posz), T._p(rotz), B, T._p(Sv["pu_saved"]), T._p(dhs1), T._p(dposz), T._p(drotz), ptrs, 0,
-                                           T._p(ws), ws.numel(), st()))
-        del ws
+        dposz, drotz = _heads_bwd(net, h, Sv, G, dpose)
 
         def encoder_bwd(acts, dy, which, src, wt):
             """fc3, fc2 in fp32 (small); fc1 on the bf16 kernels.  Returns the token gradient (position encoder) or None"""
@@ -614,24 +583,13 @@ class LiftTrainBf16Fn(torch.autograd.Function):
             if tr is not None:
                 t_.update(dx_out=dx, dxb_out=dxb)
             del dy1, dxm
-        # patch embedding (fp32 operands: the input heatmaps): weight, position embeddings, bias / mask token
-        T.gemm_tn(h, dx, Sv["hm"], G[v + "embeddings.patch_embeddings.projection.weight"], M, D, 256, loader=T.LD_PATCH)
-        dpos = G[v + "embeddings.position_embeddings"]
-        T.colsum(dx, dpos, B, seq * D)
-        _lib.check(lib.egotap_train_patch_split(h, T._p(dpos), T._p(G[v + "embeddings.patch_embeddings.projection.bias"]),
-                                                T._p(G[v + "embeddings.mask_token"]), 0, st()))
-        nb = len(ga["bounds"])
-        red.bucket_ready(ga["bounds"][nb - 3], ga["bounds"][nb - 2])
-        red.bucket_ready(ga["bounds"][nb - 2], ga["bounds"][nb - 1])
+        _patch_bwd(net, h, Sv, G, dx, red, ga)
         if dhm is not None:               # the heatmaps' position channels (bf16 dx of layer 0, bf16 projection.weight^T)
             pw = P[v + "embeddings.patch_embeddings.projection.weight"].detach().reshape(D, 256)
             pwt = torch.empty((256, D), dtype=torch.bfloat16, device=dev)
             S.prep_weight(pw, torch.empty((D, 256), dtype=torch.bfloat16, device=dev), pwt)
             S.patch_dgrad(h, dxb, pwt, dhm, B)
-        red.finish()
-        _publish_grads(P, G, held)
-        ctx.egotap = None
-        return (None, _input_grad(dhm, Sv["in_dtype"])) + (None,) * len(keys)
+        return _close_backward(ctx, red, P, G, held, dhm)
 
 
 class PoseLossFn(torch.autograd.Function):
