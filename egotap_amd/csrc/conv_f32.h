@@ -419,6 +419,215 @@ static hipError_t conv_f32_launch(ConvArgs a, hipStream_t stream, int num_cu = 2
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------- the same convolution at any map width
+// conv_f32_kernel tiles whole power-of-two rows.  conv_f32_any_kernel serves every other square width W (heatmap sides 16 ... 112 that are
+// not 64: stage maps of 2 x 2 up to 112 x 112) with the same ConvArgs contract and the same exact-fp32 MFMA (v_mfma_f32_32x32x2_f32):
+// * Pixel tile = 256 (or 64) consecutive pixels of the flattened (image, y, x) output, whatever the row length: no pixel work is wasted on
+//   padding and a tile may span rows and images.
+// * K = Cin * TAPS is walked in slabs of BK = 32 consecutive k = (ci, ky, kx) regardless of channel boundaries (Cin needs no multiple of
+//   anything; Cin * TAPS % 4 == 0 for the float4 weight rows, as conv_f32_launch requires).
+// * B operand: each slab is gathered from the input into LDS as a [k][pixel] image (im2col of that slab only).  A thread owns one pixel of
+//   the tile and every second (64-pixel tiles: fourth) k of the slab; the 3x3 taps that fall into the zero padding, k past K and pixels past the batch are zeros.
+//   The input is read 9x from L1/L2 instead of once per slab, the price of row lengths that are not multiples of the staged-row layout.
+// * A operand, fragments and accumulator layout as conv_f32_kernel; the next slab is prefetched into registers.  One workgroup accumulates the whole K of
+//   its outputs in a fixed order (slab, then k inside the slab, lane half 0 before 1): no split, no atomics, every output is written once,
+//   so a frame's result does not depend on the batch it arrives in, bit for bit.
+// * Tile shape: 128 (or 64) channels x 256 pixels, and 64 x 64 for grids that would leave CUs idle (small maps, few frames).  The k order
+//   of an output does not depend on the tile it lands in, so the choice changes no bit.
+template <int TAPS_, int STRIDE_, int CO_T_, int PX_T_ = 256>
+struct ConvAnyCfg {
+    static constexpr int TAPS = TAPS_, STRIDE = STRIDE_, CO_T = CO_T_, PX_T = PX_T_;
+    static constexpr int KS = TAPS == 9 ? 3 : 1, PAD = (KS - 1) / 2;
+    static constexpr int BK = 32, KH = BK / 2, NT = KH / 4, LDK = BK + 4;
+    static constexpr int WCO = 2, WPX = PX_T >= 256 ? 4 : PX_T / 32, THREADS = 64 * WCO * WPX;
+    static constexpr int TCO = CO_T / WCO / 32, TPX = PX_T / WPX / 32;
+    static constexpr int A_FLOATS = CO_T * LDK, B_FLOATS = BK * PX_T, STAGE = A_FLOATS + B_FLOATS;
+    static constexpr int LDS_BYTES = STAGE * 4;          // one LDS stage (51 KB at 128 x 256): two workgroups per CU ...
+    static constexpr int MIN_WAVES = TAPS == 9 ? THREADS / 128 : 1;     // ... and registers for them (the 1x1 forms would spill at 128 VGPRs)
+    static constexpr int A_V4 = CO_T * BK / 4, A_IT = (A_V4 + THREADS - 1) / THREADS;
+    static constexpr int KROWS = THREADS / PX_T, B_IT = BK / KROWS;      // k rows gathered per thread and slab
+    static_assert(TCO >= 1 && CO_T % (32 * WCO) == 0 && PX_T % (32 * WPX) == 0, "wave tile must be 32x32 MFMA tiles");
+    static_assert(THREADS % PX_T == 0 && BK % KROWS == 0, "gather: whole pixel rows of the tile per k");
+    static_assert(TAPS == 1 || KROWS < TAPS, "gather: one tap wrap per step");
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+};
+
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::THREADS, Cfg::MIN_WAVES) void conv_f32_any_kernel(ConvArgs a, int W) {
+    constexpr int TAPS = Cfg::TAPS, STRIDE = Cfg::STRIDE, KS = Cfg::KS, PAD = Cfg::PAD, CO_T = Cfg::CO_T, PX_T = Cfg::PX_T;
+    constexpr int BK = Cfg::BK, KH = Cfg::KH, NT = Cfg::NT, LDK = Cfg::LDK, TCO = Cfg::TCO, TPX = Cfg::TPX, THREADS = Cfg::THREADS;
+    constexpr int A_FLOATS = Cfg::A_FLOATS, KROWS = Cfg::KROWS;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+
+    int tpx, tco;
+    xcd_tile(blockIdx.x, gridDim.x, a.tiles_px, a.tiles_co, 32, tpx, tco);
+    const int co0 = tco * CO_T;
+    const long px0 = (long)tpx * PX_T;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wco = wid / Cfg::WPX, wpx = wid % Cfg::WPX;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int HW = W * W, WIN = W * STRIDE;
+    const long npx = (long)a.Nimg * HW;
+    const int ch_in = WIN * WIN;
+    const int K = a.Cin * TAPS;
+
+    // the gathering thread's pixel: image base, top-left tap, and which of the KS x KS taps lie inside the input
+    const int gp = tid % PX_T, gk0 = tid / PX_T;
+    const float* gbase = a.in;
+    int gorg = 0;
+    unsigned gmask = 0;
+    {
+        const long P = px0 + gp;
+        if (P < npx) {
+            const int n = (int)(P / HW), rem = (int)(P - (long)n * HW);
+            const int oy = rem / W, ox = rem - oy * W;
+            const int iy0 = oy * STRIDE - PAD, ix0 = ox * STRIDE - PAD;
+            gbase = a.in + (long)n * a.in_istride;
+            gorg = iy0 * WIN + ix0;
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t) {
+                const int iy = iy0 + t / KS, ix = ix0 + t % KS;
+                if (iy >= 0 && iy < WIN && ix >= 0 && ix < WIN) gmask |= 1u << t;
+            }
+        }
+    }
+
+    f32x4 pa[Cfg::A_IT];
+    float pb[Cfg::B_IT];
+    auto gload = [&](int slab) {
+        const int kb = slab * BK;
+#pragma unroll
+        for (int it = 0; it < Cfg::A_IT; ++it) {
+            const int idx = tid + it * THREADS;
+            const int row = idx / (BK / 4), f4 = idx - row * (BK / 4);
+            const int koff = kb + f4 * 4;
+            const bool ok = idx < Cfg::A_V4 && co0 + row < a.Cout && koff < K;
+            pa[it] = ok ? *(const f32x4*)(a.w + (long)(co0 + row) * K + koff) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        // k = kb + gk0 + KROWS * it: channel ci, tap t, stepped without a division per element
+        int ci = (kb + gk0) / TAPS, t = (kb + gk0) - ci * TAPS;
+#pragma unroll
+        for (int it = 0; it < Cfg::B_IT; ++it) {
+            const bool ok = ci < a.Cin && ((gmask >> t) & 1u);
+            pb[it] = ok ? gbase[(long)ci * ch_in + gorg + (t / KS) * WIN + t % KS] : 0.f;
+            if constexpr (TAPS == 1) {
+                ci += KROWS;
+            } else {
+                t += KROWS;
+                if (t >= TAPS) { t -= TAPS; ++ci; }
+            }
+        }
+    };
+    auto lstore = [&]() {
+        float* As = smem;
+        float* Bs = smem + A_FLOATS;
+#pragma unroll
+        for (int it = 0; it < Cfg::A_IT; ++it) {
+            const int idx = tid + it * THREADS;
+            const int row = idx / (BK / 4), f4 = idx - row * (BK / 4);
+            if (idx < Cfg::A_V4) *(f32x4*)(As + row * LDK + f4 * 4) = pa[it];
+        }
+#pragma unroll
+        for (int it = 0; it < Cfg::B_IT; ++it) Bs[(gk0 + KROWS * it) * PX_T + gp] = pb[it];
+    };
+
+    const int a_off = (wco * TCO * 32 + l31) * LDK + lh * KH;
+    const int b_off = lh * KH * PX_T + wpx * TPX * 32 + l31;
+
+    f32x16 acc[TCO][TPX];
+#pragma unroll
+    for (int i = 0; i < TCO; ++i)
+#pragma unroll
+        for (int j = 0; j < TPX; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // one LDS stage, the next slab's loads in flight in registers behind this slab's MFMAs (the other workgroup on the CU fills the barriers)
+    const int nslab = (K + BK - 1) / BK;
+    gload(0);
+    for (int s = 0; s < nslab; ++s) {
+        lstore();
+        __syncthreads();
+        if (s + 1 < nslab) gload(s + 1);
+        const float* As = smem + a_off;
+        const float* Bs = smem + A_FLOATS + b_off;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            f32x4 af[TCO];
+#pragma unroll
+            for (int i = 0; i < TCO; ++i) af[i] = *(const f32x4*)(As + i * 32 * LDK + 4 * t);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                float bv[TPX];
+#pragma unroll
+                for (int j = 0; j < TPX; ++j) bv[j] = Bs[(4 * t + u) * PX_T + j * 32];
+#pragma unroll
+                for (int i = 0; i < TCO; ++i)
+#pragma unroll
+                    for (int j = 0; j < TPX; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][u], bv[j], acc[i][j], 0, 0, 0);
+            }
+        }
+        __syncthreads();      // every wave is done with the stage before the next slab lands in it
+    }
+
+    // epilogue (same expressions as conv_f32_kernel's): accumulator register r of lane l = D[co = (r&3) + 8*(r>>2) + 4*(l>>5)][pixel l&31]
+    long ooff[TPX], roff[TPX];
+    bool pok[TPX];
+#pragma unroll
+    for (int j = 0; j < TPX; ++j) {
+        const long P = px0 + (wpx * TPX + j) * 32 + l31;
+        pok[j] = P < npx;
+        const long n = pok[j] ? P / HW : 0;
+        const long rem = P - n * HW;
+        ooff[j] = n * a.out_istride + rem;
+        roff[j] = n * a.res_istride + rem;
+    }
+#pragma unroll
+    for (int i = 0; i < TCO; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = co0 + (wco * TCO + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            if (co >= a.Cout) continue;
+            float sc = 1.f, sh;
+            if (a.gamma) {
+                sc = a.gamma[co] / sqrtf(a.var[co] + 1e-5f);
+                sh = a.beta[co] - a.mean[co] * sc;
+            } else {
+                sh = a.bias[co];
+            }
+#pragma unroll
+            for (int j = 0; j < TPX; ++j) {
+                if (!pok[j]) continue;
+                float v = acc[i][j][r] * sc + sh;
+                if (a.res) v += a.res[roff[j] + (long)co * HW];
+                v = a.relu ? fmaxf(v, 0.f) : v;
+                a.out[ooff[j] + (long)co * HW] = v;
+            }
+        }
+}
+
+template <class Cfg>
+static hipError_t conv_f32_any_launch(ConvArgs a, int W, hipStream_t stream) {
+    if (a.Nimg <= 0) return hipSuccess;
+    if (W < 1 || a.Cin <= 0 || a.Cout <= 0 || (a.Cin * Cfg::TAPS) % 4 != 0 || ((uintptr_t)a.w & 15) != 0) return hipErrorInvalidValue;
+    auto kern = conv_f32_any_kernel<Cfg>;
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        attr_done = true;
+    }
+    const long px = (long)a.Nimg * W * W;
+    const long tiles_px = (px + Cfg::PX_T - 1) / Cfg::PX_T;
+    a.tiles_co = (a.Cout + Cfg::CO_T - 1) / Cfg::CO_T;
+    if (tiles_px * a.tiles_co >= (1L << 31)) return hipErrorInvalidValue;
+    a.tiles_px = (int)tiles_px;
+    a.splits = 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a.tiles_co * tiles_px)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, a, W);
+    return hipGetLastError();
+}
+
 // ----------------------------------------------------------------------------- ResNet stem and the glue kernels
 // conv 7x7 stride 2 pad 3 (3 -> 64) + BatchNorm(eval) + ReLU, torchvision resnet18.conv1/bn1/relu via
 // net_architecture.py:69.  K = 147 is too ragged for the MFMA tiling and only 1 % of the FLOPs: direct VALU

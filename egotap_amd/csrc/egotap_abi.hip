@@ -1250,6 +1250,24 @@ static hipError_t conv(Handle* h, const char* role, const ConvArgs& a, hipStream
     return conv_f32_launch<Cfg>(b, s, device_cu_count());
 }
 
+// any other output width (conv_f32_any_kernel: pixel tiles over the flattened (image, y, x) map)
+template <int TAPS, int STRIDE, int CO_T, int PX_T>
+static hipError_t conv_gen(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
+    using Cfg = ConvAnyCfg<TAPS, STRIDE, CO_T, PX_T>;
+    static const std::string kname = std::string("conv_f32_any_kernel<") + (TAPS == 9 ? "3x3" : "1x1") + ",s" + std::to_string(STRIDE) +
+                                     ",co" + std::to_string(CO_T) + ",px" + std::to_string(PX_T) + ">";
+    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * TAPS * (double)a.Nimg * wout * wout);
+    return conv_f32_any_launch<Cfg>(a, wout, s);
+}
+// tile shape by grid size: 128 x 256 (64 x 256 for Cout <= 64) while that fills the CUs, then 64 x 256, then 64 x 64 (same bits: same k order)
+template <int TAPS, int STRIDE>
+static hipError_t conv_gen_co(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
+    const long t256 = ((long)a.Nimg * wout * wout + 255) / 256, cus = device_cu_count();
+    if (a.Cout > 64 && t256 * ((a.Cout + 127) / 128) >= cus) return conv_gen<TAPS, STRIDE, 128, 256>(h, role, wout, a, s);
+    if (t256 * ((a.Cout + 63) / 64) >= cus) return conv_gen<TAPS, STRIDE, 64, 256>(h, role, wout, a, s);
+    return conv_gen<TAPS, STRIDE, 64, 64>(h, role, wout, a, s);
+}
+
 template <class Cfg>
 static hipError_t conv_bf(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
     static const std::string kname = std::string("conv_bf16_kernel<3x3,s1,W") + std::to_string(Cfg::W) + (Cfg::NP == 3 ? ",bf16x3>" : ",bf16>");
@@ -1257,7 +1275,8 @@ static hipError_t conv_bf(Handle* h, const char* role, const ConvArgs& a, hipStr
     return conv_bf16_launch<Cfg>(a, h->conv_pack, s);
 }
 
-// dispatch on (taps, stride, output width); wout in {128, 64, 32, 16, 8}
+// dispatch on (taps, stride, output width): the power-of-two instantiations at wout in {128, 64, 32, 16, 8} (where they exist), every
+// other width >= 1 on conv_f32_any_kernel (exact fp32 in every precision mode)
 static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, int wout, const ConvArgs& a, hipStream_t s) {
     // opt-in modes: 3x3 stride-1 convs with a multiple of 128 output channels at widths 64 / 32 / 16 run on the bf16 matrix cores
     if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout >= 128) {
@@ -1296,6 +1315,11 @@ static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, in
         if (wout == 16) return conv<C1s2_16>(h, role, a, s);
         if (wout == 8) return conv<C1s2_8>(h, role, a, s);
     }
+    if (wout < 1) return hipErrorInvalidValue;
+    if (taps == 9 && stride == 1) return conv_gen_co<9, 1>(h, role, wout, a, s);
+    if (taps == 9 && stride == 2) return conv_gen_co<9, 2>(h, role, wout, a, s);
+    if (taps == 1 && stride == 1) return conv_gen_co<1, 1>(h, role, wout, a, s);
+    if (taps == 1 && stride == 2) return conv_gen_co<1, 2>(h, role, wout, a, s);
     return hipErrorInvalidValue;
 }
 
@@ -1672,7 +1696,10 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
     EGO_CHECK(B > 0 && left && right && out && ws, "egotap_hm_forward: null argument or negative batch");
     EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)out) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "pointers must be 16-byte (ws: 256-byte) aligned");
     const int S0 = h->cfg.hm_size * 4, s64 = S0 / 4, s32 = S0 / 8, s16 = S0 / 16, s8 = S0 / 32;
-    EGO_CHECK(s64 == 64 || s64 == 128, "this build instantiates the conv kernels for 256x256 and 512x512 RGB (64x64 / 128x128 heatmaps)");
+    // the bf16 channels-last path and the bf16 matrix-core convolutions exist at 64 / 128 only: every other side (any multiple of 16)
+    // runs the exact-fp32 path in every precision mode -- the power-of-two conv instantiations where they exist, conv_f32_any_kernel elsewhere
+    const bool built = s64 == 64 || s64 == 128;
+    const bool exact = h->precision == EGOTAP_PREC_F32 || !built;
     int rc = hm_resolve(h, net);
     if (rc != EGOTAP_OK) return rc;
     const HmWs w = hm_ws(h, B);
@@ -1682,10 +1709,10 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
     }
     const HmParams& p = h->hp[net];
     EGO_CHECK(out_image_stride >= (int64_t)p.n_out * s64 * s64, "out_image_stride smaller than the output image");
-    h->conv_pack = (__bf16*)((char*)ws + w.WPACK);
+    h->conv_pack = built ? (__bf16*)((char*)ws + w.WPACK) : nullptr;      // (no conv_pack: conv_any takes no bf16 kernel)
     // [r4] exact-fp32 mode: the two weight-pack regions at the end of the workspace are unused -> scratch of the serving-batch channel split (conv_f32.h)
     struct PartGuard { Handle* h; ~PartGuard() { h->conv_part = nullptr; h->conv_part_floats = 0; } } part_guard{h};
-    if (h->precision == EGOTAP_PREC_F32) {
+    if (exact) {
         h->conv_part = (float*)((char*)ws + w.WPACK);
         h->conv_part_floats = (w.total - w.WPACK) / 4;
     }
@@ -1699,10 +1726,10 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
     // [r3] ... bf16 mode: stem, BatchNorm, ReLU AND the max-pool in one kernel on the bf16 matrix cores (stem_bf16s.h): the 128 x 128 x 64
     // map never reaches HBM (round 2's two-kernel form -- fp32-MFMA stem writing bf16 channels-last, then a channels-last max-pool: 2.35 ms
     // against 0.66 per 512 images -- was retired in round 4).
-    const bool fused_stem = h->precision == EGOTAP_PREC_BF16;
+    const bool fused_stem = !exact && h->precision == EGOTAP_PREC_BF16;
     if (!fused_stem)
         EGO_HIP(stem_conv7_launch(left, right, p.stem_w, p.stem_bn.g, p.stem_bn.b, p.stem_bn.m, p.stem_bn.v, F(w.L0), S0, N2, device_cu_count(), s));
-    if (h->precision == EGOTAP_PREC_BF16) {
+    if (fused_stem) {
         // bf16 mode: everything after the stem on bf16 channels-last activations, every convolution on the bf16-storage GEMM
         // (conv_bf16s.h).  Buffers live in the fp32 path's slots (each at most half as large).
         auto Hb = [&](size_t off) { return (__bf16*)(base + off); };
@@ -1874,7 +1901,8 @@ extern "C" int egotap_hm_forward_bnbatch(egotap_handle h, int net, const float* 
     EGO_CHECK(left && right && out && ws, "egotap_hm_forward_bnbatch: null argument");
     EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)out) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "pointers must be 16-byte (ws: 256-byte) aligned");
     const int S0 = h->cfg.hm_size * 4, s64 = S0 / 4, s32 = S0 / 8, s16 = S0 / 16, s8 = S0 / 32;
-    EGO_CHECK(s64 == 64 || s64 == 128, "this build instantiates the conv kernels for 256x256 and 512x512 RGB (64x64 / 128x128 heatmaps)");
+    EGO_CHECK(s64 == 64 || s64 == 128, "egotap_hm_forward_bnbatch runs at heatmap sides 64 and 128 only (256x256 / 512x512 RGB); this handle's side is %d "
+              "(the eval-mode egotap_hm_forward runs at every multiple of 16)", s64);
     if (chunk <= 0 || chunk > B) chunk = B;
     int rc = hm_resolve(h, net);
     if (rc != EGOTAP_OK) return rc;

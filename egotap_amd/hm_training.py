@@ -293,6 +293,8 @@ class HmTrainFn(torch.autograd.Function):
 
 def hm_train_forward(net, left, right):
     """differentiable train-mode forward of HeatMap_UnrealEgo_Shared: [B,3,S0,S0] x 2 -> [B, 2n, S0/4, S0/4]"""
+    from . import spec as _spec
+    _spec.hm_check_batch_stats_side(net.hm_size, "the train-mode estimator forward (batch-statistics BatchNorm, stage-1 training)")
     params = [p for _, p in _param_items(net)]
     net._bind(left.device)
     if getattr(net, "precision", "f32") != "f32":          # bf16 modes: scratch for the repacked conv weights (kept on the module)
@@ -307,6 +309,8 @@ def hm_train_forward(net, left, right):
 def hm_train_forward_nograd(net, left, right):
     """train-mode forward (batch-statistics BatchNorm2d per eye, running stats updated) with no graph: what the reference's FROZEN
     estimators compute while the lifting head trains under train.py:91 model.train() (egotap_autoencoder_model.py:179)"""
+    from . import spec as _spec
+    _spec.hm_check_batch_stats_side(net.hm_size, "hm_train_forward_nograd (batch-statistics BatchNorm of a frozen estimator)")
     was = net.training
     net.train()
     try:

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import networks
+from . import spec as _spec
 
 
 def create_model(opt):
@@ -166,6 +167,10 @@ class EgoTAPAutoEncoderModel(nn.Module):
             B = left.shape[0]
             cat = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=left.device)
             bn_batch = self._estimator_bn_modes()
+            for net, batch_stats in ((self.net_HeatMap, bn_batch[0]), (self.net_RotHeatMap, bn_batch[1])):
+                if batch_stats and not getattr(net, "bottleneck", False):      # refuse before either estimator launches anything
+                    _spec.hm_check_batch_stats_side(net.hm_size, "a frozen estimator in train mode (batch-statistics BatchNorm; "
+                                                    "model.eval() / set_eval_mode() or --frozen_heatmap_bn_eval select the eval forward)")
             # position net: channels [0, 2J) (left | right), limb net: [2J, 6J) (left cos, sin | right cos, sin)
             for net, c0, cn, batch_stats in ((self.net_HeatMap, 0, 2 * J, bn_batch[0]), (self.net_RotHeatMap, 2 * J, 4 * J, bn_batch[1])):
                 if batch_stats and getattr(net, "bottleneck", False):
@@ -446,6 +451,7 @@ class HeatmapSharedModel(nn.Module):
     def optimize_parameters(self):
         if not self.isTrain:
             raise RuntimeError("optimize_parameters() needs a model created with opt.isTrain = True")
+        _spec.hm_check_batch_stats_side(self.net_HeatMap.hm_size, "stage-1 training (optimize_parameters)")
         self.net_HeatMap.train()
         self.optimizer_HeatMap.zero_grad()
         self.forward()

@@ -316,7 +316,8 @@ class EgoTAPAutoEncoder(nn.Module):
 class HeatMap_UnrealEgo_Shared(nn.Module):
     """Stereo heatmap estimator (reference: model/net_architecture.py:25-173 over torchvision resnet18).
 
-    forward(left[B,3,256,256], right[B,3,256,256]) -> [B, 2*n_hm, 64, 64] (left maps then right maps).
+    forward(left[B,3,256,256], right[B,3,256,256]) -> [B, 2*n_hm, 64, 64] (left maps then right maps); in eval mode any heatmap side S
+    that is a multiple of 16 runs ([B,3,4S,4S] -> [B, 2*n_hm, S, S]), train mode and the batch-statistics forward at S = 64 / 128.
     The state_dict has the reference's 258 keys, including the duplicate ``backbone.backbone.layerK.*`` views of
     the ResNet tensors (the same nn.Parameter objects registered under both paths, as in the reference).
     ``forward_into(left, right, out)`` writes the result into a channel slice of a larger tensor instead
@@ -490,6 +491,7 @@ class HeatMap_UnrealEgo_Shared(nn.Module):
         backbone runs over the whole batch, the decoder in pieces of `chunk` frames.  The module's own .training flag is not consulted."""
         if self.bottleneck:
             raise NotImplementedError(f"backbone {self.model_name!r}: no batch-statistics forward (resnet18 / resnet34 have one)")
+        _spec.hm_check_batch_stats_side(self.hm_size, "forward_bnbatch_into (batch-statistics BatchNorm)")
         if getattr(self, "precision", "f32") != "bf16":
             raise _lib.EgotapError("forward_bnbatch_into runs on the bf16 channels-last kernels: set_precision('bf16') first "
                                    "(fp32 / bf16x3: hm_training.hm_train_forward_nograd)")

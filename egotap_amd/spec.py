@@ -134,6 +134,18 @@ def _bn2d(pre, c):
             (pre + ".running_var", (c,)), (pre + ".num_batches_tracked", ())]
 
 
+# heatmap sides at which the estimators' batch-statistics forwards (forward_bnbatch_into, hm_training) and stage-1 training are built; the
+# eval-mode forward runs at every multiple of 16 (egotap.h egotap_hm_forward)
+HM_BATCH_STATS_SIDES = (64, 128)
+
+
+def hm_check_batch_stats_side(hm_size: int, what: str) -> None:
+    """raise NotImplementedError, naming the built sides, when `what` (a batch-statistics path) is asked for at another side"""
+    if hm_size not in HM_BATCH_STATS_SIDES:
+        raise NotImplementedError(f"{what} is built at heatmap sides {' and '.join(map(str, HM_BATCH_STATS_SIDES))} only "
+                                  f"(256x256 / 512x512 RGB), not {hm_size}; the eval-mode estimator forward runs at every multiple of 16")
+
+
 HM_BLOCKS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}      # BasicBlock ResNets of torchvision (net_architecture.py:57-60)
 HM_BOTTLENECK = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3)}  # Bottleneck ResNets (net_architecture.py:61-64), expansion 4
 

@@ -96,7 +96,11 @@ int egotap_lift_intermediate(egotap_handle h, int B, const char* name, size_t* o
  *   out    device f32, channel 0 of this net's output; image b starts at out + b*out_image_stride (floats), so the
  *          result can be written straight into a channel slice of the lifting head's input
  *          (torch.cat of egotap_autoencoder_model.py:195-216 is never materialised)
- *   ws     device scratch of at least egotap_hm_workspace_bytes(B), 256-byte aligned (shared by both nets) */
+ *   ws     device scratch of at least egotap_hm_workspace_bytes(B), 256-byte aligned (shared by both nets)
+ * Heatmap sides: every hm_size the handle accepts (a multiple of 16; RGB 4*hm_size).  The bf16 channels-last path (EGOTAP_PREC_BF16)
+ * and the bf16 matrix-core convolutions (EGOTAP_PREC_BF16X3 / _BF16) exist at sides 64 and 128 only; at every other side each precision
+ * mode runs the exact-fp32 path BY NAME (the same launches and bits as EGOTAP_PREC_F32), as egotap_attention does for ragged sequences.
+ * Convolutions whose map width has no power-of-two instantiation run on conv_f32_any_kernel (exact fp32, batch-independent bits). */
 int egotap_hm_workspace_bytes(egotap_handle h, int B, size_t* bytes);
 int egotap_hm_forward(egotap_handle h, int net, const float* left, const float* right, int B, float* out,
                       int64_t out_image_stride, void* ws, size_t ws_bytes, void* stream);
@@ -110,7 +114,7 @@ int egotap_hm_intermediate(egotap_handle h, int B, const char* name, size_t* off
  * EGOTAP_PREC_BF16 only (bf16 channels-last kernels; the fp32 form is composed from egotap_hmtrain_conv_fwd / egotap_hmtrain_bn2d_fwd).
  * The backbone runs over the whole batch (its statistics couple the frames); the decoder, which has no BatchNorm, runs in pieces of
  * `chunk` frames (0 = the whole batch) so that its scratch stays at the chunk's size.  B >= 2.  Arguments as egotap_hm_forward;
- * ws at least egotap_hm_forward_bnbatch_workspace_bytes(B, chunk). */
+ * ws at least egotap_hm_forward_bnbatch_workspace_bytes(B, chunk).  Heatmap sides 64 and 128 only: EGOTAP_ERR_INVALID, naming them, at any other. */
 int egotap_hm_forward_bnbatch_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes);
 int egotap_hm_forward_bnbatch(egotap_handle h, int net, const float* left, const float* right, int B, float* out, int64_t out_image_stride,
                               int chunk, void* ws, size_t ws_bytes, void* stream);
