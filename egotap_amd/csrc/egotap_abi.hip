@@ -1670,6 +1670,9 @@ extern "C" int egotap_hm_intermediate(egotap_handle h, int B, const char* name, 
     if (!strcmp(name, "layer0")) { *offset = w.L0; *numel = N2 * 64 * sq(S0 / 2); }
     else if (!strcmp(name, "pool0")) { *offset = w.P0; *numel = N2 * 64 * sq(S0 / 4); }      // stem + max-pool: fp32 NCHW, or (bf16 mode) bf16 [B * (S0/4)^2, 2 x 64]
     else if (!strcmp(name, "layer1_bf16")) { *offset = w.S[0][0]; *numel = N2 * 64 * sq(S0 / 4); }      // bf16 mode: bf16 [B * (S0/4)^2, 2 x 64]
+    else if (!strcmp(name, "layer2_bf16")) { *offset = w.S[1][0]; *numel = N2 * 128 * sq(S0 / 8); }     // ... [B * (S0/8)^2, 2 x 128]: the decoder's operands
+    else if (!strcmp(name, "layer3_bf16")) { *offset = w.S[2][0]; *numel = N2 * 256 * sq(S0 / 16); }
+    else if (!strcmp(name, "layer4_bf16")) { *offset = w.S[3][0]; *numel = N2 * 512 * sq(S0 / 32); }
     else if (!strcmp(name, "layer1")) { *offset = w.S[0][3]; *numel = N2 * 64 * sq(S0 / 4); }
     else if (!strcmp(name, "layer2")) { *offset = w.S[1][3]; *numel = N2 * 128 * sq(S0 / 8); }
     else if (!strcmp(name, "layer3")) { *offset = w.S[2][3]; *numel = N2 * 256 * sq(S0 / 16); }

@@ -104,7 +104,10 @@ int egotap_lift_intermediate(egotap_handle h, int B, const char* name, size_t* o
 int egotap_hm_workspace_bytes(egotap_handle h, int B, size_t* bytes);
 int egotap_hm_forward(egotap_handle h, int net, const float* left, const float* right, int B, float* out,
                       int64_t out_image_stride, void* ws, size_t ws_bytes, void* stream);
-/* name in {"layer0".."layer4" (backbone pyramid, images interleaved n = 2b + eye), "conv_up3","conv_up2","conv_up1"} */
+/* name in {"layer0".."layer4" (backbone pyramid, images interleaved n = 2b + eye), "conv_up3","conv_up2","conv_up1"} (fp32 NCHW).
+ * EGOTAP_PREC_BF16 at sides 64 / 128: "pool0" and "layer1_bf16".."layer4_bf16" hold the pyramid as bf16 [B * s^2, left C | right C]; "u4",
+ * "cat3", "conv_up3", "cat2", "conv_up2", "cat1", "conv_up1" hold the decoder's bf16 channels-last maps [B * s^2, C] with C = 1024, 1600
+ * (1540 + zero padding), 1024, 1280, 512, 640, 512 (numel stays the fp32 layout's). */
 int egotap_hm_intermediate(egotap_handle h, int B, const char* name, size_t* offset, int64_t* numel);
 /* [r5] The same forward with BATCH-statistics BatchNorm2d and no graph: what the reference's FROZEN estimators compute while the lifting
  * head trains -- train.py:91 model.train() leaves their BatchNorm2d in training mode (model/egotap_autoencoder_model.py:127-129 freezes

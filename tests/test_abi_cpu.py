@@ -97,6 +97,36 @@ def test_workspace_grows_with_batch():
     lib.egotap_destroy(h)
 
 
+@pytest.mark.parametrize("hm", [64, 128])
+def test_hm_intermediate_slots_hold_the_bf16_maps(hm):
+    """egotap_hm_intermediate: the bf16 pyramid levels (layer1_bf16 .. layer4_bf16) and the decoder's bf16 channels-last maps
+    (tests/test_gpu_hm_bf16_decoder_stages.py reads them) lie in distinct 256-byte aligned slots inside the workspace, each large enough for
+    its bf16 tensor; unknown names are refused"""
+    lib = L.load()
+    h = C.c_void_p()
+    L.check(lib.egotap_create(C.byref(_cfg(hm_size=hm)), C.byref(h)))
+    try:
+        B, s64 = 3, hm
+        ws = C.c_size_t()
+        L.check(lib.egotap_hm_workspace_bytes(h, B, C.byref(ws)))
+        bf16 = {f"layer{i + 1}_bf16": B * (s64 >> i) ** 2 * 2 * c for i, c in enumerate((64, 128, 256, 512))}
+        bf16.update({"u4": B * (s64 // 8) ** 2 * 1024, "cat3": B * (s64 // 4) ** 2 * 1600, "conv_up3": B * (s64 // 4) ** 2 * 1024,
+                     "cat2": B * (s64 // 2) ** 2 * 1280, "conv_up2": B * (s64 // 2) ** 2 * 512, "cat1": B * s64 ** 2 * 640,
+                     "conv_up1": B * s64 ** 2 * 512})
+        slots = []
+        for name, elems in bf16.items():
+            off, num = C.c_size_t(), C.c_int64()
+            L.check(lib.egotap_hm_intermediate(h, B, name.encode(), C.byref(off), C.byref(num)))
+            assert off.value % 256 == 0 and 2 * elems <= 4 * num.value and off.value + 4 * num.value <= ws.value, name
+            slots.append((off.value, off.value + 4 * num.value))
+        slots.sort()
+        assert all(a[1] <= b[0] for a, b in zip(slots, slots[1:]))
+        off, num = C.c_size_t(), C.c_int64()
+        assert lib.egotap_hm_intermediate(h, B, b"layer5_bf16", C.byref(off), C.byref(num)) == 1
+    finally:
+        lib.egotap_destroy(h)
+
+
 def test_module_mirror_has_reference_state_dict():
     import types
     import numpy as np
