@@ -221,3 +221,66 @@ static __global__ __launch_bounds__(256) void prep_weight_kernel(const float* __
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------------- weight preparation, all at once
+// Frozen-weight serving (egotap_lift_freeze): every bf16 weight copy of the bf16-storage inference forward -- what prep_weight_kernel
+// writes per GEMM when nothing is kept, same rounding (store_bf16x8), same row-major [N][K] layout -- and every fused q|k|v bias (what
+// concat3_kernel writes, fp32) in ONE launch into a caller-owned arena.  The segment table travels as a kernel argument.  Segments
+// [0, nround) are rounded to bf16, [nround, nseg) copied as fp32.  HBM-bound (353 MB in, 177 MB out for UnrealEgo at 64 x 64 heatmaps):
+// segments differ in size by 128 x (and the biases are 4 KB), so the work is dealt in CHUNKS of 8192 elements numbered through all
+// segments, not by segment; a workgroup walks chunks blockIdx.x, + gridDim.x, ...; a thread has its eight 16-byte loads of a chunk in
+// flight before the first store.
+struct PrepSeg {
+    const float* src;               // fp32 source, 16-byte aligned, n8 * 8 elements
+    unsigned long long dst;         // byte offset into the arena (a multiple of 256)
+    unsigned n8;                    // 8-element pieces
+    unsigned first_chunk;
+};
+struct PrepTable {
+    static constexpr int MAXS = 8 * 9 + 3;      // at most 8 ViT layers x (q, k, v, o, up, down weights + 3 biases), patch projection, two fc1
+    static constexpr int CHUNK8 = 1024;         // 8-element pieces per chunk: 256 threads x 4
+    PrepSeg s[MAXS];
+    int nseg, nround, chunks;
+};
+static_assert(sizeof(PrepTable) <= 4000, "the table is a kernel argument");
+static __global__ __launch_bounds__(256) void prep_weights_all_kernel(PrepTable T, char* __restrict__ arena) {
+    constexpr int U = PrepTable::CHUNK8 / 256;
+    int si = 0;
+    for (int ch = blockIdx.x; ch < T.chunks; ch += gridDim.x) {
+        while (si + 1 < T.nseg && T.s[si + 1].first_chunk <= (unsigned)ch) ++si;
+        const float* src = T.s[si].src;
+        char* dst = arena + T.s[si].dst;
+        const unsigned n8 = T.s[si].n8;
+        const unsigned i0 = (unsigned)(ch - (int)T.s[si].first_chunk) * PrepTable::CHUNK8 + threadIdx.x;
+        f32x4 v[U][2];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const unsigned i = i0 + u * 256;
+            if (i < n8) {
+                v[u][0] = *(const f32x4*)(src + (long)i * 8);
+                v[u][1] = *(const f32x4*)(src + (long)i * 8 + 4);
+            }
+        }
+        if (si < T.nround) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned i = i0 + u * 256;
+                if (i < n8) {
+                    float o[8];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { o[e] = v[u][0][e]; o[4 + e] = v[u][1][e]; }
+                    store_bf16x8((__bf16*)dst + (long)i * 8, o);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned i = i0 + u * 256;
+                if (i < n8) {
+                    *(f32x4*)((float*)dst + (long)i * 8) = v[u][0];
+                    *(f32x4*)((float*)dst + (long)i * 8 + 4) = v[u][1];
+                }
+            }
+        }
+    }
+}

@@ -157,6 +157,11 @@ struct egotap_handle_s {
     __bf16* conv_pack = nullptr;       // scratch for repacked conv weights (set per egotap_hm_forward call from the workspace)
     float* conv_part = nullptr;        // [r4] fp32 egotap_hm_forward only (null outside it): scratch for the input-channel-split partials of conv_f32.h
     size_t conv_part_floats = 0;
+    // frozen-weight serving (egotap_lift_freeze / egotap_hm_freeze): caller-owned arenas of prepared weights, null = not frozen
+    char* lift_arena = nullptr;                          // lift_frozen_plan's layout; read by the bf16-storage inference forward only
+    char* hm_arena[EGOTAP_NET_COUNT] = {nullptr, nullptr, nullptr};       // pack_all_bf16s_kernel's region of one estimator
+    short hm_arena_slab[EGOTAP_NET_COUNT][PackTable::MAXW] = {};          // ... and the K-slab depth of every packed weight in it: the part of the
+    int hm_arena_nw[EGOTAP_NET_COUNT] = {0, 0, 0};                        // layout that depends on the batch (hm_pack_plan)
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;   // start/stop pairs
@@ -247,6 +252,22 @@ static void hm_expect(Handle* h, int net, int n_out) {
     cv("conv_heatmap", n_out, 512, 1);
 }
 
+// whether a prepared copy of this forward-needed tensor is kept while the net is frozen (egotap_lift_freeze / egotap_hm_freeze).  Lifting head: the
+// weights of the patch projection, of the ViT's six Linear layers per block and of the two fc1, and the q / k / v biases (fused into one vector).
+// Estimators: everything the pack holds -- every convolution weight and bias and every BatchNorm tensor except the stem's, which the fused
+// stem kernel reads live.
+static bool frozen_key(int net, const char* key) {
+    const std::string k(key);
+    auto ends = [&](const char* t) { const size_t n = strlen(t); return k.size() >= n && k.compare(k.size() - n, n, t) == 0; };
+    if (net == EGOTAP_NET_LIFT) {
+        if (k.find(".attention.attention.") != std::string::npos) return true;
+        if (k.find(".encoder.layer.") != std::string::npos) return ends("dense.weight");
+        return ends("patch_embeddings.projection.weight") || ends("_heatmap_encoder.fc1.fc.weight");
+    }
+    const std::string bb = "backbone.backbone.backbone.";
+    return k.compare(0, bb.size() + 6, bb + "conv1.") != 0 && k.compare(0, bb.size() + 4, bb + "bn1.") != 0;
+}
+
 #if EGOTAP_IN(0)
 extern "C" int egotap_create(const egotap_config* cfg, egotap_handle* out) {
     EGO_CHECK(cfg && out, "egotap_create: null argument");
@@ -305,6 +326,14 @@ extern "C" int egotap_bind_param(egotap_handle h, int net, const char* key, void
     }
     Param p;
     p.ptr = dev_ptr; p.numel = numel; p.dtype = dtype;
+    // a tensor whose prepared copy sits in a frozen arena moved: the arena is stale and must never be read silently
+    if (it != h->expect[net].end() && frozen_key(net, key)) {
+        auto was = h->bound[net].find(key);
+        if (was != h->bound[net].end() && was->second.ptr != dev_ptr) {
+            if (net == EGOTAP_NET_LIFT) h->lift_arena = nullptr;
+            else h->hm_arena[net] = nullptr;
+        }
+    }
     h->bound[net][key] = p;   // keys the forward never reads (pooler, cls_token, num_batches_tracked) are kept but unused
     if (net == EGOTAP_NET_LIFT) h->lift_resolved = false;
     else h->hm_resolved[net] = false;
@@ -800,6 +829,8 @@ extern "C" int egotap_set_precision(egotap_handle h, int mode) {
     EGO_CHECK(h, "null handle");
     EGO_CHECK(mode == EGOTAP_PREC_F32 || mode == EGOTAP_PREC_BF16X3 || mode == EGOTAP_PREC_BF16, "egotap_set_precision: unknown mode %d", mode);
     h->precision = mode;
+    h->lift_arena = nullptr;         // the prepared weights belong to a precision mode: a mode change unfreezes the handle
+    for (int n = 0; n < EGOTAP_NET_COUNT; ++n) h->hm_arena[n] = nullptr;
     return EGOTAP_OK;
 }
 #endif
@@ -933,6 +964,61 @@ static bool lift_prune_last(Handle* h, int B) {
 #endif
 }
 
+// ---- frozen-weight serving: the arena of egotap_lift_freeze.  Every bf16 weight copy the bf16-storage inference forward multiplies by, in the layout
+// its GEMMs read (row-major [N][K]; q | k | v stacked as one [3D][D] block), and per layer the fused q | k | v bias (fp32); 256-byte aligned slices.
+// p != nullptr: fills T, the segment table of prep_weights_all_kernel (bf16s_ops.h).
+struct LiftFrozen {
+    size_t patch, qkv[8], o[8], up[8], dn[8], bias3[8], fc1p, fc1r, total;
+};
+// the geometry / precision for which the lifting head has prepared weights at all (the bf16-storage route; whether a given call takes it also
+// depends on its batch and on the weight scratch, as before)
+static bool lift_frozen_route(const Handle* h) { return h->precision == EGOTAP_PREC_BF16 && h->D == 1024 && h->seq % 32 == 0; }
+static LiftFrozen lift_frozen_plan(const Handle* h, const LiftParams* p, PrepTable* T) {
+    LiftFrozen f{};
+    const size_t D = h->D, K1 = (size_t)h->ppd * h->ppd * D, K1r = 2 * (size_t)h->cfg.hm_size * h->cfg.hm_size;
+    const int NL = h->cfg.vit_layers;
+    size_t o = 0;
+    int ns = 0;
+    unsigned chunk = 0;
+    auto seg = [&](const float* src, size_t elems, size_t elem_bytes, size_t at) {      // at: (size_t)-1 = a slice of its own
+        const size_t dst = at == (size_t)-1 ? o : at;
+        if (at == (size_t)-1) o = al256(o + elems * elem_bytes);
+        if (T && ns < PrepTable::MAXS) {
+            T->s[ns] = PrepSeg{src, (unsigned long long)dst, (unsigned)(elems / 8), chunk};
+            chunk += (unsigned)((elems / 8 + PrepTable::CHUNK8 - 1) / PrepTable::CHUNK8);
+        }
+        ++ns;
+        return dst;
+    };
+    const size_t own = (size_t)-1;
+    f.patch = seg(p ? p->patch_w : nullptr, D * 256, 2, own);
+    for (int i = 0; i < NL; ++i) {
+        const LiftParams::Layer* L = p ? &p->layer[i] : nullptr;
+        f.qkv[i] = o;
+        o = al256(o + 3 * D * D * 2);
+        seg(L ? L->q_w : nullptr, D * D, 2, f.qkv[i]);
+        seg(L ? L->k_w : nullptr, D * D, 2, f.qkv[i] + D * D * 2);
+        seg(L ? L->v_w : nullptr, D * D, 2, f.qkv[i] + 2 * D * D * 2);
+        f.o[i] = seg(L ? L->o_w : nullptr, D * D, 2, own);
+        f.up[i] = seg(L ? L->up_w : nullptr, 4 * D * D, 2, own);
+        f.dn[i] = seg(L ? L->dn_w : nullptr, 4 * D * D, 2, own);
+    }
+    f.fc1p = seg(p ? p->pos_fc[0].w : nullptr, 2048 * K1, 2, own);
+    f.fc1r = seg(p ? p->rot_fc[0].w : nullptr, 2048 * K1r, 2, own);
+    if (T) T->nround = ns;
+    for (int i = 0; i < NL; ++i) {
+        const LiftParams::Layer* L = p ? &p->layer[i] : nullptr;
+        f.bias3[i] = o;
+        o = al256(o + 3 * D * 4);
+        seg(L ? L->q_b : nullptr, D, 4, f.bias3[i]);
+        seg(L ? L->k_b : nullptr, D, 4, f.bias3[i] + D * 4);
+        seg(L ? L->v_b : nullptr, D, 4, f.bias3[i] + 2 * D * 4);
+    }
+    if (T) { T->nseg = ns; T->chunks = (int)chunk; }
+    f.total = o;
+    return f;
+}
+
 static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream, bool pose_only,
                              const char* who) {
     EGO_CHECK(h, "null handle");
@@ -970,17 +1056,22 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
     // fp32 tensors with bf16 products in the GEMMs and the exact-fp32 attention kernel, which masks a ragged last key tile)
     const bool bf16s = h->precision == EGOTAP_PREC_BF16 && D == 1024 && M >= g_bf16s_min_rows && h->wscratch != nullptr && h->seq % 32 == 0 &&
                        h->wscratch_bytes >= (size_t)2 * 2048 * (size_t)(h->ppd * h->ppd * D);
+    // frozen (egotap_lift_freeze): the same GEMMs read the arena's copies -- the same bits the per-call preparation would write -- and no
+    // prep_weight_kernel / concat3_kernel is launched.  Every other route ignores the arena.
+    const bool frozen = bf16s && h->lift_arena != nullptr;
+    const LiftFrozen fz = frozen ? lift_frozen_plan(h, nullptr, nullptr) : LiftFrozen{};
+    auto FW = [&](size_t off) { return (const __bf16*)(h->lift_arena + off); };
     // H1+H2: tile -> patch embed -> mask token -> + position embeddings
     if (bf16s) {
         // [r3] on the bf16-storage GEMM: the heatmaps' bf16 copy in the (still free) MLP buffer, by LDS DMA; zeros for the dummy cells in SPK
         __bf16* hmb0 = (__bf16*)HID;
         const long n8 = (long)B * h->C * HW / 8;
         hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, hmb0, n8);
-        hipLaunchKernelGGL(prep_weight_kernel, dim3((256 + 63) / 64, (D + 63) / 64), dim3(256), 0, s, p.patch_w, h->wscratch, (__bf16*)nullptr, D, 256, (long)D);
+        if (!frozen) hipLaunchKernelGGL(prep_weight_kernel, dim3((256 + 63) / 64, (D + 63) / 64), dim3(256), 0, s, p.patch_w, h->wscratch, (__bf16*)nullptr, D, 256, (long)D);
         EGO_HIP(zero_fill(SPK, 256, s));
         const XPatch xl{hmb0, (const __bf16*)SPK, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
         const SEpiPatchF32 ep{p.patch_b, p.mask_tok, p.pos_emb, X, D, h->seq, h->side, h->ppd, h->grid, h->T};
-        EGO_HIP(gemm_bf16s_launch(xl, h->wscratch, 256L, ep, M, D, 256, device_cu_count(), s));
+        EGO_HIP(gemm_bf16s_launch(xl, frozen ? FW(fz.patch) : h->wscratch, 256L, ep, M, D, 256, device_cu_count(), s));
     } else {
         ALoadPatch al{hm, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
         // [r3] fp32 at a batch that fills the chip: a zero page for the dummy cells (the head of the PU chain's ZERO slice, which is cleared as a
@@ -1006,18 +1097,21 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
         for (int i = 0; i < h->cfg.vit_layers; ++i) {
             const auto& L = p.layer[i];
             ln(L.ln1_g, L.ln1_b);
-            prep(L.q_w, Wb, D, D); prep(L.k_w, Wb + (size_t)D * D, D, D); prep(L.v_w, Wb + (size_t)2 * D * D, D, D);
-            hipLaunchKernelGGL(concat3_kernel, dim3((D + 255) / 256), dim3(256), 0, s, L.q_b, L.k_b, L.v_b, bias3, D);
+            if (!frozen) {
+                prep(L.q_w, Wb, D, D); prep(L.k_w, Wb + (size_t)D * D, D, D); prep(L.v_w, Wb + (size_t)2 * D * D, D, D);
+                hipLaunchKernelGGL(concat3_kernel, dim3((D + 255) / 256), dim3(256), 0, s, L.q_b, L.k_b, L.v_b, bias3, D);
+            }
             EGO_HIP(hipGetLastError());
-            EGO_HIP(gemm_bf16s_plain_launch(XPlain{Yb, (long)D}, Wb, (long)D, SEpiBf16{bias3, QKVb, 3L * D}, M, 3 * D, D, cu, s));
+            EGO_HIP(gemm_bf16s_plain_launch(XPlain{Yb, (long)D}, frozen ? FW(fz.qkv[i]) : Wb, (long)D,
+                                            SEpiBf16{frozen ? (const float*)(h->lift_arena + fz.bias3[i]) : bias3, QKVb, 3L * D}, M, 3 * D, D, cu, s));
             EGO_HIP(attention_bf16s_fwd_launch(QKVb, CTXb, nullptr, B, h->seq, h->cfg.vit_heads, s));
-            prep(L.o_w, Wb, D, D);
-            EGO_HIP(gemm_bf16s_plain_launch(XPlain{CTXb, (long)D}, Wb, (long)D, SEpiResF32{L.o_b, X, X, (long)D}, M, D, D, cu, s));
+            if (!frozen) prep(L.o_w, Wb, D, D);
+            EGO_HIP(gemm_bf16s_plain_launch(XPlain{CTXb, (long)D}, frozen ? FW(fz.o[i]) : Wb, (long)D, SEpiResF32{L.o_b, X, X, (long)D}, M, D, D, cu, s));
             ln(L.ln2_g, L.ln2_b);
-            prep(L.up_w, Wb, 4 * D, D);
-            EGO_HIP(gemm_bf16s_plain_launch(XPlain{Yb, (long)D}, Wb, (long)D, SEpiGelu{L.up_b, HIDb, 4L * D}, M, 4 * D, D, cu, s));
-            prep(L.dn_w, Wb, D, 4 * D);
-            EGO_HIP(gemm_bf16s_plain_launch(XPlain{HIDb, 4L * D}, Wb, 4L * D, SEpiResF32{L.dn_b, X, X, (long)D}, M, D, 4 * D, cu, s));
+            if (!frozen) prep(L.up_w, Wb, 4 * D, D);
+            EGO_HIP(gemm_bf16s_plain_launch(XPlain{Yb, (long)D}, frozen ? FW(fz.up[i]) : Wb, (long)D, SEpiGelu{L.up_b, HIDb, 4L * D}, M, 4 * D, D, cu, s));
+            if (!frozen) prep(L.dn_w, Wb, D, 4 * D);
+            EGO_HIP(gemm_bf16s_plain_launch(XPlain{HIDb, 4L * D}, frozen ? FW(fz.dn[i]) : Wb, 4L * D, SEpiResF32{L.dn_b, X, X, (long)D}, M, D, 4 * D, cu, s));
             if (h->debug_stop == 2 + i) return EGOTAP_OK;
         }
         ln(p.lnf_g, p.lnf_b);                               // tokens (bf16) -> fc1's gathering loader
@@ -1025,12 +1119,13 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
         auto bn = [](const LiftParams::Fc& f) { return EpiBnLrelu{f.b, f.g, f.beta, f.mean, f.var, 1e-5f, 0.2f}; };
         {
             const int K1 = h->ppd * h->ppd * D;
-            prep(p.pos_fc[0].w, Wb, 2048, K1);
+            if (!frozen) prep(p.pos_fc[0].w, Wb, 2048, K1);
+            const __bf16* W1 = frozen ? FW(fz.fc1p) : Wb;
             // [r3] few encoder rows (EgoCap at 128 x 128 heatmaps, B = 32: 1088 rows = 40 tiles for 256 CUs, K = 65536): split K over the chip
             const XTokens xt{Yb, h->T, D, h->seq, h->side, h->ppd, h->grid};
             const int sp = gemm_bf16s_ksplit(BT, 2048, K1, cu, SPLITK_FLOATS);
-            if (sp > 1) EGO_HIP(gemm_bf16s_splitk_launch(xt, Wb, (long)K1, bnf(p.pos_fc[0], Z1), SPK, sp, BT, 2048, K1, cu, s));
-            else EGO_HIP(fc1_nt(h, 0, Yb, Wb, (long)K1, bnf(p.pos_fc[0], Z1), BT, cu, s));
+            if (sp > 1) EGO_HIP(gemm_bf16s_splitk_launch(xt, W1, (long)K1, bnf(p.pos_fc[0], Z1), SPK, sp, BT, 2048, K1, cu, s));
+            else EGO_HIP(fc1_nt(h, 0, Yb, W1, (long)K1, bnf(p.pos_fc[0], Z1), BT, cu, s));
             EGO_HIP((fc_gemm(h, "pos_fc2", ALoadPlain{Z1, 2048}, segmat1(p.pos_fc[1].w, 512, 2048), bn(p.pos_fc[1]), Z2, 512, BT, 512, 2048, SPK, s)));
             EGO_HIP((fc_gemm(h, "pos_fc3", ALoadPlain{Z2, 512}, segmat1(p.pos_fc[2].w, hid, 512), bn(p.pos_fc[2]), POSZ, hid, BT, hid, 512, SPK, s)));
         }
@@ -1038,12 +1133,13 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
             __bf16* hmb = HIDb;                             // the MLP's hidden buffer is free now: bf16 copy of the input heatmaps
             const long n8 = (long)B * h->C * HW / 8;
             hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, hmb, n8);
-            prep(p.rot_fc[0].w, Wb, 2048, 2 * HW);
+            if (!frozen) prep(p.rot_fc[0].w, Wb, 2048, 2 * HW);
+            const __bf16* W1 = frozen ? FW(fz.fc1r) : Wb;
             EGO_HIP(hipGetLastError());
             const XRot xr{hmb, h->C, J, HW};
             const int sp = gemm_bf16s_ksplit(BT, 2048, 2 * HW, cu, SPLITK_FLOATS);
-            if (sp > 1) EGO_HIP(gemm_bf16s_splitk_launch(xr, Wb, 2L * HW, bnf(p.rot_fc[0], Z1), SPK, sp, BT, 2048, 2 * HW, cu, s));
-            else EGO_HIP(fc1_nt(h, 1, hmb, Wb, 2L * HW, bnf(p.rot_fc[0], Z1), BT, cu, s));
+            if (sp > 1) EGO_HIP(gemm_bf16s_splitk_launch(xr, W1, 2L * HW, bnf(p.rot_fc[0], Z1), SPK, sp, BT, 2048, 2 * HW, cu, s));
+            else EGO_HIP(fc1_nt(h, 1, hmb, W1, 2L * HW, bnf(p.rot_fc[0], Z1), BT, cu, s));
             EGO_HIP((fc_gemm(h, "rot_fc2", ALoadPlain{Z1, 2048}, segmat1(p.rot_fc[1].w, 512, 2048), bn(p.rot_fc[1]), Z2, 512, BT, 512, 2048, SPK, s)));
             EGO_HIP((fc_gemm(h, "rot_fc3", ALoadPlain{Z2, 512}, segmat1(p.rot_fc[2].w, hid, 512), bn(p.rot_fc[2]), ROTZ, hid, BT, hid, 512, SPK, s)));
         }
@@ -1172,6 +1268,40 @@ extern "C" int egotap_lift_forward(egotap_handle h, const float* hm, int B, floa
 }
 extern "C" int egotap_lift_predict_pose(egotap_handle h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream) {
     return lift_forward_impl(h, hm, B, pose, ws, ws_bytes, stream, true, "egotap_lift_predict_pose");
+}
+
+extern "C" int egotap_lift_frozen_bytes(egotap_handle h, size_t* bytes) {
+    EGO_CHECK(h && bytes, "egotap_lift_frozen_bytes: null argument");
+    *bytes = lift_frozen_route(h) ? lift_frozen_plan(h, nullptr, nullptr).total : 0;
+    return EGOTAP_OK;
+}
+extern "C" int egotap_lift_freeze(egotap_handle h, void* arena, size_t bytes, void* stream) {
+    EGO_CHECK(h, "null handle");
+    EGO_CHECK(h->precision == EGOTAP_PREC_BF16, "egotap_lift_freeze: nothing to freeze in this precision mode (only EGOTAP_PREC_BF16 prepares weights; "
+              "the fp32 and bf16x3 modes read the live fp32 parameters)");
+    EGO_CHECK(lift_frozen_route(h), "egotap_lift_freeze: nothing to freeze: the bf16-storage forward needs vit_dim 1024 and a sequence that is a multiple of 32 "
+              "(this handle: vit_dim %d, %d tokens)", h->D, h->seq);
+    EGO_CHECK(arena && ((uintptr_t)arena & 255) == 0, "egotap_lift_freeze: the arena must be a 256-byte aligned device pointer");
+    int rc = lift_resolve(h);
+    if (rc != EGOTAP_OK) return rc;
+    PrepTable T;
+    const LiftFrozen f = lift_frozen_plan(h, &h->lp, &T);
+    EGO_CHECK(T.nseg <= PrepTable::MAXS, "egotap_lift_freeze: more segments than the table holds");
+    if (bytes < f.total) {
+        egotap_set_error("egotap_lift_freeze: arena too small: %zu bytes given, %zu needed", bytes, f.total);
+        return EGOTAP_ERR_WORKSPACE;
+    }
+    h->lift_arena = nullptr;
+    const int grid = T.chunks < 2048 ? T.chunks : 2048;      // 8 workgroups per CU; the rest of the chunks by stride
+    hipLaunchKernelGGL(prep_weights_all_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, T, (char*)arena);
+    EGO_HIP(hipGetLastError());
+    h->lift_arena = (char*)arena;
+    return EGOTAP_OK;
+}
+extern "C" int egotap_lift_unfreeze(egotap_handle h) {
+    EGO_CHECK(h, "null handle");
+    h->lift_arena = nullptr;
+    return EGOTAP_OK;
 }
 #endif
 
@@ -1689,6 +1819,68 @@ extern "C" int egotap_hm_intermediate(egotap_handle h, int B, const char* name, 
 }
 #endif
 
+// the pack plan of the eval-mode bf16 forward at batch B (egotap_hm_forward and egotap_hm_freeze share it): the split-K budgets are the
+// workspace slices egotap_hm_forward hands the backbone (the fp32 stem map's slot) and the decoder (40 MB of the WPACK region)
+static size_t hm_forward_plan(const Handle* h, const HmParams& p, int B, PackTable* PT) {
+    const int S0 = h->cfg.hm_size * 4;
+    const int stage_sides[4] = {S0 / 4, S0 / 8, S0 / 16, S0 / 32};
+    const size_t split_floats = (size_t)2 * B * 64 * (S0 / 2) * (S0 / 2), dec_split_floats = ((size_t)40 << 20) / 4;
+    return hm_pack_plan(&p, p.nblk, PT, 2L * B, stage_sides, device_cu_count(), split_floats, dec_split_floats);
+}
+// frozen estimator: the arena holds the packed layout of the batch it was built for; a batch whose plan picks another K-slab depth for some
+// weight (hm_pack_plan: 32- or 64-channel slabs by pixel count) does not fit and packs per call
+static bool hm_arena_fits(const Handle* h, int net, const PackTable& PT) {
+    if (!h->hm_arena[net] || h->hm_arena_nw[net] != PT.nw) return false;
+    for (int i = 0; i < PT.nw; ++i)
+        if (h->hm_arena_slab[net][i] != PT.w[i].slab) return false;
+    return true;
+}
+// the precision / geometry for which an estimator has a packed region at all: the bf16 channels-last path (sides 64 / 128)
+static bool hm_frozen_route(const Handle* h) { return h->precision == EGOTAP_PREC_BF16 && (h->cfg.hm_size == 64 || h->cfg.hm_size == 128); }
+
+#if EGOTAP_IN(0)
+extern "C" int egotap_hm_frozen_bytes(egotap_handle h, int net, int B, size_t* bytes) {
+    EGO_CHECK(h && bytes, "egotap_hm_frozen_bytes: null argument");
+    EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "egotap_hm_frozen_bytes: net must be EGOTAP_NET_HM_POS or _ROT");
+    EGO_CHECK(B > 0, "egotap_hm_frozen_bytes: batch must be positive");
+    const int nblk_[4] = {hm_nblk(h, 0), hm_nblk(h, 1), hm_nblk(h, 2), hm_nblk(h, 3)};
+    *bytes = hm_frozen_route(h) ? hm_pack_plan(nullptr, nblk_, nullptr) : 0;      // (the slices' sizes do not depend on the batch; their slab order does)
+    return EGOTAP_OK;
+}
+extern "C" int egotap_hm_freeze(egotap_handle h, int net, int B, void* arena, size_t bytes, void* stream) {
+    EGO_CHECK(h, "null handle");
+    EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "egotap_hm_freeze: net must be EGOTAP_NET_HM_POS or _ROT");
+    EGO_CHECK(B > 0, "egotap_hm_freeze: batch must be positive");
+    EGO_CHECK(h->precision == EGOTAP_PREC_BF16, "egotap_hm_freeze: nothing to freeze in this precision mode (only EGOTAP_PREC_BF16 packs weights)");
+    EGO_CHECK(hm_frozen_route(h), "egotap_hm_freeze: nothing to freeze at heatmap side %d: the bf16 channels-last path exists at sides 64 and 128", h->cfg.hm_size);
+    EGO_CHECK(arena && ((uintptr_t)arena & 255) == 0, "egotap_hm_freeze: the arena must be a 256-byte aligned device pointer");
+    int rc = hm_resolve(h, net);
+    if (rc != EGOTAP_OK) return rc;
+    const int nblk_[4] = {hm_nblk(h, 0), hm_nblk(h, 1), hm_nblk(h, 2), hm_nblk(h, 3)};
+    const size_t need = hm_pack_plan(nullptr, nblk_, nullptr);
+    if (bytes < need) {
+        egotap_set_error("egotap_hm_freeze: arena too small: %zu bytes given, %zu needed", bytes, need);
+        return EGOTAP_ERR_WORKSPACE;
+    }
+    PackTable PT;
+    const size_t used = hm_forward_plan(h, h->hp[net], B, &PT);
+    EGO_CHECK(used != 0 && used <= need, "egotap_hm_freeze: the estimator has more layers than the pack table holds");
+    h->hm_arena[net] = nullptr;
+    hipLaunchKernelGGL(pack_all_bf16s_kernel, dim3(PT.blocks), dim3(256), 0, (hipStream_t)stream, PT, (char*)arena);
+    EGO_HIP(hipGetLastError());
+    h->hm_arena_nw[net] = PT.nw;
+    for (int i = 0; i < PT.nw; ++i) h->hm_arena_slab[net][i] = PT.w[i].slab;
+    h->hm_arena[net] = (char*)arena;
+    return EGOTAP_OK;
+}
+extern "C" int egotap_hm_unfreeze(egotap_handle h, int net) {
+    EGO_CHECK(h, "null handle");
+    EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "egotap_hm_unfreeze: net must be EGOTAP_NET_HM_POS or _ROT");
+    h->hm_arena[net] = nullptr;
+    return EGOTAP_OK;
+}
+#endif
+
 // HeatMap_UnrealEgo_Shared.forward(left, right) (model/net_architecture.py:32-36, 45-51, 75-85, 139-173), eval mode.
 #if EGOTAP_IN(0)
 extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, const float* right, int B, float* out,
@@ -1746,14 +1938,15 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
         q.split_floats = (size_t)N2 * 64 * (S0 / 2) * (S0 / 2);
         q.dec_slab = (float*)(base + w.WPACK);                                     // [r4] the first 40 MB of the WPACK region (the zero page sits behind them): split-K partials of the decoder
         q.dec_split_floats = ((size_t)40 << 20) / 4;
-        const int cus = device_cu_count();
         EGO_HIP(zero_fill(q.ZP, 256, s));
         // [r3] all 27 weight repacks and 19 BatchNorm folds of this forward in ONE launch (conv_bf16s.h, pack_all_bf16s_kernel): the
-        // parameters stay the caller's live fp32 tensors, nothing is kept between calls
+        // parameters stay the caller's live fp32 tensors, nothing is kept between calls ...
         PackTable PT;
-        const int stage_sides[4] = {s64, s32, s16, s8};
-        EGO_CHECK(hm_pack_plan(&p, p.nblk, &PT, N2, stage_sides, cus, q.split_floats, q.dec_split_floats) != 0, "egotap_hm_forward: the estimator has more layers than the pack table holds");
-        hipLaunchKernelGGL(pack_all_bf16s_kernel, dim3(PT.blocks), dim3(256), 0, s, PT, q.reg);
+        EGO_CHECK(hm_forward_plan(h, p, B, &PT) != 0, "egotap_hm_forward: the estimator has more layers than the pack table holds");
+        // ... unless the caller froze this estimator (egotap_hm_freeze) and the batch's packed layout is the one in the arena: then the region is
+        // the arena and nothing is packed
+        if (hm_arena_fits(h, net, PT)) q.reg = h->hm_arena[net];
+        else hipLaunchKernelGGL(pack_all_bf16s_kernel, dim3(PT.blocks), dim3(256), 0, s, PT, q.reg);
         EGO_HIP(hipGetLastError());
         int li = 0, bi = 0;
         EGO_HIP(hm_bf16_backbone(h, p, PT, li, bi, q, left, right, B, S0, nullptr, s));

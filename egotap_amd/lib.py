@@ -45,6 +45,13 @@ _PROTOS = {
     "egotap_debug_conv_addressing": (C.c_int, [C.c_int]),
     "egotap_set_weight_scratch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "egotap_set_act_scratch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    # ---- frozen-weight serving: prepared weights kept in a caller-owned arena
+    "egotap_lift_frozen_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "egotap_lift_freeze": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_lift_unfreeze": (C.c_int, [C.c_void_p]),
+    "egotap_hm_frozen_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "egotap_hm_freeze": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_hm_unfreeze": (C.c_int, [C.c_void_p, C.c_int]),
     "egotap_hm_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
     "egotap_hm_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),

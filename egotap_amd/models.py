@@ -272,6 +272,30 @@ class EgoTAPAutoEncoderModel(nn.Module):
             n.set_precision(mode)
         return self
 
+    def freeze_weights(self, batch: int = 1):
+        """Frozen-weight serving (networks._FrozenWeights): freeze every network that can be frozen as it stands -- "bf16" precision, eval mode, a
+        geometry with prepared weights -- and skip the others BY NAME: returns {model name: reason} for the skipped ones.  ``batch`` is the batch
+        the estimators' packed layout is built for (the chunk forward_heatmap() walks: min(batch size, opt.hm_chunk)).  A training step
+        afterwards works unchanged: optimize_parameters() puts the head in train mode, which unfreezes it.  Note that evaluate() under
+        --use_amp switches the networks to fp32 and back, which unfreezes them as every set_precision does."""
+        from . import lib as _lib
+        skipped = OrderedDict()
+        for name in self.model_names:
+            net = getattr(self, "net_" + name)
+            try:
+                if isinstance(net, networks.HeatMap_UnrealEgo_Shared):
+                    net.freeze_weights(batch)
+                else:
+                    net.freeze_weights()
+            except _lib.EgotapError as e:
+                skipped[name] = str(e)
+        return skipped
+
+    def unfreeze_weights(self):
+        for name in self.model_names:
+            getattr(self, "net_" + name).unfreeze_weights()
+        return self
+
     def set_eval_mode(self):
         """egotap_autoencoder_model.py:325-327: the head and the POSITION estimator; net_RotHeatMap keeps its mode, exactly as in the
         reference (every caller there runs model.eval() first: utils/evaluate.py:93, 150).  opt.frozen_heatmap_bn_eval makes the

@@ -61,7 +61,84 @@ def _kaiming_init_(module: nn.Module):
                 p.zero_()
 
 
-class EgoTAPAutoEncoder(nn.Module):
+class _FrozenWeights:
+    """Opt-in frozen-weight serving in the "bf16" mode (egotap.h, frozen-weight serving): ``freeze_weights()`` prepares every weight once, in one
+    launch, into an arena the module owns; the eval-mode forwards then read the arena and launch no weight preparation -- same bits.
+
+    Staleness: ``.train()`` and ``set_precision`` unfreeze.  Every frozen forward compares ``data_ptr()`` and ``_version`` of the frozen tensors
+    with what it recorded at the freeze and re-runs the one launch (into the same arena) when one moved: optimizer steps, ``load_state_dict``,
+    ``copy_``, ``mul_`` ... all bump ``_version``.  Writes through ``.data`` (and raw device writes) do NOT: call ``refresh_frozen_weights()``
+    after those.  Subclasses give _frozen_tensors(), _frozen_bytes(), _frozen_launch(arena, dev) and _frozen_release()."""
+
+    _frozen_sig = None          # None: not frozen; else ((data_ptr, _version), ...) of the frozen tensors at the last freeze
+    _frozen_arena = None
+    _frozen_list = None
+
+    @property
+    def weights_frozen(self) -> bool:
+        return self._frozen_sig is not None
+
+    def _frozen_device(self):
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.EgotapError("freeze_weights: the module is on the CPU; the prepared weights live on the GPU (no CPU fallback)")
+        return dev
+
+    def freeze_weights(self, *args, **kwargs):
+        dev = self._frozen_device()
+        if self.training:
+            raise _lib.EgotapError("freeze_weights: the module is in train mode (training never reads the prepared weights): call .eval() first")
+        if getattr(self, "precision", "f32") != "bf16":
+            raise _lib.EgotapError(f"freeze_weights: nothing to freeze in precision {getattr(self, 'precision', 'f32')!r}: only 'bf16' prepares "
+                                   "weights per forward (f32 / bf16x3 read the live parameters)")
+        with torch.cuda.device(dev):
+            self._frozen_prepare(*args, **kwargs)
+            self._bind(dev)
+            need = self._frozen_bytes()
+            if self._frozen_arena is None or self._frozen_arena.numel() != need or self._frozen_arena.device != dev:
+                self._frozen_arena = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._frozen_run(dev)
+        return self
+
+    def _frozen_prepare(self):
+        pass
+
+    def _frozen_run(self, dev):
+        if self._frozen_arena.device != dev:
+            self._frozen_arena = torch.empty(self._frozen_arena.numel(), dtype=torch.uint8, device=dev)
+        self._frozen_list = self._frozen_tensors()
+        self._frozen_launch(self._frozen_arena, dev)
+        self._frozen_sig = tuple((t.data_ptr(), t._version) for t in self._frozen_list)
+
+    def refresh_frozen_weights(self):
+        """prepare the weights again from the live parameters, into the same arena (a graph captured while frozen stays valid)"""
+        if not self.weights_frozen:
+            raise _lib.EgotapError("refresh_frozen_weights: the module is not frozen")
+        dev = self._frozen_device()
+        with torch.cuda.device(dev):
+            self._bind(dev)
+            self._frozen_run(dev)
+        return self
+
+    def unfreeze_weights(self):
+        if self._frozen_sig is not None:
+            if self._handle is not None:
+                self._frozen_release()
+            self._frozen_sig = self._frozen_arena = self._frozen_list = None
+        return self
+
+    def _frozen_check(self, dev):
+        """every frozen eval forward, after _bind: one tuple compare; the one launch again when a frozen tensor moved or was written"""
+        if self._frozen_sig != tuple((t.data_ptr(), t._version) for t in self._frozen_list):
+            self._frozen_run(dev)
+
+    def train(self, mode: bool = True):
+        if mode:
+            self.unfreeze_weights()
+        return super().train(mode)
+
+
+class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
     """Heatmaps -> 3D pose lifting head (reference: model/net_architecture.py:579-758).
 
     forward(input[B, 6J, S, S]) -> (pose[B, J(+1), 3], rot zeros[B, 3J], indep_pos zeros[B, 6J],
@@ -129,6 +206,29 @@ class EgoTAPAutoEncoder(nn.Module):
         _lib.check(_lib.load().egotap_pu_chain_status(self._ensure_handle(), C.byref(en), C.byref(nf)))
         return bool(en.value), nf.value
 
+    # -- frozen-weight serving (see _FrozenWeights) --------------------------------------------------
+    def _frozen_tensors(self):
+        """what egotap_lift_freeze keeps a prepared copy of: the weights of the patch projection, of the ViT blocks' six Linear layers and of the
+        two fc1 (bf16 copies), and the q / k / v biases (fused per block)"""
+        return [t for k, t in self.named_parameters()
+                if ".attention.attention." in k or (".encoder.layer." in k and k.endswith("dense.weight"))
+                or k.endswith("patch_embeddings.projection.weight") or k.endswith("_heatmap_encoder.fc1.fc.weight")]
+
+    def _frozen_bytes(self):
+        need = C.c_size_t()
+        _lib.check(_lib.load().egotap_lift_frozen_bytes(self._ensure_handle(), C.byref(need)))
+        if need.value == 0:
+            raise _lib.EgotapError(f"freeze_weights: nothing to freeze: the bf16-storage forward needs a sequence that is a multiple of 32 tokens "
+                                   f"(heatmap side {self.preset.hm_size}: {self.preset.seq} tokens run on fp32 tensors, which read the live parameters)")
+        return need.value
+
+    def _frozen_launch(self, arena, dev):
+        _lib.check(_lib.load().egotap_lift_freeze(self._ensure_handle(), C.c_void_p(arena.data_ptr()), arena.numel(),
+                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def _frozen_release(self):
+        _lib.check(_lib.load().egotap_lift_unfreeze(self._handle))
+
     def _bind(self, device):
         sd = dict(self.named_parameters())
         sd.update(dict(self.named_buffers()))
@@ -187,6 +287,7 @@ class EgoTAPAutoEncoder(nn.Module):
         "bf16x3" = fp32 operands split into hi + lo bf16, three bf16 MFMAs per product, fp32 accumulate (opt-in fast mode)."""
         if mode not in _lib.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
+        self.unfreeze_weights()        # prepared weights belong to a mode (the library unfreezes the handle too)
         _lib.check(_lib.load().egotap_set_precision(self._ensure_handle(), _lib.PRECISIONS[mode]))
         self.precision = mode
         if mode == "bf16":             # scratch for the bf16 copy of a GEMM's weights (largest: fc1 of the position encoder)
@@ -238,6 +339,8 @@ class EgoTAPAutoEncoder(nn.Module):
         if B > 0:
             with torch.cuda.device(dev):
                 self._bind(dev)
+                if self._frozen_sig is not None:
+                    self._frozen_check(dev)
                 ws = self._workspace(B, dev)
                 # predict_pose: the pose-only entry (same bits; the last ViT layer skips the rows fc1 never reads), forward(): every intermediate
                 entry = _lib.load().egotap_lift_predict_pose if pose_only else _lib.load().egotap_lift_forward
@@ -250,7 +353,7 @@ class EgoTAPAutoEncoder(nn.Module):
 
     def predict_pose_graphed(self, input):
         """predict_pose through a captured HIP graph (serving at small batches, where the ~130 launches of a forward cost more than
-        the kernels): the forward is captured once per (batch, device, precision, parameter pointers) with a static input
+        the kernels): the forward is captured once per (batch, device, precision, parameter pointers, frozen arena) with a static input
         and output buffer and replayed afterwards -- same kernels, same bits (tests/test_gpu_lift.py).  [r6] Captures the pose-only entry
         (egotap_lift_predict_pose), as predict_pose runs it.  Eval mode only; the returned
         tensor is the graph's static output buffer (valid until the next call with the same batch)."""
@@ -263,8 +366,12 @@ class EgoTAPAutoEncoder(nn.Module):
             raise ValueError(f"expected input [B, {p.in_channels}, {p.hm_size}, {p.hm_size}], got {tuple(input.shape)}")
         dev = input.device
         self._bind(dev)
+        if self._frozen_sig is not None:               # stale prepared weights are redone here, into the same arena, ahead of the replay
+            with torch.cuda.device(dev):
+                self._frozen_check(dev)
         B = input.shape[0]
-        key = (B, str(dev), getattr(self, "precision", "f32"), self._bound_sig)
+        # the frozen state (and its arena) is part of the key: a graph captured while frozen holds no preparation kernels and reads that arena
+        key = (B, str(dev), getattr(self, "precision", "f32"), self._bound_sig, self._frozen_arena.data_ptr() if self.weights_frozen else None)
         graphs = self.__dict__.setdefault("_graphs", {})
         g = graphs.get(key)
         if g is None:
@@ -280,7 +387,7 @@ class EgoTAPAutoEncoder(nn.Module):
             _lib.check(lib.egotap_lift_workspace_bytes(h, B, C.byref(need)))
             ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
             self._act_scratch(B, dev)
-            keep = (ws, getattr(self, "_ascratch", None), getattr(self, "_wscratch", None))
+            keep = (ws, getattr(self, "_ascratch", None), getattr(self, "_wscratch", None), self._frozen_arena if self.weights_frozen else None)
 
             def run():
                 _lib.check(lib.egotap_lift_predict_pose(h, C.c_void_p(static_in.data_ptr()), B, C.c_void_p(static_out.data_ptr()),
@@ -313,7 +420,7 @@ class EgoTAPAutoEncoder(nn.Module):
         return None, rot, indep, out_hm
 
 
-class HeatMap_UnrealEgo_Shared(nn.Module):
+class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
     """Stereo heatmap estimator (reference: model/net_architecture.py:25-173 over torchvision resnet18).
 
     forward(left[B,3,256,256], right[B,3,256,256]) -> [B, 2*n_hm, 64, 64] (left maps then right maps); in eval mode any heatmap side S
@@ -380,6 +487,8 @@ class HeatMap_UnrealEgo_Shared(nn.Module):
             if src_leaf in src_mod._buffers:
                 mod._buffers[leaf] = src_mod._buffers[src_leaf]
         self._bound_sig = None
+        if self._frozen_sig is not None:
+            self._frozen_sig = ()          # the buffers are new objects: the next frozen forward lists the tensors again and re-freezes
         return self
 
     def set_precision(self, mode: str = "f32"):
@@ -389,6 +498,7 @@ class HeatMap_UnrealEgo_Shared(nn.Module):
             raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
         if self.bottleneck and mode != "f32":
             raise NotImplementedError(f"backbone {self.model_name!r} runs in fp32 only (the bf16 modes cover resnet18 / resnet34)")
+        self.unfreeze_weights()        # prepared weights belong to a mode (the library unfreezes the handle too)
         _lib.check(_lib.load().egotap_set_precision(self._ensure_handle(), _lib.PRECISIONS[mode]))
         self.precision = mode
         return self
@@ -399,6 +509,48 @@ class HeatMap_UnrealEgo_Shared(nn.Module):
         for part in parts[:-1]:
             mod = mod._modules[part]
         return mod, parts[-1]
+
+    # -- frozen-weight serving (see _FrozenWeights) --------------------------------------------------
+    def freeze_weights(self, batch: int = 1):
+        """Keep this estimator's packed convolution weights, padded biases and folded BatchNorms (running statistics) for ``forward_into`` /
+        the eval forward.  The packed layout depends on the batch (which convolutions run split over K): the arena is built for ``batch``;
+        a forward at a batch with another layout packs per call as if not frozen (the library decides per call; same bits either way)."""
+        if self.bottleneck:
+            raise _lib.EgotapError(f"freeze_weights: nothing to freeze: backbone {self.model_name!r} runs in fp32 only (no bf16 mode, no packed weights)")
+        return super().freeze_weights(batch)
+
+    def _frozen_prepare(self, batch: int = 1):
+        if int(batch) < 1:
+            raise ValueError("freeze_weights: batch must be positive")
+        self._frozen_batch = int(batch)
+
+    def _frozen_tensors(self):
+        """everything pack_all_bf16s_kernel reads: every convolution weight / bias and BatchNorm tensor except the stem's (read live); the
+        ResNet's classifier (fc) is never read at all"""
+        sd = self.state_dict(keep_vars=True)
+        bb = "backbone.backbone.backbone."
+        seen = {id(t) for k, t in sd.items() if k.startswith((bb + "conv1.", bb + "bn1.", bb + "fc."))}
+        out = []
+        for k, t in sd.items():
+            if id(t) not in seen and t.dtype == torch.float32:
+                seen.add(id(t))
+                out.append(t)
+        return out
+
+    def _frozen_bytes(self):
+        need = C.c_size_t()
+        _lib.check(_lib.load().egotap_hm_frozen_bytes(self._ensure_handle(), self._net, self._frozen_batch, C.byref(need)))
+        if need.value == 0:
+            raise _lib.EgotapError(f"freeze_weights: nothing to freeze at heatmap side {self.hm_size}: the bf16 channels-last path exists at sides "
+                                   "64 and 128; every other side runs the exact-fp32 path, which reads the live parameters")
+        return need.value
+
+    def _frozen_launch(self, arena, dev):
+        _lib.check(_lib.load().egotap_hm_freeze(self._ensure_handle(), self._net, self._frozen_batch, C.c_void_p(arena.data_ptr()), arena.numel(),
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def _frozen_release(self):
+        _lib.check(_lib.load().egotap_hm_unfreeze(self._handle, self._net))
 
     def _ensure_handle(self):
         if self._handle is None:
@@ -474,6 +626,8 @@ class HeatMap_UnrealEgo_Shared(nn.Module):
             return out
         with torch.cuda.device(dev):
             self._bind(dev)
+            if self._frozen_sig is not None:
+                self._frozen_check(dev)
             ws = workspace if workspace is not None else self._workspace(B, dev)
             self._ws = ws
             hw = self.hm_size * self.hm_size
@@ -526,6 +680,8 @@ class HeatMap_UnrealEgo_Shared(nn.Module):
                 h, self._net, C.c_void_p(left.data_ptr()), C.c_void_p(right.data_ptr()), B,
                 C.c_void_p(out.data_ptr() + 4 * channel_offset * hw), out.shape[1] * hw, chunk, C.c_void_p(ws.data_ptr()), ws.numel(),
                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            if self._frozen_sig is not None:
+                self._frozen_sig = ()      # the kernels moved the running statistics without a _version bump: the next frozen forward folds them again
         return out
 
     def bnbatch_intermediate(self, name: str, B: int, chunk: int, ws=None):

@@ -696,6 +696,9 @@ class EgotapAdamW(torch.optim.Optimizer):
                 st["step"] = int(st["step"]) + 1        # torch.optim.AdamW checkpoints keep the step as a tensor
                 T.adamw(p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], group["lr"], st["step"], b1, b2, group["eps"],
                         group["weight_decay"])
+        # the kernels wrote the parameters through raw pointers: tell torch, as an in-place op of torch.optim would (host-only; frozen-weight
+        # serving compares _version to notice that a prepared copy is stale, networks._FrozenWeights)
+        torch.autograd.graph.increment_version([p for group in self.param_groups for p in group["params"] if p.grad is not None])
         return None
 
 

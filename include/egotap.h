@@ -162,6 +162,38 @@ int egotap_set_weight_scratch(egotap_handle h, void* buf, size_t bytes);
  * kernel.  NULL = off. */
 int egotap_set_act_scratch(egotap_handle h, void* buf, size_t bytes);
 
+/* ---- frozen-weight serving (opt-in): keep the prepared weights across forwards ----
+ * By default the EGOTAP_PREC_BF16 forwards prepare their weights on every call (the lifting head rounds each GEMM's weight matrix into the
+ * weight scratch and fuses the q | k | v bias; an estimator repacks its convolution weights and folds its BatchNorms), so that the live fp32
+ * parameters stay the only source of truth.  A server whose weights do not change can FREEZE a network instead: the caller hands the library
+ * an arena, ONE launch fills it with every prepared weight, and from then on the inference forwards read the arena and launch no weight
+ * preparation.  The results are the same bits: the same kernels multiply by the same bf16 values.
+ *   - The library still allocates nothing and never synchronises.  The arena is a caller-owned device buffer (256-byte aligned, at least
+ *     *_frozen_bytes) that the handle BORROWS until the matching unfreeze or egotap_destroy; the caller must keep it alive and untouched that
+ *     long.  A freeze enqueues its one launch on `stream` and is ordered there like any forward; freezing again (same or another arena)
+ *     re-prepares from the live parameters.
+ *   - Lifting head: while frozen, egotap_lift_forward / egotap_lift_predict_pose on the bf16-storage route (EGOTAP_PREC_BF16, vit_dim 1024, a
+ *     sequence that is a multiple of 32, a weight scratch attached) read the bf16 weight copies and the fused q | k | v biases from the arena.
+ *     Every other parameter (biases, LayerNorm / BatchNorm tensors, embeddings) is read live as always.  Every other route (fp32, bf16x3,
+ *     ragged sequences) ignores the arena: egotap_lift_frozen_bytes reports 0 there and egotap_lift_freeze fails, naming the reason.
+ *   - Estimators: while frozen, egotap_hm_forward in EGOTAP_PREC_BF16 at sides 64 / 128 reads the packed weights, padded biases and folded
+ *     BatchNorms (running statistics) from the arena; the stem's weight and BatchNorm are read live.  The packed layout depends on the batch
+ *     (below a pixel count a convolution's weights are packed in 32-channel slabs for the split-K kernel, above it in 64-channel slabs): the
+ *     arena holds the layout of the batch B it was built for.  A call at a batch with another layout does not read it and packs per call, as
+ *     if not frozen; the library decides per call.  Other precisions / sides: bytes = 0, freeze fails by name.
+ *   - Staleness is the caller's business with one exception the library can see: egotap_bind_param with a DIFFERENT pointer for a tensor whose
+ *     prepared copy is kept, and every egotap_set_precision, unfreeze (the lifting head and both estimators for set_precision; the net
+ *     concerned for bind_param).  A stale arena is never read silently after those.  Writing new values into the same parameter memory is
+ *     invisible to the library: freeze again afterwards.
+ *   - Training never reads an arena: egotap_lift_forward_train / egotap_lift_backward* build their own copies in `saved`, and
+ *     egotap_hm_forward_bnbatch (batch statistics) packs per call, so their results do not depend on whether the handle is frozen. */
+int egotap_lift_frozen_bytes(egotap_handle h, size_t* bytes);
+int egotap_lift_freeze(egotap_handle h, void* arena, size_t bytes, void* stream);
+int egotap_lift_unfreeze(egotap_handle h);
+int egotap_hm_frozen_bytes(egotap_handle h, int net, int B, size_t* bytes);
+int egotap_hm_freeze(egotap_handle h, int net, int B, void* arena, size_t bytes, void* stream);
+int egotap_hm_unfreeze(egotap_handle h, int net);
+
 
 /* ---- single operators (same kernels the forward uses; exported for unit tests and reuse) ---- */
 /* y = epi(x W^T + b): nn.Linear (+ residual / exact GELU / BatchNorm1d-eval + LeakyReLU 0.2).
