@@ -87,6 +87,36 @@ struct SEpiHeatNCHW {        // conv_heatmap: out f32 NCHW = acc + bias at out +
 
 template <> struct s_epi_exact<SEpiHeatNCHW> { static constexpr bool value = false; };
 
+// conv_heatmap, hand-off form (egotap_predict_pose_rgb with heatmaps == NULL): out bf16 = rne(acc + bias) straight into the tensor the
+// lifting head's bf16-storage loaders gather from -- bf16 [B, 6J, HW], the layout XPatch (patch embedding) and XRot / X64RotS (rotation fc1)
+// address, which the head otherwise fills with f32_to_bf16_kernel from the fp32 heatmaps.  The same (__bf16) rounding of the same fp32
+// sum as that kernel applies: the head's operands keep their bits and the fp32 NCHW tensor is never written.  One writer per element, no
+// atomics, nothing to clear.  The GEMM's rows are pixels and this layout keeps a channel's pixels contiguous, so the epilogue is a
+// column-wise one (s_epi_colwise, gemm_bf16s.h): a lane takes 8 consecutive pixels of one channel out of the wave's patch and stores them
+// as ONE 16-byte vector (HW is a multiple of 16 and the tile rows start at multiples of 16: the 8 pixels lie in one image, 16-byte aligned).
+struct SEpiHeatBf16 {
+    static constexpr int W = 4, STORES = 1;
+    const float* bias;       // N (padded) values
+    __bf16* out;             // 16-byte aligned
+    long img_stride;         // elements, a multiple of 8
+    int n_out, log2hw;
+    typedef SNoAux Col;
+    typedef SNoAux Aux;
+    __device__ __forceinline__ Col col(int n) const { return Col{}; }
+    __device__ __forceinline__ Aux fetch(int m, int n) const { return Aux{}; }
+    __device__ __forceinline__ void emit_col(const float* v, int m, int n) const {
+        if (n >= n_out) return;
+        const float b = bias[n];
+        const int img = m >> log2hw, pix = m & ((1 << log2hw) - 1);
+        bf16x8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (__bf16)(v[i] + b);
+        *(bf16x8*)(out + (long)img * img_stride + ((long)n << log2hw) + pix) = o;
+    }
+};
+template <> struct s_epi_colwise<SEpiHeatBf16> { static constexpr bool value = true; };
+template <> struct s_epi_exact<SEpiHeatBf16> { static constexpr bool value = false; };
+
 // ---------------------------------------------------------------------------------------------------- helpers
 // [Cout][Cin][3][3] f32 -> [Np][Cp / 32][tap][32] bf16 (channels past Cin and rows past Cout zero).  One thread = 8 consecutive ci of one (co, tap).
 static __global__ __launch_bounds__(256) void pack_conv3x3_bf16s_kernel(const float* __restrict__ w, __bf16* __restrict__ wb, int Cout, int Cin, int Cp,

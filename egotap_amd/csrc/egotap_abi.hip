@@ -162,6 +162,7 @@ struct egotap_handle_s {
     char* hm_arena[EGOTAP_NET_COUNT] = {nullptr, nullptr, nullptr};       // pack_all_bf16s_kernel's region of one estimator
     short hm_arena_slab[EGOTAP_NET_COUNT][PackTable::MAXW] = {};          // ... and the K-slab depth of every packed weight in it: the part of the
     int hm_arena_nw[EGOTAP_NET_COUNT] = {0, 0, 0};                        // layout that depends on the batch (hm_pack_plan)
+    int rgb_form = 0;                  // EGOTAP_RGB_FORM_*: how the last egotap_predict_pose_rgb handed the heatmaps to the head (egotap_debug.h)
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;   // start/stop pairs
@@ -1019,12 +1020,26 @@ static LiftFrozen lift_frozen_plan(const Handle* h, const LiftParams* p, PrepTab
     return f;
 }
 
+// EGOTAP_PREC_BF16 at a batch that fills the chip: whether the forward keeps its activations in bf16 (below).  One rule for the forward and for
+// egotap_predict_pose_rgb, which asks it whether the head will read a bf16 copy of the heatmaps.
+#ifndef EGOTAP_BF16S_MIN_ROWS
+#define EGOTAP_BF16S_MIN_ROWS 512       // [r4] 4096 before: a B = 4 forward (2304 rows) took 2.1 ms on the fp32-tensor path, 1.5 ms on this one (B = 1: 1.46 -> 1.38)
+#endif
+static bool lift_bf16s_route(const Handle* h, int B) {
+    // (sequence lengths that are not a multiple of 32 -- heatmap sides 32, 48, 96 ...: the bf16-storage attention tiles whole 32-key blocks -- stay on
+    // fp32 tensors with bf16 products in the GEMMs and the exact-fp32 attention kernel, which masks a ragged last key tile)
+    return h->precision == EGOTAP_PREC_BF16 && h->D == 1024 && (long)B * h->seq >= EGOTAP_BF16S_MIN_ROWS && h->wscratch != nullptr && h->seq % 32 == 0 &&
+           h->wscratch_bytes >= (size_t)2 * 2048 * (size_t)(h->ppd * h->ppd * h->D);
+}
+
+// hmb_ready != nullptr (egotap_predict_pose_rgb's hand-off; the bf16-storage route only): the heatmaps as bf16 [B, 6J, S, S] already, exactly what
+// f32_to_bf16_kernel would make of `hm`; hm is then not read and may be null
 static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, void* ws, size_t ws_bytes, void* stream, bool pose_only,
-                             const char* who) {
+                             const char* who, const __bf16* hmb_ready = nullptr) {
     EGO_CHECK(h, "null handle");
     if (B == 0) return EGOTAP_OK;
-    EGO_CHECK(B > 0 && hm && pose && ws, "%s: null argument or negative batch", who);
-    EGO_CHECK(((uintptr_t)hm & 15) == 0 && ((uintptr_t)ws & 255) == 0, "hm must be 16-byte and ws 256-byte aligned");
+    EGO_CHECK(B > 0 && (hm || hmb_ready) && pose && ws, "%s: null argument or negative batch", who);
+    EGO_CHECK((((uintptr_t)hm | (uintptr_t)hmb_ready) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "hm must be 16-byte and ws 256-byte aligned");
     int rc = lift_resolve(h);
     if (rc != EGOTAP_OK) return rc;
     const LiftWs w = lift_ws(h, B);
@@ -1048,14 +1063,8 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
     // EGOTAP_PREC_BF16 at a batch that fills the chip: bf16 ACTIVATION STORAGE (the same workspace slices hold bf16): LayerNorm, the
     // GEMM epilogues and attention write bf16, every GEMM reads bf16 operands through the LDS DMA (gemm_bf16s.h); weights are rounded
     // into the caller's weight scratch right before each launch (nothing cached: the fp32 parameters stay the source of truth)
-#ifndef EGOTAP_BF16S_MIN_ROWS
-#define EGOTAP_BF16S_MIN_ROWS 512       // [r4] 4096 before: a B = 4 forward (2304 rows) took 2.1 ms on the fp32-tensor path, 1.5 ms on this one (B = 1: 1.46 -> 1.38)
-#endif
-    constexpr int g_bf16s_min_rows = EGOTAP_BF16S_MIN_ROWS;
-    // (sequence lengths that are not a multiple of 32 -- heatmap sides 32, 48, 96 ...: the bf16-storage attention tiles whole 32-key blocks -- stay on
-    // fp32 tensors with bf16 products in the GEMMs and the exact-fp32 attention kernel, which masks a ragged last key tile)
-    const bool bf16s = h->precision == EGOTAP_PREC_BF16 && D == 1024 && M >= g_bf16s_min_rows && h->wscratch != nullptr && h->seq % 32 == 0 &&
-                       h->wscratch_bytes >= (size_t)2 * 2048 * (size_t)(h->ppd * h->ppd * D);
+    const bool bf16s = lift_bf16s_route(h, B);
+    EGO_CHECK(bf16s || hmb_ready == nullptr, "%s: a bf16 heatmap operand was handed to a route that reads fp32 heatmaps", who);
     // frozen (egotap_lift_freeze): the same GEMMs read the arena's copies -- the same bits the per-call preparation would write -- and no
     // prep_weight_kernel / concat3_kernel is launched.  Every other route ignores the arena.
     const bool frozen = bf16s && h->lift_arena != nullptr;
@@ -1064,9 +1073,9 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
     // H1+H2: tile -> patch embed -> mask token -> + position embeddings
     if (bf16s) {
         // [r3] on the bf16-storage GEMM: the heatmaps' bf16 copy in the (still free) MLP buffer, by LDS DMA; zeros for the dummy cells in SPK
-        __bf16* hmb0 = (__bf16*)HID;
+        const __bf16* hmb0 = hmb_ready ? hmb_ready : (const __bf16*)HID;
         const long n8 = (long)B * h->C * HW / 8;
-        hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, hmb0, n8);
+        if (!hmb_ready) hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, (__bf16*)HID, n8);
         if (!frozen) hipLaunchKernelGGL(prep_weight_kernel, dim3((256 + 63) / 64, (D + 63) / 64), dim3(256), 0, s, p.patch_w, h->wscratch, (__bf16*)nullptr, D, 256, (long)D);
         EGO_HIP(zero_fill(SPK, 256, s));
         const XPatch xl{hmb0, (const __bf16*)SPK, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
@@ -1130,9 +1139,9 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
             EGO_HIP((fc_gemm(h, "pos_fc3", ALoadPlain{Z2, 512}, segmat1(p.pos_fc[2].w, hid, 512), bn(p.pos_fc[2]), POSZ, hid, BT, hid, 512, SPK, s)));
         }
         {
-            __bf16* hmb = HIDb;                             // the MLP's hidden buffer is free now: bf16 copy of the input heatmaps
+            const __bf16* hmb = hmb_ready ? hmb_ready : HIDb;      // the MLP's hidden buffer is free now: bf16 copy of the input heatmaps
             const long n8 = (long)B * h->C * HW / 8;
-            hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, hmb, n8);
+            if (!hmb_ready) hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, HIDb, n8);
             if (!frozen) prep(p.rot_fc[0].w, Wb, 2048, 2 * HW);
             const __bf16* W1 = frozen ? FW(fz.fc1r) : Wb;
             EGO_HIP(hipGetLastError());
@@ -1700,8 +1709,9 @@ static hipError_t hm_bf16_backbone(Handle* h, const HmParams& p, const PackTable
 }
 
 // E4-E9 on Bc frames whose pyramid levels start at lv[0..3] (layer1 .. layer4 outputs, bf16 [Bc * s^2, 2 C]); li = first decoder entry of the pack table
+// out_b != nullptr: conv_heatmap writes bf16 there instead (SEpiHeatBf16: the lifting head's bf16 operand, same image stride in elements) and `out` is not touched
 static hipError_t hm_bf16_decoder(Handle* h, const HmParams& p, const PackTable& PT, int li, const HmBf16Bufs& q, const __bf16* const* lv, int B, int S0, float* out,
-                                  int64_t out_image_stride, hipStream_t s) {
+                                  int64_t out_image_stride, hipStream_t s, __bf16* out_b = nullptr) {
     const int cus = device_cu_count();
     const int s64 = S0 / 4, s32 = S0 / 8, s16 = S0 / 16, s8 = S0 / 32;
     const long p8 = (long)s8 * s8, p16 = (long)s16 * s16, p32 = (long)s32 * s32, p64 = (long)s64 * s64;
@@ -1771,12 +1781,22 @@ static hipError_t hm_bf16_decoder(Handle* h, const HmParams& p, const PackTable&
         const PackSeg& sg = PT.w[li++];
         if (sg.w != p.head.w || li != PT.nw) return hipErrorInvalidValue;      // the pack plan is out of step with the forward
         GemmTimer t(h, s, "hm.conv_heatmap", "gemm_bf16s_kernel<XPlain,heatmap>", 2.0 * B * p64 * p.n_out * 512);
-        const SEpiHeatNCHW he{(const float*)(reg + sg.dst_b), out, (long)out_image_stride, p.n_out, hm_ilog2(p64)};
+        const float* hb = (const float*)(reg + sg.dst_b);
         const __bf16* hw = (const __bf16*)(reg + sg.dst_w);
         const int hn = hm_head_np(p.n_out);
-        if (hn == 64) HMD((gemm_bf16s_launch<XPlain, SEpiHeatNCHW, 1>(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 64, 512, cus, s)));
-        else if (hn == 128) HMD((gemm_bf16s_launch<XPlain, SEpiHeatNCHW, 2>(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 128, 512, cus, s)));
-        else HMD(gemm_bf16s_launch(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 256, 512, cus, s));
+        auto head = [&](const auto& he) -> hipError_t {      // the same product, tile and k order under either epilogue
+            using E = std::decay_t<decltype(he)>;
+            if (hn == 64) return gemm_bf16s_launch<XPlain, E, 1>(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 64, 512, cus, s);
+            if (hn == 128) return gemm_bf16s_launch<XPlain, E, 2>(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 128, 512, cus, s);
+            return gemm_bf16s_launch(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 256, 512, cus, s);
+        };
+#if EGOTAP_IN(0)      // the hand-off's only caller (egotap_predict_pose_rgb) is in part 0: its kernels are instantiated in that translation unit alone
+        if (out_b) HMD(head(SEpiHeatBf16{hb, out_b, (long)out_image_stride, p.n_out, hm_ilog2(p64)}));
+        else
+#else
+        if (out_b) return hipErrorInvalidValue;
+#endif
+        HMD(head(SEpiHeatNCHW{hb, out, (long)out_image_stride, p.n_out, hm_ilog2(p64)}));
     }
 #undef HMD
     return hipSuccess;
@@ -1883,13 +1903,13 @@ extern "C" int egotap_hm_unfreeze(egotap_handle h, int net) {
 
 // HeatMap_UnrealEgo_Shared.forward(left, right) (model/net_architecture.py:32-36, 45-51, 75-85, 139-173), eval mode.
 #if EGOTAP_IN(0)
-extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, const float* right, int B, float* out,
-                                 int64_t out_image_stride, void* ws, size_t ws_bytes, void* stream) {
-    EGO_CHECK(h, "null handle");
-    EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "egotap_hm_forward: net must be EGOTAP_NET_HM_POS or _ROT");
-    if (B == 0) return EGOTAP_OK;
-    EGO_CHECK(B > 0 && left && right && out && ws, "egotap_hm_forward: null argument or negative batch");
-    EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)out) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "pointers must be 16-byte (ws: 256-byte) aligned");
+// out_b != nullptr (egotap_predict_pose_rgb's hand-off, bf16 channels-last route only): the result as bf16 at out_b, `out` unused
+static int hm_forward_impl(Handle* h, int net, const float* left, const float* right, int B, float* out, int64_t out_image_stride, void* ws, size_t ws_bytes,
+                           void* stream, __bf16* out_b) {
+    // the bf16 channels-last route (fused stem, every convolution on the bf16-storage GEMM): hm_frozen_route is its one predicate, shared with the freeze entries
+    // and with egotap_predict_pose_rgb's hand-off, which exists on this route only -- refused here, before anything is launched
+    const bool fused_stem = hm_frozen_route(h);
+    EGO_CHECK(out_b == nullptr || fused_stem, "egotap_hm_forward: the bf16 hand-off exists on the bf16 channels-last route only");
     const int S0 = h->cfg.hm_size * 4, s64 = S0 / 4, s32 = S0 / 8, s16 = S0 / 16, s8 = S0 / 32;
     // the bf16 channels-last path and the bf16 matrix-core convolutions exist at 64 / 128 only: every other side (any multiple of 16)
     // runs the exact-fp32 path in every precision mode -- the power-of-two conv instantiations where they exist, conv_f32_any_kernel elsewhere
@@ -1921,7 +1941,6 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
     // [r3] ... bf16 mode: stem, BatchNorm, ReLU AND the max-pool in one kernel on the bf16 matrix cores (stem_bf16s.h): the 128 x 128 x 64
     // map never reaches HBM (round 2's two-kernel form -- fp32-MFMA stem writing bf16 channels-last, then a channels-last max-pool: 2.35 ms
     // against 0.66 per 512 images -- was retired in round 4).
-    const bool fused_stem = !exact && h->precision == EGOTAP_PREC_BF16;
     if (!fused_stem)
         EGO_HIP(stem_conv7_launch(left, right, p.stem_w, p.stem_bn.g, p.stem_bn.b, p.stem_bn.m, p.stem_bn.v, F(w.L0), S0, N2, device_cu_count(), s));
     if (fused_stem) {
@@ -1951,7 +1970,7 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
         int li = 0, bi = 0;
         EGO_HIP(hm_bf16_backbone(h, p, PT, li, bi, q, left, right, B, S0, nullptr, s));
         const __bf16* lv[4] = {q.A[0], q.A[1], q.A[2], q.A[3]};
-        EGO_HIP(hm_bf16_decoder(h, p, PT, li, q, lv, B, S0, out, out_image_stride, s));
+        EGO_HIP(hm_bf16_decoder(h, p, PT, li, q, lv, B, S0, out, out_image_stride, s, out_b));
         EGO_CHECK(bi == PT.nb, "egotap_hm_forward: pack plan out of step with the forward");
         return EGOTAP_OK;
     }
@@ -2017,6 +2036,94 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
     EGO_HIP(biasconv("hm.layer1_1x1", 1, s64, L1, 128 * p64, p.l1x1[0], 128, 128, CAT1 + 512 * p64, 640 * p64, 1));
     EGO_HIP(biasconv("hm.conv_up1", 9, s64, CAT1, 640 * p64, p.up[0], 640, 512, X1, 512 * p64, 1));
     EGO_HIP(biasconv("hm.conv_heatmap", 1, s64, X1, 512 * p64, p.head, 512, p.n_out, out, out_image_stride, 0));
+    return EGOTAP_OK;
+}
+
+extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, const float* right, int B, float* out,
+                                 int64_t out_image_stride, void* ws, size_t ws_bytes, void* stream) {
+    EGO_CHECK(h, "null handle");
+    EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "egotap_hm_forward: net must be EGOTAP_NET_HM_POS or _ROT");
+    if (B == 0) return EGOTAP_OK;
+    EGO_CHECK(B > 0 && left && right && out && ws, "egotap_hm_forward: null argument or negative batch");
+    EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)out) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "pointers must be 16-byte (ws: 256-byte) aligned");
+    return hm_forward_impl(h, net, left, right, B, out, out_image_stride, ws, ws_bytes, stream, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ stereo RGB -> pose in one call
+// egotap_predict_pose_rgb: both estimators (eval mode, in pieces of `chunk` frames, one U-Net scratch) and then the pose-only head, composed from
+// hm_forward_impl and lift_forward_impl -- every kernel choice is theirs.  Workspace: [ scratch = max(estimator scratch of a chunk, head scratch of the
+// batch): the two never run at once | the heatmaps: fp32 [B, 6J, S, S] when the caller passes none, or their bf16 hand-off form ].
+struct RgbWs { size_t HM, total; };
+static inline int rgb_chunk(int B, int chunk) { return chunk <= 0 || chunk > B ? B : chunk; }
+static RgbWs rgb_ws(const Handle* h, int B, int chunk) {
+    const size_t a = hm_ws(h, rgb_chunk(B, chunk)).total, b = lift_ws(h, B).total;
+    RgbWs w;
+    w.HM = al256(a > b ? a : b);
+    w.total = w.HM + al256((size_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size * 4);
+    return w;
+}
+// The hand-off: nobody asked for the fp32 heatmaps, the estimators run the bf16 channels-last route (whose conv_heatmap is the bf16-storage GEMM) and
+// the head runs its bf16-storage route (which reads a bf16 copy of the heatmaps and nothing else of them): conv_heatmap then writes that copy itself.
+static bool rgb_handoff(const Handle* h, int B, const float* heatmaps) { return heatmaps == nullptr && hm_frozen_route(h) && lift_bf16s_route(h, B); }
+
+extern "C" int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
+    EGO_CHECK(h && bytes, "egotap_predict_pose_rgb_workspace_bytes: null argument");
+    EGO_CHECK(B >= 0 && chunk >= 0, "egotap_predict_pose_rgb_workspace_bytes: negative batch or chunk");
+    *bytes = rgb_ws(h, B > 0 ? B : 1, chunk).total;
+    return EGOTAP_OK;
+}
+
+extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                                       size_t ws_bytes, void* stream) {
+    static const char* const who = "egotap_predict_pose_rgb";
+    EGO_CHECK(h, "%s: null handle", who);
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(left && right && pose && ws, "%s: null argument (left, right, pose and ws are required; only heatmaps may be NULL)", who);
+    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
+    EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0,
+              "%s: left, right, pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
+    static const char* const net_name[EGOTAP_NET_COUNT] = {"the lifting head", "the position estimator", "the limb estimator"};
+    for (int net = 0; net < EGOTAP_NET_COUNT; ++net) {
+        if ((net == EGOTAP_NET_LIFT ? lift_resolve(h) : hm_resolve(h, net)) != EGOTAP_OK) {
+            const std::string key = g_err;
+            egotap_set_error("%s: unbound parameter of %s: %s", who, net_name[net], key.c_str());
+            return EGOTAP_ERR_INVALID;
+        }
+    }
+    const RgbWs w = rgb_ws(h, B, chunk);
+    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small: %zu bytes given, %zu needed for B=%d, chunk=%d", who, ws_bytes, w.total, B, chunk);
+    const int c = rgb_chunk(B, chunk), S = h->cfg.hm_size, HW = S * S, J = h->J;
+    const long img = (long)h->C * HW, rgb = 3L * (4 * S) * (4 * S);
+    const bool handoff = rgb_handoff(h, B, heatmaps);
+    float* hm = heatmaps ? heatmaps : (float*)((char*)ws + w.HM);
+    __bf16* hmb = handoff ? (__bf16*)((char*)ws + w.HM) : nullptr;
+    h->rgb_form = EGOTAP_RGB_FORM_NONE;
+    // position net: channels [0, 2J) (left | right); limb net: [2J, 6J) (left cos, sin | right cos, sin)
+    const int nets[2] = {EGOTAP_NET_HM_POS, EGOTAP_NET_HM_ROT}, c0[2] = {0, 2 * J};
+    for (int k = 0; k < 2; ++k)
+        for (int lo = 0; lo < B; lo += c) {
+            const int n = B - lo < c ? B - lo : c;
+            const long at = lo * img + (long)c0[k] * HW;
+            const int rc = hm_forward_impl(h, nets[k], left + lo * rgb, right + lo * rgb, n, handoff ? nullptr : hm + at, img, ws, w.HM, stream, handoff ? hmb + at : nullptr);
+            if (rc != EGOTAP_OK) return rc;
+        }
+    const int rc = lift_forward_impl(h, handoff ? nullptr : hm, B, pose, ws, w.HM, stream, true, who, hmb);
+    if (rc != EGOTAP_OK) return rc;
+    h->rgb_form = handoff ? EGOTAP_RGB_FORM_HANDOFF : heatmaps ? EGOTAP_RGB_FORM_HEATMAPS : EGOTAP_RGB_FORM_SCRATCH;
+    return EGOTAP_OK;
+}
+
+extern "C" int egotap_debug_predict_pose_rgb_form(egotap_handle h, int* form) {
+    EGO_CHECK(h && form, "egotap_debug_predict_pose_rgb_form: null argument");
+    *form = h->rgb_form;
+    return EGOTAP_OK;
+}
+extern "C" int egotap_debug_predict_pose_rgb_intermediate(egotap_handle h, int B, int chunk, const char* name, size_t* offset, int64_t* numel) {
+    EGO_CHECK(h && name && offset && numel, "egotap_debug_predict_pose_rgb_intermediate: null argument");
+    EGO_CHECK(B > 0 && chunk >= 0, "egotap_debug_predict_pose_rgb_intermediate: the batch must be positive, the chunk not negative");
+    EGO_CHECK(!strcmp(name, "heatmaps") || !strcmp(name, "handoff"), "egotap_debug_predict_pose_rgb_intermediate: unknown intermediate '%s' (heatmaps, handoff)", name);
+    *offset = rgb_ws(h, B, chunk).HM;
+    *numel = (int64_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size;
     return EGOTAP_OK;
 }
 #endif

@@ -114,6 +114,10 @@ struct SNoAux {};
 // false for an epilogue whose emit() may skip its stores for whole waves (column guards): the main loop then gives the previous
 // tile's stores no allowance in its vmcnt waits (the allowance must never exceed the stores really in flight)
 template <class E> struct s_epi_exact { static constexpr bool value = true; };
+// true for an epilogue whose output keeps a COLUMN's rows contiguous (rows = pixels of a channel-major map): the kernels then read the per-wave
+// patch column-wise -- a lane takes 8 consecutive rows of one column -- and call emit_col(v, m, n): v[0..8) = accumulators of rows m..m+7 (m a
+// multiple of 8, all below M) of column n -> one 16-byte store.  The row-wise read-out (emit) is not compiled for such an epilogue.
+template <class E> struct s_epi_colwise { static constexpr bool value = false; };
 // "use" of a loaded value outside any lane predicate: the compiler then waits for the load HERE.  Without it a value whose only
 // uses sit under `if (m < M)` counts as possibly pending at the loop's back edge, and the waitcnt pass protects the registers it
 // lands in with vmcnt(0) waits in the middle of the main loop (they are reused as fragment registers there).
@@ -522,6 +526,20 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
             }
             const int m0 = m_wave + mi * 16;
             if (mi == 0) s_keep(cc);
+            if constexpr (s_epi_colwise<Epi>::value) {
+                // patch[16 m][64 n] read by columns: lane = column, two pieces of 8 consecutive rows; element (r, n) sits at chunk (n >> 2) ^ r of row r, so
+                // the 64 lanes of one read hit 64 different words of that row (no bank conflict)
+#pragma unroll
+                for (int g8 = 0; g8 < 2; ++g8) {
+                    float vv[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int r = 8 * g8 + i;
+                        vv[i] = Es[r * 64 + (((lane >> 2) ^ r) << 2) + (lane & 3)];
+                    }
+                    if (lane < 16 * NI && m0 + 8 * g8 < M) epi.emit_col(vv, m0 + 8 * g8, n_wave + lane);
+                }
+            } else
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
                 const int r = (16 / IT) * it + er;

@@ -11,6 +11,7 @@ ERR_NAMES = {1: "EGOTAP_ERR_INVALID", 2: "EGOTAP_ERR_HIP", 3: "EGOTAP_ERR_UNBOUN
 NET_LIFT, NET_HM_POS, NET_HM_ROT = 0, 1, 2
 F32, I64 = 0, 1
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}      # egotap.h EGOTAP_PREC_*
+RGB_FORMS = {0: "none", 1: "heatmaps", 2: "scratch", 3: "handoff"}      # egotap_debug.h EGOTAP_RGB_FORM_*
 
 
 class EgotapConfig(C.Structure):
@@ -35,6 +36,11 @@ _PROTOS = {
     "egotap_lift_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
     "egotap_lift_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "egotap_lift_predict_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- stereo RGB -> pose in one call
+    "egotap_predict_pose_rgb_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "egotap_predict_pose_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_debug_stop": (C.c_int, [C.c_void_p, C.c_int]),
     "egotap_set_precision": (C.c_int, [C.c_void_p, C.c_int]),

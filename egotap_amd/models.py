@@ -330,6 +330,225 @@ class EgoTAPAutoEncoderModel(nn.Module):
             runnning_average_dict.update(dict(mpjpe=err[i], pa_mpjpe=pa[i]))
         return self.pred_pose, self.pred_heatmap_cat, runnning_average_dict
 
+    # ---- serving: stereo RGB -> pose in one call (egotap.h egotap_predict_pose_rgb) ------------------------------
+    def _rgb_one_call_refusal(self):
+        """None when the three networks can share ONE library handle (egotap_predict_pose_rgb), else the reason they cannot"""
+        nets = (self.net_HeatMap, self.net_RotHeatMap, self.net_AutoEncoder)
+        for n in nets[:2]:
+            if n.bottleneck:
+                return f"{n.model_name} estimators have no one-call forward (Bottleneck blocks are composed on the host)"
+        if nets[0].blocks != nets[1].blocks:
+            return "the two estimators have different backbones"
+        prec = {getattr(n, "precision", "f32") for n in nets}
+        if len(prec) != 1:
+            return f"the three networks run in different precisions {sorted(prec)} (a handle has one)"
+        return None
+
+    def _rgb_state(self, dev):
+        """The serving handle: all three networks' tensors bound to ONE egotap handle, in the networks' precision, with the head's bf16 scratch
+        buffers attached and -- for every network that is frozen -- that network's own arena (prepared once more through this handle: the same
+        kernel writes the same bytes).  Nothing here changes a network: flags, precision and frozen state are read, never set."""
+        from . import lib as _lib
+        import ctypes as C
+        lib = _lib.load()
+        st = self.__dict__.setdefault("_rgb", {"handle": None, "sig": None, "precision": None, "wscratch": None, "ascratch": None,
+                                               "frozen": [None, None, None], "ws": None, "chunk": None, "graphs": {}})
+        lift, pos, rot = self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap
+        nets = ((_lib.NET_LIFT, lift), (_lib.NET_HM_POS, pos), (_lib.NET_HM_ROT, rot))
+        if st["handle"] is None:
+            p = lift.preset
+            cfg = _lib.EgotapConfig(C.sizeof(_lib.EgotapConfig), p.n_joints_hm, int(p.estimate_head), p.hm_size, p.hidden, p.vit_dim, p.vit_heads,
+                                    p.vit_layers, p.patch, p.pu_hidden, (C.c_int32 * 4)(*pos.blocks))
+            h = C.c_void_p()
+            _lib.check(lib.egotap_create(C.byref(cfg), C.byref(h)))
+            st["handle"] = h
+            if lift._shared_device or os.environ.get("EGOTAP_SHARED_DEVICE", "0") == "1":
+                _lib.check(lib.egotap_set_pu_chain(h, 0))
+        h = st["handle"]
+        tensors = []
+        for net_id, n in nets:
+            sd = dict(n.named_parameters()) if n is lift else n.state_dict(keep_vars=True)
+            if n is lift:
+                sd.update(dict(n.named_buffers()))
+            tensors += [(net_id, k, t) for k, t in sd.items()]
+        sig = tuple((net_id, k, t.data_ptr()) for net_id, k, t in tensors)
+        if sig != st["sig"]:
+            for net_id, k, t in tensors:
+                dt = _lib.F32 if t.dtype == torch.float32 else (_lib.I64 if t.dtype == torch.long else None)
+                if t.device != dev or dt is None or not t.is_contiguous():
+                    raise _lib.EgotapError(f"parameter {k}: need a contiguous fp32 tensor (or int64 counter) on {dev}")
+                _lib.check(lib.egotap_bind_param(h, net_id, k.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt))
+            st["sig"], st["frozen"] = sig, [None, None, None]        # (a moved tensor unfreezes its network inside the library)
+        prec = getattr(lift, "precision", "f32")
+        if prec != st["precision"]:
+            _lib.check(lib.egotap_set_precision(h, _lib.PRECISIONS[prec]))
+            st["precision"], st["frozen"], st["wscratch"], st["ascratch"] = prec, [None, None, None], None, None
+            _lib.check(lib.egotap_set_weight_scratch(h, None, 0))
+            _lib.check(lib.egotap_set_act_scratch(h, None, 0))
+        if prec == "bf16":
+            wsc = getattr(lift, "_wscratch", None)
+            if wsc is not None and wsc.device == dev and st["wscratch"] is not wsc:
+                _lib.check(lib.egotap_set_weight_scratch(h, C.c_void_p(wsc.data_ptr()), wsc.numel()))
+                st["wscratch"] = wsc
+        for i, (net_id, n) in enumerate(nets):
+            if n.weights_frozen:
+                n._bind(dev)
+                n._frozen_check(dev)           # stale prepared weights are redone by their owner, into the arena this handle reads too
+                key = (n._frozen_arena.data_ptr(), getattr(n, "_frozen_batch", 0))
+                if st["frozen"][i] != key:
+                    arena, stream = C.c_void_p(n._frozen_arena.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                    if n is lift:
+                        _lib.check(lib.egotap_lift_freeze(h, arena, n._frozen_arena.numel(), stream))
+                    else:
+                        _lib.check(lib.egotap_hm_freeze(h, net_id, n._frozen_batch, arena, n._frozen_arena.numel(), stream))
+                    st["frozen"][i] = key
+            elif st["frozen"][i] is not None:
+                _lib.check(lib.egotap_lift_unfreeze(h) if n is lift else lib.egotap_hm_unfreeze(h, net_id))
+                st["frozen"][i] = None
+        return st
+
+    def _rgb_attach_act_scratch(self, st, B, dev):
+        from . import lib as _lib
+        import ctypes as C
+        lift = self.net_AutoEncoder
+        lift._act_scratch(B, dev)              # (bf16 below the bf16-storage route's batch only; grown with the batch)
+        asc = getattr(lift, "_ascratch", None)
+        if st["precision"] == "bf16" and asc is not None and st["ascratch"] is not asc:
+            _lib.check(_lib.load().egotap_set_act_scratch(st["handle"], C.c_void_p(asc.data_ptr()), asc.numel()))
+            st["ascratch"] = asc
+
+    def rgb_form(self):
+        """how the last predict_pose_from_rgb call handed the heatmaps to the head (egotap_debug.h): "heatmaps" (fp32, returned), "scratch"
+        (fp32, inside the workspace), "handoff" (conv_heatmap wrote the head's bf16 operand; no fp32 heatmaps), or "none" """
+        from . import lib as _lib
+        import ctypes as C
+        st = self.__dict__.get("_rgb")
+        if st is None or st["handle"] is None:
+            return "none"
+        form = C.c_int()
+        _lib.check(_lib.load().egotap_debug_predict_pose_rgb_form(st["handle"], C.byref(form)))
+        return _lib.RGB_FORMS[form.value]
+
+    @torch.no_grad()
+    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False):
+        """Serving entry: stereo RGB [B, 3, 4S, 4S] x 2 -> pose [B, J(+1), 3], or (pose, heatmaps [B, 6J, S, S]) with ``return_heatmaps``.
+        Replaces set_input() + evaluate() (utils/evaluate.py:104-114 without the metrics; egotap_autoencoder_model.py:177-223) for a caller
+        that has no ground truth: no set_input, no loader keys, no autograd.  ONE library call (egotap_predict_pose_rgb): both estimators in
+        eval mode (folded running statistics) in pieces of min(B, opt.hm_chunk) frames, then the pose-only head -- the same kernels, in
+        the same order, as evaluate() on an eval-mode model, hence the same bits.  The networks' ``.training`` flags and precision are
+        neither read for routing nor changed (this entry IS the inference forward); frozen networks (freeze_weights) are read from their
+        arenas.  Without ``return_heatmaps`` in "bf16" precision at sides 64 / 128 the fp32 heatmaps are never written: conv_heatmap hands
+        the head its bf16 operand directly (same pose bits; ``rgb_form()`` tells).
+
+        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps), with static input
+        and output buffers as ``net_AutoEncoder.predict_pose_graphed``: the returned tensors are the graph's own (valid until the next call
+        with the same key).
+
+        By name, not through the one call: resnet50 / resnet101 estimators (no one-call forward), estimators with different backbones and
+        networks set to different precisions run the existing module forwards (``forward_into`` x 2, chunked) followed by
+        ``net_AutoEncoder.predict_pose`` -- ungraphed (``graphed=True`` raises there), and only with eval-mode networks."""
+        from . import lib as _lib
+        import ctypes as C
+        p = self.net_AutoEncoder.preset
+        S0 = 4 * p.hm_size
+        for t in (left, right):
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise _lib.EgotapError("predict_pose_from_rgb runs on the GPU only (no CPU fallback); move the frames to cuda")
+        B = left.shape[0]
+        if tuple(left.shape) != (B, 3, S0, S0) or tuple(right.shape) != (B, 3, S0, S0):
+            raise ValueError(f"expected left / right [B, 3, {S0}, {S0}], got {tuple(left.shape)} / {tuple(right.shape)}")
+        dev = left.device
+        left, right = left.detach().float().contiguous(), right.detach().float().contiguous()
+        chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
+        why = self._rgb_one_call_refusal()
+        if why is not None:
+            if graphed:
+                raise _lib.EgotapError(f"predict_pose_from_rgb(graphed=True): {why}; this configuration runs the module forwards, ungraphed")
+            # the modules' inference forwards refuse train mode (theirs is then the differentiable path): say so before anything runs
+            for name in self.model_names:
+                if getattr(self, "net_" + name).training:
+                    raise _lib.EgotapError(f"predict_pose_from_rgb: {why}; this configuration runs the module forwards, which need net_{name} in "
+                                           "eval mode (model.eval())")
+            cat = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev)
+            J = p.n_joints_hm
+            same = self.net_HeatMap.blocks == self.net_RotHeatMap.blocks          # one scratch for both estimators where their sizes agree
+            for net, c0 in ((self.net_HeatMap, 0), (self.net_RotHeatMap, 2 * J)):
+                ws = None if net.bottleneck else (self.net_HeatMap if same else net)._workspace(chunk, dev)
+                for lo in range(0, B, chunk):
+                    net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
+            pose = self.net_AutoEncoder.predict_pose(cat)
+            return (pose, cat) if return_heatmaps else pose
+        pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
+        hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
+        if B == 0:
+            return (pose, hm) if return_heatmaps else pose
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            st = self._rgb_state(dev)
+            self._rgb_attach_act_scratch(st, B, dev)
+            h = st["handle"]
+            need = C.c_size_t()
+            _lib.check(lib.egotap_predict_pose_rgb_workspace_bytes(h, B, chunk, C.byref(need)))
+
+            def call(l, r, po, hmo, ws):
+                _lib.check(lib.egotap_predict_pose_rgb(h, C.c_void_p(l.data_ptr()), C.c_void_p(r.data_ptr()), B, C.c_void_p(po.data_ptr()),
+                                                       C.c_void_p(hmo.data_ptr()) if hmo is not None else None, chunk, C.c_void_p(ws.data_ptr()),
+                                                       ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            if not graphed:
+                if st["ws"] is None or st["ws"].numel() < need.value or st["ws"].device != dev:
+                    st["ws"] = None
+                    st["ws"] = torch.empty(need.value, dtype=torch.uint8, device=dev)
+                st["chunk"] = chunk
+                call(left, right, pose, hm, st["ws"])
+                return (pose, hm) if return_heatmaps else pose
+            # one graph per (batch, heatmaps wanted, precision, frozen arenas, bound tensors, chunk): every pointer a captured launch takes is baked
+            # in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch buffers and arenas alive
+            key = (B, bool(return_heatmaps), st["precision"], tuple(st["frozen"]), st["sig"], chunk, str(dev))
+            g = st["graphs"].get(key)
+            if g is None:
+                s_l, s_r = left.clone(), right.clone()
+                ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+                keep = (ws, st["wscratch"], st["ascratch"]) + tuple(n._frozen_arena for n in (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
+                                                                    if n.weights_frozen)
+                side = torch.cuda.Stream(dev)
+                side.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(side):
+                    call(s_l, s_r, pose, hm, ws)               # eager once: occupancy queries and kernel attributes are settled here
+                torch.cuda.current_stream(dev).wait_stream(side)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, stream=side):
+                    call(s_l, s_r, pose, hm, ws)
+                if len(st["graphs"]) >= 8:                     # a handful of serving batch sizes; drop the oldest beyond that
+                    st["graphs"].pop(next(iter(st["graphs"])))
+                g = st["graphs"][key] = (graph, s_l, s_r, pose, hm, keep)
+            graph, s_l, s_r, pose, hm, _ = g
+            s_l.copy_(left)
+            s_r.copy_(right)
+            graph.replay()
+        return (pose, hm) if return_heatmaps else pose
+
+    def rgb_intermediate(self, name: str, B: int):
+        """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity
+        tests; egotap_debug.h): "heatmaps" -> fp32 [B, 6J, S, S] after a "scratch" call, "handoff" -> bfloat16 [B, 6J, S, S] after a "handoff" call"""
+        from . import lib as _lib
+        import ctypes as C
+        st, p = self.__dict__.get("_rgb"), self.net_AutoEncoder.preset
+        if st is None or st["ws"] is None or st["chunk"] is None:
+            raise _lib.EgotapError("rgb_intermediate: no ungraphed one-call predict_pose_from_rgb has run on this model yet (a graph keeps its own workspace)")
+        off, n = C.c_size_t(), C.c_int64()
+        _lib.check(_lib.load().egotap_debug_predict_pose_rgb_intermediate(st["handle"], B, st["chunk"], name.encode(), C.byref(off), C.byref(n)))
+        dt, sz = (torch.bfloat16, 2) if name == "handoff" else (torch.float32, 4)
+        return st["ws"][off.value: off.value + sz * n.value].view(dt).view(B, p.in_channels, p.hm_size, p.hm_size)
+
+    def __del__(self):
+        try:
+            st = self.__dict__.get("_rgb")
+            if st is not None and st["handle"] is not None:
+                from . import lib as _lib
+                _lib.load().egotap_destroy(st["handle"])
+        except Exception:
+            pass
+
     # ---- checkpoints (base_model.py:64-148 file naming) --------------------------------------------------------
     def save_networks(self, which_epoch=None, checkpoint_path=None):
         if which_epoch is None and checkpoint_path is None:

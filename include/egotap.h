@@ -125,6 +125,29 @@ int egotap_hm_forward_bnbatch(egotap_handle h, int net, const float* left, const
  * "layer4"}; bf16 [B * s * s, 2 C], pixel (b, y, x) = [left C | right C]; offset in bytes, numel in bf16 elements */
 int egotap_hm_forward_bnbatch_intermediate(egotap_handle h, int B, int chunk, const char* name, size_t* offset, int64_t* numel);
 
+/* ---- stereo RGB -> pose in one call (serving; needs no ground truth) ----
+ * What utils/evaluate.py:104-114 does per batch without the metrics -- model.set_input(data) + model.evaluate() -- i.e. the wrapper's
+ * forward_heatmap() + net_AutoEncoder.predict_pose() (model/egotap_autoencoder_model.py:177-223) on a handle that has all three networks bound:
+ * both estimators in eval mode (folded running statistics) in pieces of `chunk` frames (0 = the whole batch; a piece is what one
+ * egotap_hm_forward call would get, so a frame's heatmaps are those of egotap_hm_forward at that piece's size), sharing one U-Net scratch, then
+ * the head through the egotap_lift_predict_pose route.  Every kernel is the one the separate entries choose for the handle's precision and heatmap
+ * side, and the arenas of egotap_lift_freeze / egotap_hm_freeze are honoured as those entries honour them.
+ *   left, right  device f32 [B, 3, 4*hm_size, 4*hm_size]
+ *   pose         device f32 [B, n_joints_hm + estimate_head, 3]          (egotap_lift_predict_pose's layout)
+ *   heatmaps     NULL, or device f32 [B, 6*n_joints_hm, hm_size, hm_size]: the head's input (position net -> channels [0, 2J), limb net ->
+ *                [2J, 6J)), the same bits as egotap_hm_forward writes
+ *   ws           device scratch of at least egotap_predict_pose_rgb_workspace_bytes(B, chunk), 256-byte aligned
+ * The workspace holds one fp32 [B, 6J, S, S] slot for the heatmaps whatever the call passes (one size per (B, chunk): a server sizes it once); a caller
+ * that passes `heatmaps` does not use the slot, the hand-off uses half of it.
+ * heatmaps == NULL: the heatmaps live in ws.  In EGOTAP_PREC_BF16 at heatmap sides 64 / 128, where the head takes its bf16-storage route (a
+ * weight scratch attached), they are then never written in fp32 at all: the head's only use of them is a bf16 (round-to-nearest-even) copy, and
+ * conv_heatmap's epilogue writes that copy itself -- the same rounding of the same sums, so the pose has the bits of the call with heatmaps given.
+ * Unlike the older entries this one reports EVERY refusal as EGOTAP_ERR_INVALID, by name and before any launch: a NULL handle / left / right /
+ * pose / ws, B <= 0, chunk < 0, a misaligned pointer (16 bytes; ws 256), a workspace that is too small, a network with unbound parameters. */
+int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes);
+int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                            size_t ws_bytes, void* stream);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

@@ -32,6 +32,16 @@ int egotap_debug_gemm_bk(int bk);
  * bytes are fetched either way: bit-identical results. */
 int egotap_debug_conv_addressing(int mode);
 
+/* ---- egotap_predict_pose_rgb: which form the last call on the handle took, and where its heatmaps live inside ws ---- */
+/* *form: NONE before the first successful call; HEATMAPS = fp32 heatmaps written to the caller's tensor; SCRATCH = heatmaps == NULL, fp32 heatmaps in
+ * ws; HANDOFF = heatmaps == NULL and conv_heatmap wrote the head's bf16 operand directly (no fp32 heatmaps anywhere) */
+enum { EGOTAP_RGB_FORM_NONE = 0, EGOTAP_RGB_FORM_HEATMAPS = 1, EGOTAP_RGB_FORM_SCRATCH = 2, EGOTAP_RGB_FORM_HANDOFF = 3 };
+int egotap_debug_predict_pose_rgb_form(egotap_handle h, int* form);
+/* name "heatmaps" (after a SCRATCH call: f32 [B, 6J, S, S]) or "handoff" (after a HANDOFF call: bf16 [B, 6J, S, S], element (b, c, y, x) =
+ * bf16(heatmaps[b, c, y, x]) -- the layout the head's patch-embedding and rotation-fc1 loaders gather from); the same slot of ws either way.
+ * offset in bytes, numel in elements */
+int egotap_debug_predict_pose_rgb_intermediate(egotap_handle h, int B, int chunk, const char* name, size_t* offset, int64_t* numel);
+
 /* ---- host-side planning, exposed for unit tests ---- */
 /* (test aid, host only: no device call) the number of partial slabs a weight-gradient launch splits its contraction into, and the slabs per split:
  * workgroups in a row on the busiest CU x slabs each + a fixed part per workgroup + the traffic of the slab reduction, within slab_bytes of

@@ -1,0 +1,139 @@
+"""Times stereo RGB -> pose serving: the parent's route against egotap_predict_pose_rgb, device events after warm-up, all arms in
+ONE process and interleaved:
+
+    python tools/time_predict_rgb.py [--batches 1,8,64,256] [--settings bf16_frozen,f32] [--json OUT]
+    python tools/time_predict_rgb.py --only handoff --batches 64       # one arm, a few calls: the run to put under a kernel trace
+
+Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
+  parent      chunked forward_into x 2 + net_AutoEncoder.predict_pose: three module calls per batch, the only serving route before this entry
+  heatmaps    predict_pose_from_rgb(return_heatmaps=True): one library call, fp32 heatmaps written for the caller
+  no_heatmaps predict_pose_from_rgb(): in bf16 the hand-off (conv_heatmap writes the head's bf16 operand), in fp32 the heatmaps stay in the workspace
+  graphed     predict_pose_from_rgb(graphed=True): the same pipeline replayed from a captured graph (includes the copy into its static inputs)
+Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
+per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from egotap_amd import models, spec  # noqa: E402
+from egotap_amd.options import preset_defaults  # noqa: E402
+from egotap_amd.synthetic import synth_hm_state_dict, synth_input, synth_state_dict  # noqa: E402
+
+REPS = {1: 60, 8: 40, 64: 12, 256: 6}       # calls per arm and round
+
+
+def build_model():
+    opt = preset_defaults("UnrealEgo", 64)
+    opt.model, opt.isTrain, opt.use_amp, opt.gpu_ids, opt.use_gt_heatmap, opt.hm_chunk = "egotap_autoencoder", False, False, [0], False, 256
+    m = models.create_model(opt)
+    p = spec.lift_preset("UnrealEgo", 64)
+    m.net_AutoEncoder.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(spec.lift_state_spec(p)).items()})
+    m.net_HeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(15, "hm_pos.").items()})
+    m.net_RotHeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(30, "hm_rot.").items()})
+    m.eval()
+    return m, p
+
+
+def frames(B):
+    out = []
+    for eye in "lr":
+        x = torch.from_numpy(synth_input(f"rgb_{eye}_time", (min(B, 4), 3, 256, 256), -2.0, 2.0)).cuda()
+        out.append(x[torch.arange(B, device="cuda") % x.shape[0]].contiguous())
+    return out
+
+
+def arms_for(m, p, left, right):
+    B = left.shape[0]
+    chunk = min(B, int(m.opt.hm_chunk))
+    cat = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), device="cuda")
+
+    def parent():
+        for net, c0 in ((m.net_HeatMap, 0), (m.net_RotHeatMap, 2 * p.n_joints_hm)):
+            ws = m.net_HeatMap._workspace(chunk, left.device)
+            for lo in range(0, B, chunk):
+                net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
+        return m.net_AutoEncoder.predict_pose(cat)
+
+    return {"parent": parent,
+            "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
+            "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
+            "graphed": lambda: m.predict_pose_from_rgb(left, right, graphed=True)}
+
+
+def measure(arms, per, warmup=10, rounds=3):
+    """interleaved rounds; {arm: (median ms over all calls, lowest round median, highest round median)}"""
+    for fn in arms.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    rmed = {k: [] for k in arms}
+    every = {k: [] for k in arms}
+    for _ in range(rounds):
+        for name, fn in arms.items():
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per)]
+            for a, b in ev:
+                a.record()
+                fn()
+                b.record()
+            torch.cuda.synchronize()
+            t = sorted(a.elapsed_time(b) for a, b in ev)
+            rmed[name].append(t[len(t) // 2])
+            every[name] += t
+    return {k: (sorted(v)[len(v) // 2], min(rmed[k]), max(rmed[k])) for k, v in every.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,8,64,256")
+    ap.add_argument("--settings", default="bf16_frozen,f32")
+    ap.add_argument("--only", default=None, help="run this arm alone, --calls times, untimed (for a kernel trace)")
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    m, p = build_model()
+    res = {"device": torch.cuda.get_device_name(0), "rows": []}
+    for setting in a.settings.split(","):
+        for B in (int(b) for b in a.batches.split(",")):
+            m.unfreeze_weights()
+            m.set_precision("bf16" if setting == "bf16_frozen" else "f32")
+            if setting == "bf16_frozen":
+                skipped = m.freeze_weights(batch=min(B, int(m.opt.hm_chunk)))
+                assert skipped == {}, skipped
+            left, right = frames(B)
+            arms = arms_for(m, p, left, right)
+            ref = arms["parent"]().clone()
+            for k, fn in arms.items():                       # every arm computes the parent's pose, bit for bit
+                got = fn()
+                torch.cuda.synchronize()
+                assert torch.equal(got, ref), (setting, B, k)
+            m.predict_pose_from_rgb(left, right)
+            form = m.rgb_form()
+            if a.only:
+                for _ in range(a.calls):
+                    arms[a.only]()
+                torch.cuda.synchronize()
+                print(f"{setting} B={B} arm {a.only}: {a.calls} calls done (no_heatmaps form: {form})", flush=True)
+                continue
+            r = measure(arms, REPS.get(B, 6))
+            for k, (med, lo, hi) in r.items():
+                note = f"({form})" if k in ("no_heatmaps", "graphed") else ""
+                print(f"{setting:12s} B={B:<4d} {k:12s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
+                res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
+            m._rgb["graphs"].clear()
+            del arms, left, right
+            torch.cuda.empty_cache()
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
