@@ -3,21 +3,12 @@ with torch (plumbing), the arithmetic is in libegotap_hip.so.  Used by the bf16 
 operator tests."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import lib as _lib
+from .session import ptr as _p, stream as _s
 
 EPI = {"bf16": 0, "residual": 1, "gelu_save": 2, "gelu_grad": 3, "f32": 4}
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _bf(t, what):

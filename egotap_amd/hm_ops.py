@@ -3,8 +3,6 @@ fp32 on the GPU; ``view`` arguments are (tensor, channel_offset, channels): a ch
 buffer addressed in place through its image stride.  No PyTorch compute: everything lands in libegotap_hip.so."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import lib as _lib
@@ -15,7 +13,7 @@ _scratch = Scratch()
 
 def _ws(dev, nbytes=256 << 20):
     t = _scratch.get(nbytes, dev)
-    return C.c_void_p(t.data_ptr()), t.numel()
+    return _p(t), t.numel()
 
 
 class View:
@@ -30,7 +28,7 @@ class View:
 
     @property
     def ptr(self):
-        return C.c_void_p(self.t.data_ptr() + 4 * self.c0 * self.H * self.W)
+        return _p(self.t, 4 * self.c0 * self.H * self.W)
 
     def tensor(self):
         return self.t[:, self.c0:self.c0 + self.C]

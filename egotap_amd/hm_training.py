@@ -7,6 +7,7 @@ import torch
 
 from . import hm_ops as H
 from . import train_ops as T
+from .session import grown
 
 STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))
 BB = "backbone.backbone.backbone."
@@ -169,7 +170,7 @@ class HmTrainFn(torch.autograd.Function):
     def backward(ctx, dout):
         sv, net, keys, P = ctx.sv, ctx.net, ctx.keys, ctx.P
         h = net._ensure_handle()
-        prec = getattr(net, "precision", "f32")
+        prec = net.precision
         B = sv["B"]
         N2 = 2 * B
         dev = dout.device
@@ -297,12 +298,10 @@ def hm_train_forward(net, left, right):
     _spec.hm_check_batch_stats_side(net.hm_size, "the train-mode estimator forward (batch-statistics BatchNorm, stage-1 training)")
     params = [p for _, p in _param_items(net)]
     net._bind(left.device)
-    if getattr(net, "precision", "f32") != "f32":          # bf16 modes: scratch for the repacked conv weights (kept on the module)
+    if net.precision != "f32":          # bf16 modes: scratch for the repacked conv weights (kept on the module)
         from . import lib as _lib
-        import ctypes as C
-        if getattr(net, "_pack", None) is None or net._pack.device != left.device:
-            net._pack = torch.empty(_lib.load().egotap_hmtrain_pack_bytes(), dtype=torch.uint8, device=left.device)
-        _lib.check(_lib.load().egotap_hmtrain_set_pack_buffer(net._ensure_handle(), C.c_void_p(net._pack.data_ptr()), net._pack.numel()))
+        pack = grown(net, "_pack", _lib.load().egotap_hmtrain_pack_bytes(), left.device)
+        _lib.check(_lib.load().egotap_hmtrain_set_pack_buffer(net._ensure_handle(), T._p(pack), pack.numel()))
     return HmTrainFn.apply(net, left, right, *params)
 
 

@@ -11,6 +11,7 @@ ERR_NAMES = {1: "EGOTAP_ERR_INVALID", 2: "EGOTAP_ERR_HIP", 3: "EGOTAP_ERR_UNBOUN
 NET_LIFT, NET_HM_POS, NET_HM_ROT = 0, 1, 2
 F32, I64 = 0, 1
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}      # egotap.h EGOTAP_PREC_*
+ABI_VERSION = 2                                       # egotap.h EGOTAP_ABI_VERSION: what egotap_abi_version() of a matching library returns
 RGB_FORMS = {0: "none", 1: "heatmaps", 2: "scratch", 3: "handoff"}      # egotap_debug.h EGOTAP_RGB_FORM_*
 
 
@@ -187,7 +188,7 @@ def load(build_if_missing: bool = True):
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.egotap_abi_version() != 2:
+    if lib.egotap_abi_version() != ABI_VERSION:
         raise EgotapError("libegotap_hip.so ABI version mismatch")
     _lib = lib
     return lib
@@ -199,13 +200,18 @@ def check(rc: int):
         raise EgotapError(f"{ERR_NAMES.get(rc, rc)}: {msg}")
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+def ptr(t, byte_offset: int = 0):
+    """a tensor's device address (plus `byte_offset`) as the ABI takes it; None -> null pointer"""
+    return C.c_void_p(t.data_ptr() + byte_offset) if t is not None else C.c_void_p(0)
 
 
-def _stream():
+def stream(dev=None):
+    """the current HIP stream of `dev` (None: of the current device) as the ABI takes it"""
     import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+_ptr, _stream = ptr, stream
 
 
 # ----------------------------------------------------------------------------------------- single operators

@@ -10,14 +10,18 @@ is plumbing only.
 from __future__ import annotations
 
 import copy
+import ctypes as C
 import os
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
+from . import lib as _lib
 from . import networks
+from . import session as _session
 from . import spec as _spec
+from .session import ptr, stream
 
 
 def create_model(opt):
@@ -106,7 +110,6 @@ class EgoTAPAutoEncoderModel(nn.Module):
         if self.gt_heatmap_left is None and "gt_camera_2d_left" in data and getattr(self.opt, "use_gt_heatmap", False):
             # joints instead of rendered heatmaps: synthesise them on the device (the data loader's per-frame CPU work,
             # dataloader/data_loader.py:76-215); gt_local_pose_full = all J+1 joints incl. the root, for the limb directions
-            from . import lib as _lib
             full = data.get("gt_local_pose_full", data["gt_local_pose"]).to(dev)
             syn = _lib.synth_heatmaps(data["gt_camera_2d_left"].to(dev), data["gt_camera_2d_right"].to(dev), full,
                                       self.opt.joint_preset, self.net_AutoEncoder.preset.hm_size)
@@ -184,7 +187,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
                                       "--frozen_heatmap_bn_eval; running statistics are not updated", RuntimeWarning, stacklevel=3)
                         self._warned_bottleneck_bn = True
                     batch_stats = False
-                if batch_stats and getattr(net, "precision", "f32") == "bf16" and B >= 2:
+                if batch_stats and net.precision == "bf16" and B >= 2:
                     # [r5] --use_amp: batch-statistics BatchNorm on the bf16 channels-last kernels (egotap_hm_forward_bnbatch) -- the backbone over
                     # the whole batch (the statistics couple its frames), the BatchNorm-free decoder in hm_chunk pieces, straight into the
                     # head's input slice; one scratch shared by both estimators
@@ -249,7 +252,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
             for n in (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap):
                 if getattr(n, "bottleneck", False):
                     continue                                     # resnet50 / resnet101 estimators run in fp32 only (frozen here anyway)
-                if getattr(n, "precision", "f32") != want:
+                if n.precision != want:
                     n.set_precision(want)
         for o in self.optimizers:
             o.zero_grad()
@@ -278,7 +281,6 @@ class EgoTAPAutoEncoderModel(nn.Module):
         the estimators' packed layout is built for (the chunk forward_heatmap() walks: min(batch size, opt.hm_chunk)).  A training step
         afterwards works unchanged: optimize_parameters() puts the head in train mode, which unfreezes it.  Note that evaluate() under
         --use_amp switches the networks to fp32 and back, which unfreezes them as every set_precision does."""
-        from . import lib as _lib
         skipped = OrderedDict()
         for name in self.model_names:
             net = getattr(self, "net_" + name)
@@ -307,7 +309,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
         self.set_eval_mode()
         with torch.no_grad():
             nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
-            prec = [getattr(n, "precision", "f32") for n in nets]
+            prec = [n.precision for n in nets]
             try:
                 if self.use_amp:
                     for n, q in zip(nets, prec):
@@ -317,9 +319,9 @@ class EgoTAPAutoEncoderModel(nn.Module):
             finally:                                             # an exception in the forward must not leave training in fp32
                 if self.use_amp:
                     for n, q in zip(nets, prec):
-                        if getattr(n, "precision", "f32") != q:
+                        if n.precision != q:
                             n.set_precision(q)
-            from . import lib as _lib                     # one fused launch: per-sample MPJPE + Procrustes-aligned MPJPE
+            # one fused launch: per-sample MPJPE + Procrustes-aligned MPJPE.
             # batches of 2 or 3 frames: the reference's batch_compute_similarity_transform_torch aligns the wrong axes there
             # (utils/util.py:337) and test.py prints that number; reproduced by default, opt.pa_mpjpe_reference_batch_axes = False
             # gives every frame the PA-MPJPE it has in any other batch
@@ -339,7 +341,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 return f"{n.model_name} estimators have no one-call forward (Bottleneck blocks are composed on the host)"
         if nets[0].blocks != nets[1].blocks:
             return "the two estimators have different backbones"
-        prec = {getattr(n, "precision", "f32") for n in nets}
+        prec = {n.precision for n in nets}
         if len(prec) != 1:
             return f"the three networks run in different precisions {sorted(prec)} (a handle has one)"
         return None
@@ -348,85 +350,59 @@ class EgoTAPAutoEncoderModel(nn.Module):
         """The serving handle: all three networks' tensors bound to ONE egotap handle, in the networks' precision, with the head's bf16 scratch
         buffers attached and -- for every network that is frozen -- that network's own arena (prepared once more through this handle: the same
         kernel writes the same bytes).  Nothing here changes a network: flags, precision and frozen state are read, never set."""
-        from . import lib as _lib
-        import ctypes as C
         lib = _lib.load()
-        st = self.__dict__.setdefault("_rgb", {"handle": None, "sig": None, "precision": None, "wscratch": None, "ascratch": None,
-                                               "frozen": [None, None, None], "ws": None, "chunk": None, "graphs": {}})
         lift, pos, rot = self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap
         nets = ((_lib.NET_LIFT, lift), (_lib.NET_HM_POS, pos), (_lib.NET_HM_ROT, rot))
-        if st["handle"] is None:
-            p = lift.preset
-            cfg = _lib.EgotapConfig(C.sizeof(_lib.EgotapConfig), p.n_joints_hm, int(p.estimate_head), p.hm_size, p.hidden, p.vit_dim, p.vit_heads,
-                                    p.vit_layers, p.patch, p.pu_hidden, (C.c_int32 * 4)(*pos.blocks))
-            h = C.c_void_p()
-            _lib.check(lib.egotap_create(C.byref(cfg), C.byref(h)))
-            st["handle"] = h
-            if lift._shared_device or os.environ.get("EGOTAP_SHARED_DEVICE", "0") == "1":
-                _lib.check(lib.egotap_set_pu_chain(h, 0))
-        h = st["handle"]
-        tensors = []
-        for net_id, n in nets:
-            sd = dict(n.named_parameters()) if n is lift else n.state_dict(keep_vars=True)
-            if n is lift:
-                sd.update(dict(n.named_buffers()))
-            tensors += [(net_id, k, t) for k, t in sd.items()]
-        sig = tuple((net_id, k, t.data_ptr()) for net_id, k, t in tensors)
-        if sig != st["sig"]:
-            for net_id, k, t in tensors:
-                dt = _lib.F32 if t.dtype == torch.float32 else (_lib.I64 if t.dtype == torch.long else None)
-                if t.device != dev or dt is None or not t.is_contiguous():
-                    raise _lib.EgotapError(f"parameter {k}: need a contiguous fp32 tensor (or int64 counter) on {dev}")
-                _lib.check(lib.egotap_bind_param(h, net_id, k.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt))
-            st["sig"], st["frozen"] = sig, [None, None, None]        # (a moved tensor unfreezes its network inside the library)
-        prec = getattr(lift, "precision", "f32")
-        if prec != st["precision"]:
+        st = self.__dict__.get("_rgb")
+        if st is None:
+            st = self._rgb = _session.Serving(_session.Handle(lift.preset, hm_blocks=pos.blocks, shared_device=lift._shared_device))
+        h = st.handle.h
+        if any([st.handle.bind(net_id, n._bound_tensors(), dev) for net_id, n in nets]):      # (a list: all three, whichever moved)
+            st.frozen = [None, None, None]                 # a moved tensor unfreezes its network inside the library
+        prec = lift.precision
+        if prec != st.precision:
             _lib.check(lib.egotap_set_precision(h, _lib.PRECISIONS[prec]))
-            st["precision"], st["frozen"], st["wscratch"], st["ascratch"] = prec, [None, None, None], None, None
+            st.precision, st.frozen, st.wscratch, st.ascratch = prec, [None, None, None], None, None
             _lib.check(lib.egotap_set_weight_scratch(h, None, 0))
             _lib.check(lib.egotap_set_act_scratch(h, None, 0))
         if prec == "bf16":
             wsc = getattr(lift, "_wscratch", None)
-            if wsc is not None and wsc.device == dev and st["wscratch"] is not wsc:
-                _lib.check(lib.egotap_set_weight_scratch(h, C.c_void_p(wsc.data_ptr()), wsc.numel()))
-                st["wscratch"] = wsc
+            if wsc is not None and wsc.device == dev and st.wscratch is not wsc:
+                _lib.check(lib.egotap_set_weight_scratch(h, ptr(wsc), wsc.numel()))
+                st.wscratch = wsc
         for i, (net_id, n) in enumerate(nets):
             if n.weights_frozen:
                 n._bind(dev)
                 n._frozen_check(dev)           # stale prepared weights are redone by their owner, into the arena this handle reads too
                 key = (n._frozen_arena.data_ptr(), getattr(n, "_frozen_batch", 0))
-                if st["frozen"][i] != key:
-                    arena, stream = C.c_void_p(n._frozen_arena.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                if st.frozen[i] != key:
+                    arena = n._frozen_arena
                     if n is lift:
-                        _lib.check(lib.egotap_lift_freeze(h, arena, n._frozen_arena.numel(), stream))
+                        _lib.check(lib.egotap_lift_freeze(h, ptr(arena), arena.numel(), stream(dev)))
                     else:
-                        _lib.check(lib.egotap_hm_freeze(h, net_id, n._frozen_batch, arena, n._frozen_arena.numel(), stream))
-                    st["frozen"][i] = key
-            elif st["frozen"][i] is not None:
+                        _lib.check(lib.egotap_hm_freeze(h, net_id, n._frozen_batch, ptr(arena), arena.numel(), stream(dev)))
+                    st.frozen[i] = key
+            elif st.frozen[i] is not None:
                 _lib.check(lib.egotap_lift_unfreeze(h) if n is lift else lib.egotap_hm_unfreeze(h, net_id))
-                st["frozen"][i] = None
+                st.frozen[i] = None
         return st
 
     def _rgb_attach_act_scratch(self, st, B, dev):
-        from . import lib as _lib
-        import ctypes as C
         lift = self.net_AutoEncoder
         lift._act_scratch(B, dev)              # (bf16 below the bf16-storage route's batch only; grown with the batch)
         asc = getattr(lift, "_ascratch", None)
-        if st["precision"] == "bf16" and asc is not None and st["ascratch"] is not asc:
-            _lib.check(_lib.load().egotap_set_act_scratch(st["handle"], C.c_void_p(asc.data_ptr()), asc.numel()))
-            st["ascratch"] = asc
+        if st.precision == "bf16" and asc is not None and st.ascratch is not asc:
+            _lib.check(_lib.load().egotap_set_act_scratch(st.handle.h, ptr(asc), asc.numel()))
+            st.ascratch = asc
 
     def rgb_form(self):
         """how the last predict_pose_from_rgb call handed the heatmaps to the head (egotap_debug.h): "heatmaps" (fp32, returned), "scratch"
         (fp32, inside the workspace), "handoff" (conv_heatmap wrote the head's bf16 operand; no fp32 heatmaps), or "none" """
-        from . import lib as _lib
-        import ctypes as C
         st = self.__dict__.get("_rgb")
-        if st is None or st["handle"] is None:
+        if st is None:
             return "none"
         form = C.c_int()
-        _lib.check(_lib.load().egotap_debug_predict_pose_rgb_form(st["handle"], C.byref(form)))
+        _lib.check(_lib.load().egotap_debug_predict_pose_rgb_form(st.handle.h, C.byref(form)))
         return _lib.RGB_FORMS[form.value]
 
     @torch.no_grad()
@@ -447,8 +423,6 @@ class EgoTAPAutoEncoderModel(nn.Module):
         By name, not through the one call: resnet50 / resnet101 estimators (no one-call forward), estimators with different backbones and
         networks set to different precisions run the existing module forwards (``forward_into`` x 2, chunked) followed by
         ``net_AutoEncoder.predict_pose`` -- ungraphed (``graphed=True`` raises there), and only with eval-mode networks."""
-        from . import lib as _lib
-        import ctypes as C
         p = self.net_AutoEncoder.preset
         S0 = 4 * p.hm_size
         for t in (left, right):
@@ -486,42 +460,28 @@ class EgoTAPAutoEncoderModel(nn.Module):
         with torch.cuda.device(dev):
             st = self._rgb_state(dev)
             self._rgb_attach_act_scratch(st, B, dev)
-            h = st["handle"]
-            need = C.c_size_t()
-            _lib.check(lib.egotap_predict_pose_rgb_workspace_bytes(h, B, chunk, C.byref(need)))
+            h = st.handle.h
+            need = _session.nbytes(lib.egotap_predict_pose_rgb_workspace_bytes, h, B, chunk)
 
             def call(l, r, po, hmo, ws):
-                _lib.check(lib.egotap_predict_pose_rgb(h, C.c_void_p(l.data_ptr()), C.c_void_p(r.data_ptr()), B, C.c_void_p(po.data_ptr()),
-                                                       C.c_void_p(hmo.data_ptr()) if hmo is not None else None, chunk, C.c_void_p(ws.data_ptr()),
-                                                       ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                _lib.check(lib.egotap_predict_pose_rgb(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
             if not graphed:
-                if st["ws"] is None or st["ws"].numel() < need.value or st["ws"].device != dev:
-                    st["ws"] = None
-                    st["ws"] = torch.empty(need.value, dtype=torch.uint8, device=dev)
-                st["chunk"] = chunk
-                call(left, right, pose, hm, st["ws"])
+                _session.grown(st, "ws", need, dev, drop_first=True)
+                st.chunk = chunk
+                call(left, right, pose, hm, st.ws)
                 return (pose, hm) if return_heatmaps else pose
             # one graph per (batch, heatmaps wanted, precision, frozen arenas, bound tensors, chunk): every pointer a captured launch takes is baked
             # in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch buffers and arenas alive
-            key = (B, bool(return_heatmaps), st["precision"], tuple(st["frozen"]), st["sig"], chunk, str(dev))
-            g = st["graphs"].get(key)
-            if g is None:
+            nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
+            key = (B, bool(return_heatmaps), st.precision, tuple(st.frozen), tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)),
+                   chunk, str(dev))
+
+            def build():
                 s_l, s_r = left.clone(), right.clone()
-                ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-                keep = (ws, st["wscratch"], st["ascratch"]) + tuple(n._frozen_arena for n in (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
-                                                                    if n.weights_frozen)
-                side = torch.cuda.Stream(dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    call(s_l, s_r, pose, hm, ws)               # eager once: occupancy queries and kernel attributes are settled here
-                torch.cuda.current_stream(dev).wait_stream(side)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=side):
-                    call(s_l, s_r, pose, hm, ws)
-                if len(st["graphs"]) >= 8:                     # a handful of serving batch sizes; drop the oldest beyond that
-                    st["graphs"].pop(next(iter(st["graphs"])))
-                g = st["graphs"][key] = (graph, s_l, s_r, pose, hm, keep)
-            graph, s_l, s_r, pose, hm, _ = g
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                keep = (ws, st.wscratch, st.ascratch) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
+                return (lambda: call(s_l, s_r, pose, hm, ws)), (s_l, s_r, pose, hm), keep
+            graph, (s_l, s_r, pose, hm), _ = _session.captured(st.graphs, key, build)
             s_l.copy_(left)
             s_r.copy_(right)
             graph.replay()
@@ -530,24 +490,12 @@ class EgoTAPAutoEncoderModel(nn.Module):
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity
         tests; egotap_debug.h): "heatmaps" -> fp32 [B, 6J, S, S] after a "scratch" call, "handoff" -> bfloat16 [B, 6J, S, S] after a "handoff" call"""
-        from . import lib as _lib
-        import ctypes as C
         st, p = self.__dict__.get("_rgb"), self.net_AutoEncoder.preset
-        if st is None or st["ws"] is None or st["chunk"] is None:
+        if st is None or st.ws is None or st.chunk is None:
             raise _lib.EgotapError("rgb_intermediate: no ungraphed one-call predict_pose_from_rgb has run on this model yet (a graph keeps its own workspace)")
-        off, n = C.c_size_t(), C.c_int64()
-        _lib.check(_lib.load().egotap_debug_predict_pose_rgb_intermediate(st["handle"], B, st["chunk"], name.encode(), C.byref(off), C.byref(n)))
-        dt, sz = (torch.bfloat16, 2) if name == "handoff" else (torch.float32, 4)
-        return st["ws"][off.value: off.value + sz * n.value].view(dt).view(B, p.in_channels, p.hm_size, p.hm_size)
-
-    def __del__(self):
-        try:
-            st = self.__dict__.get("_rgb")
-            if st is not None and st["handle"] is not None:
-                from . import lib as _lib
-                _lib.load().egotap_destroy(st["handle"])
-        except Exception:
-            pass
+        view = st.handle.intermediate(_lib.load().egotap_debug_predict_pose_rgb_intermediate, st.ws, B, st.chunk, name=name,
+                                      dtype=torch.bfloat16 if name == "handoff" else torch.float32)
+        return view.view(B, p.in_channels, p.hm_size, p.hm_size)
 
     # ---- checkpoints (base_model.py:64-148 file naming) --------------------------------------------------------
     def save_networks(self, which_epoch=None, checkpoint_path=None):

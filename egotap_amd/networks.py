@@ -9,13 +9,14 @@ the HIP library or off the GPU these modules raise.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 import torch.nn as nn
 
 from . import lib as _lib
+from . import session as _session
 from . import spec as _spec
+from .session import ptr, stream
 
 
 class _Node(nn.Module):
@@ -88,8 +89,8 @@ class _FrozenWeights:
         dev = self._frozen_device()
         if self.training:
             raise _lib.EgotapError("freeze_weights: the module is in train mode (training never reads the prepared weights): call .eval() first")
-        if getattr(self, "precision", "f32") != "bf16":
-            raise _lib.EgotapError(f"freeze_weights: nothing to freeze in precision {getattr(self, 'precision', 'f32')!r}: only 'bf16' prepares "
+        if self.precision != "bf16":
+            raise _lib.EgotapError(f"freeze_weights: nothing to freeze in precision {self.precision!r}: only 'bf16' prepares "
                                    "weights per forward (f32 / bf16x3 read the live parameters)")
         with torch.cuda.device(dev):
             self._frozen_prepare(*args, **kwargs)
@@ -122,7 +123,7 @@ class _FrozenWeights:
 
     def unfreeze_weights(self):
         if self._frozen_sig is not None:
-            if self._handle is not None:
+            if self._abi is not None:
                 self._frozen_release()
             self._frozen_sig = self._frozen_arena = self._frozen_list = None
         return self
@@ -138,13 +139,49 @@ class _FrozenWeights:
         return super().train(mode)
 
 
-class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
+class _AbiModule(_FrozenWeights):
+    """What both network modules do with the C ABI, on one session.Handle of their own (created at the first use): binding, the grow-only
+    workspace ``_ws``, the precision mode and views of the last forward's intermediates.  Subclasses give ``_net`` (the net id their
+    tensors are bound under), ``_intermediate_query`` (the ABI's query by name), _new_handle() and _bound_tensors()."""
+
+    def __init__(self):
+        super().__init__()
+        self._abi = None
+        self._ws = None
+        self.precision = "f32"
+
+    def _ensure_handle(self):
+        if self._abi is None:
+            self._abi = self._new_handle()
+        return self._abi.h
+
+    def _bind(self, device):
+        self._ensure_handle()
+        return self._abi.bind(self._net, self._bound_tensors(), device)
+
+    def set_precision(self, mode: str = "f32"):
+        if mode not in _lib.PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
+        self.unfreeze_weights()        # prepared weights belong to a mode (the library unfreezes the handle too)
+        _lib.check(_lib.load().egotap_set_precision(self._ensure_handle(), _lib.PRECISIONS[mode]))
+        self.precision = mode
+        return self
+
+    def intermediate(self, name: str, B: int):
+        """View of an intermediate of the LAST forward inside the workspace (parity tests)."""
+        self._ensure_handle()
+        return self._abi.intermediate(getattr(_lib.load(), self._intermediate_query), self._ws, B, name=name)
+
+
+class EgoTAPAutoEncoder(_AbiModule, nn.Module):
     """Heatmaps -> 3D pose lifting head (reference: model/net_architecture.py:579-758).
 
     forward(input[B, 6J, S, S]) -> (pose[B, J(+1), 3], rot zeros[B, 3J], indep_pos zeros[B, 6J],
     reconstructed-heatmap zeros[B, 6J, S, S]) -- the last three are all-zero in the reference too
     (net_architecture.py:718-719, 756); they are returned as cached / broadcast zeros, not re-allocated.
     """
+    _net = _lib.NET_LIFT
+    _intermediate_query = "egotap_lift_intermediate"
 
     def __init__(self, opt, input_channel_scale: int = 2, fc_dim: int = 16384):
         super().__init__()
@@ -170,26 +207,19 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
         self.rot_dim = 3 * p.n_joints_hm
         _build_tree(self, _spec.lift_state_spec(p))
         _kaiming_init_(self)
-        self._handle = None
-        self._bound_sig = None
-        self._ws = None
         self._zeros = {}
         # several processes on one GPU (rehearsals, tests): per-step propagation-unit kernels instead of the one-launch recurrence.  An OPTION of the
         # model (opt.shared_device); the EGOTAP_SHARED_DEVICE=1 environment switch remains for launchers that cannot reach opt
         self._shared_device = bool(getattr(opt, "shared_device", False))
 
     # -- C-ABI plumbing ---------------------------------------------------------------------------
-    def _ensure_handle(self):
-        if self._handle is None:
-            p = self.preset
-            cfg = _lib.EgotapConfig(C.sizeof(_lib.EgotapConfig), p.n_joints_hm, int(p.estimate_head), p.hm_size, p.hidden,
-                                    p.vit_dim, p.vit_heads, p.vit_layers, p.patch, p.pu_hidden)
-            h = C.c_void_p()
-            _lib.check(_lib.load().egotap_create(C.byref(cfg), C.byref(h)))
-            self._handle = h
-            if self._shared_device or os.environ.get("EGOTAP_SHARED_DEVICE", "0") == "1":      # several processes on one GPU: see set_pu_chain
-                _lib.check(_lib.load().egotap_set_pu_chain(h, 0))
-        return self._handle
+    def _new_handle(self):
+        return _session.Handle(self.preset, shared_device=self._shared_device)      # several processes on one GPU: see set_pu_chain
+
+    def _bound_tensors(self):
+        sd = dict(self.named_parameters())
+        sd.update(self.named_buffers())
+        return sd
 
     def set_pu_chain(self, enable: bool = True):
         """The propagation units' recurrence as one launch per layer (default; its workgroups wait for each other, so the process must
@@ -215,65 +245,37 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
                 or k.endswith("patch_embeddings.projection.weight") or k.endswith("_heatmap_encoder.fc1.fc.weight")]
 
     def _frozen_bytes(self):
-        need = C.c_size_t()
-        _lib.check(_lib.load().egotap_lift_frozen_bytes(self._ensure_handle(), C.byref(need)))
-        if need.value == 0:
+        need = _session.nbytes(_lib.load().egotap_lift_frozen_bytes, self._ensure_handle())
+        if need == 0:
             raise _lib.EgotapError(f"freeze_weights: nothing to freeze: the bf16-storage forward needs a sequence that is a multiple of 32 tokens "
                                    f"(heatmap side {self.preset.hm_size}: {self.preset.seq} tokens run on fp32 tensors, which read the live parameters)")
-        return need.value
+        return need
 
     def _frozen_launch(self, arena, dev):
-        _lib.check(_lib.load().egotap_lift_freeze(self._ensure_handle(), C.c_void_p(arena.data_ptr()), arena.numel(),
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(_lib.load().egotap_lift_freeze(self._ensure_handle(), ptr(arena), arena.numel(), stream(dev)))
 
     def _frozen_release(self):
-        _lib.check(_lib.load().egotap_lift_unfreeze(self._handle))
+        _lib.check(_lib.load().egotap_lift_unfreeze(self._abi.h))
 
-    def _bind(self, device):
-        sd = dict(self.named_parameters())
-        sd.update(dict(self.named_buffers()))
-        sig = tuple((k, t.data_ptr()) for k, t in sd.items())
-        if sig == self._bound_sig:
-            return
-        lib, h = _lib.load(), self._ensure_handle()
-        for k, t in sd.items():
-            if t.device != device:
-                raise _lib.EgotapError(f"parameter {k} is on {t.device}, input on {device}")
-            if t.dtype == torch.float32:
-                if not t.is_contiguous():
-                    raise _lib.EgotapError(f"parameter {k} must be contiguous")
-                _lib.check(lib.egotap_bind_param(h, _lib.NET_LIFT, k.encode(), C.c_void_p(t.data_ptr()), t.numel(), _lib.F32))
-            elif t.dtype == torch.long:
-                _lib.check(lib.egotap_bind_param(h, _lib.NET_LIFT, k.encode(), C.c_void_p(t.data_ptr()), t.numel(), _lib.I64))
-            else:
-                raise _lib.EgotapError(f"parameter {k}: dtype {t.dtype} not supported (fp32 path)")
-        n = C.c_int()
-        _lib.check(lib.egotap_unbound_count(h, _lib.NET_LIFT, C.byref(n)))
-        if n.value:
-            raise _lib.EgotapError(f"{n.value} parameters the forward needs are not bound")
-        self._bound_sig = sig
+    def _workspace_bytes(self, B):
+        return _session.nbytes(_lib.load().egotap_lift_workspace_bytes, self._ensure_handle(), B)
 
     def _workspace(self, B, device):
-        lib, h = _lib.load(), self._ensure_handle()
-        need = C.c_size_t()
-        _lib.check(lib.egotap_lift_workspace_bytes(h, B, C.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+        _session.grown(self, "_ws", self._workspace_bytes(B), device)      # (the new block while the old one is held: their addresses differ)
         self._act_scratch(B, device)
         return self._ws
 
     def _act_scratch(self, B, device):
         """bf16 mode: scratch for the bf16 copy of a GEMM's activation operand (egotap_set_act_scratch), sized for the ViT MLP's
         hidden activations [B * seq, 4 * D] and grown with the batch"""
-        if getattr(self, "precision", "f32") != "bf16" or device.type != "cuda":
+        if self.precision != "bf16" or device.type != "cuda":
             return
         if B * self.preset.seq >= 4096:      # the bf16-storage forward (egotap_lift_forward at batches that fill the chip) converts nothing
             return
-        need = 2 * B * self.preset.seq * 4 * self.preset.vit_dim
         cur = getattr(self, "_ascratch", None)
-        if cur is None or cur.numel() < need or cur.device != device:
-            self._ascratch = torch.empty(need, dtype=torch.uint8, device=device)
-            _lib.check(_lib.load().egotap_set_act_scratch(self._ensure_handle(), C.c_void_p(self._ascratch.data_ptr()), self._ascratch.numel()))
+        buf = _session.grown(self, "_ascratch", 2 * B * self.preset.seq * 4 * self.preset.vit_dim, device)
+        if buf is not cur:
+            _lib.check(_lib.load().egotap_set_act_scratch(self._ensure_handle(), ptr(buf), buf.numel()))
 
     def _reducer(self):
         """the overlapped gradient reducer of this module's training Function (egotap_amd.parallel.GradReducer; a no-op for one rank)"""
@@ -285,46 +287,33 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
     def set_precision(self, mode: str = "f32"):
         """Arithmetic of the large GEMMs (egotap.h egotap_set_precision): "f32" = exact fp32 MFMA (default),
         "bf16x3" = fp32 operands split into hi + lo bf16, three bf16 MFMAs per product, fp32 accumulate (opt-in fast mode)."""
-        if mode not in _lib.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
-        self.unfreeze_weights()        # prepared weights belong to a mode (the library unfreezes the handle too)
-        _lib.check(_lib.load().egotap_set_precision(self._ensure_handle(), _lib.PRECISIONS[mode]))
-        self.precision = mode
+        super().set_precision(mode)
         if mode == "bf16":             # scratch for the bf16 copy of a GEMM's weights (largest: fc1 of the position encoder)
             dev = next(self.parameters()).device
             if dev.type == "cuda" and (getattr(self, "_wscratch", None) is None or self._wscratch.device != dev):
                 need = 2 * max(p.numel() for p in self.parameters() if p.dim() >= 2)
                 self._wscratch = torch.empty(need, dtype=torch.uint8, device=dev)
             if getattr(self, "_wscratch", None) is not None:
-                _lib.check(_lib.load().egotap_set_weight_scratch(self._ensure_handle(), C.c_void_p(self._wscratch.data_ptr()), self._wscratch.numel()))
+                _lib.check(_lib.load().egotap_set_weight_scratch(self._ensure_handle(), ptr(self._wscratch), self._wscratch.numel()))
         else:                          # the activation scratch is (re)attached by the next forward in bf16 mode (_act_scratch)
             self._ascratch = None
             _lib.check(_lib.load().egotap_set_act_scratch(self._ensure_handle(), None, 0))
         return self
 
-    def intermediate(self, name: str, B: int):
-        """View of an intermediate of the LAST forward inside the workspace (parity tests)."""
-        off, n = C.c_size_t(), C.c_int64()
-        _lib.check(_lib.load().egotap_lift_intermediate(self._ensure_handle(), B, name.encode(), C.byref(off), C.byref(n)))
-        return self._ws[off.value: off.value + 4 * n.value].view(torch.float32)
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.load().egotap_destroy(self._handle)
-        except Exception:
-            pass
-
     # -- reference API ----------------------------------------------------------------------------
     def predict_pose(self, input, input_rgb_left=None, input_rgb_right=None):
         return self.forward(input, input_rgb_left, input_rgb_right, pose_only=True)
 
-    def forward(self, input, input_rgb_left=None, input_rgb_right=None, pose_only=False):
+    def _check_heatmaps(self, input):
         p = self.preset
         if not input.is_cuda:
             raise _lib.EgotapError("EgoTAPAutoEncoder runs on the GPU only (no CPU fallback); move the input to cuda")
-        if input.dim() != 4 or input.shape[1] != p.in_channels or input.shape[2] != p.hm_size or input.shape[3] != p.hm_size:
+        if input.dim() != 4 or tuple(input.shape[1:]) != (p.in_channels, p.hm_size, p.hm_size):
             raise ValueError(f"expected input [B, {p.in_channels}, {p.hm_size}, {p.hm_size}], got {tuple(input.shape)}")
+
+    def forward(self, input, input_rgb_left=None, input_rgb_right=None, pose_only=False):
+        p = self.preset
+        self._check_heatmaps(input)
         if self.training:
             from .training import lift_train_forward          # training mode: batch-statistics BatchNorm, differentiable
             pose = lift_train_forward(self, input)
@@ -344,9 +333,7 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
                 ws = self._workspace(B, dev)
                 # predict_pose: the pose-only entry (same bits; the last ViT layer skips the rows fc1 never reads), forward(): every intermediate
                 entry = _lib.load().egotap_lift_predict_pose if pose_only else _lib.load().egotap_lift_forward
-                _lib.check(entry(
-                    self._ensure_handle(), C.c_void_p(hm.data_ptr()), B, C.c_void_p(pose.data_ptr()),
-                    C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                _lib.check(entry(self._ensure_handle(), ptr(hm), B, ptr(pose), ptr(ws), ws.numel(), stream(dev)))
         if pose_only:
             return pose
         return (pose,) + self._zero_outputs(B, dev)[1:]
@@ -359,11 +346,7 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
         tensor is the graph's static output buffer (valid until the next call with the same batch)."""
         if self.training:
             raise RuntimeError("predict_pose_graphed is an inference path: call .eval() first")
-        p = self.preset
-        if not input.is_cuda:
-            raise _lib.EgotapError("EgoTAPAutoEncoder runs on the GPU only (no CPU fallback); move the input to cuda")
-        if input.dim() != 4 or tuple(input.shape[1:]) != (p.in_channels, p.hm_size, p.hm_size):
-            raise ValueError(f"expected input [B, {p.in_channels}, {p.hm_size}, {p.hm_size}], got {tuple(input.shape)}")
+        self._check_heatmaps(input)
         dev = input.device
         self._bind(dev)
         if self._frozen_sig is not None:               # stale prepared weights are redone here, into the same arena, ahead of the replay
@@ -371,39 +354,24 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
                 self._frozen_check(dev)
         B = input.shape[0]
         # the frozen state (and its arena) is part of the key: a graph captured while frozen holds no preparation kernels and reads that arena
-        key = (B, str(dev), getattr(self, "precision", "f32"), self._bound_sig, self._frozen_arena.data_ptr() if self.weights_frozen else None)
-        graphs = self.__dict__.setdefault("_graphs", {})
-        g = graphs.get(key)
-        if g is None:
+        key = (B, str(dev), self.precision, self._abi.bound[self._net], self._frozen_arena.data_ptr() if self.weights_frozen else None)
+
+        def build():
             # Every pointer a captured launch takes is baked into the graph, so the graph OWNS what it replays into: a workspace of
             # its own (the module's grow-only self._ws is replaced -- and the old one handed back to the allocator -- as soon as a
             # larger batch arrives) and references to the bf16 scratch buffers attached to the handle at capture time (replaced, not
             # resized, when they grow; their contents are transient within one launch, so sharing them between graphs is fine).
             lib, h = _lib.load(), self._ensure_handle()
             static_in = input.detach().float().contiguous().clone()
-            static_out = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
+            static_out = torch.empty((B, self.preset.out_joints, 3), dtype=torch.float32, device=dev)
             self.predict_pose(static_in)                   # eager once: lazy occupancy queries and allocations happen here
-            need = C.c_size_t()
-            _lib.check(lib.egotap_lift_workspace_bytes(h, B, C.byref(need)))
-            ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+            ws = torch.empty(self._workspace_bytes(B), dtype=torch.uint8, device=dev)
             self._act_scratch(B, dev)
             keep = (ws, getattr(self, "_ascratch", None), getattr(self, "_wscratch", None), self._frozen_arena if self.weights_frozen else None)
-
-            def run():
-                _lib.check(lib.egotap_lift_predict_pose(h, C.c_void_p(static_in.data_ptr()), B, C.c_void_p(static_out.data_ptr()),
-                                                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.device(dev), torch.cuda.stream(side):
-                run()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.device(dev), torch.cuda.graph(graph, stream=side):
-                run()
-            if len(graphs) >= 8:                           # a handful of serving batch sizes; drop the oldest beyond that
-                graphs.pop(next(iter(graphs)))
-            g = graphs[key] = (graph, static_in, static_out, keep)
-        graph, static_in, static_out, _ = g
+            return (lambda: _lib.check(lib.egotap_lift_predict_pose(h, ptr(static_in), B, ptr(static_out), ptr(ws), ws.numel(), stream(dev))),
+                    (static_in, static_out), keep)
+        with torch.cuda.device(dev):
+            graph, (static_in, static_out), _ = _session.captured(self.__dict__.setdefault("_graphs", {}), key, build)
         static_in.copy_(input)
         graph.replay()
         return static_out
@@ -420,7 +388,7 @@ class EgoTAPAutoEncoder(_FrozenWeights, nn.Module):
         return None, rot, indep, out_hm
 
 
-class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
+class HeatMap_UnrealEgo_Shared(_AbiModule, nn.Module):
     """Stereo heatmap estimator (reference: model/net_architecture.py:25-173 over torchvision resnet18).
 
     forward(left[B,3,256,256], right[B,3,256,256]) -> [B, 2*n_hm, 64, 64] (left maps then right maps); in eval mode any heatmap side S
@@ -430,6 +398,7 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
     ``forward_into(left, right, out)`` writes the result into a channel slice of a larger tensor instead
     (used by the wrapper to build the lifting head's input without torch.cat).
     """
+    _intermediate_query = "egotap_hm_intermediate"
 
     def __init__(self, opt, model_name: str = "resnet18", input_channel_scale: int = 2):
         super().__init__()
@@ -470,9 +439,6 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
                 mod.register_buffer(parts[-1], src_mod._buffers[src_leaf])
         self._aliases = [(k, a) for k, s, a in entries if a is not None]
         _kaiming_init_(self)
-        self._handle = None
-        self._bound_sig = None
-        self._ws = None
 
     def _apply(self, fn, *args, **kwargs):
         """Module._apply (.to / .cuda / .float ...) replaces every registered BUFFER by fn(buffer) -- once per registration, so the
@@ -486,7 +452,8 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
             mod, leaf = self._locate(k)
             if src_leaf in src_mod._buffers:
                 mod._buffers[leaf] = src_mod._buffers[src_leaf]
-        self._bound_sig = None
+        if self._abi is not None:
+            self._abi.bound.pop(self._net, None)
         if self._frozen_sig is not None:
             self._frozen_sig = ()          # the buffers are new objects: the next frozen forward lists the tensors again and re-freezes
         return self
@@ -494,14 +461,9 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
     def set_precision(self, mode: str = "f32"):
         """Arithmetic of the 3x3 stride-1 convolutions with >= 128 output channels (88 % of the FLOPs): "f32" exact (default),
         "bf16x3" split operands, "bf16" rounded operands; everything else stays fp32 (egotap.h egotap_set_precision)."""
-        if mode not in _lib.PRECISIONS:
-            raise ValueError(f"precision must be one of {sorted(_lib.PRECISIONS)}")
-        if self.bottleneck and mode != "f32":
+        if self.bottleneck and mode in _lib.PRECISIONS and mode != "f32":
             raise NotImplementedError(f"backbone {self.model_name!r} runs in fp32 only (the bf16 modes cover resnet18 / resnet34)")
-        self.unfreeze_weights()        # prepared weights belong to a mode (the library unfreezes the handle too)
-        _lib.check(_lib.load().egotap_set_precision(self._ensure_handle(), _lib.PRECISIONS[mode]))
-        self.precision = mode
-        return self
+        return super().set_precision(mode)
 
     def _locate(self, key):
         parts = key.split(".")
@@ -538,85 +500,52 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
         return out
 
     def _frozen_bytes(self):
-        need = C.c_size_t()
-        _lib.check(_lib.load().egotap_hm_frozen_bytes(self._ensure_handle(), self._net, self._frozen_batch, C.byref(need)))
-        if need.value == 0:
+        need = _session.nbytes(_lib.load().egotap_hm_frozen_bytes, self._ensure_handle(), self._net, self._frozen_batch)
+        if need == 0:
             raise _lib.EgotapError(f"freeze_weights: nothing to freeze at heatmap side {self.hm_size}: the bf16 channels-last path exists at sides "
                                    "64 and 128; every other side runs the exact-fp32 path, which reads the live parameters")
-        return need.value
+        return need
 
     def _frozen_launch(self, arena, dev):
-        _lib.check(_lib.load().egotap_hm_freeze(self._ensure_handle(), self._net, self._frozen_batch, C.c_void_p(arena.data_ptr()), arena.numel(),
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(_lib.load().egotap_hm_freeze(self._ensure_handle(), self._net, self._frozen_batch, ptr(arena), arena.numel(), stream(dev)))
 
     def _frozen_release(self):
-        _lib.check(_lib.load().egotap_hm_unfreeze(self._handle, self._net))
+        _lib.check(_lib.load().egotap_hm_unfreeze(self._abi.h, self._net))
 
-    def _ensure_handle(self):
-        if self._handle is None:
-            p = self.preset
-            # Bottleneck nets never bind to the handle's one-call forward (it only carries the operator calls): default block counts
-            cfg = _lib.EgotapConfig(C.sizeof(_lib.EgotapConfig), p.n_joints_hm, int(p.estimate_head), p.hm_size, p.hidden,
-                                    p.vit_dim, p.vit_heads, p.vit_layers, p.patch, p.pu_hidden,
-                                    (C.c_int32 * 4)(*((2, 2, 2, 2) if self.bottleneck else self.blocks)))
-            h = C.c_void_p()
-            _lib.check(_lib.load().egotap_create(C.byref(cfg), C.byref(h)))
-            self._handle = h
-        return self._handle
+    def _new_handle(self):
+        # Bottleneck nets never bind to the handle's one-call forward (it only carries the operator calls): default block counts
+        return _session.Handle(self.preset, hm_blocks=(2, 2, 2, 2) if self.bottleneck else self.blocks)
 
-    def _bind(self, device):
-        sd = self.state_dict(keep_vars=True)
-        sig = tuple((k, t.data_ptr()) for k, t in sd.items())
-        if sig == self._bound_sig:
-            return
-        lib, h = _lib.load(), self._ensure_handle()
-        for k, t in sd.items():
-            if t.device != device:
-                raise _lib.EgotapError(f"parameter {k} is on {t.device}, input on {device}")
-            dt = _lib.F32 if t.dtype == torch.float32 else (_lib.I64 if t.dtype == torch.long else None)
-            if dt is None or not t.is_contiguous():
-                raise _lib.EgotapError(f"parameter {k}: need contiguous fp32 (or int64 counters)")
-            _lib.check(lib.egotap_bind_param(h, self._net, k.encode(), C.c_void_p(t.data_ptr()), t.numel(), dt))
-        n = C.c_int()
-        _lib.check(lib.egotap_unbound_count(h, self._net, C.byref(n)))
-        if n.value:
-            raise _lib.EgotapError(f"{n.value} parameters the forward needs are not bound")
-        self._bound_sig = sig
+    def _bound_tensors(self):
+        return self.state_dict(keep_vars=True)          # the ``backbone.backbone.layerK.*`` aliases under both names
 
     def _workspace(self, B, device):
-        need = C.c_size_t()
-        _lib.check(_lib.load().egotap_hm_workspace_bytes(self._ensure_handle(), B, C.byref(need)))
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != device:
-            self._ws = None
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=device)
-        return self._ws
+        need = _session.nbytes(_lib.load().egotap_hm_workspace_bytes, self._ensure_handle(), B)
+        return _session.grown(self, "_ws", need, device, drop_first=True)
 
-    def intermediate(self, name: str, B: int):
-        off, n = C.c_size_t(), C.c_int64()
-        _lib.check(_lib.load().egotap_hm_intermediate(self._ensure_handle(), B, name.encode(), C.byref(off), C.byref(n)))
-        return self._ws[off.value: off.value + 4 * n.value].view(torch.float32)
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.load().egotap_destroy(self._handle)
-        except Exception:
-            pass
-
-    def forward_into(self, left, right, out, channel_offset: int = 0, workspace=None):
-        """Write this net's [B, 2*n_hm, S, S] output into out[:, channel_offset : channel_offset + 2*n_hm]."""
-        if self.training:
-            raise NotImplementedError("forward_into writes the eval-mode result (folded BatchNorm) into a caller's slice; in train mode call the module itself (differentiable path) or .eval() first")
+    def _check_stereo_io(self, left, right, out, channel_offset):
+        """left / right [B, 3, 4S, 4S] and an `out` that holds channels [channel_offset, channel_offset + 2 n_hm) of B maps; returns B"""
         for t in (left, right, out):
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                 raise _lib.EgotapError("heatmap estimator needs contiguous float32 CUDA tensors (no CPU fallback)")
         B, S = left.shape[0], 4 * self.hm_size
         if tuple(left.shape) != (B, 3, S, S) or tuple(right.shape) != (B, 3, S, S):
             raise ValueError(f"expected left/right [B, 3, {S}, {S}], got {tuple(left.shape)} / {tuple(right.shape)}")
-        n_out = 2 * self.num_heatmap
         if out.dim() != 4 or out.shape[0] != B or out.shape[2] != self.hm_size or out.shape[3] != self.hm_size \
-                or channel_offset + n_out > out.shape[1]:
+                or channel_offset + 2 * self.num_heatmap > out.shape[1]:
             raise ValueError("output tensor does not hold the requested channel slice")
+        return B
+
+    def _out_slice(self, out, channel_offset):
+        """(address of out[0, channel_offset], elements between two frames of out) as the estimator entries take them"""
+        hw = self.hm_size * self.hm_size
+        return ptr(out, 4 * channel_offset * hw), out.shape[1] * hw
+
+    def forward_into(self, left, right, out, channel_offset: int = 0, workspace=None):
+        """Write this net's [B, 2*n_hm, S, S] output into out[:, channel_offset : channel_offset + 2*n_hm]."""
+        if self.training:
+            raise NotImplementedError("forward_into writes the eval-mode result (folded BatchNorm) into a caller's slice; in train mode call the module itself (differentiable path) or .eval() first")
+        B = self._check_stereo_io(left, right, out, channel_offset)
         if B == 0:
             return out
         dev = left.device
@@ -630,11 +559,8 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
                 self._frozen_check(dev)
             ws = workspace if workspace is not None else self._workspace(B, dev)
             self._ws = ws
-            hw = self.hm_size * self.hm_size
-            _lib.check(_lib.load().egotap_hm_forward(
-                self._ensure_handle(), self._net, C.c_void_p(left.data_ptr()), C.c_void_p(right.data_ptr()), B,
-                C.c_void_p(out.data_ptr() + 4 * channel_offset * hw), out.shape[1] * hw, C.c_void_p(ws.data_ptr()),
-                ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(_lib.load().egotap_hm_forward(self._ensure_handle(), self._net, ptr(left), ptr(right), B, *self._out_slice(out, channel_offset),
+                                                     ptr(ws), ws.numel(), stream(dev)))
         return out
 
     @torch.no_grad()
@@ -646,60 +572,37 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
         if self.bottleneck:
             raise NotImplementedError(f"backbone {self.model_name!r}: no batch-statistics forward (resnet18 / resnet34 have one)")
         _spec.hm_check_batch_stats_side(self.hm_size, "forward_bnbatch_into (batch-statistics BatchNorm)")
-        if getattr(self, "precision", "f32") != "bf16":
+        if self.precision != "bf16":
             raise _lib.EgotapError("forward_bnbatch_into runs on the bf16 channels-last kernels: set_precision('bf16') first "
                                    "(fp32 / bf16x3: hm_training.hm_train_forward_nograd)")
-        for t in (left, right, out):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise _lib.EgotapError("heatmap estimator needs contiguous float32 CUDA tensors (no CPU fallback)")
-        B, S = left.shape[0], 4 * self.hm_size
-        if tuple(left.shape) != (B, 3, S, S) or tuple(right.shape) != (B, 3, S, S):
-            raise ValueError(f"expected left/right [B, 3, {S}, {S}], got {tuple(left.shape)} / {tuple(right.shape)}")
-        n_out = 2 * self.num_heatmap
-        if out.dim() != 4 or out.shape[0] != B or out.shape[2] != self.hm_size or out.shape[3] != self.hm_size \
-                or channel_offset + n_out > out.shape[1]:
-            raise ValueError("output tensor does not hold the requested channel slice")
+        B = self._check_stereo_io(left, right, out, channel_offset)
         if B < 2:
             raise ValueError("batch-statistics BatchNorm needs at least two frames")
         dev = left.device
         chunk = B if chunk is None or chunk <= 0 else min(int(chunk), B)
         with torch.cuda.device(dev):
             self._bind(dev)
-            lib, h = _lib.load(), self._ensure_handle()
-            need = C.c_size_t()
-            _lib.check(lib.egotap_hm_forward_bnbatch_workspace_bytes(h, B, chunk, C.byref(need)))
             ws = workspace
-            if ws is None or ws.numel() < need.value or ws.device != dev:
-                cur = getattr(self, "_ws_bn", None)
-                if cur is None or cur.numel() < need.value or cur.device != dev:
-                    self._ws_bn = None
-                    self._ws_bn = torch.empty(need.value, dtype=torch.uint8, device=dev)
-                ws = self._ws_bn
-            hw = self.hm_size * self.hm_size
-            _lib.check(lib.egotap_hm_forward_bnbatch(
-                h, self._net, C.c_void_p(left.data_ptr()), C.c_void_p(right.data_ptr()), B,
-                C.c_void_p(out.data_ptr() + 4 * channel_offset * hw), out.shape[1] * hw, chunk, C.c_void_p(ws.data_ptr()), ws.numel(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            if ws is None or ws.numel() < self._bnbatch_bytes(B, chunk) or ws.device != dev:
+                ws = self.bnbatch_workspace(B, chunk, dev)
+            _lib.check(_lib.load().egotap_hm_forward_bnbatch(self._ensure_handle(), self._net, ptr(left), ptr(right), B, *self._out_slice(out, channel_offset),
+                                                             chunk, ptr(ws), ws.numel(), stream(dev)))
             if self._frozen_sig is not None:
                 self._frozen_sig = ()      # the kernels moved the running statistics without a _version bump: the next frozen forward folds them again
         return out
 
     def bnbatch_intermediate(self, name: str, B: int, chunk: int, ws=None):
         """bf16 view [B * s * s, 2 C] of a backbone map of the LAST forward_bnbatch_into inside its workspace (parity tests)"""
-        off, n = C.c_size_t(), C.c_int64()
-        _lib.check(_lib.load().egotap_hm_forward_bnbatch_intermediate(self._ensure_handle(), B, min(chunk, B) if chunk else B, name.encode(), C.byref(off), C.byref(n)))
-        ws = ws if ws is not None else self._ws_bn
-        return ws[off.value: off.value + 2 * n.value].view(torch.bfloat16)
+        self._ensure_handle()
+        return self._abi.intermediate(_lib.load().egotap_hm_forward_bnbatch_intermediate, ws if ws is not None else self._ws_bn, B,
+                                      min(chunk, B) if chunk else B, name=name, dtype=torch.bfloat16)
+
+    def _bnbatch_bytes(self, B, chunk):
+        return _session.nbytes(_lib.load().egotap_hm_forward_bnbatch_workspace_bytes, self._ensure_handle(), B, min(chunk, B) if chunk else B)
 
     def bnbatch_workspace(self, B, chunk, device):
         """scratch of forward_bnbatch_into for (B, chunk), kept on the module (both estimators of a wrapper can share one)"""
-        need = C.c_size_t()
-        _lib.check(_lib.load().egotap_hm_forward_bnbatch_workspace_bytes(self._ensure_handle(), B, min(chunk, B) if chunk else B, C.byref(need)))
-        cur = getattr(self, "_ws_bn", None)
-        if cur is None or cur.numel() < need.value or cur.device != device:
-            self._ws_bn = None
-            self._ws_bn = torch.empty(need.value, dtype=torch.uint8, device=device)
-        return self._ws_bn
+        return _session.grown(self, "_ws_bn", self._bnbatch_bytes(B, chunk), device, drop_first=True)
 
     @torch.no_grad()
     def _forward_bottleneck(self, left, right, out, channel_offset):
@@ -709,10 +612,8 @@ class HeatMap_UnrealEgo_Shared(_FrozenWeights, nn.Module):
         [2B, C, s, s] IS the stereo concat [B, 2C, s, s]; upsamples and 1x1 skips write channel slices of the concat buffers in place."""
         from . import hm_ops as H
         h = self._ensure_handle()
-        sd = {k: v for k, v in self.state_dict(keep_vars=True).items()}
-        for k, t in sd.items():
-            if t.device != left.device or not t.is_contiguous() or t.dtype not in (torch.float32, torch.long):
-                raise _lib.EgotapError(f"parameter {k}: need a contiguous fp32 tensor (or int64 counter) on {left.device}")
+        sd = self._bound_tensors()
+        _session.check_bindable(sd, left.device)
         BB, AB = "backbone.backbone.backbone.", "after_backbone."
         bn = lambda k: (sd[k + ".weight"], sd[k + ".bias"], sd[k + ".running_mean"], sd[k + ".running_var"])       # noqa: E731
         B, S0, dev = left.shape[0], left.shape[2], left.device

@@ -5,35 +5,14 @@ egotap_amd/training.py (the autograd glue) and by the per-operator parity tests.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import lib as _lib
+from .session import Scratch, ptr as _p, stream as _s      # noqa: F401  (hm_ops, training.py and the tools take them from here)
 
 LD_PLAIN, LD_PATCH, LD_TOKENS, LD_ROT, LD_STEREO, LD_STEREO_GATED = range(6)
 TE_NONE, TE_BIAS, TE_BIAS_RES, TE_BIAS_GELU_SAVE, TE_ACCUM, TE_GELU_GRAD = range(6)
 TE_SCATTER_PATCH, TE_SCATTER_ROT = 7, 8          # out = the heatmaps' gradient [B, 6J, S, S] (include/egotap.h, egotap_train_gemm_nt)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-class Scratch:
-    """Grow-only device scratch for split-M slabs / column-sum partials (never shrinks, reused by every call)."""
-
-    def __init__(self):
-        self.buf = None
-
-    def get(self, nbytes: int, device):
-        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
-            self.buf = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)
-        return self.buf
 
 
 _scratch = Scratch()

@@ -121,7 +121,7 @@ def _bind_grads(net, h, ga, G):
     if getattr(net, "_grads_bound", None) != sig:
         lib = _lib.load()
         for k, g in G.items():
-            _lib.check(lib.egotap_bind_grad(h, k.encode(), C.c_void_p(g.data_ptr()), g.numel()))
+            _lib.check(lib.egotap_bind_grad(h, k.encode(), T._p(g), g.numel()))
         net._grads_bound = sig
 
 
@@ -304,7 +304,7 @@ class LiftTrainFn(torch.autograd.Function):
         # attention: exact fp32 unless the whole step is bf16.  Recomputing P = exp(S - lse) from split-bf16 scores (2^-16 per
         # product) costs ~1e-4 relative in every probability, and gradients that are sums with heavy cancellation (mask_token)
         # then miss the reference-golden gate (2.6 % of the tensor's typical magnitude against 0.5 %): bf16x3 stays fp32-grade.
-        prec = "bf16" if getattr(net, "precision", "f32") == "bf16" else "f32"
+        prec = "bf16" if net.precision == "bf16" else "f32"
         B, D, seq, heads = hm.shape[0], p.vit_dim, p.seq, p.vit_heads
         M = B * seq
         lib = _lib.load()
@@ -615,7 +615,7 @@ def lift_train_forward(net, hm):
                                   f"--load_size_heatmap {net.preset.hm_size} gives {net.preset.seq} tokens -- evaluation runs at any side that is a multiple of 16")
     params = dict(net.named_parameters())
     # net.bf16_storage = False keeps fp32 tensors in HBM under the bf16 arithmetic (round 1's path: operands converted per launch)
-    bf16 = getattr(net, "precision", "f32") == "bf16"
+    bf16 = net.precision == "bf16"
     bf16s = bf16 and net.preset.vit_dim == 1024 and getattr(net, "bf16_storage", True)
     if getattr(net, "one_call_training", True) and (bf16s or not bf16 or net.preset.vit_dim != 1024):
         fn = LiftTrainOneCallFn        # the library picks the bf16-storage step itself (precision bf16, vit_dim 1024)

@@ -328,3 +328,42 @@ def test_frames_are_independent_of_their_batch():
     err = float((big[:3] - small).abs().max())
     print(f"frame in B = 37 against the same frame in B = 3: max |diff| = {err:.2e} (gate 1e-5)")
     assert err <= 1e-5
+
+
+# ------------------------------------------------------------------------------------------------------------ 9. one session
+def test_second_call_creates_and_binds_nothing(monkeypatch):
+    """the host side of two consecutive calls (B = 2 in chunks of one frame, so the chunk loop runs twice): the serving entry creates ONE handle
+    and binds on the first call only, the head's graphed entry captures once -- and both keep the bits of evaluate() / predict_pose"""
+    from egotap_amd import lib as L
+    m, p = _model("UnrealEgo", 64)
+    m.opt.hm_chunk = 1
+    m.__dict__.pop("_rgb", None)                                   # (the cached model may have served before: start without a serving handle)
+    left, right = _frames("session", 2, 64)
+    want, want_cat = _evaluate(m, p, left, right)
+    lib, count = L.load(), {}
+    for name in ("egotap_create", "egotap_bind_param", "egotap_predict_pose_rgb_workspace_bytes", "egotap_lift_workspace_bytes"):
+        def counted(*args, _fn=getattr(lib, name), _name=name):
+            count[_name] = count.get(_name, 0) + 1
+            return _fn(*args)
+        monkeypatch.setattr(lib, name, counted)
+    first = m.predict_pose_from_rgb(left, right).clone()
+    assert count["egotap_create"] == 1 and count["egotap_bind_param"] > 0 and count["egotap_predict_pose_rgb_workspace_bytes"] == 1
+    binds = count["egotap_bind_param"]
+    second = m.predict_pose_from_rgb(left, right)
+    torch.cuda.synchronize()
+    assert count["egotap_create"] == 1 and count["egotap_bind_param"] == binds and count["egotap_predict_pose_rgb_workspace_bytes"] == 2
+    assert torch.equal(first, want) and torch.equal(second, want)
+    net = m.net_AutoEncoder
+    net.__dict__.pop("_graphs", None)
+    eager = net.predict_pose(want_cat).clone()
+    count.clear()
+    a = net.predict_pose_graphed(want_cat).clone()
+    sized = count.get("egotap_lift_workspace_bytes", 0)            # the capture sizes the module's workspace (eager warm-up) and the graph's own
+    b = net.predict_pose_graphed(want_cat)
+    torch.cuda.synchronize()
+    try:
+        assert len(net._graphs) == 1 and "egotap_create" not in count and "egotap_bind_param" not in count
+        assert sized == 2 and count["egotap_lift_workspace_bytes"] == sized      # a replay asks for nothing
+        assert torch.equal(a, eager) and torch.equal(b, eager) and torch.equal(eager, want)
+    finally:
+        net._graphs.clear()
