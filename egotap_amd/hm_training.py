@@ -10,6 +10,7 @@ from . import train_ops as T
 from .session import grown
 
 STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))
+TRACE_CANARY = -12345.0          # what a traced step fills its concat buffers with before their two writers run (net._stage_trace)
 BB = "backbone.backbone.backbone."
 AB = "after_backbone."
 
@@ -21,22 +22,31 @@ def _eyes(t, B):
     return [H.View(v, e * C_, C_) for e in range(2)]
 
 
-def _bn_fwd(z, y, P, buf, k, B, res=None, relu=True):
+def _bn_fwd(z, y, P, buf, k, B, res=None, relu=True, tr=None):
     """BatchNorm2d in train mode, ONE EYE AT A TIME: the reference runs the shared backbone once on the left batch and once on
-    the right batch (net_architecture.py:45-50), so batch statistics are per eye and the running stats move twice per step"""
+    the right batch (net_architecture.py:45-50), so batch statistics are per eye and the running stats move twice per step.
+    tr (stage trace): the running statistics before the step, after the left and after the right update, as tr["run:" + k]"""
     stats = []
+    run = (buf[k + ".running_mean"], buf[k + ".running_var"])
+    if tr is not None:
+        tr["run:" + k] = [(run[0].clone(), run[1].clone())]
     for e in range(2):
         stats.append(H.bn2d_fwd(_eyes(z, B)[e], _eyes(y, B)[e], P[k + ".weight"], P[k + ".bias"], buf[k + ".running_mean"], buf[k + ".running_var"],
                                 res=_eyes(res, B)[e] if res is not None else None, relu=relu))
         buf[k + ".num_batches_tracked"] += 1
+        if tr is not None:
+            tr["run:" + k].append((run[0].clone(), run[1].clone()))
     return stats
 
 
-def _bn_bwd(z, y, dy, P, k, stats, dz, G, B, dres=None, relu=True):
+def _bn_bwd(z, y, dy, P, k, stats, dz, G, B, dres=None, relu=True, tr=None):
+    """tr (stage trace): dgamma / dbeta as eye 0 wrote them, as tr["eye0:" + k + ".weight" / ".bias"] (eye 1 accumulates on top)"""
     for e in range(2):
         mean, rstd = stats[e]
         H.bn2d_bwd(_eyes(z, B)[e], _eyes(y, B)[e] if y is not None else None, _eyes(dy, B)[e], P[k + ".weight"], mean, rstd, _eyes(dz, B)[e],
                    G(k + ".weight"), G(k + ".bias"), dres=_eyes(dres, B)[e] if dres is not None else None, relu=relu, accumulate=e == 1)
+        if tr is not None and e == 0:
+            tr["eye0:" + k + ".weight"], tr["eye0:" + k + ".bias"] = G(k + ".weight").clone(), G(k + ".bias").clone()
 
 
 def _param_items(net):
@@ -99,12 +109,16 @@ class HmTrainFn(torch.autograd.Function):
         # frozen estimators of stage 2 (hm_train_forward_nograd): nothing is kept for a backward, every map is dropped as soon as its
         # consumer has run -- a 1024-frame batch peaks at a few concat buffers instead of every activation of the network
         keep = any(ctx.needs_input_grad[3:])
+        # net._stage_trace = {} (tests/test_gpu_hm_train_stages.py): the saved activations, the running statistics between the two eyes' updates
+        # and the concat buffers between their two writers are kept under names, so that every stage can be checked on its own inputs.
+        # The concat buffers then start from a canary.  Without the attribute nothing is cloned or kept and the launches are the same.
+        tr = getattr(net, "_stage_trace", None) if keep else None
         with torch.no_grad():
             x0 = torch.stack([left, right], 1).reshape(N2, 3, S0, S0) if keep else None   # image n = 2b + eye (plumbing copy, needed by the stem wgrad)
             z0 = new(N2, 64, S0 // 2, S0 // 2)
             H.stem_fwd(left, right, P[BB + "conv1.weight"], z0)
             l0 = torch.empty_like(z0)
-            m0 = _bn_fwd(z0, l0, P, buf, BB + "bn1", B)
+            m0 = _bn_fwd(z0, l0, P, buf, BB + "bn1", B, tr=tr)
             p0 = new(N2, 64, S0 // 4, S0 // 4)
             H.maxpool_fwd(l0, p0)
             if keep:
@@ -119,18 +133,20 @@ class HmTrainFn(torch.autograd.Function):
                     so = side // stride
                     z1, y1 = new(N2, c, so, so), new(N2, c, so, so)
                     H.conv_fwd(h, x, P[k + "conv1.weight"], z1, taps=9, stride=stride)
-                    m1 = _bn_fwd(z1, y1, P, buf, k + "bn1", B)
+                    m1 = _bn_fwd(z1, y1, P, buf, k + "bn1", B, tr=tr)
                     rec = dict(k=k, xin=x, stride=stride, cin=cin, c=c, z1=z1, y1=y1, m1=m1)
                     idt = x
                     if (k + "downsample.0.weight") in P:
                         zd, yd = new(N2, c, so, so), new(N2, c, so, so)
                         H.conv_fwd(h, x, P[k + "downsample.0.weight"], zd, taps=1, stride=stride)
-                        md = _bn_fwd(zd, yd, P, buf, k + "downsample.1", B, relu=False)
+                        md = _bn_fwd(zd, yd, P, buf, k + "downsample.1", B, relu=False, tr=tr)
                         rec.update(zd=zd, md=md)
+                        if tr is not None:
+                            rec["yd"] = yd
                         idt = yd
                     z2, y2 = new(N2, c, so, so), new(N2, c, so, so)
                     H.conv_fwd(h, y1, P[k + "conv2.weight"], z2, taps=9, stride=1)
-                    m2 = _bn_fwd(z2, y2, P, buf, k + "bn2", B, res=idt)
+                    m2 = _bn_fwd(z2, y2, P, buf, k + "bn2", B, res=idt, tr=tr)
                     rec.update(z2=z2, y2=y2, m2=m2, level=i - 1 if b == net.blocks[i - 1] - 1 else None)
                     if keep:
                         blocks.append(rec)
@@ -144,17 +160,29 @@ class HmTrainFn(torch.autograd.Function):
             u4 = new(B, 1024, s8, s8)
             H.conv_fwd(h, L[3], P[AB + "layer4_1x1.0.weight"], u4, bias=P[AB + "layer4_1x1.0.bias"], taps=1, relu=True)
             cat3 = new(B, 1540, s16, s16)
+            if tr is not None:
+                cat3.fill_(TRACE_CANARY)
             H.upsample_fwd(u4, H.View(cat3, 0, 1024))
+            if tr is not None:
+                tr["cat3_after_upsample"] = cat3.clone()
             H.conv_fwd(h, L[2], P[AB + "layer3_1x1.0.weight"], H.View(cat3, 1024, 516), bias=P[AB + "layer3_1x1.0.bias"], taps=1, relu=True)
             x3 = new(B, 1024, s16, s16)
             H.conv_fwd(h, cat3, P[AB + "conv_up3.0.weight"], x3, bias=P[AB + "conv_up3.0.bias"], taps=9, relu=True)
             cat2 = new(B, 1280, s32, s32)
+            if tr is not None:
+                cat2.fill_(TRACE_CANARY)
             H.upsample_fwd(x3, H.View(cat2, 0, 1024))
+            if tr is not None:
+                tr["cat2_after_upsample"] = cat2.clone()
             H.conv_fwd(h, L[1], P[AB + "layer2_1x1.0.weight"], H.View(cat2, 1024, 256), bias=P[AB + "layer2_1x1.0.bias"], taps=1, relu=True)
             x2 = new(B, 512, s32, s32)
             H.conv_fwd(h, cat2, P[AB + "conv_up2.0.weight"], x2, bias=P[AB + "conv_up2.0.bias"], taps=9, relu=True)
             cat1 = new(B, 640, s64, s64)
+            if tr is not None:
+                cat1.fill_(TRACE_CANARY)
             H.upsample_fwd(x2, H.View(cat1, 0, 512))
+            if tr is not None:
+                tr["cat1_after_upsample"] = cat1.clone()
             H.conv_fwd(h, L[0], P[AB + "layer1_1x1.0.weight"], H.View(cat1, 512, 128), bias=P[AB + "layer1_1x1.0.bias"], taps=1, relu=True)
             x1 = new(B, 512, s64, s64)
             H.conv_fwd(h, cat1, P[AB + "conv_up1.0.weight"], x1, bias=P[AB + "conv_up1.0.bias"], taps=9, relu=True)
@@ -163,6 +191,8 @@ class HmTrainFn(torch.autograd.Function):
             H.conv_fwd(h, x1, P[AB + "conv_heatmap.weight"], out, bias=P[AB + "conv_heatmap.bias"], taps=1)
             if keep:
                 sv.update(blocks=blocks, L=L, u4=u4, cat3=cat3, x3=x3, cat2=cat2, x2=x2, cat1=cat1, x1=x1)
+            if tr is not None:
+                tr.update(saved=sv, out=out)
         ctx.sv, ctx.net, ctx.keys, ctx.P = (sv if keep else None), net, keys, P
         return out
 
@@ -185,6 +215,13 @@ class HmTrainFn(torch.autograd.Function):
         red.begin(ga["flat"])
         G = {}
         dout = dout.detach().float().contiguous()
+        # net._stage_trace = {} (tests): every stage's incoming gradient and every tensor it writes, under a stable name; clones where the
+        # buffer is changed in place later (dy before the pyramid add, dxin before the accumulating dgrad, an arena slot after each eye)
+        tr = getattr(net, "_stage_trace", None)
+
+        def keep(name, t, clone=False):
+            if tr is not None:
+                tr[name] = t.clone() if clone else t
 
         def grad_of(key):
             if key not in G:
@@ -199,19 +236,25 @@ class HmTrainFn(torch.autograd.Function):
             H.chansum(dy_view, grad_of(AB + name + ".bias"))
             if want_dx:
                 H.conv_dgrad(h, dy_view, w, dx, taps=taps, stride=1)
+            keep("g:" + AB + name + ".weight", G[AB + name + ".weight"], True)
+            keep("g:" + AB + name + ".bias", G[AB + name + ".bias"], True)
 
         with torch.no_grad():
             L = sv["L"]
             s64, s32, s16, s8 = L[0].shape[2], L[1].shape[2], L[2].shape[2], L[3].shape[2]
             new = lambda *shape: torch.empty(shape, device=dev)    # noqa: E731
             # conv_heatmap
+            keep("dout", dout)
             dx1 = new(*sv["x1"].shape)
             bias_conv_bwd("conv_heatmap", dout, sv["x1"], 1, dx=dx1)
+            keep("dx1", dx1)
             # conv_up1 (relu) <- cat1
             dz = torch.empty_like(dx1)
             H.relu_bwd(sv["x1"], dx1, dz)
             dcat1 = new(*sv["cat1"].shape)
             bias_conv_bwd("conv_up1.0", dz, sv["cat1"], 9, dx=dcat1)
+            keep("dz:conv_up1.0", dz)
+            keep("dcat1", dcat1)
             dL = [None] * 4                 # gradients of the pyramid levels from the decoder, [B, 2C, s, s] views
 
             def skip_bwd(name, cat, dcat, c0, cn, level):
@@ -221,6 +264,8 @@ class HmTrainFn(torch.autograd.Function):
                 dl = torch.empty_like(L[level])
                 bias_conv_bwd(name, dzs, L[level], 1, dx=dl)
                 dL[level] = dl
+                keep("dz:" + name, dzs)
+                keep(f"dL{level}", dl)
 
             skip_bwd("layer1_1x1.0", sv["cat1"], dcat1, 512, 128, 0)
             dx2 = new(*sv["x2"].shape)
@@ -229,6 +274,9 @@ class HmTrainFn(torch.autograd.Function):
             H.relu_bwd(sv["x2"], dx2, dz)
             dcat2 = new(*sv["cat2"].shape)
             bias_conv_bwd("conv_up2.0", dz, sv["cat2"], 9, dx=dcat2)
+            keep("dx2", dx2)
+            keep("dz:conv_up2.0", dz)
+            keep("dcat2", dcat2)
             skip_bwd("layer2_1x1.0", sv["cat2"], dcat2, 1024, 256, 1)
             dx3 = new(*sv["x3"].shape)
             H.upsample_bwd(H.View(dcat2, 0, 1024), dx3)
@@ -236,6 +284,9 @@ class HmTrainFn(torch.autograd.Function):
             H.relu_bwd(sv["x3"], dx3, dz)
             dcat3 = new(*sv["cat3"].shape)
             bias_conv_bwd("conv_up3.0", dz, sv["cat3"], 9, dx=dcat3)
+            keep("dx3", dx3)
+            keep("dz:conv_up3.0", dz)
+            keep("dcat3", dcat3)
             skip_bwd("layer3_1x1.0", sv["cat3"], dcat3, 1024, 516, 2)
             du4 = new(*sv["u4"].shape)
             H.upsample_bwd(H.View(dcat3, 0, 1024), du4)
@@ -244,6 +295,9 @@ class HmTrainFn(torch.autograd.Function):
             dl4 = torch.empty_like(L[3])
             bias_conv_bwd("layer4_1x1.0", dz, L[3], 1, dx=dl4)
             dL[3] = dl4
+            keep("du4", du4)
+            keep("dz:layer4_1x1.0", dz)
+            keep("dL3", dl4)
             red.bucket_ready(ga["bounds"][0], ga["bounds"][1])          # the decoder's gradients are final
             # backbone, last block first.  dy = gradient of the current block's output (pyramid levels add their decoder share)
             blocks = sv["blocks"]
@@ -259,32 +313,47 @@ class HmTrainFn(torch.autograd.Function):
                     if dy is None:
                         dy = share
                     else:
+                        keep(k + "dy_before_add", dy, True)
                         T.add_inplace(dy, share)
+                keep(k + "dy", dy)
                 dz2, dres = torch.empty_like(r["z2"]), torch.empty_like(r["z2"])
-                _bn_bwd(r["z2"], r["y2"], dy, P, k + "bn2", r["m2"], dz2, grad_of, B, dres=dres)
+                _bn_bwd(r["z2"], r["y2"], dy, P, k + "bn2", r["m2"], dz2, grad_of, B, dres=dres, tr=tr)
                 H.conv_wgrad(dz2, r["y1"], grad_of(k + "conv2.weight"), ks=3, stride=1, precision=prec)
                 dy1 = torch.empty_like(r["y1"])
                 H.conv_dgrad(h, dz2, P[k + "conv2.weight"], dy1, taps=9, stride=1)
                 dz1 = torch.empty_like(r["z1"])
-                _bn_bwd(r["z1"], r["y1"], dy1, P, k + "bn1", r["m1"], dz1, grad_of, B)
+                _bn_bwd(r["z1"], r["y1"], dy1, P, k + "bn1", r["m1"], dz1, grad_of, B, tr=tr)
                 H.conv_wgrad(dz1, r["xin"], grad_of(k + "conv1.weight"), ks=3, stride=stride, precision=prec)
                 dxin = torch.empty_like(r["xin"])
                 if "zd" in r:
                     dzd = torch.empty_like(r["zd"])
-                    _bn_bwd(r["zd"], None, dres, P, k + "downsample.1", r["md"], dzd, grad_of, B, relu=False)
+                    _bn_bwd(r["zd"], None, dres, P, k + "downsample.1", r["md"], dzd, grad_of, B, relu=False, tr=tr)
                     H.conv_wgrad(dzd, r["xin"], grad_of(k + "downsample.0.weight"), ks=1, stride=stride)
                     H.conv_dgrad(h, dzd, P[k + "downsample.0.weight"], dxin, taps=1, stride=stride)
+                    keep(k + "dzd", dzd)
+                    keep(k + "dxin_first", dxin, True)
                     H.conv_dgrad(h, dz1, P[k + "conv1.weight"], dxin, taps=9, stride=stride, accumulate=True)
                 else:
                     dxin.copy_(dres)                  # identity branch (plumbing copy), then the conv branch on top
+                    keep(k + "dxin_first", dxin, True)
                     H.conv_dgrad(h, dz1, P[k + "conv1.weight"], dxin, taps=9, stride=stride, accumulate=True)
+                if tr is not None:
+                    # (dxin is cloned: the next block down adds its pyramid share into it in place)
+                    tr.update({k + "dz2": dz2, k + "dres": dres, k + "dy1": dy1, k + "dz1": dz1, k + "dxin": dxin.clone()})
+                    for name in G:
+                        if name.startswith(k):
+                            tr["g:" + name] = G[name].clone()
                 dy = dxin
             # stem
             dl0 = torch.empty_like(sv["l0"])
             H.maxpool_bwd(sv["l0"], dy, dl0)
             dz0 = torch.empty_like(sv["z0"])
-            _bn_bwd(sv["z0"], sv["l0"], dl0, P, BB + "bn1", sv["m0"], dz0, grad_of, B)
+            _bn_bwd(sv["z0"], sv["l0"], dl0, P, BB + "bn1", sv["m0"], dz0, grad_of, B, tr=tr)
             H.conv_wgrad(dz0, sv["x0"], grad_of(BB + "conv1.weight"), ks=7, stride=2)
+            if tr is not None:
+                tr.update(dp0=dy, dl0=dl0, dz0=dz0)
+                for name in (BB + "conv1.weight", BB + "bn1.weight", BB + "bn1.bias"):
+                    tr["g:" + name] = G[name].clone()
             red.bucket_ready(ga["bounds"][2], ga["bounds"][3])
             red.finish()                    # the compute stream waits for the outstanding buckets; gradients arrive averaged
         ctx.sv = None
@@ -297,6 +366,8 @@ def hm_train_forward(net, left, right):
     from . import spec as _spec
     _spec.hm_check_batch_stats_side(net.hm_size, "the train-mode estimator forward (batch-statistics BatchNorm, stage-1 training)")
     params = [p for _, p in _param_items(net)]
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):       # a backward will follow: refuse here, before anything is launched
+        _spec.hm_check_train_side(net.hm_size, "the differentiable train-mode estimator forward (stage-1 training)")
     net._bind(left.device)
     if net.precision != "f32":          # bf16 modes: scratch for the repacked conv weights (kept on the module)
         from . import lib as _lib

@@ -146,6 +146,20 @@ def hm_check_batch_stats_side(hm_size: int, what: str) -> None:
                                   f"(256x256 / 512x512 RGB), not {hm_size}; the eval-mode estimator forward runs at every multiple of 16")
 
 
+# ... and the sides at which the estimator's BACKWARD is built: the 3x3 / 1x1 weight-gradient kernels (hm_train.h conv_wgrad_kernel) have no
+# instantiation at map width 128 (their double-buffered row tiles exceed the LDS there), so a stage-1 step at 512x512 RGB cannot finish
+HM_TRAIN_SIDES = (64,)
+
+
+def hm_check_train_side(hm_size: int, what: str) -> None:
+    """raise NotImplementedError by name when `what` (a path that needs the estimator's gradient) is asked for at a side without a backward"""
+    hm_check_batch_stats_side(hm_size, what)
+    if hm_size not in HM_TRAIN_SIDES:
+        raise NotImplementedError(f"{what} is built at heatmap side {' and '.join(map(str, HM_TRAIN_SIDES))} only (256x256 RGB), not {hm_size}: "
+                                  f"the weight-gradient kernels have no instantiation at map width {hm_size}; the batch-statistics forward "
+                                  f"without a gradient (hm_train_forward_nograd) runs at sides {' and '.join(map(str, HM_BATCH_STATS_SIDES))}")
+
+
 HM_BLOCKS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}      # BasicBlock ResNets of torchvision (net_architecture.py:57-60)
 HM_BOTTLENECK = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3)}  # Bottleneck ResNets (net_architecture.py:61-64), expansion 4
 

@@ -44,3 +44,43 @@ def hm_net(which="pos", device="cuda", preset="UnrealEgo", hm=64, model_name="re
         net = net.to(device).eval()
         _cache[key] = (net, sd_np)
     return _cache[key]
+
+
+def hm_handle(precision="f32", device="cuda"):
+    """C ABI handle of an estimator at `precision` with the repacked-weight scratch of the bf16 convolution kernels bound, the way
+    hm_training.hm_train_forward binds it (without that buffer conv_any runs the fp32 kernels in every mode).  One module per precision,
+    kept alive here: the handle and the buffer belong to it."""
+    from egotap_amd import lib as L
+    from egotap_amd.session import grown
+    from egotap_amd.train_ops import _p
+    key = ("hm_handle", precision, device)
+    if key not in _cache:
+        opt = make_opt()
+        opt.num_rot_heatmap = 0
+        net = networks.HeatMap_UnrealEgo_Shared(opt, "resnet18", input_channel_scale=2).to(device)
+        net.set_precision(precision)
+        _cache[key] = net
+    net = _cache[key]
+    h = net._ensure_handle()
+    if precision != "f32":
+        pack = grown(net, "_pack", L.load().egotap_hmtrain_pack_bytes(), next(net.parameters()).device)
+        L.check(L.load().egotap_hmtrain_set_pack_buffer(h, _p(pack), pack.numel()))
+    return h
+
+
+def conv_kernels_of(h, fn):
+    """kernel names of the convolution launches `fn` makes on handle `h`, in order (the event-timing hook of egotap_debug.h, read after
+    every launch would aggregate by role: so fn is expected to make ONE conv_any launch per call of this function)"""
+    import ctypes as C
+    import json
+    from egotap_amd import lib as L
+    lib = L.load()
+    L.check(lib.egotap_timing_enable(h, 1))
+    try:
+        fn()
+        torch.cuda.synchronize()
+        n, ms, fl = C.c_int(), C.c_double(), C.c_double()
+        L.check(lib.egotap_timing_read(h, C.byref(n), C.byref(ms), C.byref(fl)))
+        return [(d["kernel"], d["launches"]) for d in json.loads(lib.egotap_timing_detail(h).decode())]
+    finally:
+        L.check(lib.egotap_timing_enable(h, 0))

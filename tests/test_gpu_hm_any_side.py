@@ -166,3 +166,19 @@ def test_batch_statistics_paths_refuse_other_sides_by_name():
                   "gt_heatmap_left": torch.zeros((2, 15, 32, 32)), "gt_heatmap_right": torch.zeros((2, 15, 32, 32))})
     with pytest.raises(NotImplementedError, match="64 and 128"):
         s1.optimize_parameters()
+    # side 128: the batch-statistics forward runs, the differentiable one is refused by name before it launches anything (the 3x3 / 1x1
+    # weight-gradient kernels stop at map width 64; tests/test_gpu_hm_train_ops.py test_width_128_operators)
+    net128, _ = hm_net("pos", hm=128)
+    l128, r128 = _rgb("rgbL_ref_128", 1, 128).cuda(), _rgb("rgbR_ref_128", 1, 128).cuda()
+    stats = {k: v.clone() for k, v in net128.named_buffers()}
+    net128.train()
+    try:
+        with pytest.raises(NotImplementedError, match="side 64 only .*not 128"):
+            net128(l128, r128)
+        assert all(torch.equal(v, stats[k]) for k, v in net128.named_buffers())
+    finally:
+        net128.eval()
+    y = hm_training.hm_train_forward_nograd(net128, l128, r128)
+    assert tuple(y.shape) == (1, 30, 128, 128) and bool(torch.isfinite(y).all()) and not y.requires_grad
+    for k, v in stats.items():                      # it ran on batch statistics: the running statistics moved; put them back (the net is shared)
+        net128.state_dict()[k].copy_(v)

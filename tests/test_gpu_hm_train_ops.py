@@ -194,3 +194,205 @@ def test_conv_wgrad_bf16_modes(mode, Cin, Cout, W, N):
     again = torch.empty_like(dw)
     H.conv_wgrad(dy.cuda(), x.cuda(), again, ks=3, stride=1, precision=mode)
     assert torch.equal(dw, again)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The operators as the training step of hm_training.py calls them: on a handle in a bf16 precision mode WITH the repacked-weight scratch
+# bound (gpu_util.hm_handle; without it conv_any takes the fp32 kernels in every mode and a test of the mode tests nothing), on channel
+# slices of wider buffers, accumulating, per eye, and at width 128.  Every case runs twice for equal bits.
+CANARY = -777.0
+
+
+def _rb(t):
+    return t.float().bfloat16().double()
+
+
+def _bf_kernel(mode, taps, stride, cout, w):
+    """does conv_any (egotap_abi.hip) route this forward-form convolution to conv_bf16_kernel?"""
+    return mode != "f32" and taps == 9 and stride == 1 and ((cout >= 128 and w in (64, 32, 16, 8)) or (cout == 64 and w == 64)
+                                                           or (mode == "bf16" and cout == 64 and w == 128))
+
+
+def _conv_gate(mode, routed, ref):
+    return ((3e-4 if mode == "bf16x3" else 2e-4) if routed else 2e-4) * float(ref.abs().mean()) + 1e-5
+
+
+def _twice(fn, out):
+    """run fn (which writes `out` from scratch or on top of what `restore` puts back) twice: equal bits"""
+    fn()
+    first = out.clone()
+    fn()
+    torch.cuda.synchronize()
+    assert torch.equal(first, out), "two runs differ"
+    return first
+
+
+DGRADS = [  # (Cout, Cin, W of dy, N, stride): dx has Cin channels -- the output channels of the kernel that computes it
+    (132, 20, 64, 2, 1), (132, 20, 32, 2, 1), (132, 20, 16, 2, 1), (132, 20, 8, 2, 1),          # fp32 kernels on a bf16-mode handle (20 < 128)
+    (20, 132, 64, 2, 1), (20, 132, 32, 2, 1), (20, 132, 16, 2, 1), (20, 132, 8, 2, 1),          # conv_bf16_kernel, ragged 128 + 4 channel tiles
+    (64, 64, 64, 2, 1),                                                                         # the 64-channel tile (layer1)
+    (128, 64, 16, 2, 2), (128, 64, 32, 2, 2),                # stride 2 through the zero-upsampled dY: dx at width 32 (fp32) and 64 (layer2.0: bf16)
+    (1024, 1540, 16, 1, 1),                                  # conv_up3: 1540 output channels, the pack buffer filled to 99.2 %
+]
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("Cout,Cin,W,N,stride", DGRADS)
+def test_conv_dgrad_bf16_modes(mode, Cout, Cin, W, N, stride):
+    """input gradient under the bf16 modes against float64 autograd of F.conv2d (mode bf16: of the operands rounded to bf16): plain,
+    accumulate=True on a canary-filled dx (res aliases y in the kernel), and dx as a channel slice of a wider canary buffer"""
+    from gpu_util import conv_kernels_of, hm_handle
+    from egotap_amd import hm_ops as H
+    h = hm_handle(mode)
+    Wx = W * stride
+    w, dy = _rand((Cout, Cin, 3, 3), 2, -0.1, 0.1), _rand((N, Cout, W, W), 3)
+    routed = _bf_kernel(mode, 9, 1, Cin, Wx)
+    x = torch.zeros((N, Cin, Wx, Wx), dtype=torch.float64, requires_grad=True)
+    w64, dy64 = (_rb(w), _rb(dy)) if routed and mode == "bf16" else (w.double(), dy.double())
+    F.conv2d(x, w64, None, stride, 1).backward(dy64)
+    ref = x.grad
+    atol = _conv_gate(mode, routed, ref)
+    wd, dyd = w.cuda(), dy.cuda()
+    dx = torch.full((N, Cin, Wx, Wx), 7.0, device="cuda")
+    kern = conv_kernels_of(h, lambda: H.conv_dgrad(h, dyd, wd, dx, taps=9, stride=stride))
+    assert len(kern) == 1 and kern[0][1] == 1, kern
+    assert kern[0][0].startswith("conv_bf16_kernel<") == routed and (not routed or kern[0][0].endswith(f"W{Wx},{mode}>")), kern
+    _twice(lambda: H.conv_dgrad(h, dyd, wd, dx, taps=9, stride=stride), dx)
+    _close(dx, ref, atol=atol, rtol=0.0, msg=f"dx {mode}")
+    # accumulate on top of a canary (small: the sum is rounded to fp32 once more, 2^-24 of its magnitude)
+    def acc():
+        dx.fill_(5.0)
+        H.conv_dgrad(h, dyd, wd, dx, taps=9, stride=stride, accumulate=True)
+    _twice(acc, dx)
+    _close(dx, ref + 5.0, atol=atol + 2.0 ** -24 * (5.0 + float(ref.abs().max())), rtol=0.0, msg=f"dx accumulate {mode}")
+    # into channels [3, 3 + Cin) of a wider buffer
+    wide = torch.full((N, Cin + 8, Wx, Wx), CANARY, device="cuda")
+    _twice(lambda: H.conv_dgrad(h, dyd, wd, H.View(wide, 3, Cin), taps=9, stride=stride), wide)
+    assert torch.equal(wide[:, 3:3 + Cin], _twice(lambda: H.conv_dgrad(h, dyd, wd, dx, taps=9, stride=stride), dx))
+    assert bool((wide[:, :3] == CANARY).all()) and bool((wide[:, 3 + Cin:] == CANARY).all())
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("Cin,Cout,W,N", [(20, 132, 32, 2), (72, 64, 64, 2)])
+def test_conv_fwd_bf16_modes_on_slices(mode, Cin, Cout, W, N):
+    """the decoder's use of the forward kernel: bias + ReLU into a channel slice of a concat buffer, input read from a channel slice"""
+    from gpu_util import conv_kernels_of, hm_handle
+    from egotap_amd import hm_ops as H
+    h = hm_handle(mode)
+    xw, w, b = _rand((N, Cin + 9, W, W), 1), _rand((Cout, Cin, 3, 3), 2, -0.1, 0.1), _rand((Cout,), 4)
+    x = xw[:, 5:5 + Cin]
+    xs, ws = (_rb(x), _rb(w)) if mode == "bf16" else (x.double(), w.double())
+    ref = F.relu(F.conv2d(xs, ws, b.double(), 1, 1))
+    xd, wd, bd = xw.cuda(), w.cuda(), b.cuda()
+    wide = torch.full((N, Cout + 11, W, W), CANARY, device="cuda")
+    run = lambda: H.conv_fwd(h, H.View(xd, 5, Cin), wd, H.View(wide, 4, Cout), bias=bd, taps=9, relu=True)     # noqa: E731
+    kern = conv_kernels_of(h, run)
+    assert kern == [(f"conv_bf16_kernel<3x3,s1,W{W},{mode}>", 1)], kern
+    _twice(run, wide)
+    _close(wide[:, 4:4 + Cout], ref, atol=_conv_gate(mode, True, ref), rtol=0.0, msg=f"conv_fwd {mode}")
+    assert float(ref.mean()) > 0 and bool((ref == 0).any())                       # the ReLU cuts
+    assert bool((wide[:, :4] == CANARY).all()) and bool((wide[:, 4 + Cout:] == CANARY).all())
+
+
+def test_conv_bf16_modes_without_a_pack_buffer_run_fp32():
+    """what the helper is for: set_precision alone leaves conv_any on the fp32 kernels"""
+    from gpu_util import conv_kernels_of
+    from egotap_amd import hm_ops as H
+    from egotap_amd import networks
+    from gpu_util import make_opt
+    opt = make_opt()
+    opt.num_rot_heatmap = 0
+    net = networks.HeatMap_UnrealEgo_Shared(opt, "resnet18", input_channel_scale=2).cuda()
+    net.set_precision("bf16")
+    h = net._ensure_handle()
+    x, w, y = _rand((1, 16, 16, 16), 1).cuda(), _rand((128, 16, 3, 3), 2).cuda(), torch.empty((1, 128, 16, 16), device="cuda")
+    kern = conv_kernels_of(h, lambda: H.conv_fwd(h, x, w, y, taps=9))
+    assert len(kern) == 1 and kern[0][0].startswith("conv_f32_kernel<"), kern
+
+
+@pytest.mark.parametrize("relu,with_res", [(True, True), (True, False), (False, False)])
+def test_bn2d_per_eye_slices_accumulate(relu, with_res):
+    """bn2d_fwd / bn2d_bwd as hm_training._bn_fwd / _bn_bwd call them: once per eye on the two channel-slice views of a [B, 2C, s, s]
+    buffer (image stride = twice the slice), dgamma / dbeta written by eye 0 and accumulated by eye 1; against float64 per-eye BatchNorm.
+    relu=False, y=None is the downsample branch."""
+    from egotap_amd import hm_ops as H
+    B, C_, s = 3, 64, 32
+    z, res, dy = _rand((B, 2 * C_, s, s), 1, -2, 2), _rand((B, 2 * C_, s, s), 2), _rand((B, 2 * C_, s, s), 7)
+    g, b = _rand((C_,), 3, 0.5, 1.5), _rand((C_,), 4)
+    rm, rv = _rand((C_,), 5), _rand((C_,), 6, 0.5, 2.0)
+    gr, br = g.double().requires_grad_(True), b.double().requires_grad_(True)
+    rm64, rv64 = rm.double().clone(), rv.double().clone()
+    refs = []
+    for e in range(2):
+        sl = slice(e * C_, (e + 1) * C_)
+        zr, rr = z[:, sl].double().requires_grad_(True), res[:, sl].double().requires_grad_(True)
+        y = F.batch_norm(zr, rm64, rv64, gr, br, True, 0.1, 1e-5)
+        if with_res:
+            y = y + rr
+        if relu:
+            y = F.relu(y)
+        y.backward(dy[:, sl].double())
+        refs.append((y.detach(), zr.grad, rr.grad, gr.grad.clone(), br.grad.clone(), rm64.clone(), rv64.clone()))
+    zd, resd, dyd, gd, bd = z.cuda(), res.cuda(), dy.cuda(), g.cuda(), b.cuda()
+    yd = torch.full_like(zd, CANARY)
+    dz, dres = torch.full_like(zd, CANARY), torch.full_like(zd, CANARY)
+    dg, db = torch.full((C_,), CANARY, device="cuda"), torch.full((C_,), CANARY, device="cuda")
+    for rep in range(2):
+        rmd, rvd = rm.cuda(), rv.cuda()
+        stats = []
+        for e in range(2):
+            stats.append(H.bn2d_fwd(H.View(zd, e * C_, C_), H.View(yd, e * C_, C_), gd, bd, rmd, rvd, res=H.View(resd, e * C_, C_) if with_res else None, relu=relu))
+            if e == 0:
+                assert bool((yd[:, C_:] == CANARY).all()) or rep == 1                   # eye 0 leaves eye 1's channels alone
+            _close(rmd, refs[e][5], 1e-6)
+            _close(rvd, refs[e][6], 1e-5)
+        for e in range(2):
+            H.bn2d_bwd(H.View(zd, e * C_, C_), H.View(yd, e * C_, C_) if relu else None, H.View(dyd, e * C_, C_), gd, stats[e][0], stats[e][1],
+                       H.View(dz, e * C_, C_), dg, db, dres=H.View(dres, e * C_, C_) if with_res else None, relu=relu, accumulate=e == 1)
+            _close(dg, refs[e][3], 2e-3, rtol=1e-4, msg=f"dgamma after eye {e}")             # (autograd accumulates over the eyes as well)
+            _close(db, refs[e][4], 2e-3, rtol=1e-4, msg=f"dbeta after eye {e}")
+        if rep == 0:
+            first = [t.clone() for t in (yd, dz, dres, dg, db, rmd, rvd)]
+        else:
+            assert all(torch.equal(a, c) for a, c in zip(first, (yd, dz, dres, dg, db, rmd, rvd)))
+    for e in range(2):
+        sl = slice(e * C_, (e + 1) * C_)
+        _close(yd[:, sl], refs[e][0], 2e-5, msg=f"y eye {e}")
+        _close(dz[:, sl], refs[e][1], 2e-5, rtol=1e-3, msg=f"dz eye {e}")
+        if with_res:
+            _close(dres[:, sl], refs[e][2], 1e-6, msg=f"dres eye {e}")
+    if not with_res:
+        assert bool((dres == CANARY).all())
+
+
+def test_width_128_operators():
+    """what a stage-1 step at heatmap side 128 (512 x 512 RGB) would reach and nothing else does.  The 3x3 and 1x1 weight gradients at
+    wout = 128 do not exist (hm_train.h: only the stem's 7x7 / 2 is instantiated at that width; a 128-wide double-buffered row tile of the
+    others exceeds the LDS): the ABI says so by name and leaves dW alone, and hm_training.hm_train_forward refuses the side.  The 3x3 input
+    gradient at wout = 128 and the max-pool backward at side 256 exist: against float64 autograd."""
+    from gpu_util import hm_handle
+    from egotap_amd import hm_ops as H
+    from egotap_amd import lib as L
+    h = hm_handle("f32")
+    N, Cin, Cout, W = 2, 20, 72, 128
+    x, dy = _rand((N, Cin, W, W), 1), _rand((N, Cout, W, W), 3)
+    for ks in (3, 1):
+        dw = torch.full((Cout, Cin, ks, ks), 3.0, device="cuda")
+        with pytest.raises(L.EgotapError, match=f"egotap_hmtrain_conv_wgrad: unsupported ks={ks} stride=1 wout=128"):
+            H.conv_wgrad(dy.cuda(), x.cuda(), dw, ks=ks, stride=1)
+        torch.cuda.synchronize()
+        assert bool((dw == 3.0).all())
+    w, dy = _rand((64, Cin, 3, 3), 2, -0.1, 0.1), _rand((N, 64, W, W), 4)
+    xr = torch.zeros((N, Cin, W, W), dtype=torch.float64, requires_grad=True)
+    F.conv2d(xr, w.double(), None, 1, 1).backward(dy.double())
+    dx = torch.full((N, Cin, W, W), 7.0, device="cuda")
+    _twice(lambda: H.conv_dgrad(h, dy.cuda(), w.cuda(), dx, taps=9), dx)
+    _close(dx, xr.grad, atol=2e-4 * float(xr.grad.abs().mean()) + 1e-5, rtol=0.0, msg="dx at width 128")
+    x = _rand((2, 3, 256, 256), 5)
+    x[1, 2, 2:7, 251:256] = 0.25                                  # ties, at the right edge
+    xr = x.double().requires_grad_(True)
+    dy = _rand((2, 3, 128, 128), 6)
+    F.max_pool2d(xr, 3, 2, 1).backward(dy.double())
+    dx = torch.full_like(x, 9.0, device="cuda")
+    _twice(lambda: H.maxpool_bwd(x.cuda(), dy.cuda(), dx), dx)
+    _close(dx, xr.grad, 1e-6, msg="maxpool backward, side 256")
