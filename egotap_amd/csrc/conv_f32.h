@@ -705,119 +705,40 @@ static __global__ __launch_bounds__(StemCfg::THREADS, 2) void stem_conv7_mfma_ke
                                                                                     const float* __restrict__ beta, const float* __restrict__ mean,
                                                                                     const float* __restrict__ var, float* __restrict__ out, int HIN,
                                                                                     int nimg) {
+#include "conv_f32_stem_body.inc"
+}
+// [r7] the fp32 NCHW stem from camera bytes (egotap_hm_forward_u8 / egotap_predict_pose_rgb_u8 outside the bf16 channels-last route): the same body
+// behind a byte-source request / publish (conv_f32_stem_body.inc).  LDS 104 KB + 3 KB: one workgroup per CU, as the fp32 source.
+struct StemU8 { static constexpr int NG = (StemCfg::PC + 1 + 3) / 4, TAB_FLOATS = 3 * 256; };
+static __global__ __launch_bounds__(StemCfg::THREADS, 2) void stem_conv7_mfma_u8_kernel(const unsigned char* __restrict__ left8, const unsigned char* __restrict__ right8,
+                                                                                       const float* __restrict__ table, const float* __restrict__ w,
+                                                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                                       const float* __restrict__ mean, const float* __restrict__ var,
+                                                                                       float* __restrict__ out, int HIN, int nimg) {
+    constexpr bool BF16OUT = false;
+#define STEM_SRC_U8 1
+#include "conv_f32_stem_body.inc"
+#undef STEM_SRC_U8
+}
+// whether the matrix-core stem takes this geometry (the byte source exists on it alone: elsewhere the caller converts the frames first)
+static inline bool stem_conv7_on_mfma(int HIN) { return (HIN / 2) % StemCfg::XT == 0 && (HIN / 2) % StemCfg::RG == 0; }
+static inline hipError_t stem_conv7_u8_launch(const unsigned char* left, const unsigned char* right, const float* table, const float* w, const float* gamma,
+                                              const float* beta, const float* mean, const float* var, float* out, int HIN, int nimg, int num_cu, hipStream_t s) {
     using Cfg = StemCfg;
-    constexpr int RG = Cfg::RG, XT = Cfg::XT, PR = Cfg::PR, PC = Cfg::PC, PLD = Cfg::PLD, KP = Cfg::KP, THREADS = Cfg::THREADS;
-    extern __shared__ __attribute__((aligned(16))) float stem_sm[];
-    float* xs = stem_sm;                          // [3][PR][PLD]
-    float* ws = stem_sm + Cfg::XS_FLOATS;         // [KP][64]
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l31 = lane & 31, lh = lane >> 5;
-    const int HO = HIN / 2, xsegs = HO / XT, ygroups = HO / RG;
-    const long items = (long)nimg * ygroups * xsegs;
-    for (int i = tid; i < KP * 64; i += THREADS) {
-        const int k = i >> 6, co = i & 63;
-        ws[i] = k < 147 ? w[co * 147 + k] : 0.f;
+    constexpr int LDS = Cfg::LDS_BYTES + StemU8::TAB_FLOATS * 4;
+    static_assert(LDS <= 160 * 1024, "the value table fits behind the weights (one workgroup per CU, as the fp32 source: 104 KB + 3 KB of LDS)");
+    const int HO = HIN / 2;
+    if (!stem_conv7_on_mfma(HIN) || ((uintptr_t)out & 15) != 0 || nimg <= 0) return hipErrorInvalidValue;
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)stem_conv7_mfma_u8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+        if (e != hipSuccess) return e;
+        attr_done = true;
     }
-    // per-lane BatchNorm constants of its two output channels (eval mode); gamma == nullptr: raw convolution output (training)
-    float sc[2] = {1.f, 1.f}, sh[2] = {0.f, 0.f};
-    if (gamma != nullptr) {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int co = nt * 32 + l31;
-            sc[nt] = gamma[co] / sqrtf(var[co] + 1e-5f);
-            sh[nt] = beta[co] - mean[co] * sc[nt];
-        }
-    }
-    // the patch of the NEXT item is requested into registers before the MFMAs of the current one and written to LDS behind them
-    constexpr int NPRE = (3 * PR * PC + THREADS - 1) / THREADS;
-    float pre[NPRE];
-    auto request = [&](long item) __attribute__((always_inline)) {
-        const int xseg_ = (int)(item % xsegs), yg_ = (int)((item / xsegs) % ygroups);
-        const int n_ = (int)(item / ((long)xsegs * ygroups));
-        const float* src = ((n_ & 1) ? right : left) + (long)(n_ >> 1) * 3 * HIN * HIN;
-        const int iy0 = yg_ * RG * 2 - 3, ix0 = xseg_ * XT * 2 - 3;
-#pragma unroll
-        for (int j = 0; j < NPRE; ++j) {
-            const int i = tid + j * THREADS;
-            const int c = i / (PR * PC), rem = i - c * PR * PC, yy = rem / PC, xx = rem - yy * PC;
-            const int y = iy0 + yy, x = ix0 + xx;
-            pre[j] = (i < 3 * PR * PC && y >= 0 && y < HIN && x >= 0 && x < HIN) ? src[((long)c * HIN + y) * HIN + x] : 0.f;
-        }
-    };
-    auto publish = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < NPRE; ++j) {
-            const int i = tid + j * THREADS;
-            const int c = i / (PR * PC), rem = i - c * PR * PC, yy = rem / PC, xx = rem - yy * PC;
-            if (i < 3 * PR * PC) xs[(c * PR + yy) * PLD + xx] = pre[j];
-        }
-    };
-    if ((long)blockIdx.x < items) request(blockIdx.x);
-    for (long it = blockIdx.x; it < items; it += gridDim.x) {
-        const int xseg = (int)(it % xsegs), yg = (int)((it / xsegs) % ygroups);
-        const int n = (int)(it / ((long)xsegs * ygroups));
-        __syncthreads();                          // everyone is done with the previous patch (and the weights are staged)
-        publish();
-        __syncthreads();
-        if (it + gridDim.x < items) request(it + gridDim.x);
-        f32x16 acc[4][2];
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-        const float* ap = xs + (2 * wid) * PLD + 2 * l31;        // output row wid, pixel l31 of row tile 0
-        const float* bp = ws + lh * 64 + l31;
-#pragma unroll
-        for (int s2 = 0; s2 < KP / 2; ++s2) {
-            constexpr int dummy = 0; (void)dummy;
-            const int k0 = 2 * s2, k1 = 2 * s2 + 1;              // this lane half multiplies k = k0 + lh
-            const int o0 = ((k0 / 49) * PR + (k0 % 49) / 7) * PLD + (k0 % 7);
-            const int o1 = k1 < 147 ? ((k1 / 49) * PR + (k1 % 49) / 7) * PLD + (k1 % 7) : 0;
-            const int ko = lh ? o1 : o0;
-            float a[4], b[2];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) a[mt] = ap[ko + 64 * mt];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) b[nt] = bp[k0 * 64 + nt * 32];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt], b[nt], acc[mt][nt], 0, 0, 0);
-        }
-        const int y = yg * RG + wid;
-        if constexpr (BF16OUT) {
-            // lane = channel: 32 lanes write the 64 contiguous bytes of 32 channels of one pixel (the lane halves: two pixels)
-            __bf16* ob = (__bf16*)out + ((((long)(n >> 1) * HO + y) * HO + xseg * XT) * 2 + (n & 1)) * 64 + l31;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int x = mt * 32 + 8 * (r >> 2) + 4 * lh + (r & 3);
-                        const float t = acc[mt][nt][r] * sc[nt] + sh[nt];
-                        ob[(long)x * 128 + nt * 32] = (__bf16)(gamma != nullptr ? fmaxf(t, 0.f) : t);
-                    }
-            continue;
-        }
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            float* dst = out + ((long)n * 64 + nt * 32 + l31) * HO * HO + (long)y * HO + xseg * XT;
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 v;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const float t = acc[mt][nt][4 * g + c] * sc[nt] + sh[nt];
-                        v[c] = gamma != nullptr ? fmaxf(t, 0.f) : t;
-                    }
-                    *(f32x4*)(dst + mt * 32 + 8 * g + 4 * lh) = v;
-                }
-        }
-    }
+    const long items = (long)nimg * (HO / Cfg::RG) * (HO / Cfg::XT);
+    const int grid = (int)(items < num_cu ? items : num_cu);
+    hipLaunchKernelGGL(stem_conv7_mfma_u8_kernel, dim3(grid), dim3(Cfg::THREADS), LDS, s, left, right, table, w, gamma, beta, mean, var, out, HIN, nimg);
+    return hipGetLastError();
 }
 static inline hipError_t stem_conv7_launch(const float* left, const float* right, const float* w, const float* gamma, const float* beta,
                                            const float* mean, const float* var, float* out, int HIN, int nimg, int num_cu, hipStream_t s) {

@@ -34,6 +34,7 @@
 #include "stem_bf16s.h"
 #include "conv64_bf16s.h"
 #include "bn_bf16s.h"
+#include "rgb_u8.h"
 
 // The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
 // inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
@@ -1462,6 +1463,30 @@ static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, in
     return hipErrorInvalidValue;
 }
 
+// [r7] Where an estimator's frames come from: the normalised planar fp32 frames (left / right), or the camera's bytes (left8 / right8: uint8
+// [B, S0, S0, 3], with the fp32 [3][256] value table).  Sides 64 / 128: both stems stage the bytes themselves.  Every other side: the frames are
+// converted into `scratch` (2 x B x 3 x S0^2 floats, the caller's workspace slice) first and the forward proceeds on them as ever.
+struct HmSrc {
+    const float *left, *right;
+    const unsigned char *left8, *right8;
+    const float* table;
+    float* scratch;
+    bool bytes() const { return left8 != nullptr; }
+    HmSrc at(long frame, long rgb) const {      // the source of the frames from `frame` on (rgb = 3 S0^2 elements per frame)
+        HmSrc r = *this;
+        if (left) { r.left = left + frame * rgb; r.right = right + frame * rgb; }
+        if (left8) { r.left8 = left8 + frame * rgb; r.right8 = right8 + frame * rgb; }
+        return r;
+    }
+};
+static inline HmSrc hm_src_f32(const float* left, const float* right) { return HmSrc{left, right, nullptr, nullptr, nullptr, nullptr}; }
+// the converter slice of a byte-source forward of B frames: nothing where the stems read the bytes themselves
+static inline bool hm_stem_reads_bytes(int hm_size) { return hm_size == 64 || hm_size == 128; }
+static inline size_t hm_u8_slice_bytes(const Handle* h, int B) {
+    const size_t S0 = (size_t)h->cfg.hm_size * 4;
+    return hm_stem_reads_bytes(h->cfg.hm_size) ? 0 : (size_t)B * 2 * 3 * S0 * S0 * 4;
+}
+
 struct HmWs {
     size_t L0, P0, S[4][4] /* per stage: Ta, Tb, Td, L */, U4, CAT3, X3, CAT2, X2, CAT1, X1, WPACK, WALL, total;
 };
@@ -1596,7 +1621,7 @@ static inline __bf16* hm_zero_tail(const __bf16* map, size_t bytes) { return (__
 struct ZeroPages { void* p[24]; };
 static __global__ __launch_bounds__(64) void zero_pages_kernel(ZeroPages z) { ((float*)z.p[blockIdx.x])[threadIdx.x] = 0.f; }
 static hipError_t hm_bf16_backbone(Handle* h, const HmParams& p, const PackTable& PT, int& li, int& bi, const HmBf16Bufs& q, const float* left, const float* right, int B,
-                                   int S0, const HmBnBatch* bnb, hipStream_t s) {
+                                   int S0, const HmBnBatch* bnb, hipStream_t s, const HmSrc* bytes = nullptr) {
     const int N2 = 2 * B, cus = device_cu_count();
     const int s64 = S0 / 4, s32 = S0 / 8, s16 = S0 / 16, s8 = S0 / 32;
     char* reg = q.reg;
@@ -1612,7 +1637,11 @@ static hipError_t hm_bf16_backbone(Handle* h, const HmParams& p, const PackTable
         hipLaunchKernelGGL(zero_pages_kernel, dim3(n), dim3(64), 0, s, z);
     }
     // E1 + E2: stem conv7x7/2 + BN + ReLU + max-pool in one kernel (stem_bf16s.h): bf16 [B * s64^2, 2 x 64], image n = 2b + eye in the eye's column half
-    if (!bnb) {
+    if (!bnb && bytes) {          // [r7] the camera's bytes: the same kernel body behind a byte-source staging (stem_bf16s.h, stem_bf16s_body.inc)
+        GemmTimer t(h, s, "hm.stem_u8", "stem_pool_bf16s_u8_kernel", 2.0 * N2 * 64 * 147 * (double)(S0 / 2) * (S0 / 2));
+        hipError_t e = stem_pool_bf16s_u8_launch(bytes->left8, bytes->right8, bytes->table, p.stem_w, p.stem_bn.g, p.stem_bn.b, p.stem_bn.m, p.stem_bn.v, q.P0, S0, N2, cus, s);
+        if (e != hipSuccess) return e;
+    } else if (!bnb) {
         hipError_t e = stem_pool_bf16s_launch(left, right, p.stem_w, p.stem_bn.g, p.stem_bn.b, p.stem_bn.m, p.stem_bn.v, q.P0, S0, N2, cus, s);
         if (e != hipSuccess) return e;
     } else {
@@ -1904,7 +1933,7 @@ extern "C" int egotap_hm_unfreeze(egotap_handle h, int net) {
 // HeatMap_UnrealEgo_Shared.forward(left, right) (model/net_architecture.py:32-36, 45-51, 75-85, 139-173), eval mode.
 #if EGOTAP_IN(0)
 // out_b != nullptr (egotap_predict_pose_rgb's hand-off, bf16 channels-last route only): the result as bf16 at out_b, `out` unused
-static int hm_forward_impl(Handle* h, int net, const float* left, const float* right, int B, float* out, int64_t out_image_stride, void* ws, size_t ws_bytes,
+static int hm_forward_impl(Handle* h, int net, const HmSrc& src, int B, float* out, int64_t out_image_stride, void* ws, size_t ws_bytes,
                            void* stream, __bf16* out_b) {
     // the bf16 channels-last route (fused stem, every convolution on the bf16-storage GEMM): hm_frozen_route is its one predicate, shared with the freeze entries
     // and with egotap_predict_pose_rgb's hand-off, which exists on this route only -- refused here, before anything is launched
@@ -1935,13 +1964,29 @@ static int hm_forward_impl(Handle* h, int net, const float* left, const float* r
     char* base = (char*)ws;
     auto F = [&](size_t off) { return (float*)(base + off); };
     const int N2 = 2 * B;
+    // [r7] the source: fp32 frames, or bytes the stems stage themselves (sides 64 / 128), or bytes converted into the caller's slice first
+    const float *left = src.left, *right = src.right;
+    const bool stem_u8 = src.bytes() && built;
+    static_assert(StemCfg::XT == 128 && StemPoolCfg::XS == 64, "sides 64 / 128 (RGB 256 / 512) are the geometries both stems take");
+    if (src.bytes() && !built) {
+        EGO_CHECK(src.scratch, "egotap_hm_forward: byte source without a converter slice");
+        float* cl = src.scratch;
+        float* cr = cl + (size_t)B * 3 * S0 * S0;
+        GemmTimer t(h, s, "rgb_u8_to_f32", "rgb_u8_to_f32_kernel", 0.0);
+        EGO_HIP(rgb_u8_to_f32_launch(src.left8, src.right8, src.table, cl, cr, B, S0, device_cu_count(), s));
+        left = cl;
+        right = cr;
+    }
 
     // E1: stem conv7x7/2 + BN + ReLU on image n = 2b + eye (the L/R channel concat of every pyramid level is then a view); in the
     // bf16 mode it writes bf16 channels-last itself (half the bytes, and the layout the max-pool and the stages read)
     // [r3] ... bf16 mode: stem, BatchNorm, ReLU AND the max-pool in one kernel on the bf16 matrix cores (stem_bf16s.h): the 128 x 128 x 64
     // map never reaches HBM (round 2's two-kernel form -- fp32-MFMA stem writing bf16 channels-last, then a channels-last max-pool: 2.35 ms
     // against 0.66 per 512 images -- was retired in round 4).
-    if (!fused_stem)
+    if (!fused_stem && stem_u8) {
+        GemmTimer t(h, s, "hm.stem_u8", "stem_conv7_mfma_u8_kernel", 2.0 * N2 * 64 * 147 * (double)(S0 / 2) * (S0 / 2));
+        EGO_HIP(stem_conv7_u8_launch(src.left8, src.right8, src.table, p.stem_w, p.stem_bn.g, p.stem_bn.b, p.stem_bn.m, p.stem_bn.v, F(w.L0), S0, N2, device_cu_count(), s));
+    } else if (!fused_stem)
         EGO_HIP(stem_conv7_launch(left, right, p.stem_w, p.stem_bn.g, p.stem_bn.b, p.stem_bn.m, p.stem_bn.v, F(w.L0), S0, N2, device_cu_count(), s));
     if (fused_stem) {
         // bf16 mode: everything after the stem on bf16 channels-last activations, every convolution on the bf16-storage GEMM
@@ -1968,7 +2013,7 @@ static int hm_forward_impl(Handle* h, int net, const float* left, const float* r
         else hipLaunchKernelGGL(pack_all_bf16s_kernel, dim3(PT.blocks), dim3(256), 0, s, PT, q.reg);
         EGO_HIP(hipGetLastError());
         int li = 0, bi = 0;
-        EGO_HIP(hm_bf16_backbone(h, p, PT, li, bi, q, left, right, B, S0, nullptr, s));
+        EGO_HIP(hm_bf16_backbone(h, p, PT, li, bi, q, left, right, B, S0, nullptr, s, stem_u8 ? &src : nullptr));
         const __bf16* lv[4] = {q.A[0], q.A[1], q.A[2], q.A[3]};
         EGO_HIP(hm_bf16_decoder(h, p, PT, li, q, lv, B, S0, out, out_image_stride, s, out_b));
         EGO_CHECK(bi == PT.nb, "egotap_hm_forward: pack plan out of step with the forward");
@@ -2046,7 +2091,56 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
     if (B == 0) return EGOTAP_OK;
     EGO_CHECK(B > 0 && left && right && out && ws, "egotap_hm_forward: null argument or negative batch");
     EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)out) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "pointers must be 16-byte (ws: 256-byte) aligned");
-    return hm_forward_impl(h, net, left, right, B, out, out_image_stride, ws, ws_bytes, stream, nullptr);
+    return hm_forward_impl(h, net, hm_src_f32(left, right), B, out, out_image_stride, ws, ws_bytes, stream, nullptr);
+}
+
+// ---- [r7] camera bytes: the converter, and one estimator from bytes
+static const char* rgb_u8_refusal(const void* left8, const void* right8, const void* table) {
+    if (!left8 || !right8) return "null frames (left8 and right8 are required)";
+    if (!table) return "null table (the fp32 [3][256] value table is required)";
+    if ((((uintptr_t)left8 | (uintptr_t)right8) & 3) != 0) return "left8 and right8 must be 4-byte aligned (rows are read as aligned dwords)";
+    if (((uintptr_t)table & 15) != 0) return "the table must be 16-byte aligned";
+    return nullptr;
+}
+extern "C" int egotap_rgb_u8_to_f32(const uint8_t* left8, const uint8_t* right8, int B, int S0, const float* table, float* left_f32, float* right_f32,
+                                    void* stream) {
+    static const char* const who = "egotap_rgb_u8_to_f32";
+    if (B == 0) return EGOTAP_OK;
+    EGO_CHECK(B > 0, "%s: negative batch (B = %d)", who, B);
+    EGO_CHECK(S0 > 0 && S0 % 4 == 0, "%s: the frame side must be a positive multiple of 4 (S0 = %d)", who, S0);
+    const char* why = rgb_u8_refusal(left8, right8, table);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(left_f32 && right_f32, "%s: null output", who);
+    EGO_CHECK((((uintptr_t)left_f32 | (uintptr_t)right_f32) & 15) == 0, "%s: left_f32 and right_f32 must be 16-byte aligned", who);
+    EGO_HIP(rgb_u8_to_f32_launch(left8, right8, table, left_f32, right_f32, B, S0, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_hm_forward_u8_workspace_bytes(egotap_handle h, int B, size_t* bytes) {
+    EGO_CHECK(h && bytes, "egotap_hm_forward_u8_workspace_bytes: null argument");
+    EGO_CHECK(B >= 0, "egotap_hm_forward_u8_workspace_bytes: negative batch");
+    const int b = B > 0 ? B : 1;
+    *bytes = hm_ws(h, b).total + hm_u8_slice_bytes(h, b);
+    return EGOTAP_OK;
+}
+extern "C" int egotap_hm_forward_u8(egotap_handle h, int net, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* out,
+                                    int64_t out_image_stride, void* ws, size_t ws_bytes, void* stream) {
+    static const char* const who = "egotap_hm_forward_u8";
+    EGO_CHECK(h, "%s: null handle", who);
+    EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "%s: net must be EGOTAP_NET_HM_POS or _ROT", who);
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    const char* why = rgb_u8_refusal(left8, right8, table);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(out && ws, "%s: null argument (out and ws are required)", who);
+    EGO_CHECK(((uintptr_t)out & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: out must be 16-byte aligned, ws 256-byte aligned", who);
+    if (hm_resolve(h, net) != EGOTAP_OK) {
+        const std::string key = g_err;
+        egotap_set_error("%s: unbound parameter of %s: %s", who, net == EGOTAP_NET_HM_POS ? "the position estimator" : "the limb estimator", key.c_str());
+        return EGOTAP_ERR_INVALID;
+    }
+    const size_t hm_bytes = hm_ws(h, B).total, need = hm_bytes + hm_u8_slice_bytes(h, B);
+    EGO_CHECK(ws_bytes >= need, "%s: workspace too small: %zu bytes given, %zu needed for B=%d", who, ws_bytes, need, B);
+    const HmSrc src{nullptr, nullptr, left8, right8, table, (float*)((char*)ws + hm_bytes)};
+    return hm_forward_impl(h, net, src, B, out, out_image_stride, ws, hm_bytes, stream, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ stereo RGB -> pose in one call
@@ -2073,15 +2167,10 @@ extern "C" int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, i
     return EGOTAP_OK;
 }
 
-extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
-                                       size_t ws_bytes, void* stream) {
-    static const char* const who = "egotap_predict_pose_rgb";
-    EGO_CHECK(h, "%s: null handle", who);
-    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    EGO_CHECK(left && right && pose && ws, "%s: null argument (left, right, pose and ws are required; only heatmaps may be NULL)", who);
-    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
-    EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0,
-              "%s: left, right, pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
+// the walk both one-call entries share: `src` holds the whole batch's frames (fp32, or bytes -- then the workspace ends with the converter slice of
+// one chunk where the stems do not read bytes themselves); the argument checks that depend on the source are the entries' own
+static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& src, int B, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
+                                 void* stream) {
     static const char* const net_name[EGOTAP_NET_COUNT] = {"the lifting head", "the position estimator", "the limb estimator"};
     for (int net = 0; net < EGOTAP_NET_COUNT; ++net) {
         if ((net == EGOTAP_NET_LIFT ? lift_resolve(h) : hm_resolve(h, net)) != EGOTAP_OK) {
@@ -2091,8 +2180,11 @@ extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const
         }
     }
     const RgbWs w = rgb_ws(h, B, chunk);
-    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small: %zu bytes given, %zu needed for B=%d, chunk=%d", who, ws_bytes, w.total, B, chunk);
     const int c = rgb_chunk(B, chunk), S = h->cfg.hm_size, HW = S * S, J = h->J;
+    const size_t need = w.total + (src.bytes() ? hm_u8_slice_bytes(h, c) : 0);
+    EGO_CHECK(ws_bytes >= need, "%s: workspace too small: %zu bytes given, %zu needed for B=%d, chunk=%d", who, ws_bytes, need, B, chunk);
+    HmSrc whole = src;
+    whole.scratch = src.bytes() ? (float*)((char*)ws + w.total) : nullptr;
     const long img = (long)h->C * HW, rgb = 3L * (4 * S) * (4 * S);
     const bool handoff = rgb_handoff(h, B, heatmaps);
     float* hm = heatmaps ? heatmaps : (float*)((char*)ws + w.HM);
@@ -2100,17 +2192,68 @@ extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const
     h->rgb_form = EGOTAP_RGB_FORM_NONE;
     // position net: channels [0, 2J) (left | right); limb net: [2J, 6J) (left cos, sin | right cos, sin)
     const int nets[2] = {EGOTAP_NET_HM_POS, EGOTAP_NET_HM_ROT}, c0[2] = {0, 2 * J};
+    if (src.bytes() && !hm_stem_reads_bytes(S)) {
+        // the converter route: a piece's frames are converted ONCE into the slice and both estimators read them there (pieces outer, estimators inner;
+        // the two share the U-Net scratch one after the other, as ever; never the hand-off: that exists at sides 64 / 128 only)
+        float* cl = whole.scratch;
+        for (int lo = 0; lo < B; lo += c) {
+            const int n = B - lo < c ? B - lo : c;
+            float* cr = cl + (size_t)n * rgb;
+            {
+                GemmTimer t(h, (hipStream_t)stream, "rgb_u8_to_f32", "rgb_u8_to_f32_kernel", 0.0);
+                EGO_HIP(rgb_u8_to_f32_launch(src.left8 + lo * rgb, src.right8 + lo * rgb, src.table, cl, cr, n, 4 * S, device_cu_count(), (hipStream_t)stream));
+            }
+            for (int k = 0; k < 2; ++k) {
+                const int rc = hm_forward_impl(h, nets[k], hm_src_f32(cl, cr), n, hm + lo * img + (long)c0[k] * HW, img, ws, w.HM, stream, nullptr);
+                if (rc != EGOTAP_OK) return rc;
+            }
+        }
+    } else
     for (int k = 0; k < 2; ++k)
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
             const long at = lo * img + (long)c0[k] * HW;
-            const int rc = hm_forward_impl(h, nets[k], left + lo * rgb, right + lo * rgb, n, handoff ? nullptr : hm + at, img, ws, w.HM, stream, handoff ? hmb + at : nullptr);
+            const int rc = hm_forward_impl(h, nets[k], whole.at(lo, rgb), n, handoff ? nullptr : hm + at, img, ws, w.HM, stream, handoff ? hmb + at : nullptr);
             if (rc != EGOTAP_OK) return rc;
         }
     const int rc = lift_forward_impl(h, handoff ? nullptr : hm, B, pose, ws, w.HM, stream, true, who, hmb);
     if (rc != EGOTAP_OK) return rc;
     h->rgb_form = handoff ? EGOTAP_RGB_FORM_HANDOFF : heatmaps ? EGOTAP_RGB_FORM_HEATMAPS : EGOTAP_RGB_FORM_SCRATCH;
     return EGOTAP_OK;
+}
+
+extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                                       size_t ws_bytes, void* stream) {
+    static const char* const who = "egotap_predict_pose_rgb";
+    EGO_CHECK(h, "%s: null handle", who);
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(left && right && pose && ws, "%s: null argument (left, right, pose and ws are required; only heatmaps may be NULL)", who);
+    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
+    EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0,
+              "%s: left, right, pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
+    return predict_pose_rgb_impl(who, h, hm_src_f32(left, right), B, pose, heatmaps, chunk, ws, ws_bytes, stream);
+}
+
+// [r7] the same call from camera bytes: uint8 [B, S0, S0, 3] per eye and the fp32 [3][256] value table
+extern "C" int egotap_predict_pose_rgb_u8_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
+    EGO_CHECK(h && bytes, "egotap_predict_pose_rgb_u8_workspace_bytes: null argument");
+    EGO_CHECK(B >= 0 && chunk >= 0, "egotap_predict_pose_rgb_u8_workspace_bytes: negative batch or chunk");
+    const int b = B > 0 ? B : 1;
+    *bytes = rgb_ws(h, b, chunk).total + hm_u8_slice_bytes(h, rgb_chunk(b, chunk));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_predict_pose_rgb_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
+                                          int chunk, void* ws, size_t ws_bytes, void* stream) {
+    static const char* const who = "egotap_predict_pose_rgb_u8";
+    EGO_CHECK(h, "%s: null handle", who);
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    const char* why = rgb_u8_refusal(left8, right8, table);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(pose && ws, "%s: null argument (pose and ws are required; only heatmaps may be NULL)", who);
+    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
+    EGO_CHECK((((uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
+    const HmSrc src{nullptr, nullptr, left8, right8, table, nullptr};
+    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream);
 }
 
 extern "C" int egotap_debug_predict_pose_rgb_form(egotap_handle h, int* form) {

@@ -40,6 +40,14 @@ _PROTOS = {
     # ---- stereo RGB -> pose in one call
     "egotap_predict_pose_rgb_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "egotap_predict_pose_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- camera bytes: uint8 [B, S0, S0, 3] frames + the fp32 [3][256] value table
+    "egotap_rgb_u8_to_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_hm_forward_u8_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
+    "egotap_hm_forward_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "egotap_predict_pose_rgb_u8_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "egotap_predict_pose_rgb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -268,6 +276,39 @@ def pose_metrics(pred, gt, want_aligned: bool = False, reference_batch_axes: boo
     fn = load().egotap_pose_metrics_batch_axes if reference_batch_axes and B in (2, 3) else load().egotap_pose_metrics
     check(fn(_ptr(pred), _ptr(gt), B, J, _ptr(e), _ptr(pa), _ptr(al), _stream()))
     return (e, pa, al) if want_aligned else (e, pa)
+
+
+def check_camera_frames(who, left8, right8, S0):
+    """the one wording of what the byte entries take: two uint8 [B, S0, S0, 3] contiguous tensors on one GPU; returns B"""
+    import torch
+    for t in (left8, right8):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the frames to cuda")
+    for t in (left8, right8):
+        if t.dtype != torch.uint8:
+            raise EgotapError(f"{who} takes the camera's bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
+    B = left8.shape[0] if left8.dim() else 0
+    if tuple(left8.shape) != (B, S0, S0, 3) or tuple(right8.shape) != (B, S0, S0, 3):
+        raise ValueError(f"{who}: expected left8 / right8 [B, {S0}, {S0}, 3] (HWC, RGB), got {tuple(left8.shape)} / {tuple(right8.shape)}")
+    if not (left8.is_contiguous() and right8.is_contiguous()) or left8.device != right8.device:
+        raise EgotapError(f"{who}: the frames must be contiguous and on one device (the bytes are read in place, nothing is copied)")
+    return B
+
+
+def rgb_u8_to_f32(left8, right8, table):
+    """camera bytes uint8 [B, S0, S0, 3] x 2 -> the planar normalised frames fp32 [B, 3, S0, S0] x 2 (egotap_rgb_u8_to_f32): out[b, c, y, x] =
+    table[c, in[b, y, x, c]]; `table` fp32 [3, 256] on the same device (spec.rgb_u8_table)"""
+    import torch
+    S0 = left8.shape[1] if left8.dim() == 4 else -1
+    B = check_camera_frames("rgb_u8_to_f32", left8, right8, S0)
+    _need_cuda_f32(table)
+    if tuple(table.shape) != (3, 256) or table.device != left8.device:
+        raise ValueError("rgb_u8_to_f32: the table is fp32 [3, 256] on the frames' device")
+    left = torch.empty((B, 3, S0, S0), dtype=torch.float32, device=left8.device)
+    right = torch.empty_like(left)
+    with torch.cuda.device(left8.device):
+        check(load().egotap_rgb_u8_to_f32(_ptr(left8), _ptr(right8), B, S0, _ptr(table), _ptr(left), _ptr(right), _stream(left8.device)))
+    return left, right
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

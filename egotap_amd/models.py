@@ -487,6 +487,80 @@ class EgoTAPAutoEncoderModel(nn.Module):
             graph.replay()
         return (pose, hm) if return_heatmaps else pose
 
+    def camera_table(self, dev):
+        """the fp32 [3, 256] value table of predict_pose_from_camera on `dev` (spec.rgb_u8_table; opt.rgb_mean / opt.rgb_std override the ImageNet
+        statistics): one small tensor the model owns, handed to every byte entry -- the library allocates nothing.  Cached per (device, mean, std):
+        changing opt.rgb_mean / opt.rgb_std between calls builds a new table (and, its address being part of the capture key, a new graph)."""
+        key = (dev, tuple(getattr(self.opt, "rgb_mean", None) or ()), tuple(getattr(self.opt, "rgb_std", None) or ()))
+        hit = self.__dict__.get("_camera_table")
+        if hit is None or hit[0] != key:
+            hit = self._camera_table = (key, torch.from_numpy(_spec.rgb_u8_table(self.opt)).to(dev))
+        return hit[1]
+
+    def _serve_one_call(self, left, right, B, dev, return_heatmaps, graphed, size_query, launch, kind=(), keep=()):
+        """The host side of a one-call serving entry on the serving handle: outputs, workspace (eager: the handle's grow-only one; graphed: the
+        graph's own), capture and replay with static inputs of the frames' dtype.  ``size_query(h, B, chunk, &bytes)`` and
+        ``launch(h, left, right, pose, heatmaps, chunk, ws)`` are the entry's two ABI calls; ``kind`` extends the capture key, ``keep`` what a graph
+        must keep alive besides its own buffers."""
+        p = self.net_AutoEncoder.preset
+        chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
+        pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
+        hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
+        if B == 0:
+            return (pose, hm) if return_heatmaps else pose
+        with torch.cuda.device(dev):
+            st = self._rgb_state(dev)
+            self._rgb_attach_act_scratch(st, B, dev)
+            h = st.handle.h
+            need = _session.nbytes(size_query, h, B, chunk)
+            if not graphed:
+                _session.grown(st, "ws", need, dev, drop_first=True)
+                st.chunk = chunk
+                launch(h, left, right, pose, hm, chunk, st.ws)
+                return (pose, hm) if return_heatmaps else pose
+            nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
+            key = (B, bool(return_heatmaps), st.precision, tuple(st.frozen), tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)),
+                   chunk, str(dev)) + tuple(kind)
+
+            def build():
+                s_l, s_r = left.clone(), right.clone()
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                held = (ws, st.wscratch, st.ascratch) + tuple(keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
+                return (lambda: launch(h, s_l, s_r, pose, hm, chunk, ws)), (s_l, s_r, pose, hm), held
+            graph, (s_l, s_r, pose, hm), _ = _session.captured(st.graphs, key, build)
+            s_l.copy_(left)
+            s_r.copy_(right)
+            graph.replay()
+        return (pose, hm) if return_heatmaps else pose
+
+    @torch.no_grad()
+    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False):
+        """predict_pose_from_rgb from what a camera delivers: stereo frames uint8 [B, 4S, 4S, 3] (HWC, RGB order, already at 4S x 4S) -> pose
+        [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_rgb_u8) on the serving handle of
+        predict_pose_from_rgb: the caller's astype(float32) / 255, normalisation, HWC -> CHW and the four-fold upload are gone -- at sides 64 / 128
+        the stem kernels look every byte up in a 768-entry table (``camera_table``) while they stage it; at other sides the library converts chunk
+        by chunk into a workspace slice.  The bits are those of predict_pose_from_rgb on the gathered frames table[c][byte].
+
+        ``graphed``: as predict_pose_from_rgb, with static BYTE inputs; the capture key also holds the source kind and the table, so the two entries
+        never share a graph.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions) run
+        egotap_rgb_u8_to_f32 followed by predict_pose_from_rgb's module route -- by name, ungraphed."""
+        S0 = 4 * self.net_AutoEncoder.preset.hm_size
+        B = _lib.check_camera_frames("predict_pose_from_camera", left8, right8, S0)
+        dev = left8.device
+        table = self.camera_table(dev)
+        why = self._rgb_one_call_refusal()
+        if why is not None:
+            if graphed:
+                raise _lib.EgotapError(f"predict_pose_from_camera(graphed=True): {why}; this configuration runs the converter and the module forwards, ungraphed")
+            left, right = _lib.rgb_u8_to_f32(left8, right8, table)
+            return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps)
+        lib = _lib.load()
+
+        def launch(h, l, r, po, hmo, chunk, ws):
+            _lib.check(lib.egotap_predict_pose_rgb_u8(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
+        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
+                                    kind=("u8", table.data_ptr()), keep=(table,))
+
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity
         tests; egotap_debug.h): "heatmaps" -> fp32 [B, 6J, S, S] after a "scratch" call, "handoff" -> bfloat16 [B, 6J, S, S] after a "handoff" call"""

@@ -9,6 +9,7 @@ the HIP library or off the GPU these modules raise.
 from __future__ import annotations
 
 import ctypes as C
+import types
 
 import torch
 import torch.nn as nn
@@ -414,6 +415,7 @@ class HeatMap_UnrealEgo_Shared(_AbiModule, nn.Module):
         hm = list(getattr(opt, "load_size_heatmap", [64, 64]))
         self.hm_size = hm[0]
         self.preset = _spec.lift_preset(opt.joint_preset, hm[0], getattr(opt, "ae_hidden_size", 128))
+        self._rgb_opt = types.SimpleNamespace(rgb_mean=getattr(opt, "rgb_mean", None), rgb_std=getattr(opt, "rgb_std", None))
         J = self.preset.n_joints_hm
         if self.num_heatmap == J:
             self._net = _lib.NET_HM_POS
@@ -561,6 +563,44 @@ class HeatMap_UnrealEgo_Shared(_AbiModule, nn.Module):
             self._ws = ws
             _lib.check(_lib.load().egotap_hm_forward(self._ensure_handle(), self._net, ptr(left), ptr(right), B, *self._out_slice(out, channel_offset),
                                                      ptr(ws), ws.numel(), stream(dev)))
+        return out
+
+    def camera_table(self, device):
+        """the fp32 [3, 256] value table of the byte entries on `device` (spec.rgb_u8_table with this net's opt.rgb_mean / opt.rgb_std): one
+        small tensor the module owns -- the library allocates nothing.  The statistics are read ONCE, when the module is constructed (a module keeps no
+        opt); a model that changes them builds a new estimator, or goes through EgoTAPAutoEncoderModel.camera_table, which follows its opt"""
+        t = self.__dict__.get("_camera_table")
+        if t is None or t.device != device:
+            t = self._camera_table = torch.from_numpy(_spec.rgb_u8_table(self._rgb_opt)).to(device)
+        return t
+
+    @torch.no_grad()
+    def forward_from_camera(self, left8, right8):
+        """The eval forward from camera bytes (egotap.h egotap_hm_forward_u8): left8 / right8 uint8 [B, 4S, 4S, 3] (HWC, RGB) -> [B, 2*n_hm, S, S],
+        bit for bit the eval forward on the normalised frames table[c][byte].  At sides 64 / 128 the stem kernels stage the bytes themselves; at
+        every other side the library converts them into a workspace slice first.  Eval mode only (the train-mode forwards keep their fp32 source).
+        resnet50 / resnet101 (composed on the host): egotap_rgb_u8_to_f32, then the module forward -- by name."""
+        if self.training:
+            raise NotImplementedError("forward_from_camera is the eval-mode forward (folded BatchNorm); .eval() first -- training reads normalised fp32 frames")
+        S0 = 4 * self.hm_size
+        B = _lib.check_camera_frames("forward_from_camera", left8, right8, S0)
+        dev = left8.device
+        out = torch.empty((B, 2 * self.num_heatmap, self.hm_size, self.hm_size), dtype=torch.float32, device=dev)
+        if B == 0:
+            return out
+        table = self.camera_table(dev)
+        if self.bottleneck:
+            left, right = _lib.rgb_u8_to_f32(left8, right8, table)
+            return self.forward_into(left, right, out)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            self._bind(dev)
+            if self._frozen_sig is not None:
+                self._frozen_check(dev)
+            need = _session.nbytes(lib.egotap_hm_forward_u8_workspace_bytes, self._ensure_handle(), B)
+            ws = self._ws = _session.grown(self, "_ws", need, dev, drop_first=True)
+            _lib.check(lib.egotap_hm_forward_u8(self._ensure_handle(), self._net, ptr(left8), ptr(right8), B, ptr(table), *self._out_slice(out, 0),
+                                                ptr(ws), ws.numel(), stream(dev)))
         return out
 
     @torch.no_grad()

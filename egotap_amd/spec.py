@@ -248,3 +248,25 @@ def hm_state_spec(n_hm_per_eye: int, model_name: str = "resnet18"):
     out += conv("conv_up1.0", 256 * f, 64 * f + 256 * f, 3)
     out += conv("conv_heatmap", 2 * n_hm_per_eye, 256 * f, 1)
     return out
+
+
+# ---- camera bytes -> network input (egotap.h: egotap_rgb_u8_to_f32 / egotap_hm_forward_u8 / egotap_predict_pose_rgb_u8) -----------------
+RGB_MEAN = (0.485, 0.456, 0.406)          # utils/util.py:188-197 normalize_ImageNet
+RGB_STD = (0.229, 0.224, 0.225)
+
+
+def rgb_u8_table(opt=None):
+    """fp32 numpy [3, 256]: the network input value of byte v in channel c, with the reference's arithmetic evaluated once per (channel, byte)
+
+        float32( (float64(float32(v) / float32(255)) - mean[c]) / std[c] )
+
+    -- astype(float32) / 255 (utils/util.py:438), normalize_ImageNet's float64 numpy branch, the loader's .float() last.  ``opt.rgb_mean`` /
+    ``opt.rgb_std`` (three floats each) override the ImageNet statistics.  Pinned bit for bit by tests/golden/rgb_u8_norm.npz."""
+    import numpy as np
+    mean = tuple(getattr(opt, "rgb_mean", None) or RGB_MEAN)
+    std = tuple(getattr(opt, "rgb_std", None) or RGB_STD)
+    if len(mean) != 3 or len(std) != 3 or any(float(s) == 0.0 for s in std):
+        raise ValueError(f"rgb_mean / rgb_std: three values each and no zero std, got {mean} / {std}")
+    x = (np.arange(256, dtype=np.uint8).astype(np.float32) / np.float32(255.0)).astype(np.float64).reshape(1, 256)
+    t = (x - np.array(mean, dtype=np.float64).reshape(3, 1)) / np.array(std, dtype=np.float64).reshape(3, 1)
+    return np.ascontiguousarray(t.astype(np.float32))

@@ -148,6 +148,36 @@ int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, int chunk, s
 int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- camera bytes: uint8 stereo frames straight into the stems (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * What a camera, decoder or capture card delivers is uint8 HWC; the reference turns it into the estimators' input offline (reprocess_*_data.py ->
+ * utils/util.py:437-440, :188-197 normalize_ImageNet): astype(float32) / 255, subtract the mean, divide by the std, HWC -> CHW.  The normalised value
+ * of a pixel is a function of one byte and one channel, so these entries take the bytes and a 768-entry table instead:
+ *   left8, right8  device uint8 [B, S0, S0, 3], RGB order, S0 = 4*hm_size, contiguous; the base pointer 4-byte aligned (a row is 3*S0 bytes, a
+ *                  multiple of 4: rows are read as aligned dwords, and no load touches a byte outside B*S0*S0*3)
+ *   table          device f32 [3][256], 16-byte aligned, caller-owned: table[c][v] = float32((float64(float32(v) / float32(255)) - mean[c]) / std[c])
+ *                  (egotap_amd/spec.py rgb_u8_table builds it; pinned against the reference by tests/golden/rgb_u8_norm.npz)
+ * Every result equals, bit for bit, that of the fp32 entry on the host gather T(x8)[b][c][y][x] = table[c][x8[b][y][x][c]]: the byte paths read the
+ * same values and keep every summation order.  Pixels outside the image are 0.0 as ever (not table[c][0]).  Every refusal is EGOTAP_ERR_INVALID,
+ * by name and before any launch: null frames / table / outputs, a misaligned pointer, a workspace that is too small, unbound parameters.
+ *
+ * egotap_rgb_u8_to_f32: the standalone converter to the planar fp32 layout the other entries read (left_f32, right_f32: device f32
+ *   [B, 3, S0, S0], 16-byte aligned; S0 any positive multiple of 4); one launch, 3 bytes in and 12 out per pixel.  B = 0 is a no-op.
+ * egotap_hm_forward_u8: egotap_hm_forward from bytes.  Heatmap sides 64 / 128: the stem kernels stage the bytes themselves (the bf16 channels-last
+ *   stem in EGOTAP_PREC_BF16, the fp32 matrix-core stem otherwise) and everything behind the stem is the launches of egotap_hm_forward; the workspace
+ *   is egotap_hm_workspace_bytes(B).  Every other side: the converter runs into a slice at the end of the workspace, which is larger by exactly
+ *   B*2*3*S0*S0*4 bytes, and the forward proceeds as egotap_hm_forward.
+ * egotap_predict_pose_rgb_u8: egotap_predict_pose_rgb with the byte source -- the same composition, chunk walk, hand-off, frozen arenas and refusals.
+ *   Workspace: egotap_predict_pose_rgb_workspace_bytes(B, chunk) at sides 64 / 128, larger by exactly chunk*2*3*S0*S0*4 bytes elsewhere (the
+ *   converter runs chunk by chunk). */
+int egotap_rgb_u8_to_f32(const uint8_t* left8, const uint8_t* right8, int B, int S0, const float* table, float* left_f32, float* right_f32,
+                         void* stream);
+int egotap_hm_forward_u8_workspace_bytes(egotap_handle h, int B, size_t* bytes);
+int egotap_hm_forward_u8(egotap_handle h, int net, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* out,
+                         int64_t out_image_stride, void* ws, size_t ws_bytes, void* stream);
+int egotap_predict_pose_rgb_u8_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes);
+int egotap_predict_pose_rgb_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
+                               int chunk, void* ws, size_t ws_bytes, void* stream);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

@@ -877,9 +877,23 @@ def gen_synth():
     print("heatmap_synth ok", len(out), "arrays")
 
 
+def gen_rgb_u8():
+    """the loader's uint8 -> network input arithmetic per (channel, byte): astype(float32) / 255 (utils/util.py:438), then the reference's
+    own normalize_ImageNet (utils/util.py:188-197; its numpy branch is float64) and the loader's .float() last.  normalize_input_img itself
+    cannot run (it passes the builtin `input`, :439), so normalize_ImageNet is the pin.  768 numbers."""
+    import utils.util as UU
+    x = np.arange(256, dtype=np.uint8).astype(np.float32) / 255.0
+    x = np.ascontiguousarray(np.broadcast_to(x.reshape(1, 256, 1), (3, 256, 1)))
+    y = UU.normalize_ImageNet(x)
+    assert y.dtype == np.float64 and y.shape == (3, 256, 1)
+    table = torch.from_numpy(y).float().numpy().reshape(3, 256)
+    np.savez_compressed(os.path.join(GOLD, "rgb_u8_norm.npz"), table=table)
+    print("rgb_u8_norm ok", table.shape, table.dtype, float(table.min()), float(table.max()))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,train_dhm,sched,synth,hmtrain,wrapper,wrapper_rgb")
+    ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,train_dhm,sched,synth,hmtrain,wrapper,wrapper_rgb,rgb_u8")
     args = ap.parse_args()
     which = set(args.only.split(","))
     os.makedirs(GOLD, exist_ok=True)
@@ -914,6 +928,8 @@ def main():
         gen_wrapper()
     if "wrapper_rgb" in which:
         gen_wrapper_rgb()
+    if "rgb_u8" in which:
+        gen_rgb_u8()
     if "wrapper_spread" in which:      # (not in the default set: six reference wrapper runs, ~10 min)
         gen_wrapper_spread()
 
