@@ -38,7 +38,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         return LIB
     hipcc = _hipcc()
-    # experiment builds (EGOTAP_LIB=<other .so>, EGOTAP_CXXFLAGS="-DEGOTAP_ABL=1 ..."): objects next to their library, extra flags
+    # experiment builds (EGOTAP_LIB=<other .so>, EGOTAP_CXXFLAGS="-Rpass-analysis=kernel-resource-usage ..."): objects next to their library, extra flags
     objdir = os.path.join(PKG, "build") if "EGOTAP_LIB" not in os.environ else LIB + ".build"
     os.makedirs(objdir, exist_ok=True)
     common = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"), "-I" + CSRC]

@@ -220,12 +220,7 @@ static hipError_t attention_bf16s_bwd_launch(const __bf16* QKV, const __bf16* O,
         constexpr size_t patch = (size_t)NW * 32 * OLD * 4, img_q = (size_t)SUB * (2 * RIMG + TIMG) * 2;
         constexpr size_t lds_q = img_q > patch ? img_q : patch;
         static_assert(2 * lds_q <= 160 * 1024, "two workgroups per CU");
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dq_bf16s_kernel<NW, SUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-            if (e != hipSuccess) return e;
-            attr_done = true;
-        }
+        if (hipError_t e = ego_allow_dynamic_lds((const void*)attn_bwd_dq_bf16s_kernel<NW, SUB>, (int)lds_q); e != hipSuccess) return e;
         hipLaunchKernelGGL((attn_bwd_dq_bf16s_kernel<NW, SUB>), dim3(B * heads * groups), dim3(64 * NW), lds_q, stream, QKV, O, dO, LSE, dQKV, DELTA, N, heads, groups,
                            1.0f / sqrtf((float)DH));
         hipError_t e = hipGetLastError();

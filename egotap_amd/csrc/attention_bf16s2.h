@@ -32,14 +32,10 @@ __device__ __forceinline__ void dma16(const void* g, unsigned lds_addr) {
 }
 // [r5] the same DMA with the address as a wave-uniform 64-bit base (scalar registers) + a 32-bit byte offset per lane: every tile of these kernels is
 // "uniform tile origin + a lane pattern fixed for the whole kernel", so the per-lane 64-bit add (and the 64-bit address operand) of the flat form is dropped.
-// -DEGOTAP_ATT_DMA_FLAT keeps the per-lane pointer form (A/B: profiles/r05_attention_ab.log).
+// The A/B against the per-lane pointer form is recorded in profiles/r05_attention_ab.log.
 __device__ __forceinline__ unsigned long long uniform64(const void* p) { return lds_dma_base(p); }      // lds_dma.h
 __device__ __forceinline__ void dma16s(unsigned voff, unsigned long long sbase, unsigned lds_addr) {
-#ifdef EGOTAP_ATT_DMA_FLAT
-    dma16((const char*)(size_t)sbase + voff, lds_addr);
-#else
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-#endif
 }
 __device__ __forceinline__ void dma4(const void* g, unsigned lds_addr) {
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
@@ -225,12 +221,7 @@ static hipError_t attention_bf16s2_dkv_launch(const __bf16* QKV, const __bf16* d
     constexpr size_t lds = img > patch ? img : patch;
     static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
     auto kern = attn_bwd_dkv_bf16s2_kernel<NW>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, (int)lds); e != hipSuccess) return e;
     const int groups = (N / 32 + NW - 1) / NW;
     hipLaunchKernelGGL(kern, dim3(B * heads * groups), dim3(64 * NW), lds, stream, QKV, dO, LSE, DELTA, dQKV, N, heads, groups, 1.0f / sqrtf((float)DH),
                        colpart);
@@ -562,12 +553,7 @@ static hipError_t attention_bf16s3_fwd_launch_t(const __bf16* QKV, __bf16* CTX, 
     constexpr size_t lds = img > patch ? img : patch;
     static_assert(NW == 2 || (12 / NW) * lds <= 160 * 1024, "twelve waves (three per SIMD) per CU (two-wave workgroups: five per CU, ten waves)");
     auto kern = attention_bf16s3_kernel<NW>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, (int)lds); e != hipSuccess) return e;
     const int groups = (N / 32 + NW - 1) / NW;
     hipLaunchKernelGGL(kern, dim3(B * heads * groups), dim3(64 * NW), lds, stream, QKV, CTX, N, heads, groups, 1.4426950408889634f / sqrtf(128.0f), LSE);
     return hipGetLastError();
@@ -586,12 +572,7 @@ static hipError_t attention_bf16s2_dq_launch(const __bf16* QKV, const __bf16* O,
     constexpr size_t lds = img > patch ? img : patch;
     static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
     auto kern = attn_bwd_dq_bf16s2_kernel<NW>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, (int)lds); e != hipSuccess) return e;
     const int groups = (N / 32 + NW - 1) / NW;
     hipLaunchKernelGGL(kern, dim3(B * heads * groups), dim3(64 * NW), lds, stream, QKV, O, dO, LSE, dQKV, DELTA, N, heads, groups, 1.0f / sqrtf((float)DH),
                        colpart);

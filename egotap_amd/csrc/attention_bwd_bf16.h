@@ -334,14 +334,9 @@ static hipError_t attention_bwd_bf16_launch(const float* QKV, const float* O, co
     constexpr size_t img_k = (size_t)(2 * rimg_pair<NP>() + timg_pair<NP>()) * 2 + 256 + (size_t)NW * rimg_pair<NP>() * 2;
     constexpr size_t lds_k = img_k > patch ? img_k : patch;
     static_assert(lds_k <= 160 * 1024, "LDS budget");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dq_bf16_kernel<NW, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dv_bf16_kernel<NW, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_v);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dk_bf16_kernel<NW, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)attn_bwd_dq_bf16_kernel<NW, NP>, (int)lds_q); e != hipSuccess) return e;
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)attn_bwd_dv_bf16_kernel<NW, NP>, (int)lds_v); e != hipSuccess) return e;
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)attn_bwd_dk_bf16_kernel<NW, NP>, (int)lds_k); e != hipSuccess) return e;
     hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<NW, NP>), dim3(B * heads * groups), dim3(64 * NW), lds_q, stream, QKV, O, dO, LSE, dQKV,
                        DELTA, N, heads, groups, scale);
     hipLaunchKernelGGL((attn_bwd_dv_bf16_kernel<NW, NP>), dim3(B * heads * groups), dim3(64 * NW), lds_v, stream, QKV, dO, LSE, dQKV, N,

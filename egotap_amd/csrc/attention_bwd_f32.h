@@ -262,13 +262,8 @@ static hipError_t attention_bwd_f32_launch(const float* QKV, const float* O, con
     const int qgroups = (N / 32 + NWQ - 1) / NWQ, kgroups = (N / 32 + NWK - 1) / NWK;
     const size_t lds_q = (size_t)(2 * KT * LD > NWQ * 32 * LD ? 2 * KT * LD : NWQ * 32 * LD) * 4;
     const size_t lds_k = (size_t)(2 * KT * LD + 64 + NWK * KT * LD) * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<NWQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<NWK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)attn_bwd_dq_kernel<NWQ>, (int)lds_q); e != hipSuccess) return e;
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)attn_bwd_dkv_kernel<NWK>, (int)lds_k); e != hipSuccess) return e;
     hipLaunchKernelGGL(attn_bwd_dq_kernel<NWQ>, dim3(B * heads * qgroups), dim3(64 * NWQ), lds_q, stream, QKV, O, dO, LSE, dQKV, DELTA,
                        N, heads, qgroups, scale);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel<NWK>, dim3(B * heads * kgroups), dim3(64 * NWK), lds_k, stream, QKV, dO, LSE, DELTA, dQKV, N,

@@ -13,10 +13,6 @@
 #pragma once
 #include "common.h"
 #include <math.h>
-#ifdef EGOTAP_ATTN_F32_OLD      // A/B builds (EGOTAP_CXXFLAGS=-DEGOTAP_ATTN_F32_OLD): round 2's kernel, both operands staged in 64 registers
-#include "../../tools/experiments/attention_f32_r2.h"
-#else
-#define EGOTAP_ATTN_F32_LIVE 1      // attention_f32_live_launch below (the pose-only forward's pruned last layer)
 
 template <int NW>
 struct AttnCfg {
@@ -308,4 +304,3 @@ static hipError_t attention_f32_live_launch(const float* Q, long ldq, int Nq, co
                        qgroups, scale_log2e, (float*)nullptr, 1, Q, ldq, Nq);
     return hipGetLastError();
 }
-#endif

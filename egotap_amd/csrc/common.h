@@ -14,7 +14,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // thread-local error text returned by egotap_last_error()
 void egotap_set_error(const char* fmt, ...);
 
-#define EGO_CHECK(cond, ...)                  \
+// Before a launch with more than the default dynamic LDS: raises the kernel's limit to `bytes` on the current device.  One
+// attribute call per (kernel, device), again only for a larger size; afterwards hipGetDevice and a lookup (lds_opt_in.h).  Thread-safe.
+hipError_t ego_allow_dynamic_lds(const void* kernel, int bytes);
+
+#define EGO_CHECK(cond, ...)               \
     do {                                      \
         if (!(cond)) {                        \
             egotap_set_error(__VA_ARGS__);    \

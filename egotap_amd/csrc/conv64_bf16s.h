@@ -206,12 +206,7 @@ static inline hipError_t conv64_direct_bf16s_launch(const __bf16* in, const __bf
     using Cfg = Conv64Cfg;
     const int S = 1 << log2S;
     if (S % Cfg::TC != 0 || S % Cfg::TR != 0 || nimg <= 0) return hipErrorInvalidValue;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv64_direct_bf16s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)conv64_direct_bf16s_kernel, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const long ntiles = (long)nimg * (S / Cfg::TR) * (S / Cfg::TC);
     const long grid = ntiles < num_cu ? ntiles : num_cu;
     hipLaunchKernelGGL(conv64_direct_bf16s_kernel, dim3((unsigned)grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, in, zero, wp, scale, shift, res, out, log2S,

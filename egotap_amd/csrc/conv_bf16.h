@@ -252,12 +252,8 @@ static hipError_t conv_bf16_launch(ConvArgs a, __bf16* wp, hipStream_t stream) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     auto kern = conv_bf16_kernel<Cfg>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES);
+    if (e != hipSuccess) return e;
     a.tiles_co = (a.Cout + Cfg::CO_T - 1) / Cfg::CO_T;      // a ragged last tile re-reads the last channel's weights and skips its stores
     a.tiles_px = Cfg::G == 1 ? (int)((long)a.Nimg * Cfg::W * Cfg::W / Cfg::PX_T) : (a.Nimg + Cfg::G - 1) / Cfg::G;
     hipLaunchKernelGGL(kern, dim3(a.tiles_co * a.tiles_px), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, a, (const __bf16*)wp, S);

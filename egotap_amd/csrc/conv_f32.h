@@ -382,12 +382,7 @@ static hipError_t conv_f32_launch(ConvArgs a, hipStream_t stream, int num_cu = 2
     if (a.Nimg <= 0) return hipSuccess;
     if ((a.Cin * Cfg::TAPS) % 4 != 0) return hipErrorInvalidValue;
     auto kern = conv_f32_kernel<Cfg>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     a.tiles_co = (a.Cout + Cfg::CO_T - 1) / Cfg::CO_T;
     a.vec_ok = (((size_t)a.gamma | (size_t)a.beta | (size_t)a.mean | (size_t)a.var | (size_t)a.bias) & 15) == 0;
     const long px = (long)a.Nimg * Cfg::W * Cfg::W;
@@ -612,12 +607,7 @@ static hipError_t conv_f32_any_launch(ConvArgs a, int W, hipStream_t stream) {
     if (a.Nimg <= 0) return hipSuccess;
     if (W < 1 || a.Cin <= 0 || a.Cout <= 0 || (a.Cin * Cfg::TAPS) % 4 != 0 || ((uintptr_t)a.w & 15) != 0) return hipErrorInvalidValue;
     auto kern = conv_f32_any_kernel<Cfg>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const long px = (long)a.Nimg * W * W;
     const long tiles_px = (px + Cfg::PX_T - 1) / Cfg::PX_T;
     a.tiles_co = (a.Cout + Cfg::CO_T - 1) / Cfg::CO_T;
@@ -729,12 +719,7 @@ static inline hipError_t stem_conv7_u8_launch(const unsigned char* left, const u
     static_assert(LDS <= 160 * 1024, "the value table fits behind the weights (one workgroup per CU, as the fp32 source: 104 KB + 3 KB of LDS)");
     const int HO = HIN / 2;
     if (!stem_conv7_on_mfma(HIN) || ((uintptr_t)out & 15) != 0 || nimg <= 0) return hipErrorInvalidValue;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)stem_conv7_mfma_u8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)stem_conv7_mfma_u8_kernel, LDS); e != hipSuccess) return e;
     const long items = (long)nimg * (HO / Cfg::RG) * (HO / Cfg::XT);
     const int grid = (int)(items < num_cu ? items : num_cu);
     hipLaunchKernelGGL(stem_conv7_mfma_u8_kernel, dim3(grid), dim3(Cfg::THREADS), LDS, s, left, right, table, w, gamma, beta, mean, var, out, HIN, nimg);
@@ -745,12 +730,7 @@ static inline hipError_t stem_conv7_launch(const float* left, const float* right
     using Cfg = StemCfg;
     const int HO = HIN / 2;
     if (HO % Cfg::XT == 0 && HO % Cfg::RG == 0 && ((uintptr_t)out & 15) == 0) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute((const void*)stem_conv7_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            attr_done = true;
-        }
+        if (hipError_t e = ego_allow_dynamic_lds((const void*)stem_conv7_mfma_kernel<false>, Cfg::LDS_BYTES); e != hipSuccess) return e;
         const long items = (long)nimg * (HO / Cfg::RG) * (HO / Cfg::XT);
         const int grid = (int)(items < num_cu ? items : num_cu);
         hipLaunchKernelGGL(stem_conv7_mfma_kernel<false>, dim3(grid), dim3(Cfg::THREADS), Cfg::LDS_BYTES, s, left, right, w, gamma, beta, mean, var, out, HIN, nimg);

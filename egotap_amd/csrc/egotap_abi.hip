@@ -11,6 +11,7 @@
 
 #include "attention_f32.h"
 #include "common.h"
+#include "lds_opt_in.h"
 #include "conv_f32.h"
 #include "conv_bf16.h"
 #include "gemm_f32.h"
@@ -52,6 +53,12 @@ void egotap_set_error(const char* fmt, ...) {
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
+}
+hipError_t ego_allow_dynamic_lds(const void* kernel, int bytes) {
+    static LdsOptIn seen;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    return seen.ensure(kernel, dev, bytes, [kernel](int b) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, b); });
 }
 #endif
 #if EGOTAP_IN(0)
@@ -952,7 +959,6 @@ static hipError_t gemm_rounds(Handle* h, const char* role, const AL& al, const S
 // k order, so the pose keeps its bits -- provided nothing SPLITS: exact fp32 only, every last-layer product of the full problem on the
 // 256 x 256 kernel (GS_BIG: the large batches) and its attention unsplit.  Anything else takes the full path.
 static bool lift_prune_last(Handle* h, int B) {
-#ifdef EGOTAP_ATTN_F32_LIVE
     const int D = h->D, M = B * h->seq, Nq = h->T * h->ppd * h->ppd;
     if (h->precision != EGOTAP_PREC_F32 || h->debug_stop != 0 || h->cfg.vit_layers < 1 || Nq < 32 || Nq >= h->seq || D % 256 != 0) return false;
     const int cus = device_cu_count();
@@ -960,10 +966,6 @@ static bool lift_prune_last(Handle* h, int B) {
         gemm_small_route(h, true, M, 4 * D, D, 4 * D, cus, true).kind != GS_BIG || gemm_small_route(h, true, M, D, 4 * D, D, cus).kind != GS_BIG)
         return false;
     return attention_f32_ksplit(B, h->seq, h->cfg.vit_heads, SPLITK_FLOATS, cus) == 1;
-#else
-    (void)h; (void)B;
-    return false;
-#endif
 }
 
 // ---- frozen-weight serving: the arena of egotap_lift_freeze.  Every bf16 weight copy the bf16-storage inference forward multiplies by, in the layout
@@ -1023,13 +1025,11 @@ static LiftFrozen lift_frozen_plan(const Handle* h, const LiftParams* p, PrepTab
 
 // EGOTAP_PREC_BF16 at a batch that fills the chip: whether the forward keeps its activations in bf16 (below).  One rule for the forward and for
 // egotap_predict_pose_rgb, which asks it whether the head will read a bf16 copy of the heatmaps.
-#ifndef EGOTAP_BF16S_MIN_ROWS
-#define EGOTAP_BF16S_MIN_ROWS 512       // [r4] 4096 before: a B = 4 forward (2304 rows) took 2.1 ms on the fp32-tensor path, 1.5 ms on this one (B = 1: 1.46 -> 1.38)
-#endif
+static constexpr int BF16S_MIN_ROWS = 512;      // [r4] 4096 before: a B = 4 forward (2304 rows) took 2.1 ms on the fp32-tensor path, 1.5 ms on this one (B = 1: 1.46 -> 1.38)
 static bool lift_bf16s_route(const Handle* h, int B) {
     // (sequence lengths that are not a multiple of 32 -- heatmap sides 32, 48, 96 ...: the bf16-storage attention tiles whole 32-key blocks -- stay on
     // fp32 tensors with bf16 products in the GEMMs and the exact-fp32 attention kernel, which masks a ragged last key tile)
-    return h->precision == EGOTAP_PREC_BF16 && h->D == 1024 && (long)B * h->seq >= EGOTAP_BF16S_MIN_ROWS && h->wscratch != nullptr && h->seq % 32 == 0 &&
+    return h->precision == EGOTAP_PREC_BF16 && h->D == 1024 && (long)B * h->seq >= BF16S_MIN_ROWS && h->wscratch != nullptr && h->seq % 32 == 0 &&
            h->wscratch_bytes >= (size_t)2 * 2048 * (size_t)(h->ppd * h->ppd * h->D);
 }
 
@@ -1161,7 +1161,6 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
     EGO_HIP(launch_ln(X, Y, NL > 0 ? p.layer[0].ln1_g : p.lnf_g, NL > 0 ? p.layer[0].ln1_b : p.lnf_b, M, 1e-12f, s));
     for (int i = 0; i < NL; ++i) {
         const auto& L = p.layer[i];
-#ifdef EGOTAP_ATTN_F32_LIVE
         if (prune && i + 1 == NL) {
             // [r6] the last layer on the live rows, compact order (b, cell < T, patch row, patch col) = fc1's (LiveRows, gemm_f32.h).  Slices:
             // K | V of all M rows into QKV's K / V columns, compact Q into its Q columns (rows 0 .. Mc); compact attention output in CTX; the
@@ -1181,7 +1180,6 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
             EGO_HIP(launch_ln(Xc, Y, p.lnf_g, p.lnf_b, Mc, 1e-12f, s));       // compact tokens: fc1 reads them as plain rows below
             break;
         }
-#endif
         {
             SegMat Wqkv; Wqkv.p[0] = L.q_w; Wqkv.p[1] = L.k_w; Wqkv.p[2] = L.v_w; Wqkv.seg = D; Wqkv.ld = D;
             SegVec bqkv; bqkv.p[0] = L.q_b; bqkv.p[1] = L.k_b; bqkv.p[2] = L.v_b; bqkv.seg = D;
@@ -2529,11 +2527,7 @@ extern "C" int egotap_synth_heatmaps(const float* pts2d_left, const float* pts2d
     for (int k = -4; k <= 4; ++k) { g.w[k + 4] = exp(-0.5 * k * k); sum += g.w[k + 4]; }
     for (int k = 0; k < 9; ++k) g.w[k] /= sum;
     const size_t lds = (size_t)2 * res * res * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        EGO_HIP(hipFuncSetAttribute((const void*)heatmap_synth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * 128 * 4));
-        attr_done = true;
-    }
+    EGO_HIP(ego_allow_dynamic_lds((const void*)heatmap_synth_kernel, 2 * 128 * 128 * 4));
     hipLaunchKernelGGL(heatmap_synth_kernel, dim3(B * 2 * J), dim3(256), lds, (hipStream_t)stream, pts2d_left, pts2d_right, pose3d, parents,
                        B, J, res, g, hm, plength, theta);
     EGO_HIP(hipGetLastError());

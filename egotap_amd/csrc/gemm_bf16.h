@@ -346,12 +346,7 @@ static hipError_t gemm_bf16_persist_launch(const ALoad& al, const WMat& W, const
     auto kern = gemm_bf16_persist_kernel<Cfg, ALoad, Epi, WMat>;
     constexpr int LDS = Cfg::LDS_BYTES + (Cfg::THREADS / 64) * 32 * 36 * 4;
     static_assert(LDS <= 160 * 1024, "LDS budget (3 slabs + per-wave transpose patches)");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, LDS); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / Cfg::BN;
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < num_cu ? ntiles : num_cu;

@@ -130,13 +130,7 @@ __device__ __forceinline__ void store_bf16x8(__bf16* p, const float* v) {
     for (int i = 0; i < 8; ++i) o[i] = (__bf16)v[i];
     // [r3] streaming store: a bf16 activation is 0.3-2.4 GB, written once and read by the NEXT kernel -- keeping its lines out of
     // the L2 leaves the operand panels this kernel re-reads there (+2-3 % on every bf16-output GEMM, profiles/r03_gemm_ablation.md)
-#if defined(EGOTAP_ABL) && (EGOTAP_ABL & 4)      // timing-only: the functor's arithmetic without the store
-    asm volatile("" ::"v"(o));
-#elif defined(EGOTAP_ABL) && (EGOTAP_ABL & 8)    // A/B: write-back instead of streaming stores
-    *(bf16x8*)p = o;
-#else
     __builtin_nontemporal_store(o, (bf16x8*)p);
-#endif
 }
 struct SBias8 { f32x4 b0, b1; };
 __device__ __forceinline__ void s_keep(const SBias8& b) { asm volatile("" ::"v"(b.b0), "v"(b.b1)); }
@@ -413,11 +407,7 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
 
     // ---- DMA duty of this wave per part: 16-row blocks wid and wid + 8.  Lane -> row lane >> 2 of the block, chunk position
     // lane & 3, which holds logical chunk (lane & 3) ^ swz(row), swz(row) = (4 - ((row >> 2) & 3)) & 3 and (row >> 2) & 3 = lane >> 4.
-#if defined(EGOTAP_ABL) && (EGOTAP_ABL & 1)      // timing-only: every DMA wave-instruction reads 8 rows x 128 B instead of 16 rows x 64 B (wrong data)
-    const int drow = lane >> 3, dchunk = lane & 7;
-#else
     const int drow = lane >> 2, dchunk = (lane & 3) ^ ((4 - (lane >> 4)) & 3);
-#endif
     typename XL::Row xr0, xr1;
     const __bf16 *pw0, *pw1;
     int lx_tile = 0, lx_kt = 0, lw_tile = 0, lw_kt = 0;       // position of the X / W issue streams (the W stream runs one phase ahead)
@@ -547,17 +537,12 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
                 if constexpr (Epi::W == 4) {
                     const f32x4 v = *(const f32x4*)(Es + r * 64 + ((l15 ^ r) << 2));
                     float vv[4] = {v[0], v[1], v[2], v[3]};
-#if !(defined(EGOTAP_ABL) && (EGOTAP_ABL & 2))      // timing-only: the epilogue without its global stores / functor
                     if ((FULL || m0 + r < M) && cact) epi.emit(vv, cc, ax[it], m0 + r, en);
-#else
-                    asm volatile("" ::"v"(vv[0]), "v"(vv[1]), "v"(vv[2]), "v"(vv[3]));
-#endif
                 } else {
                     const int c2 = lane & 7;
                     const f32x4 v0 = *(const f32x4*)(Es + r * 64 + (((2 * c2) ^ r) << 2));
                     const f32x4 v1 = *(const f32x4*)(Es + r * 64 + (((2 * c2 + 1) ^ r) << 2));
                     float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#if !(defined(EGOTAP_ABL) && (EGOTAP_ABL & 2))
                     if ((FULL || m0 + r < M) && cact) {
                         epi.emit(vv, cc, ax[it], m0 + r, en);              // (leaves the values it stored in vv)
                         if constexpr (CS) {
@@ -565,9 +550,6 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
                             for (int i = 0; i < 8; ++i) cs[i] += (float)(__bf16)vv[i];      // the sum of what was STORED (bf16)
                         }
                     }
-#else
-                    asm volatile("" ::"v"(vv[0]), "v"(vv[1]), "v"(vv[2]), "v"(vv[3]), "v"(vv[4]), "v"(vv[5]), "v"(vv[6]), "v"(vv[7]));
-#endif
                 }
             }
 #pragma unroll
@@ -687,12 +669,7 @@ static hipError_t gemm_bf16s_launch(const XL& xl, const __bf16* Wb, long ldw, co
     if (M <= 0) return hipSuccess;
     if (N % BN != 0 || K % Cfg::BK != 0 || ldw % 8 != 0) return hipErrorInvalidValue;
     auto kern = gemm_bf16s_kernel<XL, Epi, NI>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / BN;
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < num_cu ? ntiles : num_cu;
@@ -737,12 +714,7 @@ static hipError_t gemm_bf16s_splitk_launch(const XL& xl, const __bf16* Wb, long 
     if (M <= 0) return hipSuccess;
     if (N % 256 != 0 || ksplit < 2 || K % (ksplit * Cfg::BK) != 0 || ldw % 8 != 0) return hipErrorInvalidValue;
     auto kern = gemm_bf16s_kernel<XL, SEpiRawF32, 4>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / 256;
     const int ntiles = tiles_m * tiles_n * ksplit;
     const int grid = ntiles < num_cu ? ntiles : num_cu;

@@ -452,22 +452,13 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
                 if constexpr (Epi::W == 4) {
                     const f32x4 v = *(const f32x4*)(Es + r * 64 + ((ec ^ r) << 2));
                     float vv[4] = {v[0], v[1], v[2], v[3]};
-#if defined(EGOTAP_ABL) && (EGOTAP_ABL & 2)      // timing-only: the epilogue without its functor and global stores
-                    asm volatile("" ::"v"(vv[0]), "v"(vv[1]), "v"(vv[2]), "v"(vv[3]));
-#else
                     if (FULL || m0 + r < M) epi.emit(vv, cc, ax[it], m0 + r, en);
-#endif
                 } else {
                     const int c2 = ec;
                     const f32x4 v0 = *(const f32x4*)(Es + r * 64 + (((2 * c2) ^ r) << 2));
                     const f32x4 v1 = *(const f32x4*)(Es + r * 64 + (((2 * c2 + 1) ^ r) << 2));
                     float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#if defined(EGOTAP_ABL) && (EGOTAP_ABL & 2)
-                    asm volatile("" ::"v"(vv[0]), "v"(vv[1]), "v"(vv[2]), "v"(vv[3]), "v"(vv[4]), "v"(vv[5]), "v"(vv[6]), "v"(vv[7]));
-                    if (false) {
-#else
                     if (FULL || m0 + r < M) {
-#endif
                         epi.emit(vv, cc, ax[it], m0 + r, en);              // (leaves the values it stored in vv)
                         if constexpr (CS) {
 #pragma unroll
@@ -577,11 +568,7 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
     for (c_tile = 0; c_tile < my_n; ++c_tile) {
         if (slack_on) ktile(std::integral_constant<int, SLK + XB>{}, std::true_type{});
         else ktile(std::integral_constant<int, VMC + XB>{}, std::true_type{});
-#if defined(EGOTAP_ABL) && (EGOTAP_ABL & 1)      // timing-only: the store allowance never ends (waits may pass before their data has landed: wrong results)
-        for (int kt = 1; kt < KT; ++kt) ktile(std::integral_constant<int, SLK>{}, std::false_type{});
-#else
         for (int kt = 1; kt < KT; ++kt) ktile(std::integral_constant<int, VMC>{}, std::false_type{});
-#endif
         // one extra barrier per tile and group lets the two groups' epilogues run side by side (gemm_bf16s.h)
         if (grp == 0) __builtin_amdgcn_s_barrier();
         {
@@ -610,12 +597,7 @@ static hipError_t gemm_bf16s64_launch_x(const XL& xl, const __bf16* Wb, long ldw
     if (M <= 0) return hipSuccess;
     if (N % (128 * NJ) != 0 || K % 64 != 0 || K < 128 || ldw % 8 != 0 || (long)256 * ldw * 2 >= (1L << 31)) return hipErrorInvalidValue;
     auto kern = gemm_bf16s64_kernel<XL, Epi, NJ>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / (128 * NJ);
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < num_cu ? ntiles : num_cu;

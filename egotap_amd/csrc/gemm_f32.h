@@ -678,12 +678,7 @@ static hipError_t gemm_f32_pipe_launch(const ALoad& al, const SegMat& W, const E
     if (M <= 0) return hipSuccess;
     if (N % Cfg::BN != 0 || K % Cfg::BK != 0 || W.seg % Cfg::BN != 0) return hipErrorInvalidValue;
     auto kern = gemm_f32_pipe_kernel<Cfg, ALoad, Epi>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / Cfg::BN;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, al, W, epi, C, ldc, M,
                        N, K, tiles_m, tiles_n);
@@ -858,16 +853,13 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_persist_kern
             } else if (gs + 1 < total) {
                 FRAGS(0, b1, 0)
             }
-#ifndef EGOTAP_SB_VARIANT
-#define EGOTAP_SB_VARIANT 0
-#endif
-            if (EGOTAP_SB_VARIANT != 2) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             MFMAS(t & 1)
-            if (EGOTAP_SB_VARIANT == 0) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             if (t == G / 2 - 1) {
                 if (gs + 2 < total) LSTORE(b2)          // slab gs+2 (requested one slab ago) -> the free LDS slab
                 if (gs + 3 < total) GLOAD()             // request slab gs+3 into the registers just freed
-                if (EGOTAP_SB_VARIANT == 0) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         __syncthreads();
@@ -892,12 +884,7 @@ static hipError_t gemm_f32_persist_launch(const ALoad& al, const SegMat& W, cons
     auto kern = gemm_f32_persist_kernel<Cfg, ALoad, Epi>;
     constexpr int LDS = Cfg::LDS_BYTES + (Cfg::THREADS / 64) * 32 * 36 * 4;
     static_assert(LDS <= 160 * 1024, "LDS budget (3 slabs + per-wave transpose patches)");
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, LDS); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / Cfg::BN;
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < num_cu ? ntiles : num_cu;
@@ -912,12 +899,7 @@ static hipError_t gemm_f32_launch(const ALoad& al, const SegMat& W, const Epi& e
     if (M <= 0) return hipSuccess;
     if (N % Cfg::BN != 0 || K % Cfg::BK != 0 || W.seg % Cfg::BN != 0) return hipErrorInvalidValue;
     auto kern = gemm_f32_kernel<Cfg, ALoad, Epi>;
-    static bool attr_done = false;     // per instantiation
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / Cfg::BN;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, al, W, epi, C, ldc, M,
                        N, K, tiles_m, tiles_n);
@@ -1081,12 +1063,7 @@ static hipError_t gemm_f32_splitk_partials(const ALoad& al, const SegMat& W, flo
     if ((size_t)splits * M * N > p_floats) return hipErrorInvalidValue;
     const int kper = ((KT + splits - 1) / splits) * Cfg::BK;
     auto kern = gemm_f32_splitk_kernel<Cfg, ALoad>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, splits), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, al, W, P, M, N, K, tiles_m, tiles_n, kper);
     return hipGetLastError();
 }

@@ -55,14 +55,9 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
     // position lane & 3), which holds logical chunk (lane & 3) ^ ((row >> 2) & 3) = (lane & 3) ^ (lane >> 4).
     const int drow = lane >> 2, dchunk = (lane & 3) ^ (lane >> 4);
     typename ALoad::Row ra0, ra1;
-    const float *pb0, *pb1;
     // [r5] plain row-major operands: a wave-uniform 64-bit base per tile (scalar registers) + a 32-bit byte offset per lane -- the global_load_lds
-    // s[base] form -- instead of a 64-bit pointer per lane (-DEGOTAP_F32_DMA_FLAT keeps the pointer form for the A/B).  W is always plain rows.
-#ifdef EGOTAP_F32_DMA_FLAT
-    constexpr bool SBA = false, SBW = false;
-#else
-    constexpr bool SBA = std::is_same<ALoad, ALoadPlain>::value, SBW = true;
-#endif
+    // s[base] form -- instead of a 64-bit pointer per lane (the A/B is recorded in profiles/r05_dma_addressing_ab.log).  W is always plain rows.
+    constexpr bool SBA = std::is_same<ALoad, ALoadPlain>::value;
     unsigned long long abase = 0, wbase = 0;
     unsigned ao0 = 0, ao1 = 0;
     auto uniform64 = [](const void* p) __attribute__((always_inline)) { return lds_dma_base(p); };      // lds_dma.h
@@ -84,11 +79,7 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
         // vmcnt wait would drain the DMA pipeline at every tile switch
         const int n0 = tn * BN, sidx = n0 / W.seg;
         const float* wp = (sidx == 0 ? W.p[0] : (sidx == 1 ? W.p[1] : W.p[2])) + (long)(n0 - sidx * W.seg) * W.ld;
-        if constexpr (SBW) wbase = uniform64(wp);
-        else {
-        pb0 = wp + (long)(wid * 16 + drow) * W.ld + dchunk * 4;
-        pb1 = wp + (long)((wid + 8) * 16 + drow) * W.ld + dchunk * 4;
-        }
+        wbase = uniform64(wp);
     };
     set_rows(0);
     // The DMA goes through inline asm: the compiler's waitcnt pass treats __builtin_amdgcn_global_load_lds as a store to LDS that
@@ -109,8 +100,8 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
         const int k0 = l_kt * BK;
         if (part == 0) { if constexpr (SBA) dma1s(ao0, abase + (unsigned long long)k0 * 4, sa); else dma1(al.ptr(ra0, k0 + dchunk * 4), sa); }
         else if (part == 1) { if constexpr (SBA) dma1s(ao1, abase + (unsigned long long)k0 * 4, sa + 8 * 1024); else dma1(al.ptr(ra1, k0 + dchunk * 4), sa + 8 * 1024); }
-        else if (part == 2) { if constexpr (SBW) dma1s(wo0, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB); else dma1(pb0 + k0, sa + BM * ROWB); }
-        else { if constexpr (SBW) dma1s(wo1, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB + 8 * 1024); else dma1(pb1 + k0, sa + BM * ROWB + 8 * 1024); }
+        else if (part == 2) dma1s(wo0, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB);
+        else dma1s(wo1, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB + 8 * 1024);
     };
     auto dma_advance = [&]() __attribute__((always_inline)) {
         if (l_tile < my_n && ++l_kt == KT) {
@@ -301,12 +292,7 @@ static hipError_t gemm_f32_dma_launch(const ALoad& al, const SegMat& W, const Ep
     if (N % Cfg::BN != 0 || K % Cfg::BK != 0 || W.seg % Cfg::BN != 0 || !al.dma_ok() || W.ld % 4 != 0) return hipErrorInvalidValue;
     if (W.ld >= (1L << 21) || K >= (1 << 21)) return hipErrorInvalidValue;      // 256 rows of an operand within the 32-bit lane offsets of the scalar-base DMA
     auto kern = gemm_f32_dma_kernel<ALoad, Epi>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int tiles_m = (M + Cfg::BM - 1) / Cfg::BM, tiles_n = N / Cfg::BN;
     const int ntiles = tiles_m * tiles_n;
     const int grid = ntiles < num_cu ? ntiles : num_cu;

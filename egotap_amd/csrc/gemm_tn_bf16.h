@@ -196,12 +196,7 @@ static hipError_t gemm_tn_bf16_launch(const float* dY, long ldy, const XLoad& xl
     if ((direct ? (db ? (size_t)N * 4 : 0) : (size_t)splits * per_split) > slab_bytes) return hipErrorOutOfMemory;
     float* csum = db ? slabs + (direct ? 0 : (size_t)splits * N * K) : nullptr;
     auto kern = gemm_tn_bf16_kernel<Cfg, XLoad>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, dY, ldy, xl, direct ? dW : slabs, M, N, K,
                        tiles_n, tiles_k, splits, csum);
     hipError_t e = hipGetLastError();

@@ -350,18 +350,11 @@ static hipError_t gemm_tn_bf16s_launch(const __bf16* dY, long ldy, const XL& xl,
     const int rows_per = ((M + splits - 1) / splits + Cfg::BKM - 1) / Cfg::BKM * Cfg::BKM;
     // plain operand and whole 32-row steps everywhere: the scalar-base form of the DMA addresses
     bool fast = false;
-#if !(defined(EGOTAP_ABL) && (EGOTAP_ABL & 16))      // A/B: the general addressing everywhere
     if constexpr (std::is_same<XL, TXPlain>::value) fast = M % Cfg::BKM == 0 && (long)32 * (ldy > xl.lda ? ldy : xl.lda) * 2 < (1L << 31) && xl.lda % 8 == 0;
     else fast = M % Cfg::BKM == 0 && (long)32 * ldy * 2 < (1L << 31) && xl.span(M) * 2 < (1L << 32);      // gathered rows: 32-bit byte offsets from the tensor base
-#endif
     auto kern = gemm_tn_bf16s_kernel<XL>;
     if (fast) kern = gemm_tn_bf16s_kernel<XL, true>;
-    static bool attr_done[2] = {false, false};
-    if (!attr_done[fast]) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done[fast] = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     // check-in counters of the L2-sharing groups (8 XCD chunks x splits) behind the slabs, cleared per launch
     int* sync = nullptr;
     const size_t sync_off = ((size_t)splits * N * K * 4 + 255) & ~(size_t)255;

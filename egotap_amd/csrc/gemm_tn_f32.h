@@ -188,12 +188,7 @@ static hipError_t gemm_tn_f32_launch(const float* dY, long ldy, const XLoad& xl,
     const bool direct = splits == 1 && !accumulate;              // a single slab that is not added to anything IS the gradient
     if (!direct && (size_t)splits * N * K * 4 > slab_bytes) return hipErrorOutOfMemory;
     auto kern = gemm_tn_f32_kernel<Cfg, XLoad>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, dY, ldy, xl, direct ? dW : slabs, M, N, K,
                        tiles_n, tiles_k, splits);
     hipError_t e = hipGetLastError();
@@ -279,19 +274,12 @@ static __global__ __launch_bounds__(TnDmaCfg::THREADS) void gemm_tn_f32_dma_kern
 
     // the DMA goes through inline asm and vmcnt is waited for by hand (see gemm_f32_dma.h for why)
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_tnd;
-    auto dma1 = [&](const float* g, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
     // wave w stages rows w, w + 8, w + 16, w + 24 of both operands: 8 DMA instructions per wave and slab
     // [r5] a staged row is one wave instruction: wave-uniform row address (scalar registers) + 16 bytes per lane -- the global_load_lds s[base]
-    // form instead of a 64-bit pointer per lane (-DEGOTAP_TNF32_DMA_FLAT keeps the pointer form for the A/B)
+    // form instead of a 64-bit pointer per lane (the A/B is recorded in profiles/r05_dma_addressing_ab.log)
     auto dma1s = [&](unsigned voff, const float* base, unsigned lds_addr) __attribute__((always_inline)) {
-#ifdef EGOTAP_TNF32_DMA_FLAT
-        dma1((const float*)((const char*)base + voff), lds_addr);
-#else
         const unsigned long long sb = lds_dma_base(base);      // lds_dma.h
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sb), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-#endif
     };
     const float* ga = dY + (long)(m_lo + wid) * ldy + n0;
     const float* gb = X + (long)(m_lo + wid) * ldx + k0;
@@ -387,12 +375,7 @@ static hipError_t gemm_tn_f32_dma_launch(const float* dY, long ldy, const float*
     if ((slab_floats + (db ? (size_t)splits * N : 0)) * 4 > slab_bytes) return hipErrorOutOfMemory;
     const int rows_per = per * Cfg::BKM;
     float* csum = db ? slabs + slab_floats : nullptr;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_f32_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)gemm_tn_f32_dma_kernel, Cfg::LDS_BYTES); e != hipSuccess) return e;
     hipLaunchKernelGGL(gemm_tn_f32_dma_kernel, dim3(tiles * splits), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, dY, ldy, X, ldx, direct ? dW : slabs, M, N,
                        K, tiles_n, tiles_k, splits, rows_per, csum);
     hipError_t e = hipGetLastError();

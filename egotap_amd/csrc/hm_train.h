@@ -170,12 +170,7 @@ static hipError_t conv_wgrad_launch(WgArgs a, float* dw, size_t slab_bytes, int 
     if (splits < 1) return hipErrorOutOfMemory;
     a.splits = splits;
     auto kern = conv_wgrad_kernel<Cfg>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -693,12 +688,7 @@ static hipError_t conv_wgrad_bf16_launch(WgArgs a, float* dw, size_t slab_bytes,
     if (splits < 1) return hipErrorOutOfMemory;
     a.splits = splits;
     auto kern = conv_wgrad_bf16_kernel<Cfg>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)kern, Cfg::LDS_BYTES); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(tiles * splits), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -76,12 +76,7 @@ static inline hipError_t stem_pool_bf16s_launch_mode(const float* left, const fl
     using Cfg = StemPoolCfg;
     const int HO = HIN / 2, HP = HIN / 4;
     if (HO % Cfg::XS != 0 || HP % Cfg::R != 0 || nimg <= 0) return hipErrorInvalidValue;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)stem_pool_bf16s_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)stem_pool_bf16s_kernel<MODE>, Cfg::LDS_BYTES); e != hipSuccess) return e;
     const int groups = HP / Cfg::R;
     const long runs = (long)nimg * groups;
     long grid = runs < 2L * num_cu ? runs : 2L * num_cu;
@@ -105,12 +100,7 @@ static inline hipError_t stem_pool_bf16s_u8_launch(const unsigned char* left, co
     constexpr int LDS = Cfg::LDS_BYTES + StemPoolU8::LDS_EXTRA;
     const int HO = HIN / 2, HP = HIN / 4;
     if (HO % Cfg::XS != 0 || HP % Cfg::R != 0 || nimg <= 0) return hipErrorInvalidValue;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)stem_pool_bf16s_u8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
+    if (hipError_t e = ego_allow_dynamic_lds((const void*)stem_pool_bf16s_u8_kernel, LDS); e != hipSuccess) return e;
     const long runs = (long)nimg * (HP / Cfg::R);
     const long grid = runs < 2L * num_cu ? runs : 2L * num_cu;
     hipLaunchKernelGGL(stem_pool_bf16s_u8_kernel, dim3((unsigned)grid), dim3(Cfg::THREADS), LDS, s, left, right, table, w, gamma, beta, mean, var, out, HIN, nimg);

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """GPU probe: the bf16-storage attention kernels (forward, dQ + dK/dV backward) at B frames of N tokens, HIP-event timed (median of
 three rounds), with the run-to-run bit equality of their outputs.  usage: python tools/attn_probe.py [B] [N]
-To A/B a kernel change build the variant into its own library (EGOTAP_LIB=<path> EGOTAP_CXXFLAGS=-D... python -m egotap_amd.build) and
-run this probe once per library in ONE gpurun call, dumping outputs with --dump <file> to compare bits across the two runs."""
+To A/B a kernel change build the changed tree into its own library (EGOTAP_LIB=<path> python -m egotap_amd.build) and run this probe
+once per library in ONE session on one box, dumping outputs with --dump <file> to compare bits across the two runs.  The kernels carry
+no compile-time variants: the round-5 A/B of the DMA addressing made this way is recorded in profiles/r05_attention_ab.log."""
 import json
 import os
 import sys
