@@ -36,6 +36,7 @@
 #include "conv64_bf16s.h"
 #include "bn_bf16s.h"
 #include "rgb_u8.h"
+#include "rgb_u8_resize.h"
 
 // The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
 // inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
@@ -1464,11 +1465,19 @@ static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, in
 // [r7] Where an estimator's frames come from: the normalised planar fp32 frames (left / right), or the camera's bytes (left8 / right8: uint8
 // [B, S0, S0, 3], with the fp32 [3][256] value table).  Sides 64 / 128: both stems stage the bytes themselves.  Every other side: the frames are
 // converted into `scratch` (2 x B x 3 x S0^2 floats, the caller's workspace slice) first and the forward proceeds on them as ever.
+// [r8] the sensor's own frames behind a byte source (egotap_predict_pose_sensor_u8 only): uint8 [B, H, W, 3] per eye, a source rectangle and a mirror
+// flag per eye; each piece is resized into `slice` (chunk x 2 x 3 S0^2 bytes of the caller's workspace) and read there as camera bytes
+struct HmSensor {
+    const unsigned char *left8, *right8;
+    int H, W, rect[2][4], mirror[2];
+    unsigned char* slice;
+};
 struct HmSrc {
     const float *left, *right;
     const unsigned char *left8, *right8;
     const float* table;
     float* scratch;
+    const HmSensor* sensor = nullptr;      // [r8] set by the sensor entry alone
     bool bytes() const { return left8 != nullptr; }
     HmSrc at(long frame, long rgb) const {      // the source of the frames from `frame` on (rgb = 3 S0^2 elements per frame)
         HmSrc r = *this;
@@ -2156,6 +2165,11 @@ static RgbWs rgb_ws(const Handle* h, int B, int chunk) {
 }
 // The hand-off: nobody asked for the fp32 heatmaps, the estimators run the bf16 channels-last route (whose conv_heatmap is the bf16-storage GEMM) and
 // the head runs its bf16-storage route (which reads a bf16 copy of the heatmaps and nothing else of them): conv_heatmap then writes that copy itself.
+// [r8] the resized bytes of one piece of a sensor-source call: n frames x 2 eyes x 3 S0^2 bytes
+static inline size_t rgb_sensor_slice_bytes(const Handle* h, int n) {
+    const size_t S0 = (size_t)h->cfg.hm_size * 4;
+    return (size_t)n * 2 * 3 * S0 * S0;
+}
 static bool rgb_handoff(const Handle* h, int B, const float* heatmaps) { return heatmaps == nullptr && hm_frozen_route(h) && lift_bf16s_route(h, B); }
 
 extern "C" int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
@@ -2179,10 +2193,12 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
     }
     const RgbWs w = rgb_ws(h, B, chunk);
     const int c = rgb_chunk(B, chunk), S = h->cfg.hm_size, HW = S * S, J = h->J;
-    const size_t need = w.total + (src.bytes() ? hm_u8_slice_bytes(h, c) : 0);
+    // [r8] a sensor source is a byte source behind a resize: [ ... | the converter slice, where the stems do not read bytes | the resized bytes of one chunk ]
+    const size_t conv = src.bytes() || src.sensor ? hm_u8_slice_bytes(h, c) : 0;
+    const size_t need = w.total + conv + (src.sensor ? rgb_sensor_slice_bytes(h, c) : 0);
     EGO_CHECK(ws_bytes >= need, "%s: workspace too small: %zu bytes given, %zu needed for B=%d, chunk=%d", who, ws_bytes, need, B, chunk);
     HmSrc whole = src;
-    whole.scratch = src.bytes() ? (float*)((char*)ws + w.total) : nullptr;
+    whole.scratch = src.bytes() || src.sensor ? (float*)((char*)ws + w.total) : nullptr;
     const long img = (long)h->C * HW, rgb = 3L * (4 * S) * (4 * S);
     const bool handoff = rgb_handoff(h, B, heatmaps);
     float* hm = heatmaps ? heatmaps : (float*)((char*)ws + w.HM);
@@ -2190,7 +2206,37 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
     h->rgb_form = EGOTAP_RGB_FORM_NONE;
     // position net: channels [0, 2J) (left | right); limb net: [2J, 6J) (left cos, sin | right cos, sin)
     const int nets[2] = {EGOTAP_NET_HM_POS, EGOTAP_NET_HM_ROT}, c0[2] = {0, 2 * J};
-    if (src.bytes() && !hm_stem_reads_bytes(S)) {
+    if (src.sensor && !src.bytes()) {
+        // [r8] the sensor route: a piece's frames are resized ONCE into the slice and read there as camera bytes by both estimators (pieces outer,
+        // estimators inner) -- by the byte-source stems at sides 64 / 128, through the converter elsewhere.  (With bytes() set the request is the
+        // identity: the caller's frames ARE the camera bytes and the walks below read them in place.)
+        const HmSensor& q = *src.sensor;
+        const long frame = 3L * q.H * q.W;
+        unsigned char* s8l = q.slice;
+        for (int lo = 0; lo < B; lo += c) {
+            const int n = B - lo < c ? B - lo : c;
+            unsigned char* s8r = s8l + (size_t)n * rgb;
+            {
+                GemmTimer t(h, (hipStream_t)stream, "rgb_u8_resize", "rgb_u8_resize_kernel", 0.0);
+                EGO_HIP(rgb_u8_resize_launch(q.left8 + lo * frame, q.right8 + lo * frame, n, q.H, q.W, q.rect[0], q.rect[1], q.mirror[0], q.mirror[1], 4 * S, s8l, s8r,
+                                             device_cu_count(), (hipStream_t)stream));
+            }
+            HmSrc piece{nullptr, nullptr, s8l, s8r, src.table, nullptr};
+            const bool stems = hm_stem_reads_bytes(S);
+            if (!stems) {
+                float *cl = whole.scratch, *cr = cl + (size_t)n * rgb;
+                GemmTimer t(h, (hipStream_t)stream, "rgb_u8_to_f32", "rgb_u8_to_f32_kernel", 0.0);
+                EGO_HIP(rgb_u8_to_f32_launch(s8l, s8r, src.table, cl, cr, n, 4 * S, device_cu_count(), (hipStream_t)stream));
+                piece = hm_src_f32(cl, cr);
+            }
+            for (int k = 0; k < 2; ++k) {
+                const long at = lo * img + (long)c0[k] * HW;
+                const bool ho = stems && handoff;
+                const int rc = hm_forward_impl(h, nets[k], piece, n, ho ? nullptr : hm + at, img, ws, w.HM, stream, ho ? hmb + at : nullptr);
+                if (rc != EGOTAP_OK) return rc;
+            }
+        }
+    } else if (src.bytes() && !hm_stem_reads_bytes(S)) {
         // the converter route: a piece's frames are converted ONCE into the slice and both estimators read them there (pieces outer, estimators inner;
         // the two share the U-Net scratch one after the other, as ever; never the hand-off: that exists at sides 64 / 128 only)
         float* cl = whole.scratch;
@@ -2251,6 +2297,60 @@ extern "C" int egotap_predict_pose_rgb_u8(egotap_handle h, const uint8_t* left8,
     EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
     EGO_CHECK((((uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
     const HmSrc src{nullptr, nullptr, left8, right8, table, nullptr};
+    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream);
+}
+
+// ---- [r8] the sensor's own frames: crop, mirror and bilinear resize on the device (rgb_u8_resize.h), standalone and in front of the one call
+static const char* rgb_u8_resize_refusal(const void* left8, const void* right8, int H, int W, const int* rect_left, const int* rect_right) {
+    if (!left8 || !right8) return "null frames (left8 and right8 are required)";
+    if (!rect_left || !rect_right) return "null rectangle (rect_left and rect_right are four ints each: x0, y0, w, h)";
+    if (H < 1 || W < 1 || H > kResizeMaxSrc || W > kResizeMaxSrc) return "the frame height and width must be between 1 and 16384";
+    if (const char* why = rgb_u8_resize_rect_refusal(rect_left, H, W)) return why;
+    return rgb_u8_resize_rect_refusal(rect_right, H, W);
+}
+extern "C" int egotap_rgb_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rect_left, const int* rect_right, int mirror_left,
+                                    int mirror_right, int S0, uint8_t* out_left8, uint8_t* out_right8, void* stream) {
+    static const char* const who = "egotap_rgb_u8_resize";
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
+    const char* why = rgb_u8_resize_refusal(left8, right8, H, W, rect_left, rect_right);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
+    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
+    EGO_HIP(rgb_u8_resize_launch(left8, right8, B, H, W, rect_left, rect_right, mirror_left, mirror_right, S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, int B, int H, int W, int chunk, size_t* bytes) {
+    static const char* const who = "egotap_predict_pose_sensor_u8_workspace_bytes";
+    EGO_CHECK(h && bytes, "%s: null argument", who);
+    EGO_CHECK(B >= 0 && chunk >= 0, "%s: negative batch or chunk", who);
+    EGO_CHECK(H >= 1 && W >= 1 && H <= kResizeMaxSrc && W <= kResizeMaxSrc, "%s: the frame height and width must be between 1 and 16384", who);
+    const int b = B > 0 ? B : 1, c = rgb_chunk(b, chunk);
+    *bytes = rgb_ws(h, b, chunk).total + hm_u8_slice_bytes(h, c) + rgb_sensor_slice_bytes(h, c);      // (the slice holds OUTPUT frames: H and W do not enter)
+    return EGOTAP_OK;
+}
+extern "C" int egotap_predict_pose_sensor_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
+                                             const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {
+    static const char* const who = "egotap_predict_pose_sensor_u8";
+    EGO_CHECK(h, "%s: null handle", who);
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(rects && mirrors, "%s: null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)", who);
+    const char* why = rgb_u8_resize_refusal(left8, right8, H, W, rects, rects + 4);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    why = rgb_u8_refusal(left8, right8, table);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(pose && ws, "%s: null argument (pose and ws are required; only heatmaps may be NULL)", who);
+    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
+    EGO_CHECK((((uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
+    const int S0 = 4 * h->cfg.hm_size, c = rgb_chunk(B, chunk);
+    EGO_CHECK(S0 <= kResizeMaxSide, "%s: the frame side 4 * hm_size = %d is beyond the resize kernel's %d", who, S0, kResizeMaxSide);
+    HmSensor q{left8, right8, H, W, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}}, {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0},
+               (unsigned char*)ws + rgb_ws(h, B, chunk).total + hm_u8_slice_bytes(h, c)};
+    // the identity request (frames already S0 x S0, the full frame, no mirror): the caller's frames are read in place, nothing is resized
+    bool identity = H == S0 && W == S0 && !q.mirror[0] && !q.mirror[1];
+    for (int e = 0; e < 2; ++e) identity = identity && q.rect[e][0] == 0 && q.rect[e][1] == 0 && q.rect[e][2] == S0 && q.rect[e][3] == S0;
+    HmSrc src{nullptr, nullptr, identity ? left8 : nullptr, identity ? right8 : nullptr, table, nullptr};
+    src.sensor = &q;
     return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream);
 }
 

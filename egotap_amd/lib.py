@@ -48,6 +48,12 @@ _PROTOS = {
     "egotap_predict_pose_rgb_u8_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "egotap_predict_pose_rgb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_size_t, C.c_void_p]),
+    # ---- the sensor's own frames: uint8 [B, H, W, 3] + a source rectangle and a mirror flag per eye
+    "egotap_rgb_u8_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_sensor_u8_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "egotap_predict_pose_sensor_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -309,6 +315,42 @@ def rgb_u8_to_f32(left8, right8, table):
     with torch.cuda.device(left8.device):
         check(load().egotap_rgb_u8_to_f32(_ptr(left8), _ptr(right8), B, S0, _ptr(table), _ptr(left), _ptr(right), _stream(left8.device)))
     return left, right
+
+
+def check_sensor_frames(who, left8, right8):
+    """the one wording of what the sensor entries take: two uint8 [B, H, W, 3] contiguous tensors on one GPU, the same H and W for both eyes;
+    returns (B, H, W)"""
+    import torch
+    for t in (left8, right8):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the frames to cuda")
+    for t in (left8, right8):
+        if t.dtype != torch.uint8:
+            raise EgotapError(f"{who} takes the sensor's bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
+    if left8.dim() != 4 or left8.shape[3] != 3 or left8.shape[1] < 1 or left8.shape[2] < 1 or tuple(right8.shape) != tuple(left8.shape):
+        raise ValueError(f"{who}: expected left8 / right8 [B, H, W, 3] (HWC, RGB) with one H and W for both eyes, got {tuple(left8.shape)} / {tuple(right8.shape)}")
+    if not (left8.is_contiguous() and right8.is_contiguous()) or left8.device != right8.device:
+        raise EgotapError(f"{who}: the frames must be contiguous and on one device (the bytes are read in place, nothing is copied)")
+    return tuple(int(v) for v in left8.shape[:3])
+
+
+def rgb_u8_resize(left8, right8, S0, rect_left=None, rect_right=None, mirror_left=False, mirror_right=False):
+    """sensor frames uint8 [B, H, W, 3] x 2 -> camera bytes uint8 [B, S0, S0, 3] x 2 (egotap_rgb_u8_resize): per eye the source rectangle
+    (x0, y0, w, h) (None: the full frame), mirrored or not, resampled bilinearly with align_corners=False in the integer arithmetic of
+    spec.resize_u8 -- equal to it bit for bit.  One launch for both eyes."""
+    import torch
+    from . import spec as _spec
+    B, H, W = check_sensor_frames("rgb_u8_resize", left8, right8)
+    rl = (C.c_int * 4)(*_spec.check_resize_rect("rgb_u8_resize", rect_left, H, W))
+    rr = (C.c_int * 4)(*_spec.check_resize_rect("rgb_u8_resize", rect_right, H, W))
+    out_l = torch.empty((B, S0, S0, 3), dtype=torch.uint8, device=left8.device)
+    out_r = torch.empty_like(out_l)
+    if B == 0:
+        return out_l, out_r
+    with torch.cuda.device(left8.device):
+        check(load().egotap_rgb_u8_resize(_ptr(left8), _ptr(right8), B, H, W, rl, rr, int(bool(mirror_left)), int(bool(mirror_right)), int(S0), _ptr(out_l),
+                                          _ptr(out_r), _stream(left8.device)))
+    return out_l, out_r
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

@@ -561,6 +561,48 @@ class EgoTAPAutoEncoderModel(nn.Module):
         return self._serve_one_call(left8, right8, B, dev, return_heatmaps, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
                                     kind=("u8", table.data_ptr()), keep=(table,))
 
+    @torch.no_grad()
+    def predict_pose_from_sensor(self, left8, right8, crop=None, crop_right=None, mirror_right=False, return_heatmaps=False, graphed=False):
+        """predict_pose_from_camera from the sensor's own frames: stereo uint8 [B, H, W, 3] (HWC, RGB, any H x W, the same for both eyes) -> pose
+        [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_sensor_u8) on the serving handle:
+        the caller's crop, flip, F.interpolate and round to bytes are gone -- the library resizes chunk by chunk into a workspace slice
+        (rgb_u8_resize_kernel) and the byte source reads that slice.  The bits are those of predict_pose_from_camera on
+        ``spec.resize_u8(frames, rect, mirror, 4S)``, the integer restatement of the resize (within 0.5 + 510 / 4096 of exact bilinear
+        interpolation with align_corners=False on every byte).
+
+        ``crop``: the source rectangle (x0, y0, w, h) in source pixels, inside the frame (None: the full frame); ``crop_right``: the right eye's
+        (None: the same as ``crop``).  ``mirror_right``: the right eye's output column X takes what column 4S - 1 - X takes without it.  The
+        reference flips the second camera's frame and THEN crops (reprocess_egocap_data.py:100-104, :221): its rectangle x0' in flipped
+        coordinates is x0 = W - x0' - w here.  Frames already 4S x 4S with the full rectangle and no mirror are read in place.
+
+        ``graphed``: as predict_pose_from_camera; the capture key holds the source kind, H, W, the rectangles, the mirror flags and the table, so
+        no graph is shared with the other entries.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions)
+        run egotap_rgb_u8_resize followed by predict_pose_from_camera's fallback -- by name, ungraphed."""
+        p = self.net_AutoEncoder.preset
+        S0 = 4 * p.hm_size
+        B, H, W = _lib.check_sensor_frames("predict_pose_from_sensor", left8, right8)
+        rect_l = _spec.check_resize_rect("predict_pose_from_sensor", crop, H, W)
+        rect_r = _spec.check_resize_rect("predict_pose_from_sensor", crop if crop_right is None else crop_right, H, W)
+        mirrors = (0, int(bool(mirror_right)))
+        dev = left8.device
+        why = self._rgb_one_call_refusal()
+        if why is not None:
+            if graphed:
+                raise _lib.EgotapError(f"predict_pose_from_sensor(graphed=True): {why}; this configuration runs the resize, the converter and the module forwards, ungraphed")
+            l8, r8 = _lib.rgb_u8_resize(left8, right8, S0, rect_l, rect_r, False, bool(mirror_right))
+            return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps)
+        table = self.camera_table(dev)
+        lib = _lib.load()
+        rects, flags = (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors)
+
+        def size_query(h, b, chunk, out):
+            return lib.egotap_predict_pose_sensor_u8_workspace_bytes(h, b, H, W, chunk, out)
+
+        def launch(h, l, r, po, hmo, chunk, ws):
+            _lib.check(lib.egotap_predict_pose_sensor_u8(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
+        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, graphed, size_query, launch,
+                                    kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,))
+
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity
         tests; egotap_debug.h): "heatmaps" -> fp32 [B, 6J, S, S] after a "scratch" call, "handoff" -> bfloat16 [B, 6J, S, S] after a "handoff" call"""

@@ -270,3 +270,69 @@ def rgb_u8_table(opt=None):
     x = (np.arange(256, dtype=np.uint8).astype(np.float32) / np.float32(255.0)).astype(np.float64).reshape(1, 256)
     t = (x - np.array(mean, dtype=np.float64).reshape(3, 1)) / np.array(std, dtype=np.float64).reshape(3, 1)
     return np.ascontiguousarray(t.astype(np.float32))
+
+
+# ---- sensor frames -> camera bytes: crop, mirror, bilinear resize (egotap.h: egotap_rgb_u8_resize / egotap_predict_pose_sensor_u8) ------
+RESIZE_WEIGHT_ONE = 2048          # one axis weight in fixed point (11 bits); two axes and a byte: 2048^2 * 255 + 2^21 < 2^31
+
+
+def resize_taps(L: int, S0: int):
+    """The two source taps and the weight of the second one, for each of the S0 output indices along an axis of source length L, in integers
+    (align_corners=False, what F.interpolate bilinear and cv2 INTER_LINEAR sample): with n = max((2X + 1) L - S0, 0),
+
+        i0 = n div 2S0,  r = n mod 2S0,  w1 = (r * 2048 + S0) div 2S0,  w0 = 2048 - w1,  i1 = min(i0 + 1, L - 1)
+
+    Returns int64 numpy arrays (i0, i1, w1).  L = S0 gives i0 = X, w1 = 0: an exact copy.  Each weight is within 2^-12 of the real one."""
+    import numpy as np
+    if L < 1 or S0 < 1:
+        raise ValueError(f"resize_taps: source length and output side must be positive, got {L}, {S0}")
+    X = np.arange(S0, dtype=np.int64)
+    n = np.maximum((2 * X + 1) * L - S0, 0)
+    i0, r = n // (2 * S0), n % (2 * S0)
+    w1 = (r * RESIZE_WEIGHT_ONE + S0) // (2 * S0)
+    return i0, np.minimum(i0 + 1, L - 1), w1
+
+
+def check_resize_rect(who: str, rect, H: int, W: int):
+    """(x0, y0, w, h) in source pixels, inside the H x W frame, w, h >= 1; returns it as four ints"""
+    if rect is None:
+        return (0, 0, int(W), int(H))
+    if len(rect) != 4:
+        raise ValueError(f"{who}: a rectangle is (x0, y0, w, h), got {tuple(rect)}")
+    x0, y0, w, h = (int(v) for v in rect)
+    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError(f"{who}: rectangle (x0, y0, w, h) = {(x0, y0, w, h)} is empty or outside the {H} x {W} frame")
+    return x0, y0, w, h
+
+
+def resize_u8(frames, rect, mirror: bool, S0: int):
+    """The whole resize, restated in integers on the host: frames uint8 [n, H, W, 3] (numpy array or torch tensor on any device) -> uint8
+    [n, S0, S0, 3] of the same kind.  The source rectangle ``rect`` = (x0, y0, w, h) (None: the full frame) is sampled with ``resize_taps``
+    along each axis and
+
+        out = (sum_{a, b in {0, 1}} wy_a wx_b p[y0 + iy_a][x0 + ix_b][c] + 2^21) >> 22          (one rounding; the sum is exact in int32)
+
+    With ``mirror``, output column X takes the value column S0 - 1 - X has without it.  The reference flips the frame and then crops
+    (reprocess_egocap_data.py:100-104): its rectangle x0' in flipped coordinates is x0 = W - x0' - w here.  This is what rgb_u8_resize_kernel
+    computes, bit for bit; against exact bilinear interpolation E every byte satisfies |out - E| <= 0.5 + 510 / 4096."""
+    import numpy as np
+    import torch
+    is_np = isinstance(frames, np.ndarray)
+    x = torch.from_numpy(frames) if is_np else frames
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"resize_u8: frames are uint8 [n, H, W, 3], got {x.dtype} {tuple(x.shape)}")
+    H, W = int(x.shape[1]), int(x.shape[2])
+    x0, y0, w, h = check_resize_rect("resize_u8", rect, H, W)
+    dev = x.device
+    ix0, ix1, wx1 = (torch.from_numpy(a).to(dev) for a in resize_taps(w, S0))
+    iy0, iy1, wy1 = (torch.from_numpy(a).to(dev) for a in resize_taps(h, S0))
+    if mirror:
+        ix0, ix1, wx1 = ix0.flip(0), ix1.flip(0), wx1.flip(0)
+    wx0, wy0 = RESIZE_WEIGHT_ONE - wx1, RESIZE_WEIGHT_ONE - wy1
+    acc = torch.zeros((x.shape[0], S0, S0, 3), dtype=torch.int64, device=dev)
+    for iy, wy in ((iy0, wy0), (iy1, wy1)):
+        rows = x[:, y0 + iy]                                                     # [n, S0, W, 3]
+        for ix, wx in ((ix0, wx0), (ix1, wx1)):
+            acc += rows[:, :, x0 + ix].to(torch.int64) * (wy.view(1, S0, 1, 1) * wx.view(1, 1, S0, 1))
+    out = ((acc + (1 << 21)) >> 22).to(torch.uint8)
+    return out.numpy() if is_np else out

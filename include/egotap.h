@@ -178,6 +178,35 @@ int egotap_predict_pose_rgb_u8_workspace_bytes(egotap_handle h, int B, int chunk
 int egotap_predict_pose_rgb_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
                                int chunk, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the sensor's own frames: crop, mirror and bilinear resize on the device (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * No sensor delivers S0 x S0 frames; the reference brings them there offline (reprocess_egocap_data.py:72-88 crop_resize_images: centre crop,
+ * F.interpolate(..., size=(256, 256), mode='bilinear', align_corners=False) on the uint8 tensor; :100-104, :221 a flip for the second camera; the loader's
+ * resize to 4*hm_size, dataloader/data_loader.py:70-74).  These entries take the frames as they come:
+ *   left8, right8  device uint8 [B, H, W, 3], RGB order, contiguous, 1 <= H, W <= 16384; every source byte is loaded as a byte at an offset inside
+ *                  its rectangle, so no load touches a byte outside B*H*W*3
+ *   rect           per eye four ints (x0, y0, w, h) in source pixels: inside the frame, w, h >= 1
+ *   mirror         per eye 0 / 1: output column X takes what column S0 - 1 - X takes without it (the reference flips, then crops: its x0' in flipped
+ *                  coordinates is x0 = W - x0' - w here)
+ * The arithmetic is fixed in integers (egotap_amd/spec.py resize_taps / resize_u8 restate it on the host; the results are equal bit for bit).  Along an
+ * axis of source length L the taps of output index X are n = max((2X + 1) L - S0, 0), i0 = n div 2S0, r = n mod 2S0, w1 = (r * 2048 + S0) div 2S0,
+ * w0 = 2048 - w1, i1 = min(i0 + 1, L - 1); the output byte is (sum_{a, b} wy_a wx_b p[y0 + iy_a][x0 + ix_b][c] + 2^21) >> 22: one rounding, within
+ * 0.5 + 510 / 4096 of exact bilinear interpolation.  w = h = S0 is an exact copy.
+ * Every refusal is EGOTAP_ERR_INVALID, by name and before any launch: null pointers, B <= 0, a rectangle outside the frame or empty, a misaligned
+ * base, a workspace that is too small, unbound parameters.
+ *
+ * egotap_rgb_u8_resize: the standalone operator, both eyes in one launch; out_left8 / out_right8 device uint8 [B, S0, S0, 3], 4-byte aligned, S0 a
+ *   positive multiple of 4 (at most 4096); the source frames may sit at any address.
+ * egotap_predict_pose_sensor_u8: egotap_predict_pose_rgb_u8 behind the resize -- rects 2 x 4 ints (left, right), mirrors 2 ints, host memory read
+ *   during the call; left8 / right8 4-byte aligned.  The resize runs chunk by chunk into a workspace slice of chunk*2*3*S0*S0 bytes which the byte source
+ *   then reads (the byte-source stems at sides 64 / 128, the converter elsewhere): same composition, hand-off, frozen arenas and refusals.  Workspace:
+ *   egotap_predict_pose_rgb_u8_workspace_bytes(B, chunk) plus exactly that slice (H and W do not change it).  The identity request (H = W = S0, full
+ *   rectangles, no mirror) reads the caller's frames in place and launches no resize. */
+int egotap_rgb_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rect_left, const int* rect_right, int mirror_left,
+                         int mirror_right, int S0, uint8_t* out_left8, uint8_t* out_right8, void* stream);
+int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, int B, int H, int W, int chunk, size_t* bytes);
+int egotap_predict_pose_sensor_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
+                                  const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

@@ -891,9 +891,35 @@ def gen_rgb_u8():
     print("rgb_u8_norm ok", table.shape, table.dtype, float(table.min()), float(table.max()))
 
 
+def gen_sensor_resize():
+    """the reference's own crop_resize_images (reprocess_egocap_data.py:72-88, do_crop=False) on a seeded synthetic 512 x 640 frame: only its
+    OUTPUT bytes are stored; the test regenerates the input from the seed.  reprocess_egocap_data.py is a script (it opens the dataset when it
+    is imported), so the one function definition is compiled from the file in place -- nothing of it is copied.  Its uint8 F.interpolate is a
+    two-pass fixed-point scheme; the pin needs it within 1.0 of float64 bilinear on this frame, asserted here and again in the test."""
+    import ast
+    path = os.path.join(REF, "reprocess_egocap_data.py")
+    tree = ast.parse(open(path).read(), path)
+    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "crop_resize_images"]
+    assert len(fn) == 1
+    ns = {"torch": torch, "np": np}
+    exec(compile(ast.Module(body=fn, type_ignores=[]), path, "exec"), ns)
+    g = torch.Generator().manual_seed(20261018)
+    x = torch.randint(0, 256, (1, 512, 640, 3), generator=g, dtype=torch.uint8)
+    out = ns["crop_resize_images"](None, x.permute(0, 3, 1, 2).contiguous().numpy(), do_crop=False)
+    assert out.dtype == np.uint8 and out.shape == (1, 3, 256, 256)
+    exact = torch.nn.functional.interpolate(x.permute(0, 3, 1, 2).double(), size=(256, 256), mode="bilinear", align_corners=False)
+    err = float((torch.from_numpy(out).double() - exact).abs().max())
+    assert err <= 1.0, err
+    from egotap_amd import spec
+    ours = spec.resize_u8(x, None, False, 256).permute(0, 3, 1, 2)
+    d = (ours.to(torch.int16) - torch.from_numpy(out).to(torch.int16)).abs()
+    np.savez_compressed(os.path.join(GOLD, "sensor_resize_ref.npz"), out=out)
+    print("sensor_resize ok", out.shape, "reference vs float64", err, "ours vs reference: max", int(d.max()), "differing bytes", int((d != 0).sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,train_dhm,sched,synth,hmtrain,wrapper,wrapper_rgb,rgb_u8")
+    ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,train_dhm,sched,synth,hmtrain,wrapper,wrapper_rgb,rgb_u8,sensor_resize")
     args = ap.parse_args()
     which = set(args.only.split(","))
     os.makedirs(GOLD, exist_ok=True)
@@ -930,6 +956,8 @@ def main():
         gen_wrapper_rgb()
     if "rgb_u8" in which:
         gen_rgb_u8()
+    if "sensor_resize" in which:
+        gen_sensor_resize()
     if "wrapper_spread" in which:      # (not in the default set: six reference wrapper runs, ~10 min)
         gen_wrapper_spread()
 

@@ -1,0 +1,132 @@
+"""Times "sensor frames in, pose out" with and without the sensor entry, both arms in ONE process, alternating rounds:
+
+    python tools/time_predict_sensor.py [--batches 1,8,64] [--sources 1024x1024,512x640] [--reps 20] [--rounds 3] [--json OUT] [--md OUT]
+    rocprofv3 --kernel-trace --stats -- python tools/time_predict_sensor.py --once        # one call per arm: the resize kernel's duration
+
+Both arms start from the same sensor frames uint8 [B, H, W, 3] x 2 ON THE DEVICE and end with the pose on the device (wall clock around call +
+synchronize, median of --reps calls per round):
+  A    what a caller does today: torch crop, flip of the right eye, permute to NCHW float, F.interpolate(bilinear, align_corners=False) to 4S,
+       round to bytes, permute back to HWC, predict_pose_from_camera
+  B    predict_pose_from_sensor(crop=..., mirror_right=True)
+The two arms do not give equal bits (A rounds a float interpolation, B is the integer arithmetic of spec.resize_u8); the largest byte difference
+between their resized frames is reported (at most 1 is expected from the bound 0.5 + 510 / 4096).  Configurations: bf16 frozen and fp32."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from egotap_amd import lib as L  # noqa: E402
+from egotap_amd import spec  # noqa: E402
+from tools.time_predict_camera import build_model, configure  # noqa: E402
+
+
+def sensor_frames(B, H, W):
+    g = torch.Generator().manual_seed(B + H + W)
+    return [torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8).cuda() for _ in range(2)]
+
+
+def centre_crop(H, W):
+    side = min(H, W)
+    return ((W - side) // 2, (H - side) // 2, side, side)
+
+
+def host_way(x8, rect, flip, S0):
+    """arm A's resize: crop, flip, F.interpolate in fp32, round to bytes"""
+    x0, y0, w, h = rect
+    x = x8[:, y0:y0 + h, x0:x0 + w, :]
+    if flip:
+        x = x.flip(2)
+    y = F.interpolate(x.permute(0, 3, 1, 2).float(), size=(S0, S0), mode="bilinear", align_corners=False)
+    return y.round().clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def arms(m, rect, S0):
+    def a(l8, r8):
+        return m.predict_pose_from_camera(host_way(l8, rect, False, S0), host_way(r8, rect, True, S0))
+
+    def b(l8, r8):
+        return m.predict_pose_from_sensor(l8, r8, crop=rect, mirror_right=True)
+    return {"A": a, "B": b}
+
+
+def timed(fn, l, r, reps):
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn(l, r)
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,8,64")
+    ap.add_argument("--sources", default="1024x1024,512x640")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--once", action="store_true", help="one call per arm at B = 64 from 1024 x 1024, and the operator alone (for a kernel trace)")
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--md", default=None, help="write the table as markdown (profiles/predict_sensor_summary.md)")
+    args = ap.parse_args()
+    m = build_model()
+    S0 = 4 * m.net_AutoEncoder.preset.hm_size
+    if args.once:
+        l8, r8 = sensor_frames(64, 1024, 1024)
+        for mode in ("bf16_frozen", "f32"):
+            configure(m, mode, 64)
+            f = arms(m, centre_crop(1024, 1024), S0)
+            for name in ("A", "B", "A", "B"):
+                f[name](l8, r8)
+            torch.cuda.synchronize()
+        for _ in range(3):
+            L.rgb_u8_resize(l8, r8, S0, mirror_right=True)
+        torch.cuda.synchronize()
+        print("once: done")
+        return
+    rows = []
+    for mode in ("bf16_frozen", "f32"):
+        for src in args.sources.split(","):
+            H, W = (int(v) for v in src.split("x"))
+            rect = centre_crop(H, W)
+            for B in [int(b) for b in args.batches.split(",")]:
+                l8, r8 = sensor_frames(B, H, W)
+                configure(m, mode, B)
+                f = arms(m, rect, S0)
+                ours = spec.resize_u8(r8, rect, True, S0)
+                dbyte = int((ours.to(torch.int16) - host_way(r8, rect, True, S0).to(torch.int16)).abs().max())
+                pa, pb = f["A"](l8, r8).clone(), f["B"](l8, r8).clone()
+                torch.cuda.synchronize()
+                dpose = float((pa - pb).abs().max())
+                for name in f:                                           # warm-up (workspaces grown)
+                    timed(f[name], l8, r8, 3)
+                per = {name: [] for name in f}
+                for _ in range(args.rounds):
+                    for name in f:                                       # alternating: A, B, A, B, ...
+                        per[name].append(timed(f[name], l8, r8, args.reps))
+                row = {"mode": mode, "source": f"{H}x{W}", "rect": list(rect), "batch": B, "max_byte_diff_A_B": dbyte, "max_abs_pose_A_minus_B": dpose,
+                       **{name: {"rounds_ms": [round(v, 4) for v in vs], "median_ms": round(statistics.median(vs), 4),
+                                 "spread_ms": round(max(vs) - min(vs), 4)} for name, vs in per.items()}}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    for path, text in ((args.json, json.dumps(rows, indent=1)),
+                       (args.md, "| mode | source | B | A: today's caller, ms (spread) | B: predict_pose_from_sensor, ms (spread) | max byte diff |\n|---|---|---|---|---|---|\n" +
+                        "".join(f"| {r['mode']} | {r['source']} | {r['batch']} | {r['A']['median_ms']} ({r['A']['spread_ms']}) | {r['B']['median_ms']} ({r['B']['spread_ms']}) | "
+                                f"{r['max_byte_diff_A_B']} |\n" for r in rows))):
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as fh:
+                fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
