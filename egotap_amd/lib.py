@@ -9,7 +9,7 @@ from . import build as _build
 
 ERR_NAMES = {1: "EGOTAP_ERR_INVALID", 2: "EGOTAP_ERR_HIP", 3: "EGOTAP_ERR_UNBOUND", 4: "EGOTAP_ERR_WORKSPACE"}
 NET_LIFT, NET_HM_POS, NET_HM_ROT = 0, 1, 2
-F32, I64 = 0, 1
+F32, I64, BF16 = 0, 1, 2                               # egotap.h EGOTAP_F32 / _I64 / _BF16
 PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}      # egotap.h EGOTAP_PREC_*
 ABI_VERSION = 2                                       # egotap.h EGOTAP_ABI_VERSION: what egotap_abi_version() of a matching library returns
 RGB_FORMS = {0: "none", 1: "heatmaps", 2: "scratch", 3: "handoff"}      # egotap_debug.h EGOTAP_RGB_FORM_*
@@ -54,6 +54,14 @@ _PROTOS = {
     "egotap_predict_pose_sensor_u8_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     "egotap_predict_pose_sensor_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # ---- 2D joints and confidences from the position heatmaps: the operator, and the one-call entries with a keypoints output last
+    "egotap_heatmap_peaks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_rgb_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p]),
+    "egotap_predict_pose_rgb_u8_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_size_t, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_sensor_u8_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -351,6 +359,40 @@ def rgb_u8_resize(left8, right8, S0, rect_left=None, rect_right=None, mirror_lef
         check(load().egotap_rgb_u8_resize(_ptr(left8), _ptr(right8), B, H, W, rl, rr, int(bool(mirror_left)), int(bool(mirror_right)), int(S0), _ptr(out_l),
                                           _ptr(out_r), _stream(left8.device)))
     return out_l, out_r
+
+
+def heatmap_peaks(hm, c0: int = 0, n=None, groups: int = 1, affine=None):
+    """2D joints and confidences of heatmaps (egotap_heatmap_peaks): hm [B, C, S, S], float32 or bfloat16 on the GPU -- estimator outputs or
+    ground-truth maps, also a dim-1 slice of a larger contiguous tensor (read in place) -> float32 [B, n, 4], per map c0 .. c0 + n - 1 (None: all
+    from c0 on) the record (x, y, score, index) of ``spec.heatmap_peaks_ref``, bit for bit.  ``affine``: [groups, 4] = (ax, bx, ay, by) for each
+    group of n / groups consecutive maps (None: heatmap pixels, centres at i + 0.5).  One launch."""
+    import torch
+    if not (torch.is_tensor(hm) and hm.is_cuda):
+        raise EgotapError("heatmap_peaks runs on the GPU only (no CPU fallback); move the maps to cuda")
+    if hm.dtype not in (torch.float32, torch.bfloat16):
+        raise EgotapError(f"heatmap_peaks takes float32 or bfloat16 maps, got {hm.dtype}")
+    if hm.dim() != 4 or hm.shape[2] != hm.shape[3]:
+        raise ValueError(f"heatmap_peaks: maps are [B, C, S, S], got {tuple(hm.shape)}")
+    B, Cn, S, _ = (int(v) for v in hm.shape)
+    n = Cn - c0 if n is None else int(n)
+    if c0 < 0 or n < 1 or c0 + n > Cn:
+        raise ValueError(f"heatmap_peaks: maps {c0} .. {c0 + n - 1} are not inside the {Cn} channels")
+    # what the kernel addresses: element (b, c, y, x) at b * image_stride + c * S*S + y * S + x, an image stride of any size (a channel slice)
+    if B > 0 and (hm.stride(3) != 1 or hm.stride(2) != S or hm.stride(1) != S * S or (B > 1 and hm.stride(0) < Cn * S * S)):
+        raise EgotapError("heatmap_peaks: the maps must be contiguous per image (a dim-1 slice of a contiguous tensor is; nothing is copied)")
+    aff = None
+    if affine is not None:
+        flat = [float(v) for row in affine for v in row]
+        if len(flat) != 4 * groups:
+            raise ValueError(f"heatmap_peaks: affine is [groups, 4] = (ax, bx, ay, by) per group, got {len(flat)} values for {groups} groups")
+        aff = (C.c_float * len(flat))(*flat)
+    out = torch.empty((B, n, 4), dtype=torch.float32, device=hm.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(hm.device):
+        check(load().egotap_heatmap_peaks(_ptr(hm), F32 if hm.dtype == torch.float32 else BF16, B, S, hm.stride(0) if B > 1 else Cn * S * S, int(c0), n,
+                                          int(groups), aff, _ptr(out), _stream(hm.device)))
+    return out
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

@@ -406,7 +406,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
         return _lib.RGB_FORMS[form.value]
 
     @torch.no_grad()
-    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False):
+    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None):
         """Serving entry: stereo RGB [B, 3, 4S, 4S] x 2 -> pose [B, J(+1), 3], or (pose, heatmaps [B, 6J, S, S]) with ``return_heatmaps``.
         Replaces set_input() + evaluate() (utils/evaluate.py:104-114 without the metrics; egotap_autoencoder_model.py:177-223) for a caller
         that has no ground truth: no set_input, no loader keys, no autograd.  ONE library call (egotap_predict_pose_rgb): both estimators in
@@ -416,9 +416,14 @@ class EgoTAPAutoEncoderModel(nn.Module):
         arenas.  Without ``return_heatmaps`` in "bf16" precision at sides 64 / 128 the fp32 heatmaps are never written: conv_heatmap hands
         the head its bf16 operand directly (same pose bits; ``rgb_form()`` tells).
 
-        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps), with static input
-        and output buffers as ``net_AutoEncoder.predict_pose_graphed``: the returned tensors are the graph's own (valid until the next call
-        with the same key).
+        ``return_keypoints``: also the 2D joints and confidences, float32 [B, 2, J, 4] (eye, joint, (x, y, score, index)) -- the peaks of the 2J
+        position heatmaps (``lib.heatmap_peaks``, ``spec.heatmap_peaks_ref``) in pixels of the 4S x 4S input frame, appended to the result:
+        (pose, keypoints) or (pose, heatmaps, keypoints).  One more launch inside the same library call (egotap_predict_pose_rgb_kp), reading the
+        heatmaps in whichever form the call holds them, so the bf16 hand-off stays on; the pose bits do not change.
+
+        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps, return_keypoints), with
+        static input and output buffers as ``net_AutoEncoder.predict_pose_graphed``: the returned tensors are the graph's own (valid until the
+        next call with the same key).
 
         By name, not through the one call: resnet50 / resnet101 estimators (no one-call forward), estimators with different backbones and
         networks set to different precisions run the existing module forwards (``forward_into`` x 2, chunked) followed by
@@ -451,41 +456,24 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 for lo in range(0, B, chunk):
                     net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
             pose = self.net_AutoEncoder.predict_pose(cat)
-            return (pose, cat) if return_heatmaps else pose
-        pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
-        hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
-        if B == 0:
-            return (pose, hm) if return_heatmaps else pose
+            kp = None
+            if return_keypoints:
+                kp = _lib.heatmap_peaks(cat, 0, 2 * J, groups=2, affine=_keypoint_affine or [(4.0, 0.0, 4.0, 0.0)] * 2).view(B, 2, J, 4)
+            return self._served(pose, cat if return_heatmaps else None, kp)
         lib = _lib.load()
-        with torch.cuda.device(dev):
-            st = self._rgb_state(dev)
-            self._rgb_attach_act_scratch(st, B, dev)
-            h = st.handle.h
-            need = _session.nbytes(lib.egotap_predict_pose_rgb_workspace_bytes, h, B, chunk)
 
-            def call(l, r, po, hmo, ws):
+        def launch(h, l, r, po, hmo, kp, chunk, ws):
+            if kp is None:
                 _lib.check(lib.egotap_predict_pose_rgb(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
-            if not graphed:
-                _session.grown(st, "ws", need, dev, drop_first=True)
-                st.chunk = chunk
-                call(left, right, pose, hm, st.ws)
-                return (pose, hm) if return_heatmaps else pose
-            # one graph per (batch, heatmaps wanted, precision, frozen arenas, bound tensors, chunk): every pointer a captured launch takes is baked
-            # in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch buffers and arenas alive
-            nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
-            key = (B, bool(return_heatmaps), st.precision, tuple(st.frozen), tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)),
-                   chunk, str(dev))
+            else:
+                _lib.check(lib.egotap_predict_pose_rgb_kp(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
+        return self._serve_one_call(left, right, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_workspace_bytes, launch)
 
-            def build():
-                s_l, s_r = left.clone(), right.clone()
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
-                keep = (ws, st.wscratch, st.ascratch) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
-                return (lambda: call(s_l, s_r, pose, hm, ws)), (s_l, s_r, pose, hm), keep
-            graph, (s_l, s_r, pose, hm), _ = _session.captured(st.graphs, key, build)
-            s_l.copy_(left)
-            s_r.copy_(right)
-            graph.replay()
-        return (pose, hm) if return_heatmaps else pose
+    @staticmethod
+    def _served(pose, hm, kp):
+        """what a serving entry returns: the pose alone, or the pose followed by the heatmaps and / or keypoints that were asked for"""
+        extra = tuple(t for t in (hm, kp) if t is not None)
+        return (pose,) + extra if extra else pose
 
     def camera_table(self, dev):
         """the fp32 [3, 256] value table of predict_pose_from_camera on `dev` (spec.rgb_u8_table; opt.rgb_mean / opt.rgb_std override the ImageNet
@@ -497,17 +485,18 @@ class EgoTAPAutoEncoderModel(nn.Module):
             hit = self._camera_table = (key, torch.from_numpy(_spec.rgb_u8_table(self.opt)).to(dev))
         return hit[1]
 
-    def _serve_one_call(self, left, right, B, dev, return_heatmaps, graphed, size_query, launch, kind=(), keep=()):
+    def _serve_one_call(self, left, right, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch, kind=(), keep=()):
         """The host side of a one-call serving entry on the serving handle: outputs, workspace (eager: the handle's grow-only one; graphed: the
         graph's own), capture and replay with static inputs of the frames' dtype.  ``size_query(h, B, chunk, &bytes)`` and
-        ``launch(h, left, right, pose, heatmaps, chunk, ws)`` are the entry's two ABI calls; ``kind`` extends the capture key, ``keep`` what a graph
-        must keep alive besides its own buffers."""
+        ``launch(h, left, right, pose, heatmaps, keypoints, chunk, ws)`` are the entry's two ABI calls (keypoints None: the entry without that
+        output); ``kind`` extends the capture key, ``keep`` what a graph must keep alive besides its own buffers."""
         p = self.net_AutoEncoder.preset
         chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
         pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
         hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
+        kp = torch.empty((B, 2, p.n_joints_hm, 4), dtype=torch.float32, device=dev) if return_keypoints else None
         if B == 0:
-            return (pose, hm) if return_heatmaps else pose
+            return self._served(pose, hm, kp)
         with torch.cuda.device(dev):
             st = self._rgb_state(dev)
             self._rgb_attach_act_scratch(st, B, dev)
@@ -516,30 +505,34 @@ class EgoTAPAutoEncoderModel(nn.Module):
             if not graphed:
                 _session.grown(st, "ws", need, dev, drop_first=True)
                 st.chunk = chunk
-                launch(h, left, right, pose, hm, chunk, st.ws)
-                return (pose, hm) if return_heatmaps else pose
+                launch(h, left, right, pose, hm, kp, chunk, st.ws)
+                return self._served(pose, hm, kp)
+            # one graph per (batch, heatmaps wanted, keypoints wanted, precision, frozen arenas, bound tensors, chunk, source): every pointer a captured
+            # launch takes is baked in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch
+            # buffers and arenas alive
             nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
-            key = (B, bool(return_heatmaps), st.precision, tuple(st.frozen), tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)),
-                   chunk, str(dev)) + tuple(kind)
+            key = (B, bool(return_heatmaps), bool(return_keypoints), st.precision, tuple(st.frozen),
+                   tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)), chunk, str(dev)) + tuple(kind)
 
             def build():
                 s_l, s_r = left.clone(), right.clone()
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
                 held = (ws, st.wscratch, st.ascratch) + tuple(keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
-                return (lambda: launch(h, s_l, s_r, pose, hm, chunk, ws)), (s_l, s_r, pose, hm), held
-            graph, (s_l, s_r, pose, hm), _ = _session.captured(st.graphs, key, build)
+                return (lambda: launch(h, s_l, s_r, pose, hm, kp, chunk, ws)), (s_l, s_r, pose, hm, kp), held
+            graph, (s_l, s_r, pose, hm, kp), _ = _session.captured(st.graphs, key, build)
             s_l.copy_(left)
             s_r.copy_(right)
             graph.replay()
-        return (pose, hm) if return_heatmaps else pose
+        return self._served(pose, hm, kp)
 
     @torch.no_grad()
-    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False):
+    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None):
         """predict_pose_from_rgb from what a camera delivers: stereo frames uint8 [B, 4S, 4S, 3] (HWC, RGB order, already at 4S x 4S) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_rgb_u8) on the serving handle of
         predict_pose_from_rgb: the caller's astype(float32) / 255, normalisation, HWC -> CHW and the four-fold upload are gone -- at sides 64 / 128
         the stem kernels look every byte up in a 768-entry table (``camera_table``) while they stage it; at other sides the library converts chunk
-        by chunk into a workspace slice.  The bits are those of predict_pose_from_rgb on the gathered frames table[c][byte].
+        by chunk into a workspace slice.  The bits are those of predict_pose_from_rgb on the gathered frames table[c][byte].  ``return_keypoints``: as
+        predict_pose_from_rgb, in pixels of the 4S x 4S frame (egotap_predict_pose_rgb_u8_kp).
 
         ``graphed``: as predict_pose_from_rgb, with static BYTE inputs; the capture key also holds the source kind and the table, so the two entries
         never share a graph.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions) run
@@ -553,16 +546,20 @@ class EgoTAPAutoEncoderModel(nn.Module):
             if graphed:
                 raise _lib.EgotapError(f"predict_pose_from_camera(graphed=True): {why}; this configuration runs the converter and the module forwards, ungraphed")
             left, right = _lib.rgb_u8_to_f32(left8, right8, table)
-            return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps)
+            return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=_keypoint_affine)
         lib = _lib.load()
 
-        def launch(h, l, r, po, hmo, chunk, ws):
-            _lib.check(lib.egotap_predict_pose_rgb_u8(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
-        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
+        def launch(h, l, r, po, hmo, kp, chunk, ws):
+            if kp is None:
+                _lib.check(lib.egotap_predict_pose_rgb_u8(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
+            else:
+                _lib.check(lib.egotap_predict_pose_rgb_u8_kp(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
+        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
                                     kind=("u8", table.data_ptr()), keep=(table,))
 
     @torch.no_grad()
-    def predict_pose_from_sensor(self, left8, right8, crop=None, crop_right=None, mirror_right=False, return_heatmaps=False, graphed=False):
+    def predict_pose_from_sensor(self, left8, right8, crop=None, crop_right=None, mirror_right=False, return_heatmaps=False, graphed=False,
+                                 return_keypoints=False):
         """predict_pose_from_camera from the sensor's own frames: stereo uint8 [B, H, W, 3] (HWC, RGB, any H x W, the same for both eyes) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_sensor_u8) on the serving handle:
         the caller's crop, flip, F.interpolate and round to bytes are gone -- the library resizes chunk by chunk into a workspace slice
@@ -574,6 +571,9 @@ class EgoTAPAutoEncoderModel(nn.Module):
         (None: the same as ``crop``).  ``mirror_right``: the right eye's output column X takes what column 4S - 1 - X takes without it.  The
         reference flips the second camera's frame and THEN crops (reprocess_egocap_data.py:100-104, :221): its rectangle x0' in flipped
         coordinates is x0 = W - x0' - w here.  Frames already 4S x 4S with the full rectangle and no mirror are read in place.
+
+        ``return_keypoints``: as predict_pose_from_rgb, but in pixels of each eye's SENSOR frame (egotap_predict_pose_sensor_u8_kp): the inverse of the
+        resize's map, per eye from its own rectangle and mirror flag (``spec.sensor_keypoint_affine``).
 
         ``graphed``: as predict_pose_from_camera; the capture key holds the source kind, H, W, the rectangles, the mirror flags and the table, so
         no graph is shared with the other entries.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions)
@@ -590,7 +590,8 @@ class EgoTAPAutoEncoderModel(nn.Module):
             if graphed:
                 raise _lib.EgotapError(f"predict_pose_from_sensor(graphed=True): {why}; this configuration runs the resize, the converter and the module forwards, ungraphed")
             l8, r8 = _lib.rgb_u8_resize(left8, right8, S0, rect_l, rect_r, False, bool(mirror_right))
-            return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps)
+            affine = [_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)]
+            return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=affine)
         table = self.camera_table(dev)
         lib = _lib.load()
         rects, flags = (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors)
@@ -598,9 +599,14 @@ class EgoTAPAutoEncoderModel(nn.Module):
         def size_query(h, b, chunk, out):
             return lib.egotap_predict_pose_sensor_u8_workspace_bytes(h, b, H, W, chunk, out)
 
-        def launch(h, l, r, po, hmo, chunk, ws):
-            _lib.check(lib.egotap_predict_pose_sensor_u8(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
-        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, graphed, size_query, launch,
+        def launch(h, l, r, po, hmo, kp, chunk, ws):
+            if kp is None:
+                _lib.check(lib.egotap_predict_pose_sensor_u8(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
+                                                             stream(dev)))
+            else:
+                _lib.check(lib.egotap_predict_pose_sensor_u8_kp(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
+                                                                stream(dev), ptr(kp)))
+        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch,
                                     kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,))
 
     def rgb_intermediate(self, name: str, B: int):

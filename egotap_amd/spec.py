@@ -336,3 +336,75 @@ def resize_u8(frames, rect, mirror: bool, S0: int):
             acc += rows[:, :, x0 + ix].to(torch.int64) * (wy.view(1, S0, 1, 1) * wx.view(1, 1, S0, 1))
     out = ((acc + (1 << 21)) >> 22).to(torch.uint8)
     return out.numpy() if is_np else out
+
+
+# ---- heatmaps -> 2D joints and confidences (egotap.h: egotap_heatmap_peaks / egotap_predict_pose_*_kp) ----------------------------------
+def _fma_f32(a, x, b):
+    """float32(a * x + b) with ONE rounding, for float32 arrays: the product is exact in float64, the sum is rounded to odd there (TwoSum gives its
+    error), so the final rounding to float32 sees the exact sum's side of every tie -- what fmaf computes."""
+    import numpy as np
+    p = a.astype(np.float64) * x.astype(np.float64)
+    b = b.astype(np.float64)
+    s = p + b
+    bb = s - p
+    err = (p - (s - bb)) + (b - bb)
+    even = (s.view(np.int64) & 1) == 0
+    s = np.where((err != 0) & even & np.isfinite(s), np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def sensor_keypoint_affine(rect, mirror: bool, S: int):
+    """(ax, bx, ay, by) as float32: heatmap pixels (side S, pixel centres at i + 0.5) -> pixels of the sensor frame the eye's rectangle
+    (x0, y0, w, h) was cut from -- the inverse of ``resize_u8``'s map (align_corners=False).  With ``mirror`` output column X shows what
+    column 4S - 1 - X shows without it, so x runs backwards from the rectangle's right edge."""
+    import numpy as np
+    x0, y0, w, h = (int(v) for v in rect)
+    sx = np.float32(w) / np.float32(S)
+    return (np.float32(-sx if mirror else sx), np.float32(x0 + (w if mirror else 0)), np.float32(h) / np.float32(S), np.float32(y0))
+
+
+def heatmap_peaks_ref(hm, groups: int = 1, affine=None):
+    """The record egotap_heatmap_peaks writes, restated in numpy: hm [B, n, S, S] (float32, or anything exactly representable in it -- bf16
+    values upcast) -> float32 [B, n, 4] = (x, y, score, index) per map.
+
+        index = iy * S + ix   the maximum's position: values compared as float32, a larger value wins, among equal values the smallest linear
+                              index; a NaN never beats a number (the maximum starts at -inf: a map may be all negative); only NaNs -> 0
+        score = hm[iy][ix]
+        x     = ix + 0.5 + 0.25 * sgn(hm[iy][ix + 1] - hm[iy][ix - 1])      0 step when a neighbour is outside the map or the difference is 0 / NaN
+        y     = iy + 0.5 + 0.25 * sgn(hm[iy + 1][ix] - hm[iy - 1][ix])
+
+    The reference's target (utils/projection.py:263-279) puts its delta at int(x): a joint in [ix, ix + 1) peaks at ix, so ix + 0.5 is the unbiased
+    read-out; the quarter-pixel step towards the higher neighbour is the usual one of heatmap estimators.  ``affine``: [groups, 4] = (ax, bx, ay, by)
+    for each group of n / groups consecutive channels, x_out = fma(ax, x, bx), y_out = fma(ay, y, by) in float32 (None: identity).  Every step is
+    exact or a single float32 rounding, so the result is defined bit for bit."""
+    import numpy as np
+    h = np.asarray(hm, dtype=np.float32)
+    if h.ndim != 4 or h.shape[2] != h.shape[3]:
+        raise ValueError(f"heatmap_peaks_ref: maps are [B, n, S, S], got {h.shape}")
+    B, n, S, _ = h.shape
+    if groups < 1 or n % groups:
+        raise ValueError(f"heatmap_peaks_ref: n = {n} is no multiple of groups = {groups}")
+    flat = h.reshape(B * n, S * S)
+    valid = ~np.isnan(flat)
+    top = np.where(valid, flat, -np.inf).max(axis=1, keepdims=True)
+    index = np.where(valid.any(axis=1), np.argmax(valid & (flat == top), axis=1), 0)        # (argmax of booleans: the first True)
+    iy, ix = index // S, index % S
+    rows = np.arange(B * n)
+    maps = flat.reshape(B * n, S, S)
+
+    def step(lo_ok, hi_ok, lo, hi):
+        with np.errstate(invalid="ignore"):
+            d = hi - lo                                                                     # (inf - inf = NaN: no step)
+        return np.where(lo_ok & hi_ok, np.float32(0.25) * np.sign(np.nan_to_num(d, nan=0.0, posinf=1.0, neginf=-1.0)), 0).astype(np.float32)
+    dx = step(ix > 0, ix < S - 1, maps[rows, iy, np.maximum(ix - 1, 0)], maps[rows, iy, np.minimum(ix + 1, S - 1)])
+    dy = step(iy > 0, iy < S - 1, maps[rows, np.maximum(iy - 1, 0), ix], maps[rows, np.minimum(iy + 1, S - 1), ix])
+    x = ix.astype(np.float32) + np.float32(0.5) + dx
+    y = iy.astype(np.float32) + np.float32(0.5) + dy
+    if affine is not None:
+        a = np.asarray(affine, dtype=np.float32)
+        if a.shape != (groups, 4):
+            raise ValueError(f"heatmap_peaks_ref: affine is [groups, 4] = (ax, bx, ay, by) per group, got {a.shape}")
+        a = np.tile(np.repeat(a, n // groups, axis=0), (B, 1))                              # one row per map
+        x, y = _fma_f32(a[:, 0], x, a[:, 1]), _fma_f32(a[:, 2], y, a[:, 3])
+    out = np.stack([x, y, flat[rows, index], index.astype(np.float32)], axis=1).astype(np.float32)
+    return out.reshape(B, n, 4)

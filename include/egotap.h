@@ -34,7 +34,7 @@ enum { EGOTAP_OK = 0, EGOTAP_ERR_INVALID = 1, EGOTAP_ERR_HIP = 2, EGOTAP_ERR_UNB
  * (model/egotap_autoencoder_model.py:109-111: net_AutoEncoder, net_HeatMap, net_RotHeatMap) */
 enum { EGOTAP_NET_LIFT = 0, EGOTAP_NET_HM_POS = 1, EGOTAP_NET_HM_ROT = 2, EGOTAP_NET_COUNT = 3 };
 
-enum { EGOTAP_F32 = 0, EGOTAP_I64 = 1 };
+enum { EGOTAP_F32 = 0, EGOTAP_I64 = 1, EGOTAP_BF16 = 2 };      /* (EGOTAP_BF16: egotap_heatmap_peaks' maps only; parameters are bound as F32 / I64) */
 
 /* Options that shape the networks; mirrors the reference flags
  * --joint_preset/--num_heatmap/--ae_hidden_size/--load_size_heatmap (options/base_options.py:52-66,
@@ -206,6 +206,44 @@ int egotap_rgb_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, int
 int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, int B, int H, int W, int chunk, size_t* bytes);
 int egotap_predict_pose_sensor_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
                                   const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- 2D joints and confidences from the position heatmaps (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * What a tracker wants of the maps is where each joint is in each eye's image and how sure the estimator is: the ground-truth maps
+ * (utils/projection.py:263-279 coord2d_to_heatmap) are unit-peak Gaussians for a joint in view and all zero for one out of view, so the peak value gates
+ * "this joint was not seen".  Each map is reduced to one 16-byte record of four floats (x, y, score, index):
+ *   index  iy * S + ix of the maximum.  Values are compared as fp32 (bf16 upcast exactly); a larger value wins, among equal values the smallest linear
+ *          index; a NaN never beats a number; a map may be all negative (the maximum starts at -inf); a map of only NaNs gives index 0
+ *   score  the element at index, as fp32
+ *   x      ix + 0.5 + 0.25 * sgn(h[iy][ix + 1] - h[iy][ix - 1]): the reference's target puts its delta at int(x), so a joint in [ix, ix + 1) peaks at ix
+ *          and ix + 0.5 is the unbiased read-out; the quarter-pixel step towards the higher neighbour is the usual one of heatmap estimators.  The step is
+ *          0 where a neighbour lies outside the map or the difference is zero or NaN.  y the same from the rows above and below.  Exact in fp32.
+ *   affine G groups of n / G consecutive channels, each (ax, bx, ay, by): x_out = fmaf(ax, x, bx), y_out = fmaf(ay, y, by).  NULL = identity:
+ *          heatmap-pixel units, pixel centres at i + 0.5.  The values are read during the call and passed to the kernel by value.
+ * Every record is defined bit for bit (egotap_amd/spec.py heatmap_peaks_ref restates it on the host).
+ *
+ * egotap_heatmap_peaks: the standalone operator; needs no handle, one launch on the caller's stream, allocates nothing.
+ *   hm     device, EGOTAP_F32 or EGOTAP_BF16, the lifting head's input layout: element (b, c, y, x) at b * image_stride + c * S*S + y * S + x (elements),
+ *          so a channel slice of a larger tensor is read in place; maps c0 .. c0 + n - 1 of each of the B images
+ *   peaks  device f32 [B, n, 4]
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL hm / peaks; B, n or groups <= 0; more than 32 groups; n % groups != 0; c0 < 0;
+ * image_stride < (c0 + n) * S*S or not a multiple of 16 bytes; S not a multiple of 16 or outside 16 .. 128; hm or peaks not 16-byte aligned; an unknown dtype.
+ *
+ * egotap_predict_pose_rgb_kp / _rgb_u8_kp / _sensor_u8_kp: the three one-call serving entries with one more output -- the same implementation, the parents
+ * are it with keypoints = NULL.  keypoints: device f32 [B, 2, n_joints_hm, 4] (eye, joint, record), the peaks of the 2J position channels (c0 = 0, n = 2J,
+ * groups = 2: one per eye) in ONE launch over the whole batch, after the last piece's estimators and before the head.  It reads the tensor the call
+ * holds anyway: the fp32 `heatmaps` output, the workspace copy without one, or on the hand-off route the head's bf16 operand -- so the hand-off stays on
+ * and the workspace sizes are the parents'.  Units: _rgb_kp and _rgb_u8_kp pixels of the S0 x S0 input frame (ax = ay = 4, bx = by = 0); _sensor_u8_kp
+ * pixels of that eye's SENSOR frame, the inverse of the resize's map: for the eye's rectangle (x0, y0, w, h), ax = w / S, bx = x0 (mirrored: ax = -w / S,
+ * bx = x0 + w), ay = h / S, by = y0, each rounded to fp32.  Further refusals (EGOTAP_ERR_INVALID, before any launch): a NULL keypoints, one that is not
+ * 16-byte aligned, one that overlaps pose or heatmaps. */
+int egotap_heatmap_peaks(const void* hm, int dtype, int B, int S, int64_t image_stride, int c0, int n, int groups, const float* affine, float* peaks,
+                         void* stream);
+int egotap_predict_pose_rgb_kp(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                               size_t ws_bytes, void* stream, float* keypoints);
+int egotap_predict_pose_rgb_u8_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
+                                  int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints);
+int egotap_predict_pose_sensor_u8_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
+                                     const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints);
 
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)

@@ -3,12 +3,16 @@ ONE process and interleaved:
 
     python tools/time_predict_rgb.py [--batches 1,8,64,256] [--settings bf16_frozen,f32] [--json OUT]
     python tools/time_predict_rgb.py --only handoff --batches 64       # one arm, a few calls: the run to put under a kernel trace
+    python tools/time_predict_rgb.py --arms no_heatmaps,keypoints,heatmaps_argmax        # some arms only
+    python tools/time_predict_rgb.py --kernel                          # heatmap_peaks_kernel alone: duration and bytes per second
 
 Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
   parent      chunked forward_into x 2 + net_AutoEncoder.predict_pose: three module calls per batch, the only serving route before this entry
   heatmaps    predict_pose_from_rgb(return_heatmaps=True): one library call, fp32 heatmaps written for the caller
   no_heatmaps predict_pose_from_rgb(): in bf16 the hand-off (conv_heatmap writes the head's bf16 operand), in fp32 the heatmaps stay in the workspace
   graphed     predict_pose_from_rgb(graphed=True): the same pipeline replayed from a captured graph (includes the copy into its static inputs)
+  keypoints   predict_pose_from_rgb(return_keypoints=True): the 2D joints and confidences from the same call
+  heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
 """
@@ -61,7 +65,15 @@ def arms_for(m, p, left, right):
                 net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
         return m.net_AutoEncoder.predict_pose(cat)
 
+    def heatmaps_argmax():
+        pose, hm = m.predict_pose_from_rgb(left, right, return_heatmaps=True)
+        flat = hm[:, :2 * p.n_joints_hm].flatten(2)
+        flat.amax(dim=2), flat.argmax(dim=2)
+        return pose
+
     return {"parent": parent,
+            "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
+            "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
             "graphed": lambda: m.predict_pose_from_rgb(left, right, graphed=True)}
@@ -89,14 +101,73 @@ def measure(arms, per, warmup=10, rounds=3):
     return {k: (sorted(v)[len(v) // 2], min(rmed[k]), max(rmed[k])) for k, v in every.items()}
 
 
+def time_kernel(batches, J=15, S=64, C_all=90):
+    """heatmap_peaks_kernel on its own, as the serving entries launch it (the 2J position maps of [B, 6J, S, S], two groups): launches back to back
+    between two device events, over enough distinct tensors that no launch finds its maps in the 256 MiB Infinity Cache; beside it the LayerNorm
+    kernel (the project's HBM yardstick) over as many bytes, timed the same way.  Bytes are the maps read (plus, for LayerNorm, the rows written)."""
+    from egotap_amd import lib as L
+    aff = [(4.0, 0.0, 4.0, 0.0)] * 2
+    rows = []
+    for B in batches:
+        for dtype in (torch.float32, torch.bfloat16):
+            esz = 4 if dtype == torch.float32 else 2
+            copies = max(2, -(-(600 << 20) // (B * C_all * S * S * esz)))
+            hms = [torch.randn((B, C_all, S, S), device="cuda").to(dtype) for _ in range(min(copies, 64))]
+            reps = max(len(hms), 200 // len(hms) * len(hms))
+            for t in hms:
+                L.heatmap_peaks(t, 0, 2 * J, groups=2, affine=aff)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(reps):
+                L.heatmap_peaks(hms[i % len(hms)], 0, 2 * J, groups=2, affine=aff)
+            b.record()
+            torch.cuda.synchronize()
+            us = a.elapsed_time(b) * 1e3 / reps
+            nbytes = B * 2 * J * S * S * esz
+            rows.append(dict(kernel="heatmap_peaks", B=B, dtype=str(dtype), us=us, bytes=nbytes, TBps=nbytes / us / 1e6, tensors=len(hms)))
+            print(f"heatmap_peaks B={B:<4d} {str(dtype):15s} {us:9.2f} us per launch   {nbytes / 1e6:8.2f} MB read   {nbytes / us / 1e6:6.3f} TB/s", flush=True)
+            del hms
+        n_rows = B * 2 * J * S * S // 1024
+        xs = [torch.randn((n_rows, 1024), device="cuda") for _ in range(max(2, min(64, -(-(600 << 20) // (n_rows * 4096)))))]
+        g, be = torch.ones(1024, device="cuda"), torch.zeros(1024, device="cuda")
+        reps = max(len(xs), 200 // len(xs) * len(xs))
+        for x in xs:
+            L.layernorm(x, g, be)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(reps):
+            L.layernorm(xs[i % len(xs)], g, be)
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) * 1e3 / reps
+        nbytes = 2 * n_rows * 4096
+        rows.append(dict(kernel="layernorm_f32", B=B, us=us, bytes=nbytes, TBps=nbytes / us / 1e6, tensors=len(xs)))
+        print(f"layernorm_f32 rows={n_rows:<7d} (the bytes of B={B})  {us:9.2f} us per launch (incl. its output allocation)   {nbytes / 1e6:8.2f} MB read + written   "
+              f"{nbytes / us / 1e6:6.3f} TB/s", flush=True)
+        del xs
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="1,8,64,256")
     ap.add_argument("--settings", default="bf16_frozen,f32")
     ap.add_argument("--only", default=None, help="run this arm alone, --calls times, untimed (for a kernel trace)")
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--arms", default=None, help="comma-separated arms to time (default: all); parent is always run once, as the pose every arm must equal")
+    ap.add_argument("--kernel", action="store_true", help="time heatmap_peaks_kernel alone (and the LayerNorm kernel over as many bytes), nothing else")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    if a.kernel:
+        res = {"device": torch.cuda.get_device_name(0), "kernel_rows": time_kernel([int(b) for b in a.batches.split(",")])}
+        print(json.dumps(res))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     m, p = build_model()
     res = {"device": torch.cuda.get_device_name(0), "rows": []}
     for setting in a.settings.split(","):
@@ -109,6 +180,8 @@ def main():
             left, right = frames(B)
             arms = arms_for(m, p, left, right)
             ref = arms["parent"]().clone()
+            if a.arms:
+                arms = {k: arms[k] for k in a.arms.split(",")}
             for k, fn in arms.items():                       # every arm computes the parent's pose, bit for bit
                 got = fn()
                 torch.cuda.synchronize()
@@ -123,7 +196,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints") else ""
                 print(f"{setting:12s} B={B:<4d} {k:12s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
