@@ -38,6 +38,7 @@
 #include "rgb_u8.h"
 #include "rgb_u8_resize.h"
 #include "heatmap_peaks.h"
+#include "limb_decode.h"
 
 // The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
 // inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
@@ -2184,8 +2185,10 @@ extern "C" int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, i
 // one chunk where the stems do not read bytes themselves); the argument checks that depend on the source are the entries' own
 // keypoints != nullptr (the _kp entries): the peaks of the 2J position maps, one launch over the batch between the estimators and the head, read
 // from whichever form of the heatmaps this call holds; kp_affine: 2 x 4 floats (left eye, right eye)
+// limbs != nullptr (the _kpl entries): the records of the 2J (cos, sin) pairs of the limb maps (limb_decode.h), one more launch right behind it on the
+// same tensor with the same affine
 static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& src, int B, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
-                                 void* stream, float* keypoints = nullptr, const float* kp_affine = nullptr) {
+                                 void* stream, float* keypoints = nullptr, const float* kp_affine = nullptr, float* limbs = nullptr) {
     static const char* const net_name[EGOTAP_NET_COUNT] = {"the lifting head", "the position estimator", "the limb estimator"};
     for (int net = 0; net < EGOTAP_NET_COUNT; ++net) {
         if ((net == EGOTAP_NET_LIFT ? lift_resolve(h) : hm_resolve(h, net)) != EGOTAP_OK) {
@@ -2268,44 +2271,60 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
         EGO_HIP(handoff ? heatmap_peaks_launch(hmb, B, S, img, 0, 2 * J, 2, kp_affine, keypoints, (hipStream_t)stream)
                         : heatmap_peaks_launch(hm, B, S, img, 0, 2 * J, 2, kp_affine, keypoints, (hipStream_t)stream));
     }
+    if (limbs) {
+        GemmTimer t(h, (hipStream_t)stream, "limb_decode", "limb_decode_kernel", 0.0);
+        EGO_HIP(handoff ? limb_decode_launch(hmb, B, S, img, 2 * J, J, 2, kp_affine, limbs, (hipStream_t)stream)
+                        : limb_decode_launch(hm, B, S, img, 2 * J, J, 2, kp_affine, limbs, (hipStream_t)stream));
+    }
     const int rc = lift_forward_impl(h, handoff ? nullptr : hm, B, pose, ws, w.HM, stream, true, who, hmb);
     if (rc != EGOTAP_OK) return rc;
     h->rgb_form = handoff ? EGOTAP_RGB_FORM_HANDOFF : heatmaps ? EGOTAP_RGB_FORM_HEATMAPS : EGOTAP_RGB_FORM_SCRATCH;
     return EGOTAP_OK;
 }
 
-// ---- the 2D keypoints of the one-call entries (heatmap_peaks.h): each entry below is ONE body serving the parent (kp = nullptr) and its _kp form
-// what the _kp entries refuse about their extra output, or nullptr; pose / heatmaps extents from the handle
-static const char* rgb_kp_refusal(const Handle* h, int B, const float* pose, const float* heatmaps, const float* kp) {
-    if (!kp) return "null keypoints (device f32 [B, 2, n_joints_hm, 4])";
+// ---- the 2D keypoints and limb records of the one-call entries (heatmap_peaks.h, limb_decode.h): each entry below is ONE body serving the parent (no
+// extra output), its _kp form (keypoints required) and its _kpl form (keypoints and limbs, either may be NULL)
+// what the entries refuse about their extra outputs, or nullptr; pose / heatmaps extents from the handle
+static const char* rgb_kp_refusal(const Handle* h, int B, const float* pose, const float* heatmaps, bool kp_required, const float* kp, const float* limbs) {
+    if (kp_required && !kp) return "null keypoints (device f32 [B, 2, n_joints_hm, 4])";
     if ((uintptr_t)kp & 15) return "keypoints must be 16-byte aligned";
+    if ((uintptr_t)limbs & 15) return "limbs must be 16-byte aligned";
     const int S = h->cfg.hm_size;
-    const uintptr_t k0 = (uintptr_t)kp, k1 = k0 + (size_t)B * 2 * h->J * 16;
-    auto overlaps = [&](const void* q, size_t bytes) { return q && k0 < (uintptr_t)q + bytes && (uintptr_t)q < k1; };
-    if (overlaps(pose, (size_t)B * h->out_joints * 3 * 4) || overlaps(heatmaps, (size_t)B * h->C * S * S * 4)) return "keypoints overlaps pose or heatmaps";
+    const size_t kp_bytes = (size_t)B * 2 * h->J * 16, limb_bytes = (size_t)B * 2 * h->J * 32;
+    auto overlaps = [](const void* p, size_t pn, const void* q, size_t qn) {
+        return p && q && (uintptr_t)p < (uintptr_t)q + qn && (uintptr_t)q < (uintptr_t)p + pn;
+    };
+    const size_t pose_bytes = (size_t)B * h->out_joints * 3 * 4, hm_bytes = (size_t)B * h->C * S * S * 4;
+    if (overlaps(kp, kp_bytes, pose, pose_bytes) || overlaps(kp, kp_bytes, heatmaps, hm_bytes)) return "keypoints overlaps pose or heatmaps";
+    if (overlaps(limbs, limb_bytes, pose, pose_bytes) || overlaps(limbs, limb_bytes, heatmaps, hm_bytes) || overlaps(limbs, limb_bytes, kp, kp_bytes))
+        return "limbs overlaps pose, heatmaps or keypoints";
     return nullptr;
 }
 static const float kRgbKpAffine[8] = {4.f, 0.f, 4.f, 0.f, 4.f, 0.f, 4.f, 0.f};      // heatmap pixels -> pixels of the S0 = 4 S input frame, both eyes
 
 static int predict_pose_rgb_entry(const char* who, egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
-                                  size_t ws_bytes, void* stream, bool kp, float* keypoints) {
+                                  size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
     EGO_CHECK(h, "%s: null handle", who);
     EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
     EGO_CHECK(left && right && pose && ws, "%s: null argument (left, right, pose and ws are required; only heatmaps may be NULL)", who);
     EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
     EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0,
               "%s: left, right, pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
-    const char* why = kp ? rgb_kp_refusal(h, B, pose, heatmaps, keypoints) : nullptr;
+    const char* why = rgb_kp_refusal(h, B, pose, heatmaps, kp, keypoints, limbs);
     EGO_CHECK(!why, "%s: %s", who, why);
-    return predict_pose_rgb_impl(who, h, hm_src_f32(left, right), B, pose, heatmaps, chunk, ws, ws_bytes, stream, kp ? keypoints : nullptr, kRgbKpAffine);
+    return predict_pose_rgb_impl(who, h, hm_src_f32(left, right), B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, kRgbKpAffine, limbs);
 }
 extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
                                        size_t ws_bytes, void* stream) {
-    return predict_pose_rgb_entry("egotap_predict_pose_rgb", h, left, right, B, pose, heatmaps, chunk, ws, ws_bytes, stream, false, nullptr);
+    return predict_pose_rgb_entry("egotap_predict_pose_rgb", h, left, right, B, pose, heatmaps, chunk, ws, ws_bytes, stream, false, nullptr, nullptr);
 }
 extern "C" int egotap_predict_pose_rgb_kp(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
                                           size_t ws_bytes, void* stream, float* keypoints) {
-    return predict_pose_rgb_entry("egotap_predict_pose_rgb_kp", h, left, right, B, pose, heatmaps, chunk, ws, ws_bytes, stream, true, keypoints);
+    return predict_pose_rgb_entry("egotap_predict_pose_rgb_kp", h, left, right, B, pose, heatmaps, chunk, ws, ws_bytes, stream, true, keypoints, nullptr);
+}
+extern "C" int egotap_predict_pose_rgb_kpl(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                                           size_t ws_bytes, void* stream, float* keypoints, float* limbs) {
+    return predict_pose_rgb_entry("egotap_predict_pose_rgb_kpl", h, left, right, B, pose, heatmaps, chunk, ws, ws_bytes, stream, false, keypoints, limbs);
 }
 
 // [r7] the same call from camera bytes: uint8 [B, S0, S0, 3] per eye and the fp32 [3][256] value table
@@ -2317,7 +2336,7 @@ extern "C" int egotap_predict_pose_rgb_u8_workspace_bytes(egotap_handle h, int B
     return EGOTAP_OK;
 }
 static int predict_pose_rgb_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose,
-                                     float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints) {
+                                     float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
     EGO_CHECK(h, "%s: null handle", who);
     EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
     const char* why = rgb_u8_refusal(left8, right8, table);
@@ -2325,18 +2344,24 @@ static int predict_pose_rgb_u8_entry(const char* who, egotap_handle h, const uin
     EGO_CHECK(pose && ws, "%s: null argument (pose and ws are required; only heatmaps may be NULL)", who);
     EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
     EGO_CHECK((((uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
-    why = kp ? rgb_kp_refusal(h, B, pose, heatmaps, keypoints) : nullptr;
+    why = rgb_kp_refusal(h, B, pose, heatmaps, kp, keypoints, limbs);
     EGO_CHECK(!why, "%s: %s", who, why);
     const HmSrc src{nullptr, nullptr, left8, right8, table, nullptr};
-    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, kp ? keypoints : nullptr, kRgbKpAffine);
+    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, kRgbKpAffine, limbs);
 }
 extern "C" int egotap_predict_pose_rgb_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
                                           int chunk, void* ws, size_t ws_bytes, void* stream) {
-    return predict_pose_rgb_u8_entry("egotap_predict_pose_rgb_u8", h, left8, right8, B, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false, nullptr);
+    return predict_pose_rgb_u8_entry("egotap_predict_pose_rgb_u8", h, left8, right8, B, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false, nullptr, nullptr);
 }
 extern "C" int egotap_predict_pose_rgb_u8_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
                                              int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints) {
-    return predict_pose_rgb_u8_entry("egotap_predict_pose_rgb_u8_kp", h, left8, right8, B, table, pose, heatmaps, chunk, ws, ws_bytes, stream, true, keypoints);
+    return predict_pose_rgb_u8_entry("egotap_predict_pose_rgb_u8_kp", h, left8, right8, B, table, pose, heatmaps, chunk, ws, ws_bytes, stream, true, keypoints,
+                                     nullptr);
+}
+extern "C" int egotap_predict_pose_rgb_u8_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
+                                              int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints, float* limbs) {
+    return predict_pose_rgb_u8_entry("egotap_predict_pose_rgb_u8_kpl", h, left8, right8, B, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false, keypoints,
+                                     limbs);
 }
 
 // ---- [r8] the sensor's own frames: crop, mirror and bilinear resize on the device (rgb_u8_resize.h), standalone and in front of the one call
@@ -2370,7 +2395,7 @@ extern "C" int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, in
 }
 static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
                                         const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
-                                        bool kp, float* keypoints) {
+                                        bool kp, float* keypoints, float* limbs) {
     EGO_CHECK(h, "%s: null handle", who);
     EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
     EGO_CHECK(rects && mirrors, "%s: null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)", who);
@@ -2390,7 +2415,7 @@ static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const 
     for (int e = 0; e < 2; ++e) identity = identity && q.rect[e][0] == 0 && q.rect[e][1] == 0 && q.rect[e][2] == S0 && q.rect[e][3] == S0;
     HmSrc src{nullptr, nullptr, identity ? left8 : nullptr, identity ? right8 : nullptr, table, nullptr};
     src.sensor = &q;
-    why = kp ? rgb_kp_refusal(h, B, pose, heatmaps, keypoints) : nullptr;
+    why = rgb_kp_refusal(h, B, pose, heatmaps, kp, keypoints, limbs);
     EGO_CHECK(!why, "%s: %s", who, why);
     // heatmap pixels -> pixels of the eye's sensor frame: the inverse of the map rgb_u8_resize_kernel applies (pixel centres at i + 0.5, align_corners =
     // False); a mirrored eye's output column X shows source column S0 - 1 - X, so its x runs backwards from the rectangle's right edge
@@ -2402,18 +2427,24 @@ static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const 
         affine[4 * e + 2] = (float)q.rect[e][3] / S;
         affine[4 * e + 3] = (float)q.rect[e][1];
     }
-    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, kp ? keypoints : nullptr, affine);
+    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
 }
 extern "C" int egotap_predict_pose_sensor_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
                                              const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {
     return predict_pose_sensor_u8_entry("egotap_predict_pose_sensor_u8", h, left8, right8, B, H, W, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes, stream,
-                                        false, nullptr);
+                                        false, nullptr, nullptr);
 }
 extern "C" int egotap_predict_pose_sensor_u8_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
                                                 const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
                                                 void* stream, float* keypoints) {
     return predict_pose_sensor_u8_entry("egotap_predict_pose_sensor_u8_kp", h, left8, right8, B, H, W, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes,
-                                        stream, true, keypoints);
+                                        stream, true, keypoints, nullptr);
+}
+extern "C" int egotap_predict_pose_sensor_u8_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
+                                                 const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
+                                                 void* stream, float* keypoints, float* limbs) {
+    return predict_pose_sensor_u8_entry("egotap_predict_pose_sensor_u8_kpl", h, left8, right8, B, H, W, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes,
+                                        stream, false, keypoints, limbs);
 }
 
 // the standalone operator: maps c0 .. c0 + n - 1 of each image of a [B, C, S, S] tensor -> [B, n, 4] records; no handle
@@ -2434,6 +2465,26 @@ extern "C" int egotap_heatmap_peaks(const void* hm, int dtype, int B, int S, int
     EGO_CHECK((((uintptr_t)hm | (uintptr_t)peaks) & 15) == 0, "%s: hm and peaks must be 16-byte aligned", who);
     EGO_HIP(dtype == EGOTAP_F32 ? heatmap_peaks_launch((const float*)hm, B, S, (long)image_stride, c0, n, groups, affine, peaks, (hipStream_t)stream)
                                 : heatmap_peaks_launch((const __bf16*)hm, B, S, (long)image_stride, c0, n, groups, affine, peaks, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+
+// the standalone operator: the n_limbs (cos, sin) pairs of each of `eyes` eyes of each image of a [B, C, S, S] tensor -> [B, eyes, n_limbs, 8] records; no handle
+extern "C" int egotap_limb_decode(const void* hm, int dtype, int B, int S, int64_t image_stride, int c0, int n_limbs, int eyes, const float* affine, float* limbs,
+                                  void* stream) {
+    static const char* const who = "egotap_limb_decode";
+    EGO_CHECK(hm && limbs, "%s: null argument (hm and limbs are required; only affine may be NULL)", who);
+    EGO_CHECK(dtype == EGOTAP_F32 || dtype == EGOTAP_BF16, "%s: unknown dtype %d (EGOTAP_F32 or EGOTAP_BF16)", who, dtype);
+    EGO_CHECK(B > 0 && n_limbs > 0, "%s: the batch and the number of limbs must be positive (B = %d, n_limbs = %d)", who, B, n_limbs);
+    EGO_CHECK(eyes > 0 && eyes <= kPeaksMaxGroups, "%s: eyes must be between 1 and %d (eyes = %d)", who, kPeaksMaxGroups, eyes);
+    EGO_CHECK(c0 >= 0, "%s: negative first channel (c0 = %d)", who, c0);
+    EGO_CHECK(S >= 16 && S <= 128 && S % 16 == 0, "%s: the side must be a multiple of 16 from 16 to 128 (S = %d)", who, S);
+    const int esz = dtype == EGOTAP_F32 ? 4 : 2;
+    const int64_t last = (c0 + 2 * (int64_t)eyes * n_limbs) * S * S;
+    EGO_CHECK(image_stride >= last, "%s: image_stride %lld is smaller than (c0 + 2 * eyes * n_limbs) * S*S = %lld", who, (long long)image_stride, (long long)last);
+    EGO_CHECK(image_stride * esz % 16 == 0, "%s: image_stride must be a multiple of 16 bytes (%lld elements of %d bytes)", who, (long long)image_stride, esz);
+    EGO_CHECK((((uintptr_t)hm | (uintptr_t)limbs) & 15) == 0, "%s: hm and limbs must be 16-byte aligned", who);
+    EGO_HIP(dtype == EGOTAP_F32 ? limb_decode_launch((const float*)hm, B, S, (long)image_stride, c0, n_limbs, eyes, affine, limbs, (hipStream_t)stream)
+                                : limb_decode_launch((const __bf16*)hm, B, S, (long)image_stride, c0, n_limbs, eyes, affine, limbs, (hipStream_t)stream));
     return EGOTAP_OK;
 }
 

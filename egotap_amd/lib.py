@@ -62,6 +62,14 @@ _PROTOS = {
                                                 C.c_size_t, C.c_void_p, C.c_void_p]),
     "egotap_predict_pose_sensor_u8_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    # ---- limb elevation angles and 2D segments from the sin/cos limb heatmaps: the operator, and the _kp entries with a limbs output last
+    "egotap_limb_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_rgb_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_rgb_u8_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_sensor_u8_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -392,6 +400,42 @@ def heatmap_peaks(hm, c0: int = 0, n=None, groups: int = 1, affine=None):
     with torch.cuda.device(hm.device):
         check(load().egotap_heatmap_peaks(_ptr(hm), F32 if hm.dtype == torch.float32 else BF16, B, S, hm.stride(0) if B > 1 else Cn * S * S, int(c0), n,
                                           int(groups), aff, _ptr(out), _stream(hm.device)))
+    return out
+
+
+def limb_decode(hm, c0: int, n_limbs: int, eyes: int = 2, affine=None):
+    """Limb elevation angles and 2D segments of sin/cos limb heatmaps (egotap_limb_decode): hm [B, C, S, S], float32 or bfloat16 on the GPU --
+    estimator outputs or ground-truth maps, also a dim-1 slice of a larger contiguous tensor (read in place) -> float32 [B, eyes, n_limbs, 8], per
+    (cos, sin) pair the record (theta, coherence, x, y, phi, length, peak, mass) of ``spec.limb_decode_ref``.  For eye e and limb l the cos map is
+    channel c0 + e * 2 n_limbs + l, the sin map channel c0 + e * 2 n_limbs + n_limbs + l.  ``affine``: [eyes, 4] = (ax, bx, ay, by) per eye
+    (None: heatmap pixels, centres at i + 0.5).  One launch."""
+    import torch
+    if not torch.is_tensor(hm):
+        raise EgotapError("limb_decode takes a torch tensor on the GPU")
+    if hm.dtype not in (torch.float32, torch.bfloat16):
+        raise EgotapError(f"limb_decode takes float32 or bfloat16 maps, got {hm.dtype}")
+    if hm.dim() != 4 or hm.shape[2] != hm.shape[3]:
+        raise ValueError(f"limb_decode: maps are [B, C, S, S], got {tuple(hm.shape)}")
+    B, Cn, S, _ = (int(v) for v in hm.shape)
+    c0, n_limbs, eyes = int(c0), int(n_limbs), int(eyes)
+    if c0 < 0 or n_limbs < 1 or eyes < 1 or c0 + 2 * eyes * n_limbs > Cn:
+        raise ValueError(f"limb_decode: channels {c0} .. {c0 + 2 * eyes * n_limbs - 1} (eyes x (cos, sin) x n_limbs) are not inside the {Cn} channels")
+    if B > 0 and (hm.stride(3) != 1 or hm.stride(2) != S or hm.stride(1) != S * S or (B > 1 and hm.stride(0) < Cn * S * S)):
+        raise EgotapError("limb_decode: the maps must be contiguous per image (a dim-1 slice of a contiguous tensor is; nothing is copied)")
+    aff = None
+    if affine is not None:
+        flat = [float(v) for row in affine for v in row]
+        if len(flat) != 4 * eyes:
+            raise ValueError(f"limb_decode: affine is [eyes, 4] = (ax, bx, ay, by) per eye, got {len(flat)} values for {eyes} eyes")
+        aff = (C.c_float * len(flat))(*flat)
+    if not hm.is_cuda:                                   # (after the argument checks, so those can be exercised without a GPU)
+        raise EgotapError("limb_decode runs on the GPU only (no CPU fallback); move the maps to cuda")
+    out = torch.empty((B, eyes, n_limbs, 8), dtype=torch.float32, device=hm.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(hm.device):
+        check(load().egotap_limb_decode(_ptr(hm), F32 if hm.dtype == torch.float32 else BF16, B, S, hm.stride(0) if B > 1 else Cn * S * S, c0, n_limbs, eyes,
+                                        aff, _ptr(out), _stream(hm.device)))
     return out
 
 

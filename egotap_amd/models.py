@@ -406,7 +406,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
         return _lib.RGB_FORMS[form.value]
 
     @torch.no_grad()
-    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None):
+    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False):
         """Serving entry: stereo RGB [B, 3, 4S, 4S] x 2 -> pose [B, J(+1), 3], or (pose, heatmaps [B, 6J, S, S]) with ``return_heatmaps``.
         Replaces set_input() + evaluate() (utils/evaluate.py:104-114 without the metrics; egotap_autoencoder_model.py:177-223) for a caller
         that has no ground truth: no set_input, no loader keys, no autograd.  ONE library call (egotap_predict_pose_rgb): both estimators in
@@ -421,7 +421,12 @@ class EgoTAPAutoEncoderModel(nn.Module):
         (pose, keypoints) or (pose, heatmaps, keypoints).  One more launch inside the same library call (egotap_predict_pose_rgb_kp), reading the
         heatmaps in whichever form the call holds them, so the bf16 hand-off stays on; the pose bits do not change.
 
-        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps, return_keypoints), with
+        ``return_limbs``: also each limb's elevation angle and 2D segment per eye, float32 [B, 2, J, 8] (eye, limb, (theta, coherence, x, y, phi,
+        length, peak, mass)) -- the 2J (cos, sin) pairs of the limb heatmaps decoded (``lib.limb_decode``, ``spec.limb_decode_ref``), (x, y), phi and
+        length in the keypoints' units, appended after the keypoints.  One more launch inside the same library call (egotap_predict_pose_rgb_kpl)
+        on the same tensor; the hand-off stays on, the other outputs keep their bits.
+
+        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps, return_keypoints, return_limbs), with
         static input and output buffers as ``net_AutoEncoder.predict_pose_graphed``: the returned tensors are the graph's own (valid until the
         next call with the same key).
 
@@ -456,23 +461,29 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 for lo in range(0, B, chunk):
                     net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
             pose = self.net_AutoEncoder.predict_pose(cat)
-            kp = None
+            kp = lb = None
+            affine = _keypoint_affine or [(4.0, 0.0, 4.0, 0.0)] * 2
             if return_keypoints:
-                kp = _lib.heatmap_peaks(cat, 0, 2 * J, groups=2, affine=_keypoint_affine or [(4.0, 0.0, 4.0, 0.0)] * 2).view(B, 2, J, 4)
-            return self._served(pose, cat if return_heatmaps else None, kp)
+                kp = _lib.heatmap_peaks(cat, 0, 2 * J, groups=2, affine=affine).view(B, 2, J, 4)
+            if return_limbs:
+                lb = _lib.limb_decode(cat, 2 * J, J, eyes=2, affine=affine)
+            return self._served(pose, cat if return_heatmaps else None, kp, lb)
         lib = _lib.load()
 
-        def launch(h, l, r, po, hmo, kp, chunk, ws):
-            if kp is None:
+        def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
+            if lb is not None:
+                _lib.check(lib.egotap_predict_pose_rgb_kpl(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp), ptr(lb)))
+            elif kp is None:
                 _lib.check(lib.egotap_predict_pose_rgb(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
             else:
                 _lib.check(lib.egotap_predict_pose_rgb_kp(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
-        return self._serve_one_call(left, right, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_workspace_bytes, launch)
+        return self._serve_one_call(left, right, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_workspace_bytes, launch,
+                                    return_limbs=return_limbs)
 
     @staticmethod
-    def _served(pose, hm, kp):
-        """what a serving entry returns: the pose alone, or the pose followed by the heatmaps and / or keypoints that were asked for"""
-        extra = tuple(t for t in (hm, kp) if t is not None)
+    def _served(pose, hm, kp, lb=None):
+        """what a serving entry returns: the pose alone, or the pose followed by the heatmaps, keypoints and / or limb records that were asked for"""
+        extra = tuple(t for t in (hm, kp, lb) if t is not None)
         return (pose,) + extra if extra else pose
 
     def camera_table(self, dev):
@@ -485,18 +496,19 @@ class EgoTAPAutoEncoderModel(nn.Module):
             hit = self._camera_table = (key, torch.from_numpy(_spec.rgb_u8_table(self.opt)).to(dev))
         return hit[1]
 
-    def _serve_one_call(self, left, right, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch, kind=(), keep=()):
+    def _serve_one_call(self, left, right, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch, kind=(), keep=(), return_limbs=False):
         """The host side of a one-call serving entry on the serving handle: outputs, workspace (eager: the handle's grow-only one; graphed: the
         graph's own), capture and replay with static inputs of the frames' dtype.  ``size_query(h, B, chunk, &bytes)`` and
-        ``launch(h, left, right, pose, heatmaps, keypoints, chunk, ws)`` are the entry's two ABI calls (keypoints None: the entry without that
-        output); ``kind`` extends the capture key, ``keep`` what a graph must keep alive besides its own buffers."""
+        ``launch(h, left, right, pose, heatmaps, keypoints, limbs, chunk, ws)`` are the entry's two ABI calls (keypoints / limbs None: the entry
+        without that output); ``kind`` extends the capture key, ``keep`` what a graph must keep alive besides its own buffers."""
         p = self.net_AutoEncoder.preset
         chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
         pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
         hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
         kp = torch.empty((B, 2, p.n_joints_hm, 4), dtype=torch.float32, device=dev) if return_keypoints else None
+        lb = torch.empty((B, 2, p.n_joints_hm, 8), dtype=torch.float32, device=dev) if return_limbs else None
         if B == 0:
-            return self._served(pose, hm, kp)
+            return self._served(pose, hm, kp, lb)
         with torch.cuda.device(dev):
             st = self._rgb_state(dev)
             self._rgb_attach_act_scratch(st, B, dev)
@@ -505,34 +517,35 @@ class EgoTAPAutoEncoderModel(nn.Module):
             if not graphed:
                 _session.grown(st, "ws", need, dev, drop_first=True)
                 st.chunk = chunk
-                launch(h, left, right, pose, hm, kp, chunk, st.ws)
-                return self._served(pose, hm, kp)
-            # one graph per (batch, heatmaps wanted, keypoints wanted, precision, frozen arenas, bound tensors, chunk, source): every pointer a captured
+                launch(h, left, right, pose, hm, kp, lb, chunk, st.ws)
+                return self._served(pose, hm, kp, lb)
+            # one graph per (batch, heatmaps wanted, keypoints wanted, limbs wanted, precision, frozen arenas, bound tensors, chunk, source): every pointer a captured
             # launch takes is baked in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch
             # buffers and arenas alive
             nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
-            key = (B, bool(return_heatmaps), bool(return_keypoints), st.precision, tuple(st.frozen),
+            key = (B, bool(return_heatmaps), bool(return_keypoints), bool(return_limbs), st.precision, tuple(st.frozen),
                    tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)), chunk, str(dev)) + tuple(kind)
 
             def build():
                 s_l, s_r = left.clone(), right.clone()
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
                 held = (ws, st.wscratch, st.ascratch) + tuple(keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
-                return (lambda: launch(h, s_l, s_r, pose, hm, kp, chunk, ws)), (s_l, s_r, pose, hm, kp), held
-            graph, (s_l, s_r, pose, hm, kp), _ = _session.captured(st.graphs, key, build)
+                return (lambda: launch(h, s_l, s_r, pose, hm, kp, lb, chunk, ws)), (s_l, s_r, pose, hm, kp, lb), held
+            graph, (s_l, s_r, pose, hm, kp, lb), _ = _session.captured(st.graphs, key, build)
             s_l.copy_(left)
             s_r.copy_(right)
             graph.replay()
-        return self._served(pose, hm, kp)
+        return self._served(pose, hm, kp, lb)
 
     @torch.no_grad()
-    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None):
+    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False):
         """predict_pose_from_rgb from what a camera delivers: stereo frames uint8 [B, 4S, 4S, 3] (HWC, RGB order, already at 4S x 4S) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_rgb_u8) on the serving handle of
         predict_pose_from_rgb: the caller's astype(float32) / 255, normalisation, HWC -> CHW and the four-fold upload are gone -- at sides 64 / 128
         the stem kernels look every byte up in a 768-entry table (``camera_table``) while they stage it; at other sides the library converts chunk
         by chunk into a workspace slice.  The bits are those of predict_pose_from_rgb on the gathered frames table[c][byte].  ``return_keypoints``: as
-        predict_pose_from_rgb, in pixels of the 4S x 4S frame (egotap_predict_pose_rgb_u8_kp).
+        predict_pose_from_rgb, in pixels of the 4S x 4S frame (egotap_predict_pose_rgb_u8_kp).  ``return_limbs``: as predict_pose_from_rgb
+        (egotap_predict_pose_rgb_u8_kpl).
 
         ``graphed``: as predict_pose_from_rgb, with static BYTE inputs; the capture key also holds the source kind and the table, so the two entries
         never share a graph.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions) run
@@ -546,20 +559,24 @@ class EgoTAPAutoEncoderModel(nn.Module):
             if graphed:
                 raise _lib.EgotapError(f"predict_pose_from_camera(graphed=True): {why}; this configuration runs the converter and the module forwards, ungraphed")
             left, right = _lib.rgb_u8_to_f32(left8, right8, table)
-            return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=_keypoint_affine)
+            return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=_keypoint_affine,
+                                              return_limbs=return_limbs)
         lib = _lib.load()
 
-        def launch(h, l, r, po, hmo, kp, chunk, ws):
-            if kp is None:
+        def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
+            if lb is not None:
+                _lib.check(lib.egotap_predict_pose_rgb_u8_kpl(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp),
+                                                              ptr(lb)))
+            elif kp is None:
                 _lib.check(lib.egotap_predict_pose_rgb_u8(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
             else:
                 _lib.check(lib.egotap_predict_pose_rgb_u8_kp(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
         return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
-                                    kind=("u8", table.data_ptr()), keep=(table,))
+                                    kind=("u8", table.data_ptr()), keep=(table,), return_limbs=return_limbs)
 
     @torch.no_grad()
     def predict_pose_from_sensor(self, left8, right8, crop=None, crop_right=None, mirror_right=False, return_heatmaps=False, graphed=False,
-                                 return_keypoints=False):
+                                 return_keypoints=False, return_limbs=False):
         """predict_pose_from_camera from the sensor's own frames: stereo uint8 [B, H, W, 3] (HWC, RGB, any H x W, the same for both eyes) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_sensor_u8) on the serving handle:
         the caller's crop, flip, F.interpolate and round to bytes are gone -- the library resizes chunk by chunk into a workspace slice
@@ -573,7 +590,9 @@ class EgoTAPAutoEncoderModel(nn.Module):
         coordinates is x0 = W - x0' - w here.  Frames already 4S x 4S with the full rectangle and no mirror are read in place.
 
         ``return_keypoints``: as predict_pose_from_rgb, but in pixels of each eye's SENSOR frame (egotap_predict_pose_sensor_u8_kp): the inverse of the
-        resize's map, per eye from its own rectangle and mirror flag (``spec.sensor_keypoint_affine``).
+        resize's map, per eye from its own rectangle and mirror flag (``spec.sensor_keypoint_affine``).  ``return_limbs``: as predict_pose_from_rgb,
+        (x, y), phi and length in the same sensor pixels (egotap_predict_pose_sensor_u8_kpl); a rectangle whose w / S and h / S differ bends phi
+        and length (the blur is no longer isotropic in the output frame).
 
         ``graphed``: as predict_pose_from_camera; the capture key holds the source kind, H, W, the rectangles, the mirror flags and the table, so
         no graph is shared with the other entries.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions)
@@ -591,7 +610,8 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 raise _lib.EgotapError(f"predict_pose_from_sensor(graphed=True): {why}; this configuration runs the resize, the converter and the module forwards, ungraphed")
             l8, r8 = _lib.rgb_u8_resize(left8, right8, S0, rect_l, rect_r, False, bool(mirror_right))
             affine = [_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)]
-            return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=affine)
+            return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=affine,
+                                                 return_limbs=return_limbs)
         table = self.camera_table(dev)
         lib = _lib.load()
         rects, flags = (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors)
@@ -599,15 +619,18 @@ class EgoTAPAutoEncoderModel(nn.Module):
         def size_query(h, b, chunk, out):
             return lib.egotap_predict_pose_sensor_u8_workspace_bytes(h, b, H, W, chunk, out)
 
-        def launch(h, l, r, po, hmo, kp, chunk, ws):
-            if kp is None:
+        def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
+            if lb is not None:
+                _lib.check(lib.egotap_predict_pose_sensor_u8_kpl(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
+                                                                 stream(dev), ptr(kp), ptr(lb)))
+            elif kp is None:
                 _lib.check(lib.egotap_predict_pose_sensor_u8(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
                                                              stream(dev)))
             else:
                 _lib.check(lib.egotap_predict_pose_sensor_u8_kp(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
                                                                 stream(dev), ptr(kp)))
         return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch,
-                                    kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,))
+                                    kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), return_limbs=return_limbs)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

@@ -408,3 +408,59 @@ def heatmap_peaks_ref(hm, groups: int = 1, affine=None):
         x, y = _fma_f32(a[:, 0], x, a[:, 1]), _fma_f32(a[:, 2], y, a[:, 3])
     out = np.stack([x, y, flat[rows, index], index.astype(np.float32)], axis=1).astype(np.float32)
     return out.reshape(B, n, 4)
+
+
+# ---- sin/cos limb heatmaps -> elevation angles and 2D segments (egotap.h: egotap_limb_decode / egotap_predict_pose_*_kpl) ------------------
+def limb_decode_ref(hm, c0: int, n_limbs: int, eyes: int, affine=None):
+    """The record egotap_limb_decode writes, restated in float64 numpy: hm [B, C, S, S] (float32, or anything exactly representable in it -- bf16
+    values upcast) -> float32 [B, eyes, n_limbs, 8] = (theta, coherence, x, y, phi, length, peak, mass) per (cos, sin) pair.  For eye e and limb l
+    the cos map c is channel c0 + e * 2 n_limbs + l and the sin map s channel c0 + e * 2 n_limbs + n_limbs + l (the reference's cat(cos, sin) per
+    eye).  Every sum runs over all S*S pixels in float64, pixel centres at ix + 0.5, iy + 0.5:
+
+        m = sqrt(c^2 + s^2)   M = sum m   C = sum c   Sn = sum s   X = sum m x   Y = sum m y   XX = sum m x^2   YY = sum m y^2   XY = sum m x y
+        peak      = max m                      a NaN never wins; starts at 0
+        theta     = atan2(Sn, C)               exact for a target pair: both maps are the same non-negative map times sin / cos theta
+        coherence = hypot(C, Sn) / M           in [0, 1]; 1 when every pixel votes for the same angle
+        x, y      = ax * X/M + bx, ay * Y/M + by                                     the eye's affine (ax, bx, ay, by); None: identity
+        mu20 = XX/M - (X/M)^2, mu02 = YY/M - (Y/M)^2, mu11 = XY/M - (X/M)(Y/M), scaled by ax^2, ay^2, ax ay;   D = (mu20' - mu02')^2 + 4 mu11'^2
+        phi       = atan2(2 mu11', mu20' - mu02') / 2                                the segment's orientation in the output frame, in (-pi/2, pi/2]
+        length    = sqrt(12 sqrt(D))           a uniform segment of length l blurred by an isotropic sigma has variance l^2/12 + sigma^2 along its
+                                               axis and sigma^2 across it: the eigenvalues differ by sqrt(D), the blur drops out (exact for |ax| = |ay|)
+        mass      = M
+
+    The segment's ends are (x, y) +- length / 2 * (cos phi, sin phi).  theta is an angle of the pose's own frame: the affine does not touch it.
+    Empty rule, when not (M > 0) or M is not finite (an all-zero pair, a NaN or inf inside): theta = coherence = phi = length = 0, (x, y) the
+    affine of the map centre (S/2, S/2), peak as computed, mass = float32(M).  Each value is rounded once from float64."""
+    import numpy as np
+    h = np.asarray(hm, dtype=np.float32)
+    if h.ndim != 4 or h.shape[2] != h.shape[3]:
+        raise ValueError(f"limb_decode_ref: maps are [B, C, S, S], got {h.shape}")
+    B, Cn, S, _ = h.shape
+    if c0 < 0 or n_limbs < 1 or eyes < 1 or c0 + 2 * eyes * n_limbs > Cn:
+        raise ValueError(f"limb_decode_ref: channels {c0} .. {c0 + 2 * eyes * n_limbs - 1} are not inside the {Cn} channels")
+    a = np.tile(np.array([1.0, 0.0, 1.0, 0.0]), (eyes, 1)) if affine is None else np.asarray(affine, dtype=np.float32).astype(np.float64)
+    if a.shape != (eyes, 4):
+        raise ValueError(f"limb_decode_ref: affine is [eyes, 4] = (ax, bx, ay, by) per eye, got {a.shape}")
+    pairs = h[:, c0:c0 + 2 * eyes * n_limbs].astype(np.float64).reshape(B, eyes, 2, n_limbs, S, S)
+    c, s = pairs[:, :, 0], pairs[:, :, 1]                                                   # [B, eyes, n_limbs, S, S]
+    x = (np.arange(S) + 0.5).reshape(1, 1, 1, 1, S)
+    y = (np.arange(S) + 0.5).reshape(1, 1, 1, S, 1)
+    ax, bx, ay, by = (a[:, k].reshape(1, eyes, 1) for k in range(4))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = np.sqrt(c * c + s * s)
+        mx, my = m * x, m * y
+        M, C, Sn, X, Y, XX, YY, XY = (t.sum(axis=(3, 4)) for t in (m, c, s, mx, my, mx * x, my * y, mx * y))
+        peak = np.where(np.isnan(m), 0.0, m).max(axis=(3, 4))
+        full = (M > 0) & np.isfinite(M)
+        Md = np.where(full, M, 1.0)
+        xb = np.where(full, X / Md, 0.5 * S)
+        yb = np.where(full, Y / Md, 0.5 * S)
+        m20, m02, m11 = (XX / Md - xb * xb) * (ax * ax), (YY / Md - yb * yb) * (ay * ay), (XY / Md - xb * yb) * (ax * ay)
+        d = m20 - m02
+        D = d * d + 4.0 * (m11 * m11)
+        rec = [np.arctan2(Sn, C), np.hypot(C, Sn) / Md, ax * xb + bx, ay * yb + by,
+               0.5 * np.arctan2(2.0 * m11 + 0.0, d),                                        # (+ 0.0: a -0 numerator would turn pi/2 into -pi/2)
+               np.sqrt(12.0 * np.sqrt(D)), peak, M]
+        for k in (0, 1, 4, 5):
+            rec[k] = np.where(full, rec[k], 0.0)
+        return np.stack(np.broadcast_arrays(*rec), axis=-1).astype(np.float32)

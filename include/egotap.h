@@ -245,6 +245,53 @@ int egotap_predict_pose_rgb_u8_kp(egotap_handle h, const uint8_t* left8, const u
 int egotap_predict_pose_sensor_u8_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
                                      const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints);
 
+/* ---- limb elevation angles and 2D segments from the sin/cos limb heatmaps (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * The reference draws each target limb map as the anti-aliased segment parent -> joint, Gaussian-blurred and doubled, and multiplies it by cos(theta) and by
+ * sin(theta), theta = arctan(dz / |dxy|) the limb's elevation out of the image plane (utils/data.py:197-252, dataloader/data_loader.py:193-199).  Each
+ * (cos, sin) pair of maps c, s of side S is reduced to one 32-byte record of eight floats (theta, coherence, x, y, phi, length, peak, mass).  Values are
+ * fp32 (bf16 upcast exactly); every sum runs over all S*S pixels in float64; pixel centres sit at ix + 0.5, iy + 0.5:
+ *   m = sqrt(c^2 + s^2)   M = sum m   C = sum c   Sn = sum s   X = sum m x   Y = sum m y   XX = sum m x^2   YY = sum m y^2   XY = sum m x y
+ *   theta      atan2(Sn, C), radians: exact for a target pair (both maps are the same non-negative map times sin / cos theta).  An angle of the pose's own
+ *              frame: the affine and the mirror do not touch it
+ *   coherence  hypot(C, Sn) / M, in [0, 1]: 1 when every pixel votes for the same angle
+ *   x, y       ax * X/M + bx, ay * Y/M + by: the mass centre under the eye's affine (ax, bx, ay, by)
+ *   phi        atan2(2 mu11', mu20' - mu02') / 2 in (-pi/2, pi/2]: the segment's orientation in the output frame, from the central moments
+ *              mu20 = XX/M - (X/M)^2, mu02 = YY/M - (Y/M)^2, mu11 = XY/M - (X/M)(Y/M) scaled by ax^2, ay^2, ax ay
+ *   length     sqrt(12 sqrt(D)), D = (mu20' - mu02')^2 + 4 mu11'^2: a uniform segment of length l blurred by an isotropic sigma has variance
+ *              l^2/12 + sigma^2 along its axis and sigma^2 across it; the difference of the two eigenvalues is sqrt(D), so the blur drops out.  Exact when
+ *              |ax| = |ay|: a non-uniform sensor crop makes the blur anisotropic in the output frame and bends phi and length
+ *   peak       max m (a NaN never wins; starts at 0)
+ *   mass       (float)M
+ * The segment's ends are (x, y) +- length / 2 * (cos phi, sin phi).  Empty rule, when !(M > 0) or M is not finite (an all-zero pair, a NaN or inf
+ * inside): theta = coherence = phi = length = 0, (x, y) the affine of the map centre (S/2, S/2), peak as computed, mass = (float)M.  A limb out of view has
+ * all-zero target maps, so mass and peak gate "not seen" the way the keypoint score does.  Each value is rounded once from float64
+ * (egotap_amd/spec.py limb_decode_ref restates the record on the host; the order of the sums differs, so the two agree to rounding, not in bits).
+ *
+ * egotap_limb_decode: the standalone operator; needs no handle, one launch on the caller's stream, allocates nothing.
+ *   hm      device, EGOTAP_F32 or EGOTAP_BF16, the layout of egotap_heatmap_peaks.  For eye e and limb l the cos map is channel c0 + e * 2 n_limbs + l, the
+ *           sin map channel c0 + e * 2 n_limbs + n_limbs + l: the reference's cat(cos, sin) per eye
+ *   affine  host, [eyes, 4] = (ax, bx, ay, by) per eye; NULL = identity.  Read during the call and passed to the kernel by value
+ *   limbs   device f32 [B, eyes, n_limbs, 8]
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL hm / limbs; B, n_limbs or eyes <= 0; more than 32 eyes; c0 < 0;
+ * image_stride < (c0 + 2 eyes n_limbs) * S*S or not a multiple of 16 bytes; S not a multiple of 16 or outside 16 .. 128; hm or limbs not 16-byte aligned;
+ * an unknown dtype.
+ *
+ * egotap_predict_pose_rgb_kpl / _rgb_u8_kpl / _sensor_u8_kpl: the three _kp entries with one more trailing output -- the same implementation.  Either of
+ * keypoints / limbs may be NULL; with both NULL the call is the parent.  limbs: device f32 [B, 2, n_joints_hm, 8] (eye, limb, record), the records of the
+ * 4J limb channels (c0 = 2J, n_limbs = J, eyes = 2) in ONE launch over the whole batch right after the keypoint launch, on the same tensor (the fp32
+ * `heatmaps` output, the workspace copy, or on the hand-off route the head's bf16 operand: the hand-off stays on, the workspace sizes are the parents')
+ * and with the keypoints' affine, so (x, y), phi and length are in the keypoints' units.  Further refusals (EGOTAP_ERR_INVALID, before any launch): a
+ * keypoints or limbs that is not 16-byte aligned, keypoints overlapping pose or heatmaps, limbs overlapping pose, heatmaps or keypoints. */
+int egotap_limb_decode(const void* hm, int dtype, int B, int S, int64_t image_stride, int c0, int n_limbs, int eyes, const float* affine, float* limbs,
+                       void* stream);
+int egotap_predict_pose_rgb_kpl(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                                size_t ws_bytes, void* stream, float* keypoints, float* limbs);
+int egotap_predict_pose_rgb_u8_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose, float* heatmaps,
+                                   int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints, float* limbs);
+int egotap_predict_pose_sensor_u8_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
+                                      const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints,
+                                      float* limbs);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

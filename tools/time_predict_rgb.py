@@ -4,7 +4,8 @@ ONE process and interleaved:
     python tools/time_predict_rgb.py [--batches 1,8,64,256] [--settings bf16_frozen,f32] [--json OUT]
     python tools/time_predict_rgb.py --only handoff --batches 64       # one arm, a few calls: the run to put under a kernel trace
     python tools/time_predict_rgb.py --arms no_heatmaps,keypoints,heatmaps_argmax        # some arms only
-    python tools/time_predict_rgb.py --kernel                          # heatmap_peaks_kernel alone: duration and bytes per second
+    python tools/time_predict_rgb.py --kernel                          # heatmap_peaks_kernel and limb_decode_kernel alone: duration and bytes per second
+                                                                       # 
 
 Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
   parent      chunked forward_into x 2 + net_AutoEncoder.predict_pose: three module calls per batch, the only serving route before this entry
@@ -12,6 +13,7 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
   no_heatmaps predict_pose_from_rgb(): in bf16 the hand-off (conv_heatmap writes the head's bf16 operand), in fp32 the heatmaps stay in the workspace
   graphed     predict_pose_from_rgb(graphed=True): the same pipeline replayed from a captured graph (includes the copy into its static inputs)
   keypoints   predict_pose_from_rgb(return_keypoints=True): the 2D joints and confidences from the same call
+  limbs       predict_pose_from_rgb(return_limbs=True): the limb elevation angles and 2D segments from the same call
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -73,6 +75,7 @@ def arms_for(m, p, left, right):
 
     return {"parent": parent,
             "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
+            "limbs": lambda: m.predict_pose_from_rgb(left, right, return_limbs=True)[0],
             "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
@@ -104,7 +107,9 @@ def measure(arms, per, warmup=10, rounds=3):
 def time_kernel(batches, J=15, S=64, C_all=90):
     """heatmap_peaks_kernel on its own, as the serving entries launch it (the 2J position maps of [B, 6J, S, S], two groups): launches back to back
     between two device events, over enough distinct tensors that no launch finds its maps in the 256 MiB Infinity Cache; beside it the LayerNorm
-    kernel (the project's HBM yardstick) over as many bytes, timed the same way.  Bytes are the maps read (plus, for LayerNorm, the rows written)."""
+    kernel (the project's HBM yardstick) over as many bytes, timed the same way.  Bytes are the maps read (plus, for LayerNorm, the rows written).
+    limb_decode_kernel the same way over the 4J limb maps of the same tensors (c0 = 2J, J limbs, two eyes), and beside it heatmap_peaks_kernel over those
+    same 4J maps: the same bytes through both kernels."""
     from egotap_amd import lib as L
     aff = [(4.0, 0.0, 4.0, 0.0)] * 2
     rows = []
@@ -114,19 +119,22 @@ def time_kernel(batches, J=15, S=64, C_all=90):
             copies = max(2, -(-(600 << 20) // (B * C_all * S * S * esz)))
             hms = [torch.randn((B, C_all, S, S), device="cuda").to(dtype) for _ in range(min(copies, 64))]
             reps = max(len(hms), 200 // len(hms) * len(hms))
-            for t in hms:
-                L.heatmap_peaks(t, 0, 2 * J, groups=2, affine=aff)
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for i in range(reps):
-                L.heatmap_peaks(hms[i % len(hms)], 0, 2 * J, groups=2, affine=aff)
-            b.record()
-            torch.cuda.synchronize()
-            us = a.elapsed_time(b) * 1e3 / reps
-            nbytes = B * 2 * J * S * S * esz
-            rows.append(dict(kernel="heatmap_peaks", B=B, dtype=str(dtype), us=us, bytes=nbytes, TBps=nbytes / us / 1e6, tensors=len(hms)))
-            print(f"heatmap_peaks B={B:<4d} {str(dtype):15s} {us:9.2f} us per launch   {nbytes / 1e6:8.2f} MB read   {nbytes / us / 1e6:6.3f} TB/s", flush=True)
+            for name, maps, fn in (("heatmap_peaks", 2 * J, lambda t: L.heatmap_peaks(t, 0, 2 * J, groups=2, affine=aff)),
+                                   ("limb_decode", 4 * J, lambda t: L.limb_decode(t, 2 * J, J, eyes=2, affine=aff)),
+                                   ("heatmap_peaks_limb_maps", 4 * J, lambda t: L.heatmap_peaks(t, 2 * J, 4 * J, groups=2, affine=aff))):
+                for t in hms:
+                    fn(t)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for i in range(reps):
+                    fn(hms[i % len(hms)])
+                b.record()
+                torch.cuda.synchronize()
+                us = a.elapsed_time(b) * 1e3 / reps
+                nbytes = B * maps * S * S * esz
+                rows.append(dict(kernel=name, B=B, dtype=str(dtype), us=us, bytes=nbytes, TBps=nbytes / us / 1e6, tensors=len(hms)))
+                print(f"{name:23s} B={B:<4d} {str(dtype):15s} {us:9.2f} us per launch   {nbytes / 1e6:8.2f} MB read   {nbytes / us / 1e6:6.3f} TB/s", flush=True)
             del hms
         n_rows = B * 2 * J * S * S // 1024
         xs = [torch.randn((n_rows, 1024), device="cuda") for _ in range(max(2, min(64, -(-(600 << 20) // (n_rows * 4096)))))]
@@ -158,7 +166,7 @@ def main():
     ap.add_argument("--only", default=None, help="run this arm alone, --calls times, untimed (for a kernel trace)")
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--arms", default=None, help="comma-separated arms to time (default: all); parent is always run once, as the pose every arm must equal")
-    ap.add_argument("--kernel", action="store_true", help="time heatmap_peaks_kernel alone (and the LayerNorm kernel over as many bytes), nothing else")
+    ap.add_argument("--kernel", action="store_true", help="time heatmap_peaks_kernel and limb_decode_kernel alone (and the LayerNorm kernel over as many bytes), nothing else")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.kernel:
@@ -196,7 +204,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs") else ""
                 print(f"{setting:12s} B={B:<4d} {k:12s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
