@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -39,6 +40,7 @@
 #include "rgb_u8_resize.h"
 #include "heatmap_peaks.h"
 #include "limb_decode.h"
+#include "ocam.h"
 
 // The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
 // inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
@@ -183,6 +185,9 @@ struct egotap_handle_s {
     std::string detail;           // JSON written by egotap_timing_read
 };
 typedef egotap_handle_s Handle;
+// the handle whose timing hook was enabled last: where the operators that take no handle (ocam.h) record their launches; cleared when that handle's hook is
+// switched off or the handle is destroyed
+[[maybe_unused]] static Handle* g_timing_handle = nullptr;
 
 static int isqrt_floor(int v) {
     int r = 0;
@@ -318,6 +323,7 @@ extern "C" int egotap_create(const egotap_config* cfg, egotap_handle* out) {
 #if EGOTAP_IN(0)
 extern "C" void egotap_destroy(egotap_handle h) {
     if (!h) return;
+    if (g_timing_handle == h) g_timing_handle = nullptr;
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->pu_fault_host) (void)hipHostFree(h->pu_fault_host);
     delete h;
@@ -439,6 +445,8 @@ static int lift_resolve(Handle* h) {
 extern "C" int egotap_timing_enable(egotap_handle h, int enable) {
     EGO_CHECK(h, "null handle");
     h->timing = enable != 0;
+    if (h->timing) g_timing_handle = h;
+    else if (g_timing_handle == h) g_timing_handle = nullptr;
     return EGOTAP_OK;
 }
 #endif
@@ -2485,6 +2493,88 @@ extern "C" int egotap_limb_decode(const void* hm, int dtype, int B, int S, int64
     EGO_CHECK((((uintptr_t)hm | (uintptr_t)limbs) & 15) == 0, "%s: hm and limbs must be 16-byte aligned", who);
     EGO_HIP(dtype == EGOTAP_F32 ? limb_decode_launch((const float*)hm, B, S, (long)image_stride, c0, n_limbs, eyes, affine, limbs, (hipStream_t)stream)
                                 : limb_decode_launch((const __bf16*)hm, B, S, (long)image_stride, c0, n_limbs, eyes, affine, limbs, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+
+// ---- the fisheye camera model and the stereo triangulation of the keypoints (ocam.h): three operators, no handle
+static bool ego_finite(double v) { return std::isfinite(v); }
+// what is wrong with a camera model, or nullptr
+static const char* ocam_refusal(const egotap_ocam* m) {
+    if (!m) return "null camera model";
+    if (m->n_pol < 1 || m->n_pol > EGOTAP_OCAM_MAX_POL) return "polynomialC2W (n_pol) must have 1 .. 8 coefficients";
+    if (m->n_invpol < 1 || m->n_invpol > EGOTAP_OCAM_MAX_INVPOL) return "polynomialW2C (n_invpol) must have 1 .. 24 coefficients";
+    bool fin = ego_finite(m->xc) && ego_finite(m->yc) && ego_finite(m->c) && ego_finite(m->d) && ego_finite(m->e);
+    for (int k = 0; k < m->n_pol; ++k) fin = fin && ego_finite(m->pol[k]);
+    for (int k = 0; k < m->n_invpol; ++k) fin = fin && ego_finite(m->invpol[k]);
+    if (!fin) return "a calibration value is not finite";
+    if (m->ue_flip != 0.0 && m->ue_flip != 1.0) return "ue_flip must be 0 or 1";
+    if (m->c - m->d * m->e == 0.0) return "the affine is singular (c - d * e == 0)";
+    return nullptr;
+}
+// the model as the kernels take it: the coefficients behind the lengths are zero, whatever the caller left there
+static egotap_ocam ocam_clean(const egotap_ocam& m) {
+    egotap_ocam o = m;
+    for (int k = m.n_pol; k < EGOTAP_OCAM_MAX_POL; ++k) o.pol[k] = 0.0;
+    for (int k = m.n_invpol; k < EGOTAP_OCAM_MAX_INVPOL; ++k) o.invpol[k] = 0.0;
+    return o;
+}
+static bool ego_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    return p && q && (uintptr_t)p < (uintptr_t)q + qn && (uintptr_t)q < (uintptr_t)p + pn;
+}
+
+static int ocam_points_entry(const char* who, bool project, const float* in, int N, const egotap_ocam* model, float* out, void* stream) {
+    const char* in_name = project ? "points3d" : "points2d";
+    const char* out_name = project ? "points2d" : "rays";
+    EGO_CHECK(in && out, "%s: null argument (%s and %s are required)", who, in_name, out_name);
+    EGO_CHECK(N > 0, "%s: the number of points must be positive (N = %d)", who, N);
+    EGO_CHECK((((uintptr_t)in | (uintptr_t)out) & 3) == 0, "%s: %s and %s must be 4-byte aligned", who, in_name, out_name);
+    const char* why = ocam_refusal(model);
+    EGO_CHECK(!why, "%s: model: %s", who, why);
+    const size_t in_bytes = (size_t)N * (project ? 3 : 2) * 4, out_bytes = (size_t)N * (project ? 2 : 3) * 4;
+    EGO_CHECK(!ego_overlap(in, in_bytes, out, out_bytes), "%s: %s overlaps %s", who, out_name, in_name);
+    const egotap_ocam m = ocam_clean(*model);
+    GemmTimer t(g_timing_handle, (hipStream_t)stream, project ? "ocam_project" : "ocam_unproject", project ? "ocam_project_kernel" : "ocam_unproject_kernel", 0.0);
+    EGO_HIP(project ? ocam_project_launch(in, N, m, out, (hipStream_t)stream) : ocam_unproject_launch(in, N, m, out, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_ocam_project(const float* points3d, int N, const egotap_ocam* model, float* points2d, void* stream) {
+    return ocam_points_entry("egotap_ocam_project", true, points3d, N, model, points2d, stream);
+}
+extern "C" int egotap_ocam_unproject(const float* points2d, int N, const egotap_ocam* model, float* rays, void* stream) {
+    return ocam_points_entry("egotap_ocam_unproject", false, points2d, N, model, rays, stream);
+}
+
+extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
+                                         const double* affine, double min_score, const float* pose, int P, int pose_row0, float* joints3d, float* frame,
+                                         void* stream) {
+    static const char* const who = "egotap_stereo_triangulate";
+    EGO_CHECK(keypoints && t && joints3d && frame, "%s: null argument (keypoints, t, joints3d and frame are required; R, affine and pose may be NULL)", who);
+    EGO_CHECK(B > 0 && J > 0, "%s: the batch and the number of joints must be positive (B = %d, J = %d)", who, B, J);
+    EGO_CHECK(J <= kStereoMaxJoints, "%s: at most %d joints, one lane each (J = %d)", who, kStereoMaxJoints, J);
+    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)joints3d | (uintptr_t)frame) & 15) == 0 && ((uintptr_t)pose & 3) == 0,
+              "%s: keypoints, joints3d and frame must be 16-byte aligned, pose 4-byte aligned", who);
+    const char* why = ocam_refusal(left);
+    EGO_CHECK(!why, "%s: left: %s", who, why);
+    why = ocam_refusal(right);
+    EGO_CHECK(!why, "%s: right: %s", who, why);
+    if (pose) EGO_CHECK(pose_row0 >= 0 && (int64_t)pose_row0 + J <= P, "%s: pose rows pose_row0 .. pose_row0 + J - 1 = %d .. %lld are not inside the P = %d rows", who,
+                        pose_row0, (long long)pose_row0 + J - 1, P);
+    StereoRig rig;
+    rig.cam[0] = ocam_clean(*left);
+    rig.cam[1] = ocam_clean(*right);
+    bool fin = ego_finite(min_score);
+    for (int k = 0; k < 9; ++k) fin = fin && ego_finite(rig.R[k] = R ? R[k] : (k % 4 == 0 ? 1.0 : 0.0));
+    for (int k = 0; k < 3; ++k) fin = fin && ego_finite(rig.t[k] = t[k]);
+    for (int k = 0; k < 8; ++k) fin = fin && ego_finite(rig.aff[k / 4][k % 4] = affine ? affine[k] : (k & 1 ? 0.0 : 1.0));
+    rig.min_score = min_score;
+    EGO_CHECK(fin, "%s: R, t, affine and min_score must be finite", who);
+    const size_t kp_bytes = (size_t)B * 2 * J * 16, pose_bytes = pose ? (size_t)B * P * 12 : 0, j3_bytes = (size_t)B * J * 32, fr_bytes = (size_t)B * 32;
+    EGO_CHECK(!ego_overlap(joints3d, j3_bytes, keypoints, kp_bytes) && !ego_overlap(joints3d, j3_bytes, pose, pose_bytes) &&
+                  !ego_overlap(frame, fr_bytes, keypoints, kp_bytes) && !ego_overlap(frame, fr_bytes, pose, pose_bytes) &&
+                  !ego_overlap(joints3d, j3_bytes, frame, fr_bytes),
+              "%s: joints3d and frame must not overlap keypoints, pose or each other", who);
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_triangulate", "stereo_triangulate_kernel", 0.0);
+    EGO_HIP(stereo_triangulate_launch(keypoints, B, J, rig, pose, P, pose_row0, joints3d, frame, (hipStream_t)stream));
     return EGOTAP_OK;
 }
 

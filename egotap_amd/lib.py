@@ -21,6 +21,11 @@ class EgotapConfig(C.Structure):
         "patch", "pu_hidden")] + [("hm_blocks", C.c_int32 * 4)]      # zeros = resnet18's (2, 2, 2, 2)
 
 
+class EgotapOcam(C.Structure):                        # egotap.h egotap_ocam: doubles and two lengths
+    _fields_ = [("pol", C.c_double * 8), ("invpol", C.c_double * 24)] + [(n, C.c_double) for n in ("xc", "yc", "c", "d", "e", "ue_flip")] + [
+        ("n_pol", C.c_int32), ("n_invpol", C.c_int32)]
+
+
 class EgotapError(RuntimeError):
     pass
 
@@ -70,6 +75,11 @@ _PROTOS = {
                                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_predict_pose_sensor_u8_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- the fisheye camera model and the stereo triangulation of the keypoints: three operators, no handle
+    "egotap_ocam_project": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
+    "egotap_ocam_unproject": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
+    "egotap_stereo_triangulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapOcam), C.POINTER(EgotapOcam), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -437,6 +447,109 @@ def limb_decode(hm, c0: int, n_limbs: int, eyes: int = 2, affine=None):
         check(load().egotap_limb_decode(_ptr(hm), F32 if hm.dtype == torch.float32 else BF16, B, S, hm.stride(0) if B > 1 else Cn * S * S, c0, n_limbs, eyes,
                                         aff, _ptr(out), _stream(hm.device)))
     return out
+
+
+def ocam_struct(model) -> EgotapOcam:
+    """a ``spec.OcamModel`` as the ABI takes it (egotap_ocam, by pointer to host memory)"""
+    o = EgotapOcam()
+    for k, v in enumerate(model.pol):
+        o.pol[k] = v
+    for k, v in enumerate(model.invpol):
+        o.invpol[k] = v
+    o.xc, o.yc, o.c, o.d, o.e, o.ue_flip = model.xc, model.yc, model.c, model.d, model.e, 1.0 if model.ue_flip else 0.0
+    o.n_pol, o.n_invpol = len(model.pol), len(model.invpol)
+    return o
+
+
+def _ocam_points(who, fn, pts, model, n_in, n_out):
+    import torch
+    if not torch.is_tensor(pts):
+        raise EgotapError(f"{who} takes a torch tensor on the GPU")
+    if pts.dim() < 1 or pts.shape[-1] != n_in:
+        raise ValueError(f"{who}: points are [..., {n_in}], got {tuple(pts.shape)}")
+    cam = ocam_struct(model)
+    if not pts.is_cuda:                                  # (after the argument checks, so those can be exercised without a GPU)
+        raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the points to cuda")
+    x = pts.detach().float().contiguous()
+    out = torch.empty(tuple(x.shape[:-1]) + (n_out,), dtype=torch.float32, device=x.device)
+    N = x.numel() // n_in
+    if N == 0:
+        return out
+    with torch.cuda.device(x.device):
+        check(fn(_ptr(x), N, C.byref(cam), _ptr(out), _stream(x.device)))
+    return out
+
+
+def ocam_project(points3d, model):
+    """3D points [..., 3] in a camera's frame -> that camera's pixels [..., 2] through its fisheye model (egotap_ocam_project; the reference's
+    world2cam, ``spec.ocam_world2cam_ref``): float32 in and out, float64 inside, one launch.  ``model``: a ``spec.OcamModel``.  The first step
+    of ground-truth maps from 3D poses alone: ``synth_heatmaps(ocam_project(pts3d_left, left), ocam_project(pts3d_right, right), pose)``."""
+    return _ocam_points("ocam_project", load().egotap_ocam_project, points3d, model, 3, 2)
+
+
+def ocam_unproject(points2d, model):
+    """pixels [..., 2] -> unit rays [..., 3] in the frame ``ocam_project`` takes its points in (egotap_ocam_unproject; the reference's cam2world
+    as the inverse convention of world2cam, ``spec.ocam_cam2world_ref``): float32 in and out, float64 inside, one launch."""
+    return _ocam_points("ocam_unproject", load().egotap_ocam_unproject, points2d, model, 2, 3)
+
+
+def stereo_triangulate_args(left, right, t, R=None, affine=None, min_score=0.5):
+    """the host-side arguments of egotap_stereo_triangulate as ctypes values, built once per rig: (left, right, R, t, affine, min_score)"""
+    tt = [float(v) for v in t]
+    if len(tt) != 3:
+        raise ValueError(f"stereo_triangulate: t is the right camera's origin in the left frame, 3 values, got {len(tt)}")
+    Rp = None
+    if R is not None:
+        rr = [float(v) for row in R for v in row]
+        if len(rr) != 9:
+            raise ValueError(f"stereo_triangulate: R is 3 x 3, got {len(rr)} values")
+        Rp = (C.c_double * 9)(*rr)
+    ap = None
+    if affine is not None:
+        aa = [float(v) for row in affine for v in row]
+        if len(aa) != 8:
+            raise ValueError(f"stereo_triangulate: affine is [2, 4] = (ax, bx, ay, by) per eye, got {len(aa)} values")
+        ap = (C.c_double * 8)(*aa)
+    return ocam_struct(left), ocam_struct(right), Rp, (C.c_double * 3)(*tt), ap, C.c_double(float(min_score))
+
+
+def stereo_triangulate_into(args, keypoints, pose, pose_row0, joints3d, frame, dev):
+    """the launch itself on ``dev``'s current stream: ``args`` from ``stereo_triangulate_args``, tensors as the ABI takes them"""
+    cl, cr, Rp, tp, ap, ms = args
+    B, _, J, _ = keypoints.shape
+    check(load().egotap_stereo_triangulate(_ptr(keypoints), B, J, C.byref(cl), C.byref(cr), Rp, tp, ap, ms, _ptr(pose), pose.shape[1] if pose is not None else 0,
+                                           int(pose_row0), _ptr(joints3d), _ptr(frame), _stream(dev)))
+
+
+def stereo_triangulate(keypoints, left, right, t, R=None, affine=None, min_score=0.5, pose=None, pose_row0=0):
+    """The stereo keypoints triangulated through the two cameras' fisheye models (egotap_stereo_triangulate, ``spec.stereo_triangulate_ref``):
+    keypoints float32 [B, 2, J, 4] on the GPU, exactly what the serving entries return -> (joints3d float32 [B, J, 8] = (X, Y, Z, gap, den, s,
+    disagree, valid), frame float32 [B, 8] = (t_hat xyz, n, rms / max disagree, rms / max gap)) in the left camera's frame.  ``left`` / ``right``:
+    ``spec.OcamModel``; ``t`` (3) and ``R`` (3 x 3, None: identity): the right camera's origin and axes in the left frame, in the pose's units;
+    ``affine``: [2, 4] = (ax, bx, ay, by) per eye from keypoint units to the calibration's pixels (None: identity); ``pose``: the lifted pose
+    float32 [B, P, 3] whose rows pose_row0 .. pose_row0 + J - 1 pair with the joints (None: no translation, no disagreement).  One launch."""
+    import torch
+    args = stereo_triangulate_args(left, right, t, R, affine, min_score)
+    if not torch.is_tensor(keypoints) or keypoints.dim() != 4 or keypoints.shape[1] != 2 or keypoints.shape[3] != 4:
+        raise ValueError(f"stereo_triangulate: keypoints are a tensor [B, 2, J, 4], got {tuple(getattr(keypoints, 'shape', ()))}")
+    B, _, J, _ = (int(v) for v in keypoints.shape)
+    if not 1 <= J <= 64:
+        raise ValueError(f"stereo_triangulate: 1 .. 64 joints, got {J}")
+    if pose is not None and (not torch.is_tensor(pose) or pose.dim() != 3 or pose.shape[0] != B or pose.shape[2] != 3 or pose_row0 < 0
+                             or pose_row0 + J > pose.shape[1]):
+        raise ValueError(f"stereo_triangulate: pose is a tensor [B, P, 3] with pose_row0 + J <= P, got {tuple(getattr(pose, 'shape', ()))}, "
+                         f"pose_row0 = {pose_row0}, J = {J}")
+    if not keypoints.is_cuda or (pose is not None and pose.device != keypoints.device):
+        raise EgotapError("stereo_triangulate runs on the GPU only (no CPU fallback); keypoints and pose on one cuda device")
+    kp = keypoints.detach().float().contiguous()
+    ps = pose.detach().float().contiguous() if pose is not None else None
+    joints3d = torch.empty((B, J, 8), dtype=torch.float32, device=kp.device)
+    frame = torch.empty((B, 8), dtype=torch.float32, device=kp.device)
+    if B == 0:
+        return joints3d, frame
+    with torch.cuda.device(kp.device):
+        stereo_triangulate_into(args, kp, ps, pose_row0, joints3d, frame, kp.device)
+    return joints3d, frame
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

@@ -405,8 +405,35 @@ class EgoTAPAutoEncoderModel(nn.Module):
         _lib.check(_lib.load().egotap_debug_predict_pose_rgb_form(st.handle.h, C.byref(form)))
         return _lib.RGB_FORMS[form.value]
 
+    def set_stereo_rig(self, left, right, t, R=None, min_score=_spec.STEREO_MIN_SCORE):
+        """The stereo rig ``return_triangulation`` uses: ``left`` / ``right`` the two cameras' fisheye models (``spec.OcamModel``, or paths of the
+        reference's fisheye.calibration_{side}.json), ``t`` (3) the right camera's origin and ``R`` (3 x 3, None: identity -- the reference's data has
+        parallel camera axes) its axes in the left camera's frame, in the pose's units: the reference's gt_pelvis_left - gt_pelvis_right.  ``min_score``:
+        the keypoint score below which a joint is not triangulated (target maps peak at 1 in view and are zero otherwise: 0.5 is halfway)."""
+        left, right = (m if isinstance(m, _spec.OcamModel) else _spec.ocam_from_json(m) for m in (left, right))
+        t = tuple(float(v) for v in t)
+        R = None if R is None else tuple(tuple(float(v) for v in row) for row in R)
+        _lib.stereo_triangulate_args(left, right, t, R, None, min_score)           # (the shape checks, now rather than at the first request)
+        self._stereo_rig = (left, right, t, R, float(min_score))
+
+    def _triangulation(self, who, wanted, affine=None):
+        """None, or what a serving entry needs for ``return_triangulation``: (the launch's host arguments, the capture key's part, the keypoint ->
+        calibration pixel affines, pose_row0).  ``affine`` None: the RGB / byte entries' size / (4S) (``spec.stereo_pixel_affine``)."""
+        if not wanted:
+            return None
+        rig = self.__dict__.get("_stereo_rig")
+        if rig is None:
+            raise _lib.EgotapError(f"{who}(return_triangulation=True): no stereo rig is set; call set_stereo_rig(left, right, t) first")
+        left, right, t, R, min_score = rig
+        p = self.net_AutoEncoder.preset
+        if affine is None:
+            affine = (_spec.stereo_pixel_affine(left, p.hm_size), _spec.stereo_pixel_affine(right, p.hm_size))
+        affine = tuple(tuple(float(v) for v in row) for row in affine)
+        return _lib.stereo_triangulate_args(left, right, t, R, affine, min_score), ("triangulation", rig, affine), affine, _spec.stereo_pose_row0(p)
+
     @torch.no_grad()
-    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False):
+    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False,
+                              return_triangulation=False, _triangulation_affine=None):
         """Serving entry: stereo RGB [B, 3, 4S, 4S] x 2 -> pose [B, J(+1), 3], or (pose, heatmaps [B, 6J, S, S]) with ``return_heatmaps``.
         Replaces set_input() + evaluate() (utils/evaluate.py:104-114 without the metrics; egotap_autoencoder_model.py:177-223) for a caller
         that has no ground truth: no set_input, no loader keys, no autograd.  ONE library call (egotap_predict_pose_rgb): both estimators in
@@ -426,7 +453,15 @@ class EgoTAPAutoEncoderModel(nn.Module):
         length in the keypoints' units, appended after the keypoints.  One more launch inside the same library call (egotap_predict_pose_rgb_kpl)
         on the same tensor; the hand-off stays on, the other outputs keep their bits.
 
-        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps, return_keypoints, return_limbs), with
+        ``return_triangulation``: also the stereo keypoints triangulated through the rig of ``set_stereo_rig`` (``lib.stereo_triangulate``,
+        ``spec.stereo_triangulate_ref``): joints3d float32 [B, J, 8] = (X, Y, Z, gap, den, s, disagree, valid) in the left camera's frame and frame
+        float32 [B, 8] = (t_hat xyz, n, rms / max disagree, rms / max gap), appended as the last two results.  t_hat places the pelvis-relative pose
+        in the left camera's frame; disagree and gap tell per joint whether to believe it; neither needs ground truth.  One more launch on the same
+        stream right after the library call, on the keypoints (computed inside when ``return_keypoints`` is off, then not returned) and the pose of
+        this call; every other output keeps its bits and the workspace its size.  Raises by name without a rig.
+
+        ``graphed``: the whole pipeline through a captured graph, one per (B, precision, frozen state, return_heatmaps, return_keypoints, return_limbs,
+        and with ``return_triangulation`` the rig and the pixel affine), with
         static input and output buffers as ``net_AutoEncoder.predict_pose_graphed``: the returned tensors are the graph's own (valid until the
         next call with the same key).
 
@@ -444,6 +479,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
         dev = left.device
         left, right = left.detach().float().contiguous(), right.detach().float().contiguous()
         chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
+        tri = self._triangulation("predict_pose_from_rgb", return_triangulation, _triangulation_affine)
         why = self._rgb_one_call_refusal()
         if why is not None:
             if graphed:
@@ -463,11 +499,15 @@ class EgoTAPAutoEncoderModel(nn.Module):
             pose = self.net_AutoEncoder.predict_pose(cat)
             kp = lb = None
             affine = _keypoint_affine or [(4.0, 0.0, 4.0, 0.0)] * 2
-            if return_keypoints:
+            if return_keypoints or tri is not None:
                 kp = _lib.heatmap_peaks(cat, 0, 2 * J, groups=2, affine=affine).view(B, 2, J, 4)
             if return_limbs:
                 lb = _lib.limb_decode(cat, 2 * J, J, eyes=2, affine=affine)
-            return self._served(pose, cat if return_heatmaps else None, kp, lb)
+            tr = None
+            if tri is not None:
+                rig_l, rig_r, rig_t, rig_R, min_score = self._stereo_rig
+                tr = _lib.stereo_triangulate(kp, rig_l, rig_r, rig_t, R=rig_R, affine=tri[2], min_score=min_score, pose=pose, pose_row0=tri[3])
+            return self._served(pose, cat if return_heatmaps else None, kp if return_keypoints else None, lb, tr)
         lib = _lib.load()
 
         def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
@@ -478,12 +518,13 @@ class EgoTAPAutoEncoderModel(nn.Module):
             else:
                 _lib.check(lib.egotap_predict_pose_rgb_kp(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
         return self._serve_one_call(left, right, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_workspace_bytes, launch,
-                                    return_limbs=return_limbs)
+                                    return_limbs=return_limbs, tri=tri)
 
     @staticmethod
-    def _served(pose, hm, kp, lb=None):
-        """what a serving entry returns: the pose alone, or the pose followed by the heatmaps, keypoints and / or limb records that were asked for"""
-        extra = tuple(t for t in (hm, kp, lb) if t is not None)
+    def _served(pose, hm, kp, lb=None, tr=None):
+        """what a serving entry returns: the pose alone, or the pose followed by the heatmaps, keypoints and / or limb records that were asked for, and
+        last the triangulation's two records (joints3d, frame)"""
+        extra = tuple(t for t in (hm, kp, lb) + (tuple(tr) if tr is not None else ()) if t is not None)
         return (pose,) + extra if extra else pose
 
     def camera_table(self, dev):
@@ -496,19 +537,33 @@ class EgoTAPAutoEncoderModel(nn.Module):
             hit = self._camera_table = (key, torch.from_numpy(_spec.rgb_u8_table(self.opt)).to(dev))
         return hit[1]
 
-    def _serve_one_call(self, left, right, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch, kind=(), keep=(), return_limbs=False):
+    def _serve_one_call(self, left, right, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch, kind=(), keep=(), return_limbs=False,
+                        tri=None):
         """The host side of a one-call serving entry on the serving handle: outputs, workspace (eager: the handle's grow-only one; graphed: the
         graph's own), capture and replay with static inputs of the frames' dtype.  ``size_query(h, B, chunk, &bytes)`` and
         ``launch(h, left, right, pose, heatmaps, keypoints, limbs, chunk, ws)`` are the entry's two ABI calls (keypoints / limbs None: the entry
-        without that output); ``kind`` extends the capture key, ``keep`` what a graph must keep alive besides its own buffers."""
+        without that output); ``kind`` extends the capture key, ``keep`` what a graph must keep alive besides its own buffers.  ``tri``
+        (``_triangulation``): the triangulation launch follows the library call on the same stream -- inside a capture too, so a graphed request stays
+        one replay -- on keypoints that exist for it alone when they were not asked for."""
         p = self.net_AutoEncoder.preset
         chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
         pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
         hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
-        kp = torch.empty((B, 2, p.n_joints_hm, 4), dtype=torch.float32, device=dev) if return_keypoints else None
+        kp = torch.empty((B, 2, p.n_joints_hm, 4), dtype=torch.float32, device=dev) if return_keypoints or tri is not None else None
         lb = torch.empty((B, 2, p.n_joints_hm, 8), dtype=torch.float32, device=dev) if return_limbs else None
+        tr = None
+        if tri is not None:
+            tr = (torch.empty((B, p.n_joints_hm, 8), dtype=torch.float32, device=dev), torch.empty((B, 8), dtype=torch.float32, device=dev))
+            entry_launch = launch
+
+            def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
+                entry_launch(h, l, r, po, hmo, kp, lb, chunk, ws)
+                _lib.stereo_triangulate_into(tri[0], kp, po, tri[3], tr[0], tr[1], dev)
+
+        def served(pose, hm, kp, lb):
+            return self._served(pose, hm, kp if return_keypoints else None, lb, tr)
         if B == 0:
-            return self._served(pose, hm, kp, lb)
+            return served(pose, hm, kp, lb)
         with torch.cuda.device(dev):
             st = self._rgb_state(dev)
             self._rgb_attach_act_scratch(st, B, dev)
@@ -518,34 +573,37 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 _session.grown(st, "ws", need, dev, drop_first=True)
                 st.chunk = chunk
                 launch(h, left, right, pose, hm, kp, lb, chunk, st.ws)
-                return self._served(pose, hm, kp, lb)
+                return served(pose, hm, kp, lb)
             # one graph per (batch, heatmaps wanted, keypoints wanted, limbs wanted, precision, frozen arenas, bound tensors, chunk, source): every pointer a captured
             # launch takes is baked in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch
             # buffers and arenas alive
             nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
             key = (B, bool(return_heatmaps), bool(return_keypoints), bool(return_limbs), st.precision, tuple(st.frozen),
                    tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)), chunk, str(dev)) + tuple(kind)
+            if tri is not None:
+                key += (tri[1],)
 
             def build():
                 s_l, s_r = left.clone(), right.clone()
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
                 held = (ws, st.wscratch, st.ascratch) + tuple(keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
-                return (lambda: launch(h, s_l, s_r, pose, hm, kp, lb, chunk, ws)), (s_l, s_r, pose, hm, kp, lb), held
-            graph, (s_l, s_r, pose, hm, kp, lb), _ = _session.captured(st.graphs, key, build)
+                return (lambda: launch(h, s_l, s_r, pose, hm, kp, lb, chunk, ws)), (s_l, s_r, pose, hm, kp, lb, tr), held
+            graph, (s_l, s_r, pose, hm, kp, lb, tr), _ = _session.captured(st.graphs, key, build)
             s_l.copy_(left)
             s_r.copy_(right)
             graph.replay()
-        return self._served(pose, hm, kp, lb)
+        return served(pose, hm, kp, lb)
 
     @torch.no_grad()
-    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False):
+    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False,
+                                 return_triangulation=False, _triangulation_affine=None):
         """predict_pose_from_rgb from what a camera delivers: stereo frames uint8 [B, 4S, 4S, 3] (HWC, RGB order, already at 4S x 4S) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_rgb_u8) on the serving handle of
         predict_pose_from_rgb: the caller's astype(float32) / 255, normalisation, HWC -> CHW and the four-fold upload are gone -- at sides 64 / 128
         the stem kernels look every byte up in a 768-entry table (``camera_table``) while they stage it; at other sides the library converts chunk
         by chunk into a workspace slice.  The bits are those of predict_pose_from_rgb on the gathered frames table[c][byte].  ``return_keypoints``: as
         predict_pose_from_rgb, in pixels of the 4S x 4S frame (egotap_predict_pose_rgb_u8_kp).  ``return_limbs``: as predict_pose_from_rgb
-        (egotap_predict_pose_rgb_u8_kpl).
+        (egotap_predict_pose_rgb_u8_kpl).  ``return_triangulation``: as predict_pose_from_rgb.
 
         ``graphed``: as predict_pose_from_rgb, with static BYTE inputs; the capture key also holds the source kind and the table, so the two entries
         never share a graph.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions) run
@@ -554,13 +612,14 @@ class EgoTAPAutoEncoderModel(nn.Module):
         B = _lib.check_camera_frames("predict_pose_from_camera", left8, right8, S0)
         dev = left8.device
         table = self.camera_table(dev)
+        tri = self._triangulation("predict_pose_from_camera", return_triangulation, _triangulation_affine)
         why = self._rgb_one_call_refusal()
         if why is not None:
             if graphed:
                 raise _lib.EgotapError(f"predict_pose_from_camera(graphed=True): {why}; this configuration runs the converter and the module forwards, ungraphed")
             left, right = _lib.rgb_u8_to_f32(left8, right8, table)
             return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=_keypoint_affine,
-                                              return_limbs=return_limbs)
+                                              return_limbs=return_limbs, return_triangulation=return_triangulation, _triangulation_affine=_triangulation_affine)
         lib = _lib.load()
 
         def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
@@ -572,11 +631,11 @@ class EgoTAPAutoEncoderModel(nn.Module):
             else:
                 _lib.check(lib.egotap_predict_pose_rgb_u8_kp(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
         return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
-                                    kind=("u8", table.data_ptr()), keep=(table,), return_limbs=return_limbs)
+                                    kind=("u8", table.data_ptr()), keep=(table,), return_limbs=return_limbs, tri=tri)
 
     @torch.no_grad()
     def predict_pose_from_sensor(self, left8, right8, crop=None, crop_right=None, mirror_right=False, return_heatmaps=False, graphed=False,
-                                 return_keypoints=False, return_limbs=False):
+                                 return_keypoints=False, return_limbs=False, return_triangulation=False):
         """predict_pose_from_camera from the sensor's own frames: stereo uint8 [B, H, W, 3] (HWC, RGB, any H x W, the same for both eyes) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_sensor_u8) on the serving handle:
         the caller's crop, flip, F.interpolate and round to bytes are gone -- the library resizes chunk by chunk into a workspace slice
@@ -592,7 +651,8 @@ class EgoTAPAutoEncoderModel(nn.Module):
         ``return_keypoints``: as predict_pose_from_rgb, but in pixels of each eye's SENSOR frame (egotap_predict_pose_sensor_u8_kp): the inverse of the
         resize's map, per eye from its own rectangle and mirror flag (``spec.sensor_keypoint_affine``).  ``return_limbs``: as predict_pose_from_rgb,
         (x, y), phi and length in the same sensor pixels (egotap_predict_pose_sensor_u8_kpl); a rectangle whose w / S and h / S differ bends phi
-        and length (the blur is no longer isotropic in the output frame).
+        and length (the blur is no longer isotropic in the output frame).  ``return_triangulation``: as predict_pose_from_rgb, with the identity as the
+        pixel affine: the calibration is the sensor's, and the keypoints are already in sensor pixels with crop and mirror undone.
 
         ``graphed``: as predict_pose_from_camera; the capture key holds the source kind, H, W, the rectangles, the mirror flags and the table, so
         no graph is shared with the other entries.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions)
@@ -604,6 +664,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
         rect_r = _spec.check_resize_rect("predict_pose_from_sensor", crop if crop_right is None else crop_right, H, W)
         mirrors = (0, int(bool(mirror_right)))
         dev = left8.device
+        tri = self._triangulation("predict_pose_from_sensor", return_triangulation, _spec.STEREO_IDENTITY_AFFINE)
         why = self._rgb_one_call_refusal()
         if why is not None:
             if graphed:
@@ -611,7 +672,8 @@ class EgoTAPAutoEncoderModel(nn.Module):
             l8, r8 = _lib.rgb_u8_resize(left8, right8, S0, rect_l, rect_r, False, bool(mirror_right))
             affine = [_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)]
             return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=affine,
-                                                 return_limbs=return_limbs)
+                                                 return_limbs=return_limbs, return_triangulation=return_triangulation,
+                                                 _triangulation_affine=_spec.STEREO_IDENTITY_AFFINE)
         table = self.camera_table(dev)
         lib = _lib.load()
         rects, flags = (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors)
@@ -630,7 +692,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 _lib.check(lib.egotap_predict_pose_sensor_u8_kp(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
                                                                 stream(dev), ptr(kp)))
         return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch,
-                                    kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), return_limbs=return_limbs)
+                                    kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), return_limbs=return_limbs, tri=tri)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

@@ -464,3 +464,220 @@ def limb_decode_ref(hm, c0: int, n_limbs: int, eyes: int, affine=None):
         for k in (0, 1, 4, 5):
             rec[k] = np.where(full, rec[k], 0.0)
         return np.stack(np.broadcast_arrays(*rec), axis=-1).astype(np.float32)
+
+
+# ---- the fisheye camera model and stereo triangulation (egotap.h: egotap_ocam_project / _ocam_unproject / egotap_stereo_triangulate) ------
+OCAM_MAX_POL, OCAM_MAX_INVPOL = 8, 24          # egotap.h EGOTAP_OCAM_MAX_POL / _MAX_INVPOL
+STEREO_MAX_JOINTS = 64                         # one lane per joint
+STEREO_MIN_SCORE = 0.5                         # target maps peak at 1 for a joint in view and are all zero otherwise (utils/projection.py:263-279)
+
+
+@dataclass(frozen=True)
+class OcamModel:
+    """One camera's OCamCalib model as the reference reads it (utils/projection.py:13-50): ``pol`` the cam2world polynomial in the pixel
+    radius (polynomialC2W), ``invpol`` the world2cam polynomial in the elevation angle (polynomialW2C), the centre (xc, yc) -- xc multiplies
+    the FIRST pixel coordinate, as in world2cam -- and the affine (c, d, e).  ``size`` and ``radius`` are carried, not used."""
+    name: str
+    pol: tuple
+    invpol: tuple
+    xc: float
+    yc: float
+    c: float = 1.0
+    d: float = 0.0
+    e: float = 0.0
+    size: tuple = (1024, 1024)
+    radius: float = 0.0
+
+    def __post_init__(self):
+        object.__setattr__(self, "pol", tuple(float(v) for v in self.pol))
+        object.__setattr__(self, "invpol", tuple(float(v) for v in self.invpol))
+        for k in ("xc", "yc", "c", "d", "e", "radius"):
+            object.__setattr__(self, k, float(getattr(self, k)))
+        object.__setattr__(self, "size", tuple(int(v) for v in self.size))
+        if not 1 <= len(self.pol) <= OCAM_MAX_POL:
+            raise ValueError(f"OcamModel {self.name!r}: polynomialC2W has {len(self.pol)} coefficients, 1 .. {OCAM_MAX_POL} are supported")
+        if not 1 <= len(self.invpol) <= OCAM_MAX_INVPOL:
+            raise ValueError(f"OcamModel {self.name!r}: polynomialW2C has {len(self.invpol)} coefficients, 1 .. {OCAM_MAX_INVPOL} are supported")
+        if not all(math.isfinite(v) for v in self.pol + self.invpol + (self.xc, self.yc, self.c, self.d, self.e)):
+            raise ValueError(f"OcamModel {self.name!r}: a calibration value is not finite")
+        if self.c - self.d * self.e == 0.0:
+            raise ValueError(f"OcamModel {self.name!r}: the affine is singular (c - d * e == 0)")
+
+    @property
+    def ue_flip(self):         # utils/projection.py:96, 141
+        return self.name == "unreal_ego_pose"
+
+
+def ocam_from_json(data) -> OcamModel:
+    """An OcamModel from the reference's ``fisheye.calibration_{side}.json`` -- a path, or the parsed dict -- with the reference's field mapping
+    (utils/projection.py:26-44): xc = image_center[1], yc = image_center[0], affine = [c, d, e]."""
+    if not isinstance(data, dict):
+        import json
+        with open(data) as f:
+            data = json.load(f)
+    aff = data["affine"]
+    if len(aff) != 3:
+        raise ValueError(f"ocam_from_json: affine is [c, d, e], got {len(aff)} values")
+    return OcamModel(name=data["name"], pol=data["polynomialC2W"], invpol=data["polynomialW2C"], xc=data["image_center"][1], yc=data["image_center"][0],
+                     c=aff[0], d=aff[1], e=aff[2], size=tuple(data["size"]), radius=data["imageCircleRadius"])
+
+
+def _ocam_poly(coef, r):
+    """the reference's running-power sum (projection.py:73-79, 115-122): z = coef[0]; r_i *= r; z += r_i * coef[i] -- not Horner"""
+    import numpy as np
+    z = np.full(r.shape, coef[0], dtype=np.float64)
+    r_i = np.ones_like(r)
+    for k in range(1, len(coef)):
+        r_i = r_i * r
+        z = z + r_i * coef[k]
+    return z
+
+
+def ocam_world2cam_ref(points3d, model: OcamModel):
+    """utils/projection.py:89-144 world2cam in float64 numpy, operation for operation: [..., 3] -> pixels [..., 2].  With ``ue_flip`` y and z are
+    negated first (UEp2CVp) and v <- 2 yc - v last; norm = sqrt(x^2 + y^2); norm <= 1e-8 (isclose(norm, 0)) gives (xc, yc); otherwise
+    theta = arctan(z / norm), rho = invpol(theta), x' = x * (1 / norm) * rho, y' likewise, u = x' c + y' d + xc, v = x' e + y' + yc."""
+    import numpy as np
+    p = np.array(points3d, dtype=np.float64)
+    if p.shape[-1] != 3:
+        raise ValueError(f"ocam_world2cam_ref: points are [..., 3], got {p.shape}")
+    m = model
+    x, y, z = p[..., 0], p[..., 1], p[..., 2]
+    if m.ue_flip:
+        y, z = y * -1.0, z * -1.0
+    with np.errstate(all="ignore"):
+        norm = np.sqrt(x * x + y * y)
+        zero = norm <= 1e-8
+        safe = np.where(zero, 1.0, norm)
+        theta = np.arctan(z / safe)
+        invnorm = 1.0 / safe
+        rho = _ocam_poly(m.invpol, theta)
+        xs, ys = x * invnorm * rho, y * invnorm * rho
+        u = np.where(zero, m.xc, xs * m.c + ys * m.d + m.xc)
+        v = np.where(zero, m.yc, xs * m.e + ys + m.yc)
+        if m.ue_flip:
+            v = m.yc * 2 - v
+    return np.stack([u, v], axis=-1)
+
+
+def ocam_cam2world_ref(points2d, model: OcamModel):
+    """utils/projection.py:55-87 cam2world in float64 numpy, operation for operation, wrapped so that it inverts ``ocam_world2cam_ref``'s
+    convention: pixels [..., 2] -> unit rays [..., 3] in the frame of the points world2cam takes.  With ``ue_flip``, v <- 2 yc - v before and
+    (rx, -ry, -rz) after.  (The polynomials are fitted as each other's inverse: a ray's polynomial z has the sign of world2cam's z.)"""
+    import numpy as np
+    q = np.array(points2d, dtype=np.float64)
+    if q.shape[-1] != 2:
+        raise ValueError(f"ocam_cam2world_ref: pixels are [..., 2], got {q.shape}")
+    m = model
+    u, v = q[..., 0], q[..., 1]
+    with np.errstate(all="ignore"):
+        if m.ue_flip:
+            v = m.yc * 2 - v
+        invdet = 1.0 / (m.c - m.d * m.e)
+        xp = invdet * ((u - m.xc) - m.d * (v - m.yc))
+        yp = invdet * (-m.e * (u - m.xc) + m.c * (v - m.yc))
+        r = np.sqrt(xp * xp + yp * yp)
+        zp = _ocam_poly(m.pol, r)
+        invnorm = 1.0 / np.sqrt(xp * xp + yp * yp + zp * zp)
+        rx, ry, rz = invnorm * xp, invnorm * yp, invnorm * zp
+        if m.ue_flip:
+            ry, rz = ry * -1.0, rz * -1.0
+    return np.stack([rx, ry, rz], axis=-1)
+
+
+def stereo_pose_row0(preset: LiftPreset) -> int:
+    """the row of the lifted pose that heatmap joint 0 is paired with: the heatmaps are gt_camera_2d[1:] (dataloader/data_loader.py:90), the pose
+    target gt_local_pose with the head at row 0 when the head is estimated (UnrealEgo), gt_local_pose[1:] otherwise (:175); the loss pairs rows"""
+    return 1 if preset.estimate_head else 0
+
+
+def stereo_pixel_affine(model: OcamModel, S: int):
+    """(ax, bx, ay, by): keypoints of the RGB / byte serving entries (pixels of the 4S x 4S input frame) -> the calibration's pixels.  The
+    reference's maps are coord2d / 1024 * res with 1024 the calibration's image: size / (4S) per axis (size = (height, width))."""
+    return (model.size[1] / (4.0 * S), 0.0, model.size[0] / (4.0 * S), 0.0)
+
+
+STEREO_IDENTITY_AFFINE = ((1.0, 0.0, 1.0, 0.0),) * 2      # the sensor entry: its keypoints are already the calibrated sensor's pixels
+
+
+def stereo_triangulate_ref(keypoints, left: OcamModel, right: OcamModel, t, R=None, affine=None, min_score=STEREO_MIN_SCORE, pose=None, pose_row0=0,
+                           dtype="float32"):
+    """The records egotap_stereo_triangulate writes, restated in float64 numpy: keypoints [B, 2, J, 4] (eye, joint, (x, y, score, index)) ->
+    (joints3d float32 [B, J, 8], frame float32 [B, 8]).  ``t`` (3) and ``R`` (3 x 3, None: identity) are the right camera's origin and axes in
+    the left camera's frame, ``affine`` [2, 4] = (ax, bx, ay, by) per eye from keypoint units to the calibration's pixels (None: identity).
+    Per (frame, joint):
+
+        seen  = both scores >= min_score (a NaN fails) and the four coordinates finite
+        pL    = (ax x + bx, ay y + by);  dL = cam2world_L(pL);  dR = R cam2world_R(pR);  w0 = -t
+        b = dL.dR   d = dL.w0   e = dR.w0   den = 1 - b^2   s = (b e - d) / den   u = (e - b d) / den
+        PL = s dL   PR = t + u dR   X = (PL + PR) / 2   gap = |PL - PR|
+        valid = seen and den > 0 and s > 0 and u > 0 and everything finite (with a pose: its row pose[pose_row0 + j] too)
+
+    Per frame, summed over the valid joints in ascending order: n = #valid; with a pose [B, P, 3] and n >= 1,
+    t_hat = sum X / n - sum pose[pose_row0 + j] / n and disagree_j = |X_j - pose[pose_row0 + j] - t_hat|.
+
+        joints3d = (X, Y, Z, gap, den, s, disagree, valid);  an invalid joint is all zeros
+        frame    = (t_hat x, y, z, n, rms disagree, max disagree, rms gap, max gap);  without a pose t_hat and the disagreements are 0; n = 0: zeros
+
+    Each value is rounded once from float64 (``dtype="float64"``: not at all -- the records before that rounding)."""
+    import numpy as np
+    kp = np.asarray(keypoints, dtype=np.float64)
+    if kp.ndim != 4 or kp.shape[1] != 2 or kp.shape[3] != 4:
+        raise ValueError(f"stereo_triangulate_ref: keypoints are [B, 2, J, 4], got {kp.shape}")
+    B, _, J, _ = kp.shape
+    if not 1 <= J <= STEREO_MAX_JOINTS:
+        raise ValueError(f"stereo_triangulate_ref: 1 .. {STEREO_MAX_JOINTS} joints, got {J}")
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64).reshape(3, 3)
+    a = np.asarray(STEREO_IDENTITY_AFFINE if affine is None else affine, dtype=np.float64).reshape(2, 4)
+    ps = None
+    if pose is not None:
+        ps = np.asarray(pose, dtype=np.float64)
+        if ps.ndim != 3 or ps.shape[0] != B or ps.shape[2] != 3 or pose_row0 < 0 or pose_row0 + J > ps.shape[1]:
+            raise ValueError(f"stereo_triangulate_ref: pose is [B, P, 3] with pose_row0 + J <= P, got {ps.shape}, pose_row0 = {pose_row0}, J = {J}")
+        ps = ps[:, pose_row0:pose_row0 + J]
+    with np.errstate(all="ignore"):
+        seen = (kp[:, 0, :, 2] >= min_score) & (kp[:, 1, :, 2] >= min_score) & np.isfinite(kp[:, :, :, :2]).all(axis=(1, 3))
+        pix = [np.stack([a[e, 0] * kp[:, e, :, 0] + a[e, 1], a[e, 2] * kp[:, e, :, 1] + a[e, 3]], axis=-1) for e in range(2)]
+        dL, r = ocam_cam2world_ref(pix[0], left), ocam_cam2world_ref(pix[1], right)
+        dR = np.stack([R[k, 0] * r[..., 0] + R[k, 1] * r[..., 1] + R[k, 2] * r[..., 2] for k in range(3)], axis=-1)
+        w0 = -t
+
+        def dot(p, q):
+            return p[..., 0] * q[..., 0] + p[..., 1] * q[..., 1] + p[..., 2] * q[..., 2]
+        b, d, e = dot(dL, dR), dot(dL, w0[None, None]), dot(dR, w0[None, None])
+        den = 1.0 - b * b
+        s, u = (b * e - d) / den, (e - b * d) / den
+        PL, PR = s[..., None] * dL, t + u[..., None] * dR
+        X = (PL + PR) * 0.5
+        df = PL - PR
+        gap = np.sqrt(df[..., 0] * df[..., 0] + df[..., 1] * df[..., 1] + df[..., 2] * df[..., 2])
+        valid = seen & (den > 0) & (s > 0) & (u > 0) & np.isfinite(X).all(axis=-1) & np.isfinite(gap) & np.isfinite(den) & np.isfinite(s) & np.isfinite(u)
+        if ps is not None:
+            valid = valid & np.isfinite(ps).all(axis=-1)                                     # "everything finite": the joint's pose row too
+        n = np.zeros(B)
+        sx, sp = np.zeros((B, 3)), np.zeros((B, 3))
+        for j in range(J):                                                                   # ascending joint order, as the kernel adds
+            on = valid[:, j]
+            n = n + on
+            sx = np.where(on[:, None], sx + X[:, j], sx)
+            if ps is not None:
+                sp = np.where(on[:, None], sp + ps[:, j], sp)
+        nn = np.where(n > 0, n, 1.0)
+        that = np.zeros((B, 3)) if ps is None else sx / nn[:, None] - sp / nn[:, None]
+        dis = np.zeros((B, J))
+        if ps is not None:
+            q = X - ps - that[:, None]
+            dis = np.sqrt(q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1] + q[..., 2] * q[..., 2])
+        s2d, s2g, mxd, mxg = np.zeros(B), np.zeros(B), np.zeros(B), np.zeros(B)
+        for j in range(J):
+            on = valid[:, j]
+            s2d = np.where(on, s2d + dis[:, j] * dis[:, j], s2d)
+            s2g = np.where(on, s2g + gap[:, j] * gap[:, j], s2g)
+            mxd = np.where(on & (dis[:, j] > mxd), dis[:, j], mxd)
+            mxg = np.where(on & (gap[:, j] > mxg), gap[:, j], mxg)
+        rec = np.stack([X[..., 0], X[..., 1], X[..., 2], gap, den, s, dis, np.ones((B, J))], axis=-1)
+        rec = np.where(valid[..., None], rec, 0.0)
+        frame = np.stack([that[:, 0], that[:, 1], that[:, 2], n, np.sqrt(s2d / nn), mxd, np.sqrt(s2g / nn), mxg], axis=-1)
+        frame = np.where((n > 0)[:, None], frame, 0.0)
+    return rec.astype(dtype), frame.astype(dtype)

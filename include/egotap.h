@@ -292,6 +292,55 @@ int egotap_predict_pose_sensor_u8_kpl(egotap_handle h, const uint8_t* left8, con
                                       const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints,
                                       float* limbs);
 
+/* ---- the fisheye camera model and stereo triangulation of the keypoints (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * The reference carries each camera as an OCamCalib model (utils/projection.py:13-144): cam2world takes a pixel to a unit ray through the polynomial
+ * pol in the pixel radius, world2cam a 3D point to its pixel through the polynomial invpol in the elevation angle, both behind the affine (c, d, e) and the
+ * centre (xc, yc).  egotap_ocam is that model by value: doubles and two lengths, filled on the host (egotap_amd/spec.py OcamModel / ocam_from_json read the
+ * reference's fisheye.calibration_{side}.json: xc = image_center[1], yc = image_center[0], affine = [c, d, e]).  ue_flip is 1.0 exactly for the model
+ * named "unreal_ego_pose" (projection.py:96, 141), else 0.0.  All arithmetic is float64 without contraction, each polynomial the reference's
+ * running-power sum (r_i *= r; z += r_i * pol[i]), inputs and outputs fp32, every output rounded once:
+ *   project    (world2cam) with ue_flip y and z are negated first; norm = sqrt(x^2 + y^2); norm <= 1e-8 gives (xc, yc); otherwise theta = atan(z / norm),
+ *              rho = invpol(theta), x' = x * (1 / norm) * rho, y' = y * (1 / norm) * rho, u = x' c + y' d + xc, v = x' e + y' + yc; with ue_flip v <- 2 yc - v
+ *   unproject  (cam2world, as the inverse convention of project) with ue_flip v <- 2 yc - v first; invdet = 1 / (c - d e), xp = invdet ((u - xc) - d (v - yc)),
+ *              yp = invdet (-e (u - xc) + c (v - yc)), r = sqrt(xp^2 + yp^2), zp = pol(r), ray = (xp, yp, zp) / |(xp, yp, zp)|; with ue_flip (rx, -ry, -rz)
+ * egotap_amd/spec.py ocam_world2cam_ref / ocam_cam2world_ref restate both in float64 numpy, operation for operation; only atan and the divisions may differ
+ * from the host in the last float64 bit.
+ *
+ * egotap_stereo_triangulate: keypoints [B, 2, J, 4] (what the _kp serving entries write: eye, joint, (x, y, score, index)) -> joints3d [B, J, 8] and
+ * frame [B, 8].  R (row-major 3 x 3, NULL = identity) and t (3) are the right camera's axes and origin in the left camera's frame, in the pose's units;
+ * affine ([2, 4] = (ax, bx, ay, by) per eye, NULL = identity) takes keypoint units to the calibration's pixels.  left, right, R, t and affine are host
+ * memory, read during the call and passed to the kernel by value.  Per (frame, joint), float64 without contraction:
+ *   seen  = both scores >= min_score (a NaN fails) and the four coordinates finite
+ *   pL = (ax x + bx, ay y + by), dL = unproject_left(pL), dR = R unproject_right(pR), w0 = -t
+ *   b = dL.dR, d = dL.w0, e = dR.w0, den = 1 - b^2, s = (b e - d) / den, u = (e - b d) / den
+ *   PL = s dL, PR = t + u dR, X = (PL + PR) / 2, gap = |PL - PR|
+ *   valid = seen and den > 0 and s > 0 and u > 0 and everything finite (with a pose: the joint's pose row too)
+ * Per frame, summed over the valid joints in ascending joint order: n = #valid; with pose (device f32 [B, P, 3], NULL = none) and n >= 1,
+ * t_hat = sum X / n - sum pose[pose_row0 + j] / n -- the pelvis-relative pose placed in the left camera's frame without ground truth -- and
+ * disagree_j = |X_j - pose[pose_row0 + j] - t_hat|.
+ *   joints3d = (X, Y, Z, gap, den, s, disagree, valid in {0, 1}); an invalid joint is all zeros
+ *   frame    = (t_hat x, y, z, n, rms disagree, max disagree, rms gap, max gap); without a pose t_hat and the disagreements are 0; n = 0 gives zeros
+ * One wave per frame (lane = joint, J <= 64), four frames per workgroup.  egotap_amd/spec.py stereo_triangulate_ref restates the records.
+ *
+ * All three need no handle, do one launch on the caller's stream, allocate nothing, and use plain vector stores: no atomics, no workspace.  While a handle's
+ * timing hook is on (egotap_timing_enable; the handle enabled last) their launches are recorded there as ocam_project, ocam_unproject, stereo_triangulate.
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL or misaligned pointer (points 4, keypoints / joints3d / frame 16 bytes); an output that
+ * overlaps an input or another output; N, B or J <= 0; J > 64; pose_row0 < 0 or pose_row0 + J > P; n_pol outside 1 .. 8, n_invpol outside 1 .. 24;
+ * c - d e == 0; a non-finite calibration value, R, t, affine or min_score; a ue_flip that is neither 0 nor 1. */
+#define EGOTAP_OCAM_MAX_POL 8
+#define EGOTAP_OCAM_MAX_INVPOL 24
+typedef struct egotap_ocam {
+    double pol[EGOTAP_OCAM_MAX_POL];       /* polynomialC2W, n_pol coefficients */
+    double invpol[EGOTAP_OCAM_MAX_INVPOL]; /* polynomialW2C, n_invpol coefficients */
+    double xc, yc, c, d, e;
+    double ue_flip;
+    int32_t n_pol, n_invpol;
+} egotap_ocam;
+int egotap_ocam_project(const float* points3d, int N, const egotap_ocam* model, float* points2d, void* stream);
+int egotap_ocam_unproject(const float* points2d, int N, const egotap_ocam* model, float* rays, void* stream);
+int egotap_stereo_triangulate(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
+                              const double* affine, double min_score, const float* pose, int P, int pose_row0, float* joints3d, float* frame, void* stream);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

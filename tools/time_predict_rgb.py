@@ -14,6 +14,7 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
   graphed     predict_pose_from_rgb(graphed=True): the same pipeline replayed from a captured graph (includes the copy into its static inputs)
   keypoints   predict_pose_from_rgb(return_keypoints=True): the 2D joints and confidences from the same call
   limbs       predict_pose_from_rgb(return_limbs=True): the limb elevation angles and 2D segments from the same call
+  triangulation  predict_pose_from_rgb(return_triangulation=True): the keypoints triangulated through a stereo rig, one more launch behind the call
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -44,6 +45,10 @@ def build_model():
     m.net_HeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(15, "hm_pos.").items()})
     m.net_RotHeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(30, "hm_rot.").items()})
     m.eval()
+    # a rig for the triangulation arm: the launch's time depends on the polynomials' lengths, not on their values (a 5-coefficient pol as OCamCalib
+    # exports it, 16 invpol coefficients)
+    cam = spec.OcamModel(name="unreal_ego_pose", pol=(-330.0, 0.0, 1.1e-3, -4.0e-7, 1.2e-9), invpol=(480.0,) + (1.0,) * 15, xc=512.0, yc=512.0)
+    m.set_stereo_rig(cam, cam, (0.12, 0.0, 0.0))
     return m, p
 
 
@@ -76,6 +81,7 @@ def arms_for(m, p, left, right):
     return {"parent": parent,
             "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
             "limbs": lambda: m.predict_pose_from_rgb(left, right, return_limbs=True)[0],
+            "triangulation": lambda: m.predict_pose_from_rgb(left, right, return_triangulation=True)[0],
             "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
@@ -204,7 +210,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation") else ""
                 print(f"{setting:12s} B={B:<4d} {k:12s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
