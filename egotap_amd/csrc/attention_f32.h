@@ -26,13 +26,16 @@ template <int NW>
 __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* __restrict__ QKV,
                                                                  float* __restrict__ CTX, int N, int heads,
                                                                  int qgroups, float scale_log2e, float* __restrict__ LSE, int ksplit,
-                                                                 const float* __restrict__ Qsrc, long ldq, int Nq) {
+                                                                 const float* __restrict__ Qsrc, long ldq, int Nq, int shared_from) {
     // [r4] ksplit > 1 (serving batches: B x heads x query groups is a fraction of the chip): workgroup (pair, query group, split) attends to
     // key tiles [split * ntiles / ksplit, ...) only and writes its own normalised output and log-sum-exp -- CTX / LSE are then the PARTIAL
     // buffers [ksplit][B * N][D] / [ksplit][B * heads * N], merged by attention_f32_merge_kernel.
     // [r6] Queries: Nq per image, row b * Nq + q of Qsrc (row stride ldq); CTX / LSE rows follow the queries.  The full forward passes
     // Qsrc = QKV, ldq = 3 D, Nq = N; the pose-only forward's last layer passes its compact live-token Q (Nq = T ppd^2 < N) against the
     // physical K / V of all N tokens.
+    // shared_from (a multiple of 32; N = nothing shared, every caller but layer 0 of the pose-only forward): tokens [shared_from, N) are the same in
+    // every image and only image 0 holds their Q / K / V rows -- key tiles and query blocks from there on read image 0's rows (a wave-uniform base
+    // select per tile / block); CTX stays per image (the shared queries attend to each image's own keys).
     using Cfg = AttnCfg<NW>;
     constexpr int DH = Cfg::DH, KT = Cfg::KT, KLD = Cfg::KLD, THREADS = Cfg::THREADS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -53,6 +56,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
     const int D = heads * DH;
     const long ld = 3L * D;
     const float* base = QKV + (long)b * N * ld + h * DH;     // q of token 0 of this (b, h)
+    const float* base0 = QKV + h * DH;                         // ... of image 0: the shared tokens' rows
     const int qb = qg * NW + wid;                              // 32-row query block of this wave
     const bool valid = qb * 32 < Nq;                           // wave-uniform
     // [r5] N need not be a multiple of 32 (the reference allows any heatmap side that is a multiple of 16, net_architecture.py:327: N = 144 at
@@ -62,7 +66,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
 
     float qreg[64];
     {
-        const float* qp = Qsrc + ((long)b * Nq + q0 + l31) * ldq + h * DH + 4 * lh;
+        const float* qp = Qsrc + ((long)(q0 >= shared_from ? 0 : b) * Nq + q0 + l31) * ldq + h * DH + 4 * lh;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const f32x4 v = *(const f32x4*)(qp + 8 * t);
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
     constexpr int PER = KT * (DH / 4) / THREADS;
     f32x4 stg[PER];
     auto tile_req = [&](int kt, int vpart) __attribute__((always_inline)) {      // vpart: 0 = K rows, 1 = V rows of key tile kt
-        const float* kp = base + (long)min(kt * KT, N - KT) * ld + D + vpart * D;
+        const float* kp = (kt * KT >= shared_from ? base0 : base) + (long)min(kt * KT, N - KT) * ld + D + vpart * D;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
             const int idx = tid + i * THREADS, row = idx >> 5, c4 = idx & 31;
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
     // accumulators are not live yet: a second staging set costs nothing) -- they were two dependent round trips in front of every block's first MFMA
     {
         f32x4 stg2[PER];
-        const float* vp = base + (long)min(kt0 * KT, N - KT) * ld + 2 * D;
+        const float* vp = (kt0 * KT >= shared_from ? base0 : base) + (long)min(kt0 * KT, N - KT) * ld + 2 * D;
         tile_req(kt0, 0);
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
@@ -279,7 +283,7 @@ static hipError_t attention_f32_launch(const float* QKV, float* CTX, int B, int 
         float* part = scratch;
         float* lse_part = scratch + (size_t)ksplit * B * N * heads * 128;
         hipLaunchKernelGGL(kern, dim3((unsigned)(wgs * ksplit)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, part, N, heads, qgroups, scale_log2e, lse_part, ksplit,
-                           QKV, 3L * heads * Cfg::DH, N);
+                           QKV, 3L * heads * Cfg::DH, N, N);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         const long total = (long)B * N * heads * 32;
@@ -287,7 +291,22 @@ static hipError_t attention_f32_launch(const float* QKV, float* CTX, int B, int 
         return hipGetLastError();
     }
     hipLaunchKernelGGL(kern, dim3(B * heads * qgroups), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, CTX, N, heads,
-                       qgroups, scale_log2e, LSE, 1, QKV, 3L * heads * Cfg::DH, N);
+                       qgroups, scale_log2e, LSE, 1, QKV, 3L * heads * Cfg::DH, N, N);
+    return hipGetLastError();
+}
+
+// Layer 0 of the pose-only forward: tokens [shared_from, N) of every image are those of image 0 (see the kernel); rows (b > 0, n >= shared_from) of
+// QKV are not read.  Unsplit, no LSE.  shared_from = N: attention_f32_launch without a key split.
+static hipError_t attention_f32_shared_launch(const float* QKV, float* CTX, int B, int N, int heads, int shared_from, hipStream_t stream) {
+    constexpr int NW = 2;
+    using Cfg = AttnCfg<NW>;
+    if (B <= 0) return hipSuccess;
+    if (N < 32 || N % 4 != 0 || shared_from <= 0 || shared_from > N) return hipErrorInvalidValue;
+    if (shared_from < N && (N % 32 != 0 || shared_from % 32 != 0)) return hipErrorInvalidValue;      // whole key tiles and query blocks on both sides of the seam
+    const int qgroups = ((N + 31) / 32 + NW - 1) / NW;
+    const float scale_log2e = 1.4426950408889634f / sqrtf(128.0f);
+    hipLaunchKernelGGL(attention_f32_kernel<NW>, dim3(B * heads * qgroups), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, CTX, N, heads,
+                       qgroups, scale_log2e, (float*)nullptr, 1, QKV, 3L * heads * Cfg::DH, N, shared_from);
     return hipGetLastError();
 }
 
@@ -301,6 +320,6 @@ static hipError_t attention_f32_live_launch(const float* Q, long ldq, int Nq, co
     const int qgroups = ((Nq + 31) / 32 + NW - 1) / NW;
     const float scale_log2e = 1.4426950408889634f / sqrtf(128.0f);
     hipLaunchKernelGGL(attention_f32_kernel<NW>, dim3(B * heads * qgroups), dim3(Cfg::THREADS), Cfg::LDS_BYTES, stream, QKV, CTX, N, heads,
-                       qgroups, scale_log2e, (float*)nullptr, 1, Q, ldq, Nq);
+                       qgroups, scale_log2e, (float*)nullptr, 1, Q, ldq, Nq, N);
     return hipGetLastError();
 }

@@ -518,6 +518,7 @@ template <> struct AlName<ALoadPlain> { static constexpr const char* v = "ALoadP
 template <> struct AlName<ALoadPatch> { static constexpr const char* v = "ALoadPatch"; };
 template <> struct AlName<ALoadTokens> { static constexpr const char* v = "ALoadTokens"; };
 template <> struct AlName<ALoadLive> { static constexpr const char* v = "ALoadLive"; };
+template <> struct AlName<ALoadHead> { static constexpr const char* v = "ALoadHead"; };
 template <> struct AlName<ALoadRot> { static constexpr const char* v = "ALoadRot"; };
 template <> struct AlName<ALoadStereo> { static constexpr const char* v = "ALoadStereo"; };
 template <> struct AlName<ALoadStereoGated> { static constexpr const char* v = "ALoadStereoGated"; };
@@ -525,6 +526,7 @@ template <class E> struct EpiName;
 template <> struct EpiName<EpiBias> { static constexpr const char* v = "EpiBias"; };
 template <> struct EpiName<EpiBiasRes> { static constexpr const char* v = "EpiBiasRes"; };
 template <> struct EpiName<EpiBiasResLive> { static constexpr const char* v = "EpiBiasResLive"; };
+template <> struct EpiName<EpiBiasHead> { static constexpr const char* v = "EpiBiasHead"; };
 template <> struct EpiName<EpiBiasGelu> { static constexpr const char* v = "EpiBiasGelu"; };
 template <> struct EpiName<EpiBnLrelu> { static constexpr const char* v = "EpiBnLrelu"; };
 template <> struct EpiName<EpiPatch> { static constexpr const char* v = "EpiPatch"; };
@@ -979,6 +981,25 @@ static bool lift_prune_last(Handle* h, int B) {
     return attention_f32_ksplit(B, h->seq, h->cfg.vit_heads, SPLITK_FLOATS, cus) == 1;
 }
 
+// Whether the pose-only forward projects layer 0's frame-invariant rows once per call.  The grid's dummy cells hold mask_token + position embedding
+// in every image, so their LayerNorm-1 rows and their layer-0 q | k | v are those of image 0.  Where the dummy cells are whole trailing grid rows the
+// shared tokens are the contiguous tail [n0, seq) of every image: layer 0 then projects the B * n0 live rows as ONE compact product (ALoadHead /
+// EpiBiasHead, the 256 x 256 kernel) and image 0's tail as a second, small one, and its attention reads the tail's Q / K / V from image 0
+// (attention_f32_shared_launch).  Every product involved is row-independent and runs unsplit with the k order of the full forward's, so the pose
+// keeps its bits -- provided the full product is unsplit too (GS_BIG, as is the live one) and the attention is; the seam must fall between whole
+// 32-token attention tiles.  Returns n0, or 0: layer 0 as in the full forward.
+static int lift_share_layer0(Handle* h, int B, bool pose_only) {
+    const int D = h->D, seq = h->seq, rows = h->T / h->grid;
+    if (!pose_only || h->precision != EGOTAP_PREC_F32 || h->debug_stop != 0 || h->cfg.vit_layers < 2) return 0;
+    if (h->T >= h->grid * h->grid || h->T % h->grid != 0 || rows < 1) return 0;
+    const int n0 = rows * h->ppd * h->side;
+    if (n0 % 32 != 0 || seq % 32 != 0 || D % DmaF32Cfg::BN != 0 || D % DmaF32Cfg::BK != 0) return 0;
+    if ((long)B * seq >= (1L << 31) || !HeadRows::make(n0, seq).exact((long)B * n0)) return 0;
+    const int cus = device_cu_count();
+    if (gemm_small_route(h, true, B * seq, 3 * D, D, D, cus, true).kind != GS_BIG || gemm_small_route(h, true, B * n0, 3 * D, D, D, cus, true).kind != GS_BIG) return 0;
+    return attention_f32_ksplit(B, seq, h->cfg.vit_heads, SPLITK_FLOATS, cus) == 1 ? n0 : 0;
+}
+
 // ---- frozen-weight serving: the arena of egotap_lift_freeze.  Every bf16 weight copy the bf16-storage inference forward multiplies by, in the layout
 // its GEMMs read (row-major [N][K]; q | k | v stacked as one [3D][D] block), and per layer the fused q | k | v bias (fp32); 256-byte aligned slices.
 // p != nullptr: fills T, the segment table of prep_weights_all_kernel (bf16s_ops.h).
@@ -1169,6 +1190,7 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
     // where the projection is split over K (serving batches); ln1 of layer i + 1 (or the final LayerNorm) therefore rides with layer i's MLP.
     const int NL = h->cfg.vit_layers;
     const bool prune = pose_only && lift_prune_last(h, B);
+    const int share0 = lift_share_layer0(h, B, pose_only);       // > 0: layer 0's tokens from here on are projected for image 0 only
     EGO_HIP(launch_ln(X, Y, NL > 0 ? p.layer[0].ln1_g : p.lnf_g, NL > 0 ? p.layer[0].ln1_b : p.lnf_b, M, 1e-12f, s));
     for (int i = 0; i < NL; ++i) {
         const auto& L = p.layer[i];
@@ -1194,10 +1216,23 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
         {
             SegMat Wqkv; Wqkv.p[0] = L.q_w; Wqkv.p[1] = L.k_w; Wqkv.p[2] = L.v_w; Wqkv.seg = D; Wqkv.ld = D;
             SegVec bqkv; bqkv.p[0] = L.q_b; bqkv.p[1] = L.k_b; bqkv.p[2] = L.v_b; bqkv.seg = D;
+            if (i == 0 && share0 > 0) {
+                // the live rows of every image: one launch of the 256 x 256 kernel over B * n0 compact rows, read from and stored to their physical
+                // rows; then the shared tail of image 0, unsplit 128 x 128 tiles.  Rows (b > 0, n >= n0) of QKV are neither written nor read.
+                const HeadRows hr = HeadRows::make(share0, h->seq);
+                const int Ml = B * share0;
+                {
+                    static const std::string kdma = std::string("gemm_f32_dma_kernel<256x256x16,") + AlName<ALoadHead>::v + "," + EpiName<EpiBiasHead>::v + ">";
+                    GemmTimer t(h, s, "qkv", kdma.c_str(), 2.0 * Ml * 3 * D * D);
+                    EGO_HIP(gemm_f32_dma_launch(ALoadHead{Y, D, hr}, Wqkv, EpiBiasHead{{bqkv}, QKV, 3L * D, hr}, QKV, 3L * D, Ml, 3 * D, D, device_cu_count(), s));
+                }
+                EGO_HIP((gemm<TileA>(h, "qkv_shared", ALoadPlain{Y + (long)share0 * D, D}, Wqkv, EpiBias{bqkv}, QKV + (long)share0 * 3 * D, 3L * D, h->seq - share0, 3 * D, D, s)));
+            } else
             EGO_HIP((gemm_small(h, "qkv", ALoadPlain{Y, D}, Wqkv, EpiBias{bqkv}, QKV, 3L * D, M, 3 * D, D, SPK, s)));
         }
         if (h->precision == EGOTAP_PREC_BF16X3 && h->seq % 32 == 0) EGO_HIP(attention_bf16_launch<3>(QKV, CTX, B, h->seq, h->cfg.vit_heads, s));
         else if (h->precision == EGOTAP_PREC_BF16 && h->seq % 32 == 0) EGO_HIP(attention_bf16_launch<1>(QKV, CTX, B, h->seq, h->cfg.vit_heads, s));
+        else if (i == 0 && share0 > 0) EGO_HIP(attention_f32_shared_launch(QKV, CTX, B, h->seq, h->cfg.vit_heads, share0, s));
         else EGO_HIP(attention_f32_launch(QKV, CTX, B, h->seq, h->cfg.vit_heads, s, nullptr, SPK, SPLITK_FLOATS, device_cu_count()));   // (SPK: free between the GEMMs; key-split partials at B <= 2)
         EGO_HIP(gemm_res_ln(h, "attn_out", CTX, D, L.o_w, L.o_b, X, M, D, D, L.ln2_g, L.ln2_b, Y, SPK, s));
         EGO_HIP((gemm_small(h, "mlp_up", ALoadPlain{Y, D}, segmat1(L.up_w, 4 * D, D), EpiBiasGelu{segvec1(L.up_b, 4 * D)}, HID, 4L * D, M, 4 * D, D, SPK, s)));
@@ -2809,6 +2844,18 @@ extern "C" int egotap_attention_f32(const float* qkv, float* ctx, int B, int N, 
     EGO_CHECK(N >= 32 && N % 4 == 0, "egotap_attention_f32: sequence length must be at least 32 and a multiple of 4 (any heatmap side that is a multiple of 16)");
     EGO_CHECK(heads > 0, "egotap_attention_f32: heads must be positive");
     EGO_HIP(attention_f32_launch(qkv, ctx, B, N, heads, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+#endif
+
+// (test hook) the exact-fp32 attention with the tokens from shared_from on read from image 0's rows: layer 0 of the pose-only forward
+#if EGOTAP_IN(0)
+extern "C" int egotap_debug_attention_f32_shared(const float* qkv, float* ctx, int B, int N, int heads, int shared_from, void* stream) {
+    EGO_CHECK(qkv && ctx, "egotap_debug_attention_f32_shared: null argument");
+    EGO_CHECK(B >= 0 && N >= 32 && N % 4 == 0 && heads > 0, "egotap_debug_attention_f32_shared: bad shape B=%d N=%d heads=%d", B, N, heads);
+    EGO_CHECK(shared_from > 0 && shared_from <= N && (shared_from == N || (N % 32 == 0 && shared_from % 32 == 0)),
+              "egotap_debug_attention_f32_shared: shared_from=%d must be N, or a multiple of 32 below N with N a multiple of 32", shared_from);
+    EGO_HIP(attention_f32_shared_launch(qkv, ctx, B, N, heads, shared_from, (hipStream_t)stream));
     return EGOTAP_OK;
 }
 #endif

@@ -109,6 +109,34 @@ struct ALoadLive {
     __host__ bool dma_ok() const { return lda % 4 == 0 && lda < (1L << 21) && ((uintptr_t)A & 15) == 0; }
 };
 
+// The first n0 tokens of every image as compact rows: row m = (b, n < n0) -> physical row b * seq + n.  Layer 0 of the pose-only forward
+// projects these per image and the tokens behind them (the grid's dummy cells, the same in every image) once per call.
+// b = m / n0 as one multiply-high: magic = floor(2^32 / n0) + 1 = (2^32 + e) / n0 with 1 <= e <= n0, so m * magic / 2^32 =
+// m / n0 + m e / (n0 2^32), whose floor is that of m / n0 while m e < 2^32 -- guaranteed by m * n0 < 2^32 (exact(): the host checks it).
+struct HeadRows {
+    int n0, seq;
+    unsigned magic;
+    static HeadRows make(int n0, int seq) { return HeadRows{n0, seq, (unsigned)((1ull << 32) / (unsigned)n0 + 1)}; }
+    bool exact(long rows) const { return n0 > 1 && rows > 0 && (unsigned long long)rows * (unsigned)n0 < (1ull << 32); }
+    __host__ __device__ __forceinline__ long phys(int m) const {
+        const int b = (int)(((unsigned long long)(unsigned)m * magic) >> 32);
+        return (long)b * seq + (m - b * n0);
+    }
+};
+struct ALoadHead {
+    const float* A;    // [B * seq, lda] physical rows
+    long lda;
+    HeadRows hr;
+    struct Row { const float* p; };
+    __device__ __forceinline__ Row row(int m) const { return Row{A + hr.phys(m) * lda}; }
+    __device__ __forceinline__ f32x4 load(const Row& r, int k) const { return *(const f32x4*)(r.p + k); }
+    static constexpr bool HAS_PTR = true;
+    __device__ __forceinline__ const float* ptr(const Row& r, int k) const { return r.p + k; }
+    // (a 256-row tile touches at most 256 / n0 + 2 images, so its rows lie within that many * seq physical rows of its first: 32-bit byte
+    // offsets from a per-tile base)
+    __host__ bool dma_ok() const { return lda % 4 == 0 && (256L / hr.n0 + 2) * hr.seq * lda * 4 < (1L << 31) && ((uintptr_t)A & 15) == 0; }
+};
+
 // fc1 of the rotation encoder: row (b, eye*J + j) = [cos map | sin map] of limb j of that eye.
 // Reference: net_architecture.py:690-694 (channel order L_cos, L_sin, R_cos, R_sin after 2J position maps).
 struct ALoadRot {
@@ -368,15 +396,29 @@ struct EpiScatterRot : EpiNone {      // inverse of ALoadRot: row (b, eye * J + 
         return hm + (long)(b * C + 2 * J + eye * 2 * J + cs * J + j) * HW + (n - cs * HW);
     }
 };
+// ---- C = acc + bias, compact row m stored to its physical row of C (HeadRows): the pose-only forward's layer-0 q | k | v of the live tokens
+struct EpiBiasHead : EpiBias {
+    float* C;
+    long ldc;
+    HeadRows hr;
+    static constexpr bool DST_ALWAYS = true;      // dst() is never null: the stores stay unconditional
+    __device__ __forceinline__ float* dst(int m, int n) const { return C + hr.phys(m) * ldc + n; }
+};
 template <class E> struct epi_scatters : std::false_type {};
 template <> struct epi_scatters<EpiScatterPatch> : std::true_type {};
 template <> struct epi_scatters<EpiScatterRot> : std::true_type {};
+template <> struct epi_scatters<EpiBiasHead> : std::true_type {};
+template <class E, class = void> struct epi_dst_always : std::false_type {};
+template <class E> struct epi_dst_always<E, std::enable_if_t<E::DST_ALWAYS>> : std::true_type {};
 // the output stores of gemm_f32_kernel, gemm_f32_dma_kernel and gemm_bf16_persist_kernel (the kernels a scattering epilogue is
 // instantiated with; the others refuse one at compile time): row-major C, or the epilogue's own address (4 consecutive n stay contiguous:
 // n0 is a multiple of 4 and a patch run / heatmap plane holds a multiple of 4 floats)
+// DST_ALWAYS (EpiBiasHead): dst() is never null and the store unconditional, which the DMA kernel's full-tile epilogue relies on (see there)
 template <class Epi>
 __device__ __forceinline__ void epi_store(const Epi& epi, float* C, long ldc, int m, int n, float v) {
-    if constexpr (epi_scatters<Epi>::value) {
+    if constexpr (epi_dst_always<Epi>::value) {
+        *epi.dst(m, n) = v;
+    } else if constexpr (epi_scatters<Epi>::value) {
         if (float* p = epi.dst(m, n)) *p = v;
     } else {
         C[(long)m * ldc + n] = v;
@@ -384,7 +426,9 @@ __device__ __forceinline__ void epi_store(const Epi& epi, float* C, long ldc, in
 }
 template <class Epi>
 __device__ __forceinline__ void epi_store4(const Epi& epi, float* C, long ldc, int m, int n0, const f32x4& v) {
-    if constexpr (epi_scatters<Epi>::value) {
+    if constexpr (epi_dst_always<Epi>::value) {
+        *(f32x4*)epi.dst(m, n0) = v;
+    } else if constexpr (epi_scatters<Epi>::value) {
         if (float* p = epi.dst(m, n0)) *(f32x4*)p = v;
     } else {
         *(f32x4*)(C + (long)m * ldc + n0) = v;

@@ -57,7 +57,9 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
     typename ALoad::Row ra0, ra1;
     // [r5] plain row-major operands: a wave-uniform 64-bit base per tile (scalar registers) + a 32-bit byte offset per lane -- the global_load_lds
     // s[base] form -- instead of a 64-bit pointer per lane (the A/B is recorded in profiles/r05_dma_addressing_ab.log).  W is always plain rows.
-    constexpr bool SBA = std::is_same<ALoad, ALoadPlain>::value;
+    // ALoadHead likewise: its rows ascend, so a tile's rows are non-negative offsets from the tile's first row.
+    constexpr bool HEAD = std::is_same<ALoad, ALoadHead>::value;
+    constexpr bool SBA = std::is_same<ALoad, ALoadPlain>::value || HEAD;
     unsigned long long abase = 0, wbase = 0;
     unsigned ao0 = 0, ao1 = 0;
     auto uniform64 = [](const void* p) __attribute__((always_inline)) { return lds_dma_base(p); };      // lds_dma.h
@@ -66,7 +68,12 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
     auto set_rows = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
         tile_of(i, tm, tn);
-        if constexpr (SBA) {
+        if constexpr (HEAD) {
+            const long p0 = al.hr.phys(tm * BM), ld = al.lda * 4;
+            abase = uniform64(al.A + p0 * al.lda);
+            ao0 = (unsigned)((al.hr.phys(min(tm * BM + wid * 16 + drow, M - 1)) - p0) * ld + dchunk * 16);
+            ao1 = (unsigned)((al.hr.phys(min(tm * BM + (wid + 8) * 16 + drow, M - 1)) - p0) * ld + dchunk * 16);
+        } else if constexpr (SBA) {
             abase = uniform64(al.A + (long)tm * BM * al.lda);
             const long ld = al.lda * 4;                                                                      // bytes per row
             ao0 = (unsigned)((long)(min(tm * BM + wid * 16 + drow, M - 1) - tm * BM) * ld + dchunk * 16);

@@ -112,6 +112,7 @@ _PROTOS = {
     "egotap_linear_bf16_dma": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
     "egotap_layernorm_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "egotap_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "egotap_debug_attention_f32_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "egotap_pose_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_pose_metrics_batch_axes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -588,6 +589,16 @@ def layernorm(x, gamma, beta, eps: float = 1e-12):
     rows = x.numel() // x.shape[-1]
     check(load().egotap_layernorm_f32(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), rows, x.shape[-1], eps, _stream()))
     return y
+
+
+def attention_f32_shared(qkv, B: int, N: int, heads: int, shared_from: int):
+    """(test hook, egotap_debug.h) the exact-fp32 attention where tokens [shared_from, N) are the same in every image: their q | k | v rows are
+    read from image 0, rows (b > 0, n >= shared_from) of qkv not at all.  qkv [B*N, 3*heads*128] -> ctx [B*N, heads*128]"""
+    import torch
+    _need_cuda_f32(qkv)
+    ctx = torch.empty((B * N, heads * 128), device=qkv.device, dtype=torch.float32)
+    check(load().egotap_debug_attention_f32_shared(_ptr(qkv), _ptr(ctx), B, N, heads, shared_from, _stream()))
+    return ctx
 
 
 def attention(qkv, B: int, N: int, heads: int, precision: str = "f32"):

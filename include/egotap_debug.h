@@ -22,6 +22,12 @@ int egotap_debug_pu_drop_workgroups(egotap_handle h, int n);
  * 2+i = return after ViT layer i.  The state is then readable as intermediate "x". */
 int egotap_lift_debug_stop(egotap_handle h, int stage);
 
+/* ---- layer 0 of the pose-only forward (egotap_lift_predict_pose at batches that fill the chip): the exact-fp32 attention of egotap_attention_f32
+ * where tokens [shared_from, N) are the same in every image and only image 0 holds their rows of qkv [B * N, 3 * heads * 128]: key tiles and query
+ * blocks from shared_from on read image 0's rows; rows (b > 0, n >= shared_from) of qkv are not read; ctx [B * N, heads * 128] is written for every
+ * image.  shared_from = N shares nothing (any N egotap_attention_f32 takes); below N both must be multiples of 32. */
+int egotap_debug_attention_f32_shared(const float* qkv, float* ctx, int B, int N, int heads, int shared_from, void* stream);
+
 /* ---- measurement / test switch (process wide, one definition in the library): which K-tile depth the bf16-storage NT GEMM with plain
  * operands uses: 0 (default) = 64-deep kernel (csrc/gemm_bf16s64.h) where the shape allows, else the 32-deep one (csrc/gemm_bf16s.h);
  * 32 / 64 = always that one (64 fails on shapes it does not take).  Both run the same MFMAs in the same k order: bit-identical results. */
