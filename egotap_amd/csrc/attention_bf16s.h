@@ -116,10 +116,8 @@ __device__ __forceinline__ void store_rows_bf16(const f32x16 (&o)[4], float mul,
 }
 }  // namespace attns
 
-// ------------------------------------------------------------------------------------------------- forward
-// SUB sub-tiles of 32 keys per barrier pair.  The running maximum is only raised (and the output accumulators rescaled) when a
-// query's scores exceed it by more than 2^RESC in the softmax's base-2 units (cdna_hip_programming.md T13): probabilities then
-// stay below 2^RESC, harmless in fp32 sums and bf16 operands, and the 64 multiplies per sub-tile disappear from almost every tile.
+// ------------------------------------------------------------------------------------------------- dQ (register-staged; N % 64 != 0)
+// SUB sub-tiles of 32 keys per barrier pair.
 template <int NW, int SUB>
 __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq_bf16s_kernel(const __bf16* __restrict__ QKV, const __bf16* __restrict__ O,
                                                                       const __bf16* __restrict__ dO, const float* __restrict__ LSE,
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq_bf16s_kernel(const __b
     if (valid) store_rows_bf16(dq, 1.0f, (float*)bsm_s + wid * 32 * OLD, dQKV + ((long)b * N + q0) * ld3 + h * DH, ld3, lane);
 }
 
-// ------------------------------------------------------------------------------------------------- dK and dV
+// ------------------------------------------------------------------------------------------------- launchers (forward, backward)
 static hipError_t attention_bf16s3_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream);      // attention_bf16s2.h
 static hipError_t attention_bf16s_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream) {
     if (B <= 0) return hipSuccess;

@@ -27,19 +27,9 @@ constexpr int TILEB = 32 * 256;                    // one 32 x 128 bf16 image
 constexpr int LSB = 256;                           // 32 log-sum-exp + 32 delta values (fp32)
 constexpr int BUF = 2 * TILEB + LSB;               // Q image | dO image | lse, delta
 
-__device__ __forceinline__ void dma16(const void* g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-}
-// [r5] the same DMA with the address as a wave-uniform 64-bit base (scalar registers) + a 32-bit byte offset per lane: every tile of these kernels is
-// "uniform tile origin + a lane pattern fixed for the whole kernel", so the per-lane 64-bit add (and the 64-bit address operand) of the flat form is dropped.
+// [r5] the DMAs (lds_dma.h) take their address as a wave-uniform 64-bit base (scalar registers) + a 32-bit byte offset per lane: every tile of these kernels
+// is "uniform tile origin + a lane pattern fixed for the whole kernel", so the per-lane 64-bit add (and the 64-bit address operand) of the flat form is dropped.
 // The A/B against the per-lane pointer form is recorded in profiles/r05_attention_ab.log.
-__device__ __forceinline__ unsigned long long uniform64(const void* p) { return lds_dma_base(p); }      // lds_dma.h
-__device__ __forceinline__ void dma16s(unsigned voff, unsigned long long sbase, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-}
-__device__ __forceinline__ void dma4(const void* g, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-}
 
 // element offset (row * ld + column) this lane fetches for DMA piece e (0..7) of a 32 x 128 tile whose rows are ld elements apart:
 // piece e covers image bytes [1024 e, 1024 e + 1024) = rows 8 (e >> 1) .. + 7, column blocks 2 (e & 1) and 2 (e & 1) + 1
@@ -140,26 +130,26 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dkv_bf16s2_kernel(const _
     const int kb = kg * NW + wid;
     const bool valid = kb * 32 < N;            // invalid waves (last group of a head) redo the last key block and skip the store
     const int k0 = min(kb * 32, N - 32);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)sm2;
+    const unsigned lds0 = lds_addr_of(sm2);
     const unsigned vimg = 2 * BUF + wid * TILEB;               // this wave's V rows (dP = dO V^T reads them as the B operand)
 
     Frags<1> kf;                                               // K rows of this wave's 32 keys, all 128 d: B operand of S = Q K^T
     attns::load_row_frags(kf, qkv + (long)(k0 + l31) * ld3 + D, lh);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) dma16(qkv + (long)k0 * ld3 + 2 * D + dma_src(e, lane, ld3), lds0 + vimg + 1024 * e);
+    for (int e = 0; e < 8; ++e) lds_dma16(qkv + (long)k0 * ld3 + 2 * D + dma_src(e, lane, ld3), lds0 + vimg + 1024 * e);
 
     // DMA duty per tile: 8-row group `wid` of the Q tile and of the dO tile (two pieces each); wave 0 also fetches lse | delta
     const unsigned oq0 = 2u * dma_src(2 * wid, lane, ld3), oq1 = 2u * dma_src(2 * wid + 1, lane, ld3);      // byte offsets from the tile's first row
     const unsigned od0 = 2u * dma_src(2 * wid, lane, D), od1 = 2u * dma_src(2 * wid + 1, lane, D);
     auto issue = [&](int qt, unsigned boff) __attribute__((always_inline)) {
-        const unsigned long long qs = uniform64(qkv + (long)(qt * 32) * ld3);
-        const unsigned long long ds = uniform64(dob + (long)(qt * 32) * D);
+        const unsigned long long qs = lds_dma_base(qkv + (long)(qt * 32) * ld3);
+        const unsigned long long ds = lds_dma_base(dob + (long)(qt * 32) * D);
         const unsigned a = lds0 + boff + 2048 * wid;
-        dma16s(oq0, qs, a);
-        dma16s(oq1, qs, a + 1024);
-        dma16s(od0, ds, a + TILEB);
-        dma16s(od1, ds, a + TILEB + 1024);
-        if (wid == 0) dma4((lane < 32 ? lsep : delp - 32) + qt * 32 + lane, lds0 + boff + 2 * TILEB);
+        lds_dma16(oq0, qs, a);
+        lds_dma16(oq1, qs, a + 1024);
+        lds_dma16(od0, ds, a + TILEB);
+        lds_dma16(od1, ds, a + TILEB + 1024);
+        if (wid == 0) lds_dma4((lane < 32 ? lsep : delp - 32) + qt * 32 + lane, lds0 + boff + 2 * TILEB);
     };
     const LaneAddr la = lane_addr(lane);
     const float c2 = scale * 1.4426950408889634f;
@@ -252,7 +242,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq_bf16s2_kernel(const __
     const bool valid = qb * 32 < N;
     const int q0 = min(qb * 32, N - 32);
     const long orow = ((long)b * N + q0 + l31) * D + h * DH;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)sm2;
+    const unsigned lds0 = lds_addr_of(sm2);
     unsigned ok[4];                                            // this wave's 4 K pieces of a step, in bytes from the step's first row (the V pieces sit D elements further)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -260,12 +250,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_dq_bf16s2_kernel(const __
         ok[i] = 2u * (unsigned)(32 * (e >> 3) * ld3 + D + dma_src(e & 7, lane, ld3));
     }
     auto issue = [&](int kt, unsigned boff) __attribute__((always_inline)) {
-        const unsigned long long src = uniform64(qkv + (long)(kt * 64) * ld3);
+        const unsigned long long src = lds_dma_base(qkv + (long)(kt * 64) * ld3);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const unsigned a = lds0 + boff + 1024 * (4 * wid + i);         // piece e of the step: image e >> 3, piece e & 7 = byte 1024 e
-            dma16s(ok[i], src, a);
-            dma16s(ok[i], src + 2ull * D, a + 2 * TILEB);
+            lds_dma16(ok[i], src, a);
+            lds_dma16(ok[i], src + 2ull * D, a + 2 * TILEB);
         }
     };
     issue(0, 0);
@@ -378,6 +368,9 @@ __global__ __launch_bounds__(64 * NW, 3) void attention_bf16s3_kernel(const __bf
     using namespace att2;
     static_assert(NW >= 2 && NW <= 4, "the workgroup's waves share the 8 + 8 DMA pieces of a 32-key step");
     constexpr unsigned KVBUF = 2 * TILEB;                      // K image | V image
+    // The running maximum is only raised (and the output accumulators rescaled) when a query's scores exceed it by more than 2^RESC in the
+    // softmax's base-2 units (cdna_hip_programming.md T13): probabilities then stay below 2^RESC, harmless in fp32 sums and bf16 operands,
+    // and the 64 multiplies per step disappear from almost every tile.
     constexpr float RESC = 6.0f;
     extern __shared__ __attribute__((aligned(16))) char sm3[];
     const int lin = xcd_lin(blockIdx.x, gridDim.x);
@@ -390,19 +383,19 @@ __global__ __launch_bounds__(64 * NW, 3) void attention_bf16s3_kernel(const __bf
     const int qb = qg * NW + wid;
     const bool valid = qb * 32 < N;
     const int q0 = min(qb * 32, N - 32);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)sm3;
+    const unsigned lds0 = lds_addr_of(sm3);
     constexpr int PPW = (8 + NW - 1) / NW;                     // pieces per wave: wave w takes pieces w, w + NW, ... < 8 of the K and of the V image
     unsigned ok[PPW];                                          // bytes from the tile's first row
 #pragma unroll
     for (int i = 0; i < PPW; ++i) ok[i] = 2u * (unsigned)(D + dma_src(min(wid + i * NW, 7), lane, ld3));
     auto issue = [&](int kt, unsigned boff) __attribute__((always_inline)) {
-        const unsigned long long src = uniform64(qkv + (long)(kt * 32) * ld3);
+        const unsigned long long src = lds_dma_base(qkv + (long)(kt * 32) * ld3);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
             if (wid + i * NW < 8) {                             // wave-uniform
                 const unsigned a = lds0 + boff + 1024 * (wid + i * NW);
-                dma16s(ok[i], src, a);
-                dma16s(ok[i], src + 2ull * D, a + TILEB);
+                lds_dma16(ok[i], src, a);
+                lds_dma16(ok[i], src + 2ull * D, a + TILEB);
             }
         }
     };

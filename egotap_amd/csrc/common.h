@@ -112,6 +112,14 @@ static inline SegMat segmat1(const float* p, int n, long ld) {
     return v;
 }
 
+// the first row of the 256-row tile at row n0 of a segmented weight (SegMat / SegMatB).  The segment is uniform over a tile (seg % 256 == 0):
+// scalar selects, no indexed (vector) load of W.p[] whose vmcnt wait would drain the DMA pipeline at every tile switch
+template <class WMat>
+__device__ __forceinline__ auto seg_tile_row(const WMat& W, int n0) -> decltype(W.row(0)) {
+    const int sidx = n0 / W.seg;
+    return (sidx == 0 ? W.p[0] : (sidx == 1 ? W.p[1] : W.p[2])) + (long)(n0 - sidx * W.seg) * W.ld;
+}
+
 // blocks are dealt round-robin over the 8 XCDs: give every XCD a contiguous chunk of the linear work order (bijective for any grid;
 // placement affects speed only)
 __device__ __forceinline__ int xcd_lin(int bid, int nblk) {
@@ -125,8 +133,7 @@ __device__ __forceinline__ int xcd_lin(int bid, int nblk) {
 // walk M fastest, then N.  Bijective for any grid size; placement affects
 // speed only (cdna_hip_programming.md T1).
 __device__ __forceinline__ void xcd_tile(int bid, int nblk, int tiles_m, int tiles_n, int GM, int& tm, int& tn) {
-    const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
-    const int lin = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+    const int lin = xcd_lin(bid, nblk);
     const int per_group = GM * tiles_n;
     const int g = lin / per_group;
     const int first = g * GM;
@@ -135,3 +142,33 @@ __device__ __forceinline__ void xcd_tile(int bid, int nblk, int tiles_m, int til
     tm = first + in % gsz;
     tn = in / gsz;
 }
+
+// The same map for the persistent kernels, whose grid is smaller than the tile count: the grouped order (GM = 8) is cut into 8
+// contiguous chunks, one per XCD, and the nbx workgroups of an XCD (blockIdx % 8 equal: they share an L2) take consecutive tiles of
+// their chunk in lockstep -- workgroup jb the tiles jb, jb + nbx, ... -- so co-resident workgroups share A / W panels.  Every tile is
+// visited once for any grid size; the host's round counts (gemm_rounds) and the bit-identity between the register-staged and the DMA
+// kernels rest on all persistent GEMMs walking in this one order.
+// (tile_of repeats xcd_tile's six lines on purpose: routed through one shared function, hipcc commutes the sum in `tm` for one of the
+// two callers, and some 230 kernels come out with other register numbers or another schedule.)
+struct TileWalk {
+    int tiles_m, tiles_n;
+    int lo, jb, nbx, n;     // the chunk's first linear index, this workgroup's place in it, its stride, its number of tiles
+    __device__ __forceinline__ TileWalk(int tiles_m_, int tiles_n_) : tiles_m(tiles_m_), tiles_n(tiles_n_) {
+        const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7;
+        jb = blockIdx.x >> 3;
+        nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
+        const int q8 = ntiles >> 3, r8 = ntiles & 7;
+        lo = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
+        const int cnt = q8 + (x8 < r8 ? 1 : 0);
+        n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    }
+    __device__ __forceinline__ void tile_of(int i, int& tm, int& tn) const {
+        const int lin = lo + jb + i * nbx;
+        const int per_group = 8 * tiles_n;
+        const int g = lin / per_group, first = g * 8;
+        const int gsz = min(tiles_m - first, 8);
+        const int in = lin - g * per_group;
+        tm = first + in % gsz;
+        tn = in / gsz;
+    }
+};

@@ -18,6 +18,7 @@
 //     store: 8 lanes cover a pixel's 128 bytes.  Same fp32 formula as SEpiBnBf16 (conv_bf16s.h).
 #pragma once
 #include "conv_bf16s.h"
+#include "lds_dma.h"
 
 struct Conv64Cfg {
     static constexpr int TR = 8, TC = 32, HR = TR + 2, HC = TC + 2, HPIX = HR * HC;            // tile, halo (340 pixels)
@@ -69,7 +70,7 @@ static __global__ __launch_bounds__(Conv64Cfg::THREADS, 1) void conv64_direct_bf
             boff[dx][c2] = hx * 128 + (((2 * c2 + h) ^ ((hx >> 1) & 7)) << 4);
         }
 
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)c64_sm;
+    const unsigned lds0 = lds_addr_of(c64_sm);
     auto tile_of = [&](long t, int& n, int& y0, int& x0) __attribute__((always_inline)) {
         const int txi = (int)(t % tx_n), tyi = (int)((t / tx_n) % ty_n);
         n = (int)(t / ((long)tx_n * ty_n));
@@ -97,7 +98,7 @@ static __global__ __launch_bounds__(Conv64Cfg::THREADS, 1) void conv64_direct_bf
                 const int gy = y0 - 1 + ((dma_info[jj] >> 20) & 15), gx = x0 - 1 + ((dma_info[jj] >> 24) & 63);
                 const bool ok = !(dma_info[jj] >> 30) && gy >= 0 && gy < S && gx >= 0 && gx < S;
                 const __bf16* g = ok ? corner + (dma_info[jj] & 0xfffff) : zero;
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds0 + b * Cfg::HALO_BYTES + j * 1024)) : "memory");
+                lds_dma16(g, lds0 + b * Cfg::HALO_BYTES + j * 1024);
             }
         }
     };

@@ -82,32 +82,17 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_bf16_persist_ker
     // staging: thread -> (row sr of the 256-row tile, group sg); rows on the low lane bits (conflict-free b128 writes)
     const int sr = wid * 32 + l31, sg = lh;
 
-    // tiles of this block (same walk as gemm_f32_persist_kernel)
-    const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int lo_t = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int cnt = q8 + (x8 < r8 ? 1 : 0);
-    const int my_n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    const TileWalk walk(tiles_m, tiles_n);           // tiles of this workgroup (common.h)
     const int KT = K / BK;
-    const int total = my_n * KT;
+    const int total = walk.n * KT;
     if (total == 0) return;
-    auto tile_of = [&](int i, int& tm, int& tn) __attribute__((always_inline)) {
-        const int lin = lo_t + jb + i * nbx;
-        const int per_group = 8 * tiles_n;
-        const int g = lin / per_group, first = g * 8;
-        const int gsz = min(tiles_m - first, 8);
-        const int in = lin - g * per_group;
-        tm = first + in % gsz;
-        tn = in / gsz;
-    };
 
     typename ALoad::Row arow;
     decltype(W.row(0)) brow;
     int l_tile = 0, l_kt = 0;           // load position in this block's slab stream
     auto set_rows = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
+        walk.tile_of(i, tm, tn);
         arow = al.row(min(tm * BM + sr, M - 1));
         brow = W.row(tn * BN + sr);
     };
@@ -140,7 +125,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_bf16_persist_ker
         }                                                                                            \
         if (++l_kt == KT) {                                                                          \
             l_kt = 0;                                                                                \
-            if (++l_tile < my_n) set_rows(l_tile);                                                   \
+            if (++l_tile < walk.n) set_rows(l_tile);                                                 \
         }                                                                                            \
     }
     // registers -> bf16, half H (0 / 1) of this thread's floats of one operand.  NP = 3: floats 4H..4H+3 of its 8 give
@@ -231,7 +216,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_bf16_persist_ker
     auto epilogue = [&]() __attribute__((always_inline)) {
         // identical to gemm_f32_persist_kernel: accumulators -> per-wave LDS patch -> row-major float4 -> epilogue -> dwordx4
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         const int er = lane >> 3, ec = (lane & 7) * 4;
         const int nb0 = tn * BN + wn * (TN * 32) + ec, mb0 = tm * BM + wm * (TM * 32) + er;
         f32x4 rs[4];

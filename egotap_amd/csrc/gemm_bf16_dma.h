@@ -39,25 +39,10 @@ __global__ __launch_bounds__(DmaCfg::THREADS, 2) void gemm_bf16_dma_kernel(const
     const int l31 = lane & 31, lh = lane >> 5;
     float* Es = (float*)(smem_dma + NS * Cfg::STAGE + wid * Cfg::EPATCH);
 
-    // tiles of this block (same walk as gemm_f32_persist_kernel)
-    const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int lo_t = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int cnt = q8 + (x8 < r8 ? 1 : 0);
-    const int my_n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    const TileWalk walk(tiles_m, tiles_n);           // tiles of this workgroup (common.h)
     const int KT = K / BK;
-    const int total = my_n * KT;
+    const int total = walk.n * KT;
     if (total == 0) return;
-    auto tile_of = [&](int i, int& tm, int& tn) __attribute__((always_inline)) {
-        const int lin = lo_t + jb + i * nbx;
-        const int per_group = 8 * tiles_n;
-        const int g = lin / per_group, first = g * 8;
-        const int gsz = min(tiles_m - first, 8);
-        const int in = lin - g * per_group;
-        tm = first + in % gsz;
-        tn = in / gsz;
-    };
 
     // DMA duty of this wave per slab: 16-row chunks wid and wid + 8 of A and of W.  Lane -> (row lane >> 2 of the chunk, chunk
     // position lane & 3), which holds logical chunk (lane & 3) ^ ((row >> 2) & 3) = (lane & 3) ^ (lane >> 4).
@@ -65,43 +50,32 @@ __global__ __launch_bounds__(DmaCfg::THREADS, 2) void gemm_bf16_dma_kernel(const
     // [r5] wave-uniform 64-bit base per tile (scalar registers) + 32-bit byte offset per lane: the global_load_lds s[base] form
     unsigned long long abase = 0, wbase = 0;
     unsigned ao0 = 0, ao1 = 0;
-    auto uniform64 = [](const void* p) __attribute__((always_inline)) { return lds_dma_base(p); };      // lds_dma.h
     const unsigned wo0 = (unsigned)(((long)(wid * 16 + drow) * W.ld + dchunk * 8) * 2), wo1 = (unsigned)(((long)((wid + 8) * 16 + drow) * W.ld + dchunk * 8) * 2);
     int l_tile = 0, l_kt = 0;
     auto set_rows = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
-        abase = uniform64(A + (long)tm * BM * lda);
+        walk.tile_of(i, tm, tn);
+        abase = lds_dma_base(A + (long)tm * BM * lda);
         ao0 = (unsigned)(((long)(min(tm * BM + wid * 16 + drow, M - 1) - tm * BM) * lda + dchunk * 8) * 2);
         ao1 = (unsigned)(((long)(min(tm * BM + (wid + 8) * 16 + drow, M - 1) - tm * BM) * lda + dchunk * 8) * 2);
-        // the segment of W is uniform over a tile (seg % 256 == 0): scalar selects, no indexed (vector) load of W.p[] whose
-        // vmcnt wait would drain the DMA pipeline at every tile switch
-        const int n0 = tn * BN, sidx = n0 / W.seg;
-        const __bf16* wp = (sidx == 0 ? W.p[0] : (sidx == 1 ? W.p[1] : W.p[2])) + (long)(n0 - sidx * W.seg) * W.ld;
-        wbase = uniform64(wp);
+        wbase = lds_dma_base(seg_tile_row(W, tn * BN));
     };
     set_rows(0);
-    // The DMA goes through inline asm: the compiler's waitcnt pass treats __builtin_amdgcn_global_load_lds as a store to LDS that
-    // any later ds_read may alias and drains vmcnt(0) in front of every fragment read, which serialises the pipeline.  vmcnt for
-    // these instructions is counted by hand (constant number in flight, see the loop).  M0 (the LDS base of the DMA) is a reserved
-    // register: the compiler keeps no value in it across statements, so writing it here needs no clobber.
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_dma;
-    auto dma1 = [&](unsigned voff, unsigned long long sbase, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
+    // vmcnt for the DMA instructions (lds_dma.h) is counted by hand: a constant number in flight, see the loop
+    const unsigned lds0 = lds_addr_of(smem_dma);
     // one slab of this block's slab stream -> stage st.  Unconditional (past the end it re-reads the last slab into a stage
     // nobody reads) so that the number of DMA instructions in flight is a constant the waits below can count on.
     auto dma = [&](int st) __attribute__((always_inline)) {
         const unsigned sa = lds0 + st * Cfg::STAGE + wid * 1024;
         const int k0 = l_kt * BK;
         const unsigned long long ka = abase + (unsigned long long)k0 * 2, kw = wbase + (unsigned long long)k0 * 2;
-        dma1(ao0, ka, sa);
-        dma1(ao1, ka, sa + 8 * 1024);
-        dma1(wo0, kw, sa + BM * ROWB);
-        dma1(wo1, kw, sa + BM * ROWB + 8 * 1024);
-        if (l_tile < my_n && ++l_kt == KT) {
+        lds_dma16(ao0, ka, sa);
+        lds_dma16(ao1, ka, sa + 8 * 1024);
+        lds_dma16(wo0, kw, sa + BM * ROWB);
+        lds_dma16(wo1, kw, sa + BM * ROWB + 8 * 1024);
+        if (l_tile < walk.n && ++l_kt == KT) {
             l_kt = 0;
-            if (++l_tile < my_n) set_rows(l_tile);
+            if (++l_tile < walk.n) set_rows(l_tile);
             else l_kt = KT - 1;                 // stream exhausted: keep pointing at the last slab
         }
     };
@@ -121,7 +95,7 @@ __global__ __launch_bounds__(DmaCfg::THREADS, 2) void gemm_bf16_dma_kernel(const
     int c_tile = 0, c_kt = 0;
     auto epilogue = [&]() __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         const int er = lane >> 3, ec = (lane & 7) * 4;
         const int nb0 = tn * BN + wn * (TN * 32) + ec, mb0 = tm * BM + wm * (TM * 32) + er;
         // 16 half blocks (32 columns x 16 rows) per wave; the residual rows of half block q+1 are requested before half block q

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "gemm_bf16.h"
+#include "lds_dma.h"
 
 typedef __bf16 bf16x4s __attribute__((ext_vector_type(4)));
 
@@ -385,25 +386,10 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
     const int grp = wid >> 2, wc = wid & 3;
     float* Es = (float*)(smem_s + NS * STAGE + wid * Cfg::EPATCH);
 
-    // tiles of this workgroup: XCD-aware chunk of the grouped tile order (as gemm_f32_persist_kernel)
-    const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int lo_t = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int cnt = q8 + (x8 < r8 ? 1 : 0);
-    const int my_n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    const TileWalk walk(tiles_m, tiles_n);           // tiles of this workgroup (common.h)
     const int KT = K / BK;
-    const int total = my_n * KT;                     // K-tiles of this workgroup's stream
+    const int total = walk.n * KT;                   // K-tiles of this workgroup's stream
     if (total == 0) return;
-    auto tile_of = [&](int i, int& tm, int& tn) __attribute__((always_inline)) {
-        const int lin = lo_t + jb + i * nbx;
-        const int per_group = 8 * tiles_n;
-        const int g = lin / per_group, first = g * 8;
-        const int gsz = min(tiles_m - first, 8);
-        const int in = lin - g * per_group;
-        tm = first + in % gsz;
-        tn = in / gsz;
-    };
 
     // ---- DMA duty of this wave per part: 16-row blocks wid and wid + 8.  Lane -> row lane >> 2 of the block, chunk position
     // lane & 3, which holds logical chunk (lane & 3) ^ swz(row), swz(row) = (4 - ((row >> 2) & 3)) & 3 and (row >> 2) & 3 = lane >> 4.
@@ -414,14 +400,14 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
     int xkb = 0;                                               // k offset of the X stream's tile (split * K; 0 without split-K)
     auto set_x = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
+        walk.tile_of(i, tm, tn);
         xr0 = xl.row(min(tm * BM + wid * 16 + drow, M - 1));
         xr1 = xl.row(min(tm * BM + (wid + 8) * 16 + drow, M - 1));
         xkb = ksplit > 1 ? (tn / tiles_n_real) * K : 0;
     };
     auto set_w = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
+        walk.tile_of(i, tm, tn);
         long koff = 0;
         if (ksplit > 1) { const int sp = tn / tiles_n_real; tn -= sp * tiles_n_real; koff = (long)sp * K; }
         constexpr int WBLK = BN / 16;                // 16-row blocks of the W part
@@ -430,31 +416,27 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
     };
     set_x(0);
     set_w(0);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_s;
-    // inline asm: the compiler's waitcnt pass would drain vmcnt(0) before every LDS read after __builtin_amdgcn_global_load_lds;
-    // the waits are counted by hand below (a constant number of DMA instructions per phase, unconditionally)
-    auto dma1 = [&](const __bf16* g, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
+    const unsigned lds0 = lds_addr_of(smem_s);
+    // the DMA's waits (lds_dma.h) are counted by hand below: a constant number of DMA instructions per phase, unconditionally
     auto issue_w = [&](int st) __attribute__((always_inline)) {        // W part of the next K-tile of the W stream -> stage st
         const unsigned sa = lds0 + st * STAGE + PART + (wid % (BN / 16)) * 1024;
         const int k0 = lw_kt * BK;
-        dma1(pw0 + k0, sa);
-        if constexpr (NI == 4) dma1(pw1 + k0, sa + 8 * 1024);
-        if (lw_tile < my_n && ++lw_kt == KT) {
+        lds_dma16(pw0 + k0, sa);
+        if constexpr (NI == 4) lds_dma16(pw1 + k0, sa + 8 * 1024);
+        if (lw_tile < walk.n && ++lw_kt == KT) {
             lw_kt = 0;
-            if (++lw_tile < my_n) set_w(lw_tile);
+            if (++lw_tile < walk.n) set_w(lw_tile);
             else lw_kt = KT - 1;                 // stream exhausted: keep re-reading the last K-tile into a stage nobody reads
         }
     };
     auto issue_x = [&](int st) __attribute__((always_inline)) {
         const unsigned sa = lds0 + st * STAGE + wid * 1024;
         const int k0 = lx_kt * BK + xkb;
-        dma1(xl.ptr(xr0, k0, dchunk * 8), sa);
-        dma1(xl.ptr(xr1, k0, dchunk * 8), sa + 8 * 1024);
-        if (lx_tile < my_n && ++lx_kt == KT) {
+        lds_dma16(xl.ptr(xr0, k0, dchunk * 8), sa);
+        lds_dma16(xl.ptr(xr1, k0, dchunk * 8), sa + 8 * 1024);
+        if (lx_tile < walk.n && ++lx_kt == KT) {
             lx_kt = 0;
-            if (++lx_tile < my_n) set_x(lx_tile);
+            if (++lx_tile < walk.n) set_x(lx_tile);
             else lx_kt = KT - 1;
         }
     };
@@ -489,7 +471,7 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
     auto epilogue = [&](auto full_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         const int m_wave = tm * BM + grp * 128, n_wave = tn * BN + wc * 16 * NI;
         const int q = lane >> 4;
         // lane -> (row of the 16-row block, first column) of its IT pieces; with NI < 4 the wave owns 16 NI columns: the lanes of the
@@ -646,7 +628,7 @@ __global__ __launch_bounds__(SCfg::THREADS, 2) void gemm_bf16s_kernel(XL xl, con
             if (grp == 0) __builtin_amdgcn_s_barrier();
             {
                 int tm_, tn_;
-                tile_of(c_tile, tm_, tn_);
+                walk.tile_of(c_tile, tm_, tn_);
                 // (fp32-output epilogues only: with the bf16-output GELU-grad epilogue the unconditional copy let hipcc hoist aux loads across
             // blocks -- 254 VGPRs -- and ran 11 % slower)
             if (Epi::W == 4 && (tm_ + 1) * BM <= M) epilogue(std::integral_constant<bool, Epi::W == 4>{});

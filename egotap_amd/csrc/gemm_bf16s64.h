@@ -264,25 +264,10 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
     const int grp = wid >> 2, wc = wid & 3;
     float* Es = (float*)(smem_s64 + 2 * KBUF + wid * Cfg::EPATCH);
 
-    // tiles of this workgroup: XCD-aware chunk of the grouped tile order (as gemm_bf16s_kernel)
-    const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int lo_t = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int cnt = q8 + (x8 < r8 ? 1 : 0);
-    const int my_n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    const TileWalk walk(tiles_m, tiles_n);           // tiles of this workgroup (common.h)
     const int KT = K / BK;
-    const int total = my_n * KT;                     // K-tiles of this workgroup's stream
+    const int total = walk.n * KT;                   // K-tiles of this workgroup's stream
     if (total == 0) return;
-    auto tile_of = [&](int i, int& tm, int& tn) __attribute__((always_inline)) {
-        const int lin = lo_t + jb + i * nbx;
-        const int per_group = 8 * tiles_n;
-        const int g = lin / per_group, first = g * 8;
-        const int gsz = min(tiles_m - first, 8);
-        const int in = lin - g * per_group;
-        tm = first + in % gsz;
-        tn = in / gsz;
-    };
 
     // ---- DMA duty of this wave per part: row blocks wid and wid + 8 of the part's 16 (8 rows x 128 B each).  Lane -> row lane >> 3 of
     // the block, chunk position lane & 7, which holds logical chunk (lane & 7) ^ ((r >> 1) & 7), r = 8 blk + (lane >> 3) the local row:
@@ -298,13 +283,12 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
     struct Stream { int tile, kt; };                 // position of an issue stream: (tile index of this workgroup, K-tile inside it)
     Stream s_xa[2] = {{0, 0}, {0, 0}}, s_wb[2] = {{0, 0}, {0, 0}};
     unsigned long long xbase[2], wbase[2];           // wave-uniform bases of the streams' current tiles (bytes)
-    auto uniform64 = [](unsigned long long v) __attribute__((always_inline)) { return lds_dma_base(v); };      // lds_dma.h
     auto set_x = [&](int a, int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
+        walk.tile_of(i, tm, tn);
         const int r0 = tm * BM + a * 64 + 8 * wid + drow;      // group 0's row of this lane; group 1's is 128 further
         if constexpr (XL::SBASE) {
-            xbase[a] = uniform64((unsigned long long)(size_t)xl.A + (unsigned long long)tm * BM * xl.lda * 2);
+            xbase[a] = lds_dma_base((unsigned long long)(size_t)xl.A + (unsigned long long)tm * BM * xl.lda * 2);
 #pragma unroll
             for (int g = 0; g < 2; ++g) xo[a][g] = (unsigned)((long)(min(r0 + g * 128, M - 1) - tm * BM) * xl.lda * 2 + dchunk * 16);
         } else {
@@ -314,37 +298,30 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
     };
     auto set_w = [&](int b, int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
-        wbase[b] = uniform64((unsigned long long)(size_t)Wb + ((unsigned long long)(tn * BN + (NJ == 2 ? (wid >> 2) * 64 + b * 32 : (wid >> 1) * 32 + b * 16)) * ldw) * 2);
+        walk.tile_of(i, tm, tn);
+        wbase[b] = lds_dma_base((unsigned long long)(size_t)Wb + ((unsigned long long)(tn * BN + (NJ == 2 ? (wid >> 2) * 64 + b * 32 : (wid >> 1) * 32 + b * 16)) * ldw) * 2);
     };
     set_x(0, 0); set_x(1, 0);
     set_w(0, 0); set_w(1, 0);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_s64;
-    // inline asm: the compiler's waitcnt pass would drain vmcnt(0) before every LDS read after __builtin_amdgcn_global_load_lds;
-    // the waits are counted by hand below (a constant number of DMA instructions per phase, unconditionally)
-    auto dma1 = [&](unsigned voff, unsigned long long sbase, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
+    const unsigned lds0 = lds_addr_of(smem_s64);
+    // the DMA's waits (lds_dma.h) are counted by hand below: a constant number of DMA instructions per phase, unconditionally
     auto advance = [&](Stream& st, int which, bool is_x) __attribute__((always_inline)) {
-        if (__builtin_expect(st.tile < my_n && ++st.kt == KT, 0)) {          // (rare: the common path falls through without a taken branch)
+        if (__builtin_expect(st.tile < walk.n && ++st.kt == KT, 0)) {          // (rare: the common path falls through without a taken branch)
             st.kt = 0;
-            if (++st.tile < my_n) { if (is_x) set_x(which, st.tile); else set_w(which, st.tile); }
+            if (++st.tile < walk.n) { if (is_x) set_x(which, st.tile); else set_w(which, st.tile); }
             else st.kt = KT - 1;                     // stream exhausted: keep re-reading the last K-tile into a region nobody reads
         }
     };
     unsigned long long xorg = 0;                     // scalar-origin loaders: the origin, and this lane's offset into the zero page
     unsigned zoff = 0;
     const unsigned dch16 = (unsigned)dchunk * 16;
-    if constexpr (s64_sorg<XL>::value) { xorg = uniform64((unsigned long long)(size_t)xl.org); zoff = xl.zero_off + dch16; }
-    auto dma1v = [&](const __bf16* g, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
+    if constexpr (s64_sorg<XL>::value) { xorg = lds_dma_base((unsigned long long)(size_t)xl.org); zoff = xl.zero_off + dch16; }
     auto issue_x = [&](int a, int buf) __attribute__((always_inline)) {        // XA_a of the stream's next K-tile -> K-tile buffer buf
         const unsigned sa = lds0 + buf * KBUF + (a ? Cfg::O_XA1 : Cfg::O_XA0) + wid * 1024;
         if constexpr (XL::SBASE) {
             const unsigned long long kb = xbase[a] + (unsigned long long)s_xa[a].kt * (BK * 2);
-            dma1(xo[a][0], kb, sa);
-            dma1(xo[a][1], kb, sa + 8 * 1024);
+            lds_dma16(xo[a][0], kb, sa);
+            lds_dma16(xo[a][1], kb, sa + 8 * 1024);
         } else if constexpr (s64_sorg<XL>::value) {
             int koff, tap;
             xl.ktile(s_xa[a].kt, koff, tap);                                   // scalar unit
@@ -352,19 +329,19 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
                 const typename XL::Row& r = xrow.r[a][g];
-                dma1(((r.mask >> tap) & 1u) ? r.off + kc : zoff, xorg, sa + g * 8 * 1024);
+                lds_dma16(((r.mask >> tap) & 1u) ? r.off + kc : zoff, xorg, sa + g * 8 * 1024);
             }
         } else {
-            dma1v(xl.ptr(xrow.r[a][0], s_xa[a].kt, dchunk), sa);
-            dma1v(xl.ptr(xrow.r[a][1], s_xa[a].kt, dchunk), sa + 8 * 1024);
+            lds_dma16(xl.ptr(xrow.r[a][0], s_xa[a].kt, dchunk), sa);
+            lds_dma16(xl.ptr(xrow.r[a][1], s_xa[a].kt, dchunk), sa + 8 * 1024);
         }
         advance(s_xa[a], a, true);
     };
     auto issue_w = [&](int b, int buf) __attribute__((always_inline)) {
         const unsigned sa = lds0 + buf * KBUF + (b ? Cfg::O_WB1 : Cfg::O_WB0) + wid * 1024;
         const unsigned long long kb = wbase[b] + (unsigned long long)s_wb[b].kt * (BK * 2);
-        dma1(wo, kb, sa);
-        if constexpr (NJ == 2) dma1(wo, kb + (unsigned long long)128 * ldw * 2, sa + 8 * 1024);
+        lds_dma16(wo, kb, sa);
+        if constexpr (NJ == 2) lds_dma16(wo, kb + (unsigned long long)128 * ldw * 2, sa + 8 * 1024);
         advance(s_wb[b], b, false);
     };
 
@@ -400,11 +377,11 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
     const unsigned patch_lds = lds0 + 2 * KBUF + wid * Cfg::EPATCH;
     auto issue_bias = [&]() __attribute__((always_inline)) {      // the 64 bias values of this wave's columns of tile c_tile -> the head of its patch
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         // (no bias: the DMA still runs, from any valid 256 bytes -- the count per phase is a compile-time constant -- and is never read)
-        const unsigned long long b = has_bias ? uniform64((unsigned long long)(size_t)bias_g + (unsigned long long)(tn * BN + wc * 64) * 4)
-                                              : uniform64((unsigned long long)(size_t)Wb);
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"((unsigned)(lane * 4)), "s"(b), "s"(__builtin_amdgcn_readfirstlane(patch_lds)) : "memory");
+        const unsigned long long b = has_bias ? lds_dma_base((unsigned long long)(size_t)bias_g + (unsigned long long)(tn * BN + wc * 64) * 4)
+                                              : lds_dma_base((unsigned long long)(size_t)Wb);
+        lds_dma4((unsigned)(lane * 4), b, patch_lds);
     };
     // per-column constants of this lane: staged in the patch during the tile's first K-tile (LDS operations of a wave stay in order: the
     // epilogue's patch writes cannot overtake these reads), or from global memory for the epilogues with other constants / no bias
@@ -421,7 +398,7 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
     auto epilogue = [&](auto full_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         const int m_wave = tm * BM + grp * 128, n_wave = tn * BN + wc * WCOLS;
         const int q = lane >> 4;
         const int er = lane / LPR, ec = lane % LPR, ecol = ec * Epi::W;
@@ -565,7 +542,7 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
         buf ^= 1;
     };
     constexpr int XB = LB ? 1 : 0;                      // the bias DMA of a tile's first K-tile (issued whether or not there is a bias: a constant count)
-    for (c_tile = 0; c_tile < my_n; ++c_tile) {
+    for (c_tile = 0; c_tile < walk.n; ++c_tile) {
         if (slack_on) ktile(std::integral_constant<int, SLK + XB>{}, std::true_type{});
         else ktile(std::integral_constant<int, VMC + XB>{}, std::true_type{});
         for (int kt = 1; kt < KT; ++kt) ktile(std::integral_constant<int, VMC>{}, std::false_type{});
@@ -573,7 +550,7 @@ __global__ __launch_bounds__(S64Cfg::THREADS, 2) void gemm_bf16s64_kernel(XL xl,
         if (grp == 0) __builtin_amdgcn_s_barrier();
         {
             int tm_, tn_;
-            tile_of(c_tile, tm_, tn_);
+            walk.tile_of(c_tile, tm_, tn_);
             // (fp32-output epilogues only: with the bf16-output GELU-grad epilogue the unconditional copy let hipcc hoist aux loads across
             // blocks -- 254 VGPRs -- and ran 11 % slower)
             if (Epi::W == 4 && (tm_ + 1) * BM <= M) epilogue(std::integral_constant<bool, Epi::W == 4>{});

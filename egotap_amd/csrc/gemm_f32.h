@@ -758,32 +758,17 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_persist_kern
     constexpr int CH = BK / 4, RW = 64 / CH;
     const int c4 = lane / RW, r0 = wid * RW + lane % RW;
 
-    // tiles of this block
-    const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int lo = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int cnt = q8 + (x8 < r8 ? 1 : 0);
-    const int my_n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    const TileWalk walk(tiles_m, tiles_n);           // tiles of this workgroup (common.h)
     const int KT = K / BK;
-    const int total = my_n * KT;
+    const int total = walk.n * KT;
     if (total == 0) return;
-    auto tile_of = [&](int i, int& tm, int& tn) __attribute__((always_inline)) {
-        const int lin = lo + jb + i * nbx;
-        const int per_group = 8 * tiles_n;
-        const int g = lin / per_group, first = g * 8;
-        const int gsz = min(tiles_m - first, 8);
-        const int in = lin - g * per_group;
-        tm = first + in % gsz;
-        tn = in / gsz;
-    };
 
     typename ALoad::Row arow[A_V4];
     const float* brow[B_V4];
     int l_tile = 0, l_kt = 0;           // load position
     auto set_rows = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
+        walk.tile_of(i, tm, tn);
 #pragma unroll
         for (int v = 0; v < A_V4; ++v) arow[v] = al.row(min(tm * BM + r0 + v * RPP, M - 1));
 #pragma unroll
@@ -811,7 +796,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_persist_kern
         _Pragma("unroll") for (int i = 0; i < B_V4; ++i) gb[i] = *(const f32x4*)(brow[i] + k0_);     \
         if (++l_kt == KT) {                                                                          \
             l_kt = 0;                                                                                \
-            if (++l_tile < my_n) set_rows(l_tile);                                                   \
+            if (++l_tile < walk.n) set_rows(l_tile);                                                 \
         }                                                                                            \
     }
 #define LSTORE(BUF)                                                                                              \
@@ -853,7 +838,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::MINW) void gemm_f32_persist_kern
         // The residual rows of tile q+1 are requested BEFORE the stores of tile q are issued, so the wait for them is
         // a counted vmcnt(4) and never drains the stores (vmcnt is in-order and counts stores on gfx950).
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         const int er = lane >> 3, ec = (lane & 7) * 4;            // float4 #lane of an 8-row stripe
         const int nb0 = tn * BN + wn * (TN * 32) + ec, mb0 = tm * BM + wm * (TM * 32) + er;
         f32x4 rs[4];

@@ -31,25 +31,10 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
     const int l31 = lane & 31, lh = lane >> 5;
     float* Es = (float*)(smem_dmaf + NS * Cfg::STAGE + wid * Cfg::EPATCH);
 
-    // tiles of this block (same walk as gemm_f32_persist_kernel)
-    const int ntiles = tiles_m * tiles_n, nb = gridDim.x, x8 = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    const int nbx = (nb >> 3) + (x8 < (nb & 7) ? 1 : 0);
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int lo_t = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int cnt = q8 + (x8 < r8 ? 1 : 0);
-    const int my_n = cnt > jb ? (cnt - jb + nbx - 1) / nbx : 0;
+    const TileWalk walk(tiles_m, tiles_n);           // tiles of this workgroup (common.h)
     const int KT = K / BK;
-    const int total = my_n * KT;
+    const int total = walk.n * KT;
     if (total == 0) return;
-    auto tile_of = [&](int i, int& tm, int& tn) __attribute__((always_inline)) {
-        const int lin = lo_t + jb + i * nbx;
-        const int per_group = 8 * tiles_n;
-        const int g = lin / per_group, first = g * 8;
-        const int gsz = min(tiles_m - first, 8);
-        const int in = lin - g * per_group;
-        tm = first + in % gsz;
-        tn = in / gsz;
-    };
 
     // DMA duty of this wave per slab: 16-row chunks wid and wid + 8 of A and of W.  Lane -> (row lane >> 2 of the chunk, chunk
     // position lane & 3), which holds logical chunk (lane & 3) ^ ((row >> 2) & 3) = (lane & 3) ^ (lane >> 4).
@@ -62,19 +47,18 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
     constexpr bool SBA = std::is_same<ALoad, ALoadPlain>::value || HEAD;
     unsigned long long abase = 0, wbase = 0;
     unsigned ao0 = 0, ao1 = 0;
-    auto uniform64 = [](const void* p) __attribute__((always_inline)) { return lds_dma_base(p); };      // lds_dma.h
     const unsigned wo0 = (unsigned)(((long)(wid * 16 + drow) * W.ld + dchunk * 4) * 4), wo1 = (unsigned)(((long)((wid + 8) * 16 + drow) * W.ld + dchunk * 4) * 4);
     int l_tile = 0, l_kt = 0;
     auto set_rows = [&](int i) __attribute__((always_inline)) {
         int tm, tn;
-        tile_of(i, tm, tn);
+        walk.tile_of(i, tm, tn);
         if constexpr (HEAD) {
             const long p0 = al.hr.phys(tm * BM), ld = al.lda * 4;
-            abase = uniform64(al.A + p0 * al.lda);
+            abase = lds_dma_base(al.A + p0 * al.lda);
             ao0 = (unsigned)((al.hr.phys(min(tm * BM + wid * 16 + drow, M - 1)) - p0) * ld + dchunk * 16);
             ao1 = (unsigned)((al.hr.phys(min(tm * BM + (wid + 8) * 16 + drow, M - 1)) - p0) * ld + dchunk * 16);
         } else if constexpr (SBA) {
-            abase = uniform64(al.A + (long)tm * BM * al.lda);
+            abase = lds_dma_base(al.A + (long)tm * BM * al.lda);
             const long ld = al.lda * 4;                                                                      // bytes per row
             ao0 = (unsigned)((long)(min(tm * BM + wid * 16 + drow, M - 1) - tm * BM) * ld + dchunk * 16);
             ao1 = (unsigned)((long)(min(tm * BM + (wid + 8) * 16 + drow, M - 1) - tm * BM) * ld + dchunk * 16);
@@ -82,38 +66,25 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
         ra0 = al.row(min(tm * BM + wid * 16 + drow, M - 1));
         ra1 = al.row(min(tm * BM + (wid + 8) * 16 + drow, M - 1));
         }
-        // the segment of W is uniform over a tile (seg % 256 == 0): scalar selects, no indexed (vector) load of W.p[] whose
-        // vmcnt wait would drain the DMA pipeline at every tile switch
-        const int n0 = tn * BN, sidx = n0 / W.seg;
-        const float* wp = (sidx == 0 ? W.p[0] : (sidx == 1 ? W.p[1] : W.p[2])) + (long)(n0 - sidx * W.seg) * W.ld;
-        wbase = uniform64(wp);
+        wbase = lds_dma_base(seg_tile_row(W, tn * BN));
     };
     set_rows(0);
-    // The DMA goes through inline asm: the compiler's waitcnt pass treats __builtin_amdgcn_global_load_lds as a store to LDS that
-    // any later ds_read may alias and drains vmcnt(0) in front of every fragment read, which serialises the pipeline.  vmcnt for
-    // these instructions is counted by hand (constant number in flight, see the loop).  M0 (the LDS base of the DMA) is a reserved
-    // register: the compiler keeps no value in it across statements, so writing it here needs no clobber.
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_dmaf;
-    auto dma1 = [&](const float* g, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
+    // vmcnt for the DMA instructions (lds_dma.h) is counted by hand: a constant number in flight, see the loop
+    const unsigned lds0 = lds_addr_of(smem_dmaf);
     // one slab of this block's slab stream -> stage st.  Unconditional (past the end it re-reads the last slab into a stage
     // nobody reads) so that the number of DMA instructions in flight is a constant the waits below can count on.
-    auto dma1s = [&](unsigned voff, unsigned long long sbase, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
     auto dma_part = [&](int st, int part) __attribute__((always_inline)) {       // one of the four DMA instructions of a slab
         const unsigned sa = lds0 + st * Cfg::STAGE + wid * 1024;
         const int k0 = l_kt * BK;
-        if (part == 0) { if constexpr (SBA) dma1s(ao0, abase + (unsigned long long)k0 * 4, sa); else dma1(al.ptr(ra0, k0 + dchunk * 4), sa); }
-        else if (part == 1) { if constexpr (SBA) dma1s(ao1, abase + (unsigned long long)k0 * 4, sa + 8 * 1024); else dma1(al.ptr(ra1, k0 + dchunk * 4), sa + 8 * 1024); }
-        else if (part == 2) dma1s(wo0, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB);
-        else dma1s(wo1, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB + 8 * 1024);
+        if (part == 0) { if constexpr (SBA) lds_dma16(ao0, abase + (unsigned long long)k0 * 4, sa); else lds_dma16(al.ptr(ra0, k0 + dchunk * 4), sa); }
+        else if (part == 1) { if constexpr (SBA) lds_dma16(ao1, abase + (unsigned long long)k0 * 4, sa + 8 * 1024); else lds_dma16(al.ptr(ra1, k0 + dchunk * 4), sa + 8 * 1024); }
+        else if (part == 2) lds_dma16(wo0, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB);
+        else lds_dma16(wo1, wbase + (unsigned long long)k0 * 4, sa + BM * ROWB + 8 * 1024);
     };
     auto dma_advance = [&]() __attribute__((always_inline)) {
-        if (l_tile < my_n && ++l_kt == KT) {
+        if (l_tile < walk.n && ++l_kt == KT) {
             l_kt = 0;
-            if (++l_tile < my_n) set_rows(l_tile);
+            if (++l_tile < walk.n) set_rows(l_tile);
             else l_kt = KT - 1;                 // stream exhausted: keep pointing at the last slab
         }
     };
@@ -148,7 +119,7 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
     auto epilogue = [&](auto full_tag) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_tag)::value;
         int tm, tn;
-        tile_of(c_tile, tm, tn);
+        walk.tile_of(c_tile, tm, tn);
         const int er = lane >> 3, ec = (lane & 7) * 4;
         const int nb0 = tn * BN + wn * (TN * 32) + ec, mb0 = tm * BM + wm * (TM * 32) + er;
         // 16 half blocks (32 columns x 16 rows) per wave; the residual rows of half block q+1 are requested before half block q
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(DmaF32Cfg::THREADS, 2) void gemm_f32_dma_kernel(ALo
             after_epi = true;
             {
                 int tm_, tn_;
-                tile_of(c_tile, tm_, tn_);
+                walk.tile_of(c_tile, tm_, tn_);
                 // (epilogues with wide per-column constants -- patch embedding, BatchNorm -- keep the one predicated copy: two copies of
                 // their epilogue pushed the kernel past 256 registers)
                 // (... and the two training epilogues with a residual operand and no constants, EpiAccum / EpiGeluGrad, spilled with two)

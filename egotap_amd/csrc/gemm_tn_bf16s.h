@@ -142,31 +142,24 @@ __global__ __launch_bounds__(TnSCfg::THREADS, 2) void gemm_tn_bf16s_kernel(const
     const int r0 = 2 * wid + (lane >> 5), r1 = r0 + 16;
     auto fsw = [](int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); };
     const int c0 = (lane & 31) ^ fsw(r0), c1 = (lane & 31) ^ fsw(r1);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_t;
-    auto dma1 = [&](const __bf16* g, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
+    const unsigned lds0 = lds_addr_of(smem_t);
     int ly = 0, lx = 0;            // next step of the dY / X issue streams; past the end they keep re-reading the zero page
     // FAST: lane offsets (bytes) from the step's wave-uniform base; past the end the streams re-read the split's last step (valid memory,
     // landing in a stage nobody reads)
     unsigned oy0 = 0, oy1 = 0, ox0 = 0, ox1 = 0;
     unsigned long long ybase = 0, xbase = 0;
-    auto uniform64 = [](unsigned long long v) __attribute__((always_inline)) { return lds_dma_base(v); };      // lds_dma.h
-    auto dma_s = [&](unsigned voff, unsigned long long sbase, unsigned lds_addr) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
-    };
     constexpr bool PLAINX = std::is_same<XL, TXPlain>::value;
     if constexpr (FAST) {
         oy0 = (unsigned)(((long)r0 * ldy + c0 * 8) * 2); oy1 = (unsigned)(((long)r1 * ldy + c1 * 8) * 2);
-        ybase = uniform64((unsigned long long)(size_t)dY + ((unsigned long long)m_lo * ldy + n0) * 2);
+        ybase = lds_dma_base((unsigned long long)(size_t)dY + ((unsigned long long)m_lo * ldy + n0) * 2);
         if constexpr (PLAINX) {
             ox0 = (unsigned)(((long)r0 * xl.lda + c0 * 8) * 2); ox1 = (unsigned)(((long)r1 * xl.lda + c1 * 8) * 2);
-            xbase = uniform64((unsigned long long)(size_t)xl.A + ((unsigned long long)m_lo * xl.lda + k0) * 2);
+            xbase = lds_dma_base((unsigned long long)(size_t)xl.A + ((unsigned long long)m_lo * xl.lda + k0) * 2);
         } else {
             // [r5] gathered rows (fc1 of the two encoders): every row whole and in range, the tensor under 4 GB -> wave-uniform tensor base + one
             // 32-bit byte offset per lane = the lane's fixed column part + the row's gather offset; no 64-bit pointer selects, no zero page
             ox0 = (unsigned)(xl.kpart(k0 + c0 * 8) * 2); ox1 = (unsigned)(xl.kpart(k0 + c1 * 8) * 2);
-            xbase = uniform64((unsigned long long)(size_t)xl.base());
+            xbase = lds_dma_base((unsigned long long)(size_t)xl.base());
         }
     }
     // the lane's two column pieces of the X tile, fixed for the kernel (general path)
@@ -176,39 +169,39 @@ __global__ __launch_bounds__(TnSCfg::THREADS, 2) void gemm_tn_bf16s_kernel(const
         const unsigned sa = lds0 + st * STAGE + wid * 1024;
         if constexpr (FAST) {
             const unsigned long long b = ybase + (unsigned long long)min(ly, total - 1) * (BKM * 2) * ldy;
-            dma_s(oy0, b, sa);
-            dma_s(oy1, b, sa + 8 * 1024);
+            lds_dma16(oy0, b, sa);
+            lds_dma16(oy1, b, sa + 8 * 1024);
             ++ly;
             return;
         }
         const int mb = m_lo + ly * BKM;
         const bool in = ly < total;
         const int ma = mb + r0, mc = mb + r1;
-        dma1(in && ma < m_hi ? dY + (long)ma * ldy + n0 + c0 * 8 : zeros + c0 * 8, sa);
-        dma1(in && mc < m_hi ? dY + (long)mc * ldy + n0 + c1 * 8 : zeros + c1 * 8, sa + 8 * 1024);
+        lds_dma16(in && ma < m_hi ? dY + (long)ma * ldy + n0 + c0 * 8 : zeros + c0 * 8, sa);
+        lds_dma16(in && mc < m_hi ? dY + (long)mc * ldy + n0 + c1 * 8 : zeros + c1 * 8, sa + 8 * 1024);
         ++ly;
     };
     auto issue_x = [&](int st) __attribute__((always_inline)) {
         const unsigned sa = lds0 + st * STAGE + PART + wid * 1024;
         if constexpr (FAST && PLAINX) {
             const unsigned long long b = xbase + (unsigned long long)min(lx, total - 1) * (BKM * 2) * xl.lda;
-            dma_s(ox0, b, sa);
-            dma_s(ox1, b, sa + 8 * 1024);
+            lds_dma16(ox0, b, sa);
+            lds_dma16(ox1, b, sa + 8 * 1024);
             ++lx;
             return;
         }
         if constexpr (FAST && !PLAINX) {
             const int mb = m_lo + min(lx, total - 1) * BKM;
-            dma_s(ox0 + (unsigned)(xl.rowpart(mb + r0) * 2), xbase, sa);
-            dma_s(ox1 + (unsigned)(xl.rowpart(mb + r1) * 2), xbase, sa + 8 * 1024);
+            lds_dma16(ox0 + (unsigned)(xl.rowpart(mb + r0) * 2), xbase, sa);
+            lds_dma16(ox1 + (unsigned)(xl.rowpart(mb + r1) * 2), xbase, sa + 8 * 1024);
             ++lx;
             return;
         }
         const int mb = m_lo + lx * BKM;
         const bool in = lx < total;
         const int ma = mb + r0, mc = mb + r1;
-        dma1(in && ma < m_hi ? xk0 + xl.rowpart(ma) : zeros + c0 * 8, sa);
-        dma1(in && mc < m_hi ? xk1 + xl.rowpart(mc) : zeros + c1 * 8, sa + 8 * 1024);
+        lds_dma16(in && ma < m_hi ? xk0 + xl.rowpart(ma) : zeros + c0 * 8, sa);
+        lds_dma16(in && mc < m_hi ? xk1 + xl.rowpart(mc) : zeros + c1 * 8, sa + 8 * 1024);
         ++lx;
     };
 

@@ -272,14 +272,13 @@ static __global__ __launch_bounds__(TnDmaCfg::THREADS) void gemm_tn_f32_dma_kern
     const int m_lo = split * rows_per, m_hi = min(M, m_lo + rows_per);
     const int nslab = m_hi > m_lo ? (m_hi - m_lo) / BKM : 0;        // rows_per % BKM == 0 and M % BKM == 0: every slab is full
 
-    // the DMA goes through inline asm and vmcnt is waited for by hand (see gemm_f32_dma.h for why)
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem_tnd;
+    // vmcnt for the DMA instructions (lds_dma.h) is waited for by hand
+    const unsigned lds0 = lds_addr_of(smem_tnd);
     // wave w stages rows w, w + 8, w + 16, w + 24 of both operands: 8 DMA instructions per wave and slab
     // [r5] a staged row is one wave instruction: wave-uniform row address (scalar registers) + 16 bytes per lane -- the global_load_lds s[base]
     // form instead of a 64-bit pointer per lane (the A/B is recorded in profiles/r05_dma_addressing_ab.log)
     auto dma1s = [&](unsigned voff, const float* base, unsigned lds_addr) __attribute__((always_inline)) {
-        const unsigned long long sb = lds_dma_base(base);      // lds_dma.h
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sb), "s"(__builtin_amdgcn_readfirstlane(lds_addr)) : "memory");
+        lds_dma16(voff, lds_dma_base(base), lds_addr);
     };
     const float* ga = dY + (long)(m_lo + wid) * ldy + n0;
     const float* gb = X + (long)(m_lo + wid) * ldx + k0;

@@ -39,6 +39,15 @@ def test_header_and_library_agree():
     assert "getenv" not in src
 
 
+def test_dma_statement_and_persistent_tile_walk_are_written_once():
+    """Outside comments, csrc/ issues an LDS DMA only in lds_dma.h and cuts the persistent kernels' tile order only in common.h (TileWalk):
+    the kernels call those, so the M0 write / wait state of the statement and the order the host's round counts assume are one-place facts."""
+    csrc = os.path.join(REPO, "egotap_amd", "csrc")
+    code = {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, f)).read(), flags=re.S) for f in sorted(os.listdir(csrc))}
+    assert [f for f, t in code.items() if "global_load_lds" in t] == ["lds_dma.h"]
+    assert [f for f, t in code.items() if re.search(r"q8\s*=\s*ntiles\s*>>\s*3", t)] == ["common.h"]
+
+
 def _cfg(**kw):
     base = dict(n_joints_hm=15, estimate_head=1, hm_size=64, hidden=128, vit_dim=1024, vit_heads=8, vit_layers=3,
                 patch=16, pu_hidden=512)
