@@ -41,6 +41,7 @@
 #include "heatmap_peaks.h"
 #include "limb_decode.h"
 #include "ocam.h"
+#include "pose_track.h"
 
 // The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
 // inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
@@ -2610,6 +2611,55 @@ extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, c
               "%s: joints3d and frame must not overlap keypoints, pose or each other", who);
     GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_triangulate", "stereo_triangulate_kernel", 0.0);
     EGO_HIP(stereo_triangulate_launch(keypoints, B, J, rig, pose, P, pose_row0, joints3d, frame, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+
+// ---- the pose, the root and the stereo joints filtered over time (pose_track.h): one operator, no handle
+extern "C" int egotap_pose_track(const float* pose, const float* frame, const float* joints3d, int T, int S, int P, int J, const float* dts, double dt,
+                                 const egotap_track_params* params, const double* state_in, double* state_out, float* tracks, float* placed, void* stream) {
+    static const char* const who = "egotap_pose_track";
+    EGO_CHECK(pose && state_in && state_out && tracks && placed && params,
+              "%s: null argument (pose, params, state_in, state_out, tracks and placed are required; frame, joints3d and dts may be NULL)", who);
+    EGO_CHECK(T > 0 && S > 0 && P > 0, "%s: T, S and P must be positive (T = %d, S = %d, P = %d)", who, T, S, P);
+    EGO_CHECK(P <= kTrackMaxRows, "%s: at most %d pose rows, one lane each (P = %d)", who, kTrackMaxRows, P);
+    EGO_CHECK(J >= 0 && J <= kTrackMaxRows, "%s: J must be 0 .. %d joints, one lane each (J = %d)", who, kTrackMaxRows, J);
+    EGO_CHECK((J > 0) == (joints3d != nullptr), "%s: joints3d goes with J > 0 and NULL with J = 0 (J = %d, joints3d %s)", who, J, joints3d ? "given" : "NULL");
+    EGO_CHECK((int64_t)T * S <= INT32_MAX, "%s: T * S = %lld frames do not fit an int", who, (long long)T * S);
+    EGO_CHECK((((uintptr_t)pose | (uintptr_t)frame | (uintptr_t)joints3d | (uintptr_t)dts | (uintptr_t)placed) & 3) == 0,
+              "%s: pose, frame, joints3d, dts and placed must be 4-byte aligned", who);
+    EGO_CHECK(((uintptr_t)tracks & 15) == 0, "%s: tracks must be 16-byte aligned", who);
+    EGO_CHECK((((uintptr_t)state_in | (uintptr_t)state_out) & 7) == 0, "%s: state_in and state_out must be 8-byte aligned", who);
+    EGO_CHECK(dts || (ego_finite(dt) && dt > 0.0), "%s: dt must be finite and > 0 when dts is NULL (dt = %g)", who, dt);
+    const egotap_track_params& q = *params;
+    const double cls[3][3] = {{q.pose_min_cutoff, q.pose_beta, q.pose_d_cutoff}, {q.root_min_cutoff, q.root_beta, q.root_d_cutoff},
+                              {q.joints_min_cutoff, q.joints_beta, q.joints_d_cutoff}};
+    static const char* const cls_name[3] = {"pose", "root", "joints"};
+    for (int c = 0; c < 3; ++c) {
+        EGO_CHECK(ego_finite(cls[c][0]) && cls[c][0] > 0.0, "%s: params: %s_min_cutoff must be finite and > 0 (%g)", who, cls_name[c], cls[c][0]);
+        EGO_CHECK(ego_finite(cls[c][1]) && cls[c][1] >= 0.0, "%s: params: %s_beta must be finite and >= 0 (%g)", who, cls_name[c], cls[c][1]);
+        EGO_CHECK(ego_finite(cls[c][2]) && cls[c][2] > 0.0, "%s: params: %s_d_cutoff must be finite and > 0 (%g)", who, cls_name[c], cls[c][2]);
+    }
+    EGO_CHECK(q.max_disagree >= 0.0, "%s: params: max_disagree must be >= 0, +inf for off (%g)", who, q.max_disagree);      // (a NaN fails the comparison)
+    EGO_CHECK(q.max_gap >= 0.0, "%s: params: max_gap must be >= 0, +inf for off (%g)", who, q.max_gap);
+    EGO_CHECK(q.max_joint_gap >= 0.0, "%s: params: max_joint_gap must be >= 0, +inf for off (%g)", who, q.max_joint_gap);
+    EGO_CHECK(q.min_joints >= 0, "%s: params: min_joints must not be negative (%d)", who, q.min_joints);
+    EGO_CHECK(q.max_hold >= 0, "%s: params: max_hold must not be negative (%d)", who, q.max_hold);
+    const size_t B = (size_t)T * S, K = (size_t)P + 1 + J;
+    const struct {
+        const char* name;
+        const void* p;
+        size_t n;
+    } in[5] = {{"pose", pose, B * P * 12}, {"frame", frame, B * 32}, {"joints3d", joints3d, B * J * 32}, {"dts", dts, (size_t)T * 4}, {"state_in", state_in, (size_t)S * K * 96}},
+      out[3] = {{"state_out", state_out, (size_t)S * K * 96}, {"tracks", tracks, B * K * 32}, {"placed", placed, B * P * 12}};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 5; ++i) {
+            if (o == 0 && i == 4 && state_out == state_in) continue;      // in place
+            EGO_CHECK(!ego_overlap(out[o].p, out[o].n, in[i].p, in[i].n), "%s: %s overlaps %s", who, out[o].name, in[i].name);
+        }
+        for (int p = o + 1; p < 3; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
+    }
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "pose_track", "pose_track_kernel", 0.0);
+    EGO_HIP(pose_track_launch(pose, frame, joints3d, T, S, P, J, dts, dt, q, state_in, state_out, tracks, placed, (hipStream_t)stream));
     return EGOTAP_OK;
 }
 

@@ -26,6 +26,11 @@ class EgotapOcam(C.Structure):                        # egotap.h egotap_ocam: do
         ("n_pol", C.c_int32), ("n_invpol", C.c_int32)]
 
 
+class EgotapTrackParams(C.Structure):                 # egotap.h egotap_track_params: twelve doubles and two ints
+    _fields_ = [(f"{c}_{n}", C.c_double) for c in ("pose", "root", "joints") for n in ("min_cutoff", "beta", "d_cutoff")] + [
+        (n, C.c_double) for n in ("max_disagree", "max_gap", "max_joint_gap")] + [("min_joints", C.c_int32), ("max_hold", C.c_int32)]
+
+
 class EgotapError(RuntimeError):
     pass
 
@@ -80,6 +85,9 @@ _PROTOS = {
     "egotap_ocam_unproject": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
     "egotap_stereo_triangulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapOcam), C.POINTER(EgotapOcam), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- the pose, the root and the stereo joints filtered over time: one operator, no handle
+    "egotap_pose_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.POINTER(EgotapTrackParams),
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -551,6 +559,72 @@ def stereo_triangulate(keypoints, left, right, t, R=None, affine=None, min_score
     with torch.cuda.device(kp.device):
         stereo_triangulate_into(args, kp, ps, pose_row0, joints3d, frame, kp.device)
     return joints3d, frame
+
+
+def track_params_struct(params=None) -> EgotapTrackParams:
+    """a ``spec.TrackParams`` (None: the defaults) as the ABI takes it (egotap_track_params, by pointer to host memory)"""
+    from . import spec
+    prm = spec.TrackParams() if params is None else params
+    o = EgotapTrackParams()
+    for c in spec.TRACK_CLASSES:
+        for n, v in zip(("min_cutoff", "beta", "d_cutoff"), getattr(prm, c)):
+            setattr(o, f"{c}_{n}", v)
+    o.max_disagree, o.max_gap, o.max_joint_gap, o.min_joints, o.max_hold = prm.max_disagree, prm.max_gap, prm.max_joint_gap, prm.min_joints, prm.max_hold
+    return o
+
+
+def pose_track_into(prm, pose, frame, joints3d, T, S, dts, dt, state_in, state_out, tracks, placed, dev):
+    """the launch itself on ``dev``'s current stream: ``prm`` from ``track_params_struct``, tensors as the ABI takes them (frame, joints3d, dts may be
+    None; dt is read only without dts)"""
+    check(load().egotap_pose_track(_ptr(pose), _ptr(frame), _ptr(joints3d), int(T), int(S), pose.shape[1], joints3d.shape[1] if joints3d is not None else 0,
+                                   _ptr(dts), C.c_double(0.0 if dt is None else float(dt)), C.byref(prm), _ptr(state_in), _ptr(state_out), _ptr(tracks),
+                                   _ptr(placed), _stream(dev)))
+
+
+def pose_track(pose, state, dt=None, dts=None, params=None, frame=None, joints3d=None, streams=1):
+    """The pose, the root and the stereo joints filtered over time (egotap_pose_track, ``spec.pose_track_ref``): a One-Euro filter per 3-vector whose
+    state survives between calls.  pose float32 [T * streams, P, 3] on the GPU, T consecutive frames of ``streams`` camera rigs, time-major;
+    ``frame`` float32 [T * streams, 8] and ``joints3d`` float32 [T * streams, J, 8]: the last two results of a ``return_triangulation=True`` serving
+    call (None: the root / the joints are not tracked); ``state`` float64 [streams, P + 1 + J, 12] on the same device, all zeros for "never seen",
+    UPDATED IN PLACE; ``dt`` a positive number of seconds per step, or ``dts`` float32 [T] on the device (exactly one of the two); ``params`` a
+    ``spec.TrackParams`` (None: its defaults) -> (tracks float32 [T * streams, P + 1 + J, 8] = (x^, v^, cutoff, status), placed float32
+    [T * streams, P, 3] = the filtered pose plus the filtered root).  One launch on the current stream, no synchronisation."""
+    import torch
+    prm = track_params_struct(params)
+    S = int(streams)
+    if not torch.is_tensor(pose) or pose.dim() != 3 or pose.shape[2] != 3 or S < 1 or pose.shape[0] < S or pose.shape[0] % S:
+        raise ValueError(f"pose_track: pose is a tensor [T * streams, P, 3] with T >= 1, got {tuple(getattr(pose, 'shape', ()))} for {streams} streams")
+    B, P, _ = (int(v) for v in pose.shape)
+    T = B // S
+    if not 1 <= P <= 64:
+        raise ValueError(f"pose_track: 1 .. 64 pose rows, got {P}")
+    J = 0
+    if joints3d is not None:
+        if not torch.is_tensor(joints3d) or joints3d.dim() != 3 or joints3d.shape[0] != B or joints3d.shape[2] != 8 or not 1 <= joints3d.shape[1] <= 64:
+            raise ValueError(f"pose_track: joints3d is a tensor [T * streams, J, 8] with 1 .. 64 joints, got {tuple(getattr(joints3d, 'shape', ()))} for {B} frames")
+        J = int(joints3d.shape[1])
+    if frame is not None and (not torch.is_tensor(frame) or tuple(frame.shape) != (B, 8)):
+        raise ValueError(f"pose_track: frame is a tensor [T * streams, 8], got {tuple(getattr(frame, 'shape', ()))} for {B} frames")
+    K = P + 1 + J
+    if not torch.is_tensor(state) or tuple(state.shape) != (S, K, 12) or state.dtype != torch.float64 or not state.is_contiguous():
+        raise ValueError(f"pose_track: state is a contiguous float64 tensor [streams, P + 1 + J, 12] = {(S, K, 12)}, got "
+                         f"{getattr(state, 'dtype', type(state).__name__)} {tuple(getattr(state, 'shape', ()))}")
+    if (dt is None) == (dts is None):
+        raise ValueError("pose_track: give exactly one of dt (seconds per step) and dts (a float32 tensor [T] on the device)")
+    if dts is not None and (not torch.is_tensor(dts) or tuple(dts.shape) != (T,) or dts.dtype != torch.float32):
+        raise ValueError(f"pose_track: dts is a float32 tensor [T] = [{T}], got {getattr(dts, 'dtype', type(dts).__name__)} {tuple(getattr(dts, 'shape', ()))}")
+    if dt is not None and not (float(dt) > 0 and float(dt) != float("inf")):
+        raise ValueError(f"pose_track: dt must be finite and > 0, got {dt}")
+    if not pose.is_cuda or any(t is not None and t.device != pose.device for t in (frame, joints3d, dts, state)):
+        raise EgotapError("pose_track runs on the GPU only (no CPU fallback); pose, frame, joints3d, dts and state on one cuda device")
+    ps = pose.detach().float().contiguous()
+    fr = frame.detach().float().contiguous() if frame is not None else None
+    j3 = joints3d.detach().float().contiguous() if joints3d is not None else None
+    tracks = torch.empty((B, K, 8), dtype=torch.float32, device=ps.device)
+    placed = torch.empty((B, P, 3), dtype=torch.float32, device=ps.device)
+    with torch.cuda.device(ps.device):
+        pose_track_into(prm, ps, fr, j3, T, S, dts.contiguous() if dts is not None else None, dt, state, state, tracks, placed, ps.device)
+    return tracks, placed
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

@@ -36,6 +36,64 @@ def create_model(opt):
     return model
 
 
+class PoseTracker:
+    """The serving outputs followed over time on the device (``lib.pose_track``, egotap_pose_track, ``spec.pose_track_ref``): per stream (camera rig)
+    P pose rows, the root (the triangulation's t_hat) and J triangulated joints, each a One-Euro filtered 3-vector that is held over rejected frames
+    and forgotten after ``params.max_hold`` of them.  ``state``: float64 [streams, P + 1 + J, 12] on the device, zeros = never seen.  Made by
+    ``model.new_pose_tracker``; holds no reference to the model and takes no part in its graphs."""
+
+    def __init__(self, P, J, streams=1, params=None):
+        self.P, self.J, self.streams = int(P), int(J), int(streams)
+        if self.streams < 1:
+            raise ValueError(f"PoseTracker: streams must be at least 1, got {streams}")
+        self.params = _spec.TrackParams() if params is None else params
+        _lib.track_params_struct(self.params)              # (the field checks, now rather than at the first update)
+        self._state = None
+        self._unseen = None
+
+    @property
+    def state(self):
+        """the device tensor (made on the current cuda device at its first use: an update makes it on the pose's device)"""
+        return self._state_on(torch.device("cuda", torch.cuda.current_device()))
+
+    def _state_on(self, dev):
+        if self._state is None:
+            self._state = torch.zeros((self.streams, self.P + 1 + self.J, _spec.POSE_TRACK_STATE), dtype=torch.float64, device=dev)
+        return self._state
+
+    @torch.no_grad()
+    def update(self, pose, joints3d=None, frame=None, dt=None, dts=None):
+        """T consecutive frames of every stream, time-major: ``pose`` [T * streams, P, 3]; ``joints3d`` [T * streams, J, 8] and ``frame``
+        [T * streams, 8] the last two results of a ``return_triangulation=True`` serving call (None: no joint / no root is seen in these frames, which
+        holds their tracks); ``dt`` seconds per step, or ``dts`` float32 [T] on the device -> (placed [T * streams, P, 3], tracks
+        [T * streams, P + 1 + J, 8]).  ONE launch on the current stream, no synchronisation: it queues behind the serving call that made its inputs."""
+        if not torch.is_tensor(pose) or pose.dim() != 3 or tuple(pose.shape[1:]) != (self.P, 3):
+            raise ValueError(f"PoseTracker.update: pose is a tensor [T * streams, {self.P}, 3], got {tuple(getattr(pose, 'shape', ()))}")
+        if joints3d is not None and (not torch.is_tensor(joints3d) or joints3d.dim() != 3 or joints3d.shape[1] != self.J):
+            raise ValueError(f"PoseTracker.update: joints3d is a tensor [T * streams, {self.J}, 8], got {tuple(getattr(joints3d, 'shape', ()))}")
+        if not pose.is_cuda:
+            raise _lib.EgotapError("PoseTracker.update runs on the GPU only (no CPU fallback); move the pose to cuda")
+        if joints3d is None and self.J:                    # the state keeps its joint tracks: an all-invalid record per joint
+            if self._unseen is None or self._unseen.shape[0] != pose.shape[0] or self._unseen.device != pose.device:
+                self._unseen = torch.zeros((pose.shape[0], self.J, 8), dtype=torch.float32, device=pose.device)
+            joints3d = self._unseen
+        tracks, placed = _lib.pose_track(pose, self._state_on(pose.device), dt=dt, dts=dts, params=self.params, frame=frame, joints3d=joints3d,
+                                         streams=self.streams)
+        return placed, tracks
+
+    def reset(self, streams=None):
+        """forget everything (None) or the named streams: their next frame is a first frame"""
+        if self._state is None:
+            return
+        if streams is None:
+            self._state.zero_()
+        else:
+            idx = [int(s) for s in ([streams] if isinstance(streams, int) else streams)]
+            if any(not 0 <= s < self.streams for s in idx):
+                raise ValueError(f"PoseTracker.reset: streams are 0 .. {self.streams - 1}, got {idx}")
+            self._state[idx] = 0.0
+
+
 class EgoTAPAutoEncoderModel(nn.Module):
     def name(self):
         return "EgoTAP AutoEncoder model"
@@ -693,6 +751,14 @@ class EgoTAPAutoEncoderModel(nn.Module):
                                                                 stream(dev), ptr(kp)))
         return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch,
                                     kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), return_limbs=return_limbs, tri=tri)
+
+    def new_pose_tracker(self, streams=1, params=None):
+        """A ``PoseTracker`` for this model's outputs: P = the lifted pose's rows, J = the heatmap joints the triangulation returns; ``streams`` camera
+        rigs side by side, ``params`` a ``spec.TrackParams`` (None: its defaults, which nobody has tuned on real data).  Feed it what a serving entry
+        returns: ``pose, joints3d, frame = model.predict_pose_from_camera(l8, r8, return_triangulation=True)``;
+        ``placed, tracks = tracker.update(pose, joints3d, frame, dt=1 / 30)``.  The serving entries, their graphs and their outputs do not change."""
+        p = self.net_AutoEncoder.preset
+        return PoseTracker(p.out_joints, p.n_joints_hm, streams=streams, params=params)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

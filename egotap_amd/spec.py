@@ -681,3 +681,170 @@ def stereo_triangulate_ref(keypoints, left: OcamModel, right: OcamModel, t, R=No
         frame = np.stack([that[:, 0], that[:, 1], that[:, 2], n, np.sqrt(s2d / nn), mxd, np.sqrt(s2g / nn), mxg], axis=-1)
         frame = np.where((n > 0)[:, None], frame, 0.0)
     return rec.astype(dtype), frame.astype(dtype)
+
+
+# ---- the pose, the root and the stereo joints filtered over time (egotap.h: egotap_pose_track) ---------------------------------------------
+POSE_TRACK_STATE = 12                          # per track: x^ (3), v^ (3), m_prev (3), gap_t, age, live
+POSE_TRACK_MAX_ROWS = 64                       # P and J: one lane each
+TRACK_CLASSES = ("pose", "root", "joints")
+TWO_PI = 6.283185307179586
+
+
+@dataclass(frozen=True)
+class TrackParams:
+    """egotap.h egotap_track_params.  ``pose`` / ``root`` / ``joints``: (min_cutoff [Hz], beta [1 / (pose unit / s)], d_cutoff [Hz]) of the One-Euro
+    filter per class of track -- 1.0, 0.007, 1.0 are the paper's starting values (Casiez et al. 2012).  ``max_disagree`` / ``max_gap``: the frame's rms
+    disagree / rms gap above which the triangulation's t_hat is not accepted; ``max_joint_gap``: a joint's gap above which it is not; +inf: off.
+    ``min_joints``: fewest triangulated joints behind an accepted t_hat (below 3 it is a mean of one or two points); ``max_hold``: most consecutive
+    steps a track is held without an accepted sample before it is forgotten.  Nobody has tuned any of these on real data: there is no dataset here."""
+    pose: tuple = (1.0, 0.007, 1.0)
+    root: tuple = (1.0, 0.007, 1.0)
+    joints: tuple = (1.0, 0.007, 1.0)
+    max_disagree: float = math.inf
+    max_gap: float = math.inf
+    max_joint_gap: float = math.inf
+    min_joints: int = 3
+    max_hold: int = 8
+
+    def __post_init__(self):
+        for name in TRACK_CLASSES:
+            c = tuple(float(v) for v in getattr(self, name))
+            if len(c) != 3:
+                raise ValueError(f"TrackParams: {name} is (min_cutoff, beta, d_cutoff), got {len(c)} values")
+            if not (math.isfinite(c[0]) and c[0] > 0 and math.isfinite(c[2]) and c[2] > 0):
+                raise ValueError(f"TrackParams: {name}: min_cutoff and d_cutoff must be finite and > 0, got {c[0]}, {c[2]}")
+            if not (math.isfinite(c[1]) and c[1] >= 0):
+                raise ValueError(f"TrackParams: {name}: beta must be finite and >= 0, got {c[1]}")
+            object.__setattr__(self, name, c)
+        for name in ("max_disagree", "max_gap", "max_joint_gap"):
+            v = float(getattr(self, name))
+            if not v >= 0:
+                raise ValueError(f"TrackParams: {name} must be >= 0 (+inf: off), got {v}")
+            object.__setattr__(self, name, v)
+        for name in ("min_joints", "max_hold"):
+            v = int(getattr(self, name))
+            if v < 0:
+                raise ValueError(f"TrackParams: {name} must not be negative, got {v}")
+            object.__setattr__(self, name, v)
+
+    @classmethod
+    def uniform(cls, min_cutoff=1.0, beta=0.007, d_cutoff=1.0, **rest):
+        """the same filter for the three classes"""
+        c = (min_cutoff, beta, d_cutoff)
+        return cls(pose=c, root=c, joints=c, **rest)
+
+
+def pose_track_ref(pose, state, dt_or_dts, params=None, frame=None, joints3d=None, streams=1, dtype="float32"):
+    """The records and the state egotap_pose_track writes, restated in float64 numpy, operation for operation: pose [B, P, 3] with B = T * streams
+    frames, time-major (frame b = t * streams + s); state [streams, K, 12] float64 with K = P + 1 + J (not modified); ``dt_or_dts`` a positive number for
+    every step, or T values (rounded to float32 first: what the device reads); frame [B, 8] / joints3d [B, J, 8] the triangulation's records or None
+    -> (tracks [B, K, 8], placed [B, P, 3], new_state [streams, K, 12]).  Per track and step, with measurement m, accept flag a, ok = dt finite and
+    > 0, alpha(fc, te) = r / (r + 1), r = (6.283185307179586 fc) te:
+
+        not live, a      x^ = m_prev = m; v^ = 0; gap_t = age = 0; live = 1                                     status 1, cutoff = min_cutoff
+        not live, not a                                                                                         status 0, record all zeros
+        live, a and ok   te = gap_t + dt; ad = alpha(d_cutoff, te); dx = (m - m_prev) / te; v^ = v^ + ad (dx - v^);
+                         speed = sqrt(v^x v^x + v^y v^y + v^z v^z); fc = min_cutoff + beta speed; ax = alpha(fc, te);
+                         x^ = x^ + ax (m - x^); m_prev = m; gap_t = age = 0                                     status 1, cutoff = fc
+        live, otherwise  age += 1; if ok: gap_t += dt; age > max_hold: the state zeroed                         status 0, record all zeros
+                                                       else x^, v^ unchanged                                    status 2, cutoff = 0
+
+    a: a pose row is accepted when finite; the root (frame[:, 0:3]) when the frame is given, n >= min_joints, t_hat finite, rms disagree <=
+    max_disagree and rms gap <= max_gap; a joint when valid == 1, X finite and gap <= max_joint_gap (every comparison false on a NaN).
+    tracks = (x^, v^, cutoff, status); placed = x^_pose + x^_root (added in float64) while the root's status is 1 or 2, x^_pose alone otherwise, zeros
+    for a pose row of status 0.  Each output is rounded once from float64 (``dtype="float64"``: not at all)."""
+    import numpy as np
+    prm = TrackParams() if params is None else params
+    ps = np.asarray(pose, dtype=np.float64)
+    S = int(streams)
+    if ps.ndim != 3 or ps.shape[2] != 3 or S < 1 or ps.shape[0] < S or ps.shape[0] % S:
+        raise ValueError(f"pose_track_ref: pose is [T * streams, P, 3] with T >= 1, got {ps.shape} for {S} streams")
+    B, P, _ = ps.shape
+    T = B // S
+    J = 0
+    j3 = None
+    if joints3d is not None:
+        j3 = np.asarray(joints3d, dtype=np.float64)
+        if j3.ndim != 3 or j3.shape[0] != B or j3.shape[2] != 8 or j3.shape[1] < 1:
+            raise ValueError(f"pose_track_ref: joints3d is [T * streams, J, 8] with J >= 1, got {j3.shape} for {B} frames")
+        J = j3.shape[1]
+    if not (1 <= P <= POSE_TRACK_MAX_ROWS and J <= POSE_TRACK_MAX_ROWS):
+        raise ValueError(f"pose_track_ref: at most {POSE_TRACK_MAX_ROWS} pose rows and joints, got P = {P}, J = {J}")
+    fr = None
+    if frame is not None:
+        fr = np.asarray(frame, dtype=np.float64)
+        if fr.shape != (B, 8):
+            raise ValueError(f"pose_track_ref: frame is [T * streams, 8], got {fr.shape} for {B} frames")
+    K = P + 1 + J
+    st = np.array(state, dtype=np.float64)
+    if st.shape != (S, K, POSE_TRACK_STATE):
+        raise ValueError(f"pose_track_ref: state is [streams, P + 1 + J, {POSE_TRACK_STATE}] = {(S, K, POSE_TRACK_STATE)}, got {st.shape}")
+    if np.ndim(dt_or_dts) == 0:
+        if not (math.isfinite(float(dt_or_dts)) and float(dt_or_dts) > 0):
+            raise ValueError(f"pose_track_ref: dt must be finite and > 0, got {dt_or_dts}")
+        dts = np.full(T, float(dt_or_dts))
+    else:
+        dts = np.asarray(dt_or_dts, dtype=np.float32).astype(np.float64)
+        if dts.shape != (T,):
+            raise ValueError(f"pose_track_ref: dts holds one value per time step, [{T}], got {dts.shape}")
+    cls = np.empty((K, 3))                                   # (min_cutoff, beta, d_cutoff) per track
+    cls[:P], cls[P], cls[P + 1:] = prm.pose, prm.root, prm.joints
+    c_min, c_beta, c_d = (cls[None, :, k] for k in range(3))
+
+    def alpha(fc, te):
+        r = (TWO_PI * fc) * te
+        return r / (r + 1.0)
+    x, v, mp = st[..., 0:3].copy(), st[..., 3:6].copy(), st[..., 6:9].copy()
+    gap_t, age, live = st[..., 9].copy(), st[..., 10].copy(), st[..., 11] != 0
+    tracks = np.zeros((T, S, K, 8))
+    placed = np.zeros((T, S, P, 3))
+    meas = np.zeros((T, S, K, 3))
+    acc = np.zeros((T, S, K), dtype=bool)
+    with np.errstate(all="ignore"):
+        meas[:, :, :P] = ps.reshape(T, S, P, 3)
+        acc[:, :, :P] = np.isfinite(meas[:, :, :P]).all(axis=-1)
+        if fr is not None:
+            f = fr.reshape(T, S, 8)
+            meas[:, :, P] = f[..., 0:3]
+            acc[:, :, P] = (f[..., 3] >= prm.min_joints) & np.isfinite(f[..., 0:3]).all(axis=-1) & (f[..., 4] <= prm.max_disagree) & (f[..., 6] <= prm.max_gap)
+        if j3 is not None:
+            q = j3.reshape(T, S, J, 8)
+            meas[:, :, P + 1:] = q[..., 0:3]
+            acc[:, :, P + 1:] = (q[..., 7] == 1) & np.isfinite(q[..., 0:3]).all(axis=-1) & (q[..., 3] <= prm.max_joint_gap)
+        for t in range(T):
+            dt = dts[t]
+            ok = bool(np.isfinite(dt) and dt > 0)
+            a = acc[t]
+            m = np.where(a[..., None], meas[t], 0.0)          # a rejected measurement is never read
+            first = ~live & a
+            upd = live & a & ok
+            miss = live & ~upd
+            # live, accepted, ok (computed everywhere, kept where upd)
+            te = gap_t + dt
+            ad = alpha(c_d, te)
+            dx = (m - mp) / te[..., None]
+            v_u = v + ad[..., None] * (dx - v)
+            speed = np.sqrt(v_u[..., 0] * v_u[..., 0] + v_u[..., 1] * v_u[..., 1] + v_u[..., 2] * v_u[..., 2])
+            fc = c_min + c_beta * speed
+            ax = alpha(fc, te)
+            x_u = x + ax[..., None] * (m - x)
+            # live, otherwise
+            age_m = age + 1.0
+            gap_m = gap_t + dt if ok else gap_t
+            expire = miss & (age_m > prm.max_hold)
+            hold = miss & ~expire
+            x = np.where(first[..., None], m, np.where(upd[..., None], x_u, np.where(expire[..., None], 0.0, x)))
+            v = np.where(first[..., None] | expire[..., None], 0.0, np.where(upd[..., None], v_u, v))
+            mp = np.where((first | upd)[..., None], m, np.where(expire[..., None], 0.0, mp))
+            gap_t = np.where(first | upd | expire, 0.0, np.where(hold, gap_m, gap_t))
+            age = np.where(first | upd | expire, 0.0, np.where(hold, age_m, age))
+            live = (live | first) & ~expire
+            status = np.where(first | upd, 1.0, np.where(hold, 2.0, 0.0))
+            cutoff = np.where(first, c_min, np.where(upd, fc, 0.0))
+            rec = np.concatenate([x, v, cutoff[..., None], status[..., None]], axis=-1)
+            tracks[t] = np.where((status != 0)[..., None], rec, 0.0)
+            root_on = status[:, P] != 0
+            pl = np.where(root_on[:, None, None], x[:, :P] + x[:, P:P + 1], x[:, :P])
+            placed[t] = np.where((status[:, :P] != 0)[..., None], pl, 0.0)
+    new_state = np.concatenate([x, v, mp, gap_t[..., None], age[..., None], live[..., None].astype(np.float64)], axis=-1)
+    return tracks.reshape(B, K, 8).astype(dtype), placed.reshape(B, P, 3).astype(dtype), new_state

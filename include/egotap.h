@@ -341,6 +341,50 @@ int egotap_ocam_unproject(const float* points2d, int N, const egotap_ocam* model
 int egotap_stereo_triangulate(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
                               const double* affine, double min_score, const float* pose, int P, int pose_row0, float* joints3d, float* frame, void* stream);
 
+/* ---- the pose, the root and the stereo joints filtered over time (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * Every serving output is a single-frame estimate; egotap_pose_track follows them over time with a One-Euro filter (Casiez et al. 2012) on 3-vectors in
+ * which a missing sample is irregular sampling.  A TRACK is one 3-vector followed over time, a STREAM one camera rig.  A call carries T consecutive frames of
+ * S streams, time-major: frame b = t * S + s, B = T * S.  Stream s has K = P + 1 + J tracks:
+ *   0 .. P-1      pose[b, row]            (device f32 [B, P, 3])                             accepted when the three values are finite
+ *   P (the root)  frame[b, 0:3] = t_hat   (device f32 [B, 8], the triangulation's; or NULL)  accepted when frame is given, n >= min_joints, t_hat is
+ *                                                                                             finite, rms disagree <= max_disagree, rms gap <= max_gap
+ *   P+1 .. P+J    joints3d[b, j, 0:3] = X (device f32 [B, J, 8], the triangulation's; NULL   accepted when valid == 1, X is finite,
+ *                                          exactly when J = 0)                                gap <= max_joint_gap
+ * Every comparison is false on a NaN; a threshold of +inf lets every value but a NaN through.  state [S, K, 12] float64 on the device holds per track
+ * (x^[3], v^[3], m_prev[3], gap_t, age, live); all zeros is "never seen", so a reset is a memset.  One step of one track with measurement m, accept flag a
+ * and step time dt, in float64 without contraction and in exactly this order; ok = dt finite and dt > 0; alpha(fc, te) = r / (r + 1) with
+ * r = (6.283185307179586 fc) te:
+ *   not live, a      x^ = m_prev = m, v^ = 0, gap_t = 0, age = 0, live = 1                               status 1, cutoff = min_cutoff  (needs no dt)
+ *   not live, not a                                                                                      status 0, the record all zeros
+ *   live, a and ok   te = gap_t + dt, ad = alpha(d_cutoff, te); per c: dx = (m_c - m_prev_c) / te, v^_c = v^_c + ad (dx - v^_c);
+ *                    speed = sqrt(v^x v^x + v^y v^y + v^z v^z) (added in that order); fc = min_cutoff + beta speed, ax = alpha(fc, te);
+ *                    per c: x^_c = x^_c + ax (m_c - x^_c); m_prev = m, gap_t = 0, age = 0                status 1, cutoff = fc
+ *   live, otherwise  age += 1; if ok: gap_t += dt;  age > max_hold: the track's state zeroed             status 0, the record all zeros
+ *                                                   else: x^, v^ unchanged                               status 2, cutoff = 0
+ * The derivative is taken between ACCEPTED RAW samples (the paper's own code), so v^ converges to the slope of a ramp; a held frame is a missing sample:
+ * the next accepted one sees the elapsed time te, and a dropped frame gives the bits of "the frame removed, the next dt longer".  A rejected measurement is
+ * never read into the state.  Outputs are f32, each value rounded once from float64:
+ *   tracks [B, K, 8] = (x^, y^, z^, v^x, v^y, v^z, cutoff, status)
+ *   placed [B, P, 3] = the filtered pose row plus the filtered root, added in float64, when the root's status is 1 or 2; the filtered pose row alone when
+ *                      it is 0; zeros for a pose row whose own status is 0 -- the skeleton in the left camera's frame, smoothed and held over bad frames
+ * Time: dts (device f32 [T], one value per time step, shared by the S streams) or, with dts NULL, the host double dt for every step.
+ * One wave per stream, four streams per workgroup, the T steps a loop inside the ONE launch, the state in registers between its one read and its one write;
+ * no handle, no allocation, no atomics, no workspace, plain vector stores; recorded as pose_track while a handle's timing hook is on.  state_out may be
+ * state_in (in place).  egotap_amd/spec.py pose_track_ref restates the records and the state; TrackParams there holds the defaults.
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL pose, state_in, state_out, tracks, placed or params; a misaligned pointer (f32 arrays 4 bytes,
+ * tracks 16, the states 8); T, S or P <= 0; P > 64; J < 0, J > 64, J > 0 without joints3d or joints3d with J = 0; dts NULL with a dt that is not finite
+ * and > 0; a min_cutoff or d_cutoff that is not finite and > 0; a beta that is not finite and >= 0; a gate that is NaN or < 0; min_joints < 0;
+ * max_hold < 0; an output that overlaps an input or another output (state_out partly overlapping state_in included). */
+typedef struct egotap_track_params {
+    double pose_min_cutoff, pose_beta, pose_d_cutoff;       /* Hz, 1 / (pose unit / s), Hz */
+    double root_min_cutoff, root_beta, root_d_cutoff;
+    double joints_min_cutoff, joints_beta, joints_d_cutoff;
+    double max_disagree, max_gap, max_joint_gap;            /* the gates, in the pose's units; +inf: off */
+    int32_t min_joints, max_hold;                           /* fewest triangulated joints behind an accepted t_hat; most consecutive held steps */
+} egotap_track_params;
+int egotap_pose_track(const float* pose, const float* frame, const float* joints3d, int T, int S, int P, int J, const float* dts, double dt,
+                      const egotap_track_params* params, const double* state_in, double* state_out, float* tracks, float* placed, void* stream);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

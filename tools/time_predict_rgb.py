@@ -15,6 +15,8 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
   keypoints   predict_pose_from_rgb(return_keypoints=True): the 2D joints and confidences from the same call
   limbs       predict_pose_from_rgb(return_limbs=True): the limb elevation angles and 2D segments from the same call
   triangulation  predict_pose_from_rgb(return_triangulation=True): the keypoints triangulated through a stereo rig, one more launch behind the call
+  tracking    the triangulation arm followed by PoseTracker.update on its pose, joints3d and frame: the B frames as B consecutive steps of one stream, one
+              more launch behind the triangulation's (report only)
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -78,10 +80,18 @@ def arms_for(m, p, left, right):
         flat.amax(dim=2), flat.argmax(dim=2)
         return pose
 
+    tracker = m.new_pose_tracker(streams=1)
+
+    def tracking():
+        pose, joints3d, frame = m.predict_pose_from_rgb(left, right, return_triangulation=True)
+        tracker.update(pose, joints3d, frame, dt=1.0 / 30)
+        return pose
+
     return {"parent": parent,
             "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
             "limbs": lambda: m.predict_pose_from_rgb(left, right, return_limbs=True)[0],
             "triangulation": lambda: m.predict_pose_from_rgb(left, right, return_triangulation=True)[0],
+            "tracking": tracking,
             "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
@@ -210,7 +220,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking") else ""
                 print(f"{setting:12s} B={B:<4d} {k:12s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
