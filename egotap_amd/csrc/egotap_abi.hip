@@ -2199,34 +2199,35 @@ extern "C" int egotap_hm_forward_u8(egotap_handle h, int net, const uint8_t* lef
 // ------------------------------------------------------------------------------------------------ stereo RGB -> pose in one call
 // egotap_predict_pose_rgb: both estimators (eval mode, in pieces of `chunk` frames, one U-Net scratch) and then the pose-only head, composed from
 // hm_forward_impl and lift_forward_impl -- every kernel choice is theirs.  Workspace: [ scratch = max(estimator scratch of a chunk, head scratch of the
-// batch): the two never run at once | the heatmaps: fp32 [B, 6J, S, S] when the caller passes none, or their bf16 hand-off form ].
-struct RgbWs { size_t HM, total; };
+// batch): the two never run at once | the heatmaps: fp32 [B, 6J, S, S] when the caller passes none, or their bf16 hand-off form | a byte source's
+// converter slice of one chunk, where the stems do not read bytes themselves | [r8] a sensor source's resized bytes of one chunk: n frames x 2 eyes x
+// 3 S0^2 bytes (OUTPUT frames: H and W do not enter) ].  The one statement of it: the size queries, the walk and the debug query read nothing else.
+enum RgbSource { RGB_SRC_F32, RGB_SRC_U8, RGB_SRC_SENSOR };
+struct RgbWs { size_t HM /* = the scratch's bytes */, conv, resized, total; };
 static inline int rgb_chunk(int B, int chunk) { return chunk <= 0 || chunk > B ? B : chunk; }
-static RgbWs rgb_ws(const Handle* h, int B, int chunk) {
-    const size_t a = hm_ws(h, rgb_chunk(B, chunk)).total, b = lift_ws(h, B).total;
+static RgbWs rgb_ws(const Handle* h, int B, int chunk, RgbSource kind) {
+    const int c = rgb_chunk(B, chunk);
+    const size_t a = hm_ws(h, c).total, b = lift_ws(h, B).total, S0 = (size_t)h->cfg.hm_size * 4;
     RgbWs w;
     w.HM = al256(a > b ? a : b);
-    w.total = w.HM + al256((size_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size * 4);
+    w.conv = w.HM + al256((size_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size * 4);
+    w.resized = w.conv + (kind == RGB_SRC_F32 ? 0 : hm_u8_slice_bytes(h, c));
+    w.total = w.resized + (kind == RGB_SRC_SENSOR ? (size_t)c * 2 * 3 * S0 * S0 : 0);
     return w;
 }
 // The hand-off: nobody asked for the fp32 heatmaps, the estimators run the bf16 channels-last route (whose conv_heatmap is the bf16-storage GEMM) and
 // the head runs its bf16-storage route (which reads a bf16 copy of the heatmaps and nothing else of them): conv_heatmap then writes that copy itself.
-// [r8] the resized bytes of one piece of a sensor-source call: n frames x 2 eyes x 3 S0^2 bytes
-static inline size_t rgb_sensor_slice_bytes(const Handle* h, int n) {
-    const size_t S0 = (size_t)h->cfg.hm_size * 4;
-    return (size_t)n * 2 * 3 * S0 * S0;
-}
 static bool rgb_handoff(const Handle* h, int B, const float* heatmaps) { return heatmaps == nullptr && hm_frozen_route(h) && lift_bf16s_route(h, B); }
 
 extern "C" int egotap_predict_pose_rgb_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
     EGO_CHECK(h && bytes, "egotap_predict_pose_rgb_workspace_bytes: null argument");
     EGO_CHECK(B >= 0 && chunk >= 0, "egotap_predict_pose_rgb_workspace_bytes: negative batch or chunk");
-    *bytes = rgb_ws(h, B > 0 ? B : 1, chunk).total;
+    *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_F32).total;
     return EGOTAP_OK;
 }
 
-// the walk both one-call entries share: `src` holds the whole batch's frames (fp32, or bytes -- then the workspace ends with the converter slice of
-// one chunk where the stems do not read bytes themselves); the argument checks that depend on the source are the entries' own
+// the walk the one-call entries share: `src` holds the whole batch's frames (fp32, or bytes, or a sensor's frames behind `src.sensor`); the argument
+// checks that depend on the source are the entries' own
 // keypoints != nullptr (the _kp entries): the peaks of the 2J position maps, one launch over the batch between the estimators and the head, read
 // from whichever form of the heatmaps this call holds; kp_affine: 2 x 4 floats (left eye, right eye)
 // limbs != nullptr (the _kpl entries): the records of the 2J (cos, sin) pairs of the limb maps (limb_decode.h), one more launch right behind it on the
@@ -2241,14 +2242,17 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
             return EGOTAP_ERR_INVALID;
         }
     }
-    const RgbWs w = rgb_ws(h, B, chunk);
+    const RgbSource kind = src.sensor ? RGB_SRC_SENSOR : src.bytes() ? RGB_SRC_U8 : RGB_SRC_F32;      // [r8] a sensor source is a byte source behind a resize
+    const RgbWs w = rgb_ws(h, B, chunk, kind);
     const int c = rgb_chunk(B, chunk), S = h->cfg.hm_size, HW = S * S, J = h->J;
-    // [r8] a sensor source is a byte source behind a resize: [ ... | the converter slice, where the stems do not read bytes | the resized bytes of one chunk ]
-    const size_t conv = src.bytes() || src.sensor ? hm_u8_slice_bytes(h, c) : 0;
-    const size_t need = w.total + conv + (src.sensor ? rgb_sensor_slice_bytes(h, c) : 0);
-    EGO_CHECK(ws_bytes >= need, "%s: workspace too small: %zu bytes given, %zu needed for B=%d, chunk=%d", who, ws_bytes, need, B, chunk);
+    EGO_CHECK(ws_bytes >= w.total, "%s: workspace too small: %zu bytes given, %zu needed for B=%d, chunk=%d", who, ws_bytes, w.total, B, chunk);
     HmSrc whole = src;
-    whole.scratch = src.bytes() || src.sensor ? (float*)((char*)ws + w.total) : nullptr;
+    HmSensor sensor{};
+    whole.scratch = kind != RGB_SRC_F32 ? (float*)((char*)ws + w.conv) : nullptr;
+    if (src.sensor) {
+        sensor = *src.sensor;
+        sensor.slice = (unsigned char*)ws + w.resized;
+    }
     const long img = (long)h->C * HW, rgb = 3L * (4 * S) * (4 * S);
     const bool handoff = rgb_handoff(h, B, heatmaps);
     float* hm = heatmaps ? heatmaps : (float*)((char*)ws + w.HM);
@@ -2256,53 +2260,39 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
     h->rgb_form = EGOTAP_RGB_FORM_NONE;
     // position net: channels [0, 2J) (left | right); limb net: [2J, 6J) (left cos, sin | right cos, sin)
     const int nets[2] = {EGOTAP_NET_HM_POS, EGOTAP_NET_HM_ROT}, c0[2] = {0, 2 * J};
-    if (src.sensor && !src.bytes()) {
-        // [r8] the sensor route: a piece's frames are resized ONCE into the slice and read there as camera bytes by both estimators (pieces outer,
-        // estimators inner) -- by the byte-source stems at sides 64 / 128, through the converter elsewhere.  (With bytes() set the request is the
-        // identity: the caller's frames ARE the camera bytes and the walks below read them in place.)
-        const HmSensor& q = *src.sensor;
-        const long frame = 3L * q.H * q.W;
-        unsigned char* s8l = q.slice;
+    const bool resize = src.sensor && !src.bytes(), stems = hm_stem_reads_bytes(S);
+    if (resize || (src.bytes() && !stems)) {
+        // the prepared walk (pieces outer, estimators inner): a piece's frames are made ready ONCE and both estimators read them there, sharing the
+        // U-Net scratch one after the other, as ever.  [r8] A sensor's frames are resized into the slice and are camera bytes from there on.  (A sensor
+        // source with bytes() set is the identity request: the caller's frames ARE the camera bytes and are read in place.)  Bytes are read by the
+        // byte-source stems at sides 64 / 128 and go through the converter into its slice elsewhere (never with the hand-off: that exists at sides
+        // 64 / 128 only).
+        unsigned char* s8l = sensor.slice;
+        const long frame = 3L * sensor.H * sensor.W;
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
-            unsigned char* s8r = s8l + (size_t)n * rgb;
-            {
+            HmSrc piece = whole.at(lo, rgb);
+            if (resize) {
+                unsigned char* s8r = s8l + (size_t)n * rgb;
                 GemmTimer t(h, (hipStream_t)stream, "rgb_u8_resize", "rgb_u8_resize_kernel", 0.0);
-                EGO_HIP(rgb_u8_resize_launch(q.left8 + lo * frame, q.right8 + lo * frame, n, q.H, q.W, q.rect[0], q.rect[1], q.mirror[0], q.mirror[1], 4 * S, s8l, s8r,
-                                             device_cu_count(), (hipStream_t)stream));
+                EGO_HIP(rgb_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, sensor.H, sensor.W, sensor.rect[0], sensor.rect[1],
+                                             sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
+                piece = HmSrc{nullptr, nullptr, s8l, s8r, src.table, nullptr};
             }
-            HmSrc piece{nullptr, nullptr, s8l, s8r, src.table, nullptr};
-            const bool stems = hm_stem_reads_bytes(S);
             if (!stems) {
                 float *cl = whole.scratch, *cr = cl + (size_t)n * rgb;
                 GemmTimer t(h, (hipStream_t)stream, "rgb_u8_to_f32", "rgb_u8_to_f32_kernel", 0.0);
-                EGO_HIP(rgb_u8_to_f32_launch(s8l, s8r, src.table, cl, cr, n, 4 * S, device_cu_count(), (hipStream_t)stream));
+                EGO_HIP(rgb_u8_to_f32_launch(piece.left8, piece.right8, src.table, cl, cr, n, 4 * S, device_cu_count(), (hipStream_t)stream));
                 piece = hm_src_f32(cl, cr);
             }
+            const bool ho = stems && handoff;
             for (int k = 0; k < 2; ++k) {
                 const long at = lo * img + (long)c0[k] * HW;
-                const bool ho = stems && handoff;
                 const int rc = hm_forward_impl(h, nets[k], piece, n, ho ? nullptr : hm + at, img, ws, w.HM, stream, ho ? hmb + at : nullptr);
                 if (rc != EGOTAP_OK) return rc;
             }
         }
-    } else if (src.bytes() && !hm_stem_reads_bytes(S)) {
-        // the converter route: a piece's frames are converted ONCE into the slice and both estimators read them there (pieces outer, estimators inner;
-        // the two share the U-Net scratch one after the other, as ever; never the hand-off: that exists at sides 64 / 128 only)
-        float* cl = whole.scratch;
-        for (int lo = 0; lo < B; lo += c) {
-            const int n = B - lo < c ? B - lo : c;
-            float* cr = cl + (size_t)n * rgb;
-            {
-                GemmTimer t(h, (hipStream_t)stream, "rgb_u8_to_f32", "rgb_u8_to_f32_kernel", 0.0);
-                EGO_HIP(rgb_u8_to_f32_launch(src.left8 + lo * rgb, src.right8 + lo * rgb, src.table, cl, cr, n, 4 * S, device_cu_count(), (hipStream_t)stream));
-            }
-            for (int k = 0; k < 2; ++k) {
-                const int rc = hm_forward_impl(h, nets[k], hm_src_f32(cl, cr), n, hm + lo * img + (long)c0[k] * HW, img, ws, w.HM, stream, nullptr);
-                if (rc != EGOTAP_OK) return rc;
-            }
-        }
-    } else
+    } else      // float frames, and bytes the stems read themselves: estimators outer, pieces inner
     for (int k = 0; k < 2; ++k)
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
@@ -2346,16 +2336,32 @@ static const char* rgb_kp_refusal(const Handle* h, int B, const float* pose, con
 }
 static const float kRgbKpAffine[8] = {4.f, 0.f, 4.f, 0.f, 4.f, 0.f, 4.f, 0.f};      // heatmap pixels -> pixels of the S0 = 4 S input frame, both eyes
 
-static int predict_pose_rgb_entry(const char* who, egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
-                                  size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
+// What the three *_entry functions below check alike, in the order they always did: the handle and the batch; `source_why`, what the entry's own
+// source refuses about its frame arguments (nullptr: nothing; tested by the entry, told here, in its place); pose, ws, the chunk and the alignments --
+// with the float entry's frames (`f32`: left, right; nullptr for a byte entry, whose source_why spoke for its frames) in the same two statements; for
+// frames that go through the resize (`resized`) its side limit; the extra outputs.
+static int rgb_entry_checks(const char* who, egotap_handle h, int B, const char* source_why, const float* const* f32, const float* pose, const float* heatmaps,
+                            int chunk, const void* ws, bool resized, bool kp, const float* keypoints, const float* limbs) {
     EGO_CHECK(h, "%s: null handle", who);
     EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    EGO_CHECK(left && right && pose && ws, "%s: null argument (left, right, pose and ws are required; only heatmaps may be NULL)", who);
+    EGO_CHECK(!source_why, "%s: %s", who, source_why);
+    const char* frames = f32 ? "left, right, " : "";
+    EGO_CHECK((!f32 || (f32[0] && f32[1])) && pose && ws, "%s: null argument (%spose and ws are required; only heatmaps may be NULL)", who, frames);
     EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
-    EGO_CHECK((((uintptr_t)left | (uintptr_t)right | (uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0,
-              "%s: left, right, pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
+    const uintptr_t bits = (f32 ? (uintptr_t)f32[0] | (uintptr_t)f32[1] : 0) | (uintptr_t)pose | (uintptr_t)heatmaps;
+    EGO_CHECK((bits & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: %spose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who, frames);
+    const int S0 = 4 * h->cfg.hm_size;
+    EGO_CHECK(!resized || S0 <= kResizeMaxSide, "%s: the frame side 4 * hm_size = %d is beyond the resize kernel's %d", who, S0, kResizeMaxSide);
     const char* why = rgb_kp_refusal(h, B, pose, heatmaps, kp, keypoints, limbs);
     EGO_CHECK(!why, "%s: %s", who, why);
+    return EGOTAP_OK;
+}
+
+static int predict_pose_rgb_entry(const char* who, egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
+                                  size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
+    const float* const frames[2] = {left, right};
+    const int rc = rgb_entry_checks(who, h, B, nullptr, frames, pose, heatmaps, chunk, ws, false, kp, keypoints, limbs);
+    if (rc != EGOTAP_OK) return rc;
     return predict_pose_rgb_impl(who, h, hm_src_f32(left, right), B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, kRgbKpAffine, limbs);
 }
 extern "C" int egotap_predict_pose_rgb(egotap_handle h, const float* left, const float* right, int B, float* pose, float* heatmaps, int chunk, void* ws,
@@ -2375,21 +2381,13 @@ extern "C" int egotap_predict_pose_rgb_kpl(egotap_handle h, const float* left, c
 extern "C" int egotap_predict_pose_rgb_u8_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
     EGO_CHECK(h && bytes, "egotap_predict_pose_rgb_u8_workspace_bytes: null argument");
     EGO_CHECK(B >= 0 && chunk >= 0, "egotap_predict_pose_rgb_u8_workspace_bytes: negative batch or chunk");
-    const int b = B > 0 ? B : 1;
-    *bytes = rgb_ws(h, b, chunk).total + hm_u8_slice_bytes(h, rgb_chunk(b, chunk));
+    *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_U8).total;
     return EGOTAP_OK;
 }
 static int predict_pose_rgb_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const float* table, float* pose,
                                      float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
-    EGO_CHECK(h, "%s: null handle", who);
-    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    const char* why = rgb_u8_refusal(left8, right8, table);
-    EGO_CHECK(!why, "%s: %s", who, why);
-    EGO_CHECK(pose && ws, "%s: null argument (pose and ws are required; only heatmaps may be NULL)", who);
-    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
-    EGO_CHECK((((uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
-    why = rgb_kp_refusal(h, B, pose, heatmaps, kp, keypoints, limbs);
-    EGO_CHECK(!why, "%s: %s", who, why);
+    const int rc = rgb_entry_checks(who, h, B, rgb_u8_refusal(left8, right8, table), nullptr, pose, heatmaps, chunk, ws, false, kp, keypoints, limbs);
+    if (rc != EGOTAP_OK) return rc;
     const HmSrc src{nullptr, nullptr, left8, right8, table, nullptr};
     return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, kRgbKpAffine, limbs);
 }
@@ -2433,34 +2431,25 @@ extern "C" int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, in
     EGO_CHECK(h && bytes, "%s: null argument", who);
     EGO_CHECK(B >= 0 && chunk >= 0, "%s: negative batch or chunk", who);
     EGO_CHECK(H >= 1 && W >= 1 && H <= kResizeMaxSrc && W <= kResizeMaxSrc, "%s: the frame height and width must be between 1 and 16384", who);
-    const int b = B > 0 ? B : 1, c = rgb_chunk(b, chunk);
-    *bytes = rgb_ws(h, b, chunk).total + hm_u8_slice_bytes(h, c) + rgb_sensor_slice_bytes(h, c);      // (the slice holds OUTPUT frames: H and W do not enter)
+    *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_SENSOR).total;
     return EGOTAP_OK;
 }
 static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
                                         const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
                                         bool kp, float* keypoints, float* limbs) {
-    EGO_CHECK(h, "%s: null handle", who);
-    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    EGO_CHECK(rects && mirrors, "%s: null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)", who);
-    const char* why = rgb_u8_resize_refusal(left8, right8, H, W, rects, rects + 4);
-    EGO_CHECK(!why, "%s: %s", who, why);
-    why = rgb_u8_refusal(left8, right8, table);
-    EGO_CHECK(!why, "%s: %s", who, why);
-    EGO_CHECK(pose && ws, "%s: null argument (pose and ws are required; only heatmaps may be NULL)", who);
-    EGO_CHECK(chunk >= 0, "%s: negative chunk (0 = the whole batch)", who);
-    EGO_CHECK((((uintptr_t)pose | (uintptr_t)heatmaps) & 15) == 0 && ((uintptr_t)ws & 255) == 0, "%s: pose and heatmaps must be 16-byte aligned, ws 256-byte aligned", who);
-    const int S0 = 4 * h->cfg.hm_size, c = rgb_chunk(B, chunk);
-    EGO_CHECK(S0 <= kResizeMaxSide, "%s: the frame side 4 * hm_size = %d is beyond the resize kernel's %d", who, S0, kResizeMaxSide);
+    const char* why = !(rects && mirrors) ? "null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)"
+                                          : rgb_u8_resize_refusal(left8, right8, H, W, rects, rects + 4);
+    const int rc = rgb_entry_checks(who, h, B, why ? why : rgb_u8_refusal(left8, right8, table), nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
+    if (rc != EGOTAP_OK) return rc;
+    const int S0 = 4 * h->cfg.hm_size;
+    // (q.slice is the walk's to place: the workspace layout is read there, once)
     HmSensor q{left8, right8, H, W, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}}, {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0},
-               (unsigned char*)ws + rgb_ws(h, B, chunk).total + hm_u8_slice_bytes(h, c)};
+               nullptr};
     // the identity request (frames already S0 x S0, the full frame, no mirror): the caller's frames are read in place, nothing is resized
     bool identity = H == S0 && W == S0 && !q.mirror[0] && !q.mirror[1];
     for (int e = 0; e < 2; ++e) identity = identity && q.rect[e][0] == 0 && q.rect[e][1] == 0 && q.rect[e][2] == S0 && q.rect[e][3] == S0;
     HmSrc src{nullptr, nullptr, identity ? left8 : nullptr, identity ? right8 : nullptr, table, nullptr};
     src.sensor = &q;
-    why = rgb_kp_refusal(h, B, pose, heatmaps, kp, keypoints, limbs);
-    EGO_CHECK(!why, "%s: %s", who, why);
     // heatmap pixels -> pixels of the eye's sensor frame: the inverse of the map rgb_u8_resize_kernel applies (pixel centres at i + 0.5, align_corners =
     // False); a mirrored eye's output column X shows source column S0 - 1 - X, so its x runs backwards from the rectangle's right edge
     float affine[8];
@@ -2672,7 +2661,7 @@ extern "C" int egotap_debug_predict_pose_rgb_intermediate(egotap_handle h, int B
     EGO_CHECK(h && name && offset && numel, "egotap_debug_predict_pose_rgb_intermediate: null argument");
     EGO_CHECK(B > 0 && chunk >= 0, "egotap_debug_predict_pose_rgb_intermediate: the batch must be positive, the chunk not negative");
     EGO_CHECK(!strcmp(name, "heatmaps") || !strcmp(name, "handoff"), "egotap_debug_predict_pose_rgb_intermediate: unknown intermediate '%s' (heatmaps, handoff)", name);
-    *offset = rgb_ws(h, B, chunk).HM;
+    *offset = rgb_ws(h, B, chunk, RGB_SRC_F32).HM;
     *numel = (int64_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size;
     return EGOTAP_OK;
 }

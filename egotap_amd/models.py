@@ -13,6 +13,7 @@ import copy
 import ctypes as C
 import os
 from collections import OrderedDict
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -92,6 +93,23 @@ class PoseTracker:
             if any(not 0 <= s < self.streams for s in idx):
                 raise ValueError(f"PoseTracker.reset: streams are 0 .. {self.streams - 1}, got {idx}")
             self._state[idx] = 0.0
+
+
+class _Source(NamedTuple):
+    """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor); everything else about a request is ``_serve``'s."""
+    who: str                          # the entry's name, for messages
+    left: torch.Tensor                # the frames as the ABI entry reads them (a graph's static inputs are clones of these) ...
+    right: torch.Tensor
+    B: int                            # ... and their batch
+    size_query: Callable              # (h, B, chunk, &bytes): the entry's workspace size
+    entries: tuple                    # the ABI functions: (base, _kp, _kpl)
+    args: tuple                       # their arguments between the frames and ``pose``
+    kind: tuple = ()                  # what the capture key holds besides: two sources never share a graph
+    keep: tuple = ()                  # tensors a graph must keep alive besides its own buffers
+    float_frames: Optional[Callable] = None       # () -> the float frames the module route reads (None: left / right are those)
+    keypoint_affine: Optional[list] = None        # the module route's heatmap -> frame pixel map per eye (None: x 4)
+    triangulation_affine: Optional[tuple] = None  # ``_triangulation``'s affine (None: size / (4S))
+    module_route: str = "the module forwards"     # what the ``graphed=True`` refusal says this configuration runs instead
 
 
 class EgoTAPAutoEncoderModel(nn.Module):
@@ -490,8 +508,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
         return _lib.stereo_triangulate_args(left, right, t, R, affine, min_score), ("triangulation", rig, affine), affine, _spec.stereo_pose_row0(p)
 
     @torch.no_grad()
-    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False,
-                              return_triangulation=False, _triangulation_affine=None):
+    def predict_pose_from_rgb(self, left, right, return_heatmaps=False, graphed=False, return_keypoints=False, return_limbs=False, return_triangulation=False):
         """Serving entry: stereo RGB [B, 3, 4S, 4S] x 2 -> pose [B, J(+1), 3], or (pose, heatmaps [B, 6J, S, S]) with ``return_heatmaps``.
         Replaces set_input() + evaluate() (utils/evaluate.py:104-114 without the metrics; egotap_autoencoder_model.py:177-223) for a caller
         that has no ground truth: no set_input, no loader keys, no autograd.  ONE library call (egotap_predict_pose_rgb): both estimators in
@@ -534,49 +551,11 @@ class EgoTAPAutoEncoderModel(nn.Module):
         B = left.shape[0]
         if tuple(left.shape) != (B, 3, S0, S0) or tuple(right.shape) != (B, 3, S0, S0):
             raise ValueError(f"expected left / right [B, 3, {S0}, {S0}], got {tuple(left.shape)} / {tuple(right.shape)}")
-        dev = left.device
-        left, right = left.detach().float().contiguous(), right.detach().float().contiguous()
-        chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
-        tri = self._triangulation("predict_pose_from_rgb", return_triangulation, _triangulation_affine)
-        why = self._rgb_one_call_refusal()
-        if why is not None:
-            if graphed:
-                raise _lib.EgotapError(f"predict_pose_from_rgb(graphed=True): {why}; this configuration runs the module forwards, ungraphed")
-            # the modules' inference forwards refuse train mode (theirs is then the differentiable path): say so before anything runs
-            for name in self.model_names:
-                if getattr(self, "net_" + name).training:
-                    raise _lib.EgotapError(f"predict_pose_from_rgb: {why}; this configuration runs the module forwards, which need net_{name} in "
-                                           "eval mode (model.eval())")
-            cat = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev)
-            J = p.n_joints_hm
-            same = self.net_HeatMap.blocks == self.net_RotHeatMap.blocks          # one scratch for both estimators where their sizes agree
-            for net, c0 in ((self.net_HeatMap, 0), (self.net_RotHeatMap, 2 * J)):
-                ws = None if net.bottleneck else (self.net_HeatMap if same else net)._workspace(chunk, dev)
-                for lo in range(0, B, chunk):
-                    net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
-            pose = self.net_AutoEncoder.predict_pose(cat)
-            kp = lb = None
-            affine = _keypoint_affine or [(4.0, 0.0, 4.0, 0.0)] * 2
-            if return_keypoints or tri is not None:
-                kp = _lib.heatmap_peaks(cat, 0, 2 * J, groups=2, affine=affine).view(B, 2, J, 4)
-            if return_limbs:
-                lb = _lib.limb_decode(cat, 2 * J, J, eyes=2, affine=affine)
-            tr = None
-            if tri is not None:
-                rig_l, rig_r, rig_t, rig_R, min_score = self._stereo_rig
-                tr = _lib.stereo_triangulate(kp, rig_l, rig_r, rig_t, R=rig_R, affine=tri[2], min_score=min_score, pose=pose, pose_row0=tri[3])
-            return self._served(pose, cat if return_heatmaps else None, kp if return_keypoints else None, lb, tr)
         lib = _lib.load()
-
-        def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
-            if lb is not None:
-                _lib.check(lib.egotap_predict_pose_rgb_kpl(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp), ptr(lb)))
-            elif kp is None:
-                _lib.check(lib.egotap_predict_pose_rgb(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
-            else:
-                _lib.check(lib.egotap_predict_pose_rgb_kp(h, ptr(l), ptr(r), B, ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
-        return self._serve_one_call(left, right, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_workspace_bytes, launch,
-                                    return_limbs=return_limbs, tri=tri)
+        left, right = left.detach().float().contiguous(), right.detach().float().contiguous()
+        src = _Source("predict_pose_from_rgb", left, right, B, lib.egotap_predict_pose_rgb_workspace_bytes,
+                      (lib.egotap_predict_pose_rgb, lib.egotap_predict_pose_rgb_kp, lib.egotap_predict_pose_rgb_kpl), (B,))
+        return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
     @staticmethod
     def _served(pose, hm, kp, lb=None, tr=None):
@@ -595,66 +574,114 @@ class EgoTAPAutoEncoderModel(nn.Module):
             hit = self._camera_table = (key, torch.from_numpy(_spec.rgb_u8_table(self.opt)).to(dev))
         return hit[1]
 
-    def _serve_one_call(self, left, right, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch, kind=(), keep=(), return_limbs=False,
-                        tri=None):
-        """The host side of a one-call serving entry on the serving handle: outputs, workspace (eager: the handle's grow-only one; graphed: the
-        graph's own), capture and replay with static inputs of the frames' dtype.  ``size_query(h, B, chunk, &bytes)`` and
-        ``launch(h, left, right, pose, heatmaps, keypoints, limbs, chunk, ws)`` are the entry's two ABI calls (keypoints / limbs None: the entry
-        without that output); ``kind`` extends the capture key, ``keep`` what a graph must keep alive besides its own buffers.  ``tri``
-        (``_triangulation``): the triangulation launch follows the library call on the same stream -- inside a capture too, so a graphed request stays
-        one replay -- on keypoints that exist for it alone when they were not asked for."""
-        p = self.net_AutoEncoder.preset
+    def _serve(self, src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation):
+        """One request of a serving entry, whichever ``src`` (``_Source``) it reads: through the one library call, or -- where one handle cannot express
+        the three networks (``_rgb_one_call_refusal``) -- through the module forwards, by name and ungraphed."""
+        tri = self._triangulation(src.who, return_triangulation, src.triangulation_affine)
+        why = self._rgb_one_call_refusal()
+        if why is None:
+            return self._serve_one_call(src, return_heatmaps, return_keypoints, return_limbs, graphed, tri)
+        if graphed:
+            raise _lib.EgotapError(f"{src.who}(graphed=True): {why}; this configuration runs {src.module_route}, ungraphed")
+        return self._serve_modules(src, why, return_heatmaps, return_keypoints, return_limbs, tri)
+
+    def _serve_modules(self, src, why, return_heatmaps, return_keypoints, return_limbs, tri):
+        """the module route: the source's float frames through ``forward_into`` x 2 (chunked) and ``net_AutoEncoder.predict_pose``, then the standalone
+        operators for the extra outputs"""
+        # the modules' inference forwards refuse train mode (theirs is then the differentiable path): say so before anything runs
+        for name in self.model_names:
+            if getattr(self, "net_" + name).training:
+                raise _lib.EgotapError(f"predict_pose_from_rgb: {why}; this configuration runs the module forwards, which need net_{name} in "
+                                       "eval mode (model.eval())")
+        p, B = self.net_AutoEncoder.preset, src.B
+        left, right = src.float_frames() if src.float_frames else (src.left, src.right)
+        dev = left.device
         chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
-        pose = torch.empty((B, p.out_joints, 3), dtype=torch.float32, device=dev)
-        hm = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev) if return_heatmaps else None
-        kp = torch.empty((B, 2, p.n_joints_hm, 4), dtype=torch.float32, device=dev) if return_keypoints or tri is not None else None
-        lb = torch.empty((B, 2, p.n_joints_hm, 8), dtype=torch.float32, device=dev) if return_limbs else None
+        cat = torch.empty((B, p.in_channels, p.hm_size, p.hm_size), dtype=torch.float32, device=dev)
+        J = p.n_joints_hm
+        same = self.net_HeatMap.blocks == self.net_RotHeatMap.blocks          # one scratch for both estimators where their sizes agree
+        for net, c0 in ((self.net_HeatMap, 0), (self.net_RotHeatMap, 2 * J)):
+            ws = None if net.bottleneck else (self.net_HeatMap if same else net)._workspace(chunk, dev)
+            for lo in range(0, B, chunk):
+                net.forward_into(left[lo:lo + chunk], right[lo:lo + chunk], cat[lo:lo + chunk], c0, workspace=ws)
+        pose = self.net_AutoEncoder.predict_pose(cat)
+        kp = lb = None
+        affine = src.keypoint_affine or [(4.0, 0.0, 4.0, 0.0)] * 2
+        if return_keypoints or tri is not None:
+            kp = _lib.heatmap_peaks(cat, 0, 2 * J, groups=2, affine=affine).view(B, 2, J, 4)
+        if return_limbs:
+            lb = _lib.limb_decode(cat, 2 * J, J, eyes=2, affine=affine)
         tr = None
         if tri is not None:
-            tr = (torch.empty((B, p.n_joints_hm, 8), dtype=torch.float32, device=dev), torch.empty((B, 8), dtype=torch.float32, device=dev))
-            entry_launch = launch
+            rig_l, rig_r, rig_t, rig_R, min_score = self._stereo_rig
+            tr = _lib.stereo_triangulate(kp, rig_l, rig_r, rig_t, R=rig_R, affine=tri[2], min_score=min_score, pose=pose, pose_row0=tri[3])
+        return self._served(pose, cat if return_heatmaps else None, kp if return_keypoints else None, lb, tr)
 
-            def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
-                entry_launch(h, l, r, po, hmo, kp, lb, chunk, ws)
-                _lib.stereo_triangulate_into(tri[0], kp, po, tri[3], tr[0], tr[1], dev)
+    @staticmethod
+    def _launch(src, h, left, right, out, chunk, ws, dev, tri):
+        """the source's ABI entry on ``out`` = (pose, heatmaps, keypoints, limbs, triangulation records), picked by the outputs present -- limbs: _kpl; no
+        keypoints: the base entry; otherwise _kp -- and, with ``tri``, the triangulation launch behind it on the same stream"""
+        pose, hm, kp, lb, tr = out
+        fn, extra = (src.entries[2], (ptr(kp), ptr(lb))) if lb is not None else (src.entries[0], ()) if kp is None else (src.entries[1], (ptr(kp),))
+        _lib.check(fn(h, ptr(left), ptr(right), *src.args, ptr(pose), ptr(hm), chunk, ptr(ws), ws.numel(), stream(dev), *extra))
+        if tri is not None:
+            _lib.stereo_triangulate_into(tri[0], kp, pose, tri[3], tr[0], tr[1], dev)
 
-        def served(pose, hm, kp, lb):
+    def _serve_one_call(self, src, return_heatmaps, return_keypoints, return_limbs, graphed, tri):
+        """The host side of a one-call serving entry on the serving handle: outputs, workspace (eager: the handle's grow-only one; graphed: the
+        graph's own), capture and replay with static inputs of the frames' dtype.  ``src.size_query(h, B, chunk, &bytes)`` and ``_launch`` are the
+        entry's two ABI calls; ``src.kind`` extends the capture key, ``src.keep`` is what a graph must keep alive besides its own buffers.  ``tri``
+        (``_triangulation``): the triangulation launch follows the library call on the same stream -- inside a capture too, so a graphed request stays
+        one replay -- on keypoints that exist for it alone when they were not asked for."""
+        p, B, left, right = self.net_AutoEncoder.preset, src.B, src.left, src.right
+        dev = left.device
+        chunk = max(1, min(B, int(getattr(self.opt, "hm_chunk", 256))))
+
+        def f32(*shape):
+            return torch.empty((B,) + shape, dtype=torch.float32, device=dev)
+        out = (f32(p.out_joints, 3),
+               f32(p.in_channels, p.hm_size, p.hm_size) if return_heatmaps else None,
+               f32(2, p.n_joints_hm, 4) if return_keypoints or tri is not None else None,
+               f32(2, p.n_joints_hm, 8) if return_limbs else None,
+               (f32(p.n_joints_hm, 8), f32(8)) if tri is not None else None)
+
+        def served(out):
+            pose, hm, kp, lb, tr = out
             return self._served(pose, hm, kp if return_keypoints else None, lb, tr)
         if B == 0:
-            return served(pose, hm, kp, lb)
+            return served(out)
         with torch.cuda.device(dev):
             st = self._rgb_state(dev)
             self._rgb_attach_act_scratch(st, B, dev)
             h = st.handle.h
-            need = _session.nbytes(size_query, h, B, chunk)
+            need = _session.nbytes(src.size_query, h, B, chunk)
             if not graphed:
                 _session.grown(st, "ws", need, dev, drop_first=True)
                 st.chunk = chunk
-                launch(h, left, right, pose, hm, kp, lb, chunk, st.ws)
-                return served(pose, hm, kp, lb)
+                self._launch(src, h, left, right, out, chunk, st.ws, dev, tri)
+                return served(out)
             # one graph per (batch, heatmaps wanted, keypoints wanted, limbs wanted, precision, frozen arenas, bound tensors, chunk, source): every pointer a captured
             # launch takes is baked in, so the graph owns its buffers -- static inputs and outputs, a workspace of its own -- and keeps the scratch
             # buffers and arenas alive
             nets = (self.net_AutoEncoder, self.net_HeatMap, self.net_RotHeatMap)
             key = (B, bool(return_heatmaps), bool(return_keypoints), bool(return_limbs), st.precision, tuple(st.frozen),
-                   tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)), chunk, str(dev)) + tuple(kind)
+                   tuple(st.handle.bound[i] for i in (_lib.NET_LIFT, _lib.NET_HM_POS, _lib.NET_HM_ROT)), chunk, str(dev)) + tuple(src.kind)
             if tri is not None:
                 key += (tri[1],)
 
             def build():
                 s_l, s_r = left.clone(), right.clone()
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
-                held = (ws, st.wscratch, st.ascratch) + tuple(keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
-                return (lambda: launch(h, s_l, s_r, pose, hm, kp, lb, chunk, ws)), (s_l, s_r, pose, hm, kp, lb, tr), held
-            graph, (s_l, s_r, pose, hm, kp, lb, tr), _ = _session.captured(st.graphs, key, build)
+                held = (ws, st.wscratch, st.ascratch) + tuple(src.keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
+                return (lambda: self._launch(src, h, s_l, s_r, out, chunk, ws, dev, tri)), (s_l, s_r, out), held
+            graph, (s_l, s_r, out), _ = _session.captured(st.graphs, key, build)
             s_l.copy_(left)
             s_r.copy_(right)
             graph.replay()
-        return served(pose, hm, kp, lb)
+        return served(out)
 
     @torch.no_grad()
-    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, _keypoint_affine=None, return_limbs=False,
-                                 return_triangulation=False, _triangulation_affine=None):
+    def predict_pose_from_camera(self, left8, right8, return_heatmaps=False, graphed=False, return_keypoints=False, return_limbs=False, return_triangulation=False):
         """predict_pose_from_rgb from what a camera delivers: stereo frames uint8 [B, 4S, 4S, 3] (HWC, RGB order, already at 4S x 4S) -> pose
         [B, J(+1), 3], or (pose, heatmaps) with ``return_heatmaps``.  ONE library call (egotap_predict_pose_rgb_u8) on the serving handle of
         predict_pose_from_rgb: the caller's astype(float32) / 255, normalisation, HWC -> CHW and the four-fold upload are gone -- at sides 64 / 128
@@ -668,28 +695,12 @@ class EgoTAPAutoEncoderModel(nn.Module):
         egotap_rgb_u8_to_f32 followed by predict_pose_from_rgb's module route -- by name, ungraphed."""
         S0 = 4 * self.net_AutoEncoder.preset.hm_size
         B = _lib.check_camera_frames("predict_pose_from_camera", left8, right8, S0)
-        dev = left8.device
-        table = self.camera_table(dev)
-        tri = self._triangulation("predict_pose_from_camera", return_triangulation, _triangulation_affine)
-        why = self._rgb_one_call_refusal()
-        if why is not None:
-            if graphed:
-                raise _lib.EgotapError(f"predict_pose_from_camera(graphed=True): {why}; this configuration runs the converter and the module forwards, ungraphed")
-            left, right = _lib.rgb_u8_to_f32(left8, right8, table)
-            return self.predict_pose_from_rgb(left, right, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=_keypoint_affine,
-                                              return_limbs=return_limbs, return_triangulation=return_triangulation, _triangulation_affine=_triangulation_affine)
-        lib = _lib.load()
-
-        def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
-            if lb is not None:
-                _lib.check(lib.egotap_predict_pose_rgb_u8_kpl(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp),
-                                                              ptr(lb)))
-            elif kp is None:
-                _lib.check(lib.egotap_predict_pose_rgb_u8(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev)))
-            else:
-                _lib.check(lib.egotap_predict_pose_rgb_u8_kp(h, ptr(l), ptr(r), B, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(), stream(dev), ptr(kp)))
-        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, lib.egotap_predict_pose_rgb_u8_workspace_bytes, launch,
-                                    kind=("u8", table.data_ptr()), keep=(table,), return_limbs=return_limbs, tri=tri)
+        lib, table = _lib.load(), self.camera_table(left8.device)
+        src = _Source("predict_pose_from_camera", left8, right8, B, lib.egotap_predict_pose_rgb_u8_workspace_bytes,
+                      (lib.egotap_predict_pose_rgb_u8, lib.egotap_predict_pose_rgb_u8_kp, lib.egotap_predict_pose_rgb_u8_kpl), (B, ptr(table)),
+                      kind=("u8", table.data_ptr()), keep=(table,), float_frames=lambda: _lib.rgb_u8_to_f32(left8, right8, table),
+                      module_route="the converter and the module forwards")
+        return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
     @torch.no_grad()
     def predict_pose_from_sensor(self, left8, right8, crop=None, crop_right=None, mirror_right=False, return_heatmaps=False, graphed=False,
@@ -721,36 +732,18 @@ class EgoTAPAutoEncoderModel(nn.Module):
         rect_l = _spec.check_resize_rect("predict_pose_from_sensor", crop, H, W)
         rect_r = _spec.check_resize_rect("predict_pose_from_sensor", crop if crop_right is None else crop_right, H, W)
         mirrors = (0, int(bool(mirror_right)))
-        dev = left8.device
-        tri = self._triangulation("predict_pose_from_sensor", return_triangulation, _spec.STEREO_IDENTITY_AFFINE)
-        why = self._rgb_one_call_refusal()
-        if why is not None:
-            if graphed:
-                raise _lib.EgotapError(f"predict_pose_from_sensor(graphed=True): {why}; this configuration runs the resize, the converter and the module forwards, ungraphed")
-            l8, r8 = _lib.rgb_u8_resize(left8, right8, S0, rect_l, rect_r, False, bool(mirror_right))
-            affine = [_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)]
-            return self.predict_pose_from_camera(l8, r8, return_heatmaps=return_heatmaps, return_keypoints=return_keypoints, _keypoint_affine=affine,
-                                                 return_limbs=return_limbs, return_triangulation=return_triangulation,
-                                                 _triangulation_affine=_spec.STEREO_IDENTITY_AFFINE)
-        table = self.camera_table(dev)
-        lib = _lib.load()
-        rects, flags = (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors)
+        lib, table = _lib.load(), self.camera_table(left8.device)
 
-        def size_query(h, b, chunk, out):
-            return lib.egotap_predict_pose_sensor_u8_workspace_bytes(h, b, H, W, chunk, out)
-
-        def launch(h, l, r, po, hmo, kp, lb, chunk, ws):
-            if lb is not None:
-                _lib.check(lib.egotap_predict_pose_sensor_u8_kpl(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
-                                                                 stream(dev), ptr(kp), ptr(lb)))
-            elif kp is None:
-                _lib.check(lib.egotap_predict_pose_sensor_u8(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
-                                                             stream(dev)))
-            else:
-                _lib.check(lib.egotap_predict_pose_sensor_u8_kp(h, ptr(l), ptr(r), B, H, W, rects, flags, ptr(table), ptr(po), ptr(hmo), chunk, ptr(ws), ws.numel(),
-                                                                stream(dev), ptr(kp)))
-        return self._serve_one_call(left8, right8, B, dev, return_heatmaps, return_keypoints, graphed, size_query, launch,
-                                    kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), return_limbs=return_limbs, tri=tri)
+        def float_frames():
+            return _lib.rgb_u8_to_f32(*_lib.rgb_u8_resize(left8, right8, S0, rect_l, rect_r, False, bool(mirror_right)), table)
+        src = _Source("predict_pose_from_sensor", left8, right8, B,
+                      lambda h, b, chunk, out: lib.egotap_predict_pose_sensor_u8_workspace_bytes(h, b, H, W, chunk, out),
+                      (lib.egotap_predict_pose_sensor_u8, lib.egotap_predict_pose_sensor_u8_kp, lib.egotap_predict_pose_sensor_u8_kpl),
+                      (B, H, W, (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors), ptr(table)),
+                      kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), float_frames=float_frames,
+                      keypoint_affine=[_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)],
+                      triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the resize, the converter and the module forwards")
+        return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
     def new_pose_tracker(self, streams=1, params=None):
         """A ``PoseTracker`` for this model's outputs: P = the lifted pose's rows, J = the heatmap joints the triangulation returns; ``streams`` camera

@@ -84,3 +84,45 @@ def conv_kernels_of(h, fn):
         return [(d["kernel"], d["launches"]) for d in json.loads(lib.egotap_timing_detail(h).decode())]
     finally:
         L.check(lib.egotap_timing_enable(h, 0))
+
+
+def serving_model(preset="UnrealEgo", hm=64):
+    """test-mode wrapper with the hash-RNG weights in all three networks (built and uploaded once per (preset, hm), shared by every serving test file);
+    every fetch resets it: f32, unfrozen, eval mode, opt.hm_chunk = 256.  Returns (model, lift preset)."""
+    from egotap_amd import models
+    from egotap_amd.synthetic import synth_hm_state_dict
+    key = ("serving", preset, hm)
+    if key not in _cache:
+        opt = make_opt(preset, hm)
+        opt.model, opt.isTrain, opt.use_amp, opt.gpu_ids, opt.use_gt_heatmap = "egotap_autoencoder", False, False, [0], False
+        m = models.create_model(opt)
+        p = spec.lift_preset(preset, hm)
+        J = p.n_joints_hm
+        m.net_AutoEncoder.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(spec.lift_state_spec(p)).items()})
+        m.net_HeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(J, "hm_pos.").items()})
+        m.net_RotHeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(2 * J, "hm_rot.").items()})
+        m.eval()
+        _cache[key] = (m, p)
+    m, p = _cache[key]
+    m.set_precision("f32")
+    m.unfreeze_weights()
+    m.eval()
+    m.opt.hm_chunk = 256
+    return m, p
+
+
+def timed_launches(m, fn):
+    """(role, kernel, launches) of the timed launches `fn` makes on the serving handle of `m` (egotap_debug.h egotap_timing_*)"""
+    import ctypes as C
+    import json
+    from egotap_amd import lib as L
+    lib, h = L.load(), m._rgb["handle"].h
+    L.check(lib.egotap_timing_enable(h, 1))
+    try:
+        fn()
+        torch.cuda.synchronize()
+        n, ms, fl = C.c_int(), C.c_double(), C.c_double()
+        L.check(lib.egotap_timing_read(h, C.byref(n), C.byref(ms), C.byref(fl)))
+        return [(d["role"], d["kernel"], d["launches"]) for d in json.loads(lib.egotap_timing_detail(h).decode())]
+    finally:
+        L.check(lib.egotap_timing_enable(h, 0))

@@ -6,19 +6,15 @@ paths read the same values and keep every summation order, so EVERY comparison h
 
 Frames are random bytes in which 0 and 255 both occur; the outermost two rows and columns of every image are byte 0 in some cases and byte 255 in
 others, so a halo filled with table[c][0] (about -2.1) instead of 0.0, or a clamped edge, fails."""
-import ctypes as C
-import json
 
 import pytest
 import torch
 
 from egotap_amd import lib as L
 from egotap_amd import spec
-from egotap_amd.synthetic import synth_hm_state_dict, synth_state_dict
-from gpu_util import hm_net
+from gpu_util import hm_net, serving_model as _model, timed_launches as _launches
 
 pytestmark = pytest.mark.gpu
-_models = {}
 
 
 def _table():
@@ -91,30 +87,6 @@ def test_forward_from_camera_equals_the_eval_forward_on_the_gather(which, model_
 
 
 # ------------------------------------------------------------------------------------------------------------ 3. one call
-def _model(preset="UnrealEgo", hm=64):
-    """test-mode wrapper with the hash-RNG weights in all three networks, eval mode (cached)"""
-    from egotap_amd import models
-    from egotap_amd.options import preset_defaults
-    key = (preset, hm)
-    if key not in _models:
-        opt = preset_defaults(preset, hm)
-        opt.model, opt.isTrain, opt.use_amp, opt.gpu_ids, opt.use_gt_heatmap = "egotap_autoencoder", False, False, [0], False
-        m = models.create_model(opt)
-        p = spec.lift_preset(preset, hm)
-        J = p.n_joints_hm
-        m.net_AutoEncoder.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(spec.lift_state_spec(p)).items()})
-        m.net_HeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(J, "hm_pos.").items()})
-        m.net_RotHeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(2 * J, "hm_rot.").items()})
-        m.eval()
-        _models[key] = (m, p)
-    m, p = _models[key]
-    m.set_precision("f32")
-    m.unfreeze_weights()
-    m.eval()
-    m.opt.hm_chunk = 256
-    return m, p
-
-
 @pytest.mark.parametrize("mode", ["f32", "bf16"])
 def test_predict_pose_from_camera_equals_the_float_entry_on_the_gather(mode):
     m, p = _model()
@@ -209,20 +181,6 @@ def test_second_call_creates_and_binds_nothing(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------ 4. the float path is untouched
-def _launches(m, fn):
-    """(role, kernel, launches) of the timed launches `fn` makes on the serving handle (egotap_debug.h egotap_timing_*)"""
-    lib, h = L.load(), m._rgb["handle"].h
-    L.check(lib.egotap_timing_enable(h, 1))
-    try:
-        fn()
-        torch.cuda.synchronize()
-        n, ms, fl = C.c_int(), C.c_double(), C.c_double()
-        L.check(lib.egotap_timing_read(h, C.byref(n), C.byref(ms), C.byref(fl)))
-        return [(d["role"], d["kernel"], d["launches"]) for d in json.loads(lib.egotap_timing_detail(h).decode())]
-    finally:
-        L.check(lib.egotap_timing_enable(h, 0))
-
-
 @pytest.mark.parametrize("mode,hm", [("f32", 64), ("bf16", 64), ("f32", 32)])
 def test_float_entry_launches_what_it_launched(mode, hm):
     """the byte call's timed launches are the float call's plus the byte-source stem (sides 64 / 128, one per estimator forward) or the converter

@@ -7,17 +7,15 @@ torch.equal.  The expected value of the one call is predict_pose_from_camera on 
 Frames are random bytes in which 0 and 255 both occur, with a two-pixel border of byte 0 in some cases and 255 in others, so a clamped or wrapped
 edge fails; the operator writes into a canary-filled buffer whose bytes around the outputs must stay untouched."""
 import ctypes as C
-import json
 
 import pytest
 import torch
 
 from egotap_amd import lib as L
 from egotap_amd import spec
-from egotap_amd.synthetic import synth_hm_state_dict, synth_state_dict
+from gpu_util import serving_model as _model, timed_launches as _launches
 
 pytestmark = pytest.mark.gpu
-_models = {}
 
 
 def _frames8(seed, B, H, W, edge):
@@ -85,30 +83,6 @@ def test_operator_copies_exactly_when_the_rectangle_has_the_output_size():
 
 
 # ------------------------------------------------------------------------------------------------------------ 2. one call
-def _model(preset="UnrealEgo", hm=64):
-    """test-mode wrapper with the hash-RNG weights in all three networks, eval mode (cached)"""
-    from egotap_amd import models
-    from egotap_amd.options import preset_defaults
-    key = (preset, hm)
-    if key not in _models:
-        opt = preset_defaults(preset, hm)
-        opt.model, opt.isTrain, opt.use_amp, opt.gpu_ids, opt.use_gt_heatmap = "egotap_autoencoder", False, False, [0], False
-        m = models.create_model(opt)
-        p = spec.lift_preset(preset, hm)
-        J = p.n_joints_hm
-        m.net_AutoEncoder.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(spec.lift_state_spec(p)).items()})
-        m.net_HeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(J, "hm_pos.").items()})
-        m.net_RotHeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(2 * J, "hm_rot.").items()})
-        m.eval()
-        _models[key] = (m, p)
-    m, p = _models[key]
-    m.set_precision("f32")
-    m.unfreeze_weights()
-    m.eval()
-    m.opt.hm_chunk = 256
-    return m, p
-
-
 CROP, CROP_R = (8, 0, 112, 96), (0, 2, 110, 94)          # of 96 x 120 sensor frames
 
 
@@ -197,20 +171,6 @@ def test_graphed_replays_with_fresh_bytes_on_a_graph_of_its_own():
 
 
 # ------------------------------------------------------------------------------------------------------------ 4. the timing hook
-def _launches(m, fn):
-    """(role, kernel, launches) of the timed launches `fn` makes on the serving handle (egotap_debug.h egotap_timing_*)"""
-    lib, h = L.load(), m._rgb["handle"].h
-    L.check(lib.egotap_timing_enable(h, 1))
-    try:
-        fn()
-        torch.cuda.synchronize()
-        n, ms, fl = C.c_int(), C.c_double(), C.c_double()
-        L.check(lib.egotap_timing_read(h, C.byref(n), C.byref(ms), C.byref(fl)))
-        return [(d["role"], d["kernel"], d["launches"]) for d in json.loads(lib.egotap_timing_detail(h).decode())]
-    finally:
-        L.check(lib.egotap_timing_enable(h, 0))
-
-
 @pytest.mark.parametrize("hm,B,chunk,pieces", [(64, 5, 2, 3), (32, 2, 256, 1)])
 def test_one_resize_launch_per_piece_and_none_in_the_existing_entries(hm, B, chunk, pieces):
     m, p = _model("UnrealEgo", hm)

@@ -18,10 +18,9 @@ import torch
 import ocam_inputs as I
 from egotap_amd import lib as L
 from egotap_amd import spec
-from egotap_amd.synthetic import synth_hm_state_dict, synth_state_dict
+from gpu_util import serving_model as _model
 
 pytestmark = pytest.mark.gpu
-_models = {}
 CANARY = -12345.0
 
 
@@ -169,30 +168,6 @@ def test_triangulate_nothing_valid_and_the_largest_frame():
 
 
 # ------------------------------------------------------------------------------------------------------------ 3. serving
-def _model(preset="UnrealEgo", hm=64):
-    """test-mode wrapper with the hash-RNG weights in all three networks, eval mode (cached)"""
-    from egotap_amd import models
-    from egotap_amd.options import preset_defaults
-    key = (preset, hm)
-    if key not in _models:
-        opt = preset_defaults(preset, hm)
-        opt.model, opt.isTrain, opt.use_amp, opt.gpu_ids, opt.use_gt_heatmap = "egotap_autoencoder", False, False, [0], False
-        m = models.create_model(opt)
-        p = spec.lift_preset(preset, hm)
-        J = p.n_joints_hm
-        m.net_AutoEncoder.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(spec.lift_state_spec(p)).items()})
-        m.net_HeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(J, "hm_pos.").items()})
-        m.net_RotHeatMap.load_state_dict({k: torch.from_numpy(v) for k, v in synth_hm_state_dict(2 * J, "hm_rot.").items()})
-        m.eval()
-        _models[key] = (m, p)
-    m, p = _models[key]
-    m.set_precision("f32")
-    m.unfreeze_weights()
-    m.eval()
-    m.opt.hm_chunk = 256
-    return m, p
-
-
 B = 2
 CROP, CROP_R = (8, 0, 112, 96), (0, 2, 110, 94)                     # of 96 x 120 sensor frames
 MIN_SCORE = -1e30                                                   # the synthetic estimators' peaks are no probabilities: every joint is "seen"
