@@ -2899,6 +2899,47 @@ extern "C" int egotap_debug_attention_f32_shared(const float* qkv, float* ctx, i
 }
 #endif
 
+// (test hook) the exact-fp32 attention as lift_forward launches it: with the caller's scratch for the key-split partials, the split count being
+// attention_f32_ksplit's own decision for scratch_floats and num_cu (egotap_debug_attention_f32_ksplit tells which)
+#if EGOTAP_IN(0)
+extern "C" int egotap_debug_attention_f32_split(const float* qkv, float* ctx, int B, int N, int heads, float* scratch, size_t scratch_floats, int num_cu, void* stream) {
+    EGO_CHECK(qkv && ctx && scratch, "egotap_debug_attention_f32_split: null argument");
+    EGO_CHECK(B >= 0 && N >= 32 && N % 4 == 0 && heads > 0, "egotap_debug_attention_f32_split: bad shape B=%d N=%d heads=%d (N at least 32 and a multiple of 4)", B, N, heads);
+    EGO_CHECK(num_cu > 0, "egotap_debug_attention_f32_split: num_cu=%d must be positive", num_cu);
+    EGO_HIP(attention_f32_launch(qkv, ctx, B, N, heads, (hipStream_t)stream, nullptr, scratch, scratch_floats, num_cu));
+    return EGOTAP_OK;
+}
+#endif
+
+// (test hook) the live-query attention of the pose-only forward's last layer: Nq compact query rows per image (row b * Nq + q of q, stride ldq)
+// against the K / V columns of all N tokens of qkv; ctx [B * Nq, heads * 128]
+#if EGOTAP_IN(0)
+extern "C" int egotap_debug_attention_f32_live(const float* q, int64_t ldq, int Nq, const float* qkv, float* ctx, int B, int N, int heads, void* stream) {
+    EGO_CHECK(q && qkv && ctx, "egotap_debug_attention_f32_live: null argument");
+    EGO_CHECK(B >= 0 && N >= 32 && N % 4 == 0 && heads > 0, "egotap_debug_attention_f32_live: bad shape B=%d N=%d heads=%d (N at least 32 and a multiple of 4)", B, N, heads);
+    EGO_CHECK(Nq >= 32 && Nq <= N, "egotap_debug_attention_f32_live: Nq=%d must lie in [32, N=%d]", Nq, N);
+    EGO_CHECK(ldq >= (int64_t)heads * 128 && ldq % 4 == 0, "egotap_debug_attention_f32_live: ldq=%lld must be a multiple of 4 and at least heads * 128", (long long)ldq);
+    EGO_HIP(attention_f32_live_launch(q, (long)ldq, Nq, qkv, ctx, B, N, heads, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+#endif
+
+// (test aid, host only: no device call) the key-split count attention_f32_launch picks for a forward with scratch_floats of scratch on num_cu
+// compute units: 1 = unsplit.  0 (never a split count) with egotap_last_error set where the arguments are refused
+#if EGOTAP_IN(0)
+extern "C" int egotap_debug_attention_f32_ksplit(int B, int N, int heads, size_t scratch_floats, int num_cu) {
+    if (!(B > 0 && N >= 32 && N % 4 == 0 && heads > 0)) {
+        egotap_set_error("egotap_debug_attention_f32_ksplit: bad shape B=%d N=%d heads=%d (N at least 32 and a multiple of 4)", B, N, heads);
+        return 0;
+    }
+    if (num_cu <= 0) {
+        egotap_set_error("egotap_debug_attention_f32_ksplit: num_cu=%d must be positive", num_cu);
+        return 0;
+    }
+    return attention_f32_ksplit(B, N, heads, scratch_floats, num_cu);
+}
+#endif
+
 // per-sample MPJPE / PA-MPJPE of a batch of poses (egotap_autoencoder_model.py:329-350, utils/util.py:328-379)
 #if EGOTAP_IN(0)
 extern "C" int egotap_pose_metrics(const float* pred, const float* gt, int B, int J, float* mpjpe, float* pa_mpjpe, float* aligned,

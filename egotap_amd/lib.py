@@ -121,6 +121,9 @@ _PROTOS = {
     "egotap_layernorm_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "egotap_attention_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "egotap_debug_attention_f32_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "egotap_debug_attention_f32_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "egotap_debug_attention_f32_live": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "egotap_debug_attention_f32_ksplit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int]),
     "egotap_pose_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_pose_metrics_batch_axes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_attention": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -675,10 +678,51 @@ def attention_f32_shared(qkv, B: int, N: int, heads: int, shared_from: int):
     return ctx
 
 
-def attention(qkv, B: int, N: int, heads: int, precision: str = "f32"):
-    """qkv [B*N, 3*heads*128] (q|k|v) -> ctx [B*N, heads*128]"""
+def _attention_out(out, rows: int, heads: int, dev):
+    """the ctx buffer of an attention wrapper: a fresh [rows, heads*128], or the caller's ``out`` (at least that many rows; the tests put sentinel
+    rows behind them)"""
     import torch
+    if out is None:
+        return torch.empty((rows, heads * 128), device=dev, dtype=torch.float32)
+    _need_cuda_f32(out)
+    if out.dim() != 2 or out.shape[0] < rows or out.shape[1] != heads * 128 or out.device != dev:
+        raise ValueError(f"out: a float32 tensor [>= {rows}, {heads * 128}] on {dev}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def attention_f32_ksplit(B: int, N: int, heads: int, scratch_floats: int, num_cu: int = 256) -> int:
+    """(test aid, host only) the key-split count the fp32 attention of a forward picks: 1 = unsplit"""
+    k = load().egotap_debug_attention_f32_ksplit(B, N, heads, scratch_floats, num_cu)
+    if k <= 0:
+        check(1)
+    return k
+
+
+def attention_f32_split(qkv, B: int, N: int, heads: int, scratch, scratch_floats: int, num_cu: int = 256, out=None):
+    """(test hook, egotap_debug.h) the exact-fp32 attention as the forward launches it, key-split partials in the first ``scratch_floats`` floats
+    of ``scratch``; the split count is ``attention_f32_ksplit`` of the same arguments.  qkv [B*N, 3*heads*128] -> ctx [B*N, heads*128]"""
+    _need_cuda_f32(qkv, scratch)
+    if scratch.numel() < scratch_floats:
+        raise ValueError(f"scratch holds {scratch.numel()} floats, scratch_floats = {scratch_floats}")
+    ctx = _attention_out(out, B * N, heads, qkv.device)
+    check(load().egotap_debug_attention_f32_split(_ptr(qkv), _ptr(ctx), B, N, heads, _ptr(scratch), scratch_floats, num_cu, _stream()))
+    return ctx
+
+
+def attention_f32_live(q, ldq: int, Nq: int, qkv, B: int, N: int, heads: int, out=None):
+    """(test hook, egotap_debug.h) Nq live queries per image -- row b*Nq + i of ``q``, row stride ``ldq`` floats (``q`` may be ``qkv`` itself with
+    ldq = 3*heads*128: the product's layout) -- against the keys and values of all N tokens of qkv [B*N, 3*heads*128] -> ctx [B*Nq, heads*128]"""
+    _need_cuda_f32(q, qkv)
+    if q.numel() < (B * Nq - 1) * ldq + heads * 128:
+        raise ValueError(f"q holds {q.numel()} floats: fewer than {B * Nq} rows of stride {ldq}")
+    ctx = _attention_out(out, B * Nq, heads, qkv.device)
+    check(load().egotap_debug_attention_f32_live(_ptr(q), ldq, Nq, _ptr(qkv), _ptr(ctx), B, N, heads, _stream()))
+    return ctx
+
+
+def attention(qkv, B: int, N: int, heads: int, precision: str = "f32", out=None):
+    """qkv [B*N, 3*heads*128] (q|k|v) -> ctx [B*N, heads*128] (``out``: the caller's buffer of at least that many rows)"""
     _need_cuda_f32(qkv)
-    ctx = torch.empty((B * N, heads * 128), device=qkv.device, dtype=torch.float32)
+    ctx = _attention_out(out, B * N, heads, qkv.device)
     check(load().egotap_attention(_ptr(qkv), _ptr(ctx), B, N, heads, PRECISIONS[precision], _stream()))
     return ctx

@@ -99,9 +99,16 @@ def bn_lrelu_bwd(z, y, dy, gamma, mean, rstd, dgamma, dbeta, accumulate=False):
     return dz
 
 
-def attention_fwd(qkv, B, N, heads, precision="f32"):
-    ctx = torch.empty((B * N, heads * 128), dtype=torch.float32, device=qkv.device)
-    lse = torch.empty((B * heads * N,), dtype=torch.float32, device=qkv.device)
+def attention_fwd(qkv, B, N, heads, precision="f32", out=None):
+    """out: the caller's (ctx [>= B*N, heads*128], lse [>= B*heads*N]) float32 buffers instead of fresh ones (the tests put sentinels behind them)"""
+    if out is None:
+        ctx = torch.empty((B * N, heads * 128), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((B * heads * N,), dtype=torch.float32, device=qkv.device)
+    else:
+        ctx, lse = out
+        for t, n in ((ctx, B * N * heads * 128), (lse, B * heads * N)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n):
+                raise ValueError(f"attention_fwd: out = contiguous float32 GPU buffers of at least {B * N * heads * 128} and {B * heads * N} floats")
     _lib.check(_lib.load().egotap_train_attention_fwd(_p(qkv), _p(ctx), _p(lse), B, N, heads, _lib.PRECISIONS[precision], _s()))
     return ctx, lse
 

@@ -28,6 +28,19 @@ int egotap_lift_debug_stop(egotap_handle h, int stage);
  * image.  shared_from = N shares nothing (any N egotap_attention_f32 takes); below N both must be multiples of 32. */
 int egotap_debug_attention_f32_shared(const float* qkv, float* ctx, int B, int N, int heads, int shared_from, void* stream);
 
+/* ---- the exact-fp32 attention's other modes, one operator call each (tests/test_gpu_attention_f32_modes.py) ---- */
+/* as egotap_lift_forward launches it: scratch (scratch_floats floats, caller-owned) takes the key-split partials [k][B * N][heads * 128] followed by
+ * their log-sum-exps [k][B * heads * N]; the split count k is the library's own decision for (B, N, heads, scratch_floats, num_cu) -- 1 = unsplit,
+ * scratch untouched -- and is what egotap_debug_attention_f32_ksplit returns for the same arguments. */
+int egotap_debug_attention_f32_split(const float* qkv, float* ctx, int B, int N, int heads, float* scratch, size_t scratch_floats, int num_cu, void* stream);
+/* the last ViT layer of egotap_lift_predict_pose: Nq live queries per image (32 <= Nq <= N), row b * Nq + i of q with a row stride of ldq floats (a
+ * multiple of 4; q == qkv, ldq = 3 * heads * 128 is the product's layout), against the K / V columns of all N tokens of qkv; ctx [B * Nq, heads * 128]. */
+int egotap_debug_attention_f32_live(const float* q, int64_t ldq, int Nq, const float* qkv, float* ctx, int B, int N, int heads, void* stream);
+/* (host only: no device call) the key-split count of a forward: a divisor of the number of 32-key tiles, at most 8, that keeps B * heads * query
+ * groups * k within 4.5 workgroups per compute unit and the partials within scratch_floats; 1 = unsplit.  Returns 0 -- never a split count -- with
+ * egotap_last_error set when the arguments are refused (the return value is the count, so the usual error codes cannot be told from it). */
+int egotap_debug_attention_f32_ksplit(int B, int N, int heads, size_t scratch_floats, int num_cu);
+
 /* ---- measurement / test switch (process wide, one definition in the library): which K-tile depth the bf16-storage NT GEMM with plain
  * operands uses: 0 (default) = 64-deep kernel (csrc/gemm_bf16s64.h) where the shape allows, else the 32-deep one (csrc/gemm_bf16s.h);
  * 32 / 64 = always that one (64 fails on shapes it does not take).  Both run the same MFMAs in the same k order: bit-identical results. */

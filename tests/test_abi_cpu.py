@@ -224,6 +224,32 @@ def test_host_side_argument_checks_of_the_newer_entry_points():
         # attention: any sequence that is a multiple of 4 from 32 on is a shape the fp32 kernel takes (null pointers are still refused first)
         assert lib.egotap_attention_f32(None, None, 1, 144, 8, None) == 1 and b"null" in lib.egotap_last_error()
         assert lib.egotap_attention_f32(C.c_void_p(256), C.c_void_p(256), 1, 30, 8, None) == 1 and b"at least 32" in lib.egotap_last_error()
+        # the test hooks of its key-split and live-query modes refuse by name before any launch; the host-only planner hook returns the split
+        # count itself, so its refusal is 0 (never a count) with the message set
+        p = C.c_void_p(256)
+        split, live, ksplit = lib.egotap_debug_attention_f32_split, lib.egotap_debug_attention_f32_live, lib.egotap_debug_attention_f32_ksplit
+        assert split(None, p, 1, 64, 1, p, 1 << 20, 256, None) == 1 and b"_split: null" in lib.egotap_last_error()
+        assert split(p, None, 1, 64, 1, p, 1 << 20, 256, None) == 1 and b"_split: null" in lib.egotap_last_error()
+        assert split(p, p, 1, 64, 1, None, 1 << 20, 256, None) == 1 and b"_split: null" in lib.egotap_last_error()
+        assert split(p, p, 1, 28, 1, p, 1 << 20, 256, None) == 1 and b"at least 32" in lib.egotap_last_error()
+        assert split(p, p, 1, 66, 1, p, 1 << 20, 256, None) == 1 and b"multiple of 4" in lib.egotap_last_error()
+        assert split(p, p, 1, 64, 0, p, 1 << 20, 256, None) == 1 and b"heads=0" in lib.egotap_last_error()
+        assert split(p, p, 1, 64, 1, p, 1 << 20, 0, None) == 1 and b"num_cu=0" in lib.egotap_last_error()
+        assert live(None, 128, 32, p, p, 1, 64, 1, None) == 1 and b"_live: null" in lib.egotap_last_error()
+        assert live(p, 128, 32, None, p, 1, 64, 1, None) == 1 and b"_live: null" in lib.egotap_last_error()
+        assert live(p, 128, 32, p, None, 1, 64, 1, None) == 1 and b"_live: null" in lib.egotap_last_error()
+        assert live(p, 128, 32, p, p, 1, 28, 1, None) == 1 and b"at least 32" in lib.egotap_last_error()
+        assert live(p, 128, 32, p, p, 1, 66, 1, None) == 1 and b"multiple of 4" in lib.egotap_last_error()
+        assert live(p, 128, 32, p, p, 1, 64, 0, None) == 1 and b"heads=0" in lib.egotap_last_error()
+        assert live(p, 128, 28, p, p, 1, 64, 1, None) == 1 and b"Nq=28" in lib.egotap_last_error()
+        assert live(p, 128, 68, p, p, 1, 64, 1, None) == 1 and b"Nq=68" in lib.egotap_last_error()
+        assert live(p, 130, 32, p, p, 1, 64, 1, None) == 1 and b"ldq=130" in lib.egotap_last_error()
+        assert ksplit(1, 28, 8, 1 << 24, 256) == 0 and b"_ksplit: bad shape" in lib.egotap_last_error()
+        assert ksplit(1, 66, 8, 1 << 24, 256) == 0 and b"multiple of 4" in lib.egotap_last_error()
+        assert ksplit(1, 64, 0, 1 << 24, 256) == 0 and b"heads=0" in lib.egotap_last_error()
+        assert ksplit(0, 64, 8, 1 << 24, 256) == 0 and b"B=0" in lib.egotap_last_error()
+        assert ksplit(1, 64, 8, 1 << 24, 0) == 0 and b"num_cu=0" in lib.egotap_last_error()
+        assert ksplit(1, 576, 8, 1 << 24, 256) == 6
         L.check(lib.egotap_set_precision(h, 0))
         # [r5] the measurement switch of the convolution operands' addressing (host state only): 0 / 1, anything else refused by name
         assert lib.egotap_debug_conv_addressing(2) == 1 and b"mode must be 0" in lib.egotap_last_error()
