@@ -38,6 +38,7 @@
 #include "bn_bf16s.h"
 #include "rgb_u8.h"
 #include "rgb_u8_resize.h"
+#include "yuv_u8_resize.h"
 #include "heatmap_peaks.h"
 #include "limb_decode.h"
 #include "ocam.h"
@@ -1513,10 +1514,13 @@ static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, in
 // converted into `scratch` (2 x B x 3 x S0^2 floats, the caller's workspace slice) first and the forward proceeds on them as ever.
 // [r8] the sensor's own frames behind a byte source (egotap_predict_pose_sensor_u8 only): uint8 [B, H, W, 3] per eye, a source rectangle and a mirror
 // flag per eye; each piece is resized into `slice` (chunk x 2 x 3 S0^2 bytes of the caller's workspace) and read there as camera bytes
+// `yuv` (egotap_predict_pose_sensor_yuv only): the frames are NV12 / YUYV of that layout and colour, frame_stride bytes each; the piece is converted
+// and resized into the same slice by yuv_u8_resize_kernel
 struct HmSensor {
     const unsigned char *left8, *right8;
     int H, W, rect[2][4], mirror[2];
     unsigned char* slice;
+    const YuvSource* yuv = nullptr;
 };
 struct HmSrc {
     const float *left, *right;
@@ -2268,15 +2272,21 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
         // byte-source stems at sides 64 / 128 and go through the converter into its slice elsewhere (never with the hand-off: that exists at sides
         // 64 / 128 only).
         unsigned char* s8l = sensor.slice;
-        const long frame = 3L * sensor.H * sensor.W;
+        const long frame = sensor.yuv ? sensor.yuv->frame_stride : 3L * sensor.H * sensor.W;
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
             HmSrc piece = whole.at(lo, rgb);
             if (resize) {
                 unsigned char* s8r = s8l + (size_t)n * rgb;
-                GemmTimer t(h, (hipStream_t)stream, "rgb_u8_resize", "rgb_u8_resize_kernel", 0.0);
-                EGO_HIP(rgb_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, sensor.H, sensor.W, sensor.rect[0], sensor.rect[1],
-                                             sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
+                if (sensor.yuv) {
+                    GemmTimer t(h, (hipStream_t)stream, "yuv_u8_resize", "yuv_u8_resize_kernel", 0.0);
+                    EGO_HIP(yuv_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, *sensor.yuv, sensor.rect[0], sensor.rect[1],
+                                                 sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
+                } else {
+                    GemmTimer t(h, (hipStream_t)stream, "rgb_u8_resize", "rgb_u8_resize_kernel", 0.0);
+                    EGO_HIP(rgb_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, sensor.H, sensor.W, sensor.rect[0], sensor.rect[1],
+                                                 sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
+                }
                 piece = HmSrc{nullptr, nullptr, s8l, s8r, src.table, nullptr};
             }
             if (!stems) {
@@ -2434,6 +2444,17 @@ extern "C" int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, in
     *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_SENSOR).total;
     return EGOTAP_OK;
 }
+// heatmap pixels -> pixels of the eye's sensor frame: the inverse of the map the resize kernels apply (pixel centres at i + 0.5, align_corners = False); a
+// mirrored eye's output column X shows source column S0 - 1 - X, so its x runs backwards from the rectangle's right edge
+static void sensor_keypoint_affine(const Handle* h, const HmSensor& q, float* affine) {
+    for (int e = 0; e < 2; ++e) {
+        const float S = (float)h->cfg.hm_size, sx = (float)q.rect[e][2] / S;
+        affine[4 * e + 0] = q.mirror[e] ? -sx : sx;
+        affine[4 * e + 1] = (float)(q.rect[e][0] + (q.mirror[e] ? q.rect[e][2] : 0));
+        affine[4 * e + 2] = (float)q.rect[e][3] / S;
+        affine[4 * e + 3] = (float)q.rect[e][1];
+    }
+}
 static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
                                         const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
                                         bool kp, float* keypoints, float* limbs) {
@@ -2450,16 +2471,8 @@ static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const 
     for (int e = 0; e < 2; ++e) identity = identity && q.rect[e][0] == 0 && q.rect[e][1] == 0 && q.rect[e][2] == S0 && q.rect[e][3] == S0;
     HmSrc src{nullptr, nullptr, identity ? left8 : nullptr, identity ? right8 : nullptr, table, nullptr};
     src.sensor = &q;
-    // heatmap pixels -> pixels of the eye's sensor frame: the inverse of the map rgb_u8_resize_kernel applies (pixel centres at i + 0.5, align_corners =
-    // False); a mirrored eye's output column X shows source column S0 - 1 - X, so its x runs backwards from the rectangle's right edge
     float affine[8];
-    for (int e = 0; e < 2; ++e) {
-        const float S = (float)h->cfg.hm_size, sx = (float)q.rect[e][2] / S;
-        affine[4 * e + 0] = q.mirror[e] ? -sx : sx;
-        affine[4 * e + 1] = (float)(q.rect[e][0] + (q.mirror[e] ? q.rect[e][2] : 0));
-        affine[4 * e + 2] = (float)q.rect[e][3] / S;
-        affine[4 * e + 3] = (float)q.rect[e][1];
-    }
+    sensor_keypoint_affine(h, q, affine);
     return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
 }
 extern "C" int egotap_predict_pose_sensor_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
@@ -2478,6 +2491,79 @@ extern "C" int egotap_predict_pose_sensor_u8_kpl(egotap_handle h, const uint8_t*
                                                  void* stream, float* keypoints, float* limbs) {
     return predict_pose_sensor_u8_entry("egotap_predict_pose_sensor_u8_kpl", h, left8, right8, B, H, W, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes,
                                         stream, false, keypoints, limbs);
+}
+
+// ---- NV12 / YUYV sensor frames: the colour conversion inside the resize (yuv_u8_resize.h), standalone and in front of the one call
+// what is wrong with a descriptor or the frames behind it, or nullptr; fills `q` (layout and integer coefficients) when nothing is
+static const char* yuv_source_refusal(const egotap_yuv_source* src, const void* left8, const void* right8, YuvSource* q) {
+    if (!src) return "null source descriptor (egotap_yuv_source)";
+    if (src->struct_size != (int32_t)sizeof(egotap_yuv_source)) return "wrong struct_size (sizeof(egotap_yuv_source) expected)";
+    if (const char* why = yuv_layout_refusal(src->format, src->H, src->W, src->pitch, (long)src->uv_offset, (long)src->frame_stride)) return why;
+    if (src->matrix != EGOTAP_YUV_BT601 && src->matrix != EGOTAP_YUV_BT709) return "unknown matrix (EGOTAP_YUV_BT601 or EGOTAP_YUV_BT709)";
+    if (src->range != EGOTAP_YUV_LIMITED && src->range != EGOTAP_YUV_FULL) return "unknown range (EGOTAP_YUV_LIMITED or EGOTAP_YUV_FULL)";
+    if (!left8 || !right8) return "null frames (left8 and right8 are required)";
+    if ((((uintptr_t)left8 | (uintptr_t)right8) & (uintptr_t)(yuv_base_alignment(src->format) - 1)) != 0)
+        return src->format == YUV_NV12 ? "left8 and right8 must be 2-byte aligned (NV12: the chroma pair is one aligned 16-bit load)"
+                                       : "left8 and right8 must be 4-byte aligned (YUYV: the pixel pair is one aligned dword)";
+    *q = YuvSource{src->format, src->H, src->W, src->pitch, src->format == YUV_NV12 ? (long)src->uv_offset : 0L, (long)src->frame_stride,
+                   yuv_coefficients(src->matrix, src->range)};
+    return nullptr;
+}
+static const char* yuv_rects_refusal(const YuvSource& q, const int* rect_left, const int* rect_right) {
+    if (const char* why = rgb_u8_resize_rect_refusal(rect_left, q.H, q.W)) return why;
+    return rgb_u8_resize_rect_refusal(rect_right, q.H, q.W);
+}
+extern "C" int egotap_yuv_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rect_left, const int* rect_right,
+                                    int mirror_left, int mirror_right, int S0, uint8_t* out_left8, uint8_t* out_right8, void* stream) {
+    static const char* const who = "egotap_yuv_u8_resize";
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
+    YuvSource q{};
+    const char* why = yuv_source_refusal(src, left8, right8, &q);
+    if (!why) why = !(rect_left && rect_right) ? "null rectangle (rect_left and rect_right are four ints each: x0, y0, w, h)" : yuv_rects_refusal(q, rect_left, rect_right);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
+    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
+    EGO_HIP(yuv_u8_resize_launch(left8, right8, B, q, rect_left, rect_right, mirror_left, mirror_right, S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+// the sensor entry with the descriptor in place of H, W: the same checks in the same order, the same affine, the same walk
+static int predict_pose_sensor_yuv_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* ysrc,
+                                         const int* rects, const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws,
+                                         size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
+    YuvSource yuv{};
+    const char* why = !(rects && mirrors) ? "null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)"
+                                          : yuv_source_refusal(ysrc, left8, right8, &yuv);
+    if (!why) why = yuv_rects_refusal(yuv, rects, rects + 4);
+    if (!why && !table) why = "null table (the fp32 [3][256] value table is required)";
+    if (!why && ((uintptr_t)table & 15) != 0) why = "the table must be 16-byte aligned";
+    const int rc = rgb_entry_checks(who, h, B, why, nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
+    if (rc != EGOTAP_OK) return rc;
+    HmSensor q{left8, right8, yuv.H, yuv.W, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}},
+               {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0}, nullptr, &yuv};
+    HmSrc src{nullptr, nullptr, nullptr, nullptr, table, nullptr};      // never the identity request: a YUV source always converts
+    src.sensor = &q;
+    float affine[8];
+    sensor_keypoint_affine(h, q, affine);
+    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
+}
+extern "C" int egotap_predict_pose_sensor_yuv(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
+                                              const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
+                                              void* stream) {
+    return predict_pose_sensor_yuv_entry("egotap_predict_pose_sensor_yuv", h, left8, right8, B, src, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes, stream,
+                                         false, nullptr, nullptr);
+}
+extern "C" int egotap_predict_pose_sensor_yuv_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
+                                                 const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
+                                                 void* stream, float* keypoints) {
+    return predict_pose_sensor_yuv_entry("egotap_predict_pose_sensor_yuv_kp", h, left8, right8, B, src, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes,
+                                         stream, true, keypoints, nullptr);
+}
+extern "C" int egotap_predict_pose_sensor_yuv_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
+                                                  const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
+                                                  void* stream, float* keypoints, float* limbs) {
+    return predict_pose_sensor_yuv_entry("egotap_predict_pose_sensor_yuv_kpl", h, left8, right8, B, src, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes,
+                                         stream, false, keypoints, limbs);
 }
 
 // the standalone operator: maps c0 .. c0 + n - 1 of each image of a [B, C, S, S] tensor -> [B, n, 4] records; no handle

@@ -31,6 +31,10 @@ class EgotapTrackParams(C.Structure):                 # egotap.h egotap_track_pa
         (n, C.c_double) for n in ("max_disagree", "max_gap", "max_joint_gap")] + [("min_joints", C.c_int32), ("max_hold", C.c_int32)]
 
 
+class EgotapYuvSource(C.Structure):                   # egotap.h egotap_yuv_source: seven int32 (then padding) and two int64
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "format", "matrix", "range", "H", "W", "pitch")] + [("uv_offset", C.c_int64), ("frame_stride", C.c_int64)]
+
+
 class EgotapError(RuntimeError):
     pass
 
@@ -80,6 +84,15 @@ _PROTOS = {
                                                  C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_predict_pose_sensor_u8_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- NV12 / YUYV sensor frames: the descriptor in place of H, W
+    "egotap_yuv_u8_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapYuvSource), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_sensor_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapYuvSource), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_predict_pose_sensor_yuv_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapYuvSource), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_sensor_yuv_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapYuvSource), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # ---- the fisheye camera model and the stereo triangulation of the keypoints: three operators, no handle
     "egotap_ocam_project": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
     "egotap_ocam_unproject": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
@@ -388,6 +401,55 @@ def rgb_u8_resize(left8, right8, S0, rect_left=None, rect_right=None, mirror_lef
     with torch.cuda.device(left8.device):
         check(load().egotap_rgb_u8_resize(_ptr(left8), _ptr(right8), B, H, W, rl, rr, int(bool(mirror_left)), int(bool(mirror_right)), int(S0), _ptr(out_l),
                                           _ptr(out_r), _stream(left8.device)))
+    return out_l, out_r
+
+
+def yuv_source(layout, colour):
+    """the egotap_yuv_source of a ``spec.YuvLayout`` and a ``spec.YuvColour``"""
+    from . import spec as _spec
+    return EgotapYuvSource(C.sizeof(EgotapYuvSource), _spec.YUV_FORMATS[layout.format], _spec.YUV_MATRICES[colour.matrix][0], _spec.YUV_RANGES[colour.range],
+                           layout.H, layout.W, layout.pitch, layout.uv_offset, layout.frame_stride)
+
+
+def check_yuv_frames(who, left8, right8, layout):
+    """the one wording of what the YUV entries take: two contiguous uint8 tensors on one GPU, B frames of ``layout.frame_stride`` bytes each (any shape
+    whose first axis is B), frame 0 at a multiple of the format's load width (2 bytes for nv12, 4 for yuyv); returns B"""
+    import torch
+    for t in (left8, right8):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the frames to cuda")
+    for t in (left8, right8):
+        if t.dtype != torch.uint8:
+            raise EgotapError(f"{who} takes the sensor's bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
+    fs = layout.frame_stride
+    B = int(left8.shape[0]) if left8.dim() else -1
+    if B < 0 or left8.numel() != B * fs or tuple(right8.shape) != tuple(left8.shape):
+        raise ValueError(f"{who}: expected left8 / right8 of one shape, B {layout.format} frames of frame_stride = {fs} bytes each ([B, {fs}]), got "
+                         f"{tuple(left8.shape)} / {tuple(right8.shape)}")
+    if not (left8.is_contiguous() and right8.is_contiguous()) or left8.device != right8.device:
+        raise EgotapError(f"{who}: the frames must be contiguous and on one device (the bytes are read in place, nothing is copied)")
+    a = layout.base_alignment
+    if B > 0 and (left8.data_ptr() % a or right8.data_ptr() % a):
+        raise EgotapError(f"{who}: {layout.format} frames must start at a multiple of {a} bytes (the widest load of the format)")
+    return B
+
+
+def yuv_u8_resize(left8, right8, layout, colour, S0, rect_left=None, rect_right=None, mirror_left=False, mirror_right=False):
+    """NV12 / YUYV sensor frames (``check_yuv_frames``) x 2 -> camera bytes uint8 [B, S0, S0, 3] x 2 (egotap_yuv_u8_resize): per eye the source
+    rectangle (x0, y0, w, h) in pixels (None: the full frame), mirrored or not, each tap converted to RGB bytes with ``colour`` and resampled
+    bilinearly -- equal to spec.yuv_resize_u8 bit for bit.  One launch for both eyes."""
+    import torch
+    from . import spec as _spec
+    B = check_yuv_frames("yuv_u8_resize", left8, right8, layout)
+    rl = (C.c_int * 4)(*_spec.check_resize_rect("yuv_u8_resize", rect_left, layout.H, layout.W))
+    rr = (C.c_int * 4)(*_spec.check_resize_rect("yuv_u8_resize", rect_right, layout.H, layout.W))
+    out_l = torch.empty((B, S0, S0, 3), dtype=torch.uint8, device=left8.device)
+    out_r = torch.empty_like(out_l)
+    if B == 0:
+        return out_l, out_r
+    with torch.cuda.device(left8.device):
+        check(load().egotap_yuv_u8_resize(_ptr(left8), _ptr(right8), B, C.byref(yuv_source(layout, colour)), rl, rr, int(bool(mirror_left)),
+                                          int(bool(mirror_right)), int(S0), _ptr(out_l), _ptr(out_r), _stream(left8.device)))
     return out_l, out_r
 
 

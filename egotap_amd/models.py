@@ -96,7 +96,7 @@ class PoseTracker:
 
 
 class _Source(NamedTuple):
-    """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor); everything else about a request is ``_serve``'s."""
+    """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor / _sensor_yuv); everything else about a request is ``_serve``'s."""
     who: str                          # the entry's name, for messages
     left: torch.Tensor                # the frames as the ABI entry reads them (a graph's static inputs are clones of these) ...
     right: torch.Tensor
@@ -743,6 +743,45 @@ class EgoTAPAutoEncoderModel(nn.Module):
                       kind=("sensor", H, W, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), float_frames=float_frames,
                       keypoint_affine=[_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)],
                       triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the resize, the converter and the module forwards")
+        return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
+
+    @torch.no_grad()
+    def predict_pose_from_sensor_yuv(self, left8, right8, layout, colour=_spec.YuvColour("bt601", "limited"), crop=None, crop_right=None, mirror_right=False,
+                                     return_heatmaps=False, graphed=False, return_keypoints=False, return_limbs=False, return_triangulation=False):
+        """predict_pose_from_sensor from the camera's own buffer: stereo NV12 or YUYV frames, uint8, B frames of ``layout.frame_stride`` bytes per eye
+        (``spec.YuvLayout``: format, H, W, row pitch, chroma offset; ``lib.check_yuv_frames``) -> pose [B, J(+1), 3].  ONE library call
+        (egotap_predict_pose_sensor_yuv) on the serving handle: the caller's plane unpacking, float colour conversion, rounding and the three-bytes-per-pixel
+        upload are gone -- the library converts and resizes chunk by chunk into the sensor entry's workspace slice (yuv_u8_resize_kernel) and the byte
+        source reads that slice.  The bits are those of predict_pose_from_sensor on ``spec.yuv_to_rgb_u8(frames, layout, colour)``, the integer
+        restatement of the conversion (``spec.YuvColour``: matrix bt601 / bt709, range limited / full; chroma replicated, nothing interpolated in YUV).
+        A YUV source always converts: there is no in-place identity request.
+
+        ``crop``, ``crop_right``, ``mirror_right``, ``return_keypoints``, ``return_limbs``, ``return_triangulation``: as predict_pose_from_sensor, in
+        pixels of the H x W sensor frame.  ``graphed``: as predict_pose_from_sensor; the capture key holds the source kind, the layout, the colour, the
+        rectangles, the mirror flags and the table, so no graph is shared with the other entries.  Configurations one handle cannot express (Bottleneck
+        backbones, mixed backbones or precisions) run egotap_yuv_u8_resize followed by predict_pose_from_camera's fallback -- by name, ungraphed."""
+        p = self.net_AutoEncoder.preset
+        S0 = 4 * p.hm_size
+        who = "predict_pose_from_sensor_yuv"
+        if not isinstance(layout, _spec.YuvLayout) or not isinstance(colour, _spec.YuvColour):
+            raise ValueError(f"{who}: layout is a spec.YuvLayout and colour a spec.YuvColour, got {type(layout).__name__} / {type(colour).__name__}")
+        B = _lib.check_yuv_frames(who, left8, right8, layout)
+        H, W = layout.H, layout.W
+        rect_l = _spec.check_resize_rect(who, crop, H, W)
+        rect_r = _spec.check_resize_rect(who, crop if crop_right is None else crop_right, H, W)
+        mirrors = (0, int(bool(mirror_right)))
+        lib, table = _lib.load(), self.camera_table(left8.device)
+        desc = _lib.yuv_source(layout, colour)
+
+        def float_frames():
+            return _lib.rgb_u8_to_f32(*_lib.yuv_u8_resize(left8, right8, layout, colour, S0, rect_l, rect_r, False, bool(mirror_right)), table)
+        src = _Source(who, left8, right8, B,
+                      lambda h, b, chunk, out: lib.egotap_predict_pose_sensor_u8_workspace_bytes(h, b, H, W, chunk, out),
+                      (lib.egotap_predict_pose_sensor_yuv, lib.egotap_predict_pose_sensor_yuv_kp, lib.egotap_predict_pose_sensor_yuv_kpl),
+                      (B, C.byref(desc), (C.c_int * 8)(*rect_l, *rect_r), (C.c_int * 2)(*mirrors), ptr(table)),
+                      kind=("sensor_yuv", layout, colour, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), float_frames=float_frames,
+                      keypoint_affine=[_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)],
+                      triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the conversion and resize, the converter and the module forwards")
         return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
     def new_pose_tracker(self, streams=1, params=None):

@@ -338,6 +338,164 @@ def resize_u8(frames, rect, mirror: bool, S0: int):
     return out.numpy() if is_np else out
 
 
+# ---- NV12 / YUYV sensor frames -> RGB bytes -> camera bytes (egotap.h: egotap_yuv_u8_resize / egotap_predict_pose_sensor_yuv) ------------
+YUV_FORMATS = {"nv12": 0, "yuyv": 1}                 # egotap.h EGOTAP_YUV_NV12 / _YUYV
+YUV_MATRICES = {"bt601": (0, 0.299, 0.114), "bt709": (1, 0.2126, 0.0722)}      # egotap.h EGOTAP_YUV_BT601 / _BT709: (code, Kr, Kb)
+YUV_RANGES = {"limited": 0, "full": 1}               # egotap.h EGOTAP_YUV_LIMITED / _FULL
+YUV_SHIFT = 14                                       # coefficients are round(real * 2^14); every intermediate stays below 2^24 in magnitude
+YUV_MAX_SIDE = 16384                                 # H, W <= 16384, as for the resize
+
+
+@dataclass(frozen=True)
+class YuvLayout:
+    """Where the bytes of one H x W frame sit inside its ``frame_stride`` bytes (egotap.h egotap_yuv_source).
+
+    nv12: Y(y, x) at y * pitch + x; the chroma pair of pixel (y, x) at uv_offset + (y >> 1) * pitch + 2 * (x >> 1), U then V.  H and W even,
+          pitch >= W, uv_offset >= pitch * (H - 1) + W (the planes do not overlap), the last chroma byte inside frame_stride; pitch, uv_offset and
+          frame_stride even (the chroma pair is one aligned 16-bit load).
+    yuyv: the pixel pair x >> 1 of row y is the four bytes Y0 U Y1 V at y * pitch + 4 * (x >> 1).  W even, pitch >= 2 W, the last row inside
+          frame_stride; pitch and frame_stride multiples of 4 (the pair is one aligned dword); uv_offset is 0.
+    Chroma is replicated: every pixel of a 2 x 2 block (nv12) or of a pair (yuyv) takes the block's U and V.  Use the constructors ``nv12`` /
+    ``yuyv``: their defaults give the tight layout."""
+    format: str
+    H: int
+    W: int
+    pitch: int
+    uv_offset: int
+    frame_stride: int
+
+    def __post_init__(self):
+        f, H, W, pitch, uv, fs = self.format, self.H, self.W, self.pitch, self.uv_offset, self.frame_stride
+        if f not in YUV_FORMATS:
+            raise ValueError(f"YuvLayout: unknown format {f!r} (one of {sorted(YUV_FORMATS)})")
+        who = f"YuvLayout.{f}"
+        if not (1 <= H <= YUV_MAX_SIDE and 1 <= W <= YUV_MAX_SIDE):
+            raise ValueError(f"{who}: the frame height and width must be between 1 and {YUV_MAX_SIDE}, got {H} x {W}")
+        if f == "nv12":
+            if H % 2 or W % 2:
+                raise ValueError(f"{who}: H and W must be even (4:2:0 chroma covers 2 x 2 blocks), got {H} x {W}")
+            if pitch < W:
+                raise ValueError(f"{who}: pitch {pitch} is smaller than W = {W}")
+            if uv < pitch * (H - 1) + W:
+                raise ValueError(f"{who}: the planes overlap: uv_offset {uv} is smaller than pitch * (H - 1) + W = {pitch * (H - 1) + W}")
+            if uv + (H // 2 - 1) * pitch + W > fs:
+                raise ValueError(f"{who}: the last chroma byte {uv + (H // 2 - 1) * pitch + W - 1} is past frame_stride {fs}")
+            if pitch % 2 or uv % 2 or fs % 2:
+                raise ValueError(f"{who}: pitch, uv_offset and frame_stride must be even, got {pitch}, {uv}, {fs}")
+        else:
+            if W % 2:
+                raise ValueError(f"{who}: W must be even (4:2:2 chroma covers pixel pairs), got {W}")
+            if pitch < 2 * W:
+                raise ValueError(f"{who}: pitch {pitch} is smaller than 2 W = {2 * W}")
+            if uv != 0:
+                raise ValueError(f"{who}: a packed format has no chroma plane (uv_offset must be 0, got {uv})")
+            if (H - 1) * pitch + 2 * W > fs:
+                raise ValueError(f"{who}: the last byte {(H - 1) * pitch + 2 * W - 1} is past frame_stride {fs}")
+            if pitch % 4 or fs % 4:
+                raise ValueError(f"{who}: pitch and frame_stride must be multiples of 4, got {pitch}, {fs}")
+
+    @staticmethod
+    def nv12(H, W, pitch=None, uv_offset=None, frame_stride=None):
+        H, W = int(H), int(W)
+        pitch = W if pitch is None else int(pitch)
+        uv_offset = pitch * H if uv_offset is None else int(uv_offset)
+        frame_stride = uv_offset + pitch * (H // 2) if frame_stride is None else int(frame_stride)
+        return YuvLayout("nv12", H, W, pitch, uv_offset, frame_stride)
+
+    @staticmethod
+    def yuyv(H, W, pitch=None, frame_stride=None):
+        H, W = int(H), int(W)
+        pitch = 2 * W if pitch is None else int(pitch)
+        return YuvLayout("yuyv", H, W, pitch, 0, pitch * H if frame_stride is None else int(frame_stride))
+
+    @property
+    def base_alignment(self):
+        """what the address of frame 0 must be a multiple of: the widest load of the format"""
+        return 2 if self.format == "nv12" else 4
+
+
+@dataclass(frozen=True)
+class YuvColour:
+    """Which Y'CbCr a source carries: matrix bt601 (Kr, Kb = 0.299, 0.114) or bt709 (0.2126, 0.0722), range limited (Y 16 .. 235, chroma
+    16 .. 240) or full (0 .. 255).  With Kg = 1 - Kr - Kb, (cy, cc, y_off) = (255/219, 255/224, 16) limited or (1, 1, 0) full:
+
+        rv = 2 (1 - Kr) cc    bu = 2 (1 - Kb) cc    gu = 2 Kb (1 - Kb) / Kg cc    gv = 2 Kr (1 - Kr) / Kg cc
+
+    ``coefficients()`` returns the integers (CY, RV, GU, GV, BU, y_off), each coefficient round(real * 2^14)."""
+    matrix: str = "bt601"
+    range: str = "limited"
+
+    def __post_init__(self):
+        if self.matrix not in YUV_MATRICES:
+            raise ValueError(f"YuvColour: unknown matrix {self.matrix!r} (one of {sorted(YUV_MATRICES)})")
+        if self.range not in YUV_RANGES:
+            raise ValueError(f"YuvColour: unknown range {self.range!r} (one of {sorted(YUV_RANGES)})")
+
+    def real_coefficients(self):
+        """(cy, rv, gu, gv, bu, y_off) as float64"""
+        _, kr, kb = YUV_MATRICES[self.matrix]
+        kg = 1.0 - kr - kb
+        limited = self.range == "limited"
+        cy = 255.0 / 219.0 if limited else 1.0
+        cc = 255.0 / 224.0 if limited else 1.0
+        return (cy, 2.0 * (1.0 - kr) * cc, 2.0 * kb * (1.0 - kb) / kg * cc, 2.0 * kr * (1.0 - kr) / kg * cc, 2.0 * (1.0 - kb) * cc,
+                16 if limited else 0)
+
+    def coefficients(self):
+        real = self.real_coefficients()
+        return tuple(int(math.floor(v * float(1 << YUV_SHIFT) + 0.5)) for v in real[:5]) + (real[5],)
+
+
+def yuv_rgb_bytes(Y, U, V, colour: YuvColour):
+    """The colour arithmetic alone, elementwise on integer torch tensors of one shape holding bytes: returns (R, G, B) as int32 tensors in 0 .. 255.
+
+        R = clip((CY (Y - y_off) + RV (V - 128) + 2^13) >> 14, 0, 255)
+        G = clip((CY (Y - y_off) - GU (U - 128) - GV (V - 128) + 2^13) >> 14, 0, 255)
+        B = clip((CY (Y - y_off) + BU (U - 128) + 2^13) >> 14, 0, 255)
+
+    The shift is arithmetic, there is one rounding, every intermediate stays below 2^24 in magnitude.  Against the real formula every byte is within
+    0.5 + (max |Y - y_off| + the sum of max |C - 128| over the channel's chroma terms) * 2^-15: each coefficient is off by at most 2^-15."""
+    import torch
+    cy, rv, gu, gv, bu, y_off = colour.coefficients()
+    half = 1 << (YUV_SHIFT - 1)
+    c = cy * (Y.to(torch.int32) - y_off) + half
+    u, v = U.to(torch.int32) - 128, V.to(torch.int32) - 128
+    return tuple(((t) >> YUV_SHIFT).clamp_(0, 255) for t in (c + rv * v, c - gu * u - gv * v, c + bu * u))
+
+
+def yuv_to_rgb_u8(frames, layout: YuvLayout, colour: YuvColour):
+    """NV12 / YUYV frames -> RGB bytes, restated in integers on the host: ``frames`` uint8 (numpy array or torch tensor on any device) of n frames
+    of ``layout.frame_stride`` bytes each (any shape whose first axis is n) -> uint8 [n, H, W, 3] of the same kind.  Each pixel takes its own Y and
+    the U, V of its block (``YuvLayout``: replicated chroma, no interpolation) through ``yuv_rgb_bytes``.  Bytes outside the planes (row padding
+    past W or 2 W, the gap in front of the chroma plane, the tail of the frame) are never read."""
+    import numpy as np
+    import torch
+    is_np = isinstance(frames, np.ndarray)
+    x = torch.from_numpy(frames) if is_np else frames
+    n = int(x.shape[0]) if x.dim() else 0
+    fs, H, W, pitch = layout.frame_stride, layout.H, layout.W, layout.pitch
+    if x.dtype != torch.uint8 or x.dim() < 1 or x.numel() != n * fs:
+        raise ValueError(f"yuv_to_rgb_u8: frames are uint8, n frames of frame_stride = {fs} bytes each, got {x.dtype} {tuple(x.shape)}")
+    x = x.reshape(n, fs).contiguous()
+    at = x.storage_offset()
+    if layout.format == "nv12":
+        Y = torch.as_strided(x, (n, H, W), (fs, pitch, 1), at)
+        U, V = (torch.as_strided(x, (n, H // 2, W // 2), (fs, pitch, 2), at + layout.uv_offset + k).repeat_interleave(2, 1).repeat_interleave(2, 2)
+                for k in (0, 1))
+    else:
+        Y = torch.as_strided(x, (n, H, W), (fs, pitch, 2), at)
+        U, V = (torch.as_strided(x, (n, H, W // 2), (fs, pitch, 4), at + k).repeat_interleave(2, 2) for k in (1, 3))
+    out = torch.stack(yuv_rgb_bytes(Y, U, V, colour), dim=-1).to(torch.uint8)
+    return out.numpy() if is_np else out
+
+
+def yuv_resize_u8(frames, layout: YuvLayout, colour: YuvColour, rect, mirror: bool, S0: int):
+    """The whole conversion-and-resize, by definition ``resize_u8(yuv_to_rgb_u8(frames, layout, colour), rect, mirror, S0)``: each of the four taps
+    of an output pixel is converted to RGB bytes (clipped and rounded), then the bilinear formula runs on those bytes -- nothing is interpolated in
+    YUV.  This is what yuv_u8_resize_kernel computes, bit for bit."""
+    return resize_u8(yuv_to_rgb_u8(frames, layout, colour), rect, mirror, S0)
+
+
 # ---- heatmaps -> 2D joints and confidences (egotap.h: egotap_heatmap_peaks / egotap_predict_pose_*_kp) ----------------------------------
 def _fma_f32(a, x, b):
     """float32(a * x + b) with ONE rounding, for float32 arrays: the product is exact in float64, the sum is rounded to odd there (TwoSum gives its

@@ -292,6 +292,63 @@ int egotap_predict_pose_sensor_u8_kpl(egotap_handle h, const uint8_t* left8, con
                                       const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints,
                                       float* limbs);
 
+/* ---- NV12 / YUYV sensor frames: colour conversion inside the resize (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * UVC, V4L2 and ISP pipelines hand out NV12 (4:2:0: a Y plane followed by an interleaved UV plane) or YUYV (packed 4:2:2), with a row pitch that is
+ * usually wider than the image -- not uint8 RGB.  These entries read the camera's buffer itself: 1.5 or 2 bytes per pixel instead of 3, nothing is
+ * unpacked or converted by the caller.  egotap_yuv_source describes one frame (egotap_amd/spec.py YuvLayout, YuvColour):
+ *   struct_size   sizeof(egotap_yuv_source)
+ *   format        EGOTAP_YUV_NV12: Y(y, x) at y * pitch + x; the chroma pair of pixel (y, x) at uv_offset + (y >> 1) * pitch + 2 * (x >> 1), U then V.
+ *                   H and W even, pitch >= W, uv_offset >= pitch * (H - 1) + W, the last chroma byte inside frame_stride; pitch, uv_offset,
+ *                   frame_stride and the address of frame 0 even (the chroma pair is one aligned 16-bit load)
+ *                 EGOTAP_YUV_YUYV: the pixel pair x >> 1 of row y is the four bytes Y0 U Y1 V at y * pitch + 4 * (x >> 1).  W even, pitch >= 2 W, the last
+ *                   row inside frame_stride; pitch, frame_stride and the address of frame 0 multiples of 4 (the pair is one aligned dword); uv_offset
+ *                   is not read
+ *   matrix, range EGOTAP_YUV_BT601 (Kr, Kb = 0.299, 0.114) or _BT709 (0.2126, 0.0722); EGOTAP_YUV_LIMITED (Y 16 .. 235) or _FULL (0 .. 255)
+ *   H, W          1 .. 16384, the same for both eyes; frame b of an eye starts at b * frame_stride
+ * Chroma is replicated: every pixel of a 2 x 2 block (NV12) or of a pair (YUYV) takes the block's U and V.  The arithmetic is fixed in integers
+ * (spec.py yuv_to_rgb_u8 / yuv_resize_u8 restate it on the host; the results are equal bit for bit).  With Kg = 1 - Kr - Kb and (cy, cc, y_off) =
+ * (255/219, 255/224, 16) limited or (1, 1, 0) full, the real coefficients are rv = 2 (1 - Kr) cc, bu = 2 (1 - Kb) cc, gu = 2 Kb (1 - Kb) / Kg cc,
+ * gv = 2 Kr (1 - Kr) / Kg cc; each integer coefficient is round(real * 2^14), and
+ *   R = clip((CY (Y - y_off) + RV (V - 128) + 2^13) >> 14, 0, 255)
+ *   G = clip((CY (Y - y_off) - GU (U - 128) - GV (V - 128) + 2^13) >> 14, 0, 255)
+ *   B = clip((CY (Y - y_off) + BU (U - 128) + 2^13) >> 14, 0, 255)
+ * (arithmetic shift, one rounding: within 0.5 + (max |Y - y_off| + sum of max |C - 128| over the channel's chroma terms) * 2^-15 of the real formula).
+ * Each of the four taps of an output pixel is converted to these bytes and the resize's bilinear formula (above) runs on them: the result is
+ * egotap_rgb_u8_resize on the converted frame, bit for bit.  Nothing is interpolated in YUV.  No load touches a byte outside B * frame_stride or a
+ * byte of a row past pitch.
+ *
+ * egotap_yuv_u8_resize: the standalone operator; needs no handle, one launch for both eyes on the caller's stream, allocates nothing.  Rectangles,
+ *   mirrors, S0 and the outputs as egotap_rgb_u8_resize.
+ * egotap_predict_pose_sensor_yuv / _kp / _kpl: egotap_predict_pose_sensor_u8 / _kp / _kpl with the descriptor in place of H, W -- the same walk: each
+ *   piece is converted and resized ONCE into the workspace slice of chunk*2*3*S0*S0 bytes and both estimators read it as camera bytes; hand-off, frozen
+ *   arenas, the keypoint affine (from the rectangles) and the limb records are the sensor entry's.  Workspace:
+ *   egotap_predict_pose_sensor_u8_workspace_bytes(B, H, W, chunk) -- there is no query of its own.  There is no identity request: a YUV source always
+ *   converts.  The descriptor, rects and mirrors are host memory read during the call.
+ * Every refusal is EGOTAP_ERR_INVALID, by name and before any launch: a NULL descriptor or a wrong struct_size; an unknown format, matrix or range; an
+ * odd H or W where the format needs it even; a pitch that is too small; planes that overlap; a last byte past frame_stride; a pitch, uv_offset,
+ * frame_stride or frame address that is not a multiple of what the format's loads need (2 bytes for NV12, 4 for YUYV); and everything the RGB
+ * operator or the sensor entry refuses. */
+#define EGOTAP_YUV_NV12 0
+#define EGOTAP_YUV_YUYV 1
+#define EGOTAP_YUV_BT601 0
+#define EGOTAP_YUV_BT709 1
+#define EGOTAP_YUV_LIMITED 0
+#define EGOTAP_YUV_FULL 1
+typedef struct egotap_yuv_source {
+    int32_t struct_size, format, matrix, range, H, W, pitch;
+    int64_t uv_offset, frame_stride;
+} egotap_yuv_source;
+int egotap_yuv_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rect_left, const int* rect_right,
+                         int mirror_left, int mirror_right, int S0, uint8_t* out_left8, uint8_t* out_right8, void* stream);
+int egotap_predict_pose_sensor_yuv(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
+                                   const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream);
+int egotap_predict_pose_sensor_yuv_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
+                                      const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
+                                      float* keypoints);
+int egotap_predict_pose_sensor_yuv_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
+                                       const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
+                                       float* keypoints, float* limbs);
+
 /* ---- the fisheye camera model and stereo triangulation of the keypoints (additive; EGOTAP_ABI_VERSION stays 2) ----
  * The reference carries each camera as an OCamCalib model (utils/projection.py:13-144): cam2world takes a pixel to a unit ray through the polynomial
  * pol in the pixel radius, world2cam a 3D point to its pixel through the polynomial invpol in the elevation angle, both behind the affine (c, d, e) and the

@@ -9,7 +9,15 @@ synchronize, median of --reps calls per round):
        round to bytes, permute back to HWC, predict_pose_from_camera
   B    predict_pose_from_sensor(crop=..., mirror_right=True)
 The two arms do not give equal bits (A rounds a float interpolation, B is the integer arithmetic of spec.resize_u8); the largest byte difference
-between their resized frames is reported (at most 1 is expected from the bound 0.5 + 510 / 4096).  Configurations: bf16 frozen and fp32."""
+between their resized frames is reported (at most 1 is expected from the bound 0.5 + 510 / 4096).  Configurations: bf16 frozen and fp32.
+
+    python tools/time_predict_sensor.py --yuv [--batches 1,8,64,256] [--sources 1024x1024] [--reps 10] [--rounds 3] [--md OUT]
+
+The same protocol from the camera's own buffer, tight NV12 frames uint8 [B, H * W * 3 / 2] x 2 on the device (report only, nothing is gated):
+  A    colour conversion in torch on the device (planes unpacked, chroma replicated, float BT.601 limited-range matrix, round, clamp, to bytes), then
+       predict_pose_from_sensor(crop=..., mirror_right=True) on the RGB frames
+  B    predict_pose_from_sensor_yuv(layout, colour, crop=..., mirror_right=True)
+The largest byte difference between A's RGB frames and spec.yuv_to_rgb_u8 is reported (at most 1 is expected: both are within 0.52 of the real value)."""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +65,65 @@ def arms(m, rect, S0):
     return {"A": a, "B": b}
 
 
+def nv12_frames(B, H, W):
+    g = torch.Generator().manual_seed(B + H + W + 12)
+    return [torch.randint(0, 256, (B, H * W * 3 // 2), generator=g, dtype=torch.uint8).cuda() for _ in range(2)]
+
+
+def torch_nv12_to_rgb(f8, H, W, matrix, offset):
+    """arm A's conversion of tight NV12 frames: unpack, replicate the chroma, float matrix, round, clamp, to bytes -> uint8 [B, H, W, 3]"""
+    B = f8.shape[0]
+    y = f8[:, :H * W].view(B, H, W)
+    uv = f8[:, H * W:].view(B, H // 2, W // 2, 2).repeat_interleave(2, 1).repeat_interleave(2, 2)
+    yuv = torch.cat([y.unsqueeze(-1), uv], dim=-1).float() - offset
+    return (yuv @ matrix.t()).round_().clamp_(0, 255).to(torch.uint8)
+
+
+def yuv_arms(m, layout, colour, rect):
+    cy, rv, gu, gv, bu, y_off = colour.real_coefficients()
+    matrix = torch.tensor([[cy, 0.0, rv], [cy, -gu, -gv], [cy, bu, 0.0]], dtype=torch.float32, device="cuda")
+    offset = torch.tensor([float(y_off), 128.0, 128.0], dtype=torch.float32, device="cuda")
+
+    def convert(f8):
+        return torch_nv12_to_rgb(f8, layout.H, layout.W, matrix, offset)
+
+    def a(l8, r8):
+        return m.predict_pose_from_sensor(convert(l8), convert(r8), crop=rect, mirror_right=True)
+
+    def b(l8, r8):
+        return m.predict_pose_from_sensor_yuv(l8, r8, layout, colour, crop=rect, mirror_right=True)
+    return {"A": a, "B": b}, convert
+
+
+def yuv_rows(m, args):
+    colour = spec.YuvColour("bt601", "limited")
+    rows = []
+    for mode in ("bf16_frozen", "f32"):
+        for src in args.sources.split(","):
+            H, W = (int(v) for v in src.split("x"))
+            layout, rect = spec.YuvLayout.nv12(H, W), centre_crop(H, W)
+            for B in [int(b) for b in args.batches.split(",")]:
+                l8, r8 = nv12_frames(B, H, W)
+                configure(m, mode, B)
+                f, convert = yuv_arms(m, layout, colour, rect)
+                dbyte = int((spec.yuv_to_rgb_u8(r8[:1], layout, colour).to(torch.int16) - convert(r8[:1]).to(torch.int16)).abs().max())
+                pa, pb = f["A"](l8, r8).clone(), f["B"](l8, r8).clone()
+                torch.cuda.synchronize()
+                dpose = float((pa - pb).abs().max())
+                for name in f:                                           # warm-up (workspaces grown)
+                    timed(f[name], l8, r8, 3)
+                per = {name: [] for name in f}
+                for _ in range(args.rounds):
+                    for name in f:                                       # alternating: A, B, A, B, ...
+                        per[name].append(timed(f[name], l8, r8, args.reps))
+                row = {"mode": mode, "source": f"nv12 {H}x{W}", "rect": list(rect), "batch": B, "max_byte_diff_A_B": dbyte, "max_abs_pose_A_minus_B": dpose,
+                       **{name: {"rounds_ms": [round(v, 4) for v in vs], "median_ms": round(statistics.median(vs), 4),
+                                 "spread_ms": round(max(vs) - min(vs), 4)} for name, vs in per.items()}}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    return rows
+
+
 def timed(fn, l, r, reps):
     ts = []
     for _ in range(reps):
@@ -75,6 +142,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--once", action="store_true", help="one call per arm at B = 64 from 1024 x 1024, and the operator alone (for a kernel trace)")
+    ap.add_argument("--yuv", action="store_true", help="the NV12 arms: torch conversion + predict_pose_from_sensor against predict_pose_from_sensor_yuv")
     ap.add_argument("--json", default=None)
     ap.add_argument("--md", default=None, help="write the table as markdown (profiles/predict_sensor_summary.md)")
     args = ap.parse_args()
@@ -93,8 +161,9 @@ def main():
         torch.cuda.synchronize()
         print("once: done")
         return
-    rows = []
-    for mode in ("bf16_frozen", "f32"):
+    rows = yuv_rows(m, args) if args.yuv else []
+    heads = ("A: torch conversion + predict_pose_from_sensor", "B: predict_pose_from_sensor_yuv") if args.yuv else ("A: today's caller", "B: predict_pose_from_sensor")
+    for mode in () if args.yuv else ("bf16_frozen", "f32"):
         for src in args.sources.split(","):
             H, W = (int(v) for v in src.split("x"))
             rect = centre_crop(H, W)
@@ -119,7 +188,7 @@ def main():
                 rows.append(row)
                 print(json.dumps(row), flush=True)
     for path, text in ((args.json, json.dumps(rows, indent=1)),
-                       (args.md, "| mode | source | B | A: today's caller, ms (spread) | B: predict_pose_from_sensor, ms (spread) | max byte diff |\n|---|---|---|---|---|---|\n" +
+                       (args.md, f"| mode | source | B | {heads[0]}, ms (spread) | {heads[1]}, ms (spread) | max byte diff |\n|---|---|---|---|---|---|\n" +
                         "".join(f"| {r['mode']} | {r['source']} | {r['batch']} | {r['A']['median_ms']} ({r['A']['spread_ms']}) | {r['B']['median_ms']} ({r['B']['spread_ms']}) | "
                                 f"{r['max_byte_diff_A_B']} |\n" for r in rows))):
         if path:
