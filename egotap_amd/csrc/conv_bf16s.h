@@ -16,26 +16,21 @@
 // Weights are repacked per call into [Cout][tap][Cp] bf16 (the parameters stay the caller's live fp32 tensors).  Producers write
 // straight into channel slices of the next concat buffer (row stride = the concat's channel count): no concat pass.
 #pragma once
+#include "conv_taps.h"
 #include "gemm_bf16s.h"
 
 // ---------------------------------------------------------------------------------------------------- loader
 struct XConv3 {
     const __bf16* in;        // [Nimg * S * S, Cp] bf16, channels-last
     const __bf16* zero;      // 64 bytes of zeros
-    int Cp, log2S;           // the slab / tap split of a K-tile index is a multiply by 7282 >> 16 (kt / 9 exactly for kt < 7000)
+    int Cp, log2S;
     struct Row { const __bf16* p; unsigned mask; };
     __device__ __forceinline__ Row row(int m) const {
-        const int S = 1 << log2S, x = m & (S - 1), y = (m >> log2S) & (S - 1);
-        unsigned mask = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int dy = t / 3 - 1, dx = t % 3 - 1;
-            if (y + dy >= 0 && y + dy < S && x + dx >= 0 && x + dx < S) mask |= 1u << t;
-        }
+        const unsigned mask = conv3_pixel(m, log2S).mask;
         return Row{in + (long)m * Cp, mask};
     }
     __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const {      // k0 wave-uniform: the tap arithmetic is scalar
-        const int kt = k0 >> 5, slab = (kt * 7282) >> 16, tap = kt - 9 * slab;      // kt / 9 exactly for kt < 7000
+        const int kt = k0 >> 5, slab = (kt * 7282) >> 16, tap = kt - 9 * slab;      // (own lines: with Conv3Tap hipcc orders this address arithmetic differently -- a different kernel)
         const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
         const int off = ((dy << log2S) + dx) * Cp + 32 * slab;
         return ((r.mask >> tap) & 1u) ? r.p + off + ko : zero + ko;
@@ -198,19 +193,12 @@ struct XConvE {
     int C, log2So, stride, taps;
     struct Row { const __bf16* p; unsigned mask; };
     __device__ __forceinline__ Row row(int m) const {
-        const int So = 1 << log2So, xo = m & (So - 1), yo = (m >> log2So) & (So - 1), n = m >> (2 * log2So);
-        const int Si = So * stride, yi = yo * stride, xi = xo * stride;
-        unsigned mask = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int dy = t / 3 - 1, dx = t % 3 - 1;
-            if (yi + dy >= 0 && yi + dy < Si && xi + dx >= 0 && xi + dx < Si) mask |= 1u << t;
-        }
-        return Row{in + ((long)(n >> 1) * Si * Si + (long)yi * Si + xi) * (2 * C) + (n & 1) * C, mask};
+        const Conv3Px p = conv3_pixel<true>(m, log2So, stride);
+        return Row{in + ((long)(p.n >> 1) * p.S * p.S + (long)p.y * p.S + p.x) * (2 * C) + (p.n & 1) * C, p.mask};
     }
     __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const {
         if (taps == 1) return r.p + k0 + ko;                   // 1x1 (stride-2 downsample): the centre pixel, always inside
-        const int kt = k0 >> 5, slab = (kt * 7282) >> 16, tap = kt - 9 * slab;
+        const int kt = k0 >> 5, slab = (kt * 7282) >> 16, tap = kt - 9 * slab;      // (own lines: with Conv3Tap hipcc orders this address arithmetic differently -- a different kernel)
         const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
         const int Si = stride << log2So;
         const int off = (dy * Si + dx) * (2 * C) + 32 * slab;

@@ -148,6 +148,10 @@ struct egotap_handle_s {
     egotap_config cfg;
     // derived (spec.py LiftPreset)
     int J, T, grid, ppd, side, seq, C, D, H, hid, out_joints;
+    CellGrid cells() const { return CellGrid{seq, side, ppd, grid, T}; }
+    PatchCells patches() const { return PatchCells{C, cfg.hm_size, cells()}; }
+    TokenGather tokens() const { return TokenGather{T, D, seq, side, ppd, grid}; }
+    RotRows rots() const { return RotRows{C, J, cfg.hm_size * cfg.hm_size}; }      // the head's operand layouts (head_layout.h) of this preset
     std::unordered_map<std::string, int64_t> expect[EGOTAP_NET_COUNT];   // key -> numel (forward-needed keys)
     std::unordered_map<std::string, Param> bound[EGOTAP_NET_COUNT];
     bool lift_resolved = false;
@@ -898,14 +902,14 @@ static hipError_t fc1_nt(Handle* h, int which, const __bf16* src, const __bf16* 
         // [r5] tensors under 4 GB (every shipped batch): scalar origin + 32-bit lane offsets (X64TokensS / X64RotS); the pointer loaders otherwise
         const size_t tok_bytes = (size_t)(BT / h->T) * h->seq * h->D * 2;
         if (deep && g_conv_addressing == 0 && tok_bytes < ((size_t)1 << 32) - 4096)
-            return gemm_bf16s64_launch_x(X64TokensS{src, 0u, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, w, K, ep, BT, 2048, (int)K, cus, s);
-        if (deep) return gemm_bf16s64_launch_x(X64Tokens{src, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, w, K, ep, BT, 2048, (int)K, cus, s);
-        return gemm_bf16s_launch(XTokens{src, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, w, K, ep, BT, 2048, (int)K, cus, s);
+            return gemm_bf16s64_launch_x(X64TokensS{src, 0u, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
+        if (deep) return gemm_bf16s64_launch_x(X64Tokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
+        return gemm_bf16s_launch(XTokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
     }
     const size_t hm_bytes = (size_t)(BT / (2 * h->J)) * h->C * HW * 2;
-    if (deep && g_conv_addressing == 0 && hm_bytes < ((size_t)1 << 32) - 4096) return gemm_bf16s64_launch_x(X64RotS{src, 0u, h->C, h->J, HW}, w, K, ep, BT, 2048, (int)K, cus, s);
-    if (deep) return gemm_bf16s64_launch_x(X64Rot{src, h->C, h->J, HW}, w, K, ep, BT, 2048, (int)K, cus, s);
-    return gemm_bf16s_launch(XRot{src, h->C, h->J, HW}, w, K, ep, BT, 2048, (int)K, cus, s);
+    if (deep && g_conv_addressing == 0 && hm_bytes < ((size_t)1 << 32) - 4096) return gemm_bf16s64_launch_x(X64RotS{src, 0u, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
+    if (deep) return gemm_bf16s64_launch_x(X64Rot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
+    return gemm_bf16s_launch(XRot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -1113,18 +1117,18 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
         if (!hmb_ready) hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, hm, (__bf16*)HID, n8);
         if (!frozen) hipLaunchKernelGGL(prep_weight_kernel, dim3((256 + 63) / 64, (D + 63) / 64), dim3(256), 0, s, p.patch_w, h->wscratch, (__bf16*)nullptr, D, 256, (long)D);
         EGO_HIP(zero_fill(SPK, 256, s));
-        const XPatch xl{hmb0, (const __bf16*)SPK, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
-        const SEpiPatchF32 ep{p.patch_b, p.mask_tok, p.pos_emb, X, D, h->seq, h->side, h->ppd, h->grid, h->T};
+        const XPatch xl{hmb0, (const __bf16*)SPK, h->patches()};
+        const SEpiPatchF32 ep{p.patch_b, p.mask_tok, p.pos_emb, X, D, h->cells()};
         EGO_HIP(gemm_bf16s_launch(xl, frozen ? FW(fz.patch) : h->wscratch, 256L, ep, M, D, 256, device_cu_count(), s));
     } else {
-        ALoadPatch al{hm, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
+        ALoadPatch al{hm, h->patches()};
         // [r3] fp32 at a batch that fills the chip: a zero page for the dummy cells (the head of the PU chain's ZERO slice, which is cleared as a
         // whole further down and not read before) makes the loader pure address math -> the LDS-DMA kernel instead of the register-staged one
         if (h->precision == EGOTAP_PREC_F32 && (long)((M + 255) / 256) * (D / 256) >= 160 && (size_t)B * H * 4 >= 1024) {
             EGO_HIP(zero_fill(ZERO, 1024, s));
             al.zeros = ZERO;
         }
-        EpiPatch ep{p.patch_b, p.mask_tok, p.pos_emb, D, h->seq, h->side, h->ppd, h->grid, h->T};
+        EpiPatch ep{p.patch_b, p.mask_tok, p.pos_emb, D, h->cells()};
         EGO_HIP((gemm_small(h, "patch_embed", al, segmat1(p.patch_w, D, 256), ep, X, D, M, D, 256, SPK, s)));
     }
     if (h->debug_stop == 1) return EGOTAP_OK;
@@ -1166,7 +1170,7 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
             if (!frozen) prep(p.pos_fc[0].w, Wb, 2048, K1);
             const __bf16* W1 = frozen ? FW(fz.fc1p) : Wb;
             // [r3] few encoder rows (EgoCap at 128 x 128 heatmaps, B = 32: 1088 rows = 40 tiles for 256 CUs, K = 65536): split K over the chip
-            const XTokens xt{Yb, h->T, D, h->seq, h->side, h->ppd, h->grid};
+            const XTokens xt{Yb, h->tokens()};
             const int sp = gemm_bf16s_ksplit(BT, 2048, K1, cu, SPLITK_FLOATS);
             if (sp > 1) EGO_HIP(gemm_bf16s_splitk_launch(xt, W1, (long)K1, bnf(p.pos_fc[0], Z1), SPK, sp, BT, 2048, K1, cu, s));
             else EGO_HIP(fc1_nt(h, 0, Yb, W1, (long)K1, bnf(p.pos_fc[0], Z1), BT, cu, s));
@@ -1180,7 +1184,7 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
             if (!frozen) prep(p.rot_fc[0].w, Wb, 2048, 2 * HW);
             const __bf16* W1 = frozen ? FW(fz.fc1r) : Wb;
             EGO_HIP(hipGetLastError());
-            const XRot xr{hmb, h->C, J, HW};
+            const XRot xr{hmb, h->rots()};
             const int sp = gemm_bf16s_ksplit(BT, 2048, 2 * HW, cu, SPLITK_FLOATS);
             if (sp > 1) EGO_HIP(gemm_bf16s_splitk_launch(xr, W1, 2L * HW, bnf(p.rot_fc[0], Z1), SPK, sp, BT, 2048, 2 * HW, cu, s));
             else EGO_HIP(fc1_nt(h, 1, hmb, W1, 2L * HW, bnf(p.rot_fc[0], Z1), BT, cu, s));
@@ -1260,13 +1264,13 @@ static int lift_forward_impl(Handle* h, const float* hm, int B, float* pose, voi
         };
         // [r6] after the pruned last layer Y holds the compact tokens, row (b, i) = ppd^2 * D contiguous floats: the same values in the same k order
         if (prune) EGO_HIP(fc1(ALoadPlain{Y, (long)K1}));
-        else EGO_HIP(fc1(ALoadTokens{Y, h->T, D, h->seq, h->side, h->ppd, h->grid}));
+        else EGO_HIP(fc1(ALoadTokens{Y, h->tokens()}));
         EGO_HIP((fc_gemm(h, "pos_fc2", ALoadPlain{Z1, 2048}, segmat1(p.pos_fc[1].w, 512, 2048), bn(p.pos_fc[1]), Z2, 512, BT, 512, 2048, SPK, s)));
         EGO_HIP((fc_gemm(h, "pos_fc3", ALoadPlain{Z2, 512}, segmat1(p.pos_fc[2].w, hid, 512), bn(p.pos_fc[2]), POSZ, hid, BT, hid, 512, SPK, s)));
     }
     // H11-H12: rotation (cos/sin) heatmaps straight from the input tensor
     {
-        ALoadRot al{hm, h->C, J, HW};
+        ALoadRot al{hm, h->rots()};
         if (skinny_fc1 && BT <= 64)
             EGO_HIP((gemm_f32_splitk_launch<TileS>(al, segmat1(p.rot_fc[0].w, 2048, 2L * HW), bn(p.rot_fc[0]), Z1, 2048, SPK, SPLITK_FLOATS, BT, 2048, 2 * HW, s, device_cu_count())));
         else if (skinny_fc1)
@@ -3183,16 +3187,16 @@ extern "C" int egotap_train_gemm_nt(egotap_handle h, int loader, const float* x,
                   "egotap_train_gemm_nt: the %s scatter takes plain rows, M a multiple of %d, N = %d, K = %d (got loader %d, M=%d N=%d K=%d)",
                   patch ? "patch" : "rotation", rows, patch ? 256 : 2 * S * S, patch ? h->D : 2048, loader, M, N, K);
         EGO_CHECK(((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0 && lda % 4 == 0, "egotap_train_gemm_nt: dhm and x must be 16-byte aligned, lda a multiple of 4");
-        e = patch ? nt_scatter(h, x, lda, w, EpiScatterPatch{{}, y, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T}, M, N, K, s)
-                  : nt_scatter(h, x, lda, w, EpiScatterRot{{}, y, h->C, h->J, S * S}, M, N, K, s);
+        e = patch ? nt_scatter(h, x, lda, w, EpiScatterPatch{{}, y, h->patches()}, M, N, K, s)
+                  : nt_scatter(h, x, lda, w, EpiScatterRot{{}, y, h->rots()}, M, N, K, s);
         if (e == hipErrorInvalidValue) { egotap_set_error("egotap_train_gemm_nt: unsupported shape M=%d N=%d K=%d epi=%d", M, N, K, epi); return EGOTAP_ERR_INVALID; }
         EGO_HIP(e);
         return EGOTAP_OK;
     }
     switch (loader) {
         case LD_PLAIN: e = nt_epi(ALoadPlain{x, (long)lda}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
-        case LD_TOKENS: e = nt_epi(ALoadTokens{x, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
-        case LD_ROT: e = nt_epi(ALoadRot{x, h->C, h->J, S * S}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
+        case LD_TOKENS: e = nt_epi(ALoadTokens{x, h->tokens()}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
+        case LD_ROT: e = nt_epi(ALoadRot{x, h->rots()}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
         case LD_STEREO: e = nt_epi(ALoadStereo{x, Bsz, h->J, h->hid}, w, b, y, M, N, K, epi, r, z, nullptr, h, s); break;
         case LD_STEREO_GATED:
             e = nt_epi(ALoadStereoGated{ALoadStereo{x, Bsz, h->J, h->hid}, aux, h->H + 2 * h->hid, h->H}, w, b, y, M, N, K, epi, r, z, nullptr, h, s);
@@ -3211,8 +3215,8 @@ extern "C" int egotap_train_patch_fwd(egotap_handle h, const float* hm, int B, c
                                       const float* pos, float* x, void* stream) {
     EGO_CHECK(h && hm && w && b && mask_tok && pos && x, "egotap_train_patch_fwd: null argument");
     const int S = h->cfg.hm_size, D = h->D, M = B * h->seq;
-    ALoadPatch al{hm, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
-    EpiPatch ep{b, mask_tok, pos, D, h->seq, h->side, h->ppd, h->grid, h->T};
+    ALoadPatch al{hm, h->patches()};
+    EpiPatch ep{b, mask_tok, pos, D, h->cells()};
     EGO_HIP((gemm_big(h, "patch_embed", al, segmat1(w, D, 256), ep, x, D, M, D, 256, (hipStream_t)stream)));
     return EGOTAP_OK;
 }
@@ -3246,9 +3250,9 @@ extern "C" int egotap_train_gemm_tn(egotap_handle h, int loader, const float* dy
     hipError_t e;
     switch (loader) {
         case LD_PLAIN: e = tn_any(h, dy, ALoadPlain{x, K}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
-        case LD_PATCH: e = tn_any(h, dy, ALoadPatch{x, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
-        case LD_TOKENS: e = tn_any(h, dy, ALoadTokens{x, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
-        case LD_ROT: e = tn_any(h, dy, ALoadRot{x, h->C, h->J, S * S}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
+        case LD_PATCH: e = tn_any(h, dy, ALoadPatch{x, h->patches()}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
+        case LD_TOKENS: e = tn_any(h, dy, ALoadTokens{x, h->tokens()}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
+        case LD_ROT: e = tn_any(h, dy, ALoadRot{x, h->rots()}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
         case LD_STEREO: e = tn_any(h, dy, ALoadStereo{x, Bsz, h->J, h->hid}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy); break;
         case LD_STEREO_GATED:
             e = tn_any(h, dy, ALoadStereoGated{ALoadStereo{x, Bsz, h->J, h->hid}, aux, h->H + 2 * h->hid, h->H}, dw, w, ws_bytes, M, N, K, accumulate, s, ldy);
@@ -3745,7 +3749,7 @@ static __global__ __launch_bounds__(256) void patch_split_kernel(const float* __
     for (int tok = 0; tok < seq; ++tok) {
         const int pr = tok / side, pc = tok - pr * side;
         const float v = dpos[(long)tok * D + n];
-        if ((pr / ppd) * grid + pc / ppd >= T) sm += v; else sb += v;
+        if ((pr / ppd) * grid + pc / ppd >= T) sm += v; else sb += v;      // CellGrid::dummy on its own lines: through the call hipcc swaps the two selects (a different kernel)
     }
     dbias[n] = (accumulate ? dbias[n] : 0.f) + sb;
     dmask[n] = (accumulate ? dmask[n] : 0.f) + sm;
@@ -3770,7 +3774,7 @@ static __global__ __launch_bounds__(256) void tokens_scatter_kernel(const float*
     const long bt = i / D4;
     const int tok = (int)(bt % seq), b = (int)(bt / seq);
     const int pr = tok / side, pc = tok - pr * side;
-    const int cell = (pr / ppd) * grid + pc / ppd;
+    const int cell = CellGrid{seq, side, ppd, grid, T}.cell(tok);
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (cell < T) {
         const int sseg = (pr % ppd) * ppd + (pc % ppd);
@@ -4273,8 +4277,8 @@ extern "C" int egotap_bf16_patch_fwd(egotap_handle h, const void* hmb, const voi
                                      const void* zeros, float* x, int B, void* stream) {
     EGO_CHECK(h && hmb && w && bias && mask_tok && pos && zeros && x && B > 0, "egotap_bf16_patch_fwd: bad argument");
     const int S = h->cfg.hm_size, D = h->D, M = B * h->seq;
-    const XPatch xl{(const __bf16*)hmb, (const __bf16*)zeros, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T};
-    const SEpiPatchF32 ep{bias, mask_tok, pos, x, D, h->seq, h->side, h->ppd, h->grid, h->T};
+    const XPatch xl{(const __bf16*)hmb, (const __bf16*)zeros, h->patches()};
+    const SEpiPatchF32 ep{bias, mask_tok, pos, x, D, h->cells()};
     EGO_HIP(gemm_bf16s_launch(xl, (const __bf16*)w, 256L, ep, M, D, 256, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
@@ -4294,8 +4298,8 @@ extern "C" int egotap_bf16_fc1_wgrad(egotap_handle h, int which, const void* dz,
     EGO_CHECK(h && dz && src && dw && zeros && ws && (which == 0 || which == 1), "egotap_bf16_fc1_wgrad: bad argument");
     const int BT = B * h->T, S = h->cfg.hm_size, K = which == 0 ? h->ppd * h->ppd * h->D : 2 * S * S;
     hipError_t e;
-    if (which == 0) e = gemm_tn_bf16s_launch((const __bf16*)dz, 2048L, TXTokens{(const __bf16*)src, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, (const __bf16*)zeros, dw, (float*)ws, ws_bytes, BT, 2048, K, device_cu_count(), 0, (hipStream_t)stream);
-    else e = gemm_tn_bf16s_launch((const __bf16*)dz, 2048L, TXRot{(const __bf16*)src, h->C, h->J, S * S}, (const __bf16*)zeros, dw, (float*)ws, ws_bytes, BT, 2048, K, device_cu_count(), 0, (hipStream_t)stream);
+    if (which == 0) e = gemm_tn_bf16s_launch((const __bf16*)dz, 2048L, TXTokens{(const __bf16*)src, h->tokens()}, (const __bf16*)zeros, dw, (float*)ws, ws_bytes, BT, 2048, K, device_cu_count(), 0, (hipStream_t)stream);
+    else e = gemm_tn_bf16s_launch((const __bf16*)dz, 2048L, TXRot{(const __bf16*)src, h->rots()}, (const __bf16*)zeros, dw, (float*)ws, ws_bytes, BT, 2048, K, device_cu_count(), 0, (hipStream_t)stream);
     if (e == hipErrorOutOfMemory) { egotap_set_error("egotap_bf16_fc1_wgrad: workspace too small"); return EGOTAP_ERR_WORKSPACE; }
     EGO_HIP(e);
     return EGOTAP_OK;
@@ -4309,7 +4313,7 @@ extern "C" int egotap_bf16_fc1_dgrad_tokens(egotap_handle h, const void* dz, con
     const int BT = B * h->T, K1 = h->ppd * h->ppd * h->D;
     hipStream_t s = (hipStream_t)stream;
     EGO_HIP(zero_fill(dtok, (size_t)B * h->seq * h->D * 2, s));
-    EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dz, 2048L}, (const __bf16*)wt, 2048L, SEpiScatterTokens{(__bf16*)dtok, h->T, h->D, h->seq, h->side, h->ppd, h->grid}, BT, K1,
+    EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dz, 2048L}, (const __bf16*)wt, 2048L, SEpiScatterTokens{(__bf16*)dtok, h->tokens()}, BT, K1,
                                     2048, device_cu_count(), s));      // [r5] the 64-deep kernel where its shape rules hold (plain operand)
     return EGOTAP_OK;
 }
@@ -4321,7 +4325,7 @@ extern "C" int egotap_bf16_fc1_dgrad_tokens(egotap_handle h, const void* dz, con
 extern "C" int egotap_bf16_fc1_dgrad_rot(egotap_handle h, const void* dz, const void* wt, float* dhm, int B, void* stream) {
     EGO_CHECK(h && dz && wt && dhm && B > 0 && ((uintptr_t)dhm & 15) == 0, "egotap_bf16_fc1_dgrad_rot: bad argument");
     const int BT = B * h->T, S = h->cfg.hm_size;
-    EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dz, 2048L}, (const __bf16*)wt, 2048L, SEpiScatterRot{dhm, h->C, h->J, S * S}, BT, 2 * S * S, 2048,
+    EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dz, 2048L}, (const __bf16*)wt, 2048L, SEpiScatterRot{dhm, h->rots()}, BT, 2 * S * S, 2048,
                                     device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
@@ -4334,7 +4338,7 @@ extern "C" int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const vo
     EGO_CHECK(h && dx && wt && dhm && B > 0 && ((uintptr_t)dhm & 15) == 0, "egotap_bf16_patch_dgrad: bad argument");
     const int M = B * h->seq, D = h->D, S = h->cfg.hm_size;
     EGO_HIP(gemm_bf16s_plain_launch(XPlain{(const __bf16*)dx, (long)D}, (const __bf16*)wt, (long)D,
-                                    SEpiScatterPatch{dhm, h->C, S, h->seq, h->side, h->ppd, h->grid, h->T}, M, 256, D, device_cu_count(), (hipStream_t)stream));
+                                    SEpiScatterPatch{dhm, h->patches()}, M, 256, D, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
 #endif

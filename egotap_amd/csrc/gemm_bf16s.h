@@ -55,33 +55,24 @@ struct XPlain {
 // fc1 of the position encoder: row (b, i) = the ppd x ppd patch tokens of heatmap i (net_architecture.py:388-406), tokens bf16 [B*seq, D]
 struct XTokens {
     const __bf16* Y;
-    int T, D, seq, side, ppd, grid;
+    TokenGather L;
     struct Row { const __bf16* p; };
-    __device__ __forceinline__ Row row(int m) const {
-        const int b = m / T, i = m - b * T;
-        return Row{Y + ((long)b * seq + (long)(ppd * (i / grid)) * side + ppd * (i % grid)) * D};
-    }
-    __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const {      // D % 32 == 0: a K-tile stays inside one patch token
-        const int s = k0 / D, c = k0 - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        return r.p + (long)(prl * side + pcl) * D + c + ko;
-    }
+    __device__ __forceinline__ Row row(int m) const { return Row{Y + L.rowpart(m)}; }
+    // D % 32 == 0: a K-tile stays inside one patch token
+    __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const { return L.col(r.p, k0) + ko; }
 };
 // fc1 of the rotation encoder: row (b, eye*J + j) = [cos map | sin map] of limb j (net_architecture.py:690-694), hm bf16 [B, C, HW]
 struct XRot {
     const __bf16* hm;
-    int C, J, HW;
+    RotRows L;
     struct Row { const __bf16* p; };
     __device__ __forceinline__ Row row(int m) const {
-        const int T = 2 * J;
+        const int T = 2 * L.J;      // (own lines: through RotRows::rowpart hipcc associates the channel sum differently -- a different kernel)
         const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J;
-        return Row{hm + (long)(b * C + 2 * J + eye * 2 * J + j) * HW};
+        const int eye = t / L.J, j = t - eye * L.J;
+        return Row{hm + (long)(b * L.C + 2 * L.J + eye * 2 * L.J + j) * L.HW};
     }
-    __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const {      // HW % 32 == 0
-        const int cs = k0 / HW;
-        return r.p + (long)cs * J * HW + (k0 - cs * HW) + ko;
-    }
+    __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const { return L.col(r.p, k0) + ko; }      // HW % 32 == 0
 };
 
 // [r3] patch embedding (modeling_vit.py:137-153 over the tiled heatmap image, net_architecture.py:326-336): row (b, token) = the 16 x 16
@@ -90,19 +81,10 @@ struct XRot {
 struct XPatch {
     const __bf16* hm;
     const __bf16* zero;
-    int C, S, seq, side, ppd, grid, T;
+    PatchCells L;
     struct Row { const __bf16* p; };
-    __device__ __forceinline__ Row row(int m) const {
-        const int b = m / seq, tok = m - b * seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const int cell = (pr / ppd) * grid + pc / ppd;
-        if (cell >= T) return Row{nullptr};
-        return Row{hm + ((long)(b * C + cell) * S + (pr % ppd) * 16) * S + (pc % ppd) * 16};
-    }
-    __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const {
-        const int k = k0 + ko;
-        return r.p ? r.p + (k >> 4) * S + (k & 15) : zero + ko;
-    }
+    __device__ __forceinline__ Row row(int m) const { return Row{L.pixel(hm, m)}; }
+    __device__ __forceinline__ const __bf16* ptr(const Row& r, int k0, int ko) const { return r.p ? L.col(r.p, k0 + ko) : zero + ko; }
 };
 
 // ---------------------------------------------------------------------------------------------------- epilogues
@@ -193,15 +175,14 @@ struct SEpiPatchF32 {        // out f32 = (dummy cell ? mask_token : acc + bias)
     static constexpr int W = 4, STORES = 1;
     const float *bias, *mask_tok, *pos;
     float* out;
-    int D, seq, side, ppd, grid, T;
+    int D;
+    CellGrid g;
     typedef SPatch4 Col;
     typedef f32x4 Aux;
     __device__ __forceinline__ Col col(int n) const { return Col{*(const f32x4*)(bias + n), *(const f32x4*)(mask_tok + n)}; }
-    __device__ __forceinline__ Aux fetch(int m, int n) const { return *(const f32x4*)(pos + (long)(m % seq) * D + n); }
+    __device__ __forceinline__ Aux fetch(int m, int n) const { return *(const f32x4*)(pos + (long)(m % g.seq) * D + n); }
     __device__ __forceinline__ void emit(float* v, const Col& c, const Aux& pe, int m, int n) const {
-        const int tok = m % seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const bool dummy = (pr / ppd) * grid + pc / ppd >= T;
+        const bool dummy = g.dummy(m % g.seq);
         f32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = (dummy ? c.mt[i] : v[i] + c.b[i]) + pe[i];
@@ -316,17 +297,17 @@ template <> struct s_epi_colsum<SEpiGeluGradCS> { static constexpr bool value = 
 struct SEpiScatterTokens {
     static constexpr int W = 8, STORES = 1;
     __bf16* out;
-    int T, D, seq, side, ppd, grid;
+    TokenGather L;
     typedef SNoAux Col;
     typedef SNoAux Aux;
     __device__ __forceinline__ Col col(int n) const { return Col{}; }
     __device__ __forceinline__ Aux fetch(int m, int n) const { return Aux{}; }
     __device__ __forceinline__ void emit(float* v, const Col&, const Aux&, int m, int n) const {
-        const int b = m / T, i = m - b * T;
-        const int s = n / D, c = n - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        const long tok = (long)b * seq + (long)(ppd * (i / grid) + prl) * side + ppd * (i % grid) + pcl;
-        store_bf16x8(out + tok * D + c, v);
+        const int b = m / L.T, i = m - b * L.T;      // (own lines: through TokenGather hipcc orders the index arithmetic differently -- a different kernel)
+        const int s = n / L.D, c = n - s * L.D;
+        const int prl = s / L.ppd, pcl = s - prl * L.ppd;
+        const long tok = (long)b * L.seq + (long)(L.ppd * (i / L.grid) + prl) * L.side + L.ppd * (i % L.grid) + pcl;
+        store_bf16x8(out + tok * L.D + c, v);
     }
 };
 // input gradient of the lifting head w.r.t. its heatmaps, fp32 into dhm [B, C, S, S] (NCHW; SEpiHeatNCHW of conv_bf16s.h is the other fp32
@@ -335,33 +316,33 @@ struct SEpiScatterTokens {
 struct SEpiScatterPatch {
     static constexpr int W = 4, STORES = 1;
     float* hm;
-    int C, S, seq, side, ppd, grid, T;
+    PatchCells L;
     typedef SNoAux Col;
     typedef SNoAux Aux;
     __device__ __forceinline__ Col col(int n) const { return Col{}; }
     __device__ __forceinline__ Aux fetch(int m, int n) const { return Aux{}; }
     __device__ __forceinline__ void emit(float* v, const Col&, const Aux&, int m, int n) const {
-        const int b = m / seq, tok = m - b * seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const int cell = (pr / ppd) * grid + pc / ppd;
-        if (cell >= T) return;
-        *(f32x4*)(hm + ((long)(b * C + cell) * S + (pr % ppd) * 16 + (n >> 4)) * S + (pc % ppd) * 16 + (n & 15)) = f32x4{v[0], v[1], v[2], v[3]};
+        const int b = m / L.g.seq, tok = m - b * L.g.seq;      // (own lines: a null test of PatchCells::pixel's result instead of the cell test -- a different kernel)
+        const int pr = tok / L.g.side, pc = tok - pr * L.g.side;
+        const int cell = (pr / L.g.ppd) * L.g.grid + pc / L.g.ppd;
+        if (cell >= L.g.T) return;
+        *(f32x4*)(hm + ((long)(b * L.C + cell) * L.S + (pr % L.g.ppd) * 16 + (n >> 4)) * L.S + (pc % L.g.ppd) * 16 + (n & 15)) = f32x4{v[0], v[1], v[2], v[3]};
     }
 };
 template <> struct s_epi_exact<SEpiScatterPatch> { static constexpr bool value = false; };    // a wave whose rows are all dummy cells stores nothing
 struct SEpiScatterRot {
     static constexpr int W = 4, STORES = 1;
     float* hm;
-    int C, J, HW;
+    RotRows L;
     typedef SNoAux Col;
     typedef SNoAux Aux;
     __device__ __forceinline__ Col col(int n) const { return Col{}; }
     __device__ __forceinline__ Aux fetch(int m, int n) const { return Aux{}; }
     __device__ __forceinline__ void emit(float* v, const Col&, const Aux&, int m, int n) const {
-        const int T = 2 * J;
+        const int T = 2 * L.J;      // (own lines: through RotRows::rowpart hipcc associates the channel sum differently -- a different kernel)
         const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J, cs = n / HW;
-        *(f32x4*)(hm + (long)(b * C + 2 * J + eye * 2 * J + cs * J + j) * HW + (n - cs * HW)) = f32x4{v[0], v[1], v[2], v[3]};
+        const int eye = t / L.J, j = t - eye * L.J, cs = n / L.HW;
+        *(f32x4*)(hm + (long)(b * L.C + 2 * L.J + eye * 2 * L.J + cs * L.J + j) * L.HW + (n - cs * L.HW)) = f32x4{v[0], v[1], v[2], v[3]};
     }
 };
 

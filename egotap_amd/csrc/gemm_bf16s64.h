@@ -26,6 +26,7 @@
 #pragma once
 #include <type_traits>
 
+#include "conv_taps.h"
 #include "gemm_bf16s.h"
 #include "lds_dma.h"
 
@@ -59,17 +60,11 @@ struct X64Conv3 {
     int Cp, log2S;
     struct Row { const __bf16* p; unsigned mask; };
     __device__ __forceinline__ Row row(int m) const {
-        const int S = 1 << log2S, x = m & (S - 1), y = (m >> log2S) & (S - 1);
-        unsigned mask = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int dy = t / 3 - 1, dx = t % 3 - 1;
-            if (y + dy >= 0 && y + dy < S && x + dx >= 0 && x + dx < S) mask |= 1u << t;
-        }
+        const unsigned mask = conv3_pixel(m, log2S).mask;
         return Row{in + (long)m * Cp, mask};
     }
     __device__ __forceinline__ const __bf16* ptr(const Row& r, int kt, int chunk) const {
-        const int slab = (kt * 7282) >> 16, tap = kt - 9 * slab;                     // kt / 9 exactly for kt < 7000
+        const int slab = (kt * 7282) >> 16, tap = kt - 9 * slab;      // (own lines: with Conv3Tap hipcc orders this address arithmetic differently -- a different kernel)
         const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
         const int off = ((dy << log2S) + dx) * Cp + 64 * slab;
         return ((r.mask >> tap) & 1u) ? r.p + off + chunk * 8 : zero + chunk * 8;
@@ -86,18 +81,11 @@ struct X64ConvE {
     int C, log2So, stride;
     struct Row { const __bf16* p; unsigned mask; };
     __device__ __forceinline__ Row row(int m) const {
-        const int So = 1 << log2So, xo = m & (So - 1), yo = (m >> log2So) & (So - 1), n = m >> (2 * log2So);
-        const int Si = So * stride, yi = yo * stride, xi = xo * stride;
-        unsigned mask = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int dy = t / 3 - 1, dx = t % 3 - 1;
-            if (yi + dy >= 0 && yi + dy < Si && xi + dx >= 0 && xi + dx < Si) mask |= 1u << t;
-        }
-        return Row{in + (((long)(n >> 1) * Si * Si + (long)yi * Si + xi) * 2 + (n & 1)) * C, mask};
+        const Conv3Px p = conv3_pixel<true>(m, log2So, stride);
+        return Row{in + (((long)(p.n >> 1) * p.S * p.S + (long)p.y * p.S + p.x) * 2 + (p.n & 1)) * C, p.mask};
     }
     __device__ __forceinline__ const __bf16* ptr(const Row& r, int kt, int chunk) const {
-        const int slab = (kt * 7282) >> 16, tap = kt - 9 * slab;                     // kt / 9 exactly for kt < 7000
+        const int slab = (kt * 7282) >> 16, tap = kt - 9 * slab;      // (own lines: with Conv3Tap hipcc orders this address arithmetic differently -- a different kernel)
         const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
         const int off = (dy * (stride << log2So) + dx) * (2 * C) + 64 * slab;
         return ((r.mask >> tap) & 1u) ? r.p + off + chunk * 8 : zero + chunk * 8;
@@ -117,20 +105,13 @@ struct X64Conv3S {
     int Cp, log2S;
     struct Row { unsigned off; unsigned mask; };
     __device__ __forceinline__ Row row(int m) const {
-        const int S = 1 << log2S, x = m & (S - 1), y = (m >> log2S) & (S - 1);
-        unsigned mask = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int dy = t / 3 - 1, dx = t % 3 - 1;
-            if (y + dy >= 0 && y + dy < S && x + dx >= 0 && x + dx < S) mask |= 1u << t;
-        }
+        const unsigned mask = conv3_pixel(m, log2S).mask;
         return Row{in_off + (unsigned)m * (unsigned)(Cp * 2), mask};
     }
     __device__ __forceinline__ void ktile(int kt, int& koff, int& tap) const {
-        const int slab = (kt * 7282) >> 16;
-        tap = kt - 9 * slab;
-        const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
-        koff = (((dy << log2S) + dx) * Cp + 64 * slab) * 2;
+        const Conv3Tap t(kt);
+        tap = t.tap;
+        koff = (t.pixels(1 << log2S) * Cp + 64 * t.slab) * 2;
     }
 };
 struct X64ConvES {
@@ -140,7 +121,7 @@ struct X64ConvES {
     int C, log2So, stride;
     struct Row { unsigned off; unsigned mask; };
     __device__ __forceinline__ Row row(int m) const {
-        const int So = 1 << log2So, xo = m & (So - 1), yo = (m >> log2So) & (So - 1), n = m >> (2 * log2So);
+        const int So = 1 << log2So, xo = m & (So - 1), yo = (m >> log2So) & (So - 1), n = m >> (2 * log2So);      // (own lines: conv3_pixel -> a different kernel)
         const int Si = So * stride, yi = yo * stride, xi = xo * stride;
         unsigned mask = 0;
 #pragma unroll
@@ -151,10 +132,9 @@ struct X64ConvES {
         return Row{in_off + (((unsigned)(n >> 1) * (unsigned)(Si * Si) + (unsigned)(yi * Si + xi)) * 2u + (unsigned)(n & 1)) * (unsigned)(C * 2), mask};
     }
     __device__ __forceinline__ void ktile(int kt, int& koff, int& tap) const {
-        const int slab = (kt * 7282) >> 16;
-        tap = kt - 9 * slab;
-        const int dy = ((tap * 11) >> 5) - 1, dx = tap - 3 * (dy + 1) - 1;
-        koff = ((dy * (stride << log2So) + dx) * (2 * C) + 64 * slab) * 2;
+        const Conv3Tap t(kt);
+        tap = t.tap;
+        koff = (t.pixels(stride << log2So) * (2 * C) + 64 * t.slab) * 2;
     }
 };
 // [r5] the fc1 gathers in the same form: a row's byte offset from the tensor + a wave-uniform offset per K-tile (every lane valid: mask 1, tap 0)
@@ -162,16 +142,11 @@ struct X64TokensS {
     static constexpr bool SBASE = false, SORG = true;
     const __bf16* org;               // = Y
     unsigned zero_off;               // unused (no lane is ever invalid)
-    int T, D, seq, side, ppd, grid;
+    TokenGather L;
     struct Row { unsigned off; unsigned mask; };
-    __device__ __forceinline__ Row row(int m) const {
-        const int b = m / T, i = m - b * T;
-        return Row{(unsigned)(((long)b * seq + (long)(ppd * (i / grid)) * side + ppd * (i % grid)) * D * 2), 1u};
-    }
+    __device__ __forceinline__ Row row(int m) const { return Row{(unsigned)(L.rowpart(m) * 2), 1u}; }
     __device__ __forceinline__ void ktile(int kt, int& koff, int& tap) const {
-        const int k0 = kt * 64, s = k0 / D, c = k0 - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        koff = ((prl * side + pcl) * D + c) * 2;
+        koff = L.kpart<int>(kt * 64) * 2;
         tap = 0;
     }
 };
@@ -179,17 +154,11 @@ struct X64RotS {
     static constexpr bool SBASE = false, SORG = true;
     const __bf16* org;               // = hm
     unsigned zero_off;
-    int C, J, HW;
+    RotRows L;
     struct Row { unsigned off; unsigned mask; };
-    __device__ __forceinline__ Row row(int m) const {
-        const int T = 2 * J;
-        const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J;
-        return Row{(unsigned)((long)(b * C + 2 * J + eye * 2 * J + j) * HW * 2), 1u};
-    }
+    __device__ __forceinline__ Row row(int m) const { return Row{(unsigned)(L.rowpart(m) * 2), 1u}; }
     __device__ __forceinline__ void ktile(int kt, int& koff, int& tap) const {
-        const int k0 = kt * 64, cs = k0 / HW;
-        koff = (cs * J * HW + (k0 - cs * HW)) * 2;
+        koff = L.kpart<int>(kt * 64) * 2;
         tap = 0;
     }
 };
@@ -201,33 +170,23 @@ template <class XL> struct s64_sorg<XL, std::enable_if_t<XL::SORG>> { static con
 struct X64Tokens {
     static constexpr bool SBASE = false;
     const __bf16* Y;
-    int T, D, seq, side, ppd, grid;
+    TokenGather L;
     struct Row { const __bf16* p; };
-    __device__ __forceinline__ Row row(int m) const {
-        const int b = m / T, i = m - b * T;
-        return Row{Y + ((long)b * seq + (long)(ppd * (i / grid)) * side + ppd * (i % grid)) * D};
-    }
-    __device__ __forceinline__ const __bf16* ptr(const Row& r, int kt, int chunk) const {       // kt wave-uniform: scalar arithmetic
-        const int k0 = kt * 64, s = k0 / D, c = k0 - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        return r.p + (long)(prl * side + pcl) * D + c + chunk * 8;
-    }
+    __device__ __forceinline__ Row row(int m) const { return Row{Y + L.rowpart(m)}; }
+    __device__ __forceinline__ const __bf16* ptr(const Row& r, int kt, int chunk) const { return L.col(r.p, kt * 64) + chunk * 8; }       // kt wave-uniform: scalar arithmetic
 };
 struct X64Rot {
     static constexpr bool SBASE = false;
     const __bf16* hm;
-    int C, J, HW;
+    RotRows L;
     struct Row { const __bf16* p; };
     __device__ __forceinline__ Row row(int m) const {
-        const int T = 2 * J;
+        const int T = 2 * L.J;      // (own lines: through RotRows::rowpart hipcc associates the channel sum differently -- a different kernel)
         const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J;
-        return Row{hm + (long)(b * C + 2 * J + eye * 2 * J + j) * HW};
+        const int eye = t / L.J, j = t - eye * L.J;
+        return Row{hm + (long)(b * L.C + 2 * L.J + eye * 2 * L.J + j) * L.HW};
     }
-    __device__ __forceinline__ const __bf16* ptr(const Row& r, int kt, int chunk) const {
-        const int k0 = kt * 64, cs = k0 / HW;
-        return r.p + (long)cs * J * HW + (k0 - cs * HW) + chunk * 8;
-    }
+    __device__ __forceinline__ const __bf16* ptr(const Row& r, int kt, int chunk) const { return L.col(r.p, kt * 64) + chunk * 8; }
 };
 
 // Epilogues whose per-column constants are just the bias (Col = SBias8 or f32x4 read from `bias`): the kernel stages the wave's 64 bias

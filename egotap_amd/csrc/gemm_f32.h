@@ -18,6 +18,7 @@
 // feeding four MFMAs.
 #pragma once
 #include "common.h"
+#include "head_layout.h"
 #include <type_traits>
 
 // ----------------------------------------------------------------------------- A loaders
@@ -37,24 +38,18 @@ struct ALoadPlain {
 // pixels of one patch.  Reference: net_architecture.py:375-383 + modeling_vit.py:195.
 struct ALoadPatch {
     const float* hm;   // [B, C, S, S] heatmaps, position channels first
-    int C, S, seq, side, ppd, grid, T;
+    PatchCells L;
     // [r3] zeros != nullptr: 256 zero floats (16-byte aligned) that stand in for the dummy cells, so that the loader is pure address math and can
     // feed the global -> LDS DMA (gemm_f32_dma.h); nullptr (the default): the register-staged kernels, as before
     const float* zeros = nullptr;
     struct Row { const float* p; };   // nullptr: dummy cell (zeros)
     static constexpr bool HAS_PTR = true;
-    __device__ __forceinline__ const float* ptr(const Row& r, int k) const { return r.p ? r.p + (k >> 4) * S + (k & 15) : zeros + k; }
-    __host__ bool dma_ok() const { return zeros != nullptr && S % 4 == 0 && ((uintptr_t)hm & 15) == 0 && ((uintptr_t)zeros & 15) == 0; }
-    __device__ __forceinline__ Row row(int m) const {
-        const int b = m / seq, tok = m - b * seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const int cell = (pr / ppd) * grid + pc / ppd;
-        if (cell >= T) return Row{nullptr};
-        return Row{hm + ((long)(b * C + cell) * S + (pr % ppd) * 16) * S + (pc % ppd) * 16};
-    }
+    __device__ __forceinline__ const float* ptr(const Row& r, int k) const { return r.p ? L.col(r.p, k) : zeros + k; }
+    __host__ bool dma_ok() const { return zeros != nullptr && L.S % 4 == 0 && ((uintptr_t)hm & 15) == 0 && ((uintptr_t)zeros & 15) == 0; }
+    __device__ __forceinline__ Row row(int m) const { return Row{L.pixel(hm, m)}; }
     __device__ __forceinline__ f32x4 load(const Row& r, int k) const {
         if (r.p == nullptr) return f32x4{0.f, 0.f, 0.f, 0.f};
-        return *(const f32x4*)(r.p + (k >> 4) * S + (k & 15));
+        return *(const f32x4*)L.col(r.p, k);
     }
 };
 
@@ -62,24 +57,13 @@ struct ALoadPatch {
 // flattened (patch-row, patch-col, channel).  Reference: net_architecture.py:388-406.
 struct ALoadTokens {
     const float* Y;    // [B*seq, D] final-LayerNorm tokens
-    int T, D, seq, side, ppd, grid;
+    TokenGather L;
     struct Row { const float* p; };
-    __device__ __forceinline__ Row row(int m) const {
-        const int b = m / T, i = m - b * T;
-        return Row{Y + ((long)b * seq + (long)(ppd * (i / grid)) * side + ppd * (i % grid)) * D};
-    }
-    __device__ __forceinline__ f32x4 load(const Row& r, int k) const {
-        const int s = k / D, c = k - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        return *(const f32x4*)(r.p + (long)(prl * side + pcl) * D + c);
-    }
+    __device__ __forceinline__ Row row(int m) const { return Row{Y + L.rowpart(m)}; }
+    __device__ __forceinline__ f32x4 load(const Row& r, int k) const { return *(const f32x4*)ptr(r, k); }
     static constexpr bool HAS_PTR = true;
-    __device__ __forceinline__ const float* ptr(const Row& r, int k) const {
-        const int s = k / D, c = k - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        return r.p + (long)(prl * side + pcl) * D + c;
-    }
-    __host__ bool dma_ok() const { return D % 4 == 0 && ((uintptr_t)Y & 15) == 0; }
+    __device__ __forceinline__ const float* ptr(const Row& r, int k) const { return L.col(r.p, k); }
+    __host__ bool dma_ok() const { return L.D % 4 == 0 && ((uintptr_t)Y & 15) == 0; }
 };
 
 // [r6] The pose-only forward's compact row order over the ViT's live tokens: row m = (b, cell i < T, patch row, patch col) -- fc1's
@@ -141,24 +125,18 @@ struct ALoadHead {
 // Reference: net_architecture.py:690-694 (channel order L_cos, L_sin, R_cos, R_sin after 2J position maps).
 struct ALoadRot {
     const float* hm;   // [B, C, S, S]
-    int C, J, HW;      // HW = S*S
+    RotRows L;         // HW = S*S
     struct Row { const float* p; };
     __device__ __forceinline__ Row row(int m) const {
-        const int T = 2 * J;
+        const int T = 2 * L.J;      // (own lines: through RotRows::rowpart hipcc associates the channel sum differently -- a different kernel)
         const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J;
-        return Row{hm + (long)(b * C + 2 * J + eye * 2 * J + j) * HW};
+        const int eye = t / L.J, j = t - eye * L.J;
+        return Row{hm + (long)(b * L.C + 2 * L.J + eye * 2 * L.J + j) * L.HW};
     }
-    __device__ __forceinline__ f32x4 load(const Row& r, int k) const {
-        const int cs = k / HW;
-        return *(const f32x4*)(r.p + (long)cs * J * HW + (k - cs * HW));
-    }
+    __device__ __forceinline__ f32x4 load(const Row& r, int k) const { return *(const f32x4*)ptr(r, k); }
     static constexpr bool HAS_PTR = true;
-    __device__ __forceinline__ const float* ptr(const Row& r, int k) const {
-        const int cs = k / HW;
-        return r.p + (long)cs * J * HW + (k - cs * HW);
-    }
-    __host__ bool dma_ok() const { return HW % 4 == 0 && ((uintptr_t)hm & 15) == 0; }
+    __device__ __forceinline__ const float* ptr(const Row& r, int k) const { return L.col(r.p, k); }
+    __host__ bool dma_ok() const { return L.HW % 4 == 0 && ((uintptr_t)hm & 15) == 0; }
 };
 
 // Propagation-unit inputs, time-major rows m = t*B + b: [left_t | right_t] features of
@@ -284,24 +262,20 @@ struct EpiBnLrelu {       // LeakyReLU_0.2(BatchNorm1d_eval(acc + bias))  (netwo
 };
 struct EpiPatch {         // (dummy ? mask_token : acc + bias) + position_embeddings   (modeling_vit.py:137-153)
     const float *bias, *mask_tok, *pos;
-    int D, seq, side, ppd, grid, T;
+    int D;
+    CellGrid g;
     struct Col { float b, mt; };
     __device__ __forceinline__ Col col(int n) const { return Col{bias[n], mask_tok[n]}; }
     __device__ __forceinline__ float apply(float acc, const Col& c, int m, int n) const {
-        const int tok = m % seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const bool dummy = (pr / ppd) * grid + pc / ppd >= T;
-        return (dummy ? c.mt : acc + c.b) + pos[(long)tok * D + n];
+        const int tok = m % g.seq;
+        return (g.dummy(tok) ? c.mt : acc + c.b) + pos[(long)tok * D + n];
     }
     struct Col4 { f32x4 b, mt; };
     __device__ __forceinline__ Col4 col4(int n0) const { return Col4{*(const f32x4*)(bias + n0), *(const f32x4*)(mask_tok + n0)}; }
     static constexpr bool HAS_RES = true;     // the position embedding row plays the residual's role
-    __device__ __forceinline__ f32x4 res4(int m, int n0) const { return *(const f32x4*)(pos + (long)(m % seq) * D + n0); }
+    __device__ __forceinline__ f32x4 res4(int m, int n0) const { return *(const f32x4*)(pos + (long)(m % g.seq) * D + n0); }
     __device__ __forceinline__ f32x4 apply4(f32x4 acc, const Col4& c, f32x4 res, int m, int n0) const {
-        const int tok = m % seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const bool dummy = (pr / ppd) * grid + pc / ppd >= T;
-        return (dummy ? c.mt : acc + c.b) + res;
+        return (g.dummy(m % g.seq) ? c.mt : acc + c.b) + res;
     }
 };
 
@@ -377,23 +351,17 @@ struct EpiGeluGrad {      // C = acc * gelu'(Z[m, n])   (input gradient of the M
 // row-major C.  Each element of the heatmaps is read by exactly one (row, column) of its forward loader, so each is written exactly once.
 struct EpiScatterPatch : EpiNone {    // inverse of ALoadPatch: row m = ViT token, column k = pixel (k >> 4, k & 15) of its 16 x 16 patch
     float* hm;
-    int C, S, seq, side, ppd, grid, T;
+    PatchCells L;
     __device__ __forceinline__ float* dst(int m, int n) const {      // nullptr: a dummy cell of the grid, which no heatmap pixel feeds
-        const int b = m / seq, tok = m - b * seq;
-        const int pr = tok / side, pc = tok - pr * side;
-        const int cell = (pr / ppd) * grid + pc / ppd;
-        if (cell >= T) return nullptr;
-        return hm + ((long)(b * C + cell) * S + (pr % ppd) * 16 + (n >> 4)) * S + (pc % ppd) * 16 + (n & 15);
+        return L.pixel<true>(hm, m, n >> 4, n & 15);
     }
 };
 struct EpiScatterRot : EpiNone {      // inverse of ALoadRot: row (b, eye * J + j), columns [cos plane | sin plane] of that limb
     float* hm;
-    int C, J, HW;
+    RotRows L;
     __device__ __forceinline__ float* dst(int m, int n) const {
-        const int T = 2 * J;
-        const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J, cs = n / HW;
-        return hm + (long)(b * C + 2 * J + eye * 2 * J + cs * J + j) * HW + (n - cs * HW);
+        const int cs = L.plane(n);
+        return hm + L.rowpart<true>(m, cs) + (n - cs * L.HW);
     }
 };
 // ---- C = acc + bias, compact row m stored to its physical row of C (HeadRows): the pose-only forward's layer-0 q | k | v of the live tokens

@@ -46,37 +46,25 @@ struct TXPlain {
 };
 struct TXTokens {            // rows gathered as XTokens (fc1 of the position encoder)
     const __bf16* Y;
-    int T, D, seq, side, ppd, grid;
+    TokenGather L;
     __device__ __forceinline__ const __bf16* base() const { return Y; }
-    __device__ __forceinline__ long kpart(int k) const {
-        const int s = k / D, c = k - s * D;
-        const int prl = s / ppd, pcl = s - prl * ppd;
-        return (long)(prl * side + pcl) * D + c;
-    }
+    __device__ __forceinline__ long kpart(int k) const { return L.kpart(k); }
     __device__ __forceinline__ long rowpart(int m) const {
-        const int b = m / T, i = m - b * T;
-        const int gr = i / grid;
-        return ((long)b * seq + (long)(ppd * gr) * side + ppd * (i - gr * grid)) * D;
+        const int b = m / L.T, i = m - b * L.T;      // (own lines: through TokenGather::rowpart hipcc orders the index arithmetic differently -- a different kernel)
+        const int gr = i / L.grid;
+        return ((long)b * L.seq + (long)(L.ppd * gr) * L.side + L.ppd * (i - gr * L.grid)) * L.D;
     }
     __device__ __forceinline__ const __bf16* ptr(int m, int k) const { return Y + rowpart(m) + kpart(k); }
-    long span(int M) const { return (long)((M + T - 1) / T) * seq * D; }
+    long span(int M) const { return (long)((M + L.T - 1) / L.T) * L.seq * L.D; }
 };
 struct TXRot {               // rows gathered as XRot (fc1 of the rotation encoder)
     const __bf16* hm;
-    int C, J, HW;
+    RotRows L;
     __device__ __forceinline__ const __bf16* base() const { return hm; }
-    __device__ __forceinline__ long kpart(int k) const {
-        const int cs = k / HW;
-        return (long)cs * J * HW + (k - cs * HW);
-    }
-    __device__ __forceinline__ long rowpart(int m) const {
-        const int T = 2 * J;
-        const int b = m / T, t = m - b * T;
-        const int eye = t / J, j = t - eye * J;
-        return (long)(b * C + 2 * J + eye * 2 * J + j) * HW;
-    }
+    __device__ __forceinline__ long kpart(int k) const { return L.kpart(k); }
+    __device__ __forceinline__ long rowpart(int m) const { return L.rowpart(m); }
     __device__ __forceinline__ const __bf16* ptr(int m, int k) const { return hm + rowpart(m) + kpart(k); }
-    long span(int M) const { return (long)((M + 2 * J - 1) / (2 * J)) * C * HW; }
+    long span(int M) const { return (long)((M + 2 * L.J - 1) / (2 * L.J)) * L.C * L.HW; }
 };
 
 // FAST (plain X operand, M a multiple of 32: every 32-row step of every split is whole): the DMA addresses are a wave-uniform 64-bit base

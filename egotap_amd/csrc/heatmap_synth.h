@@ -16,6 +16,7 @@
 // source (Zingl's anti-aliased Bresenham): parity of that step is unpinned; everything else is pinned (see oracle).
 #pragma once
 #include "common.h"
+#include "head_layout.h"
 
 struct GaussTaps { double w[9]; };
 
@@ -110,7 +111,7 @@ static __global__ __launch_bounds__(256) void heatmap_synth_kernel(const float* 
     }
     __syncthreads();
     const float cs = cosf(th), sn = sinf(th);
-    float* dcos = out + (long)(2 * J + eye * 2 * J + (j - 1)) * HW;
+    float* dcos = out + (long)rot_channel(J, eye, j - 1) * HW;
     float* dsin = dcos + (long)J * HW;
     for (int i = tid; i < HW; i += 256) {
         const int r = i / S, c = i - r * S;

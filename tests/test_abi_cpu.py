@@ -48,6 +48,37 @@ def test_dma_statement_and_persistent_tile_walk_are_written_once():
     assert [f for f, t in code.items() if re.search(r"q8\s*=\s*ntiles\s*>>\s*3", t)] == ["common.h"]
 
 
+def test_head_layouts_and_conv_taps_are_written_once():
+    """Outside comments, csrc/ spells out the head's grid arithmetic and rotation channel order only in head_layout.h and the 3x3 tap
+    decode / nine-tap mask of the bf16 conv loaders only in conv_taps.h.  EXCEPT lists, per pattern, the files that keep copies and how
+    many: LiveRows (not a loader layout: gemm_f32.h's grid arithmetic) and the callers that hipcc compiles to a different kernel through the
+    shared functions (each says so on the spot; profiles/operand_layout_summary.md names them).  A new copy anywhere fails here."""
+    csrc = os.path.join(REPO, "egotap_amd", "csrc")
+    code = {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, f)).read(), flags=re.S) for f in sorted(os.listdir(csrc))}
+    q = r"(?:\w+\.)*"      # a member written through its struct (L.grid, L.g.ppd)
+    EXCEPT = {
+        # pattern: (home, {file: copies outside the home})
+        rf"/\s*{q}grid\b": ("head_layout.h", {"gemm_f32.h": 1,            # LiveRows
+                                              "gemm_bf16s.h": 1,          # SEpiScatterTokens
+                                              "gemm_tn_bf16s.h": 1}),     # TXTokens::rowpart
+        rf"%\s*{q}grid\b": ("head_layout.h", {"gemm_f32.h": 1,            # LiveRows
+                                              "gemm_bf16s.h": 1}),        # SEpiScatterTokens
+        rf"/\s*{q}ppd\)\s*\*\s*{q}grid\b": ("head_layout.h", {"gemm_bf16s.h": 1,          # SEpiScatterPatch
+                                                              "egotap_abi.hip": 1}),      # patch_split_kernel
+        rf"eye\s*\*\s*2\s*\*\s*{q}J\b": ("head_layout.h", {"gemm_f32.h": 1,               # ALoadRot::row
+                                                           "gemm_bf16s.h": 2,             # XRot::row, SEpiScatterRot
+                                                           "gemm_bf16s64.h": 1}),         # X64Rot::row
+        r"\*\s*7282\b": ("conv_taps.h", {"conv_bf16s.h": 2,               # XConv3::ptr, XConvE::ptr
+                                         "gemm_bf16s64.h": 2}),           # X64Conv3::ptr, X64ConvE::ptr
+        r"\*\s*11\)\s*>>\s*5\b": ("conv_taps.h", {"conv_bf16s.h": 2, "gemm_bf16s64.h": 2}),      # the same four
+        r"\bt\s*<\s*9\b": ("conv_taps.h", {"gemm_bf16s64.h": 1}),         # X64ConvES::row
+    }
+    for pat, (home, copies) in EXCEPT.items():
+        found = {f: len(re.findall(pat, t)) for f, t in code.items() if re.search(pat, t)}
+        assert found.pop(home, 0) >= 1, (pat, home)
+        assert found == copies, (pat, found)
+
+
 def _cfg(**kw):
     base = dict(n_joints_hm=15, estimate_head=1, hm_size=64, hidden=128, vit_dim=1024, vit_heads=8, vit_layers=3,
                 patch=16, pu_hidden=512)
