@@ -14,6 +14,7 @@
 //                              fixed summation order: bitwise reproducible).  7 products per tile pair instead of 8.
 #pragma once
 #include "attention_bwd_bf16.h"
+#include "gemm_bf16s.h"      // store_bf16x8
 
 namespace attns {
 using namespace attnbf;

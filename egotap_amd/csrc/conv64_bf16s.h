@@ -9,7 +9,7 @@
 //     tile multiplies.  All nine taps read it in place: a tap is an address offset.
 //   * v_mfma_f32_32x32x16_bf16 with A = weights, B = pixels: wave (mh, rg) owns output channels 32 mh .. +31 and tile rows 4 rg .. 4 rg + 3.
 //     Its A fragments -- 32 channels x 576 k -- stay in registers for the whole kernel (144 VGPRs, read once from the packed weights
-//     [co][ci / 32][tap][ci % 32] of pack_conv3x3_bf16s_kernel); the only LDS traffic of the loop is one ds_read_b128 per MFMA.
+//     [co][ci / 32][tap][ci % 32] of pack_all_bf16s_kernel); the only LDS traffic of the loop is one ds_read_b128 per MFMA.
 //     A pixel's eight 16-byte channel chunks sit at chunk ^ ((x >> 1) & 7): the 16 lanes a ds_read_b128 serves together are 16
 //     consecutive x of one row, i.e. 16 distinct 16-byte slots of the 256-byte bank row (conflict-free); the DMA applies the swizzle
 //     on the global side.

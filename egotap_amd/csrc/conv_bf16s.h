@@ -113,48 +113,6 @@ template <> struct s_epi_colwise<SEpiHeatBf16> { static constexpr bool value = t
 template <> struct s_epi_exact<SEpiHeatBf16> { static constexpr bool value = false; };
 
 // ---------------------------------------------------------------------------------------------------- helpers
-// [Cout][Cin][3][3] f32 -> [Np][Cp / 32][tap][32] bf16 (channels past Cin and rows past Cout zero).  One thread = 8 consecutive ci of one (co, tap).
-static __global__ __launch_bounds__(256) void pack_conv3x3_bf16s_kernel(const float* __restrict__ w, __bf16* __restrict__ wb, int Cout, int Cin, int Cp,
-                                                                        int Np) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c8n = Cp / 8;
-    if (i >= (long)Np * 9 * c8n) return;
-    const int c8 = (int)(i % c8n), tap = (int)((i / c8n) % 9), co = (int)(i / (9L * c8n));
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ci = c8 * 8 + j;
-        o[j] = (ci < Cin && co < Cout) ? (__bf16)w[((long)co * Cin + ci) * 9 + tap] : (__bf16)0.f;
-    }
-    *(bf16x8*)(wb + (long)co * 9 * Cp + ((long)(c8 >> 2) * 9 + tap) * 32 + (c8 & 3) * 8) = o;       // k = (ci / 32, tap, ci % 32)
-}
-// [Cout][Cin] f32 (+ bias) -> [Np][Cin] bf16, [Np] f32: rows past Cout zero
-static __global__ __launch_bounds__(256) void pack_conv1x1_bf16s_kernel(const float* __restrict__ w, const float* __restrict__ b,
-                                                                        __bf16* __restrict__ wb, float* __restrict__ bp, int Cout, int Cin, int Np) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c8n = Cin / 8;
-    if (i >= (long)Np * c8n) return;
-    const int c8 = (int)(i % c8n), co = (int)(i / c8n);
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = co < Cout ? (__bf16)w[(long)co * Cin + c8 * 8 + j] : (__bf16)0.f;
-    *(bf16x8*)(wb + (long)co * Cin + c8 * 8) = o;
-    if (c8 == 0 && b != nullptr) bp[co] = co < Cout ? b[co] : 0.f;
-}
-// pyramid level: f32 NCHW [Nimg, C, HW] -> bf16 channels-last [Nimg * HW, C].  Lanes along pixels (coalesced reads), 8 channels each.
-static __global__ __launch_bounds__(256) void nchw_to_nhwc_bf16s_kernel(const float* __restrict__ in, __bf16* __restrict__ out, int C, int HW, long total) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int pix = (int)(i % HW);
-    const long t = i / HW;
-    const int c8 = (int)(t % (C / 8));
-    const long img = t / (C / 8);
-    const float* p = in + (img * C + c8 * 8) * (long)HW + pix;
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (__bf16)p[(long)j * HW];
-    *(bf16x8*)(out + (img * HW + pix) * (long)C + c8 * 8) = o;
-}
 // F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) on channels-last bf16: in [Nimg, h, h, C] -> the first C channels
 // of out rows [Nimg, 2h, 2h, ld].  One thread = 8 channels of one output pixel; fp32 arithmetic in the order of upsample2x_kernel.
 static __global__ __launch_bounds__(256) void upsample2x_nhwc_bf16s_kernel(const __bf16* __restrict__ in, __bf16* __restrict__ out, int C, int h, long ld,
@@ -243,22 +201,6 @@ struct SEpiBnBf16 {          // out bf16 = relu?(acc * scale + shift (+ R)) in t
     }
 };
 template <> struct s_epi_exact<SEpiBnBf16<true>> { static constexpr bool value = false; };
-
-// eval-mode BatchNorm folded to y = x * scale + shift, padded with zeros to Np channels (as conv_f32.h's epilogue computes it)
-static __global__ __launch_bounds__(256) void bn_fold_bf16s_kernel(const float* __restrict__ g, const float* __restrict__ b, const float* __restrict__ m,
-                                                                   const float* __restrict__ v, float* __restrict__ scale, float* __restrict__ shift,
-                                                                   int C, int Np) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= Np) return;
-    float sc = 0.f, sh = 0.f;
-    if (c < C) {
-        sc = g[c] / sqrtf(v[c] + 1e-5f);
-        sh = b[c] - m[c] * sc;
-    }
-    scale[c] = sc;
-    shift[c] = sh;
-}
-
 // ---------------------------------------------------------------------------------------------------- [r3] one launch for all of them
 // An estimator forward repacked its 27 convolution weights and folded its 19 BatchNorms with 46 tiny launches (0.46 ms of a 15 ms
 // forward at B = 256, 5 % at B = 32 and 512 x 512).  The parameters stay the caller's live fp32 tensors and nothing is cached across

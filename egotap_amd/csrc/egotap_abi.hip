@@ -1,4 +1,4 @@
-// C ABI of libegotap_hip.so (include/egotap.h): handle, parameter binding, the lifting-head forward
+// C ABI of libegotap_hip.so (include/egotap.h, include/egotap_debug.h): handle, parameter binding, the lifting-head forward
 // (EgoTAPAutoEncoder.forward, model/net_architecture.py:682-758) as a sequence of HIP launches on the
 // caller's stream, single-operator entry points and the GEMM timing hook.
 #include <stdarg.h>
@@ -10,9 +10,24 @@
 #include <unordered_map>
 #include <vector>
 
-#include "attention_f32.h"
 #include "common.h"
+
+// The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
+// inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
+// part.  Without EGOTAP_PART the file is a single translation unit.
+//
+// A part sees only what it launches.  A static launcher or kernel a part can see is compiled into that part's code object whether the part
+// launches it or not, so each part includes only the kernel headers it launches from, and the code below stands in sections: what all four parts use, what two or
+// three share (one guarded section per set of parts), then each part's own code with the helpers only it uses.  `hipcc -DEGOTAP_PART=n --cuda-host-only -fsyntax-only -Wunused-function` names what a part sees
+// and does not use (tests/test_abi_cpu.py runs it); a helper withheld from a part that needs it does not compile.
+#ifndef EGOTAP_PART
+#define EGOTAP_PART -1
+#endif
+#define EGOTAP_IN(n) (EGOTAP_PART < 0 || EGOTAP_PART == (n))
+
+#if EGOTAP_IN(0)
 #include "lds_opt_in.h"
+#include "attention_f32.h"
 #include "conv_f32.h"
 #include "conv_bf16.h"
 #include "gemm_f32.h"
@@ -24,14 +39,10 @@
 #include "metrics.h"
 #include "heatmap_synth.h"
 #include "pu_chain.h"
-#include "gemm_tn_bf16.h"
-#include "train_ops.h"
 #include "gemm_bf16s.h"
 #include "gemm_bf16s64.h"
-#include "gemm_tn_bf16s.h"
 #include "bf16s_ops.h"
-#include "attention_bf16s.h"
-#include "attention_bf16s2.h"
+#include "attention_bf16s2.h"      // and attention_bf16s.h, which it includes: the launchers there call into it
 #include "conv_bf16s.h"
 #include "stem_bf16s.h"
 #include "conv64_bf16s.h"
@@ -43,78 +54,44 @@
 #include "limb_decode.h"
 #include "ocam.h"
 #include "pose_track.h"
-
-// The library is ONE source compiled as four translation units in parallel (egotap_amd/build.py: -DEGOTAP_PART=0 core and
-// inference, 1 lifting-head training operators, 2 heatmap-estimator training operators, 3 bf16-storage operators); every exported function belongs to one
-// part, the static helpers and kernel templates are visible to all.  Without EGOTAP_PART the file is a single translation unit.
-#ifndef EGOTAP_PART
-#define EGOTAP_PART -1
 #endif
-#define EGOTAP_IN(n) (EGOTAP_PART < 0 || EGOTAP_PART == (n))
-
-// ------------------------------------------------------------------------------------------------ errors
-#if EGOTAP_IN(0)
-static thread_local char g_err[1024] = "";
-void egotap_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-hipError_t ego_allow_dynamic_lds(const void* kernel, int bytes) {
-    static LdsOptIn seen;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    return seen.ensure(kernel, dev, bytes, [kernel](int b) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, b); });
-}
+#if EGOTAP_IN(1)
+#include "attention_f32.h"
+#include "gemm_f32.h"
+#include "gemm_bf16.h"
+#include "gemm_bf16_dma.h"
+#include "gemm_f32_dma.h"
+#include "attention_bf16.h"
+#include "pu_chain.h"
+#include "gemm_tn_bf16.h"
+#include "train_ops.h"
+#include "attention_bwd_f32.h"
+#include "attention_bwd_bf16.h"
+#include "gemm_tn_f32.h"
+// Not launched from part 1, kept for the device code of attn_bwd_dq / _dk / _dv_bf16_kernel<4, 1> (attention_bwd_bf16.h), which it does launch:
+// attention_bf16s.h (behind attention_bf16s2.h) instantiates attn_bwd_dq_bf16s_kernel<4, 1> first, and clang emits the inline helpers the two share (attnbf::tile_x_frags<1>,
+// attnbf::acc_tile_t_x_p<1>) in order of first reference.  Without it they are emitted, and inlined, later, and the three kernels come out with the
+// same instructions in another schedule (profiles/abi_parts_summary.md).  Costs this part four kernels it does not launch.
+#include "attention_bf16s2.h"      // and attention_bf16s.h, which it includes: the launchers there call into it
 #endif
-#if EGOTAP_IN(0)
-extern "C" const char* egotap_last_error(void) { return g_err; }
+#if EGOTAP_IN(2)
+#include "conv_f32.h"
+#include "conv_bf16.h"
+#include "hm_train.h"
 #endif
-#if EGOTAP_IN(0)
-extern "C" int egotap_abi_version(void) { return EGOTAP_ABI_VERSION; }
+#if EGOTAP_IN(3)
+#include "gemm_bf16.h"
+#include "gemm_bf16s.h"
+#include "gemm_bf16s64.h"
+#include "gemm_tn_bf16s.h"
+#include "bf16s_ops.h"
+#include "attention_bf16s2.h"      // and attention_bf16s.h, which it includes: the launchers there call into it
+#include "gemm_tn_f32.h"
 #endif
+#include "head_layout.h"      // the head's operand layouts the handle hands out
+#include "conv_bf16s.h"       // PackTable::MAXW sizes a member of the handle: parts 1-3 see this header for the type alone (part 0 launches from it, above)
 
-// ------------------------------------------------------------------------------------------------ tiles
-using TileA = GemmCfg<128, 128, 32, 2, 2, 2>;   // 4 waves, 64x64 per wave, 2 blocks/CU
-using TileB = GemmCfg<256, 128, 32, 4, 2, 2>;   // 8 waves, 64x64 per wave, 1 block/CU
-using TileC = GemmCfg<128, 256, 32, 2, 4, 2>;   // 8 waves, 64x64 per wave, 1 block/CU
-using TileD = GemmCfg<256, 256, 16, 4, 2, 2>;   // 8 waves, 64x128 per wave, 1 block/CU
-using TileE = GemmCfg<256, 128, 16, 2, 2, 2>;   // 4 waves, 128x64 per wave, 2 blocks/CU
-using TileF = GemmCfg<64, 64, 32, 2, 2, 2>;     // 4 waves, 32x32 per wave (small problems)
-using TileG = GemmCfg<256, 128, 32, 2, 2, 1>;   // 4 waves, 128x64 per wave, 1 block/CU
-using TileS = GemmCfg<64, 128, 32, 2, 4, 1>;    // [r4] 8 waves, 32x32 per wave (two waves per SIMD when the workgroup is alone on its CU: -1.8 % on a B = 1 forward against 4 waves): GEMMs of at most 64 rows (the encoders' fc layers and the PU projections at B <= 2-4) --
-                                                // on the 128-row tile a 30-row product is paced by its MFMAs on 98 rows of zeros (fc1 at B = 1: 1.7 TB/s of weights)
-using PipeA = PipeCfg<128, 128, 16, 2, 2, 2>;   // pipelined: 3 x 20 KiB slabs, 2 blocks/CU
-using PipeB = PipeCfg<128, 128, 32, 2, 2, 1>;   // pipelined: 3 x 36 KiB slabs, 1 block/CU
-using PipeC = PipeCfg<256, 128, 16, 4, 2, 2>;   // pipelined, 8 waves: 3 x 30 KiB slabs, 1 block/CU
-using PipeD = PipeCfg<256, 256, 16, 4, 2, 2>;   // pipelined, 8 waves 64x128 per wave: 3 x 40 KiB slabs
-
-#if EGOTAP_IN(0)
-extern "C" const char* egotap_gemm_tile_name(int tile) {
-    switch (tile) {
-        case 0: case 1: return "128x128x32/4w";
-        case 2: return "256x128x32/8w";
-        case 3: return "128x256x32/8w";
-        case 4: return "256x256x16/8w";
-        case 5: return "256x128x16/4w";
-        case 6: return "64x64x32/4w";
-        case 7: return "256x128x32/4w";
-        case 8: return "pipe128x128x16/4w";
-        case 9: return "pipe128x128x32/4w";
-        case 10: return "pipe256x128x16/8w";
-        case 11: return "pipe256x256x16/8w";
-        case 12: return "persist256x256x16/8w";
-        case 13: return "persist256x256x16/8w/bf16x3";
-        case 14: return "persist256x256x32/8w/bf16";
-        case 15: return "persist256x256x16/8w/bf16x3/interleaved";
-        case 16: return "persist256x256x32/8w/bf16/interleaved";
-        case 19: return "dma256x256x16/8w (exact fp32, LDS-DMA staging)";
-        default: return nullptr;
-    }
-}
-#endif
-
+// ================================================================================================ all four parts: the handle, the bound parameters, the timing bracket
 // ------------------------------------------------------------------------------------------------ handle
 struct Param {
     void* ptr = nullptr;
@@ -191,6 +168,450 @@ struct egotap_handle_s {
     std::string detail;           // JSON written by egotap_timing_read
 };
 typedef egotap_handle_s Handle;
+
+struct GemmTimer {   // brackets one GEMM launch when the handle's timing hook is on
+    Handle* h;
+    hipStream_t s;
+    bool on;
+    GemmTimer(Handle* h_, hipStream_t s_, const char* role, const char* kernel, double flops)
+        : h(h_), s(s_), on(h_ && h_->timing) {
+        if (!on) return;
+        if (h->ev_used + 2 > h->ev.size()) {
+            hipEvent_t a, b;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
+            h->ev.push_back(a);
+            h->ev.push_back(b);
+        }
+        (void)hipEventRecord(h->ev[h->ev_used], s);
+        h->rec.push_back({role, kernel, flops});
+    }
+    ~GemmTimer() {
+        if (!on) return;
+        (void)hipEventRecord(h->ev[h->ev_used + 1], s);
+        h->ev_used += 2;
+    }
+};
+
+// large GEMMs (ViT projections, fc1): 256x256 tile, 3-stage pipelined kernel -- fewest global-load
+// instructions per MFMA (each costs the matrix pipe ~56 cycles, tools/mfma_probe.hip), DESIGN.md section 4
+static int device_cu_count() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else n = 256;
+    }
+    return n;
+}
+
+// ================================================================================================ parts 0, 1 and 3: the zero fill
+#if EGOTAP_IN(0) || EGOTAP_IN(1) || EGOTAP_IN(3)
+// stream-ordered zero fill as a KERNEL: a hipMemsetAsync captured into a HIP graph did not re-execute on replay (ROCm 7.2: the
+// propagation units' cell state then carried over from one replay to the next), a kernel node does
+static __global__ __launch_bounds__(256) void zero_fill_kernel(f32x4* __restrict__ p, long n16) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n16) p[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+static hipError_t zero_fill(void* p, size_t bytes, hipStream_t s) {       // p 16-byte aligned, bytes a multiple of 16
+    if (bytes == 0) return hipSuccess;
+    if ((((uintptr_t)p) | bytes) & 15) return hipErrorInvalidValue;
+    const long n16 = (long)(bytes / 16);
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (f32x4*)p, n16);
+    return hipGetLastError();
+}
+#endif
+
+// ================================================================================================ parts 0 and 1: what the lifting head's forward and its training operators share
+// (GEMM tiles and routing, parameter resolver, the propagation units' residency probe)
+#if EGOTAP_IN(0) || EGOTAP_IN(1)
+// ------------------------------------------------------------------------------------------------ tiles
+using TileA = GemmCfg<128, 128, 32, 2, 2, 2>;   // 4 waves, 64x64 per wave, 2 blocks/CU
+using TileB = GemmCfg<256, 128, 32, 4, 2, 2>;   // 8 waves, 64x64 per wave, 1 block/CU
+using TileC = GemmCfg<128, 256, 32, 2, 4, 2>;   // 8 waves, 64x64 per wave, 1 block/CU
+using TileD = GemmCfg<256, 256, 16, 4, 2, 2>;   // 8 waves, 64x128 per wave, 1 block/CU
+using TileE = GemmCfg<256, 128, 16, 2, 2, 2>;   // 4 waves, 128x64 per wave, 2 blocks/CU
+using TileF = GemmCfg<64, 64, 32, 2, 2, 2>;     // 4 waves, 32x32 per wave (small problems)
+using TileG = GemmCfg<256, 128, 32, 2, 2, 1>;   // 4 waves, 128x64 per wave, 1 block/CU
+using TileS = GemmCfg<64, 128, 32, 2, 4, 1>;    // [r4] 8 waves, 32x32 per wave (two waves per SIMD when the workgroup is alone on its CU: -1.8 % on a B = 1 forward against 4 waves): GEMMs of at most 64 rows (the encoders' fc layers and the PU projections at B <= 2-4) --
+                                                // on the 128-row tile a 30-row product is paced by its MFMAs on 98 rows of zeros (fc1 at B = 1: 1.7 TB/s of weights)
+using PipeA = PipeCfg<128, 128, 16, 2, 2, 2>;   // pipelined: 3 x 20 KiB slabs, 2 blocks/CU
+using PipeB = PipeCfg<128, 128, 32, 2, 2, 1>;   // pipelined: 3 x 36 KiB slabs, 1 block/CU
+using PipeC = PipeCfg<256, 128, 16, 4, 2, 2>;   // pipelined, 8 waves: 3 x 30 KiB slabs, 1 block/CU
+using PipeD = PipeCfg<256, 256, 16, 4, 2, 2>;   // pipelined, 8 waves 64x128 per wave: 3 x 40 KiB slabs
+
+typedef std::unordered_map<std::string, Param> ParamMap;
+static const float* P(Handle*, const ParamMap& m, const std::string& key, bool& ok) {
+    auto it = m.find(key);
+    if (it == m.end()) {
+        if (ok) egotap_set_error("'%s' is not bound", key.c_str());
+        ok = false;
+        return nullptr;
+    }
+    return (const float*)it->second.ptr;
+}
+
+// fills a LiftParams from a key -> pointer map: the parameters (with_stats: and the BatchNorm running statistics) or their gradients
+static int lift_resolve_into(Handle* h, const ParamMap& N, LiftParams& p, bool with_stats) {
+    bool ok = true;
+    const std::string v = "pos_heatmap_encoder.vit.";
+    p.mask_tok = P(h, N, v + "embeddings.mask_token", ok);
+    p.pos_emb = P(h, N, v + "embeddings.position_embeddings", ok);
+    p.patch_w = P(h, N, v + "embeddings.patch_embeddings.projection.weight", ok);
+    p.patch_b = P(h, N, v + "embeddings.patch_embeddings.projection.bias", ok);
+    for (int i = 0; i < h->cfg.vit_layers; ++i) {
+        const std::string l = v + "encoder.layer." + std::to_string(i) + ".";
+        auto& L = p.layer[i];
+        L.q_w = P(h, N, l + "attention.attention.query.weight", ok); L.q_b = P(h, N, l + "attention.attention.query.bias", ok);
+        L.k_w = P(h, N, l + "attention.attention.key.weight", ok);   L.k_b = P(h, N, l + "attention.attention.key.bias", ok);
+        L.v_w = P(h, N, l + "attention.attention.value.weight", ok); L.v_b = P(h, N, l + "attention.attention.value.bias", ok);
+        L.o_w = P(h, N, l + "attention.output.dense.weight", ok);    L.o_b = P(h, N, l + "attention.output.dense.bias", ok);
+        L.up_w = P(h, N, l + "intermediate.dense.weight", ok);       L.up_b = P(h, N, l + "intermediate.dense.bias", ok);
+        L.dn_w = P(h, N, l + "output.dense.weight", ok);             L.dn_b = P(h, N, l + "output.dense.bias", ok);
+        L.ln1_g = P(h, N, l + "layernorm_before.weight", ok);        L.ln1_b = P(h, N, l + "layernorm_before.bias", ok);
+        L.ln2_g = P(h, N, l + "layernorm_after.weight", ok);         L.ln2_b = P(h, N, l + "layernorm_after.bias", ok);
+    }
+    p.lnf_g = P(h, N, v + "layernorm.weight", ok);
+    p.lnf_b = P(h, N, v + "layernorm.bias", ok);
+    const char* encs[2] = {"pos_heatmap_encoder", "rot_heatmap_encoder"};
+    for (int e = 0; e < 2; ++e)
+        for (int i = 0; i < 3; ++i) {
+            const std::string f = std::string(encs[e]) + ".fc" + std::to_string(i + 1);
+            LiftParams::Fc& fc = e == 0 ? p.pos_fc[i] : p.rot_fc[i];
+            fc.w = P(h, N, f + ".fc.weight", ok);        fc.b = P(h, N, f + ".fc.bias", ok);
+            fc.g = P(h, N, f + ".bn.weight", ok);        fc.beta = P(h, N, f + ".bn.bias", ok);
+            fc.mean = fc.var = nullptr;
+            if (with_stats) { fc.mean = P(h, N, f + ".bn.running_mean", ok); fc.var = P(h, N, f + ".bn.running_var", ok); }
+        }
+    const std::string c = "skel_sequential_layer.lstm_custom.layers.";
+    p.x2f0_w = P(h, N, c + "0.x2f.weight", ok); p.x2f0_b = P(h, N, c + "0.x2f.bias", ok);
+    p.x2h0_w = P(h, N, c + "0.x2h.weight", ok); p.x2h0_b = P(h, N, c + "0.x2h.bias", ok);
+    p.b2h0_w = P(h, N, c + "0.b2h.weight", ok); p.b2h0_b = P(h, N, c + "0.b2h.bias", ok);
+    p.h2h0_w = P(h, N, c + "0.h2h.weight", ok); p.h2h0_b = P(h, N, c + "0.h2h.bias", ok);
+    p.x2f1_w = P(h, N, c + "1.x2f.weight", ok); p.x2f1_b = P(h, N, c + "1.x2f.bias", ok);
+    p.x2h1_w = P(h, N, c + "1.x2h.weight", ok); p.x2h1_b = P(h, N, c + "1.x2h.bias", ok);
+    p.h2h1_w = P(h, N, c + "1.h2h.weight", ok); p.h2h1_b = P(h, N, c + "1.h2h.bias", ok);
+    p.pose_w = P(h, N, "pose_mlp.pose_fcs.0.weight", ok); p.pose_b = P(h, N, "pose_mlp.pose_fcs.0.bias", ok);
+    p.glob_w = p.glob_b = nullptr;
+    if (h->cfg.estimate_head) {
+        p.glob_w = P(h, N, "global_mlp.pose_fcs.0.weight", ok);
+        p.glob_b = P(h, N, "global_mlp.pose_fcs.0.bias", ok);
+    }
+    return ok ? EGOTAP_OK : EGOTAP_ERR_UNBOUND;
+}
+
+static int lift_resolve(Handle* h) {
+    if (h->lift_resolved) return EGOTAP_OK;
+    const int rc = lift_resolve_into(h, h->bound[EGOTAP_NET_LIFT], h->lp, true);
+    if (rc != EGOTAP_OK) return rc;
+    h->lift_resolved = true;
+    return EGOTAP_OK;
+}
+
+template <class AL> struct AlName;
+template <> struct AlName<ALoadPlain> { static constexpr const char* v = "ALoadPlain"; };
+template <> struct AlName<ALoadPatch> { static constexpr const char* v = "ALoadPatch"; };
+template <> struct AlName<ALoadTokens> { static constexpr const char* v = "ALoadTokens"; };
+template <> struct AlName<ALoadLive> { static constexpr const char* v = "ALoadLive"; };
+template <> struct AlName<ALoadHead> { static constexpr const char* v = "ALoadHead"; };
+template <> struct AlName<ALoadRot> { static constexpr const char* v = "ALoadRot"; };
+template <> struct AlName<ALoadStereo> { static constexpr const char* v = "ALoadStereo"; };
+template <> struct AlName<ALoadStereoGated> { static constexpr const char* v = "ALoadStereoGated"; };
+template <class E> struct EpiName;
+template <> struct EpiName<EpiBias> { static constexpr const char* v = "EpiBias"; };
+template <> struct EpiName<EpiBiasRes> { static constexpr const char* v = "EpiBiasRes"; };
+template <> struct EpiName<EpiBiasResLive> { static constexpr const char* v = "EpiBiasResLive"; };
+template <> struct EpiName<EpiBiasHead> { static constexpr const char* v = "EpiBiasHead"; };
+template <> struct EpiName<EpiBiasGelu> { static constexpr const char* v = "EpiBiasGelu"; };
+template <> struct EpiName<EpiBnLrelu> { static constexpr const char* v = "EpiBnLrelu"; };
+template <> struct EpiName<EpiPatch> { static constexpr const char* v = "EpiPatch"; };
+
+template <class Cfg, class AL, class Epi>
+static hipError_t gemm(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc,
+                       int M, int N, int K, hipStream_t s) {
+    static const std::string kname = std::string("gemm_f32_kernel<") + std::to_string(Cfg::BM) + "x" +
+                                     std::to_string(Cfg::BN) + "x" + std::to_string(Cfg::BK) + "," + AlName<AL>::v + "," +
+                                     EpiName<Epi>::v + ">";
+    GemmTimer t(h, s, role, kname.c_str(), 2.0 * M * N * K);
+    return gemm_f32_launch<Cfg, AL, Epi>(al, W, epi, C, ldc, M, N, K, s);
+}
+
+// rows of an fp32 matrix (row stride lda) -> dense bf16 [M, K]
+static __global__ __launch_bounds__(256) void f32_to_bf16_rows_kernel(const float* __restrict__ src, long lda, __bf16* __restrict__ dst, int k8, long n8) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    const long row = i / k8;
+    const float* p = src + row * lda + (i - row * k8) * 8;
+    *(bf16x8*)(dst + i * 8) = bf16_round8(*(const f32x4*)p, *(const f32x4*)(p + 4));
+}
+// plain-bf16 GEMM: W rounded to bf16 into the handle's scratch right before the launch (stream ordered), so the W operand costs
+// half the vector-memory bytes; without a scratch (or if it is too small) the kernel converts fp32 weights on the fly.
+// A plain row-major activation operand is rounded to bf16 the same way (egotap_set_act_scratch; skipped when the scratch is
+// absent or too small) and the product runs on the
+// LDS-DMA kernel (gemm_bf16_dma.h): same rounding of both operands, same fp32 accumulation order per output element.
+template <class AL, class Epi>
+static hipError_t gemm_bf16_plain(Handle* h, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc, int M, int N, int K, hipStream_t s) {
+    const int nseg = N / W.seg;
+    if (h && h->wscratch && (size_t)N * K * 2 <= h->wscratch_bytes && K % 8 == 0 && W.ld == K && nseg >= 1 && nseg <= 3 && nseg * W.seg == N) {
+        SegMatB B;
+        for (int i = 0; i < 3; ++i) B.p[i] = h->wscratch + (size_t)(i < nseg ? i : 0) * W.seg * K;
+        B.seg = W.seg; B.ld = K;
+        const long n8 = (long)W.seg * K / 8;
+        for (int i = 0; i < nseg; ++i)
+            hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, W.p[i], h->wscratch + (size_t)i * W.seg * K, n8);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if constexpr (std::is_same<AL, ALoadPlain>::value) {
+            if (K % DmaCfg::BK == 0 && N % DmaCfg::BN == 0 && W.seg % DmaCfg::BN == 0 && al.lda % 4 == 0 && M >= 1024) {
+                __bf16* a = (size_t)M * K * 2 <= h->ascratch_bytes ? h->ascratch : nullptr;
+                if (a) {
+                    const long a8 = (long)M * K / 8;
+                    hipLaunchKernelGGL(f32_to_bf16_rows_kernel, dim3((unsigned)((a8 + 255) / 256)), dim3(256), 0, s, al.A, al.lda, a, K / 8, a8);
+                    e = hipGetLastError();
+                    if (e != hipSuccess) return e;
+                    return gemm_bf16_dma_launch(a, (long)K, B, epi, C, ldc, M, N, K, device_cu_count(), s);
+                }
+            }
+        }
+        return gemm_bf16_persist_launch<BfCfg<1, 1>, AL, Epi, SegMatB>(al, B, epi, C, ldc, M, N, K, device_cu_count(), s);
+    }
+    return gemm_bf16_persist_launch<BfCfg<1, 1>, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
+}
+
+template <class AL, class Epi>
+static hipError_t gemm_big(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc,
+                           int M, int N, int K, hipStream_t s) {
+    using Cfg = PipeD;
+    if (h && h->precision == EGOTAP_PREC_BF16X3) {
+        static const std::string kname3 = std::string("gemm_bf16_persist_kernel<256x256x16,bf16x3,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
+        GemmTimer t(h, s, role, kname3.c_str(), 2.0 * M * N * K);
+        return gemm_bf16_persist_launch<BfCfg<3, 1>, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
+    }
+    if (h && h->precision == EGOTAP_PREC_BF16) {
+        static const std::string kname1 = std::string("gemm_bf16_persist_kernel<256x256x32,bf16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
+        GemmTimer t(h, s, role, kname1.c_str(), 2.0 * M * N * K);
+        return gemm_bf16_plain(h, al, W, epi, C, ldc, M, N, K, s);
+    }
+    if constexpr (AL::HAS_PTR) {
+        // loaders that are pure address math: same tile, same k order (bit-identical), slabs staged global -> LDS by DMA (gemm_f32_dma.h)
+        if (N % DmaF32Cfg::BN == 0 && K % DmaF32Cfg::BK == 0 && W.seg % DmaF32Cfg::BN == 0 && W.ld % 4 == 0 && al.dma_ok()) {
+            static const std::string kdma = std::string("gemm_f32_dma_kernel<256x256x16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
+            GemmTimer t(h, s, role, kdma.c_str(), 2.0 * M * N * K);
+            return gemm_f32_dma_launch(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
+        }
+    }
+    static const std::string kname = std::string("gemm_f32_persist_kernel<256x256x16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
+    GemmTimer t(h, s, role, kname.c_str(), 2.0 * M * N * K);
+    return gemm_f32_persist_launch<Cfg, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
+}
+
+// ------------------------------------------------------------------------------------------------ workspace
+// asks the device once how many workgroups of the one-launch PU chain it keeps resident (pu_chain.h)
+static void pu_chain_probe(Handle* h) {
+    // A chain launch of an EARLIER call whose row blocks were not co-resident (shared device) was redone on the device by
+    // pu_solo_kernel -- the results were right, but it cost a ~0.1 s stall: from now on this handle walks the steps with the per-step
+    // kernels (same bits).  Read without synchronising: the word is host memory the device writes through.
+    if (h->pu_fault_host && __atomic_load_n(h->pu_fault_host, __ATOMIC_RELAXED) != 0u) {
+        __atomic_store_n(h->pu_fault_host, 0u, __ATOMIC_RELAXED);
+        h->pu_faults++;
+        h->pu_chain = false;
+    }
+    if (!h->pu_chain) { h->pu_resident[0] = h->pu_resident[1] = 0; return; }      // 0 resident workgroups: pu_chain_launch declines
+    if (!h->pu_fault_host) {           // once per handle, at its first forward (never inside a stream capture: wrappers run eagerly first)
+        void* hp = nullptr; void* dp = nullptr;
+        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+            h->pu_fault_host = (unsigned*)hp; h->pu_fault_dev = (unsigned*)dp;
+            *h->pu_fault_host = 0u;
+        } else {
+            if (hp) (void)hipHostFree(hp);
+            (void)hipGetLastError();
+        }
+    }
+    if (h->pu_resident[0] <= 0) {
+        h->pu_resident[0] = pu_chain_resident<1>();
+        h->pu_resident[1] = pu_chain_resident<2>();
+    }
+}
+static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+enum { TE_NONE = 0, TE_BIAS = 1, TE_BIAS_RES = 2, TE_BIAS_GELU_SAVE = 3, TE_ACCUM = 4, TE_GELU_GRAD = 5, TE_PATCH = 6, TE_SCATTER_PATCH = 7, TE_SCATTER_ROT = 8 };
+#endif
+
+// ================================================================================================ parts 0 and 2: the fp32-tensor convolution routing (estimator forward and training)
+#if EGOTAP_IN(0) || EGOTAP_IN(2)
+//                      taps stride log2W CO_T WCO WPX CI_S
+using C3s1_128_co64 = ConvCfg<9, 1, 7,  64, 2, 4, 8>;    // 128-wide maps: 512x512 RGB (BASELINE config 5)
+using C3s1_128      = ConvCfg<9, 1, 7, 128, 2, 4, 8>;
+using C3s2_64       = ConvCfg<9, 2, 6,  64, 2, 4, 8>;
+using C1s1_128      = ConvCfg<1, 1, 7,  64, 2, 4, 32>;
+using C1s2_64       = ConvCfg<1, 2, 6,  64, 2, 4, 8>;
+using C3s1_64_co64  = ConvCfg<9, 1, 6,  64, 2, 4, 8>;
+using C3s1_64       = ConvCfg<9, 1, 6, 128, 2, 4, 8>;
+using C3s1_32       = ConvCfg<9, 1, 5, 128, 2, 4, 8>;
+using C3s1_16       = ConvCfg<9, 1, 4, 128, 2, 4, 8>;
+using C3s1_8        = ConvCfg<9, 1, 3, 128, 2, 4, 8>;
+using C3s1_16_co64  = ConvCfg<9, 1, 4,  64, 2, 4, 8>;    // [r3] the same two widths with 64-channel tiles: twice the workgroups where 128-channel
+using C3s1_8_co64   = ConvCfg<9, 1, 3,  64, 2, 4, 8>;    // tiles leave CUs without one (training batches, serving batches); same bits (k order unchanged)
+using C3s2_32       = ConvCfg<9, 2, 5,  64, 2, 4, 8>;
+using C3s2_16       = ConvCfg<9, 2, 4,  64, 2, 4, 8>;
+using C3s2_8        = ConvCfg<9, 2, 3,  64, 2, 4, 8>;
+using C1s1_64       = ConvCfg<1, 1, 6,  64, 2, 4, 32>;
+using C1s1_32       = ConvCfg<1, 1, 5, 128, 2, 4, 32>;
+using C1s1_16       = ConvCfg<1, 1, 4, 128, 2, 4, 32>;
+using C1s1_8        = ConvCfg<1, 1, 3, 128, 2, 4, 32>;
+using C1s2_32       = ConvCfg<1, 2, 5,  64, 2, 4, 8>;
+using C1s2_16       = ConvCfg<1, 2, 4,  64, 2, 4, 8>;
+using C1s2_8        = ConvCfg<1, 2, 3,  64, 2, 4, 8>;
+
+template <class Cfg>
+static hipError_t conv(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
+    static const std::string kname = std::string("conv_f32_kernel<") + (Cfg::TAPS == 9 ? "3x3" : "1x1") + ",s" +
+                                     std::to_string(Cfg::STRIDE) + ",W" + std::to_string(Cfg::W) + ",co" +
+                                     std::to_string(Cfg::CO_T) + ">";
+    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * Cfg::TAPS * (double)a.Nimg * Cfg::W * Cfg::W);
+    ConvArgs b = a;
+    b.part = h->conv_part;
+    b.part_floats = h->conv_part_floats;
+    return conv_f32_launch<Cfg>(b, s, device_cu_count());
+}
+
+// any other output width (conv_f32_any_kernel: pixel tiles over the flattened (image, y, x) map)
+template <int TAPS, int STRIDE, int CO_T, int PX_T>
+static hipError_t conv_gen(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
+    using Cfg = ConvAnyCfg<TAPS, STRIDE, CO_T, PX_T>;
+    static const std::string kname = std::string("conv_f32_any_kernel<") + (TAPS == 9 ? "3x3" : "1x1") + ",s" + std::to_string(STRIDE) +
+                                     ",co" + std::to_string(CO_T) + ",px" + std::to_string(PX_T) + ">";
+    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * TAPS * (double)a.Nimg * wout * wout);
+    return conv_f32_any_launch<Cfg>(a, wout, s);
+}
+// tile shape by grid size: 128 x 256 (64 x 256 for Cout <= 64) while that fills the CUs, then 64 x 256, then 64 x 64 (same bits: same k order)
+template <int TAPS, int STRIDE>
+static hipError_t conv_gen_co(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
+    const long t256 = ((long)a.Nimg * wout * wout + 255) / 256, cus = device_cu_count();
+    if (a.Cout > 64 && t256 * ((a.Cout + 127) / 128) >= cus) return conv_gen<TAPS, STRIDE, 128, 256>(h, role, wout, a, s);
+    if (t256 * ((a.Cout + 63) / 64) >= cus) return conv_gen<TAPS, STRIDE, 64, 256>(h, role, wout, a, s);
+    return conv_gen<TAPS, STRIDE, 64, 64>(h, role, wout, a, s);
+}
+
+template <class Cfg>
+static hipError_t conv_bf(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
+    static const std::string kname = std::string("conv_bf16_kernel<3x3,s1,W") + std::to_string(Cfg::W) + (Cfg::NP == 3 ? ",bf16x3>" : ",bf16>");
+    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * 9 * (double)a.Nimg * Cfg::W * Cfg::W);
+    return conv_bf16_launch<Cfg>(a, h->conv_pack, s);
+}
+
+// dispatch on (taps, stride, output width): the power-of-two instantiations at wout in {128, 64, 32, 16, 8} (where they exist), every
+// other width >= 1 on conv_f32_any_kernel (exact fp32 in every precision mode)
+static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, int wout, const ConvArgs& a, hipStream_t s) {
+    // opt-in modes: 3x3 stride-1 convs with a multiple of 128 output channels at widths 64 / 32 / 16 run on the bf16 matrix cores
+    if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout >= 128) {
+        const bool x3 = h->precision == EGOTAP_PREC_BF16X3;
+        if (wout == 64) return x3 ? conv_bf<ConvBfCfg<6, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<6, 1>>(h, role, a, s);
+        if (wout == 32) return x3 ? conv_bf<ConvBfCfg<5, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<5, 1>>(h, role, a, s);
+        if (wout == 16) return x3 ? conv_bf<ConvBfCfg<4, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<4, 1>>(h, role, a, s);
+        if (wout == 8) return x3 ? conv_bf<ConvBfCfg<3, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<3, 1>>(h, role, a, s);
+    }
+    if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout == 64 && wout == 64)   // ResNet layer1
+        return h->precision == EGOTAP_PREC_BF16X3 ? conv_bf<ConvBfCfg<6, 3, 64>>(h, role, a, s) : conv_bf<ConvBfCfg<6, 1, 64>>(h, role, a, s);
+    if (h->precision == EGOTAP_PREC_BF16 && h->conv_pack && taps == 9 && stride == 1 && a.Cout == 64 && wout == 128)   // layer1 at 512x512 RGB
+        return conv_bf<ConvBfCfg<7, 1, 64>>(h, role, a, s);
+    if (taps == 9 && stride == 1) {
+        if (wout == 128) return a.Cout <= 64 ? conv<C3s1_128_co64>(h, role, a, s) : conv<C3s1_128>(h, role, a, s);
+        if (wout == 64) return a.Cout <= 64 ? conv<C3s1_64_co64>(h, role, a, s) : conv<C3s1_64>(h, role, a, s);
+        if (wout == 32) return conv<C3s1_32>(h, role, a, s);
+        // layer3 / layer4 at a 32-frame training batch: 128 / 64 workgroups of 128-channel tiles for 256 CUs (MFMA busy 0.21 on the 8 x 8 maps)
+        const long co128 = (a.Cout + 127) / 128;
+        if (wout == 16) return (long)a.Nimg * co128 < device_cu_count() ? conv<C3s1_16_co64>(h, role, a, s) : conv<C3s1_16>(h, role, a, s);
+        if (wout == 8) return (long)((a.Nimg + 3) / 4) * co128 < device_cu_count() ? conv<C3s1_8_co64>(h, role, a, s) : conv<C3s1_8>(h, role, a, s);
+    } else if (taps == 9 && stride == 2) {
+        if (wout == 64) return conv<C3s2_64>(h, role, a, s);
+        if (wout == 32) return conv<C3s2_32>(h, role, a, s);
+        if (wout == 16) return conv<C3s2_16>(h, role, a, s);
+        if (wout == 8) return conv<C3s2_8>(h, role, a, s);
+    } else if (taps == 1 && stride == 1) {
+        if (wout == 128) return conv<C1s1_128>(h, role, a, s);
+        if (wout == 64) return conv<C1s1_64>(h, role, a, s);
+        if (wout == 32) return conv<C1s1_32>(h, role, a, s);
+        if (wout == 16) return conv<C1s1_16>(h, role, a, s);
+        if (wout == 8) return conv<C1s1_8>(h, role, a, s);
+    } else if (taps == 1 && stride == 2) {
+        if (wout == 64) return conv<C1s2_64>(h, role, a, s);
+        if (wout == 32) return conv<C1s2_32>(h, role, a, s);
+        if (wout == 16) return conv<C1s2_16>(h, role, a, s);
+        if (wout == 8) return conv<C1s2_8>(h, role, a, s);
+    }
+    if (wout < 1) return hipErrorInvalidValue;
+    if (taps == 9 && stride == 1) return conv_gen_co<9, 1>(h, role, wout, a, s);
+    if (taps == 9 && stride == 2) return conv_gen_co<9, 2>(h, role, wout, a, s);
+    if (taps == 1 && stride == 1) return conv_gen_co<1, 1>(h, role, wout, a, s);
+    if (taps == 1 && stride == 2) return conv_gen_co<1, 2>(h, role, wout, a, s);
+    return hipErrorInvalidValue;
+}
+#endif
+
+// ================================================================================================ parts 0 and 3: fc1 of the encoders on the bf16-storage GEMMs
+#if EGOTAP_IN(0) || EGOTAP_IN(3)
+// fc1 of an encoder (rows gathered from the ViT tokens / the limb heatmaps) as an NT product: [r5] on the 64-deep kernel where its shape rules hold
+// (D, HW multiples of 64: a K-tile inside one token / map), the 32-deep kernel otherwise or when egotap_debug_gemm_bk pins it; same k order per
+// output element: same bits
+template <class Epi>
+static hipError_t fc1_nt(Handle* h, int which, const __bf16* src, const __bf16* w, long K, const Epi& ep, int BT, int cus, hipStream_t s) {
+    const int HW = h->cfg.hm_size * h->cfg.hm_size;
+    const bool deep = g_gemm_bf16s_bk != 32 && K % 64 == 0 && K >= 128 && (which == 0 ? h->D % 64 == 0 : HW % 64 == 0) && (long)256 * K * 2 < (1L << 31);
+    if (which == 0) {
+        // [r5] tensors under 4 GB (every shipped batch): scalar origin + 32-bit lane offsets (X64TokensS / X64RotS); the pointer loaders otherwise
+        const size_t tok_bytes = (size_t)(BT / h->T) * h->seq * h->D * 2;
+        if (deep && g_conv_addressing == 0 && tok_bytes < ((size_t)1 << 32) - 4096)
+            return gemm_bf16s64_launch_x(X64TokensS{src, 0u, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
+        if (deep) return gemm_bf16s64_launch_x(X64Tokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
+        return gemm_bf16s_launch(XTokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
+    }
+    const size_t hm_bytes = (size_t)(BT / (2 * h->J)) * h->C * HW * 2;
+    if (deep && g_conv_addressing == 0 && hm_bytes < ((size_t)1 << 32) - 4096) return gemm_bf16s64_launch_x(X64RotS{src, 0u, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
+    if (deep) return gemm_bf16s64_launch_x(X64Rot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
+    return gemm_bf16s_launch(XRot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
+}
+#endif
+
+// ================================================================================================ one part each, in the order 0 (core and inference), 1, 2, 3, 0 (the one-call training step)
+#if EGOTAP_IN(0)
+// ------------------------------------------------------------------------------------------------ errors
+static thread_local char g_err[1024] = "";
+void egotap_set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+hipError_t ego_allow_dynamic_lds(const void* kernel, int bytes) {
+    static LdsOptIn seen;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    return seen.ensure(kernel, dev, bytes, [kernel](int b) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, b); });
+}
+extern "C" const char* egotap_last_error(void) { return g_err; }
+extern "C" int egotap_abi_version(void) { return EGOTAP_ABI_VERSION; }
+
+extern "C" const char* egotap_gemm_tile_name(int tile) {
+    switch (tile) {
+        case 0: case 1: return "128x128x32/4w";
+        case 2: return "256x128x32/8w";
+        case 3: return "128x256x32/8w";
+        case 4: return "256x256x16/8w";
+        case 5: return "256x128x16/4w";
+        case 6: return "64x64x32/4w";
+        case 7: return "256x128x32/4w";
+        case 8: return "pipe128x128x16/4w";
+        case 9: return "pipe128x128x32/4w";
+        case 10: return "pipe256x128x16/8w";
+        case 11: return "pipe256x256x16/8w";
+        case 12: return "persist256x256x16/8w";
+        case 13: return "persist256x256x16/8w/bf16x3";
+        case 14: return "persist256x256x32/8w/bf16";
+        case 15: return "persist256x256x16/8w/bf16x3/interleaved";
+        case 16: return "persist256x256x32/8w/bf16/interleaved";
+        case 19: return "dma256x256x16/8w (exact fp32, LDS-DMA staging)";
+        default: return nullptr;
+    }
+}
 // the handle whose timing hook was enabled last: where the operators that take no handle (ocam.h) record their launches; cleared when that handle's hook is
 // switched off or the handle is destroyed
 [[maybe_unused]] static Handle* g_timing_handle = nullptr;
@@ -291,7 +712,6 @@ static bool frozen_key(int net, const char* key) {
     return k.compare(0, bb.size() + 6, bb + "conv1.") != 0 && k.compare(0, bb.size() + 4, bb + "bn1.") != 0;
 }
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_create(const egotap_config* cfg, egotap_handle* out) {
     EGO_CHECK(cfg && out, "egotap_create: null argument");
     EGO_CHECK(cfg->struct_bytes == (int32_t)sizeof(egotap_config), "egotap_create: egotap_config is %d bytes, library expects %d",
@@ -324,9 +744,7 @@ extern "C" int egotap_create(const egotap_config* cfg, egotap_handle* out) {
     *out = h;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" void egotap_destroy(egotap_handle h) {
     if (!h) return;
     if (g_timing_handle == h) g_timing_handle = nullptr;
@@ -334,9 +752,7 @@ extern "C" void egotap_destroy(egotap_handle h) {
     if (h->pu_fault_host) (void)hipHostFree(h->pu_fault_host);
     delete h;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_bind_param(egotap_handle h, int net, const char* key, void* dev_ptr, int64_t numel, int dtype) {
     EGO_CHECK(h && key, "egotap_bind_param: null argument");
     EGO_CHECK(net >= 0 && net < EGOTAP_NET_COUNT, "egotap_bind_param: bad net id %d", net);
@@ -363,9 +779,7 @@ extern "C" int egotap_bind_param(egotap_handle h, int net, const char* key, void
     else h->hm_resolved[net] = false;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_unbound_count(egotap_handle h, int net, int* count) {
     EGO_CHECK(h && count, "egotap_unbound_count: null argument");
     EGO_CHECK(net >= 0 && net < EGOTAP_NET_COUNT, "bad net id %d", net);
@@ -375,79 +789,9 @@ extern "C" int egotap_unbound_count(egotap_handle h, int net, int* count) {
     *count = n;
     return EGOTAP_OK;
 }
-#endif
-
-typedef std::unordered_map<std::string, Param> ParamMap;
-static const float* P(Handle*, const ParamMap& m, const std::string& key, bool& ok) {
-    auto it = m.find(key);
-    if (it == m.end()) {
-        if (ok) egotap_set_error("'%s' is not bound", key.c_str());
-        ok = false;
-        return nullptr;
-    }
-    return (const float*)it->second.ptr;
-}
 static const float* P(Handle* h, int net, const std::string& key, bool& ok) { return P(h, h->bound[net], key, ok); }
 
-// fills a LiftParams from a key -> pointer map: the parameters (with_stats: and the BatchNorm running statistics) or their gradients
-static int lift_resolve_into(Handle* h, const ParamMap& N, LiftParams& p, bool with_stats) {
-    bool ok = true;
-    const std::string v = "pos_heatmap_encoder.vit.";
-    p.mask_tok = P(h, N, v + "embeddings.mask_token", ok);
-    p.pos_emb = P(h, N, v + "embeddings.position_embeddings", ok);
-    p.patch_w = P(h, N, v + "embeddings.patch_embeddings.projection.weight", ok);
-    p.patch_b = P(h, N, v + "embeddings.patch_embeddings.projection.bias", ok);
-    for (int i = 0; i < h->cfg.vit_layers; ++i) {
-        const std::string l = v + "encoder.layer." + std::to_string(i) + ".";
-        auto& L = p.layer[i];
-        L.q_w = P(h, N, l + "attention.attention.query.weight", ok); L.q_b = P(h, N, l + "attention.attention.query.bias", ok);
-        L.k_w = P(h, N, l + "attention.attention.key.weight", ok);   L.k_b = P(h, N, l + "attention.attention.key.bias", ok);
-        L.v_w = P(h, N, l + "attention.attention.value.weight", ok); L.v_b = P(h, N, l + "attention.attention.value.bias", ok);
-        L.o_w = P(h, N, l + "attention.output.dense.weight", ok);    L.o_b = P(h, N, l + "attention.output.dense.bias", ok);
-        L.up_w = P(h, N, l + "intermediate.dense.weight", ok);       L.up_b = P(h, N, l + "intermediate.dense.bias", ok);
-        L.dn_w = P(h, N, l + "output.dense.weight", ok);             L.dn_b = P(h, N, l + "output.dense.bias", ok);
-        L.ln1_g = P(h, N, l + "layernorm_before.weight", ok);        L.ln1_b = P(h, N, l + "layernorm_before.bias", ok);
-        L.ln2_g = P(h, N, l + "layernorm_after.weight", ok);         L.ln2_b = P(h, N, l + "layernorm_after.bias", ok);
-    }
-    p.lnf_g = P(h, N, v + "layernorm.weight", ok);
-    p.lnf_b = P(h, N, v + "layernorm.bias", ok);
-    const char* encs[2] = {"pos_heatmap_encoder", "rot_heatmap_encoder"};
-    for (int e = 0; e < 2; ++e)
-        for (int i = 0; i < 3; ++i) {
-            const std::string f = std::string(encs[e]) + ".fc" + std::to_string(i + 1);
-            LiftParams::Fc& fc = e == 0 ? p.pos_fc[i] : p.rot_fc[i];
-            fc.w = P(h, N, f + ".fc.weight", ok);        fc.b = P(h, N, f + ".fc.bias", ok);
-            fc.g = P(h, N, f + ".bn.weight", ok);        fc.beta = P(h, N, f + ".bn.bias", ok);
-            fc.mean = fc.var = nullptr;
-            if (with_stats) { fc.mean = P(h, N, f + ".bn.running_mean", ok); fc.var = P(h, N, f + ".bn.running_var", ok); }
-        }
-    const std::string c = "skel_sequential_layer.lstm_custom.layers.";
-    p.x2f0_w = P(h, N, c + "0.x2f.weight", ok); p.x2f0_b = P(h, N, c + "0.x2f.bias", ok);
-    p.x2h0_w = P(h, N, c + "0.x2h.weight", ok); p.x2h0_b = P(h, N, c + "0.x2h.bias", ok);
-    p.b2h0_w = P(h, N, c + "0.b2h.weight", ok); p.b2h0_b = P(h, N, c + "0.b2h.bias", ok);
-    p.h2h0_w = P(h, N, c + "0.h2h.weight", ok); p.h2h0_b = P(h, N, c + "0.h2h.bias", ok);
-    p.x2f1_w = P(h, N, c + "1.x2f.weight", ok); p.x2f1_b = P(h, N, c + "1.x2f.bias", ok);
-    p.x2h1_w = P(h, N, c + "1.x2h.weight", ok); p.x2h1_b = P(h, N, c + "1.x2h.bias", ok);
-    p.h2h1_w = P(h, N, c + "1.h2h.weight", ok); p.h2h1_b = P(h, N, c + "1.h2h.bias", ok);
-    p.pose_w = P(h, N, "pose_mlp.pose_fcs.0.weight", ok); p.pose_b = P(h, N, "pose_mlp.pose_fcs.0.bias", ok);
-    p.glob_w = p.glob_b = nullptr;
-    if (h->cfg.estimate_head) {
-        p.glob_w = P(h, N, "global_mlp.pose_fcs.0.weight", ok);
-        p.glob_b = P(h, N, "global_mlp.pose_fcs.0.bias", ok);
-    }
-    return ok ? EGOTAP_OK : EGOTAP_ERR_UNBOUND;
-}
-
-static int lift_resolve(Handle* h) {
-    if (h->lift_resolved) return EGOTAP_OK;
-    const int rc = lift_resolve_into(h, h->bound[EGOTAP_NET_LIFT], h->lp, true);
-    if (rc != EGOTAP_OK) return rc;
-    h->lift_resolved = true;
-    return EGOTAP_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ timing
-#if EGOTAP_IN(0)
 extern "C" int egotap_timing_enable(egotap_handle h, int enable) {
     EGO_CHECK(h, "null handle");
     h->timing = enable != 0;
@@ -455,8 +799,6 @@ extern "C" int egotap_timing_enable(egotap_handle h, int enable) {
     else if (g_timing_handle == h) g_timing_handle = nullptr;
     return EGOTAP_OK;
 }
-#endif
-#if EGOTAP_IN(0)
 extern "C" int egotap_timing_read(egotap_handle h, int* launches, double* total_ms, double* total_flops) {
     EGO_CHECK(h && launches && total_ms && total_flops, "null argument");
     struct Agg { std::string role, kernel; int n = 0; double ms = 0, flops = 0; };
@@ -491,162 +833,13 @@ extern "C" int egotap_timing_read(egotap_handle h, int* launches, double* total_
     h->rec.clear();
     return EGOTAP_OK;
 }
-#endif
-#if EGOTAP_IN(0)
 extern "C" const char* egotap_timing_detail(egotap_handle h) { return h ? h->detail.c_str() : ""; }
-#endif
-
-struct GemmTimer {   // brackets one GEMM launch when the handle's timing hook is on
-    Handle* h;
-    hipStream_t s;
-    bool on;
-    GemmTimer(Handle* h_, hipStream_t s_, const char* role, const char* kernel, double flops)
-        : h(h_), s(s_), on(h_ && h_->timing) {
-        if (!on) return;
-        if (h->ev_used + 2 > h->ev.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-            h->ev.push_back(a);
-            h->ev.push_back(b);
-        }
-        (void)hipEventRecord(h->ev[h->ev_used], s);
-        h->rec.push_back({role, kernel, flops});
-    }
-    ~GemmTimer() {
-        if (!on) return;
-        (void)hipEventRecord(h->ev[h->ev_used + 1], s);
-        h->ev_used += 2;
-    }
-};
-
-template <class AL> struct AlName;
-template <> struct AlName<ALoadPlain> { static constexpr const char* v = "ALoadPlain"; };
-template <> struct AlName<ALoadPatch> { static constexpr const char* v = "ALoadPatch"; };
-template <> struct AlName<ALoadTokens> { static constexpr const char* v = "ALoadTokens"; };
-template <> struct AlName<ALoadLive> { static constexpr const char* v = "ALoadLive"; };
-template <> struct AlName<ALoadHead> { static constexpr const char* v = "ALoadHead"; };
-template <> struct AlName<ALoadRot> { static constexpr const char* v = "ALoadRot"; };
-template <> struct AlName<ALoadStereo> { static constexpr const char* v = "ALoadStereo"; };
-template <> struct AlName<ALoadStereoGated> { static constexpr const char* v = "ALoadStereoGated"; };
-template <class E> struct EpiName;
-template <> struct EpiName<EpiBias> { static constexpr const char* v = "EpiBias"; };
-template <> struct EpiName<EpiBiasRes> { static constexpr const char* v = "EpiBiasRes"; };
-template <> struct EpiName<EpiBiasResLive> { static constexpr const char* v = "EpiBiasResLive"; };
-template <> struct EpiName<EpiBiasHead> { static constexpr const char* v = "EpiBiasHead"; };
-template <> struct EpiName<EpiBiasGelu> { static constexpr const char* v = "EpiBiasGelu"; };
-template <> struct EpiName<EpiBnLrelu> { static constexpr const char* v = "EpiBnLrelu"; };
-template <> struct EpiName<EpiPatch> { static constexpr const char* v = "EpiPatch"; };
-
-template <class Cfg, class AL, class Epi>
-static hipError_t gemm(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc,
-                       int M, int N, int K, hipStream_t s) {
-    static const std::string kname = std::string("gemm_f32_kernel<") + std::to_string(Cfg::BM) + "x" +
-                                     std::to_string(Cfg::BN) + "x" + std::to_string(Cfg::BK) + "," + AlName<AL>::v + "," +
-                                     EpiName<Epi>::v + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * M * N * K);
-    return gemm_f32_launch<Cfg, AL, Epi>(al, W, epi, C, ldc, M, N, K, s);
-}
-
-// large GEMMs (ViT projections, fc1): 256x256 tile, 3-stage pipelined kernel -- fewest global-load
-// instructions per MFMA (each costs the matrix pipe ~56 cycles, tools/mfma_probe.hip), DESIGN.md section 4
-static int device_cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
-// stream-ordered zero fill as a KERNEL: a hipMemsetAsync captured into a HIP graph did not re-execute on replay (ROCm 7.2: the
-// propagation units' cell state then carried over from one replay to the next), a kernel node does
-static __global__ __launch_bounds__(256) void zero_fill_kernel(f32x4* __restrict__ p, long n16) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n16) p[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-static hipError_t zero_fill(void* p, size_t bytes, hipStream_t s) {       // p 16-byte aligned, bytes a multiple of 16
-    if (bytes == 0) return hipSuccess;
-    if ((((uintptr_t)p) | bytes) & 15) return hipErrorInvalidValue;
-    const long n16 = (long)(bytes / 16);
-    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (f32x4*)p, n16);
-    return hipGetLastError();
-}
 
 // out[0:n | n:2n | 2n:3n] = a | b | c  (the fused q|k|v bias of the bf16-storage forward)
 static __global__ __launch_bounds__(256) void concat3_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c,
                                                              float* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { out[i] = a[i]; out[n + i] = b[i]; out[2 * n + i] = c[i]; }
-}
-
-// rows of an fp32 matrix (row stride lda) -> dense bf16 [M, K]
-static __global__ __launch_bounds__(256) void f32_to_bf16_rows_kernel(const float* __restrict__ src, long lda, __bf16* __restrict__ dst, int k8, long n8) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n8) return;
-    const long row = i / k8;
-    const float* p = src + row * lda + (i - row * k8) * 8;
-    *(bf16x8*)(dst + i * 8) = bf16_round8(*(const f32x4*)p, *(const f32x4*)(p + 4));
-}
-// plain-bf16 GEMM: W rounded to bf16 into the handle's scratch right before the launch (stream ordered), so the W operand costs
-// half the vector-memory bytes; without a scratch (or if it is too small) the kernel converts fp32 weights on the fly.
-// A plain row-major activation operand is rounded to bf16 the same way (egotap_set_act_scratch; skipped when the scratch is
-// absent or too small) and the product runs on the
-// LDS-DMA kernel (gemm_bf16_dma.h): same rounding of both operands, same fp32 accumulation order per output element.
-template <class AL, class Epi>
-static hipError_t gemm_bf16_plain(Handle* h, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc, int M, int N, int K, hipStream_t s) {
-    const int nseg = N / W.seg;
-    if (h && h->wscratch && (size_t)N * K * 2 <= h->wscratch_bytes && K % 8 == 0 && W.ld == K && nseg >= 1 && nseg <= 3 && nseg * W.seg == N) {
-        SegMatB B;
-        for (int i = 0; i < 3; ++i) B.p[i] = h->wscratch + (size_t)(i < nseg ? i : 0) * W.seg * K;
-        B.seg = W.seg; B.ld = K;
-        const long n8 = (long)W.seg * K / 8;
-        for (int i = 0; i < nseg; ++i)
-            hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, W.p[i], h->wscratch + (size_t)i * W.seg * K, n8);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if constexpr (std::is_same<AL, ALoadPlain>::value) {
-            if (K % DmaCfg::BK == 0 && N % DmaCfg::BN == 0 && W.seg % DmaCfg::BN == 0 && al.lda % 4 == 0 && M >= 1024) {
-                __bf16* a = (size_t)M * K * 2 <= h->ascratch_bytes ? h->ascratch : nullptr;
-                if (a) {
-                    const long a8 = (long)M * K / 8;
-                    hipLaunchKernelGGL(f32_to_bf16_rows_kernel, dim3((unsigned)((a8 + 255) / 256)), dim3(256), 0, s, al.A, al.lda, a, K / 8, a8);
-                    e = hipGetLastError();
-                    if (e != hipSuccess) return e;
-                    return gemm_bf16_dma_launch(a, (long)K, B, epi, C, ldc, M, N, K, device_cu_count(), s);
-                }
-            }
-        }
-        return gemm_bf16_persist_launch<BfCfg<1, 1>, AL, Epi, SegMatB>(al, B, epi, C, ldc, M, N, K, device_cu_count(), s);
-    }
-    return gemm_bf16_persist_launch<BfCfg<1, 1>, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-}
-
-template <class AL, class Epi>
-static hipError_t gemm_big(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc,
-                           int M, int N, int K, hipStream_t s) {
-    using Cfg = PipeD;
-    if (h && h->precision == EGOTAP_PREC_BF16X3) {
-        static const std::string kname3 = std::string("gemm_bf16_persist_kernel<256x256x16,bf16x3,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-        GemmTimer t(h, s, role, kname3.c_str(), 2.0 * M * N * K);
-        return gemm_bf16_persist_launch<BfCfg<3, 1>, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-    }
-    if (h && h->precision == EGOTAP_PREC_BF16) {
-        static const std::string kname1 = std::string("gemm_bf16_persist_kernel<256x256x32,bf16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-        GemmTimer t(h, s, role, kname1.c_str(), 2.0 * M * N * K);
-        return gemm_bf16_plain(h, al, W, epi, C, ldc, M, N, K, s);
-    }
-    if constexpr (AL::HAS_PTR) {
-        // loaders that are pure address math: same tile, same k order (bit-identical), slabs staged global -> LDS by DMA (gemm_f32_dma.h)
-        if (N % DmaF32Cfg::BN == 0 && K % DmaF32Cfg::BK == 0 && W.seg % DmaF32Cfg::BN == 0 && W.ld % 4 == 0 && al.dma_ok()) {
-            static const std::string kdma = std::string("gemm_f32_dma_kernel<256x256x16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-            GemmTimer t(h, s, role, kdma.c_str(), 2.0 * M * N * K);
-            return gemm_f32_dma_launch(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-        }
-    }
-    static const std::string kname = std::string("gemm_f32_persist_kernel<256x256x16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * M * N * K);
-    return gemm_f32_persist_launch<Cfg, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
 }
 
 // Small batches (serving): the 256x256 persistent tiling leaves most CUs idle (B = 1: 12 tiles for attn_out / mlp_down, one
@@ -754,38 +947,9 @@ static hipError_t fc_gemm(Handle* h, const char* role, const AL& al, const SegMa
     return gemm_f32_splitk_launch<TileA>(al, W, epi, C, ldc, P, SPLITK_FLOATS, M, N, K, s);
 }
 
-// ------------------------------------------------------------------------------------------------ workspace
-// asks the device once how many workgroups of the one-launch PU chain it keeps resident (pu_chain.h)
-static void pu_chain_probe(Handle* h) {
-    // A chain launch of an EARLIER call whose row blocks were not co-resident (shared device) was redone on the device by
-    // pu_solo_kernel -- the results were right, but it cost a ~0.1 s stall: from now on this handle walks the steps with the per-step
-    // kernels (same bits).  Read without synchronising: the word is host memory the device writes through.
-    if (h->pu_fault_host && __atomic_load_n(h->pu_fault_host, __ATOMIC_RELAXED) != 0u) {
-        __atomic_store_n(h->pu_fault_host, 0u, __ATOMIC_RELAXED);
-        h->pu_faults++;
-        h->pu_chain = false;
-    }
-    if (!h->pu_chain) { h->pu_resident[0] = h->pu_resident[1] = 0; return; }      // 0 resident workgroups: pu_chain_launch declines
-    if (!h->pu_fault_host) {           // once per handle, at its first forward (never inside a stream capture: wrappers run eagerly first)
-        void* hp = nullptr; void* dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            h->pu_fault_host = (unsigned*)hp; h->pu_fault_dev = (unsigned*)dp;
-            *h->pu_fault_host = 0u;
-        } else {
-            if (hp) (void)hipHostFree(hp);
-            (void)hipGetLastError();
-        }
-    }
-    if (h->pu_resident[0] <= 0) {
-        h->pu_resident[0] = pu_chain_resident<1>();
-        h->pu_resident[1] = pu_chain_resident<2>();
-    }
-}
-
 struct LiftWs {
     size_t X, Y, QKV, CTX, HID, Z1, Z2, POSZ, ROTZ, F0, G0, HS0, F1, G1, HS1, C0, C1, ZERO, HPA, HPB, FAULT, SPLITK, total;
 };
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 static LiftWs lift_ws(const Handle* h, int B) {
     LiftWs w;
     const size_t M = (size_t)B * h->seq, D = h->D, BT = (size_t)B * h->T, JB = (size_t)h->J * B, H = h->H;
@@ -804,16 +968,13 @@ static LiftWs lift_ws(const Handle* h, int B) {
     return w;
 }
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_lift_workspace_bytes(egotap_handle h, int B, size_t* bytes) {
     EGO_CHECK(h && bytes, "null argument");
     EGO_CHECK(B >= 0, "negative batch");
     *bytes = lift_ws(h, B > 0 ? B : 1).total;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_lift_intermediate(egotap_handle h, int B, const char* name, size_t* offset, int64_t* numel) {
     EGO_CHECK(h && name && offset && numel, "null argument");
     const LiftWs w = lift_ws(h, B > 0 ? B : 1);
@@ -826,9 +987,7 @@ extern "C" int egotap_lift_intermediate(egotap_handle h, int B, const char* name
     else { egotap_set_error("unknown intermediate '%s'", name); return EGOTAP_ERR_INVALID; }
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_set_pu_chain(egotap_handle h, int enable) {
     EGO_CHECK(h, "null handle");
     h->pu_chain = enable != 0;
@@ -861,9 +1020,7 @@ extern "C" int egotap_set_precision(egotap_handle h, int mode) {
     for (int n = 0; n < EGOTAP_NET_COUNT; ++n) h->hm_arena[n] = nullptr;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_set_weight_scratch(egotap_handle h, void* buf, size_t bytes) {
     EGO_CHECK(h, "null handle");
     EGO_CHECK(((uintptr_t)buf & 15) == 0, "egotap_set_weight_scratch: 16-byte alignment");
@@ -871,9 +1028,7 @@ extern "C" int egotap_set_weight_scratch(egotap_handle h, void* buf, size_t byte
     h->wscratch_bytes = buf ? bytes : 0;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_set_act_scratch(egotap_handle h, void* buf, size_t bytes) {
     EGO_CHECK(h, "null handle");
     EGO_CHECK(((uintptr_t)buf & 15) == 0, "egotap_set_act_scratch: 16-byte alignment");
@@ -881,35 +1036,11 @@ extern "C" int egotap_set_act_scratch(egotap_handle h, void* buf, size_t bytes) 
     h->ascratch_bytes = buf ? bytes : 0;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_lift_debug_stop(egotap_handle h, int stage) {
     EGO_CHECK(h, "null handle");
     h->debug_stop = stage;   // 0: full forward; 1: after embeddings; 2+i: after ViT layer i  ("x" holds the state)
     return EGOTAP_OK;
-}
-#endif
-
-// fc1 of an encoder (rows gathered from the ViT tokens / the limb heatmaps) as an NT product: [r5] on the 64-deep kernel where its shape rules hold
-// (D, HW multiples of 64: a K-tile inside one token / map), the 32-deep kernel otherwise or when egotap_debug_gemm_bk pins it; same k order per
-// output element: same bits
-template <class Epi>
-static hipError_t fc1_nt(Handle* h, int which, const __bf16* src, const __bf16* w, long K, const Epi& ep, int BT, int cus, hipStream_t s) {
-    const int HW = h->cfg.hm_size * h->cfg.hm_size;
-    const bool deep = g_gemm_bf16s_bk != 32 && K % 64 == 0 && K >= 128 && (which == 0 ? h->D % 64 == 0 : HW % 64 == 0) && (long)256 * K * 2 < (1L << 31);
-    if (which == 0) {
-        // [r5] tensors under 4 GB (every shipped batch): scalar origin + 32-bit lane offsets (X64TokensS / X64RotS); the pointer loaders otherwise
-        const size_t tok_bytes = (size_t)(BT / h->T) * h->seq * h->D * 2;
-        if (deep && g_conv_addressing == 0 && tok_bytes < ((size_t)1 << 32) - 4096)
-            return gemm_bf16s64_launch_x(X64TokensS{src, 0u, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
-        if (deep) return gemm_bf16s64_launch_x(X64Tokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
-        return gemm_bf16s_launch(XTokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
-    }
-    const size_t hm_bytes = (size_t)(BT / (2 * h->J)) * h->C * HW * 2;
-    if (deep && g_conv_addressing == 0 && hm_bytes < ((size_t)1 << 32) - 4096) return gemm_bf16s64_launch_x(X64RotS{src, 0u, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
-    if (deep) return gemm_bf16s64_launch_x(X64Rot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
-    return gemm_bf16s_launch(XRot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -920,7 +1051,6 @@ static hipError_t launch_ln(const float* x, float* y, const float* g, const floa
     return hipGetLastError();
 }
 
-#if EGOTAP_IN(0)
 // [r4] x = x + ctx W^T + bias, y = LayerNorm(x): at serving batches (the product is split over K) the reduce of the partials and the LayerNorm
 // that follows are ONE launch (splitk_reduce_res_ln_kernel: same bits as the two); otherwise gemm_small + launch_ln as before.
 static hipError_t gemm_res_ln(Handle* h, const char* role, const float* A, long lda, const float* Wp, const float* bias, float* X, int M, int D, int K,
@@ -1363,7 +1493,6 @@ extern "C" int egotap_lift_unfreeze(egotap_handle h) {
     h->lift_arena = nullptr;
     return EGOTAP_OK;
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------ heatmap estimator
 static int hm_resolve(Handle* h, int net) {
@@ -1402,115 +1531,6 @@ static int hm_resolve(Handle* h, int net) {
     if (!ok) return EGOTAP_ERR_UNBOUND;
     h->hm_resolved[net] = true;
     return EGOTAP_OK;
-}
-
-//                      taps stride log2W CO_T WCO WPX CI_S
-using C3s1_128_co64 = ConvCfg<9, 1, 7,  64, 2, 4, 8>;    // 128-wide maps: 512x512 RGB (BASELINE config 5)
-using C3s1_128      = ConvCfg<9, 1, 7, 128, 2, 4, 8>;
-using C3s2_64       = ConvCfg<9, 2, 6,  64, 2, 4, 8>;
-using C1s1_128      = ConvCfg<1, 1, 7,  64, 2, 4, 32>;
-using C1s2_64       = ConvCfg<1, 2, 6,  64, 2, 4, 8>;
-using C3s1_64_co64  = ConvCfg<9, 1, 6,  64, 2, 4, 8>;
-using C3s1_64       = ConvCfg<9, 1, 6, 128, 2, 4, 8>;
-using C3s1_32       = ConvCfg<9, 1, 5, 128, 2, 4, 8>;
-using C3s1_16       = ConvCfg<9, 1, 4, 128, 2, 4, 8>;
-using C3s1_8        = ConvCfg<9, 1, 3, 128, 2, 4, 8>;
-using C3s1_16_co64  = ConvCfg<9, 1, 4,  64, 2, 4, 8>;    // [r3] the same two widths with 64-channel tiles: twice the workgroups where 128-channel
-using C3s1_8_co64   = ConvCfg<9, 1, 3,  64, 2, 4, 8>;    // tiles leave CUs without one (training batches, serving batches); same bits (k order unchanged)
-using C3s2_32       = ConvCfg<9, 2, 5,  64, 2, 4, 8>;
-using C3s2_16       = ConvCfg<9, 2, 4,  64, 2, 4, 8>;
-using C3s2_8        = ConvCfg<9, 2, 3,  64, 2, 4, 8>;
-using C1s1_64       = ConvCfg<1, 1, 6,  64, 2, 4, 32>;
-using C1s1_32       = ConvCfg<1, 1, 5, 128, 2, 4, 32>;
-using C1s1_16       = ConvCfg<1, 1, 4, 128, 2, 4, 32>;
-using C1s1_8        = ConvCfg<1, 1, 3, 128, 2, 4, 32>;
-using C1s2_32       = ConvCfg<1, 2, 5,  64, 2, 4, 8>;
-using C1s2_16       = ConvCfg<1, 2, 4,  64, 2, 4, 8>;
-using C1s2_8        = ConvCfg<1, 2, 3,  64, 2, 4, 8>;
-
-template <class Cfg>
-static hipError_t conv(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
-    static const std::string kname = std::string("conv_f32_kernel<") + (Cfg::TAPS == 9 ? "3x3" : "1x1") + ",s" +
-                                     std::to_string(Cfg::STRIDE) + ",W" + std::to_string(Cfg::W) + ",co" +
-                                     std::to_string(Cfg::CO_T) + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * Cfg::TAPS * (double)a.Nimg * Cfg::W * Cfg::W);
-    ConvArgs b = a;
-    b.part = h->conv_part;
-    b.part_floats = h->conv_part_floats;
-    return conv_f32_launch<Cfg>(b, s, device_cu_count());
-}
-
-// any other output width (conv_f32_any_kernel: pixel tiles over the flattened (image, y, x) map)
-template <int TAPS, int STRIDE, int CO_T, int PX_T>
-static hipError_t conv_gen(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
-    using Cfg = ConvAnyCfg<TAPS, STRIDE, CO_T, PX_T>;
-    static const std::string kname = std::string("conv_f32_any_kernel<") + (TAPS == 9 ? "3x3" : "1x1") + ",s" + std::to_string(STRIDE) +
-                                     ",co" + std::to_string(CO_T) + ",px" + std::to_string(PX_T) + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * TAPS * (double)a.Nimg * wout * wout);
-    return conv_f32_any_launch<Cfg>(a, wout, s);
-}
-// tile shape by grid size: 128 x 256 (64 x 256 for Cout <= 64) while that fills the CUs, then 64 x 256, then 64 x 64 (same bits: same k order)
-template <int TAPS, int STRIDE>
-static hipError_t conv_gen_co(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
-    const long t256 = ((long)a.Nimg * wout * wout + 255) / 256, cus = device_cu_count();
-    if (a.Cout > 64 && t256 * ((a.Cout + 127) / 128) >= cus) return conv_gen<TAPS, STRIDE, 128, 256>(h, role, wout, a, s);
-    if (t256 * ((a.Cout + 63) / 64) >= cus) return conv_gen<TAPS, STRIDE, 64, 256>(h, role, wout, a, s);
-    return conv_gen<TAPS, STRIDE, 64, 64>(h, role, wout, a, s);
-}
-
-template <class Cfg>
-static hipError_t conv_bf(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
-    static const std::string kname = std::string("conv_bf16_kernel<3x3,s1,W") + std::to_string(Cfg::W) + (Cfg::NP == 3 ? ",bf16x3>" : ",bf16>");
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * 9 * (double)a.Nimg * Cfg::W * Cfg::W);
-    return conv_bf16_launch<Cfg>(a, h->conv_pack, s);
-}
-
-// dispatch on (taps, stride, output width): the power-of-two instantiations at wout in {128, 64, 32, 16, 8} (where they exist), every
-// other width >= 1 on conv_f32_any_kernel (exact fp32 in every precision mode)
-static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, int wout, const ConvArgs& a, hipStream_t s) {
-    // opt-in modes: 3x3 stride-1 convs with a multiple of 128 output channels at widths 64 / 32 / 16 run on the bf16 matrix cores
-    if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout >= 128) {
-        const bool x3 = h->precision == EGOTAP_PREC_BF16X3;
-        if (wout == 64) return x3 ? conv_bf<ConvBfCfg<6, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<6, 1>>(h, role, a, s);
-        if (wout == 32) return x3 ? conv_bf<ConvBfCfg<5, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<5, 1>>(h, role, a, s);
-        if (wout == 16) return x3 ? conv_bf<ConvBfCfg<4, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<4, 1>>(h, role, a, s);
-        if (wout == 8) return x3 ? conv_bf<ConvBfCfg<3, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<3, 1>>(h, role, a, s);
-    }
-    if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout == 64 && wout == 64)   // ResNet layer1
-        return h->precision == EGOTAP_PREC_BF16X3 ? conv_bf<ConvBfCfg<6, 3, 64>>(h, role, a, s) : conv_bf<ConvBfCfg<6, 1, 64>>(h, role, a, s);
-    if (h->precision == EGOTAP_PREC_BF16 && h->conv_pack && taps == 9 && stride == 1 && a.Cout == 64 && wout == 128)   // layer1 at 512x512 RGB
-        return conv_bf<ConvBfCfg<7, 1, 64>>(h, role, a, s);
-    if (taps == 9 && stride == 1) {
-        if (wout == 128) return a.Cout <= 64 ? conv<C3s1_128_co64>(h, role, a, s) : conv<C3s1_128>(h, role, a, s);
-        if (wout == 64) return a.Cout <= 64 ? conv<C3s1_64_co64>(h, role, a, s) : conv<C3s1_64>(h, role, a, s);
-        if (wout == 32) return conv<C3s1_32>(h, role, a, s);
-        // layer3 / layer4 at a 32-frame training batch: 128 / 64 workgroups of 128-channel tiles for 256 CUs (MFMA busy 0.21 on the 8 x 8 maps)
-        const long co128 = (a.Cout + 127) / 128;
-        if (wout == 16) return (long)a.Nimg * co128 < device_cu_count() ? conv<C3s1_16_co64>(h, role, a, s) : conv<C3s1_16>(h, role, a, s);
-        if (wout == 8) return (long)((a.Nimg + 3) / 4) * co128 < device_cu_count() ? conv<C3s1_8_co64>(h, role, a, s) : conv<C3s1_8>(h, role, a, s);
-    } else if (taps == 9 && stride == 2) {
-        if (wout == 64) return conv<C3s2_64>(h, role, a, s);
-        if (wout == 32) return conv<C3s2_32>(h, role, a, s);
-        if (wout == 16) return conv<C3s2_16>(h, role, a, s);
-        if (wout == 8) return conv<C3s2_8>(h, role, a, s);
-    } else if (taps == 1 && stride == 1) {
-        if (wout == 128) return conv<C1s1_128>(h, role, a, s);
-        if (wout == 64) return conv<C1s1_64>(h, role, a, s);
-        if (wout == 32) return conv<C1s1_32>(h, role, a, s);
-        if (wout == 16) return conv<C1s1_16>(h, role, a, s);
-        if (wout == 8) return conv<C1s1_8>(h, role, a, s);
-    } else if (taps == 1 && stride == 2) {
-        if (wout == 64) return conv<C1s2_64>(h, role, a, s);
-        if (wout == 32) return conv<C1s2_32>(h, role, a, s);
-        if (wout == 16) return conv<C1s2_16>(h, role, a, s);
-        if (wout == 8) return conv<C1s2_8>(h, role, a, s);
-    }
-    if (wout < 1) return hipErrorInvalidValue;
-    if (taps == 9 && stride == 1) return conv_gen_co<9, 1>(h, role, wout, a, s);
-    if (taps == 9 && stride == 2) return conv_gen_co<9, 2>(h, role, wout, a, s);
-    if (taps == 1 && stride == 1) return conv_gen_co<1, 1>(h, role, wout, a, s);
-    if (taps == 1 && stride == 2) return conv_gen_co<1, 2>(h, role, wout, a, s);
-    return hipErrorInvalidValue;
 }
 
 // [r7] Where an estimator's frames come from: the normalised planar fp32 frames (left / right), or the camera's bytes (left8 / right8: uint8
@@ -1880,28 +1900,21 @@ static hipError_t hm_bf16_decoder(Handle* h, const HmParams& p, const PackTable&
             if (hn == 128) return gemm_bf16s_launch<XPlain, E, 2>(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 128, 512, cus, s);
             return gemm_bf16s_launch(XPlain{Y1, 512}, hw, 512L, he, (int)(B * p64), 256, 512, cus, s);
         };
-#if EGOTAP_IN(0)      // the hand-off's only caller (egotap_predict_pose_rgb) is in part 0: its kernels are instantiated in that translation unit alone
         if (out_b) HMD(head(SEpiHeatBf16{hb, out_b, (long)out_image_stride, p.n_out, hm_ilog2(p64)}));
         else
-#else
-        if (out_b) return hipErrorInvalidValue;
-#endif
         HMD(head(SEpiHeatNCHW{hb, out, (long)out_image_stride, p.n_out, hm_ilog2(p64)}));
     }
 #undef HMD
     return hipSuccess;
 }
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_hm_workspace_bytes(egotap_handle h, int B, size_t* bytes) {
     EGO_CHECK(h && bytes, "null argument");
     EGO_CHECK(B >= 0, "negative batch");
     *bytes = hm_ws(h, B > 0 ? B : 1).total;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_hm_intermediate(egotap_handle h, int B, const char* name, size_t* offset, int64_t* numel) {
     EGO_CHECK(h && name && offset && numel, "null argument");
     const HmWs w = hm_ws(h, B > 0 ? B : 1);
@@ -1927,7 +1940,6 @@ extern "C" int egotap_hm_intermediate(egotap_handle h, int B, const char* name, 
     else { egotap_set_error("unknown intermediate '%s'", name); return EGOTAP_ERR_INVALID; }
     return EGOTAP_OK;
 }
-#endif
 
 // the pack plan of the eval-mode bf16 forward at batch B (egotap_hm_forward and egotap_hm_freeze share it): the split-K budgets are the
 // workspace slices egotap_hm_forward hands the backbone (the fp32 stem map's slot) and the decoder (40 MB of the WPACK region)
@@ -1948,7 +1960,6 @@ static bool hm_arena_fits(const Handle* h, int net, const PackTable& PT) {
 // the precision / geometry for which an estimator has a packed region at all: the bf16 channels-last path (sides 64 / 128)
 static bool hm_frozen_route(const Handle* h) { return h->precision == EGOTAP_PREC_BF16 && (h->cfg.hm_size == 64 || h->cfg.hm_size == 128); }
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_hm_frozen_bytes(egotap_handle h, int net, int B, size_t* bytes) {
     EGO_CHECK(h && bytes, "egotap_hm_frozen_bytes: null argument");
     EGO_CHECK(net == EGOTAP_NET_HM_POS || net == EGOTAP_NET_HM_ROT, "egotap_hm_frozen_bytes: net must be EGOTAP_NET_HM_POS or _ROT");
@@ -1989,10 +2000,8 @@ extern "C" int egotap_hm_unfreeze(egotap_handle h, int net) {
     h->hm_arena[net] = nullptr;
     return EGOTAP_OK;
 }
-#endif
 
 // HeatMap_UnrealEgo_Shared.forward(left, right) (model/net_architecture.py:32-36, 45-51, 75-85, 139-173), eval mode.
-#if EGOTAP_IN(0)
 // out_b != nullptr (egotap_predict_pose_rgb's hand-off, bf16 channels-last route only): the result as bf16 at out_b, `out` unused
 static int hm_forward_impl(Handle* h, int net, const HmSrc& src, int B, float* out, int64_t out_image_stride, void* ws, size_t ws_bytes,
                            void* stream, __bf16* out_b) {
@@ -2755,7 +2764,6 @@ extern "C" int egotap_debug_predict_pose_rgb_intermediate(egotap_handle h, int B
     *numel = (int64_t)B * h->C * h->cfg.hm_size * h->cfg.hm_size;
     return EGOTAP_OK;
 }
-#endif
 
 // ---- [r5] batch-statistics forward of a frozen estimator on the bf16 channels-last kernels (train.py:91; egotap_autoencoder_model.py:127-129, 177-216)
 struct HmBnWs {
@@ -2793,7 +2801,6 @@ static __global__ __launch_bounds__(256) void fill_f32_kernel(float* __restrict_
     if (i < n) p[i] = v;
 }
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_hm_forward_bnbatch_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
     EGO_CHECK(h && bytes, "null argument");
     EGO_CHECK(B >= 0 && chunk >= 0, "negative batch or chunk");
@@ -2801,9 +2808,7 @@ extern "C" int egotap_hm_forward_bnbatch_workspace_bytes(egotap_handle h, int B,
     *bytes = hm_bn_ws(h, b, chunk > 0 && chunk < b ? chunk : b).total;
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_hm_forward_bnbatch_intermediate(egotap_handle h, int B, int chunk, const char* name, size_t* offset, int64_t* numel) {
     EGO_CHECK(h && name && offset && numel, "null argument");
     EGO_CHECK(B >= 1, "batch");
@@ -2818,9 +2823,7 @@ extern "C" int egotap_hm_forward_bnbatch_intermediate(egotap_handle h, int B, in
     else { egotap_set_error("unknown intermediate '%s'", name); return EGOTAP_ERR_INVALID; }
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_hm_forward_bnbatch(egotap_handle h, int net, const float* left, const float* right, int B, float* out, int64_t out_image_stride, int chunk,
                                          void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(h, "null handle");
@@ -2881,7 +2884,6 @@ extern "C" int egotap_hm_forward_bnbatch(egotap_handle h, int net, const float* 
     }
     return EGOTAP_OK;
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------ single operators
 template <class Cfg>
@@ -2899,7 +2901,6 @@ static hipError_t linear_tile(const float* x, const float* w, const float* b, fl
     }
 }
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_linear_f32(const float* x, const float* w, const float* b, float* y, int M, int N, int K, int epi,
                                  const float* r, const float* g, const float* beta, const float* mean, const float* var,
                                  int tile, void* stream) {
@@ -2938,9 +2939,7 @@ extern "C" int egotap_linear_f32(const float* x, const float* w, const float* b,
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 // y = x w^T + b on gemm_bf16_dma_kernel with CALLER-OWNED bf16 copies of both operands (x [M,K], w [N,K], row-major) -- the
 // kernel the plain-bf16 mode runs after rounding its operands; exported for the operator tests
 extern "C" int egotap_linear_bf16_dma(const void* x_bf16, const void* w_bf16, const float* b, float* y, int M, int N, int K, void* stream) {
@@ -2955,9 +2954,7 @@ extern "C" int egotap_linear_bf16_dma(const void* x_bf16, const void* w_bf16, co
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_layernorm_f32(const float* x, float* y, const float* gamma, const float* beta, int rows, int dim,
                                     float eps, void* stream) {
     EGO_CHECK(x && y && gamma && beta, "egotap_layernorm_f32: null argument");
@@ -2965,9 +2962,7 @@ extern "C" int egotap_layernorm_f32(const float* x, float* y, const float* gamma
     EGO_HIP(launch_ln(x, y, gamma, beta, rows, eps, (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(0)
 extern "C" int egotap_attention_f32(const float* qkv, float* ctx, int B, int N, int heads, void* stream) {
     EGO_CHECK(qkv && ctx, "egotap_attention_f32: null argument");
     EGO_CHECK(N >= 32 && N % 4 == 0, "egotap_attention_f32: sequence length must be at least 32 and a multiple of 4 (any heatmap side that is a multiple of 16)");
@@ -2975,10 +2970,8 @@ extern "C" int egotap_attention_f32(const float* qkv, float* ctx, int B, int N, 
     EGO_HIP(attention_f32_launch(qkv, ctx, B, N, heads, (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
 // (test hook) the exact-fp32 attention with the tokens from shared_from on read from image 0's rows: layer 0 of the pose-only forward
-#if EGOTAP_IN(0)
 extern "C" int egotap_debug_attention_f32_shared(const float* qkv, float* ctx, int B, int N, int heads, int shared_from, void* stream) {
     EGO_CHECK(qkv && ctx, "egotap_debug_attention_f32_shared: null argument");
     EGO_CHECK(B >= 0 && N >= 32 && N % 4 == 0 && heads > 0, "egotap_debug_attention_f32_shared: bad shape B=%d N=%d heads=%d", B, N, heads);
@@ -2987,11 +2980,9 @@ extern "C" int egotap_debug_attention_f32_shared(const float* qkv, float* ctx, i
     EGO_HIP(attention_f32_shared_launch(qkv, ctx, B, N, heads, shared_from, (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
 // (test hook) the exact-fp32 attention as lift_forward launches it: with the caller's scratch for the key-split partials, the split count being
 // attention_f32_ksplit's own decision for scratch_floats and num_cu (egotap_debug_attention_f32_ksplit tells which)
-#if EGOTAP_IN(0)
 extern "C" int egotap_debug_attention_f32_split(const float* qkv, float* ctx, int B, int N, int heads, float* scratch, size_t scratch_floats, int num_cu, void* stream) {
     EGO_CHECK(qkv && ctx && scratch, "egotap_debug_attention_f32_split: null argument");
     EGO_CHECK(B >= 0 && N >= 32 && N % 4 == 0 && heads > 0, "egotap_debug_attention_f32_split: bad shape B=%d N=%d heads=%d (N at least 32 and a multiple of 4)", B, N, heads);
@@ -2999,11 +2990,9 @@ extern "C" int egotap_debug_attention_f32_split(const float* qkv, float* ctx, in
     EGO_HIP(attention_f32_launch(qkv, ctx, B, N, heads, (hipStream_t)stream, nullptr, scratch, scratch_floats, num_cu));
     return EGOTAP_OK;
 }
-#endif
 
 // (test hook) the live-query attention of the pose-only forward's last layer: Nq compact query rows per image (row b * Nq + q of q, stride ldq)
 // against the K / V columns of all N tokens of qkv; ctx [B * Nq, heads * 128]
-#if EGOTAP_IN(0)
 extern "C" int egotap_debug_attention_f32_live(const float* q, int64_t ldq, int Nq, const float* qkv, float* ctx, int B, int N, int heads, void* stream) {
     EGO_CHECK(q && qkv && ctx, "egotap_debug_attention_f32_live: null argument");
     EGO_CHECK(B >= 0 && N >= 32 && N % 4 == 0 && heads > 0, "egotap_debug_attention_f32_live: bad shape B=%d N=%d heads=%d (N at least 32 and a multiple of 4)", B, N, heads);
@@ -3012,11 +3001,9 @@ extern "C" int egotap_debug_attention_f32_live(const float* q, int64_t ldq, int 
     EGO_HIP(attention_f32_live_launch(q, (long)ldq, Nq, qkv, ctx, B, N, heads, (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
 // (test aid, host only: no device call) the key-split count attention_f32_launch picks for a forward with scratch_floats of scratch on num_cu
 // compute units: 1 = unsplit.  0 (never a split count) with egotap_last_error set where the arguments are refused
-#if EGOTAP_IN(0)
 extern "C" int egotap_debug_attention_f32_ksplit(int B, int N, int heads, size_t scratch_floats, int num_cu) {
     if (!(B > 0 && N >= 32 && N % 4 == 0 && heads > 0)) {
         egotap_set_error("egotap_debug_attention_f32_ksplit: bad shape B=%d N=%d heads=%d (N at least 32 and a multiple of 4)", B, N, heads);
@@ -3028,10 +3015,8 @@ extern "C" int egotap_debug_attention_f32_ksplit(int B, int N, int heads, size_t
     }
     return attention_f32_ksplit(B, N, heads, scratch_floats, num_cu);
 }
-#endif
 
 // per-sample MPJPE / PA-MPJPE of a batch of poses (egotap_autoencoder_model.py:329-350, utils/util.py:328-379)
-#if EGOTAP_IN(0)
 extern "C" int egotap_pose_metrics(const float* pred, const float* gt, int B, int J, float* mpjpe, float* pa_mpjpe, float* aligned,
                                    void* stream) {
     if (B == 0) return EGOTAP_OK;
@@ -3041,10 +3026,8 @@ extern "C" int egotap_pose_metrics(const float* pred, const float* gt, int B, in
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // the same metrics as the reference computes them for a batch of 2 or 3 frames (utils/util.py:337 skips its transpose there)
-#if EGOTAP_IN(0)
 extern "C" int egotap_pose_metrics_batch_axes(const float* pred, const float* gt, int B, int J, float* mpjpe, float* pa_mpjpe, float* aligned,
                                               void* stream) {
     EGO_CHECK(pred && gt && mpjpe && pa_mpjpe, "egotap_pose_metrics_batch_axes: null argument");
@@ -3054,10 +3037,8 @@ extern "C" int egotap_pose_metrics_batch_axes(const float* pred, const float* gt
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // joints -> ground-truth heatmaps in the lifting head's input layout (dataloader/data_loader.py:76-215 with --use_gt_heatmap)
-#if EGOTAP_IN(0)
 extern "C" int egotap_synth_heatmaps(const float* pts2d_left, const float* pts2d_right, const float* pose3d, const int* parents, int B,
                                      int J, int res, float* hm, float* plength, float* theta, void* stream) {
     if (B == 0) return EGOTAP_OK;
@@ -3074,10 +3055,8 @@ extern "C" int egotap_synth_heatmaps(const float* pts2d_left, const float* pts2d
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // same operator with the arithmetic of egotap_set_precision (EGOTAP_PREC_*): fp32 MFMA, bf16x3 split or plain bf16
-#if EGOTAP_IN(0)
 extern "C" int egotap_attention(const float* qkv, float* ctx, int B, int N, int heads, int precision, void* stream) {
     EGO_CHECK(qkv && ctx, "egotap_attention: null argument");
     EGO_CHECK(N >= 32 && N % 4 == 0, "egotap_attention: sequence length must be at least 32 and a multiple of 4");
@@ -3092,20 +3071,15 @@ extern "C" int egotap_attention(const float* qkv, float* ctx, int B, int N, int 
 }
 #endif
 
+#if EGOTAP_IN(1)
 // ================================================================================================ training operators
 // Building blocks of the training step (egotap_autoencoder_model.py:299-323), called by the autograd glue in
 // egotap_amd/autograd.py.  Each takes caller-owned device buffers and the caller's stream.
-#include "attention_bwd_f32.h"
-#include "attention_bwd_bf16.h"
-#include "gemm_tn_f32.h"
-#include "gemm_tn_bf16.h"
-#include "train_ops.h"
 
 using TnBig = TnCfg<256, 256, 16, 4, 2>;     // 8 waves, 64x128 per wave
 using TnSmall = TnCfg<128, 128, 16, 2, 2>;   // 4 waves, 64x64 per wave
 
 enum { LD_PLAIN = 0, LD_PATCH = 1, LD_TOKENS = 2, LD_ROT = 3, LD_STEREO = 4, LD_STEREO_GATED = 5 };
-enum { TE_NONE = 0, TE_BIAS = 1, TE_BIAS_RES = 2, TE_BIAS_GELU_SAVE = 3, TE_ACCUM = 4, TE_GELU_GRAD = 5, TE_PATCH = 6, TE_SCATTER_PATCH = 7, TE_SCATTER_ROT = 8 };
 
 template <class AL, class Epi>
 static hipError_t nt_any(Handle* h, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc, int M, int N, int K, hipStream_t s) {
@@ -3172,7 +3146,6 @@ static hipError_t nt_scatter(Handle* h, const float* A, long lda, const float* w
 // TE_SCATTER_PATCH / TE_SCATTER_ROT (loader LD_PLAIN, no bias): y = dhm fp32 [B, C, S, S] (16-byte aligned), the heatmap gradient of the patch
 // embedding (x = its output gradient [B * seq, D], w = projection.weight^T [256, D]; M = B * seq, N = 256, K = D) or of the rotation
 // encoder's fc1 (x = its pre-activation gradient [B * T, 2048], w = fc1.weight^T [2 S^2, 2048]; M = B * T, N = 2 S^2, K = 2048)
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_gemm_nt(egotap_handle h, int loader, const float* x, int64_t lda, const float* aux, const float* w, const float* b,
                                     float* y, int M, int N, int K, int epi, const float* r, float* z, int Bsz, void* stream) {
     EGO_CHECK(h && x && w && y, "egotap_train_gemm_nt: null argument");
@@ -3207,10 +3180,8 @@ extern "C" int egotap_train_gemm_nt(egotap_handle h, int loader, const float* x,
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
 // patch embedding forward in training (same kernel as eval): hm [B,C,S,S] -> x [B*seq, D]
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_patch_fwd(egotap_handle h, const float* hm, int B, const float* w, const float* b, const float* mask_tok,
                                       const float* pos, float* x, void* stream) {
     EGO_CHECK(h && hm && w && b && mask_tok && pos && x, "egotap_train_patch_fwd: null argument");
@@ -3220,7 +3191,6 @@ extern "C" int egotap_train_patch_fwd(egotap_handle h, const float* hm, int B, c
     EGO_HIP((gemm_big(h, "patch_embed", al, segmat1(w, D, 256), ep, x, D, M, D, 256, (hipStream_t)stream)));
     return EGOTAP_OK;
 }
-#endif
 
 template <class XL>
 static hipError_t tn_any(Handle* h, const float* dy, const XL& xl, float* dw, float* ws, size_t ws_bytes, int M, int N, int K, int acc, hipStream_t s,
@@ -3240,7 +3210,6 @@ static hipError_t tn_any(Handle* h, const float* dy, const XL& xl, float* dw, fl
 }
 
 // dW[N,K] (+)= dY[M,N]^T A(x)[M,K]   (weight gradient; x goes through the forward's loader)
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_gemm_tn(egotap_handle h, int loader, const float* dy, int64_t ldy, const float* x, const float* aux, float* dw, int M,
                                     int N, int K, int accumulate, int Bsz, void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(h && dy && x && dw && ws, "egotap_train_gemm_tn: null argument");
@@ -3264,19 +3233,15 @@ extern "C" int egotap_train_gemm_tn(egotap_handle h, int loader, const float* dy
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_colsum(const float* y, int64_t ldy, float* out, int M, int N, int accumulate, void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(y && out && ws, "egotap_train_colsum: null argument");
     EGO_CHECK(N % 4 == 0, "egotap_train_colsum: N must be a multiple of 4");
     EGO_HIP(colsum_f32_launch(y, ldy > 0 ? ldy : N, out, (float*)ws, ws_bytes, M, N, accumulate, (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
 // (test aid, host only) the split count the weight-gradient launches choose: wgrad_pick_splits of gemm_tn_f32.h
-#if EGOTAP_IN(1)
 extern "C" int egotap_debug_wgrad_splits(int tiles, int64_t slabs, int64_t n_floats, size_t slab_bytes, int num_cu, int lds_bytes, double slab_us,
                                          double fixed_us, int* per) {
     int p = 0;
@@ -3284,12 +3249,10 @@ extern "C" int egotap_debug_wgrad_splits(int tiles, int64_t slabs, int64_t n_flo
     if (per) *per = p;
     return s;
 }
-#endif
 
 // [r3] dW[N,K] (+)= dY^T X and db[N] (+)= column sums of dY in one call: weight and bias gradient of a Linear layer with a plain input.  In fp32,
 // when the DMA-staged kernel applies, the workgroups that stage dY for the product also sum its columns (no second pass over dY: 5.4 GB per
 // ViT layer at B = 256); otherwise the two operators one after the other.
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_gemm_tn_bias(egotap_handle h, const float* dy, int64_t ldy, const float* x, float* dw, float* db, int M, int N, int K,
                                          int accumulate, void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(h && dy && x && dw && db && ws, "egotap_train_gemm_tn_bias: null argument");
@@ -3314,18 +3277,14 @@ extern "C" int egotap_train_gemm_tn_bias(egotap_handle h, const float* dy, int64
     if (rc != EGOTAP_OK) return rc;
     return egotap_train_colsum(dy, ldy, db, M, N, accumulate, ws, ws_bytes, stream);
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_transpose(const float* in, float* out, int R, int C, int64_t ldo, void* stream) {
     EGO_CHECK(in && out, "egotap_train_transpose: null argument");
     hipLaunchKernelGGL(transpose_f32_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, (hipStream_t)stream, in, out, R, C, (long)(ldo > 0 ? ldo : R));
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_layernorm_fwd(const float* x, float* y, const float* g, const float* b, float* mean, float* rstd, int rows,
                                           float eps, void* stream) {
     EGO_CHECK(x && y && g && b && mean && rstd, "egotap_train_layernorm_fwd: null argument");
@@ -3333,10 +3292,8 @@ extern "C" int egotap_train_layernorm_fwd(const float* x, float* y, const float*
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // dx = LN'(dy) (+ dres); dgamma / dbeta (+)= column sums.  ws: >= (b + 1 + ceil(b/64)) * 2048 floats, b = ceil(rows/64)
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_layernorm_bwd(const float* x, const float* dy, const float* g, const float* mean, const float* rstd,
                                           const float* dres, float* dx, float* dgamma, float* dbeta, int rows, int accumulate,
                                           void* ws, size_t ws_bytes, void* stream) {
@@ -3360,11 +3317,9 @@ extern "C" int egotap_train_layernorm_bwd(const float* x, const float* dy, const
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // BatchNorm1d (training mode) + LeakyReLU(0.2) over z [R, C]: y, saved mean / rstd, running-stat update
 // (network_utils.py:123-142; momentum 0.1, unbiased running variance).  ws >= (2 * ceil(R/256) * C + 2C) floats
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_bn_lrelu_fwd(const float* z, float* y, const float* gamma, const float* beta, float* mean, float* rstd,
                                          float* run_mean, float* run_var, int R, int C, float eps, float momentum, void* ws,
                                          size_t ws_bytes, void* stream) {
@@ -3387,9 +3342,7 @@ extern "C" int egotap_train_bn_lrelu_fwd(const float* z, float* y, const float* 
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_bn_lrelu_bwd(const float* z, const float* y, const float* dy, const float* gamma, const float* mean,
                                          const float* rstd, float* dz, float* dgamma, float* dbeta, int R, int C, int accumulate,
                                          void* ws, size_t ws_bytes, void* stream) {
@@ -3409,9 +3362,7 @@ extern "C" int egotap_train_bn_lrelu_bwd(const float* z, const float* y, const f
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_attention_fwd(const float* qkv, float* ctx, float* lse, int B, int N, int heads, int precision, void* stream) {
     EGO_CHECK(qkv && ctx && lse, "egotap_train_attention_fwd: null argument");
     EGO_CHECK(N >= 32 && N % 4 == 0 && heads > 0, "egotap_train_attention_fwd: bad shape");
@@ -3422,9 +3373,7 @@ extern "C" int egotap_train_attention_fwd(const float* qkv, float* ctx, float* l
     else EGO_HIP(attention_f32_launch(qkv, ctx, B, N, heads, s, lse));
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_attention_bwd(const float* qkv, const float* ctx, const float* dctx, const float* lse, float* delta,
                                           float* dqkv, int B, int N, int heads, int precision, void* stream) {
     EGO_CHECK(qkv && ctx && dctx && lse && delta && dqkv, "egotap_train_attention_bwd: null argument");
@@ -3437,9 +3386,7 @@ extern "C" int egotap_train_attention_bwd(const float* qkv, const float* ctx, co
     else EGO_HIP(attention_bwd_f32_launch(qkv, ctx, dctx, lse, delta, dqkv, B, N, heads, s));
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pose_loss(egotap_handle h, const float* pred, const float* gt, float* dpred, float* out, float* partial,
                                       int B, float lambda_mpjpe, float lambda_cos_sim, void* stream) {
     EGO_CHECK(h && pred && gt && dpred && out && partial, "egotap_train_pose_loss: null argument");
@@ -3458,9 +3405,7 @@ extern "C" int egotap_train_pose_loss(egotap_handle h, const float* pred, const 
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_adamw(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                                   double weight_decay, int step, void* stream) {
     EGO_CHECK(p && g && m && v && step >= 1, "egotap_train_adamw: bad argument");
@@ -3472,9 +3417,7 @@ extern "C" int egotap_train_adamw(float* p, const float* g, float* m, float* v, 
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_adamw_multi(const void* table, int nseg, const float* g, float* m, float* v, int64_t span, double lr, double beta1,
                                         double beta2, double eps, double weight_decay, int step, void* stream) {
     EGO_CHECK(table && g && m && v && nseg >= 1 && span >= 1 && step >= 1, "egotap_train_adamw_multi: bad argument");
@@ -3484,16 +3427,13 @@ extern "C" int egotap_train_adamw_multi(const void* table, int nseg, const float
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_add_inplace(float* out, const float* in, int64_t n, void* stream) {
     EGO_CHECK(out && in && n % 4 == 0, "egotap_train_add_inplace: bad argument");
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, in, (long)(n / 4));
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------ PU chain + pose head (training)
 struct PuSaved { size_t F0, G0, GP0, HS0, C0, F1, G1, GP1, HS1, C1, ZERO, HPA, HPB, FAULT, total; };
@@ -3512,7 +3452,6 @@ static PuSaved pu_saved(const Handle* h, int B) {
     w.total = o;
     return w;
 }
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pu_saved_bytes(egotap_handle h, int B, size_t* bytes, size_t* hs1_offset) {
     EGO_CHECK(h && bytes && hs1_offset, "null argument");
     const PuSaved w = pu_saved(h, B > 0 ? B : 1);
@@ -3520,10 +3459,8 @@ extern "C" int egotap_train_pu_saved_bytes(egotap_handle h, int B, size_t* bytes
     *hs1_offset = w.HS1;
     return EGOTAP_OK;
 }
-#endif
 
 // SkelNet(mode "PU") forward keeping what the backward needs: posz, rotz [B*2J, hid] -> saved[HS1] = skel_embed [J, B, H]
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pu_fwd(egotap_handle h, const float* posz, const float* rotz, int B, void* saved, size_t saved_bytes,
                                    void* stream) {
     EGO_CHECK(h && posz && rotz && saved, "egotap_train_pu_fwd: null argument");
@@ -3574,7 +3511,6 @@ extern "C" int egotap_train_pu_fwd(egotap_handle h, const float* posz, const flo
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 struct PuBwdWs { size_t dG, dF, HP, dHS0, dXs, dBp, DHP, dHrec[2], dC[2], WT, part, total; };
 static PuBwdWs pu_bwd_ws(const Handle* h, int B) {
@@ -3589,18 +3525,15 @@ static PuBwdWs pu_bwd_ws(const Handle* h, int B) {
     w.total = o;
     return w;
 }
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pu_bwd_ws_bytes(egotap_handle h, int B, size_t* bytes) {
     EGO_CHECK(h && bytes, "null argument");
     *bytes = pu_bwd_ws(h, B > 0 ? B : 1).total;
     return EGOTAP_OK;
 }
-#endif
 
 // Backward of egotap_train_pu_fwd.  dhs1: gradient w.r.t. skel_embed [J,B,H]; dposz is ACCUMULATED into (the pose head's
 // contribution is already there), drotz is written; grads[14] (state_dict order of skel_sequential_layer) are accumulated
 // when accumulate != 0, else overwritten.
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pu_bwd(egotap_handle h, const float* posz, const float* rotz, int B, const void* saved,
                                    const float* dhs1, float* dposz, float* drotz, float* const* grads, int accumulate, void* ws,
                                    size_t ws_bytes, void* stream) {
@@ -3705,10 +3638,8 @@ extern "C" int egotap_train_pu_bwd(egotap_handle h, const float* posz, const flo
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // pose head (training): forward = the eval kernel; backward: data gradients + weight gradients
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pose_head_fwd(egotap_handle h, const float* posz, const float* hs1, int B, float* pose, void* stream) {
     EGO_CHECK(h && posz && hs1 && pose, "egotap_train_pose_head_fwd: null argument");
     int rc = lift_resolve(h);
@@ -3719,8 +3650,6 @@ extern "C" int egotap_train_pose_head_fwd(egotap_handle h, const float* posz, co
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_pose_head_bwd(egotap_handle h, const float* posz, const float* hs1, const float* dpose, int B, float* dposz,
                                           float* dhs1, float* dWp, float* dbp, float* dWg, float* dbg, int accumulate, void* stream) {
     EGO_CHECK(h && posz && hs1 && dpose && dposz && dhs1 && dWp && dbp, "egotap_train_pose_head_bwd: null argument");
@@ -3737,8 +3666,6 @@ extern "C" int egotap_train_pose_head_bwd(egotap_handle h, const float* posz, co
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
-
 
 // patch-embedding bias / mask-token gradients from dpos[seq, D] = sum_b dx[b]: rows of real cells -> dbias, dummy cells -> dmask
 static __global__ __launch_bounds__(256) void patch_split_kernel(const float* __restrict__ dpos, float* __restrict__ dbias, float* __restrict__ dmask,
@@ -3754,7 +3681,6 @@ static __global__ __launch_bounds__(256) void patch_split_kernel(const float* __
     dbias[n] = (accumulate ? dbias[n] : 0.f) + sb;
     dmask[n] = (accumulate ? dmask[n] : 0.f) + sm;
 }
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_patch_split(egotap_handle h, const float* dpos, float* dbias, float* dmask, int accumulate, void* stream) {
     EGO_CHECK(h && dpos && dbias && dmask, "egotap_train_patch_split: null argument");
     hipLaunchKernelGGL(patch_split_kernel, dim3((h->D + 255) / 256), dim3(256), 0, (hipStream_t)stream, dpos, dbias, dmask, h->D, h->seq,
@@ -3762,7 +3688,6 @@ extern "C" int egotap_train_patch_split(egotap_handle h, const float* dpos, floa
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // input gradient of fc1 (position encoder): dA [B*T, ppd*ppd*D] (heatmap-major) -> dtokens [B*seq, D]; dummy tokens get zero
 static __global__ __launch_bounds__(256) void tokens_scatter_kernel(const float* __restrict__ dA, float* __restrict__ dtok, int B, int T, int D,
@@ -3782,7 +3707,6 @@ static __global__ __launch_bounds__(256) void tokens_scatter_kernel(const float*
     }
     *(f32x4*)(dtok + bt * D + c4 * 4) = v;
 }
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_tokens_scatter(egotap_handle h, const float* dA, float* dtok, int B, void* stream) {
     EGO_CHECK(h && dA && dtok, "egotap_train_tokens_scatter: null argument");
     const long n = (long)B * h->seq * (h->D / 4);
@@ -3791,11 +3715,8 @@ extern "C" int egotap_train_tokens_scatter(egotap_handle h, const float* dA, flo
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
-
 
 // fused Q|K|V projection (three nn.Linear of ViTSelfAttention, modeling_vit.py:212-214) into one [M, 3D] buffer
-#if EGOTAP_IN(1)
 extern "C" int egotap_train_qkv_fwd(egotap_handle h, const float* y, const float* wq, const float* bq, const float* wk, const float* bk, const float* wv,
                                     const float* bv, float* qkv, int M, int D, void* stream) {
     EGO_CHECK(h && y && wq && bq && wk && bk && wv && bv && qkv, "egotap_train_qkv_fwd: null argument");
@@ -3807,16 +3728,14 @@ extern "C" int egotap_train_qkv_fwd(egotap_handle h, const float* y, const float
 }
 #endif
 
-
+#if EGOTAP_IN(2)
 // ================================================================================================ heatmap-estimator training
 // Building blocks of one optimisation step of the stage-1 model (model/heatmap_shared_model.py:98-172: HeatMap_UnrealEgo_Shared
 // in train mode, MSE losses, Adam), called by the autograd glue in egotap_amd/hm_training.py.  All tensors are caller-owned
 // NCHW fp32 device buffers with explicit image strides (so concat slices are read and written in place).
-#include "hm_train.h"
 
 // scratch for the repacked weights of the bf16 convolution kernels when the training operators run under a bf16 precision mode
 // (egotap_hm_forward takes it from its workspace); bytes >= egotap_hmtrain_pack_bytes()
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_set_pack_buffer(egotap_handle h, void* buf, size_t bytes) {
     EGO_CHECK(h, "null handle");
     EGO_CHECK(buf == nullptr || bytes >= conv_bf16_pack_bytes(1024, 1540), "egotap_hmtrain_set_pack_buffer: buffer too small");
@@ -3824,12 +3743,8 @@ extern "C" int egotap_hmtrain_set_pack_buffer(egotap_handle h, void* buf, size_t
     h->conv_pack = (__bf16*)buf;
     return EGOTAP_OK;
 }
-#endif
-#if EGOTAP_IN(2)
 extern "C" size_t egotap_hmtrain_pack_bytes(void) { return conv_bf16_pack_bytes(1024, 1540); }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_conv_fwd(egotap_handle h, const float* x, const float* w, const float* bias, const float* res, float* y,
                                        int Nimg, int Cin, int Cout, int wout, int taps, int stride, int relu, int64_t in_istride,
                                        int64_t out_istride, int64_t res_istride, void* stream) {
@@ -3840,12 +3755,10 @@ extern "C" int egotap_hmtrain_conv_fwd(egotap_handle h, const float* x, const fl
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
 // [r3] Eval-mode building blocks for the backbones the one-call forward does not cover (the Bottleneck ResNets of --model_name resnet50 /
 // resnet101, net_architecture.py:61-64): y = [relu](BatchNorm_eval(conv(x, w)) [+ res]) on the fp32 convolution kernels, BatchNorm folded
 // in the epilogue exactly as egotap_hm_forward folds it (gamma / sqrt(var + 1e-5)), and the stem with its BatchNorm + ReLU.
-#if EGOTAP_IN(2)
 extern "C" int egotap_hm_conv_bn_fwd(egotap_handle h, const float* x, const float* w, const float* gamma, const float* beta, const float* mean,
                                      const float* var, const float* res, float* y, int Nimg, int Cin, int Cout, int wout, int taps, int stride,
                                      int relu, int64_t in_istride, int64_t out_istride, int64_t res_istride, void* stream) {
@@ -3862,20 +3775,16 @@ extern "C" int egotap_hm_stem_bn_fwd(const float* left, const float* right, cons
     EGO_HIP(stem_conv7_launch(left, right, w, gamma, beta, mean, var, y, S0, 2 * B, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
 // conv 7x7 / 2 of the ResNet stem without BatchNorm: z [2B, 64, S0/2, S0/2], image n = 2b + eye
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_stem_fwd(const float* left, const float* right, const float* w, float* z, int B, int S0, void* stream) {
     EGO_CHECK(left && right && w && z && B > 0 && S0 % 32 == 0, "egotap_hmtrain_stem_fwd: bad argument");
     EGO_HIP(stem_conv7_launch(left, right, w, nullptr, nullptr, nullptr, nullptr, z, S0, 2 * B, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
 static int bn_splits(int N, int C) { int s = (1024 + C - 1) / C; if (s > N) s = N; if (s < 1) s = 1; return s; }
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_bn2d_fwd(const float* z, float* y, const float* res, const float* gamma, const float* beta, float* mean, float* rstd,
                                        float* run_mean, float* run_var, int N, int C, int HW, int64_t z_istride, int64_t y_istride,
                                        int64_t res_istride, int relu, float eps, float momentum, void* ws, size_t ws_bytes, void* stream) {
@@ -3894,9 +3803,7 @@ extern "C" int egotap_hmtrain_bn2d_fwd(const float* z, float* y, const float* re
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_bn2d_bwd(const float* z, const float* y, const float* dy, const float* gamma, const float* mean, const float* rstd,
                                        float* dz, float* dres, float* dgamma, float* dbeta, int N, int C, int HW, int64_t z_istride,
                                        int64_t dy_istride, int relu, int accumulate, int dres_accumulate, void* ws, size_t ws_bytes, void* stream) {
@@ -3918,7 +3825,6 @@ extern "C" int egotap_hmtrain_bn2d_bwd(const float* z, const float* y, const flo
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 static __global__ void chansum_finish_kernel(const double* __restrict__ part, int splits, int C, float* __restrict__ out, int accumulate) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3929,7 +3835,6 @@ static __global__ void chansum_finish_kernel(const double* __restrict__ part, in
 }
 
 // per-channel sums over N*H*W (bias gradients)
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_chansum(const float* dy, float* out, int N, int C, int HW, int64_t istride, int accumulate, void* ws, size_t ws_bytes,
                                       void* stream) {
     EGO_CHECK(dy && out && ws && HW % 4 == 0, "egotap_hmtrain_chansum: bad argument");
@@ -3942,9 +3847,7 @@ extern "C" int egotap_hmtrain_chansum(const float* dy, float* out, int N, int C,
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_conv_wt(const float* w, float* wt, int Cout, int Cin, int taps, void* stream) {
     EGO_CHECK(w && wt && Cout > 0 && Cin > 0 && taps > 0, "egotap_hmtrain_conv_wt: bad argument");
     const long total = (long)Cout * Cin * taps;
@@ -3952,9 +3855,7 @@ extern "C" int egotap_hmtrain_conv_wt(const float* w, float* wt, int Cout, int C
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_zero_upsample(const float* in, float* out, int N, int C, int H, int64_t in_istride, int64_t out_istride, void* stream) {
     EGO_CHECK(in && out && N > 0 && C > 0 && H > 0, "egotap_hmtrain_zero_upsample: bad argument");
     const long total = (long)N * C * 4 * H * H;
@@ -3963,7 +3864,6 @@ extern "C" int egotap_hmtrain_zero_upsample(const float* in, float* out, int N, 
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 template <int KS, int STRIDE, int CI_T>
 static hipError_t wgrad_w(int wout, const WgArgs& a, float* dw, size_t sb, int acc, hipStream_t s) {
@@ -3988,7 +3888,6 @@ static hipError_t wgrad_bf(int wout, const WgArgs& a, float* dw, size_t sb, int 
     return hipErrorInvalidValue;
 }
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_conv_wgrad(const float* dy, const float* x, float* dw, int Nimg, int Cin, int Cout, int wout, int ks, int stride,
                                          int64_t dy_istride, int64_t x_istride, int accumulate, int precision, void* ws, size_t ws_bytes,
                                          void* stream) {
@@ -4011,9 +3910,7 @@ extern "C" int egotap_hmtrain_conv_wgrad(const float* dy, const float* x, float*
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_relu_bwd(const float* y, const float* dy, float* dz, int N, int C, int HW, int64_t y_istride, int64_t dy_istride,
                                        int64_t dz_istride, void* stream) {
     EGO_CHECK(y && dy && dz && HW % 4 == 0, "egotap_hmtrain_relu_bwd: bad argument");
@@ -4023,9 +3920,7 @@ extern "C" int egotap_hmtrain_relu_bwd(const float* y, const float* dy, float* d
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_maxpool_bwd(const float* x, const float* dy, float* dx, int64_t planes, int HIN, void* stream) {
     EGO_CHECK(x && dy && dx && planes > 0 && HIN % 2 == 0, "egotap_hmtrain_maxpool_bwd: bad argument");
     const long total = planes * HIN * HIN;
@@ -4039,9 +3934,7 @@ extern "C" int egotap_hmtrain_maxpool_bwd(const float* x, const float* dy, float
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_upsample_bwd(const float* dy, float* dx, int N, int C, int HIN, int64_t dy_istride, int64_t dx_istride, void* stream) {
     EGO_CHECK(dy && dx && N > 0 && C > 0 && HIN > 1, "egotap_hmtrain_upsample_bwd: bad argument");
     const long total = (long)N * C * HIN * HIN;
@@ -4050,10 +3943,8 @@ extern "C" int egotap_hmtrain_upsample_bwd(const float* dy, float* dx, int N, in
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
 // loss[0] = lambda * (mean_left + mean_right) of (pred - gt)^2 / plen,  dpred = d loss / d pred   (pred, gt contiguous [B, Cn, HW])
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_mse(const float* pred, const float* gt, const float* plen, float* dpred, float* loss, int B, int Cn, int HW,
                                   float lambda, void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(pred && gt && dpred && loss && ws && HW % 4 == 0 && Cn > 0, "egotap_hmtrain_mse: bad argument");
@@ -4065,18 +3956,14 @@ extern "C" int egotap_hmtrain_mse(const float* pred, const float* gt, const floa
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_maxpool_fwd(const float* x, float* y, int64_t planes, int HIN, void* stream) {
     EGO_CHECK(x && y && planes > 0 && HIN % 2 == 0, "egotap_hmtrain_maxpool_fwd: bad argument");
     maxpool3s2_launch(x, y, (long)planes, HIN, (hipStream_t)stream);
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(2)
 extern "C" int egotap_hmtrain_upsample_fwd(const float* x, float* y, int N, int C, int HIN, int64_t in_istride, int64_t out_istride, void* stream) {
     EGO_CHECK(x && y && N > 0 && C > 0 && HIN > 1, "egotap_hmtrain_upsample_fwd: bad argument");
     const long threads = (long)N * C * (2 * HIN) * (2 * HIN / 4);
@@ -4087,11 +3974,10 @@ extern "C" int egotap_hmtrain_upsample_fwd(const float* x, float* y, int N, int 
 }
 #endif
 
-
+#if EGOTAP_IN(3)
 // ================================================================================================ bf16-storage operators (part 3)
 // EGOTAP_PREC_BF16 with bf16 tensors in HBM: activations are written as bf16 by their producers, weights are rounded once per
 // step; every GEMM reads bf16 through the LDS DMA (gemm_bf16s.h).  Single operators first (tests, tools), the whole step below.
-#if EGOTAP_IN(3)
 int g_conv_addressing = 0;           // the one definition (gemm_bf16s64.h)
 extern "C" int egotap_debug_conv_addressing(int mode) {
     EGO_CHECK(mode == 0 || mode == 1, "egotap_debug_conv_addressing: mode must be 0 (scalar origin where it fits) or 1 (per-lane pointers)");
@@ -4104,8 +3990,6 @@ extern "C" int egotap_debug_gemm_bk(int bk) {
     g_gemm_bf16s_bk = bk;
     return EGOTAP_OK;
 }
-#endif
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_gemm_nt(const void* x, int64_t ldx, const void* w, const float* bias, int M, int N, int K, int epi, const void* aux,
                                    void* out0, void* out1, int64_t ldo, void* stream) {
     EGO_CHECK(x && w && out0, "egotap_bf16_gemm_nt: null argument");
@@ -4135,9 +4019,7 @@ extern "C" int egotap_bf16_gemm_nt(const void* x, int64_t ldx, const void* w, co
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_gemm_tn(const void* dy, int64_t ldy, const void* x, int64_t ldx, float* dw, int M, int N, int K, int accumulate,
                                    const void* zeros, void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(dy && x && dw && zeros, "egotap_bf16_gemm_tn: null argument");
@@ -4150,9 +4032,7 @@ extern "C" int egotap_bf16_gemm_tn(const void* dy, int64_t ldy, const void* x, i
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_layernorm_fwd(const float* x, void* y, const float* g, const float* b, float* mean, float* rstd, int rows, float eps, void* stream) {
     EGO_CHECK(x && y && g && b, "egotap_bf16_layernorm_fwd: null argument");
     if (rows <= 0) return EGOTAP_OK;
@@ -4160,9 +4040,7 @@ extern "C" int egotap_bf16_layernorm_fwd(const float* x, void* y, const float* g
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 // ws >= (3 * blocks + 3 + 3 * ceil(blocks / 64)) * 1024 floats, blocks = ceil(rows / 64)
 extern "C" int egotap_bf16_layernorm_bwd(const float* x, const void* dy, const float* g, const float* mean, const float* rstd, const float* dres, float* dx,
                                          void* dxb, float* dgamma, float* dbeta, float* dcolsum, int rows, int accumulate, void* ws, size_t ws_bytes,
@@ -4185,9 +4063,7 @@ extern "C" int egotap_bf16_layernorm_bwd(const float* x, const void* dy, const f
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_colsum(const void* y, int64_t ldy, float* out, int M, int N, int accumulate, void* ws, size_t ws_bytes, void* stream) {
     EGO_CHECK(y && out && ws && N % 8 == 0 && ldy % 8 == 0, "egotap_bf16_colsum: bad argument");
     hipError_t e = colsum_bf16_launch((const __bf16*)y, (long)ldy, out, M, N, accumulate, (float*)ws, ws_bytes, (hipStream_t)stream);
@@ -4195,9 +4071,7 @@ extern "C" int egotap_bf16_colsum(const void* y, int64_t ldy, float* out, int M,
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_prep_weight(const float* w, void* wb, void* wt, int N, int K, int64_t ldt, void* stream) {
     EGO_CHECK(w && wb && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0, "egotap_bf16_prep_weight: bad argument (N, K multiples of 8)");
     EGO_CHECK(wt == nullptr || (ldt >= N && ldt % 8 == 0), "egotap_bf16_prep_weight: ldt must be >= N and a multiple of 8");
@@ -4205,9 +4079,7 @@ extern "C" int egotap_bf16_prep_weight(const float* w, void* wb, void* wt, int N
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_from_f32(const float* src, void* dst, int64_t n, void* stream) {
     EGO_CHECK(src && dst && n % 8 == 0, "egotap_bf16_from_f32: n must be a multiple of 8");
     if (n == 0) return EGOTAP_OK;
@@ -4215,9 +4087,7 @@ extern "C" int egotap_bf16_from_f32(const float* src, void* dst, int64_t n, void
     EGO_HIP(hipGetLastError());
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_attention_fwd(const void* qkv, void* ctx, float* lse, int B, int N, int heads, void* stream) {
     EGO_CHECK(qkv && ctx, "egotap_bf16_attention_fwd: null argument");
     hipError_t e = attention_bf16s_fwd_launch((const __bf16*)qkv, (__bf16*)ctx, lse, B, N, heads, (hipStream_t)stream);
@@ -4225,9 +4095,7 @@ extern "C" int egotap_bf16_attention_fwd(const void* qkv, void* ctx, float* lse,
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_attention_bwd(const void* qkv, const void* ctx, const void* dctx, const float* lse, float* delta, void* dqkv, int B, int N, int heads,
                                          void* stream) {
     EGO_CHECK(qkv && ctx && dctx && lse && delta && dqkv, "egotap_bf16_attention_bwd: null argument");
@@ -4236,9 +4104,7 @@ extern "C" int egotap_bf16_attention_bwd(const void* qkv, const void* ctx, const
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 // the same, also producing the q | k | v BIAS gradients (column sums of dqkv) without a pass over dqkv: the kernels' epilogues leave
 // per-block partial sums in ws (fp32 [B * N / 32][3 * heads * 128]); three small fp32 column sums finish them.  Shapes
 // without that epilogue (N % 64 != 0) take the column-sum pass over dqkv instead.
@@ -4265,11 +4131,9 @@ extern "C" int egotap_bf16_attention_bwd_bias(const void* qkv, const void* ctx, 
     }
     return EGOTAP_OK;
 }
-#endif
 
 // fc1 of the two heatmap encoders on bf16 operands, the gathers folded into the loaders (net_architecture.py:388-406, 690-694):
 //   which 0: rows = per-heatmap patch tokens gathered from tokens bf16 [B*seq, D];  1: rows = [cos | sin] maps from hm bf16 [B, C, S, S]
-#if EGOTAP_IN(3)
 // [r3] patch embedding of the bf16-storage step on the bf16-storage GEMM: hmb = bf16 copy of the heatmaps [B, C, S, S], w = bf16 copy of
 // projection.weight [D, 256] (egotap_bf16_prep_weight), zeros >= 16 bytes of zeros; x fp32 [B * seq, D] = the embeddings
 // (net_architecture.py:326-336, modeling_vit.py:137-153).  Replaces the fp32-operand kernel of the opt-in modes (VALU conversion per element).
@@ -4282,17 +4146,13 @@ extern "C" int egotap_bf16_patch_fwd(egotap_handle h, const void* hmb, const voi
     EGO_HIP(gemm_bf16s_launch(xl, (const __bf16*)w, 256L, ep, M, D, 256, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_fc1_fwd(egotap_handle h, int which, const void* src, const void* w, const float* bias, float* z, int B, void* stream) {
     EGO_CHECK(h && src && w && bias && z && (which == 0 || which == 1), "egotap_bf16_fc1_fwd: bad argument");
     const int BT = B * h->T, S = h->cfg.hm_size, K = which == 0 ? h->ppd * h->ppd * h->D : 2 * S * S;
     EGO_HIP(fc1_nt(h, which, (const __bf16*)src, (const __bf16*)w, (long)K, SEpiF32{bias, z, 2048L}, BT, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 extern "C" int egotap_bf16_fc1_wgrad(egotap_handle h, int which, const void* dz, const void* src, float* dw, int B, const void* zeros, void* ws,
                                      size_t ws_bytes, void* stream) {
     EGO_CHECK(h && dz && src && dw && zeros && ws && (which == 0 || which == 1), "egotap_bf16_fc1_wgrad: bad argument");
@@ -4304,9 +4164,7 @@ extern "C" int egotap_bf16_fc1_wgrad(egotap_handle h, int which, const void* dz,
     EGO_HIP(e);
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 // input gradient of fc1 of the position encoder, scattered back to token order: dtok bf16 [B*seq, D] (cleared here: dummy cells get zero)
 extern "C" int egotap_bf16_fc1_dgrad_tokens(egotap_handle h, const void* dz, const void* wt, void* dtok, int B, void* stream) {
     EGO_CHECK(h && dz && wt && dtok, "egotap_bf16_fc1_dgrad_tokens: null argument");
@@ -4317,9 +4175,7 @@ extern "C" int egotap_bf16_fc1_dgrad_tokens(egotap_handle h, const void* dz, con
                                     2048, device_cu_count(), s));      // [r5] the 64-deep kernel where its shape rules hold (plain operand)
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 // input gradient of fc1 of the rotation encoder, scattered back to the heatmaps (the inverse of the XRot gather): dz bf16 [B*T, 2048], wt bf16
 // [2 S^2, 2048] = fc1.weight^T (egotap_bf16_prep_weight), dhm fp32 [B, C, S, S] (16-byte aligned): channels [2J, 6J) written, each element once
 extern "C" int egotap_bf16_fc1_dgrad_rot(egotap_handle h, const void* dz, const void* wt, float* dhm, int B, void* stream) {
@@ -4329,9 +4185,7 @@ extern "C" int egotap_bf16_fc1_dgrad_rot(egotap_handle h, const void* dz, const 
                                     device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
-#endif
 
-#if EGOTAP_IN(3)
 // input gradient of the patch embedding, scattered back to the heatmaps (the inverse of the XPatch gather): dx bf16 [B*seq, D], wt bf16 [256, D]
 // = projection.weight^T, dhm fp32 [B, C, S, S] (16-byte aligned): channels [0, 2J) written, each element once; dummy cells store nothing
 extern "C" int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const void* wt, float* dhm, int B, void* stream) {
@@ -4343,6 +4197,7 @@ extern "C" int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const vo
 }
 #endif
 
+#if EGOTAP_IN(0)
 // ------------------------------------------------------------------------------------------------ one-call training step
 // egotap_lift_forward_train + egotap_lift_backward: the lifting head's training-mode forward (activations kept in `saved`) and its
 // whole backward as ONE call each (egotap_lift_forward(…, saved, …) / egotap_lift_backward; reference:
@@ -4355,7 +4210,6 @@ extern "C" int egotap_bf16_patch_dgrad(egotap_handle h, const void* dx, const vo
 // They differ in the patch-embedding forward, the ViT layers and the encoders' fc1 (lift_forward_train16 / lift_backward16 against the fp32
 // bodies in the entries); the plan, the buffer checks, fc2 / fc3 and the BatchNorms, the propagation units, the pose head, the bucket events
 // and the patch-embedding gradients are shared.  Everything is enqueued on the caller's stream; no allocation, no synchronisation.
-#if EGOTAP_IN(0)
 #define EGO_RC(call) do { const int rc_ = (call); if (rc_ != EGOTAP_OK) return rc_; } while (0)
 
 struct LiftTrainPlan {      // byte offsets into `saved`; hmb, the w_* weight copies and b_qkv only in bf16 storage (0 otherwise)

@@ -79,6 +79,65 @@ def test_head_layouts_and_conv_taps_are_written_once():
         assert found == copies, (pat, found)
 
 
+def test_part_switch_and_exports_are_written_once():
+    """Outside comments only egotap_abi.hip names the part switch (no kernel header decides which part compiles it), the file stands in
+    sections a reader can take in without counting guards, and every exported function is defined exactly once across csrc/."""
+    csrc = os.path.join(REPO, "egotap_amd", "csrc")
+    code = {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, f)).read(), flags=re.S) for f in sorted(os.listdir(csrc))}
+    assert [f for f, t in code.items() if "EGOTAP_IN(" in t] == ["egotap_abi.hip"]
+    assert [f for f, t in code.items() if "EGOTAP_PART" in t] == ["egotap_abi.hip"]
+    # egotap_abi.hip stands in sections: part guards are never nested and have one branch; the code guarded for a set of several parts is ONE
+    # run, in front of every single part's code; a single part's code is one run (part 0: two, the one-call training step comes last)
+    runs, cond, body = [], None, []      # (parts, holds code besides #include lines)
+    for line in code["egotap_abi.hip"].splitlines():
+        line = line.strip()
+        if "EGOTAP_IN(" in line and not line.startswith("#define"):
+            assert line.startswith("#if ") and cond is None, line
+            cond, body = tuple(int(p) for p in re.findall(r"EGOTAP_IN\((\d)\)", line)), []
+            assert line == "#if " + " || ".join(f"EGOTAP_IN({p})" for p in cond), line
+        elif cond is not None and re.match(r"#\s*(else|elif)", line):
+            raise AssertionError("a part guard has one branch")
+        elif cond is not None and line.startswith("#endif"):
+            runs.append((cond, any(not l.startswith("#include") for l in body)))
+            cond = None
+        elif cond is not None and line:
+            assert not re.match(r"#\s*if", line), "nothing conditional inside a part guard: " + line
+            body.append(line)
+    sections = [c for c, has_code in runs if has_code]
+    shared = [c for c in sections if len(c) > 1]
+    assert len(set(shared)) == len(shared) >= 1 and sections[:len(shared)] == shared, sections
+    assert sections[len(shared):] == [(0,), (1,), (2,), (3,), (0,)], sections
+    everything = "\n".join(code.values())
+    for name in L.exported_symbols():
+        assert len(re.findall(rf'extern\s+"C"[^;{{}}()]*\b{name}\s*\(', everything)) == 1, name
+
+
+@pytest.mark.parametrize("part", [0, 1, 2, 3, None])
+def test_no_part_sees_an_abi_helper_it_does_not_use(part):
+    """A static launcher or kernel a translation unit can see is compiled into its code object whether it launches it or not, so each part
+    (-DEGOTAP_PART=n) must use every function egotap_abi.hip shows it: the host-only syntax pass with -Wunused-function names none that is
+    defined in egotap_abi.hip.  (Kernel headers two parts use different halves of may still warn there:
+    profiles/abi_parts_summary.md lists them.)  Built as a single translation unit (no part) nothing at all is unused.  The opposite mistake
+    is an error in the same pass: a part that calls a static launcher whose defining header it was not given (-Werror=undefined-internal; the
+    build itself only warns, and the shared library would link with the symbol missing)."""
+    import subprocess
+    try:
+        hipcc = L._build._hipcc()
+    except RuntimeError:
+        pytest.skip("hipcc not found")
+    csrc = os.path.join(REPO, "egotap_amd", "csrc")
+    cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"), "-I" + csrc]
+    cmd += [] if part is None else [f"-DEGOTAP_PART={part}"]
+    cmd += ["--cuda-host-only", "-fsyntax-only", "-Wunused-function", "-Werror=undefined-internal", os.path.join(csrc, "egotap_abi.hip")]
+    res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-4000:]
+    unused = re.findall(r"^(\S+?):\d+:\d+: warning: unused function '(\w+)'", res.stderr, flags=re.M)
+    assert "unused function" not in re.sub(r"^\S+?:\d+:\d+: warning: unused function '\w+'", "", res.stderr, flags=re.M)      # every such warning was parsed
+    assert not [(f, n) for f, n in unused if os.path.basename(f) == "egotap_abi.hip"]
+    if part is None:
+        assert not unused
+
+
 def _cfg(**kw):
     base = dict(n_joints_hm=15, estimate_head=1, hm_size=64, hidden=128, vit_dim=1024, vit_heads=8, vit_layers=3,
                 patch=16, pu_hidden=512)
