@@ -50,6 +50,7 @@
 #include "rgb_u8.h"
 #include "rgb_u8_resize.h"
 #include "yuv_u8_resize.h"
+#include "lens_remap.h"
 #include "heatmap_peaks.h"
 #include "limb_decode.h"
 #include "ocam.h"
@@ -1540,11 +1541,16 @@ static int hm_resolve(Handle* h, int net) {
 // flag per eye; each piece is resized into `slice` (chunk x 2 x 3 S0^2 bytes of the caller's workspace) and read there as camera bytes
 // `yuv` (egotap_predict_pose_sensor_yuv only): the frames are NV12 / YUYV of that layout and colour, frame_stride bytes each; the piece is converted
 // and resized into the same slice by yuv_u8_resize_kernel
+// `lens` (egotap_predict_pose_lens only): the frames are another lens's, of that layout; the piece is gathered into the same slice through the two
+// lens maps (lens_remap_kernel) -- rect and mirror are not read then
 struct HmSensor {
     const unsigned char *left8, *right8;
     int H, W, rect[2][4], mirror[2];
     unsigned char* slice;
     const YuvSource* yuv = nullptr;
+    const LensSource* lens = nullptr;
+    const int *map_left = nullptr, *map_right = nullptr;
+    unsigned fill[2] = {0u, 0u};
 };
 struct HmSrc {
     const float *left, *right;
@@ -2285,13 +2291,17 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
         // byte-source stems at sides 64 / 128 and go through the converter into its slice elsewhere (never with the hand-off: that exists at sides
         // 64 / 128 only).
         unsigned char* s8l = sensor.slice;
-        const long frame = sensor.yuv ? sensor.yuv->frame_stride : 3L * sensor.H * sensor.W;
+        const long frame = sensor.lens ? sensor.lens->frame_stride : sensor.yuv ? sensor.yuv->frame_stride : 3L * sensor.H * sensor.W;
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
             HmSrc piece = whole.at(lo, rgb);
             if (resize) {
                 unsigned char* s8r = s8l + (size_t)n * rgb;
-                if (sensor.yuv) {
+                if (sensor.lens) {
+                    GemmTimer t(h, (hipStream_t)stream, "lens_remap", "lens_remap_kernel", 0.0);
+                    EGO_HIP(lens_remap_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, *sensor.lens, sensor.map_left, sensor.map_right,
+                                              sensor.fill[0], sensor.fill[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
+                } else if (sensor.yuv) {
                     GemmTimer t(h, (hipStream_t)stream, "yuv_u8_resize", "yuv_u8_resize_kernel", 0.0);
                     EGO_HIP(yuv_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, *sensor.yuv, sensor.rect[0], sensor.rect[1],
                                                  sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
@@ -2577,6 +2587,90 @@ extern "C" int egotap_predict_pose_sensor_yuv_kpl(egotap_handle h, const uint8_t
                                                   void* stream, float* keypoints, float* limbs) {
     return predict_pose_sensor_yuv_entry("egotap_predict_pose_sensor_yuv_kpl", h, left8, right8, B, src, rects, mirrors, table, pose, heatmaps, chunk, ws, ws_bytes,
                                          stream, false, keypoints, limbs);
+}
+
+// ---- frames from another lens: the lens maps applied as a bilinear gather (lens_remap.h), standalone and in front of the one call
+// what is wrong with a descriptor or the frames behind it, or nullptr; fills `q` (layout, fetch and integer coefficients) when nothing is
+static const char* lens_source_refusal(const egotap_lens_source* src, const void* left8, const void* right8, LensSource* q) {
+    if (!src) return "null source descriptor (egotap_lens_source)";
+    if (src->struct_size != (int32_t)sizeof(egotap_lens_source)) return "wrong struct_size (sizeof(egotap_lens_source) expected)";
+    if (src->format != EGOTAP_LENS_RGB8 && src->format != EGOTAP_LENS_NV12 && src->format != EGOTAP_LENS_YUYV)
+        return "unknown format (EGOTAP_LENS_RGB8, EGOTAP_LENS_NV12 or EGOTAP_LENS_YUYV)";
+    if (src->format == EGOTAP_LENS_RGB8) {
+        if (src->H < 1 || src->W < 1 || src->H > kResizeMaxSrc || src->W > kResizeMaxSrc) return "the frame height and width must be between 1 and 16384";
+        if (!left8 || !right8) return "null frames (left8 and right8 are required)";
+        *q = lens_source_rgb8(src->H, src->W);
+    } else {
+        if (src->yuv.format != (src->format == EGOTAP_LENS_NV12 ? EGOTAP_YUV_NV12 : EGOTAP_YUV_YUYV)) return "the embedded egotap_yuv_source has another format than the descriptor";
+        if (src->yuv.H != src->H || src->yuv.W != src->W) return "the embedded egotap_yuv_source has another H or W than the descriptor";
+        YuvSource y{};
+        if (const char* why = yuv_source_refusal(&src->yuv, left8, right8, &y)) return why;
+        *q = lens_source_yuv(y);
+    }
+    if (!src->map_left || !src->map_right) return "null lens map (map_left and map_right are device int32 [S0 * S0][2])";
+    if ((((uintptr_t)src->map_left | (uintptr_t)src->map_right) & 15) != 0) return "map_left and map_right must be 16-byte aligned (four entries are two 16-byte loads)";
+    return nullptr;
+}
+extern "C" int egotap_lens_remap(const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S0, uint8_t* out_left8, uint8_t* out_right8,
+                                 void* stream) {
+    static const char* const who = "egotap_lens_remap";
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
+    LensSource q{};
+    const char* why = lens_source_refusal(src, left8, right8, &q);
+    EGO_CHECK(!why, "%s: %s", who, why);
+    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
+    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
+    EGO_HIP(lens_remap_launch(left8, right8, B, q, (const int*)src->map_left, (const int*)src->map_right, lens_fill(src->fill[0]), lens_fill(src->fill[1]), S0,
+                              out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_predict_pose_lens_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes) {
+    static const char* const who = "egotap_predict_pose_lens_workspace_bytes";
+    EGO_CHECK(h && bytes, "%s: null argument", who);
+    EGO_CHECK(B >= 0 && chunk >= 0, "%s: negative batch or chunk", who);
+    *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_SENSOR).total;      // the sensor entry's: the slice holds OUTPUT frames
+    return EGOTAP_OK;
+}
+// the sensor entry with the descriptor in place of H, W, rectangles and mirrors: the same checks in the same order, the same walk.  The keypoints
+// come out in the model camera's calibration pixels: the sensor entry's affine on a frame of that size, the full rectangle, the eye's mirror flag
+static int predict_pose_lens_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* lsrc,
+                                   const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints,
+                                   float* limbs) {
+    LensSource lens{};
+    const char* why = lens_source_refusal(lsrc, left8, right8, &lens);
+    if (!why && (lsrc->model_h < 1 || lsrc->model_w < 1 || lsrc->model_h > kResizeMaxSrc || lsrc->model_w > kResizeMaxSrc))
+        why = "the model camera's calibration image (model_h, model_w) must be between 1 and 16384 on each side";
+    if (!why && !table) why = "null table (the fp32 [3][256] value table is required)";
+    if (!why && ((uintptr_t)table & 15) != 0) why = "the table must be 16-byte aligned";
+    const int rc = rgb_entry_checks(who, h, B, why, nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
+    if (rc != EGOTAP_OK) return rc;
+    HmSensor q{left8, right8, lens.H, lens.W, {{0, 0, lsrc->model_w, lsrc->model_h}, {0, 0, lsrc->model_w, lsrc->model_h}},
+               {lsrc->mirror[0] ? 1 : 0, lsrc->mirror[1] ? 1 : 0}, nullptr};
+    q.lens = &lens;
+    q.map_left = (const int*)lsrc->map_left;
+    q.map_right = (const int*)lsrc->map_right;
+    q.fill[0] = lens_fill(lsrc->fill[0]);
+    q.fill[1] = lens_fill(lsrc->fill[1]);
+    HmSrc src{nullptr, nullptr, nullptr, nullptr, table, nullptr};      // never the identity request: a lens source always gathers
+    src.sensor = &q;
+    float affine[8];
+    sensor_keypoint_affine(h, q, affine);
+    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
+}
+extern "C" int egotap_predict_pose_lens(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
+                                        float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {
+    return predict_pose_lens_entry("egotap_predict_pose_lens", h, left8, right8, B, src, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false, nullptr, nullptr);
+}
+extern "C" int egotap_predict_pose_lens_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
+                                           float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints) {
+    return predict_pose_lens_entry("egotap_predict_pose_lens_kp", h, left8, right8, B, src, table, pose, heatmaps, chunk, ws, ws_bytes, stream, true, keypoints,
+                                   nullptr);
+}
+extern "C" int egotap_predict_pose_lens_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
+                                            float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints, float* limbs) {
+    return predict_pose_lens_entry("egotap_predict_pose_lens_kpl", h, left8, right8, B, src, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false, keypoints,
+                                   limbs);
 }
 
 // the standalone operator: maps c0 .. c0 + n - 1 of each image of a [B, C, S, S] tensor -> [B, n, 4] records; no handle

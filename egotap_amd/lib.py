@@ -35,6 +35,14 @@ class EgotapYuvSource(C.Structure):                   # egotap.h egotap_yuv_sour
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "format", "matrix", "range", "H", "W", "pitch")] + [("uv_offset", C.c_int64), ("frame_stride", C.c_int64)]
 
 
+class EgotapLensSource(C.Structure):                  # egotap.h egotap_lens_source: eight int32, two device pointers, six fill bytes (then padding), the yuv source
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "format", "H", "W", "model_h", "model_w")] + [("mirror", C.c_int32 * 2), ("map_left", C.c_void_p),
+                ("map_right", C.c_void_p), ("fill", (C.c_uint8 * 3) * 2), ("yuv", EgotapYuvSource)]
+
+
+LENS_FORMATS = {"rgb8": 0, "nv12": 1, "yuyv": 2}     # egotap.h EGOTAP_LENS_RGB8 / _NV12 / _YUYV
+
+
 class EgotapError(RuntimeError):
     pass
 
@@ -93,6 +101,15 @@ _PROTOS = {
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "egotap_predict_pose_sensor_yuv_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapYuvSource), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- frames from another lens: the descriptor (format, H, W, the two device maps, fills) in place of H, W, rectangles and mirrors
+    "egotap_lens_remap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_lens_workspace_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "egotap_predict_pose_lens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_predict_pose_lens_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_lens_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # ---- the fisheye camera model and the stereo triangulation of the keypoints: three operators, no handle
     "egotap_ocam_project": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
     "egotap_ocam_unproject": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
@@ -450,6 +467,112 @@ def yuv_u8_resize(left8, right8, layout, colour, S0, rect_left=None, rect_right=
     with torch.cuda.device(left8.device):
         check(load().egotap_yuv_u8_resize(_ptr(left8), _ptr(right8), B, C.byref(yuv_source(layout, colour)), rl, rr, int(bool(mirror_left)),
                                           int(bool(mirror_right)), int(S0), _ptr(out_l), _ptr(out_r), _stream(left8.device)))
+    return out_l, out_r
+
+
+class LensMaps:
+    """A rig's two lens maps on the device (``lens_maps``): ``left`` / ``right`` the ``spec.LensMap`` of each eye, ``map_left`` / ``map_right`` their
+    taps as int32 [S0 * S0, 2] device tensors (uploaded once, kept alive here), ``fill`` the (R, G, B) of an invalid pixel per eye."""
+
+    def __init__(self, left, right, map_left, map_right, fill):
+        self.left, self.right, self.map_left, self.map_right, self.fill = left, right, map_left, map_right, fill
+        self.S0, self.H, self.W, self.model_size = left.S0, left.H, left.W, left.model_size
+        self.mirrors = (int(left.mirror), int(right.mirror))
+
+    @property
+    def key(self):
+        """what tells two uploads apart in a capture key: both map addresses and the fill"""
+        return (self.map_left.data_ptr(), self.map_right.data_ptr(), self.fill)
+
+
+def lens_maps(left, right, fill=(0, 0, 0), device=None):
+    """``LensMaps`` of two ``spec.LensMap`` (left eye, right eye) on ``device`` (None: the current GPU): one upload per rig.  Both maps must share S0,
+    the sensor frame's (H, W) and the model camera's calibration size -- one descriptor serves both eyes; the mirror flags may differ.  ``fill``: three
+    bytes (R, G, B) for both eyes, or a pair of them (left, right)."""
+    import numpy as np
+    import torch
+    from . import spec as _spec
+    for m in (left, right):
+        if not isinstance(m, _spec.LensMap):
+            raise ValueError(f"lens_maps: left and right are spec.LensMap (spec.lens_map builds one per eye), got {type(m).__name__}")
+    if left.S0 != right.S0:
+        raise ValueError(f"lens_maps: both eyes' maps must have one output side, got S0 = {left.S0} / {right.S0}")
+    if (left.H, left.W) != (right.H, right.W):
+        raise ValueError(f"lens_maps: both eyes' maps must be built for one frame size, got {left.H} x {left.W} / {right.H} x {right.W}")
+    if left.model_size != right.model_size:
+        raise ValueError(f"lens_maps: both eyes' maps must share the model camera's calibration size, got {left.model_size} / {right.model_size}")
+    if left.S0 % 4 or left.S0 > 4096:
+        raise ValueError(f"lens_maps: the output side must be a multiple of 4, at most 4096, got S0 = {left.S0}")
+    def triple(f):
+        return hasattr(f, "__len__") and len(f) == 3 and all(isinstance(v, (int, np.integer)) and 0 <= v <= 255 for v in f)
+    both = (fill, fill) if triple(fill) else fill
+    if not (hasattr(both, "__len__") and len(both) == 2 and all(triple(f) for f in both)):
+        raise ValueError(f"lens_maps: fill is three bytes (R, G, B), or one such triple per eye, got {fill}")
+    fill = tuple(tuple(int(v) for v in f) for f in both)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise EgotapError("lens_maps: the maps live on the GPU (no CPU fallback); pass a cuda device")
+    up = [torch.from_numpy(np.array(m.taps).reshape(m.S0 * m.S0, 2)).to(dev) for m in (left, right)]
+    if any(t.data_ptr() % 16 for t in up):
+        raise EgotapError("lens_maps: a device map is not 16-byte aligned")
+    return LensMaps(left, right, up[0], up[1], fill)
+
+
+def lens_source(maps, layout=None, colour=None):
+    """the egotap_lens_source of a ``LensMaps`` and the frames' kind: ``layout`` None for uint8 [B, H, W, 3], or a ``spec.YuvLayout`` with its
+    ``spec.YuvColour``"""
+    d = EgotapLensSource()
+    d.struct_size, d.H, d.W = C.sizeof(EgotapLensSource), maps.H, maps.W
+    d.format = LENS_FORMATS["rgb8" if layout is None else layout.format]
+    d.model_h, d.model_w = maps.model_size
+    d.mirror[0], d.mirror[1] = maps.mirrors
+    d.map_left, d.map_right = maps.map_left.data_ptr(), maps.map_right.data_ptr()
+    for e in range(2):
+        for c in range(3):
+            d.fill[e][c] = maps.fill[e][c]
+    if layout is not None:
+        d.yuv = yuv_source(layout, colour)
+    return d
+
+
+def check_lens_frames(who, left8, right8, maps, layout=None, colour=None):
+    """the one wording of what the lens entries take: a ``LensMaps`` on the frames' device, and frames of the size the maps were built for --
+    ``check_sensor_frames``' (``layout`` None) or ``check_yuv_frames``' (a ``spec.YuvLayout`` with a ``spec.YuvColour``); returns B"""
+    from . import spec as _spec
+    if not isinstance(maps, LensMaps):
+        raise ValueError(f"{who}: maps is what lens_maps returns (the rig's two uploaded spec.LensMap), got {type(maps).__name__}")
+    if layout is None:
+        B, H, W = check_sensor_frames(who, left8, right8)
+    else:
+        if not isinstance(layout, _spec.YuvLayout) or not isinstance(colour, _spec.YuvColour):
+            raise ValueError(f"{who}: layout is a spec.YuvLayout (or None for uint8 [B, H, W, 3]) and colour a spec.YuvColour, got "
+                             f"{type(layout).__name__} / {type(colour).__name__}")
+        B, H, W = check_yuv_frames(who, left8, right8, layout), layout.H, layout.W
+    if (H, W) != (maps.H, maps.W):
+        raise ValueError(f"{who}: the maps were built for {maps.H} x {maps.W} frames, got {H} x {W} (spec.lens_map(..., frame_size=(H, W)))")
+    if maps.map_left.device != left8.device:
+        raise EgotapError(f"{who}: the maps are on {maps.map_left.device}, the frames on {left8.device}")
+    return B
+
+
+def lens_remap(left8, right8, maps, S0, layout=None, colour=None):
+    """frames from another lens x 2 -> camera bytes uint8 [B, S0, S0, 3] x 2 (egotap_lens_remap): each eye gathered bilinearly through its lens map
+    (``lens_maps``), the fill bytes where the sensor does not see the model camera's pixel -- equal to spec.lens_remap_u8 bit for bit.  ``layout``
+    None: uint8 [B, H, W, 3]; a ``spec.YuvLayout``: NV12 / YUYV frames (``check_yuv_frames``), each tap converted with ``colour`` (default bt601
+    limited) first -- equal to spec.lens_remap_u8(spec.yuv_to_rgb_u8(frames, layout, colour), map).  One launch for both eyes."""
+    import torch
+    from . import spec as _spec
+    colour = _spec.YuvColour() if colour is None else colour
+    B = check_lens_frames("lens_remap", left8, right8, maps, layout, colour)
+    if int(S0) != maps.S0:
+        raise ValueError(f"lens_remap: the maps were built for S0 = {maps.S0}, got S0 = {S0}")
+    out_l = torch.empty((B, maps.S0, maps.S0, 3), dtype=torch.uint8, device=left8.device)
+    out_r = torch.empty_like(out_l)
+    if B == 0:
+        return out_l, out_r
+    with torch.cuda.device(left8.device):
+        check(load().egotap_lens_remap(_ptr(left8), _ptr(right8), B, C.byref(lens_source(maps, layout, colour)), maps.S0, _ptr(out_l), _ptr(out_r),
+                                       _stream(left8.device)))
     return out_l, out_r
 
 

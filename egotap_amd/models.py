@@ -96,7 +96,7 @@ class PoseTracker:
 
 
 class _Source(NamedTuple):
-    """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor / _sensor_yuv); everything else about a request is ``_serve``'s."""
+    """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor / _sensor_yuv / _lens); everything else about a request is ``_serve``'s."""
     who: str                          # the entry's name, for messages
     left: torch.Tensor                # the frames as the ABI entry reads them (a graph's static inputs are clones of these) ...
     right: torch.Tensor
@@ -782,6 +782,58 @@ class EgoTAPAutoEncoderModel(nn.Module):
                       kind=("sensor_yuv", layout, colour, rect_l + rect_r, mirrors, table.data_ptr()), keep=(table,), float_frames=float_frames,
                       keypoint_affine=[_spec.sensor_keypoint_affine(rect_l, False, p.hm_size), _spec.sensor_keypoint_affine(rect_r, bool(mirror_right), p.hm_size)],
                       triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the conversion and resize, the converter and the module forwards")
+        return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
+
+    def lens_maps(self, left, right, fill=(0, 0, 0), device=None):
+        """The rig's two lens maps for ``predict_pose_from_lens``: ``left`` / ``right`` a ``spec.LensMap`` each (``spec.lens_map(model_camera,
+        sensor, 4 * hm_size, R, frame_size, mirror)``), uploaded ONCE to ``device`` (None: the current GPU); returns the handle object that keeps the
+        device tensors (``lib.LensMaps``).  Refused by name: maps whose S0 is not 4 * hm_size, and maps that differ between the eyes in S0, the
+        sensor frame's (H, W) or the model camera's calibration size (one descriptor serves both eyes).  ``fill``: the (R, G, B) of a pixel the
+        sensor does not see, for both eyes or one triple per eye."""
+        S0 = 4 * self.net_AutoEncoder.preset.hm_size
+        for m in (left, right):
+            if isinstance(m, _spec.LensMap) and m.S0 != S0:
+                raise ValueError(f"lens_maps: the estimators read {S0} x {S0} frames (4 * hm_size), the map was built for S0 = {m.S0}")
+        return _lib.lens_maps(left, right, fill, device)
+
+    @torch.no_grad()
+    def predict_pose_from_lens(self, left8, right8, maps, layout=None, colour=_spec.YuvColour("bt601", "limited"), return_heatmaps=False, graphed=False,
+                               return_keypoints=False, return_limbs=False, return_triangulation=False):
+        """predict_pose_from_sensor for a rig whose lens is not the one the estimators were trained on: stereo frames of the sensor's own H x W ->
+        pose [B, J(+1), 3].  ``maps`` (``lens_maps``) says per eye where in the sensor's frame each pixel of the model camera's 4S x 4S frame is
+        sampled; ``layout`` None: uint8 [B, H, W, 3] frames, a ``spec.YuvLayout``: the camera's NV12 / YUYV buffer with its ``colour``.  ONE library
+        call (egotap_predict_pose_lens) on the serving handle: the caller's cv2.remap on the host and the three-bytes-per-pixel upload are gone -- the
+        library gathers chunk by chunk into the sensor entry's workspace slice (lens_remap_kernel) and the byte source reads that slice.  The bits are
+        those of predict_pose_from_camera on ``spec.lens_remap_u8(frames, map, fill)`` (for YUV: of the frames ``spec.yuv_to_rgb_u8`` gives), the
+        integer restatement of the gather.  A lens source always gathers: there is no in-place identity request.
+
+        ``return_keypoints`` / ``return_limbs``: as predict_pose_from_sensor, in pixels of the MODEL camera's calibration image
+        (egotap_predict_pose_lens_kp / _kpl): per eye ``spec.sensor_keypoint_affine((0, 0, model_w, model_h), mirror, S)``;
+        ``spec.lens_map_points`` takes them on to the sensor's frame for drawing.  ``return_triangulation``: as predict_pose_from_sensor, with the
+        identity as the pixel affine -- the rig of ``set_stereo_rig`` is then the two MODEL cameras, with the R and t of the virtual rig the maps
+        render.  ``graphed``: as predict_pose_from_sensor; the capture key holds the source kind, the format, the layout, the colour, both map addresses,
+        the fill and the table.  Configurations one handle cannot express (Bottleneck backbones, mixed backbones or precisions) run egotap_lens_remap
+        followed by predict_pose_from_camera's fallback -- by name, ungraphed."""
+        p = self.net_AutoEncoder.preset
+        S0 = 4 * p.hm_size
+        who = "predict_pose_from_lens"
+        B = _lib.check_lens_frames(who, left8, right8, maps, layout, colour)
+        if maps.S0 != S0:
+            raise ValueError(f"{who}: the estimators read {S0} x {S0} frames (4 * hm_size), the maps were built for S0 = {maps.S0}")
+        lib, table = _lib.load(), self.camera_table(left8.device)
+        desc = _lib.lens_source(maps, layout, colour)
+        model_h, model_w = maps.model_size
+
+        def float_frames():
+            return _lib.rgb_u8_to_f32(*_lib.lens_remap(left8, right8, maps, S0, layout, colour), table)
+        src = _Source(who, left8, right8, B, lib.egotap_predict_pose_lens_workspace_bytes,
+                      (lib.egotap_predict_pose_lens, lib.egotap_predict_pose_lens_kp, lib.egotap_predict_pose_lens_kpl),
+                      (B, C.byref(desc), ptr(table)),
+                      kind=("lens", "rgb8" if layout is None else layout.format, layout, colour if layout is not None else None) + maps.key
+                      + (maps.H, maps.W, maps.model_size, maps.mirrors, table.data_ptr()),
+                      keep=(table, maps, desc), float_frames=float_frames,
+                      keypoint_affine=[_spec.sensor_keypoint_affine((0, 0, model_w, model_h), bool(m), p.hm_size) for m in maps.mirrors],
+                      triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the lens remap, the converter and the module forwards")
         return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
     def new_pose_tracker(self, streams=1, params=None):

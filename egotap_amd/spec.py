@@ -634,7 +634,7 @@ STEREO_MIN_SCORE = 0.5                         # target maps peak at 1 for a joi
 class OcamModel:
     """One camera's OCamCalib model as the reference reads it (utils/projection.py:13-50): ``pol`` the cam2world polynomial in the pixel
     radius (polynomialC2W), ``invpol`` the world2cam polynomial in the elevation angle (polynomialW2C), the centre (xc, yc) -- xc multiplies
-    the FIRST pixel coordinate, as in world2cam -- and the affine (c, d, e).  ``size`` and ``radius`` are carried, not used."""
+    the FIRST pixel coordinate, as in world2cam -- and the affine (c, d, e).  ``size`` (h, w) and ``radius`` (the image circle, 0: none) are carried; only ``lens_map`` reads them."""
     name: str
     pol: tuple
     invpol: tuple
@@ -839,6 +839,170 @@ def stereo_triangulate_ref(keypoints, left: OcamModel, right: OcamModel, t, R=No
         frame = np.stack([that[:, 0], that[:, 1], that[:, 2], n, np.sqrt(s2d / nn), mxd, np.sqrt(s2g / nn), mxg], axis=-1)
         frame = np.where((n > 0)[:, None], frame, 0.0)
     return rec.astype(dtype), frame.astype(dtype)
+
+
+# ---- frames from another lens -> the model camera's frame (egotap.h: egotap_lens_remap / egotap_predict_pose_lens) -----------------------
+LENS_FRAC_BITS = 11                            # a map entry is a sensor pixel coordinate in Q11: the resize's weight precision
+LENS_MAX_SIDE = 16384                          # H, W <= 16384, as for the resize: an entry stays below 2^25
+LENS_INVALID = -1                              # both halves of an entry whose output pixel has no source: the kernel writes the fill bytes
+
+
+@dataclass(frozen=True, eq=False)
+class LensMap:
+    """One eye's lens map (``lens_map`` builds it): ``taps`` int32 [S0, S0, 2], entry (Y, X) = (fx, fy), the Q11 pixel coordinates in the H x W
+    sensor frame that output pixel (X, Y) of the S0 x S0 frame the stems read is sampled at, or (-1, -1) where it has none.  ``model_size`` is
+    (h, w) of the model camera's calibration image -- the units keypoints come back in -- and ``mirror`` whether output column X shows the model
+    camera's column S0 - 1 - X.  The array is read-only: a map is uploaded once and reused for every frame of the rig."""
+    taps: object
+    S0: int
+    H: int
+    W: int
+    model_size: tuple
+    mirror: bool = False
+
+    def __post_init__(self):
+        import numpy as np
+        S0, H, W = int(self.S0), int(self.H), int(self.W)
+        if S0 < 1 or not (1 <= H <= LENS_MAX_SIDE and 1 <= W <= LENS_MAX_SIDE):
+            raise ValueError(f"LensMap: S0 must be positive and the frame height and width between 1 and {LENS_MAX_SIDE}, got S0 = {S0}, {H} x {W}")
+        t = np.asarray(self.taps)
+        if t.dtype != np.int32 or t.shape != (S0, S0, 2):
+            raise ValueError(f"LensMap: taps are int32 [{S0}, {S0}, 2], got {t.dtype} {t.shape}")
+        t = np.ascontiguousarray(t).copy()
+        ok = t[..., 0] >= 0
+        if np.any((t[..., 1] >= 0) != ok) or np.any(t[~ok] != LENS_INVALID):
+            raise ValueError("LensMap: an entry is valid in both halves or (-1, -1)")
+        if np.any(t[..., 0][ok] > (W - 1) << LENS_FRAC_BITS) or np.any(t[..., 1][ok] > (H - 1) << LENS_FRAC_BITS):
+            raise ValueError(f"LensMap: an entry lies outside the {H} x {W} frame")
+        t.setflags(write=False)
+        size = tuple(int(v) for v in self.model_size)
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError(f"LensMap: model_size is (h, w) of the model camera's calibration image, got {self.model_size}")
+        for k, v in (("taps", t), ("S0", S0), ("H", H), ("W", W), ("model_size", size), ("mirror", bool(self.mirror))):
+            object.__setattr__(self, k, v)
+
+    @property
+    def valid(self):
+        """bool [S0, S0]: the output pixels that have a source"""
+        return self.taps[..., 0] >= 0
+
+
+def _lens_frame_size(who, sensor: OcamModel, frame_size):
+    H, W = (int(v) for v in (sensor.size if frame_size is None else frame_size))
+    if not (1 <= H <= LENS_MAX_SIDE and 1 <= W <= LENS_MAX_SIDE):
+        raise ValueError(f"{who}: the frame height and width must be between 1 and {LENS_MAX_SIDE}, got {H} x {W}")
+    return H, W
+
+
+def _lens_chain(uv, model: OcamModel, sensor: OcamModel, R, frame):
+    """model-camera calibration pixels [..., 2] -> (pixels of the sensor's H x W frame, pixels of the sensor's calibration image), float64"""
+    import numpy as np
+    ray = ocam_cam2world_ref(uv, model)
+    if R is not None:
+        R = np.asarray(R, dtype=np.float64)
+        if R.shape != (3, 3):
+            raise ValueError(f"lens map: R is 3 x 3 (the model camera's axes in the sensor camera's frame), got {R.shape}")
+        with np.errstate(all="ignore"):
+            ray = ray @ R.T
+    cal = ocam_world2cam_ref(ray, sensor)
+    H, W = frame
+    with np.errstate(all="ignore"):
+        xs = cal[..., 0] if W == sensor.size[1] else (cal[..., 0] + 0.5) * (W / sensor.size[1]) - 0.5
+        ys = cal[..., 1] if H == sensor.size[0] else (cal[..., 1] + 0.5) * (H / sensor.size[0]) - 0.5
+    return np.stack([xs, ys], axis=-1), cal
+
+
+def lens_map(model: OcamModel, sensor: OcamModel, S0: int, R=None, frame_size=None, mirror: bool = False) -> LensMap:
+    """The lens map of one eye, in float64 numpy on the host, once per rig: where in the SENSOR's frame each pixel of the S0 x S0 frame the stems
+    read is sampled, so that the stems see what the MODEL camera (the lens the estimators were trained on) would have seen.
+
+    For output pixel (X, Y), with X' = S0 - 1 - X if ``mirror`` else X:
+        u = (X' + 0.5) * model.size[1] / S0 - 0.5,  v = (Y + 0.5) * model.size[0] / S0 - 0.5      (calibration pixel, align_corners=False)
+        ray = ocam_cam2world_ref((u, v), model);  ray_s = R @ ray  (R 3 x 3: the model camera's axes in the sensor camera's frame; None: identity)
+        (xs, ys) = ocam_world2cam_ref(ray_s, sensor)
+    ``frame_size`` = (H, W) of the frames the sensor delivers, by default ``sensor.size``; another size scales the calibration pixels per axis by
+    (p + 0.5) * ratio - 0.5.  The entry is valid when xs, ys are finite, 0 <= xs <= W - 1 and 0 <= ys <= H - 1, and -- for a model with
+    ``radius`` > 0 -- (u, v) lies inside the model's image circle and the sensor's calibration pixel inside the sensor's.  THE IMAGE CIRCLES ARE
+    THE ONLY GUARD against a polynomial that extrapolates outside its field of view: a calibration with radius 0 is believed wherever its
+    polynomial lands inside the frame.  A valid entry is (floor(xs * 2048 + 0.5), floor(ys * 2048 + 0.5)) (Q11, below 2^25), an invalid one
+    (-1, -1)."""
+    import numpy as np
+    S0 = int(S0)
+    if S0 < 1:
+        raise ValueError(f"lens_map: the output side must be positive, got {S0}")
+    H, W = _lens_frame_size("lens_map", sensor, frame_size)
+    X, Y = np.meshgrid(np.arange(S0, dtype=np.float64), np.arange(S0, dtype=np.float64))
+    if mirror:
+        X = S0 - 1 - X
+    u = (X + 0.5) * (model.size[1] / S0) - 0.5
+    v = (Y + 0.5) * (model.size[0] / S0) - 0.5
+    pix, cal = _lens_chain(np.stack([u, v], axis=-1), model, sensor, R, (H, W))
+    xs, ys = pix[..., 0], pix[..., 1]
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(xs) & np.isfinite(ys) & (xs >= 0) & (xs <= W - 1) & (ys >= 0) & (ys <= H - 1)
+        if model.radius > 0:
+            ok &= np.hypot(u - model.xc, v - model.yc) <= model.radius
+        if sensor.radius > 0:
+            ok &= np.hypot(cal[..., 0] - sensor.xc, cal[..., 1] - sensor.yc) <= sensor.radius
+    one = float(1 << LENS_FRAC_BITS)
+    taps = np.stack([np.floor(np.where(ok, xs, 0.0) * one + 0.5), np.floor(np.where(ok, ys, 0.0) * one + 0.5)], axis=-1).astype(np.int32)
+    taps[~ok] = LENS_INVALID
+    return LensMap(taps, S0, H, W, tuple(model.size), bool(mirror))
+
+
+def lens_map_points(points_xy, model: OcamModel, sensor: OcamModel, R=None, frame_size=None):
+    """Model-camera calibration pixels [..., 2] -> pixels of the sensor's frame, float64, through the chain of ``lens_map`` (no validity test:
+    a point outside either lens comes back wherever the polynomials put it, or NaN).  For drawing the keypoints a lens entry returns -- they are
+    in the model camera's calibration pixels -- over the frame the sensor delivered.  Host only."""
+    import numpy as np
+    q = np.array(points_xy, dtype=np.float64)
+    if q.shape[-1] != 2:
+        raise ValueError(f"lens_map_points: points are [..., 2], got {q.shape}")
+    return _lens_chain(q, model, sensor, R, _lens_frame_size("lens_map_points", sensor, frame_size))[0]
+
+
+def lens_taps(lens: LensMap):
+    """The integer taps the kernel derives from a map: int64 numpy arrays (valid, ix0, ix1, wx1, iy0, iy1, wy1), each [S0, S0]:
+    ix0 = fx >> 11, wx1 = fx & 2047, ix1 = min(ix0 + 1, W - 1), likewise in y; zeros where the entry is invalid."""
+    import numpy as np
+    ok = lens.valid
+    fx, fy = (np.where(ok, lens.taps[..., k], 0).astype(np.int64) for k in (0, 1))
+    mask = (1 << LENS_FRAC_BITS) - 1
+    ix0, iy0 = fx >> LENS_FRAC_BITS, fy >> LENS_FRAC_BITS
+    return ok, ix0, np.minimum(ix0 + 1, lens.W - 1), fx & mask, iy0, np.minimum(iy0 + 1, lens.H - 1), fy & mask
+
+
+def lens_remap_u8(frames, lens: LensMap, fill=(0, 0, 0)):
+    """The whole remap, restated in integers on the host: frames uint8 [n, H, W, 3] (numpy array or torch tensor on any device) of the map's H x W
+    -> uint8 [n, S0, S0, 3] of the same kind.  With the taps of ``lens_taps`` and wx0 = 2048 - wx1, wy0 = 2048 - wy1:
+
+        out = (wy0 (wx0 p[iy0][ix0] + wx1 p[iy0][ix1]) + wy1 (wx0 p[iy1][ix0] + wx1 p[iy1][ix1]) + 2^21) >> 22        (``resize_u8``'s formula)
+
+    and the ``fill`` bytes (R, G, B) where the entry is invalid.  This is what lens_remap_kernel computes, bit for bit.  For an NV12 / YUYV source
+    the definition is ``lens_remap_u8(yuv_to_rgb_u8(frames, layout, colour), lens)``: nothing is interpolated in YUV."""
+    import numpy as np
+    import torch
+    if not isinstance(lens, LensMap):
+        raise ValueError(f"lens_remap_u8: the map is a spec.LensMap, got {type(lens).__name__}")
+    is_np = isinstance(frames, np.ndarray)
+    x = torch.from_numpy(frames) if is_np else frames
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"lens_remap_u8: frames are uint8 [n, H, W, 3], got {x.dtype} {tuple(x.shape)}")
+    if (int(x.shape[1]), int(x.shape[2])) != (lens.H, lens.W):
+        raise ValueError(f"lens_remap_u8: the map was built for {lens.H} x {lens.W} frames, got {int(x.shape[1])} x {int(x.shape[2])} "
+                         "(build it with frame_size=(H, W))")
+    fill = tuple(int(v) for v in fill)
+    if len(fill) != 3 or not all(0 <= v <= 255 for v in fill):
+        raise ValueError(f"lens_remap_u8: fill is three bytes (R, G, B), got {fill}")
+    dev = x.device
+    ok, ix0, ix1, wx1, iy0, iy1, wy1 = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in lens_taps(lens))
+    wx1, wy1 = wx1.view(1, lens.S0, lens.S0, 1), wy1.view(1, lens.S0, lens.S0, 1)
+    wx0, wy0 = RESIZE_WEIGHT_ONE - wx1, RESIZE_WEIGHT_ONE - wy1
+    top = wx0 * x[:, iy0, ix0].to(torch.int64) + wx1 * x[:, iy0, ix1].to(torch.int64)
+    bot = wx0 * x[:, iy1, ix0].to(torch.int64) + wx1 * x[:, iy1, ix1].to(torch.int64)
+    out = ((wy0 * top + wy1 * bot + (1 << 21)) >> 22).to(torch.uint8)
+    out = torch.where(ok.view(1, lens.S0, lens.S0, 1), out, torch.tensor(fill, dtype=torch.uint8, device=dev).view(1, 1, 1, 3))
+    return out.numpy() if is_np else out
 
 
 # ---- the pose, the root and the stereo joints filtered over time (egotap.h: egotap_pose_track) ---------------------------------------------

@@ -349,6 +349,59 @@ int egotap_predict_pose_sensor_yuv_kpl(egotap_handle h, const uint8_t* left8, co
                                        const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
                                        float* keypoints, float* limbs);
 
+/* ---- frames from another lens: a per-eye lens map in front of the one call (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * The estimators were trained on one fisheye lens.  A rig with another lens, another image centre or a camera mounted a few degrees off must show
+ * them what THAT lens would have seen; the entries above only crop, mirror and resize.  These entries gather each frame through a LENS MAP: for every
+ * pixel (X, Y) of the S0 x S0 frame the stems read, one entry (fx, fy) of int32 [S0 * S0][2] (row-major, entry Y * S0 + X): the pixel coordinates in
+ * the sensor's H x W frame it is sampled at, in Q11 (pixels * 2048, rounded), or (-1, -1) where the sensor does not see it.  The map is built once
+ * per rig on the host in float64 from the model camera's and the sensor's OCamCalib models and the rotation between them (egotap_amd/spec.py
+ * lens_map: calibration pixel -> ray -> rotated ray -> sensor pixel, valid inside both image circles and the frame) and uploaded by the caller; the
+ * library cannot inspect device memory, so that a map was built for this H x W is the caller's contract -- the kernel clamps every tap to the frame
+ * on both sides, so whatever a map holds no load leaves B * frame bytes.  Per entry, with ix0 = fx >> 11, wx1 = fx & 2047, wx0 = 2048 - wx1,
+ * ix1 = min(ix0 + 1, W - 1), and likewise iy0, wy1, wy0, iy1 from fy:
+ *   byte = (wy0 (wx0 p[iy0][ix0] + wx1 p[iy0][ix1]) + wy1 (wx0 p[iy1][ix0] + wx1 p[iy1][ix1]) + 2^21) >> 22      (the resize's formula, above)
+ * and the eye's fill bytes where the entry is invalid (spec.py lens_remap_u8 restates it on the host; equal bit for bit).  egotap_lens_source:
+ *   struct_size   sizeof(egotap_lens_source)
+ *   format        EGOTAP_LENS_RGB8: uint8 [B, H, W, 3] at any address.  EGOTAP_LENS_NV12 / _YUYV: the camera's buffer, described by the embedded `yuv`
+ *                   (an egotap_yuv_source with the matching format and the same H, W; its rules and the frame alignment are those above); each tap is
+ *                   converted to RGB bytes first -- the result is the RGB8 remap of the converted frame, nothing is interpolated in YUV
+ *   H, W          the sensor frame, 1 .. 16384, the same for both eyes
+ *   model_h, model_w, mirror[2]   the model camera's calibration image and the mirror flag each map was built with: read by the one-call entries only,
+ *                   for the keypoint affine
+ *   map_left, map_right   device pointers, 16-byte aligned, int32 [S0 * S0][2] each
+ *   fill[2][3]    (R, G, B) of an invalid pixel, left eye then right
+ * egotap_lens_remap: the standalone operator; needs no handle, ONE launch for both eyes on the caller's stream, allocates nothing.  S0 a positive
+ *   multiple of 4, at most 4096; outputs uint8 [B, S0, S0, 3], 4-byte aligned.
+ * egotap_predict_pose_lens / _kp / _kpl: egotap_predict_pose_sensor_u8 / _kp / _kpl with the descriptor in place of H, W, rectangles and mirrors -- the
+ *   same walk: each piece is gathered ONCE into the workspace slice of chunk*2*3*S0*S0 bytes (S0 = 4 * hm_size) and both estimators read it as camera
+ *   bytes; hand-off, frozen arenas and the limb records are the sensor entry's.  Keypoints and limb records come out in the MODEL camera's calibration
+ *   pixels: per eye the sensor entry's affine for the rectangle (0, 0, model_w, model_h) and mirror[eye] (ax = model_w / S, bx = 0; mirrored:
+ *   ax = -model_w / S, bx = model_w; ay = model_h / S, by = 0).  Workspace: egotap_predict_pose_lens_workspace_bytes(B, chunk), equal to
+ *   egotap_predict_pose_sensor_u8_workspace_bytes for any frame size.  There is no identity request: a lens source always gathers.  The descriptor is
+ *   host memory read during the call; the maps must stay valid until the stream has run it.
+ * Every refusal is EGOTAP_ERR_INVALID, by name and before any launch: a NULL descriptor, frame, map or output; a wrong struct_size; an unknown
+ * format; H or W outside 1 .. 16384; a map that is not 16-byte aligned; an embedded yuv source of another format, H or W, or one egotap_yuv_u8_resize
+ * refuses (layout, matrix, range, frame alignment); S0 not a positive multiple of 4 up to 4096 or outputs not 4-byte aligned (the operator);
+ * model_h or model_w outside 1 .. 16384 (the one-call entries); B <= 0; and everything the sensor entry refuses about its other arguments. */
+#define EGOTAP_LENS_RGB8 0
+#define EGOTAP_LENS_NV12 1
+#define EGOTAP_LENS_YUYV 2
+typedef struct egotap_lens_source {
+    int32_t struct_size, format, H, W, model_h, model_w, mirror[2];
+    const int32_t *map_left, *map_right;
+    uint8_t fill[2][3];
+    egotap_yuv_source yuv;
+} egotap_lens_source;
+int egotap_lens_remap(const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S0, uint8_t* out_left8, uint8_t* out_right8,
+                      void* stream);
+int egotap_predict_pose_lens_workspace_bytes(egotap_handle h, int B, int chunk, size_t* bytes);
+int egotap_predict_pose_lens(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
+                             float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream);
+int egotap_predict_pose_lens_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
+                                float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints);
+int egotap_predict_pose_lens_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
+                                 float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints, float* limbs);
+
 /* ---- the fisheye camera model and stereo triangulation of the keypoints (additive; EGOTAP_ABI_VERSION stays 2) ----
  * The reference carries each camera as an OCamCalib model (utils/projection.py:13-144): cam2world takes a pixel to a unit ray through the polynomial
  * pol in the pixel radius, world2cam a 3D point to its pixel through the polynomial invpol in the elevation angle, both behind the affine (c, d, e) and the

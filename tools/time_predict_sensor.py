@@ -17,7 +17,16 @@ The same protocol from the camera's own buffer, tight NV12 frames uint8 [B, H * 
   A    colour conversion in torch on the device (planes unpacked, chroma replicated, float BT.601 limited-range matrix, round, clamp, to bytes), then
        predict_pose_from_sensor(crop=..., mirror_right=True) on the RGB frames
   B    predict_pose_from_sensor_yuv(layout, colour, crop=..., mirror_right=True)
-The largest byte difference between A's RGB frames and spec.yuv_to_rgb_u8 is reported (at most 1 is expected: both are within 0.52 of the real value)."""
+The largest byte difference between A's RGB frames and spec.yuv_to_rgb_u8 is reported (at most 1 is expected: both are within 0.52 of the real value).
+
+    python tools/time_predict_sensor.py --lens [--batches 1,8,64] [--sources 1024x1024] [--reps 10] [--rounds 3] [--md OUT]
+
+The lens entry beside the sensor entry on the same RGB frames (report only, nothing is gated; the two arms compute different things):
+  sensor   predict_pose_from_sensor(mirror_right=True): the full frame resized
+  lens     predict_pose_from_lens through the maps of calibration 0 of tests/golden/ocam.npz seen by itself, 0.02 rad about the axis apart, the right
+           eye mirrored
+and, at B = 256, the two standalone kernels (egotap_rgb_u8_resize, egotap_lens_remap) timed with events, with the bytes per second each achieves
+counted the same way for both: per output pixel 3 bytes written and 12 source bytes for a pixel that has a source, plus the lens kernel's 8 map bytes."""
 from __future__ import annotations
 
 import argparse
@@ -124,6 +133,75 @@ def yuv_rows(m, args):
     return rows
 
 
+def fixture_calibration(k=0):
+    """calibration k of tests/golden/ocam.npz (tools/make_golden_ocam.py) as a spec.OcamModel"""
+    import numpy as np
+    g = dict(np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "ocam.npz")))
+    return spec.ocam_from_json({"name": str(g[f"c{k}_name"]), "polynomialC2W": g[f"c{k}_pol"].tolist(), "polynomialW2C": g[f"c{k}_invpol"].tolist(),
+                                "image_center": g[f"c{k}_image_center"].tolist(), "affine": g[f"c{k}_affine"].tolist(), "size": g[f"c{k}_size"].tolist(),
+                                "imageCircleRadius": float(g[f"c{k}_radius"])})
+
+
+def lens_maps_for(m, H, W, S0):
+    import math
+    cam, a = fixture_calibration(0), 0.02
+    R = [[math.cos(a), -math.sin(a), 0.0], [math.sin(a), math.cos(a), 0.0], [0.0, 0.0, 1.0]]
+    return m.lens_maps(spec.lens_map(cam, cam, S0, R, frame_size=(H, W)), spec.lens_map(cam, cam, S0, R, frame_size=(H, W), mirror=True))
+
+
+def kernel_ms(fn, reps):
+    """median of `reps` event-timed calls of a standalone operator"""
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def lens_rows(m, args, S0):
+    rows = []
+    for src in args.sources.split(","):
+        H, W = (int(v) for v in src.split("x"))
+        maps = lens_maps_for(m, H, W, S0)
+        share = float(maps.left.valid.mean() + maps.right.valid.mean()) / 2
+        for mode in ("bf16_frozen", "f32"):
+            for B in [int(b) for b in args.batches.split(",")]:
+                l8, r8 = sensor_frames(B, H, W)
+                configure(m, mode, B)
+                f = {"A": lambda l, r: m.predict_pose_from_sensor(l, r, mirror_right=True), "B": lambda l, r: m.predict_pose_from_lens(l, r, maps)}
+                for name in f:                                           # warm-up (workspaces grown)
+                    timed(f[name], l8, r8, 3)
+                per = {name: [] for name in f}
+                for _ in range(args.rounds):
+                    for name in f:                                       # alternating: sensor, lens, sensor, lens, ...
+                        per[name].append(timed(f[name], l8, r8, args.reps))
+                row = {"mode": mode, "source": f"{H}x{W}", "batch": B, "max_byte_diff_A_B": "n/a", "valid_share": round(share, 4),
+                       **{name: {"rounds_ms": [round(v, 4) for v in vs], "median_ms": round(statistics.median(vs), 4),
+                                 "spread_ms": round(max(vs) - min(vs), 4)} for name, vs in per.items()}}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+        B = 256
+        l8, r8 = sensor_frames(B, H, W)
+        import ctypes as C
+        lib, out_l, out_r = L.load(), torch.empty((B, S0, S0, 3), dtype=torch.uint8, device="cuda"), torch.empty((B, S0, S0, 3), dtype=torch.uint8, device="cuda")
+        full, desc = (C.c_int * 4)(0, 0, W, H), L.lens_source(maps)
+        ops = {"rgb_u8_resize": (lambda: L.check(lib.egotap_rgb_u8_resize(L.ptr(l8), L.ptr(r8), B, H, W, full, full, 0, 1, S0, L.ptr(out_l), L.ptr(out_r), L.stream())), 15.0),
+               "lens_remap": (lambda: L.check(lib.egotap_lens_remap(L.ptr(l8), L.ptr(r8), B, C.byref(desc), S0, L.ptr(out_l), L.ptr(out_r), L.stream())), 12.0 * share + 11.0)}
+        for name, (fn, per_pixel) in ops.items():
+            for _ in range(3):
+                fn()
+            ms = [kernel_ms(fn, args.reps) for _ in range(args.rounds)]
+            nbytes = 2.0 * B * S0 * S0 * per_pixel
+            print(json.dumps({"kernel": name, "source": f"{H}x{W}", "batch": B, "S0": S0, "rounds_ms": [round(v, 4) for v in ms],
+                              "median_ms": round(statistics.median(ms), 4), "counted_bytes": nbytes,
+                              "TB_per_s": round(nbytes / (statistics.median(ms) * 1e-3) / 1e12, 3)}), flush=True)
+    return rows
+
+
 def timed(fn, l, r, reps):
     ts = []
     for _ in range(reps):
@@ -143,6 +221,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--once", action="store_true", help="one call per arm at B = 64 from 1024 x 1024, and the operator alone (for a kernel trace)")
     ap.add_argument("--yuv", action="store_true", help="the NV12 arms: torch conversion + predict_pose_from_sensor against predict_pose_from_sensor_yuv")
+    ap.add_argument("--lens", action="store_true", help="report only: predict_pose_from_sensor beside predict_pose_from_lens, and the two standalone kernels at B = 256")
     ap.add_argument("--json", default=None)
     ap.add_argument("--md", default=None, help="write the table as markdown (profiles/predict_sensor_summary.md)")
     args = ap.parse_args()
@@ -161,9 +240,10 @@ def main():
         torch.cuda.synchronize()
         print("once: done")
         return
-    rows = yuv_rows(m, args) if args.yuv else []
-    heads = ("A: torch conversion + predict_pose_from_sensor", "B: predict_pose_from_sensor_yuv") if args.yuv else ("A: today's caller", "B: predict_pose_from_sensor")
-    for mode in () if args.yuv else ("bf16_frozen", "f32"):
+    rows = yuv_rows(m, args) if args.yuv else lens_rows(m, args, S0) if args.lens else []
+    heads = (("A: torch conversion + predict_pose_from_sensor", "B: predict_pose_from_sensor_yuv") if args.yuv else
+             ("A: predict_pose_from_sensor", "B: predict_pose_from_lens") if args.lens else ("A: today's caller", "B: predict_pose_from_sensor"))
+    for mode in () if args.yuv or args.lens else ("bf16_frozen", "f32"):
         for src in args.sources.split(","):
             H, W = (int(v) for v in src.split("x"))
             rect = centre_crop(H, W)
