@@ -2796,22 +2796,32 @@ extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, c
     return EGOTAP_OK;
 }
 
-// ---- the pose, the root and the stereo joints filtered over time (pose_track.h): one operator, no handle
-extern "C" int egotap_pose_track(const float* pose, const float* frame, const float* joints3d, int T, int S, int P, int J, const float* dts, double dt,
-                                 const egotap_track_params* params, const double* state_in, double* state_out, float* tracks, float* placed, void* stream) {
-    static const char* const who = "egotap_pose_track";
-    EGO_CHECK(pose && state_in && state_out && tracks && placed && params,
-              "%s: null argument (pose, params, state_in, state_out, tracks and placed are required; frame, joints3d and dts may be NULL)", who);
+// ---- the pose, the root and the stereo joints filtered over time (pose_track.h): one operator in the camera's frame or in a world frame, no handle
+// both entries: `world` adds rig_pose, ortho_tol and placed_cam, and calls the fourth output placed_world
+static int pose_track_entry(const char* who, bool world, const float* pose, const float* frame, const float* joints3d, const double* rig_pose, int T, int S, int P,
+                            int J, const float* dts, double dt, const egotap_track_params* params, double ortho_tol, const double* state_in, double* state_out,
+                            float* tracks, float* placed, float* placed_cam, void* stream) {
+    const char* const placed_name = world ? "placed_world" : "placed";
+    if (world)
+        EGO_CHECK(pose && state_in && state_out && tracks && placed && params && rig_pose && placed_cam,
+                  "%s: null argument (pose, rig_pose, params, state_in, state_out, tracks, placed_world and placed_cam are required; frame, joints3d and dts may be "
+                  "NULL)", who);
+    else
+        EGO_CHECK(pose && state_in && state_out && tracks && placed && params,
+                  "%s: null argument (pose, params, state_in, state_out, tracks and placed are required; frame, joints3d and dts may be NULL)", who);
     EGO_CHECK(T > 0 && S > 0 && P > 0, "%s: T, S and P must be positive (T = %d, S = %d, P = %d)", who, T, S, P);
     EGO_CHECK(P <= kTrackMaxRows, "%s: at most %d pose rows, one lane each (P = %d)", who, kTrackMaxRows, P);
     EGO_CHECK(J >= 0 && J <= kTrackMaxRows, "%s: J must be 0 .. %d joints, one lane each (J = %d)", who, kTrackMaxRows, J);
     EGO_CHECK((J > 0) == (joints3d != nullptr), "%s: joints3d goes with J > 0 and NULL with J = 0 (J = %d, joints3d %s)", who, J, joints3d ? "given" : "NULL");
     EGO_CHECK((int64_t)T * S <= INT32_MAX, "%s: T * S = %lld frames do not fit an int", who, (long long)T * S);
     EGO_CHECK((((uintptr_t)pose | (uintptr_t)frame | (uintptr_t)joints3d | (uintptr_t)dts | (uintptr_t)placed) & 3) == 0,
-              "%s: pose, frame, joints3d, dts and placed must be 4-byte aligned", who);
+              "%s: pose, frame, joints3d, dts and %s must be 4-byte aligned", who, placed_name);
+    EGO_CHECK(((uintptr_t)placed_cam & 3) == 0, "%s: placed_cam must be 4-byte aligned", who);
     EGO_CHECK(((uintptr_t)tracks & 15) == 0, "%s: tracks must be 16-byte aligned", who);
     EGO_CHECK((((uintptr_t)state_in | (uintptr_t)state_out) & 7) == 0, "%s: state_in and state_out must be 8-byte aligned", who);
+    EGO_CHECK(((uintptr_t)rig_pose & 7) == 0, "%s: rig_pose must be 8-byte aligned", who);
     EGO_CHECK(dts || (ego_finite(dt) && dt > 0.0), "%s: dt must be finite and > 0 when dts is NULL (dt = %g)", who, dt);
+    EGO_CHECK(!world || ortho_tol >= 0.0, "%s: ortho_tol must be >= 0 (%g)", who, ortho_tol);      // (a NaN fails the comparison)
     const egotap_track_params& q = *params;
     const double cls[3][3] = {{q.pose_min_cutoff, q.pose_beta, q.pose_d_cutoff}, {q.root_min_cutoff, q.root_beta, q.root_d_cutoff},
                               {q.joints_min_cutoff, q.joints_beta, q.joints_d_cutoff}};
@@ -2831,18 +2841,37 @@ extern "C" int egotap_pose_track(const float* pose, const float* frame, const fl
         const char* name;
         const void* p;
         size_t n;
-    } in[5] = {{"pose", pose, B * P * 12}, {"frame", frame, B * 32}, {"joints3d", joints3d, B * J * 32}, {"dts", dts, (size_t)T * 4}, {"state_in", state_in, (size_t)S * K * 96}},
-      out[3] = {{"state_out", state_out, (size_t)S * K * 96}, {"tracks", tracks, B * K * 32}, {"placed", placed, B * P * 12}};
-    for (int o = 0; o < 3; ++o) {
-        for (int i = 0; i < 5; ++i) {
+    } in[6] = {{"pose", pose, B * P * 12}, {"frame", frame, B * 32}, {"joints3d", joints3d, B * J * 32}, {"dts", dts, (size_t)T * 4}, {"state_in", state_in, (size_t)S * K * 96},
+               {"rig_pose", rig_pose, B * 96}},
+      out[4] = {{"state_out", state_out, (size_t)S * K * 96}, {"tracks", tracks, B * K * 32}, {placed_name, placed, B * P * 12}, {"placed_cam", placed_cam, B * P * 12}};
+    for (int o = 0; o < 4; ++o) {      // (the camera-frame entry's rig_pose and placed_cam are NULL: they overlap nothing)
+        for (int i = 0; i < 6; ++i) {
             if (o == 0 && i == 4 && state_out == state_in) continue;      // in place
             EGO_CHECK(!ego_overlap(out[o].p, out[o].n, in[i].p, in[i].n), "%s: %s overlaps %s", who, out[o].name, in[i].name);
         }
-        for (int p = o + 1; p < 3; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
+        for (int p = o + 1; p < 4; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
     }
-    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "pose_track", "pose_track_kernel", 0.0);
-    EGO_HIP(pose_track_launch(pose, frame, joints3d, T, S, P, J, dts, dt, q, state_in, state_out, tracks, placed, (hipStream_t)stream));
+    for (int i = 0; i < 5; ++i) EGO_CHECK(!ego_overlap(rig_pose, B * 96, in[i].p, in[i].n), "%s: rig_pose overlaps %s", who, in[i].name);
+    if (world) {
+        GemmTimer tm(g_timing_handle, (hipStream_t)stream, "pose_track_world", "pose_track_world_kernel", 0.0);
+        EGO_HIP(pose_track_world_launch(pose, frame, joints3d, rig_pose, T, S, P, J, dts, dt, q, ortho_tol, state_in, state_out, tracks, placed, placed_cam,
+                                        (hipStream_t)stream));
+    } else {
+        GemmTimer tm(g_timing_handle, (hipStream_t)stream, "pose_track", "pose_track_kernel", 0.0);
+        EGO_HIP(pose_track_launch(pose, frame, joints3d, T, S, P, J, dts, dt, q, state_in, state_out, tracks, placed, (hipStream_t)stream));
+    }
     return EGOTAP_OK;
+}
+extern "C" int egotap_pose_track(const float* pose, const float* frame, const float* joints3d, int T, int S, int P, int J, const float* dts, double dt,
+                                 const egotap_track_params* params, const double* state_in, double* state_out, float* tracks, float* placed, void* stream) {
+    return pose_track_entry("egotap_pose_track", false, pose, frame, joints3d, nullptr, T, S, P, J, dts, dt, params, 0.0, state_in, state_out, tracks, placed, nullptr,
+                            stream);
+}
+extern "C" int egotap_pose_track_world(const float* pose, const float* frame, const float* joints3d, const double* rig_pose, int T, int S, int P, int J, const float* dts,
+                                       double dt, const egotap_track_params* params, double ortho_tol, const double* state_in, double* state_out, float* tracks,
+                                       float* placed_world, float* placed_cam, void* stream) {
+    return pose_track_entry("egotap_pose_track_world", true, pose, frame, joints3d, rig_pose, T, S, P, J, dts, dt, params, ortho_tol, state_in, state_out, tracks,
+                            placed_world, placed_cam, stream);
 }
 
 extern "C" int egotap_debug_predict_pose_rgb_form(egotap_handle h, int* form) {

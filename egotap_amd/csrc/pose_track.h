@@ -7,6 +7,11 @@
 //       (a uniform address), so all lanes hold the same bits and the lane that owns track P writes them.  Step t + 1's measurements are requested
 //       before step t's arithmetic.  No LDS, no barrier, no atomics, no workspace; plain vector stores, the 32-byte track records as two 16-byte ones.
 //       A wave whose stream lies past S loads and stores nothing.
+//   pose_track_world_kernel  the same walk in a WORLD frame (egotap.h egotap_pose_track_world; spec.py pose_track_world_ref): each step carries the
+//       left camera's pose in the world, 12 doubles (R | t) that every lane reads from the same address (why not into SGPRs: at the kernel).  A rig
+//       pose that is finite, orthonormal within ortho_tol and right-handed moves the step's measurements into the world before track_step (points
+//       R m + t, the pose rows R m); any other one accepts no track, so the step is a missing sample.  placed_world as placed; placed_cam the same
+//       float64 value brought back through this step's rig pose.  A sibling of pose_track_kernel, whose text and code stay as they are.
 // Bound by LATENCY, not by any rate: per step a serial chain of float64 divisions (dx / te, two alphas) and a square root per track, on a few KB of
 // data; a call of T steps costs T times that chain whatever S is, up to 4 streams per workgroup and one workgroup per CU.
 // Compiler's resource summary for gfx950 (-Rpass-analysis=kernel-resource-usage): see the numbers at the kernel.
@@ -127,6 +132,43 @@ static __device__ __forceinline__ void track_record(const TrackState& s, int sta
     *(f32x4v*)(out + 4) = hi;
 }
 
+// ---- the world frame: one step's rig pose g = the row-major 3 x 4 (R | t) of the left camera in the world, x_w = R x_c + t; wave-uniform
+// finite, every |E_ij| <= tol with E = R R^T - 1 (symmetric in bits: six entries), det R > 0 by cofactors along row 0; every comparison false on a NaN
+static __device__ __forceinline__ bool rig_seen(const double (&g)[12], double tol) {
+#pragma clang fp contract(off)
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) ok = ok && track_finite(g[k]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = i; j < 3; ++j) {
+            const double e = ((g[4 * i] * g[4 * j] + g[4 * i + 1] * g[4 * j + 1]) + g[4 * i + 2] * g[4 * j + 2]) - (i == j ? 1.0 : 0.0);
+            ok = ok && fabs(e) <= tol;
+        }
+    const double c0 = g[5] * g[10] - g[6] * g[9], c1 = g[4] * g[10] - g[6] * g[8], c2 = g[4] * g[9] - g[5] * g[8];
+    const double det = (g[0] * c0 - g[1] * c1) + g[2] * c2;
+    return ok && det > 0.0;
+}
+// a camera-frame measurement in the world: a point gets R m + t, a pelvis-relative offset (a pose row) R m
+static __device__ __forceinline__ void rig_to_world(const double (&g)[12], const double (&m)[3], bool point, double (&w)[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double rot = (g[4 * r] * m[0] + g[4 * r + 1] * m[1]) + g[4 * r + 2] * m[2];
+        w[r] = point ? rot + g[4 * r + 3] : rot;
+    }
+}
+// a world value back in this step's camera: R^T (p - t) for a point, R^T p for an offset
+static __device__ __forceinline__ void rig_to_camera(const double (&g)[12], const double (&p)[3], bool point, double (&o)[3]) {
+#pragma clang fp contract(off)
+    double d[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) d[r] = point ? p[r] - g[4 * r + 3] : p[r];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (g[c] * d[0] + g[4 + c] * d[1]) + g[8 + c] * d[2];
+}
+
 // gfx950, -O3: 220 VGPRs (four track states of 12 doubles and the next step's measurements), 0 AGPRs, 96 SGPRs, scratch 0 bytes, no spills, LDS 0
 // bytes, 2 waves per SIMD (a workgroup puts one on each).
 // state_in and state_out may be the same array (each lane reads its tracks before the loop and writes them after it): not __restrict__.
@@ -240,5 +282,143 @@ static inline hipError_t pose_track_launch(const float* pose, const float* frame
     const unsigned blocks = (unsigned)(((long)S + kTrackStreamsPerBlock - 1) / kTrackStreamsPerBlock);
     hipLaunchKernelGGL(pose_track_kernel, dim3(blocks), dim3(64 * kTrackStreamsPerBlock), 0, s, pose, frame, joints3d, T, S, P, J, dts, dt, prm, state_in, state_out,
                        tracks, placed);
+    return hipGetLastError();
+}
+
+// The camera-frame kernel's walk with a rig pose per step; the step itself, the loads, the stores and the records are the shared functions above.
+// The 12 rig values are wave-uniform but live in VGPRs: the 96 SGPRs of the walk leave no room for 24 more (the scalar-load form spills 15 of
+// them), and a copy of the NEXT step's rig pose in flight would take the kernel to 256 VGPRs + 6 AGPRs and one wave per SIMD, so this step's
+// rig pose is asked for at the top of the step and not a step ahead; the measurements still travel a step ahead.
+// gfx950, -O3: 248 VGPRs (the camera-frame walk's 220, this step's rig pose and the transform's temporaries), 0 AGPRs, 104 SGPRs, scratch 0 bytes, no
+// spills, LDS 0 bytes, 2 waves per SIMD.
+// state_in and state_out may be the same array, as above: not __restrict__.
+static __global__ __launch_bounds__(64 * kTrackStreamsPerBlock) void pose_track_world_kernel(const float* __restrict__ pose, const float* __restrict__ frame,
+                                                                                             const float* __restrict__ joints3d, const double* __restrict__ rig_pose,
+                                                                                             int T, int S, int P, int J, const float* __restrict__ dts, double dt_host,
+                                                                                             egotap_track_params prm, double ortho_tol, const double* state_in,
+                                                                                             double* state_out, float* __restrict__ tracks,
+                                                                                             float* __restrict__ placed_world, float* __restrict__ placed_cam) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long s = (long)blockIdx.x * kTrackStreamsPerBlock + wave;
+    if (s >= S) return;                                      // (no barrier anywhere: a wave may leave)
+    const int K = P + 1 + J;
+    const TrackClass cls_pose = {prm.pose_min_cutoff, prm.pose_beta, prm.pose_d_cutoff}, cls_root = {prm.root_min_cutoff, prm.root_beta, prm.root_d_cutoff},
+                     cls_joint = {prm.joints_min_cutoff, prm.joints_beta, prm.joints_d_cutoff};
+    const double max_hold = (double)prm.max_hold, min_joints = (double)prm.min_joints;
+    // slot i of this lane is track lane + 64 i; the root (track P) is run by every lane below and skipped as a slot
+    bool on[3], is_pose[3];
+    TrackState st[3], root;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const int k = lane + 64 * i;
+        on[i] = k < K && k != P;
+        is_pose[i] = k < P;
+        st[i] = TrackState{};
+        if (on[i]) track_load(st[i], state_in + (s * K + k) * kTrackState);
+    }
+    track_load(root, state_in + (s * K + P) * kTrackState);
+    const bool owns_root = lane == (P & 63);
+
+    TrackRaw nxt[3] = {};
+    float nfr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ndt = 0.f;
+    auto fetch = [&](int t) {
+        const long b = (long)t * S + s;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (!on[i]) continue;
+            const int k = lane + 64 * i;
+            if (is_pose[i]) {
+                const float* p = pose + (b * P + k) * 3;
+                nxt[i].m[0] = p[0];
+                nxt[i].m[1] = p[1];
+                nxt[i].m[2] = p[2];
+                nxt[i].gap = 0.f;
+                nxt[i].valid = 1.f;
+            } else {
+                const float* q = joints3d + (b * J + (k - P - 1)) * 8;
+                nxt[i].m[0] = q[0];
+                nxt[i].m[1] = q[1];
+                nxt[i].m[2] = q[2];
+                nxt[i].gap = q[3];
+                nxt[i].valid = q[7];
+            }
+        }
+        if (frame) {
+            const float* f = frame + b * 8;
+            nfr[0] = f[0];
+            nfr[1] = f[1];
+            nfr[2] = f[2];
+            nfr[3] = f[3];
+            nfr[4] = f[4];
+            nfr[5] = f[6];
+        }
+        if (dts) ndt = dts[t];
+    };
+    fetch(0);
+    for (int t = 0; t < T; ++t) {
+        TrackRaw cur[3];
+        float fr[6];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cur[i] = nxt[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) fr[i] = nfr[i];
+        const double dt = dts ? (double)ndt : dt_host;
+        const long b = (long)t * S + s;
+        double rig[12];                                      // asked for first: everything below waits for it
+#pragma unroll
+        for (int k = 0; k < 12; ++k) rig[k] = rig_pose[b * 12 + k];
+        if (t + 1 < T) fetch(t + 1);                         // the next step's measurements travel during this step's chain
+        const bool ok = track_finite(dt) && dt > 0.0;
+        const bool seen = rig_seen(rig, ortho_tol);          // not seen: no track accepts, the step is a missing sample
+        // the root, by every lane for itself: (t^, n, rms disagree, rms gap) of the frame record
+        const double mr[3] = {(double)fr[0], (double)fr[1], (double)fr[2]};
+        const bool ar = frame != nullptr && (double)fr[3] >= min_joints && track_finite(mr[0]) && track_finite(mr[1]) && track_finite(mr[2]) &&
+                        (double)fr[4] <= prm.max_disagree && (double)fr[5] <= prm.max_gap;
+        double cutoff, wr[3];
+        rig_to_world(rig, mr, true, wr);
+        const int root_status = track_step(root, wr, ar && seen, dt, ok, cls_root, max_hold, cutoff);
+        if (owns_root) track_record(root, root_status, cutoff, tracks + (b * K + P) * 8);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (!on[i]) continue;
+            const int k = lane + 64 * i;
+            const double m[3] = {(double)cur[i].m[0], (double)cur[i].m[1], (double)cur[i].m[2]};
+            const bool a = cur[i].valid == 1.f && track_finite(m[0]) && track_finite(m[1]) && track_finite(m[2]) &&
+                           (is_pose[i] || (double)cur[i].gap <= prm.max_joint_gap);
+            double w[3];
+            rig_to_world(rig, m, !is_pose[i], w);
+            const int status = track_step(st[i], w, a && seen, dt, ok, is_pose[i] ? cls_pose : cls_joint, max_hold, cutoff);
+            track_record(st[i], status, cutoff, tracks + (b * K + k) * 8);
+            if (i == 0 && is_pose[0]) {                      // (P <= 64: every pose row is a slot-0 track)
+                const bool with_root = root_status != 0;
+                double pw[3], pc[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) pw[c] = with_root ? st[0].x[c] + root.x[c] : st[0].x[c];
+                rig_to_camera(rig, pw, with_root, pc);       // the same float64 value, back through this step's rig pose
+                float *o = placed_world + (b * P + k) * 3, *oc = placed_cam + (b * P + k) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    o[c] = status == 0 ? 0.f : (float)pw[c];
+                    oc[c] = status == 0 || !seen ? 0.f : (float)pc[c];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if (on[i]) track_store(st[i], state_out + (s * K + lane + 64 * i) * kTrackState);
+    if (owns_root) track_store(root, state_out + (s * K + P) * kTrackState);
+}
+
+// the same checks; rig_pose, placed_world and placed_cam checked by the caller.
+static inline hipError_t pose_track_world_launch(const float* pose, const float* frame, const float* joints3d, const double* rig_pose, int T, int S, int P, int J,
+                                                 const float* dts, double dt, const egotap_track_params& prm, double ortho_tol, const double* state_in,
+                                                 double* state_out, float* tracks, float* placed_world, float* placed_cam, hipStream_t s) {
+    if (T <= 0 || S <= 0 || P <= 0 || P > kTrackMaxRows || J < 0 || J > kTrackMaxRows || (J > 0) != (joints3d != nullptr) || !rig_pose || !placed_cam)
+        return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((long)S + kTrackStreamsPerBlock - 1) / kTrackStreamsPerBlock);
+    hipLaunchKernelGGL(pose_track_world_kernel, dim3(blocks), dim3(64 * kTrackStreamsPerBlock), 0, s, pose, frame, joints3d, rig_pose, T, S, P, J, dts, dt, prm,
+                       ortho_tol, state_in, state_out, tracks, placed_world, placed_cam);
     return hipGetLastError();
 }

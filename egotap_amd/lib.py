@@ -118,6 +118,9 @@ _PROTOS = {
     # ---- the pose, the root and the stereo joints filtered over time: one operator, no handle
     "egotap_pose_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.POINTER(EgotapTrackParams),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (pose, frame, joints3d, rig_pose, T, S, P, J, dts, dt, params, ortho_tol, state_in, state_out, tracks, placed_world, placed_cam, stream)
+    "egotap_pose_track_world": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
+                                          C.POINTER(EgotapTrackParams), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -769,6 +772,47 @@ def pose_track_into(prm, pose, frame, joints3d, T, S, dts, dt, state_in, state_o
                                    _ptr(placed), _stream(dev)))
 
 
+def _pose_track_args(who, pose, state, dt, dts, params, frame, joints3d, streams):
+    """the shape, dtype and value checks ``pose_track`` and ``pose_track_world`` make alike, under the face's name -> (prm, T, S, P, J); each face
+    then checks what is its own and, last, the devices"""
+    import torch
+    prm = track_params_struct(params)
+    S = int(streams)
+    if not torch.is_tensor(pose) or pose.dim() != 3 or pose.shape[2] != 3 or S < 1 or pose.shape[0] < S or pose.shape[0] % S:
+        raise ValueError(f"{who}: pose is a tensor [T * streams, P, 3] with T >= 1, got {tuple(getattr(pose, 'shape', ()))} for {streams} streams")
+    B, P, _ = (int(v) for v in pose.shape)
+    T = B // S
+    if not 1 <= P <= 64:
+        raise ValueError(f"{who}: 1 .. 64 pose rows, got {P}")
+    J = 0
+    if joints3d is not None:
+        if not torch.is_tensor(joints3d) or joints3d.dim() != 3 or joints3d.shape[0] != B or joints3d.shape[2] != 8 or not 1 <= joints3d.shape[1] <= 64:
+            raise ValueError(f"{who}: joints3d is a tensor [T * streams, J, 8] with 1 .. 64 joints, got {tuple(getattr(joints3d, 'shape', ()))} for {B} frames")
+        J = int(joints3d.shape[1])
+    if frame is not None and (not torch.is_tensor(frame) or tuple(frame.shape) != (B, 8)):
+        raise ValueError(f"{who}: frame is a tensor [T * streams, 8], got {tuple(getattr(frame, 'shape', ()))} for {B} frames")
+    K = P + 1 + J
+    if not torch.is_tensor(state) or tuple(state.shape) != (S, K, 12) or state.dtype != torch.float64 or not state.is_contiguous():
+        raise ValueError(f"{who}: state is a contiguous float64 tensor [streams, P + 1 + J, 12] = {(S, K, 12)}, got "
+                         f"{getattr(state, 'dtype', type(state).__name__)} {tuple(getattr(state, 'shape', ()))}")
+    if (dt is None) == (dts is None):
+        raise ValueError(f"{who}: give exactly one of dt (seconds per step) and dts (a float32 tensor [T] on the device)")
+    if dts is not None and (not torch.is_tensor(dts) or tuple(dts.shape) != (T,) or dts.dtype != torch.float32):
+        raise ValueError(f"{who}: dts is a float32 tensor [T] = [{T}], got {getattr(dts, 'dtype', type(dts).__name__)} {tuple(getattr(dts, 'shape', ()))}")
+    if dt is not None and not (float(dt) > 0 and float(dt) != float("inf")):
+        raise ValueError(f"{who}: dt must be finite and > 0, got {dt}")
+    return prm, T, S, P, J
+
+
+def _on_one_gpu(pose, *others):
+    return pose.is_cuda and all(t is None or t.device == pose.device for t in others)
+
+
+def _f32c(t):
+    """a float tensor as the ABI reads it (None stays None)"""
+    return t.detach().float().contiguous() if t is not None else None
+
+
 def pose_track(pose, state, dt=None, dts=None, params=None, frame=None, joints3d=None, streams=1):
     """The pose, the root and the stereo joints filtered over time (egotap_pose_track, ``spec.pose_track_ref``): a One-Euro filter per 3-vector whose
     state survives between calls.  pose float32 [T * streams, P, 3] on the GPU, T consecutive frames of ``streams`` camera rigs, time-major;
@@ -778,41 +822,51 @@ def pose_track(pose, state, dt=None, dts=None, params=None, frame=None, joints3d
     ``spec.TrackParams`` (None: its defaults) -> (tracks float32 [T * streams, P + 1 + J, 8] = (x^, v^, cutoff, status), placed float32
     [T * streams, P, 3] = the filtered pose plus the filtered root).  One launch on the current stream, no synchronisation."""
     import torch
-    prm = track_params_struct(params)
-    S = int(streams)
-    if not torch.is_tensor(pose) or pose.dim() != 3 or pose.shape[2] != 3 or S < 1 or pose.shape[0] < S or pose.shape[0] % S:
-        raise ValueError(f"pose_track: pose is a tensor [T * streams, P, 3] with T >= 1, got {tuple(getattr(pose, 'shape', ()))} for {streams} streams")
-    B, P, _ = (int(v) for v in pose.shape)
-    T = B // S
-    if not 1 <= P <= 64:
-        raise ValueError(f"pose_track: 1 .. 64 pose rows, got {P}")
-    J = 0
-    if joints3d is not None:
-        if not torch.is_tensor(joints3d) or joints3d.dim() != 3 or joints3d.shape[0] != B or joints3d.shape[2] != 8 or not 1 <= joints3d.shape[1] <= 64:
-            raise ValueError(f"pose_track: joints3d is a tensor [T * streams, J, 8] with 1 .. 64 joints, got {tuple(getattr(joints3d, 'shape', ()))} for {B} frames")
-        J = int(joints3d.shape[1])
-    if frame is not None and (not torch.is_tensor(frame) or tuple(frame.shape) != (B, 8)):
-        raise ValueError(f"pose_track: frame is a tensor [T * streams, 8], got {tuple(getattr(frame, 'shape', ()))} for {B} frames")
-    K = P + 1 + J
-    if not torch.is_tensor(state) or tuple(state.shape) != (S, K, 12) or state.dtype != torch.float64 or not state.is_contiguous():
-        raise ValueError(f"pose_track: state is a contiguous float64 tensor [streams, P + 1 + J, 12] = {(S, K, 12)}, got "
-                         f"{getattr(state, 'dtype', type(state).__name__)} {tuple(getattr(state, 'shape', ()))}")
-    if (dt is None) == (dts is None):
-        raise ValueError("pose_track: give exactly one of dt (seconds per step) and dts (a float32 tensor [T] on the device)")
-    if dts is not None and (not torch.is_tensor(dts) or tuple(dts.shape) != (T,) or dts.dtype != torch.float32):
-        raise ValueError(f"pose_track: dts is a float32 tensor [T] = [{T}], got {getattr(dts, 'dtype', type(dts).__name__)} {tuple(getattr(dts, 'shape', ()))}")
-    if dt is not None and not (float(dt) > 0 and float(dt) != float("inf")):
-        raise ValueError(f"pose_track: dt must be finite and > 0, got {dt}")
-    if not pose.is_cuda or any(t is not None and t.device != pose.device for t in (frame, joints3d, dts, state)):
+    prm, T, S, P, J = _pose_track_args("pose_track", pose, state, dt, dts, params, frame, joints3d, streams)
+    if not _on_one_gpu(pose, frame, joints3d, dts, state):
         raise EgotapError("pose_track runs on the GPU only (no CPU fallback); pose, frame, joints3d, dts and state on one cuda device")
-    ps = pose.detach().float().contiguous()
-    fr = frame.detach().float().contiguous() if frame is not None else None
-    j3 = joints3d.detach().float().contiguous() if joints3d is not None else None
+    ps, fr, j3 = _f32c(pose), _f32c(frame), _f32c(joints3d)
+    B, K = T * S, P + 1 + J
     tracks = torch.empty((B, K, 8), dtype=torch.float32, device=ps.device)
     placed = torch.empty((B, P, 3), dtype=torch.float32, device=ps.device)
     with torch.cuda.device(ps.device):
         pose_track_into(prm, ps, fr, j3, T, S, dts.contiguous() if dts is not None else None, dt, state, state, tracks, placed, ps.device)
     return tracks, placed
+
+
+def pose_track_world_into(prm, pose, frame, joints3d, rig_pose, T, S, dts, dt, ortho_tol, state_in, state_out, tracks, placed_world, placed_cam, dev):
+    """the launch itself on ``dev``'s current stream, as ``pose_track_into``; rig_pose float64 [T * S, 12]"""
+    check(load().egotap_pose_track_world(_ptr(pose), _ptr(frame), _ptr(joints3d), _ptr(rig_pose), int(T), int(S), pose.shape[1],
+                                         joints3d.shape[1] if joints3d is not None else 0, _ptr(dts), C.c_double(0.0 if dt is None else float(dt)), C.byref(prm),
+                                         C.c_double(float(ortho_tol)), _ptr(state_in), _ptr(state_out), _ptr(tracks), _ptr(placed_world), _ptr(placed_cam),
+                                         _stream(dev)))
+
+
+def pose_track_world(pose, state, rig_pose, dt=None, dts=None, params=None, frame=None, joints3d=None, streams=1, ortho_tol=1e-6):
+    """``pose_track`` in a world frame (egotap_pose_track_world, ``spec.pose_track_world_ref``): ``rig_pose`` float64 [T * streams, 12] on the pose's
+    device holds, per frame, the row-major 3 x 4 (R | t) of the LEFT CAMERA IN THE WORLD, x_w = R x_c + t, t in the pose's units (``spec.rig_pose`` /
+    ``spec.rig_compose`` build it).  A frame whose rig pose is not finite, not orthonormal within ``ortho_tol`` or left-handed accepts no track: the
+    tracks hold as over any missing sample.  The other arguments are ``pose_track``'s; ``state`` is UPDATED IN PLACE and belongs to the frame it was
+    made in (zeros suit both) -> (tracks float32 [T * streams, P + 1 + J, 8] in the world, placed_world float32 [T * streams, P, 3], placed_cam float32
+    [T * streams, P, 3] = placed_world back in each frame's own camera, zeros for a frame whose rig pose is not seen).  One launch, no synchronisation."""
+    import torch
+    prm, T, S, P, J = _pose_track_args("pose_track_world", pose, state, dt, dts, params, frame, joints3d, streams)
+    B, K = T * S, P + 1 + J
+    if not torch.is_tensor(rig_pose) or rig_pose.dtype != torch.float64 or tuple(rig_pose.shape) != (B, 12):
+        raise ValueError(f"pose_track_world: rig_pose is a float64 tensor [T * streams, 12] = {(B, 12)}, got "
+                         f"{getattr(rig_pose, 'dtype', type(rig_pose).__name__)} {tuple(getattr(rig_pose, 'shape', ()))}")
+    if not float(ortho_tol) >= 0:
+        raise ValueError(f"pose_track_world: ortho_tol must be >= 0, got {ortho_tol}")
+    if not _on_one_gpu(pose, frame, joints3d, dts, state, rig_pose):
+        raise EgotapError("pose_track_world runs on the GPU only (no CPU fallback); pose, frame, joints3d, dts, state and rig_pose on one cuda device")
+    ps, fr, j3 = _f32c(pose), _f32c(frame), _f32c(joints3d)
+    tracks = torch.empty((B, K, 8), dtype=torch.float32, device=ps.device)
+    placed_world = torch.empty((B, P, 3), dtype=torch.float32, device=ps.device)
+    placed_cam = torch.empty((B, P, 3), dtype=torch.float32, device=ps.device)
+    with torch.cuda.device(ps.device):
+        pose_track_world_into(prm, ps, fr, j3, rig_pose.detach().contiguous(), T, S, dts.contiguous() if dts is not None else None, dt, ortho_tol, state, state,
+                              tracks, placed_world, placed_cam, ps.device)
+    return tracks, placed_world, placed_cam
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

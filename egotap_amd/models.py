@@ -41,10 +41,18 @@ class PoseTracker:
     """The serving outputs followed over time on the device (``lib.pose_track``, egotap_pose_track, ``spec.pose_track_ref``): per stream (camera rig)
     P pose rows, the root (the triangulation's t_hat) and J triangulated joints, each a One-Euro filtered 3-vector that is held over rejected frames
     and forgotten after ``params.max_hold`` of them.  ``state``: float64 [streams, P + 1 + J, 12] on the device, zeros = never seen.  Made by
-    ``model.new_pose_tracker``; holds no reference to the model and takes no part in its graphs."""
+    ``model.new_pose_tracker``; holds no reference to the model and takes no part in its graphs.  ``world=True``: the tracks live in a world frame
+    (``lib.pose_track_world``, egotap_pose_track_world): every update then takes the headset's own pose, so a head turn no longer moves a motionless body
+    through the filter; ``ortho_tol`` (None: 1e-6) is how far such a pose's matrix may be from a rotation and still count.  The state belongs to the
+    frame it was made in: a tracker is one or the other for life."""
 
-    def __init__(self, P, J, streams=1, params=None):
-        self.P, self.J, self.streams = int(P), int(J), int(streams)
+    def __init__(self, P, J, streams=1, params=None, world=False, ortho_tol=None):
+        self.P, self.J, self.streams, self.world = int(P), int(J), int(streams), bool(world)
+        if ortho_tol is not None and not self.world:
+            raise ValueError("PoseTracker: ortho_tol goes with a world tracker (world=True); this one reads no rig pose")
+        self.ortho_tol = 1e-6 if ortho_tol is None else float(ortho_tol)
+        if not self.ortho_tol >= 0:
+            raise ValueError(f"PoseTracker: ortho_tol must be >= 0, got {ortho_tol}")
         if self.streams < 1:
             raise ValueError(f"PoseTracker: streams must be at least 1, got {streams}")
         self.params = _spec.TrackParams() if params is None else params
@@ -63,11 +71,18 @@ class PoseTracker:
         return self._state
 
     @torch.no_grad()
-    def update(self, pose, joints3d=None, frame=None, dt=None, dts=None):
+    def update(self, pose, joints3d=None, frame=None, dt=None, dts=None, rig_pose=None):
         """T consecutive frames of every stream, time-major: ``pose`` [T * streams, P, 3]; ``joints3d`` [T * streams, J, 8] and ``frame``
         [T * streams, 8] the last two results of a ``return_triangulation=True`` serving call (None: no joint / no root is seen in these frames, which
         holds their tracks); ``dt`` seconds per step, or ``dts`` float32 [T] on the device -> (placed [T * streams, P, 3], tracks
-        [T * streams, P + 1 + J, 8]).  ONE launch on the current stream, no synchronisation: it queues behind the serving call that made its inputs."""
+        [T * streams, P + 1 + J, 8]).  ONE launch on the current stream, no synchronisation: it queues behind the serving call that made its inputs.
+        A world tracker also takes ``rig_pose`` float64 [T * streams, 12] on the device, per frame the row-major 3 x 4 (R | t) of the left camera in
+        the world (``spec.rig_pose``) -> (placed_world, tracks, placed_cam): the skeleton and the tracks in the world, and the skeleton back in
+        each frame's own camera for an overlay; a frame whose rig pose is not a rotation within the tracker's ``ortho_tol`` is a missing sample."""
+        if self.world and rig_pose is None:
+            raise ValueError("PoseTracker.update: a world tracker needs rig_pose, float64 [T * streams, 12]: the left camera in the world per frame")
+        if not self.world and rig_pose is not None:
+            raise ValueError("PoseTracker.update: rig_pose goes with a world tracker (model.new_pose_tracker(world=True)); this one filters in the camera's frame")
         if not torch.is_tensor(pose) or pose.dim() != 3 or tuple(pose.shape[1:]) != (self.P, 3):
             raise ValueError(f"PoseTracker.update: pose is a tensor [T * streams, {self.P}, 3], got {tuple(getattr(pose, 'shape', ()))}")
         if joints3d is not None and (not torch.is_tensor(joints3d) or joints3d.dim() != 3 or joints3d.shape[1] != self.J):
@@ -78,6 +93,10 @@ class PoseTracker:
             if self._unseen is None or self._unseen.shape[0] != pose.shape[0] or self._unseen.device != pose.device:
                 self._unseen = torch.zeros((pose.shape[0], self.J, 8), dtype=torch.float32, device=pose.device)
             joints3d = self._unseen
+        if self.world:
+            tracks, placed_world, placed_cam = _lib.pose_track_world(pose, self._state_on(pose.device), rig_pose, dt=dt, dts=dts, params=self.params, frame=frame,
+                                                                     joints3d=joints3d, streams=self.streams, ortho_tol=self.ortho_tol)
+            return placed_world, tracks, placed_cam
         tracks, placed = _lib.pose_track(pose, self._state_on(pose.device), dt=dt, dts=dts, params=self.params, frame=frame, joints3d=joints3d,
                                          streams=self.streams)
         return placed, tracks
@@ -836,13 +855,16 @@ class EgoTAPAutoEncoderModel(nn.Module):
                       triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the lens remap, the converter and the module forwards")
         return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
-    def new_pose_tracker(self, streams=1, params=None):
+    def new_pose_tracker(self, streams=1, params=None, world=False, ortho_tol=None):
         """A ``PoseTracker`` for this model's outputs: P = the lifted pose's rows, J = the heatmap joints the triangulation returns; ``streams`` camera
         rigs side by side, ``params`` a ``spec.TrackParams`` (None: its defaults, which nobody has tuned on real data).  Feed it what a serving entry
         returns: ``pose, joints3d, frame = model.predict_pose_from_camera(l8, r8, return_triangulation=True)``;
-        ``placed, tracks = tracker.update(pose, joints3d, frame, dt=1 / 30)``.  The serving entries, their graphs and their outputs do not change."""
+        ``placed, tracks = tracker.update(pose, joints3d, frame, dt=1 / 30)``.  The serving entries, their graphs and their outputs do not change.
+        ``world=True``: the tracker follows the skeleton in a world frame from the headset's own pose,
+        ``placed_world, tracks, placed_cam = tracker.update(pose, joints3d, frame, dt=1 / 30, rig_pose=spec.rig_pose(t, quat=q) on the device)``;
+        ``ortho_tol`` (None: 1e-6; a world tracker's alone) bounds how far a rig pose's matrix may be from a rotation and still count."""
         p = self.net_AutoEncoder.preset
-        return PoseTracker(p.out_joints, p.n_joints_hm, streams=streams, params=params)
+        return PoseTracker(p.out_joints, p.n_joints_hm, streams=streams, params=params, world=world, ortho_tol=ortho_tol)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

@@ -1056,31 +1056,15 @@ class TrackParams:
         return cls(pose=c, root=c, joints=c, **rest)
 
 
-def pose_track_ref(pose, state, dt_or_dts, params=None, frame=None, joints3d=None, streams=1, dtype="float32"):
-    """The records and the state egotap_pose_track writes, restated in float64 numpy, operation for operation: pose [B, P, 3] with B = T * streams
-    frames, time-major (frame b = t * streams + s); state [streams, K, 12] float64 with K = P + 1 + J (not modified); ``dt_or_dts`` a positive number for
-    every step, or T values (rounded to float32 first: what the device reads); frame [B, 8] / joints3d [B, J, 8] the triangulation's records or None
-    -> (tracks [B, K, 8], placed [B, P, 3], new_state [streams, K, 12]).  Per track and step, with measurement m, accept flag a, ok = dt finite and
-    > 0, alpha(fc, te) = r / (r + 1), r = (6.283185307179586 fc) te:
-
-        not live, a      x^ = m_prev = m; v^ = 0; gap_t = age = 0; live = 1                                     status 1, cutoff = min_cutoff
-        not live, not a                                                                                         status 0, record all zeros
-        live, a and ok   te = gap_t + dt; ad = alpha(d_cutoff, te); dx = (m - m_prev) / te; v^ = v^ + ad (dx - v^);
-                         speed = sqrt(v^x v^x + v^y v^y + v^z v^z); fc = min_cutoff + beta speed; ax = alpha(fc, te);
-                         x^ = x^ + ax (m - x^); m_prev = m; gap_t = age = 0                                     status 1, cutoff = fc
-        live, otherwise  age += 1; if ok: gap_t += dt; age > max_hold: the state zeroed                         status 0, record all zeros
-                                                       else x^, v^ unchanged                                    status 2, cutoff = 0
-
-    a: a pose row is accepted when finite; the root (frame[:, 0:3]) when the frame is given, n >= min_joints, t_hat finite, rms disagree <=
-    max_disagree and rms gap <= max_gap; a joint when valid == 1, X finite and gap <= max_joint_gap (every comparison false on a NaN).
-    tracks = (x^, v^, cutoff, status); placed = x^_pose + x^_root (added in float64) while the root's status is 1 or 2, x^_pose alone otherwise, zeros
-    for a pose row of status 0.  Each output is rounded once from float64 (``dtype="float64"``: not at all)."""
+def _track_inputs(who, pose, state, dt_or_dts, params, frame, joints3d, streams):
+    """the arguments of pose_track_ref / pose_track_world_ref read and checked -> (prm, S, T, P, J, state copy, dts [T], meas [T, S, K, 3], acc [T, S, K]):
+    the camera-frame measurement of every track and whether it is accepted (finite, valid, the gates)"""
     import numpy as np
     prm = TrackParams() if params is None else params
     ps = np.asarray(pose, dtype=np.float64)
     S = int(streams)
     if ps.ndim != 3 or ps.shape[2] != 3 or S < 1 or ps.shape[0] < S or ps.shape[0] % S:
-        raise ValueError(f"pose_track_ref: pose is [T * streams, P, 3] with T >= 1, got {ps.shape} for {S} streams")
+        raise ValueError(f"{who}: pose is [T * streams, P, 3] with T >= 1, got {ps.shape} for {S} streams")
     B, P, _ = ps.shape
     T = B // S
     J = 0
@@ -1088,38 +1072,27 @@ def pose_track_ref(pose, state, dt_or_dts, params=None, frame=None, joints3d=Non
     if joints3d is not None:
         j3 = np.asarray(joints3d, dtype=np.float64)
         if j3.ndim != 3 or j3.shape[0] != B or j3.shape[2] != 8 or j3.shape[1] < 1:
-            raise ValueError(f"pose_track_ref: joints3d is [T * streams, J, 8] with J >= 1, got {j3.shape} for {B} frames")
+            raise ValueError(f"{who}: joints3d is [T * streams, J, 8] with J >= 1, got {j3.shape} for {B} frames")
         J = j3.shape[1]
     if not (1 <= P <= POSE_TRACK_MAX_ROWS and J <= POSE_TRACK_MAX_ROWS):
-        raise ValueError(f"pose_track_ref: at most {POSE_TRACK_MAX_ROWS} pose rows and joints, got P = {P}, J = {J}")
+        raise ValueError(f"{who}: at most {POSE_TRACK_MAX_ROWS} pose rows and joints, got P = {P}, J = {J}")
     fr = None
     if frame is not None:
         fr = np.asarray(frame, dtype=np.float64)
         if fr.shape != (B, 8):
-            raise ValueError(f"pose_track_ref: frame is [T * streams, 8], got {fr.shape} for {B} frames")
+            raise ValueError(f"{who}: frame is [T * streams, 8], got {fr.shape} for {B} frames")
     K = P + 1 + J
     st = np.array(state, dtype=np.float64)
     if st.shape != (S, K, POSE_TRACK_STATE):
-        raise ValueError(f"pose_track_ref: state is [streams, P + 1 + J, {POSE_TRACK_STATE}] = {(S, K, POSE_TRACK_STATE)}, got {st.shape}")
+        raise ValueError(f"{who}: state is [streams, P + 1 + J, {POSE_TRACK_STATE}] = {(S, K, POSE_TRACK_STATE)}, got {st.shape}")
     if np.ndim(dt_or_dts) == 0:
         if not (math.isfinite(float(dt_or_dts)) and float(dt_or_dts) > 0):
-            raise ValueError(f"pose_track_ref: dt must be finite and > 0, got {dt_or_dts}")
+            raise ValueError(f"{who}: dt must be finite and > 0, got {dt_or_dts}")
         dts = np.full(T, float(dt_or_dts))
     else:
         dts = np.asarray(dt_or_dts, dtype=np.float32).astype(np.float64)
         if dts.shape != (T,):
-            raise ValueError(f"pose_track_ref: dts holds one value per time step, [{T}], got {dts.shape}")
-    cls = np.empty((K, 3))                                   # (min_cutoff, beta, d_cutoff) per track
-    cls[:P], cls[P], cls[P + 1:] = prm.pose, prm.root, prm.joints
-    c_min, c_beta, c_d = (cls[None, :, k] for k in range(3))
-
-    def alpha(fc, te):
-        r = (TWO_PI * fc) * te
-        return r / (r + 1.0)
-    x, v, mp = st[..., 0:3].copy(), st[..., 3:6].copy(), st[..., 6:9].copy()
-    gap_t, age, live = st[..., 9].copy(), st[..., 10].copy(), st[..., 11] != 0
-    tracks = np.zeros((T, S, K, 8))
-    placed = np.zeros((T, S, P, 3))
+            raise ValueError(f"{who}: dts holds one value per time step, [{T}], got {dts.shape}")
     meas = np.zeros((T, S, K, 3))
     acc = np.zeros((T, S, K), dtype=bool)
     with np.errstate(all="ignore"):
@@ -1133,6 +1106,27 @@ def pose_track_ref(pose, state, dt_or_dts, params=None, frame=None, joints3d=Non
             q = j3.reshape(T, S, J, 8)
             meas[:, :, P + 1:] = q[..., 0:3]
             acc[:, :, P + 1:] = (q[..., 7] == 1) & np.isfinite(q[..., 0:3]).all(axis=-1) & (q[..., 3] <= prm.max_joint_gap)
+    return prm, S, T, P, J, st, dts, meas, acc
+
+
+def _track_run(prm, P, st, dts, meas, acc):
+    """the T steps of every track: state [S, K, 12], dts [T], meas [T, S, K, 3] read only where acc [T, S, K] is set -> float64 (tracks [T, S, K, 8],
+    placed [T, S, P, 3], with_root [T, S] = the root took part in placed, new_state)"""
+    import numpy as np
+    T, S, K = acc.shape
+    cls = np.empty((K, 3))                                   # (min_cutoff, beta, d_cutoff) per track
+    cls[:P], cls[P], cls[P + 1:] = prm.pose, prm.root, prm.joints
+    c_min, c_beta, c_d = (cls[None, :, k] for k in range(3))
+
+    def alpha(fc, te):
+        r = (TWO_PI * fc) * te
+        return r / (r + 1.0)
+    x, v, mp = st[..., 0:3].copy(), st[..., 3:6].copy(), st[..., 6:9].copy()
+    gap_t, age, live = st[..., 9].copy(), st[..., 10].copy(), st[..., 11] != 0
+    tracks = np.zeros((T, S, K, 8))
+    placed = np.zeros((T, S, P, 3))
+    with_root = np.zeros((T, S), dtype=bool)
+    with np.errstate(all="ignore"):
         for t in range(T):
             dt = dts[t]
             ok = bool(np.isfinite(dt) and dt > 0)
@@ -1168,5 +1162,131 @@ def pose_track_ref(pose, state, dt_or_dts, params=None, frame=None, joints3d=Non
             root_on = status[:, P] != 0
             pl = np.where(root_on[:, None, None], x[:, :P] + x[:, P:P + 1], x[:, :P])
             placed[t] = np.where((status[:, :P] != 0)[..., None], pl, 0.0)
+            with_root[t] = root_on
     new_state = np.concatenate([x, v, mp, gap_t[..., None], age[..., None], live[..., None].astype(np.float64)], axis=-1)
-    return tracks.reshape(B, K, 8).astype(dtype), placed.reshape(B, P, 3).astype(dtype), new_state
+    return tracks, placed, with_root, new_state
+
+
+def pose_track_ref(pose, state, dt_or_dts, params=None, frame=None, joints3d=None, streams=1, dtype="float32"):
+    """The records and the state egotap_pose_track writes, restated in float64 numpy, operation for operation: pose [B, P, 3] with B = T * streams
+    frames, time-major (frame b = t * streams + s); state [streams, K, 12] float64 with K = P + 1 + J (not modified); ``dt_or_dts`` a positive number for
+    every step, or T values (rounded to float32 first: what the device reads); frame [B, 8] / joints3d [B, J, 8] the triangulation's records or None
+    -> (tracks [B, K, 8], placed [B, P, 3], new_state [streams, K, 12]).  Per track and step, with measurement m, accept flag a, ok = dt finite and
+    > 0, alpha(fc, te) = r / (r + 1), r = (6.283185307179586 fc) te:
+
+        not live, a      x^ = m_prev = m; v^ = 0; gap_t = age = 0; live = 1                                     status 1, cutoff = min_cutoff
+        not live, not a                                                                                         status 0, record all zeros
+        live, a and ok   te = gap_t + dt; ad = alpha(d_cutoff, te); dx = (m - m_prev) / te; v^ = v^ + ad (dx - v^);
+                         speed = sqrt(v^x v^x + v^y v^y + v^z v^z); fc = min_cutoff + beta speed; ax = alpha(fc, te);
+                         x^ = x^ + ax (m - x^); m_prev = m; gap_t = age = 0                                     status 1, cutoff = fc
+        live, otherwise  age += 1; if ok: gap_t += dt; age > max_hold: the state zeroed                         status 0, record all zeros
+                                                       else x^, v^ unchanged                                    status 2, cutoff = 0
+
+    a: a pose row is accepted when finite; the root (frame[:, 0:3]) when the frame is given, n >= min_joints, t_hat finite, rms disagree <=
+    max_disagree and rms gap <= max_gap; a joint when valid == 1, X finite and gap <= max_joint_gap (every comparison false on a NaN).
+    tracks = (x^, v^, cutoff, status); placed = x^_pose + x^_root (added in float64) while the root's status is 1 or 2, x^_pose alone otherwise, zeros
+    for a pose row of status 0.  Each output is rounded once from float64 (``dtype="float64"``: not at all)."""
+    prm, S, T, P, J, st, dts, meas, acc = _track_inputs("pose_track_ref", pose, state, dt_or_dts, params, frame, joints3d, streams)
+    tracks, placed, _, new_state = _track_run(prm, P, st, dts, meas, acc)
+    return tracks.reshape(T * S, -1, 8).astype(dtype), placed.reshape(T * S, P, 3).astype(dtype), new_state
+
+
+# ---- the same filter in a world frame, from the rig's own pose (egotap.h: egotap_pose_track_world) ---------------------------------------
+RIG_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)      # row-major 3 x 4 (R | t)
+
+
+def rig_pose(t, R=None, quat=None):
+    """The 12 values egotap_pose_track_world reads per frame: the row-major 3 x 4 (R | t) of the left camera in the world, x_w = R x_c + t, float64
+    [..., 12].  ``t`` [..., 3] in the pose's units; the rotation as ``R`` [..., 3, 3] or as a quaternion ``quat`` [..., 4] = (w, x, y, z), which is
+    normalised in float64 (a zero or non-finite norm is refused); neither: no rotation.  Leading dimensions broadcast."""
+    import numpy as np
+    t = np.asarray(t, dtype=np.float64)
+    if t.ndim < 1 or t.shape[-1] != 3:
+        raise ValueError(f"rig_pose: t is [..., 3], got {t.shape}")
+    if R is not None and quat is not None:
+        raise ValueError("rig_pose: give the rotation as R or as quat, not both")
+    if quat is not None:
+        q = np.asarray(quat, dtype=np.float64)
+        if q.ndim < 1 or q.shape[-1] != 4:
+            raise ValueError(f"rig_pose: quat is [..., 4] = (w, x, y, z), got {q.shape}")
+        with np.errstate(all="ignore"):
+            n = np.sqrt((q * q).sum(axis=-1, keepdims=True))
+        if not (np.isfinite(n).all() and (n > 0).all()):
+            raise ValueError("rig_pose: quat must have a finite, non-zero norm")
+        w, x, y, z = np.moveaxis(q / n, -1, 0)
+        R = np.stack([np.stack([1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)], axis=-1),
+                      np.stack([2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)], axis=-1),
+                      np.stack([2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)], axis=-1)], axis=-2)
+    elif R is None:
+        R = np.eye(3)
+    R = np.asarray(R, dtype=np.float64)
+    if R.ndim < 2 or R.shape[-2:] != (3, 3):
+        raise ValueError(f"rig_pose: R is [..., 3, 3], got {R.shape}")
+    lead = np.broadcast_shapes(R.shape[:-2], t.shape[:-1])
+    out = np.empty(lead + (3, 4))
+    out[..., :3] = R
+    out[..., 3] = t
+    return out.reshape(lead + (12,))
+
+
+_rig_pose = rig_pose      # pose_track_world_ref's parameter of that name hides the function inside its body: this name does not
+
+
+def rig_compose(a, b):
+    """``b`` and then ``a``, both [..., 12] as ``rig_pose`` makes them: x -> R_a (R_b x + t_b) + t_a.  "Device in world o left camera in device" is
+    rig_compose(device_in_world, camera_in_device)."""
+    import numpy as np
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if a.ndim < 1 or b.ndim < 1 or a.shape[-1] != 12 or b.shape[-1] != 12:
+        raise ValueError(f"rig_compose: two rig poses [..., 12], got {a.shape} and {b.shape}")
+    A, Bm = a.reshape(a.shape[:-1] + (3, 4)), b.reshape(b.shape[:-1] + (3, 4))
+    R = A[..., :3] @ Bm[..., :3]
+    t = (A[..., :3] @ Bm[..., 3:4])[..., 0] + A[..., 3]
+    return _rig_pose(t, R=R)
+
+
+def pose_track_world_ref(pose, state, rig_pose, dt_or_dts, params=None, frame=None, joints3d=None, streams=1, ortho_tol=1e-6, dtype="float32"):
+    """The records and the state egotap_pose_track_world writes, restated in float64 numpy, operation for operation.  The arguments of
+    ``pose_track_ref`` and ``rig_pose`` [B, 12] float64, per frame the row-major 3 x 4 (R | t) of the left camera in the world
+    -> (tracks [B, K, 8], placed_world [B, P, 3], placed_cam [B, P, 3], new_state [streams, K, 12]).
+
+    A frame's rig pose is seen when its 12 values are finite, every |E_ij| <= ortho_tol with E_ij = ((r_i0 r_j0 + r_i1 r_j1) + r_i2 r_j2) - delta_ij,
+    and det R = (r00 (r11 r22 - r12 r21) - r01 (r10 r22 - r12 r20)) + r02 (r10 r21 - r11 r20) > 0 (every comparison false on a NaN).  The
+    acceptance tests of ``pose_track_ref`` apply to the camera-frame values; an accepted m enters ``pose_track_ref``'s step as
+    ((R[r][0] m0 + R[r][1] m1) + R[r][2] m2), plus t[r] for the root and the joints (points; the pose rows are offsets).  A frame whose rig pose is
+    not seen accepts no track: a missing sample.  placed_world is ``pose_track_ref``'s placed; placed_cam the same float64 value p back in the frame's
+    camera, d = p - t where the root took part and d = p where not, out[c] = ((R[0][c] d0 + R[1][c] d1) + R[2][c] d2), zeros where placed_world is
+    zeros and for a frame whose rig pose is not seen."""
+    import numpy as np
+    who = "pose_track_world_ref"
+    prm, S, T, P, J, st, dts, meas, acc = _track_inputs(who, pose, state, dt_or_dts, params, frame, joints3d, streams)
+    g = np.asarray(rig_pose, dtype=np.float64)
+    if g.shape != (T * S, 12):
+        raise ValueError(f"{who}: rig_pose is [T * streams, 12] = {(T * S, 12)}, got {g.shape}")
+    tol = float(ortho_tol)
+    if not tol >= 0:
+        raise ValueError(f"{who}: ortho_tol must be >= 0, got {ortho_tol}")
+    g = g.reshape(T, S, 3, 4)
+    R, tr = g[..., :3], g[..., 3]
+    with np.errstate(all="ignore"):
+        seen = np.isfinite(g).all(axis=(-1, -2))
+        for i in range(3):
+            for j in range(i, 3):
+                e = ((R[..., i, 0] * R[..., j, 0] + R[..., i, 1] * R[..., j, 1]) + R[..., i, 2] * R[..., j, 2]) - (1.0 if i == j else 0.0)
+                seen &= np.abs(e) <= tol
+        c0 = R[..., 1, 1] * R[..., 2, 2] - R[..., 1, 2] * R[..., 2, 1]
+        c1 = R[..., 1, 0] * R[..., 2, 2] - R[..., 1, 2] * R[..., 2, 0]
+        c2 = R[..., 1, 0] * R[..., 2, 1] - R[..., 1, 1] * R[..., 2, 0]
+        seen &= (R[..., 0, 0] * c0 - R[..., 0, 1] * c1) + R[..., 0, 2] * c2 > 0.0
+        acc = acc & seen[..., None]
+        m = np.where(acc[..., None], meas, 0.0)               # a rejected measurement is never read
+        Rk = R[:, :, None]                                    # [T, S, 1, 3, 3] against the K tracks
+        rot = (Rk[..., 0] * m[..., 0:1] + Rk[..., 1] * m[..., 1:2]) + Rk[..., 2] * m[..., 2:3]
+        point = np.arange(P + 1 + J) >= P
+        m_w = np.where(point[:, None], rot + tr[:, :, None], rot)
+        tracks, placed, with_root, new_state = _track_run(prm, P, st, dts, m_w, acc)
+        d = np.where(with_root[..., None, None], placed - tr[:, :, None], placed)
+        cam = (Rk[..., 0, :] * d[..., 0:1] + Rk[..., 1, :] * d[..., 1:2]) + Rk[..., 2, :] * d[..., 2:3]
+        cam = np.where((tracks[..., :P, 7] != 0)[..., None] & seen[..., None, None], cam, 0.0)
+    B = T * S
+    return tracks.reshape(B, -1, 8).astype(dtype), placed.reshape(B, P, 3).astype(dtype), cam.reshape(B, P, 3).astype(dtype), new_state

@@ -494,6 +494,37 @@ typedef struct egotap_track_params {
 } egotap_track_params;
 int egotap_pose_track(const float* pose, const float* frame, const float* joints3d, int T, int S, int P, int J, const float* dts, double dt,
                       const egotap_track_params* params, const double* state_in, double* state_out, float* tracks, float* placed, void* stream);
+/* ---- the same filter in a world frame, from the headset's own pose (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * egotap_pose_track filters in the left camera's frame, and the camera sits on a head: every head turn moves a motionless body through that frame, so the
+ * filter either lags the whole skeleton or opens its cutoff and passes the jitter it exists to remove.  egotap_pose_track_world takes, per frame, the pose of
+ * the LEFT CAMERA IN THE WORLD and filters there.  Tracks (K = P + 1 + J), state [S, K, 12] float64, time-major frames b = t * S + s, egotap_track_params,
+ * dts / dt and the step are those of egotap_pose_track, all float64 without contraction.  New:
+ *   rig_pose   device f64 [B, 12], 8-byte aligned: the row-major 3 x 4 (R | t) with x_w = R x_c + t, t in the pose's units
+ *   ortho_tol  host double, >= 0
+ * A frame's rig pose is SEEN when all three hold (every comparison false on a NaN): its 12 values are finite; every |E_ij| <= ortho_tol with
+ * E_ij = ((r_i0 r_j0 + r_i1 r_j1) + r_i2 r_j2) - delta_ij; det R > 0 by cofactors along row 0,
+ * det = (r00 (r11 r22 - r12 r21) - r01 (r10 r22 - r12 r20)) + r02 (r10 r21 - r11 r20).  (ortho_tol = +inf leaves only "finite products" and the sign of det.)
+ * The acceptance tests of egotap_pose_track (finite, valid, gates) apply to the camera-frame values; an accepted measurement m then enters the step as
+ *   the root and the joints (points)          m_w[r] = (((R[r][0] m0 + R[r][1] m1) + R[r][2] m2) + t[r])
+ *   the pose rows (pelvis-relative offsets)   m_w[r] =  ((R[r][0] m0 + R[r][1] m1) + R[r][2] m2)
+ * A frame whose rig pose is not seen accepts NO track: by the step's own rule that is a missing sample (the tracks hold, gap_t grows, they expire after
+ * max_hold), and a rig pose that is not seen is never read into the state.  Outputs, f32, each value rounded once from float64:
+ *   tracks       [B, K, 8]  as egotap_pose_track's, in the world
+ *   placed_world [B, P, 3]  egotap_pose_track's placed rule: pose row + root while the root's status is 1 or 2, the pose row alone otherwise, zeros for a
+ *                           pose row of status 0
+ *   placed_cam   [B, P, 3]  the same float64 value p brought back into THIS frame's camera (what an overlay draws): d = p - t where the root took part,
+ *                           d = p where it did not; out[c] = ((R[0][c] d0 + R[1][c] d1) + R[2][c] d2); zeros where placed_world is zeros and for a frame
+ *                           whose rig pose is not seen
+ * A STATE BELONGS TO THE FRAME IT WAS MADE IN: one written by egotap_pose_track holds camera-frame values, one written here world values (of one world:
+ * re-anchoring the world needs a reset), and neither entry can tell.  A zeroed state suits both.
+ * One launch of the same shape (one wave per stream, four streams per workgroup, the state in registers over the T steps), no handle, no allocation, no
+ * atomics, no workspace, plain vector stores; recorded as pose_track_world while a handle's timing hook is on.  egotap_amd/spec.py pose_track_world_ref
+ * restates it; spec.rig_pose / spec.rig_compose build the 12 values ("device in world o left camera in device").
+ * EGOTAP_ERR_INVALID, by name and before any launch: everything egotap_pose_track refuses (its placed is placed_world here); a NULL or misaligned rig_pose
+ * (8 bytes) or placed_cam (4 bytes); an ortho_tol that is NaN or < 0; any overlap that involves rig_pose, placed_world or placed_cam. */
+int egotap_pose_track_world(const float* pose, const float* frame, const float* joints3d, const double* rig_pose, int T, int S, int P, int J, const float* dts,
+                            double dt, const egotap_track_params* params, double ortho_tol, const double* state_in, double* state_out, float* tracks,
+                            float* placed_world, float* placed_cam, void* stream);
 
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)

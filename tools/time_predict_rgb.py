@@ -17,6 +17,8 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
   triangulation  predict_pose_from_rgb(return_triangulation=True): the keypoints triangulated through a stereo rig, one more launch behind the call
   tracking    the triangulation arm followed by PoseTracker.update on its pose, joints3d and frame: the B frames as B consecutive steps of one stream, one
               more launch behind the triangulation's (report only)
+  tracking_world  the same with a world PoseTracker and the rig's pose per frame (a head that turns and walks; every pose counts): the launch of
+              egotap_pose_track_world in the place of egotap_pose_track's (report only)
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -87,11 +89,23 @@ def arms_for(m, p, left, right):
         tracker.update(pose, joints3d, frame, dt=1.0 / 30)
         return pose
 
+    world_tracker = m.new_pose_tracker(streams=1, world=True)
+    t = torch.arange(B, dtype=torch.float64) / 30
+    half = 0.5 * torch.sin(2 * torch.pi * 0.5 * t)                     # a yaw of up to a radian at 0.5 Hz, as a quaternion about y
+    quat = torch.stack([torch.cos(half), torch.zeros_like(t), torch.sin(half), torch.zeros_like(t)], dim=1)
+    rig_pose = torch.from_numpy(spec.rig_pose(torch.stack([0.3 * t, 1.6 + 0.0 * t, 0.1 * t], dim=1).numpy(), quat=quat.numpy())).cuda()
+
+    def tracking_world():
+        pose, joints3d, frame = m.predict_pose_from_rgb(left, right, return_triangulation=True)
+        world_tracker.update(pose, joints3d, frame, dt=1.0 / 30, rig_pose=rig_pose)
+        return pose
+
     return {"parent": parent,
             "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
             "limbs": lambda: m.predict_pose_from_rgb(left, right, return_limbs=True)[0],
             "triangulation": lambda: m.predict_pose_from_rgb(left, right, return_triangulation=True)[0],
             "tracking": tracking,
+            "tracking_world": tracking_world,
             "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
@@ -220,8 +234,8 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking") else ""
-                print(f"{setting:12s} B={B:<4d} {k:12s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world") else ""
+                print(f"{setting:12s} B={B:<4d} {k:14s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
             del arms, left, right
