@@ -143,8 +143,9 @@ def fc1_wgrad(h, which, dz, src, dw, B):
     return dw
 
 
-def fc1_dgrad_tokens(h, dz, wt, B, seq, D):
-    dtok = torch.empty((B * seq, D), dtype=torch.bfloat16, device=dz.device)
+def fc1_dgrad_tokens(h, dz, wt, B, seq, D, out=None):
+    """dtok bf16 [B*seq, D] = scatter(dz bf16 [B*T, 2048] x wt bf16 [ppd^2 D, 2048]^T) in token order, dummy tokens zero; out: the caller's buffer"""
+    dtok = out if out is not None else torch.empty((B * seq, D), dtype=torch.bfloat16, device=dz.device)
     _lib.check(_lib.load().egotap_bf16_fc1_dgrad_tokens(h, _p(dz), _p(wt), _p(dtok), B, _s()))
     return dtok
 

@@ -516,11 +516,15 @@ class LiftTrainBf16Fn(torch.autograd.Function):
                 f = a["name"]
                 dz = T.bn_lrelu_bwd(a["z"], a["y"], dy, P[f + ".bn.weight"], a["mean"], a["rstd"], G[f + ".bn.weight"], G[f + ".bn.bias"])
                 T.colsum(dz, G[f + ".fc.bias"], BT, a["N"])
+                if tr is not None:
+                    tr[f] = t_ = dict(dz=dz)
                 if j > 0:
                     T.gemm_tn(h, dz, a["a_in"], G[f + ".fc.weight"], BT, a["N"], a["K"])
                     dy = T.gemm_nt(h, dz, T.transpose(P[f + ".fc.weight"]), None, BT, a["K"], a["N"], epi=T.TE_NONE)
                 else:
                     dzb = S.from_f32(dz)
+                    if tr is not None:
+                        t_["dzb"] = dzb
                     S.fc1_wgrad(h, which, dzb, src, G[f + ".fc.weight"], B)
                     if wt is not None:
                         return S.fc1_dgrad_tokens(h, dzb, wt, B, seq, D)
@@ -529,6 +533,8 @@ class LiftTrainBf16Fn(torch.autograd.Function):
                         wrt = torch.empty((a["K"], a["N"]), dtype=torch.bfloat16, device=dev)
                         S.prep_weight(wr, torch.empty(wr.shape, dtype=torch.bfloat16, device=dev), wrt)
                         S.fc1_dgrad_rot(h, dzb, wrt, dhm, B)
+                        if tr is not None:
+                            tr["wrt"] = wrt
                     return None
 
         encoder_bwd(Sv["rot_acts"], drotz, 1, Sv["hm_b"], None)
@@ -589,6 +595,8 @@ class LiftTrainBf16Fn(torch.autograd.Function):
             pwt = torch.empty((256, D), dtype=torch.bfloat16, device=dev)
             S.prep_weight(pw, torch.empty((D, 256), dtype=torch.bfloat16, device=dev), pwt)
             S.patch_dgrad(h, dxb, pwt, dhm, B)
+            if tr is not None:
+                tr.update(pwt=pwt, dhm=dhm)
         return _close_backward(ctx, red, P, G, held, dhm)
 
 

@@ -250,6 +250,14 @@ def _vit_layer_bf16(x, sd, pre, heads, r):
     return x + r.bwd(h @ r.w(sd[pre + "output.dense.weight"]).T) + sd[pre + "output.dense.bias"]
 
 
+def tokens_to_cells(x, p: LiftPreset):
+    """[B, seq, D] ViT tokens -> [B*T, ppd*ppd*D]: heatmap i <- its q x q patches, flattened (patch-row, patch-col, channel); the cells
+    past T are dummies and are dropped; net_architecture.py:388-402."""
+    B, T, G, q, D = x.shape[0], p.tokens, p.grid, p.ppd, x.shape[-1]
+    grid = x.view(B, G, q, G, q, D).permute(0, 1, 3, 2, 4, 5).reshape(B, G * G, q * q * D)
+    return grid[:, :T].reshape(B * T, q * q * D)
+
+
 def pos_encoder(pos_hm, sd, p: LiftPreset, trace=None, training=False, round=None, lrelu=None):
     """[B,T,hm,hm] -> [B*T, hidden]  (T tokens in [L_1..L_J, R_1..R_J] order)."""
     pre = "pos_heatmap_encoder."
@@ -265,10 +273,7 @@ def pos_encoder(pos_hm, sd, p: LiftPreset, trace=None, training=False, round=Non
         x = round.act(x)
     if trace is not None:
         trace["final_ln"] = x
-    B, T, G, q, S, D = pos_hm.shape[0], p.tokens, p.grid, p.ppd, p.side, p.vit_dim
-    # heatmap i <- its q x q patches, flattened (patch-row, patch-col, channel); net_architecture.py:388-402
-    grid = x.view(B, G, q, G, q, D).permute(0, 1, 3, 2, 4, 5).reshape(B, G * G, q * q * D)
-    z = grid[:, :T].reshape(B * T, q * q * D)
+    z = tokens_to_cells(x, p)
     stats = {}
     for name in ("fc1", "fc2", "fc3"):
         z = fc_block(z, sd, pre + name, training, round=round if name == "fc1" else None, lrelu=lrelu)

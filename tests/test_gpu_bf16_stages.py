@@ -7,6 +7,8 @@ rows (tools/bf16_emu_probe.py): every bf16 rounding that fl
 fan-out spreads it.  What CAN be gated at one bf16 rounding is every STAGE of the real, orchestrated step against that stage's own
 inputs as the GPU produced them: a tensor wired to the wrong consumer, a missing residual, a transposed weight copy, a wrong bias /
 gradient slot all show up as O(1) errors here, which the 20 % end-to-end gate of test_gpu_configs.py cannot see.
+Both ends of the backward are stages too: fc1's bf16 dz, weight copies and weight gradients, the scattered token gradient, the heatmaps'
+gradient (the step runs with hm.requires_grad_()) and the patch embedding's parameter gradients, with the layouts of head_layout_cases.py.
 The step checked is the operator composition (net.one_call_training = False), which tests/test_gpu_train_step.py proves
 bit-identical to the one-call ABI the wrapper trains through."""
 import math
@@ -15,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import head_layout_cases as H
 from egotap_amd.synthetic import synth_input, synth_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +61,7 @@ def _attn(qkv, B, N, heads, D):
 def test_every_stage_of_the_bf16_step_against_its_own_inputs(preset, B):
     from egotap_amd import networks, spec
     from egotap_amd.options import preset_defaults
+    from egotap_amd import train_ops as T
     from egotap_amd.training import PoseLossFn
     p = spec.lift_preset(preset)
     net = networks.EgoTAPAutoEncoder(preset_defaults(preset), input_channel_scale=2)
@@ -66,7 +70,7 @@ def test_every_stage_of_the_bf16_step_against_its_own_inputs(preset, B):
     net.set_precision("bf16")
     net.one_call_training = False
     net._stage_trace = tr = {}
-    hm = torch.from_numpy(synth_input(f"hm_stage_{preset}", (B, p.in_channels, 64, 64))).cuda()
+    hm = torch.from_numpy(synth_input(f"hm_stage_{preset}", (B, p.in_channels, 64, 64))).cuda().requires_grad_()
     gt = torch.from_numpy(synth_input(f"gt_stage_{preset}", (B, p.out_joints, 3), -1.0, 1.0)).cuda()
     pose = net(hm)[0]
     PoseLossFn.apply(net, pose, gt, 0.1, -0.01).sum().backward()
@@ -171,11 +175,63 @@ def test_every_stage_of_the_bf16_step_against_its_own_inputs(preset, B):
             gate("db " + nme, G[a + nme + ".bias"], d(t["dqkv"])[:, sl].sum(0), 1e-4)
         gate("dy1", d(t["dy1"]), d(t["dqkv"]) @ d(Wl["qkv_t"]).T, ULP)
         gate("dx_out", d(t["dx_out"]), d(t["dxm"]) + _ln_bwd(d(L["x"]), d(t["dy1"]), P[l + "layernorm_before.weight"]), 2e-5)
+        gate("dxb_out", d(t["dxb_out"]), d(t["dx_out"]), ULP)      # (layer 0's feeds the heatmaps' gradient)
         if i > 0:
-            gate("dxb_out", d(t["dxb_out"]), d(t["dx_out"]), ULP)
             gate("db output.dense below (LN column sums)", G[f"{v_}encoder.layer.{i - 1}.output.dense.bias"], d(t["dx_out"]).sum(0), 1e-4)
             assert torch.equal(tr[f"L{i - 1}"]["dx_in"], t["dx_out"]) and torch.equal(tr[f"L{i - 1}"]["dxb_in"], t["dxb_out"])      # wiring
     # patch embedding: position embeddings = batch sum of dx; (bias | mask token) split by the dummy cells
     dx0 = d(tr["L0"]["dx_out"]).view(B, seq, D)
     gate("d position_embeddings", G[v_ + "embeddings.position_embeddings"].reshape(seq, D), dx0.sum(0), 1e-4)
-    print({k: f"{v:.2e}" for k, v in sorted(worst.items(), key=lambda kv: -kv[1])[:8]})
+    vit_gates = set(worst)
+    # ------------------------------------------------------------------------------------------------ both ends of the backward
+    # (layouts from head_layout_cases.py on the host: the oracle's view / permute statements, scatters by autograd)
+    c = lambda t: t.double().cpu()          # noqa: E731
+    fp, fr = "pos_heatmap_encoder.fc1", "rot_heatmap_encoder.fc1"
+    # the remaining weight copies are the rounded masters too: fc1 of both encoders, and the transposed copies built for the heatmaps' gradient
+    pw = P[v_ + "embeddings.patch_embeddings.projection.weight"].reshape(D, 256)
+    assert torch.equal(d(W["fc1p"]), bf(P[fp + ".fc.weight"])) and torch.equal(d(W["fc1p_t"]), bf(P[fp + ".fc.weight"]).T)
+    assert torch.equal(d(W["fc1r"]), bf(P[fr + ".fc.weight"])) and torch.equal(d(tr["wrt"]), bf(P[fr + ".fc.weight"]).T)
+    assert torch.equal(d(tr["pwt"]), bf(pw).T)
+    # the FC encoders: fc3, fc2 in fp32 on their saved inputs; fc1's weight gradient on the bf16 dz and the gathered bf16 rows
+    grad32 = {k: v.grad for k, v in net.named_parameters() if v.grad is not None}
+
+    def gate_fc_bias(f):
+        """An FC bias sits in front of a train-mode BatchNorm1d, so its gradient -- the column sums of dz -- is zero but for rounding: the
+        step's and float64's sums are both ~1e-10 against summands of ~1e-5, and 0.68 apart in relative L2 (measured, UnrealEgo B = 2, fc2 of
+        the position encoder).  A relative gate on such a result says nothing about the kernel.  Instead: the slot holds the very bits the
+        column-sum operator gives on the traced dz (wiring), and every column is within the bound of an fp32 sum of n terms taken in any
+        order, n 2^-24 sum|dz|, of the float64 sum (arithmetic)."""
+        dz = tr[f]["dz"]
+        n, cols = dz.shape
+        assert torch.equal(grad32[f + ".fc.bias"], T.colsum(dz, torch.empty(cols, device=dz.device), n, cols)), f
+        err, lim = (G[f + ".fc.bias"] - d(dz).sum(0)).abs(), n * 2.0 ** -24 * d(dz).abs().sum(0)
+        assert bool((err <= lim).all()), f"db {f}: {float((err / lim).max()):.2f} x the fp32 summation bound"
+
+    for acts in (Sv["pos_acts"], Sv["rot_acts"]):
+        for a in acts[1:]:
+            f = a["name"]
+            gate("dW " + f, G[f + ".fc.weight"], d(tr[f]["dz"]).T @ d(a["a_in"]), 1e-4)
+            gate_fc_bias(f)
+    for f, rows in ((fp, tok), (fr, rot)):
+        assert torch.equal(d(tr[f]["dzb"]), bf(tr[f]["dz"])), f
+        gate("dW " + f, G[f + ".fc.weight"], d(tr[f]["dzb"]).T @ rows, 1e-4)
+        gate_fc_bias(f)
+    # fc1's input gradients, scattered: the token gradient (bf16: one rounding) and the heatmaps' rotation channels (fp32 result of bf16 operands)
+    gate("dtok", c(tr["dtok"]), H.scatter(lambda x: H.cells(x, p), (B * seq, D), c(d(tr[fp]["dzb"]) @ d(W["fc1p_t"]).T)), ULP)
+    dhm = c(tr["dhm"])
+    assert torch.equal(hm.grad, tr["dhm"]) and bool(torch.isfinite(dhm).all())
+    sp, sr = H.pos_channels(p), H.rot_channels(p)
+    gate("dhm rotation", dhm[:, sr], H.scatter(lambda x: H.rot_rows(x, p), dhm.shape, c(d(tr[fr]["dzb"]) @ d(tr["wrt"]).T))[:, sr], 2e-5)
+    # the patch embedding: the heatmaps' position channels from layer 0's bf16 dx, the parameter gradients from its fp32 dx
+    gate("dhm position", dhm[:, sp], H.scatter(lambda x: H.patches_of_hm(x, p), dhm.shape, c(d(tr["L0"]["dxb_out"]) @ d(tr["pwt"]).T))[:, sp], 2e-5)
+    # projection.weight: dx0^T patches(hm), a weight-gradient GEMM of the mode (egotap.h, EGOTAP_PREC_BF16: fp32 tensors, operands rounded to
+    # bf16 in registers, fp32 accumulation) -- so the product of the ROUNDED operands is what 1e-4 can hold it to, as for every other weight
+    # gradient above; against the unrounded fp32 operands it is 3.8e-3 away (measured, UnrealEgo B = 2), which is the operand rounding
+    rows, dummy = H.patches(c(Sv["hm_b"])[:, sp], p)
+    dx0c = c(tr["L0"]["dx_out"])
+    e_ = v_ + "embeddings."
+    gate("dW projection", c(G[e_ + "patch_embeddings.projection.weight"]).reshape(D, 256), c(bf(tr["L0"]["dx_out"])).T @ rows, 1e-4)
+    gate("db projection", c(G[e_ + "patch_embeddings.projection.bias"]), dx0c.view(B, seq, D)[:, ~dummy].sum((0, 1)), 1e-4)
+    gate("d mask_token", c(G[e_ + "mask_token"]).reshape(D), dx0c.view(B, seq, D)[:, dummy].sum((0, 1)), 1e-4)
+    print({k: f"{v:.2e}" for k, v in sorted(((k, v) for k, v in worst.items() if k in vit_gates), key=lambda kv: -kv[1])[:8]})
+    print({k: f"{v:.2e}" for k, v in worst.items() if k not in vit_gates})
