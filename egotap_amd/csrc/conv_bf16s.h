@@ -16,6 +16,7 @@
 // Weights are repacked per call into [Cout][tap][Cp] bf16 (the parameters stay the caller's live fp32 tensors).  Producers write
 // straight into channel slices of the next concat buffer (row stride = the concat's channel count): no concat pass.
 #pragma once
+#include "conv_pack_table.h"
 #include "conv_taps.h"
 #include "gemm_bf16s.h"
 
@@ -205,27 +206,8 @@ template <> struct s_epi_exact<SEpiBnBf16<true>> { static constexpr bool value =
 // An estimator forward repacked its 27 convolution weights and folded its 19 BatchNorms with 46 tiny launches (0.46 ms of a 15 ms
 // forward at B = 256, 5 % at B = 32 and 512 x 512).  The parameters stay the caller's live fp32 tensors and nothing is cached across
 // calls -- the whole set is simply converted by ONE launch at the start of the forward, into a region of the workspace that holds
-// every layer's packed copy.  The segment table travels as a kernel argument (2.6 KB): no device-side table to allocate or upload.
-struct PackSeg {
-    const float *w, *b;              // [Cout][Cin][taps] weights, bias (1x1 with bias) or null
-    unsigned dst_w, dst_b;           // byte offsets into the region: packed bf16 weights, padded fp32 bias
-    unsigned short Cout, Cin, Cp, Np;
-    short taps, slab;                // slab: input channels per K slab of a 3x3 weight: 32 (gemm_bf16s.h's XConv3 / XConvE) or 64 (gemm_bf16s64.h's X64Conv3)
-    int first_block;
-};
-struct BnSeg {
-    const float *g, *b, *m, *v;
-    unsigned dst_sc, dst_sh;
-    unsigned short C, Np;
-    int first_block;
-};
-struct PackTable {
-    static constexpr int MAXW = 44, MAXB = 36;        // resnet34: 32 + 3 + 8 convolutions, 35 BatchNorms
-    PackSeg w[MAXW];
-    BnSeg bn[MAXB];
-    int nw, nb, blocks_w, blocks;
-};
-static_assert(sizeof(PackTable) <= 4000, "the table is a kernel argument");
+// every layer's packed copy.  The segment table (PackSeg, BnSeg, PackTable: conv_pack_table.h) travels as a kernel argument (2.6 KB): no
+// device-side table to allocate or upload.
 static __global__ __launch_bounds__(256) void pack_all_bf16s_kernel(PackTable T, char* __restrict__ region) {
     const int blk = blockIdx.x;
     if (blk < T.blocks_w) {

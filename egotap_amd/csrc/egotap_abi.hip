@@ -1,6 +1,12 @@
-// C ABI of libegotap_hip.so (include/egotap.h, include/egotap_debug.h): handle, parameter binding, the lifting-head forward
-// (EgoTAPAutoEncoder.forward, model/net_architecture.py:682-758) as a sequence of HIP launches on the
-// caller's stream, single-operator entry points and the GEMM timing hook.
+// C ABI of libegotap_hip.so (include/egotap.h, include/egotap_debug.h): the one file build.py compiles.  It holds the part switch, each
+// part's list of kernel headers and, below them, the host code.  What more than one part compiles stands in area files, one #include each
+// (abi_*.inc: the handle, the zero fill, the lifting head's and the convolutions' routing, fc1 on the bf16-storage GEMMs); what a single
+// part compiles still stands here, one guarded run per part (core and inference, the three families of training operators, the one-call
+// training step), each to move into area files of its own.
+//
+// The order of the #include lines and of the text is part of the build: it fixes the order in which host code first references kernel
+// templates, clang emits device helpers in that order, and so it decides the schedules hipcc produces (profiles/abi_parts_summary.md
+// section 2, profiles/abi_areas_summary.md).  The fragments are included exactly once, from here, and include nothing themselves.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -90,486 +96,30 @@
 #include "gemm_tn_f32.h"
 #endif
 #include "head_layout.h"      // the head's operand layouts the handle hands out
-#include "conv_bf16s.h"       // PackTable::MAXW sizes a member of the handle: parts 1-3 see this header for the type alone (part 0 launches from it, above)
+#include "conv_pack_table.h"  // PackTable::MAXW sizes a member of the handle: types only (the kernels that read the table are conv_bf16s.h's, in part 0's list)
 
 // ================================================================================================ all four parts: the handle, the bound parameters, the timing bracket
-// ------------------------------------------------------------------------------------------------ handle
-struct Param {
-    void* ptr = nullptr;
-    int64_t numel = 0;
-    int dtype = EGOTAP_F32;
-};
-
-struct LiftParams {   // resolved raw pointers of net_AutoEncoder
-    const float *mask_tok, *pos_emb, *patch_w, *patch_b;
-    struct Layer {
-        const float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *o_w, *o_b, *up_w, *up_b, *dn_w, *dn_b;
-        const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
-    } layer[8];
-    const float *lnf_g, *lnf_b;
-    struct Fc { const float *w, *b, *g, *beta, *mean, *var; } pos_fc[3], rot_fc[3];
-    const float *x2f0_w, *x2f0_b, *x2h0_w, *x2h0_b, *b2h0_w, *b2h0_b, *h2h0_w, *h2h0_b;
-    const float *x2f1_w, *x2f1_b, *x2h1_w, *x2h1_b, *h2h1_w, *h2h1_b;
-    const float *pose_w, *pose_b, *glob_w, *glob_b;
-};
-
-struct HmParams {   // resolved raw pointers of one heatmap estimator (net_HeatMap / net_RotHeatMap)
-    struct Bn { const float *g, *b, *m, *v; long long* nbt; };      // nbt: num_batches_tracked where bound (EGOTAP_I64), else null; m / v are written by the batch-statistics forward
-    const float* stem_w; Bn stem_bn;
-    struct Block { const float *w1, *w2, *wd; Bn bn1, bn2, bnd; } blk[4][6];
-    int nblk[4];        // BasicBlocks per stage (resnet18: 2,2,2,2; resnet34: 3,4,6,3)
-    struct Cv { const float *w, *b; } l1x1[4], up[3], head;   // layerK_1x1 (K=1..4), conv_up1..3, conv_heatmap
-    int n_out;   // output channels of conv_heatmap (2 * heatmaps per eye)
-};
-
-struct egotap_handle_s {
-    egotap_config cfg;
-    // derived (spec.py LiftPreset)
-    int J, T, grid, ppd, side, seq, C, D, H, hid, out_joints;
-    CellGrid cells() const { return CellGrid{seq, side, ppd, grid, T}; }
-    PatchCells patches() const { return PatchCells{C, cfg.hm_size, cells()}; }
-    TokenGather tokens() const { return TokenGather{T, D, seq, side, ppd, grid}; }
-    RotRows rots() const { return RotRows{C, J, cfg.hm_size * cfg.hm_size}; }      // the head's operand layouts (head_layout.h) of this preset
-    std::unordered_map<std::string, int64_t> expect[EGOTAP_NET_COUNT];   // key -> numel (forward-needed keys)
-    std::unordered_map<std::string, Param> bound[EGOTAP_NET_COUNT];
-    bool lift_resolved = false;
-    LiftParams lp;
-    std::unordered_map<std::string, Param> bound_grad;                   // egotap_bind_grad: where egotap_lift_backward writes
-    bool grad_resolved = false;
-    LiftParams lg;                                                       // the same tensors' gradient buffers (running stats unused)
-    bool hm_resolved[EGOTAP_NET_COUNT] = {false, false, false};
-    HmParams hp[EGOTAP_NET_COUNT];
-    int debug_stop = 0;
-    int pu_resident[2] = {-1, -1};     // workgroups of pu_chain_kernel<1> / <2> the device keeps resident (-1: not asked yet)
-    bool pu_chain = true;              // egotap_set_pu_chain: one-launch recurrence (needs the device to itself) or per-step kernels
-    unsigned* pu_fault_host = nullptr; // pinned, device-mapped word: set by pu_solo_kernel when a chain launch had to be redone (pu_chain.h)
-    unsigned* pu_fault_dev = nullptr;  // the same word as the device sees it
-    int pu_faults = 0;                 // chain launches found faulted so far (the chain is switched off for the handle at the first)
-    int pu_debug_drop = 0;             // egotap_debug_pu_drop_workgroups
-    int precision = EGOTAP_PREC_F32;   // arithmetic of the large GEMMs (egotap_set_precision)
-    __bf16* wscratch = nullptr;        // scratch for the bf16 copy of a GEMM's weight matrix (plain-bf16 mode), caller-owned
-    size_t wscratch_bytes = 0;
-    __bf16* ascratch = nullptr;        // scratch for the bf16 copy of a GEMM's activation operand (plain-bf16 mode, gemm_bf16_dma_kernel), caller-owned
-    size_t ascratch_bytes = 0;
-    __bf16* conv_pack = nullptr;       // scratch for repacked conv weights (set per egotap_hm_forward call from the workspace)
-    float* conv_part = nullptr;        // [r4] fp32 egotap_hm_forward only (null outside it): scratch for the input-channel-split partials of conv_f32.h
-    size_t conv_part_floats = 0;
-    // frozen-weight serving (egotap_lift_freeze / egotap_hm_freeze): caller-owned arenas of prepared weights, null = not frozen
-    char* lift_arena = nullptr;                          // lift_frozen_plan's layout; read by the bf16-storage inference forward only
-    char* hm_arena[EGOTAP_NET_COUNT] = {nullptr, nullptr, nullptr};       // pack_all_bf16s_kernel's region of one estimator
-    short hm_arena_slab[EGOTAP_NET_COUNT][PackTable::MAXW] = {};          // ... and the K-slab depth of every packed weight in it: the part of the
-    int hm_arena_nw[EGOTAP_NET_COUNT] = {0, 0, 0};                        // layout that depends on the batch (hm_pack_plan)
-    int rgb_form = 0;                  // EGOTAP_RGB_FORM_*: how the last egotap_predict_pose_rgb handed the heatmaps to the head (egotap_debug.h)
-    // timing
-    bool timing = false;
-    std::vector<hipEvent_t> ev;   // start/stop pairs
-    struct Rec { const char* role; const char* kernel; double flops; };
-    std::vector<Rec> rec;         // one per recorded pair
-    size_t ev_used = 0;
-    std::string detail;           // JSON written by egotap_timing_read
-};
-typedef egotap_handle_s Handle;
-
-struct GemmTimer {   // brackets one GEMM launch when the handle's timing hook is on
-    Handle* h;
-    hipStream_t s;
-    bool on;
-    GemmTimer(Handle* h_, hipStream_t s_, const char* role, const char* kernel, double flops)
-        : h(h_), s(s_), on(h_ && h_->timing) {
-        if (!on) return;
-        if (h->ev_used + 2 > h->ev.size()) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-            h->ev.push_back(a);
-            h->ev.push_back(b);
-        }
-        (void)hipEventRecord(h->ev[h->ev_used], s);
-        h->rec.push_back({role, kernel, flops});
-    }
-    ~GemmTimer() {
-        if (!on) return;
-        (void)hipEventRecord(h->ev[h->ev_used + 1], s);
-        h->ev_used += 2;
-    }
-};
-
-// large GEMMs (ViT projections, fc1): 256x256 tile, 3-stage pipelined kernel -- fewest global-load
-// instructions per MFMA (each costs the matrix pipe ~56 cycles, tools/mfma_probe.hip), DESIGN.md section 4
-static int device_cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
+#include "abi_handle.inc"
 
 // ================================================================================================ parts 0, 1 and 3: the zero fill
 #if EGOTAP_IN(0) || EGOTAP_IN(1) || EGOTAP_IN(3)
-// stream-ordered zero fill as a KERNEL: a hipMemsetAsync captured into a HIP graph did not re-execute on replay (ROCm 7.2: the
-// propagation units' cell state then carried over from one replay to the next), a kernel node does
-static __global__ __launch_bounds__(256) void zero_fill_kernel(f32x4* __restrict__ p, long n16) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n16) p[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-static hipError_t zero_fill(void* p, size_t bytes, hipStream_t s) {       // p 16-byte aligned, bytes a multiple of 16
-    if (bytes == 0) return hipSuccess;
-    if ((((uintptr_t)p) | bytes) & 15) return hipErrorInvalidValue;
-    const long n16 = (long)(bytes / 16);
-    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (f32x4*)p, n16);
-    return hipGetLastError();
-}
+#include "abi_zero_fill.inc"
 #endif
 
 // ================================================================================================ parts 0 and 1: what the lifting head's forward and its training operators share
 // (GEMM tiles and routing, parameter resolver, the propagation units' residency probe)
 #if EGOTAP_IN(0) || EGOTAP_IN(1)
-// ------------------------------------------------------------------------------------------------ tiles
-using TileA = GemmCfg<128, 128, 32, 2, 2, 2>;   // 4 waves, 64x64 per wave, 2 blocks/CU
-using TileB = GemmCfg<256, 128, 32, 4, 2, 2>;   // 8 waves, 64x64 per wave, 1 block/CU
-using TileC = GemmCfg<128, 256, 32, 2, 4, 2>;   // 8 waves, 64x64 per wave, 1 block/CU
-using TileD = GemmCfg<256, 256, 16, 4, 2, 2>;   // 8 waves, 64x128 per wave, 1 block/CU
-using TileE = GemmCfg<256, 128, 16, 2, 2, 2>;   // 4 waves, 128x64 per wave, 2 blocks/CU
-using TileF = GemmCfg<64, 64, 32, 2, 2, 2>;     // 4 waves, 32x32 per wave (small problems)
-using TileG = GemmCfg<256, 128, 32, 2, 2, 1>;   // 4 waves, 128x64 per wave, 1 block/CU
-using TileS = GemmCfg<64, 128, 32, 2, 4, 1>;    // [r4] 8 waves, 32x32 per wave (two waves per SIMD when the workgroup is alone on its CU: -1.8 % on a B = 1 forward against 4 waves): GEMMs of at most 64 rows (the encoders' fc layers and the PU projections at B <= 2-4) --
-                                                // on the 128-row tile a 30-row product is paced by its MFMAs on 98 rows of zeros (fc1 at B = 1: 1.7 TB/s of weights)
-using PipeA = PipeCfg<128, 128, 16, 2, 2, 2>;   // pipelined: 3 x 20 KiB slabs, 2 blocks/CU
-using PipeB = PipeCfg<128, 128, 32, 2, 2, 1>;   // pipelined: 3 x 36 KiB slabs, 1 block/CU
-using PipeC = PipeCfg<256, 128, 16, 4, 2, 2>;   // pipelined, 8 waves: 3 x 30 KiB slabs, 1 block/CU
-using PipeD = PipeCfg<256, 256, 16, 4, 2, 2>;   // pipelined, 8 waves 64x128 per wave: 3 x 40 KiB slabs
-
-typedef std::unordered_map<std::string, Param> ParamMap;
-static const float* P(Handle*, const ParamMap& m, const std::string& key, bool& ok) {
-    auto it = m.find(key);
-    if (it == m.end()) {
-        if (ok) egotap_set_error("'%s' is not bound", key.c_str());
-        ok = false;
-        return nullptr;
-    }
-    return (const float*)it->second.ptr;
-}
-
-// fills a LiftParams from a key -> pointer map: the parameters (with_stats: and the BatchNorm running statistics) or their gradients
-static int lift_resolve_into(Handle* h, const ParamMap& N, LiftParams& p, bool with_stats) {
-    bool ok = true;
-    const std::string v = "pos_heatmap_encoder.vit.";
-    p.mask_tok = P(h, N, v + "embeddings.mask_token", ok);
-    p.pos_emb = P(h, N, v + "embeddings.position_embeddings", ok);
-    p.patch_w = P(h, N, v + "embeddings.patch_embeddings.projection.weight", ok);
-    p.patch_b = P(h, N, v + "embeddings.patch_embeddings.projection.bias", ok);
-    for (int i = 0; i < h->cfg.vit_layers; ++i) {
-        const std::string l = v + "encoder.layer." + std::to_string(i) + ".";
-        auto& L = p.layer[i];
-        L.q_w = P(h, N, l + "attention.attention.query.weight", ok); L.q_b = P(h, N, l + "attention.attention.query.bias", ok);
-        L.k_w = P(h, N, l + "attention.attention.key.weight", ok);   L.k_b = P(h, N, l + "attention.attention.key.bias", ok);
-        L.v_w = P(h, N, l + "attention.attention.value.weight", ok); L.v_b = P(h, N, l + "attention.attention.value.bias", ok);
-        L.o_w = P(h, N, l + "attention.output.dense.weight", ok);    L.o_b = P(h, N, l + "attention.output.dense.bias", ok);
-        L.up_w = P(h, N, l + "intermediate.dense.weight", ok);       L.up_b = P(h, N, l + "intermediate.dense.bias", ok);
-        L.dn_w = P(h, N, l + "output.dense.weight", ok);             L.dn_b = P(h, N, l + "output.dense.bias", ok);
-        L.ln1_g = P(h, N, l + "layernorm_before.weight", ok);        L.ln1_b = P(h, N, l + "layernorm_before.bias", ok);
-        L.ln2_g = P(h, N, l + "layernorm_after.weight", ok);         L.ln2_b = P(h, N, l + "layernorm_after.bias", ok);
-    }
-    p.lnf_g = P(h, N, v + "layernorm.weight", ok);
-    p.lnf_b = P(h, N, v + "layernorm.bias", ok);
-    const char* encs[2] = {"pos_heatmap_encoder", "rot_heatmap_encoder"};
-    for (int e = 0; e < 2; ++e)
-        for (int i = 0; i < 3; ++i) {
-            const std::string f = std::string(encs[e]) + ".fc" + std::to_string(i + 1);
-            LiftParams::Fc& fc = e == 0 ? p.pos_fc[i] : p.rot_fc[i];
-            fc.w = P(h, N, f + ".fc.weight", ok);        fc.b = P(h, N, f + ".fc.bias", ok);
-            fc.g = P(h, N, f + ".bn.weight", ok);        fc.beta = P(h, N, f + ".bn.bias", ok);
-            fc.mean = fc.var = nullptr;
-            if (with_stats) { fc.mean = P(h, N, f + ".bn.running_mean", ok); fc.var = P(h, N, f + ".bn.running_var", ok); }
-        }
-    const std::string c = "skel_sequential_layer.lstm_custom.layers.";
-    p.x2f0_w = P(h, N, c + "0.x2f.weight", ok); p.x2f0_b = P(h, N, c + "0.x2f.bias", ok);
-    p.x2h0_w = P(h, N, c + "0.x2h.weight", ok); p.x2h0_b = P(h, N, c + "0.x2h.bias", ok);
-    p.b2h0_w = P(h, N, c + "0.b2h.weight", ok); p.b2h0_b = P(h, N, c + "0.b2h.bias", ok);
-    p.h2h0_w = P(h, N, c + "0.h2h.weight", ok); p.h2h0_b = P(h, N, c + "0.h2h.bias", ok);
-    p.x2f1_w = P(h, N, c + "1.x2f.weight", ok); p.x2f1_b = P(h, N, c + "1.x2f.bias", ok);
-    p.x2h1_w = P(h, N, c + "1.x2h.weight", ok); p.x2h1_b = P(h, N, c + "1.x2h.bias", ok);
-    p.h2h1_w = P(h, N, c + "1.h2h.weight", ok); p.h2h1_b = P(h, N, c + "1.h2h.bias", ok);
-    p.pose_w = P(h, N, "pose_mlp.pose_fcs.0.weight", ok); p.pose_b = P(h, N, "pose_mlp.pose_fcs.0.bias", ok);
-    p.glob_w = p.glob_b = nullptr;
-    if (h->cfg.estimate_head) {
-        p.glob_w = P(h, N, "global_mlp.pose_fcs.0.weight", ok);
-        p.glob_b = P(h, N, "global_mlp.pose_fcs.0.bias", ok);
-    }
-    return ok ? EGOTAP_OK : EGOTAP_ERR_UNBOUND;
-}
-
-static int lift_resolve(Handle* h) {
-    if (h->lift_resolved) return EGOTAP_OK;
-    const int rc = lift_resolve_into(h, h->bound[EGOTAP_NET_LIFT], h->lp, true);
-    if (rc != EGOTAP_OK) return rc;
-    h->lift_resolved = true;
-    return EGOTAP_OK;
-}
-
-template <class AL> struct AlName;
-template <> struct AlName<ALoadPlain> { static constexpr const char* v = "ALoadPlain"; };
-template <> struct AlName<ALoadPatch> { static constexpr const char* v = "ALoadPatch"; };
-template <> struct AlName<ALoadTokens> { static constexpr const char* v = "ALoadTokens"; };
-template <> struct AlName<ALoadLive> { static constexpr const char* v = "ALoadLive"; };
-template <> struct AlName<ALoadHead> { static constexpr const char* v = "ALoadHead"; };
-template <> struct AlName<ALoadRot> { static constexpr const char* v = "ALoadRot"; };
-template <> struct AlName<ALoadStereo> { static constexpr const char* v = "ALoadStereo"; };
-template <> struct AlName<ALoadStereoGated> { static constexpr const char* v = "ALoadStereoGated"; };
-template <class E> struct EpiName;
-template <> struct EpiName<EpiBias> { static constexpr const char* v = "EpiBias"; };
-template <> struct EpiName<EpiBiasRes> { static constexpr const char* v = "EpiBiasRes"; };
-template <> struct EpiName<EpiBiasResLive> { static constexpr const char* v = "EpiBiasResLive"; };
-template <> struct EpiName<EpiBiasHead> { static constexpr const char* v = "EpiBiasHead"; };
-template <> struct EpiName<EpiBiasGelu> { static constexpr const char* v = "EpiBiasGelu"; };
-template <> struct EpiName<EpiBnLrelu> { static constexpr const char* v = "EpiBnLrelu"; };
-template <> struct EpiName<EpiPatch> { static constexpr const char* v = "EpiPatch"; };
-
-template <class Cfg, class AL, class Epi>
-static hipError_t gemm(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc,
-                       int M, int N, int K, hipStream_t s) {
-    static const std::string kname = std::string("gemm_f32_kernel<") + std::to_string(Cfg::BM) + "x" +
-                                     std::to_string(Cfg::BN) + "x" + std::to_string(Cfg::BK) + "," + AlName<AL>::v + "," +
-                                     EpiName<Epi>::v + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * M * N * K);
-    return gemm_f32_launch<Cfg, AL, Epi>(al, W, epi, C, ldc, M, N, K, s);
-}
-
-// rows of an fp32 matrix (row stride lda) -> dense bf16 [M, K]
-static __global__ __launch_bounds__(256) void f32_to_bf16_rows_kernel(const float* __restrict__ src, long lda, __bf16* __restrict__ dst, int k8, long n8) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n8) return;
-    const long row = i / k8;
-    const float* p = src + row * lda + (i - row * k8) * 8;
-    *(bf16x8*)(dst + i * 8) = bf16_round8(*(const f32x4*)p, *(const f32x4*)(p + 4));
-}
-// plain-bf16 GEMM: W rounded to bf16 into the handle's scratch right before the launch (stream ordered), so the W operand costs
-// half the vector-memory bytes; without a scratch (or if it is too small) the kernel converts fp32 weights on the fly.
-// A plain row-major activation operand is rounded to bf16 the same way (egotap_set_act_scratch; skipped when the scratch is
-// absent or too small) and the product runs on the
-// LDS-DMA kernel (gemm_bf16_dma.h): same rounding of both operands, same fp32 accumulation order per output element.
-template <class AL, class Epi>
-static hipError_t gemm_bf16_plain(Handle* h, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc, int M, int N, int K, hipStream_t s) {
-    const int nseg = N / W.seg;
-    if (h && h->wscratch && (size_t)N * K * 2 <= h->wscratch_bytes && K % 8 == 0 && W.ld == K && nseg >= 1 && nseg <= 3 && nseg * W.seg == N) {
-        SegMatB B;
-        for (int i = 0; i < 3; ++i) B.p[i] = h->wscratch + (size_t)(i < nseg ? i : 0) * W.seg * K;
-        B.seg = W.seg; B.ld = K;
-        const long n8 = (long)W.seg * K / 8;
-        for (int i = 0; i < nseg; ++i)
-            hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, W.p[i], h->wscratch + (size_t)i * W.seg * K, n8);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if constexpr (std::is_same<AL, ALoadPlain>::value) {
-            if (K % DmaCfg::BK == 0 && N % DmaCfg::BN == 0 && W.seg % DmaCfg::BN == 0 && al.lda % 4 == 0 && M >= 1024) {
-                __bf16* a = (size_t)M * K * 2 <= h->ascratch_bytes ? h->ascratch : nullptr;
-                if (a) {
-                    const long a8 = (long)M * K / 8;
-                    hipLaunchKernelGGL(f32_to_bf16_rows_kernel, dim3((unsigned)((a8 + 255) / 256)), dim3(256), 0, s, al.A, al.lda, a, K / 8, a8);
-                    e = hipGetLastError();
-                    if (e != hipSuccess) return e;
-                    return gemm_bf16_dma_launch(a, (long)K, B, epi, C, ldc, M, N, K, device_cu_count(), s);
-                }
-            }
-        }
-        return gemm_bf16_persist_launch<BfCfg<1, 1>, AL, Epi, SegMatB>(al, B, epi, C, ldc, M, N, K, device_cu_count(), s);
-    }
-    return gemm_bf16_persist_launch<BfCfg<1, 1>, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-}
-
-template <class AL, class Epi>
-static hipError_t gemm_big(Handle* h, const char* role, const AL& al, const SegMat& W, const Epi& epi, float* C, long ldc,
-                           int M, int N, int K, hipStream_t s) {
-    using Cfg = PipeD;
-    if (h && h->precision == EGOTAP_PREC_BF16X3) {
-        static const std::string kname3 = std::string("gemm_bf16_persist_kernel<256x256x16,bf16x3,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-        GemmTimer t(h, s, role, kname3.c_str(), 2.0 * M * N * K);
-        return gemm_bf16_persist_launch<BfCfg<3, 1>, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-    }
-    if (h && h->precision == EGOTAP_PREC_BF16) {
-        static const std::string kname1 = std::string("gemm_bf16_persist_kernel<256x256x32,bf16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-        GemmTimer t(h, s, role, kname1.c_str(), 2.0 * M * N * K);
-        return gemm_bf16_plain(h, al, W, epi, C, ldc, M, N, K, s);
-    }
-    if constexpr (AL::HAS_PTR) {
-        // loaders that are pure address math: same tile, same k order (bit-identical), slabs staged global -> LDS by DMA (gemm_f32_dma.h)
-        if (N % DmaF32Cfg::BN == 0 && K % DmaF32Cfg::BK == 0 && W.seg % DmaF32Cfg::BN == 0 && W.ld % 4 == 0 && al.dma_ok()) {
-            static const std::string kdma = std::string("gemm_f32_dma_kernel<256x256x16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-            GemmTimer t(h, s, role, kdma.c_str(), 2.0 * M * N * K);
-            return gemm_f32_dma_launch(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-        }
-    }
-    static const std::string kname = std::string("gemm_f32_persist_kernel<256x256x16,") + AlName<AL>::v + "," + EpiName<Epi>::v + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * M * N * K);
-    return gemm_f32_persist_launch<Cfg, AL, Epi>(al, W, epi, C, ldc, M, N, K, device_cu_count(), s);
-}
-
-// ------------------------------------------------------------------------------------------------ workspace
-// asks the device once how many workgroups of the one-launch PU chain it keeps resident (pu_chain.h)
-static void pu_chain_probe(Handle* h) {
-    // A chain launch of an EARLIER call whose row blocks were not co-resident (shared device) was redone on the device by
-    // pu_solo_kernel -- the results were right, but it cost a ~0.1 s stall: from now on this handle walks the steps with the per-step
-    // kernels (same bits).  Read without synchronising: the word is host memory the device writes through.
-    if (h->pu_fault_host && __atomic_load_n(h->pu_fault_host, __ATOMIC_RELAXED) != 0u) {
-        __atomic_store_n(h->pu_fault_host, 0u, __ATOMIC_RELAXED);
-        h->pu_faults++;
-        h->pu_chain = false;
-    }
-    if (!h->pu_chain) { h->pu_resident[0] = h->pu_resident[1] = 0; return; }      // 0 resident workgroups: pu_chain_launch declines
-    if (!h->pu_fault_host) {           // once per handle, at its first forward (never inside a stream capture: wrappers run eagerly first)
-        void* hp = nullptr; void* dp = nullptr;
-        if (hipHostMalloc(&hp, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            h->pu_fault_host = (unsigned*)hp; h->pu_fault_dev = (unsigned*)dp;
-            *h->pu_fault_host = 0u;
-        } else {
-            if (hp) (void)hipHostFree(hp);
-            (void)hipGetLastError();
-        }
-    }
-    if (h->pu_resident[0] <= 0) {
-        h->pu_resident[0] = pu_chain_resident<1>();
-        h->pu_resident[1] = pu_chain_resident<2>();
-    }
-}
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-enum { TE_NONE = 0, TE_BIAS = 1, TE_BIAS_RES = 2, TE_BIAS_GELU_SAVE = 3, TE_ACCUM = 4, TE_GELU_GRAD = 5, TE_PATCH = 6, TE_SCATTER_PATCH = 7, TE_SCATTER_ROT = 8 };
+#include "abi_lift_routing.inc"
 #endif
 
 // ================================================================================================ parts 0 and 2: the fp32-tensor convolution routing (estimator forward and training)
 #if EGOTAP_IN(0) || EGOTAP_IN(2)
-//                      taps stride log2W CO_T WCO WPX CI_S
-using C3s1_128_co64 = ConvCfg<9, 1, 7,  64, 2, 4, 8>;    // 128-wide maps: 512x512 RGB (BASELINE config 5)
-using C3s1_128      = ConvCfg<9, 1, 7, 128, 2, 4, 8>;
-using C3s2_64       = ConvCfg<9, 2, 6,  64, 2, 4, 8>;
-using C1s1_128      = ConvCfg<1, 1, 7,  64, 2, 4, 32>;
-using C1s2_64       = ConvCfg<1, 2, 6,  64, 2, 4, 8>;
-using C3s1_64_co64  = ConvCfg<9, 1, 6,  64, 2, 4, 8>;
-using C3s1_64       = ConvCfg<9, 1, 6, 128, 2, 4, 8>;
-using C3s1_32       = ConvCfg<9, 1, 5, 128, 2, 4, 8>;
-using C3s1_16       = ConvCfg<9, 1, 4, 128, 2, 4, 8>;
-using C3s1_8        = ConvCfg<9, 1, 3, 128, 2, 4, 8>;
-using C3s1_16_co64  = ConvCfg<9, 1, 4,  64, 2, 4, 8>;    // [r3] the same two widths with 64-channel tiles: twice the workgroups where 128-channel
-using C3s1_8_co64   = ConvCfg<9, 1, 3,  64, 2, 4, 8>;    // tiles leave CUs without one (training batches, serving batches); same bits (k order unchanged)
-using C3s2_32       = ConvCfg<9, 2, 5,  64, 2, 4, 8>;
-using C3s2_16       = ConvCfg<9, 2, 4,  64, 2, 4, 8>;
-using C3s2_8        = ConvCfg<9, 2, 3,  64, 2, 4, 8>;
-using C1s1_64       = ConvCfg<1, 1, 6,  64, 2, 4, 32>;
-using C1s1_32       = ConvCfg<1, 1, 5, 128, 2, 4, 32>;
-using C1s1_16       = ConvCfg<1, 1, 4, 128, 2, 4, 32>;
-using C1s1_8        = ConvCfg<1, 1, 3, 128, 2, 4, 32>;
-using C1s2_32       = ConvCfg<1, 2, 5,  64, 2, 4, 8>;
-using C1s2_16       = ConvCfg<1, 2, 4,  64, 2, 4, 8>;
-using C1s2_8        = ConvCfg<1, 2, 3,  64, 2, 4, 8>;
-
-template <class Cfg>
-static hipError_t conv(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
-    static const std::string kname = std::string("conv_f32_kernel<") + (Cfg::TAPS == 9 ? "3x3" : "1x1") + ",s" +
-                                     std::to_string(Cfg::STRIDE) + ",W" + std::to_string(Cfg::W) + ",co" +
-                                     std::to_string(Cfg::CO_T) + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * Cfg::TAPS * (double)a.Nimg * Cfg::W * Cfg::W);
-    ConvArgs b = a;
-    b.part = h->conv_part;
-    b.part_floats = h->conv_part_floats;
-    return conv_f32_launch<Cfg>(b, s, device_cu_count());
-}
-
-// any other output width (conv_f32_any_kernel: pixel tiles over the flattened (image, y, x) map)
-template <int TAPS, int STRIDE, int CO_T, int PX_T>
-static hipError_t conv_gen(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
-    using Cfg = ConvAnyCfg<TAPS, STRIDE, CO_T, PX_T>;
-    static const std::string kname = std::string("conv_f32_any_kernel<") + (TAPS == 9 ? "3x3" : "1x1") + ",s" + std::to_string(STRIDE) +
-                                     ",co" + std::to_string(CO_T) + ",px" + std::to_string(PX_T) + ">";
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * TAPS * (double)a.Nimg * wout * wout);
-    return conv_f32_any_launch<Cfg>(a, wout, s);
-}
-// tile shape by grid size: 128 x 256 (64 x 256 for Cout <= 64) while that fills the CUs, then 64 x 256, then 64 x 64 (same bits: same k order)
-template <int TAPS, int STRIDE>
-static hipError_t conv_gen_co(Handle* h, const char* role, int wout, const ConvArgs& a, hipStream_t s) {
-    const long t256 = ((long)a.Nimg * wout * wout + 255) / 256, cus = device_cu_count();
-    if (a.Cout > 64 && t256 * ((a.Cout + 127) / 128) >= cus) return conv_gen<TAPS, STRIDE, 128, 256>(h, role, wout, a, s);
-    if (t256 * ((a.Cout + 63) / 64) >= cus) return conv_gen<TAPS, STRIDE, 64, 256>(h, role, wout, a, s);
-    return conv_gen<TAPS, STRIDE, 64, 64>(h, role, wout, a, s);
-}
-
-template <class Cfg>
-static hipError_t conv_bf(Handle* h, const char* role, const ConvArgs& a, hipStream_t s) {
-    static const std::string kname = std::string("conv_bf16_kernel<3x3,s1,W") + std::to_string(Cfg::W) + (Cfg::NP == 3 ? ",bf16x3>" : ",bf16>");
-    GemmTimer t(h, s, role, kname.c_str(), 2.0 * a.Cout * a.Cin * 9 * (double)a.Nimg * Cfg::W * Cfg::W);
-    return conv_bf16_launch<Cfg>(a, h->conv_pack, s);
-}
-
-// dispatch on (taps, stride, output width): the power-of-two instantiations at wout in {128, 64, 32, 16, 8} (where they exist), every
-// other width >= 1 on conv_f32_any_kernel (exact fp32 in every precision mode)
-static hipError_t conv_any(Handle* h, const char* role, int taps, int stride, int wout, const ConvArgs& a, hipStream_t s) {
-    // opt-in modes: 3x3 stride-1 convs with a multiple of 128 output channels at widths 64 / 32 / 16 run on the bf16 matrix cores
-    if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout >= 128) {
-        const bool x3 = h->precision == EGOTAP_PREC_BF16X3;
-        if (wout == 64) return x3 ? conv_bf<ConvBfCfg<6, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<6, 1>>(h, role, a, s);
-        if (wout == 32) return x3 ? conv_bf<ConvBfCfg<5, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<5, 1>>(h, role, a, s);
-        if (wout == 16) return x3 ? conv_bf<ConvBfCfg<4, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<4, 1>>(h, role, a, s);
-        if (wout == 8) return x3 ? conv_bf<ConvBfCfg<3, 3>>(h, role, a, s) : conv_bf<ConvBfCfg<3, 1>>(h, role, a, s);
-    }
-    if (h->precision != EGOTAP_PREC_F32 && h->conv_pack && taps == 9 && stride == 1 && a.Cout == 64 && wout == 64)   // ResNet layer1
-        return h->precision == EGOTAP_PREC_BF16X3 ? conv_bf<ConvBfCfg<6, 3, 64>>(h, role, a, s) : conv_bf<ConvBfCfg<6, 1, 64>>(h, role, a, s);
-    if (h->precision == EGOTAP_PREC_BF16 && h->conv_pack && taps == 9 && stride == 1 && a.Cout == 64 && wout == 128)   // layer1 at 512x512 RGB
-        return conv_bf<ConvBfCfg<7, 1, 64>>(h, role, a, s);
-    if (taps == 9 && stride == 1) {
-        if (wout == 128) return a.Cout <= 64 ? conv<C3s1_128_co64>(h, role, a, s) : conv<C3s1_128>(h, role, a, s);
-        if (wout == 64) return a.Cout <= 64 ? conv<C3s1_64_co64>(h, role, a, s) : conv<C3s1_64>(h, role, a, s);
-        if (wout == 32) return conv<C3s1_32>(h, role, a, s);
-        // layer3 / layer4 at a 32-frame training batch: 128 / 64 workgroups of 128-channel tiles for 256 CUs (MFMA busy 0.21 on the 8 x 8 maps)
-        const long co128 = (a.Cout + 127) / 128;
-        if (wout == 16) return (long)a.Nimg * co128 < device_cu_count() ? conv<C3s1_16_co64>(h, role, a, s) : conv<C3s1_16>(h, role, a, s);
-        if (wout == 8) return (long)((a.Nimg + 3) / 4) * co128 < device_cu_count() ? conv<C3s1_8_co64>(h, role, a, s) : conv<C3s1_8>(h, role, a, s);
-    } else if (taps == 9 && stride == 2) {
-        if (wout == 64) return conv<C3s2_64>(h, role, a, s);
-        if (wout == 32) return conv<C3s2_32>(h, role, a, s);
-        if (wout == 16) return conv<C3s2_16>(h, role, a, s);
-        if (wout == 8) return conv<C3s2_8>(h, role, a, s);
-    } else if (taps == 1 && stride == 1) {
-        if (wout == 128) return conv<C1s1_128>(h, role, a, s);
-        if (wout == 64) return conv<C1s1_64>(h, role, a, s);
-        if (wout == 32) return conv<C1s1_32>(h, role, a, s);
-        if (wout == 16) return conv<C1s1_16>(h, role, a, s);
-        if (wout == 8) return conv<C1s1_8>(h, role, a, s);
-    } else if (taps == 1 && stride == 2) {
-        if (wout == 64) return conv<C1s2_64>(h, role, a, s);
-        if (wout == 32) return conv<C1s2_32>(h, role, a, s);
-        if (wout == 16) return conv<C1s2_16>(h, role, a, s);
-        if (wout == 8) return conv<C1s2_8>(h, role, a, s);
-    }
-    if (wout < 1) return hipErrorInvalidValue;
-    if (taps == 9 && stride == 1) return conv_gen_co<9, 1>(h, role, wout, a, s);
-    if (taps == 9 && stride == 2) return conv_gen_co<9, 2>(h, role, wout, a, s);
-    if (taps == 1 && stride == 1) return conv_gen_co<1, 1>(h, role, wout, a, s);
-    if (taps == 1 && stride == 2) return conv_gen_co<1, 2>(h, role, wout, a, s);
-    return hipErrorInvalidValue;
-}
+#include "abi_conv_routing.inc"
 #endif
 
 // ================================================================================================ parts 0 and 3: fc1 of the encoders on the bf16-storage GEMMs
 #if EGOTAP_IN(0) || EGOTAP_IN(3)
-// fc1 of an encoder (rows gathered from the ViT tokens / the limb heatmaps) as an NT product: [r5] on the 64-deep kernel where its shape rules hold
-// (D, HW multiples of 64: a K-tile inside one token / map), the 32-deep kernel otherwise or when egotap_debug_gemm_bk pins it; same k order per
-// output element: same bits
-template <class Epi>
-static hipError_t fc1_nt(Handle* h, int which, const __bf16* src, const __bf16* w, long K, const Epi& ep, int BT, int cus, hipStream_t s) {
-    const int HW = h->cfg.hm_size * h->cfg.hm_size;
-    const bool deep = g_gemm_bf16s_bk != 32 && K % 64 == 0 && K >= 128 && (which == 0 ? h->D % 64 == 0 : HW % 64 == 0) && (long)256 * K * 2 < (1L << 31);
-    if (which == 0) {
-        // [r5] tensors under 4 GB (every shipped batch): scalar origin + 32-bit lane offsets (X64TokensS / X64RotS); the pointer loaders otherwise
-        const size_t tok_bytes = (size_t)(BT / h->T) * h->seq * h->D * 2;
-        if (deep && g_conv_addressing == 0 && tok_bytes < ((size_t)1 << 32) - 4096)
-            return gemm_bf16s64_launch_x(X64TokensS{src, 0u, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
-        if (deep) return gemm_bf16s64_launch_x(X64Tokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
-        return gemm_bf16s_launch(XTokens{src, h->tokens()}, w, K, ep, BT, 2048, (int)K, cus, s);
-    }
-    const size_t hm_bytes = (size_t)(BT / (2 * h->J)) * h->C * HW * 2;
-    if (deep && g_conv_addressing == 0 && hm_bytes < ((size_t)1 << 32) - 4096) return gemm_bf16s64_launch_x(X64RotS{src, 0u, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
-    if (deep) return gemm_bf16s64_launch_x(X64Rot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
-    return gemm_bf16s_launch(XRot{src, h->rots()}, w, K, ep, BT, 2048, (int)K, cus, s);
-}
+#include "abi_fc1_bf16s.inc"
 #endif
 
 // ================================================================================================ one part each, in the order 0 (core and inference), 1, 2, 3, 0 (the one-call training step)

@@ -279,7 +279,7 @@ static __global__ __launch_bounds__(1024) void pu_chain_kernel(const PuChain p) 
 // of every step itself (Whh re-read from L2 each step: ~16 x slower than the chain).  Launched behind every pu_chain_kernel launch and
 // exits at once unless that launch raised its fault word (a row block whose workgroups were not co-resident: the device is shared with
 // another process, CU-masked, or being debugged) -- then it redoes the launch from the untouched inputs, so the caller still gets the
-// right answer; the host learns about it through the mapped word and stops using the chain for the handle (egotap_abi.hip).
+// right answer; the host learns about it through the mapped word and stops using the chain for the handle (pu_chain_probe, abi_lift_routing.inc).
 // Same k order, reduction order and pointwise expressions as pu_chain_kernel / pu_step_r16_kernel: bit-identical results.
 static __global__ __launch_bounds__(1024) void pu_solo_kernel(const PuChain p) {
     if (__hip_atomic_load(p.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;

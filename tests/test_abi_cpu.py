@@ -80,15 +80,30 @@ def test_head_layouts_and_conv_taps_are_written_once():
 
 
 def test_part_switch_and_exports_are_written_once():
-    """Outside comments only egotap_abi.hip names the part switch (no kernel header decides which part compiles it), the file stands in
-    sections a reader can take in without counting guards, and every exported function is defined exactly once across csrc/."""
+    """Outside comments only egotap_abi.hip names the part switch (no kernel header and no area file decides which part compiles it), the
+    host code that several parts compile stands in area files (abi_*.inc) it includes exactly once each, the file stands in sections a reader
+    can take in without counting guards, and every exported function is defined exactly once across csrc/."""
     csrc = os.path.join(REPO, "egotap_amd", "csrc")
     code = {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, f)).read(), flags=re.S) for f in sorted(os.listdir(csrc))}
     assert [f for f, t in code.items() if "EGOTAP_IN(" in t] == ["egotap_abi.hip"]
     assert [f for f, t in code.items() if "EGOTAP_PART" in t] == ["egotap_abi.hip"]
+    # every area file is included exactly once, from egotap_abi.hip and from nowhere else, and is plain text of its one place: it includes
+    # nothing and holds no conditional (a file-local #define / #undef, EGO_RC for one, is all the preprocessor it may speak)
+    areas = sorted(f for f in code if re.fullmatch(r"abi_\w+\.inc", f))
+    assert areas
+    included = {f: re.findall(r'#\s*include\s*"(abi_\w+\.inc)"', t) for f, t in code.items()}
+    assert sorted(included["egotap_abi.hip"]) == areas, sorted(set(included["egotap_abi.hip"]) ^ set(areas))
+    assert not [f for f, inc in included.items() if inc and f != "egotap_abi.hip"]
+    for f in areas:
+        directives = re.findall(r"^[ \t]*#[ \t]*(\w+)", code[f], flags=re.M)
+        assert set(directives) <= {"define", "undef"}, (f, sorted(set(directives)))
     # egotap_abi.hip stands in sections: part guards are never nested and have one branch; the code guarded for a set of several parts is ONE
     # run, in front of every single part's code; a single part's code is one run (part 0: two, the one-call training step comes last)
-    runs, cond, body = [], None, []      # (parts, holds code besides #include lines)
+    # A run is one of three kinds and never a mixture: kernel headers alone (#include lines, no area file), area files alone, or -- a single
+    # part's run only, until it has moved into area files too -- text with no area file in it.  Whatever several parts compile, and
+    # whatever stands outside every guard, is preprocessor lines only: no host code enters egotap_abi.hip except in a single part's run.
+    area_line = lambda l: re.match(r'#\s*include\s*"abi_\w+\.inc"', l)
+    runs, cond, body = [], None, []      # (parts, holds code: area files or text, not kernel headers alone)
     for line in code["egotap_abi.hip"].splitlines():
         line = line.strip()
         if "EGOTAP_IN(" in line and not line.startswith("#define"):
@@ -98,7 +113,10 @@ def test_part_switch_and_exports_are_written_once():
         elif cond is not None and re.match(r"#\s*(else|elif)", line):
             raise AssertionError("a part guard has one branch")
         elif cond is not None and line.startswith("#endif"):
-            runs.append((cond, any(not l.startswith("#include") for l in body)))
+            n_area, n_text = sum(1 for l in body if area_line(l)), sum(1 for l in body if not l.startswith("#include"))
+            assert n_area in (0, len(body)) and not (n_area and n_text), ("a run mixes area files with other lines", cond)
+            assert not (n_text and len(cond) > 1), ("what several parts compile stands in area files", cond)
+            runs.append((cond, bool(n_area or n_text)))
             cond = None
         elif cond is not None and line:
             assert not re.match(r"#\s*if", line), "nothing conditional inside a part guard: " + line
@@ -107,6 +125,12 @@ def test_part_switch_and_exports_are_written_once():
     shared = [c for c in sections if len(c) > 1]
     assert len(set(shared)) == len(shared) >= 1 and sections[:len(shared)] == shared, sections
     assert sections[len(shared):] == [(0,), (1,), (2,), (3,), (0,)], sections
+    # no part takes a kernel header for a type: the handle's PackTable::MAXW comes from a header without kernels or launchers, and
+    # conv_bf16s.h is named once, inside a guard (part 0's list of kernel headers)
+    assert not re.search(r"__global__|hipLaunchKernelGGL|#\s*include", code["conv_pack_table.h"])
+    unguarded = re.sub(r"#if EGOTAP_IN.*?#endif", "", code["egotap_abi.hip"], flags=re.S)
+    assert not [l for l in unguarded.splitlines() if l.strip() and not l.lstrip().startswith("#")]
+    assert '"conv_pack_table.h"' in unguarded and '"conv_bf16s.h"' not in unguarded and code["egotap_abi.hip"].count('"conv_bf16s.h"') == 1
     everything = "\n".join(code.values())
     for name in L.exported_symbols():
         assert len(re.findall(rf'extern\s+"C"[^;{{}}()]*\b{name}\s*\(', everything)) == 1, name
@@ -116,7 +140,7 @@ def test_part_switch_and_exports_are_written_once():
 def test_no_part_sees_an_abi_helper_it_does_not_use(part):
     """A static launcher or kernel a translation unit can see is compiled into its code object whether it launches it or not, so each part
     (-DEGOTAP_PART=n) must use every function egotap_abi.hip shows it: the host-only syntax pass with -Wunused-function names none that is
-    defined in egotap_abi.hip.  (Kernel headers two parts use different halves of may still warn there:
+    defined in egotap_abi.hip or in an area file it includes (abi_*.inc).  (Kernel headers two parts use different halves of may still warn there:
     profiles/abi_parts_summary.md lists them.)  Built as a single translation unit (no part) nothing at all is unused.  The opposite mistake
     is an error in the same pass: a part that calls a static launcher whose defining header it was not given (-Werror=undefined-internal; the
     build itself only warns, and the shared library would link with the symbol missing)."""
@@ -133,7 +157,7 @@ def test_no_part_sees_an_abi_helper_it_does_not_use(part):
     assert res.returncode == 0, res.stderr[-4000:]
     unused = re.findall(r"^(\S+?):\d+:\d+: warning: unused function '(\w+)'", res.stderr, flags=re.M)
     assert "unused function" not in re.sub(r"^\S+?:\d+:\d+: warning: unused function '\w+'", "", res.stderr, flags=re.M)      # every such warning was parsed
-    assert not [(f, n) for f, n in unused if os.path.basename(f) == "egotap_abi.hip"]
+    assert not [(f, n) for f, n in unused if os.path.basename(f) == "egotap_abi.hip" or re.fullmatch(r"abi_\w+\.inc", os.path.basename(f))]
     if part is None:
         assert not unused
 

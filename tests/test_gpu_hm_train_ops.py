@@ -208,7 +208,7 @@ def _rb(t):
 
 
 def _bf_kernel(mode, taps, stride, cout, w):
-    """does conv_any (egotap_abi.hip) route this forward-form convolution to conv_bf16_kernel?"""
+    """does conv_any (abi_conv_routing.inc) route this forward-form convolution to conv_bf16_kernel?"""
     return mode != "f32" and taps == 9 and stride == 1 and ((cout >= 128 and w in (64, 32, 16, 8)) or (cout == 64 and w == 64)
                                                            or (mode == "bf16" and cout == 64 and w == 128))
 

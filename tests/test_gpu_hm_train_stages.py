@@ -59,7 +59,7 @@ def rb(t):
 
 
 def fwd_route(mode, taps, stride, cout, w):
-    """precision of the kernel conv_any picks (egotap_abi.hip) for a forward-form convolution with `cout` output channels at width w"""
+    """precision of the kernel conv_any picks (abi_conv_routing.inc) for a forward-form convolution with `cout` output channels at width w"""
     if mode == "f32" or taps != 9 or stride != 1:
         return "f32"
     if (cout >= 128 and w in (64, 32, 16, 8)) or (cout == 64 and w == 64) or (mode == "bf16" and cout == 64 and w == 128):
