@@ -61,6 +61,7 @@
 #include "limb_decode.h"
 #include "ocam.h"
 #include "pose_track.h"
+#include "skeleton_fit.h"
 #endif
 #if EGOTAP_IN(1)
 #include "attention_f32.h"
@@ -2422,6 +2423,99 @@ extern "C" int egotap_pose_track_world(const float* pose, const float* frame, co
                                        float* placed_world, float* placed_cam, void* stream) {
     return pose_track_entry("egotap_pose_track_world", true, pose, frame, joints3d, rig_pose, T, S, P, J, dts, dt, params, ortho_tol, state_in, state_out, tracks,
                             placed_world, placed_cam, stream);
+}
+
+// ---- a rigid skeleton and bone rotations from the tracked pose (skeleton_fit.h): one operator behind the trackers, no handle
+extern "C" int egotap_skeleton_fit(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_params* params,
+                                   const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths, void* stream) {
+    static const char* const who = "egotap_skeleton_fit";
+    EGO_CHECK(points && rig && params && rigid && rotations && lengths,
+              "%s: null argument (points, rig, params, rigid, rotations and lengths are required; tracks may be NULL)", who);
+    const bool fixed = rig->has_fixed_length != 0;
+    EGO_CHECK(fixed || (state_in && state_out), "%s: null argument (state_in and state_out are required unless the rig has fixed_length)", who);
+    if (fixed) state_in = nullptr, state_out = nullptr;      // neither read nor written
+    const int P = rig->P;
+    EGO_CHECK(T > 0 && S > 0 && P > 0, "%s: T, S and P must be positive (T = %d, S = %d, P = %d)", who, T, S, P);
+    EGO_CHECK(P <= kSkelMaxRows, "%s: at most %d rows, one lane each (P = %d)", who, kSkelMaxRows, P);
+    EGO_CHECK((int64_t)T * S <= INT32_MAX, "%s: T * S = %lld frames do not fit an int", who, (long long)T * S);
+    EGO_CHECK((((uintptr_t)points | (uintptr_t)tracks) & 3) == 0, "%s: points and tracks must be 4-byte aligned", who);
+    EGO_CHECK((((uintptr_t)rigid | (uintptr_t)rotations | (uintptr_t)lengths) & 15) == 0, "%s: rigid, rotations and lengths must be 16-byte aligned", who);
+    EGO_CHECK((((uintptr_t)state_in | (uintptr_t)state_out) & 7) == 0, "%s: state_in and state_out must be 8-byte aligned", who);
+    // the rig, and what the kernel takes of it
+    SkelRigDev dev = {};
+    dev.P = P;
+    dev.has_fixed = fixed;
+    int roots = 0;
+    for (int j = 0; j < P; ++j) roots += rig->parent[j] == -1;
+    EGO_CHECK(roots > 0, "%s: rig: no root row (parent -1)", who);
+    for (int j = 0; j < P; ++j) {
+        const int p = rig->parent[j];
+        EGO_CHECK(p == -1 || (p >= 0 && p < j), "%s: rig: parent[%d] = %d: a parent is -1 (a root row) or an earlier row, 0 <= parent < row", who, j, p);
+        dev.parent[j] = (int8_t)p;
+        dev.mirror[j] = -1;
+        dev.depth[j] = p < 0 ? 0 : (int8_t)(dev.depth[p] + 1);
+        dev.max_depth = dev.depth[j] > dev.max_depth ? dev.depth[j] : dev.max_depth;
+    }
+    const int32_t* fr = rig->frame_rows;
+    EGO_CHECK(fr[0] >= 0 && fr[0] < P && fr[1] >= 0 && fr[1] < P && fr[2] >= 0 && fr[2] < P && fr[0] != fr[1] && fr[0] != fr[2] && fr[1] != fr[2],
+              "%s: rig: frame_rows are three distinct rows 0 .. %d (%d, %d, %d)", who, P - 1, fr[0], fr[1], fr[2]);
+    dev.fa = fr[0], dev.fb = fr[1], dev.fc = fr[2];
+    SkelVec rest[kSkelMaxRows];
+    for (int j = 0; j < P; ++j)
+        for (int c = 0; c < 3; ++c) {
+            EGO_CHECK(ego_finite(rig->rest_pos[j][c]), "%s: rig: rest_pos[%d][%d] is not finite", who, j, c);
+            rest[j].v[c] = rig->rest_pos[j][c];
+        }
+    for (int j = 0; j < P; ++j) {
+        if (dev.parent[j] < 0) continue;
+        const SkelVec &a = rest[j], &b = rest[dev.parent[j]], d = {{a.v[0] - b.v[0], a.v[1] - b.v[1], a.v[2] - b.v[2]}};
+        const double n = skel_norm3(d);
+        EGO_CHECK(skel_pos_finite(n), "%s: rig: the rest bone of row %d has length %g: a zero or non-finite rest bone has no direction", who, j, n);
+        for (int c = 0; c < 3; ++c) dev.rest_dir[j][c] = d.v[c] / n;
+    }
+    SkelVec frame[3];
+    EGO_CHECK(skel_frame(rest[fr[0]], rest[fr[1]], rest[fr[2]], frame), "%s: rig: the rest pose's triangle of rows (%d, %d, %d) is degenerate", who, fr[0], fr[1],
+              fr[2]);
+    for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < 3; ++c) dev.rest_frame[k][c] = frame[k].v[c];
+    if (rig->has_mirror)
+        for (int j = 0; j < P; ++j) {
+            const int m = rig->mirror[j];
+            if (m == -1) continue;
+            EGO_CHECK(m >= 0 && m < P && rig->mirror[m] == j, "%s: rig: mirror[%d] = %d is not an involution (mirror[mirror[j]] == j, or -1)", who, j, m);
+            EGO_CHECK(dev.parent[j] >= 0 && dev.parent[m] >= 0, "%s: rig: mirror[%d] = %d pairs a root row, which has no bone", who, j, m);
+            dev.mirror[j] = (int8_t)m;
+        }
+    if (fixed)
+        for (int j = 0; j < P; ++j) {
+            if (dev.parent[j] < 0) continue;
+            EGO_CHECK(skel_pos_finite(rig->fixed_length[j]), "%s: rig: fixed_length[%d] = %g must be finite and > 0", who, j, rig->fixed_length[j]);
+            dev.fixed_length[j] = rig->fixed_length[j];
+        }
+    const egotap_skeleton_params& q = *params;
+    EGO_CHECK(q.window >= 1, "%s: params: window must be at least 1 (%d)", who, q.window);
+    EGO_CHECK(q.min_samples >= 0, "%s: params: min_samples must not be negative (%d)", who, q.min_samples);
+    EGO_CHECK(q.max_dev >= 0.0, "%s: params: max_dev must be >= 0, +inf for off (%g)", who, q.max_dev);      // (a NaN fails the comparison)
+    EGO_CHECK(!tracks || q.track_rows == 0 || q.track_rows >= P, "%s: params: track_rows = %d: tracks holds at least the P = %d rows (0: exactly P)", who,
+              q.track_rows, P);
+    const size_t B = (size_t)T * S, K = tracks && q.track_rows ? (size_t)q.track_rows : (size_t)P;
+    const SkelParamsDev prm = {(double)q.window, (double)q.min_samples, q.max_dev, q.freeze != 0, (int32_t)K};
+    const struct {
+        const char* name;
+        const void* p;
+        size_t n;
+    } in[3] = {{"points", points, B * P * 12}, {"tracks", tracks, B * K * 32}, {"state_in", state_in, (size_t)S * P * 16}},
+      out[4] = {{"state_out", state_out, (size_t)S * P * 16}, {"rigid", rigid, B * P * 16}, {"rotations", rotations, B * P * 32}, {"lengths", lengths, B * P * 8}};
+    for (int o = 0; o < 4; ++o) {      // (with fixed_length the states are NULL: they overlap nothing)
+        for (int i = 0; i < 3; ++i) {
+            if (o == 0 && i == 2 && state_out == state_in) continue;      // in place
+            EGO_CHECK(!ego_overlap(out[o].p, out[o].n, in[i].p, in[i].n), "%s: %s overlaps %s", who, out[o].name, in[i].name);
+        }
+        for (int p = o + 1; p < 4; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
+    }
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "skeleton_fit", "skeleton_fit_kernel", 0.0);
+    EGO_HIP(skeleton_fit_launch(points, tracks, T, S, dev, prm, state_in, state_out, rigid, rotations, lengths, (hipStream_t)stream));
+    return EGOTAP_OK;
 }
 
 extern "C" int egotap_debug_predict_pose_rgb_form(egotap_handle h, int* form) {

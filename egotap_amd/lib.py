@@ -31,6 +31,15 @@ class EgotapTrackParams(C.Structure):                 # egotap.h egotap_track_pa
         (n, C.c_double) for n in ("max_disagree", "max_gap", "max_joint_gap")] + [("min_joints", C.c_int32), ("max_hold", C.c_int32)]
 
 
+class EgotapSkeletonRig(C.Structure):                 # egotap.h egotap_skeleton_rig: 2584 bytes
+    _fields_ = [("P", C.c_int32), ("has_mirror", C.c_int32), ("has_fixed_length", C.c_int32), ("frame_rows", C.c_int32 * 3), ("parent", C.c_int32 * 64),
+                ("mirror", C.c_int32 * 64), ("rest_pos", (C.c_double * 3) * 64), ("fixed_length", C.c_double * 64)]
+
+
+class EgotapSkeletonParams(C.Structure):              # egotap.h egotap_skeleton_params: a double and four ints
+    _fields_ = [("max_dev", C.c_double), ("window", C.c_int32), ("min_samples", C.c_int32), ("freeze", C.c_int32), ("track_rows", C.c_int32)]
+
+
 class EgotapYuvSource(C.Structure):                   # egotap.h egotap_yuv_source: seven int32 (then padding) and two int64
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "format", "matrix", "range", "H", "W", "pitch")] + [("uv_offset", C.c_int64), ("frame_stride", C.c_int64)]
 
@@ -121,6 +130,10 @@ _PROTOS = {
     # (pose, frame, joints3d, rig_pose, T, S, P, J, dts, dt, params, ortho_tol, state_in, state_out, tracks, placed_world, placed_cam, stream)
     "egotap_pose_track_world": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double,
                                           C.POINTER(EgotapTrackParams), C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ---- a rigid skeleton and bone rotations from the tracked pose: one operator, no handle
+    # (points, tracks, T, S, rig, params, state_in, state_out, rigid, rotations, lengths, stream)
+    "egotap_skeleton_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapSkeletonRig), C.POINTER(EgotapSkeletonParams), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -867,6 +880,82 @@ def pose_track_world(pose, state, rig_pose, dt=None, dts=None, params=None, fram
         pose_track_world_into(prm, ps, fr, j3, rig_pose.detach().contiguous(), T, S, dts.contiguous() if dts is not None else None, dt, ortho_tol, state, state,
                               tracks, placed_world, placed_cam, ps.device)
     return tracks, placed_world, placed_cam
+
+
+def skeleton_rig_struct(rig) -> EgotapSkeletonRig:
+    """a ``spec.SkeletonRig`` as the ABI takes it (egotap_skeleton_rig, by pointer to host memory)"""
+    from . import spec
+    if not isinstance(rig, spec.SkeletonRig):
+        raise ValueError(f"skeleton_fit: rig is a spec.SkeletonRig (spec.skeleton_rig builds one), got {type(rig).__name__}")
+    o = EgotapSkeletonRig()
+    o.P, o.has_mirror, o.has_fixed_length = rig.P, rig.mirror is not None, rig.fixed_length is not None
+    o.frame_rows[:] = rig.frame_rows
+    for j in range(rig.P):
+        o.parent[j] = rig.parents[j]
+        o.mirror[j] = rig.mirror[j] if rig.mirror is not None else -1
+        o.rest_pos[j][:] = [float(v) for v in rig.rest_pos[j]]
+        o.fixed_length[j] = float(rig.fixed_length[j]) if rig.fixed_length is not None else 0.0
+    return o
+
+
+def skeleton_params_struct(params=None, track_rows=0) -> EgotapSkeletonParams:
+    """a ``spec.SkeletonParams`` (None: the defaults) as the ABI takes it; ``track_rows``: K of the tracks array (0: none, or exactly P)"""
+    from . import spec
+    prm = spec.SkeletonParams() if params is None else params
+    if not isinstance(prm, spec.SkeletonParams):
+        raise ValueError(f"skeleton_fit: params is a spec.SkeletonParams, got {type(prm).__name__}")
+    return EgotapSkeletonParams(prm.max_dev, prm.window, prm.min_samples, int(prm.freeze), int(track_rows))
+
+
+def skeleton_fit_into(rig_c, prm_c, points, tracks, T, S, state_in, state_out, rigid, rotations, lengths, dev):
+    """the launch itself on ``dev``'s current stream: ``rig_c`` / ``prm_c`` from ``skeleton_rig_struct`` / ``skeleton_params_struct``, tensors as the
+    ABI takes them (tracks may be None; the states too with a fixed_length rig)"""
+    check(load().egotap_skeleton_fit(_ptr(points), _ptr(tracks), int(T), int(S), C.byref(rig_c), C.byref(prm_c), _ptr(state_in), _ptr(state_out), _ptr(rigid),
+                                     _ptr(rotations), _ptr(lengths), _stream(dev)))
+
+
+def skeleton_fit(points, state, rig, params=None, tracks=None, streams=1, _structs=None):
+    """A rigid skeleton and a rotation per bone from tracked joint positions (egotap_skeleton_fit, ``spec.skeleton_fit_ref``): points float32
+    [T * streams, P, 3] on the GPU, T consecutive frames of ``streams`` camera rigs, time-major -- a tracker's ``placed``, ``placed_world`` or
+    ``placed_cam``; ``state`` float64 [streams, P, 2] = (L^, n) per row on the same device, all zeros for uncalibrated, UPDATED IN PLACE (None with a
+    rig that has ``fixed_length``, which reads and writes none); ``rig`` a ``spec.SkeletonRig`` of the same P; ``params`` a ``spec.SkeletonParams``
+    (None: its defaults); ``tracks`` float32 [T * streams, K, 8] the tracker's records (a row then also needs status 1 or 2 to count as seen)
+    -> (rigid float32 [T * streams, P, 4] = (x, y, z, flags), rotations float32 [T * streams, P, 8] = (global wxyz, local wxyz), lengths float32
+    [T * streams, P, 2] = (the length used, n)).  One launch on the current stream, no synchronisation."""
+    import torch
+    who = "skeleton_fit"
+    rig_c, prm_c = _structs if _structs is not None else (skeleton_rig_struct(rig), skeleton_params_struct(params))
+    S, P = int(streams), rig.P
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] != 3 or S < 1 or points.shape[0] < S or points.shape[0] % S:
+        raise ValueError(f"{who}: points is a tensor [T * streams, P, 3] with T >= 1, got {tuple(getattr(points, 'shape', ()))} for {streams} streams")
+    if points.shape[1] != P:
+        raise ValueError(f"{who}: the rig has P = {P} rows, points has {points.shape[1]}")
+    if points.dtype != torch.float32 or not points.is_contiguous():
+        raise ValueError(f"{who}: points is a contiguous float32 tensor, got {points.dtype}{'' if points.is_contiguous() else ', not contiguous'}")
+    B = int(points.shape[0])
+    T = B // S
+    K = 0
+    if tracks is not None:
+        if not torch.is_tensor(tracks) or tracks.dim() != 3 or tracks.shape[0] != B or tracks.shape[1] < P or tracks.shape[2] != 8:
+            raise ValueError(f"{who}: tracks is a tensor [T * streams, K, 8] with K >= P = {P}, got {tuple(getattr(tracks, 'shape', ()))} for {B} frames")
+        if tracks.dtype != torch.float32 or not tracks.is_contiguous():
+            raise ValueError(f"{who}: tracks is a contiguous float32 tensor, got {tracks.dtype}{'' if tracks.is_contiguous() else ', not contiguous'}")
+        K = int(tracks.shape[1])
+    fixed = rig.fixed_length is not None
+    if fixed and state is not None:
+        raise ValueError(f"{who}: a rig with fixed_length calibrates nothing: it reads and writes no state (pass state=None)")
+    if not fixed and (not torch.is_tensor(state) or tuple(state.shape) != (S, P, 2) or state.dtype != torch.float64 or not state.is_contiguous()):
+        raise ValueError(f"{who}: state is a contiguous float64 tensor [streams, P, 2] = {(S, P, 2)}, got "
+                         f"{getattr(state, 'dtype', type(state).__name__)} {tuple(getattr(state, 'shape', ()))}")
+    if not _on_one_gpu(points, tracks, state):
+        raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); points, tracks and state on one cuda device")
+    prm_c.track_rows = K
+    rigid = torch.empty((B, P, 4), dtype=torch.float32, device=points.device)
+    rotations = torch.empty((B, P, 8), dtype=torch.float32, device=points.device)
+    lengths = torch.empty((B, P, 2), dtype=torch.float32, device=points.device)
+    with torch.cuda.device(points.device):
+        skeleton_fit_into(rig_c, prm_c, points.detach(), tracks.detach() if tracks is not None else None, T, S, state, state, rigid, rotations, lengths, points.device)
+    return rigid, rotations, lengths
 
 
 KINEMATIC_PARENTS = {          # utils/util.py:51-52

@@ -114,6 +114,82 @@ class PoseTracker:
             self._state[idx] = 0.0
 
 
+class Skeleton:
+    """A rigid skeleton and a rotation per bone behind a tracker (``lib.skeleton_fit``, egotap_skeleton_fit, ``spec.skeleton_fit_ref``): per stream the
+    bone lengths are calibrated over time ((L^, n) per row, float64 [streams, P, 2] on the device, zeros = uncalibrated), re-imposed on the tracked
+    positions, and each bone gets a global and a parent-relative rotation against the rig's rest pose.  Made by ``model.new_skeleton``; holds no
+    reference to the model and takes no part in its graphs.  A rig with ``fixed_length`` retargets to the avatar's own proportions and keeps no state."""
+
+    def __init__(self, P, joint_preset=None, rig=None, streams=1, params=None):
+        self.P, self.joint_preset, self.streams = int(P), joint_preset, int(streams)
+        if self.streams < 1:
+            raise ValueError(f"Skeleton: streams must be at least 1, got {streams}")
+        self.params = _spec.SkeletonParams() if params is None else params
+        _lib.skeleton_params_struct(self.params)           # (the type check, now rather than at the first update)
+        self.rig = None
+        self._state = None
+        self._structs = None
+        if rig is not None:
+            self._set_rig(rig)
+
+    def _set_rig(self, rig):
+        rig_c = _lib.skeleton_rig_struct(rig)
+        if rig.P != self.P:
+            raise ValueError(f"Skeleton: the rig has P = {rig.P} rows, the model's pose has {self.P}")
+        self.rig, self._structs = rig, (rig_c, _lib.skeleton_params_struct(self.params))
+
+    def set_rest_pose(self, pose_rows, mirror=True):
+        """one frame [P, 3] (a tensor or an array) taken as the rest pose, the "stand in a T-pose" calibration (``spec.skeleton_rig_from_pose`` with the
+        model's joint preset); the calibrated lengths stay"""
+        if self.joint_preset is None:
+            raise ValueError("Skeleton.set_rest_pose: this skeleton was made without a joint preset; give new_skeleton a rig")
+        self._set_rig(_spec.skeleton_rig_from_pose(self.joint_preset, pose_rows, mirror=mirror))
+        return self.rig
+
+    @property
+    def state(self):
+        """the device tensor (made on the current cuda device at its first use: an update makes it on the points' device); None with fixed_length"""
+        return self._state_on(torch.device("cuda", torch.cuda.current_device()))
+
+    def _state_on(self, dev):
+        if self.rig is not None and self.rig.fixed_length is not None:
+            return None
+        if self._state is None:
+            self._state = torch.zeros((self.streams, self.P, _spec.SKELETON_STATE), dtype=torch.float64, device=dev)
+        return self._state
+
+    @torch.no_grad()
+    def update(self, points, tracks=None):
+        """T consecutive frames of every stream, time-major: ``points`` float32 [T * streams, P, 3], a tracker's ``placed``, ``placed_world`` or
+        ``placed_cam``; ``tracks`` the tracker's records [T * streams, K, 8] (a row that the tracker has forgotten is then not seen)
+        -> (rigid [T * streams, P, 4], rotations [T * streams, P, 8], lengths [T * streams, P, 2]).  ONE launch on the current stream, no
+        synchronisation: it queues behind the tracker's."""
+        if self.rig is None:
+            raise ValueError("Skeleton.update: no rig: the project ships no avatar; give model.new_skeleton a spec.skeleton_rig(...) or call "
+                             "set_rest_pose(pose_rows) with one frame to take as the rest pose")
+        if not torch.is_tensor(points) or not points.is_cuda:
+            raise _lib.EgotapError("Skeleton.update runs on the GPU only (no CPU fallback); points is a cuda tensor")
+        return _lib.skeleton_fit(points, self._state_on(points.device), self.rig, params=self.params, tracks=tracks, streams=self.streams, _structs=self._structs)
+
+    def freeze(self, on=True):
+        """stop (or resume) calibrating: the lengths found so far go on being used"""
+        self.params = _spec.SkeletonParams(self.params.window, self.params.min_samples, self.params.max_dev, bool(on))
+        if self._structs is not None:
+            self._structs[1].freeze = int(bool(on))
+
+    def reset(self, streams=None):
+        """forget the calibration of every stream (None) or of the named ones: their next frame is a first frame"""
+        if self._state is None:
+            return
+        if streams is None:
+            self._state.zero_()
+        else:
+            idx = [int(s) for s in ([streams] if isinstance(streams, int) else streams)]
+            if any(not 0 <= s < self.streams for s in idx):
+                raise ValueError(f"Skeleton.reset: streams are 0 .. {self.streams - 1}, got {idx}")
+            self._state[idx] = 0.0
+
+
 class _Source(NamedTuple):
     """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor / _sensor_yuv / _lens); everything else about a request is ``_serve``'s."""
     who: str                          # the entry's name, for messages
@@ -865,6 +941,14 @@ class EgoTAPAutoEncoderModel(nn.Module):
         ``ortho_tol`` (None: 1e-6; a world tracker's alone) bounds how far a rig pose's matrix may be from a rotation and still count."""
         p = self.net_AutoEncoder.preset
         return PoseTracker(p.out_joints, p.n_joints_hm, streams=streams, params=params, world=world, ortho_tol=ortho_tol)
+
+    def new_skeleton(self, rig=None, streams=1, params=None):
+        """A ``Skeleton`` for this model's pose rows: rigid bones and a rotation per bone from what a tracker returns,
+        ``placed, tracks = tracker.update(...)``; ``rigid, rotations, lengths = skeleton.update(placed, tracks)`` -- one more launch on the same stream.
+        ``rig`` a ``spec.skeleton_rig(...)`` of the avatar (its rest pose, and its own bone lengths to retarget); None: the skeleton refuses to update
+        until ``set_rest_pose(pose_rows)`` has taken one frame as the rest pose -- the project ships no avatar.  ``params`` a ``spec.SkeletonParams``
+        (None: its defaults, which nobody has tuned on real data).  The serving entries, the trackers, their graphs and their outputs do not change."""
+        return Skeleton(self.net_AutoEncoder.preset.out_joints, joint_preset=self.opt.joint_preset, rig=rig, streams=streams, params=params)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

@@ -1290,3 +1290,352 @@ def pose_track_world_ref(pose, state, rig_pose, dt_or_dts, params=None, frame=No
         cam = np.where((tracks[..., :P, 7] != 0)[..., None] & seen[..., None, None], cam, 0.0)
     B = T * S
     return tracks.reshape(B, -1, 8).astype(dtype), placed.reshape(B, P, 3).astype(dtype), cam.reshape(B, P, 3).astype(dtype), new_state
+
+
+# ---- a rigid skeleton and bone rotations from the tracked pose (egotap.h: egotap_skeleton_fit) -------------------------------------------
+SKELETON_MAX_ROWS = 64                         # P: one lane each
+SKELETON_STATE = 2                             # per row: (L^, n)
+SKELETON_ANTIPARALLEL = -1.0 + 1e-12           # v . u above this: the shortest arc's regular branch
+SKELETON_FRAME_ROWS = {"UnrealEgo": (1, 2, 3),       # neck_01, upperarm_l, upperarm_r
+                       "EgoCap": (0, 9, 13)}         # neck, left_hip, right_hip (rows = the reference's joints 1 .. 17)
+SKELETON_MIRROR = {"UnrealEgo": (-1, -1) + tuple(j ^ 1 for j in range(2, 16)),
+                   "EgoCap": (-1,) + tuple(range(5, 9)) + tuple(range(1, 5)) + tuple(range(13, 17)) + tuple(range(9, 13))}
+
+
+@dataclass(frozen=True)
+class SkeletonParams:
+    """egotap.h egotap_skeleton_params.  ``window``: a bone's length is the exact mean of its first ``window`` accepted samples, then an exponential
+    average with alpha = 1 / window; ``min_samples``: below this many accepted samples every valid sample is taken; from then on one is taken when
+    |l - L^| <= max_dev L^ (``max_dev`` relative, +inf: every one); ``freeze``: the lengths are used and no longer updated.  With min_samples = 0 an
+    empty state never accepts a sample (|l - 0| <= max_dev 0 is false).  Nobody has tuned any of these on real data: there is no dataset here."""
+    window: int = 120
+    min_samples: int = 10
+    max_dev: float = math.inf
+    freeze: bool = False
+
+    def __post_init__(self):
+        w, m, d = int(self.window), int(self.min_samples), float(self.max_dev)
+        if w < 1:
+            raise ValueError(f"SkeletonParams: window must be at least 1, got {self.window}")
+        if m < 0:
+            raise ValueError(f"SkeletonParams: min_samples must not be negative, got {self.min_samples}")
+        if not d >= 0:
+            raise ValueError(f"SkeletonParams: max_dev must be >= 0 (+inf: off), got {self.max_dev}")
+        for name, v in (("window", w), ("min_samples", m), ("max_dev", d), ("freeze", bool(self.freeze))):
+            object.__setattr__(self, name, v)
+
+
+def skeleton_parents(joint_preset):
+    """The parent row of every pose row, -1 for the root row (utils/util.py:51-52).  "UnrealEgo": the 16 rows with the head as the root.  "EgoCap":
+    joints 1 .. 17 as rows 0 .. 16, the neck the root row: the camera-to-neck bone is dropped, as the reference's loss drops it."""
+    from .lib import KINEMATIC_PARENTS
+    if joint_preset not in KINEMATIC_PARENTS:
+        raise ValueError(f"skeleton_parents: joint_preset is {joint_preset!r}, expected one of {sorted(KINEMATIC_PARENTS)}")
+    par = KINEMATIC_PARENTS[joint_preset]
+    if joint_preset == "EgoCap":
+        return tuple(p - 1 if j > 1 else -1 for j, p in enumerate(par) if j >= 1)
+    return tuple(p if j > 0 else -1 for j, p in enumerate(par))
+
+
+def _sk_norm3(d):
+    return math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+
+
+def _sk_cross(a, b):
+    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+
+
+def _sk_ok(n):
+    return 0.0 < n <= 1.7976931348623157e308          # finite and > 0; false on a NaN
+
+
+def skeleton_frame(xa, xb, xc):
+    """the orthonormal frame of three points, rows (e0, e1, e2), or None where a norm in its construction is zero or not finite:
+    e0 = normalize(xb - xc); w = xa - (xb + xc) / 2; e1 = normalize(w - (w . e0) e0); e2 = e0 x e1"""
+    f = tuple(xb[i] - xc[i] for i in range(3))
+    n0 = _sk_norm3(f)
+    if not _sk_ok(n0):
+        return None
+    e0 = tuple(f[i] / n0 for i in range(3))
+    w = tuple(xa[i] - 0.5 * (xb[i] + xc[i]) for i in range(3))
+    p = (w[0] * e0[0] + w[1] * e0[1]) + w[2] * e0[2]
+    g = tuple(w[i] - p * e0[i] for i in range(3))
+    n1 = _sk_norm3(g)
+    if not _sk_ok(n1):
+        return None
+    e1 = tuple(g[i] / n1 for i in range(3))
+    return (e0, e1, _sk_cross(e0, e1))
+
+
+def quat_sign(q):
+    """the sign rule: w >= 0; at w == 0 the first non-zero of x, y, z is positive"""
+    w, x, y, z = q
+    neg = w < 0 or (w == 0 and (x < 0 or (x == 0 and (y < 0 or (y == 0 and z < 0)))))
+    return (-w, -x, -y, -z) if neg else (w, x, y, z)
+
+
+def quat_normalize(q):
+    n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
+    return (q[0] / n, q[1] / n, q[2] / n, q[3] / n)
+
+
+def quat_mul(a, b):
+    """Hamilton's a (x) b on (w, x, y, z), each component added left to right"""
+    return (((a[0] * b[0] - a[1] * b[1]) - a[2] * b[2]) - a[3] * b[3],
+            ((a[0] * b[1] + a[1] * b[0]) + a[2] * b[3]) - a[3] * b[2],
+            ((a[0] * b[2] - a[1] * b[3]) + a[2] * b[0]) + a[3] * b[1],
+            ((a[0] * b[3] + a[1] * b[2]) - a[2] * b[1]) + a[3] * b[0])
+
+
+def quat_conj(q):
+    return (q[0], -q[1], -q[2], -q[3])
+
+
+def quat_rotate(q, v):
+    """v' = (v + w t) + q_v x t with t = 2 (q_v x v)"""
+    qv = q[1:]
+    c = _sk_cross(qv, v)
+    t = (2.0 * c[0], 2.0 * c[1], 2.0 * c[2])
+    k = _sk_cross(qv, t)
+    return tuple((v[i] + q[0] * t[i]) + k[i] for i in range(3))
+
+
+def quat_from_frames(cur, rest):
+    """quat(M_cur M_rest^T) of two frames given as rows (e0, e1, e2): R[i][j] = (e0c[i] e0r[j] + e1c[i] e1r[j]) + e2c[i] e2r[j], then Shepperd's rule,
+    which divides by the largest of (trace, R00, R11, R22) only -- t = (R00 + R11) + R22:
+        t > 0                     s = 2 sqrt(t + 1);                  (w, x, y, z) = (s / 4, (R21 - R12) / s, (R02 - R20) / s, (R10 - R01) / s)
+        R00 >= R11 and R00 >= R22 s = 2 sqrt(((1 + R00) - R11) - R22); (w, x, y, z) = ((R21 - R12) / s, s / 4, (R01 + R10) / s, (R02 + R20) / s)
+        R11 >= R22                s = 2 sqrt(((1 + R11) - R00) - R22); (w, x, y, z) = ((R02 - R20) / s, (R01 + R10) / s, s / 4, (R12 + R21) / s)
+        otherwise                 s = 2 sqrt(((1 + R22) - R00) - R11); (w, x, y, z) = ((R10 - R01) / s, (R02 + R20) / s, (R12 + R21) / s, s / 4)
+    then normalised and given its sign"""
+    R = [[(cur[0][i] * rest[0][j] + cur[1][i] * rest[1][j]) + cur[2][i] * rest[2][j] for j in range(3)] for i in range(3)]
+    t = (R[0][0] + R[1][1]) + R[2][2]
+    if t > 0:
+        s = math.sqrt(t + 1.0) * 2.0
+        q = (0.25 * s, (R[2][1] - R[1][2]) / s, (R[0][2] - R[2][0]) / s, (R[1][0] - R[0][1]) / s)
+    elif R[0][0] >= R[1][1] and R[0][0] >= R[2][2]:
+        s = math.sqrt(max(((1.0 + R[0][0]) - R[1][1]) - R[2][2], 0.0)) * 2.0
+        q = ((R[2][1] - R[1][2]) / s, 0.25 * s, (R[0][1] + R[1][0]) / s, (R[0][2] + R[2][0]) / s)
+    elif R[1][1] >= R[2][2]:
+        s = math.sqrt(max(((1.0 + R[1][1]) - R[0][0]) - R[2][2], 0.0)) * 2.0
+        q = ((R[0][2] - R[2][0]) / s, (R[0][1] + R[1][0]) / s, 0.25 * s, (R[1][2] + R[2][1]) / s)
+    else:
+        s = math.sqrt(max(((1.0 + R[2][2]) - R[0][0]) - R[1][1], 0.0)) * 2.0
+        q = ((R[1][0] - R[0][1]) / s, (R[0][2] + R[2][0]) / s, (R[1][2] + R[2][1]) / s, 0.25 * s)
+    return quat_sign(quat_normalize(q))
+
+
+def quat_shortest_arc(v, u):
+    """the swing that takes the unit vector v to the unit vector u by the shortest arc, c = v . u: c > -1 + 1e-12: normalize(1 + c, v x u); otherwise
+    (0, normalize(v x e_k)), k the lowest index of the smallest |v_k| (a half turn about an axis at right angles to v).  Not given a sign."""
+    c = (v[0] * u[0] + v[1] * u[1]) + v[2] * u[2]
+    if c > SKELETON_ANTIPARALLEL:
+        x = _sk_cross(v, u)
+        return quat_normalize((1.0 + c, x[0], x[1], x[2]))
+    k = 0
+    for i in (1, 2):
+        if abs(v[i]) < abs(v[k]):
+            k = i
+    x = _sk_cross(v, tuple(1.0 if i == k else 0.0 for i in range(3)))
+    n = _sk_norm3(x)
+    return (0.0, x[0] / n, x[1] / n, x[2] / n)
+
+
+@dataclass(frozen=True, eq=False)
+class SkeletonRig:
+    """egotap.h egotap_skeleton_rig, checked, with what the entry derives from it: ``rest_dir`` [P, 3] and ``rest_len`` [P] (zeros for root rows),
+    ``rest_frame`` (the rows e0, e1, e2 of the rest pose's triangle) and ``depth`` [P].  Built by ``skeleton_rig``."""
+    P: int
+    parents: tuple
+    rest_pos: object
+    frame_rows: tuple
+    mirror: object
+    fixed_length: object
+    rest_dir: object
+    rest_len: object
+    rest_frame: tuple
+    depth: tuple
+
+
+def skeleton_rig(parents, rest_pos, frame_rows, mirror=None, fixed_length=None):
+    """The avatar a skeleton is fitted to: ``parents`` [P] (-1: a root row; otherwise 0 <= parent < row), ``rest_pos`` [P, 3] the rest pose in any
+    unit, ``frame_rows`` (a, b, c) three distinct rows whose triangle orients the root rows, ``mirror`` [P] the row on the other side of the body or
+    -1 (None: no row has one), ``fixed_length`` [P] the avatar's own bone lengths (None: calibrated from the data) -> a ``SkeletonRig``.  Refuses, by
+    name, what egotap_skeleton_fit refuses."""
+    import numpy as np
+    who = "skeleton_rig"
+    par = tuple(int(p) for p in parents)
+    P = len(par)
+    if not 1 <= P <= SKELETON_MAX_ROWS:
+        raise ValueError(f"{who}: 1 .. {SKELETON_MAX_ROWS} rows, got {P}")
+    if -1 not in par:
+        raise ValueError(f"{who}: no root row (parent -1)")
+    for j, p in enumerate(par):
+        if p != -1 and not 0 <= p < j:
+            raise ValueError(f"{who}: parent[{j}] = {p}: a parent is -1 (a root row) or an earlier row, 0 <= parent < row")
+    rp = np.array(rest_pos, dtype=np.float64)
+    if rp.shape != (P, 3):
+        raise ValueError(f"{who}: rest_pos is [P, 3] = {(P, 3)}, got {rp.shape}")
+    if not np.isfinite(rp).all():
+        raise ValueError(f"{who}: rest_pos must be finite")
+    fr = tuple(int(r) for r in frame_rows)
+    if len(fr) != 3 or any(not 0 <= r < P for r in fr) or len(set(fr)) != 3:
+        raise ValueError(f"{who}: frame_rows are three distinct rows 0 .. {P - 1}, got {fr}")
+    rest_dir, rest_len, depth = np.zeros((P, 3)), np.zeros(P), [0] * P
+    for j, p in enumerate(par):
+        if p < 0:
+            continue
+        d = tuple(float(rp[j, i]) - float(rp[p, i]) for i in range(3))
+        n = _sk_norm3(d)
+        if not _sk_ok(n):
+            raise ValueError(f"{who}: the rest bone of row {j} (to its parent {p}) has length {n}: a zero or non-finite rest bone has no direction")
+        rest_dir[j], rest_len[j], depth[j] = [d[i] / n for i in range(3)], n, depth[p] + 1
+    frame = skeleton_frame(*(tuple(float(v) for v in rp[r]) for r in fr))
+    if frame is None:
+        raise ValueError(f"{who}: the rest pose's triangle of rows {fr} is degenerate: it orients nothing")
+    mir = None
+    if mirror is not None:
+        mir = tuple(int(m) for m in mirror)
+        if len(mir) != P:
+            raise ValueError(f"{who}: mirror holds one row per row, [{P}], got {len(mir)}")
+        for j, m in enumerate(mir):
+            if m == -1:
+                continue
+            if not 0 <= m < P or mir[m] != j:
+                raise ValueError(f"{who}: mirror[{j}] = {m} is not an involution (mirror[mirror[j]] == j, or -1)")
+            if par[j] < 0 or par[m] < 0:
+                raise ValueError(f"{who}: mirror[{j}] = {m} pairs a root row, which has no bone")
+    fixed = None
+    if fixed_length is not None:
+        fixed = np.array(fixed_length, dtype=np.float64)
+        if fixed.shape != (P,):
+            raise ValueError(f"{who}: fixed_length holds one length per row, [{P}], got {fixed.shape}")
+        for j, p in enumerate(par):
+            if p >= 0 and not _sk_ok(float(fixed[j])):
+                raise ValueError(f"{who}: fixed_length[{j}] = {fixed[j]} must be finite and > 0")
+        fixed = np.where(np.array(par) >= 0, fixed, 0.0)
+        fixed.setflags(write=False)
+    for a in (rp, rest_dir, rest_len):
+        a.setflags(write=False)
+    return SkeletonRig(P, par, rp, fr, mir, fixed, rest_dir, rest_len, frame, tuple(depth))
+
+
+def skeleton_rig_from_pose(joint_preset, pose_rows, mirror=True, fixed_length=None):
+    """One frame taken as the rest pose, the "stand in a T-pose" calibration: the preset's parents, frame rows and (``mirror=True``) left / right
+    pairs, ``pose_rows`` [P, 3] relative to its root row"""
+    import numpy as np
+    par = skeleton_parents(joint_preset)
+    ps = np.array(pose_rows.detach().cpu().numpy() if hasattr(pose_rows, "detach") else pose_rows, dtype=np.float64)
+    if ps.shape != (len(par), 3):
+        raise ValueError(f"skeleton_rig_from_pose: pose_rows is one frame [P, 3] = {(len(par), 3)} for {joint_preset}, got {ps.shape}")
+    return skeleton_rig(par, ps - ps[par.index(-1)], SKELETON_FRAME_ROWS[joint_preset], mirror=SKELETON_MIRROR[joint_preset] if mirror else None,
+                        fixed_length=fixed_length)
+
+
+def _sk_div(a, b):
+    """a / b as IEEE has it (a state the caller wrote may hold anything)"""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def skeleton_fit_ref(points, state, rig, params=None, tracks=None, streams=1, dtype="float32"):
+    """The records and the state egotap_skeleton_fit writes, restated in float64, operation for operation: points [B, P, 3] with B = T * streams frames,
+    time-major (frame b = t * streams + s); state [streams, P, 2] float64 = (L^, n) per row (not modified; None with a ``fixed_length`` rig, which
+    reads none); tracks [B, K, 8] (K >= P) the tracker's records or None -> (rigid [B, P, 4], rotations [B, P, 8], lengths [B, P, 2], new_state).
+    One step of one stream, every comparison false on a NaN:
+
+        seen        the row's three inputs are finite (and, with tracks, its status is 1 or 2)
+        sample      non-root: d = x_j - x_p, l = sqrt((d0 d0 + d1 d1) + d2 d2); valid: both ends seen, l finite and > 0; u = d / l
+        update      valid, not frozen, no fixed_length, and (n < min_samples or |l - L^| <= max_dev L^): n = min(n + 1, window), L^ = L^ + (l - L^) / n
+        length L_j  fixed_length[j]; else, after every row's update: L^_j where n_j >= 1, (L^_j + L^_m) / 2 with a mirror m of n_m >= 1; else none
+        rigid       a seen root row passes through; r_j = r_p + L_j u_j where the sample is valid, L_j exists and the parent is ok; else zeros
+        rotation    root rows: quat_from_frames(skeleton_frame(x_a, x_b, x_c), rest frame) where a, b, c are seen and the frame is not degenerate;
+                    others, with a valid sample and a parent whose rotation is ok: v = rotate(Q_p, rest_dir_j), s = quat_shortest_arc(v, u_j),
+                    Q_j = sign(normalize(s (x) Q_p)), local_j = sign(conj(Q_p) (x) Q_j); else the identity (local = global for a root row)
+
+    rigid = (x, y, z, 1 (position ok) + 2 (rotation ok)); rotations = (global wxyz, local wxyz); lengths = (L_j or 0, n_j), zeros for root rows.
+    Each output is rounded once from float64 (``dtype="float64"``: not at all)."""
+    import numpy as np
+    who = "skeleton_fit_ref"
+    if not isinstance(rig, SkeletonRig):
+        raise ValueError(f"{who}: rig is a spec.SkeletonRig (spec.skeleton_rig builds one), got {type(rig).__name__}")
+    prm = SkeletonParams() if params is None else params
+    pts = np.asarray(points, dtype=np.float64)
+    S, P = int(streams), rig.P
+    if pts.ndim != 3 or pts.shape[1:] != (P, 3) or S < 1 or pts.shape[0] < S or pts.shape[0] % S:
+        raise ValueError(f"{who}: points is [T * streams, P, 3] with T >= 1 and the rig's P = {P}, got {pts.shape} for {S} streams")
+    B = pts.shape[0]
+    T = B // S
+    status = None
+    if tracks is not None:
+        tr = np.asarray(tracks, dtype=np.float64)
+        if tr.ndim != 3 or tr.shape[0] != B or tr.shape[1] < P or tr.shape[2] != 8:
+            raise ValueError(f"{who}: tracks is [T * streams, K, 8] with K >= P, got {tr.shape} for {B} frames of {P} rows")
+        status = tr[:, :P, 7]
+    fixed = rig.fixed_length is not None
+    if fixed:
+        st = None
+    else:
+        if state is None:
+            raise ValueError(f"{who}: state is [streams, P, 2]; only a rig with fixed_length goes without one")
+        st = np.array(state, dtype=np.float64)
+        if st.shape != (S, P, SKELETON_STATE):
+            raise ValueError(f"{who}: state is [streams, P, {SKELETON_STATE}] = {(S, P, SKELETON_STATE)}, got {st.shape}")
+    par, mir = rig.parents, rig.mirror
+    rest_dir = [tuple(float(v) for v in r) for r in rig.rest_dir]
+    window, min_samples, max_dev = float(prm.window), float(prm.min_samples), prm.max_dev
+    fa, fb, fc = rig.frame_rows
+    rigid, rot, lens = np.zeros((B, P, 4)), np.zeros((B, P, 8)), np.zeros((B, P, 2))
+    ident = (1.0, 0.0, 0.0, 0.0)
+    fin = math.isfinite
+    for t in range(T):
+        for s in range(S):
+            b = t * S + s
+            x = [tuple(float(v) for v in pts[b, j]) for j in range(P)]
+            seen = [fin(x[j][0]) and fin(x[j][1]) and fin(x[j][2]) and (status is None or status[b, j] == 1 or status[b, j] == 2) for j in range(P)]
+            valid, u, ell = [False] * P, [None] * P, [0.0] * P
+            for j, p in enumerate(par):
+                if p < 0 or not (seen[j] and seen[p]):
+                    continue
+                d = (x[j][0] - x[p][0], x[j][1] - x[p][1], x[j][2] - x[p][2])
+                n = _sk_norm3(d)
+                if _sk_ok(n):
+                    valid[j], ell[j], u[j] = True, n, (d[0] / n, d[1] / n, d[2] / n)
+            if not fixed and not prm.freeze:
+                for j in range(P):
+                    if not valid[j]:
+                        continue
+                    L, n = float(st[s, j, 0]), float(st[s, j, 1])
+                    if n < min_samples or abs(ell[j] - L) <= max_dev * L:
+                        n = n + 1.0 if n + 1.0 < window else window
+                        st[s, j] = (L + _sk_div(ell[j] - L, n), n)
+            frame = skeleton_frame(x[fa], x[fb], x[fc]) if seen[fa] and seen[fb] and seen[fc] else None
+            q_root = quat_from_frames(frame, rig.rest_frame) if frame is not None else None
+            r, Q, r_ok, q_ok = [None] * P, [ident] * P, [False] * P, [False] * P
+            for j, p in enumerate(par):
+                loc = ident
+                if p < 0:
+                    r_ok[j], r[j] = seen[j], x[j]
+                    if q_root is not None:
+                        q_ok[j], Q[j] = True, q_root
+                        loc = q_root
+                else:
+                    if fixed:
+                        L, have, n = float(rig.fixed_length[j]), True, 0.0
+                    else:
+                        L, n = float(st[s, j, 0]), float(st[s, j, 1])
+                        have = n >= 1
+                        if have and mir is not None and mir[j] >= 0 and st[s, mir[j], 1] >= 1:
+                            L = 0.5 * (L + float(st[s, mir[j], 0]))
+                    lens[b, j] = (L if have else 0.0, n)
+                    if valid[j] and have and r_ok[p]:
+                        r_ok[j], r[j] = True, tuple(r[p][i] + L * u[j][i] for i in range(3))
+                    if valid[j] and q_ok[p]:
+                        v = quat_rotate(Q[p], rest_dir[j])
+                        Q[j] = quat_sign(quat_normalize(quat_mul(quat_shortest_arc(v, u[j]), Q[p])))
+                        loc = quat_sign(quat_mul(quat_conj(Q[p]), Q[j]))
+                        q_ok[j] = True
+                rigid[b, j] = ((r[j] if r_ok[j] else (0.0, 0.0, 0.0)) + (1.0 * r_ok[j] + 2.0 * q_ok[j],))
+                rot[b, j] = Q[j] + loc
+    return rigid.astype(dtype), rot.astype(dtype), lens.astype(dtype), st

@@ -525,6 +525,68 @@ int egotap_pose_track(const float* pose, const float* frame, const float* joints
 int egotap_pose_track_world(const float* pose, const float* frame, const float* joints3d, const double* rig_pose, int T, int S, int P, int J, const float* dts,
                             double dt, const egotap_track_params* params, double ortho_tol, const double* state_in, double* state_out, float* tracks,
                             float* placed_world, float* placed_cam, void* stream);
+/* ---- a rigid skeleton and bone rotations from the tracked pose (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * The trackers return joint POSITIONS, each row filtered on its own: a limb's length changes from frame to frame, and a skinned avatar is driven by a
+ * rotation per bone.  egotap_skeleton_fit runs behind them: it calibrates a length per bone over time, re-imposes it, and derives a rotation per bone
+ * against the avatar's rest pose.  Frames are egotap_pose_track's: T steps of S streams, time-major, b = t * S + s; a stream has P <= 64 rows.  All
+ * arithmetic is float64 without contraction, in exactly the order written here; every comparison is false on a NaN; each output is rounded to f32 once.
+ * THE RIG, egotap_skeleton_rig, a HOST struct of 2584 bytes, checked before any launch; the kernel takes what the entry derives from it (rest directions,
+ * the rest frame, depths: 2344 bytes) by value, under the 4 KB kernel-argument segment:
+ *   P, parent[P]      parent[j] = -1 makes j a ROOT ROW (its position passes through, it has no bone); otherwise 0 <= parent[j] < j (the walk's order)
+ *   rest_pos[P][3]    the avatar's rest pose, in any unit; rest_dir[j] = d / sqrt((d0 d0 + d1 d1) + d2 d2) with d = rest_pos[j] - rest_pos[parent[j]]
+ *   frame_rows[3]     (a, b, c), three distinct rows whose triangle orients the root rows.  The frame of three points, rows (e0, e1, e2):
+ *                     e0 = normalize(x_b - x_c); w = x_a - (x_b + x_c) / 2; e1 = normalize(w - (w . e0) e0); e2 = e0 x e1; a norm that is zero or not
+ *                     finite anywhere makes it DEGENERATE (an exactly collinear triangle; a nearly collinear one gives an ill-conditioned frame).
+ *                     M_rest is the frame of rest_pos.
+ *   mirror[P]         with has_mirror: the row on the other side of the body or -1, an involution; fixed_length[P], with has_fixed_length: the avatar's
+ *                     own bone lengths; then nothing is calibrated and the state is neither read nor written (retargeting to other proportions)
+ * egotap_skeleton_params: window >= 1, min_samples >= 0, max_dev >= 0 (relative; +inf: off), freeze 0 / 1; track_rows = K of tracks (0: P).  Nobody has
+ * tuned these on data (spec.SkeletonParams holds the defaults 120, 10, +inf, 0).
+ * state [S, P, 2] float64 on the device = (L^, n) per row; all zeros is uncalibrated, so a reset is a memset; state_out may be state_in (in place).
+ * One step of one stream:
+ *   1 seen      row j's three inputs are finite; with tracks (device f32 [B, K, 8], egotap_pose_track's records, K >= P) its status is also 1 or 2
+ *   2 sample    non-root: d = x_j - x_p, l = sqrt((d0 d0 + d1 d1) + d2 d2); VALID when both ends are seen and l is finite and > 0; u_j = d / l
+ *   3 update    valid, not frozen, and (n < min_samples or |l - L^| <= max_dev L^): n = min(n + 1, window), then L^ = L^ + (l - L^) / n -- the exact
+ *               mean of the first `window` samples, then an exponential average with alpha = 1 / window; the first sample gives L^ = l in bits; a
+ *               rejected sample is never read into the state (min_samples = 0 on an empty state accepts nothing: |l - 0| <= max_dev 0 is false)
+ *   4 length    L_j = fixed_length[j]; else, after all rows' updates of this step, L^_j where n_j >= 1 -- (L^_j + L^_m) / 2 with a mirror m that also
+ *               has n_m >= 1, so both sides get the same bits; unavailable otherwise
+ *   5 rigid     a seen root row passes through; a non-root row with a valid sample, an available L_j and a parent whose rigid position is ok gets
+ *               r_j[c] = r_p[c] + L_j u_j[c]; anything else is not ok and stores zeros, and so do all its descendants
+ *   6 rotation  unit quaternions (w, x, y, z) with w >= 0 (at w == 0 the first non-zero of x, y, z is positive).  Root rows, when a, b, c are seen and
+ *               their frame is not degenerate: Q = quat(M_cur M_rest^T) by Shepperd's rule (spec.quat_from_frames spells it out).  A non-root row
+ *               with a valid sample and a parent whose rotation is ok: v = rotate(Q_p, rest_dir_j); the swing s is the shortest arc v -> u_j (c = v . u;
+ *               c > -1 + 1e-12: s = normalize(1 + c, v x u); otherwise s = (0, normalize(v x e_k)), k the lowest index of the smallest |v_k|);
+ *               Q_j = normalize(s (x) Q_p); local_j = conj(Q_p) (x) Q_j.  Anything else is not ok, stores the identity, and so do its descendants.
+ *               TWIST about a bone cannot be observed from positions: it follows the parent.
+ * Outputs, f32, 16-byte aligned:
+ *   rigid     [B, P, 4]  (x, y, z, flags), flags = 1 (position ok) + 2 (rotation ok) as a float
+ *   rotations [B, P, 8]  (global wxyz, local wxyz); for a root row local = global
+ *   lengths   [B, P, 2]  (L_j or 0, n_j); zeros for root rows (and n = 0 with fixed_length)
+ * Global rotations and rigid positions live in the frame of the input: placed_world for an avatar in the world, placed / placed_cam for an overlay.
+ * One launch on the caller's stream: one wave per stream, four streams per workgroup, lane j owns row j, the state in registers over the T steps, the
+ * tree walked level by level with cross-lane reads; no handle, no allocation, no atomics, no workspace, plain vector stores, never synchronises;
+ * recorded as skeleton_fit while a handle's timing hook is on.  egotap_amd/spec.py skeleton_fit_ref restates it.
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL points, rig, params or output; NULL states without fixed_length; a misaligned pointer (f32
+ * inputs 4 bytes, the three outputs 16, the states 8); T, S or P <= 0; P > 64; a parent out of order or out of range; no root row; frame_rows out of
+ * range or not distinct; a zero or non-finite rest bone; a degenerate rest frame; a mirror that is no involution or pairs a root row; a fixed_length that
+ * is not finite and > 0 on a non-root row; window < 1; min_samples < 0; a max_dev that is NaN or < 0; tracks with 0 < track_rows < P; an output that
+ * overlaps an input or another output (state_out partly overlapping state_in included). */
+#define EGOTAP_SKELETON_MAX_ROWS 64
+typedef struct egotap_skeleton_rig {
+    int32_t P, has_mirror, has_fixed_length;
+    int32_t frame_rows[3];
+    int32_t parent[EGOTAP_SKELETON_MAX_ROWS];
+    int32_t mirror[EGOTAP_SKELETON_MAX_ROWS];
+    double rest_pos[EGOTAP_SKELETON_MAX_ROWS][3];
+    double fixed_length[EGOTAP_SKELETON_MAX_ROWS];
+} egotap_skeleton_rig;
+typedef struct egotap_skeleton_params {
+    double max_dev;
+    int32_t window, min_samples, freeze, track_rows;
+} egotap_skeleton_params;
+int egotap_skeleton_fit(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_params* params,
+                        const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths, void* stream);
 
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)

@@ -19,6 +19,8 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
               more launch behind the triangulation's (report only)
   tracking_world  the same with a world PoseTracker and the rig's pose per frame (a head that turns and walks; every pose counts): the launch of
               egotap_pose_track_world in the place of egotap_pose_track's (report only)
+  skeleton    the tracking arm followed by Skeleton.update on its placed and tracks (the first call's first frame taken as the rest pose): one more launch
+              behind the tracker's, egotap_skeleton_fit (report only)
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -100,12 +102,23 @@ def arms_for(m, p, left, right):
         world_tracker.update(pose, joints3d, frame, dt=1.0 / 30, rig_pose=rig_pose)
         return pose
 
+    skel_tracker, skeleton = m.new_pose_tracker(streams=1), m.new_skeleton(streams=1)
+
+    def skeleton_arm():
+        pose, joints3d, frame = m.predict_pose_from_rgb(left, right, return_triangulation=True)
+        placed, tracks = skel_tracker.update(pose, joints3d, frame, dt=1.0 / 30)
+        if skeleton.rig is None:
+            skeleton.set_rest_pose(placed[0] - placed[0, :1])      # (synchronises once, outside the timed rounds: the warm-up makes this call)
+        skeleton.update(placed, tracks)
+        return pose
+
     return {"parent": parent,
             "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
             "limbs": lambda: m.predict_pose_from_rgb(left, right, return_limbs=True)[0],
             "triangulation": lambda: m.predict_pose_from_rgb(left, right, return_triangulation=True)[0],
             "tracking": tracking,
             "tracking_world": tracking_world,
+            "skeleton": skeleton_arm,
             "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
@@ -234,7 +247,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "skeleton") else ""
                 print(f"{setting:12s} B={B:<4d} {k:14s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
