@@ -2426,11 +2426,13 @@ extern "C" int egotap_pose_track_world(const float* pose, const float* frame, co
 }
 
 // ---- a rigid skeleton and bone rotations from the tracked pose (skeleton_fit.h): one operator behind the trackers, no handle
-extern "C" int egotap_skeleton_fit(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_params* params,
-                                   const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths, void* stream) {
-    static const char* const who = "egotap_skeleton_fit";
+// (both entries: with_twist says which, and twist is read only then)
+static int skeleton_fit_entry(const char* who, bool with_twist, const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig,
+                              const egotap_skeleton_twist* twist, const egotap_skeleton_params* params, const double* state_in, double* state_out, float* rigid,
+                              float* rotations, float* lengths, void* stream) {
     EGO_CHECK(points && rig && params && rigid && rotations && lengths,
               "%s: null argument (points, rig, params, rigid, rotations and lengths are required; tracks may be NULL)", who);
+    EGO_CHECK(!with_twist || twist, "%s: null argument (twist is required: egotap_skeleton_fit is the entry without one)", who);
     const bool fixed = rig->has_fixed_length != 0;
     EGO_CHECK(fixed || (state_in && state_out), "%s: null argument (state_in and state_out are required unless the rig has fixed_length)", who);
     if (fixed) state_in = nullptr, state_out = nullptr;      // neither read nor written
@@ -2492,6 +2494,31 @@ extern "C" int egotap_skeleton_fit(const float* points, const float* tracks, int
             EGO_CHECK(skel_pos_finite(rig->fixed_length[j]), "%s: rig: fixed_length[%d] = %g must be finite and > 0", who, j, rig->fixed_length[j]);
             dev.fixed_length[j] = rig->fixed_length[j];
         }
+    // the twist table, and what the kernel takes of it
+    SkelTwistDev tw = {};
+    if (with_twist) {
+        EGO_CHECK(twist->bend_lo >= 0.0 && twist->bend_lo < twist->bend_hi && twist->bend_hi <= 1.0,
+                  "%s: twist: 0 <= bend_lo < bend_hi <= 1, sines of the bend angle (bend_lo = %g, bend_hi = %g)", who, twist->bend_lo, twist->bend_hi);
+        tw.bend_lo = twist->bend_lo, tw.bend_hi = twist->bend_hi;
+        for (int j = 0; j < kSkelMaxRows; ++j) tw.pole[j] = -1;
+        for (int j = 0; j < P; ++j) {
+            const int c = twist->pole[j];
+            if (c == -1) continue;
+            EGO_CHECK(c >= 0 && c < P, "%s: twist: pole[%d] = %d is -1 or a row 0 .. %d", who, j, c, P - 1);
+            EGO_CHECK(dev.parent[j] >= 0, "%s: twist: pole[%d] = %d is set on a root row, which has no bone to roll", who, j, c);
+            EGO_CHECK(dev.parent[c] == j, "%s: twist: pole[%d] = %d: the pole of a row is one of its children (parent[%d] = %d)", who, j, c, c, dev.parent[c]);
+            const double* h = twist->hinge[j];
+            EGO_CHECK(ego_finite(h[0]) && ego_finite(h[1]) && ego_finite(h[2]), "%s: twist: hinge[%d] is not finite", who, j);
+            const double* e = dev.rest_dir[j];
+            const double dot = (h[0] * e[0] + h[1] * e[1]) + h[2] * e[2];
+            const SkelVec g = {{h[0] - dot * e[0], h[1] - dot * e[1], h[2] - dot * e[2]}};
+            const double n = skel_norm3(g);
+            EGO_CHECK(n >= 1e-6 && skel_pos_finite(n), "%s: twist: hinge[%d] is (nearly) parallel to the rest bone of row %d: its part at right angles has norm %g < 1e-6",
+                      who, j, j, n);
+            tw.pole[j] = (int8_t)c;
+            for (int k = 0; k < 3; ++k) tw.g[j][k] = g.v[k] / n;
+        }
+    }
     const egotap_skeleton_params& q = *params;
     EGO_CHECK(q.window >= 1, "%s: params: window must be at least 1 (%d)", who, q.window);
     EGO_CHECK(q.min_samples >= 0, "%s: params: min_samples must not be negative (%d)", who, q.min_samples);
@@ -2513,9 +2540,21 @@ extern "C" int egotap_skeleton_fit(const float* points, const float* tracks, int
         }
         for (int p = o + 1; p < 4; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
     }
-    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "skeleton_fit", "skeleton_fit_kernel", 0.0);
-    EGO_HIP(skeleton_fit_launch(points, tracks, T, S, dev, prm, state_in, state_out, rigid, rotations, lengths, (hipStream_t)stream));
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, with_twist ? "skeleton_fit_twist" : "skeleton_fit", "skeleton_fit_kernel", 0.0);
+    if (with_twist)
+        EGO_HIP(skeleton_fit_launch(points, tracks, T, S, dev, tw, prm, state_in, state_out, rigid, rotations, lengths, (hipStream_t)stream));
+    else
+        EGO_HIP(skeleton_fit_launch(points, tracks, T, S, dev, SkelNoTwist{}, prm, state_in, state_out, rigid, rotations, lengths, (hipStream_t)stream));
     return EGOTAP_OK;
+}
+extern "C" int egotap_skeleton_fit(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_params* params,
+                                   const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths, void* stream) {
+    return skeleton_fit_entry("egotap_skeleton_fit", false, points, tracks, T, S, rig, nullptr, params, state_in, state_out, rigid, rotations, lengths, stream);
+}
+extern "C" int egotap_skeleton_fit_twist(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_twist* twist,
+                                         const egotap_skeleton_params* params, const double* state_in, double* state_out, float* rigid, float* rotations,
+                                         float* lengths, void* stream) {
+    return skeleton_fit_entry("egotap_skeleton_fit_twist", true, points, tracks, T, S, rig, twist, params, state_in, state_out, rigid, rotations, lengths, stream);
 }
 
 extern "C" int egotap_debug_predict_pose_rgb_form(egotap_handle h, int* form) {

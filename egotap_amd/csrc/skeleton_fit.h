@@ -7,6 +7,10 @@
 //       its parent's rigid position r (3 doubles), rotation Q (4 doubles) and the two ok flags from the parent's lane.  The root rows' rotation comes
 //       from the three frame rows, which every lane reads for itself (three cross-lane reads with a uniform source), so all lanes hold the same bits.
 //       Step t + 1's inputs are requested before step t's arithmetic.  A wave whose stream lies past S loads and stores nothing.
+//   skeleton_fit_kernel<true>  the same walk with the TWIST of egotap_skeleton_fit_twist (spec.py skeleton_fit_twist_ref): next to the bone sample lane j
+//       takes its pole child's input position from the child's lane (one more per-lane-constant source; three fp32 reads and the seen flag), repeats the
+//       child's own sample arithmetic on it (the same operations, hence the child's bits), and has the bend normal n and the weight w before the walk;
+//       at its level it rolls Q_s about its bone so that the rotated hinge g meets n.  <false> is egotap_skeleton_fit's kernel, operation for operation.
 // Cross-lane reads, not LDS: __shfl on a double is two ds_bpermute_b32, which go through the LDS crossbar but allocate no LDS and need no barrier or
 // fence -- the exchange is inside one wave, all 64 lanes take part in every one (no lane leaves the loop early, rows past P are idle root rows), and
 // the parent's lane is a per-lane constant.  The LDS form (7 doubles + flags per row, ~4 KB a workgroup) would need a fence between a level's
@@ -19,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "egotap.h"
 
 constexpr int kSkelMaxRows = EGOTAP_SKELETON_MAX_ROWS;      // P: one lane each
@@ -37,6 +42,18 @@ struct SkelParamsDev {
     double window, min_samples, max_dev;
     int32_t freeze, track_rows;
 };
+
+// what the entry derives from an egotap_skeleton_twist and the twist instantiation takes by value: 1616 bytes; with the rest of the block (two
+// pointers, T and S, the rig, the parameters, five pointers: 2440 bytes) 4056 of the 4 KB kernel-argument segment
+struct SkelTwistDev {
+    double g[kSkelMaxRows][3];             // the rest hinge made orthogonal to rest_dir and normalised; zeros where the row has no pole
+    double bend_lo, bend_hi;
+    int8_t pole[kSkelMaxRows];             // the row whose bone bends against this row's, or -1
+};
+struct SkelNoTwist {};                     // egotap_skeleton_fit's instantiation takes nothing more
+static_assert(sizeof(SkelTwistDev) == 1616 && sizeof(egotap_skeleton_twist) == 1808, "egotap.h states both sizes");
+static_assert(2 * sizeof(void*) + 2 * sizeof(int) + sizeof(SkelRigDev) + sizeof(SkelParamsDev) + 5 * sizeof(void*) + sizeof(SkelTwistDev) <= 4096,
+              "the twist instantiation's argument block fits the 4 KB kernel-argument segment");
 
 struct SkelQuat {
     double w, x, y, z;
@@ -128,15 +145,43 @@ static __device__ __forceinline__ SkelQuat skel_shortest_arc(const SkelVec& v, c
     const double n = skel_norm3(x);
     return SkelQuat{0.0, x.v[0] / n, x.v[1] / n, x.v[2] / n};
 }
+// the twist (egotap.h egotap_skeleton_fit_twist): Q = Q_s rolled about the bone u so that the rotated hinge g, made orthogonal to u, moves the share w of
+// the way to the bend normal n; false, and Q as it was, where a norm is zero or not finite
+static __device__ __forceinline__ bool skel_twist(SkelQuat& Q, const SkelVec& g, const SkelVec& u, const SkelVec& n, double w) {
+#pragma clang fp contract(off)
+    const SkelVec h = skel_rotate(Q, g);
+    const double p = (h.v[0] * u.v[0] + h.v[1] * u.v[1]) + h.v[2] * u.v[2];
+    const SkelVec hr = {{h.v[0] - p * u.v[0], h.v[1] - p * u.v[1], h.v[2] - p * u.v[2]}};
+    const double nh = skel_norm3(hr);
+    const SkelVec hp = {{hr.v[0] / nh, hr.v[1] / nh, hr.v[2] / nh}};
+    const double w1 = 1.0 - w;
+    const SkelVec br = {{w1 * hp.v[0] + w * n.v[0], w1 * hp.v[1] + w * n.v[1], w1 * hp.v[2] + w * n.v[2]}};
+    const double nb = skel_norm3(br);
+    if (!(skel_pos_finite(nh) && skel_pos_finite(nb))) return false;
+    const SkelVec b = {{br.v[0] / nb, br.v[1] / nb, br.v[2] / nb}};
+    const double k = (hp.v[0] * b.v[0] + hp.v[1] * b.v[1]) + hp.v[2] * b.v[2];
+    SkelQuat tw = {0.0, u.v[0], u.v[1], u.v[2]};             // h' = -b: the half turn about the bone
+    if (k > -1.0 + 1e-12) {
+        const SkelVec x = skel_cross(hp, b);
+        tw = skel_normalize(SkelQuat{1.0 + k, x.v[0], x.v[1], x.v[2]});
+    }
+    Q = skel_normalize(skel_mul(tw, Q));
+    return true;
+}
 static __device__ __forceinline__ bool skel_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for NaN and +-inf
 
 // gfx950, -O3: 92 VGPRs (the row's sample, r, Q, local, the parent's r and Q in flight, the next step's inputs), 0 AGPRs, 106 SGPRs (the rest frame, the
 // parameters and the frame rows are uniform; 14 of them parked in VGPR lanes), scratch 0 bytes, LDS 0 bytes, 5 waves per SIMD (a workgroup puts one on each).
+// <false> is the kernel above (the same 1673 instructions as before it became a template; the empty SkelNoTwist makes its argument block 2444 bytes for
+// 2440).  <true>, gfx950, -O3: 117 VGPRs (the hinge, the bend normal and its weight, the child's position in flight), 0 AGPRs, 106 SGPRs (27 of them
+// parked in VGPR lanes), scratch 0 bytes, LDS 0 bytes, 4 waves per SIMD; 4056 bytes of arguments.
 // state_in and state_out may be the same array (each lane reads its row before the loop and writes it after it): not __restrict__.
+template <bool TWIST>
 static __global__ __launch_bounds__(64 * kSkelStreamsPerBlock) void skeleton_fit_kernel(const float* __restrict__ points, const float* __restrict__ tracks, int T,
                                                                                         int S, SkelRigDev rig, SkelParamsDev prm, const double* state_in,
                                                                                         double* state_out, float* __restrict__ rigid,
-                                                                                        float* __restrict__ rotations, float* __restrict__ lengths) {
+                                                                                        float* __restrict__ rotations, float* __restrict__ lengths,
+                                                                                        std::conditional_t<TWIST, SkelTwistDev, SkelNoTwist> tw) {
 #pragma clang fp contract(off)
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     typedef float f32x2v __attribute__((ext_vector_type(2)));
@@ -154,6 +199,18 @@ static __global__ __launch_bounds__(64 * kSkelStreamsPerBlock) void skeleton_fit
 #pragma unroll
         for (int c = 0; c < 3; ++c) rest.v[c] = rig.rest_dir[lane][c];
         if (fixed) L_fixed = rig.fixed_length[lane];
+    }
+    int src_c = lane;                                        // (twist) the pole child's lane, and the hinge of the lane's own bone
+    bool poled = false;
+    SkelVec hinge = {{0.0, 0.0, 0.0}};
+    if constexpr (TWIST) {
+        const int pol = row ? tw.pole[lane] : -1;
+        poled = pol >= 0;
+        if (poled) {
+            src_c = pol;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) hinge.v[c] = tw.g[lane][c];
+        }
     }
     const bool stateful = row && !fixed;                     // a root row's (L^, n) passes through: state_out is a whole state
     if (stateful) {
@@ -185,6 +242,27 @@ static __global__ __launch_bounds__(64 * kSkelStreamsPerBlock) void skeleton_fit
         const double ell = skel_norm3(d);
         const bool valid = bone && seen && pseen && skel_pos_finite(ell);
         const SkelVec u = {{d.v[0] / ell, d.v[1] / ell, d.v[2] / ell}};      // read only where valid
+        // (twist) the pole child's sample from its input position, as the child's own lane takes it; the bend normal and its weight
+        double bend_w = 0.0;
+        SkelVec bend_n = {{0.0, 0.0, 0.0}};
+        if constexpr (TWIST) {
+            const float cx0 = __shfl(x0, src_c), cx1 = __shfl(x1, src_c), cx2 = __shfl(x2, src_c);
+            const bool cseen = __shfl((int)seen, src_c) != 0;
+            const SkelVec dc = {{(double)cx0 - (double)x0, (double)cx1 - (double)x1, (double)cx2 - (double)x2}};
+            const double ellc = skel_norm3(dc);
+            const SkelVec uc = {{dc.v[0] / ellc, dc.v[1] / ellc, dc.v[2] / ellc}};
+            const SkelVec m = skel_cross(u, uc);
+            const double sigma = skel_norm3(m);
+            if (valid && poled && seen && cseen && skel_pos_finite(ellc) && sigma > tw.bend_lo && skel_pos_finite(sigma)) {
+                if (sigma >= tw.bend_hi) {
+                    bend_w = 1.0;
+                } else {
+                    const double ramp = (sigma - tw.bend_lo) / (tw.bend_hi - tw.bend_lo);
+                    bend_w = (ramp * ramp) * (3.0 - 2.0 * ramp);
+                }
+                bend_n = SkelVec{{m.v[0] / sigma, m.v[1] / sigma, m.v[2] / sigma}};
+            }
+        }
         // 3 the length
         if (valid && calibrate && !prm.freeze && (n_hat < prm.min_samples || fabs(ell - L_hat) <= prm.max_dev * L_hat)) {
             n_hat = n_hat + 1.0 < prm.window ? n_hat + 1.0 : prm.window;
@@ -209,7 +287,7 @@ static __global__ __launch_bounds__(64 * kSkelStreamsPerBlock) void skeleton_fit
         const bool frame_ok = skel_frame(fx[0], fx[1], fx[2], cur) && fseen;
         SkelQuat Q = {1.0, 0.0, 0.0, 0.0}, loc = {1.0, 0.0, 0.0, 0.0};
         SkelVec r = {{0.0, 0.0, 0.0}};
-        bool r_ok = false, q_ok = false;
+        bool r_ok = false, q_ok = false, t_ok = false;
         if (!bone) {
             r_ok = seen;
             r = SkelVec{{(double)x0, (double)x1, (double)x2}};
@@ -238,14 +316,17 @@ static __global__ __launch_bounds__(64 * kSkelStreamsPerBlock) void skeleton_fit
                 }
                 if (valid && (pflags & 2)) {
                     const SkelVec v = skel_rotate(pq, rest);
-                    Q = skel_sign(skel_normalize(skel_mul(skel_shortest_arc(v, u), pq)));
+                    SkelQuat Qs = skel_normalize(skel_mul(skel_shortest_arc(v, u), pq));
+                    if constexpr (TWIST)
+                        if (bend_w > 0.0) t_ok = skel_twist(Qs, hinge, u, bend_n, bend_w);
+                    Q = skel_sign(Qs);
                     loc = skel_sign(skel_mul(SkelQuat{pq.w, -pq.x, -pq.y, -pq.z}, Q));
                     q_ok = true;
                 }
             }
         }
         if (row) {
-            const f32x4v rec = {r_ok ? (float)r.v[0] : 0.f, r_ok ? (float)r.v[1] : 0.f, r_ok ? (float)r.v[2] : 0.f, (float)((int)r_ok + 2 * (int)q_ok)};
+            const f32x4v rec = {r_ok ? (float)r.v[0] : 0.f, r_ok ? (float)r.v[1] : 0.f, r_ok ? (float)r.v[2] : 0.f, (float)((int)r_ok + 2 * (int)q_ok + 4 * (int)t_ok)};
             const f32x4v glob = {(float)Q.w, (float)Q.x, (float)Q.y, (float)Q.z}, locl = {(float)loc.w, (float)loc.x, (float)loc.y, (float)loc.z};
             const f32x2v len = {bone && have ? (float)L : 0.f, bone ? (float)n_hat : 0.f};
             *(f32x4v*)(rigid + (b * P + lane) * 4) = rec;
@@ -260,13 +341,16 @@ static __global__ __launch_bounds__(64 * kSkelStreamsPerBlock) void skeleton_fit
     }
 }
 
-// T, S > 0, the rig, the pointers and the parameters checked by the caller.
-static inline hipError_t skeleton_fit_launch(const float* points, const float* tracks, int T, int S, const SkelRigDev& rig, const SkelParamsDev& prm,
+// T, S > 0, the rig, the table, the pointers and the parameters checked by the caller.  tw a SkelTwistDev: the twist instantiation; a SkelNoTwist:
+// egotap_skeleton_fit's.
+template <class Twist>
+static inline hipError_t skeleton_fit_launch(const float* points, const float* tracks, int T, int S, const SkelRigDev& rig, const Twist& tw, const SkelParamsDev& prm,
                                              const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths, hipStream_t s) {
     if (T <= 0 || S <= 0 || rig.P <= 0 || rig.P > kSkelMaxRows || !points || !rigid || !rotations || !lengths || (!rig.has_fixed && (!state_in || !state_out)))
         return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)(((long)S + kSkelStreamsPerBlock - 1) / kSkelStreamsPerBlock);
-    hipLaunchKernelGGL(skeleton_fit_kernel, dim3(blocks), dim3(64 * kSkelStreamsPerBlock), 0, s, points, tracks, T, S, rig, prm, state_in, state_out, rigid, rotations,
-                       lengths);
+    constexpr bool with_twist = std::is_same<Twist, SkelTwistDev>::value;
+    hipLaunchKernelGGL(skeleton_fit_kernel<with_twist>, dim3(blocks), dim3(64 * kSkelStreamsPerBlock), 0, s, points, tracks, T, S, rig, prm, state_in, state_out,
+                       rigid, rotations, lengths, tw);
     return hipGetLastError();
 }

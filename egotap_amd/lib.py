@@ -40,6 +40,10 @@ class EgotapSkeletonParams(C.Structure):              # egotap.h egotap_skeleton
     _fields_ = [("max_dev", C.c_double), ("window", C.c_int32), ("min_samples", C.c_int32), ("freeze", C.c_int32), ("track_rows", C.c_int32)]
 
 
+class EgotapSkeletonTwist(C.Structure):               # egotap.h egotap_skeleton_twist: 1808 bytes
+    _fields_ = [("pole", C.c_int32 * 64), ("hinge", (C.c_double * 3) * 64), ("bend_lo", C.c_double), ("bend_hi", C.c_double)]
+
+
 class EgotapYuvSource(C.Structure):                   # egotap.h egotap_yuv_source: seven int32 (then padding) and two int64
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "format", "matrix", "range", "H", "W", "pitch")] + [("uv_offset", C.c_int64), ("frame_stride", C.c_int64)]
 
@@ -134,6 +138,9 @@ _PROTOS = {
     # (points, tracks, T, S, rig, params, state_in, state_out, rigid, rotations, lengths, stream)
     "egotap_skeleton_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapSkeletonRig), C.POINTER(EgotapSkeletonParams), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (points, tracks, T, S, rig, twist, params, state_in, state_out, rigid, rotations, lengths, stream)
+    "egotap_skeleton_fit_twist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapSkeletonRig), C.POINTER(EgotapSkeletonTwist),
+                                            C.POINTER(EgotapSkeletonParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egotap_debug_predict_pose_rgb_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egotap_debug_predict_pose_rgb_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "egotap_lift_intermediate": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
@@ -914,6 +921,26 @@ def skeleton_fit_into(rig_c, prm_c, points, tracks, T, S, state_in, state_out, r
                                      _ptr(rotations), _ptr(lengths), _stream(dev)))
 
 
+def skeleton_twist_struct(twist) -> EgotapSkeletonTwist:
+    """a ``spec.SkeletonTwist`` as the ABI takes it (egotap_skeleton_twist, by pointer to host memory)"""
+    from . import spec
+    if not isinstance(twist, spec.SkeletonTwist):
+        raise ValueError(f"skeleton_fit_twist: twist is a spec.SkeletonTwist (spec.skeleton_twist builds one), got {type(twist).__name__}")
+    o = EgotapSkeletonTwist()
+    o.bend_lo, o.bend_hi = twist.bend_lo, twist.bend_hi
+    for j in range(64):
+        o.pole[j] = twist.pole[j] if j < twist.P else -1
+        if j < twist.P:
+            o.hinge[j][:] = [float(v) for v in twist.hinge[j]]
+    return o
+
+
+def skeleton_fit_twist_into(rig_c, twist_c, prm_c, points, tracks, T, S, state_in, state_out, rigid, rotations, lengths, dev):
+    """the launch itself on ``dev``'s current stream, as ``skeleton_fit_into`` with ``twist_c`` from ``skeleton_twist_struct``"""
+    check(load().egotap_skeleton_fit_twist(_ptr(points), _ptr(tracks), int(T), int(S), C.byref(rig_c), C.byref(twist_c), C.byref(prm_c), _ptr(state_in),
+                                           _ptr(state_out), _ptr(rigid), _ptr(rotations), _ptr(lengths), _stream(dev)))
+
+
 def skeleton_fit(points, state, rig, params=None, tracks=None, streams=1, _structs=None):
     """A rigid skeleton and a rotation per bone from tracked joint positions (egotap_skeleton_fit, ``spec.skeleton_fit_ref``): points float32
     [T * streams, P, 3] on the GPU, T consecutive frames of ``streams`` camera rigs, time-major -- a tracker's ``placed``, ``placed_world`` or
@@ -922,8 +949,23 @@ def skeleton_fit(points, state, rig, params=None, tracks=None, streams=1, _struc
     (None: its defaults); ``tracks`` float32 [T * streams, K, 8] the tracker's records (a row then also needs status 1 or 2 to count as seen)
     -> (rigid float32 [T * streams, P, 4] = (x, y, z, flags), rotations float32 [T * streams, P, 8] = (global wxyz, local wxyz), lengths float32
     [T * streams, P, 2] = (the length used, n)).  One launch on the current stream, no synchronisation."""
+    return _skeleton_fit("skeleton_fit", points, state, rig, None, params, tracks, streams, _structs)
+
+
+def skeleton_fit_twist(points, state, rig, twist, params=None, tracks=None, streams=1, _structs=None):
+    """``skeleton_fit`` with the bone twist taken from the bend plane of the child bone (egotap_skeleton_fit_twist, ``spec.skeleton_fit_twist_ref``):
+    ``twist`` a ``spec.SkeletonTwist`` of the same rig (``spec.skeleton_twist`` builds one); every other argument and the three results as
+    ``skeleton_fit``'s, with flags = 1 (position ok) + 2 (rotation ok) + 4 (twist observed).  rigid[..., :3], lengths and the state are
+    ``skeleton_fit``'s in bits.  One launch on the current stream, no synchronisation."""
+    twist_c = _structs[2] if _structs is not None else skeleton_twist_struct(twist)
+    if twist.P != getattr(rig, "P", twist.P):              # (a rig of another type is refused below, by name)
+        raise ValueError(f"skeleton_fit_twist: the twist table has P = {twist.P} rows, the rig {rig.P}")
+    return _skeleton_fit("skeleton_fit_twist", points, state, rig, twist_c, params, tracks, streams, None if _structs is None else _structs[:2])
+
+
+def _skeleton_fit(who, points, state, rig, twist_c, params, tracks, streams, _structs):
+    """the argument checks, the outputs and the launch of ``skeleton_fit`` (``twist_c`` None) and ``skeleton_fit_twist``"""
     import torch
-    who = "skeleton_fit"
     rig_c, prm_c = _structs if _structs is not None else (skeleton_rig_struct(rig), skeleton_params_struct(params))
     S, P = int(streams), rig.P
     if not torch.is_tensor(points) or points.dim() != 3 or points.shape[2] != 3 or S < 1 or points.shape[0] < S or points.shape[0] % S:
@@ -954,7 +996,11 @@ def skeleton_fit(points, state, rig, params=None, tracks=None, streams=1, _struc
     rotations = torch.empty((B, P, 8), dtype=torch.float32, device=points.device)
     lengths = torch.empty((B, P, 2), dtype=torch.float32, device=points.device)
     with torch.cuda.device(points.device):
-        skeleton_fit_into(rig_c, prm_c, points.detach(), tracks.detach() if tracks is not None else None, T, S, state, state, rigid, rotations, lengths, points.device)
+        trk = tracks.detach() if tracks is not None else None
+        if twist_c is None:
+            skeleton_fit_into(rig_c, prm_c, points.detach(), trk, T, S, state, state, rigid, rotations, lengths, points.device)
+        else:
+            skeleton_fit_twist_into(rig_c, twist_c, prm_c, points.detach(), trk, T, S, state, state, rigid, rotations, lengths, points.device)
     return rigid, rotations, lengths
 
 

@@ -118,9 +118,11 @@ class Skeleton:
     """A rigid skeleton and a rotation per bone behind a tracker (``lib.skeleton_fit``, egotap_skeleton_fit, ``spec.skeleton_fit_ref``): per stream the
     bone lengths are calibrated over time ((L^, n) per row, float64 [streams, P, 2] on the device, zeros = uncalibrated), re-imposed on the tracked
     positions, and each bone gets a global and a parent-relative rotation against the rig's rest pose.  Made by ``model.new_skeleton``; holds no
-    reference to the model and takes no part in its graphs.  A rig with ``fixed_length`` retargets to the avatar's own proportions and keeps no state."""
+    reference to the model and takes no part in its graphs.  A rig with ``fixed_length`` retargets to the avatar's own proportions and keeps no state.
+    With ``twist`` (a ``spec.SkeletonTwist`` of the rig, or ``set_hinges``) the bones that have a pole also roll about their own axis, from the bend
+    plane of the child bone (``lib.skeleton_fit_twist``, egotap_skeleton_fit_twist); without one nothing differs from what is described above."""
 
-    def __init__(self, P, joint_preset=None, rig=None, streams=1, params=None):
+    def __init__(self, P, joint_preset=None, rig=None, streams=1, params=None, twist=None):
         self.P, self.joint_preset, self.streams = int(P), joint_preset, int(streams)
         if self.streams < 1:
             raise ValueError(f"Skeleton: streams must be at least 1, got {streams}")
@@ -129,22 +131,44 @@ class Skeleton:
         self.rig = None
         self._state = None
         self._structs = None
+        self.twist = None
+        if twist is not None and rig is None:
+            raise ValueError("Skeleton: a twist table belongs to a rig: give both, or call set_rest_pose and then set_hinges")
         if rig is not None:
-            self._set_rig(rig)
+            self._set_rig(rig, twist)
 
-    def _set_rig(self, rig):
+    def _set_rig(self, rig, twist=None):
         rig_c = _lib.skeleton_rig_struct(rig)
         if rig.P != self.P:
             raise ValueError(f"Skeleton: the rig has P = {rig.P} rows, the model's pose has {self.P}")
-        self.rig, self._structs = rig, (rig_c, _lib.skeleton_params_struct(self.params))
+        structs = (rig_c, _lib.skeleton_params_struct(self.params))
+        if twist is not None:
+            structs += (_lib.skeleton_twist_struct(twist),)
+            if twist.P != rig.P:
+                raise ValueError(f"Skeleton: the twist table has P = {twist.P} rows, the rig {rig.P}")
+            _spec._sk_pole_rows("Skeleton", rig, twist.pole)       # (a table made for another rig of the same size)
+        self.rig, self.twist, self._structs = rig, twist, structs
 
     def set_rest_pose(self, pose_rows, mirror=True):
         """one frame [P, 3] (a tensor or an array) taken as the rest pose, the "stand in a T-pose" calibration (``spec.skeleton_rig_from_pose`` with the
         model's joint preset); the calibrated lengths stay"""
         if self.joint_preset is None:
             raise ValueError("Skeleton.set_rest_pose: this skeleton was made without a joint preset; give new_skeleton a rig")
-        self._set_rig(_spec.skeleton_rig_from_pose(self.joint_preset, pose_rows, mirror=mirror))
+        self._set_rig(_spec.skeleton_rig_from_pose(self.joint_preset, pose_rows, mirror=mirror))      # (a new rest pose: the hinges of the old one go)
         return self.rig
+
+    def set_hinges(self, pose_rows, pole=None, bend_lo=_spec.SKELETON_BEND_LO, bend_hi=_spec.SKELETON_BEND_HI):
+        """one frame [P, 3] with bent elbows and knees, the "now bend your elbows and knees" calibration (``spec.skeleton_hinges_from_pose``, then
+        ``spec.skeleton_twist``); ``pole`` None: the joint preset's ``spec.SKELETON_POLE``.  From then on ``update`` also observes the twist."""
+        if self.rig is None:
+            raise ValueError("Skeleton.set_hinges: no rig: give model.new_skeleton a rig or call set_rest_pose(pose_rows) first")
+        if pole is None:
+            if self.joint_preset is None:
+                raise ValueError("Skeleton.set_hinges: this skeleton was made without a joint preset; name the pole rows")
+            pole = _spec.SKELETON_POLE[self.joint_preset]
+        hinge = _spec.skeleton_hinges_from_pose(self.rig, pole, pose_rows, bend_hi=bend_hi)
+        self._set_rig(self.rig, _spec.skeleton_twist(self.rig, pole, hinge, bend_lo=bend_lo, bend_hi=bend_hi))
+        return self.twist
 
     @property
     def state(self):
@@ -169,6 +193,9 @@ class Skeleton:
                              "set_rest_pose(pose_rows) with one frame to take as the rest pose")
         if not torch.is_tensor(points) or not points.is_cuda:
             raise _lib.EgotapError("Skeleton.update runs on the GPU only (no CPU fallback); points is a cuda tensor")
+        if self.twist is not None:
+            return _lib.skeleton_fit_twist(points, self._state_on(points.device), self.rig, self.twist, params=self.params, tracks=tracks, streams=self.streams,
+                                           _structs=self._structs)
         return _lib.skeleton_fit(points, self._state_on(points.device), self.rig, params=self.params, tracks=tracks, streams=self.streams, _structs=self._structs)
 
     def freeze(self, on=True):
@@ -942,13 +969,15 @@ class EgoTAPAutoEncoderModel(nn.Module):
         p = self.net_AutoEncoder.preset
         return PoseTracker(p.out_joints, p.n_joints_hm, streams=streams, params=params, world=world, ortho_tol=ortho_tol)
 
-    def new_skeleton(self, rig=None, streams=1, params=None):
+    def new_skeleton(self, rig=None, streams=1, params=None, twist=None):
         """A ``Skeleton`` for this model's pose rows: rigid bones and a rotation per bone from what a tracker returns,
         ``placed, tracks = tracker.update(...)``; ``rigid, rotations, lengths = skeleton.update(placed, tracks)`` -- one more launch on the same stream.
         ``rig`` a ``spec.skeleton_rig(...)`` of the avatar (its rest pose, and its own bone lengths to retarget); None: the skeleton refuses to update
         until ``set_rest_pose(pose_rows)`` has taken one frame as the rest pose -- the project ships no avatar.  ``params`` a ``spec.SkeletonParams``
-        (None: its defaults, which nobody has tuned on real data).  The serving entries, the trackers, their graphs and their outputs do not change."""
-        return Skeleton(self.net_AutoEncoder.preset.out_joints, joint_preset=self.opt.joint_preset, rig=rig, streams=streams, params=params)
+        (None: its defaults, which nobody has tuned on real data).  ``twist`` a ``spec.skeleton_twist(rig, ...)`` of that rig: bones with a pole then
+        also roll about their own axis (None: they follow their parent, until ``set_hinges(pose_rows)`` has taken a frame with bent elbows and knees).
+        The serving entries, the trackers, their graphs and their outputs do not change."""
+        return Skeleton(self.net_AutoEncoder.preset.out_joints, joint_preset=self.opt.joint_preset, rig=rig, streams=streams, params=params, twist=twist)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

@@ -1556,8 +1556,12 @@ def skeleton_fit_ref(points, state, rig, params=None, tracks=None, streams=1, dt
 
     rigid = (x, y, z, 1 (position ok) + 2 (rotation ok)); rotations = (global wxyz, local wxyz); lengths = (L_j or 0, n_j), zeros for root rows.
     Each output is rounded once from float64 (``dtype="float64"``: not at all)."""
+    return _skeleton_fit_walk("skeleton_fit_ref", points, state, rig, params, tracks, streams, dtype, None)
+
+
+def _skeleton_fit_walk(who, points, state, rig, params, tracks, streams, dtype, twist):
+    """the one body of skeleton_fit_ref (``twist`` None) and skeleton_fit_twist_ref (a checked SkeletonTwist of the same rig)"""
     import numpy as np
-    who = "skeleton_fit_ref"
     if not isinstance(rig, SkeletonRig):
         raise ValueError(f"{who}: rig is a spec.SkeletonRig (spec.skeleton_rig builds one), got {type(rig).__name__}")
     prm = SkeletonParams() if params is None else params
@@ -1586,6 +1590,7 @@ def skeleton_fit_ref(points, state, rig, params=None, tracks=None, streams=1, dt
     rest_dir = [tuple(float(v) for v in r) for r in rig.rest_dir]
     window, min_samples, max_dev = float(prm.window), float(prm.min_samples), prm.max_dev
     fa, fb, fc = rig.frame_rows
+    hinge_g = None if twist is None else [tuple(float(v) for v in row) for row in twist.g]
     rigid, rot, lens = np.zeros((B, P, 4)), np.zeros((B, P, 8)), np.zeros((B, P, 2))
     ident = (1.0, 0.0, 0.0, 0.0)
     fin = math.isfinite
@@ -1614,7 +1619,7 @@ def skeleton_fit_ref(points, state, rig, params=None, tracks=None, streams=1, dt
             q_root = quat_from_frames(frame, rig.rest_frame) if frame is not None else None
             r, Q, r_ok, q_ok = [None] * P, [ident] * P, [False] * P, [False] * P
             for j, p in enumerate(par):
-                loc = ident
+                loc, t_ok = ident, False
                 if p < 0:
                     r_ok[j], r[j] = seen[j], x[j]
                     if q_root is not None:
@@ -1633,9 +1638,206 @@ def skeleton_fit_ref(points, state, rig, params=None, tracks=None, streams=1, dt
                         r_ok[j], r[j] = True, tuple(r[p][i] + L * u[j][i] for i in range(3))
                     if valid[j] and q_ok[p]:
                         v = quat_rotate(Q[p], rest_dir[j])
-                        Q[j] = quat_sign(quat_normalize(quat_mul(quat_shortest_arc(v, u[j]), Q[p])))
+                        q_s = quat_normalize(quat_mul(quat_shortest_arc(v, u[j]), Q[p]))
+                        if twist is not None and twist.pole[j] >= 0 and valid[twist.pole[j]]:
+                            rolled = quat_twist(q_s, hinge_g[j], u[j], u[twist.pole[j]], twist.bend_lo, twist.bend_hi)
+                            if rolled is not None:
+                                q_s, t_ok = rolled, True
+                        Q[j] = quat_sign(q_s)
                         loc = quat_sign(quat_mul(quat_conj(Q[p]), Q[j]))
                         q_ok[j] = True
-                rigid[b, j] = ((r[j] if r_ok[j] else (0.0, 0.0, 0.0)) + (1.0 * r_ok[j] + 2.0 * q_ok[j],))
+                rigid[b, j] = ((r[j] if r_ok[j] else (0.0, 0.0, 0.0)) + (1.0 * r_ok[j] + 2.0 * q_ok[j] + 4.0 * t_ok,))
                 rot[b, j] = Q[j] + loc
     return rigid.astype(dtype), rot.astype(dtype), lens.astype(dtype), st
+
+
+# ---- bone twist from the bend plane of the child bone (egotap.h: egotap_skeleton_fit_twist) ----------------------------------------------
+SKELETON_BEND_LO = 0.17364817766693033         # sin 10 deg: at or below this sine of the bend angle the twist is not observed
+SKELETON_BEND_HI = 0.42261826174069944         # sin 25 deg: from here on the bend normal is fully taken.  Nobody has tuned either on data: there is no dataset here.
+SKELETON_HINGE_MIN = 1e-6                      # a hinge's part at right angles to its rest bone is at least this long
+# row j -> the row c whose bone bends against j's (rows are skeleton_parents' rows): upper arm -> forearm, thigh -> shank, shank -> foot.  The EgoCap
+# wrists are left out: a hand flexes both ways, so the normal's sign is not stable there.
+SKELETON_POLE = {"UnrealEgo": {4: 6, 5: 7, 10: 12, 11: 13, 12: 14, 13: 15},
+                 "EgoCap": {2: 3, 6: 7, 10: 11, 14: 15, 11: 12, 15: 16}}
+
+
+def _sk_dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def quat_twist(q_s, g, u, u_c, bend_lo, bend_hi):
+    """egotap.h's twist step: ``q_s`` the swung rotation of a bone (unit, no sign), ``g`` its unit rest hinge at right angles to its rest direction,
+    ``u`` the bone's direction, ``u_c`` its pole child's -> normalize(tw (x) q_s), not given a sign, or None where the twist is not observed:
+        m = u x u_c, sigma = |m|; w = 0 unless sigma > bend_lo, 1 if sigma >= bend_hi, else t = (sigma - bend_lo) / (bend_hi - bend_lo), w = (t t)(3 - 2 t)
+        w > 0: n = m / sigma; h = rotate(q_s, g), h' = normalize(h - (h . u) u); b = normalize((1 - w) h' + w n); a zero or non-finite norm: None
+        k = h' . b; k > -1 + 1e-12: tw = normalize(1 + k, h' x b); otherwise tw = (0, u), the half turn about the bone"""
+    m = _sk_cross(u, u_c)
+    sigma = _sk_norm3(m)
+    if not (sigma > bend_lo and _sk_ok(sigma)):
+        return None
+    if sigma >= bend_hi:
+        w = 1.0
+    else:
+        t = (sigma - bend_lo) / (bend_hi - bend_lo)
+        w = (t * t) * (3.0 - 2.0 * t)
+    if not w > 0.0:
+        return None
+    n = (m[0] / sigma, m[1] / sigma, m[2] / sigma)
+    h = quat_rotate(q_s, g)
+    p = _sk_dot(h, u)
+    hr = (h[0] - p * u[0], h[1] - p * u[1], h[2] - p * u[2])
+    nh = _sk_norm3(hr)
+    if not _sk_ok(nh):
+        return None
+    hp = (hr[0] / nh, hr[1] / nh, hr[2] / nh)
+    w1 = 1.0 - w
+    br = (w1 * hp[0] + w * n[0], w1 * hp[1] + w * n[1], w1 * hp[2] + w * n[2])
+    nb = _sk_norm3(br)
+    if not _sk_ok(nb):
+        return None
+    b = (br[0] / nb, br[1] / nb, br[2] / nb)
+    k = _sk_dot(hp, b)
+    if k > SKELETON_ANTIPARALLEL:
+        x = _sk_cross(hp, b)
+        tw = quat_normalize((1.0 + k, x[0], x[1], x[2]))
+    else:
+        tw = (0.0, u[0], u[1], u[2])
+    return quat_normalize(quat_mul(tw, q_s))
+
+
+@dataclass(frozen=True, eq=False)
+class SkeletonTwist:
+    """egotap.h egotap_skeleton_twist, checked against its rig, with what the entry derives from it: ``pole`` [P] (-1: none), ``hinge`` [P, 3] (zeros
+    where the row has no pole), ``g`` [P, 3] = the hinge made orthogonal to rest_dir and normalised, the two thresholds.  Built by ``skeleton_twist``."""
+    P: int
+    pole: tuple
+    hinge: object
+    g: object
+    bend_lo: float
+    bend_hi: float
+
+
+def _sk_pole_rows(who, rig, pole):
+    """``pole`` as a tuple [P]: given as a mapping {row: child} or as one entry per row (-1: none); refuses what egotap_skeleton_fit_twist refuses"""
+    if not isinstance(rig, SkeletonRig):
+        raise ValueError(f"{who}: rig is a spec.SkeletonRig (spec.skeleton_rig builds one), got {type(rig).__name__}")
+    P = rig.P
+    if hasattr(pole, "items"):
+        rows = [-1] * P
+        for j, c in pole.items():
+            if not 0 <= int(j) < P:
+                raise ValueError(f"{who}: pole names row {j}: rows are 0 .. {P - 1}")
+            rows[int(j)] = int(c)
+    else:
+        rows = [int(c) for c in pole]
+        if len(rows) != P:
+            raise ValueError(f"{who}: pole holds one row per row, [{P}], or is a mapping row -> child; got {len(rows)} entries")
+    for j, c in enumerate(rows):
+        if c == -1:
+            continue
+        if not 0 <= c < P:
+            raise ValueError(f"{who}: pole[{j}] = {c} is -1 or a row 0 .. {P - 1}")
+        if rig.parents[j] < 0:
+            raise ValueError(f"{who}: pole[{j}] = {c} is set on a root row, which has no bone to roll")
+        if rig.parents[c] != j:
+            raise ValueError(f"{who}: pole[{j}] = {c}: the pole of a row is one of its children (parent[{c}] = {rig.parents[c]})")
+    return tuple(rows)
+
+
+def _sk_thresholds(who, bend_lo, bend_hi):
+    lo, hi = float(bend_lo), float(bend_hi)
+    if not (0.0 <= lo < hi <= 1.0):
+        raise ValueError(f"{who}: 0 <= bend_lo < bend_hi <= 1, sines of the bend angle, got bend_lo = {bend_lo}, bend_hi = {bend_hi}")
+    return lo, hi
+
+
+def skeleton_twist(rig, pole, hinge=None, bend_lo=SKELETON_BEND_LO, bend_hi=SKELETON_BEND_HI):
+    """The twist table of egotap_skeleton_fit_twist for ``rig``: ``pole`` a mapping {row j: the row c whose bone bends against j's} (``SKELETON_POLE``
+    holds the presets') or one entry per row, -1 for none; ``hinge`` [P, 3] the hinge axis of every pole row IN THE REST POSE, the direction
+    rest_dir_j x rest_dir_c would have if the joint were bent the way it anatomically bends (rows without a pole are not read), None: the rest pose's
+    own rest_dir_j x rest_dir_c, which needs a rest pose bent by at least ``bend_hi`` at every pole joint; ``bend_lo`` / ``bend_hi`` sines of the bend
+    angle (at or below the first the twist is not observed, from the second on it is fully taken; the defaults, sin 10 deg and sin 25 deg, have not
+    been tuned on data) -> a ``SkeletonTwist``.  Refuses, by name, what the entry refuses."""
+    import numpy as np
+    who = "skeleton_twist"
+    rows = _sk_pole_rows(who, rig, pole)
+    lo, hi = _sk_thresholds(who, bend_lo, bend_hi)
+    P = rig.P
+    rest_dir = [tuple(float(v) for v in r) for r in rig.rest_dir]
+    hg = np.zeros((P, 3))
+    if hinge is not None:
+        given = np.array(hinge, dtype=np.float64)
+        if given.shape != (P, 3):
+            raise ValueError(f"{who}: hinge is [P, 3] = {(P, 3)}, got {given.shape}")
+    g = np.zeros((P, 3))
+    for j, c in enumerate(rows):
+        if c < 0:
+            continue
+        if hinge is None:
+            h = _sk_cross(rest_dir[j], rest_dir[c])
+            n = _sk_norm3(h)
+            if not n >= hi:
+                raise ValueError(f"{who}: the rest pose is straight at row {j}: |rest_dir[{j}] x rest_dir[{c}]| = {n} is below bend_hi = {hi}, so it has no "
+                                 "hinge of its own (a T-pose has straight arms); take the hinges from a frame with bent elbows and knees "
+                                 "(skeleton_hinges_from_pose) or give an explicit axis")
+        else:
+            h = tuple(float(v) for v in given[j])
+            if not all(math.isfinite(v) for v in h):
+                raise ValueError(f"{who}: hinge[{j}] is not finite")
+        d = _sk_dot(h, rest_dir[j])
+        gr = (h[0] - d * rest_dir[j][0], h[1] - d * rest_dir[j][1], h[2] - d * rest_dir[j][2])
+        n = _sk_norm3(gr)
+        if not (n >= SKELETON_HINGE_MIN and _sk_ok(n)):
+            raise ValueError(f"{who}: hinge[{j}] is (nearly) parallel to the rest bone of row {j}: its part at right angles has norm {n} < {SKELETON_HINGE_MIN}")
+        hg[j], g[j] = h, (gr[0] / n, gr[1] / n, gr[2] / n)
+    for a in (hg, g):
+        a.setflags(write=False)
+    return SkeletonTwist(P, rows, hg, g, lo, hi)
+
+
+def skeleton_hinges_from_pose(rig, pole, pose_rows, bend_hi=SKELETON_BEND_HI):
+    """The "now bend your elbows and knees" calibration: one frame ``pose_rows`` [P, 3] in which every pole joint is bent the way it anatomically
+    bends, by at least ``bend_hi`` (a sine) -> hinge [P, 3] for ``skeleton_twist``: the float64 swing walk of skeleton_fit_ref on that frame gives
+    Q_s per row, the frame's bend normal is n_j = normalize(u_j x u_c), and hinge_j = rotate(conj(Q_s_j), n_j) -- the normal carried back into the rest
+    pose; zeros for rows without a pole.  Refuses by name a frame in which a pole row or its child is missing or a joint is too straight."""
+    import numpy as np
+    who = "skeleton_hinges_from_pose"
+    rows = _sk_pole_rows(who, rig, pole)
+    hi = _sk_thresholds(who, 0.0, bend_hi)[1]
+    ps = np.array(pose_rows.detach().cpu().numpy() if hasattr(pose_rows, "detach") else pose_rows, dtype=np.float64)
+    if ps.shape != (rig.P, 3):
+        raise ValueError(f"{who}: pose_rows is one frame [P, 3] = {(rig.P, 3)}, got {ps.shape}")
+    state = None if rig.fixed_length is not None else np.zeros((1, rig.P, SKELETON_STATE))
+    rigid, rot, _, _ = _skeleton_fit_walk(who, ps[None], state, rig, None, None, 1, "float64", None)
+    hinge = np.zeros((rig.P, 3))
+    for j, c in enumerate(rows):
+        if c < 0:
+            continue
+        if rigid[0, j, 3] < 2 or rigid[0, c, 3] < 2:
+            raise ValueError(f"{who}: row {j} or its pole child {c} has no rotation in this frame (a missing row, a zero-length bone or a degenerate triangle)")
+        x = [tuple(float(v) for v in ps[k]) for k in (rig.parents[j], j, c)]
+        dj, dc = tuple(x[1][i] - x[0][i] for i in range(3)), tuple(x[2][i] - x[1][i] for i in range(3))
+        nj, nc = _sk_norm3(dj), _sk_norm3(dc)
+        m = _sk_cross(tuple(v / nj for v in dj), tuple(v / nc for v in dc))
+        sigma = _sk_norm3(m)
+        if not sigma >= hi:
+            raise ValueError(f"{who}: the frame is straight at row {j}: the sine of the bend between the bones of rows {j} and {c} is {sigma}, below bend_hi = {hi}; "
+                             "bend the elbows and knees")
+        hinge[j] = quat_rotate(quat_conj(tuple(float(v) for v in rot[0, j, :4])), tuple(v / sigma for v in m))
+    return hinge
+
+
+def skeleton_fit_twist_ref(points, state, rig, twist, params=None, tracks=None, streams=1, dtype="float32"):
+    """The records and the state egotap_skeleton_fit_twist writes, restated in float64, operation for operation: skeleton_fit_ref's arguments and
+    results with ``twist`` a ``SkeletonTwist`` of the same rig (``skeleton_twist`` builds one).  Every step is skeleton_fit_ref's but a non-root row's
+    rotation: with q_s = normalize(s (x) Q_p) its swung rotation, a row j whose pole child c has a valid sample gets
+    Q_j = sign(quat_twist(q_s, g_j, u_j, u_c, bend_lo, bend_hi)) and flags + 4 where that observes a twist, Q_j = sign(q_s) otherwise; descendants read
+    the twisted Q_j.  rigid[..., :3], lengths and the state equal skeleton_fit_ref's in bits."""
+    who = "skeleton_fit_twist_ref"
+    if not isinstance(twist, SkeletonTwist):
+        raise ValueError(f"{who}: twist is a spec.SkeletonTwist (spec.skeleton_twist builds one), got {type(twist).__name__}")
+    if isinstance(rig, SkeletonRig):
+        if twist.P != rig.P:
+            raise ValueError(f"{who}: the twist table has P = {twist.P} rows, the rig {rig.P}")
+        _sk_pole_rows(who, rig, twist.pole)
+    return _skeleton_fit_walk(who, points, state, rig, params, tracks, streams, dtype, twist)

@@ -558,7 +558,8 @@ int egotap_pose_track_world(const float* pose, const float* frame, const float* 
  *               with a valid sample and a parent whose rotation is ok: v = rotate(Q_p, rest_dir_j); the swing s is the shortest arc v -> u_j (c = v . u;
  *               c > -1 + 1e-12: s = normalize(1 + c, v x u); otherwise s = (0, normalize(v x e_k)), k the lowest index of the smallest |v_k|);
  *               Q_j = normalize(s (x) Q_p); local_j = conj(Q_p) (x) Q_j.  Anything else is not ok, stores the identity, and so do its descendants.
- *               TWIST about a bone cannot be observed from positions: it follows the parent.
+ *               TWIST about a bone cannot be observed from positions: it follows the parent.  (egotap_skeleton_fit_twist, below, observes it for
+ *               the bones that have a POLE: from the plane of a bent two-bone chain.)
  * Outputs, f32, 16-byte aligned:
  *   rigid     [B, P, 4]  (x, y, z, flags), flags = 1 (position ok) + 2 (rotation ok) as a float
  *   rotations [B, P, 8]  (global wxyz, local wxyz); for a root row local = global
@@ -587,6 +588,48 @@ typedef struct egotap_skeleton_params {
 } egotap_skeleton_params;
 int egotap_skeleton_fit(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_params* params,
                         const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths, void* stream);
+/* ---- bone twist from the bend plane of the child bone (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * egotap_skeleton_fit leaves the roll of a bone about its own axis to the parent, so an upper arm, a thigh or a shank never rolls and the child's swing
+ * absorbs whatever roll the pose has: the local quaternion of an elbow that simply flexes is then no rotation about the elbow's hinge.  A bent two-bone
+ * chain defines a plane, and the plane's normal fixes the roll of the upper bone.  egotap_skeleton_fit_twist is egotap_skeleton_fit with that one step
+ * added; steps 1 - 5 and step 6 for root rows are egotap_skeleton_fit's, and rigid[..., 0:3], lengths and the state equal its outputs in bits.
+ * THE TWIST TABLE, egotap_skeleton_twist, a HOST struct of 1808 bytes, checked before any launch; the kernel takes what the entry derives from it (pole as
+ * int8, g, the two thresholds: 1616 bytes) by value beside the rig's 2344, 4056 bytes of arguments in all under the 4 KB kernel-argument segment:
+ *   pole[P]           for row j the row c whose bone bends against j's bone, or -1: parent[c] == j, and j is no root row
+ *   hinge[P][3]       row j's hinge axis IN THE REST POSE: where rest_dir_j x rest_dir_c would point if the joint were bent the way it anatomically bends;
+ *                     only roughly at right angles to rest_dir_j: the entry takes g_j = normalize(hinge_j - (hinge_j . rest_dir_j) rest_dir_j) in float64
+ *                     (the dot product added left to right) and refuses a hinge that is not finite or whose g_j has a norm below 1e-6 before normalising;
+ *                     read only where pole[j] >= 0
+ *   bend_lo, bend_hi  0 <= bend_lo < bend_hi <= 1, SINES of the bend angle: below bend_lo the twist is not observed, from bend_hi on it is fully taken.
+ *                     spec.skeleton_twist defaults to sin 10 deg and sin 25 deg; nobody has tuned these on data.
+ * Step 6 for a non-root row j with a valid sample and a parent whose rotation is ok: s the swing as above, Q_s = normalize(s (x) Q_p) (egotap_skeleton_fit's
+ * Q_j before its sign).  When pole[j] = c >= 0 and c's sample is valid, float64 without contraction in this order, every comparison false on a NaN:
+ *   m = u_j x u_c, sigma = sqrt((m0 m0 + m1 m1) + m2 m2)
+ *   w = 0 unless sigma > bend_lo; w = 1 if sigma >= bend_hi; otherwise t = (sigma - bend_lo) / (bend_hi - bend_lo), w = (t t)(3 - 2 t)
+ *   if w > 0: n = m / sigma; h = rotate(Q_s, g_j), h' = normalize(h - (h . u_j) u_j); b = normalize((1 - w) h' + w n); a norm that is zero or not finite
+ *             (sigma's included) makes the twist NOT OBSERVED
+ *   the twist tw is the arc h' -> b: k = h' . b; k > -1 + 1e-12: tw = normalize(1 + k, h' x b); otherwise the half turn ABOUT THE BONE, (0, u_j)
+ *   Q_j = sign(normalize(tw (x) Q_s)) and the row's flags gain 4 (twist observed, w > 0)
+ * Not observed: Q_j = sign(Q_s), as egotap_skeleton_fit has it, and the flags gain nothing.  Then local_j = sign(conj(Q_p) (x) Q_j) as there.  Descendants
+ * read the twisted Q_j as their parent and their swings absorb it: rotate(Q_j, rest_dir_j) = u_j holds for every row as before.  Only square roots,
+ * divisions, products and sums: no atan2, sin or cos.  The twist is taken frame by frame: over a straight limb (sigma <= bend_lo) it falls back to the
+ * parent's, nothing is held.
+ * Outputs as egotap_skeleton_fit's, with flags = 1 (position ok) + 2 (rotation ok) + 4 (twist observed).  One launch of the same shape, the second
+ * instantiation of the same kernel: lane j takes its pole child's input position from the child's lane next to the bone sample; no handle, no allocation,
+ * no atomics, no workspace, plain vector stores, never synchronises; recorded as skeleton_fit_twist while a handle's timing hook is on.
+ * egotap_amd/spec.py skeleton_fit_twist_ref restates it; spec.skeleton_twist builds the table, spec.skeleton_hinges_from_pose takes the hinges from one
+ * frame with bent elbows and knees.
+ * EGOTAP_ERR_INVALID, by name and before any launch: everything egotap_skeleton_fit refuses; a NULL twist; a pole[j] that is not -1 and out of range, whose
+ * parent is not j, or that is set on a root row; a hinge of a pole row that is not finite or (nearly) parallel to its rest bone; thresholds outside
+ * 0 <= bend_lo < bend_hi <= 1 (a NaN included). */
+typedef struct egotap_skeleton_twist {
+    int32_t pole[EGOTAP_SKELETON_MAX_ROWS];
+    double hinge[EGOTAP_SKELETON_MAX_ROWS][3];
+    double bend_lo, bend_hi;
+} egotap_skeleton_twist;
+int egotap_skeleton_fit_twist(const float* points, const float* tracks, int T, int S, const egotap_skeleton_rig* rig, const egotap_skeleton_twist* twist,
+                              const egotap_skeleton_params* params, const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths,
+                              void* stream);
 
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)

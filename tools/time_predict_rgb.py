@@ -21,6 +21,8 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
               egotap_pose_track_world in the place of egotap_pose_track's (report only)
   skeleton    the tracking arm followed by Skeleton.update on its placed and tracks (the first call's first frame taken as the rest pose): one more launch
               behind the tracker's, egotap_skeleton_fit (report only)
+  skeleton_twist  the same with a twist table on the skeleton (the preset's pole rows, a hinge at right angles to every pole row's rest bone, the default
+              thresholds): the launch of egotap_skeleton_fit_twist in the place of egotap_skeleton_fit's (report only)
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -112,6 +114,21 @@ def arms_for(m, p, left, right):
         skeleton.update(placed, tracks)
         return pose
 
+    twist_tracker, twisted = m.new_pose_tracker(streams=1), []
+
+    def skeleton_twist_arm():
+        import numpy as np
+        pose, joints3d, frame = m.predict_pose_from_rgb(left, right, return_triangulation=True)
+        placed, tracks = twist_tracker.update(pose, joints3d, frame, dt=1.0 / 30)
+        if not twisted:                                            # (synchronises once, outside the timed rounds, as the skeleton arm does)
+            rig = spec.skeleton_rig_from_pose("UnrealEgo", placed[0] - placed[0, :1])
+            hinge = np.zeros((rig.P, 3))
+            for j in spec.SKELETON_POLE["UnrealEgo"]:              # any axis at right angles to the rest bone: the launch's time does not depend on it
+                hinge[j] = np.cross(rig.rest_dir[j], np.eye(3)[int(np.argmin(np.abs(rig.rest_dir[j])))])
+            twisted.append(m.new_skeleton(rig, streams=1, twist=spec.skeleton_twist(rig, spec.SKELETON_POLE["UnrealEgo"], hinge)))
+        twisted[0].update(placed, tracks)
+        return pose
+
     return {"parent": parent,
             "keypoints": lambda: m.predict_pose_from_rgb(left, right, return_keypoints=True)[0],
             "limbs": lambda: m.predict_pose_from_rgb(left, right, return_limbs=True)[0],
@@ -119,6 +136,7 @@ def arms_for(m, p, left, right):
             "tracking": tracking,
             "tracking_world": tracking_world,
             "skeleton": skeleton_arm,
+            "skeleton_twist": skeleton_twist_arm,
             "heatmaps_argmax": heatmaps_argmax,
             "heatmaps": lambda: m.predict_pose_from_rgb(left, right, return_heatmaps=True)[0],
             "no_heatmaps": lambda: m.predict_pose_from_rgb(left, right),
@@ -247,7 +265,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "skeleton") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "skeleton", "skeleton_twist") else ""
                 print(f"{setting:12s} B={B:<4d} {k:14s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
