@@ -64,7 +64,7 @@ def test_head_layouts_and_conv_taps_are_written_once():
         rf"%\s*{q}grid\b": ("head_layout.h", {"gemm_f32.h": 1,            # LiveRows
                                               "gemm_bf16s.h": 1}),        # SEpiScatterTokens
         rf"/\s*{q}ppd\)\s*\*\s*{q}grid\b": ("head_layout.h", {"gemm_bf16s.h": 1,          # SEpiScatterPatch
-                                                              "egotap_abi.hip": 1}),      # patch_split_kernel
+                                                              "abi_train_lift.inc": 1}),  # patch_split_kernel
         rf"eye\s*\*\s*2\s*\*\s*{q}J\b": ("head_layout.h", {"gemm_f32.h": 1,               # ALoadRot::row
                                                            "gemm_bf16s.h": 2,             # XRot::row, SEpiScatterRot
                                                            "gemm_bf16s64.h": 1}),         # X64Rot::row
