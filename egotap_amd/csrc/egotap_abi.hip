@@ -62,6 +62,7 @@
 #include "ocam.h"
 #include "pose_track.h"
 #include "skeleton_fit.h"
+#include "stereo_fuse.h"
 #endif
 #if EGOTAP_IN(1)
 #include "attention_f32.h"
@@ -2265,7 +2266,7 @@ extern "C" int egotap_limb_decode(const void* hm, int dtype, int B, int S, int64
     return EGOTAP_OK;
 }
 
-// ---- the fisheye camera model and the stereo triangulation of the keypoints (ocam.h): three operators, no handle
+// ---- the fisheye camera model, the stereo triangulation of the keypoints (ocam.h) and their fusion with the lifted joints (stereo_fuse.h): four operators, no handle
 static bool ego_finite(double v) { return std::isfinite(v); }
 // what is wrong with a camera model, or nullptr
 static const char* ocam_refusal(const egotap_ocam* m) {
@@ -2313,22 +2314,18 @@ extern "C" int egotap_ocam_unproject(const float* points2d, int N, const egotap_
     return ocam_points_entry("egotap_ocam_unproject", false, points2d, N, model, rays, stream);
 }
 
-extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
-                                         const double* affine, double min_score, const float* pose, int P, int pose_row0, float* joints3d, float* frame,
-                                         void* stream) {
-    static const char* const who = "egotap_stereo_triangulate";
-    EGO_CHECK(keypoints && t && joints3d && frame, "%s: null argument (keypoints, t, joints3d and frame are required; R, affine and pose may be NULL)", who);
+// what egotap_stereo_triangulate and egotap_stereo_fuse check alike, after their own pointers: the sizes, the two models, the pose rows, and the rig as the
+// kernels take it (R NULL: identity, affine NULL: identity) with everything in it finite
+static int stereo_rig_checks(const char* who, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t, const double* affine,
+                             double min_score, bool has_pose, int P, int pose_row0, StereoRig& rig) {
     EGO_CHECK(B > 0 && J > 0, "%s: the batch and the number of joints must be positive (B = %d, J = %d)", who, B, J);
     EGO_CHECK(J <= kStereoMaxJoints, "%s: at most %d joints, one lane each (J = %d)", who, kStereoMaxJoints, J);
-    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)joints3d | (uintptr_t)frame) & 15) == 0 && ((uintptr_t)pose & 3) == 0,
-              "%s: keypoints, joints3d and frame must be 16-byte aligned, pose 4-byte aligned", who);
     const char* why = ocam_refusal(left);
     EGO_CHECK(!why, "%s: left: %s", who, why);
     why = ocam_refusal(right);
     EGO_CHECK(!why, "%s: right: %s", who, why);
-    if (pose) EGO_CHECK(pose_row0 >= 0 && (int64_t)pose_row0 + J <= P, "%s: pose rows pose_row0 .. pose_row0 + J - 1 = %d .. %lld are not inside the P = %d rows", who,
-                        pose_row0, (long long)pose_row0 + J - 1, P);
-    StereoRig rig;
+    if (has_pose) EGO_CHECK(pose_row0 >= 0 && (int64_t)pose_row0 + J <= P, "%s: pose rows pose_row0 .. pose_row0 + J - 1 = %d .. %lld are not inside the P = %d rows", who,
+                            pose_row0, (long long)pose_row0 + J - 1, P);
     rig.cam[0] = ocam_clean(*left);
     rig.cam[1] = ocam_clean(*right);
     bool fin = ego_finite(min_score);
@@ -2337,6 +2334,18 @@ extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, c
     for (int k = 0; k < 8; ++k) fin = fin && ego_finite(rig.aff[k / 4][k % 4] = affine ? affine[k] : (k & 1 ? 0.0 : 1.0));
     rig.min_score = min_score;
     EGO_CHECK(fin, "%s: R, t, affine and min_score must be finite", who);
+    return EGOTAP_OK;
+}
+
+extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
+                                         const double* affine, double min_score, const float* pose, int P, int pose_row0, float* joints3d, float* frame,
+                                         void* stream) {
+    static const char* const who = "egotap_stereo_triangulate";
+    EGO_CHECK(keypoints && t && joints3d && frame, "%s: null argument (keypoints, t, joints3d and frame are required; R, affine and pose may be NULL)", who);
+    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)joints3d | (uintptr_t)frame) & 15) == 0 && ((uintptr_t)pose & 3) == 0,
+              "%s: keypoints, joints3d and frame must be 16-byte aligned, pose 4-byte aligned", who);
+    StereoRig rig;
+    if (int rc = stereo_rig_checks(who, B, J, left, right, R, t, affine, min_score, pose != nullptr, P, pose_row0, rig)) return rc;
     const size_t kp_bytes = (size_t)B * 2 * J * 16, pose_bytes = pose ? (size_t)B * P * 12 : 0, j3_bytes = (size_t)B * J * 32, fr_bytes = (size_t)B * 32;
     EGO_CHECK(!ego_overlap(joints3d, j3_bytes, keypoints, kp_bytes) && !ego_overlap(joints3d, j3_bytes, pose, pose_bytes) &&
                   !ego_overlap(frame, fr_bytes, keypoints, kp_bytes) && !ego_overlap(frame, fr_bytes, pose, pose_bytes) &&
@@ -2344,6 +2353,41 @@ extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, c
               "%s: joints3d and frame must not overlap keypoints, pose or each other", who);
     GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_triangulate", "stereo_triangulate_kernel", 0.0);
     EGO_HIP(stereo_triangulate_launch(keypoints, B, J, rig, pose, P, pose_row0, joints3d, frame, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+
+// the lifted joints fused with the keypoint rays (stereo_fuse.h): one operator behind the triangulation, no handle
+extern "C" int egotap_stereo_fuse(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
+                                  const double* affine, double min_score, const float* pose, int P, int pose_row0, const float* frame,
+                                  const egotap_fuse_params* params, float* fused, float* pose_fused, float* stats, void* stream) {
+    static const char* const who = "egotap_stereo_fuse";
+    EGO_CHECK(keypoints && t && pose && frame && params && fused && pose_fused && stats,
+              "%s: null argument (keypoints, t, pose, frame, params, fused, pose_fused and stats are required; R and affine may be NULL)", who);
+    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)frame | (uintptr_t)fused | (uintptr_t)stats) & 15) == 0 && (((uintptr_t)pose | (uintptr_t)pose_fused) & 3) == 0,
+              "%s: keypoints, frame, fused and stats must be 16-byte aligned, pose and pose_fused 4-byte aligned", who);
+    StereoRig rig;
+    if (int rc = stereo_rig_checks(who, B, J, left, right, R, t, affine, min_score, true, P, pose_row0, rig)) return rc;
+    const egotap_fuse_params& q = *params;
+    EGO_CHECK(ego_finite(q.sigma_ray) && q.sigma_ray > 0.0, "%s: params: sigma_ray must be finite and > 0 (%g)", who, q.sigma_ray);
+    EGO_CHECK(ego_finite(q.sigma_prior) && q.sigma_prior > 0.0, "%s: params: sigma_prior must be finite and > 0 (%g)", who, q.sigma_prior);
+    EGO_CHECK(q.max_sigma >= 0.0, "%s: params: max_sigma must be >= 0, +inf for no gate (%g)", who, q.max_sigma);      // (a NaN fails the comparison)
+    EGO_CHECK(q.min_joints >= 0, "%s: params: min_joints must not be negative (%d)", who, q.min_joints);
+    const struct {
+        const char* name;
+        const void* p;
+        size_t n;
+    } in[3] = {{"keypoints", keypoints, (size_t)B * 2 * J * 16}, {"pose", pose, (size_t)B * P * 12}, {"frame", frame, (size_t)B * 32}},
+      out[3] = {{"fused", fused, (size_t)B * J * 32}, {"pose_fused", pose_fused, (size_t)B * P * 12}, {"stats", stats, (size_t)B * 32}};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 3; ++i) {
+            if (o == 1 && i == 1 && pose_fused == pose) continue;      // in place
+            EGO_CHECK(!ego_overlap(out[o].p, out[o].n, in[i].p, in[i].n), "%s: %s overlaps %s", who, out[o].name, in[i].name);
+        }
+        for (int p = o + 1; p < 3; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
+    }
+    egotap_fuse_params prm = {q.sigma_ray, q.sigma_prior, q.max_sigma, q.min_joints};
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_fuse", "stereo_fuse_kernel", 0.0);
+    EGO_HIP(stereo_fuse_launch(keypoints, B, J, rig, pose, P, pose_row0, frame, prm, fused, pose_fused, stats, (hipStream_t)stream));
     return EGOTAP_OK;
 }
 

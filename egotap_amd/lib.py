@@ -31,6 +31,10 @@ class EgotapTrackParams(C.Structure):                 # egotap.h egotap_track_pa
         (n, C.c_double) for n in ("max_disagree", "max_gap", "max_joint_gap")] + [("min_joints", C.c_int32), ("max_hold", C.c_int32)]
 
 
+class EgotapFuseParams(C.Structure):                  # egotap.h egotap_fuse_params: three doubles and an int
+    _fields_ = [(n, C.c_double) for n in ("sigma_ray", "sigma_prior", "max_sigma")] + [("min_joints", C.c_int32)]
+
+
 class EgotapSkeletonRig(C.Structure):                 # egotap.h egotap_skeleton_rig: 2584 bytes
     _fields_ = [("P", C.c_int32), ("has_mirror", C.c_int32), ("has_fixed_length", C.c_int32), ("frame_rows", C.c_int32 * 3), ("parent", C.c_int32 * 64),
                 ("mirror", C.c_int32 * 64), ("rest_pos", (C.c_double * 3) * 64), ("fixed_length", C.c_double * 64)]
@@ -128,6 +132,10 @@ _PROTOS = {
     "egotap_ocam_unproject": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EgotapOcam), C.c_void_p, C.c_void_p]),
     "egotap_stereo_triangulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapOcam), C.POINTER(EgotapOcam), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (keypoints, B, J, left, right, R, t, affine, min_score, pose, P, pose_row0, frame, params, fused, pose_fused, stats, stream)
+    "egotap_stereo_fuse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapOcam), C.POINTER(EgotapOcam), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(EgotapFuseParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     # ---- the pose, the root and the stereo joints filtered over time: one operator, no handle
     "egotap_pose_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.POINTER(EgotapTrackParams),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -770,6 +778,67 @@ def stereo_triangulate(keypoints, left, right, t, R=None, affine=None, min_score
     with torch.cuda.device(kp.device):
         stereo_triangulate_into(args, kp, ps, pose_row0, joints3d, frame, kp.device)
     return joints3d, frame
+
+
+def fuse_params_struct(params) -> EgotapFuseParams:
+    """a ``spec.FuseParams`` as the ABI takes it (egotap_fuse_params, by pointer to host memory); there is no default: sigma_prior carries a unit"""
+    from . import spec
+    if not isinstance(params, spec.FuseParams):
+        raise ValueError(f"stereo_fuse: params is a spec.FuseParams(sigma_prior=...) -- sigma_prior has no default -- got {type(params).__name__}")
+    o = EgotapFuseParams()
+    o.sigma_ray, o.sigma_prior, o.max_sigma, o.min_joints = params.sigma_ray, params.sigma_prior, params.max_sigma, params.min_joints
+    return o
+
+
+def stereo_fuse_into(args, prm, keypoints, pose, pose_row0, frame, fused, pose_fused, stats, dev):
+    """the launch itself on ``dev``'s current stream: ``args`` from ``stereo_triangulate_args``, ``prm`` from ``fuse_params_struct``, tensors as the ABI
+    takes them (pose_fused may be pose)"""
+    cl, cr, Rp, tp, ap, ms = args
+    B, _, J, _ = keypoints.shape
+    check(load().egotap_stereo_fuse(_ptr(keypoints), B, J, C.byref(cl), C.byref(cr), Rp, tp, ap, ms, _ptr(pose), pose.shape[1], int(pose_row0), _ptr(frame),
+                                    C.byref(prm), _ptr(fused), _ptr(pose_fused), _ptr(stats), _stream(dev)))
+
+
+def _stereo_fuse_shapes(who, keypoints, pose, frame, pose_row0):
+    """the shape checks of ``stereo_fuse`` and ``StereoFusion.update`` under the face's name -> (B, J, P)"""
+    import torch
+    if not torch.is_tensor(keypoints) or keypoints.dim() != 4 or keypoints.shape[1] != 2 or keypoints.shape[3] != 4:
+        raise ValueError(f"{who}: keypoints are a tensor [B, 2, J, 4], got {tuple(getattr(keypoints, 'shape', ()))}")
+    B, _, J, _ = (int(v) for v in keypoints.shape)
+    if not 1 <= J <= 64:
+        raise ValueError(f"{who}: 1 .. 64 joints, got {J}")
+    if not torch.is_tensor(pose) or pose.dim() != 3 or pose.shape[0] != B or pose.shape[2] != 3 or pose_row0 < 0 or pose_row0 + J > pose.shape[1]:
+        raise ValueError(f"{who}: pose is a tensor [B, P, 3] with pose_row0 + J <= P, got {tuple(getattr(pose, 'shape', ()))}, pose_row0 = {pose_row0}, J = {J}")
+    if not torch.is_tensor(frame) or tuple(frame.shape) != (B, 8):
+        raise ValueError(f"{who}: frame is a tensor [B, 8] = {(B, 8)}, the triangulation's frame record, got {tuple(getattr(frame, 'shape', ()))}")
+    return B, J, int(pose.shape[1])
+
+
+def _stereo_fuse_run(who, args, prm, keypoints, pose, frame, pose_row0):
+    import torch
+    B, J, P = _stereo_fuse_shapes(who, keypoints, pose, frame, pose_row0)
+    if not _on_one_gpu(keypoints, pose, frame):
+        raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); keypoints, pose and frame on one cuda device")
+    kp, ps, fr = _f32c(keypoints), _f32c(pose), _f32c(frame)
+    pose_fused = torch.empty((B, P, 3), dtype=torch.float32, device=kp.device)
+    fused = torch.empty((B, J, 8), dtype=torch.float32, device=kp.device)
+    stats = torch.empty((B, 8), dtype=torch.float32, device=kp.device)
+    if B == 0:
+        return pose_fused, fused, stats
+    with torch.cuda.device(kp.device):
+        stereo_fuse_into(args, prm, kp, ps, pose_row0, fr, fused, pose_fused, stats, kp.device)
+    return pose_fused, fused, stats
+
+
+def stereo_fuse(keypoints, pose, frame, left, right, t, params, R=None, affine=None, min_score=0.5, pose_row0=0):
+    """The lifted joints fused with the keypoint rays of whichever eyes see them (egotap_stereo_fuse, ``spec.stereo_fuse_ref``): keypoints float32
+    [B, 2, J, 4], pose float32 [B, P, 3] and frame float32 [B, 8] on the GPU -- what a ``return_keypoints=True, return_triangulation=True`` serving call
+    returns -> (pose_fused float32 [B, P, 3], fused float32 [B, J, 8] = (x, y, z, move, res left, res right, share, mode), stats float32 [B, 8]).
+    pose_fused goes into ``pose_track`` / ``PoseTracker.update`` in place of pose.  The rig arguments are ``stereo_triangulate``'s; ``params`` a
+    ``spec.FuseParams(sigma_prior=...)``: sigma_prior is in the pose's units and has no default.  One launch."""
+    args = stereo_triangulate_args(left, right, t, R, affine, min_score)
+    prm = fuse_params_struct(params)
+    return _stereo_fuse_run("stereo_fuse", args, prm, keypoints, pose, frame, pose_row0)
 
 
 def track_params_struct(params=None) -> EgotapTrackParams:

@@ -114,6 +114,25 @@ class PoseTracker:
             self._state[idx] = 0.0
 
 
+class StereoFusion:
+    """The lifted joints fused with the keypoint rays, in front of a tracker (``lib.stereo_fuse``, egotap_stereo_fuse, ``spec.stereo_fuse_ref``): per joint
+    the pose row placed by t_hat is a prior, every eye that sees the joint pulls it onto its ray, one eye is enough.  Made by
+    ``model.new_stereo_fusion`` from the rig of ``set_stereo_rig`` as it was at that moment; holds no reference to the model and takes no part in its
+    graphs.  It keeps no state between frames."""
+
+    def __init__(self, left, right, t, params, R=None, affine=None, min_score=_spec.STEREO_MIN_SCORE, pose_row0=0):
+        self.params, self.pose_row0 = params, int(pose_row0)
+        self._prm = _lib.fuse_params_struct(params)        # (the field checks, now rather than at the first update)
+        self._args = _lib.stereo_triangulate_args(left, right, t, R, affine, min_score)
+
+    @torch.no_grad()
+    def update(self, pose, keypoints, frame):
+        """``pose`` [B, P, 3], ``keypoints`` [B, 2, J, 4] and ``frame`` [B, 8]: what a ``return_keypoints=True, return_triangulation=True`` serving call
+        returns -> (pose_fused [B, P, 3], fused [B, J, 8], stats [B, 8]).  ONE launch on the current stream, no synchronisation: it queues behind the
+        serving call that made its inputs; ``tracker.update(pose_fused, joints3d, frame, ...)`` follows it."""
+        return _lib._stereo_fuse_run("StereoFusion.update", self._args, self._prm, keypoints, pose, frame, self.pose_row0)
+
+
 class Skeleton:
     """A rigid skeleton and a rotation per bone behind a tracker (``lib.skeleton_fit``, egotap_skeleton_fit, ``spec.skeleton_fit_ref``): per stream the
     bone lengths are calibrated over time ((L^, n) per row, float64 [streams, P, 2] on the device, zeros = uncalibrated), re-imposed on the tracked
@@ -968,6 +987,31 @@ class EgoTAPAutoEncoderModel(nn.Module):
         ``ortho_tol`` (None: 1e-6; a world tracker's alone) bounds how far a rig pose's matrix may be from a rotation and still count."""
         p = self.net_AutoEncoder.preset
         return PoseTracker(p.out_joints, p.n_joints_hm, streams=streams, params=params, world=world, ortho_tol=ortho_tol)
+
+    def new_stereo_fusion(self, sigma_prior, params=None, affine=None):
+        """A ``StereoFusion`` for this model's outputs and the rig of ``set_stereo_rig``:
+        ``pose, kp, joints3d, frame = model.predict_pose_from_camera(l8, r8, return_keypoints=True, return_triangulation=True)``;
+        ``pose_fused, fused, stats = fusion.update(pose, kp, frame)``; ``placed, tracks = tracker.update(pose_fused, joints3d, frame, dt=1 / 30)``.
+        ``sigma_prior``: the standard deviation of a lifted joint in the pose's units -- required, the project knows no dataset's; ``params`` a
+        ``spec.FuseParams`` for the other fields (None: its defaults, which nobody has tuned on real data; its sigma_prior must then agree).
+        ``affine``: None for the RGB / byte entries' keypoints (``spec.stereo_pixel_affine``), ``"identity"`` for the sensor and lens entries', or an
+        explicit [2, 4].  The serving entries, the trackers, their graphs and their outputs do not change."""
+        rig = self.__dict__.get("_stereo_rig")
+        if rig is None:
+            raise _lib.EgotapError("new_stereo_fusion: no stereo rig is set; call set_stereo_rig(left, right, t) first")
+        left, right, t, R, min_score = rig
+        if params is None:
+            params = _spec.FuseParams(sigma_prior=sigma_prior)
+        elif not isinstance(params, _spec.FuseParams) or params.sigma_prior != float(sigma_prior):
+            raise ValueError(f"new_stereo_fusion: params is a spec.FuseParams whose sigma_prior is the one given ({sigma_prior}), got {params!r}")
+        p = self.net_AutoEncoder.preset
+        if affine is None:
+            affine = (_spec.stereo_pixel_affine(left, p.hm_size), _spec.stereo_pixel_affine(right, p.hm_size))
+        elif isinstance(affine, str):
+            if affine != "identity":
+                raise ValueError(f'new_stereo_fusion: affine is None, "identity" or a [2, 4] of (ax, bx, ay, by) per eye, got {affine!r}')
+            affine = _spec.STEREO_IDENTITY_AFFINE
+        return StereoFusion(left, right, t, params, R=R, affine=affine, min_score=min_score, pose_row0=_spec.stereo_pose_row0(p))
 
     def new_skeleton(self, rig=None, streams=1, params=None, twist=None):
         """A ``Skeleton`` for this model's pose rows: rigid bones and a rotation per bone from what a tracker returns,

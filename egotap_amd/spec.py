@@ -841,6 +841,159 @@ def stereo_triangulate_ref(keypoints, left: OcamModel, right: OcamModel, t, R=No
     return rec.astype(dtype), frame.astype(dtype)
 
 
+# ---- the lifted joints fused with the keypoint rays (egotap.h: egotap_stereo_fuse) ----------------------------------------------------------
+FUSE_PRIOR, FUSE_USED, FUSE_GATED, FUSE_NOT_IN_FRONT, FUSE_FALLBACK = 1, (2, 4), (8, 16), (32, 64), 128      # the mode bits; pairs: (left, right)
+
+
+@dataclass(frozen=True)
+class FuseParams:
+    """egotap.h egotap_fuse_params.  ``sigma_prior``: the standard deviation of a lifted joint, in the pose's units -- it carries a unit, the project
+    knows no dataset's, so it has no default.  ``sigma_ray``: the angular standard deviation of a keypoint's ray in radians; 0.02 is about a third of a
+    heatmap pixel on a 64-pixel map across a 180 degree lens.  ``max_sigma``: the gate in standard deviations, before and after the fit (+inf: none).
+    ``min_joints``: fewest triangulated joints behind a t_hat that places a prior, as the tracker's.  Nobody has tuned any of these on real data."""
+    sigma_prior: float
+    sigma_ray: float = 0.02
+    max_sigma: float = 3.0
+    min_joints: int = 3
+
+    def __post_init__(self):
+        for name in ("sigma_prior", "sigma_ray"):
+            v = float(getattr(self, name))
+            if not (math.isfinite(v) and v > 0):
+                raise ValueError(f"FuseParams: {name} must be finite and > 0, got {v}")
+            object.__setattr__(self, name, v)
+        v = float(self.max_sigma)
+        if not v >= 0:
+            raise ValueError(f"FuseParams: max_sigma must be >= 0 (+inf: no gate), got {v}")
+        object.__setattr__(self, "max_sigma", v)
+        n = int(self.min_joints)
+        if n < 0:
+            raise ValueError(f"FuseParams: min_joints must not be negative, got {n}")
+        object.__setattr__(self, "min_joints", n)
+
+
+def stereo_fuse_ref(keypoints, pose, frame, left: OcamModel, right: OcamModel, t, params: FuseParams, R=None, affine=None, min_score=STEREO_MIN_SCORE,
+                    pose_row0=0, dtype="float32"):
+    """The records egotap_stereo_fuse writes, restated in float64 numpy operation for operation (egotap.h holds the definition and its order):
+    keypoints [B, 2, J, 4], pose [B, P, 3], frame [B, 8] (the triangulation's; t_hat and n are read) -> (pose_fused [B, P, 3], fused [B, J, 8] =
+    (x, y, z, move, res left, res right, share, mode), stats [B, 8] = (priors, kept fits of both eyes, kept fits of one eye, eyes rejected, rms move,
+    max move, rms res, max res)).  The rig arguments are ``stereo_triangulate_ref``'s.  pose_fused is float32 whatever ``dtype``: its untouched rows are
+    the input's bits.  ``dtype="float64"``: fused and stats before their one rounding."""
+    import numpy as np
+    kp = np.asarray(keypoints, dtype=np.float64)
+    if kp.ndim != 4 or kp.shape[1] != 2 or kp.shape[3] != 4:
+        raise ValueError(f"stereo_fuse_ref: keypoints are [B, 2, J, 4], got {kp.shape}")
+    B, _, J, _ = kp.shape
+    if not 1 <= J <= STEREO_MAX_JOINTS:
+        raise ValueError(f"stereo_fuse_ref: 1 .. {STEREO_MAX_JOINTS} joints, got {J}")
+    if not isinstance(params, FuseParams):
+        raise ValueError("stereo_fuse_ref: params is a spec.FuseParams (sigma_prior has no default)")
+    p32 = np.ascontiguousarray(np.asarray(pose), dtype=np.float32)
+    if p32.ndim != 3 or p32.shape[0] != B or p32.shape[2] != 3 or pose_row0 < 0 or pose_row0 + J > p32.shape[1]:
+        raise ValueError(f"stereo_fuse_ref: pose is [B, P, 3] with pose_row0 + J <= P, got {p32.shape}, pose_row0 = {pose_row0}, J = {J}")
+    fr = np.asarray(frame, dtype=np.float32).astype(np.float64)
+    if fr.shape != (B, 8):
+        raise ValueError(f"stereo_fuse_ref: frame is [B, 8] = {(B, 8)}, got {fr.shape}")
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64).reshape(3, 3)
+    af = np.asarray(STEREO_IDENTITY_AFFINE if affine is None else affine, dtype=np.float64).reshape(2, 4)
+    s_ray, s_pri, max_sigma = params.sigma_ray, params.sigma_prior, params.max_sigma
+
+    def dot(p, q):
+        return p[..., 0] * q[..., 0] + p[..., 1] * q[..., 1] + p[..., 2] * q[..., 2]
+
+    with np.errstate(all="ignore"):
+        that = fr[:, None, :3]
+        root_ok = (fr[:, 3] >= params.min_joints) & np.isfinite(fr[:, :3]).all(axis=-1)
+        q = p32[:, pose_row0:pose_row0 + J].astype(np.float64)
+        prior = root_ok[:, None] & np.isfinite(q).all(axis=-1)
+        x0 = q + that
+        wp = 1.0 / (s_pri * s_pri)
+        pix = [np.stack([af[e, 0] * kp[:, e, :, 0] + af[e, 1], af[e, 2] * kp[:, e, :, 1] + af[e, 3]], axis=-1) for e in range(2)]
+        dL, r = ocam_cam2world_ref(pix[0], left), ocam_cam2world_ref(pix[1], right)
+        dR = np.stack([R[k, 0] * r[..., 0] + R[k, 1] * r[..., 1] + R[k, 2] * r[..., 2] for k in range(3)], axis=-1)
+        mode = np.where(prior, FUSE_PRIOR, 0)
+        eyes = []
+        for e, (d, o) in enumerate(((dL, np.zeros(3)), (dR, t))):
+            score = kp[:, e, :, 2]
+            seen = prior & (score >= min_score) & np.isfinite(kp[:, e, :, :2]).all(axis=-1)
+            y0 = x0 - o
+            a, rho = dot(d, y0), np.sqrt(dot(y0, y0))
+            rr = y0 - a[..., None] * d
+            sr = s_ray * rho
+            sr2 = sr * sr
+            g = np.sqrt(dot(rr, rr)) / np.sqrt(sr2 + s_pri * s_pri)
+            front = (a > 0) & np.isfinite(g)
+            used = seen & front & (g <= max_sigma)
+            mode = mode + np.where(seen & ~front, FUSE_NOT_IN_FRONT[e], 0) + np.where(seen & front & ~(g <= max_sigma), FUSE_GATED[e], 0) + np.where(used, FUSE_USED[e], 0)
+            eyes.append((used, d, o, score / sr2, sr))
+        # the system: the upper triangle (A00, A01, A02, A11, A12, A22), left before right; the left origin is 0 and adds nothing to b
+        zero = np.zeros((B, J))
+        A = [zero + wp, zero, zero, zero + wp, zero, zero + wp]
+        b = [wp * x0[..., k] for k in range(3)]
+        sw = zero
+        for e, (used, d, o, w, sr) in enumerate(eyes):
+            m00, m01, m02 = 1.0 - d[..., 0] * d[..., 0], -(d[..., 0] * d[..., 1]), -(d[..., 0] * d[..., 2])
+            m11, m12, m22 = 1.0 - d[..., 1] * d[..., 1], -(d[..., 1] * d[..., 2]), 1.0 - d[..., 2] * d[..., 2]
+            A = [np.where(used, Ak + w * m, Ak) for Ak, m in zip(A, (m00, m01, m02, m11, m12, m22))]
+            if e == 1:
+                c = [(m00 * o[0] + m01 * o[1]) + m02 * o[2], (m01 * o[0] + m11 * o[1]) + m12 * o[2], (m02 * o[0] + m12 * o[1]) + m22 * o[2]]
+                b = [np.where(used, bk + w * ck, bk) for bk, ck in zip(b, c)]
+            sw = np.where(used, sw + w, sw)
+        l10, l20 = A[1] / A[0], A[2] / A[0]
+        D1, c21 = A[3] - l10 * A[1], A[4] - l20 * A[1]
+        l21 = c21 / D1
+        D2 = (A[5] - l20 * A[2]) - l21 * c21
+        z1 = b[1] - l10 * b[0]
+        z2 = (b[2] - l20 * b[0]) - l21 * z1
+        y0, y1, y2 = b[0] / A[0], z1 / D1, z2 / D2
+        x2 = y2
+        x1 = y1 - l21 * x2
+        xs = np.stack([(y0 - l10 * x1) - l20 * x2, x1, x2], axis=-1)
+        tried = eyes[0][0] | eyes[1][0]
+        keep = tried & np.isfinite(xs).all(axis=-1)
+        res = []
+        for used, d, o, w, sr in eyes:
+            v = xs - o
+            c = dot(v, d)
+            pp = v - c[..., None] * d
+            rs = np.sqrt(dot(pp, pp)) / sr
+            keep = keep & (~used | ((rs <= max_sigma) & (c > 0)))
+            res.append(np.where(used & np.isfinite(rs), rs, 0.0))
+        mode = mode + np.where(tried & ~keep, FUSE_FALLBACK, 0)
+        x = np.where(keep[..., None], xs, x0)
+        dx = xs - x0
+        move = np.where(keep, np.sqrt(dot(dx, dx)), 0.0)
+        share = np.where(keep, sw / (wp + sw), 0.0)
+        rec = np.stack([x[..., 0], x[..., 1], x[..., 2], move, res[0], res[1], share, mode.astype(np.float64)], axis=-1)
+        rec = np.where(prior[..., None], rec, 0.0)
+        pose_fused = p32.copy()
+        rows = pose_fused[:, pose_row0:pose_row0 + J]
+        rows[keep] = (xs - that)[keep].astype(np.float32)
+        # the frame's statistics: ascending joint order, left before right
+        n_prior, n_both, n_one, n_rej, n_res = (np.zeros(B) for _ in range(5))
+        s2m, mxm, s2r, mxr = (np.zeros(B) for _ in range(4))
+        for j in range(J):
+            on, kj = prior[:, j], keep[:, j]
+            uL, uR = eyes[0][0][:, j], eyes[1][0][:, j]
+            n_prior = n_prior + on
+            s2m = np.where(on, s2m + move[:, j] * move[:, j], s2m)
+            mxm = np.where(on & (move[:, j] > mxm), move[:, j], mxm)
+            rejected = sum(((mode[:, j] & bit) != 0).astype(np.float64) for bit in FUSE_GATED + FUSE_NOT_IN_FRONT)
+            n_rej = n_rej + rejected + np.where(on & ~kj, uL.astype(np.float64) + uR, 0.0)
+            n_both = n_both + (kj & uL & uR)
+            n_one = n_one + (kj & (uL ^ uR))
+            for u, rs in ((uL, res[0][:, j]), (uR, res[1][:, j])):
+                inc = kj & u
+                n_res = n_res + inc
+                s2r = np.where(inc, s2r + rs * rs, s2r)
+                mxr = np.where(inc & (rs > mxr), rs, mxr)
+        some, some_res = n_prior > 0, n_res > 0
+        stats = np.stack([n_prior, n_both, n_one, n_rej, np.where(some, np.sqrt(s2m / np.where(some, n_prior, 1.0)), 0.0), mxm,
+                          np.where(some_res, np.sqrt(s2r / np.where(some_res, n_res, 1.0)), 0.0), mxr], axis=-1)
+    return pose_fused, rec.astype(dtype), stats.astype(dtype)
+
+
 # ---- frames from another lens -> the model camera's frame (egotap.h: egotap_lens_remap / egotap_predict_pose_lens) -----------------------
 LENS_FRAC_BITS = 11                            # a map entry is a sensor pixel coordinate in Q11: the resize's weight precision
 LENS_MAX_SIDE = 16384                          # H, W <= 16384, as for the resize: an entry stays below 2^25

@@ -451,6 +451,60 @@ int egotap_ocam_unproject(const float* points2d, int N, const egotap_ocam* model
 int egotap_stereo_triangulate(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
                               const double* affine, double min_score, const float* pose, int P, int pose_row0, float* joints3d, float* frame, void* stream);
 
+/* ---- the lifted joints fused with the keypoint rays, one eye enough (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * The lifted pose placed by t_hat and the keypoints are two opinions about where a joint is.  egotap_stereo_fuse merges them per joint: the placed
+ * joint is a prior with an isotropic standard deviation, every eye that sees the joint adds the constraint "the joint lies on my ray" with an angular
+ * standard deviation, and the fused joint is the weighted least-squares point -- a 3 x 3 symmetric positive-definite solve, no iteration.  One ray is
+ * enough: a joint only one eye sees is pulled onto that ray and keeps the prior's depth along it.  Nothing here was tuned on data.
+ * keypoints, left, right, R, t, affine, min_score, pose, P and pose_row0 are egotap_stereo_triangulate's; frame [B, 8] is its frame record, of which only
+ * t_hat = frame[0:3] and n = frame[3] are read.  params is host memory, read during the call:
+ *   sigma_ray    angular standard deviation of a keypoint's ray [rad]
+ *   sigma_prior  standard deviation of a lifted joint, in the pose's units
+ *   max_sigma    the gate, in standard deviations; +inf: no gate
+ *   min_joints   fewest triangulated joints behind a t_hat that places a prior
+ * Float64 without contraction, every comparison false on a NaN, dot(p, q) = p0 q0 + p1 q1 + p2 q2 and |p| = sqrt(dot(p, p)), in exactly this order:
+ *   per frame   root_ok = n >= min_joints and t_hat finite;  wp = 1 / (sigma_prior sigma_prior)
+ *   prior       q = pose[pose_row0 + j];  exists when root_ok and q is finite;  x0 = q + t_hat.  Without a prior the record is all zeros.
+ *   eye e       (left, then right) seen = score >= min_score and both coordinates finite;  d = the triangulation's dL / dR;  o = 0 (left), t (right)
+ *               y0 = x0 - o, a = dot(d, y0), rho = |y0|, r = y0 - a d, sr = sigma_ray rho, sr2 = sr sr,
+ *               g = |r| / sqrt(sr2 + sigma_prior sigma_prior)
+ *               a seen eye is   not in front  when not (a > 0) or g is not finite      mode bit 32 (left) / 64 (right)
+ *                               gated         otherwise, when not (g <= max_sigma)     mode bit 8 / 16
+ *                               used          otherwise, with w = score / sr2          mode bit 2 / 4
+ *   system      A = wp I, b = wp x0;  then per used eye, left before right:  m_kk = 1 - d_k d_k, m_kl = -(d_k d_l),  A_kl = A_kl + w m_kl (six entries),
+ *               and for the right eye c_k = (m_k0 t_0 + m_k1 t_1) + m_k2 t_2, b_k = b_k + w c_k  (the left origin is 0 and adds nothing to b)
+ *   LDL^T       l10 = A01 / A00, l20 = A02 / A00, D1 = A11 - l10 A01, c21 = A12 - l20 A01, l21 = c21 / D1, D2 = (A22 - l20 A02) - l21 c21
+ *               z1 = b1 - l10 b0, z2 = (b2 - l20 b0) - l21 z1;  y0 = b0 / A00, y1 = z1 / D1, y2 = z2 / D2
+ *               x2 = y2, x1 = y1 - l21 x2, x0' = (y0 - l10 x1) - l20 x2;  x = (x0', x1, x2).  The pivots are >= wp > 0.  Without a used eye x = x0: no solve.
+ *   post-fit    per used eye v = x - o, c = dot(v, d), p = v - c d, res = |p| / sr;  the eye passes when res <= max_sigma and c > 0.
+ *               A used eye that does not pass, or an x that is not finite, is the FALLBACK: x = x0 and mode bit 128; the used bits stay set.
+ *   mode        bit 1 (a prior exists) plus the bits above
+ * Outputs, f32, each value rounded once from float64:
+ *   fused [B, J, 8]      (x, y, z, move = |x - x0|, res left, res right, share, mode), in the left camera's frame.  res is 0 for an eye that is not used
+ *                        or whose res is not finite;  share = sw / (wp + sw) with sw the used eyes' w added left before right;  move and share are 0
+ *                        where x = x0 (no used eye, fallback)
+ *   pose_fused [B, P, 3] row pose_row0 + j = x - t_hat, subtracted in float64, where a fit was kept (a used eye, no bit 128).  Every other row -- no
+ *                        prior, no used eye, fallback, rows outside the joint rows, every row of a frame without root_ok -- is the input's bits
+ *                        ((q + t_hat) - t_hat need not return q: where nothing moved nothing is rounded again).  It takes pose's place in
+ *                        egotap_pose_track's arguments.
+ *   stats [B, 8]         (joints with a prior, joints whose kept fit used both eyes, joints whose kept fit used one eye, eyes rejected = eyes not in
+ *                        front or gated plus the used eyes of a fallback, rms move, max move, rms res, max res).  move runs over the joints with a
+ *                        prior, res over the used eyes of kept fits; the sums are added in ascending joint order, left before right; zeros where
+ *                        there is nothing to count.
+ * One wave per frame (lane = joint, J <= 64), four frames per workgroup, one launch on the caller's stream, no handle, no synchronisation, no allocation, no
+ * atomics, no workspace, plain vector stores; recorded as stereo_fuse while a handle's timing hook is on.  pose_fused may be pose itself (in place): every
+ * element is then read and written by the same thread.  egotap_amd/spec.py stereo_fuse_ref restates the records; FuseParams there holds the defaults.
+ * EGOTAP_ERR_INVALID, by name and before any launch: what egotap_stereo_triangulate refuses of the arguments the two share (pose is required here); a NULL
+ * frame, params, fused, pose_fused or stats; fused, stats or frame not 16-byte aligned, pose_fused not 4-byte aligned; a sigma_ray or sigma_prior that is
+ * not finite and > 0; a max_sigma that is NaN or < 0; min_joints < 0; an output that overlaps an input or another output, except pose_fused == pose. */
+typedef struct egotap_fuse_params {
+    double sigma_ray, sigma_prior, max_sigma;
+    int32_t min_joints;
+} egotap_fuse_params;
+int egotap_stereo_fuse(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
+                       const double* affine, double min_score, const float* pose, int P, int pose_row0, const float* frame, const egotap_fuse_params* params,
+                       float* fused, float* pose_fused, float* stats, void* stream);
+
 /* ---- the pose, the root and the stereo joints filtered over time (additive; EGOTAP_ABI_VERSION stays 2) ----
  * Every serving output is a single-frame estimate; egotap_pose_track follows them over time with a One-Euro filter (Casiez et al. 2012) on 3-vectors in
  * which a missing sample is irregular sampling.  A TRACK is one 3-vector followed over time, a STREAM one camera rig.  A call carries T consecutive frames of

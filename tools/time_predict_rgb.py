@@ -23,6 +23,8 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
               behind the tracker's, egotap_skeleton_fit (report only)
   skeleton_twist  the same with a twist table on the skeleton (the preset's pole rows, a hinge at right angles to every pole row's rest bone, the default
               thresholds): the launch of egotap_skeleton_fit_twist in the place of egotap_skeleton_fit's (report only)
+  fusion      the tracking arm with StereoFusion.update between the serving call and the tracker (return_keypoints=True as well; sigma_prior 0.05, the other
+              defaults): one more launch in front of the tracker's, egotap_stereo_fuse (report only)
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -104,6 +106,14 @@ def arms_for(m, p, left, right):
         world_tracker.update(pose, joints3d, frame, dt=1.0 / 30, rig_pose=rig_pose)
         return pose
 
+    fuse_tracker, fusion = m.new_pose_tracker(streams=1), m.new_stereo_fusion(0.05)
+
+    def fusion_arm():
+        pose, keypoints, joints3d, frame = m.predict_pose_from_rgb(left, right, return_keypoints=True, return_triangulation=True)
+        pose_fused, _, _ = fusion.update(pose, keypoints, frame)
+        fuse_tracker.update(pose_fused, joints3d, frame, dt=1.0 / 30)
+        return pose
+
     skel_tracker, skeleton = m.new_pose_tracker(streams=1), m.new_skeleton(streams=1)
 
     def skeleton_arm():
@@ -135,6 +145,7 @@ def arms_for(m, p, left, right):
             "triangulation": lambda: m.predict_pose_from_rgb(left, right, return_triangulation=True)[0],
             "tracking": tracking,
             "tracking_world": tracking_world,
+            "fusion": fusion_arm,
             "skeleton": skeleton_arm,
             "skeleton_twist": skeleton_twist_arm,
             "heatmaps_argmax": heatmaps_argmax,
@@ -265,7 +276,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "skeleton", "skeleton_twist") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "fusion", "skeleton", "skeleton_twist") else ""
                 print(f"{setting:12s} B={B:<4d} {k:14s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
