@@ -54,8 +54,7 @@
 #include "conv64_bf16s.h"
 #include "bn_bf16s.h"
 #include "rgb_u8.h"
-#include "rgb_u8_resize.h"
-#include "yuv_u8_resize.h"
+#include "frame_resize.h"          // and frame_source.h, which it and lens_remap.h include: the fetch, the blend and the store of both
 #include "lens_remap.h"
 #include "heatmap_peaks.h"
 #include "limb_decode.h"
@@ -1089,20 +1088,18 @@ static int hm_resolve(Handle* h, int net) {
 // [r7] Where an estimator's frames come from: the normalised planar fp32 frames (left / right), or the camera's bytes (left8 / right8: uint8
 // [B, S0, S0, 3], with the fp32 [3][256] value table).  Sides 64 / 128: both stems stage the bytes themselves.  Every other side: the frames are
 // converted into `scratch` (2 x B x 3 x S0^2 floats, the caller's workspace slice) first and the forward proceeds on them as ever.
-// [r8] the sensor's own frames behind a byte source (egotap_predict_pose_sensor_u8 only): uint8 [B, H, W, 3] per eye, a source rectangle and a mirror
-// flag per eye; each piece is resized into `slice` (chunk x 2 x 3 S0^2 bytes of the caller's workspace) and read there as camera bytes
-// `yuv` (egotap_predict_pose_sensor_yuv only): the frames are NV12 / YUYV of that layout and colour, frame_stride bytes each; the piece is converted
-// and resized into the same slice by yuv_u8_resize_kernel
-// `lens` (egotap_predict_pose_lens only): the frames are another lens's, of that layout; the piece is gathered into the same slice through the two
-// lens maps (lens_remap_kernel) -- rect and mirror are not read then
+// [r8] the sensor's own frames behind a byte source (the sensor and lens entries only): frames of the layout `src` (packed RGB8, NV12 or YUYV,
+// src.frame_stride bytes each), a source rectangle and a mirror flag per eye; each piece is converted and resized into `slice` (chunk x 2 x 3 S0^2
+// bytes of the caller's workspace) and read there as camera bytes
+// with maps (egotap_predict_pose_lens only): the frames are another lens's; the piece is gathered into the same slice through the two lens maps, an
+// eye's fill where a map has no source -- rect and mirror say where the keypoints come out and are not read by the gather
 struct HmSensor {
     const unsigned char *left8, *right8;
-    int H, W, rect[2][4], mirror[2];
+    FrameSource src;
+    int rect[2][4], mirror[2];
+    const int *map_left, *map_right;
+    unsigned fill[2];
     unsigned char* slice;
-    const YuvSource* yuv = nullptr;
-    const LensSource* lens = nullptr;
-    const int *map_left = nullptr, *map_right = nullptr;
-    unsigned fill[2] = {0u, 0u};
 };
 struct HmSrc {
     const float *left, *right;
@@ -1723,10 +1720,11 @@ extern "C" int egotap_hm_forward(egotap_handle h, int net, const float* left, co
 }
 
 // ---- [r7] camera bytes: the converter, and one estimator from bytes
-static const char* rgb_u8_refusal(const void* left8, const void* right8, const void* table) {
+// (camera_bytes = false: frames of a sensor source that go through a resize or gather first, at whatever alignment their own fetch asks for)
+static const char* rgb_u8_refusal(const void* left8, const void* right8, const void* table, bool camera_bytes = true) {
     if (!left8 || !right8) return "null frames (left8 and right8 are required)";
     if (!table) return "null table (the fp32 [3][256] value table is required)";
-    if ((((uintptr_t)left8 | (uintptr_t)right8) & 3) != 0) return "left8 and right8 must be 4-byte aligned (rows are read as aligned dwords)";
+    if (camera_bytes && (((uintptr_t)left8 | (uintptr_t)right8) & 3) != 0) return "left8 and right8 must be 4-byte aligned (rows are read as aligned dwords)";
     if (((uintptr_t)table & 15) != 0) return "the table must be 16-byte aligned";
     return nullptr;
 }
@@ -1843,25 +1841,23 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
         // byte-source stems at sides 64 / 128 and go through the converter into its slice elsewhere (never with the hand-off: that exists at sides
         // 64 / 128 only).
         unsigned char* s8l = sensor.slice;
-        const long frame = sensor.lens ? sensor.lens->frame_stride : sensor.yuv ? sensor.yuv->frame_stride : 3L * sensor.H * sensor.W;
+        const long frame = sensor.src.frame_stride;
+        const bool gather = sensor.map_left != nullptr;
+        const char* const role = gather ? "lens_remap" : sensor.src.fetch == FETCH_RGB8 ? "rgb_u8_resize" : "yuv_u8_resize";      // the timing hook's names
+        const char* const kernel = gather ? "lens_remap_kernel" : sensor.src.fetch == FETCH_RGB8 ? "rgb_u8_resize_kernel" : "yuv_u8_resize_kernel";
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
             HmSrc piece = whole.at(lo, rgb);
             if (resize) {
                 unsigned char* s8r = s8l + (size_t)n * rgb;
-                if (sensor.lens) {
-                    GemmTimer t(h, (hipStream_t)stream, "lens_remap", "lens_remap_kernel", 0.0);
-                    EGO_HIP(lens_remap_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, *sensor.lens, sensor.map_left, sensor.map_right,
-                                              sensor.fill[0], sensor.fill[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
-                } else if (sensor.yuv) {
-                    GemmTimer t(h, (hipStream_t)stream, "yuv_u8_resize", "yuv_u8_resize_kernel", 0.0);
-                    EGO_HIP(yuv_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, *sensor.yuv, sensor.rect[0], sensor.rect[1],
-                                                 sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
-                } else {
-                    GemmTimer t(h, (hipStream_t)stream, "rgb_u8_resize", "rgb_u8_resize_kernel", 0.0);
-                    EGO_HIP(rgb_u8_resize_launch(sensor.left8 + lo * frame, sensor.right8 + lo * frame, n, sensor.H, sensor.W, sensor.rect[0], sensor.rect[1],
-                                                 sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
-                }
+                const unsigned char *fl = sensor.left8 + lo * frame, *fr = sensor.right8 + lo * frame;
+                GemmTimer t(h, (hipStream_t)stream, role, kernel, 0.0);
+                if (gather)
+                    EGO_HIP(lens_remap_launch(fl, fr, n, sensor.src, sensor.map_left, sensor.map_right, sensor.fill[0], sensor.fill[1], 4 * S, s8l, s8r,
+                                              device_cu_count(), (hipStream_t)stream));
+                else
+                    EGO_HIP(frame_resize_launch(fl, fr, n, sensor.src, sensor.rect[0], sensor.rect[1], sensor.mirror[0], sensor.mirror[1], 4 * S, s8l, s8r,
+                                                device_cu_count(), (hipStream_t)stream));
                 piece = HmSrc{nullptr, nullptr, s8l, s8r, src.table, nullptr};
             }
             if (!stems) {
@@ -1991,31 +1987,39 @@ extern "C" int egotap_predict_pose_rgb_u8_kpl(egotap_handle h, const uint8_t* le
                                      limbs);
 }
 
-// ---- [r8] the sensor's own frames: crop, mirror and bilinear resize on the device (rgb_u8_resize.h), standalone and in front of the one call
-static const char* rgb_u8_resize_refusal(const void* left8, const void* right8, int H, int W, const int* rect_left, const int* rect_right) {
+// ---- [r8] the sensor's own frames (frame_source.h): cropped, mirrored and resized (frame_resize.h) or gathered through lens maps (lens_remap.h) on
+// the device, standalone and in front of the one call.  Each entry turns its arguments into a FrameSource and says what it refuses about them; the
+// rest is shared: sensor_op_checks by the three standalone operators, predict_pose_sensor_impl by the three one-call entries.
+static const char* rgb8_source_refusal(const void* left8, const void* right8, int H, int W, const int* rect_left, const int* rect_right, FrameSource* q) {
     if (!left8 || !right8) return "null frames (left8 and right8 are required)";
     if (!rect_left || !rect_right) return "null rectangle (rect_left and rect_right are four ints each: x0, y0, w, h)";
-    if (H < 1 || W < 1 || H > kResizeMaxSrc || W > kResizeMaxSrc) return "the frame height and width must be between 1 and 16384";
-    if (const char* why = rgb_u8_resize_rect_refusal(rect_left, H, W)) return why;
-    return rgb_u8_resize_rect_refusal(rect_right, H, W);
+    if (const char* why = frame_layout_refusal(FETCH_RGB8, H, W, 0, 0L, 0L)) return why;
+    *q = frame_source_rgb8(H, W);
+    return resize_rects_refusal(*q, rect_left, rect_right);
+}
+// what the standalone operators check alike, in their order: the batch, the output side, the operator's source (`source_why`), the outputs
+static int sensor_op_checks(const char* who, int B, int S0, const char* source_why, const void* out_left8, const void* out_right8) {
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
+    EGO_CHECK(!source_why, "%s: %s", who, source_why);
+    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
+    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
+    return EGOTAP_OK;
 }
 extern "C" int egotap_rgb_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rect_left, const int* rect_right, int mirror_left,
                                     int mirror_right, int S0, uint8_t* out_left8, uint8_t* out_right8, void* stream) {
-    static const char* const who = "egotap_rgb_u8_resize";
-    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
-    const char* why = rgb_u8_resize_refusal(left8, right8, H, W, rect_left, rect_right);
-    EGO_CHECK(!why, "%s: %s", who, why);
-    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
-    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
-    EGO_HIP(rgb_u8_resize_launch(left8, right8, B, H, W, rect_left, rect_right, mirror_left, mirror_right, S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
+    FrameSource q{};
+    const int rc = sensor_op_checks("egotap_rgb_u8_resize", B, S0, rgb8_source_refusal(left8, right8, H, W, rect_left, rect_right, &q), out_left8, out_right8);
+    if (rc != EGOTAP_OK) return rc;
+    EGO_HIP(frame_resize_launch(left8, right8, B, q, rect_left, rect_right, mirror_left, mirror_right, S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
 extern "C" int egotap_predict_pose_sensor_u8_workspace_bytes(egotap_handle h, int B, int H, int W, int chunk, size_t* bytes) {
     static const char* const who = "egotap_predict_pose_sensor_u8_workspace_bytes";
     EGO_CHECK(h && bytes, "%s: null argument", who);
     EGO_CHECK(B >= 0 && chunk >= 0, "%s: negative batch or chunk", who);
-    EGO_CHECK(H >= 1 && W >= 1 && H <= kResizeMaxSrc && W <= kResizeMaxSrc, "%s: the frame height and width must be between 1 and 16384", who);
+    const char* why = frame_layout_refusal(FETCH_RGB8, H, W, 0, 0L, 0L);
+    EGO_CHECK(!why, "%s: %s", who, why);
     *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_SENSOR).total;
     return EGOTAP_OK;
 }
@@ -2030,25 +2034,38 @@ static void sensor_keypoint_affine(const Handle* h, const HmSensor& q, float* af
         affine[4 * e + 3] = (float)q.rect[e][1];
     }
 }
-static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
-                                        const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
-                                        bool kp, float* keypoints, float* limbs) {
-    const char* why = !(rects && mirrors) ? "null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)"
-                                          : rgb_u8_resize_refusal(left8, right8, H, W, rects, rects + 4);
-    const int rc = rgb_entry_checks(who, h, B, why ? why : rgb_u8_refusal(left8, right8, table), nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
+static const char* const kNullRectsOrMirrors = "null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)";
+// What the three sensor entries do alike once their source is stated.  `why`: what the entry refuses about its own arguments (nullptr: nothing), told
+// in its place among the shared checks, the table's two behind it.  rects (2 x 4 ints) and mirrors (2 ints) are read once nothing is refused; `lens`
+// brings the maps and fills of a gather.  `in_place`: the u8 entry's identity request, the caller's frames ARE the camera bytes.
+static int predict_pose_sensor_impl(const char* who, egotap_handle h, const char* why, const uint8_t* left8, const uint8_t* right8, int B, const FrameSource& fs,
+                                    const int* rects, const int32_t* mirrors, const egotap_lens_source* lens, bool in_place, const float* table, float* pose,
+                                    float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
+    if (!why) why = rgb_u8_refusal(left8, right8, table, false);
+    const int rc = rgb_entry_checks(who, h, B, why, nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
     if (rc != EGOTAP_OK) return rc;
-    const int S0 = 4 * h->cfg.hm_size;
     // (q.slice is the walk's to place: the workspace layout is read there, once)
-    HmSensor q{left8, right8, H, W, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}}, {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0},
-               nullptr};
-    // the identity request (frames already S0 x S0, the full frame, no mirror): the caller's frames are read in place, nothing is resized
-    bool identity = H == S0 && W == S0 && !q.mirror[0] && !q.mirror[1];
-    for (int e = 0; e < 2; ++e) identity = identity && q.rect[e][0] == 0 && q.rect[e][1] == 0 && q.rect[e][2] == S0 && q.rect[e][3] == S0;
-    HmSrc src{nullptr, nullptr, identity ? left8 : nullptr, identity ? right8 : nullptr, table, nullptr};
+    HmSensor q{left8, right8, fs, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}}, {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0},
+               lens ? (const int*)lens->map_left : nullptr, lens ? (const int*)lens->map_right : nullptr,
+               {lens ? lens_fill(lens->fill[0]) : 0u, lens ? lens_fill(lens->fill[1]) : 0u}, nullptr};
+    HmSrc src{nullptr, nullptr, in_place ? left8 : nullptr, in_place ? right8 : nullptr, table, nullptr};
     src.sensor = &q;
     float affine[8];
     sensor_keypoint_affine(h, q, affine);
     return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
+}
+static int predict_pose_sensor_u8_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects,
+                                        const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
+                                        bool kp, float* keypoints, float* limbs) {
+    FrameSource fs{};
+    const char* why = !(rects && mirrors) ? kNullRectsOrMirrors : rgb8_source_refusal(left8, right8, H, W, rects, rects + 4, &fs);
+    if (!why) why = rgb_u8_refusal(left8, right8, table);      // frames a stem may read in place: its alignment, behind the table's presence as ever
+    // the identity request (frames already S0 x S0, the full frame, no mirror): the caller's frames are read in place, nothing is resized
+    const int S0 = h ? 4 * h->cfg.hm_size : 0;
+    bool identity = !why && H == S0 && W == S0 && !mirrors[0] && !mirrors[1];
+    for (int e = 0; identity && e < 2; ++e) identity = rects[4 * e] == 0 && rects[4 * e + 1] == 0 && rects[4 * e + 2] == S0 && rects[4 * e + 3] == S0;
+    return predict_pose_sensor_impl(who, h, why, left8, right8, B, fs, rects, mirrors, nullptr, identity, table, pose, heatmaps, chunk, ws, ws_bytes, stream, kp,
+                                    keypoints, limbs);
 }
 extern "C" int egotap_predict_pose_sensor_u8(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, int H, int W, const int* rects, const int* mirrors,
                                              const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {
@@ -2068,59 +2085,43 @@ extern "C" int egotap_predict_pose_sensor_u8_kpl(egotap_handle h, const uint8_t*
                                         stream, false, keypoints, limbs);
 }
 
-// ---- NV12 / YUYV sensor frames: the colour conversion inside the resize (yuv_u8_resize.h), standalone and in front of the one call
-// what is wrong with a descriptor or the frames behind it, or nullptr; fills `q` (layout and integer coefficients) when nothing is
-static const char* yuv_source_refusal(const egotap_yuv_source* src, const void* left8, const void* right8, YuvSource* q) {
+// ---- NV12 / YUYV sensor frames: the colour conversion inside the resize, standalone and in front of the one call
+// what is wrong with a descriptor or the frames behind it, or nullptr; fills `q` (layout, fetch and integer coefficients) when nothing is
+static const char* yuv_source_refusal(const egotap_yuv_source* src, const void* left8, const void* right8, FrameSource* q) {
     if (!src) return "null source descriptor (egotap_yuv_source)";
     if (src->struct_size != (int32_t)sizeof(egotap_yuv_source)) return "wrong struct_size (sizeof(egotap_yuv_source) expected)";
-    if (const char* why = yuv_layout_refusal(src->format, src->H, src->W, src->pitch, (long)src->uv_offset, (long)src->frame_stride)) return why;
+    if (src->format != EGOTAP_YUV_NV12 && src->format != EGOTAP_YUV_YUYV) return "unknown format (EGOTAP_YUV_NV12 or EGOTAP_YUV_YUYV)";
+    const int fetch = src->format == EGOTAP_YUV_NV12 ? FETCH_NV12 : FETCH_YUYV;
+    if (const char* why = frame_layout_refusal(fetch, src->H, src->W, src->pitch, (long)src->uv_offset, (long)src->frame_stride)) return why;
     if (src->matrix != EGOTAP_YUV_BT601 && src->matrix != EGOTAP_YUV_BT709) return "unknown matrix (EGOTAP_YUV_BT601 or EGOTAP_YUV_BT709)";
     if (src->range != EGOTAP_YUV_LIMITED && src->range != EGOTAP_YUV_FULL) return "unknown range (EGOTAP_YUV_LIMITED or EGOTAP_YUV_FULL)";
     if (!left8 || !right8) return "null frames (left8 and right8 are required)";
-    if ((((uintptr_t)left8 | (uintptr_t)right8) & (uintptr_t)(yuv_base_alignment(src->format) - 1)) != 0)
-        return src->format == YUV_NV12 ? "left8 and right8 must be 2-byte aligned (NV12: the chroma pair is one aligned 16-bit load)"
-                                       : "left8 and right8 must be 4-byte aligned (YUYV: the pixel pair is one aligned dword)";
-    *q = YuvSource{src->format, src->H, src->W, src->pitch, src->format == YUV_NV12 ? (long)src->uv_offset : 0L, (long)src->frame_stride,
-                   yuv_coefficients(src->matrix, src->range)};
+    if ((((uintptr_t)left8 | (uintptr_t)right8) & (uintptr_t)(frame_base_alignment(fetch) - 1)) != 0)
+        return fetch == FETCH_NV12 ? "left8 and right8 must be 2-byte aligned (NV12: the chroma pair is one aligned 16-bit load)"
+                                   : "left8 and right8 must be 4-byte aligned (YUYV: the pixel pair is one aligned dword)";
+    *q = FrameSource{fetch, src->H, src->W, src->pitch, fetch == FETCH_NV12 ? (long)src->uv_offset : 0L, (long)src->frame_stride,
+                     yuv_coefficients(src->matrix, src->range)};
     return nullptr;
-}
-static const char* yuv_rects_refusal(const YuvSource& q, const int* rect_left, const int* rect_right) {
-    if (const char* why = rgb_u8_resize_rect_refusal(rect_left, q.H, q.W)) return why;
-    return rgb_u8_resize_rect_refusal(rect_right, q.H, q.W);
 }
 extern "C" int egotap_yuv_u8_resize(const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rect_left, const int* rect_right,
                                     int mirror_left, int mirror_right, int S0, uint8_t* out_left8, uint8_t* out_right8, void* stream) {
-    static const char* const who = "egotap_yuv_u8_resize";
-    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
-    YuvSource q{};
+    FrameSource q{};
     const char* why = yuv_source_refusal(src, left8, right8, &q);
-    if (!why) why = !(rect_left && rect_right) ? "null rectangle (rect_left and rect_right are four ints each: x0, y0, w, h)" : yuv_rects_refusal(q, rect_left, rect_right);
-    EGO_CHECK(!why, "%s: %s", who, why);
-    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
-    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
-    EGO_HIP(yuv_u8_resize_launch(left8, right8, B, q, rect_left, rect_right, mirror_left, mirror_right, S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
+    if (!why) why = !(rect_left && rect_right) ? "null rectangle (rect_left and rect_right are four ints each: x0, y0, w, h)" : resize_rects_refusal(q, rect_left, rect_right);
+    const int rc = sensor_op_checks("egotap_yuv_u8_resize", B, S0, why, out_left8, out_right8);
+    if (rc != EGOTAP_OK) return rc;
+    EGO_HIP(frame_resize_launch(left8, right8, B, q, rect_left, rect_right, mirror_left, mirror_right, S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
 }
-// the sensor entry with the descriptor in place of H, W: the same checks in the same order, the same affine, the same walk
+// the sensor entry with the descriptor in place of H, W; never the identity request: a YUV source always converts
 static int predict_pose_sensor_yuv_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* ysrc,
                                          const int* rects, const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws,
                                          size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
-    YuvSource yuv{};
-    const char* why = !(rects && mirrors) ? "null rectangles or mirror flags (rects: 2 x 4 ints, left then right; mirrors: 2 ints)"
-                                          : yuv_source_refusal(ysrc, left8, right8, &yuv);
-    if (!why) why = yuv_rects_refusal(yuv, rects, rects + 4);
-    if (!why && !table) why = "null table (the fp32 [3][256] value table is required)";
-    if (!why && ((uintptr_t)table & 15) != 0) why = "the table must be 16-byte aligned";
-    const int rc = rgb_entry_checks(who, h, B, why, nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
-    if (rc != EGOTAP_OK) return rc;
-    HmSensor q{left8, right8, yuv.H, yuv.W, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}},
-               {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0}, nullptr, &yuv};
-    HmSrc src{nullptr, nullptr, nullptr, nullptr, table, nullptr};      // never the identity request: a YUV source always converts
-    src.sensor = &q;
-    float affine[8];
-    sensor_keypoint_affine(h, q, affine);
-    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
+    FrameSource fs{};
+    const char* why = !(rects && mirrors) ? kNullRectsOrMirrors : yuv_source_refusal(ysrc, left8, right8, &fs);
+    if (!why) why = resize_rects_refusal(fs, rects, rects + 4);
+    return predict_pose_sensor_impl(who, h, why, left8, right8, B, fs, rects, mirrors, nullptr, false, table, pose, heatmaps, chunk, ws, ws_bytes, stream, kp,
+                                    keypoints, limbs);
 }
 extern "C" int egotap_predict_pose_sensor_yuv(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_yuv_source* src, const int* rects,
                                               const int* mirrors, const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes,
@@ -2143,21 +2144,19 @@ extern "C" int egotap_predict_pose_sensor_yuv_kpl(egotap_handle h, const uint8_t
 
 // ---- frames from another lens: the lens maps applied as a bilinear gather (lens_remap.h), standalone and in front of the one call
 // what is wrong with a descriptor or the frames behind it, or nullptr; fills `q` (layout, fetch and integer coefficients) when nothing is
-static const char* lens_source_refusal(const egotap_lens_source* src, const void* left8, const void* right8, LensSource* q) {
+static const char* lens_source_refusal(const egotap_lens_source* src, const void* left8, const void* right8, FrameSource* q) {
     if (!src) return "null source descriptor (egotap_lens_source)";
     if (src->struct_size != (int32_t)sizeof(egotap_lens_source)) return "wrong struct_size (sizeof(egotap_lens_source) expected)";
     if (src->format != EGOTAP_LENS_RGB8 && src->format != EGOTAP_LENS_NV12 && src->format != EGOTAP_LENS_YUYV)
         return "unknown format (EGOTAP_LENS_RGB8, EGOTAP_LENS_NV12 or EGOTAP_LENS_YUYV)";
     if (src->format == EGOTAP_LENS_RGB8) {
-        if (src->H < 1 || src->W < 1 || src->H > kResizeMaxSrc || src->W > kResizeMaxSrc) return "the frame height and width must be between 1 and 16384";
+        if (const char* why = frame_layout_refusal(FETCH_RGB8, src->H, src->W, 0, 0L, 0L)) return why;
         if (!left8 || !right8) return "null frames (left8 and right8 are required)";
-        *q = lens_source_rgb8(src->H, src->W);
+        *q = frame_source_rgb8(src->H, src->W);
     } else {
         if (src->yuv.format != (src->format == EGOTAP_LENS_NV12 ? EGOTAP_YUV_NV12 : EGOTAP_YUV_YUYV)) return "the embedded egotap_yuv_source has another format than the descriptor";
         if (src->yuv.H != src->H || src->yuv.W != src->W) return "the embedded egotap_yuv_source has another H or W than the descriptor";
-        YuvSource y{};
-        if (const char* why = yuv_source_refusal(&src->yuv, left8, right8, &y)) return why;
-        *q = lens_source_yuv(y);
+        if (const char* why = yuv_source_refusal(&src->yuv, left8, right8, q)) return why;
     }
     if (!src->map_left || !src->map_right) return "null lens map (map_left and map_right are device int32 [S0 * S0][2])";
     if ((((uintptr_t)src->map_left | (uintptr_t)src->map_right) & 15) != 0) return "map_left and map_right must be 16-byte aligned (four entries are two 16-byte loads)";
@@ -2165,14 +2164,9 @@ static const char* lens_source_refusal(const egotap_lens_source* src, const void
 }
 extern "C" int egotap_lens_remap(const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S0, uint8_t* out_left8, uint8_t* out_right8,
                                  void* stream) {
-    static const char* const who = "egotap_lens_remap";
-    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
-    EGO_CHECK(S0 > 0 && S0 % 4 == 0 && S0 <= kResizeMaxSide, "%s: the output side must be a positive multiple of 4, at most %d (S0 = %d)", who, kResizeMaxSide, S0);
-    LensSource q{};
-    const char* why = lens_source_refusal(src, left8, right8, &q);
-    EGO_CHECK(!why, "%s: %s", who, why);
-    EGO_CHECK(out_left8 && out_right8, "%s: null output", who);
-    EGO_CHECK((((uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: out_left8 and out_right8 must be 4-byte aligned (rows are written as aligned dwords)", who);
+    FrameSource q{};
+    const int rc = sensor_op_checks("egotap_lens_remap", B, S0, lens_source_refusal(src, left8, right8, &q), out_left8, out_right8);
+    if (rc != EGOTAP_OK) return rc;
     EGO_HIP(lens_remap_launch(left8, right8, B, q, (const int*)src->map_left, (const int*)src->map_right, lens_fill(src->fill[0]), lens_fill(src->fill[1]), S0,
                               out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
@@ -2184,31 +2178,20 @@ extern "C" int egotap_predict_pose_lens_workspace_bytes(egotap_handle h, int B, 
     *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_SENSOR).total;      // the sensor entry's: the slice holds OUTPUT frames
     return EGOTAP_OK;
 }
-// the sensor entry with the descriptor in place of H, W, rectangles and mirrors: the same checks in the same order, the same walk.  The keypoints
-// come out in the model camera's calibration pixels: the sensor entry's affine on a frame of that size, the full rectangle, the eye's mirror flag
+// the sensor entry with the descriptor in place of H, W, rectangles and mirrors; never the identity request: a lens source always gathers.  The
+// keypoints come out in the model camera's calibration pixels: the sensor entry's affine on a frame of that size, the full rectangle, the eye's
+// mirror flag
 static int predict_pose_lens_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* lsrc,
                                    const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints,
                                    float* limbs) {
-    LensSource lens{};
-    const char* why = lens_source_refusal(lsrc, left8, right8, &lens);
+    FrameSource fs{};
+    const char* why = lens_source_refusal(lsrc, left8, right8, &fs);
     if (!why && (lsrc->model_h < 1 || lsrc->model_w < 1 || lsrc->model_h > kResizeMaxSrc || lsrc->model_w > kResizeMaxSrc))
         why = "the model camera's calibration image (model_h, model_w) must be between 1 and 16384 on each side";
-    if (!why && !table) why = "null table (the fp32 [3][256] value table is required)";
-    if (!why && ((uintptr_t)table & 15) != 0) why = "the table must be 16-byte aligned";
-    const int rc = rgb_entry_checks(who, h, B, why, nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
-    if (rc != EGOTAP_OK) return rc;
-    HmSensor q{left8, right8, lens.H, lens.W, {{0, 0, lsrc->model_w, lsrc->model_h}, {0, 0, lsrc->model_w, lsrc->model_h}},
-               {lsrc->mirror[0] ? 1 : 0, lsrc->mirror[1] ? 1 : 0}, nullptr};
-    q.lens = &lens;
-    q.map_left = (const int*)lsrc->map_left;
-    q.map_right = (const int*)lsrc->map_right;
-    q.fill[0] = lens_fill(lsrc->fill[0]);
-    q.fill[1] = lens_fill(lsrc->fill[1]);
-    HmSrc src{nullptr, nullptr, nullptr, nullptr, table, nullptr};      // never the identity request: a lens source always gathers
-    src.sensor = &q;
-    float affine[8];
-    sensor_keypoint_affine(h, q, affine);
-    return predict_pose_rgb_impl(who, h, src, B, pose, heatmaps, chunk, ws, ws_bytes, stream, keypoints, affine, limbs);
+    const int mw = why ? 0 : lsrc->model_w, mh = why ? 0 : lsrc->model_h;      // (a refused descriptor may be NULL)
+    const int full[8] = {0, 0, mw, mh, 0, 0, mw, mh};
+    return predict_pose_sensor_impl(who, h, why, left8, right8, B, fs, full, why ? nullptr : lsrc->mirror, lsrc, false, table, pose, heatmaps, chunk, ws, ws_bytes,
+                                    stream, kp, keypoints, limbs);
 }
 extern "C" int egotap_predict_pose_lens(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
                                         float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {

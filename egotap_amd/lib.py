@@ -383,21 +383,31 @@ def pose_metrics(pred, gt, want_aligned: bool = False, reference_batch_axes: boo
     return (e, pa, al) if want_aligned else (e, pa)
 
 
-def check_camera_frames(who, left8, right8, S0):
-    """the one wording of what the byte entries take: two uint8 [B, S0, S0, 3] contiguous tensors on one GPU; returns B"""
+def _check_u8_frames(who, whose, left8, right8, expected):
+    """what every byte entry refuses alike, in this order: frames off the GPU, another dtype than uint8, a shape that is not the entry's
+    (``expected()`` names the one it wants, or returns None), frames that are not contiguous or sit on two devices"""
     import torch
     for t in (left8, right8):
         if not (torch.is_tensor(t) and t.is_cuda):
             raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the frames to cuda")
     for t in (left8, right8):
         if t.dtype != torch.uint8:
-            raise EgotapError(f"{who} takes the camera's bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
-    B = left8.shape[0] if left8.dim() else 0
-    if tuple(left8.shape) != (B, S0, S0, 3) or tuple(right8.shape) != (B, S0, S0, 3):
-        raise ValueError(f"{who}: expected left8 / right8 [B, {S0}, {S0}, 3] (HWC, RGB), got {tuple(left8.shape)} / {tuple(right8.shape)}")
+            raise EgotapError(f"{who} takes the {whose}'s bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
+    want = expected()
+    if want:
+        raise ValueError(f"{who}: expected left8 / right8 {want}, got {tuple(left8.shape)} / {tuple(right8.shape)}")
     if not (left8.is_contiguous() and right8.is_contiguous()) or left8.device != right8.device:
         raise EgotapError(f"{who}: the frames must be contiguous and on one device (the bytes are read in place, nothing is copied)")
-    return B
+
+
+def check_camera_frames(who, left8, right8, S0):
+    """the one wording of what the byte entries take: two uint8 [B, S0, S0, 3] contiguous tensors on one GPU; returns B"""
+    def shape():
+        B = left8.shape[0] if left8.dim() else 0
+        if tuple(left8.shape) != (B, S0, S0, 3) or tuple(right8.shape) != (B, S0, S0, 3):
+            return f"[B, {S0}, {S0}, 3] (HWC, RGB)"
+    _check_u8_frames(who, "camera", left8, right8, shape)
+    return left8.shape[0]
 
 
 def rgb_u8_to_f32(left8, right8, table):
@@ -419,17 +429,10 @@ def rgb_u8_to_f32(left8, right8, table):
 def check_sensor_frames(who, left8, right8):
     """the one wording of what the sensor entries take: two uint8 [B, H, W, 3] contiguous tensors on one GPU, the same H and W for both eyes;
     returns (B, H, W)"""
-    import torch
-    for t in (left8, right8):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the frames to cuda")
-    for t in (left8, right8):
-        if t.dtype != torch.uint8:
-            raise EgotapError(f"{who} takes the sensor's bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
-    if left8.dim() != 4 or left8.shape[3] != 3 or left8.shape[1] < 1 or left8.shape[2] < 1 or tuple(right8.shape) != tuple(left8.shape):
-        raise ValueError(f"{who}: expected left8 / right8 [B, H, W, 3] (HWC, RGB) with one H and W for both eyes, got {tuple(left8.shape)} / {tuple(right8.shape)}")
-    if not (left8.is_contiguous() and right8.is_contiguous()) or left8.device != right8.device:
-        raise EgotapError(f"{who}: the frames must be contiguous and on one device (the bytes are read in place, nothing is copied)")
+    def shape():
+        if left8.dim() != 4 or left8.shape[3] != 3 or left8.shape[1] < 1 or left8.shape[2] < 1 or tuple(right8.shape) != tuple(left8.shape):
+            return "[B, H, W, 3] (HWC, RGB) with one H and W for both eyes"
+    _check_u8_frames(who, "sensor", left8, right8, shape)
     return tuple(int(v) for v in left8.shape[:3])
 
 
@@ -462,21 +465,14 @@ def yuv_source(layout, colour):
 def check_yuv_frames(who, left8, right8, layout):
     """the one wording of what the YUV entries take: two contiguous uint8 tensors on one GPU, B frames of ``layout.frame_stride`` bytes each (any shape
     whose first axis is B), frame 0 at a multiple of the format's load width (2 bytes for nv12, 4 for yuyv); returns B"""
-    import torch
-    for t in (left8, right8):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); move the frames to cuda")
-    for t in (left8, right8):
-        if t.dtype != torch.uint8:
-            raise EgotapError(f"{who} takes the sensor's bytes: dtype uint8, got {t.dtype} (normalised float frames go to the float entry)")
     fs = layout.frame_stride
-    B = int(left8.shape[0]) if left8.dim() else -1
-    if B < 0 or left8.numel() != B * fs or tuple(right8.shape) != tuple(left8.shape):
-        raise ValueError(f"{who}: expected left8 / right8 of one shape, B {layout.format} frames of frame_stride = {fs} bytes each ([B, {fs}]), got "
-                         f"{tuple(left8.shape)} / {tuple(right8.shape)}")
-    if not (left8.is_contiguous() and right8.is_contiguous()) or left8.device != right8.device:
-        raise EgotapError(f"{who}: the frames must be contiguous and on one device (the bytes are read in place, nothing is copied)")
-    a = layout.base_alignment
+
+    def shape():
+        B = int(left8.shape[0]) if left8.dim() else -1
+        if B < 0 or left8.numel() != B * fs or tuple(right8.shape) != tuple(left8.shape):
+            return f"of one shape, B {layout.format} frames of frame_stride = {fs} bytes each ([B, {fs}])"
+    _check_u8_frames(who, "sensor", left8, right8, shape)
+    B, a = int(left8.shape[0]), layout.base_alignment
     if B > 0 and (left8.data_ptr() % a or right8.data_ptr() % a):
         raise EgotapError(f"{who}: {layout.format} frames must start at a multiple of {a} bytes (the widest load of the format)")
     return B

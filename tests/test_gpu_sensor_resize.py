@@ -43,37 +43,61 @@ def _rects(H, W):
             ((0, 1, 1, 1), (3, 2, W - 5, H - 4))]                                # a single pixel | an interior rectangle
 
 
-OPERATOR = [(37, 53, 64), (96, 120, 64), (130, 258, 64), (512, 640, 256)]
+# (37, 53, 260): more columns than a workgroup has threads, so the tap table is built in two passes; the odd W puts rows at every byte alignment
+OPERATOR = [(37, 53, 64), (96, 120, 64), (130, 258, 64), (512, 640, 256), (37, 53, 260)]
+
+
+def _at_odd_addresses(lh, rh):
+    """the frames on the device at an odd byte address inside a larger allocation: source rows start at any byte"""
+    store = [torch.empty(t.numel() + 8, dtype=torch.uint8, device="cuda") for t in (lh, rh)]
+    return store[0][1:1 + lh.numel()].view(lh.shape).copy_(lh), store[1][3:3 + rh.numel()].view(rh.shape).copy_(rh)
+
+
+def _run_between_canaries(l8, r8, rect_l, rect_r, mirror_l, mirror_r, S0):
+    """egotap_rgb_u8_resize into a canary-filled buffer -> (left, right) uint8 [B, S0, S0, 3] on the device; the bytes in front of, between and
+    behind the outputs must stay untouched"""
+    B, H, W = l8.shape[:3]
+    n, pad, canary = B * S0 * S0 * 3, 1024, 0xA5
+    flat = torch.full((2 * (n + pad) + pad,), canary, dtype=torch.uint8, device="cuda")
+    out_l, out_r = flat[pad:pad + n], flat[2 * pad + n:2 * pad + 2 * n]
+    assert out_l.data_ptr() % 4 == 0 and out_r.data_ptr() % 4 == 0
+    rl = (C.c_int * 4)(*spec.check_resize_rect("t", rect_l, H, W))
+    rr = (C.c_int * 4)(*spec.check_resize_rect("t", rect_r, H, W))
+    L.check(L.load().egotap_rgb_u8_resize(L.ptr(l8), L.ptr(r8), B, H, W, rl, rr, mirror_l, mirror_r, S0, L.ptr(out_l), L.ptr(out_r), L.stream()))
+    torch.cuda.synchronize()
+    for lo, hi in ((0, pad), (pad + n, 2 * pad + n), (2 * pad + 2 * n, flat.numel())):
+        assert bool((flat[lo:hi] == canary).all()), (lo, hi)
+    return out_l.view(B, S0, S0, 3), out_r.view(B, S0, S0, 3)
 
 
 @pytest.mark.parametrize("H,W,S0", OPERATOR)
 @pytest.mark.parametrize("B", [1, 3])
 def test_operator_equals_the_integer_restatement_and_stays_inside_its_outputs(H, W, S0, B):
     lh, rh = _frames8(1, B, H, W, 255 if B == 1 else 0)
-    # the frames sit at an odd byte address inside a larger allocation: source rows start at any byte
-    store = [torch.empty(t.numel() + 8, dtype=torch.uint8, device="cuda") for t in (lh, rh)]
-    l8 = store[0][1:1 + lh.numel()].view(lh.shape).copy_(lh)
-    r8 = store[1][3:3 + rh.numel()].view(rh.shape).copy_(rh)
-    n, pad, canary = B * S0 * S0 * 3, 1024, 0xA5
-    lib = L.load()
+    l8, r8 = _at_odd_addresses(lh, rh)
     for k, (rect_l, rect_r) in enumerate(_rects(H, W)):
         for mirror_l, mirror_r in ((0, 0), (0, 1)) if k % 2 else ((1, 0), (0, 0)):
-            flat = torch.full((2 * (n + pad) + pad,), canary, dtype=torch.uint8, device="cuda")
-            out_l, out_r = flat[pad:pad + n], flat[2 * pad + n:2 * pad + 2 * n]          # canaries in front of, between and behind the outputs
-            assert out_l.data_ptr() % 4 == 0 and out_r.data_ptr() % 4 == 0
-            rl = (C.c_int * 4)(*spec.check_resize_rect("t", rect_l, H, W))
-            rr = (C.c_int * 4)(*spec.check_resize_rect("t", rect_r, H, W))
-            L.check(lib.egotap_rgb_u8_resize(L.ptr(l8), L.ptr(r8), B, H, W, rl, rr, mirror_l, mirror_r, S0, L.ptr(out_l), L.ptr(out_r), L.stream()))
-            torch.cuda.synchronize()
+            got_l, got_r = (t.cpu() for t in _run_between_canaries(l8, r8, rect_l, rect_r, mirror_l, mirror_r, S0))
             want_l, want_r = spec.resize_u8(lh, rect_l, bool(mirror_l), S0), spec.resize_u8(rh, rect_r, bool(mirror_r), S0)
-            got_l, got_r = out_l.view(B, S0, S0, 3).cpu(), out_r.view(B, S0, S0, 3).cpu()
             assert torch.equal(got_l, want_l), (rect_l, mirror_l, int((got_l != want_l).sum()))
             assert torch.equal(got_r, want_r), (rect_r, mirror_r, int((got_r != want_r).sum()))
-            for lo, hi in ((0, pad), (pad + n, 2 * pad + n), (2 * pad + 2 * n, flat.numel())):
-                assert bool((flat[lo:hi] == canary).all()), (lo, hi)
     # the Python face: aligned frames, the same bytes
     a, b = L.rgb_u8_resize(lh.cuda(), rh.cuda(), S0, rect_right=_rects(H, W)[1][1], mirror_right=True)
     assert torch.equal(a.cpu(), spec.resize_u8(lh, None, False, S0)) and torch.equal(b.cpu(), spec.resize_u8(rh, _rects(H, W)[1][1], True, S0))
+
+
+def test_grid_stride_loop_takes_a_second_turn():
+    H, W, S0 = 7, 9, 64
+    B = 2 * torch.cuda.get_device_properties(0).multi_processor_count + 1          # the smallest batch with more thread groups than the grid holds
+    assert B * S0 * (S0 // 4) > 8 * torch.cuda.get_device_properties(0).multi_processor_count * 256 >= (B - 1) * S0 * (S0 // 4)
+    lh, rh = _frames8(9, B, H, W, 255)
+    l8, r8 = _at_odd_addresses(lh, rh)
+    rect_l, rect_r = (1, 0, 7, 6), None
+    for mirror_l, mirror_r in ((0, 1), (1, 0)):
+        got_l, got_r = _run_between_canaries(l8, r8, rect_l, rect_r, mirror_l, mirror_r, S0)
+        # (the restatement in torch integers on the device's copy of the same bytes: exact wherever it runs, and quick at this size)
+        assert torch.equal(got_l, spec.resize_u8(lh.cuda(), rect_l, bool(mirror_l), S0))
+        assert torch.equal(got_r, spec.resize_u8(rh.cuda(), rect_r, bool(mirror_r), S0))
 
 
 def test_operator_copies_exactly_when_the_rectangle_has_the_output_size():

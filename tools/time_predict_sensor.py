@@ -25,8 +25,10 @@ The lens entry beside the sensor entry on the same RGB frames (report only, noth
   sensor   predict_pose_from_sensor(mirror_right=True): the full frame resized
   lens     predict_pose_from_lens through the maps of calibration 0 of tests/golden/ocam.npz seen by itself, 0.02 rad about the axis apart, the right
            eye mirrored
-and, at B = 256, the two standalone kernels (egotap_rgb_u8_resize, egotap_lens_remap) timed with events, with the bytes per second each achieves
-counted the same way for both: per output pixel 3 bytes written and 12 source bytes for a pixel that has a source, plus the lens kernel's 8 map bytes."""
+and, at B = 256, the two standalone kernels in each of their three fetches (egotap_rgb_u8_resize / egotap_yuv_u8_resize on tight NV12 and YUYV frames,
+egotap_lens_remap on RGB8, NV12 and YUYV frames) timed with events, with the bytes per second each achieves counted the same way for all six: per
+output pixel 3 bytes written and 12 source bytes for a pixel that has a source, plus the lens kernel's 8 map bytes.  EGOTAP_LIB=<another build's .so>
+times that build with the same script (profiles/sensor_sources_summary.md: two builds alternating)."""
 from __future__ import annotations
 
 import argparse
@@ -185,20 +187,29 @@ def lens_rows(m, args, S0):
                 rows.append(row)
                 print(json.dumps(row), flush=True)
         B = 256
-        l8, r8 = sensor_frames(B, H, W)
         import ctypes as C
         lib, out_l, out_r = L.load(), torch.empty((B, S0, S0, 3), dtype=torch.uint8, device="cuda"), torch.empty((B, S0, S0, 3), dtype=torch.uint8, device="cuda")
-        full, desc = (C.c_int * 4)(0, 0, W, H), L.lens_source(maps)
-        ops = {"rgb_u8_resize": (lambda: L.check(lib.egotap_rgb_u8_resize(L.ptr(l8), L.ptr(r8), B, H, W, full, full, 0, 1, S0, L.ptr(out_l), L.ptr(out_r), L.stream())), 15.0),
-               "lens_remap": (lambda: L.check(lib.egotap_lens_remap(L.ptr(l8), L.ptr(r8), B, C.byref(desc), S0, L.ptr(out_l), L.ptr(out_r), L.stream())), 12.0 * share + 11.0)}
-        for name, (fn, per_pixel) in ops.items():
-            for _ in range(3):
-                fn()
-            ms = [kernel_ms(fn, args.reps) for _ in range(args.rounds)]
-            nbytes = 2.0 * B * S0 * S0 * per_pixel
-            print(json.dumps({"kernel": name, "source": f"{H}x{W}", "batch": B, "S0": S0, "rounds_ms": [round(v, 4) for v in ms],
-                              "median_ms": round(statistics.median(ms), 4), "counted_bytes": nbytes,
-                              "TB_per_s": round(nbytes / (statistics.median(ms) * 1e-3) / 1e12, 3)}), flush=True)
+        full, colour, outs = (C.c_int * 4)(0, 0, W, H), spec.YuvColour("bt601", "limited"), (L.ptr(out_l), L.ptr(out_r))
+        for fmt, layout in (("rgb8", None), ("nv12", spec.YuvLayout.nv12(H, W)), ("yuyv", spec.YuvLayout.yuyv(H, W))):
+            if layout is None:
+                l8, r8 = sensor_frames(B, H, W)
+                resize = lambda: L.check(lib.egotap_rgb_u8_resize(L.ptr(l8), L.ptr(r8), B, H, W, full, full, 0, 1, S0, *outs, L.stream()))
+            else:
+                g = torch.Generator().manual_seed(B + H + W + len(fmt))
+                l8, r8 = (torch.randint(0, 256, (B, layout.frame_stride), generator=g, dtype=torch.uint8).cuda() for _ in range(2))
+                ysrc = L.yuv_source(layout, colour)
+                resize = lambda: L.check(lib.egotap_yuv_u8_resize(L.ptr(l8), L.ptr(r8), B, C.byref(ysrc), full, full, 0, 1, S0, *outs, L.stream()))
+            desc = L.lens_source(maps, layout, colour if layout else None)
+            remap = lambda: L.check(lib.egotap_lens_remap(L.ptr(l8), L.ptr(r8), B, C.byref(desc), S0, *outs, L.stream()))
+            # (the same count for every fetch: 12 source bytes per pixel that has a source, whatever the format stores them in)
+            for name, fn, per_pixel in ((("rgb" if layout is None else "yuv") + "_u8_resize " + fmt, resize, 15.0), ("lens_remap " + fmt, remap, 12.0 * share + 11.0)):
+                for _ in range(3):
+                    fn()
+                ms = [kernel_ms(fn, args.reps) for _ in range(args.rounds)]
+                nbytes = 2.0 * B * S0 * S0 * per_pixel
+                print(json.dumps({"kernel": name, "source": f"{H}x{W}", "batch": B, "S0": S0, "rounds_ms": [round(v, 4) for v in ms],
+                                  "median_ms": round(statistics.median(ms), 4), "counted_bytes": nbytes,
+                                  "TB_per_s": round(nbytes / (statistics.median(ms) * 1e-3) / 1e12, 3)}), flush=True)
     return rows
 
 
