@@ -16,7 +16,8 @@
 // transposed block sit 64 bytes apart modulo 256).  The next key tile's global loads are in flight during the current
 // tile's MFMAs; conversion + LDS write sit between the two barriers, where the CU's second block keeps the pipe busy.
 #pragma once
-#include "gemm_tn_bf16.h"
+#include "common.h"
+#include "gemm_bf16.h"      // bf16x8, bf16x4, lds_bf16x4_ptr, bf16_split8, bf16_round8
 #include <math.h>
 
 template <int NW, int NP_>

@@ -3,8 +3,11 @@
 // for the input-gradient GEMMs).  All HBM-bound: 16-byte accesses, one pass over each tensor.
 // Reference semantics: nn.LayerNorm(1024, eps 1e-12) of model/modeling_vit.py:357-358, 367, 378, 609 and its autograd.
 #pragma once
-#include "gemm_bf16s.h"
-#include "train_ops.h"
+#include "common.h"
+#include "gemm_bf16.h"        // bf16x8
+#include "gemm_bf16s.h"       // store_bf16x8
+#include "gemm_tn_f32.h"      // colsum_partial_kernel, reduce_slabs_kernel
+#include "layernorm.h"        // wave_sum
 
 // ---------------------------------------------------------------------------------------------------- LayerNorm forward
 // one wave per row: y bf16 = (x - mean) * rstd * gamma + beta; mean / rstd kept for the backward (fp32)

@@ -13,7 +13,8 @@
 // The statistics are those of the bf16 values the normalisation then reads (under autocast the reference's BatchNorm likewise sees the
 // half-precision convolution output), accumulated in fp32 per thread (<= a few hundred values), folded in float64.
 #pragma once
-#include "gemm_bf16s.h"
+#include "common.h"
+#include "gemm_bf16.h"      // bf16x8
 
 // part[block][NC][2] = (sum, sum of squares) of rows [block * rows_per_block, ...) per column.  NC / 8 threads per row (16 bytes each).
 static __global__ __launch_bounds__(256) void bn_colstats_bf16s_kernel(const __bf16* __restrict__ z, long R, int NC, long rows_per_block,

@@ -17,7 +17,8 @@
 //     way in; on the way out one thread takes 8 channels of a pixel -- 16-byte residual load, ReLU, one rounding to bf16, 16-byte
 //     store: 8 lanes cover a pixel's 128 bytes.  Same fp32 formula as SEpiBnBf16 (conv_bf16s.h).
 #pragma once
-#include "conv_bf16s.h"
+#include "common.h"
+#include "gemm_bf16.h"      // bf16x8
 #include "lds_dma.h"
 
 struct Conv64Cfg {

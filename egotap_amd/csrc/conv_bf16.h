@@ -16,6 +16,7 @@
 // * epilogue = conv_f32.h's: BatchNorm(eval) or bias, residual, ReLU, 128-byte NCHW row segments with a caller-given image
 //   stride (concat-free).
 #pragma once
+#include "common.h"
 #include "conv_f32.h"
 #include "gemm_bf16.h"
 

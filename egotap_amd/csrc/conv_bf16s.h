@@ -16,8 +16,10 @@
 // Weights are repacked per call into [Cout][tap][Cp] bf16 (the parameters stay the caller's live fp32 tensors).  Producers write
 // straight into channel slices of the next concat buffer (row stride = the concat's channel count): no concat pass.
 #pragma once
+#include "common.h"
 #include "conv_pack_table.h"
 #include "conv_taps.h"
+#include "gemm_bf16.h"      // bf16x8
 #include "gemm_bf16s.h"
 
 // ---------------------------------------------------------------------------------------------------- loader

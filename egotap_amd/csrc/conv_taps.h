@@ -2,6 +2,7 @@
 // pointer and scalar-origin forms), stated once.  k = (channel slab, tap, channel in slab): a K-tile is ONE tap of one slab, the nine
 // taps of a slab are consecutive K-tiles, tap t = (dy + 1) * 3 + (dx + 1).
 #pragma once
+#include <hip/hip_runtime.h>
 // Output row m = (image n, yo, xo) of So x So maps, So = 1 << log2So; its centre tap is pixel (y, x) = (yo, xo) * stride of image n's S x S input
 // map, S = So * stride (STRIDED: a run-time stride; else stride 1).  Bit t of mask set: tap t lies inside the map (else the loader reads its
 // page of zeros: F.conv2d's padding).

@@ -48,13 +48,15 @@
 #include "gemm_bf16s.h"
 #include "gemm_bf16s64.h"
 #include "bf16s_ops.h"
-#include "attention_bf16s2.h"      // and attention_bf16s.h, which it includes: the launchers there call into it
+#include "attention_bf16s_fwd.h"
+#include "attention_bf16s_bwd.h"   // not launched from part 0: without it attention_bf16s3_kernel<4>, the serving forward, comes out in another schedule (profiles/kernel_headers_summary.md)
 #include "conv_bf16s.h"
 #include "stem_bf16s.h"
 #include "conv64_bf16s.h"
 #include "bn_bf16s.h"
 #include "rgb_u8.h"
-#include "frame_resize.h"          // and frame_source.h, which it and lens_remap.h include: the fetch, the blend and the store of both
+#include "frame_source.h"          // the fetch, the blend and the store that frame_resize.h and lens_remap.h share
+#include "frame_resize.h"
 #include "lens_remap.h"
 #include "heatmap_peaks.h"
 #include "limb_decode.h"
@@ -77,10 +79,11 @@
 #include "attention_bwd_bf16.h"
 #include "gemm_tn_f32.h"
 // Not launched from part 1, kept for the device code of attn_bwd_dq / _dk / _dv_bf16_kernel<4, 1> (attention_bwd_bf16.h), which it does launch:
-// attention_bf16s.h (behind attention_bf16s2.h) instantiates attn_bwd_dq_bf16s_kernel<4, 1> first, and clang emits the inline helpers the two share (attnbf::tile_x_frags<1>,
-// attnbf::acc_tile_t_x_p<1>) in order of first reference.  Without it they are emitted, and inlined, later, and the three kernels come out with the
-// same instructions in another schedule (profiles/abi_parts_summary.md).  Costs this part four kernels it does not launch.
-#include "attention_bf16s2.h"      // and attention_bf16s.h, which it includes: the launchers there call into it
+// attention_bf16s_bwd.h instantiates attn_bwd_dq_bf16s_kernel<4, 1>, and clang emits the inline helpers the two share (attnbf::tile_x_frags<1>,
+// attnbf::acc_tile_t_x_p<1> of attention_bf16_tiles.h) in order of first reference.  Without the two headers they are emitted, and inlined, later, and the three kernels
+// come out with the same instructions in another schedule (profiles/abi_parts_summary.md section 2).  Costs this part four kernels it does not launch.
+#include "attention_bf16s_fwd.h"
+#include "attention_bf16s_bwd.h"
 #endif
 #if EGOTAP_IN(2)
 #include "conv_f32.h"
@@ -93,7 +96,8 @@
 #include "gemm_bf16s64.h"
 #include "gemm_tn_bf16s.h"
 #include "bf16s_ops.h"
-#include "attention_bf16s2.h"      // and attention_bf16s.h, which it includes: the launchers there call into it
+#include "attention_bf16s_fwd.h"
+#include "attention_bf16s_bwd.h"
 #include "gemm_tn_f32.h"
 #endif
 #include "head_layout.h"      // the head's operand layouts the handle hands out

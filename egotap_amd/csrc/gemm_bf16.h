@@ -24,9 +24,12 @@
 // 32 fragments): a spill reload inside the slab loop is a vector-memory operation that the in-order vmcnt makes wait
 // for every older global load.
 #pragma once
+#include "common.h"
 #include "gemm_f32.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
 
 template <int NP_, int SCHED_ = 0>
 struct BfCfg {

@@ -15,7 +15,9 @@
 // Wave tiling, persistent XCD-aware tile walk and the epilogue functors are those of gemm_bf16_persist_kernel; the epilogue's
 // per-wave transpose patch is 16 rows (two passes per 32x32 block) to leave LDS for the fourth stage.
 #pragma once
+#include "common.h"
 #include "gemm_bf16.h"
+#include "gemm_f32.h"      // the loaders and epilogues (Col4, apply4, res4, epi_scatters)
 #include "lds_dma.h"
 
 struct DmaCfg {

@@ -27,7 +27,9 @@
 #pragma once
 #include <type_traits>
 
+#include "common.h"
 #include "gemm_bf16.h"
+#include "head_layout.h"
 #include "lds_dma.h"
 
 typedef __bf16 bf16x4s __attribute__((ext_vector_type(4)));

@@ -26,8 +26,11 @@
 #pragma once
 #include <type_traits>
 
+#include "common.h"
 #include "conv_taps.h"
+#include "gemm_bf16.h"      // bf16x8
 #include "gemm_bf16s.h"
+#include "head_layout.h"
 #include "lds_dma.h"
 
 struct S64Cfg {

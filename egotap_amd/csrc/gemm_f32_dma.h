@@ -8,6 +8,7 @@
 // k order per output element is that of every other fp32 tile: bit-identical results.
 #pragma once
 #include <type_traits>
+#include "common.h"
 #include "gemm_f32.h"
 #include "lds_dma.h"
 

@@ -13,11 +13,9 @@
 // M is split over blocks and the partial [N,K] slabs are summed in a fixed order by reduce_slabs_kernel, exactly like
 // gemm_tn_f32.h (bitwise reproducible, no float atomics).
 #pragma once
+#include "common.h"
 #include "gemm_bf16.h"
 #include "gemm_tn_f32.h"
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
 
 template <int NP_>
 struct TnBfCfg {

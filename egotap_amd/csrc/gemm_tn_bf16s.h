@@ -19,8 +19,10 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "gemm_bf16s.h"
-#include "gemm_tn_bf16.h"
+#include "common.h"
+#include "gemm_bf16.h"        // bf16x8, bf16x4, lds_bf16x4_ptr
+#include "gemm_tn_f32.h"      // reduce_slabs_kernel
+#include "head_layout.h"
 #include "lds_dma.h"
 
 struct TnSCfg {

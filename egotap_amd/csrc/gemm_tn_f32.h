@@ -11,7 +11,6 @@
 // no float atomics) and optionally accumulates into the existing gradient.
 #pragma once
 #include "common.h"
-#include "gemm_f32.h"
 #include "lds_dma.h"
 
 template <int BN_, int BK_, int BKM_, int WN_, int WK_>

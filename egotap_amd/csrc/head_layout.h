@@ -5,6 +5,7 @@
 // int members of the loaders / epilogues, in this order (their kernel-argument offsets).  spec.py states the same layouts in Python.
 // A caller that hipcc compiles differently through these functions keeps its own lines and says so (profiles/operand_layout_summary.md).
 #pragma once
+#include <hip/hip_runtime.h>
 // The ViT's input is the heatmaps tiled into one image: grid x grid cells of ppd x ppd patches (ppd = hm_size / 16), side = grid * ppd
 // patches per image row, seq = side^2 tokens, token (pr, pc) row-major.  Cell (pr / ppd) * grid + pc / ppd is heatmap `cell`; the cells
 // >= T (grid^2 > T) are dummies: no heatmap feeds them, the patch embedding puts the mask token there.  Reference:

@@ -15,7 +15,6 @@
 // skimage is not installed in the build container, so the line walk restates skimage 0.2x's _line_aa from its published
 // source (Zingl's anti-aliased Bresenham): parity of that step is unpinned; everything else is pinned (see oracle).
 #pragma once
-#include "common.h"
 #include "head_layout.h"
 
 struct GaussTaps { double w[9]; };

@@ -19,7 +19,9 @@
 //   * Max-pool padding: post-ReLU values are >= 0 and every window holds a valid element, so a zero column / row stands in for -inf.
 //     The last stem column of a segment is the left neighbour of the next one's first pooling window: carried in LDS.
 #pragma once
-#include "gemm_bf16s.h"
+#include "common.h"
+#include "gemm_bf16.h"       // bf16x8
+#include "gemm_bf16s.h"      // bf16x4s
 
 struct StemPoolCfg {
     static constexpr int R = 8, SR = 2 * R + 1, PR = 2 * SR + 5;       // pooled rows per item, stem rows, patch rows (39)

@@ -162,6 +162,51 @@ def test_no_part_sees_an_abi_helper_it_does_not_use(part):
         assert not unused
 
 
+_CSRC = os.path.join(REPO, "egotap_amd", "csrc")
+
+
+@pytest.mark.parametrize("header", sorted(f for f in os.listdir(_CSRC) if f.endswith(".h")))
+def test_every_kernel_header_stands_alone(header):
+    """A kernel header includes the project headers whose names it uses and relies on nobody's list: a two-line file (common.h, then the
+    header) passes the host-only syntax pass of test_no_part_sees_an_abi_helper_it_does_not_use, where a static launcher declared without
+    its definition is an error too.  The .inc bodies are text of their one includer and exempt."""
+    import subprocess
+    import tempfile
+    try:
+        hipcc = L._build._hipcc()
+    except RuntimeError:
+        pytest.skip("hipcc not found")
+    with tempfile.TemporaryDirectory() as tmp:
+        src = os.path.join(tmp, "alone.hip")
+        with open(src, "w") as f:
+            f.write(f'#include "common.h"\n#include "{header}"\n')
+        cmd = [hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"), "-I" + _CSRC,
+               "--cuda-host-only", "-fsyntax-only", "-Werror=undefined-internal", src]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-4000:]
+
+
+def _csrc_code():
+    return {f: re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(_CSRC, f)).read(), flags=re.S) for f in sorted(os.listdir(_CSRC))}
+
+
+def test_attention_tile_headers_hold_no_kernel():
+    """attention_bf16_tiles.h and attention_bf16s_tiles.h are what several attention families share (types, LDS images, tile products):
+    a part that lists one for a family it launches gets no kernel and no launcher with it."""
+    code = _csrc_code()
+    for f in ("attention_bf16_tiles.h", "attention_bf16s_tiles.h"):
+        assert "__global__" not in code[f] and "hipLaunchKernelGGL" not in code[f], f
+
+
+def test_no_launcher_is_declared_without_its_body():
+    """No file in csrc/ declares a static launcher that another file defines: every launcher stands after what it calls, so a header's
+    include lines alone say what it needs."""
+    declared = {f: re.findall(r"\bstatic\s+hipError_t\s+(\w+)\s*\([^(){};]*\)\s*;", t) for f, t in _csrc_code().items()}
+    assert not {f: d for f, d in declared.items() if d}
+    old = "static hipError_t a_launch(const __bf16* QKV, int B,\n        hipStream_t stream, float* colpart);\nstatic hipError_t b(int x) { return hipSuccess; }"
+    assert re.findall(r"\bstatic\s+hipError_t\s+(\w+)\s*\([^(){};]*\)\s*;", old) == ["a_launch"]      # the pattern sees a declaration, not a definition
+
+
 def _cfg(**kw):
     base = dict(n_joints_hm=15, estimate_head=1, hm_size=64, hidden=128, vit_dim=1024, vit_heads=8, vit_layers=3,
                 patch=16, pu_hidden=512)

@@ -157,7 +157,7 @@ def test_every_stage_of_the_bf16_step_against_its_own_inputs(preset, B):
         dxmb = d(t["dxmb"])
         gate("dW attention.output.dense", G[l + "attention.output.dense.weight"], dxmb.T @ d(L["ctx"]), 1e-4)
         gate("dctx", d(t["dctx"]), dxmb @ d(Wl["o_t"]).T, ULP)
-        # flash-style backward as the kernels compute it (csrc/attention_bf16s.h): P recomputed from q, k and the forward's log-sum-exp,
+        # flash-style backward as the kernels compute it (csrc/attention_bf16s_bwd.h): P recomputed from q, k and the forward's log-sum-exp,
         # delta = rowsum(dO * O) from the STORED (bf16) O, P and dS rounded to bf16 where they become MFMA operands
         dh = D // heads
         qh, kh, vh = (d(L["qkv"])[:, j * D:(j + 1) * D].view(B, seq, heads, dh).transpose(1, 2) for j in range(3))

@@ -240,7 +240,7 @@ def test_attention_fwd_bwd_bf16(B, N):
 
 @pytest.mark.parametrize("B,N", [(2, 576), (1, 96)])
 def test_attention_forward_running_maximum_rescale_with_a_pending_tile(B, N):
-    """The forward defers P V of a key tile by one step and runs it under the next tile's exponentials (attention_bf16s2.h); the running
+    """The forward defers P V of a key tile by one step and runs it under the next tile's exponentials (attention_bf16s_fwd.h); the running
     maximum is raised only when a tile exceeds it by 2^6.  On bounded random scores that branch fires at the first tile only, so a passing
     random test says nothing about it (cdna_hip_programming.md T13: nothing pending may be left at the old scale).  Here the scores of a row
     GROW along the keys by `slope` per key in log2 units -- a rescale at every tile with the previous tile's P V still pending (slope 0.5, 2),

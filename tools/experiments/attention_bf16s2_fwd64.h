@@ -1,7 +1,7 @@
 // RETIRED from the shipped library in round 4 (kept for the record; not compiled): the 64-key-step forward of the DMA-staged bf16 attention
 // (generation 2) and its launcher.  Same-box A/B against the 32-key, three-workgroups-per-CU forward that ships (attention_bf16s3_kernel):
 // 2.10 -> 1.74 ms per layer at B = 1024, N = 576; 0.90 -> 1.04 PF at N = 2304; bit-identical context and log-sum-exp
-// (tools/attn_fwd_gen_probe.py, round 3).  Needs the helpers of egotap_amd/csrc/attention_bf16s2.h (namespace att2).
+// (tools/attn_fwd_gen_probe.py, round 3).  Needs the helpers of egotap_amd/csrc/attention_bf16s_tiles.h (namespace att2) and imgT_x_ph / store_rows_bf16 of attention_bf16s_fwd.h / _tiles.h.
 // ------------------------------------------------------------------------------------------------- forward, generation 2
 // S^T = K Q^T (K rows from the image, Q^T in registers), online softmax per lane (the query is the lane), O^T += V^T P^T (V transposed
 // from its image, the probability accumulators as the B operand where they stand).  64 keys per step, staged as in the dQ kernel.
@@ -11,7 +11,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_bf16s2_kernel(const __bf
     using namespace att2;
     static_assert(NW == 4, "four waves share the DMA duty of a 64-key step");
     constexpr unsigned KVBUF = 4 * TILEB;
-    constexpr float RESC = 6.0f;                               // deferred running-maximum update (attention_bf16s.h)
+    constexpr float RESC = 6.0f;                               // deferred running-maximum update (attention_bf16s_fwd.h)
     extern __shared__ __attribute__((aligned(16))) char sm2[];
     const int lin = xcd_lin(blockIdx.x, gridDim.x);
     const int bh = lin / qgroups, qg = lin - bh * qgroups;

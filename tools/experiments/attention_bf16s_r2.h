@@ -1,7 +1,7 @@
 // RETIRED from the shipped library in round 4 (kept for the record; not compiled).  Round 2's register-staged bf16-storage attention kernels:
 // forward (`attention_bf16s_kernel`), dQ (`attn_bwd_dq_bf16s_kernel`, whose 32-key instantiation still ships as the fallback for sequence
 // lengths that are not a multiple of 64) and dK + dV (`attn_bwd_dkv_bf16s_kernel`).  Same-box A/B against the DMA-staged kernels of
-// attention_bf16s2.h at B = 1024, N = 576 (round 3, profiles/r03_config3_summary.md): forward 2.35 -> 1.74-1.80 ms,
+// attention_bf16s_fwd.h / attention_bf16s_bwd.h at B = 1024, N = 576 (round 3, profiles/r03_config3_summary.md): forward 2.35 -> 1.74-1.80 ms,
 // dQ 3.0 -> 2.6 ms, dK + dV 4.87 -> 3.25 ms per layer; bit-identical outputs (max |gen 1 - gen 2| = 0 on 450 M elements).
 // Fused softmax attention with bf16 tensors in HBM (bf16-storage training mode, EGOTAP_PREC_BF16):
 //   forward   ctx = softmax(Q K^T / sqrt(128)) V                                   (model/modeling_vit.py:226-252)
@@ -355,8 +355,8 @@ static hipError_t attention_bf16s_fwd_launch_t(const __bf16* QKV, __bf16* CTX, f
     hipLaunchKernelGGL(kern, dim3(B * heads * qgroups), dim3(64 * NW), lds, stream, QKV, CTX, N, heads, qgroups, 1.4426950408889634f / sqrtf(128.0f), LSE);
     return hipGetLastError();
 }
-static hipError_t attention_bf16s2_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream);      // attention_bf16s2.h
-static hipError_t attention_bf16s3_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream);      // attention_bf16s2.h
+static hipError_t attention_bf16s2_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream);      // attention_bf16s2_fwd64.h
+static hipError_t attention_bf16s3_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream);      // egotap_amd/csrc/attention_bf16s_fwd.h
 static hipError_t attention_bf16s_fwd_launch(const __bf16* QKV, __bf16* CTX, float* LSE, int B, int N, int heads, hipStream_t stream, int gen = 3) {
     if (B <= 0) return hipSuccess;
     if (N % 32 != 0) return hipErrorInvalidValue;
@@ -366,7 +366,7 @@ static hipError_t attention_bf16s_fwd_launch(const __bf16* QKV, __bf16* CTX, flo
 }
 
 static hipError_t attention_bf16s2_dkv_launch(const __bf16* QKV, const __bf16* dO, const float* LSE, const float* DELTA, __bf16* dQKV, int B, int N,
-                                              int heads, hipStream_t stream, float* colpart);      // attention_bf16s2.h
+                                              int heads, hipStream_t stream, float* colpart);      // egotap_amd/csrc/attention_bf16s_bwd.h
 static hipError_t attention_bf16s2_dq_launch(const __bf16* QKV, const __bf16* O, const __bf16* dO, const float* LSE, float* DELTA, __bf16* dQKV, int B, int N,
                                              int heads, hipStream_t stream, float* colpart);
 
