@@ -64,6 +64,7 @@
 #include "pose_track.h"
 #include "skeleton_fit.h"
 #include "stereo_fuse.h"
+#include "overlay.h"               // last: its entries stand at the end of part 0's text, so no other kernel is referenced later than before
 #endif
 #if EGOTAP_IN(1)
 #include "attention_f32.h"
@@ -3867,5 +3868,86 @@ extern "C" int egotap_lift_backward_dhm(egotap_handle h, const float* hm, const 
         EGO_CHECK(a + bytes <= b || b + bytes <= a, "egotap_lift_backward_dhm: dhm must not overlap hm");
     }
     return lift_backward_impl("egotap_lift_backward_dhm", h, hm, dpose, B, saved, saved_bytes, ws, ws_bytes, bucket_events, n_events, stream, dhm);
+}
+
+// ---- heatmaps, keypoints and bones drawn onto the frames (overlay.h): two operators, no handle
+extern "C" int egotap_heat_u8(const void* hm, int dtype, int B, int C, int S, int64_t image_stride, int c0, int n, int groups, uint8_t* heat8, void* stream) {
+    static const char* const who = "egotap_heat_u8";
+    EGO_CHECK(hm && heat8, "%s: null argument (hm and heat8 are required)", who);
+    EGO_CHECK(dtype == EGOTAP_F32 || dtype == EGOTAP_BF16, "%s: unknown dtype %d (EGOTAP_F32 or EGOTAP_BF16)", who, dtype);
+    EGO_CHECK(B > 0, "%s: the batch must be positive (B = %d)", who, B);
+    EGO_CHECK(n >= 1, "%s: the number of channels must be at least 1 (n = %d)", who, n);
+    EGO_CHECK(groups >= 1 && n % groups == 0, "%s: n must be a multiple of groups >= 1 (n = %d, groups = %d)", who, n, groups);
+    EGO_CHECK(c0 >= 0 && (int64_t)c0 + n <= C, "%s: channels c0 .. c0 + n - 1 = %d .. %lld are not inside the C = %d channels", who, c0, (long long)c0 + n - 1, C);
+    EGO_CHECK(S > 0 && S % 16 == 0 && S <= kOverlayMaxHeatSide, "%s: the side must be a positive multiple of 16, at most %d (S = %d)", who, kOverlayMaxHeatSide, S);
+    const int esz = dtype == EGOTAP_F32 ? 4 : 2;
+    EGO_CHECK(image_stride >= (int64_t)C * S * S, "%s: image_stride %lld is smaller than C * S*S = %lld", who, (long long)image_stride, (long long)C * S * S);
+    EGO_CHECK(image_stride * esz % 16 == 0, "%s: image_stride must be a multiple of 16 bytes (%lld elements of %d bytes)", who, (long long)image_stride, esz);
+    EGO_CHECK(((uintptr_t)hm & 15) == 0 && ((uintptr_t)heat8 & 7) == 0, "%s: hm must be 16-byte aligned, heat8 8-byte aligned", who);
+    const size_t in_bytes = ((size_t)(B - 1) * image_stride + (size_t)C * S * S) * esz, out_bytes = (size_t)B * groups * S * S;
+    EGO_CHECK(!ego_overlap(heat8, out_bytes, hm, in_bytes), "%s: heat8 overlaps hm", who);
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "heat_u8", "heat_u8_kernel", 0.0);
+    EGO_HIP(dtype == EGOTAP_F32 ? heat_u8_launch((const float*)hm, B, S, (long)image_stride, c0, n, groups, heat8, (hipStream_t)stream)
+                                : heat_u8_launch((const __bf16*)hm, B, S, (long)image_stride, c0, n, groups, heat8, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+
+extern "C" int egotap_overlay_u8(const uint8_t* left8, const uint8_t* right8, int B, int Hc, int Wc, const uint8_t* heat8, int S, const int32_t* tx_left,
+                                 const int32_t* ty_left, const int32_t* tx_right, const int32_t* ty_right, const float* marks, const egotap_overlay_style* style,
+                                 uint8_t* out_left8, uint8_t* out_right8, void* stream) {
+    static const char* const who = "egotap_overlay_u8";
+    EGO_CHECK(left8 && out_left8 && style, "%s: null argument (left8, out_left8 and style are required)", who);
+    EGO_CHECK((right8 == nullptr) == (out_right8 == nullptr), "%s: right8 and out_right8 are both given or both NULL (one eye)", who);
+    const int E = right8 ? 2 : 1;
+    EGO_CHECK(B > 0 && B <= 65535, "%s: the batch must be between 1 and 65535 (B = %d)", who, B);
+    EGO_CHECK(Hc >= 1 && Wc >= 4 && Wc % 4 == 0 && Hc <= kOverlayMaxSide && Wc <= kOverlayMaxSide,
+              "%s: the canvas must be 1 .. %d rows of 4 .. %d pixels, the width a multiple of 4 (Hc = %d, Wc = %d)", who, kOverlayMaxSide, kOverlayMaxSide, Hc, Wc);
+    EGO_CHECK((((uintptr_t)left8 | (uintptr_t)right8 | (uintptr_t)out_left8 | (uintptr_t)out_right8) & 3) == 0, "%s: every canvas must be 4-byte aligned", who);
+    if (heat8) {
+        EGO_CHECK(S >= 1 && S <= kOverlayMaxHeatSide, "%s: the heat side must be between 1 and %d (S = %d)", who, kOverlayMaxHeatSide, S);
+        EGO_CHECK(tx_left && ty_left && (E == 1 || (tx_right && ty_right)), "%s: with heat8 every drawn eye needs its two tap tables (tx, ty)", who);
+        EGO_CHECK((((uintptr_t)tx_left | (uintptr_t)(E == 2 ? tx_right : nullptr)) & 15) == 0 && (((uintptr_t)ty_left | (uintptr_t)(E == 2 ? ty_right : nullptr)) & 3) == 0,
+                  "%s: the x tap tables must be 16-byte aligned, the y tap tables 4-byte aligned", who);
+    }
+    const egotap_overlay_style& q = *style;
+    EGO_CHECK(q.r16 >= 0 && q.r16 <= kOverlayMaxR16 && q.w16 >= 0 && q.w16 <= kOverlayMaxR16, "%s: style: r16 and w16 must be between 0 and %d (%d, %d)", who,
+              kOverlayMaxR16, q.r16, q.w16);
+    EGO_CHECK(q.min_score == q.min_score, "%s: style: min_score must not be NaN", who);
+    egotap_overlay_style st = q;
+    if (marks) {
+        EGO_CHECK(((uintptr_t)marks & 15) == 0, "%s: marks must be 16-byte aligned", who);
+        EGO_CHECK(q.n_marks >= 1 && q.n_marks <= EGOTAP_OVERLAY_MAX, "%s: style: n_marks must be between 1 and %d (%d)", who, EGOTAP_OVERLAY_MAX, q.n_marks);
+        EGO_CHECK(q.n_bones >= 0 && q.n_bones <= EGOTAP_OVERLAY_MAX, "%s: style: n_bones must be between 0 and %d (%d)", who, EGOTAP_OVERLAY_MAX, q.n_bones);
+        for (int l = 0; l < q.n_bones; ++l)
+            EGO_CHECK(q.bones[l][0] < q.n_marks && q.bones[l][1] < q.n_marks, "%s: style: bone %d joins marks %d and %d, outside 0 .. %d", who, l, q.bones[l][0],
+                      q.bones[l][1], q.n_marks - 1);
+    } else {
+        st.n_marks = st.n_bones = 0;
+    }
+    const size_t canvas = (size_t)B * Hc * Wc * 3;
+    const struct {
+        const char* name;
+        const void* p;
+        size_t n;
+    } arg[10] = {{"left8", left8, canvas},
+                 {"right8", right8, canvas},
+                 {"out_left8", out_left8, canvas},
+                 {"out_right8", out_right8, canvas},
+                 {"heat8", heat8, heat8 ? (size_t)B * E * S * S : 0},
+                 {"tx_left", heat8 ? tx_left : nullptr, (size_t)Wc * 4},
+                 {"ty_left", heat8 ? ty_left : nullptr, (size_t)Hc * 4},
+                 {"tx_right", heat8 && E == 2 ? tx_right : nullptr, (size_t)Wc * 4},
+                 {"ty_right", heat8 && E == 2 ? ty_right : nullptr, (size_t)Hc * 4},
+                 {"marks", marks, marks ? (size_t)B * E * st.n_marks * 16 : 0}};
+    for (int i = 0; i < 10; ++i)
+        for (int j = i + 1; j < 10; ++j) {
+            if ((i == 0 && j == 2 && out_left8 == left8) || (i == 1 && j == 3 && out_right8 == right8)) continue;      // in place
+            EGO_CHECK(!ego_overlap(arg[i].p, arg[i].n, arg[j].p, arg[j].n), "%s: %s overlaps %s", who, arg[j].name, arg[i].name);
+        }
+    const OverlayEye el{left8, out_left8, heat8 ? tx_left : nullptr, heat8 ? ty_left : nullptr};
+    const OverlayEye er{right8, out_right8, heat8 && E == 2 ? tx_right : nullptr, heat8 && E == 2 ? ty_right : nullptr};
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "overlay_u8", "overlay_u8_kernel", 0.0);
+    EGO_HIP(overlay_u8_launch(el, er, E, B, Hc, Wc, heat8, S, marks, st, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
 }
 #endif

@@ -48,6 +48,11 @@ class EgotapSkeletonTwist(C.Structure):               # egotap.h egotap_skeleton
     _fields_ = [("pole", C.c_int32 * 64), ("hinge", (C.c_double * 3) * 64), ("bend_lo", C.c_double), ("bend_hi", C.c_double)]
 
 
+class EgotapOverlayStyle(C.Structure):                # egotap.h egotap_overlay_style: 664 bytes
+    _fields_ = [(n, C.c_int32) for n in ("n_marks", "n_bones", "r16", "w16")] + [("min_score", C.c_float), ("heat_rgba", C.c_uint8 * 4),
+                ("bones", (C.c_uint8 * 2) * 64), ("mark_rgba", (C.c_uint8 * 4) * 64), ("bone_rgba", (C.c_uint8 * 4) * 64)]
+
+
 class EgotapYuvSource(C.Structure):                   # egotap.h egotap_yuv_source: seven int32 (then padding) and two int64
     _fields_ = [(n, C.c_int32) for n in ("struct_size", "format", "matrix", "range", "H", "W", "pitch")] + [("uv_offset", C.c_int64), ("frame_stride", C.c_int64)]
 
@@ -136,6 +141,12 @@ _PROTOS = {
     "egotap_stereo_fuse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapOcam), C.POINTER(EgotapOcam), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(EgotapFuseParams), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    # ---- heatmaps, keypoints and bones drawn onto the frames: two operators, no handle
+    # (hm, dtype, B, C, S, image_stride, c0, n, groups, heat8, stream)
+    "egotap_heat_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # (left8, right8, B, Hc, Wc, heat8, S, tx_left, ty_left, tx_right, ty_right, marks, style, out_left8, out_right8, stream)
+    "egotap_overlay_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.POINTER(EgotapOverlayStyle), C.c_void_p, C.c_void_p, C.c_void_p]),
     # ---- the pose, the root and the stereo joints filtered over time: one operator, no handle
     "egotap_pose_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.POINTER(EgotapTrackParams),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -887,6 +898,113 @@ def _pose_track_args(who, pose, state, dt, dts, params, frame, joints3d, streams
     if dt is not None and not (float(dt) > 0 and float(dt) != float("inf")):
         raise ValueError(f"{who}: dt must be finite and > 0, got {dt}")
     return prm, T, S, P, J
+
+
+def heat_u8(hm, c0: int = 0, n=None, groups: int = 1):
+    """The reference's picture of a heatmap stack per group of channels (egotap_heat_u8, ``spec.heat_u8``, bit for bit): hm [B, C, S, S], float32 or
+    bfloat16 on the GPU, also a dim-1 slice of a larger contiguous tensor (read in place) -> uint8 [B, groups, S, S]: channels c0 .. c0 + n - 1
+    (None: all from c0 on) in ``groups`` groups of consecutive channels, each added up, clamped to [0, 1] and scaled to a byte.  One launch."""
+    import torch
+    if not torch.is_tensor(hm):
+        raise EgotapError("heat_u8 takes a torch tensor on the GPU")
+    if hm.dtype not in (torch.float32, torch.bfloat16):
+        raise EgotapError(f"heat_u8 takes float32 or bfloat16 maps, got {hm.dtype}")
+    if hm.dim() != 4 or hm.shape[2] != hm.shape[3]:
+        raise ValueError(f"heat_u8: maps are [B, C, S, S], got {tuple(hm.shape)}")
+    B, Cn, S, _ = (int(v) for v in hm.shape)
+    c0, groups = int(c0), int(groups)
+    n = Cn - c0 if n is None else int(n)
+    if c0 < 0 or n < 1 or c0 + n > Cn or groups < 1 or n % groups:
+        raise ValueError(f"heat_u8: channels {c0} .. {c0 + n - 1} in {groups} groups are not a slice of the {Cn} channels in equal groups")
+    if B > 0 and (hm.stride(3) != 1 or hm.stride(2) != S or hm.stride(1) != S * S or (B > 1 and hm.stride(0) < Cn * S * S)):
+        raise EgotapError("heat_u8: the maps must be contiguous per image (a dim-1 slice of a contiguous tensor is; nothing is copied)")
+    if not hm.is_cuda:                                   # (after the argument checks, so those can be exercised without a GPU)
+        raise EgotapError("heat_u8 runs on the GPU only (no CPU fallback); move the maps to cuda")
+    out = torch.empty((B, groups, S, S), dtype=torch.uint8, device=hm.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(hm.device):
+        check(load().egotap_heat_u8(_ptr(hm), F32 if hm.dtype == torch.float32 else BF16, B, Cn, S, hm.stride(0) if B > 1 else Cn * S * S, c0, n, groups,
+                                    _ptr(out), _stream(hm.device)))
+    return out
+
+
+def overlay_style_struct(style) -> EgotapOverlayStyle:
+    """a ``spec.OverlayStyle`` as the ABI takes it (egotap_overlay_style, by pointer to host memory)"""
+    from . import spec
+    if not isinstance(style, spec.OverlayStyle):
+        raise ValueError(f"overlay_u8: style is a spec.OverlayStyle (spec.overlay_style(joint_preset) makes a preset's), got {type(style).__name__}")
+    o = EgotapOverlayStyle()
+    o.n_marks, o.n_bones, o.r16, o.w16, o.min_score = len(style.mark_rgba), len(style.bones), style.r16, style.w16, style.min_score
+    o.heat_rgba[:] = style.heat_rgba
+    for l, (i, j) in enumerate(style.bones):
+        o.bones[l][:] = (i, j)
+        o.bone_rgba[l][:] = style.bone_rgba[l]
+    for j, c in enumerate(style.mark_rgba):
+        o.mark_rgba[j][:] = c
+    return o
+
+
+def overlay_tap_tables(affine, S: int, Hc: int, Wc: int, device):
+    """the heat layer's tap tables of one eye on ``device``: (tx int32 [Wc], ty int32 [Hc]) from the eye's keypoint affine (ax, bx, ay, by)
+    (``spec.overlay_taps``, built on the host in float64)"""
+    import torch
+    from . import spec
+    ax, bx, ay, by = (float(v) for v in affine)
+    return (torch.from_numpy(spec.overlay_taps(ax, bx, S, Wc)).to(device), torch.from_numpy(spec.overlay_taps(ay, by, S, Hc)).to(device))
+
+
+def overlay_u8(left8, right8, style, marks=None, heat8=None, taps=None, out=None):
+    """Three layers blended onto packed RGB8 canvases (egotap_overlay_u8, ``spec.overlay_u8``, equal in every byte): left8 / right8 uint8
+    [B, Hc, Wc, 3] on the GPU (``right8`` None: one eye, E = 1; else E = 2), Wc a multiple of 4 -> (out_left, out_right or None).  ``style`` a
+    ``spec.OverlayStyle``; ``marks`` float32 [B, E, M, 4] = (x, y, score, _) in canvas pixels with M the style's number of marks (None: neither marks nor
+    bones); ``heat8`` uint8 [B, E, S, S] (``heat_u8`` with groups = E) with ``taps`` = per eye (tx, ty) from ``overlay_tap_tables`` (None: no heat);
+    ``out`` = (out_left, out_right) to write into -- the inputs themselves draw in place -- or None for new tensors.  One launch."""
+    import torch
+    who = "overlay_u8"
+    prm = overlay_style_struct(style)
+    eyes = [left8] if right8 is None else [left8, right8]
+    E = len(eyes)
+    for t in eyes:
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape != left8.shape:
+            raise ValueError(f"{who}: canvases are uint8 tensors [B, Hc, Wc, 3] of one shape, got {[tuple(getattr(e, 'shape', ())) for e in eyes]}")
+    B, Hc, Wc, _ = (int(v) for v in left8.shape)
+    if Wc % 4 or Wc < 4 or Hc < 1 or Hc > 16384 or Wc > 16384:
+        raise ValueError(f"{who}: a canvas is 1 .. 16384 rows of 4 .. 16384 pixels, the width a multiple of 4, got {Hc} x {Wc}")
+    M = len(style.mark_rgba)
+    if marks is None:
+        if M or style.bones:
+            raise ValueError(f"{who}: the style has {M} marks and {len(style.bones)} bones and no marks are given")
+    elif not torch.is_tensor(marks) or tuple(marks.shape) != (B, E, M, 4):
+        raise ValueError(f"{who}: marks are a tensor [B, E, M, 4] = {(B, E, M, 4)} with M the style's marks, got {tuple(getattr(marks, 'shape', ()))}")
+    S = 0
+    if heat8 is not None:
+        if not torch.is_tensor(heat8) or heat8.dtype != torch.uint8 or heat8.dim() != 4 or tuple(heat8.shape[:2]) != (B, E) or heat8.shape[2] != heat8.shape[3]:
+            raise ValueError(f"{who}: heat8 is a uint8 tensor [B, E, S, S] with (B, E) = {(B, E)}, got {tuple(getattr(heat8, 'shape', ()))}")
+        S = int(heat8.shape[2])
+        if taps is None or len(taps) != E or any(tuple(tx.shape) != (Wc,) or tuple(ty.shape) != (Hc,) or tx.dtype != torch.int32 or ty.dtype != torch.int32
+                                                 for tx, ty in taps):
+            raise ValueError(f"{who}: with heat8, taps are per eye (tx int32 [{Wc}], ty int32 [{Hc}]) from overlay_tap_tables")
+    if out is not None:
+        out = list(out) + [None] * (2 - len(out))
+        if any(not torch.is_tensor(o) or o.dtype != torch.uint8 or o.shape != left8.shape for o in out[:E]) or (E == 1 and out[1] is not None):
+            raise ValueError(f"{who}: out is (out_left, out_right) of the canvases' dtype and shape, out_right None for one eye")
+    tensors = eyes + [t for t in (marks, heat8) if t is not None] + [t for pair in (taps if heat8 is not None else ()) for t in pair] + (out[:E] if out else [])
+    if not all(t.is_cuda and t.device == left8.device for t in tensors):
+        raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); every tensor on one cuda device")
+    if not all(t.is_contiguous() for t in tensors if t is not marks):
+        raise EgotapError(f"{who}: the canvases, heat8, the tap tables and out must be contiguous (the bytes are read and written in place)")
+    mk = _f32c(marks)
+    if out is None:
+        out = [torch.empty_like(t) for t in eyes] + [None] * (2 - E)
+    if B == 0:
+        return out[0], out[1]
+    tl = taps[0] if heat8 is not None else (None, None)
+    tr = taps[1] if heat8 is not None and E == 2 else (None, None)
+    with torch.cuda.device(left8.device):
+        check(load().egotap_overlay_u8(_ptr(left8), _ptr(right8), B, Hc, Wc, _ptr(heat8), S, _ptr(tl[0]), _ptr(tl[1]), _ptr(tr[0]), _ptr(tr[1]), _ptr(mk),
+                                       C.byref(prm), _ptr(out[0]), _ptr(out[1]), _stream(left8.device)))
+    return out[0], out[1]
 
 
 def _on_one_gpu(pose, *others):

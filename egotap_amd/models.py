@@ -236,6 +236,90 @@ class Skeleton:
             self._state[idx] = 0.0
 
 
+class Overlay:
+    """What the estimators saw and found, drawn onto the frames on the device (``lib.heat_u8``, ``lib.overlay_u8``; egotap_heat_u8, egotap_overlay_u8;
+    ``spec.heat_u8``, ``spec.overlay_u8``): the position heatmaps as a tinted layer, the limbs and the skeleton's bones as lines, the keypoints as discs.
+    Made by ``model.new_overlay``; holds no reference to the model or its graphs.  It keeps the heat layer's tap tables per (affine, S, Hc, Wc) and
+    nothing else between frames."""
+
+    def __init__(self, n_joints, style):
+        if not isinstance(style, _spec.OverlayStyle) or len(style.mark_rgba) != int(n_joints):
+            raise ValueError(f"Overlay: style is a spec.OverlayStyle with one mark per heatmap joint ({n_joints}), got {style!r}")
+        self.J, self.style = int(n_joints), style
+        self._taps, self._styles = {}, {}
+
+    def style_for(self, keypoints: bool, limbs: bool):
+        """the style of one draw: the keypoints' marks and bones (``self.style``) and / or, per limb, two end marks that are not drawn themselves
+        (alpha 0) and one bone between them in the colour of the limb's joint; the limbs' bones come after the skeleton's"""
+        key = (bool(keypoints), bool(limbs))
+        if key not in self._styles:
+            s, J = self.style, self.J
+            marks, bones, bcol = (s.mark_rgba, s.bones, s.bone_rgba) if keypoints else ((), (), ())
+            if limbs:
+                base = len(marks)
+                marks = marks + tuple(c[:3] + (0,) for c in s.mark_rgba for _ in range(2))
+                bones = bones + tuple((base + 2 * l, base + 2 * l + 1) for l in range(J))
+                bcol = bcol + s.mark_rgba
+            self._styles[key] = _spec.OverlayStyle(bones=bones, mark_rgba=marks, bone_rgba=bcol, r16=s.r16, w16=s.w16, min_score=s.min_score, heat_rgba=s.heat_rgba)
+        return self._styles[key]
+
+    @torch.no_grad()
+    def marks(self, keypoints=None, limbs=None, eyes=2):
+        """the marks of one draw, float32 [B, eyes, M, 4] (None without keypoints and limbs): the keypoint records as they are, then per limb
+        (x, y) -+ length / 2 (cos phi, sin phi) with the limb's peak as the score -- computed with torch, inputs of the kernel"""
+        parts = []
+        if keypoints is not None:
+            if not torch.is_tensor(keypoints) or keypoints.dim() != 4 or tuple(keypoints.shape[1:]) != (2, self.J, 4):
+                raise ValueError(f"Overlay.draw: keypoints are a tensor [B, 2, {self.J}, 4], got {tuple(getattr(keypoints, 'shape', ()))}")
+            parts.append(keypoints[:, :eyes].float())
+        if limbs is not None:
+            if not torch.is_tensor(limbs) or limbs.dim() != 4 or tuple(limbs.shape[1:]) != (2, self.J, 8):
+                raise ValueError(f"Overlay.draw: limbs are a tensor [B, 2, {self.J}, 8], got {tuple(getattr(limbs, 'shape', ()))}")
+            lb = limbs[:, :eyes].float()
+            half = 0.5 * lb[..., 5]
+            hx, hy = half * torch.cos(lb[..., 4]), half * torch.sin(lb[..., 4])
+            zero = torch.zeros_like(hx)
+            ends = torch.stack([torch.stack([lb[..., 2] - hx, lb[..., 3] - hy, lb[..., 6], zero], dim=-1),
+                                torch.stack([lb[..., 2] + hx, lb[..., 3] + hy, lb[..., 6], zero], dim=-1)], dim=3)      # [B, eyes, J, 2, 4]
+            parts.append(ends.reshape(lb.shape[0], lb.shape[1], 2 * self.J, 4))
+        return torch.cat(parts, dim=2).contiguous() if parts else None
+
+    def taps(self, affine, S, Hc, Wc, device, eyes=2):
+        """the heat layer's tap tables, per eye (tx, ty), cached: ``affine`` None for the camera entries' keypoints (pixels of the 4S x 4S frame: x 4),
+        "identity" for a canvas of the maps' own side, or per eye (ax, bx, ay, by) -- ``spec.sensor_keypoint_affine(...)`` for sensor frames"""
+        if affine is None:
+            affine = ((4.0, 0.0, 4.0, 0.0),) * 2
+        elif isinstance(affine, str):
+            if affine != "identity":
+                raise ValueError(f'Overlay.draw: affine is None, "identity" or per eye (ax, bx, ay, by), got {affine!r}')
+            affine = ((1.0, 0.0, 1.0, 0.0),) * 2
+        affine = tuple(tuple(float(v) for v in a) for a in affine)
+        if len(affine) != 2 or any(len(a) != 4 for a in affine):
+            raise ValueError(f"Overlay.draw: affine is per eye (ax, bx, ay, by), two eyes, got {affine!r}")
+        key = (affine[:eyes], int(S), int(Hc), int(Wc), str(device))
+        if key not in self._taps:
+            self._taps[key] = tuple(_lib.overlay_tap_tables(a, S, Hc, Wc, device) for a in affine[:eyes])      # (one table per eye: no two arguments alias)
+        return self._taps[key]
+
+    @torch.no_grad()
+    def draw(self, left8, right8, keypoints=None, heatmaps=None, limbs=None, affine=None, out=None):
+        """``left8`` / ``right8`` uint8 [B, Hc, Wc, 3] on the GPU (``right8`` None: the left eye alone) and the tensors a ``predict_pose_from_*`` call
+        returned -- ``keypoints`` [B, 2, J, 4] and ``limbs`` [B, 2, J, 8] in the canvases' pixels, ``heatmaps`` [B, 6J, S, S] (its 2J position channels
+        are drawn, through ``lib.heat_u8``) -> (out_left, out_right or None).  ``affine``: see ``taps``; it places the heat layer only, the keypoints
+        and limbs are already canvas pixels.  ``out`` = (out_left, out_right) to write into, the canvases themselves to draw in place, None for new
+        tensors.  One launch, two with heatmaps, on the current stream; no synchronisation."""
+        E = 1 if right8 is None else 2
+        style = self.style_for(keypoints is not None, limbs is not None)
+        marks = self.marks(keypoints, limbs, E)
+        heat8 = taps = None
+        if heatmaps is not None:
+            if not torch.is_tensor(heatmaps) or heatmaps.dim() != 4 or heatmaps.shape[1] < 2 * self.J:
+                raise ValueError(f"Overlay.draw: heatmaps are a tensor [B, C >= {2 * self.J}, S, S], got {tuple(getattr(heatmaps, 'shape', ()))}")
+            heat8 = _lib.heat_u8(heatmaps, 0, E * self.J, E)
+            taps = self.taps(affine, heatmaps.shape[2], left8.shape[1], left8.shape[2], heat8.device, E)
+        return _lib.overlay_u8(left8, right8, style, marks=marks, heat8=heat8, taps=taps, out=out)
+
+
 class _Source(NamedTuple):
     """What is specific to one serving entry (predict_pose_from_rgb / _camera / _sensor / _sensor_yuv / _lens); everything else about a request is ``_serve``'s."""
     who: str                          # the entry's name, for messages
@@ -1022,6 +1106,13 @@ class EgoTAPAutoEncoderModel(nn.Module):
         also roll about their own axis (None: they follow their parent, until ``set_hinges(pose_rows)`` has taken a frame with bent elbows and knees).
         The serving entries, the trackers, their graphs and their outputs do not change."""
         return Skeleton(self.net_AutoEncoder.preset.out_joints, joint_preset=self.opt.joint_preset, rig=rig, streams=streams, params=params, twist=twist)
+
+    def new_overlay(self, style=None):
+        """An ``Overlay`` for this model's outputs: ``pose, hm, kp = model.predict_pose_from_camera(l8, r8, return_heatmaps=True, return_keypoints=True)``;
+        ``out_l, out_r = ov.draw(l8, r8, keypoints=kp, heatmaps=hm)`` -- the frames with the position heatmaps, the skeleton's bones and the keypoints
+        drawn on, one or two launches behind the serving call on the same stream.  ``style`` a ``spec.OverlayStyle`` with one mark per heatmap joint
+        (None: ``spec.overlay_style(joint_preset)``, which nobody has tuned).  The serving entries, their graphs and their outputs do not change."""
+        return Overlay(self.net_AutoEncoder.preset.n_joints_hm, _spec.overlay_style(self.opt.joint_preset) if style is None else style)
 
     def rgb_intermediate(self, name: str, B: int):
         """View of the heatmaps the last UNGRAPHED predict_pose_from_rgb(return_heatmaps=False) call of batch B kept inside its workspace (parity

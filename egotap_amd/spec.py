@@ -1994,3 +1994,237 @@ def skeleton_fit_twist_ref(points, state, rig, twist, params=None, tracks=None, 
             raise ValueError(f"{who}: the twist table has P = {twist.P} rows, the rig {rig.P}")
         _sk_pole_rows(who, rig, twist.pole)
     return _skeleton_fit_walk(who, points, state, rig, params, tracks, streams, dtype, twist)
+
+
+# ---- heatmaps, keypoints and bones drawn onto the frames (egotap.h: egotap_heat_u8 / egotap_overlay_u8) -----------------------------------
+OVERLAY_MAX_MARKS = 64                         # M: prepared once per workgroup, one thread each
+OVERLAY_MAX_BONES = 64                         # L
+OVERLAY_MAX_SIDE = 16384                       # Hc, Wc <= 16384: a pixel centre 16 X + 8 stays below 2^18
+OVERLAY_MAX_HEAT_SIDE = 4096                   # S <= 4096: a tap index fits the low 16 bits of a table entry
+OVERLAY_MAX_R16 = 16384                        # r16, w16 <= 16384 (1024 pixels): a culling box stays inside int32
+OVERLAY_MARK_LIMIT = 32768.0                   # |x|, |y| < 32768: |rint(16 x)| <= 2^19, so every product below stays under 2^42
+OVERLAY_TAP_OUTSIDE = -1                       # a tap table entry whose canvas pixel lies outside the map's extent
+
+
+def heat_u8(hm, c0: int, n: int, groups: int = 1):
+    """The reference's picture of a heatmap stack (utils/util.py:160-175 tensor2im(is_heatmap=True)) per group of channels, restated in numpy: hm
+    [B, C, S, S] (float32, or anything exactly representable in it -- bf16 values upcast) -> uint8 [B, groups, S, S].  Group g is channels
+    c0 + g n/groups .. c0 + (g + 1) n/groups - 1; per pixel, in float32:
+
+        v = the group's channels added in ascending order;  v = v > 0 ? (v < 1 ? v : 1) : 0  (a NaN gives 0);  byte = (uint8)(int)(v * 255.0f)
+
+    truncated, as the reference's astype(np.uint8) truncates.  This is what heat_u8_kernel computes, bit for bit."""
+    import numpy as np
+    h = np.asarray(hm, dtype=np.float32)
+    if h.ndim != 4 or h.shape[2] != h.shape[3]:
+        raise ValueError(f"heat_u8: maps are [B, C, S, S], got {h.shape}")
+    B, C, S, _ = h.shape
+    c0, n, groups = int(c0), int(n), int(groups)
+    if n < 1 or groups < 1 or n % groups or c0 < 0 or c0 + n > C:
+        raise ValueError(f"heat_u8: channels {c0} .. {c0 + n - 1} in {groups} groups are not a slice of the {C} channels in equal groups")
+    per = n // groups
+    out = np.empty((B, groups, S, S), dtype=np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for g in range(groups):
+            v = h[:, c0 + g * per].copy()
+            for k in range(1, per):
+                v = (v + h[:, c0 + g * per + k]).astype(np.float32)
+            v = np.where(v > 0, np.where(v < 1, v, np.float32(1)), np.float32(0)).astype(np.float32)
+            out[:, g] = (v * np.float32(255.0)).astype(np.float32).astype(np.int32).astype(np.uint8)
+    return out
+
+
+def overlay_taps(a: float, b: float, S: int, L: int):
+    """The tap table of one canvas axis of length L over a heat map of side S: int32 [L].  Canvas coordinate = a u + b with u the heat coordinate
+    (heat pixel centres at i + 0.5, canvas pixel centres at X + 0.5; a < 0 is a mirror) -- one component, (ax, bx) or (ay, by), of the eye's keypoint
+    affine.  In float64: u = (X + 0.5 - b) / a;  outside the map's extent (not 0 <= u <= S) the entry is -1;  otherwise p = max(u - 0.5, 0),
+    i0 = floor(p) (<= S - 1, as u <= S), w1 = floor((p - i0) * 2048 + 0.5), entry = i0 | w1 << 16 -- ``resize_taps``' pair for a = L / S, b = 0.  The second tap is
+    i1 = min(i0 + 1, S - 1), the first one's weight 2048 - w1.  Built once on the host; the device reads the table and never the affine."""
+    import numpy as np
+    a, b, S, L = float(a), float(b), int(S), int(L)
+    if not (math.isfinite(a) and math.isfinite(b)) or a == 0.0:
+        raise ValueError(f"overlay_taps: the affine component must be finite with a != 0, got ({a}, {b})")
+    if not (1 <= S <= OVERLAY_MAX_HEAT_SIDE and 1 <= L <= OVERLAY_MAX_SIDE):
+        raise ValueError(f"overlay_taps: the heat side is 1 .. {OVERLAY_MAX_HEAT_SIDE} and the canvas length 1 .. {OVERLAY_MAX_SIDE}, got {S}, {L}")
+    u = (np.arange(L, dtype=np.float64) + 0.5 - b) / a
+    inside = (u >= 0.0) & (u <= float(S))
+    p = np.where(inside, np.maximum(u - 0.5, 0.0), 0.0)
+    i0 = np.floor(p)
+    w1 = np.floor((p - i0) * float(RESIZE_WEIGHT_ONE) + 0.5)
+    entry = i0.astype(np.int64) | (w1.astype(np.int64) << 16)
+    return np.where(inside, entry, OVERLAY_TAP_OUTSIDE).astype(np.int32)
+
+
+@dataclass(frozen=True)
+class OverlayStyle:
+    """egotap.h egotap_overlay_style: what is drawn and how.  ``bones`` [L][2] indices into the marks, ``mark_rgba`` [M][4] and ``bone_rgba`` [L][4]
+    bytes (alpha 0 draws nothing), ``r16`` / ``w16`` the marks' radius and the bones' half-width in sixteenths of a pixel, ``min_score`` the least score
+    of a mark that is drawn, ``heat_rgba`` the heat layer's one colour and its alpha."""
+    bones: tuple = ()
+    mark_rgba: tuple = ()
+    bone_rgba: tuple = ()
+    r16: int = 40
+    w16: int = 16
+    min_score: float = STEREO_MIN_SCORE
+    heat_rgba: tuple = (255, 255, 255, 160)
+
+    def __post_init__(self):
+        bones = tuple((int(i), int(j)) for i, j in self.bones)
+        marks = tuple(tuple(int(v) for v in c) for c in self.mark_rgba)
+        bcol = tuple(tuple(int(v) for v in c) for c in self.bone_rgba)
+        heat = tuple(int(v) for v in self.heat_rgba)
+        M, L = len(marks), len(bones)
+        if M > OVERLAY_MAX_MARKS or L > OVERLAY_MAX_BONES:
+            raise ValueError(f"OverlayStyle: at most {OVERLAY_MAX_MARKS} marks and {OVERLAY_MAX_BONES} bones, got {M} and {L}")
+        if len(bcol) != L:
+            raise ValueError(f"OverlayStyle: bone_rgba has one colour per bone, got {len(bcol)} for {L} bones")
+        if any(not (0 <= i < M and 0 <= j < M) for i, j in bones):
+            raise ValueError(f"OverlayStyle: a bone's ends are mark indices 0 .. {M - 1}, got {bones}")
+        if any(len(c) != 4 or any(not 0 <= v <= 255 for v in c) for c in marks + bcol + (heat,)):
+            raise ValueError("OverlayStyle: a colour is four bytes (R, G, B, alpha)")
+        r16, w16, ms = int(self.r16), int(self.w16), float(self.min_score)
+        if not (0 <= r16 <= OVERLAY_MAX_R16 and 0 <= w16 <= OVERLAY_MAX_R16):
+            raise ValueError(f"OverlayStyle: r16 and w16 are 0 .. {OVERLAY_MAX_R16} sixteenths of a pixel, got {self.r16}, {self.w16}")
+        if math.isnan(ms):
+            raise ValueError("OverlayStyle: min_score must not be NaN")
+        for name, v in (("bones", bones), ("mark_rgba", marks), ("bone_rgba", bcol), ("heat_rgba", heat), ("r16", r16), ("w16", w16), ("min_score", ms)):
+            object.__setattr__(self, name, v)
+
+
+OVERLAY_LEFT_RGBA = (64, 160, 255, 255)        # the lower row of a mirrored pair (SKELETON_MIRROR)
+OVERLAY_RIGHT_RGBA = (255, 96, 64, 255)        # the higher row
+OVERLAY_CENTRE_RGBA = (96, 255, 96, 255)       # a row without a mirror row
+
+
+def overlay_style(joint_preset, r16: int = 40, w16: int = 16, min_score: float = STEREO_MIN_SCORE, heat_rgba=(255, 255, 255, 160)):
+    """The style of a preset's keypoints: one mark per heatmap joint, a bone from every joint to its parent (``skeleton_parents``; the pose rows the
+    joints are paired with start at ``stereo_pose_row0``, and a bone whose parent is the head UnrealEgo has no heatmap of is left out), the colours by
+    body side from ``SKELETON_MIRROR`` (the lower row of a mirrored pair, the higher one, rows without a mirror row); a bone takes its child's colour.
+    Nothing here was tuned on data."""
+    p = lift_preset(joint_preset)
+    row0, par, mir = stereo_pose_row0(p), skeleton_parents(joint_preset), SKELETON_MIRROR[joint_preset]
+
+    def colour(row):
+        return OVERLAY_CENTRE_RGBA if mir[row] < 0 else OVERLAY_LEFT_RGBA if row < mir[row] else OVERLAY_RIGHT_RGBA
+    rows = range(row0, row0 + p.n_joints_hm)
+    bones = tuple((par[r] - row0, r - row0) for r in rows if par[r] >= row0)
+    return OverlayStyle(bones=bones, mark_rgba=tuple(colour(r) for r in rows), bone_rgba=tuple(colour(r) for r in rows if par[r] >= row0), r16=r16, w16=w16,
+                        min_score=min_score, heat_rgba=heat_rgba)
+
+
+def overlay_isqrt(n):
+    """floor(sqrt(n)) of int64 values 0 <= n < 2^52: the float64 square root truncated, then one integer correction step each way"""
+    import numpy as np
+    n = np.asarray(n, dtype=np.int64)
+    r = np.sqrt(n.astype(np.float64)).astype(np.int64)
+    r = r - (r * r > n)
+    return r + ((r + 1) * (r + 1) <= n)
+
+
+def overlay_blend(c, colour, t):
+    """one channel under one layer: (c (65536 - t) + colour t + 32768) >> 16 with t = coverage (0 .. 256) * alpha (0 .. 255); t = 0 returns c"""
+    return (c * (65536 - t) + colour * t + 32768) >> 16
+
+
+def overlay_eligible(marks, min_score):
+    """which marks [..., 4] = (x, y, score, _) float32 are drawn: score >= min_score in float32 (false on a NaN), x and y finite, |x|, |y| < 32768"""
+    import numpy as np
+    m = np.asarray(marks, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        return (m[..., 2] >= np.float32(min_score)) & (np.abs(m[..., 0]) < np.float32(OVERLAY_MARK_LIMIT)) & (np.abs(m[..., 1]) < np.float32(OVERLAY_MARK_LIMIT))
+
+
+def _overlay_coverage(d, half16):
+    import numpy as np
+    return np.clip(half16 + 8 - d, 0, 16) * 16
+
+
+def overlay_u8(left8, right8, style: OverlayStyle, marks=None, heat8=None, taps=None):
+    """What egotap_overlay_u8 writes, restated in numpy integers: canvases uint8 [B, Hc, Wc, 3] (``right8`` None: one eye, E = 1, else E = 2) -> the
+    canvases with three layers blended on, in this order: the heat, the bones in ascending index, the marks in ascending index.  Every layer
+    changes every channel by ``overlay_blend`` with t = coverage * alpha.
+
+      heat   ``heat8`` uint8 [B, E, S, S] (``heat_u8``) and ``taps`` = per eye (x table int32 [Wc], y table int32 [Hc]) from ``overlay_taps``:  a pixel
+             whose x or y entry is -1 is left alone;  otherwise A = (wy0 (wx0 p00 + wx1 p01) + wy1 (wx0 p10 + wx1 p11) + 2^21) >> 22 over the four
+             taps (the sensor front ends' blend of one byte), t = A * heat alpha, the one heat colour
+      marks  ``marks`` float32 [B, E, M, 4] = (x, y, score, _) in canvas pixels (pixel centres at X + 0.5), ``overlay_eligible``;  in sixteenths:
+             mx = rint(16 x), my = rint(16 y) (ties to even), pixel centre (16 X + 8, 16 Y + 8), d = isqrt(dx^2 + dy^2) (a floor),
+             coverage = clamp(r16 + 8 - d, 0, 16) * 16, colour and alpha of the mark's palette row
+      bones  a bone (i, j) is drawn when both marks are eligible;  a, b their sixteenths, e = b - a, dd = e . e, s = (p - a) . e:
+             dd == 0 or s <= 0: d = the distance to a as above;  s >= dd: to b;  otherwise d = |cross(p - a, e)| div isqrt(dd);
+             coverage = clamp(w16 + 8 - d, 0, 16) * 16, colour and alpha of the bone's palette row
+    Every intermediate is an integer below 2^42.  Returns (out_left, out_right or None) as numpy arrays."""
+    import numpy as np
+    eyes = [np.asarray(left8)] + ([np.asarray(right8)] if right8 is not None else [])
+    E = len(eyes)
+    for c in eyes:
+        if c.dtype != np.uint8 or c.ndim != 4 or c.shape[3] != 3 or c.shape != eyes[0].shape:
+            raise ValueError(f"overlay_u8: canvases are uint8 [B, Hc, Wc, 3] of one shape, got {[(str(e.dtype), e.shape) for e in eyes]}")
+    B, Hc, Wc, _ = eyes[0].shape
+    M, L = len(style.mark_rgba), len(style.bones)
+    if marks is None:
+        if M or L:
+            raise ValueError("overlay_u8: the style has marks or bones and no marks are given")
+    else:
+        marks = np.asarray(marks, dtype=np.float32)
+        if marks.shape != (B, E, M, 4):
+            raise ValueError(f"overlay_u8: marks are [B, E, M, 4] = {(B, E, M, 4)}, got {marks.shape}")
+    if heat8 is not None:
+        heat8 = np.asarray(heat8)
+        if heat8.dtype != np.uint8 or heat8.ndim != 4 or heat8.shape[:2] != (B, E) or heat8.shape[2] != heat8.shape[3]:
+            raise ValueError(f"overlay_u8: heat8 is uint8 [B, E, S, S] with (B, E) = {(B, E)}, got {heat8.dtype} {heat8.shape}")
+        if taps is None or len(taps) != E or any(np.asarray(tx).shape != (Wc,) or np.asarray(ty).shape != (Hc,) for tx, ty in taps):
+            raise ValueError(f"overlay_u8: taps are per eye (x table [{Wc}], y table [{Hc}]) from overlay_taps")
+    px = (16 * np.arange(Wc, dtype=np.int64) + 8).reshape(1, Wc)
+    py = (16 * np.arange(Hc, dtype=np.int64) + 8).reshape(Hc, 1)
+
+    def layer(acc, cov, rgba):
+        t = (cov * rgba[3]).astype(np.int64)[..., None]
+        return overlay_blend(acc, np.asarray(rgba[:3], dtype=np.int64), t)
+
+    def dist(ax, ay):
+        dx, dy = px - ax, py - ay
+        return overlay_isqrt(dx * dx + dy * dy)
+
+    outs = []
+    for e, canvas in enumerate(eyes):
+        out = np.empty_like(canvas)
+        for b in range(B):
+            acc = canvas[b].astype(np.int64)
+            if heat8 is not None:
+                S = heat8.shape[2]
+                tx, ty = (np.asarray(t, dtype=np.int64) for t in taps[e])
+                ok = (ty >= 0).reshape(Hc, 1) & (tx >= 0).reshape(1, Wc)
+                ix0, wx1 = np.where(tx >= 0, tx & 0xffff, 0), np.where(tx >= 0, tx >> 16, 0)
+                iy0, wy1 = np.where(ty >= 0, ty & 0xffff, 0), np.where(ty >= 0, ty >> 16, 0)
+                ix1, iy1 = np.minimum(ix0 + 1, S - 1), np.minimum(iy0 + 1, S - 1)
+                wx0, wy0 = (RESIZE_WEIGHT_ONE - wx1).reshape(1, Wc), (RESIZE_WEIGHT_ONE - wy1).reshape(Hc, 1)
+                h = heat8[b, e].astype(np.int64)
+                top = wx0 * h[iy0][:, ix0] + wx1.reshape(1, Wc) * h[iy0][:, ix1]
+                bot = wx0 * h[iy1][:, ix0] + wx1.reshape(1, Wc) * h[iy1][:, ix1]
+                A = (wy0 * top + wy1.reshape(Hc, 1) * bot + (1 << 21)) >> 22
+                acc = layer(acc, np.where(ok, A, 0), style.heat_rgba)
+            if M:
+                m = marks[b, e]
+                elig = overlay_eligible(m, style.min_score)
+                with np.errstate(invalid="ignore", over="ignore"):
+                    q = np.where(elig[:, None], np.rint(np.float32(16) * np.where(elig[:, None], m[:, :2], np.float32(0))), 0).astype(np.int64)
+                for l, (i, j) in enumerate(style.bones):
+                    if not (elig[i] and elig[j]):
+                        continue
+                    ax, ay, bx, by = int(q[i, 0]), int(q[i, 1]), int(q[j, 0]), int(q[j, 1])
+                    ex, ey = bx - ax, by - ay
+                    dd = ex * ex + ey * ey
+                    if dd == 0:
+                        d = dist(ax, ay)
+                    else:
+                        s = (px - ax) * ex + (py - ay) * ey
+                        cross = np.abs((px - ax) * ey - (py - ay) * ex)
+                        d = np.where(s <= 0, dist(ax, ay), np.where(s >= dd, dist(bx, by), cross // int(overlay_isqrt(dd))))
+                    acc = layer(acc, _overlay_coverage(d, style.w16), style.bone_rgba[l])
+                for j in range(M):
+                    if elig[j]:
+                        acc = layer(acc, _overlay_coverage(dist(int(q[j, 0]), int(q[j, 1])), style.r16), style.mark_rgba[j])
+            out[b] = acc.astype(np.uint8)
+        outs.append(out)
+    return outs[0], (outs[1] if E == 2 else None)

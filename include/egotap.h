@@ -685,6 +685,61 @@ int egotap_skeleton_fit_twist(const float* points, const float* tracks, int T, i
                               const egotap_skeleton_params* params, const double* state_in, double* state_out, float* rigid, float* rotations, float* lengths,
                               void* stream);
 
+/* ---- heatmaps, keypoints and bones drawn onto the frames (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * Nothing in the serving chain let a person see what the estimators saw and found; a wrong crop rectangle, mirror flag, lens map or keypoint affine
+ * shows at once in a picture.  Two operators, no handle, one launch each on the caller's stream, no synchronisation, no allocation, no atomics, no
+ * workspace; recorded as heat_u8 and overlay_u8 while a handle's timing hook is on.  egotap_amd/spec.py restates both (heat_u8, overlay_taps,
+ * overlay_u8); the device equals the restatement in every byte.
+ *
+ * egotap_heat_u8: the reference's picture of a heatmap stack (utils/util.py:160-175 tensor2im(is_heatmap=True)) per group of channels.  hm is
+ * [B, C, S, S], EGOTAP_F32 or EGOTAP_BF16, element (b, c, y, x) at b * image_stride + c * S*S + y * S + x (image_stride in elements, >= C * S*S: a channel
+ * slice of a wider tensor is read in place); heat8 is uint8 [B, groups, S, S], contiguous.  Group g is the n / groups consecutive channels from
+ * c0 + g * n / groups.  Per pixel, in fp32 (bf16 upcast exactly), nothing contracted:
+ *   v = the group's channels added in ascending order;  v = v > 0 ? (v < 1 ? v : 1) : 0, so a NaN gives 0;  byte = (uint8)(int)(v * 255.0f), truncated
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL hm or heat8; an unknown dtype; B < 1; n < 1; groups < 1 or not dividing n; c0 < 0 or
+ * c0 + n > C; S not a positive multiple of 16, or above 4096; image_stride below C * S*S or no multiple of 16 bytes; hm not 16-byte or heat8 not 8-byte
+ * aligned; heat8 overlapping hm.
+ *
+ * egotap_overlay_u8: three layers blended onto packed RGB8 canvases, uint8 [B, Hc, Wc, 3], left and right; right8 and out_right8 both NULL: one eye
+ * (E = 1, otherwise E = 2).  Wc % 4 == 0, every canvas base 4-byte aligned, Hc, Wc <= 16384, B <= 65535.  out == in exactly (per eye) is the one
+ * permitted overlap: any other overlap between any two array arguments is refused.  The layers go on in this order -- the heat, the bones in
+ * ascending index, the marks in ascending index -- and every layer changes every channel as
+ *   c = (c * (65536 - t) + colour * t + 32768) >> 16      t = coverage (0 .. 256) * alpha (0 .. 255);  t = 0 returns c
+ * heat   (heat8 NULL: none)  heat8 uint8 [B, E, S, S], as egotap_heat_u8 writes it with groups = E, and per eye two tap tables on the device, int32
+ *        [Wc] (tx) and [Hc] (ty), built once on the host in float64 (spec.overlay_taps(a, b, S, L) from the eye's keypoint affine component (a, b):
+ *        canvas coordinate = a * u + b, heat pixel centres at i + 0.5, a < 0 a mirror).  An entry is i0 | w1 << 16 with w1 the second tap's weight in
+ *        Q11, or -1 where the canvas pixel lies outside the map's extent; the second tap is min(i0 + 1, S - 1).  A pixel whose x or y entry is -1 is
+ *        left alone.  Otherwise A = (wy0 (wx0 p00 + wx1 p01) + wy1 (wx0 p10 + wx1 p11) + 2^21) >> 22 (the sensor front ends' blend of one byte),
+ *        t = A * heat alpha, the one colour heat_rgba.  The device reads the tables and never the affine; an index past S - 1 is clamped to it.
+ * marks  (marks NULL: none, and no bones; the style's n_marks and n_bones are then not read)  fp32 [B, E, M, 4] = (x, y, score, _) in canvas pixels,
+ *        pixel centres at X + 0.5 -- the keypoint record of the _kp entries passed straight in.  A mark is eligible when score >= min_score (false on
+ *        a NaN), x and y are finite and |x|, |y| < 32768.  In sixteenths of a pixel: mx = rint(16 x), my = rint(16 y) (ties to even), a pixel centre
+ *        is (16 X + 8, 16 Y + 8), d = isqrt(dx^2 + dy^2) (a floor), coverage = clamp(r16 + 8 - d, 0, 16) * 16; colour and alpha mark_rgba[j].
+ * bones  bones[l] = two mark indices; drawn when both marks are eligible.  a, b their sixteenths, e = b - a, dd = e . e, s = (p - a) . e:
+ *        dd == 0 or s <= 0: d = the distance to a, as above;  s >= dd: to b;  otherwise d = |cross(p - a, e)| div isqrt(dd), an integer floor division;
+ *        coverage = clamp(w16 + 8 - d, 0, 16) * 16; colour and alpha bone_rgba[l].
+ * Every intermediate is an integer below 2^42 (|mx| <= 2^19, a pixel centre < 2^18, so a difference is below 2^20 and a sum of two products below 2^41).
+ * The style is host memory, read during the call.  One thread draws four pixels of a row; a frame's marks, bones and culling boxes are prepared once per
+ * workgroup; culling changes no byte.
+ * EGOTAP_ERR_INVALID, by name and before any launch: a NULL left8, out_left8 or style; right8 and out_right8 not both NULL or both given; B < 1 or
+ * > 65535; Hc < 1, Wc < 4, Wc % 4 != 0, Hc or Wc > 16384; a canvas base not 4-byte aligned; heat8 given with S < 1 or S > 4096, a NULL tap table of a
+ * drawn eye, tx not 16-byte or ty not 4-byte aligned; marks not 16-byte aligned; with marks: n_marks outside 1 .. 64, n_bones outside 0 .. 64, a bone index
+ * outside 0 .. n_marks - 1; r16 or w16 outside 0 .. 16384; a NaN min_score; any overlap other than out == in. */
+#define EGOTAP_OVERLAY_MAX 64
+typedef struct egotap_overlay_style {
+    int32_t n_marks, n_bones;                        /* M, L */
+    int32_t r16, w16;                                /* the marks' radius and the bones' half-width, sixteenths of a pixel */
+    float min_score;
+    uint8_t heat_rgba[4];                            /* R, G, B, alpha */
+    uint8_t bones[EGOTAP_OVERLAY_MAX][2];
+    uint8_t mark_rgba[EGOTAP_OVERLAY_MAX][4];
+    uint8_t bone_rgba[EGOTAP_OVERLAY_MAX][4];
+} egotap_overlay_style;
+int egotap_heat_u8(const void* hm, int dtype, int B, int C, int S, int64_t image_stride, int c0, int n, int groups, uint8_t* heat8, void* stream);
+int egotap_overlay_u8(const uint8_t* left8, const uint8_t* right8, int B, int Hc, int Wc, const uint8_t* heat8, int S, const int32_t* tx_left,
+                      const int32_t* ty_left, const int32_t* tx_right, const int32_t* ty_right, const float* marks, const egotap_overlay_style* style,
+                      uint8_t* out_left8, uint8_t* out_right8, void* stream);
+
 /* Arithmetic of the large GEMMs of the lifting head (nn.Linear layers of the ViT and fc1; everything else is always fp32).
  *   EGOTAP_PREC_F32     v_mfma_f32_32x32x2_f32: exact fp32 products (default; what the headline benchmark measures)
  *   EGOTAP_PREC_BF16X3  each fp32 operand split in registers into hi + lo bf16 (16 significant bits), a*b taken as

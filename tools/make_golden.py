@@ -917,6 +917,34 @@ def gen_sensor_resize():
     print("sensor_resize ok", out.shape, "reference vs float64", err, "ours vs reference: max", int(d.max()), "differing bytes", int((d != 0).sum()))
 
 
+def gen_visuals():
+    """the reference's picture of a heatmap stack, utils/util.py:160-175 tensor2im(x, is_heatmap=True), per frame of a seeded stack of 15 maps of
+    side 32.  The inputs are dyadic -- int16 numerators k, value k / 1024 -- so every partial sum of a frame's channels is a multiple of 2^-10 below
+    2^3 and exact in float32: whatever order torch.sum adds in, the sum is the same, checked here against float64 and the reversed order.  Stored: the
+    numerators and the reference's bytes [2, 32, 32, 1].  Frame 0 straddles the clamp at 1, frame 1 the clamp at 0."""
+    import utils.util as UU
+    g = torch.Generator().manual_seed(20261021)
+    k = torch.randint(-64, 201, (2, 15, 32, 32), generator=g, dtype=torch.int32)
+    k[1] -= 68                                                     # sums around 0: the lower clamp
+    x = k.float() / 1024.0
+    assert torch.equal(x.double() * 1024.0, k.double())
+    out = []
+    for b in range(2):
+        exact = x[b].double().sum(0)
+        fwd, rev = torch.zeros(32, 32), torch.zeros(32, 32)
+        for c in range(15):
+            fwd, rev = fwd + x[b, c], rev + x[b, 14 - c]
+        assert torch.equal(fwd.double(), exact) and torch.equal(rev.double(), exact) and torch.equal(torch.sum(x[b], dim=0).double(), exact)
+        out.append(UU.tensor2im(x[b], is_heatmap=True))
+        assert out[-1].dtype == np.uint8 and out[-1].shape == (32, 32, 1)
+    out = np.stack(out)
+    from egotap_amd import spec
+    ours = spec.heat_u8(x.numpy(), 0, 15, 1)[:, 0]
+    diff = int((ours != out[..., 0]).sum())
+    np.savez_compressed(os.path.join(GOLD, "visuals_heat.npz"), hm_q=k.to(torch.int16).numpy(), out=out)
+    print("visuals_heat ok", out.shape, "bytes at 0 / 255:", int((out == 0).sum()), int((out == 255).sum()), "spec.heat_u8 differs in", diff, "pixels")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="lift,pu,fc,loss,hm,procrustes,train,train_dhm,sched,synth,hmtrain,wrapper,wrapper_rgb,rgb_u8,sensor_resize")
@@ -958,6 +986,8 @@ def main():
         gen_rgb_u8()
     if "sensor_resize" in which:
         gen_sensor_resize()
+    if "visuals" in which:             # (not in the default set: added after the other fixtures were pinned)
+        gen_visuals()
     if "wrapper_spread" in which:      # (not in the default set: six reference wrapper runs, ~10 min)
         gen_wrapper_spread()
 

@@ -25,6 +25,9 @@ Arms (UnrealEgo, 64 x 64 heatmaps, resnet18 estimators, opt.hm_chunk 256):
               thresholds): the launch of egotap_skeleton_fit_twist in the place of egotap_skeleton_fit's (report only)
   fusion      the tracking arm with StereoFusion.update between the serving call and the tracker (return_keypoints=True as well; sigma_prior 0.05, the other
               defaults): one more launch in front of the tracker's, egotap_stereo_fuse (report only)
+  overlay     predict_pose_from_rgb(return_heatmaps=True, return_keypoints=True) followed by Overlay.draw of the heatmaps, the skeleton's bones and the
+              keypoints onto two uint8 [B, 256, 256, 3] canvases (out of place, into preallocated outputs): two more launches behind the call, egotap_heat_u8
+              and egotap_overlay_u8 (report only -- the heatmaps arm plus the keypoints launch is what it adds to)
   heatmaps_argmax  what a caller did for them before: return_heatmaps=True, then torch amax / argmax on the device over the 2J position channels
 Settings: "bf16_frozen" (set_precision("bf16") + freeze_weights) and "f32".  Every arm is warmed up, then timed in three alternating rounds;
 per arm the median over all calls and the lowest / highest of the three round medians (the run-to-run spread) are printed.
@@ -114,6 +117,16 @@ def arms_for(m, p, left, right):
         fuse_tracker.update(pose_fused, joints3d, frame, dt=1.0 / 30)
         return pose
 
+    overlay = m.new_overlay()
+    g = torch.Generator().manual_seed(30)
+    canvases = [torch.randint(0, 256, (B, 4 * p.hm_size, 4 * p.hm_size, 3), generator=g, dtype=torch.uint8).cuda() for _ in range(2)]
+    drawn = [torch.empty_like(c) for c in canvases]
+
+    def overlay_arm():
+        pose, hm, keypoints = m.predict_pose_from_rgb(left, right, return_heatmaps=True, return_keypoints=True)
+        overlay.draw(canvases[0], canvases[1], keypoints=keypoints, heatmaps=hm, out=drawn)
+        return pose
+
     skel_tracker, skeleton = m.new_pose_tracker(streams=1), m.new_skeleton(streams=1)
 
     def skeleton_arm():
@@ -146,6 +159,7 @@ def arms_for(m, p, left, right):
             "tracking": tracking,
             "tracking_world": tracking_world,
             "fusion": fusion_arm,
+            "overlay": overlay_arm,
             "skeleton": skeleton_arm,
             "skeleton_twist": skeleton_twist_arm,
             "heatmaps_argmax": heatmaps_argmax,
@@ -276,7 +290,7 @@ def main():
                 continue
             r = measure(arms, REPS.get(B, 6))
             for k, (med, lo, hi) in r.items():
-                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "fusion", "skeleton", "skeleton_twist") else ""
+                note = f"({form})" if k in ("no_heatmaps", "graphed", "keypoints", "limbs", "triangulation", "tracking", "tracking_world", "fusion", "overlay", "skeleton", "skeleton_twist") else ""
                 print(f"{setting:12s} B={B:<4d} {k:14s} median {med:9.3f} ms   round medians {lo:9.3f} .. {hi:9.3f} {note}", flush=True)
                 res["rows"].append(dict(setting=setting, B=B, arm=k, median_ms=med, round_lo_ms=lo, round_hi_ms=hi, form=form))
             m._rgb["graphs"].clear()
