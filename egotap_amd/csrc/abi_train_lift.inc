@@ -121,20 +121,44 @@ extern "C" int egotap_train_patch_fwd(egotap_handle h, const float* hm, int B, c
     return EGOTAP_OK;
 }
 
+// Which kernel family tn_any launches (host only, no launch; egotap_debug_pu_train_routes reports it).  plain_dma_ok: the operands are plain
+// row-major matrices that gemm_tn_f32_dma_ok accepts (false for every gathering loader).  EGOTAP_TN_*: egotap_debug.h.
+static int tn_family(int precision, bool plain_dma_ok, int M, int N, int K) {
+    if (N % 256 == 0 && K % 256 == 0 && M >= 1024 && precision == EGOTAP_PREC_BF16X3) return EGOTAP_TN_BF16X3;
+    if (N % 256 == 0 && K % 256 == 0 && M >= 1024 && precision == EGOTAP_PREC_BF16) return EGOTAP_TN_BF16;
+    if (M >= 1024 && plain_dma_ok) return EGOTAP_TN_F32_DMA;
+    if (N % 256 == 0 && K % 256 == 0) return EGOTAP_TN_F32_BIG;
+    if (N % 128 == 0 && K % 128 == 0) return EGOTAP_TN_F32_SMALL;
+    return EGOTAP_TN_NONE;
+}
+// Split count of the launch tn_any makes for `family` with ws_bytes of slab scratch (host only).  *capped: the scratch set the count.
+static int tn_splits(int family, int M, int N, int K, size_t ws_bytes, int num_cu, bool* capped) {
+    *capped = false;
+    int per = 0;
+    switch (family) {
+        case EGOTAP_TN_BF16X3: return gemm_tn_bf16_splits<TnBfCfg<3>>(M, N, K, num_cu, ws_bytes, false, capped);
+        case EGOTAP_TN_BF16: return gemm_tn_bf16_splits<TnBfCfg<1>>(M, N, K, num_cu, ws_bytes, false, capped);
+        case EGOTAP_TN_F32_DMA: return gemm_tn_f32_dma_splits(M, N, K, num_cu, ws_bytes, false, &per);
+        case EGOTAP_TN_F32_BIG: return gemm_tn_f32_splits<TnBig>(M, N, K, num_cu, ws_bytes, capped);
+        case EGOTAP_TN_F32_SMALL: return gemm_tn_f32_splits<TnSmall>(M, N, K, num_cu, ws_bytes, capped);
+        default: return 0;
+    }
+}
+
 template <class XL>
 static hipError_t tn_any(Handle* h, const float* dy, const XL& xl, float* dw, float* ws, size_t ws_bytes, int M, int N, int K, int acc, hipStream_t s,
                          long ldy = 0) {
     if (ldy <= 0) ldy = N;
-    if (N % 256 == 0 && K % 256 == 0 && M >= 1024 && h->precision == EGOTAP_PREC_BF16X3)
-        return gemm_tn_bf16_launch<TnBfCfg<3>, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
-    if (N % 256 == 0 && K % 256 == 0 && M >= 1024 && h->precision == EGOTAP_PREC_BF16)
-        return gemm_tn_bf16_launch<TnBfCfg<1>, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
+    bool plain_dma_ok = false;
+    if constexpr (std::is_same<XL, ALoadPlain>::value) plain_dma_ok = gemm_tn_f32_dma_ok(dy, ldy, xl.A, xl.lda, M, N, K);
+    const int family = tn_family(h->precision, plain_dma_ok, M, N, K);
+    if (family == EGOTAP_TN_BF16X3) return gemm_tn_bf16_launch<TnBfCfg<3>, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
+    if (family == EGOTAP_TN_BF16) return gemm_tn_bf16_launch<TnBfCfg<1>, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
     if constexpr (std::is_same<XL, ALoadPlain>::value) {      // [r3] plain operands: the DMA-staged kernel (gemm_tn_f32.h), same summation order per element
-        if (M >= 1024 && gemm_tn_f32_dma_ok(dy, ldy, xl.A, xl.lda, M, N, K))
-            return gemm_tn_f32_dma_launch(dy, ldy, xl.A, xl.lda, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
+        if (family == EGOTAP_TN_F32_DMA) return gemm_tn_f32_dma_launch(dy, ldy, xl.A, xl.lda, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
     }
-    if (N % 256 == 0 && K % 256 == 0) return gemm_tn_f32_launch<TnBig, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
-    if (N % 128 == 0 && K % 128 == 0) return gemm_tn_f32_launch<TnSmall, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
+    if (family == EGOTAP_TN_F32_BIG) return gemm_tn_f32_launch<TnBig, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
+    if (family == EGOTAP_TN_F32_SMALL) return gemm_tn_f32_launch<TnSmall, XL>(dy, ldy, xl, dw, ws, ws_bytes, M, N, K, device_cu_count(), acc, s);
     return hipErrorInvalidValue;
 }
 
@@ -460,6 +484,52 @@ extern "C" int egotap_train_pu_bwd_ws_bytes(egotap_handle h, int B, size_t* byte
     return EGOTAP_OK;
 }
 
+// The input-gradient GEMMs of egotap_train_pu_bwd ([M, K] x WT[N, K]^T) split K over the CUs while the output is fewer than 128 tiles of
+// 128 x 128 and the two partial outputs fit the slab scratch (host only, no launch).
+static bool pu_bwd_nt_splits_k(int M, int N, int K, size_t part_bytes) {
+    const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
+    return tiles < 128 && K >= 1024 && N % 128 == 0 && K % 32 == 0 && (size_t)2 * M * N * 4 <= part_bytes;
+}
+
+// (test aid, host only) which kernels egotap_train_pu_fwd and egotap_train_pu_bwd launch at batch B, from the predicates those launches call
+// themselves: the layout of egotap_debug.h (EGOTAP_PU_ROUTE_*).  Operands at 16-byte aligned addresses, as the two workspaces place them.
+static void pu_train_routes(const Handle* h, int B, int resident1, int resident2, int num_cu, int* out) {
+    const int J = h->J, H = h->H, x = 2 * h->hid, NF0 = H + x, JB = J * B;
+    const PuBwdWs w = pu_bwd_ws(h, B);
+    const size_t part_bytes = w.total - w.part;
+    const PuChainRoute c = pu_chain_route(resident1, resident2, B);
+    out[EGOTAP_PU_ROUTE_CHAIN] = c.chunks > 0 ? c.ut : 0;
+    out[EGOTAP_PU_ROUTE_CHUNKS] = c.chunks;
+    out[EGOTAP_PU_ROUTE_ROW_BLOCKS] = c.nrb;
+    out[EGOTAP_PU_ROUTE_LAST_ROWS] = c.last_rows;
+    // weight gradients in the order of grads[]: x2f0, x2h0, b2h0 (gathering loaders), h2h0, x2f1, x2h1, h2h1 (plain operands)
+    const int wn[7] = {NF0, 4 * H, 4 * H, 4 * H, H, 4 * H, 4 * H}, wk[7] = {x, x, x, H, H, H, H};
+    for (int i = 0; i < 7; ++i) {
+        const bool plain = i >= 3;
+        const int fam = tn_family(h->precision, plain && gemm_tn_f32_dma_ok(nullptr, wn[i], nullptr, wk[i], JB, wn[i], wk[i]), JB, wn[i], wk[i]);
+        bool capped = false;
+        out[EGOTAP_PU_ROUTE_WGRAD_SPLITS + i] = tn_splits(fam, JB, wn[i], wk[i], part_bytes, num_cu, &capped);
+        out[EGOTAP_PU_ROUTE_WGRAD_FAMILY + i] = fam;
+        out[EGOTAP_PU_ROUTE_WGRAD_CAPPED + i] = capped ? 1 : 0;
+    }
+    // input gradients: a step of either recurrence, then x2h1, x2f1, b2h0, x2h0, x2f0 over all J * B rows
+    const int gm[6] = {B, JB, JB, JB, JB, JB}, gn[6] = {H, H, H, x, x, x}, gk[6] = {4 * H, 4 * H, H, 4 * H, 4 * H, NF0};
+    for (int i = 0; i < 6; ++i) out[EGOTAP_PU_ROUTE_DGRAD_SPLITK + i] = pu_bwd_nt_splits_k(gm[i], gn[i], gk[i], part_bytes) ? 1 : 0;
+    int rows_per_block = 0;
+    out[EGOTAP_PU_ROUTE_COLSUM_GY] = colsum_f32_rows(JB, 4 * H, part_bytes, &rows_per_block);
+}
+extern "C" int egotap_debug_pu_train_routes_for(egotap_handle h, int B, int resident1, int resident2, int num_cu, int* out, int n) {
+    EGO_CHECK(h && out && B > 0 && num_cu > 0 && n >= EGOTAP_PU_ROUTE_WORDS, "egotap_debug_pu_train_routes_for: a handle, a positive batch and CU count, and room for %d ints", EGOTAP_PU_ROUTE_WORDS);
+    pu_train_routes(h, B, resident1, resident2, num_cu, out);
+    return EGOTAP_OK;
+}
+extern "C" int egotap_debug_pu_train_routes(egotap_handle h, int B, int* out, int n) {
+    EGO_CHECK(h && out && B > 0 && n >= EGOTAP_PU_ROUTE_WORDS, "egotap_debug_pu_train_routes: a handle, a positive batch and room for %d ints", EGOTAP_PU_ROUTE_WORDS);
+    pu_chain_probe(h);
+    pu_train_routes(h, B, h->pu_resident[0], h->pu_resident[1], device_cu_count(), out);
+    return EGOTAP_OK;
+}
+
 // Backward of egotap_train_pu_fwd.  dhs1: gradient w.r.t. skel_embed [J,B,H]; dposz is ACCUMULATED into (the pose head's
 // contribution is already there), drotz is written; grads[14] (state_dict order of skel_sequential_layer) are accumulated
 // when accumulate != 0, else overwritten.
@@ -495,8 +565,7 @@ extern "C" int egotap_train_pu_bwd(egotap_handle h, const float* posz, const flo
     auto nt = [&](const float* a, int M, int N, int K, float* y, const float* acc_src) -> hipError_t {   // y[M,N] = a[M,K] WT[N,K]^T (+ acc)
         // the per-step input gradient of the recurrence is [B, H] x K = 4H: 8 tiles of 128 x 128 at B = 256 would walk K = 2048 on 8
         // CUs (144 us, 32 times per step) -- K is split over the CUs instead, partial sums in the (idle) slab scratch
-        const long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-        if (tiles < 128 && K >= 1024 && N % 128 == 0 && K % 32 == 0 && (size_t)2 * M * N * 4 <= part_bytes) {
+        if (pu_bwd_nt_splits_k(M, N, K, part_bytes)) {
             if (acc_src) return gemm_f32_splitk_launch<TileA>(ALoadPlain{a, K}, segmat1(WT, N, K), EpiAccum{acc_src, N}, y, N, part, part_bytes / 4, M, N, K, s);
             return gemm_f32_splitk_launch<TileA>(ALoadPlain{a, K}, segmat1(WT, N, K), EpiNone{}, y, N, part, part_bytes / 4, M, N, K, s);
         }

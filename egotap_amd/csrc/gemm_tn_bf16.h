@@ -177,6 +177,13 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_tn_bf16_kernel(const flo
     }
 }
 
+// gemm_tn_bf16_launch's split count (host only, no launch): one 512-thread block per CU (144 KB of LDS each)
+template <class Cfg>
+static inline int gemm_tn_bf16_splits(int M, int N, int K, int num_cu, size_t slab_bytes, bool with_db, bool* capped = nullptr) {
+    const size_t per_split = ((size_t)N * K + (with_db ? (size_t)N : 0)) * 4;      // with db: the split's column-sum row behind the slabs
+    return wgrad_row_splits((N / Cfg::BN) * (K / Cfg::BK), 1, Cfg::BKM, M, per_split, slab_bytes, num_cu, capped);
+}
+
 // db != nullptr: also db[N] (+)= column sums of dY (the bias gradient of the same Linear layer)
 template <class Cfg, class XLoad>
 static hipError_t gemm_tn_bf16_launch(const float* dY, long ldy, const XLoad& xl, float* dW, float* slabs, size_t slab_bytes,
@@ -184,12 +191,8 @@ static hipError_t gemm_tn_bf16_launch(const float* dY, long ldy, const XLoad& xl
     if (N % Cfg::BN != 0 || K % Cfg::BK != 0) return hipErrorInvalidValue;
     const int tiles_n = N / Cfg::BN, tiles_k = K / Cfg::BK;
     const int tiles = tiles_n * tiles_k;
-    int splits = (num_cu + tiles - 1) / tiles;                   // one 512-thread block per CU (144 KB of LDS each)
-    const int max_by_rows = (M + 4 * Cfg::BKM - 1) / (4 * Cfg::BKM);
-    if (splits > max_by_rows) splits = max_by_rows;
-    if (splits < 1) splits = 1;
     const size_t per_split = ((size_t)N * K + (db ? (size_t)N : 0)) * 4;      // with db: the split's column-sum row behind the slabs
-    while ((size_t)splits * per_split > slab_bytes && splits > 1) --splits;
+    const int splits = gemm_tn_bf16_splits<Cfg>(M, N, K, num_cu, slab_bytes, db != nullptr);
     const bool direct = splits == 1 && !accumulate;              // a single slab that is not added to anything IS the gradient
     if ((direct ? (db ? (size_t)N * 4 : 0) : (size_t)splits * per_split) > slab_bytes) return hipErrorOutOfMemory;
     float* csum = db ? slabs + (direct ? 0 : (size_t)splits * N * K) : nullptr;

@@ -172,6 +172,25 @@ static __global__ __launch_bounds__(256) void transpose_f32_kernel(const float* 
     }
 }
 
+// Split count of a register-staged weight-gradient launch (gemm_tn_f32_launch and, with per_cu = 1 and the column-sum row in per_split,
+// gemm_tn_bf16_launch): per_cu workgroups per CU, at least 4 * bkm rows per split, within slab_bytes of workspace (host only, no launch).
+// *capped: the workspace, not the shape, set the count.
+static inline int wgrad_row_splits(int tiles, int per_cu, int bkm, int M, size_t per_split, size_t slab_bytes, int num_cu, bool* capped = nullptr) {
+    int splits = (per_cu * num_cu + tiles - 1) / tiles;
+    const int max_by_rows = (M + 4 * bkm - 1) / (4 * bkm);
+    if (splits > max_by_rows) splits = max_by_rows;
+    if (splits < 1) splits = 1;
+    const int by_shape = splits;
+    while ((size_t)splits * per_split > slab_bytes && splits > 1) --splits;
+    if (capped) *capped = splits != by_shape;
+    return splits;
+}
+// gemm_tn_f32_launch's split count: about two blocks per CU
+template <class Cfg>
+static inline int gemm_tn_f32_splits(int M, int N, int K, int num_cu, size_t slab_bytes, bool* capped = nullptr) {
+    return wgrad_row_splits((N / Cfg::BN) * (K / Cfg::BK), 2, Cfg::BKM, M, (size_t)N * K * 4, slab_bytes, num_cu, capped);
+}
+
 template <class Cfg, class XLoad>
 static hipError_t gemm_tn_f32_launch(const float* dY, long ldy, const XLoad& xl, float* dW, float* slabs, size_t slab_bytes,
                                      int M, int N, int K, int num_cu, int accumulate, hipStream_t stream) {
@@ -179,11 +198,7 @@ static hipError_t gemm_tn_f32_launch(const float* dY, long ldy, const XLoad& xl,
     const int tiles_n = (N + Cfg::BN - 1) / Cfg::BN, tiles_k = (K + Cfg::BK - 1) / Cfg::BK;
     if (N % Cfg::BN != 0 || K % Cfg::BK != 0) return hipErrorInvalidValue;
     const int tiles = tiles_n * tiles_k;
-    int splits = (2 * num_cu + tiles - 1) / tiles;               // about two blocks per CU
-    const int max_by_rows = (M + 4 * Cfg::BKM - 1) / (4 * Cfg::BKM);
-    if (splits > max_by_rows) splits = max_by_rows;
-    if (splits < 1) splits = 1;
-    while ((size_t)splits * N * K * 4 > slab_bytes && splits > 1) --splits;
+    const int splits = gemm_tn_f32_splits<Cfg>(M, N, K, num_cu, slab_bytes);
     const bool direct = splits == 1 && !accumulate;              // a single slab that is not added to anything IS the gradient
     if (!direct && (size_t)splits * N * K * 4 > slab_bytes) return hipErrorOutOfMemory;
     auto kern = gemm_tn_f32_kernel<Cfg, XLoad>;
@@ -355,19 +370,28 @@ static inline bool gemm_tn_f32_dma_ok(const float* dY, long ldy, const float* X,
     return M % TnDmaCfg::BKM == 0 && N % TnDmaCfg::BN == 0 && K % TnDmaCfg::BK == 0 && ldy % 4 == 0 && ldx % 4 == 0 && ((uintptr_t)dY & 15) == 0 &&
            ((uintptr_t)X & 15) == 0;
 }
+// Split count of a DMA-staged launch and the slabs per split (host only, no launch; with_db: the call also sums dY's columns).
+static inline int gemm_tn_f32_dma_splits(int M, int N, int K, int num_cu, size_t slab_bytes, bool with_db, int* per_out) {
+    using Cfg = TnDmaCfg;
+    const int tiles = (N / Cfg::BN) * (K / Cfg::BK);
+    // split count from the model shared with the convolution weight gradients: the q | k | v gradient (48 tiles) took 11 splits = 528 workgroups =
+    // three rounds for 2.06 rounds of work under the "two blocks per CU" rule; 16 splits are three full rounds
+    int per = 0;
+    // with db every split needs N more floats (its column-sum partial row) behind its N x K slab
+    const size_t avail = with_db ? slab_bytes / (size_t)(K + 1) * (size_t)K : slab_bytes;
+    int splits = wgrad_pick_splits(tiles, M / Cfg::BKM, (long)N * K, avail, num_cu, Cfg::LDS_BYTES, Cfg::BKM / 2 * Cfg::TN * Cfg::TK * 64 / 2400.0, 6.0, &per);
+    if (splits < 1) { splits = 1; per = M / Cfg::BKM; }
+    *per_out = per;
+    return splits;
+}
 // db != nullptr: also db[N] (+)= column sums of dY (the layer's bias gradient), summed by the workgroups that stage dY anyway
 static hipError_t gemm_tn_f32_dma_launch(const float* dY, long ldy, const float* X, long ldx, float* dW, float* slabs, size_t slab_bytes, int M, int N,
                                          int K, int num_cu, int accumulate, hipStream_t stream, float* db = nullptr) {
     using Cfg = TnDmaCfg;
     if (!gemm_tn_f32_dma_ok(dY, ldy, X, ldx, M, N, K)) return hipErrorInvalidValue;
     const int tiles_n = N / Cfg::BN, tiles_k = K / Cfg::BK, tiles = tiles_n * tiles_k;
-    // split count from the model shared with the convolution weight gradients: the q | k | v gradient (48 tiles) took 11 splits = 528 workgroups =
-    // three rounds for 2.06 rounds of work under the "two blocks per CU" rule; 16 splits are three full rounds
     int per = 0;
-    // with db every split needs N more floats (its column-sum partial row) behind its N x K slab
-    const size_t avail = db ? slab_bytes / (size_t)(K + 1) * (size_t)K : slab_bytes;
-    int splits = wgrad_pick_splits(tiles, M / Cfg::BKM, (long)N * K, avail, num_cu, Cfg::LDS_BYTES, Cfg::BKM / 2 * Cfg::TN * Cfg::TK * 64 / 2400.0, 6.0, &per);
-    if (splits < 1) { splits = 1; per = M / Cfg::BKM; }
+    const int splits = gemm_tn_f32_dma_splits(M, N, K, num_cu, slab_bytes, db != nullptr, &per);
     const bool direct = splits == 1 && !accumulate;
     const size_t slab_floats = direct ? 0 : (size_t)splits * N * K;
     if ((slab_floats + (db ? (size_t)splits * N : 0)) * 4 > slab_bytes) return hipErrorOutOfMemory;
@@ -385,15 +409,22 @@ static hipError_t gemm_tn_f32_dma_launch(const float* dY, long ldy, const float*
     return hipGetLastError();
 }
 
-static hipError_t colsum_f32_launch(const float* Y, long ldy, float* out, float* part, size_t part_bytes, int M, int N,
-                                    int accumulate, hipStream_t stream) {
-    if (N % 4 != 0) return hipErrorInvalidValue;
+// Partial rows of a column sum over M rows: 512 rows per workgroup row, more where part_bytes cannot hold a partial row each (host only, no launch).
+static inline int colsum_f32_rows(int M, int N, size_t part_bytes, int* rows_per_block_out) {
     int rows_per_block = 512;
     int gy = (M + rows_per_block - 1) / rows_per_block;
     while ((size_t)gy * N * 4 > part_bytes && rows_per_block < (1 << 30)) {
         rows_per_block *= 2;
         gy = (M + rows_per_block - 1) / rows_per_block;
     }
+    *rows_per_block_out = rows_per_block;
+    return gy;
+}
+static hipError_t colsum_f32_launch(const float* Y, long ldy, float* out, float* part, size_t part_bytes, int M, int N,
+                                    int accumulate, hipStream_t stream) {
+    if (N % 4 != 0) return hipErrorInvalidValue;
+    int rows_per_block = 512;
+    const int gy = colsum_f32_rows(M, N, part_bytes, &rows_per_block);
     hipLaunchKernelGGL(colsum_partial_kernel, dim3((N / 4 + 63) / 64, gy), dim3(256), 0, stream, Y, ldy, part, M, N, rows_per_block);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -374,14 +374,29 @@ static inline int pu_chain_resident() {
     return per_cu * prop.multiProcessorCount;
 }
 
+// Which launches pu_chain_launch makes for B rows (host only, no launch; egotap_debug_pu_train_routes reports it): nrb row blocks of 16 rows,
+// the last one holding last_rows; pu_chain_kernel<ut> with nbg workgroups per row block; chunk_rb row blocks per launch (0: the chain kernel
+// cannot run here, the caller walks the steps) and chunks launches.
+struct PuChainRoute { int ut, nbg, nrb, last_rows, chunk_rb, chunks; };
+static inline PuChainRoute pu_chain_route(int resident1, int resident2, int B) {
+    PuChainRoute r;
+    r.nrb = (B + 15) / 16;
+    r.last_rows = B - (r.nrb - 1) * 16;
+    const bool small = r.nrb * 32 <= resident1 && r.nrb <= 8;      // few rows: 16 units per workgroup, twice the workgroups
+    r.ut = small ? 1 : 2;
+    r.nbg = small ? 32 : 16;
+    r.chunk_rb = (small ? resident1 : resident2) / r.nbg;
+    r.chunks = r.chunk_rb < 1 ? 0 : (r.nrb + r.chunk_rb - 1) / r.chunk_rb;
+    return r;
+}
+
 // One PU layer over all J steps of B rows (p.HP: (J - 1) * hp_stride floats, armed here; p.fault: PU_FAULT_WORDS words, zeroed here, one per chunk).
 // resident1/resident2: pu_chain_resident<1/2>().  Returns false when the chain kernel cannot run here (the caller then walks the steps
 // with pu_step_launch).  Every chain launch is followed by its pu_solo_kernel, which does nothing unless the launch faulted.
 static inline bool pu_chain_launch(hipStream_t s, int resident1, int resident2, PuChain p, int B, int debug_drop = 0) {
-    const int nrb = (B + 15) / 16;
-    const bool small = nrb * 32 <= resident1 && nrb <= 8;      // few rows: 16 units per workgroup, twice the workgroups
-    const int nbg = small ? 32 : 16, resident = small ? resident1 : resident2;
-    const int chunk_rb = resident / nbg;
+    const PuChainRoute r = pu_chain_route(resident1, resident2, B);
+    const int nrb = r.nrb, nbg = r.nbg, chunk_rb = r.chunk_rb;
+    const bool small = r.ut == 1;
     if (chunk_rb < 1) return false;
     {   // every gated-state word starts as "not stored yet" (a kernel, so a captured graph re-arms it on every replay)
         const long n = (long)(p.J - 1) * p.hp_stride;

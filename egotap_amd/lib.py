@@ -168,6 +168,8 @@ _PROTOS = {
     "egotap_set_pu_chain": (C.c_int, [C.c_void_p, C.c_int]),
     "egotap_pu_chain_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "egotap_debug_pu_drop_workgroups": (C.c_int, [C.c_void_p, C.c_int]),
+    "egotap_debug_pu_train_routes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "egotap_debug_pu_train_routes_for": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "egotap_debug_gemm_bk": (C.c_int, [C.c_int]),
     "egotap_debug_conv_addressing": (C.c_int, [C.c_int]),
     "egotap_set_weight_scratch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -1253,6 +1255,26 @@ def attention_f32_ksplit(B: int, N: int, heads: int, scratch_floats: int, num_cu
     if k <= 0:
         check(1)
     return k
+
+
+TN_FAMILIES = {0: "none", 1: "f32_big", 2: "f32_small", 3: "f32_dma", 4: "bf16x3", 5: "bf16"}      # egotap_debug.h EGOTAP_TN_*
+PU_WGRADS = ("x2f0", "x2h0", "b2h0", "h2h0", "x2f1", "x2h1", "h2h1")                                   # the order of egotap_train_pu_bwd's grads
+PU_DGRADS = ("step", "x2h1", "x2f1", "b2h0", "x2h0", "x2f0")
+
+
+def pu_train_routes(h, B: int, resident=None, num_cu: int = 256) -> dict:
+    """(test aid, egotap_debug.h) which kernels the PU stage of training launches at batch ``B`` on handle ``h``, as a dictionary: "chain" (0 per
+    step, 1, 2), "chunks", "row_blocks", "last_rows", "colsum_gy", and per GEMM name "wgrad_splits", "wgrad_family" (TN_FAMILIES), "wgrad_capped",
+    "dgrad_splitk".  ``resident`` = None asks the device; (resident1, resident2) with ``num_cu`` is host only."""
+    out = (C.c_int * 32)()
+    if resident is None:
+        check(load().egotap_debug_pu_train_routes(h, B, out, 32))
+    else:
+        check(load().egotap_debug_pu_train_routes_for(h, B, int(resident[0]), int(resident[1]), num_cu, out, 32))
+    v = list(out)
+    return {"chain": v[0], "chunks": v[1], "row_blocks": v[2], "last_rows": v[3], "colsum_gy": v[31],
+            "wgrad_splits": dict(zip(PU_WGRADS, v[4:11])), "wgrad_family": {k: TN_FAMILIES[f] for k, f in zip(PU_WGRADS, v[11:18])},
+            "wgrad_capped": dict(zip(PU_WGRADS, v[18:25])), "dgrad_splitk": dict(zip(PU_DGRADS, v[25:31]))}
 
 
 def attention_f32_split(qkv, B: int, N: int, heads: int, scratch, scratch_floats: int, num_cu: int = 256, out=None):

@@ -68,6 +68,23 @@ int egotap_debug_predict_pose_rgb_intermediate(egotap_handle h, int B, int chunk
 int egotap_debug_wgrad_splits(int tiles, int64_t slabs, int64_t n_floats, size_t slab_bytes, int num_cu, int lds_bytes, double slab_us, double fixed_us,
                               int* per);
 
+/* (test aid) which kernels the PU stage of training (egotap_train_pu_fwd, egotap_train_pu_bwd) launches at batch B on this handle: the batch alone
+ * picks them, and the answers come from the predicates the launches themselves call.  out[n >= EGOTAP_PU_ROUTE_WORDS]:
+ *   CHAIN        0 = per-step kernels, 1 = pu_chain_kernel<1>, 2 = pu_chain_kernel<2>;  CHUNKS = chain launches per layer (0 per step)
+ *   ROW_BLOCKS   ceil(B / 16);  LAST_ROWS = rows of the last row block
+ *   WGRAD_*[7]   weight gradients in the order of the grads argument (x2f0, x2h0, b2h0, h2h0, x2f1, x2h1, h2h1): SPLITS of the J * B rows,
+ *                FAMILY (EGOTAP_TN_*), CAPPED = 1 when the workspace, not the shape, set the split count
+ *   DGRAD_SPLITK[6]  input gradients (one step of the recurrence, x2h1, x2f1, b2h0, x2h0, x2f0): 1 = K split over the CUs
+ *   COLSUM_GY    partial rows of the bias gradients' column sums over J * B rows
+ * The first form asks the device (resident workgroups of the chain kernels, CU count; follows egotap_set_pu_chain and the handle's precision);
+ * _for is host only: the caller states them. */
+enum { EGOTAP_PU_ROUTE_CHAIN = 0, EGOTAP_PU_ROUTE_CHUNKS = 1, EGOTAP_PU_ROUTE_ROW_BLOCKS = 2, EGOTAP_PU_ROUTE_LAST_ROWS = 3, EGOTAP_PU_ROUTE_WGRAD_SPLITS = 4,
+       EGOTAP_PU_ROUTE_WGRAD_FAMILY = 11, EGOTAP_PU_ROUTE_WGRAD_CAPPED = 18, EGOTAP_PU_ROUTE_DGRAD_SPLITK = 25, EGOTAP_PU_ROUTE_COLSUM_GY = 31,
+       EGOTAP_PU_ROUTE_WORDS = 32 };
+enum { EGOTAP_TN_NONE = 0, EGOTAP_TN_F32_BIG = 1, EGOTAP_TN_F32_SMALL = 2, EGOTAP_TN_F32_DMA = 3, EGOTAP_TN_BF16X3 = 4, EGOTAP_TN_BF16 = 5 };
+int egotap_debug_pu_train_routes(egotap_handle h, int B, int* out, int n);
+int egotap_debug_pu_train_routes_for(egotap_handle h, int B, int resident1, int resident2, int num_cu, int* out, int n);
+
 /* ---- measurement hooks (bench.py roofline) ---- */
 /* when enabled, every GEMM launch of the handle is bracketed by HIP events on the caller's stream */
 int egotap_timing_enable(egotap_handle h, int enable);

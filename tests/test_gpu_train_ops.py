@@ -1,5 +1,4 @@
 """GPU parity of the training-step operators (C ABI) against float64 torch autograd on the CPU."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -271,55 +270,19 @@ def test_adamw_multi_tensor_launch_matches_torch_on_ragged_segments():
 
 
 def test_pu_chain_and_pose_head_backward():
-    """SkelNet(PU) + pose head: forward in training mode and full backward vs autograd of the oracle"""
-    from egotap_amd import lib as L, train_ops as T
-    from oracle import lift_ref as O
-    h, net, p = _handle()
-    B, J, hid, H = 3, p.n_joints_hm, p.hidden, p.pu_hidden
-    posz, rotz, dpose = _rand((B * 2 * J, hid), 61), _rand((B * 2 * J, hid), 62), _rand((B, 16, 3), 63)
-    sd64 = {k: v.detach().cpu().double() for k, v in net.state_dict().items() if v.is_floating_point()}
-    keys = [k for k in sd64 if k.startswith("skel_sequential_layer.") or k.startswith("pose_mlp.") or k.startswith("global_mlp.")]
-    leaves = {k: sd64[k].clone().requires_grad_(True) for k in keys}
-    sdr = dict(sd64); sdr.update(leaves)
-    pz, rz = posz.double().requires_grad_(True), rotz.double().requires_grad_(True)
-    pos_j, rot_j = O.stereo_interleave(pz, B, p), O.stereo_interleave(rz, B, p)
-    skel = O.pu_chain(pos_j.transpose(0, 1), rot_j.transpose(0, 1), sdr)
-    pose_ref = O.pose_head(pos_j, skel, sdr, p)
-    pose_ref.backward(dpose.double())
-    # GPU
-    lib = L.load()
-    nb, off = C.c_size_t(), C.c_size_t()
-    L.check(lib.egotap_train_pu_saved_bytes(h, B, C.byref(nb), C.byref(off)))
-    saved = torch.empty(nb.value, dtype=torch.uint8, device="cuda")
-    pc, rc = posz.cuda(), rotz.cuda()
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    L.check(lib.egotap_train_pu_fwd(h, T._p(pc), T._p(rc), B, T._p(saved), saved.numel(), st))
-    hs1 = saved[off.value: off.value + 4 * J * B * H].view(torch.float32)
-    _close(hs1.reshape(J, B, H), skel.detach(), 2e-6)
-    pose = torch.empty((B, 16, 3), device="cuda")
-    L.check(lib.egotap_train_pose_head_fwd(h, T._p(pc), T._p(hs1), B, T._p(pose), st))
-    _close(pose, pose_ref.detach(), 3e-6)
-    dposz, dhs1, drotz = torch.empty_like(pc), torch.empty(J * B * H, device="cuda"), torch.empty_like(rc)
-    g = {k: torch.zeros_like(net.state_dict()[k]) for k in keys}
-    dpose_dev = dpose.cuda()                  # (kept alive: the call takes a raw pointer)
-    L.check(lib.egotap_train_pose_head_bwd(h, T._p(pc), T._p(hs1), T._p(dpose_dev), B, T._p(dposz), T._p(dhs1),
-                                           T._p(g["pose_mlp.pose_fcs.0.weight"]), T._p(g["pose_mlp.pose_fcs.0.bias"]),
-                                           T._p(g["global_mlp.pose_fcs.0.weight"]), T._p(g["global_mlp.pose_fcs.0.bias"]), 0, st))
-    wsb = C.c_size_t()
-    L.check(lib.egotap_train_pu_bwd_ws_bytes(h, B, C.byref(wsb)))
-    ws = torch.empty(wsb.value, dtype=torch.uint8, device="cuda")
-    order = ["0.x2f", "0.x2h", "0.b2h", "0.h2h", "1.x2f", "1.x2h", "1.h2h"]
-    ptrs = (C.c_void_p * 14)()
-    for i, nme in enumerate(order):
-        ptrs[2 * i] = g[f"skel_sequential_layer.lstm_custom.layers.{nme}.weight"].data_ptr()
-        ptrs[2 * i + 1] = g[f"skel_sequential_layer.lstm_custom.layers.{nme}.bias"].data_ptr()
-    L.check(lib.egotap_train_pu_bwd(h, T._p(pc), T._p(rc), B, T._p(saved), T._p(dhs1), T._p(dposz), T._p(drotz), ptrs, 0, T._p(ws),
-                                    ws.numel(), st))
-    torch.cuda.synchronize()
-    _close(dposz, pz.grad, 2e-6, rtol=1e-3, msg="dposz")
-    _close(drotz, rz.grad, 2e-6, rtol=1e-3, msg="drotz")
+    """SkelNet(PU) + pose head: forward in training mode and full backward vs autograd of the oracle (the case, its inputs and the C ABI calls are
+    tests/pu_train_cases.py; tests/test_gpu_pu_train_batches.py runs it at the batch sizes that take the other kernels).  Every output starts as NaN."""
+    import pu_train_cases as P
+    B = 3
+    ref, got = P.reference("UnrealEgo", B, torch.float64), P.run_gpu("UnrealEgo", B, "f32", 0, True)
+    _close(got["skel"], ref["skel"], 2e-6)
+    _close(got["pose"], ref["pose"], 3e-6)
+    _close(got["dposz"], ref["dposz"], 2e-6, rtol=1e-3, msg="dposz")
+    _close(got["drotz"], ref["drotz"], 2e-6, rtol=1e-3, msg="drotz")
+    keys = [k for k in ref if k not in P.DATA]
+    assert len(keys) == 18
     for k in keys:
-        _close(g[k], leaves[k].grad, 3e-6, rtol=2e-3, msg=k)
+        _close(got[k], ref[k], 3e-6, rtol=2e-3, msg=k)
 
 
 # ---- weight-gradient / training GEMMs on the bf16 matrix cores (gemm_tn_bf16.h, gemm_bf16.h) selected by the handle's precision
