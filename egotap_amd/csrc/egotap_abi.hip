@@ -1098,6 +1098,7 @@ static int hm_resolve(Handle* h, int net) {
 // bytes of the caller's workspace) and read there as camera bytes
 // with maps (egotap_predict_pose_lens only): the frames are another lens's; the piece is gathered into the same slice through the two lens maps, an
 // eye's fill where a map has no source -- rect and mirror say where the keypoints come out and are not read by the gather
+// with map_streams > 0 (egotap_predict_pose_lens_streams only): each map pointer is a table of that many maps and frame b of the batch reads map b % map_streams
 struct HmSensor {
     const unsigned char *left8, *right8;
     FrameSource src;
@@ -1105,6 +1106,7 @@ struct HmSensor {
     const int *map_left, *map_right;
     unsigned fill[2];
     unsigned char* slice;
+    int map_streams;
 };
 struct HmSrc {
     const float *left, *right;
@@ -1848,8 +1850,9 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
         unsigned char* s8l = sensor.slice;
         const long frame = sensor.src.frame_stride;
         const bool gather = sensor.map_left != nullptr;
-        const char* const role = gather ? "lens_remap" : sensor.src.fetch == FETCH_RGB8 ? "rgb_u8_resize" : "yuv_u8_resize";      // the timing hook's names
-        const char* const kernel = gather ? "lens_remap_kernel" : sensor.src.fetch == FETCH_RGB8 ? "rgb_u8_resize_kernel" : "yuv_u8_resize_kernel";
+        const bool per_stream = gather && sensor.map_streams > 0;
+        const char* const role = per_stream ? "lens_remap_streams" : gather ? "lens_remap" : sensor.src.fetch == FETCH_RGB8 ? "rgb_u8_resize" : "yuv_u8_resize";      // the timing hook's names
+        const char* const kernel = per_stream ? "lens_remap_streams_kernel" : gather ? "lens_remap_kernel" : sensor.src.fetch == FETCH_RGB8 ? "rgb_u8_resize_kernel" : "yuv_u8_resize_kernel";
         for (int lo = 0; lo < B; lo += c) {
             const int n = B - lo < c ? B - lo : c;
             HmSrc piece = whole.at(lo, rgb);
@@ -1857,7 +1860,10 @@ static int predict_pose_rgb_impl(const char* who, egotap_handle h, const HmSrc& 
                 unsigned char* s8r = s8l + (size_t)n * rgb;
                 const unsigned char *fl = sensor.left8 + lo * frame, *fr = sensor.right8 + lo * frame;
                 GemmTimer t(h, (hipStream_t)stream, role, kernel, 0.0);
-                if (gather)
+                if (per_stream)      // the piece's first frame is frame `lo` of the batch: its frames read maps (lo + b) % S
+                    EGO_HIP(lens_remap_streams_launch(fl, fr, n, sensor.src, sensor.map_left, sensor.map_right, sensor.map_streams, (long)lo, sensor.fill[0],
+                                                      sensor.fill[1], 4 * S, s8l, s8r, device_cu_count(), (hipStream_t)stream));
+                else if (gather)
                     EGO_HIP(lens_remap_launch(fl, fr, n, sensor.src, sensor.map_left, sensor.map_right, sensor.fill[0], sensor.fill[1], 4 * S, s8l, s8r,
                                               device_cu_count(), (hipStream_t)stream));
                 else
@@ -2045,14 +2051,15 @@ static const char* const kNullRectsOrMirrors = "null rectangles or mirror flags 
 // brings the maps and fills of a gather.  `in_place`: the u8 entry's identity request, the caller's frames ARE the camera bytes.
 static int predict_pose_sensor_impl(const char* who, egotap_handle h, const char* why, const uint8_t* left8, const uint8_t* right8, int B, const FrameSource& fs,
                                     const int* rects, const int32_t* mirrors, const egotap_lens_source* lens, bool in_place, const float* table, float* pose,
-                                    float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs) {
+                                    float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints, float* limbs,
+                                    int lens_streams = 0) {
     if (!why) why = rgb_u8_refusal(left8, right8, table, false);
     const int rc = rgb_entry_checks(who, h, B, why, nullptr, pose, heatmaps, chunk, ws, true, kp, keypoints, limbs);
     if (rc != EGOTAP_OK) return rc;
     // (q.slice is the walk's to place: the workspace layout is read there, once)
     HmSensor q{left8, right8, fs, {{rects[0], rects[1], rects[2], rects[3]}, {rects[4], rects[5], rects[6], rects[7]}}, {mirrors[0] ? 1 : 0, mirrors[1] ? 1 : 0},
                lens ? (const int*)lens->map_left : nullptr, lens ? (const int*)lens->map_right : nullptr,
-               {lens ? lens_fill(lens->fill[0]) : 0u, lens ? lens_fill(lens->fill[1]) : 0u}, nullptr};
+               {lens ? lens_fill(lens->fill[0]) : 0u, lens ? lens_fill(lens->fill[1]) : 0u}, nullptr, lens ? lens_streams : 0};
     HmSrc src{nullptr, nullptr, in_place ? left8 : nullptr, in_place ? right8 : nullptr, table, nullptr};
     src.sensor = &q;
     float affine[8];
@@ -2183,20 +2190,27 @@ extern "C" int egotap_predict_pose_lens_workspace_bytes(egotap_handle h, int B, 
     *bytes = rgb_ws(h, B > 0 ? B : 1, chunk, RGB_SRC_SENSOR).total;      // the sensor entry's: the slice holds OUTPUT frames
     return EGOTAP_OK;
 }
+// what is wrong with the number of streams of a batch of B frames, or nullptr (B <= 0 is the entry's own refusal)
+static const char* lens_streams_refusal(int B, int S) {
+    if (S < 1 || S > EGOTAP_MAX_STREAM_RIGS) return "the number of streams S must be between 1 and 4096 (map_left and map_right hold S maps each)";
+    if (B > 0 && B % S != 0) return "the batch B must be a multiple of the number of streams S (frame b is gathered through map b % S)";
+    return nullptr;
+}
 // the sensor entry with the descriptor in place of H, W, rectangles and mirrors; never the identity request: a lens source always gathers.  The
 // keypoints come out in the model camera's calibration pixels: the sensor entry's affine on a frame of that size, the full rectangle, the eye's
-// mirror flag
+// mirror flag.  `streams`: the _streams entries, S maps per eye (otherwise one map per eye and S is not read)
 static int predict_pose_lens_entry(const char* who, egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* lsrc,
                                    const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, bool kp, float* keypoints,
-                                   float* limbs) {
+                                   float* limbs, bool streams = false, int S = 0) {
     FrameSource fs{};
     const char* why = lens_source_refusal(lsrc, left8, right8, &fs);
+    if (!why && streams) why = lens_streams_refusal(B, S);
     if (!why && (lsrc->model_h < 1 || lsrc->model_w < 1 || lsrc->model_h > kResizeMaxSrc || lsrc->model_w > kResizeMaxSrc))
         why = "the model camera's calibration image (model_h, model_w) must be between 1 and 16384 on each side";
     const int mw = why ? 0 : lsrc->model_w, mh = why ? 0 : lsrc->model_h;      // (a refused descriptor may be NULL)
     const int full[8] = {0, 0, mw, mh, 0, 0, mw, mh};
     return predict_pose_sensor_impl(who, h, why, left8, right8, B, fs, full, why ? nullptr : lsrc->mirror, lsrc, false, table, pose, heatmaps, chunk, ws, ws_bytes,
-                                    stream, kp, keypoints, limbs);
+                                    stream, kp, keypoints, limbs, streams ? S : 0);
 }
 extern "C" int egotap_predict_pose_lens(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, const float* table,
                                         float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {
@@ -2302,18 +2316,27 @@ extern "C" int egotap_ocam_unproject(const float* points2d, int N, const egotap_
     return ocam_points_entry("egotap_ocam_unproject", false, points2d, N, model, rays, stream);
 }
 
+// the sizes and the pose rows, as the single-rig and the per-stream entries refuse them alike
+static int stereo_batch_checks(const char* who, int B, int J) {
+    EGO_CHECK(B > 0 && J > 0, "%s: the batch and the number of joints must be positive (B = %d, J = %d)", who, B, J);
+    EGO_CHECK(J <= kStereoMaxJoints, "%s: at most %d joints, one lane each (J = %d)", who, kStereoMaxJoints, J);
+    return EGOTAP_OK;
+}
+static int stereo_pose_rows_check(const char* who, bool has_pose, int J, int P, int pose_row0) {
+    if (has_pose) EGO_CHECK(pose_row0 >= 0 && (int64_t)pose_row0 + J <= P, "%s: pose rows pose_row0 .. pose_row0 + J - 1 = %d .. %lld are not inside the P = %d rows", who,
+                            pose_row0, (long long)pose_row0 + J - 1, P);
+    return EGOTAP_OK;
+}
 // what egotap_stereo_triangulate and egotap_stereo_fuse check alike, after their own pointers: the sizes, the two models, the pose rows, and the rig as the
 // kernels take it (R NULL: identity, affine NULL: identity) with everything in it finite
 static int stereo_rig_checks(const char* who, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t, const double* affine,
                              double min_score, bool has_pose, int P, int pose_row0, StereoRig& rig) {
-    EGO_CHECK(B > 0 && J > 0, "%s: the batch and the number of joints must be positive (B = %d, J = %d)", who, B, J);
-    EGO_CHECK(J <= kStereoMaxJoints, "%s: at most %d joints, one lane each (J = %d)", who, kStereoMaxJoints, J);
+    if (int rc = stereo_batch_checks(who, B, J)) return rc;
     const char* why = ocam_refusal(left);
     EGO_CHECK(!why, "%s: left: %s", who, why);
     why = ocam_refusal(right);
     EGO_CHECK(!why, "%s: right: %s", who, why);
-    if (has_pose) EGO_CHECK(pose_row0 >= 0 && (int64_t)pose_row0 + J <= P, "%s: pose rows pose_row0 .. pose_row0 + J - 1 = %d .. %lld are not inside the P = %d rows", who,
-                            pose_row0, (long long)pose_row0 + J - 1, P);
+    if (int rc = stereo_pose_rows_check(who, has_pose, J, P, pose_row0)) return rc;
     rig.cam[0] = ocam_clean(*left);
     rig.cam[1] = ocam_clean(*right);
     bool fin = ego_finite(min_score);
@@ -2322,6 +2345,15 @@ static int stereo_rig_checks(const char* who, int B, int J, const egotap_ocam* l
     for (int k = 0; k < 8; ++k) fin = fin && ego_finite(rig.aff[k / 4][k % 4] = affine ? affine[k] : (k & 1 ? 0.0 : 1.0));
     rig.min_score = min_score;
     EGO_CHECK(fin, "%s: R, t, affine and min_score must be finite", who);
+    return EGOTAP_OK;
+}
+
+static int stereo_triangulate_overlap_check(const char* who, const float* keypoints, int B, int J, const float* pose, int P, const float* joints3d, const float* frame) {
+    const size_t kp_bytes = (size_t)B * 2 * J * 16, pose_bytes = pose ? (size_t)B * P * 12 : 0, j3_bytes = (size_t)B * J * 32, fr_bytes = (size_t)B * 32;
+    EGO_CHECK(!ego_overlap(joints3d, j3_bytes, keypoints, kp_bytes) && !ego_overlap(joints3d, j3_bytes, pose, pose_bytes) &&
+                  !ego_overlap(frame, fr_bytes, keypoints, kp_bytes) && !ego_overlap(frame, fr_bytes, pose, pose_bytes) &&
+                  !ego_overlap(joints3d, j3_bytes, frame, fr_bytes),
+              "%s: joints3d and frame must not overlap keypoints, pose or each other", who);
     return EGOTAP_OK;
 }
 
@@ -2334,27 +2366,15 @@ extern "C" int egotap_stereo_triangulate(const float* keypoints, int B, int J, c
               "%s: keypoints, joints3d and frame must be 16-byte aligned, pose 4-byte aligned", who);
     StereoRig rig;
     if (int rc = stereo_rig_checks(who, B, J, left, right, R, t, affine, min_score, pose != nullptr, P, pose_row0, rig)) return rc;
-    const size_t kp_bytes = (size_t)B * 2 * J * 16, pose_bytes = pose ? (size_t)B * P * 12 : 0, j3_bytes = (size_t)B * J * 32, fr_bytes = (size_t)B * 32;
-    EGO_CHECK(!ego_overlap(joints3d, j3_bytes, keypoints, kp_bytes) && !ego_overlap(joints3d, j3_bytes, pose, pose_bytes) &&
-                  !ego_overlap(frame, fr_bytes, keypoints, kp_bytes) && !ego_overlap(frame, fr_bytes, pose, pose_bytes) &&
-                  !ego_overlap(joints3d, j3_bytes, frame, fr_bytes),
-              "%s: joints3d and frame must not overlap keypoints, pose or each other", who);
+    if (int rc = stereo_triangulate_overlap_check(who, keypoints, B, J, pose, P, joints3d, frame)) return rc;
     GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_triangulate", "stereo_triangulate_kernel", 0.0);
     EGO_HIP(stereo_triangulate_launch(keypoints, B, J, rig, pose, P, pose_row0, joints3d, frame, (hipStream_t)stream));
     return EGOTAP_OK;
 }
 
-// the lifted joints fused with the keypoint rays (stereo_fuse.h): one operator behind the triangulation, no handle
-extern "C" int egotap_stereo_fuse(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
-                                  const double* affine, double min_score, const float* pose, int P, int pose_row0, const float* frame,
-                                  const egotap_fuse_params* params, float* fused, float* pose_fused, float* stats, void* stream) {
-    static const char* const who = "egotap_stereo_fuse";
-    EGO_CHECK(keypoints && t && pose && frame && params && fused && pose_fused && stats,
-              "%s: null argument (keypoints, t, pose, frame, params, fused, pose_fused and stats are required; R and affine may be NULL)", who);
-    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)frame | (uintptr_t)fused | (uintptr_t)stats) & 15) == 0 && (((uintptr_t)pose | (uintptr_t)pose_fused) & 3) == 0,
-              "%s: keypoints, frame, fused and stats must be 16-byte aligned, pose and pose_fused 4-byte aligned", who);
-    StereoRig rig;
-    if (int rc = stereo_rig_checks(who, B, J, left, right, R, t, affine, min_score, true, P, pose_row0, rig)) return rc;
+// what egotap_stereo_fuse and egotap_stereo_fuse_streams check alike after the rig: the parameters (copied into `prm` as the kernel takes them) and the overlaps
+static int stereo_fuse_arg_checks(const char* who, const float* keypoints, int B, int J, const float* pose, int P, const float* frame, const egotap_fuse_params* params,
+                                  const float* fused, const float* pose_fused, const float* stats, egotap_fuse_params& prm) {
     const egotap_fuse_params& q = *params;
     EGO_CHECK(ego_finite(q.sigma_ray) && q.sigma_ray > 0.0, "%s: params: sigma_ray must be finite and > 0 (%g)", who, q.sigma_ray);
     EGO_CHECK(ego_finite(q.sigma_prior) && q.sigma_prior > 0.0, "%s: params: sigma_prior must be finite and > 0 (%g)", who, q.sigma_prior);
@@ -2373,7 +2393,23 @@ extern "C" int egotap_stereo_fuse(const float* keypoints, int B, int J, const eg
         }
         for (int p = o + 1; p < 3; ++p) EGO_CHECK(!ego_overlap(out[o].p, out[o].n, out[p].p, out[p].n), "%s: %s overlaps %s", who, out[o].name, out[p].name);
     }
-    egotap_fuse_params prm = {q.sigma_ray, q.sigma_prior, q.max_sigma, q.min_joints};
+    prm = egotap_fuse_params{q.sigma_ray, q.sigma_prior, q.max_sigma, q.min_joints};
+    return EGOTAP_OK;
+}
+
+// the lifted joints fused with the keypoint rays (stereo_fuse.h): one operator behind the triangulation, no handle
+extern "C" int egotap_stereo_fuse(const float* keypoints, int B, int J, const egotap_ocam* left, const egotap_ocam* right, const double* R, const double* t,
+                                  const double* affine, double min_score, const float* pose, int P, int pose_row0, const float* frame,
+                                  const egotap_fuse_params* params, float* fused, float* pose_fused, float* stats, void* stream) {
+    static const char* const who = "egotap_stereo_fuse";
+    EGO_CHECK(keypoints && t && pose && frame && params && fused && pose_fused && stats,
+              "%s: null argument (keypoints, t, pose, frame, params, fused, pose_fused and stats are required; R and affine may be NULL)", who);
+    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)frame | (uintptr_t)fused | (uintptr_t)stats) & 15) == 0 && (((uintptr_t)pose | (uintptr_t)pose_fused) & 3) == 0,
+              "%s: keypoints, frame, fused and stats must be 16-byte aligned, pose and pose_fused 4-byte aligned", who);
+    StereoRig rig;
+    if (int rc = stereo_rig_checks(who, B, J, left, right, R, t, affine, min_score, true, P, pose_row0, rig)) return rc;
+    egotap_fuse_params prm;
+    if (int rc = stereo_fuse_arg_checks(who, keypoints, B, J, pose, P, frame, params, fused, pose_fused, stats, prm)) return rc;
     GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_fuse", "stereo_fuse_kernel", 0.0);
     EGO_HIP(stereo_fuse_launch(keypoints, B, J, rig, pose, P, pose_row0, frame, prm, fused, pose_fused, stats, (hipStream_t)stream));
     return EGOTAP_OK;
@@ -3949,5 +3985,95 @@ extern "C" int egotap_overlay_u8(const uint8_t* left8, const uint8_t* right8, in
     GemmTimer tm(g_timing_handle, (hipStream_t)stream, "overlay_u8", "overlay_u8_kernel", 0.0);
     EGO_HIP(overlay_u8_launch(el, er, E, B, Hc, Wc, heat8, S, marks, st, device_cu_count(), (hipStream_t)stream));
     return EGOTAP_OK;
+}
+
+// ---- a camera rig per stream (ocam.h, stereo_fuse.h, lens_remap.h): a table of S rigs, or S lens maps per eye, in device memory; frame b of a
+// time-major batch is served by rig or map b % S.  The entries stand last in part 0's text, behind every kernel the other entries reference.
+extern "C" int egotap_stereo_rigs_check(const egotap_stereo_rig* rigs_host, int S) {
+    static const char* const who = "egotap_stereo_rigs_check";
+    EGO_CHECK(rigs_host, "%s: null rig table (rigs_host is S egotap_stereo_rig in host memory)", who);
+    EGO_CHECK(S >= 1 && S <= EGOTAP_MAX_STREAM_RIGS, "%s: the number of streams must be between 1 and %d (S = %d)", who, EGOTAP_MAX_STREAM_RIGS, S);
+    for (int s = 0; s < S; ++s) {
+        const egotap_stereo_rig& r = rigs_host[s];
+        const char* why = ocam_refusal(&r.left);
+        EGO_CHECK(!why, "%s: rig %d: left: %s", who, s, why);
+        why = ocam_refusal(&r.right);
+        EGO_CHECK(!why, "%s: rig %d: right: %s", who, s, why);
+        bool fin = true;
+        for (int k = 0; k < 9; ++k) fin = fin && ego_finite(r.R[k]);
+        EGO_CHECK(fin, "%s: rig %d: R must be finite", who, s);
+        for (int k = 0; k < 3; ++k) fin = fin && ego_finite(r.t[k]);
+        EGO_CHECK(fin, "%s: rig %d: t must be finite", who, s);
+        for (int k = 0; k < 8; ++k) fin = fin && ego_finite(r.affine[k / 4][k % 4]);
+        EGO_CHECK(fin, "%s: rig %d: affine must be finite", who, s);
+        EGO_CHECK(ego_finite(r.min_score), "%s: rig %d: min_score must be finite", who, s);
+    }
+    return EGOTAP_OK;
+}
+// what the two per-stream stereo entries refuse about the table and the batch, after the sizes
+static int stereo_rig_table_checks(const char* who, int B, const egotap_stereo_rig* rigs_dev, int S) {
+    EGO_CHECK(rigs_dev, "%s: null rig table (rigs_dev is S egotap_stereo_rig in device memory)", who);
+    EGO_CHECK(((uintptr_t)rigs_dev & 7) == 0, "%s: the rig table (rigs_dev) must be 8-byte aligned", who);
+    EGO_CHECK(S >= 1 && S <= EGOTAP_MAX_STREAM_RIGS, "%s: the number of streams must be between 1 and %d (S = %d)", who, EGOTAP_MAX_STREAM_RIGS, S);
+    EGO_CHECK(B % S == 0, "%s: the batch must be a multiple of the number of streams: frame b uses rig b %% S (B = %d, S = %d)", who, B, S);
+    return EGOTAP_OK;
+}
+extern "C" int egotap_stereo_triangulate_streams(const float* keypoints, int B, int J, const egotap_stereo_rig* rigs_dev, int S, const float* pose, int P,
+                                                 int pose_row0, float* joints3d, float* frame, void* stream) {
+    static const char* const who = "egotap_stereo_triangulate_streams";
+    EGO_CHECK(keypoints && joints3d && frame, "%s: null argument (keypoints, joints3d and frame are required; pose may be NULL)", who);
+    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)joints3d | (uintptr_t)frame) & 15) == 0 && ((uintptr_t)pose & 3) == 0,
+              "%s: keypoints, joints3d and frame must be 16-byte aligned, pose 4-byte aligned", who);
+    if (int rc = stereo_batch_checks(who, B, J)) return rc;
+    if (int rc = stereo_rig_table_checks(who, B, rigs_dev, S)) return rc;
+    if (int rc = stereo_pose_rows_check(who, pose != nullptr, J, P, pose_row0)) return rc;
+    if (int rc = stereo_triangulate_overlap_check(who, keypoints, B, J, pose, P, joints3d, frame)) return rc;
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_triangulate_streams", "stereo_triangulate_streams_kernel", 0.0);
+    EGO_HIP(stereo_triangulate_streams_launch(keypoints, B, J, (const StereoRig*)rigs_dev, S, pose, P, pose_row0, joints3d, frame, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_stereo_fuse_streams(const float* keypoints, int B, int J, const egotap_stereo_rig* rigs_dev, int S, const float* pose, int P, int pose_row0,
+                                          const float* frame, const egotap_fuse_params* params, float* fused, float* pose_fused, float* stats, void* stream) {
+    static const char* const who = "egotap_stereo_fuse_streams";
+    EGO_CHECK(keypoints && pose && frame && params && fused && pose_fused && stats,
+              "%s: null argument (keypoints, pose, frame, params, fused, pose_fused and stats are required)", who);
+    EGO_CHECK((((uintptr_t)keypoints | (uintptr_t)frame | (uintptr_t)fused | (uintptr_t)stats) & 15) == 0 && (((uintptr_t)pose | (uintptr_t)pose_fused) & 3) == 0,
+              "%s: keypoints, frame, fused and stats must be 16-byte aligned, pose and pose_fused 4-byte aligned", who);
+    if (int rc = stereo_batch_checks(who, B, J)) return rc;
+    if (int rc = stereo_rig_table_checks(who, B, rigs_dev, S)) return rc;
+    if (int rc = stereo_pose_rows_check(who, true, J, P, pose_row0)) return rc;
+    egotap_fuse_params prm;
+    if (int rc = stereo_fuse_arg_checks(who, keypoints, B, J, pose, P, frame, params, fused, pose_fused, stats, prm)) return rc;
+    GemmTimer tm(g_timing_handle, (hipStream_t)stream, "stereo_fuse_streams", "stereo_fuse_streams_kernel", 0.0);
+    EGO_HIP(stereo_fuse_streams_launch(keypoints, B, J, (const StereoRig*)rigs_dev, S, pose, P, pose_row0, frame, prm, fused, pose_fused, stats, (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_lens_remap_streams(const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S, int S0, uint8_t* out_left8,
+                                         uint8_t* out_right8, void* stream) {
+    FrameSource q{};
+    const char* why = lens_source_refusal(src, left8, right8, &q);
+    if (!why) why = lens_streams_refusal(B, S);
+    const int rc = sensor_op_checks("egotap_lens_remap_streams", B, S0, why, out_left8, out_right8);
+    if (rc != EGOTAP_OK) return rc;
+    EGO_HIP(lens_remap_streams_launch(left8, right8, B, q, (const int*)src->map_left, (const int*)src->map_right, S, 0L, lens_fill(src->fill[0]),
+                                      lens_fill(src->fill[1]), S0, out_left8, out_right8, device_cu_count(), (hipStream_t)stream));
+    return EGOTAP_OK;
+}
+extern "C" int egotap_predict_pose_lens_streams(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S,
+                                                const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream) {
+    return predict_pose_lens_entry("egotap_predict_pose_lens_streams", h, left8, right8, B, src, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false, nullptr,
+                                   nullptr, true, S);
+}
+extern "C" int egotap_predict_pose_lens_streams_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S,
+                                                   const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
+                                                   float* keypoints) {
+    return predict_pose_lens_entry("egotap_predict_pose_lens_streams_kp", h, left8, right8, B, src, table, pose, heatmaps, chunk, ws, ws_bytes, stream, true,
+                                   keypoints, nullptr, true, S);
+}
+extern "C" int egotap_predict_pose_lens_streams_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S,
+                                                    const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream,
+                                                    float* keypoints, float* limbs) {
+    return predict_pose_lens_entry("egotap_predict_pose_lens_streams_kpl", h, left8, right8, B, src, table, pose, heatmaps, chunk, ws, ws_bytes, stream, false,
+                                   keypoints, limbs, true, S);
 }
 #endif

@@ -6,6 +6,9 @@
 //       workgroup.  Each lane unprojects its joint through both cameras, intersects the two rays (closest approach) and leaves (valid, X, pose row, gap)
 //       in LDS; every lane then adds the frame's sums from LDS in ASCENDING joint order (same address for all lanes: a broadcast read), so the host
 //       restatement, which adds in that order, gets the same bits.  Lane = joint writes its record as two 16-byte stores, lane 0 the frame record.
+//   stereo_triangulate_streams_kernel  the same body with a rig PER STREAM: a table of S StereoRig in device memory (egotap.h egotap_stereo_rig), the
+//       wave of frame b reads rig b % S -- a wave-uniform index, so the rig's doubles are plain uniform loads, fetched once per wave -- and n_pol is
+//       clamped to the array's length: whatever the table holds, no load leaves it.  Same records in the same bits as the by-value kernel with that rig.
 // The models, R, t and the affines travel by value in the kernel arguments (uniform indices: scalar loads).  Contraction is off in every function here:
 // the definitions (egotap.h, spec.py ocam_world2cam_ref / ocam_cam2world_ref / stereo_triangulate_ref) keep products and sums apart, and each polynomial is
 // the reference's running-power sum (r_i *= r; z += r_i * pol[i]), not Horner.  sqrt and the divisions are correctly rounded; atan is the library's.
@@ -21,6 +24,8 @@ struct StereoRig {
     egotap_ocam cam[2];
     double R[9], t[3], aff[2][4], min_score;
 };
+static_assert(sizeof(StereoRig) == sizeof(egotap_stereo_rig) && alignof(StereoRig) == alignof(egotap_stereo_rig),
+              "a row of the caller's rig table (egotap.h egotap_stereo_rig) is read as a StereoRig");
 
 static __device__ __forceinline__ double ocam_poly(const double* coef, int n, double r) {
 #pragma clang fp contract(off)
@@ -53,6 +58,9 @@ static __device__ __forceinline__ void ocam_project_one(const egotap_ocam& m, do
     if (flip) v = m.yc * 2.0 - v;
 }
 
+// CLAMP: the model was read from device memory the library cannot inspect (a rig table): n_pol is held to the array's length, so whatever the table
+// holds no load leaves the model.  A model passed by value was checked on the host and is read as it stands.
+template <bool CLAMP = false>
 static __device__ __forceinline__ void ocam_unproject_one(const egotap_ocam& m, double u, double v, double (&ray)[3]) {
 #pragma clang fp contract(off)
     const bool flip = m.ue_flip != 0.0;
@@ -62,7 +70,7 @@ static __device__ __forceinline__ void ocam_unproject_one(const egotap_ocam& m, 
     const double xp = invdet * (du - m.d * dv);
     const double yp = invdet * (-m.e * du + m.c * dv);
     const double r = sqrt(xp * xp + yp * yp);
-    const double zp = ocam_poly(m.pol, m.n_pol, r);
+    const double zp = ocam_poly(m.pol, CLAMP && m.n_pol > EGOTAP_OCAM_MAX_POL ? EGOTAP_OCAM_MAX_POL : m.n_pol, r);
     const double invnorm = 1.0 / sqrt(xp * xp + yp * yp + zp * zp);
     ray[0] = invnorm * xp;
     ray[1] = invnorm * yp;
@@ -98,8 +106,12 @@ static __device__ __forceinline__ double stereo_dot(const double (&p)[3], const 
 }
 static __device__ __forceinline__ bool stereo_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN and +-inf
 
-static __global__ __launch_bounds__(256) void stereo_triangulate_kernel(const float* __restrict__ kp, int B, int J, StereoRig rig, const float* __restrict__ pose,
-                                                                       int P, int row0, float* __restrict__ joints3d, float* __restrict__ frame) {
+// The kernel's body, shared by the two places a rig comes from.  TABLE false: `rig` is the kernel's by-value argument.  TABLE true: `rig` is one row of
+// a table in device memory, picked by a wave-uniform index -- plain uniform loads of doubles, and the polynomial lengths clamped.  Where a value of the
+// rig was loaded from does not enter the arithmetic: both kernels return the same bits for the same rig.
+template <bool TABLE>
+static __device__ __forceinline__ void stereo_triangulate_body(const float* __restrict__ kp, int B, int J, const StereoRig& rig, const float* __restrict__ pose,
+                                                               int P, int row0, float* __restrict__ joints3d, float* __restrict__ frame) {
 #pragma clang fp contract(off)
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     __shared__ double sj[kStereoFramesPerBlock][kStereoMaxJoints][8];      // per joint: valid, X (3), pose row (3), gap
@@ -116,8 +128,8 @@ static __global__ __launch_bounds__(256) void stereo_triangulate_kernel(const fl
         const bool seen = (double)kl[2] >= rig.min_score && (double)kr[2] >= rig.min_score && stereo_finite(xl) && stereo_finite(yl) && stereo_finite(xr) &&
                           stereo_finite(yr);
         double dL[3], r[3], dR[3], w0[3];
-        ocam_unproject_one(rig.cam[0], rig.aff[0][0] * xl + rig.aff[0][1], rig.aff[0][2] * yl + rig.aff[0][3], dL);
-        ocam_unproject_one(rig.cam[1], rig.aff[1][0] * xr + rig.aff[1][1], rig.aff[1][2] * yr + rig.aff[1][3], r);
+        ocam_unproject_one<TABLE>(rig.cam[0], rig.aff[0][0] * xl + rig.aff[0][1], rig.aff[0][2] * yl + rig.aff[0][3], dL);
+        ocam_unproject_one<TABLE>(rig.cam[1], rig.aff[1][0] * xr + rig.aff[1][1], rig.aff[1][2] * yr + rig.aff[1][3], r);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             dR[k] = rig.R[3 * k] * r[0] + rig.R[3 * k + 1] * r[1] + rig.R[3 * k + 2] * r[2];
@@ -224,6 +236,24 @@ static __global__ __launch_bounds__(256) void stereo_triangulate_kernel(const fl
     *(f32x4v*)(out + 4) = hi;
 }
 
+static __global__ __launch_bounds__(256) void stereo_triangulate_kernel(const float* __restrict__ kp, int B, int J, StereoRig rig, const float* __restrict__ pose,
+                                                                       int P, int row0, float* __restrict__ joints3d, float* __restrict__ frame) {
+    stereo_triangulate_body<false>(kp, B, J, rig, pose, P, row0, joints3d, frame);
+}
+
+// the rig of a wave's frame in a table of S rigs (frame b uses rig b % S; time-major batches, b = t * S + s): the index made uniform, so the rig's
+// values are fetched once per wave.  A wave past the batch still picks a row inside the table.
+static __device__ __forceinline__ const StereoRig& stereo_stream_rig(const StereoRig* __restrict__ rigs, int S) {
+    const unsigned f = blockIdx.x * (unsigned)kStereoFramesPerBlock + (threadIdx.x >> 6);
+    return rigs[__builtin_amdgcn_readfirstlane((int)(f % (unsigned)S))];
+}
+
+static __global__ __launch_bounds__(256) void stereo_triangulate_streams_kernel(const float* __restrict__ kp, int B, int J, const StereoRig* __restrict__ rigs, int S,
+                                                                               const float* __restrict__ pose, int P, int row0, float* __restrict__ joints3d,
+                                                                               float* __restrict__ frame) {
+    stereo_triangulate_body<true>(kp, B, J, stereo_stream_rig(rigs, S), pose, P, row0, joints3d, frame);
+}
+
 // N > 0 and the pointers checked by the caller.
 static inline hipError_t ocam_project_launch(const float* p3, int N, const egotap_ocam& m, float* p2, hipStream_t s) {
     if (N <= 0) return hipErrorInvalidValue;
@@ -241,5 +271,13 @@ static inline hipError_t stereo_triangulate_launch(const float* kp, int B, int J
     if (B <= 0 || J <= 0 || J > kStereoMaxJoints || (pose && (row0 < 0 || row0 + J > P))) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)(((long)B + kStereoFramesPerBlock - 1) / kStereoFramesPerBlock);
     hipLaunchKernelGGL(stereo_triangulate_kernel, dim3(blocks), dim3(64 * kStereoFramesPerBlock), 0, s, kp, B, J, rig, pose, P, row0, joints3d, frame);
+    return hipGetLastError();
+}
+// the same with a table of S rigs in device memory (8-byte aligned, S >= 1, B a multiple of S: checked by the caller)
+static inline hipError_t stereo_triangulate_streams_launch(const float* kp, int B, int J, const StereoRig* rigs, int S, const float* pose, int P, int row0,
+                                                           float* joints3d, float* frame, hipStream_t s) {
+    if (B <= 0 || J <= 0 || J > kStereoMaxJoints || (pose && (row0 < 0 || row0 + J > P)) || !rigs || S < 1 || B % S != 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((long)B + kStereoFramesPerBlock - 1) / kStereoFramesPerBlock);
+    hipLaunchKernelGGL(stereo_triangulate_streams_kernel, dim3(blocks), dim3(64 * kStereoFramesPerBlock), 0, s, kp, B, J, rigs, S, pose, P, row0, joints3d, frame);
     return hipGetLastError();
 }

@@ -6,6 +6,8 @@
 //       LDS; after the workgroup's one barrier lane 0 adds the frame's statistics from LDS in ASCENDING joint order, so the host restatement, which adds in
 //       that order, gets the same bits.  Lane = joint writes its record as two 16-byte stores and its pose_fused row; the wave copies the rows outside the
 //       joint rows.  pose_fused may be pose: every element is read and written by the same thread, and neither pointer is __restrict__.
+//   stereo_fuse_streams_kernel  the same body with a rig per stream: frame b reads rig b % S of a table in device memory (ocam.h
+//       stereo_triangulate_streams_kernel); the parameters stay by value, one set for all streams.
 // The rig and the parameters travel by value in the kernel arguments (uniform indices: scalar loads).  Contraction is off in every function here: the
 // definition keeps products and sums apart.  sqrt and the divisions are correctly rounded; the six divisions of the solve form two short chains
 // (l10, l20 | D1 -> l21 -> D2 -> y2), latency the one wave per frame cannot hide and does not need to: a call is a few KB of work.
@@ -73,9 +75,11 @@ static __device__ __forceinline__ bool fuse_check_eye(const FuseEye& eye, const 
     return res <= max_sigma && c > 0.0;
 }
 
-static __global__ __launch_bounds__(256) void stereo_fuse_kernel(const float* __restrict__ kp, int B, int J, StereoRig rig, const float* pose, int P, int row0,
-                                                                const float* __restrict__ frame, egotap_fuse_params prm, float* __restrict__ fused, float* pose_fused,
-                                                                float* __restrict__ stats) {
+// the kernel's body, shared by the two places a rig comes from (ocam.h stereo_triangulate_body: TABLE false the by-value argument, true a row of a table)
+template <bool TABLE>
+static __device__ __forceinline__ void stereo_fuse_body(const float* __restrict__ kp, int B, int J, const StereoRig& rig, const float* pose, int P, int row0,
+                                                        const float* __restrict__ frame, const egotap_fuse_params& prm, float* __restrict__ fused, float* pose_fused,
+                                                        float* __restrict__ stats) {
 #pragma clang fp contract(off)
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     __shared__ double sj[kStereoFramesPerBlock][kStereoMaxJoints][4];      // per joint: mode, move, res left, res right
@@ -109,8 +113,8 @@ static __global__ __launch_bounds__(256) void stereo_fuse_kernel(const float* __
             const bool seenL = (double)kl[2] >= rig.min_score && stereo_finite(xl) && stereo_finite(yl);
             const bool seenR = (double)kr[2] >= rig.min_score && stereo_finite(xr) && stereo_finite(yr);
             double dL[3], r[3], dR[3], x0[3];
-            ocam_unproject_one(rig.cam[0], rig.aff[0][0] * xl + rig.aff[0][1], rig.aff[0][2] * yl + rig.aff[0][3], dL);
-            ocam_unproject_one(rig.cam[1], rig.aff[1][0] * xr + rig.aff[1][1], rig.aff[1][2] * yr + rig.aff[1][3], r);
+            ocam_unproject_one<TABLE>(rig.cam[0], rig.aff[0][0] * xl + rig.aff[0][1], rig.aff[0][2] * yl + rig.aff[0][3], dL);
+            ocam_unproject_one<TABLE>(rig.cam[1], rig.aff[1][0] * xr + rig.aff[1][1], rig.aff[1][2] * yr + rig.aff[1][3], r);
             const double zero[3] = {0.0, 0.0, 0.0}, wp = 1.0 / (prm.sigma_prior * prm.sigma_prior);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -217,11 +221,33 @@ static __global__ __launch_bounds__(256) void stereo_fuse_kernel(const float* __
     *(f32x4v*)(out + 4) = hi;
 }
 
+static __global__ __launch_bounds__(256) void stereo_fuse_kernel(const float* __restrict__ kp, int B, int J, StereoRig rig, const float* pose, int P, int row0,
+                                                                const float* __restrict__ frame, egotap_fuse_params prm, float* __restrict__ fused, float* pose_fused,
+                                                                float* __restrict__ stats) {
+    stereo_fuse_body<false>(kp, B, J, rig, pose, P, row0, frame, prm, fused, pose_fused, stats);
+}
+
+// frame b fused with rig b % S of a table in device memory (ocam.h stereo_stream_rig); one set of parameters serves all streams
+static __global__ __launch_bounds__(256) void stereo_fuse_streams_kernel(const float* __restrict__ kp, int B, int J, const StereoRig* __restrict__ rigs, int S,
+                                                                        const float* pose, int P, int row0, const float* __restrict__ frame, egotap_fuse_params prm,
+                                                                        float* __restrict__ fused, float* pose_fused, float* __restrict__ stats) {
+    stereo_fuse_body<true>(kp, B, J, stereo_stream_rig(rigs, S), pose, P, row0, frame, prm, fused, pose_fused, stats);
+}
+
 // keypoints, frame, fused, stats 16-byte aligned, 1 <= J <= kStereoMaxJoints, 0 <= row0 and row0 + J <= P: checked by the caller.
 static inline hipError_t stereo_fuse_launch(const float* kp, int B, int J, const StereoRig& rig, const float* pose, int P, int row0, const float* frame,
                                             const egotap_fuse_params& prm, float* fused, float* pose_fused, float* stats, hipStream_t s) {
     if (B <= 0 || J <= 0 || J > kStereoMaxJoints || row0 < 0 || row0 + J > P) return hipErrorInvalidValue;
     const unsigned blocks = (unsigned)(((long)B + kStereoFramesPerBlock - 1) / kStereoFramesPerBlock);
     hipLaunchKernelGGL(stereo_fuse_kernel, dim3(blocks), dim3(64 * kStereoFramesPerBlock), 0, s, kp, B, J, rig, pose, P, row0, frame, prm, fused, pose_fused, stats);
+    return hipGetLastError();
+}
+// the same with a table of S rigs in device memory (8-byte aligned, S >= 1, B a multiple of S: checked by the caller)
+static inline hipError_t stereo_fuse_streams_launch(const float* kp, int B, int J, const StereoRig* rigs, int S, const float* pose, int P, int row0, const float* frame,
+                                                    const egotap_fuse_params& prm, float* fused, float* pose_fused, float* stats, hipStream_t s) {
+    if (B <= 0 || J <= 0 || J > kStereoMaxJoints || row0 < 0 || row0 + J > P || !rigs || S < 1 || B % S != 0) return hipErrorInvalidValue;
+    const unsigned blocks = (unsigned)(((long)B + kStereoFramesPerBlock - 1) / kStereoFramesPerBlock);
+    hipLaunchKernelGGL(stereo_fuse_streams_kernel, dim3(blocks), dim3(64 * kStereoFramesPerBlock), 0, s, kp, B, J, rigs, S, pose, P, row0, frame, prm, fused,
+                       pose_fused, stats);
     return hipGetLastError();
 }

@@ -26,6 +26,11 @@ class EgotapOcam(C.Structure):                        # egotap.h egotap_ocam: do
         ("n_pol", C.c_int32), ("n_invpol", C.c_int32)]
 
 
+class EgotapStereoRig(C.Structure):                   # egotap.h egotap_stereo_rig: two models and 21 doubles, 792 bytes
+    _fields_ = [("left", EgotapOcam), ("right", EgotapOcam), ("R", C.c_double * 9), ("t", C.c_double * 3), ("affine", (C.c_double * 4) * 2),
+                ("min_score", C.c_double)]
+
+
 class EgotapTrackParams(C.Structure):                 # egotap.h egotap_track_params: twelve doubles and two ints
     _fields_ = [(f"{c}_{n}", C.c_double) for c in ("pose", "root", "joints") for n in ("min_cutoff", "beta", "d_cutoff")] + [
         (n, C.c_double) for n in ("max_disagree", "max_gap", "max_joint_gap")] + [("min_joints", C.c_int32), ("max_hold", C.c_int32)]
@@ -141,6 +146,21 @@ _PROTOS = {
     "egotap_stereo_fuse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(EgotapOcam), C.POINTER(EgotapOcam), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(EgotapFuseParams), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    # ---- a camera rig per stream: a table of S rigs, or S lens maps per eye, in device memory
+    "egotap_stereo_rigs_check": (C.c_int, [C.POINTER(EgotapStereoRig), C.c_int]),
+    # (keypoints, B, J, rigs_dev, S, pose, P, pose_row0, joints3d, frame, stream)
+    "egotap_stereo_triangulate_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    # (keypoints, B, J, rigs_dev, S, pose, P, pose_row0, frame, params, fused, pose_fused, stats, stream)
+    "egotap_stereo_fuse_streams": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.POINTER(EgotapFuseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_lens_remap_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_lens_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "egotap_predict_pose_lens_streams_kp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "egotap_predict_pose_lens_streams_kpl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EgotapLensSource), C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     # ---- heatmaps, keypoints and bones drawn onto the frames: two operators, no handle
     # (hm, dtype, B, C, S, image_stride, c0, n, groups, heat8, stream)
     "egotap_heat_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -512,12 +532,16 @@ def yuv_u8_resize(left8, right8, layout, colour, S0, rect_left=None, rect_right=
 
 class LensMaps:
     """A rig's two lens maps on the device (``lens_maps``): ``left`` / ``right`` the ``spec.LensMap`` of each eye, ``map_left`` / ``map_right`` their
-    taps as int32 [S0 * S0, 2] device tensors (uploaded once, kept alive here), ``fill`` the (R, G, B) of an invalid pixel per eye."""
+    taps as int32 [S0 * S0, 2] device tensors (uploaded once, kept alive here), ``fill`` the (R, G, B) of an invalid pixel per eye.  With a rig per
+    stream (``lens_maps`` of a list of pairs) ``S`` is the number of streams, ``streams`` the per-stream (left, right) ``spec.LensMap`` pairs,
+    ``map_left`` / ``map_right`` int32 [S, S0 * S0, 2], and ``left`` / ``right`` stream 0's."""
 
-    def __init__(self, left, right, map_left, map_right, fill):
+    def __init__(self, left, right, map_left, map_right, fill, streams=None):
         self.left, self.right, self.map_left, self.map_right, self.fill = left, right, map_left, map_right, fill
         self.S0, self.H, self.W, self.model_size = left.S0, left.H, left.W, left.model_size
         self.mirrors = (int(left.mirror), int(right.mirror))
+        self.streams = ((left, right),) if streams is None else tuple(streams)
+        self.S = len(self.streams)
 
     @property
     def key(self):
@@ -525,16 +549,28 @@ class LensMaps:
         return (self.map_left.data_ptr(), self.map_right.data_ptr(), self.fill)
 
 
-def lens_maps(left, right, fill=(0, 0, 0), device=None):
+def lens_maps(left, right=None, fill=(0, 0, 0), device=None):
     """``LensMaps`` of two ``spec.LensMap`` (left eye, right eye) on ``device`` (None: the current GPU): one upload per rig.  Both maps must share S0,
     the sensor frame's (H, W) and the model camera's calibration size -- one descriptor serves both eyes; the mirror flags may differ.  ``fill``: three
-    bytes (R, G, B) for both eyes, or a pair of them (left, right)."""
+    bytes (R, G, B) for both eyes, or a pair of them (left, right).  A rig per stream: ``left`` a list of (left, right) pairs, stream 0 first, and
+    ``right`` None -- every pair must share all of the above and each eye's mirror flag (the descriptor is one); the result has ``S`` = the number of
+    pairs and frame b of a time-major batch is gathered through pair b % S (``lens_remap_streams``)."""
     import numpy as np
     import torch
     from . import spec as _spec
-    for m in (left, right):
+    streams = None
+    if right is None:
+        streams = [tuple(pair) if hasattr(pair, "__len__") else (pair,) for pair in (left if isinstance(left, (list, tuple)) else ())]
+        if not 1 <= len(streams) <= _spec.STEREO_MAX_STREAMS or any(len(pair) != 2 for pair in streams):
+            raise ValueError(f"lens_maps: without right, left is a list of 1 .. {_spec.STEREO_MAX_STREAMS} (left, right) pairs of spec.LensMap, one per stream")
+        left, right = streams[0]
+    for m in (left, right) if streams is None else tuple(m for pair in streams for m in pair):
         if not isinstance(m, _spec.LensMap):
             raise ValueError(f"lens_maps: left and right are spec.LensMap (spec.lens_map builds one per eye), got {type(m).__name__}")
+    for s, (ml, mr) in enumerate(streams or ()):
+        for m, first in ((ml, left), (mr, right)):
+            if (m.S0, m.H, m.W, m.model_size, m.mirror) != (first.S0, first.H, first.W, first.model_size, first.mirror):
+                raise ValueError(f"lens_maps: stream {s}'s maps differ from stream 0's in S0, frame size, model size or mirror flag (one descriptor serves all streams)")
     if left.S0 != right.S0:
         raise ValueError(f"lens_maps: both eyes' maps must have one output side, got S0 = {left.S0} / {right.S0}")
     if (left.H, left.W) != (right.H, right.W):
@@ -552,10 +588,13 @@ def lens_maps(left, right, fill=(0, 0, 0), device=None):
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.type != "cuda":
         raise EgotapError("lens_maps: the maps live on the GPU (no CPU fallback); pass a cuda device")
-    up = [torch.from_numpy(np.array(m.taps).reshape(m.S0 * m.S0, 2)).to(dev) for m in (left, right)]
+    if streams is None:
+        up = [torch.from_numpy(np.array(m.taps).reshape(m.S0 * m.S0, 2)).to(dev) for m in (left, right)]
+    else:
+        up = [torch.from_numpy(np.stack([pair[e].taps.reshape(left.S0 * left.S0, 2) for pair in streams])).to(dev) for e in range(2)]
     if any(t.data_ptr() % 16 for t in up):
         raise EgotapError("lens_maps: a device map is not 16-byte aligned")
-    return LensMaps(left, right, up[0], up[1], fill)
+    return LensMaps(left, right, up[0], up[1], fill, streams)
 
 
 def lens_source(maps, layout=None, colour=None):
@@ -595,6 +634,28 @@ def check_lens_frames(who, left8, right8, maps, layout=None, colour=None):
     return B
 
 
+def lens_remap_streams(left8, right8, maps, S0, layout=None, colour=None):
+    """``lens_remap`` with a rig per stream (egotap_lens_remap_streams): ``maps`` a ``LensMaps`` of S streams (``lens_maps`` of a list of pairs; S = 1
+    too), frames time-major (frame b = t * S + s), frame b gathered through stream b % S's maps -- equal to spec.lens_remap_streams_u8 bit for bit, and
+    on frames s, s + S, .. to ``lens_remap`` with stream s's maps.  B must be a multiple of S.  One launch for both eyes and all streams."""
+    import torch
+    from . import spec as _spec
+    colour = _spec.YuvColour() if colour is None else colour
+    B = check_lens_frames("lens_remap_streams", left8, right8, maps, layout, colour)
+    if int(S0) != maps.S0:
+        raise ValueError(f"lens_remap_streams: the maps were built for S0 = {maps.S0}, got S0 = {S0}")
+    if B % maps.S:
+        raise ValueError(f"lens_remap_streams: the batch must be a multiple of the number of streams (frame b uses map b % S), got B = {B}, S = {maps.S}")
+    out_l = torch.empty((B, maps.S0, maps.S0, 3), dtype=torch.uint8, device=left8.device)
+    out_r = torch.empty_like(out_l)
+    if B == 0:
+        return out_l, out_r
+    with torch.cuda.device(left8.device):
+        check(load().egotap_lens_remap_streams(_ptr(left8), _ptr(right8), B, C.byref(lens_source(maps, layout, colour)), maps.S, maps.S0, _ptr(out_l),
+                                               _ptr(out_r), _stream(left8.device)))
+    return out_l, out_r
+
+
 def lens_remap(left8, right8, maps, S0, layout=None, colour=None):
     """frames from another lens x 2 -> camera bytes uint8 [B, S0, S0, 3] x 2 (egotap_lens_remap): each eye gathered bilinearly through its lens map
     (``lens_maps``), the fill bytes where the sensor does not see the model camera's pixel -- equal to spec.lens_remap_u8 bit for bit.  ``layout``
@@ -604,6 +665,8 @@ def lens_remap(left8, right8, maps, S0, layout=None, colour=None):
     from . import spec as _spec
     colour = _spec.YuvColour() if colour is None else colour
     B = check_lens_frames("lens_remap", left8, right8, maps, layout, colour)
+    if maps.S != 1:
+        raise ValueError(f"lens_remap: the maps hold {maps.S} streams; lens_remap_streams gathers frame b through stream b % S's maps")
     if int(S0) != maps.S0:
         raise ValueError(f"lens_remap: the maps were built for S0 = {maps.S0}, got S0 = {S0}")
     out_l = torch.empty((B, maps.S0, maps.S0, 3), dtype=torch.uint8, device=left8.device)
@@ -848,6 +911,156 @@ def stereo_fuse(keypoints, pose, frame, left, right, t, params, R=None, affine=N
     args = stereo_triangulate_args(left, right, t, R, affine, min_score)
     prm = fuse_params_struct(params)
     return _stereo_fuse_run("stereo_fuse", args, prm, keypoints, pose, frame, pose_row0)
+
+
+# ---- a camera rig per stream: the rig table and the two operators that read it
+STEREO_RIG_BYTES = C.sizeof(EgotapStereoRig)          # 792
+
+
+def stereo_rig_struct(rig) -> EgotapStereoRig:
+    """a ``spec.StereoRig`` as one row of a rig table (egotap_stereo_rig): every value spelled out, the identity where R or affine is None"""
+    from . import spec as _spec
+    if not isinstance(rig, _spec.StereoRig):
+        raise ValueError(f"stereo rig table: a rig is a spec.StereoRig, got {type(rig).__name__}")
+    o = EgotapStereoRig()
+    o.left, o.right = ocam_struct(rig.left), ocam_struct(rig.right)
+    R = rig.R if rig.R is not None else ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    aff = rig.affine if rig.affine is not None else _spec.STEREO_IDENTITY_AFFINE
+    for k in range(9):
+        o.R[k] = R[k // 3][k % 3]
+    for k in range(3):
+        o.t[k] = rig.t[k]
+    for e in range(2):
+        for k in range(4):
+            o.affine[e][k] = aff[e][k]
+    o.min_score = rig.min_score
+    return o
+
+
+def stereo_rigs_host(rigs):
+    """a list of ``spec.StereoRig`` as a checked host table (egotap_stereo_rigs_check: every refusal names the field and the stream): a ctypes array of
+    S egotap_stereo_rig.  Needs no GPU."""
+    rigs = list(rigs)
+    host = (EgotapStereoRig * max(1, len(rigs)))(*[stereo_rig_struct(r) for r in rigs])
+    check(load().egotap_stereo_rigs_check(host, len(rigs)))
+    return host
+
+
+def stereo_rigs_table(rigs, device=None):
+    """The rig table of S streams on ``device`` (None: the current GPU): (table, host) -- ``table`` a uint8 device tensor of S * 792 bytes, uploaded
+    once, that ``stereo_triangulate_streams`` / ``stereo_fuse_streams`` read rig b % S of for frame b; ``host`` the checked ctypes array it was
+    uploaded from.  The library cannot inspect device memory: write the tensor through ``stereo_rig_write`` only."""
+    import torch
+    host = stereo_rigs_host(rigs)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise EgotapError("stereo_rigs_table: the table lives on the GPU (no CPU fallback); pass a cuda device")
+    table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+    if table.data_ptr() % 8:
+        raise EgotapError("stereo_rigs_table: the device table is not 8-byte aligned")
+    return table, host
+
+
+def stereo_rig_check(rig, s):
+    """one ``spec.StereoRig`` checked as stream ``s``'s (egotap_stereo_rigs_check; the refusal names the field and stream s) -> a ctypes array of one row"""
+    one = (EgotapStereoRig * 1)(stereo_rig_struct(rig))
+    try:
+        check(load().egotap_stereo_rigs_check(one, 1))
+    except EgotapError as e:
+        raise EgotapError(str(e).replace("rig 0:", f"rig {int(s)}:")) from None
+    return one
+
+
+def stereo_rig_write(table, host, s, rig):
+    """Row ``s`` of a rig table rewritten in place with ``rig`` (a ``spec.StereoRig``), checked first; the copy is ordered on the table's device's
+    current stream, so launches and graph replays enqueued after it read the new rig and those before it the old one."""
+    import torch
+    S = len(host)
+    if not 0 <= int(s) < S:
+        raise ValueError(f"stereo_rig_write: stream {s} is not one of the table's {S}")
+    one = stereo_rig_check(rig, s)
+    host[int(s)] = one[0]
+    with torch.cuda.device(table.device):
+        table[int(s) * STEREO_RIG_BYTES:(int(s) + 1) * STEREO_RIG_BYTES].copy_(torch.frombuffer(bytearray(bytes(one)), dtype=torch.uint8))
+
+
+def _check_rig_table(who, table, S, B, dev):
+    import torch
+    if not (torch.is_tensor(table) and table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous()) or int(S) < 1 or \
+            table.numel() != int(S) * STEREO_RIG_BYTES:
+        raise ValueError(f"{who}: the rig table is what stereo_rigs_table returns, uint8 [S * {STEREO_RIG_BYTES}] with S >= 1, got "
+                         f"{tuple(getattr(table, 'shape', ()))} for S = {S}")
+    if B % int(S):
+        raise ValueError(f"{who}: the batch must be a multiple of the number of streams (frame b uses rig b % S), got B = {B}, S = {S}")
+    if dev is not None and table.device != dev:
+        raise EgotapError(f"{who}: the rig table is on {table.device}, the keypoints on {dev}")
+
+
+def stereo_triangulate_streams_into(table, S, keypoints, pose, pose_row0, joints3d, frame, dev):
+    """the launch itself on ``dev``'s current stream: tensors as the ABI takes them"""
+    B, _, J, _ = keypoints.shape
+    check(load().egotap_stereo_triangulate_streams(_ptr(keypoints), B, J, _ptr(table), int(S), _ptr(pose), pose.shape[1] if pose is not None else 0, int(pose_row0),
+                                                   _ptr(joints3d), _ptr(frame), _stream(dev)))
+
+
+def stereo_triangulate_streams(keypoints, table, S, pose=None, pose_row0=0):
+    """``stereo_triangulate`` with a rig per stream (egotap_stereo_triangulate_streams, ``spec.stereo_triangulate_streams_ref``): keypoints float32
+    [B, 2, J, 4] of T frames of S streams, time-major (frame b = t * S + s); ``table`` the device table of ``stereo_rigs_table``; frame b is
+    triangulated through rig b % S.  Rows s, s + S, .. equal ``stereo_triangulate`` on those rows with rig s in every bit.  One launch."""
+    import torch
+    who = "stereo_triangulate_streams"
+    if not torch.is_tensor(keypoints) or keypoints.dim() != 4 or keypoints.shape[1] != 2 or keypoints.shape[3] != 4:
+        raise ValueError(f"{who}: keypoints are a tensor [B, 2, J, 4], got {tuple(getattr(keypoints, 'shape', ()))}")
+    B, _, J, _ = (int(v) for v in keypoints.shape)
+    if not 1 <= J <= 64:
+        raise ValueError(f"{who}: 1 .. 64 joints, got {J}")
+    if pose is not None and (not torch.is_tensor(pose) or pose.dim() != 3 or pose.shape[0] != B or pose.shape[2] != 3 or pose_row0 < 0
+                             or pose_row0 + J > pose.shape[1]):
+        raise ValueError(f"{who}: pose is a tensor [B, P, 3] with pose_row0 + J <= P, got {tuple(getattr(pose, 'shape', ()))}, "
+                         f"pose_row0 = {pose_row0}, J = {J}")
+    _check_rig_table(who, table, S, B, None)
+    if not keypoints.is_cuda or (pose is not None and pose.device != keypoints.device) or table.device != keypoints.device:
+        raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); keypoints, pose and the rig table on one cuda device")
+    kp = keypoints.detach().float().contiguous()
+    ps = pose.detach().float().contiguous() if pose is not None else None
+    joints3d = torch.empty((B, J, 8), dtype=torch.float32, device=kp.device)
+    frame = torch.empty((B, 8), dtype=torch.float32, device=kp.device)
+    if B == 0:
+        return joints3d, frame
+    with torch.cuda.device(kp.device):
+        stereo_triangulate_streams_into(table, S, kp, ps, pose_row0, joints3d, frame, kp.device)
+    return joints3d, frame
+
+
+def stereo_fuse_streams_into(table, S, prm, keypoints, pose, pose_row0, frame, fused, pose_fused, stats, dev):
+    """the launch itself on ``dev``'s current stream: ``prm`` from ``fuse_params_struct``, tensors as the ABI takes them (pose_fused may be pose)"""
+    B, _, J, _ = keypoints.shape
+    check(load().egotap_stereo_fuse_streams(_ptr(keypoints), B, J, _ptr(table), int(S), _ptr(pose), pose.shape[1], int(pose_row0), _ptr(frame), C.byref(prm),
+                                            _ptr(fused), _ptr(pose_fused), _ptr(stats), _stream(dev)))
+
+
+def _stereo_fuse_streams_run(who, table, S, prm, keypoints, pose, frame, pose_row0):
+    import torch
+    B, J, P = _stereo_fuse_shapes(who, keypoints, pose, frame, pose_row0)
+    _check_rig_table(who, table, S, B, None)
+    if not _on_one_gpu(keypoints, pose, frame, table):
+        raise EgotapError(f"{who} runs on the GPU only (no CPU fallback); keypoints, pose, frame and the rig table on one cuda device")
+    kp, ps, fr = _f32c(keypoints), _f32c(pose), _f32c(frame)
+    pose_fused = torch.empty((B, P, 3), dtype=torch.float32, device=kp.device)
+    fused = torch.empty((B, J, 8), dtype=torch.float32, device=kp.device)
+    stats = torch.empty((B, 8), dtype=torch.float32, device=kp.device)
+    if B == 0:
+        return pose_fused, fused, stats
+    with torch.cuda.device(kp.device):
+        stereo_fuse_streams_into(table, S, prm, kp, ps, pose_row0, fr, fused, pose_fused, stats, kp.device)
+    return pose_fused, fused, stats
+
+
+def stereo_fuse_streams(keypoints, pose, frame, table, S, params, pose_row0=0):
+    """``stereo_fuse`` with a rig per stream (egotap_stereo_fuse_streams, ``spec.stereo_fuse_streams_ref``): the tensors are ``stereo_fuse``'s for T
+    frames of S streams, time-major; ``table`` the device table of ``stereo_rigs_table``; one ``params`` (``spec.FuseParams``) serves all streams.
+    Rows s, s + S, .. equal ``stereo_fuse`` on those rows with rig s in every bit.  One launch."""
+    return _stereo_fuse_streams_run("stereo_fuse_streams", table, S, fuse_params_struct(params), keypoints, pose, frame, pose_row0)
 
 
 def track_params_struct(params=None) -> EgotapTrackParams:

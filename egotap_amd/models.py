@@ -25,6 +25,12 @@ from . import spec as _spec
 from .session import ptr, stream
 
 
+class _StreamTri(NamedTuple):
+    """what a serving entry's triangulation launch reads with a rig per stream: the device table and the number of streams"""
+    table: object
+    S: int
+
+
 def create_model(opt):
     name = getattr(opt, "model", "egotap_autoencoder")
     if name == "egotap_autoencoder":
@@ -131,6 +137,61 @@ class StereoFusion:
         returns -> (pose_fused [B, P, 3], fused [B, J, 8], stats [B, 8]).  ONE launch on the current stream, no synchronisation: it queues behind the
         serving call that made its inputs; ``tracker.update(pose_fused, joints3d, frame, ...)`` follows it."""
         return _lib._stereo_fuse_run("StereoFusion.update", self._args, self._prm, keypoints, pose, frame, self.pose_row0)
+
+
+class StreamRigs:
+    """The rigs of S streams behind ``model.set_stereo_rigs``: ``rigs`` a list of (left, right, t, R) and one ``min_score``.  A device table
+    (``lib.stereo_rigs_table``) exists per keypoint -> calibration pixel affine a serving entry or a fusion asks for and per device, each uploaded ONCE
+    at its first use; ``update`` rewrites row s of every one of them in place, in stream order, so whoever holds a table -- a captured graph, a
+    ``StreamStereoFusion`` -- serves the new rig from the next launch on."""
+
+    def __init__(self, rigs, min_score, hm_size):
+        self.rigs, self.min_score, self.hm_size = list(rigs), float(min_score), int(hm_size)
+        self.S = len(self.rigs)
+        self._tables = {}                                   # (affine kind, device) -> (table, host)
+        _lib.stereo_rigs_host([self.spec_rig(s, None) for s in range(self.S)])      # (the checks, now rather than at the first request)
+
+    def spec_rig(self, s, affine, rig=None):
+        """stream s's ``spec.StereoRig`` under ``affine``: None for the RGB / byte entries' keypoints (``spec.stereo_pixel_affine`` of the stream's own
+        models), or one explicit [2, 4] for all streams"""
+        left, right, t, R = self.rigs[s] if rig is None else rig
+        if affine is None:
+            affine = (_spec.stereo_pixel_affine(left, self.hm_size), _spec.stereo_pixel_affine(right, self.hm_size))
+        return _spec.StereoRig(left, right, t, R, affine, self.min_score)
+
+    def table(self, affine, dev):
+        key = (None if affine is None else tuple(tuple(float(v) for v in row) for row in affine), str(dev))
+        hit = self._tables.get(key)
+        if hit is None:
+            hit = self._tables[key] = _lib.stereo_rigs_table([self.spec_rig(s, key[0]) for s in range(self.S)], dev)
+        return hit[0]
+
+    def update(self, s, rig):
+        if not 0 <= int(s) < self.S:
+            raise ValueError(f"update_stereo_rig: stream {s} is not one of the {self.S} set by set_stereo_rigs")
+        new = {key: self.spec_rig(int(s), key[0], rig) for key in self._tables}
+        _lib.stereo_rig_check(self.spec_rig(int(s), None, rig), s)     # refused before any table is touched
+        for key, (table, host) in self._tables.items():
+            _lib.stereo_rig_write(table, host, int(s), new[key])
+        self.rigs[int(s)] = rig
+
+
+class StreamStereoFusion:
+    """``StereoFusion`` with a rig per stream (``lib.stereo_fuse_streams``, egotap_stereo_fuse_streams): made by ``model.new_stereo_fusion`` after
+    ``set_stereo_rigs``.  It reads the model's rig table, so ``model.update_stereo_rig`` is seen by the next update; one ``params`` serves all streams."""
+
+    def __init__(self, rigs, params, affine=None, pose_row0=0):
+        self.params, self.pose_row0, self.streams = params, int(pose_row0), rigs.S
+        self._prm = _lib.fuse_params_struct(params)
+        self._rigs, self._affine = rigs, affine
+
+    @torch.no_grad()
+    def update(self, pose, keypoints, frame):
+        """as ``StereoFusion.update`` on T frames of S streams, time-major (frame b = t * S + s): frame b is fused through rig b % S.  ONE launch."""
+        if not (torch.is_tensor(keypoints) and keypoints.is_cuda):
+            raise _lib.EgotapError("StreamStereoFusion.update runs on the GPU only (no CPU fallback); keypoints, pose and frame on one cuda device")
+        table = self._rigs.table(self._affine, keypoints.device)
+        return _lib._stereo_fuse_streams_run("StreamStereoFusion.update", table, self._rigs.S, self._prm, keypoints, pose, frame, self.pose_row0)
 
 
 class Skeleton:
@@ -716,12 +777,50 @@ class EgoTAPAutoEncoderModel(nn.Module):
         R = None if R is None else tuple(tuple(float(v) for v in row) for row in R)
         _lib.stereo_triangulate_args(left, right, t, R, None, min_score)           # (the shape checks, now rather than at the first request)
         self._stereo_rig = (left, right, t, R, float(min_score))
+        self._stereo_rigs = None                            # the later of set_stereo_rig / set_stereo_rigs wins
 
-    def _triangulation(self, who, wanted, affine=None):
+    @staticmethod
+    def _parsed_rig(who, rig):
+        if not (isinstance(rig, (tuple, list)) and len(rig) in (3, 4)):
+            raise ValueError(f"{who}: a rig is (left, right, t) or (left, right, t, R), got {rig!r}")
+        left, right = (m if isinstance(m, _spec.OcamModel) else _spec.ocam_from_json(m) for m in rig[:2])
+        t = tuple(float(v) for v in rig[2])
+        R = None if len(rig) == 3 or rig[3] is None else tuple(tuple(float(v) for v in row) for row in rig[3])
+        return left, right, t, R
+
+    def set_stereo_rigs(self, rigs, min_score=_spec.STEREO_MIN_SCORE):
+        """A camera rig per stream for ``return_triangulation`` and ``new_stereo_fusion``: ``rigs`` a list of (left, right, t, R=None) as
+        ``set_stereo_rig`` takes them, stream 0 first; a serving call then carries T frames of S = len(rigs) streams, time-major (frame b = t * S + s,
+        as the trackers take them), B a multiple of S, and frame b is triangulated through rig b % S in ONE launch
+        (egotap_stereo_triangulate_streams).  The rigs live in a device table uploaded once; a captured graph holds the table's address and S, not the
+        rigs, so ``update_stereo_rig`` needs no recapture.  The later of ``set_stereo_rig`` and ``set_stereo_rigs`` wins."""
+        rigs = [self._parsed_rig("set_stereo_rigs", r) for r in rigs]
+        if not 1 <= len(rigs) <= _spec.STEREO_MAX_STREAMS:
+            raise ValueError(f"set_stereo_rigs: 1 .. {_spec.STEREO_MAX_STREAMS} rigs, one per stream, got {len(rigs)}")
+        self._stereo_rigs = StreamRigs(rigs, min_score, self.net_AutoEncoder.preset.hm_size)
+        self._stereo_rig = None
+
+    def update_stereo_rig(self, s, left, right, t, R=None):
+        """Stream ``s``'s rig replaced (a headset that joined or was recalibrated): checked, then written into row s of the device table(s) of
+        ``set_stereo_rigs`` in place, ordered on the current stream.  Requests, graph replays and fusions enqueued afterwards serve the new rig;
+        nothing is recaptured."""
+        rigs = self.__dict__.get("_stereo_rigs")
+        if rigs is None:
+            raise _lib.EgotapError("update_stereo_rig: no per-stream rigs are set; call set_stereo_rigs(rigs) first")
+        rigs.update(s, self._parsed_rig("update_stereo_rig", (left, right, t, R)))
+
+    def _triangulation(self, who, wanted, affine=None, dev=None, B=0):
         """None, or what a serving entry needs for ``return_triangulation``: (the launch's host arguments, the capture key's part, the keypoint ->
         calibration pixel affines, pose_row0).  ``affine`` None: the RGB / byte entries' size / (4S) (``spec.stereo_pixel_affine``)."""
         if not wanted:
             return None
+        rigs = self.__dict__.get("_stereo_rigs")
+        if rigs is not None:      # a rig per stream: the launch reads the device table, and the capture key holds its address and S, not its contents
+            if B % rigs.S:
+                raise ValueError(f"{who}(return_triangulation=True): the batch must be a multiple of the {rigs.S} streams of set_stereo_rigs "
+                                 f"(frame b uses rig b % S), got B = {B}")
+            table = rigs.table(affine, dev)
+            return _StreamTri(table, rigs.S), ("triangulation_streams", table.data_ptr(), rigs.S), affine, _spec.stereo_pose_row0(self.net_AutoEncoder.preset)
         rig = self.__dict__.get("_stereo_rig")
         if rig is None:
             raise _lib.EgotapError(f"{who}(return_triangulation=True): no stereo rig is set; call set_stereo_rig(left, right, t) first")
@@ -802,7 +901,7 @@ class EgoTAPAutoEncoderModel(nn.Module):
     def _serve(self, src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation):
         """One request of a serving entry, whichever ``src`` (``_Source``) it reads: through the one library call, or -- where one handle cannot express
         the three networks (``_rgb_one_call_refusal``) -- through the module forwards, by name and ungraphed."""
-        tri = self._triangulation(src.who, return_triangulation, src.triangulation_affine)
+        tri = self._triangulation(src.who, return_triangulation, src.triangulation_affine, src.left.device, src.B)
         why = self._rgb_one_call_refusal()
         if why is None:
             return self._serve_one_call(src, return_heatmaps, return_keypoints, return_limbs, graphed, tri)
@@ -837,7 +936,9 @@ class EgoTAPAutoEncoderModel(nn.Module):
         if return_limbs:
             lb = _lib.limb_decode(cat, 2 * J, J, eyes=2, affine=affine)
         tr = None
-        if tri is not None:
+        if tri is not None and isinstance(tri[0], _StreamTri):
+            tr = _lib.stereo_triangulate_streams(kp, tri[0].table, tri[0].S, pose=pose, pose_row0=tri[3])
+        elif tri is not None:
             rig_l, rig_r, rig_t, rig_R, min_score = self._stereo_rig
             tr = _lib.stereo_triangulate(kp, rig_l, rig_r, rig_t, R=rig_R, affine=tri[2], min_score=min_score, pose=pose, pose_row0=tri[3])
         return self._served(pose, cat if return_heatmaps else None, kp if return_keypoints else None, lb, tr)
@@ -849,7 +950,9 @@ class EgoTAPAutoEncoderModel(nn.Module):
         pose, hm, kp, lb, tr = out
         fn, extra = (src.entries[2], (ptr(kp), ptr(lb))) if lb is not None else (src.entries[0], ()) if kp is None else (src.entries[1], (ptr(kp),))
         _lib.check(fn(h, ptr(left), ptr(right), *src.args, ptr(pose), ptr(hm), chunk, ptr(ws), ws.numel(), stream(dev), *extra))
-        if tri is not None:
+        if tri is not None and isinstance(tri[0], _StreamTri):
+            _lib.stereo_triangulate_streams_into(tri[0].table, tri[0].S, kp, pose, tri[3], tr[0], tr[1], dev)
+        elif tri is not None:
             _lib.stereo_triangulate_into(tri[0], kp, pose, tri[3], tr[0], tr[1], dev)
 
     def _serve_one_call(self, src, return_heatmaps, return_keypoints, return_limbs, graphed, tri):
@@ -898,6 +1001,8 @@ class EgoTAPAutoEncoderModel(nn.Module):
                 s_l, s_r = left.clone(), right.clone()
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
                 held = (ws, st.wscratch, st.ascratch) + tuple(src.keep) + tuple(n._frozen_arena for n in nets if n.weights_frozen)
+                if tri is not None and isinstance(tri[0], _StreamTri):
+                    held += (tri[0].table,)
                 return (lambda: self._launch(src, h, s_l, s_r, out, chunk, ws, dev, tri)), (s_l, s_r, out), held
             graph, (s_l, s_r, out), _ = _session.captured(st.graphs, key, build)
             s_l.copy_(left)
@@ -1009,14 +1114,16 @@ class EgoTAPAutoEncoderModel(nn.Module):
                       triangulation_affine=_spec.STEREO_IDENTITY_AFFINE, module_route="the conversion and resize, the converter and the module forwards")
         return self._serve(src, return_heatmaps, graphed, return_keypoints, return_limbs, return_triangulation)
 
-    def lens_maps(self, left, right, fill=(0, 0, 0), device=None):
+    def lens_maps(self, left, right=None, fill=(0, 0, 0), device=None):
         """The rig's two lens maps for ``predict_pose_from_lens``: ``left`` / ``right`` a ``spec.LensMap`` each (``spec.lens_map(model_camera,
         sensor, 4 * hm_size, R, frame_size, mirror)``), uploaded ONCE to ``device`` (None: the current GPU); returns the handle object that keeps the
         device tensors (``lib.LensMaps``).  Refused by name: maps whose S0 is not 4 * hm_size, and maps that differ between the eyes in S0, the
         sensor frame's (H, W) or the model camera's calibration size (one descriptor serves both eyes).  ``fill``: the (R, G, B) of a pixel the
-        sensor does not see, for both eyes or one triple per eye."""
+        sensor does not see, for both eyes or one triple per eye.  A rig per stream: ``left`` a list of per-stream (left_map, right_map) pairs and
+        ``right`` None; the result has ``.S`` streams and ``predict_pose_from_lens`` gathers frame b of a time-major batch through pair b % S."""
         S0 = 4 * self.net_AutoEncoder.preset.hm_size
-        for m in (left, right):
+        pairs = left if right is None and isinstance(left, (list, tuple)) else ()
+        for m in (left, right) + tuple(m for pair in pairs if isinstance(pair, (list, tuple)) for m in pair):
             if isinstance(m, _spec.LensMap) and m.S0 != S0:
                 raise ValueError(f"lens_maps: the estimators read {S0} x {S0} frames (4 * hm_size), the map was built for S0 = {m.S0}")
         return _lib.lens_maps(left, right, fill, device)
@@ -1045,16 +1152,22 @@ class EgoTAPAutoEncoderModel(nn.Module):
         B = _lib.check_lens_frames(who, left8, right8, maps, layout, colour)
         if maps.S0 != S0:
             raise ValueError(f"{who}: the estimators read {S0} x {S0} frames (4 * hm_size), the maps were built for S0 = {maps.S0}")
+        per_stream = maps.S > 1      # a map per stream: the _streams entries, frame b through map b % S
+        if B % maps.S:
+            raise ValueError(f"{who}: the batch must be a multiple of the maps' {maps.S} streams (frame b uses map b % S), got B = {B}")
         lib, table = _lib.load(), self.camera_table(left8.device)
         desc = _lib.lens_source(maps, layout, colour)
         model_h, model_w = maps.model_size
 
         def float_frames():
-            return _lib.rgb_u8_to_f32(*_lib.lens_remap(left8, right8, maps, S0, layout, colour), table)
-        src = _Source(who, left8, right8, B, lib.egotap_predict_pose_lens_workspace_bytes,
-                      (lib.egotap_predict_pose_lens, lib.egotap_predict_pose_lens_kp, lib.egotap_predict_pose_lens_kpl),
-                      (B, C.byref(desc), ptr(table)),
-                      kind=("lens", "rgb8" if layout is None else layout.format, layout, colour if layout is not None else None) + maps.key
+            return _lib.rgb_u8_to_f32(*(_lib.lens_remap_streams if per_stream else _lib.lens_remap)(left8, right8, maps, S0, layout, colour), table)
+        entries = (lib.egotap_predict_pose_lens, lib.egotap_predict_pose_lens_kp, lib.egotap_predict_pose_lens_kpl)
+        if per_stream:
+            entries = (lib.egotap_predict_pose_lens_streams, lib.egotap_predict_pose_lens_streams_kp, lib.egotap_predict_pose_lens_streams_kpl)
+        src = _Source(who, left8, right8, B, lib.egotap_predict_pose_lens_workspace_bytes, entries,
+                      (B, C.byref(desc), maps.S, ptr(table)) if per_stream else (B, C.byref(desc), ptr(table)),
+                      kind=(("lens_streams", maps.S) if per_stream else ("lens",)) + ("rgb8" if layout is None else layout.format, layout,
+                                                                                      colour if layout is not None else None) + maps.key
                       + (maps.H, maps.W, maps.model_size, maps.mirrors, table.data_ptr()),
                       keep=(table, maps, desc), float_frames=float_frames,
                       keypoint_affine=[_spec.sensor_keypoint_affine((0, 0, model_w, model_h), bool(m), p.hm_size) for m in maps.mirrors],
@@ -1080,21 +1193,24 @@ class EgoTAPAutoEncoderModel(nn.Module):
         ``spec.FuseParams`` for the other fields (None: its defaults, which nobody has tuned on real data; its sigma_prior must then agree).
         ``affine``: None for the RGB / byte entries' keypoints (``spec.stereo_pixel_affine``), ``"identity"`` for the sensor and lens entries', or an
         explicit [2, 4].  The serving entries, the trackers, their graphs and their outputs do not change."""
+        rigs = self.__dict__.get("_stereo_rigs")
         rig = self.__dict__.get("_stereo_rig")
-        if rig is None:
+        if rig is None and rigs is None:
             raise _lib.EgotapError("new_stereo_fusion: no stereo rig is set; call set_stereo_rig(left, right, t) first")
-        left, right, t, R, min_score = rig
         if params is None:
             params = _spec.FuseParams(sigma_prior=sigma_prior)
         elif not isinstance(params, _spec.FuseParams) or params.sigma_prior != float(sigma_prior):
             raise ValueError(f"new_stereo_fusion: params is a spec.FuseParams whose sigma_prior is the one given ({sigma_prior}), got {params!r}")
         p = self.net_AutoEncoder.preset
-        if affine is None:
-            affine = (_spec.stereo_pixel_affine(left, p.hm_size), _spec.stereo_pixel_affine(right, p.hm_size))
-        elif isinstance(affine, str):
+        if isinstance(affine, str):
             if affine != "identity":
                 raise ValueError(f'new_stereo_fusion: affine is None, "identity" or a [2, 4] of (ax, bx, ay, by) per eye, got {affine!r}')
             affine = _spec.STEREO_IDENTITY_AFFINE
+        if rigs is not None:      # a rig per stream: the fusion reads the model's table (None: each stream's own pixel affine), so update_stereo_rig is seen
+            return StreamStereoFusion(rigs, params, affine=affine, pose_row0=_spec.stereo_pose_row0(p))
+        left, right, t, R, min_score = rig
+        if affine is None:
+            affine = (_spec.stereo_pixel_affine(left, p.hm_size), _spec.stereo_pixel_affine(right, p.hm_size))
         return StereoFusion(left, right, t, params, R=R, affine=affine, min_score=min_score, pose_row0=_spec.stereo_pose_row0(p))
 
     def new_skeleton(self, rig=None, streams=1, params=None, twist=None):

@@ -994,6 +994,88 @@ def stereo_fuse_ref(keypoints, pose, frame, left: OcamModel, right: OcamModel, t
     return pose_fused, rec.astype(dtype), stats.astype(dtype)
 
 
+# ---- a camera rig per stream (egotap.h: egotap_stereo_rig, egotap_stereo_triangulate_streams / egotap_stereo_fuse_streams) ---------------------
+STEREO_MAX_STREAMS = 4096                      # egotap.h EGOTAP_MAX_STREAM_RIGS
+
+
+@dataclass(frozen=True, eq=False)
+class StereoRig:
+    """One stream's camera rig, the arguments ``stereo_triangulate_ref`` takes about a rig: the two ``OcamModel``, ``t`` (3) and ``R`` (3 x 3, None:
+    identity) the right camera's origin and axes in the left camera's frame, ``affine`` [2, 4] from keypoint units to the calibration's pixels (None:
+    identity) and ``min_score``.  A table of rigs (egotap.h egotap_stereo_rig) is a list of these, stream s first to last."""
+    left: OcamModel
+    right: OcamModel
+    t: tuple
+    R: object = None
+    affine: object = None
+    min_score: float = STEREO_MIN_SCORE
+
+    def __post_init__(self):
+        for side in ("left", "right"):
+            if not isinstance(getattr(self, side), OcamModel):
+                raise ValueError(f"StereoRig: {side} is a spec.OcamModel, got {type(getattr(self, side)).__name__}")
+        t = tuple(float(v) for v in self.t)
+        if len(t) != 3:
+            raise ValueError(f"StereoRig: t is the right camera's origin in the left frame, 3 values, got {len(t)}")
+        object.__setattr__(self, "t", t)
+        if self.R is not None:
+            R = tuple(tuple(float(v) for v in row) for row in self.R)
+            if len(R) != 3 or any(len(row) != 3 for row in R):
+                raise ValueError("StereoRig: R is 3 x 3")
+            object.__setattr__(self, "R", R)
+        if self.affine is not None:
+            a = tuple(tuple(float(v) for v in row) for row in self.affine)
+            if len(a) != 2 or any(len(row) != 4 for row in a):
+                raise ValueError("StereoRig: affine is [2, 4] = (ax, bx, ay, by) per eye")
+            object.__setattr__(self, "affine", a)
+        object.__setattr__(self, "min_score", float(self.min_score))
+
+
+def _stream_rigs(who, rigs, B):
+    rigs = list(rigs)
+    if not 1 <= len(rigs) <= STEREO_MAX_STREAMS or not all(isinstance(r, StereoRig) for r in rigs):
+        raise ValueError(f"{who}: rigs is a list of 1 .. {STEREO_MAX_STREAMS} spec.StereoRig, one per stream")
+    if B % len(rigs):
+        raise ValueError(f"{who}: the batch must be a multiple of the number of streams (frame b uses rig b % S), got B = {B}, S = {len(rigs)}")
+    return rigs
+
+
+def stereo_triangulate_streams_ref(keypoints, rigs, pose=None, pose_row0=0, dtype="float32"):
+    """The records egotap_stereo_triangulate_streams writes: ``stereo_triangulate_ref`` on rows s, s + S, .. of a time-major batch (frame b = t * S + s)
+    with rig s of ``rigs`` (a list of S ``StereoRig``).  No arithmetic of its own."""
+    import numpy as np
+    kp = np.asarray(keypoints)
+    rigs = _stream_rigs("stereo_triangulate_streams_ref", rigs, kp.shape[0])
+    S = len(rigs)
+    ps = None if pose is None else np.asarray(pose)
+    rec = frame = None
+    for s, g in enumerate(rigs):
+        r, f = stereo_triangulate_ref(kp[s::S], g.left, g.right, g.t, R=g.R, affine=g.affine, min_score=g.min_score, pose=None if ps is None else ps[s::S],
+                                      pose_row0=pose_row0, dtype=dtype)
+        if rec is None:
+            rec, frame = np.empty((kp.shape[0],) + r.shape[1:], dtype=r.dtype), np.empty((kp.shape[0],) + f.shape[1:], dtype=f.dtype)
+        rec[s::S], frame[s::S] = r, f
+    return rec, frame
+
+
+def stereo_fuse_streams_ref(keypoints, pose, frame, rigs, params: FuseParams, pose_row0=0, dtype="float32"):
+    """The records egotap_stereo_fuse_streams writes: ``stereo_fuse_ref`` on rows s, s + S, .. with rig s of ``rigs``; one ``params`` for all streams.
+    No arithmetic of its own."""
+    import numpy as np
+    kp, ps, fr = np.asarray(keypoints), np.asarray(pose), np.asarray(frame)
+    rigs = _stream_rigs("stereo_fuse_streams_ref", rigs, kp.shape[0])
+    S = len(rigs)
+    out = None
+    for s, g in enumerate(rigs):
+        part = stereo_fuse_ref(kp[s::S], ps[s::S], fr[s::S], g.left, g.right, g.t, params, R=g.R, affine=g.affine, min_score=g.min_score, pose_row0=pose_row0,
+                               dtype=dtype)
+        if out is None:
+            out = tuple(np.empty((kp.shape[0],) + a.shape[1:], dtype=a.dtype) for a in part)
+        for whole, a in zip(out, part):
+            whole[s::S] = a
+    return out
+
+
 # ---- frames from another lens -> the model camera's frame (egotap.h: egotap_lens_remap / egotap_predict_pose_lens) -----------------------
 LENS_FRAC_BITS = 11                            # a map entry is a sensor pixel coordinate in Q11: the resize's weight precision
 LENS_MAX_SIDE = 16384                          # H, W <= 16384, as for the resize: an entry stays below 2^25
@@ -1156,6 +1238,28 @@ def lens_remap_u8(frames, lens: LensMap, fill=(0, 0, 0)):
     out = ((wy0 * top + wy1 * bot + (1 << 21)) >> 22).to(torch.uint8)
     out = torch.where(ok.view(1, lens.S0, lens.S0, 1), out, torch.tensor(fill, dtype=torch.uint8, device=dev).view(1, 1, 1, 3))
     return out.numpy() if is_np else out
+
+
+def lens_remap_streams_u8(frames, lenses, fill=(0, 0, 0)):
+    """The remap of egotap_lens_remap_streams: ``lens_remap_u8`` on frames s, s + S, .. of a time-major batch with map s of ``lenses`` (one eye's S
+    ``LensMap``, all of one S0 and frame size).  No arithmetic of its own; S = 1 is ``lens_remap_u8``."""
+    import numpy as np
+    lenses = list(lenses)
+    if not lenses or not all(isinstance(m, LensMap) for m in lenses):
+        raise ValueError("lens_remap_streams_u8: lenses is a list of spec.LensMap, one per stream")
+    if len({(m.S0, m.H, m.W) for m in lenses}) != 1:
+        raise ValueError("lens_remap_streams_u8: every stream's map must have one S0 and one frame size")
+    S, n = len(lenses), int(frames.shape[0])
+    if n % S:
+        raise ValueError(f"lens_remap_streams_u8: the batch must be a multiple of the number of streams (frame b uses map b % S), got {n} frames, S = {S}")
+    parts = [lens_remap_u8(frames[s::S], m, fill) for s, m in enumerate(lenses)]
+    if isinstance(frames, np.ndarray):
+        out = np.empty((n,) + parts[0].shape[1:], dtype=np.uint8)
+    else:
+        out = frames.new_empty((n,) + tuple(parts[0].shape[1:]))
+    for s, a in enumerate(parts):
+        out[s::S] = a
+    return out
 
 
 # ---- the pose, the root and the stereo joints filtered over time (egotap.h: egotap_pose_track) ---------------------------------------------

@@ -505,6 +505,55 @@ int egotap_stereo_fuse(const float* keypoints, int B, int J, const egotap_ocam* 
                        const double* affine, double min_score, const float* pose, int P, int pose_row0, const float* frame, const egotap_fuse_params* params,
                        float* fused, float* pose_fused, float* stats, void* stream);
 
+/* ---- a camera rig per stream: a rig table and a lens map per stream in front of the tracker (additive; EGOTAP_ABI_VERSION stays 2) ----
+ * egotap_pose_track and egotap_skeleton_fit take T frames of S streams, time-major (frame b = t * S + s), one camera rig per stream.  These entries feed
+ * them: each is the entry of the same name with S rigs or S lens maps in DEVICE memory in place of one, ONE launch for the whole batch, frame b served by
+ * rig (or map) b % S.  B must be a multiple of S.  Nothing about a rig is a kernel argument, so a captured graph holds the table's address and not its
+ * contents: a rig rewritten in place (in stream order) is served by the next replay.
+ *
+ * egotap_stereo_rig is one rig by value: the two models, R (row-major 3 x 3), t, affine ([2][4] = (ax, bx, ay, by) per eye) and min_score, every value
+ * spelled out -- the identity R and affine that the single-rig entries take as NULL are written as numbers here, and the coefficients behind n_pol and
+ * n_invpol are ignored.  792 bytes.  A TABLE is S of them, contiguous, 8-byte aligned, in device memory the caller owns and uploads.
+ * egotap_stereo_rigs_check: host only, launches nothing.  rigs_host is the table in HOST memory before the upload.  EGOTAP_ERR_INVALID, by name and with
+ *   the stream's index in the message ("rig 2: left: ..."): everything egotap_stereo_triangulate refuses about one rig -- n_pol outside 1 .. 8, n_invpol
+ *   outside 1 .. 24, c - d e == 0, a non-finite calibration value, R, t, affine or min_score, a ue_flip that is neither 0 nor 1 -- and S < 1, S > 4096 or
+ *   a NULL table.  The library cannot inspect device memory: that the uploaded table equals the checked one is the caller's contract, as for a lens map.
+ *   The kernels are memory-safe whatever a table holds: the stream index is b % S, and n_pol is clamped to the array's length before the polynomial is
+ *   read (the kernels unproject only and never read invpol), so a corrupt table gives wrong numbers and never a load outside the table.
+ * egotap_stereo_triangulate_streams / egotap_stereo_fuse_streams: egotap_stereo_triangulate / egotap_stereo_fuse with (rigs_dev, S) in place of (left,
+ *   right, R, t, affine, min_score).  The same records, the same kernels' shape (one wave per frame, lane = joint, four frames per workgroup), the same
+ *   device functions: rows s, s + S, s + 2 S .. equal the single-rig entry on those rows with rig s in every bit -- where a value of the rig was loaded from
+ *   does not enter the float64 arithmetic.  The wave of frame b reads rig b % S with uniform loads, once per wave.  One egotap_fuse_params serves all
+ *   streams; pose_fused may be pose.  No handle, no atomics, no workspace, no allocation; recorded as stereo_triangulate_streams / stereo_fuse_streams
+ *   while a handle's timing hook is on.  Refused by name before any launch: what the single-rig entry refuses of the arguments the two share; a NULL
+ *   table or one that is not 8-byte aligned; S < 1 or S > 4096; B not a multiple of S.
+ * egotap_lens_remap_streams, egotap_predict_pose_lens_streams / _kp / _kpl: egotap_lens_remap and egotap_predict_pose_lens / _kp / _kpl with S after the
+ *   descriptor.  map_left and map_right then point at int32 [S][S0 * S0][2]: stream s's map starts s * 2 * S0 * S0 ints in (16-byte aligned where the
+ *   first is, S0 being a multiple of 4), and frame b of the batch is gathered through map b % S.  H, W, the YUV layout, fill, mirror, model_h and
+ *   model_w are shared by the streams: the model camera is one camera, every stream's keypoints come out in the same calibration pixels, and a stream's
+ *   own crop or resize is expressed in its map.  The one-call entries gather piece by piece and each piece indexes by the frame's place in the whole
+ *   batch, whatever chunk is.  Workspace: egotap_predict_pose_lens_workspace_bytes.  S = 1 gives the bits of the entries without _streams.  Refused by
+ *   name before any launch: what the entry without _streams refuses; S < 1 or S > 4096; B not a multiple of S. */
+#define EGOTAP_MAX_STREAM_RIGS 4096
+typedef struct egotap_stereo_rig {
+    egotap_ocam left, right;
+    double R[9], t[3], affine[2][4], min_score;
+} egotap_stereo_rig;
+int egotap_stereo_rigs_check(const egotap_stereo_rig* rigs_host, int S);
+int egotap_stereo_triangulate_streams(const float* keypoints, int B, int J, const egotap_stereo_rig* rigs_dev, int S, const float* pose, int P, int pose_row0,
+                                      float* joints3d, float* frame, void* stream);
+int egotap_stereo_fuse_streams(const float* keypoints, int B, int J, const egotap_stereo_rig* rigs_dev, int S, const float* pose, int P, int pose_row0,
+                               const float* frame, const egotap_fuse_params* params, float* fused, float* pose_fused, float* stats, void* stream);
+int egotap_lens_remap_streams(const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S, int S0, uint8_t* out_left8,
+                              uint8_t* out_right8, void* stream);
+int egotap_predict_pose_lens_streams(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S, const float* table,
+                                     float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream);
+int egotap_predict_pose_lens_streams_kp(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S,
+                                        const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints);
+int egotap_predict_pose_lens_streams_kpl(egotap_handle h, const uint8_t* left8, const uint8_t* right8, int B, const egotap_lens_source* src, int S,
+                                         const float* table, float* pose, float* heatmaps, int chunk, void* ws, size_t ws_bytes, void* stream, float* keypoints,
+                                         float* limbs);
+
 /* ---- the pose, the root and the stereo joints filtered over time (additive; EGOTAP_ABI_VERSION stays 2) ----
  * Every serving output is a single-frame estimate; egotap_pose_track follows them over time with a One-Euro filter (Casiez et al. 2012) on 3-vectors in
  * which a missing sample is irregular sampling.  A TRACK is one 3-vector followed over time, a STREAM one camera rig.  A call carries T consecutive frames of
